@@ -11,16 +11,20 @@ driver's `python -m torch.distributed.run ... bench.py --gpus N` it uses the giv
 configs[3] instead (256 requests sharded i mod N, static batches of 32 per GPU, strong scaling).  Without a visible MI355X the
 ranks exercise the control path only (dry run, value null): libfishrt has no CPU path.
 
+A plain run sets up, warms up, times the --steps steps and prints the JSON line; `--dump-outputs DIR` then also writes the codes the last
+timed step returned as DIR/<name>.npy (float32; the inputs are seeded, so two builds can be compared output for output).  Everything
+that needs runs of its own -- roofline.kernels / dominant_kernel / sampled, extras, cpu_baseline + parity -- runs only with --full.
+
 Extra objects on the JSON line:
   roofline     -- HBM roofline of the decode FRAME (the unit of the hot loop, replayed from hipGraphs of 8 frames: the two persistent launches
                   k_slow_persist + k_fast_persist; 266 kernels with --no-persistent):
                   achieved = B_frame(T_avg) / t_frame, t_frame from HIP events recorded on the engine's own stream
                   (fs_lm_last_stats); B_frame is SURVEY.md §8(d)'s algorithmic-bytes formula; frac_min prices the same time against
                   B_min (fast-decoder weights counted once per frame: they stay on chip for the 8 passes).
-                  roofline.kernels itemises both launches of the timed region (HIP events around every launch of one more request
-                  in FS_GEN_TIME_KERNELS mode): algorithmic bytes per launch, average duration, both fractions; dominant_kernel is
-                  the longer of the two.  tools/check_roofline.py recomputes every number from this line + profiles/rNN_*.
-  cpu_baseline -- the CPU restatement (oracle/, kind "port": the reference is Rust+candle and cannot be built here) timed
+                  With --full, roofline.kernels itemises both launches of the timed region (HIP events around every launch of one more
+                  request in FS_GEN_TIME_KERNELS mode): algorithmic bytes per launch, average duration, both fractions; dominant_kernel
+                  is the longer of the two.  tools/check_roofline.py recomputes every number from this line + profiles/rNN_*.
+  cpu_baseline -- (--full) the CPU restatement (oracle/, kind "port": the reference is Rust+candle and cannot be built here) timed
                   on this host on BASELINE.json configs[0] (rank 0, N=1 only), which also yields the greedy golden
                   token stream: the GPU f32 path must reproduce it bit-identically (reported under "parity").
 """
@@ -149,6 +153,15 @@ def dry_run(args, dist, rank, world):
     sys.exit(0 if ok else 1)
 
 
+def dump_outputs(dirname, **arrays):
+    """--dump-outputs: DIR/<name>.npy in float32 (codes and frame counts are integers below 2^24, exact in float32; a few MB at most)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        assert a.size == 0 or (a.min() >= 0 and a.max() < 1 << 24), (name, a.min(), a.max())
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float32))
+
+
 def run_config3(args, lm_factory, dist, rank, world, cfg, tok):
     """BASELINE.json configs[3]: 256 requests (configs[2] prompts), request i -> rank i mod N, static batches of 32 per rank
     (generate_static_batch, temp 0.7 / top-p 0.8 / top-k 256, on-device sampling), `frames` frames per request.  The prompt batch is
@@ -200,6 +213,8 @@ def run_config3(args, lm_factory, dist, rank, world, cfg, tok):
     barrier()
     dt = fanout.max_over_ranks(dist, time.perf_counter() - t0)
     assert seen == world and fa.shape == (world, len(mine)) and int(fa.sum()) == n_req * frames, (seen, fa.shape, int(fa.sum()))
+    if rank == 0 and args.dump_outputs:  # the job's result: every rank's codes as fanned in, (world, requests per rank, 8, frames)
+        dump_outputs(args.dump_outputs, codes=ca, frames=fa)
     frames_total = n_req * frames * args.steps
     n_batches = (len(mine) + B - 1) // B
     step_s = dec_s / (n_batches * (frames - 1))
@@ -238,10 +253,15 @@ def main():
     ap.add_argument("--frames", type=int, default=256)
     ap.add_argument("--config", type=int, default=1, choices=(1, 3),
                     help="1: BASELINE.json configs[1] (batch-1 request per GPU, the headline metric); 3: configs[3] (256 requests sharded 32/GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the untimed configs[2] / vocoder side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements that take runs of their own: per-kernel roofline, sampled decode, extras, CPU baseline + parity")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity check")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the untimed configs[2] / vocoder side measurements")
     ap.add_argument("--no-persistent", action="store_true", help="FS_GEN_NO_PERSIST: fast decoder as 144 graph nodes per frame (A/B)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     self_launch(args)
 
     import torch  # before libfishrt: both bring a HIP runtime, and the one loaded first serves the process
@@ -332,6 +352,8 @@ def main():
     ca, fa, seen = fanout.all_gather_codes(dist, out[None], np.array([out.shape[1]], np.int32))
     assert seen == world and ca.shape == (world, 1, 8, args.frames)
     assert (ca == ca[0]).all(), "replicas disagree on the greedy tokens of the same request (weight broadcast / load mismatch)"
+    if rank == 0 and args.dump_outputs:  # what generate_blocking returned in the last timed step: (8 codebooks, frames)
+        dump_outputs(args.dump_outputs, codes=out)
 
     frames_total = args.frames * args.steps * world
     value = frames_total / dt
@@ -342,47 +364,52 @@ def main():
     T_avg = L + args.frames / 2.0
     bf = frame_bytes(cfg, tok, T_avg)
     achieved = bf / t_frame
-    # the kernels of the timed region, one by one: one more request in measurement mode (FS_GEN_TIME_KERNELS: the same two persistent
-    # launches per frame, a HIP event in front of / between / behind them on the engine stream); rocprofv3's averages for the same
-    # kernels are committed under profiles/ and checked against these by tools/check_roofline.py
-    kernels, dominant = {}, None
     b_slow, b_fast, b_fast_min = frame_bytes_split(cfg, tok, T_avg)
-    if kpf == 2:
-        lm.clear_slow_layer_caches()
-        outk = lm.generate_blocking(prompt, M, time_kernels=True, **samp)
-        assert np.array_equal(outk, out), "measurement mode changed the tokens"
-        stk = lm.last_stats()
-        for name, us, nb, nb_min, what in (
-                ("k_slow_persist", stk["slow_kernel_us"], b_slow, b_slow, "one launch = forward_generate of one token: 24 blocks over the paged KV cache + norm + audio-range head"),
-                ("k_fast_persist", stk["fast_kernel_us"], b_fast, b_fast_min, "one launch = the slow-token decision + 8 x forward_generate_fast + 8 codebook decisions + next-input embedding; "
-                                                                            "algorithmic bytes count the weights once per pass (SURVEY.md 8d), bytes_min once per launch (they stay on chip)")):
-            kernels[name] = {"what": what, "avg_us": round(us, 2), "launches_per_frame": 1, "algorithmic_bytes_per_launch": int(nb),
-                             "achieved": round(nb / us / 1e3, 1), "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": round(nb / (us * 1e-6) / HBM_PEAK, 4),
-                             "bytes_min_per_launch": int(nb_min), "frac_min": round(nb_min / (us * 1e-6) / HBM_PEAK, 4)}
-        dn = max(kernels, key=lambda k: kernels[k]["avg_us"])
-        dominant = {"name": dn, **kernels[dn], "share_of_frame_time": round(kernels[dn]["avg_us"] / (t_frame * 1e6), 3),
-                    "note": "HIP events on the engine stream around every launch of a 256-frame request (fs_gen_stats.slow_kernel_us / fast_kernel_us)"}
-    else:  # per-node path (--no-persistent): the frame's biggest node by bytes, measured as a graph node over distinct layer weights
-        up_us = lm.bench_kernel(3, int(T_avg), 50)
-        up_bytes = 2 * (2 * cfg["intermediate_size"] * cfg["dim"]) + 8 * cfg["dim"] + 4 * cfg["intermediate_size"]
-        dominant = {"name": "k_ffn_up<bf16, 1024> (RMSNorm + W1||W3 GEMV + SwiGLU; 56 launches per frame)", "algorithmic_bytes_per_launch": up_bytes,
-                    "avg_us": round(up_us, 2), "achieved": round(up_bytes / up_us / 1e3, 1), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                    "frac": round(up_bytes / (up_us * 1e-6) / HBM_PEAK, 4), "note": "graph node incl. the launch floor; fs_lm_bench_kernel"}
     b_min = b_slow + b_fast_min
-    # the reference's DEFAULT request is sampled (temp 0.7 / top-k 256: llama_generate.rs:114-124, server/lib/utils/load.rs:116-125; top-p 0.8 as
-    # BASELINE.json configs[2]); `value` above is the greedy-parity configuration BASELINE.json names.  Same prompt, same 256 frames, same two
-    # launches per frame with the block-parallel sampler inside k_fast_persist<true>; outside the timed region.  "flat" = the synthetic weights'
-    # near-uniform rows (every draw runs the full top-k / top-p chain: the worst case); "peaked" = temp 0.02 on the same weights (the largest
-    # probability alone exceeds top_p on most rows, as on a trained head: the sampler's one-weight shortcut).
-    sampled = {}
-    for tag, skw in (("flat_rows", dict(temp=0.7, top_p=0.8, top_k=256)), ("peaked_rows", dict(temp=0.02, top_p=0.8, top_k=256))):
-        for _ in range(2):
+    full = {}  # roofline.kernels / dominant_kernel / sampled: --full only, each takes requests of its own
+    if args.full:
+        kernels, dominant = {}, None
+        # the kernels of the timed region, one by one: one more request in measurement mode (FS_GEN_TIME_KERNELS: the same two persistent
+        # launches per frame, a HIP event in front of / between / behind them on the engine stream); rocprofv3's averages for the same
+        # kernels are committed under profiles/ and checked against these by tools/check_roofline.py
+        if kpf == 2:
             lm.clear_slow_layer_caches()
-            lm.generate_blocking(prompt, M, repetition_penalty=1.2, seed=1, ignore_eos=True, persistent=not args.no_persistent, **skw)
-        sst = lm.last_stats()
-        s_frame = sst["decode_ms"] * 1e-3 / (args.frames - 1)
-        sampled[tag] = {"sampling": skw, "frame_us": round(s_frame * 1e6, 2), "decode_frames_per_s": round(1.0 / s_frame, 1),
-                        "achieved": round(bf / s_frame / 1e9, 2), "frac": round(bf / s_frame / HBM_PEAK, 4), "kernels_per_frame": int(sst["kernels_per_frame"])}
+            outk = lm.generate_blocking(prompt, M, time_kernels=True, **samp)
+            assert np.array_equal(outk, out), "measurement mode changed the tokens"
+            stk = lm.last_stats()
+            for name, us, nb, nb_min, what in (
+                    ("k_slow_persist", stk["slow_kernel_us"], b_slow, b_slow, "one launch = forward_generate of one token: 24 blocks over the paged KV cache + norm + audio-range head"),
+                    ("k_fast_persist", stk["fast_kernel_us"], b_fast, b_fast_min, "one launch = the slow-token decision + 8 x forward_generate_fast + 8 codebook decisions + next-input embedding; "
+                                                                                "algorithmic bytes count the weights once per pass (SURVEY.md 8d), bytes_min once per launch (they stay on chip)")):
+                kernels[name] = {"what": what, "avg_us": round(us, 2), "launches_per_frame": 1, "algorithmic_bytes_per_launch": int(nb),
+                                 "achieved": round(nb / us / 1e3, 1), "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": round(nb / (us * 1e-6) / HBM_PEAK, 4),
+                                 "bytes_min_per_launch": int(nb_min), "frac_min": round(nb_min / (us * 1e-6) / HBM_PEAK, 4)}
+            dn = max(kernels, key=lambda k: kernels[k]["avg_us"])
+            dominant = {"name": dn, **kernels[dn], "share_of_frame_time": round(kernels[dn]["avg_us"] / (t_frame * 1e6), 3),
+                        "note": "HIP events on the engine stream around every launch of a 256-frame request (fs_gen_stats.slow_kernel_us / fast_kernel_us)"}
+        else:  # per-node path (--no-persistent): the frame's biggest node by bytes, measured as a graph node over distinct layer weights
+            up_us = lm.bench_kernel(3, int(T_avg), 50)
+            up_bytes = 2 * (2 * cfg["intermediate_size"] * cfg["dim"]) + 8 * cfg["dim"] + 4 * cfg["intermediate_size"]
+            dominant = {"name": "k_ffn_up<bf16, 1024> (RMSNorm + W1||W3 GEMV + SwiGLU; 56 launches per frame)", "algorithmic_bytes_per_launch": up_bytes,
+                        "avg_us": round(up_us, 2), "achieved": round(up_bytes / up_us / 1e3, 1), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+                        "frac": round(up_bytes / (up_us * 1e-6) / HBM_PEAK, 4), "note": "graph node incl. the launch floor; fs_lm_bench_kernel"}
+        # the reference's DEFAULT request is sampled (temp 0.7 / top-k 256: llama_generate.rs:114-124, server/lib/utils/load.rs:116-125; top-p 0.8 as
+        # BASELINE.json configs[2]); `value` above is the greedy-parity configuration BASELINE.json names.  Same prompt, same 256 frames, same two
+        # launches per frame with the block-parallel sampler inside k_fast_persist<true>; outside the timed region.  "flat" = the synthetic weights'
+        # near-uniform rows (every draw runs the full top-k / top-p chain: the worst case); "peaked" = temp 0.02 on the same weights (the largest
+        # probability alone exceeds top_p on most rows, as on a trained head: the sampler's one-weight shortcut).
+        sampled = {}
+        for tag, skw in (("flat_rows", dict(temp=0.7, top_p=0.8, top_k=256)), ("peaked_rows", dict(temp=0.02, top_p=0.8, top_k=256))):
+            for _ in range(2):
+                lm.clear_slow_layer_caches()
+                lm.generate_blocking(prompt, M, repetition_penalty=1.2, seed=1, ignore_eos=True, persistent=not args.no_persistent, **skw)
+            sst = lm.last_stats()
+            s_frame = sst["decode_ms"] * 1e-3 / (args.frames - 1)
+            sampled[tag] = {"sampling": skw, "frame_us": round(s_frame * 1e6, 2), "decode_frames_per_s": round(1.0 / s_frame, 1),
+                            "achieved": round(bf / s_frame / 1e9, 2), "frac": round(bf / s_frame / HBM_PEAK, 4), "kernels_per_frame": int(sst["kernels_per_frame"])}
+        full = {"kernels": kernels, "dominant_kernel": dominant,
+                "sampled": {"what": "the same request under the reference's default sampling (on-device top-k / top-p / WeightedIndex, token-exact StdRng stream) "
+                                    "instead of greedy: decode frame time and fraction of the same algorithmic bytes", **sampled}}
     traffic = offline_traffic(kpf)
     res = {
         "metric": "codec tokens/sec (frames/s; 1 frame = 1 slow + 8 codebook tokens = 2048 PCM samples), Fish-1.5 batch=1",
@@ -403,14 +430,11 @@ def main():
                      "frac": round(achieved / HBM_PEAK, 4),
                      **traffic,
                      "algorithmic_bytes_per_frame": int(bf), "frame_us": round(t_frame * 1e6, 2), "kv_len_avg": T_avg, "kernels_per_frame": kpf,
-                     "bytes_min_per_frame": int(b_min), "frac_min": round(b_min / t_frame / HBM_PEAK, 4),
-                     "kernels": kernels, "dominant_kernel": dominant,
-                     "sampled": {"what": "the same request under the reference's default sampling (on-device top-k / top-p / WeightedIndex, token-exact StdRng stream) "
-                                         "instead of greedy: decode frame time and fraction of the same algorithmic bytes", **sampled}},
+                     "bytes_min_per_frame": int(b_min), "frac_min": round(b_min / t_frame / HBM_PEAK, 4), **full},
     }
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         res["extras"] = extras(cfg, tok)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         res.update(cpu_baseline_and_parity(cfg, tok))
     if rank == 0:
         print(json.dumps(res), flush=True)

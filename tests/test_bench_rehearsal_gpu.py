@@ -77,7 +77,21 @@ def test_bench_config3_two_ranks_on_one_gpu():
 def test_bench_config1_two_ranks_on_one_gpu():
     """`bench.py --gpus 2` (the headline configuration, replicas): rank 0 loads, rank 1 receives the arena and adopts it; bench.py itself
     asserts that the replicas' greedy tokens are identical and deterministic across requests"""
-    check_config1(run_bench(["--gpus", "2", "--frames", "48", "--steps", "2", "--warmup", "1"], ONE_GPU), 2, 48, 2, 1)
+    check_config1(run_bench(["--gpus", "2", "--frames", "48", "--steps", "2", "--warmup", "1", "--full"], ONE_GPU), 2, 48, 2, 1)
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """a plain `bench.py --gpus 1` (no --full) times its --steps requests and prints the line, without the measurements that take runs of
+    their own; --dump-outputs writes the codes the last timed step returned, identical from run to run with the same arguments"""
+    dumps = []
+    for d in ("a", "b"):
+        j = run_bench(["--gpus", "1", "--frames", "32", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / d)])
+        check_config1(j, 1, 32, 2, 1)
+        assert not {"extras", "cpu_baseline", "parity"} & set(j) and not {"kernels", "dominant_kernel", "sampled"} & set(j["roofline"])
+        dumps.append(np.load(tmp_path / d / "codes.npy"))
+    a = dumps[0]
+    assert a.dtype == np.float32 and a.shape == (8, 32) and (a == np.round(a)).all() and a.min() >= 0 and a.max() < 1024
+    assert np.array_equal(a, dumps[1])
 
 
 def test_two_processes_one_gpu_share_the_persistent_kernels():

@@ -71,7 +71,7 @@ def test_bad_arguments_are_errors(comm):
 
 
 def test_bench_config1_through_a_one_rank_communicator():
-    j = run_bench(["--gpus", "1", "--frames", "32", "--steps", "1", "--warmup", "1", "--no-extras", "--no-cpu-baseline"], {"FISHRT_BENCH_COMM1": "1"})
+    j = run_bench(["--gpus", "1", "--frames", "32", "--steps", "1", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline"], {"FISHRT_BENCH_COMM1": "1"})
     assert j["fanout_backend"].startswith("rccl") and j["rccl_ranks"] == 1
     wb = j["weight_broadcast"]
     assert "error" not in wb and wb["bytes"] > 1.2e9 and wb["how"].startswith("fs_comm_broadcast_weights")

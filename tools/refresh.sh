@@ -34,7 +34,7 @@ bash tools/pmc_traffic.sh > $O/pmc_traffic.log 2>&1; tail -3 $O/pmc_traffic.log
 PMC_BATCH_PREV=${PREV:-r05_pmc_batch_traffic.json} bash tools/pmc_batch.sh > $O/pmc_batch.log 2>&1; tail -3 $O/pmc_batch.log
 [ -s $O/pmc_hbm_traffic.json ] && cp $O/pmc_hbm_traffic.json profiles/${R}_pmc_hbm_traffic.json
 [ -s $O/pmc_batch_traffic.json ] && cp $O/pmc_batch_traffic.json profiles/${R}_pmc_batch_traffic.json
-bash tools/run_bench_prof.sh > $O/run_bench_prof.log 2>&1
+bash tools/run_bench_prof.sh $O > $O/run_bench_prof.log 2>&1
 for F in 32 96; do bash tools/prof_batch.sh 32 $F > $O/prof_batch_F$F.txt 2>&1; cp $O/batch_kernel_stats.csv $O/batch_kernel_stats_F$F.csv; done
 export TMPDIR=/tmp; cd /tmp
 for RR in 4 8; do
