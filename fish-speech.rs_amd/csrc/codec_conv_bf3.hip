@@ -45,13 +45,14 @@ size_t codec_pack_bf3_elems(int Cin, int K, int Cout, bool f16);
 void codec_pack_bf3(const float* relaid, uint16_t* dst, int Cin, int K, int Cout, bool f16, hipStream_t st);
 void codec_conv1d_bf3(const float* x, const uint16_t* xp, int B, int Cin, int T, const uint16_t* wp, bool f16, const float* bias, int Cout, int K,
                       int dil, bool pre_silu, int epi, const float* res, const float* gamma, float* y, uint16_t* yp, bool post_silu, int ps,
-                      hipStream_t st, const uint16_t* ctx_in, uint16_t* ctx_out, const float* mean_a, const float* mean_b);
+                      hipStream_t st, const uint16_t* ctx_in, uint16_t* ctx_out, const float* mean_a, const float* mean_b, const long long* ctx_off);
 void codec_respair_f16(const uint16_t* xp, int B, int C, int T, const uint16_t* w1p, const float* b1, const uint16_t* w2p, const float* b2, int K, int dil,
                        const float* res, float* y, uint16_t* yp, hipStream_t st, const uint16_t* mid_ctx_in, uint16_t* mid_ctx_out,
-                       const uint16_t* ctx_in, uint16_t* ctx_out, const float* mean_a, const float* mean_b);
-void codec_act_split(const float* x, int B, int C, int T, bool silu, uint16_t* planes, bool f16, hipStream_t st, const uint16_t* ctx_in, uint16_t* ctx_out);
+                       const uint16_t* ctx_in, uint16_t* ctx_out, const float* mean_a, const float* mean_b, const long long* ctx_off);
+void codec_act_split(const float* x, int B, int C, int T, bool silu, uint16_t* planes, bool f16, hipStream_t st, const uint16_t* ctx_in, uint16_t* ctx_out,
+                     const long long* ctx_off);
 void codec_mean3_planes(const float* a, const float* b, const float* c, int B, int C, int T, bool silu, uint16_t* planes, bool f16, hipStream_t st,
-                        const uint16_t* ctx_in, uint16_t* ctx_out);
+                        const uint16_t* ctx_in, uint16_t* ctx_out, const long long* ctx_off);
 void codec_range_reset(hipStream_t st);
 void codec_range_read(unsigned long long* out2, hipStream_t st);
 }  // namespace c3chk
@@ -165,7 +166,18 @@ __device__ unsigned long long g_c3prof[8];
 // ParallelBlock mean folded into a residual conv (hifi_gan.rs:114-117): when `mean_a` is set, the residual epilogue's value c = res + conv
 // (the third ResBlock's output) becomes ((mean_a + mean_b) + c) / 3 -- the same f32 operations in the same order as k_mean3_planes / k_mean3 --
 // before it is stored / split, so the third block's f32 output and the mean kernel's three reads never touch memory.
-struct PlaneCtx { const uint16_t* ci; uint16_t* co; const float* mean_a = nullptr; const float* mean_b = nullptr; };
+// Multi-stream decoding (fs_codec_streams_*): the items of a launch are chunks of different streams, each with its own contexts -- item z reads
+// its context at ci + off[2z] and writes it at co + off[2z + 1] (u16 element offsets into the engine's context pool; off null: one stream).
+struct PlaneCtx {
+    const uint16_t* ci; uint16_t* co; const float* mean_a = nullptr; const float* mean_b = nullptr; const long long* off = nullptr;
+};
+__device__ __forceinline__ PlaneCtx c3_item_ctx(PlaneCtx pc, int z) {
+    if (pc.off) {
+        if (pc.ci) pc.ci += pc.off[2 * z];
+        if (pc.co) pc.co += pc.off[2 * z + 1];
+    }
+    return pc;
+}
 template <bool F16>
 __device__ __forceinline__ void c3_zero_pad(uint16_t* pb, int CG, int T, int g_first, int n_groups, int tid, int nthreads, const uint16_t* ci = nullptr) {
     constexpr int NP = F16 ? 1 : 2;
@@ -181,6 +193,7 @@ __device__ __forceinline__ void c3_zero_pad(uint16_t* pb, int CG, int T, int g_f
 // f32 (C, T) -> planes, optional SiLU.  One thread per (8-channel group, t).
 template <bool F16>
 __global__ void k_act_split(const float* __restrict__ x, int C, int T, int silu, uint16_t* __restrict__ planes, PlaneCtx pc) {
+    pc = c3_item_ctx(pc, blockIdx.z);
     const int t = blockIdx.x * blockDim.x + threadIdx.x, g = blockIdx.y, CG = C >> 3;
     const float* xb = x + (size_t)blockIdx.z * C * T;
     uint16_t* pb = planes + (size_t)blockIdx.z * (F16 ? 1 : 2) * CG * (PP + T) * 8;
@@ -207,6 +220,7 @@ __global__ void k_act_split(const float* __restrict__ x, int C, int T, int silu,
 template <bool F16>
 __global__ void k_mean3_planes(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ c, int C, int T, int silu,
                                uint16_t* __restrict__ planes, PlaneCtx pc) {
+    pc = c3_item_ctx(pc, blockIdx.z);
     const int t = blockIdx.x * blockDim.x + threadIdx.x, g = blockIdx.y, CG = C >> 3;
     const size_t boff = (size_t)blockIdx.z * C * T;
     uint16_t* pb = planes + (size_t)blockIdx.z * (F16 ? 1 : 2) * CG * (PP + T) * 8;
@@ -448,10 +462,11 @@ __global__ __launch_bounds__(256) void k_conv1d_bf3(const float* __restrict__ x,
                 }
             }
         }
+        const PlaneCtx pcb = c3_item_ctx(pc, blockIdx.z);
         uint16_t* ypb = yp ? yp + (size_t)blockIdx.z * (F16 ? 1 : 2) * (Cout >> 3) * (PP + T) * 8 : nullptr;
-        if (ypb && t0 == 0) c3_zero_pad<F16>(ypb, Cout >> 3, T, o0 >> 3, OT / 8, tid, 256, pc.ci);
+        if (ypb && t0 == 0) c3_zero_pad<F16>(ypb, Cout >> 3, T, o0 >> 3, OT / 8, tid, 256, pcb.ci);
         c3_epilogue<F16, NT>(acc, o0 + ob, t0 + tb, h, c, Cout, T, ps, bias, epi, res ? res + boff_out : nullptr, gamma, y ? y + boff_out : nullptr,
-                        ypb, post_silu, ypb ? pc.co : nullptr);
+                        ypb, post_silu, ypb ? pcb.co : nullptr);
     }
 }
 
@@ -551,6 +566,7 @@ __global__ __launch_bounds__(256, F16 ? 3 : 2) void k_conv1d_bf3p(const uint16_t
         }
         C3_TICK(4);
     }
+    pc = c3_item_ctx(pc, blockIdx.z);  // (here, not at the top: nothing of it is live across the main loop)
     uint16_t* ypb = yp ? yp + (size_t)blockIdx.z * NPART * (Cout >> 3) * row * 8 : nullptr;
     if (ypb && t0 == 0) c3_zero_pad<F16>(ypb, Cout >> 3, T, o0 >> 3, OT / 8, tid, 256, pc.ci);
     c3_epilogue<F16, NT, EPI, PS1>(acc, o0 + ob, t0 + tb, h, c, Cout, T, ps, bias, epi, res ? res + boff_out : nullptr, gamma,
@@ -573,6 +589,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void k_conv1d_bf3t(const uint
                                                         const float* __restrict__ bias, int Cout, int dil, int epi,
                                                         const float* __restrict__ res, const float* __restrict__ gamma,
                                                         float* __restrict__ y, uint16_t* __restrict__ yp, int post_silu, int ps, int nwt, PlaneCtx pc) {
+    pc = c3_item_ctx(pc, blockIdx.z);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     u32x4* ws = reinterpret_cast<u32x4*>(smem_raw);  // [NIB][K][NPL][32]
     constexpr int NPL = F16 ? 2 : 4, NPART = F16 ? 1 : 2;
@@ -642,6 +659,11 @@ __global__ __launch_bounds__(NW * 64) void k_respair_f16t(const uint16_t* __rest
                                                    int Cp, const float* __restrict__ b1, const float* __restrict__ b2, int dil, const float* __restrict__ res,
                                                    float* __restrict__ y, uint16_t* __restrict__ yp, int nwt, PlaneCtx pc, const uint16_t* __restrict__ mci,
                                                    uint16_t* __restrict__ mco) {
+    if (pc.off) {  // multi-stream: the intermediate's contexts sit at the same per-item offsets as the output's
+        if (mci) mci += pc.off[2 * blockIdx.z];
+        if (mco) mco += pc.off[2 * blockIdx.z + 1];
+    }
+    pc = c3_item_ctx(pc, blockIdx.z);
     constexpr int C = 16 * NIB, CG = 2 * NIB, NT1 = NTO + NH, HS = NT1 * 32, WCH = NIB * K * 2 * 32;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     u32x4* ws1 = reinterpret_cast<u32x4*>(smem_raw);  // [NIB][K][2][32]
@@ -768,12 +790,14 @@ bool codec_conv1d_bf3_ok(int Cin, int Cout, int K, int dil) { return Cin >= 16 &
 template <bool F16>
 static void conv1d_bf3_impl(const float* x, const uint16_t* xp, int B, int Cin, int T, const uint16_t* wp, const float* bias, int Cout, int K,
                             int dil, bool pre_silu, int epi, const float* res, const float* gamma, float* y, uint16_t* yp, bool post_silu, int ps,
-                            hipStream_t st, const uint16_t* ctx_in, uint16_t* ctx_out, const float* mean_a, const float* mean_b) {
+                            hipStream_t st, const uint16_t* ctx_in, uint16_t* ctx_out, const float* mean_a, const float* mean_b,
+                            const long long* ctx_off) {
     constexpr int NPL = F16 ? 2 : 4;
-    const PlaneCtx pc{ctx_in, ctx_out, mean_a, mean_b};
+    const PlaneCtx pc{ctx_in, ctx_out, mean_a, mean_b, ctx_off};
     FS_REQUIRE((mean_a != nullptr) == (mean_b != nullptr) && (!mean_a || (xp && epi == CODEC_EPI_RES && ps == 1)),
                "the folded ParallelBlock mean needs both partners and a plane-input residual conv");
-    FS_REQUIRE((!ctx_in && !ctx_out) || (yp && B == 1 && T >= PP), "streaming contexts need a plane output, one item and >= 64 samples per chunk");
+    FS_REQUIRE((!ctx_in && !ctx_out) || (yp && (B == 1 || ctx_off) && T >= PP),
+               "streaming contexts need a plane output, one item (or per-item context offsets) and >= 64 samples per chunk");
     FS_REQUIRE(codec_conv1d_bf3_ok(Cin, Cout, K, dil), "conv shape outside the bf16x3 kernel's range");
     FS_REQUIRE((x != nullptr) != (xp != nullptr), "exactly one of the f32 input and the plane input");
     FS_REQUIRE(y || yp, "no output");
@@ -916,12 +940,12 @@ static void conv1d_bf3_impl(const float* x, const uint16_t* xp, int B, int Cin, 
 
 void codec_conv1d_bf3(const float* x, const uint16_t* xp, int B, int Cin, int T, const uint16_t* wp, bool f16, const float* bias, int Cout, int K,
                       int dil, bool pre_silu, int epi, const float* res, const float* gamma, float* y, uint16_t* yp, bool post_silu, int ps,
-                      hipStream_t st, const uint16_t* ctx_in, uint16_t* ctx_out, const float* mean_a, const float* mean_b) {
+                      hipStream_t st, const uint16_t* ctx_in, uint16_t* ctx_out, const float* mean_a, const float* mean_b, const long long* ctx_off) {
 #ifndef FS_C3_CHECK
-    if (g_c3_checked) return c3chk::codec_conv1d_bf3(x, xp, B, Cin, T, wp, f16, bias, Cout, K, dil, pre_silu, epi, res, gamma, y, yp, post_silu, ps, st, ctx_in, ctx_out, mean_a, mean_b);
+    if (g_c3_checked) return c3chk::codec_conv1d_bf3(x, xp, B, Cin, T, wp, f16, bias, Cout, K, dil, pre_silu, epi, res, gamma, y, yp, post_silu, ps, st, ctx_in, ctx_out, mean_a, mean_b, ctx_off);
 #endif
-    if (f16) conv1d_bf3_impl<true>(x, xp, B, Cin, T, wp, bias, Cout, K, dil, pre_silu, epi, res, gamma, y, yp, post_silu, ps, st, ctx_in, ctx_out, mean_a, mean_b);
-    else conv1d_bf3_impl<false>(x, xp, B, Cin, T, wp, bias, Cout, K, dil, pre_silu, epi, res, gamma, y, yp, post_silu, ps, st, ctx_in, ctx_out, mean_a, mean_b);
+    if (f16) conv1d_bf3_impl<true>(x, xp, B, Cin, T, wp, bias, Cout, K, dil, pre_silu, epi, res, gamma, y, yp, post_silu, ps, st, ctx_in, ctx_out, mean_a, mean_b, ctx_off);
+    else conv1d_bf3_impl<false>(x, xp, B, Cin, T, wp, bias, Cout, K, dil, pre_silu, epi, res, gamma, y, yp, post_silu, ps, st, ctx_in, ctx_out, mean_a, mean_b, ctx_off);
 }
 
 bool codec_respair_ok(int C, int K, int dil, bool f16) {
@@ -930,15 +954,16 @@ bool codec_respair_ok(int C, int K, int dil, bool f16) {
 
 void codec_respair_f16(const uint16_t* xp, int B, int C, int T, const uint16_t* w1p, const float* b1, const uint16_t* w2p, const float* b2, int K, int dil,
                        const float* res, float* y, uint16_t* yp, hipStream_t st, const uint16_t* mid_ctx_in, uint16_t* mid_ctx_out, const uint16_t* ctx_in,
-                       uint16_t* ctx_out, const float* mean_a, const float* mean_b) {
+                       uint16_t* ctx_out, const float* mean_a, const float* mean_b, const long long* ctx_off) {
 #ifndef FS_C3_CHECK
-    if (g_c3_checked) return c3chk::codec_respair_f16(xp, B, C, T, w1p, b1, w2p, b2, K, dil, res, y, yp, st, mid_ctx_in, mid_ctx_out, ctx_in, ctx_out, mean_a, mean_b);
+    if (g_c3_checked) return c3chk::codec_respair_f16(xp, B, C, T, w1p, b1, w2p, b2, K, dil, res, y, yp, st, mid_ctx_in, mid_ctx_out, ctx_in, ctx_out, mean_a, mean_b, ctx_off);
 #endif
     FS_REQUIRE(codec_respair_ok(C, K, dil, true), "ResBlock pair outside the fused kernel's range");
     FS_REQUIRE(res && (y || yp), "the fused ResBlock pair needs the residual input and an output");
     FS_REQUIRE((mean_a != nullptr) == (mean_b != nullptr), "the folded ParallelBlock mean needs both partners");
-    FS_REQUIRE((!mid_ctx_in && !mid_ctx_out && !ctx_in && !ctx_out) || (B == 1 && T >= PP), "streaming contexts need one item and >= 64 samples per chunk");
-    const PlaneCtx pc{ctx_in, ctx_out, mean_a, mean_b};
+    FS_REQUIRE((!mid_ctx_in && !mid_ctx_out && !ctx_in && !ctx_out) || ((B == 1 || ctx_off) && T >= PP),
+               "streaming contexts need one item (or per-item context offsets) and >= 64 samples per chunk");
+    const PlaneCtx pc{ctx_in, ctx_out, mean_a, mean_b, ctx_off};
     const int Cp = 64, halo = (K - 1) * dil, nib = C / 16;
     constexpr int NTO = 4;
     const int nwt = (T + 32 * NTO - 1) / (32 * NTO);
@@ -969,28 +994,30 @@ void codec_respair_f16(const uint16_t* xp, int B, int C, int T, const uint16_t* 
 }
 
 void codec_act_split(const float* x, int B, int C, int T, bool silu, uint16_t* planes, bool f16, hipStream_t st, const uint16_t* ctx_in,
-                     uint16_t* ctx_out) {
+                     uint16_t* ctx_out, const long long* ctx_off) {
 #ifndef FS_C3_CHECK
-    if (g_c3_checked) return c3chk::codec_act_split(x, B, C, T, silu, planes, f16, st, ctx_in, ctx_out);
+    if (g_c3_checked) return c3chk::codec_act_split(x, B, C, T, silu, planes, f16, st, ctx_in, ctx_out, ctx_off);
 #endif
     FS_REQUIRE(C % 8 == 0, "activation planes need a multiple of 8 channels");
-    FS_REQUIRE((!ctx_in && !ctx_out) || (B == 1 && T >= PP), "streaming contexts need one item and >= 64 samples per chunk");
+    FS_REQUIRE((!ctx_in && !ctx_out) || ((B == 1 || ctx_off) && T >= PP),
+               "streaming contexts need one item (or per-item context offsets) and >= 64 samples per chunk");
     const dim3 grid((T + 255) / 256, C / 8, B);
-    const PlaneCtx pc{ctx_in, ctx_out};
+    const PlaneCtx pc{ctx_in, ctx_out, nullptr, nullptr, ctx_off};
     if (f16) hipLaunchKernelGGL(k_act_split<true>, grid, dim3(256), 0, st, x, C, T, silu ? 1 : 0, planes, pc);
     else hipLaunchKernelGGL(k_act_split<false>, grid, dim3(256), 0, st, x, C, T, silu ? 1 : 0, planes, pc);
     FS_HIP(hipGetLastError());
 }
 
 void codec_mean3_planes(const float* a, const float* b, const float* c, int B, int C, int T, bool silu, uint16_t* planes, bool f16,
-                        hipStream_t st, const uint16_t* ctx_in, uint16_t* ctx_out) {
+                        hipStream_t st, const uint16_t* ctx_in, uint16_t* ctx_out, const long long* ctx_off) {
 #ifndef FS_C3_CHECK
-    if (g_c3_checked) return c3chk::codec_mean3_planes(a, b, c, B, C, T, silu, planes, f16, st, ctx_in, ctx_out);
+    if (g_c3_checked) return c3chk::codec_mean3_planes(a, b, c, B, C, T, silu, planes, f16, st, ctx_in, ctx_out, ctx_off);
 #endif
     FS_REQUIRE(C % 8 == 0, "activation planes need a multiple of 8 channels");
-    FS_REQUIRE((!ctx_in && !ctx_out) || (B == 1 && T >= PP), "streaming contexts need one item and >= 64 samples per chunk");
+    FS_REQUIRE((!ctx_in && !ctx_out) || ((B == 1 || ctx_off) && T >= PP),
+               "streaming contexts need one item (or per-item context offsets) and >= 64 samples per chunk");
     const dim3 grid((T + 255) / 256, C / 8, B);
-    const PlaneCtx pc{ctx_in, ctx_out};
+    const PlaneCtx pc{ctx_in, ctx_out, nullptr, nullptr, ctx_off};
     if (f16) hipLaunchKernelGGL(k_mean3_planes<true>, grid, dim3(256), 0, st, a, b, c, C, T, silu ? 1 : 0, planes, pc);
     else hipLaunchKernelGGL(k_mean3_planes<false>, grid, dim3(256), 0, st, a, b, c, C, T, silu ? 1 : 0, planes, pc);
     FS_HIP(hipGetLastError());

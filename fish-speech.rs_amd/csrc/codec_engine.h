@@ -16,6 +16,10 @@ class CodecBase {
     virtual void stream_begin() = 0;
     virtual void stream_decode(const uint32_t* codes, int T, float* pcm_out) = 0;
     virtual void stream_end() = 0;
+    // many concurrent streams on one handle (fs_codec_streams_*): one call advances n streams by T frames each; codes [n][8][T] per item
+    virtual int streams_open() = 0;
+    virtual void streams_close(int id) = 0;
+    virtual void streams_decode(int n, const int* ids, const uint32_t* codes, int T, float* pcm_out) = 0;
     virtual void encode(const float* pcm, int n, uint32_t* codes_out, size_t cap, size_t* L_out) = 0;
     virtual int sample_rate() = 0;
     virtual void set_precision(int mode) = 0;  // 0 = f32 (exact f32 products), 1 = bf16x3, 2 = f16 (default); decode only

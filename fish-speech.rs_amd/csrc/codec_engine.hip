@@ -144,21 +144,21 @@ class Codec final : public CodecBase {
     }
 
     void decode(const uint32_t* codes, int B, int T, float* pcm_out) override {
-        if (!(range_check_ && bf3_ && f16_)) { decode_impl(codes, B, T, pcm_out, false); return; }
+        if (!(range_check_ && bf3_ && f16_)) { decode_impl(codes, B, T, pcm_out, kOneShot); return; }
         FS_HIP(hipSetDevice(device_));
         unsigned long long r[2] = {0, 0};
         {
             std::lock_guard<std::mutex> g(range_guard_mutex());
             codec_range_check(true);
             codec_range_reset(st_);
-            try { decode_impl(codes, B, T, pcm_out, false); } catch (...) { codec_range_check(false); throw; }
+            try { decode_impl(codes, B, T, pcm_out, kOneShot); } catch (...) { codec_range_check(false); throw; }
             codec_range_check(false);
             codec_range_read(r, st_);
         }
         range_act_[0] += r[0]; range_act_[1] += r[1];
         std::vector<float> wide((size_t)B * T * samples_per_frame());  // (4 x 8 x 8 x 2 x 2 x 2 = 2048 for the Fish codec: config.rs:196-202)
         f16_ = false;
-        try { decode_impl(codes, B, T, wide.data(), false); } catch (...) { f16_ = true; throw; }
+        try { decode_impl(codes, B, T, wide.data(), kOneShot); } catch (...) { f16_ = true; throw; }
         f16_ = true;
         double ss = 0.0;
         bool finite = true;
@@ -203,44 +203,139 @@ class Codec final : public CodecBase {
         if (chk) {
             std::lock_guard<std::mutex> g(range_guard_mutex());
             codec_range_check(true); codec_range_reset(st_);
-            try { decode_impl(codes, 1, T, pcm_out, true); } catch (...) { codec_range_check(false); throw; }
+            try { decode_impl(codes, 1, T, pcm_out, kSingle); } catch (...) { codec_range_check(false); throw; }
             codec_range_check(false);
             unsigned long long r[2] = {0, 0};
             codec_range_read(r, st_);
             range_act_[0] += r[0]; range_act_[1] += r[1];
         } else {
-            decode_impl(codes, 1, T, pcm_out, true);
+            decode_impl(codes, 1, T, pcm_out, kSingle);
         }
         ++stream_chunk_;
     }
     void stream_end() override { stream_chunk_ = -1; }
 
+    // ---- many concurrent streams on one handle (fs_codec_streams_*).  Every open stream owns two halves (ping-pong, like the single stream)
+    // of the plane and the f32 contexts in one pool per kind, [stream][half][slot...]; a call decodes its n chunks as the n items of ONE
+    // launch sequence, and every context-carrying kernel finds item b's "in" / "out" half through a per-call device table of offsets
+    // (codec_kernels.h ctx_off) instead of a single pointer.  No copies: each item reads its context where the previous chunk left it.
+    static constexpr int kMaxStreams = 64;
+    int streams_open() override {
+        FS_HIP(hipSetDevice(device_));
+        FS_REQUIRE(loaded_, "weights not loaded: call fs_codec_load_safetensors or fs_codec_load_synthetic first");
+        FS_REQUIRE(bf3_ && C_ % 128 == 0 && (C_ >> 5) >= 16, "streaming state needs the plane data flow: f16 / bf16x3 precision, full-size codec");
+        int id = 0;
+        while (id < (int)ms_.size() && ms_[id].chunk >= 0) ++id;
+        FS_REQUIRE(id < kMaxStreams, "all 64 streams of this codec handle are open (fs_codec_streams_close one first)");
+        if (id >= ms_cap_) {  // grow the pools (doubling), keeping the contexts of the open streams
+            const int cap = std::min(kMaxStreams, std::max(4, 2 * ms_cap_));
+            DBuf np, nf;
+            np.alloc((size_t)cap * ms_stream_p_bytes());
+            nf.alloc((size_t)cap * ms_stream_f_bytes());
+            FS_HIP(hipStreamSynchronize(st_));
+            if (ms_cap_) {
+                FS_HIP(hipMemcpyAsync(np.p, mpool_p_.p, (size_t)ms_cap_ * ms_stream_p_bytes(), hipMemcpyDeviceToDevice, st_));
+                FS_HIP(hipMemcpyAsync(nf.p, mpool_f_.p, (size_t)ms_cap_ * ms_stream_f_bytes(), hipMemcpyDeviceToDevice, st_));
+                FS_HIP(hipStreamSynchronize(st_));
+            }
+            std::swap(mpool_p_.p, np.p); std::swap(mpool_p_.n, np.n);
+            std::swap(mpool_f_.p, nf.p); std::swap(mpool_f_.n, nf.n);
+            ms_cap_ = cap;
+        }
+        if (id == (int)ms_.size()) ms_.push_back(MStream{});
+        FS_HIP(hipMemsetAsync((uint8_t*)mpool_p_.p + (size_t)id * ms_stream_p_bytes(), 0, ms_stream_p_bytes(), st_));
+        FS_HIP(hipMemsetAsync((uint8_t*)mpool_f_.p + (size_t)id * ms_stream_f_bytes(), 0, ms_stream_f_bytes(), st_));
+        FS_HIP(hipStreamSynchronize(st_));
+        ms_[id].chunk = 0;
+        ms_[id].prec = precision();
+        return id;
+    }
+    void streams_close(int id) override {
+        FS_REQUIRE(id >= 0 && id < (int)ms_.size() && ms_[id].chunk >= 0, "not an open stream id of this codec handle");
+        ms_[id].chunk = -1;
+    }
+    void streams_decode(int n, const int* ids, const uint32_t* codes, int T, float* pcm_out) override {
+        // everything is validated before the first launch: a rejected call leaves every stream's contexts and parity as they were
+        FS_REQUIRE(n >= 1 && n <= kMaxStreams, "fs_codec_streams_decode takes 1 .. 64 streams per call");
+        FS_REQUIRE(T >= kStreamMinFrames, "a streamed chunk needs >= 16 frames (64 samples at the vocoder's lowest rate)");
+        for (int b = 0; b < n; ++b) {
+            FS_REQUIRE(ids[b] >= 0 && ids[b] < (int)ms_.size() && ms_[ids[b]].chunk >= 0, "not an open stream id of this codec handle");
+            for (int a = 0; a < b; ++a) FS_REQUIRE(ids[a] != ids[b], "a stream id appears twice in one call");
+            FS_REQUIRE(precision() == ms_[ids[b]].prec, "the precision mode changed since the stream was opened");
+        }
+        check_codes(codes, (size_t)n * 8 * T);
+        const size_t pb = ms_stream_p_bytes() / 2, fb = ms_stream_f_bytes() / 2;  // bytes per half
+        ms_tab_.resize((size_t)4 * n);
+        for (int b = 0; b < n; ++b) {  // element offsets of item b's (in, out) halves: plane table (u16), then f32 table
+            const int s = ids[b], par = ms_[s].chunk & 1;
+            ms_tab_[2 * b] = (long long)(((size_t)2 * s + par) * pb / 2);
+            ms_tab_[2 * b + 1] = (long long)(((size_t)2 * s + (par ^ 1)) * pb / 2);
+            ms_tab_[2 * n + 2 * b] = (long long)(((size_t)2 * s + par) * fb / 4);
+            ms_tab_[2 * n + 2 * b + 1] = (long long)(((size_t)2 * s + (par ^ 1)) * fb / 4);
+        }
+        const bool chk = range_check_ && bf3_ && f16_;
+        if (chk) {
+            std::lock_guard<std::mutex> g(range_guard_mutex());
+            codec_range_check(true); codec_range_reset(st_);
+            try { decode_impl(codes, n, T, pcm_out, kMulti); } catch (...) { codec_range_check(false); throw; }
+            codec_range_check(false);
+            unsigned long long r[2] = {0, 0};
+            codec_range_read(r, st_);
+            range_act_[0] += r[0]; range_act_[1] += r[1];
+        } else {
+            decode_impl(codes, n, T, pcm_out, kMulti);
+        }
+        for (int b = 0; b < n; ++b) ++ms_[ids[b]].chunk;  // only after the whole call went through
+    }
+
     static constexpr int kCtxSlots = 96, kStreamMinFrames = 16;
     size_t ctx_slot_bytes() const { return (size_t)2 * (C_ / 8) * CODEC_PLANE_PAD * 16; }  // 2 parts x C/8 groups x PAD slots x 16 B (largest tensor)
+    size_t ms_stream_p_bytes() const { return (size_t)2 * kCtxSlots * ctx_slot_bytes(); }             // both halves of one stream
+    size_t ms_stream_f_bytes() const { return (size_t)2 * 3 * C_ * CODEC_CTX_F32 * sizeof(float); }
 
-    void decode_impl(const uint32_t* codes, int B, int T, float* pcm_out, bool streaming) {
+    static void check_codes(const uint32_t* codes, size_t n) {
+        for (size_t i = 0; i < n; ++i)
+            if (codes[i] >= 1000u) throw Error("FSQ index out of range (gather out of bounds)");
+    }
+
+    enum { kOneShot = 0, kSingle = 1, kMulti = 2 };  // decode_impl's `streaming`: none, fs_codec_stream_*, fs_codec_streams_*
+    void decode_impl(const uint32_t* codes, int B, int T, float* pcm_out, int streaming) {
         FS_HIP(hipSetDevice(device_));
         FS_REQUIRE(loaded_, "weights not loaded: call fs_codec_load_safetensors or fs_codec_load_synthetic first");
         FS_REQUIRE(B >= 1 && T >= 1, "empty input");
+        FS_REQUIRE(streaming != kMulti || ms_tab_.size() == (size_t)4 * B, "multi-stream offset table");
         use_bf3_now_ = bf3_;
-        // streaming: context slot k of this chunk is read from the buffer the previous chunk wrote and written to the other one
+        const int G = 8;
+        check_codes(codes, (size_t)B * G * T);
+        // streaming: context slot k of this chunk is read from the buffer the previous chunk wrote and written to the other one.  Multi-stream:
+        // ci = co = slot k of stream 0's first half in the pool; the per-item table adds each item's (in, out) half
+        const long long *tab_p = nullptr, *tab_f = nullptr;
+        if (streaming == kMulti) {
+            // stream-ordered upload; ms_tab_ stays untouched until the synchronisation at the end of this call
+            dtab_.ensure(ms_tab_.size() * sizeof(long long));
+            FS_HIP(hipMemcpyAsync(dtab_.p, ms_tab_.data(), ms_tab_.size() * sizeof(long long), hipMemcpyHostToDevice, st_));
+            tab_p = (const long long*)dtab_.p;
+            tab_f = tab_p + 2 * B;
+        }
         int slot = 0, fslot = 0;
-        struct PC { const uint16_t* ci; uint16_t* co; };
+        struct PC { const uint16_t* ci; uint16_t* co; const long long* off; };
         auto pctx = [&]() -> PC {
-            if (!streaming) return PC{nullptr, nullptr};
+            if (!streaming) return PC{nullptr, nullptr, nullptr};
             FS_REQUIRE(slot < kCtxSlots, "streaming context slots exhausted");
             const size_t off = (size_t)slot++ * ctx_slot_bytes();
-            return PC{reinterpret_cast<const uint16_t*>((const uint8_t*)sctx_p_[stream_chunk_ & 1].p + off), reinterpret_cast<uint16_t*>((uint8_t*)sctx_p_[(stream_chunk_ + 1) & 1].p + off)};
+            if (streaming == kMulti) {
+                uint16_t* p = reinterpret_cast<uint16_t*>((uint8_t*)mpool_p_.p + off);
+                return PC{p, p, tab_p};
+            }
+            return PC{reinterpret_cast<const uint16_t*>((const uint8_t*)sctx_p_[stream_chunk_ & 1].p + off), reinterpret_cast<uint16_t*>((uint8_t*)sctx_p_[(stream_chunk_ + 1) & 1].p + off), nullptr};
         };
-        struct FC { const float* ci; float* co; };
+        struct FC { const float* ci; float* co; const long long* off; };
         auto fctx = [&]() -> FC {
-            if (!streaming) return FC{nullptr, nullptr};
+            if (!streaming) return FC{nullptr, nullptr, nullptr};
             const size_t off = (size_t)fslot++ * C_ * CODEC_CTX_F32;
-            return FC{sctx_f_[stream_chunk_ & 1].f() + off, sctx_f_[(stream_chunk_ + 1) & 1].f() + off};
+            if (streaming == kMulti) return FC{mpool_f_.f() + off, mpool_f_.f() + off, tab_f};
+            return FC{sctx_f_[stream_chunk_ & 1].f() + off, sctx_f_[(stream_chunk_ + 1) & 1].f() + off, nullptr};
         };
-        const int G = 8;
-        for (size_t i = 0; i < (size_t)B * G * T; ++i)
-            if (codes[i] >= 1000u) throw Error("FSQ index out of range (gather out of bounds)");
         const size_t max_elems = (size_t)B * C_ * 4 * T * 8;  // largest activation: (C/2) x 32T .. (C/32) x 2048T = C*64*T
         (void)max_elems;
         const size_t act = (size_t)B * (size_t)C_ * 64 * T;   // every HiFiGAN stage holds C * 64 * T / 2^(i+1) * 2^... <= C*64*T... see stages
@@ -250,7 +345,7 @@ class Codec final : public CodecBase {
         float *x = buf_[0].f(), *t1 = buf_[1].f(), *t2 = buf_[2].f(), *r = buf_[3].f(), *acc0 = buf_[4].f(), *acc1 = buf_[5].f(),
               *acc2 = buf_[6].f();
         // quantizer.decode: FSQ lookup + project_out, concat groups -> (B, C, T)
-        codec_fsq_project((const uint32_t*)dcodes_.p, B, G, T, R(proj_w_), R(proj_b_), C_ / G, x, st_);
+        codec_fsq_project((const uint32_t*)dcodes_.p, B, G, T, R(proj_w_), R(proj_b_), C_ / G, x, st_, streaming == kMulti);
         int Tc = T;
         // upsample.0 then upsample.1 (quantizer.rs:126-133): transposed conv (k = s = 2) + ConvNeXt block
         // bf16x3 mode with 16-channel-block widths: the pointwise convs read and write activation planes as well (codec_conv_bf3.hip)
@@ -267,15 +362,15 @@ class Codec final : public CodecBase {
                 codec_tconv1d_planes(bp0, B, C_, Tc, conv(up_conv_[i]), 2, t1, st_);
                 Tc *= 2;
                 const FC fd = fctx();  // the depthwise k = 7 conv reads 6 samples of left context
-                codec_dwconv_ln(t1, B, C_, Tc, R(c.dw), R(c.db), R(c.lnw), R(c.lnb), t2, st_, fd.ci);
-                if (streaming) codec_save_tail_f32(t1, C_, Tc, fd.co, st_);
+                codec_dwconv_ln(t1, B, C_, Tc, R(c.dw), R(c.db), R(c.lnw), R(c.lnb), t2, st_, fd.ci, fd.off);
+                if (streaming) codec_save_tail_f32(t1, B, C_, Tc, fd.co, st_, fd.off);
                 codec_act_split(t2, B, C_, Tc, false, bp0, f16_, st_);
                 codec_conv1d_planes(nullptr, bp0, B, C_, Tc, conv(c.pw1), 1, false, CODEC_EPI_GELU, nullptr, nullptr, nullptr, bp1, false, st_);
                 // pwconv2 + gamma + residual: the sum feeds the next transposed conv / conv_pre as planes (no SiLU in front of either);
                 // only conv_pre (after the second block) reads left context from it
-                const PC pb = i == 1 ? pctx() : PC{nullptr, nullptr};
+                const PC pb = i == 1 ? pctx() : PC{nullptr, nullptr, nullptr};
                 codec_conv1d_planes(nullptr, bp1, B, 4 * C_, Tc, conv(c.pw2), 1, false, CODEC_EPI_GAMMA_RES, t1, R(c.gamma), nullptr, bp0, false, st_,
-                                    pb.ci, pb.co);
+                                    pb.ci, pb.co, nullptr, nullptr, pb.off);
                 continue;
             }
             codec_tconv1d(x, B, C_, Tc, conv(up_conv_[i]), 2, false, t1, st_);
@@ -295,8 +390,8 @@ class Codec final : public CodecBase {
             for (auto& b : pbuf_) b.ensure(act * sizeof(float) + (size_t)B * C_ * CODEC_PLANE_PAD * 4 + (256 << 10));
             xp = pbuf_[2].u16(); t1p = pbuf_[1].u16(); t2p = pbuf_[3].u16(); accp = pbuf_[4].u16();
             const PC px = pctx();
-            if (bb_planes) codec_conv1d_planes(nullptr, bp0, B, C_, Tc, conv(conv_pre_), 1, false, CODEC_EPI_NONE, nullptr, nullptr, nullptr, xp, true, st_, px.ci, px.co);
-            else codec_conv1d_planes(x, nullptr, B, C_, Tc, conv(conv_pre_), 1, false, CODEC_EPI_NONE, nullptr, nullptr, nullptr, xp, true, st_, px.ci, px.co);
+            if (bb_planes) codec_conv1d_planes(nullptr, bp0, B, C_, Tc, conv(conv_pre_), 1, false, CODEC_EPI_NONE, nullptr, nullptr, nullptr, xp, true, st_, px.ci, px.co, nullptr, nullptr, px.off);
+            else codec_conv1d_planes(x, nullptr, B, C_, Tc, conv(conv_pre_), 1, false, CODEC_EPI_NONE, nullptr, nullptr, nullptr, xp, true, st_, px.ci, px.co, nullptr, nullptr, px.off);
         } else {
             codec_conv1d(x, B, C_, Tc, conv(conv_pre_), 1, false, CODEC_EPI_NONE, nullptr, nullptr, t1, st_);
             std::swap(x, t1);
@@ -308,12 +403,12 @@ class Codec final : public CodecBase {
                 codec_tconv1d_planes(xp, B, ch, Tc, conv(ups_[s]), rates[s], t1, st_);  // ups[i](silu(x)); xp holds split(silu(x))
                 ch /= 2; Tc *= rates[s];
                 const PC p1 = pctx();
-                codec_act_split(t1, B, ch, Tc, true, t1p, f16_, st_, p1.ci, p1.co);
+                codec_act_split(t1, B, ch, Tc, true, t1p, f16_, st_, p1.ci, p1.co, p1.off);
                 for (int j = 0; j < 3; ++j) {  // ResBlock1 (hifi_gan.rs:74-85): x += c2(silu(c1(silu(x)))), both convs dilated
                     const float* cur = t1;
                     const uint16_t* curp = t1p;
                     for (int m = 0; m < 3; ++m) {
-                        const PC pa = pctx(), pb2 = m < 2 ? pctx() : PC{nullptr, nullptr};
+                        const PC pa = pctx(), pb2 = m < 2 ? pctx() : PC{nullptr, nullptr, nullptr};
                         const ConvW w1 = conv(res_[s][j][0][m]), w2 = conv(res_[s][j][1][m]);
                         if (w1.f16 && w2.f16 && w1.k == w2.k && codec_respair_ok(ch, w1.k, dils[m], true)) {
                             // thin stages, f16 mode: the pair in ONE kernel (the intermediate stays in LDS).  Its output planes go to the buffer the
@@ -323,20 +418,20 @@ class Codec final : public CodecBase {
                                 if (stage_planes(s + 1)) {
                                     const PC pm = pctx();
                                     codec_respair_f16(curp, B, ch, Tc, w1.wp, w1.b, w2.wp, w2.b, w1.k, dils[m], cur, nullptr, xp, st_, pa.ci, pa.co, pm.ci, pm.co,
-                                                      acc0, acc1);
+                                                      acc0, acc1, pa.off);
                                 } else {
                                     codec_respair_f16(curp, B, ch, Tc, w1.wp, w1.b, w2.wp, w2.b, w1.k, dils[m], cur, x, nullptr, st_, pa.ci, pa.co, nullptr, nullptr,
-                                                      acc0, acc1);
+                                                      acc0, acc1, pa.off);
                                 }
                                 break;
                             }
                             codec_respair_f16(curp, B, ch, Tc, w1.wp, w1.b, w2.wp, w2.b, w1.k, dils[m], cur, accs[j], m < 2 ? outp : nullptr, st_, pa.ci, pa.co,
-                                              pb2.ci, pb2.co);
+                                              pb2.ci, pb2.co, nullptr, nullptr, pa.off);
                             cur = accs[j]; curp = outp;
                             continue;
                         }
                         codec_conv1d_planes(nullptr, curp, B, ch, Tc, conv(res_[s][j][0][m]), dils[m], true, CODEC_EPI_NONE, nullptr, nullptr,
-                                            nullptr, t2p, true, st_, pa.ci, pa.co);
+                                            nullptr, t2p, true, st_, pa.ci, pa.co, nullptr, nullptr, pa.off);
                         if (j == 2 && m == 2 && fold_mean_) {
                             // the ParallelBlock mean (hifi_gan.rs:114-117) inside the epilogue of the last residual conv: ((acc0 + acc1) + this
                             // block's output) / 3 goes straight to the next stage's input planes (or, after the last stage, to conv_post's f32
@@ -344,7 +439,7 @@ class Codec final : public CodecBase {
                             if (stage_planes(s + 1)) {
                                 const PC pm = pctx();
                                 codec_conv1d_planes(nullptr, t2p, B, ch, Tc, conv(res_[s][j][1][m]), dils[m], true, CODEC_EPI_RES, cur, nullptr, nullptr,
-                                                    xp, true, st_, pm.ci, pm.co, acc0, acc1);
+                                                    xp, true, st_, pm.ci, pm.co, acc0, acc1, pm.off);
                             } else {
                                 codec_conv1d_planes(nullptr, t2p, B, ch, Tc, conv(res_[s][j][1][m]), dils[m], true, CODEC_EPI_RES, cur, nullptr, x,
                                                     nullptr, true, st_, nullptr, nullptr, acc0, acc1);
@@ -352,14 +447,14 @@ class Codec final : public CodecBase {
                             break;
                         }
                         codec_conv1d_planes(nullptr, t2p, B, ch, Tc, conv(res_[s][j][1][m]), dils[m], true, CODEC_EPI_RES, cur, nullptr, accs[j],
-                                            m < 2 ? accp : nullptr, true, st_, pb2.ci, pb2.co);
+                                            m < 2 ? accp : nullptr, true, st_, pb2.ci, pb2.co, nullptr, nullptr, pb2.off);
                         cur = accs[j]; curp = accp;
                     }
                 }
                 if (fold_mean_) continue;
                 if (stage_planes(s + 1)) {
                     const PC pm = pctx();
-                    codec_mean3_planes(acc0, acc1, acc2, B, ch, Tc, true, xp, f16_, st_, pm.ci, pm.co);
+                    codec_mean3_planes(acc0, acc1, acc2, B, ch, Tc, true, xp, f16_, st_, pm.ci, pm.co, pm.off);
                 } else codec_mean3(acc0, acc1, acc2, x, (size_t)B * ch * Tc, st_);
                 continue;
             }
@@ -376,8 +471,8 @@ class Codec final : public CodecBase {
             codec_mean3(acc0, acc1, acc2, x, (size_t)B * ch * Tc, st_);
         }
         const FC fp = fctx();  // conv_post (k = 13 on the 16-channel f32 mean)
-        codec_conv1d(x, B, ch, Tc, conv(conv_post_), 1, true, CODEC_EPI_TANH, nullptr, nullptr, t1, st_, fp.ci);
-        if (streaming) codec_save_tail_f32(x, ch, Tc, fp.co, st_);
+        codec_conv1d(x, B, ch, Tc, conv(conv_post_), 1, true, CODEC_EPI_TANH, nullptr, nullptr, t1, st_, fp.ci, fp.off);
+        if (streaming) codec_save_tail_f32(x, B, ch, Tc, fp.co, st_, fp.off);
         FS_HIP(hipMemcpyAsync(pcm_out, t1, sizeof(float) * (size_t)B * Tc, hipMemcpyDeviceToHost, st_));
         FS_HIP(hipStreamSynchronize(st_));
     }
@@ -648,6 +743,11 @@ class Codec final : public CodecBase {
     DBuf raw_, relaid_, packed_, packed16_, dcodes_, buf_[7], pbuf_[5];
     DBuf sctx_p_[2], sctx_f_[2];            // streaming contexts (plane tensors / f32 conv inputs), ping-pong per chunk
     int stream_chunk_ = -1, stream_prec_ = 0;  // -1: no stream open
+    struct MStream { int chunk = -1, prec = 0; };  // chunk: chunks decoded so far (its parity picks the "in" half), -1 = id free
+    std::vector<MStream> ms_;                      // fs_codec_streams_*, index = stream id
+    int ms_cap_ = 0;                               // streams the pools hold
+    DBuf mpool_p_, mpool_f_, dtab_;                // context pools [stream][half][...] and the per-call device offset table
+    std::vector<long long> ms_tab_;                // host side of the table (alive until the call's final synchronisation)
     std::vector<size_t> packed_off_, packed16_off_;
     bool fold_mean_ = getenv("FISHRT_VOC_NO_FOLD_MEAN") == nullptr;  // ParallelBlock mean inside the last residual conv's epilogue (A/B switch)
     bool range_check_ = false;              // fs_codec_set_range_check

@@ -27,13 +27,14 @@ __device__ __forceinline__ float dgelu(float x) {
 //   code[k] = ((idx / basis_k) % levels_k - hw_k) / hw_k, levels (8,5,5,5), basis (1,8,40,200), hw (4,2,2,2)
 //   z[g*dg + o][t] = sum_k code[k] * Wout_g[o][k] + b_g[o]
 // `rows`: the source row of (batch b', group slot g') is r = g'*B + b' of the (B*G, T) index matrix -- the reference's raw
-// reshape (b, g, t) -> (g, b, t, 1) (quantizer.rs:138-143), which is the identity only for B == 1.
+// reshape (b, g, t) -> (g, b, t, 1) (quantizer.rs:138-143), which is the identity only for B == 1.  item_rows: r = b'*G + g' instead (per-item
+// codes [B][G][T]: the multi-stream path, whose items are chunks of unrelated streams).
 __global__ void k_fsq_project(const uint32_t* __restrict__ codes, int B, int G, int T, const float* __restrict__ pw /*[G][dg][4]*/,
-                              const float* __restrict__ pb /*[G][dg]*/, int dg, float* __restrict__ z /*[B][G*dg][T]*/) {
+                              const float* __restrict__ pb /*[G][dg]*/, int dg, float* __restrict__ z /*[B][G*dg][T]*/, int item_rows) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int g = blockIdx.y, b = blockIdx.z;
     if (t >= T) return;
-    const int r = g * B + b;
+    const int r = item_rows ? b * G + g : g * B + b;
     const uint32_t idx = codes[(size_t)r * T + t];
     float code[4];
     const int levels[4] = {8, 5, 5, 5}, basis[4] = {1, 8, 40, 200};
@@ -62,8 +63,10 @@ template <int CPT, int TPT, int ICH>
 __global__ __launch_bounds__(256) void k_conv1d(const float* __restrict__ x, int Cin, int T, const float* __restrict__ wt /*[Cin][K][Cout]*/,
                                                 const float* __restrict__ bias, int Cout, int K, int dil, int pre_silu, int epi,
                                                 const float* __restrict__ res, const float* __restrict__ gamma, float* __restrict__ y, int ps,
-                                                const float* __restrict__ ctx /*streaming: [Cin][CODEC_CTX_F32] left context, or null*/) {
+                                                const float* __restrict__ ctx /*streaming: [Cin][CODEC_CTX_F32] left context, or null*/,
+                                                const long long* __restrict__ ctx_off /*multi-stream: per-item context offsets, or null*/) {
     constexpr int OT = 8 * CPT, TT = 32 * TPT;
+    if (ctx && ctx_off) ctx += ctx_off[2 * blockIdx.z];
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int halo = (K - 1) * dil;
     const int XS = TT + halo;
@@ -136,8 +139,9 @@ __global__ __launch_bounds__(256) void k_conv1d(const float* __restrict__ x, int
 template <int CIN>
 __global__ __launch_bounds__(128) void k_conv1d_one(const float* __restrict__ x, int T, const float* __restrict__ wt /*[CIN][K][1]*/,
                                                     const float* __restrict__ bias, int K, int pre_silu, int epi, float* __restrict__ y,
-                                                    const float* __restrict__ ctx) {
+                                                    const float* __restrict__ ctx, const long long* __restrict__ ctx_off) {
     constexpr int TT = 512, HMAX = CODEC_CTX_F32;  // 128 threads x 4 consecutive samples
+    if (ctx && ctx_off) ctx += ctx_off[2 * blockIdx.z];
     __shared__ __attribute__((aligned(16))) float xs[CIN][TT + HMAX];
     __shared__ float ws[CIN * (HMAX + 1)];
     const int halo = K - 1, t0 = blockIdx.x * TT;
@@ -322,8 +326,10 @@ __global__ __launch_bounds__(256) void k_conv1d_mfma(const float* __restrict__ x
 // One block per time step (C <= 1024 threads-strided); output stays (C, T) for the pointwise convs (k = 1) that follow.
 __global__ __launch_bounds__(256) void k_dwconv_ln(const float* __restrict__ x, int C, int T, const float* __restrict__ dw /*[C][7]*/,
                                                    const float* __restrict__ db, const float* __restrict__ lnw,
-                                                   const float* __restrict__ lnb, float* __restrict__ y, const float* __restrict__ ctx) {
+                                                   const float* __restrict__ lnb, float* __restrict__ y, const float* __restrict__ ctx,
+                                                   const long long* __restrict__ ctx_off) {
     __shared__ float red[256];
+    if (ctx && ctx_off) ctx += ctx_off[2 * blockIdx.y];
     __shared__ float vals[1024];
     const int t = blockIdx.x;
     const size_t boff = (size_t)blockIdx.y * C * T;
@@ -396,29 +402,30 @@ __global__ void k_synth_f32(float* __restrict__ dst, uint64_t key, size_t n, flo
 // ================================================================================================ launchers
 #define FS_LAUNCH_CHECK() FS_HIP(hipGetLastError())
 
-void codec_fsq_project(const uint32_t* codes, int B, int G, int T, const float* pw, const float* pb, int dg, float* z, hipStream_t st) {
-    hipLaunchKernelGGL(k_fsq_project, dim3((T + 63) / 64, G, B), dim3(64), 0, st, codes, B, G, T, pw, pb, dg, z);
+void codec_fsq_project(const uint32_t* codes, int B, int G, int T, const float* pw, const float* pb, int dg, float* z, hipStream_t st, bool item_rows) {
+    hipLaunchKernelGGL(k_fsq_project, dim3((T + 63) / 64, G, B), dim3(64), 0, st, codes, B, G, T, pw, pb, dg, z, item_rows ? 1 : 0);
     FS_LAUNCH_CHECK();
 }
 
 static void conv1d_launch(const float* x, int B, int Cin, int T, const ConvW& w, int dil, bool pre_silu, int epi, const float* res,
-                          const float* gamma, float* y, int ps, hipStream_t st, const float* ctx = nullptr) {
+                          const float* gamma, float* y, int ps, hipStream_t st, const float* ctx = nullptr, const long long* ctx_off = nullptr) {
     const int K = w.k, Cout = w.cout;
     const int halo = (K - 1) * dil;
-    FS_REQUIRE(!ctx || (B == 1 && halo <= CODEC_CTX_F32 && Cout < 16), "f32 streaming context: one item, halo <= 16, the VALU conv kernel");
+    FS_REQUIRE(!ctx || ((B == 1 || ctx_off) && halo <= CODEC_CTX_F32 && Cout < 16),
+               "f32 streaming context: one item (or per-item context offsets), halo <= 16, the VALU conv kernel");
     auto launch = [&](auto cpt, auto tpt, auto ich) {
         constexpr int CPT = decltype(cpt)::value, TPT = decltype(tpt)::value, ICH = decltype(ich)::value;
         constexpr int OT = 8 * CPT, TT = 32 * TPT;
         const size_t smem = sizeof(float) * ((size_t)ICH * (TT + halo) + (size_t)ICH * K * OT);
         FS_REQUIRE(smem <= 64 * 1024, "conv tile does not fit LDS");
         hipLaunchKernelGGL((k_conv1d<CPT, TPT, ICH>), dim3((T + TT - 1) / TT, (Cout + OT - 1) / OT, B), dim3(256), smem, st, x, Cin, T,
-                           w.wt, w.b, Cout, K, dil, pre_silu ? 1 : 0, epi, res, gamma, y, ps, ctx);
+                           w.wt, w.b, Cout, K, dil, pre_silu ? 1 : 0, epi, res, gamma, y, ps, ctx, ctx_off);
     };
     using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>; using I4 = std::integral_constant<int, 4>;
     using I8 = std::integral_constant<int, 8>; using I16 = std::integral_constant<int, 16>;
     const bool mfma_ok = Cin >= 16 && Cout >= 16 && K <= 13 && halo <= 256;
     if (Cout == 1 && Cin == 16 && dil == 1 && ps == 1 && K - 1 <= CODEC_CTX_F32 && (epi == CODEC_EPI_NONE || epi == CODEC_EPI_TANH || epi == CODEC_EPI_GELU)) {
-        hipLaunchKernelGGL((k_conv1d_one<16>), dim3((T + 511) / 512, 1, B), dim3(128), 0, st, x, T, w.wt, w.b, K, pre_silu ? 1 : 0, epi, y, ctx);
+        hipLaunchKernelGGL((k_conv1d_one<16>), dim3((T + 511) / 512, 1, B), dim3(128), 0, st, x, T, w.wt, w.b, K, pre_silu ? 1 : 0, epi, y, ctx, ctx_off);
         FS_LAUNCH_CHECK();
         return;
     }
@@ -459,8 +466,8 @@ static void conv1d_launch(const float* x, int B, int Cin, int T, const ConvW& w,
 }
 
 void codec_conv1d(const float* x, int B, int Cin, int T, const ConvW& w, int dil, bool pre_silu, int epi, const float* res,
-                  const float* gamma, float* y, hipStream_t st, const float* ctx) {
-    conv1d_launch(x, B, Cin, T, w, dil, pre_silu, epi, res, gamma, y, 1, st, ctx);
+                  const float* gamma, float* y, hipStream_t st, const float* ctx, const long long* ctx_off) {
+    conv1d_launch(x, B, Cin, T, w, dil, pre_silu, epi, res, gamma, y, 1, st, ctx, ctx_off);
 }
 
 // Transposed conv (stride s, K = s * Kc taps, right trim K - s: utils/mod.rs:110-122) as ONE causal conv with Kc taps and
@@ -476,10 +483,10 @@ void codec_tconv1d(const float* x, int B, int Cin, int Tin, const ConvW& w, int 
 
 void codec_conv1d_planes(const float* x, const uint16_t* xp, int B, int Cin, int T, const ConvW& w, int dil, bool pre_silu, int epi,
                          const float* res, const float* gamma, float* y, uint16_t* yp, bool post_silu, hipStream_t st,
-                         const uint16_t* ctx_in, uint16_t* ctx_out, const float* mean_a, const float* mean_b) {
+                         const uint16_t* ctx_in, uint16_t* ctx_out, const float* mean_a, const float* mean_b, const long long* ctx_off) {
     FS_REQUIRE(w.wp, "the plane data flow needs packed bf16x3 weights");
     codec_conv1d_bf3(x, xp, B, Cin, T, w.wp, w.f16, w.b, w.cout, w.k, dil, pre_silu, epi, res, gamma, y, yp, post_silu, 1, st, ctx_in, ctx_out, mean_a,
-                     mean_b);
+                     mean_b, ctx_off);
 }
 
 void codec_tconv1d_planes(const uint16_t* xp, int B, int Cin, int Tin, const ConvW& w, int stride, float* y, hipStream_t st) {
@@ -488,20 +495,24 @@ void codec_tconv1d_planes(const uint16_t* xp, int B, int Cin, int Tin, const Con
                      false, stride, st);
 }
 
-__global__ void k_save_tail_f32(const float* __restrict__ x, int T, float* __restrict__ ctx) {
-    ctx[(size_t)blockIdx.x * CODEC_CTX_F32 + threadIdx.x] = x[(size_t)blockIdx.x * T + T - CODEC_CTX_F32 + threadIdx.x];
+// the last CODEC_CTX_F32 samples of every channel of item blockIdx.y -> its context (ctx_off: per-item offsets, the "out" entry)
+__global__ void k_save_tail_f32(const float* __restrict__ x, int C, int T, float* __restrict__ ctx, const long long* __restrict__ ctx_off) {
+    const int b = blockIdx.y;
+    float* cb = ctx_off ? ctx + ctx_off[2 * b + 1] : ctx;
+    cb[(size_t)blockIdx.x * CODEC_CTX_F32 + threadIdx.x] = x[((size_t)b * C + blockIdx.x) * T + T - CODEC_CTX_F32 + threadIdx.x];
 }
-void codec_save_tail_f32(const float* x, int C, int T, float* ctx_out, hipStream_t st) {
+void codec_save_tail_f32(const float* x, int B, int C, int T, float* ctx_out, hipStream_t st, const long long* ctx_off) {
     FS_REQUIRE(T >= CODEC_CTX_F32, "chunk shorter than the f32 streaming context");
-    hipLaunchKernelGGL(k_save_tail_f32, dim3(C), dim3(CODEC_CTX_F32), 0, st, x, T, ctx_out);
+    FS_REQUIRE(B == 1 || ctx_off, "f32 streaming context: one item (or per-item context offsets)");
+    hipLaunchKernelGGL(k_save_tail_f32, dim3(C, B), dim3(CODEC_CTX_F32), 0, st, x, C, T, ctx_out, ctx_off);
     FS_LAUNCH_CHECK();
 }
 
 void codec_dwconv_ln(const float* x, int B, int C, int T, const float* dw, const float* db, const float* lnw, const float* lnb, float* y,
-                     hipStream_t st, const float* ctx) {
+                     hipStream_t st, const float* ctx, const long long* ctx_off) {
     FS_REQUIRE(C <= 1024, "ConvNeXt width above 1024 channels");
-    FS_REQUIRE(!ctx || B == 1, "f32 streaming context: one item");
-    hipLaunchKernelGGL(k_dwconv_ln, dim3(T, B), dim3(256), 0, st, x, C, T, dw, db, lnw, lnb, y, ctx);
+    FS_REQUIRE(!ctx || B == 1 || ctx_off, "f32 streaming context: one item (or per-item context offsets)");
+    hipLaunchKernelGGL(k_dwconv_ln, dim3(T, B), dim3(256), 0, st, x, C, T, dw, db, lnw, lnb, y, ctx, ctx_off);
     FS_LAUNCH_CHECK();
 }
 

@@ -256,6 +256,15 @@ int fs_codec_stream_decode(fs_codec_t* c, const uint32_t* codes, int T, float* p
     FS_TRY(c->impl->stream_decode(codes, T, pcm_out))
 }
 int fs_codec_stream_end(fs_codec_t* c) { FS_ARG(c, "null argument"); FS_TRY(c->impl->stream_end()) }
+int fs_codec_streams_open(fs_codec_t* c, int* stream_id) {
+    FS_ARG(c && stream_id, "null argument");
+    FS_TRY(*stream_id = c->impl->streams_open())
+}
+int fs_codec_streams_close(fs_codec_t* c, int stream_id) { FS_ARG(c, "null argument"); FS_TRY(c->impl->streams_close(stream_id)) }
+int fs_codec_streams_decode(fs_codec_t* c, int n, const int* stream_ids, const uint32_t* codes, int T, float* pcm_out) {
+    FS_ARG(c && stream_ids && codes && pcm_out, "null argument");
+    FS_TRY(c->impl->streams_decode(n, stream_ids, codes, T, pcm_out))
+}
 int fs_codec_set_precision(fs_codec_t* c, int mode) { FS_ARG(c, "null argument"); FS_TRY(c->impl->set_precision(mode)) }
 int fs_codec_precision(fs_codec_t* c) { return c ? c->impl->precision() : -1; }
 int fs_codec_set_range_check(fs_codec_t* c, int on) { FS_ARG(c, "null argument"); FS_TRY(c->impl->set_range_check(on != 0)) }

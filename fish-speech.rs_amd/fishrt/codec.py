@@ -84,6 +84,32 @@ class FireflyCodec:
     def stream_end(self):
         _ffi.check(_ffi.lib().fs_codec_stream_end(self._h))
 
+    # ---- many concurrent streams on one handle (fishrt.h fs_codec_streams_*): one launch sequence advances n streams by T frames each
+    STREAMS_MAX = 64
+
+    def streams_open(self):
+        """-> stream id: a new stream from zero left context, in the handle's current precision mode"""
+        sid = C.c_int(-1)
+        _ffi.check(_ffi.lib().fs_codec_streams_open(self._h, C.byref(sid)))
+        return int(sid.value)
+
+    def streams_close(self, stream_id):
+        _ffi.check(_ffi.lib().fs_codec_streams_close(self._h, int(stream_id)))
+
+    def streams_decode(self, ids, codes):
+        """ids: n distinct open stream ids; codes u32 (n, 8, T), T >= 16: item i is the next chunk of stream ids[i] -> f32 (n, 2048 T) PCM.
+        Per stream, the chunks' PCM concatenated is bit-identical to decode() of its whole sequence."""
+        ids = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1))
+        codes = np.ascontiguousarray(codes, np.uint32)
+        if codes.ndim != 3 or codes.shape[1] != 8 or codes.shape[0] != ids.shape[0]:
+            raise ValueError("streams_decode: codes must have shape (n, 8, T) with one item per stream id")
+        n, _, T = codes.shape
+        pcm = np.empty((n, 2048 * T), np.float32)
+        _ffi.check(_ffi.lib().fs_codec_streams_decode(self._h, int(n), ids.ctypes.data_as(C.POINTER(C.c_int)),
+                                                      codes.ctypes.data_as(C.POINTER(C.c_uint32)), int(T),
+                                                      pcm.ctypes.data_as(C.POINTER(C.c_float))))
+        return pcm
+
     def encode(self, pcm_data, lengths=None):
         """codec.rs:73-94 / firefly.rs:36-39: f32 (b, 1, n) mono 44.1 kHz PCM -> u32 (b, 8, L).  Every clip is encoded on its own
         (fishrt.h fs_codec_encode_batch; the reference's front-end would glue a batch into one signal, spectrogram.rs:33).  lengths: optional

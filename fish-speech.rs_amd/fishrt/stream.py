@@ -144,3 +144,147 @@ class StreamingSynth:
         self.stats = dict(stateful=stateful, frames=n_frames[0], lm_s=t_lm, vocoder_busy_s=t_busy[0], total_s=t_all, first_audio_s=t_first[0],
                           overlap_efficiency=(t_lm + t_busy[0] - t_all) / max(t_busy[0], 1e-9))
         return out, pcm
+
+
+class SessionStreamer:
+    """Streams the PCM of every request of a continuous-batching session (lm.Session, fs_lm_session_*) while it generates, through the
+    codec's multi-stream decode (FireflyCodec.streams_*: one stateful stream per request, many streams per vocoder call).
+
+    Every request gets its own codec stream when it is added.  After each step(k) of the session, every live request with at least
+    `chunk` frames not yet vocoded (`first_chunk` for its first piece) contributes exactly that many frames to ONE streams_decode call: one
+    call per distinct chunk length, T uniform within a call.  A request that has finished is flushed: its remaining frames go through
+    streams_decode with n = 1 when there are >= 16 of them, else through decode_chunk's halo path; then its stream is closed and its slot
+    released.  Per request, the PCM pieces concatenated are bit-identical to codec.decode of its final codes.
+
+    The vocoder runs inline, on the thread that steps the session, between two steps: rows sessions hold every CU for their persistent
+    kernels (see StreamingSynth.inline), so a vocoder in another thread would only interleave at kernel boundaries.  Keep k <= chunk: a
+    request contributes one chunk per step, so frames beyond that wait for the next step.
+
+    on_audio(tag, pcm, final) is called for every PCM piece, in order per request; step() also returns the pieces as (tag, pcm, final).
+    stats[tag]: frames, first_audio_s (add() to its first PCM piece), vocoder_s (wall time of the vocoder calls that carried its audio; a
+    shared call counts in full for each request in it), chunks.  calls: one record per vocoder call (quantum, kind, n, T)."""
+
+    def __init__(self, session, codec, chunk=64, first_chunk=32, halo=HALO, on_audio=None, clock=time.perf_counter):
+        min_frames = getattr(codec, "STREAM_MIN_FRAMES", 16)
+        if chunk < min_frames or first_chunk < min_frames:
+            raise ValueError(f"chunk and first_chunk must be >= {min_frames} frames (the codec's minimum streamed chunk)")
+        self.session, self.codec, self.chunk, self.first_chunk, self.halo = session, codec, int(chunk), int(first_chunk), halo
+        self.min_frames, self.on_audio, self.clock = min_frames, on_audio, clock
+        self.live = {}       # slot -> request record
+        self.results = {}    # tag -> final codes (C, n) of every finished request
+        self.stats = {}      # tag -> per-request numbers
+        self.calls = []      # (quantum, kind: "chunk" | "tail" | "halo", n, T)
+        self.quantum = 0
+        self.n_active = 0
+        self._admitted = 0
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def add(self, prompt, max_new_tokens, tag=None):
+        """admit a request: -> its session slot, or None when the session is full (nothing is opened then).  tag: the name its audio and
+        stats are reported under (default: the admission number 0, 1, 2, ...)"""
+        if tag is None:
+            tag = self._admitted
+        if tag in self.stats:
+            raise ValueError(f"tag {tag!r} is already in use")
+        sid = self.codec.streams_open()
+        try:
+            slot = self.session.add(prompt, max_new_tokens)
+        except BaseException:
+            self.codec.streams_close(sid)
+            raise
+        if slot is None:
+            self.codec.streams_close(sid)
+            return None
+        self._admitted += 1
+        self.live[slot] = dict(tag=tag, sid=sid, done_upto=0, t_add=self.clock())
+        self.stats[tag] = dict(frames=0, first_audio_s=None, vocoder_s=0.0, chunks=0)
+        return slot
+
+    def step(self, n_frames=8):
+        """one session step of up to n_frames frames, then the vocoder calls it makes due -> list of (tag, pcm, final).  self.n_active = the
+        session's slots still generating afterwards"""
+        self.n_active = self.session.step(n_frames)
+        self.quantum += 1
+        out = []
+        groups, finished = {}, []
+        for slot, r in self.live.items():
+            n, done = self.session.poll(slot, codes=False)
+            r["n"] = n
+            if done:
+                finished.append(slot)
+                continue
+            T = self.first_chunk if r["done_upto"] == 0 else self.chunk
+            if n - r["done_upto"] >= T:
+                groups.setdefault(T, []).append(slot)
+        for T in sorted(groups):
+            slots = groups[T]
+            codes = np.stack([self._codes(s)[:, self.live[s]["done_upto"]:self.live[s]["done_upto"] + T] for s in slots])
+            t1 = self.clock()
+            pcm = self.codec.streams_decode([self.live[s]["sid"] for s in slots], codes)
+            self._account([self.live[s] for s in slots], "chunk", T, self.clock() - t1)
+            for i, s in enumerate(slots):
+                out.append(self._deliver(self.live[s], pcm[i], T, False))
+        for slot in finished:
+            out.extend(self._finish(slot))
+        return out
+
+    def close(self):
+        """close the codec streams of requests still in flight (their slots stay with the session)"""
+        for r in self.live.values():
+            try:
+                self.codec.streams_close(r["sid"])
+            except Exception:
+                pass
+        self.live = {}
+
+    # ---- internals
+    def _codes(self, slot):
+        r = self.live[slot]
+        if r.get("codes") is None or r["codes"].shape[1] < r["n"]:
+            r["codes"], _ = self.session.poll(slot)
+        return r["codes"]
+
+    def _account(self, recs, kind, T, dt):
+        self.calls.append((self.quantum, kind, len(recs), T))
+        for r in recs:
+            self.stats[r["tag"]]["vocoder_s"] += dt
+
+    def _deliver(self, r, pcm, T, final):
+        r["done_upto"] += T
+        st = self.stats[r["tag"]]
+        st["frames"] = r["done_upto"]
+        st["chunks"] += 1
+        if st["first_audio_s"] is None:
+            st["first_audio_s"] = self.clock() - r["t_add"]
+        if self.on_audio is not None:
+            self.on_audio(r["tag"], pcm, final)
+        return (r["tag"], pcm, final)
+
+    def _finish(self, slot):
+        r = self.live[slot]
+        out = []
+        try:
+            codes = self._codes(slot)
+            a, b = r["done_upto"], r["n"]
+            t1 = self.clock()
+            if b - a >= self.min_frames:
+                pcm = self.codec.streams_decode([r["sid"]], np.ascontiguousarray(codes[None, :, a:b]))[0]
+                self._account([r], "tail", b - a, self.clock() - t1)
+                out.append(self._deliver(r, pcm, b - a, True))
+            elif b > a:
+                pcm = decode_chunk(self.codec, codes, a, b, self.halo)
+                self._account([r], "halo", b - a, self.clock() - t1)
+                out.append(self._deliver(r, pcm, b - a, True))
+            elif self.on_audio is not None:  # nothing left: the last piece was already delivered; signal the end
+                self.on_audio(r["tag"], np.zeros(0, np.float32), True)
+            self.results[r["tag"]] = codes[:, :b].copy()
+        finally:
+            del self.live[slot]
+            self.codec.streams_close(r["sid"])
+            self.session.release(slot)
+        return out

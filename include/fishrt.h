@@ -338,6 +338,22 @@ int fs_codec_encode_batch(fs_codec_t* c, const float* pcm, int b, size_t stride,
 int fs_codec_stream_begin(fs_codec_t* c);
 int fs_codec_stream_decode(fs_codec_t* c, const uint32_t* codes, int T, float* pcm_out);
 int fs_codec_stream_end(fs_codec_t* c);
+/* Many concurrent streams on ONE handle (one copy of the weights): every call advances n streams by T frames each in one launch sequence.
+ * fs_codec_streams_open: *stream_id = a new stream (0 .. 63) starting from zero left context, like fs_codec_stream_begin; its precision mode
+ * is the handle's mode at this moment, and a call that includes the stream after the mode changed is an error.  Ids of closed streams are
+ * reused (a reopened id starts clean).  At most 64 streams are open per handle.  fs_codec_streams_close frees the id.
+ * fs_codec_streams_decode: 1 <= n <= 64 DISTINCT open ids, in any order (the order does not change any stream's PCM); T >= 16 frames, the
+ * same for every item.  codes u32 [n][8][T]: item i is the next (8, T) chunk of stream stream_ids[i] -- per item, NOT the raw reshape
+ * (b, g, t) -> (g, b, t) that fs_codec_decode follows for b > 1 after the reference; pcm_out f32 [n][2048 T].  Per stream, the PCM of its
+ * chunks concatenated is bit-identical to fs_codec_decode of its whole sequence at b = 1.  Everything (ids, T, codes < 1000, precision) is
+ * validated before the first launch: a failed call leaves every stream's left context untouched.  Needs the plane data flow like the
+ * single stream ("plane data flow" error for mode-0 and channel_div > 1 handles).  With the range check on, multi-stream chunks are
+ * counted only.  Multi-streams and the single stream of fs_codec_stream_* are independent of each other.
+ * Device memory per open stream: 2 x 96 x (C/4) x 1 KiB of plane contexts + 2 x 3 x C x 64 B of f32 contexts = 24.2 MiB at C = 512; the
+ * pool keeps its high-water mark (grown in steps of doubling) until the handle is destroyed. */
+int fs_codec_streams_open(fs_codec_t* c, int* stream_id);
+int fs_codec_streams_close(fs_codec_t* c, int stream_id);
+int fs_codec_streams_decode(fs_codec_t* c, int n, const int* stream_ids, const uint32_t* codes, int T, float* pcm_out);
 /* FireflyCodec.sample_rate (codec/firefly.rs:13) */
 int fs_codec_sample_rate(fs_codec_t* c);
 /* Arithmetic of the decode path's convolutions (no reference counterpart: the reference runs the codec in f32,
