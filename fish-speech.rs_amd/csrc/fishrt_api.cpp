@@ -214,6 +214,16 @@ int fs_lm_session_poll(fs_lm_t* lm, int slot, uint32_t* codes_out, size_t cap, s
 }
 int fs_lm_session_release(fs_lm_t* lm, int slot) { FS_ARG(lm, "null argument"); FS_TRY(lm->impl->session_release(slot)) }
 int fs_lm_session_end(fs_lm_t* lm) { FS_ARG(lm, "null argument"); FS_TRY(lm->impl->session_end()) }
+int fs_lm_session_prefix_create(fs_lm_t* lm, const uint32_t* prompt, int P, int* prefix_id) {
+    FS_ARG(lm && prompt && prefix_id, "null argument");
+    FS_TRY(*prefix_id = lm->impl->session_prefix_create(prompt, P))
+}
+int fs_lm_session_prefix_release(fs_lm_t* lm, int prefix_id) { FS_ARG(lm, "null argument"); FS_TRY(lm->impl->session_prefix_release(prefix_id)) }
+int fs_lm_session_add_prefixed(fs_lm_t* lm, int prefix_id, const uint32_t* body, int L_body, int max_new_tokens, int* slot) {
+    FS_ARG(lm && body && slot, "null argument");
+    FS_TRY(*slot = lm->impl->session_add_prefixed(prefix_id, body, L_body, max_new_tokens))
+}
+int fs_lm_session_info(fs_lm_t* lm, int64_t out[8]) { FS_ARG(lm && out, "null argument"); FS_TRY(lm->impl->session_info(out)) }
 int fs_lm_last_stats(fs_lm_t* lm, fs_gen_stats* out) { FS_ARG(lm && out, "null argument"); FS_TRY(*out = lm->impl->last_stats()) }
 void* fs_lm_stream(fs_lm_t* lm) { return lm ? lm->impl->stream() : nullptr; }
 int fs_lm_bench_kernel(fs_lm_t* lm, int kind, int kv_len, int reps, float* us_per_launch) {

@@ -42,6 +42,11 @@ class LMBase {
     virtual void session_poll(int slot, uint32_t* codes_out, size_t cap, size_t* n_frames, int* done) = 0;
     virtual void session_release(int slot) = 0;
     virtual void session_end() = 0;
+    // shared conditioning prefixes of a session (fishrt.h: fs_lm_session_prefix_create / _release / fs_lm_session_add_prefixed / _info)
+    virtual int session_prefix_create(const uint32_t* prompt, int P) = 0;
+    virtual void session_prefix_release(int id) = 0;
+    virtual int session_add_prefixed(int id, const uint32_t* body, int L_body, int max_new_tokens) = 0;
+    virtual void session_info(int64_t out[8]) = 0;
     virtual void debug_capture(int n_frames) = 0;
     virtual void debug_read(float* out, int n_frames) = 0;
     virtual void debug_read_row(int row, float* out, int n_frames) = 0;

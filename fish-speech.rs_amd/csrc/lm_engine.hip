@@ -225,6 +225,7 @@ class LM final : public LMBase {
         for (auto& e : ev_batch_) if (e) (void)hipEventDestroy(e);
         if (h_pin_) (void)hipHostFree(h_pin_);
         if (ev_pf_) (void)hipEventDestroy(ev_pf_);
+        for (hipEvent_t e : ev_pft_) if (e) (void)hipEventDestroy(e);
         if (st_pf_) (void)hipStreamDestroy(st_pf_);
         if (st_) (void)hipStreamDestroy(st_);
     }
@@ -1011,12 +1012,15 @@ class LM final : public LMBase {
         FS_HIP(hipMemcpyAsync(d_rng_.p, &rng, sizeof(rng), hipMemcpyHostToDevice, st_));
         // empty slots: dead, frame 1 (so the frame-0 rule never fires), position 0 of a scratch page nobody reads
         FS_REQUIRE(!free_pages_.empty(), "KV page pool exhausted");
-        sess_scratch_ = free_pages_.back();
-        free_pages_.pop_back();
+        sess_scratch_ = take_page();
         sess_left_.assign(B_, -1);
         sess_pos_.assign(B_, 0);
         sess_hs_.assign(B_, SeqState{});
         sess_queue_.clear(); sess_flight_.clear();
+        sess_prefixes_.clear();
+        for (auto& v : sess_count_) v = 0;
+        sess_pf_ms_ = 0.0;
+        sess_timed_ = false;
         for (int b = 0; b < B_; ++b) park_slot(b);
         FS_HIP(hipMemsetAsync(d_pfx_.p, 0, sizeof(float) * (size_t)B_ * a_.dim, st_));
         FS_HIP(hipStreamSynchronize(st_));
@@ -1068,18 +1072,123 @@ class LM final : public LMBase {
         stats_.prompt_tokens += (uint64_t)L;
         return b;
     }
+    // a queued request: plain add (prompt = all L columns, start 0), prefixed add (prompt = the body's L - start columns, start = the
+    // prefix's P, tail = the prefix's partly filled last page, held until the copy has run) or a prefix's own pass (create: prompt = its P
+    // columns, all of them prefilled into the prefix's pages; slot -1)
+    struct PendingAdd {
+        int slot = -1, L = 0, n_iter = 0, order = 0, start = 0, prefix = -1, tail = -1;
+        bool create = false;
+        std::vector<uint32_t> prompt;
+        int rows() const { return create ? L : L - start - 1; }   // tokens this member runs through the slow transformer
+        int cols() const { return create ? L : L - start; }       // columns of `prompt`
+        int end() const { return create ? L : L + n_iter - 1; }   // positions whose K/V the member keeps
+    };
+    // a session's shared prefix: its pages (one reference each, held until released or the session ends; slots add their own on the
+    // full ones) and whether its own pass has still to be activated (a release then waits for that)
+    struct SessPrefix { int P = 0; std::vector<int> pages; bool live = false, pending = false; };
+    // Shared conditioning prefixes (fishrt.h: fs_lm_session_prefix_create).  The prefix is queued like an add; its pages are taken now,
+    // so the pool check stays cumulative over everything admitted since.
+    int session_prefix_create(const uint32_t* prompt, int P) override {
+        use_device();
+        FS_REQUIRE(sess_active_, "no open session");
+        FS_REQUIRE(P >= 1, "empty prefix");
+        FS_REQUIRE(P < a_.max_seq_len, "prefix leaves no room for a body within max_seq_len");
+        validate_tokens(prompt, 0, 1, P);
+        ensure_prefill2_buffers();
+        const int np = (P + KV_PAGE - 1) / KV_PAGE;
+        if ((int)free_pages_.size() < np) return -1;
+        const int C1 = a_.num_codebooks + 1;
+        SessPrefix px;
+        px.P = P; px.live = true; px.pending = true;
+        for (int j = 0; j < np; ++j) px.pages.push_back(take_page());
+        sess_prefixes_.push_back(std::move(px));
+        PendingAdd pa;
+        pa.create = true; pa.L = P; pa.prefix = (int)sess_prefixes_.size() - 1;
+        pa.prompt.assign(prompt, prompt + (size_t)C1 * P);
+        sess_queue_.push_back(std::move(pa));
+        return (int)sess_prefixes_.size() - 1;
+    }
+    SessPrefix& live_prefix(int id) {
+        FS_REQUIRE(sess_active_, "no open session");
+        FS_REQUIRE(id >= 0 && id < (int)sess_prefixes_.size() && sess_prefixes_[id].live, "unknown or released prefix id");
+        return sess_prefixes_[id];
+    }
+    void drop_prefix_pages(SessPrefix& px) {
+        for (int p : px.pages) put_page(p);
+        px.pages.clear();
+    }
+    void session_prefix_release(int id) override {
+        use_device();
+        SessPrefix& px = live_prefix(id);
+        px.live = false;
+        if (!px.pending) drop_prefix_pages(px);  // (its pass still queued or in flight: activate_pending drops them after it)
+    }
+    // == session_add(concat(prefix, body)) except that the slot's page table starts with the prefix's full pages (shared) and only the
+    // body is prefilled; the slot reserves its private pages only
+    int session_add_prefixed(int id, const uint32_t* body, int L_body, int max_new_tokens) override {
+        use_device();
+        SessPrefix& px = live_prefix(id);
+        FS_REQUIRE(L_body >= 1, "empty body (a prefixed add needs its last prompt column)");
+        const int P = px.P, L = P + L_body;
+        if (L > a_.max_seq_len) throw Error("prompt exceeds max_seq_len (dual_ar.rs:623-624)");
+        int b = -1;
+        for (int i = 0; i < B_; ++i) if (sess_left_[i] == -1) { b = i; break; }
+        if (b < 0) return -1;
+        const int C1 = a_.num_codebooks + 1;
+        validate_tokens(body, 0, 1, L_body);
+        long long n_iter = 1 + std::max<long long>(0, (long long)max_new_tokens - L + 1);  // static_batch.rs:122,262-267
+        n_iter = std::min<long long>(n_iter, (long long)a_.max_seq_len - L + 1);           // a slot stops at max_seq_len instead of erroring
+        FS_REQUIRE(n_iter <= out_cap_, "generation longer than the output staging buffer");
+        ensure_prefill2_buffers();
+        const int nfull = P / KV_PAGE;
+        auto& pg = seq_pages_[b];
+        FS_REQUIRE(pg.empty(), "a free slot still holds KV pages");
+        {   // not enough free KV pages for the private ones right now: not an error, like session_add
+            const int need = (L + (int)n_iter - 1 + KV_PAGE - 1) / KV_PAGE;
+            if ((int)free_pages_.size() < need - nfull) return -1;
+        }
+        for (int j = 0; j < nfull; ++j) { pg.push_back(px.pages[j]); ++page_refs_[px.pages[j]]; }
+        alloc_pages(b, L + (int)n_iter - 1);
+        PendingAdd pa;
+        pa.slot = b; pa.L = L; pa.n_iter = (int)n_iter; pa.order = sess_adds_++; pa.start = P; pa.prefix = id;
+        if (P % KV_PAGE) { pa.tail = px.pages[nfull]; ++page_refs_[pa.tail]; }
+        pa.prompt.assign(body, body + (size_t)C1 * L_body);
+        sess_queue_.push_back(std::move(pa));
+        sess_left_[b] = -2;  // reserved: prefilling
+        stats_.prompt_tokens += (uint64_t)L;
+        return b;
+    }
+    void session_info(int64_t out[8]) override {
+        int64_t shared = 0, live = 0;
+        for (int r : page_refs_) shared += r > 1;
+        for (const SessPrefix& px : sess_prefixes_) live += px.live;
+        out[0] = (int64_t)free_pages_.size(); out[1] = shared; out[2] = live;
+        for (int k = 0; k < 4; ++k) out[3 + k] = sess_count_[k];
+        out[7] = (int64_t)std::llround(sess_pf_ms_ * 1000.0);
+    }
     // launch the prefill of the next group of queued requests (ONE pass on the prefill stream, nothing waited for); no-op while an
-    // earlier group is still in flight -- the rest of the queue follows once that one has been activated
+    // earlier group is still in flight -- the rest of the queue follows once that one has been activated.
+    // Shared prefixes: a prefix's own pass (pa.create) prefills all P of its positions into its pages; creations go in passes of their
+    // own, ahead of every add queued with them (an add on a prefix reads its pages, and stream order on the prefill stream puts that
+    // read after the creating pass).  A prefixed member starts at position P (RowsCtx.seq_states in a group pass) and runs its body
+    // columns only; when P % 64 != 0 its first private page first gets a copy of the prefix's partly filled last page (k_kv_page_copy,
+    // one launch for the pass, in stream order ahead of it).
     void flush_pending() {
         if (sess_queue_.empty() || !sess_flight_.empty()) return;
         const int C1 = a_.num_codebooks + 1, C = a_.num_codebooks;
-        std::stable_sort(sess_queue_.begin(), sess_queue_.end(), [](const PendingAdd& x, const PendingAdd& y) { return x.L > y.L; });
+        std::stable_sort(sess_queue_.begin(), sess_queue_.end(),
+                         [](const PendingAdd& x, const PendingAdd& y) { return x.create != y.create ? x.create : x.rows() > y.rows(); });
         const bool flash = a_.head_dim == 64;
         size_t i = 0;
         int S = 1;
+        FS_HIP(hipEventRecord(ev_pft_[0], st_pf_));
+        sess_timed_ = true;
         {
-            const int Lp = sess_queue_[i].L - 1;  // the longest of this pass (sorted): tokens that run through the slow transformer
-            if (Lp < 1) {                         // only single-token prompts are left: no pass, they go live at the next activation
+            const int Lp = sess_queue_[i].rows();  // the longest of this pass (sorted): tokens that run through the slow transformer
+            if (Lp < 1) {                          // only single-token prompts are left: no pass, they go live at the next activation
+                launch_tail_copies(sess_queue_.begin(), sess_queue_.end());
+                for (const PendingAdd& pa : sess_queue_) sess_count_[2] += pa.start;
+                FS_HIP(hipEventRecord(ev_pft_[1], st_pf_));
                 FS_HIP(hipEventRecord(ev_pf_, st_pf_));
                 sess_flight_ = std::move(sess_queue_);
                 sess_queue_.clear();
@@ -1087,15 +1196,18 @@ class LM final : public LMBase {
             }
             if (flash && Lp <= kRowsCap) {
                 const int fit = std::max(1, std::min(kRowsCap / Lp, B_));
-                // pad positions write K/V up to Lp: every member must own pages that far (bounded: they go back with the slot).  The extra
-                // pages are counted CUMULATIVELY over the group -- checked per member, several short-budget members could each pass and
-                // alloc_pages would then throw in the middle of the flush with the queue half consumed
+                // pad positions write K/V up to start + Lp: every member must own pages that far (bounded: they go back with the slot,
+                // or at activation for a prefix).  The extra pages are counted CUMULATIVELY over the group -- checked per member,
+                // several short-budget members could each pass and alloc_pages would then throw in the middle of the flush with the
+                // queue half consumed
                 auto extra = [&](const PendingAdd& pa) {
-                    const int want = (std::max(pa.L + pa.n_iter - 1, Lp) + KV_PAGE - 1) / KV_PAGE;
-                    return std::max(0, want - (int)seq_pages_[pa.slot].size());
+                    const int want = (std::max(pa.end(), pa.start + Lp) + KV_PAGE - 1) / KV_PAGE;
+                    return std::max(0, want - (int)member_pages(pa).size());
                 };
+                const bool create = sess_queue_[i].create;
                 int need_sum = extra(sess_queue_[i]);
-                while (i + S < sess_queue_.size() && S < fit && sess_queue_[i + S].L - 1 >= 1) {
+                while (i + S < sess_queue_.size() && S < fit && sess_queue_[i + S].rows() >= 1 && sess_queue_[i + S].create == create &&
+                       sess_queue_[i + S].start + Lp <= a_.max_seq_len) {
                     const int need = extra(sess_queue_[i + S]);
                     if (need_sum + need > (int)free_pages_.size()) break;
                     need_sum += need;
@@ -1103,19 +1215,23 @@ class LM final : public LMBase {
                 }
                 if (need_sum > (int)free_pages_.size()) S = 1;  // (the first member alone does not fit a group pass either: its own pages were reserved by session_add)
             }
+            launch_tail_copies(sess_queue_.begin() + i, sess_queue_.begin() + i + S);
             if (S == 1 || !flash) {  // one sequence, passes of <= kRowsCap rows
                 const PendingAdd& pa = sess_queue_[i];
-                const auto& pg = seq_pages_[pa.slot];
+                const auto& pg = member_pages(pa);
+                if (!pa.create) require_private(pa.slot, pa.start);
                 FS_HIP(hipMemcpyAsync(d_page_table_.as<int>() + (size_t)B_ * max_pages_, pg.data(), sizeof(int) * pg.size(), hipMemcpyHostToDevice, st_pf_));
-                if (d2_prompt_.n < sizeof(uint32_t) * (size_t)C1 * pa.L) d2_prompt_.alloc(sizeof(uint32_t) * (size_t)C1 * pa.L);
-                FS_HIP(hipMemcpyAsync(d2_prompt_.p, pa.prompt.data(), sizeof(uint32_t) * (size_t)C1 * pa.L, hipMemcpyHostToDevice, st_pf_));
+                const int cols = pa.cols();
+                if (d2_prompt_.n < sizeof(uint32_t) * (size_t)C1 * cols) d2_prompt_.alloc(sizeof(uint32_t) * (size_t)C1 * cols);
+                FS_HIP(hipMemcpyAsync(d2_prompt_.p, pa.prompt.data(), sizeof(uint32_t) * (size_t)C1 * cols, hipMemcpyHostToDevice, st_pf_));
                 sess_stage_ = SeqState{};
-                sess_stage_.prompt_L = pa.L;
+                sess_stage_.prompt_L = cols;
+                sess_stage_.pos = pa.start;  // (a prefixed member: its body's first column sits at position P)
                 FS_HIP(hipMemcpyAsync(state(B_), &sess_stage_, sizeof(SeqState), hipMemcpyHostToDevice, st_pf_));
                 RowsCtx c = rows_ctx2(state(B_), /*pos_step=*/1, /*pt_stride=*/0);
                 for (int done = 0; done < Lp;) {
                     const int M = std::min(flash ? kRowsCap : kPartRows, Lp - done);
-                    c.nc_launch = chunk_bucket(done + M);
+                    c.nc_launch = chunk_bucket(pa.start + done + M);
                     LmKernels<WT>::prefill_embed(d_, tok_emb_, cb_emb_, C, a_.codebook_size, d_cfg_.as<SampleCfg>(),
                                                  d2_prompt_.as<uint32_t>(), state(B_), M, d2_pfx_.as<float>(), st_pf_);
                     for (int l = 0; l < a_.n_layer; ++l) LmKernels<WT>::rows_layer(d_, M, c, slow_[l], slow_kv(l, B_), l == 0, st_pf_);
@@ -1127,15 +1243,26 @@ class LM final : public LMBase {
                 const size_t pstride = (size_t)C1 * Lp;
                 std::vector<uint32_t>& padded = sess_stage_prompts_;  // (members: alive until the pass has been activated)
                 std::vector<int>& rows = sess_stage_rows_;
+                std::vector<SeqState>& pos0 = sess_stage_pos0_;
                 padded.assign(pstride * S, 0u);
                 rows.assign((size_t)S * max_pages_, sess_scratch_);
+                pos0.assign(S, SeqState{});
+                int max_start = 0;
                 for (int s = 0; s < S; ++s) {
-                    const PendingAdd& pa = sess_queue_[i + s];
-                    alloc_pages(pa.slot, std::max(pa.L + pa.n_iter - 1, Lp));
-                    const int n = pa.L - 1;
-                    for (int r = 0; r < C1; ++r) std::memcpy(&padded[pstride * s + (size_t)r * Lp], &pa.prompt[(size_t)r * pa.L], sizeof(uint32_t) * n);
-                    const auto& pg = seq_pages_[pa.slot];
+                    PendingAdd& pa = sess_queue_[i + s];
+                    if (pa.create) {
+                        auto& pp = sess_prefixes_[pa.prefix].pages;
+                        while ((int)pp.size() * KV_PAGE < std::max(pa.L, Lp)) pp.push_back(take_page());  // (pad rows; trimmed at activation)
+                    } else {
+                        alloc_pages(pa.slot, std::max(pa.end(), pa.start + Lp));
+                        require_private(pa.slot, pa.start);
+                    }
+                    const int n = pa.rows(), cols = pa.cols();
+                    for (int r = 0; r < C1; ++r) std::memcpy(&padded[pstride * s + (size_t)r * Lp], &pa.prompt[(size_t)r * cols], sizeof(uint32_t) * n);
+                    const auto& pg = member_pages(pa);
                     std::copy(pg.begin(), pg.end(), rows.begin() + (size_t)s * max_pages_);
+                    pos0[s].pos = pa.start;
+                    max_start = std::max(max_start, pa.start);
                 }
                 if (d2_prompt_.n < sizeof(uint32_t) * padded.size()) d2_prompt_.alloc(sizeof(uint32_t) * padded.size());
                 FS_HIP(hipMemcpyAsync(d2_prompt_.p, padded.data(), sizeof(uint32_t) * padded.size(), hipMemcpyHostToDevice, st_pf_));
@@ -1145,17 +1272,46 @@ class LM final : public LMBase {
                 FS_HIP(hipMemcpyAsync(state(B_), &sess_stage_, sizeof(SeqState), hipMemcpyHostToDevice, st_pf_));
                 RowsCtx c = rows_ctx2(state(B_), /*pos_step=*/1, /*pt_stride=*/max_pages_);
                 c.seq_rows = Lp;
-                c.nc_launch = chunk_bucket(Lp);
+                c.nc_launch = chunk_bucket(max_start + Lp);
+                if (max_start > 0) {  // (members that all start at 0 keep the plain group pass)
+                    FS_HIP(hipMemcpyAsync(d2_seqpos_.p, pos0.data(), sizeof(SeqState) * S, hipMemcpyHostToDevice, st_pf_));
+                    c.seq_states = d2_seqpos_.as<SeqState>();
+                }
                 const int M = S * Lp;
                 LmKernels<WT>::prefill_embed(d_, tok_emb_, cb_emb_, C, a_.codebook_size, d_cfg_.as<SampleCfg>(), d2_prompt_.as<uint32_t>(), state(B_), M,
                                              d2_pfx_.as<float>(), st_pf_, Lp, pstride);
                 for (int l = 0; l < a_.n_layer; ++l) LmKernels<WT>::rows_layer(d_, M, c, slow_[l], slow_kv(l, B_), l == 0, st_pf_);
             }
         }
+        ++sess_count_[0];
+        for (int s = 0; s < S; ++s) { sess_count_[1] += sess_queue_[i + s].rows(); sess_count_[2] += sess_queue_[i + s].create ? 0 : sess_queue_[i + s].start; }
+        FS_HIP(hipEventRecord(ev_pft_[1], st_pf_));
         FS_HIP(hipEventRecord(ev_pf_, st_pf_));
         sess_flight_.assign(std::make_move_iterator(sess_queue_.begin()), std::make_move_iterator(sess_queue_.begin() + S));
         sess_queue_.erase(sess_queue_.begin(), sess_queue_.begin() + S);
     }
+    // copy-on-write of the partly filled last page of a prefix into the joining slot's first private page, for all members of a pass
+    // that need it: ONE k_kv_page_copy launch over every slow layer's K and V pools, on the prefill stream ahead of the pass
+    template <typename It>
+    void launch_tail_copies(It first, It last) {
+        std::vector<int>& pairs = sess_stage_copy_;  // (alive until the pass has been activated)
+        pairs.clear();
+        for (It it = first; it != last; ++it)
+            if (!it->create && it->tail >= 0) {
+                const int dst = seq_pages_[it->slot][it->start / KV_PAGE];
+                FS_REQUIRE(page_refs_[dst] == 1, "a session slot would write a shared KV page");
+                pairs.push_back(it->tail);
+                pairs.push_back(dst);
+            }
+        if (pairs.empty()) return;
+        const int n = (int)pairs.size() / 2;
+        FS_REQUIRE(n <= B_, "more tail copies than slots");
+        FS_HIP(hipMemcpyAsync(d2_copy_.p, pairs.data(), sizeof(int) * pairs.size(), hipMemcpyHostToDevice, st_pf_));
+        const size_t page_bytes = page_elems_ * sizeof(KT);
+        launch_kv_page_copy(kv_pool_.p, 2 * a_.n_layer, (size_t)n_pages_ * page_bytes, page_bytes, d2_copy_.as<int>(), n, st_pf_);
+        sess_count_[3] += n;
+    }
+    const std::vector<int>& member_pages(const PendingAdd& pa) const { return pa.create ? sess_prefixes_[pa.prefix].pages : seq_pages_[pa.slot]; }
     // the requests whose prefill is in flight (if it has finished, or after waiting for it) become live slots; called between steps only
     void activate_pending(bool wait) {
         if (sess_flight_.empty()) return;
@@ -1165,15 +1321,31 @@ class LM final : public LMBase {
             FS_HIP(q);
         }
         FS_HIP(hipEventSynchronize(ev_pf_));
+        if (sess_timed_) {
+            float ms = 0.f;
+            FS_HIP(hipEventElapsedTime(&ms, ev_pft_[0], ev_pft_[1]));
+            sess_pf_ms_ += ms;
+            sess_timed_ = false;
+        }
         const int C1 = a_.num_codebooks + 1;
         for (const PendingAdd& pa : sess_flight_) {
-            const int b = pa.slot, L = pa.L, Lp = L - 1;
+            if (pa.create) {  // the prefix's K/V are in place: its pad pages go back; a prefix released meanwhile goes now
+                SessPrefix& px = sess_prefixes_[pa.prefix];
+                px.pending = false;
+                const size_t keep = (size_t)((px.P + KV_PAGE - 1) / KV_PAGE);
+                while (px.pages.size() > keep) { put_page(px.pages.back()); px.pages.pop_back(); }
+                if (!px.live) drop_prefix_pages(px);
+                continue;
+            }
+            if (pa.tail >= 0) put_page(pa.tail);  // (copied: the joining slot's hold on the prefix's last page ends)
+            const int b = pa.slot, L = pa.L, Lp = L - 1, cols = pa.cols();
+            require_private(b, Lp);
             const auto& pg = seq_pages_[b];
             FS_HIP(hipMemcpyAsync(d_page_table_.as<int>() + (size_t)b * max_pages_, pg.data(), sizeof(int) * pg.size(), hipMemcpyHostToDevice, st_));
             seq_len_[b] = Lp;
             SeqState ss = {};
             ss.pos = Lp; ss.prompt_L = L; ss.step = Lp;
-            for (int r = 0; r < C1; ++r) ss.cur[r] = pa.prompt[(size_t)r * L + (L - 1)];
+            for (int r = 0; r < C1; ++r) ss.cur[r] = pa.prompt[(size_t)r * cols + (cols - 1)];
             sess_hs_[b] = ss;
             FS_HIP(hipMemcpyAsync(state(b), &sess_hs_[b], sizeof(SeqState), hipMemcpyHostToDevice, st_));
             if (sess_rows_) {  // the slot becomes a live row: first-frame input, iteration budget, fresh repetition-penalty window and sampler stream
@@ -1199,12 +1371,15 @@ class LM final : public LMBase {
         const int need = (n_tokens + KV_PAGE - 1) / KV_PAGE;
         auto& pg = seq_pages_[b];
         FS_REQUIRE((int)free_pages_.size() >= need - (int)pg.size(), "KV page pool exhausted");
-        while ((int)pg.size() < need) { pg.push_back(free_pages_.back()); free_pages_.pop_back(); }
+        while ((int)pg.size() < need) pg.push_back(take_page());
     }
     void ensure_prefill2_buffers() {
         if (d2_pfx_.p) return;
         FS_HIP(hipStreamCreateWithFlags(&st_pf_, hipStreamNonBlocking));
         FS_HIP(hipEventCreateWithFlags(&ev_pf_, hipEventDisableTiming));
+        for (hipEvent_t& e : ev_pft_) FS_HIP(hipEventCreate(&e));  // (timed: fs_lm_session_info's prefill-stream time)
+        d2_seqpos_.alloc(sizeof(SeqState) * (size_t)B_);
+        d2_copy_.alloc(sizeof(int) * 2 * (size_t)B_);
         d2_pfx_.alloc(d_pfx_.n); d2_pfq_.alloc(d_pfq_.n); d2_pfslab_.alloc(d_pfslab_.n); d2_pfa_.alloc(d_pfa_.n); d2_pfa2_.alloc(d_pfa2_.n);
         d2_pfss_.alloc(d_pfss_.n); d2_pfc_.alloc(d_pfc_.n); d2_pfpart_.alloc(d_pfpart_.n);
         for (DevBuf* bf : {&d2_pfx_, &d2_pfa_, &d2_pfa2_, &d2_pfss_, &d2_pfc_, &d2_pfpart_}) FS_HIP(hipMemsetAsync(bf->p, 0, bf->n, st_pf_));
@@ -1320,9 +1495,13 @@ class LM final : public LMBase {
         if (!sess_active_) return;
         use_device();
         if (!sess_flight_.empty()) (void)hipEventSynchronize(ev_pf_);
+        for (auto* q : {&sess_flight_, &sess_queue_})
+            for (const PendingAdd& pa : *q) if (pa.tail >= 0) put_page(pa.tail);
         sess_flight_.clear(); sess_queue_.clear();
         for (int b = 0; b < B_; ++b) truncate(b, 0);
-        free_pages_.push_back(sess_scratch_);
+        for (SessPrefix& px : sess_prefixes_) drop_prefix_pages(px);  // (live or not: the session's references end with it)
+        sess_prefixes_.clear();
+        put_page(sess_scratch_);
         SampleCfg cfg = base_cfg();
         FS_HIP(hipMemcpyAsync(d_cfg_.p, &cfg, sizeof(cfg), hipMemcpyHostToDevice, st_));
         FS_HIP(hipStreamSynchronize(st_));
@@ -1738,6 +1917,7 @@ class LM final : public LMBase {
         d_page_table_.alloc(sizeof(int) * (size_t)std::max(2 * B_ + 1, PR_MAX_ROWS) * max_pages_);  // + the staging rows of a session's joining requests (one group pass)
         FS_HIP(hipMemset(d_page_table_.p, 0, d_page_table_.n));
         for (int p = n_pages_ - 1; p >= 0; --p) free_pages_.push_back(p);
+        page_refs_.assign(n_pages_, 0);
         seq_pages_.assign(B_, {});
         seq_len_.assign(B_, 0);
         fast_len_.assign(B_, 0);
@@ -1839,8 +2019,7 @@ class LM final : public LMBase {
         if ((int)pg.size() >= need) return;
         while ((int)pg.size() < need) {
             FS_REQUIRE(!free_pages_.empty(), "KV page pool exhausted");
-            pg.push_back(free_pages_.back());
-            free_pages_.pop_back();
+            pg.push_back(take_page());
         }
         FS_HIP(hipMemcpyAsync(d_page_table_.as<int>() + (size_t)b * max_pages_, pg.data(), sizeof(int) * pg.size(),
                               hipMemcpyHostToDevice, st_));
@@ -1849,8 +2028,27 @@ class LM final : public LMBase {
     void truncate(int b, int pos) {  // keep the first `pos` tokens (dual_ar.rs:392-404)
         const int keep = (pos + KV_PAGE - 1) / KV_PAGE;
         auto& pg = seq_pages_[b];
-        while ((int)pg.size() > keep) { free_pages_.push_back(pg.back()); pg.pop_back(); }
+        while ((int)pg.size() > keep) { put_page(pg.back()); pg.pop_back(); }
         seq_len_[b] = pos;
+    }
+    // pages are reference counted (a session's shared prefix pages have the prefix + every slot on it as owners); a page goes back to the
+    // free list when its last owner drops it.  Outside sessions every page has one owner and this is the plain free list.
+    int take_page() {
+        const int p = free_pages_.back();
+        free_pages_.pop_back();
+        page_refs_[p] = 1;
+        return p;
+    }
+    void put_page(int p) {
+        FS_REQUIRE(page_refs_[p] > 0, "KV page released twice");
+        if (--page_refs_[p] == 0) free_pages_.push_back(p);
+    }
+    // the ownership invariant: nothing writes a page with more than one owner.  Slot b writes positions >= pos0 (its prefill starts there,
+    // its pad rows and decode steps lie beyond), so every page from pos0's on must be the slot's alone.
+    void require_private(int b, int pos0) {
+        const auto& pg = seq_pages_[b];
+        for (size_t j = (size_t)(pos0 / KV_PAGE); j < pg.size(); ++j)
+            FS_REQUIRE(page_refs_[pg[j]] == 1, "a session slot would write a shared KV page");
     }
 
     // Runs the next `n` prompt tokens (columns state->step ..) of the staged prompt through the slow transformer,
@@ -2420,7 +2618,15 @@ class LM final : public LMBase {
     std::vector<SeqState> sess_hs_;
     int sess_scratch_ = 0;
     uint64_t sess_released_frames_ = 0;
-    struct PendingAdd { int slot = -1, L = 0, n_iter = 0, order = 0; std::vector<uint32_t> prompt; };
+    std::vector<SessPrefix> sess_prefixes_;
+    std::vector<int> page_refs_;                       // owners of every slow KV page (0: on the free list)
+    std::vector<SeqState> sess_stage_pos0_;            // a group pass's member start positions (pos; rope_off 0)
+    std::vector<int> sess_stage_copy_;
+    DevBuf d2_seqpos_, d2_copy_;                       // device copies of the two above: member start states / tail-copy page pairs
+    hipEvent_t ev_pft_[2] = {nullptr, nullptr};        // timing events around each prefill-stream pass (fs_lm_session_info)
+    bool sess_timed_ = false;
+    int64_t sess_count_[4] = {0, 0, 0, 0};             // passes, tokens prefilled, prefix tokens reused, tail pages copied
+    double sess_pf_ms_ = 0.0;
     std::vector<uint32_t> sess_stage_prompts_;
     std::vector<int> sess_stage_rows_;
     std::vector<PendingAdd> sess_queue_, sess_flight_;  // joining requests: queued by session_add / prefill launched (flush_pending)

@@ -91,6 +91,7 @@ struct RowsCtx {
     int pos_step;        // 1: rows = consecutive tokens of one sequence (prefill); 0: rows = sequences (batched decode)
     int pt_stride;       // page-table stride between rows (0 for prefill) / between sequences (group prefill)
     int seq_rows = 0;    // > 0: group prefill -- rows = seq_rows consecutive tokens of each of M / seq_rows sequences, all starting at state->pos
+    const SeqState* seq_states = nullptr;  // group prefill, device [M / seq_rows]: sequence s starts at seq_states[s].pos (null: all at state->pos)
     bool no_flash = false;       // micro-benchmark / test hook: keep the chunked row attention for prefill passes
     bool chunked_attn = false;   // micro-benchmark / test hook: keep k_attn_decode + k_attn_combine for rows-are-sequences passes
     bool small_attn = false;     // every row attends over <= 8 tokens of ONE page (fast decoder): fused attention node
@@ -238,6 +239,8 @@ void launch_cap_rows_logits(const float* logits, int ld, int n, const SeqState* 
                             hipStream_t st);
 void launch_cap_rows_picks(const SeqState* states, const SampleCfg* cfg, int B, float* cap, int cap_frames, int n_cb, hipStream_t st);  // pos += n, step += n (chunked prefill)
 void launch_reppen_reset(RepPenState rp, int n_cb, int cb_size, hipStream_t st);
+// copy KV page pairs[2i] -> pairs[2i + 1] (device int array) in each of n_regions pool regions region_bytes apart: ONE launch
+void launch_kv_page_copy(void* pool, int n_regions, size_t region_bytes, size_t page_bytes, const int* pairs, int n_pairs, hipStream_t st);
 
 // synthetic tensor fill (fs_synth.h): n_rows x n_cols, destination row = r * row_mul + row_off (W1/W3 interleave)
 template <typename WT>

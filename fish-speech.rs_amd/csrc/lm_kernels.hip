@@ -787,7 +787,10 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 constexpr int PF_M = 32;    // activation rows per pass
 
-enum { EPI_STORE = 0, EPI_RESIDUAL = 1, EPI_SWIGLU = 2, EPI_QKV = 3, EPI_RESIDUAL_NORM = 4, EPI_SWIGLU_RMS = 5, EPI_QKV_RMS = 6, EPI_STORE_RMS = 7 };
+// EPI_QKV_SEQ: EPI_QKV for a group prefill pass whose sequences start at different positions -- sequence s of the pass sits at
+// state[s].pos (+ state[s].rope_off); its own instantiation, so that the other QKV GEMMs compile exactly as without it
+enum { EPI_STORE = 0, EPI_RESIDUAL = 1, EPI_SWIGLU = 2, EPI_QKV = 3, EPI_RESIDUAL_NORM = 4, EPI_SWIGLU_RMS = 5, EPI_QKV_RMS = 6, EPI_STORE_RMS = 7,
+       EPI_QKV_SEQ = 8 };
 // epilogues that divide the K-summed accumulators by the row's rms (the producer left split(x * g) and sum-of-squares partials: NormAux)
 __host__ __device__ constexpr bool epi_rms(int e) { return e == EPI_SWIGLU_RMS || e == EPI_QKV_RMS || e == EPI_STORE_RMS; }
 // RMSNorm folded into the GEMMs around it (saves the k_prep node between Wo and W13): the Wo GEMM's epilogue writes the new
@@ -963,6 +966,7 @@ __device__ __forceinline__ void gemm_epilogue(float a, float b, int r, int m, in
         const int sq = rm.seq_rows > 0 ? m / rm.seq_rows : m;  // sequence of row m / its token index within the pass
         int pos = pos0 + (rm.seq_rows > 0 ? m - sq * rm.seq_rows : m * rm.pos_step), rpos = pos + rope_off;
         if (rm.pos_step < 0) { pos = g.states[m].pos; rpos = pos + g.states[m].rope_off; }
+        if (EPI == EPI_QKV_SEQ) { pos = g.states[sq].pos + (m - sq * rm.seq_rows); rpos = pos + g.states[sq].rope_off; }
         const int* ptab = kv.page_table + (size_t)sq * rm.pt_stride;
         const int qdim = H * Dh, kdim = Hk * Dh, half = Dh / 2;
         if (r < qdim + kdim) {
@@ -1031,7 +1035,7 @@ __global__ __launch_bounds__(256) void k_gemm3(const bf16_t* __restrict__ Xf, in
     int pos0 = 0, rope_off = 0;
     if (EPI == EPI_QKV || EPI == EPI_QKV_RMS) { pos0 = state->pos; rope_off = state->rope_off; }  // requested up front: the epilogue must not start a dependent chain
     const GemmEpi ge{Y, ldy, slab_stride, Of, ldo, cos_t, sin_t, kv, H, Hk, Dh, rm, na, pos0, rope_off, N, state,
-                     (EPI == EPI_QKV || EPI == EPI_QKV_RMS) ? Of : nullptr};  // (Of of a QKV launch: GemmEpi::o1)
+                     (EPI == EPI_QKV || EPI == EPI_QKV_RMS || EPI == EPI_QKV_SEQ) ? Of : nullptr};  // (Of of a QKV launch: GemmEpi::o1)
     u32x4 wf[RT][NKS];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
@@ -1780,9 +1784,11 @@ __global__ __launch_bounds__((AttnGeom<WT, DH>::NW * 64)) void k_attn_rows(const
 //                                                      wave's private LDS copy of the tile (token-major -> 4 strided bf16)
 // The softmax scale 2^-3 is folded into q (exact).  Rows >= M and tokens past a row's position are masked.
 typedef short short4v __attribute__((ext_vector_type(4)));
-// blockIdx.y = sequence of a group pass (rows [y * M, (y + 1) * M), page table y * pt_stride further on); one sequence: gridDim.y = 1.
+// blockIdx.y = sequence of a group pass (rows [y * M, (y + 1) * M), page table y * pt_stride further on, first position state->pos +
+// seq_states[y].pos when seq_states is set: members that join on a shared prefix start past it); one sequence: gridDim.y = 1.
 __global__ __launch_bounds__(256) void k_attn_prefill_mfma(const float* __restrict__ q_all, KVView kv, const SeqState* __restrict__ state,
-                                                           int M, int H, int Hk, bf16_t* __restrict__ Ohi, int pt_stride) {
+                                                           int M, int H, int Hk, bf16_t* __restrict__ Ohi, int pt_stride,
+                                                           const SeqState* __restrict__ seq_states) {
     constexpr int DH = 64, VLD = DH + 8;
     __shared__ __attribute__((aligned(16))) bf16_t vt[4][KV_PAGE * VLD];
     __shared__ __attribute__((aligned(16))) float sm_o[4][16][DH + 4];
@@ -1790,7 +1796,7 @@ __global__ __launch_bounds__(256) void k_attn_prefill_mfma(const float* __restri
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int h = blockIdx.x % H, rt = blockIdx.x / H;  // query head, row tile
     const int g = h / (H / Hk);
-    const int row0 = rt * 16, pos0 = state->pos;        // row m of this sequence sits at position pos0 + m
+    const int row0 = rt * 16, pos0 = seq_states ? seq_states[blockIdx.y].pos : state->pos;  // row m of this sequence sits at position pos0 + m
     const int mbase = (int)blockIdx.y * M;              // first activation row of this sequence
     const int* ptab = kv.page_table + (size_t)blockIdx.y * pt_stride;
     const int c16 = lane & 15, q4 = lane >> 4;
@@ -3532,6 +3538,9 @@ void LmKernels<WT>::rows_layer(const ModelDims& d, int M, const RowsCtx& c, cons
         else if (fold && !first)
             launch_gemm3<EPI_QKV_RMS>(qkv_rows, 1, rt_qkv, st, c.A, M, d.dim, w.wqkv, w.s_qkv, c.Q, d.dim, 0, o1, 0,
                                       c.cos_t, c.sin_t, c.state, kv, d.H, d.Hk, d.Dh, rm, NormAux{nullptr, c.ss, nullptr, nblk_d, d.dim, d.eps});
+        else if ((c.stage_mask & 2u) && c.seq_rows > 0 && c.seq_states)
+            launch_gemm3<EPI_QKV_SEQ>(qkv_rows, 1, rt_qkv, st, c.A, M, d.dim, w.wqkv, w.s_qkv, c.Q, d.dim, 0, o1, 0,
+                                      c.cos_t, c.sin_t, c.seq_states, kv, d.H, d.Hk, d.Dh, rm);
         else if (c.stage_mask & 2u) launch_gemm3<EPI_QKV>(qkv_rows, 1, rt_qkv, st, c.A, M, d.dim, w.wqkv, w.s_qkv, c.Q, d.dim, 0, o1, 0,
                               c.cos_t, c.sin_t, c.state, kv, d.H, d.Hk, d.Dh, rm);
         // (3) attention over each row's KV prefix + chunk combine -> hi/lo
@@ -3540,14 +3549,15 @@ void LmKernels<WT>::rows_layer(const ModelDims& d, int M, const RowsCtx& c, cons
             hipLaunchKernelGGL((k_attn_small_rows_tbl<64>), dim3(M), dim3(256), 0, st, c.qkv0_tbl, c.row_states, c.code_slot, kv, c.state, d.H, d.Hk, c.pos_step,
                                c.pt_stride, c.cos_t, c.sin_t, c.A, (int)c.identity_pages);
         else if (c.seq_rows > 0) {
-            // group prefill: M = n_seq * seq_rows rows, every sequence starts at state->pos; flash attention per sequence
+            // group prefill: M = n_seq * seq_rows rows, sequence s starts at state->pos (or c.seq_states[s].pos); flash attention per sequence
             FS_REQUIRE(d.Dh == 64 && M % c.seq_rows == 0 && !c.no_flash, "group prefill needs head_dim 64 and whole sequences");
             if (c.stage_mask & 4u)
                 hipLaunchKernelGGL(k_attn_prefill_mfma, dim3(d.H * ((c.seq_rows + 15) / 16), M / c.seq_rows), dim3(256), 0, st, c.Q, kv, c.state,
-                                   c.seq_rows, d.H, d.Hk, c.A, c.pt_stride);
+                                   c.seq_rows, d.H, d.Hk, c.A, c.pt_stride, c.seq_states);
         } else if (c.pos_step == 1 && c.pt_stride == 0 && (c.stage_mask & 4u) && d.Dh == 64 && M > 1 && !c.no_flash) {
             // prefill: causal flash attention on the matrix cores, result straight into the Wo GEMM's input
-            hipLaunchKernelGGL(k_attn_prefill_mfma, dim3(d.H * ((M + 15) / 16)), dim3(256), 0, st, c.Q, kv, c.state, M, d.H, d.Hk, c.A, 0);
+            hipLaunchKernelGGL(k_attn_prefill_mfma, dim3(d.H * ((M + 15) / 16)), dim3(256), 0, st, c.Q, kv, c.state, M, d.H, d.Hk, c.A, 0,
+                               (const SeqState*)nullptr);
         } else if (c.small_attn && (c.stage_mask & 4u) && d.H <= 32 && (d.Dh == 64 || d.Dh == 32)) {
             // fast decoder: <= 8 tokens in one page -> one node instead of two
             if (d.Dh == 64)
@@ -3678,6 +3688,24 @@ void launch_cap_rows_picks(const SeqState* states, const SampleCfg* cfg, int B, 
 
 void launch_advance_n(SeqState* state, int n, hipStream_t st) {
     hipLaunchKernelGGL(k_advance_n, dim3(1), dim3(1), 0, st, state, n);
+    FS_LAUNCH_CHECK();
+}
+
+// Copy-on-write of shared KV pages: page pairs[2i] -> page pairs[2i + 1] in every one of the n_regions regions of the pool (the K and
+// the V pages of every slow layer: region r starts r * region_bytes in).  Block = (pair, region); 16-byte vector loads and stores.
+__global__ __launch_bounds__(256) void k_kv_page_copy(uint8_t* __restrict__ pool, size_t region_bytes, size_t page_bytes,
+                                                      const int* __restrict__ pairs) {
+    const int src = pairs[2 * blockIdx.x], dst = pairs[2 * blockIdx.x + 1];
+    uint8_t* const base = pool + (size_t)blockIdx.y * region_bytes;
+    const uint4* s = reinterpret_cast<const uint4*>(base + (size_t)src * page_bytes);
+    uint4* d = reinterpret_cast<uint4*>(base + (size_t)dst * page_bytes);
+    const size_t n16 = page_bytes / 16;
+    for (size_t i = threadIdx.x; i < n16; i += blockDim.x) d[i] = s[i];
+}
+void launch_kv_page_copy(void* pool, int n_regions, size_t region_bytes, size_t page_bytes, const int* pairs, int n_pairs, hipStream_t st) {
+    if (n_pairs <= 0) return;
+    FS_REQUIRE(page_bytes % 16 == 0 && region_bytes % 16 == 0, "KV pages must be whole 16-byte units");
+    hipLaunchKernelGGL(k_kv_page_copy, dim3(n_pairs, n_regions), dim3(256), 0, st, reinterpret_cast<uint8_t*>(pool), region_bytes, page_bytes, pairs);
     FS_LAUNCH_CHECK();
 }
 

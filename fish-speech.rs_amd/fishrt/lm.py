@@ -283,14 +283,45 @@ class Session:
             self._open = False
             _ffi.check(_ffi.lib().fs_lm_session_end(self.lm._h))
 
-    def add(self, prompt, max_new_tokens):
+    def _prompt(self, prompt, what="prompt"):
         p = _u32(prompt)
         if p.ndim != 2 or p.shape[0] != self.lm.cfg["num_codebooks"] + 1 or p.shape[1] < 1:  # the C side reads (C + 1) * L words
-            raise ValueError(f"prompt must be u32 [{self.lm.cfg['num_codebooks'] + 1}, L >= 1], got {p.shape}")
+            raise ValueError(f"{what} must be u32 [{self.lm.cfg['num_codebooks'] + 1}, L >= 1], got {p.shape}")
+        return p
+
+    def add(self, prompt, max_new_tokens, prefix=None):
+        """prefix (an add_prefix id): `prompt` is the request's BODY -- the slot generates what add(concat(prefix prompt, body)) would,
+        reading the prefix's K/V from its shared pages and prefilling the body only"""
+        p = self._prompt(prompt, "prompt" if prefix is None else "body")
         slot = C.c_int(-1)
-        _ffi.check(_ffi.lib().fs_lm_session_add(self.lm._h, p.ctypes.data_as(C.POINTER(C.c_uint32)), int(p.shape[1]), int(max_new_tokens),
-                                                C.byref(slot)))
+        if prefix is None:
+            _ffi.check(_ffi.lib().fs_lm_session_add(self.lm._h, p.ctypes.data_as(C.POINTER(C.c_uint32)), int(p.shape[1]), int(max_new_tokens),
+                                                    C.byref(slot)))
+        else:
+            _ffi.check(_ffi.lib().fs_lm_session_add_prefixed(self.lm._h, int(prefix), p.ctypes.data_as(C.POINTER(C.c_uint32)), int(p.shape[1]),
+                                                             int(max_new_tokens), C.byref(slot)))
         return None if slot.value < 0 else int(slot.value)
+
+    def add_prefix(self, prompt):
+        """prefill a conditioning prefix (system text + voice prompt) once into pages of this session -> prefix id, or None when the KV
+        page pool cannot hold it right now.  Slots admitted with add(body, ..., prefix=id) share its pages."""
+        p = self._prompt(prompt, "prefix")
+        pid = C.c_int(-1)
+        _ffi.check(_ffi.lib().fs_lm_session_prefix_create(self.lm._h, p.ctypes.data_as(C.POINTER(C.c_uint32)), int(p.shape[1]), C.byref(pid)))
+        return None if pid.value < 0 else int(pid.value)
+
+    def release_prefix(self, prefix):
+        """drop the session's reference; the pages go back once no slot uses them any more"""
+        _ffi.check(_ffi.lib().fs_lm_session_prefix_release(self.lm._h, int(prefix)))
+
+    INFO_KEYS = ("free_pages", "shared_pages", "live_prefixes", "prefill_passes", "tokens_prefilled", "prefix_tokens_reused",
+                 "tail_pages_copied", "prefill_us")
+
+    def info(self):
+        """KV page pool and prefill counters of this session (fs_lm_session_info)"""
+        out = (C.c_int64 * 8)()
+        _ffi.check(_ffi.lib().fs_lm_session_info(self.lm._h, out))
+        return dict(zip(self.INFO_KEYS, (int(v) for v in out)))
 
     def step(self, n_frames=8):
         act = C.c_int(0)

@@ -23,6 +23,7 @@ several jobs are in flight (or a request asks for `batch_size`) on a `max_batch 
 A lone job takes the batch-1 path with its persistent decode kernels.  `Scheduler(continuous=False)` keeps the lock-step variant
 (jobs waiting together go through one `generate_static_batch` call).
 """
+import collections
 import hashlib
 import io
 import json
@@ -100,10 +101,12 @@ class LMState:  # server/lib/state.rs:12-21
 
 class AppState:  # server/lib/state.rs:23-29
     def __init__(self, lm_state, codec, sample_rate=44100, opus_encoder=None, preprocess=preprocess_text, batch_window_s=0.002,
-                 continuous=True, auto_batch=False):
+                 continuous=True, auto_batch=False, session_prefixes=False):
         self.lm, self.codec, self.sample_rate, self.opus_encoder, self.preprocess = lm_state, codec, sample_rate, opus_encoder, preprocess
         self.auto_batch = auto_batch  # True: every chunk may join the batching session (batch sampling semantics) without `batch_size`
-        self.scheduler = Scheduler(lm_state, batch_window_s, continuous)
+        # session_prefixes (off by default): session jobs share their voice's conditioning prefix (Session.add_prefix) instead of prefilling
+        # it per chunk.  A prefix prefilled on its own may round differently from the full prompt and flip a near-tie, so it stays opt-in.
+        self.scheduler = Scheduler(lm_state, batch_window_s, continuous, session_prefixes=session_prefixes)
 
 
 class _Job:
@@ -121,11 +124,17 @@ _STOP = object()  # Scheduler.close() sentinel
 class Scheduler:
     """Replaces `state.lm.model.lock().await`: chunk jobs from all requests in one queue, one worker per handle."""
 
-    def __init__(self, lm_state, batch_window_s=0.002, continuous=True, step_frames=8):
+    PREFIX_LRU = 8  # conditioning prefixes kept per session (session_prefixes)
+
+    def __init__(self, lm_state, batch_window_s=0.002, continuous=True, step_frames=8, session_prefixes=False):
         self.s, self.q, self.window = lm_state, queue.Queue(), batch_window_s
         self.continuous, self.step_frames = continuous, step_frames
+        self.session_prefixes = session_prefixes
+        self.prefixes = collections.OrderedDict()  # session_prefixes: cond_key -> prefix id of the open session (LRU order)
         self.cached_key = None
         self.stats = dict(jobs=0, single=0, batched_rows=0, batches=0, prefix_hits=0, rerolls=0)
+        if session_prefixes:
+            self.stats.update(session_prefix_hits=0, session_prefix_tokens_saved=0)
         self._stop = False
         self.th = threading.Thread(target=self._run, daemon=True)
         self.th.start()
@@ -201,12 +210,14 @@ class Scheduler:
                         if sess is not None:  # idle: give the handle back (its other entry points work between bursts)
                             sess.close()
                             sess = None
+                            self.prefixes.clear()
                         held = self.q.get()
                     if held is _STOP:
                         held, stopping = None, True
                 if stopping and not live:
                     if sess is not None:
                         sess.close()
+                        self.prefixes.clear()
                     return
                 if held is not None:
                     lone = not live and self.q.empty()
@@ -215,6 +226,7 @@ class Scheduler:
                             if sess is not None:
                                 sess.close()
                                 sess = None
+                                self.prefixes.clear()
                             j, held = held, None
                             self._single(j)
                             continue
@@ -236,13 +248,17 @@ class Scheduler:
                             else:
                                 self.stats["row_sessions"] = self.stats.get("row_sessions", 0) + 1
                             self.cached_key = None
+                            self.prefixes.clear()
                         try:
-                            slot = sess.add(held.full_prompt(), self.s.max_new_tokens)
+                            slot, hit = self._session_add(sess, held)
                         except BaseException as e:  # a bad request (prompt longer than max_seq_len, ...) fails ALONE: the live slots go on
                             held.future.set_exception(e)
                             held = None
                             continue
                         if slot is not None:
+                            if hit:
+                                self.stats["session_prefix_hits"] += 1
+                                self.stats["session_prefix_tokens_saved"] += int(held.cond.shape[1])
                             live[slot] = held
                             held = None
                             self.stats["jobs"] += 1
@@ -252,6 +268,7 @@ class Scheduler:
                         if not live:  # nothing will ever free a slot / KV pages for it: the batch-1 path (or its error) instead of spinning
                             sess.close()
                             sess = None
+                            self.prefixes.clear()
                             j, held = held, None
                             self._single(j)
                             continue
@@ -286,6 +303,28 @@ class Scheduler:
                 except BaseException:
                     pass
                 sess = None
+                self.prefixes.clear()
+
+    def _session_add(self, sess, j):
+        """admit job j into the session -> (slot or None, whether it joined on an existing prefix).  session_prefixes: the job's
+        conditioning prefix is prefilled once per session (LRU of PREFIX_LRU) and the job prefills its body only; a prefix the KV pool
+        cannot hold falls back to the full prompt"""
+        if not self.session_prefixes or j.cond is None or j.cond.shape[1] < 1 or j.body.shape[1] < 1:
+            return sess.add(j.full_prompt(), self.s.max_new_tokens), False
+        pid = self.prefixes.get(j.cond_key)
+        hit = pid is not None and not getattr(j, "made_prefix", False)  # (a job retried while the slots were full created its own)
+        if pid is not None:
+            self.prefixes.move_to_end(j.cond_key)
+        else:
+            pid = sess.add_prefix(j.cond)
+            if pid is None:
+                return sess.add(j.full_prompt(), self.s.max_new_tokens), False
+            self.prefixes[j.cond_key] = pid
+            j.made_prefix = True
+            while len(self.prefixes) > self.PREFIX_LRU:  # (slots still on an evicted prefix keep its pages until they are released)
+                _, old = self.prefixes.popitem(last=False)
+                sess.release_prefix(old)
+        return sess.add(j.body, self.s.max_new_tokens, prefix=pid), hit
 
     def _codes_out(self, codes):
         if self.s.model_type != fprompt.FISH_1_5:  # speech.rs:63-68: Fish <= 1.4 codes are shifted by one

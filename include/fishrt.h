@@ -285,6 +285,23 @@ int fs_lm_session_poll(fs_lm_t* lm, int slot, uint32_t* codes_out, size_t cap, s
 /* give the slot (and its KV pages) back */
 int fs_lm_session_release(fs_lm_t* lm, int slot);
 int fs_lm_session_end(fs_lm_t* lm);
+/* Shared conditioning prefixes: the KV of a prompt prefix (system text + voice prompt) is prefilled ONCE into pages owned by the session,
+ * and any number of slots admitted with fs_lm_session_add_prefixed point their page tables at its full pages (reference counted; nothing
+ * writes a page with more than one owner) and get a private copy of its partly filled last page; only their own body is prefilled.
+ * A prefix lives until fs_lm_session_prefix_release or fs_lm_session_end, whichever comes first.
+ * Prefill prompt u32 [C+1, P] (P >= 1; all P positions get K/V) into pages owned by the session; *prefix_id >= 0, or -1 when the KV page
+ * pool cannot hold it right now (not an error, like fs_lm_session_add).  Queued on the prefill stream like an add. */
+int fs_lm_session_prefix_create(fs_lm_t* lm, const uint32_t* prompt, int P, int* prefix_id);
+/* drop the session's reference; the pages return to the pool when the last slot that uses them is released */
+int fs_lm_session_prefix_release(fs_lm_t* lm, int prefix_id);
+/* == fs_lm_session_add(lm, concat(prefix prompt, body), P + L_body, max_new_tokens, slot) in every respect (iteration count from
+ * L = P + L_body, max_seq_len rule, admission number -> rows-mode sampler seed, frame-0 rule, EOS, budget), except that only the
+ * L_body - 1 body positions are prefilled.  body u32 [C+1, L_body], L_body >= 1. */
+int fs_lm_session_add_prefixed(fs_lm_t* lm, int prefix_id, const uint32_t* body, int L_body, int max_new_tokens, int* slot);
+/* out[8] = {free pages, pages referenced by more than one owner, live prefixes, prefill passes, tokens prefilled,
+ *           prefix tokens reused, tail pages copied, prefill-stream microseconds (HIP events around each pass)};
+ * counters since fs_lm_session_begin */
+int fs_lm_session_info(fs_lm_t* lm, int64_t out[8]);
 
 /* timing of the last generate call, measured with HIP events on the handle's stream (the reference prints the
  * same quantities: single_batch.rs:233-246,291-304) */
