@@ -223,6 +223,11 @@ int fs_lm_session_add_prefixed(fs_lm_t* lm, int prefix_id, const uint32_t* body,
     FS_ARG(lm && body && slot, "null argument");
     FS_TRY(*slot = lm->impl->session_add_prefixed(prefix_id, body, L_body, max_new_tokens))
 }
+int fs_lm_session_add_ex(fs_lm_t* lm, int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling,
+                         const uint64_t* seed, int* slot) {
+    FS_ARG(lm && prompt && slot, "null argument");
+    FS_TRY(*slot = lm->impl->session_add_ex(prefix_id, prompt, L, max_new_tokens, sampling, seed))
+}
 int fs_lm_session_info(fs_lm_t* lm, int64_t out[8]) { FS_ARG(lm && out, "null argument"); FS_TRY(lm->impl->session_info(out)) }
 int fs_lm_last_stats(fs_lm_t* lm, fs_gen_stats* out) { FS_ARG(lm && out, "null argument"); FS_TRY(*out = lm->impl->last_stats()) }
 void* fs_lm_stream(fs_lm_t* lm) { return lm ? lm->impl->stream() : nullptr; }

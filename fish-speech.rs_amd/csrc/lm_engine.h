@@ -47,6 +47,9 @@ class LMBase {
     virtual void session_prefix_release(int id) = 0;
     virtual int session_add_prefixed(int id, const uint32_t* body, int L_body, int max_new_tokens) = 0;
     virtual void session_info(int64_t out[8]) = 0;
+    // fishrt.h: fs_lm_session_add_ex (prefix_id < 0: plain add; sampling / seed nullable: the session's)
+    virtual int session_add_ex(int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling,
+                               const uint64_t* seed) = 0;
     virtual void debug_capture(int n_frames) = 0;
     virtual void debug_read(float* out, int n_frames) = 0;
     virtual void debug_read_row(int row, float* out, int n_frames) = 0;

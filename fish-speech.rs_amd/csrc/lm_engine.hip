@@ -972,6 +972,15 @@ class LM final : public LMBase {
         // its own generate_blocking (repetition penalty, its own LogitsProcessor stream seeded seed + its admission number) -- instead of the
         // static-batch sampler's.  Needs max_batch <= 8, a bf16 Fish-1.5 handle and a sampler setting the in-launch decisions cover.
         sess_rows_ = false;
+        // FS_SESSION_PER_SLOT: the slots stay on the static-batch step, but its 9 sampler nodes are the per-slot ones (k_sample_*_slots):
+        // every slot decides like its own generate_blocking call, with its own settings, StdRng stream and repetition-penalty windows
+        const bool per_slot = (flags & FS_SESSION_PER_SLOT) != 0;
+        FS_REQUIRE(!(per_slot && (flags & FS_SESSION_ROWS)), "FS_SESSION_PER_SLOT and FS_SESSION_ROWS exclude each other (a row session's slots already sample per slot)");
+        if (per_slot) {
+            FS_REQUIRE(n_audio_ <= 2048 && a_.codebook_size <= 1024, "FS_SESSION_PER_SLOT needs <= 2048 slow candidates and codebooks of <= 1024 entries");
+            require_slot_sampling(s);
+        }
+        sess_slots_ = false;
         std::unique_lock<PersistLock> rows_lock;
         struct RowsGuard {  // anything thrown below leaves the handle out of row mode (the local lock releases itself)
             bool& flag; bool armed = true;
@@ -989,15 +998,35 @@ class LM final : public LMBase {
             ensure_rows(sess_R_);
             sess_rows_ = true;
             sess_sampled_ = s.temp != 0.0;
-            sess_seed_ = seed;
-            sess_adds_ = 0;
         }
+        sess_seed_ = seed;
+        sess_adds_ = 0;
         ensure_rows_capture(sess_rows_ ? sess_R_ : B_);
         SampleCfg cfg = base_cfg();
         cfg.temp = (float)s.temp; cfg.top_p = (float)s.top_p; cfg.top_p64 = s.top_p;
         cfg.top_k = (int)std::min<uint64_t>(s.top_k, 1u << 30);
-        cfg.rep_pen = sess_rows_ ? s.repetition_penalty : 1.0f; cfg.ignore_eos = (flags & FS_GEN_IGNORE_EOS) ? 1 : 0;
+        cfg.rep_pen = (sess_rows_ || per_slot) ? s.repetition_penalty : 1.0f; cfg.ignore_eos = (flags & FS_GEN_IGNORE_EOS) ? 1 : 0;
         cfg.session = sess_rows_ ? 0 : 1;
+        sess_cfg_ = cfg;
+        if (per_slot) {
+            // per-slot sampler state, allocated once per handle (the captured step graphs hold these pointers) and re-initialised for every
+            // slot at its activation, so nothing of an earlier session or occupant is ever read
+            const size_t nc = (size_t)B_ * a_.num_codebooks;
+            if (!d_scfg_.p) {
+                d_scfg_.alloc(sizeof(SampleCfg) * B_);
+                d_srng_.alloc(sizeof(SlotRng) * B_);
+                d_srp_mask_.alloc(sizeof(float) * nc * a_.codebook_size);
+                d_srp_seen_.alloc(nc * a_.codebook_size);
+                d_srp_ring_.alloc(sizeof(int) * nc * 17);
+                d_srp_meta_.alloc(sizeof(int) * nc * 2);
+            }
+            std::vector<SampleCfg> cfgs(B_, cfg);
+            FS_HIP(hipMemcpyAsync(d_scfg_.p, cfgs.data(), sizeof(SampleCfg) * B_, hipMemcpyHostToDevice, st_));
+            FS_HIP(hipMemsetAsync(d_srng_.p, 0xFF, d_srng_.n, st_));
+            FS_HIP(hipMemsetAsync(d_srp_ring_.p, 0, d_srp_ring_.n, st_));
+            for (int b = 0; b < B_; ++b) launch_reppen_reset(slot_rp(b), a_.num_codebooks, a_.codebook_size, st_);
+            FS_HIP(hipStreamSynchronize(st_));  // (cfgs is a local)
+        }
         if (sess_rows_) {
             std::vector<SampleCfg> cfgs(sess_R_, cfg);
             FS_HIP(hipMemcpyAsync(d_rcfg_.p, cfgs.data(), sizeof(SampleCfg) * sess_R_, hipMemcpyHostToDevice, st_));
@@ -1005,7 +1034,7 @@ class LM final : public LMBase {
             FS_HIP(hipMemcpyAsync(d_hid_slot_.p, &nullp, sizeof(nullp), hipMemcpyHostToDevice, st_));
             FS_HIP(hipStreamSynchronize(st_));  // (cfgs is a local)
         }
-        rows_par_ = rows_par_sampler_ok(s.temp, s.top_k, n_audio_, a_.codebook_size) && !getenv("FISHRT_ROWS_SAMPLER_1024");
+        rows_par_ = !per_slot && rows_par_sampler_ok(s.temp, s.top_k, n_audio_, a_.codebook_size) && !getenv("FISHRT_ROWS_SAMPLER_1024");
         FS_HIP(hipMemcpyAsync(d_cfg_.p, &cfg, sizeof(cfg), hipMemcpyHostToDevice, st_));
         RngState rng = {};
         seed_key(seed, rng.key);
@@ -1027,7 +1056,52 @@ class LM final : public LMBase {
         stats_ = {};
         rows_guard.armed = false;
         if (sess_rows_) sess_plock_ = std::move(rows_lock);
+        sess_slots_ = per_slot;
         sess_active_ = true;
+    }
+    // what a slot of a FS_SESSION_PER_SLOT session may sample with: the boundary of the in-launch samplers (fishrt.h: fs_lm_generate)
+    void require_slot_sampling(const fs_sampling& s) const {
+        const bool ok = s.temp == 0.0 || (s.temp > 0.0 && s.top_k > 0 && s.top_k <= 256);
+        if (!ok) throw Error("FS_SESSION_PER_SLOT: a slot samples greedy (temp == 0) or with temp > 0 and 0 < top_k <= 256 (the in-launch samplers' limit)");
+    }
+    SampleCfg slot_cfg(const fs_sampling& s) const {  // the session's SampleCfg with one request's settings
+        SampleCfg c = sess_cfg_;
+        c.temp = (float)s.temp; c.top_p = (float)s.top_p; c.top_p64 = s.top_p;
+        c.top_k = (int)std::min<uint64_t>(s.top_k, 1u << 30);
+        c.rep_pen = s.repetition_penalty;
+        return c;
+    }
+    RepPenState slot_rp(int b) {
+        const size_t nc = (size_t)b * a_.num_codebooks;
+        RepPenState rp;
+        rp.mask = d_srp_mask_.as<float>() + nc * a_.codebook_size; rp.seen = d_srp_seen_.as<uint8_t>() + nc * a_.codebook_size;
+        rp.ring = d_srp_ring_.as<int>() + nc * 17; rp.ring_meta = d_srp_meta_.as<int>() + nc * 2;
+        return rp;
+    }
+    // fs_lm_session_add_ex: an add (plain, or on a prefix) whose slot samples with its own settings and / or seed.  Per-slot sessions take
+    // anything inside require_slot_sampling; row sessions what their launch instantiation covers together with the session's setting (all
+    // greedy or all sampled); the lock-step sampler has no per-slot notion, so a plain session refuses both.
+    int session_add_ex(int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling, const uint64_t* seed) override {
+        use_device();
+        FS_REQUIRE(sess_active_, "no open session");
+        if (sampling || seed) {
+            if (!sess_slots_ && !sess_rows_)
+                throw Error("per-slot sampling / seed need a session begun with FS_SESSION_PER_SLOT or FS_SESSION_ROWS (the lock-step sampler has one setting and one stream per session)");
+            if (sampling && sess_slots_) require_slot_sampling(*sampling);
+            if (sampling && sess_rows_) {
+                const int tk = (int)std::min<uint64_t>(sampling->top_k, 1u << 30);
+                if ((sampling->temp != 0.0) != sess_sampled_) throw Error("FS_SESSION_ROWS: every slot greedy or every slot sampled, like the session's own setting");
+                if (sess_sampled_ && !fast_persist_samples((float)sampling->temp, tk, a_.codebook_size))
+                    throw Error("FS_SESSION_ROWS: sampled slots need temp > 0 and 0 < top_k <= 256");
+            }
+        }
+        const int b = prefix_id >= 0 ? session_add_prefixed(prefix_id, prompt, L, max_new_tokens) : session_add(prompt, L, max_new_tokens);
+        if (b >= 0) {
+            PendingAdd& pa = sess_queue_.back();
+            if (sampling) { pa.has_cfg = true; pa.cfg = slot_cfg(*sampling); }
+            if (seed) { pa.has_seed = true; pa.seed = *seed; }
+        }
+        return b;
     }
     void park_slot(int b) {
         SeqState ss = {};
@@ -1078,6 +1152,9 @@ class LM final : public LMBase {
     struct PendingAdd {
         int slot = -1, L = 0, n_iter = 0, order = 0, start = 0, prefix = -1, tail = -1;
         bool create = false;
+        bool has_cfg = false, has_seed = false;  // fs_lm_session_add_ex: the slot's own settings / sampler seed
+        SampleCfg cfg = {};
+        uint64_t seed = 0;
         std::vector<uint32_t> prompt;
         int rows() const { return create ? L : L - start - 1; }   // tokens this member runs through the slow transformer
         int cols() const { return create ? L : L - start; }       // columns of `prompt`
@@ -1206,7 +1283,11 @@ class LM final : public LMBase {
                 };
                 const bool create = sess_queue_[i].create;
                 int need_sum = extra(sess_queue_[i]);
+                // A member admitted with a sampler seed of its own (fs_lm_session_add_ex) is prefilled in a pass of its own: a group pass
+                // rounds differently from a single one (other tiling: ~5e-4 on the first logits), and whoever names a seed asks for codes
+                // that are a function of the request alone, not of what happened to be queued with it
                 while (i + S < sess_queue_.size() && S < fit && sess_queue_[i + S].rows() >= 1 && sess_queue_[i + S].create == create &&
+                       !sess_queue_[i].has_seed && !sess_queue_[i + S].has_seed &&
                        sess_queue_[i + S].start + Lp <= a_.max_seq_len) {
                     const int need = extra(sess_queue_[i + S]);
                     if (need_sum + need > (int)free_pages_.size()) break;
@@ -1328,6 +1409,10 @@ class LM final : public LMBase {
             sess_timed_ = false;
         }
         const int C1 = a_.num_codebooks + 1;
+        // per-slot sampler state of the joining slots, staged here until the stream has been waited for below
+        std::vector<SampleCfg> up_cfg;
+        std::vector<SlotRng> up_rng;
+        up_cfg.reserve(sess_flight_.size()); up_rng.reserve(sess_flight_.size());
         for (const PendingAdd& pa : sess_flight_) {
             if (pa.create) {  // the prefix's K/V are in place: its pad pages go back; a prefix released meanwhile goes now
                 SessPrefix& px = sess_prefixes_[pa.prefix];
@@ -1353,13 +1438,27 @@ class LM final : public LMBase {
                 sess_budget_tmp_ = pa.n_iter;
                 FS_HIP(hipMemcpyAsync(d_rbudget_.as<int>() + b, &sess_budget_tmp_, sizeof(int), hipMemcpyHostToDevice, st_));
                 RngState rng = {};
-                seed_key(sess_seed_ + (uint64_t)pa.order, rng.key);
+                seed_key(pa.has_seed ? pa.seed : sess_seed_ + (uint64_t)pa.order, rng.key);
                 FS_HIP(hipMemcpyAsync(d_rrng_.as<RngState>() + b, &rng, sizeof(rng), hipMemcpyHostToDevice, st_));
+                up_cfg.push_back(pa.has_cfg ? pa.cfg : sess_cfg_);  // (the slot's own settings, or the session's back after an occupant that had its own)
+                FS_HIP(hipMemcpyAsync(d_rcfg_.as<SampleCfg>() + b, &up_cfg.back(), sizeof(SampleCfg), hipMemcpyHostToDevice, st_));
                 launch_reppen_reset(rows_rp(b), a_.num_codebooks, a_.codebook_size, st_);
                 FS_HIP(hipStreamSynchronize(st_));  // (rng / budget are locals)
-            } else
+            } else {
+            if (sess_slots_) {  // the slot's settings, a StdRng stream at word 0 (no look-ahead word yet) and empty repetition-penalty windows
+                up_cfg.push_back(pa.has_cfg ? pa.cfg : sess_cfg_);
+                SlotRng sr;
+                std::memset(&sr, 0xFF, sizeof(sr));
+                sr.rng = RngState{};
+                seed_key(pa.has_seed ? pa.seed : sess_seed_ + (uint64_t)pa.order, sr.rng.key);
+                up_rng.push_back(sr);
+                FS_HIP(hipMemcpyAsync(d_scfg_.as<SampleCfg>() + b, &up_cfg.back(), sizeof(SampleCfg), hipMemcpyHostToDevice, st_));
+                FS_HIP(hipMemcpyAsync(d_srng_.as<SlotRng>() + b, &up_rng.back(), sizeof(SlotRng), hipMemcpyHostToDevice, st_));
+                launch_reppen_reset(slot_rp(b), a_.num_codebooks, a_.codebook_size, st_);
+            }
             LmKernels<WT>::embed(d_, tok_emb_, cb_emb_, a_.num_codebooks, a_.codebook_size, d_cfg_.as<SampleCfg>(), nullptr, state(b),
                                  d_pfx_.as<float>() + (size_t)b * a_.dim, st_);
+            }
             sess_left_[b] = pa.n_iter;
             sess_pos_[b] = Lp;
         }
@@ -1506,6 +1605,7 @@ class LM final : public LMBase {
         FS_HIP(hipMemcpyAsync(d_cfg_.p, &cfg, sizeof(cfg), hipMemcpyHostToDevice, st_));
         FS_HIP(hipStreamSynchronize(st_));
         sess_active_ = false;
+        sess_slots_ = false;
         sess_released_frames_ = 0;
         if (sess_rows_) {
             uint32_t ctl[4];
@@ -2154,12 +2254,17 @@ class LM final : public LMBase {
         if (!fold) LmKernels<WT>::rows_finish(d_, B, cs, norm_w_, st_);
         LmKernels<WT>::rows_head(d_, B, cs, slow_head_w(), slow_head_s(), n_audio_, d_lrows_.as<float>(), ld_slow_, st_, fold);
         // block-parallel samplers (temp > 1e-7, top_k <= 256): the step's C + 1 StdRng words per row are derived up front
+        const bool slots = sess_active_ && sess_slots_;  // FS_SESSION_PER_SLOT: the 9 sampler nodes are the per-slot ones, one for one
         const uint32_t* words = rows_par_ ? d_rwords_.as<uint32_t>() : nullptr;
         if (rows_par_) SampleKernels<WT>::rows_rng_words(d_rng_.as<RngState>(), B, C + 1, state(0), d_rwords_.as<uint32_t>(), st_);
         const bool capt = cap_frames_ > 0 && d_rcap_.p && d_rcap_.n >= sizeof(float) * (size_t)B * cap_frames_ * 9 * 2048;  // (fs_lm_debug_capture)
         if (capt) launch_cap_rows_logits(d_lrows_.as<float>(), ld_slow_, n_audio_, state(0), d_cfg_.as<SampleCfg>(), B, d_rcap_.as<float>(), cap_frames_, 0, st_);
         // folded steps: the sampler that writes a fast-decoder input row also leaves its first layer's normalised GEMM input (no k_prep node)
         const float* prep_g = fold && a_.dim <= 1024 ? fast_[0].attn_norm : nullptr;
+        if (slots)
+            SampleKernels<WT>::sample_slow_slots(d_, d_lrows_.as<float>(), ld_slow_, n_audio_, d_scfg_.as<SampleCfg>(), d_srng_.as<SlotRng>(), B, state(0),
+                                                 cs.X, d_xfrows_.as<float>(), st_, prep_g, cs.A, fold ? d_epoch_.as<uint32_t>() : nullptr);
+        else
         SampleKernels<WT>::sample_slow_rows(d_, d_lrows_.as<float>(), ld_slow_, n_audio_, d_cfg_.as<SampleCfg>(), d_rng_.as<RngState>(), B,
                                             C + 1, state(0), cs.X, d_xfrows_.as<float>(), st_, words, prep_g, cs.A, fold ? d_epoch_.as<uint32_t>() : nullptr);
         for (int cbi = 0; cbi < C; ++cbi) {
@@ -2187,11 +2292,17 @@ class LM final : public LMBase {
             LmKernels<WT>::rows_head(d_, B, cf, fast_out_w_, kFp8 ? fast_out_s_ : nullptr, a_.codebook_size, d_lfast_.as<float>(), a_.codebook_size, st_, fold);
             if (capt) launch_cap_rows_logits(d_lfast_.as<float>(), a_.codebook_size, a_.codebook_size, state(0), d_cfg_.as<SampleCfg>(), B, d_rcap_.as<float>(),
                                              cap_frames_, 1 + cbi, st_);
+            // (with the qkv table the next pass's first layer needs no normalised GEMM input from this sampler)
+            const float* prep_f = (fold && d_qkv0_.p && !getenv("FISHRT_ROWS_NO_QKV0") && a_.codebook_size == 1024) ? nullptr : prep_g;
+            if (slots) {
+                RepPenState rp0 = slot_rp(0);
+                SampleKernels<WT>::sample_fast_slots(d_, d_lfast_.as<float>(), cbi, C, a_.codebook_size, d_scfg_.as<SampleCfg>(), d_srng_.as<SlotRng>(), rp0,
+                                                     B, state(0), fast_emb_, d_xfrows_.as<float>(), tok_emb_, cb_emb_, cs.X, d_out_.as<uint32_t>(), out_cap_,
+                                                     st_, prep_f, cs.A);
+            } else
             SampleKernels<WT>::sample_fast_rows(d_, d_lfast_.as<float>(), cbi, C, a_.codebook_size, d_cfg_.as<SampleCfg>(),
                                                 d_rng_.as<RngState>(), B, state(0), fast_emb_, d_xfrows_.as<float>(), tok_emb_, cb_emb_,
-                                                cs.X, d_out_.as<uint32_t>(), out_cap_, st_, words,
-                                                // (with the qkv table the next pass's first layer needs no normalised GEMM input from this sampler)
-                                                (fold && d_qkv0_.p && !getenv("FISHRT_ROWS_NO_QKV0") && a_.codebook_size == 1024) ? nullptr : prep_g, cs.A);
+                                                cs.X, d_out_.as<uint32_t>(), out_cap_, st_, words, prep_f, cs.A);
         }
         if (capt) launch_cap_rows_picks(state(0), d_cfg_.as<SampleCfg>(), B, d_rcap_.as<float>(), cap_frames_, C, st_);
     }
@@ -2207,7 +2318,7 @@ class LM final : public LMBase {
         batch_graphs_.clear();
     }
     hipGraphExec_t batch_graph(int B) {
-        const int key = (sess_active_ ? 1 << 24 : 0) + (rows_par_ ? 1 << 25 : 0) + B * 1024 + nc_launch_;
+        const int key = (sess_active_ ? 1 << 24 : 0) + (rows_par_ ? 1 << 25 : 0) + (sess_active_ && sess_slots_ ? 1 << 26 : 0) + B * 1024 + nc_launch_;
         auto it = batch_graphs_.find(key);
         if (it != batch_graphs_.end()) return it->second;
         {   // the co-residency query of the folded step (rows_fold_ok -> occupancy API) is answered once, OUTSIDE stream capture
@@ -2611,6 +2722,9 @@ class LM final : public LMBase {
     int batch_rows_ = 0, batch_row_ = 0;  // generate_batch_sequential: batch sampler semantics for the row being generated
     // continuous-batching session: per-slot remaining iterations (-1 = empty), host copy of the slot states, scratch KV page of empty slots
     bool sess_active_ = false, sess_rows_ = false, sess_sampled_ = false;  // sess_rows_: FS_SESSION_ROWS (slots on the request-row kernels)
+    bool sess_slots_ = false;  // FS_SESSION_PER_SLOT (slots on the static-batch step with the per-slot samplers)
+    SampleCfg sess_cfg_ = {};  // the session's own SampleCfg (slots admitted without settings of their own)
+    DevBuf d_scfg_, d_srng_, d_srp_mask_, d_srp_seen_, d_srp_ring_, d_srp_meta_;  // per-slot sampler state [max_batch] (k_sample_*_slots)
     int sess_R_ = 0, sess_adds_ = 0, sess_budget_tmp_ = 0;
     uint64_t sess_seed_ = 0;
     std::unique_lock<PersistLock> sess_plock_;

@@ -200,6 +200,14 @@ struct RngState {      // rand 0.8.5 StdRng (ChaCha12) stream position
     unsigned long long consumed;  // u32 words consumed so far
 };
 
+struct SlotRng {       // per-slot sampler stream of a FS_SESSION_PER_SLOT session (k_sample_*_slots)
+    RngState rng;
+    // look-ahead cells, one per decision of a frame (0 slow, 1 + codebook): ahead_word[d] = the stream's word at position ahead_at[d],
+    // derived by a spare wave of the previous decision's launch; ~0 = none (reset when the slot is activated)
+    unsigned long long ahead_at[16];
+    uint32_t ahead_word[16];
+};
+
 template <typename WT>
 struct SampleKernels {
     // slow token: logits over [im_end, V) (utils.rs:13-16) -> token = idx + im_end; sets done; copies x -> xf; *hid_slot (device
@@ -224,6 +232,16 @@ struct SampleKernels {
                                  const RngState* master, int B, SeqState* states, const void* fast_emb, float* XF, const void* tok_emb,
                                  const void* cb_emb, float* X, uint32_t* out_codes, int out_cap, hipStream_t st, const uint32_t* words = nullptr,
                                  const float* prep_g = nullptr, uint16_t* prep_A = nullptr);
+    // per-slot samplers of a FS_SESSION_PER_SLOT session: one block per slot, every decision that of the slot's own generate_blocking --
+    // cfgs[B], rngs[B] and the repetition-penalty state (rp: mask / seen [B][n_cb][cb_size], ring [B][n_cb][17], ring_meta [B][n_cb][2])
+    // are per slot.  Settings per slot: temp == 0, or temp > 0 with 0 < top_k <= 256; n <= 2048, cb_size <= 1024.
+    static void sample_slow_slots(const ModelDims& d, const float* logits, int ld, int n, const SampleCfg* cfgs, SlotRng* rngs, int B,
+                                  SeqState* states, const float* X, float* XF, hipStream_t st, const float* prep_g = nullptr,
+                                  uint16_t* prep_A = nullptr, uint32_t* epoch = nullptr);
+    static void sample_fast_slots(const ModelDims& d, const float* logits, int cb, int n_cb, int cb_size, const SampleCfg* cfgs, SlotRng* rngs,
+                                  RepPenState rp, int B, SeqState* states, const void* fast_emb, float* XF, const void* tok_emb,
+                                  const void* cb_emb, float* X, uint32_t* out_codes, int out_cap, hipStream_t st,
+                                  const float* prep_g = nullptr, uint16_t* prep_A = nullptr);
     // words[b * 16 + call] = the StdRng word of sample() call `call` of this step for row b (child stream of master u64 number (frame * calls + call) * B + b)
     static void rows_rng_words(const RngState* master, int B, int calls_per_frame, const SeqState* states, uint32_t* words, hipStream_t st);
 };

@@ -2985,6 +2985,208 @@ __global__ __launch_bounds__(PAR_THREADS) void k_sample_fast_rows_par(const floa
     embed_tokens<WT>(tok_emb, cb_emb, dim, n_cb, cb_size, c.sem_lo, c.sem_hi, cur, 1, X + (size_t)b * dim, tid, PAR_THREADS);
 }
 
+// ---- per-slot samplers (fs_lm_session_begin with FS_SESSION_PER_SLOT): one block per session slot on the static-batch step, every decision
+// that of the slot's OWN generate_blocking call (k_sample_slow / k_sample_fast above; single_batch.rs:102-210, sampling/mod.rs:51-75,
+// rep_pen.rs:4-72): the slot's SampleCfg, one StdRng stream per slot whose consumed count lives on the device, the 16-deep repetition
+// penalty window per codebook from the slot's second frame on, greedy iff temp == 0 with the LAST-max tie rule, top-p compared in f32, and
+// no codebook decision (codes 0, nothing drawn, window untouched) once the slow token is <|im_end|>.  Everything is read through per-slot
+// pointers, so one captured graph serves every mix of settings; greedy / sampled is a block-uniform branch.  A parked, frozen or
+// finished slot (done != 0) decides nothing, draws nothing and leaves its generator state alone; it still writes finite fast-decoder
+// input rows, because the step's GEMMs run over all rows.
+// The block has one wave more than the sampler needs.  The StdRng word of a draw is one ChaCha12 block of dependent integer work; all
+// PAR_THREADS threads take part in bsample's barriers, so none of them can compute it while the selection runs.  The extra wave does:
+// while decision d selects, it derives the word decision d + 1 will most likely need (stream position consumed + 1) into the slot's
+// look-ahead cell, tagged with that position, and ends (a terminated wave does not count at the block's barriers).  Decision d + 1 takes
+// the cell when its tag equals the stream position and derives the word itself otherwise (first decision after activation, a draw that
+// consumed nothing) -- the tag makes the look-ahead a pure latency matter, never one of correctness.
+constexpr int SLOT_THREADS = PAR_THREADS + 64;
+__device__ __forceinline__ void slot_word_ahead(SlotRng* rg, int next_decision) {
+    const unsigned long long at = rg->rng.consumed + 1ull;
+    rg->ahead_word[next_decision] = chacha12_word(rg->rng.key, at);
+    rg->ahead_at[next_decision] = at;
+}
+__device__ __forceinline__ uint32_t slot_word(const SlotRng* rg, int decision, unsigned long long at) {
+    if (rg->ahead_at[decision] == at) return rg->ahead_word[decision];
+    return chacha12_word(rg->rng.key, at);  // (block-uniform: every thread derives the same word)
+}
+// greedy_pick's rule (host ArgMax: the LAST maximal index) for bsample's blocked ownership (thread t owns candidates t * EPT ..): the
+// block maximum of {order-preserving value bits : index}.  *s_key must have been zeroed before the previous barrier; one barrier.
+template <int EPT>
+__device__ __forceinline__ int slot_greedy_pick(const float (&lv)[EPT], int n, unsigned long long* s_key) {
+    const int tid = threadIdx.x;
+    unsigned long long key = 0ull;
+#pragma unroll
+    for (int s = 0; s < EPT; ++s) {
+        const int i = tid * EPT + s;
+        if (i < n) {
+            uint32_t u = __float_as_uint(lv[s] + 0.f);  // (-0 -> +0: equal values, the later index wins)
+            u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;  // unsigned order == float order
+            const unsigned long long k = ((unsigned long long)u << 32) | (unsigned long long)(uint32_t)i;
+            key = k > key ? k : key;
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) { const unsigned long long o = __shfl_xor(key, m, 64); key = o > key ? o : key; }
+    if ((tid & 63) == 0) atomicMax(s_key, key);
+    __syncthreads();
+    return (int)(*s_key & 0xFFFFFFFFull);
+}
+template <typename WT>
+__global__ __launch_bounds__(SLOT_THREADS) void k_sample_slow_slots(const float* __restrict__ logits, int ld, int n, const SampleCfg* __restrict__ cfgs,
+                                                                     SlotRng* __restrict__ rngs, SeqState* __restrict__ states,
+                                                                     const float* __restrict__ X, float* __restrict__ XF, int dim, PrepOut po) {
+    __shared__ float red4[4];
+    __shared__ BSampLds S;
+    __shared__ unsigned long long s_key;
+    const int tid = threadIdx.x, b = blockIdx.x;
+    SeqState* st = states + b;
+    SlotRng* rg = rngs + b;
+    const bool live = st->done == 0;
+    const float temp = cfgs[b].temp;
+    if (tid >= PAR_THREADS) {  // the look-ahead wave (see above)
+        if (tid == PAR_THREADS && live && temp != 0.f) slot_word_ahead(rg, 1);
+        return;
+    }
+    const SampleCfg c = cfgs[b];
+    if (tid == 0) s_key = 0ull;
+    for (int i = tid; i < dim; i += PAR_THREADS) XF[(size_t)b * dim + i] = X[(size_t)b * dim + i];  // hidden_states -> fast decoder input
+    if (live) {
+        float lv[4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int i = tid * 4 + s;
+            lv[s] = i < n ? logits[(size_t)b * ld + i] : 0.f;
+            if (i == 0 && c.ignore_eos) lv[s] = -INFINITY;
+        }
+        int idx;
+        if (temp == 0.f) {
+            __syncthreads();  // s_key
+            idx = slot_greedy_pick<4>(lv, n, &s_key);
+        } else {
+            const unsigned long long at = rg->rng.consumed;
+            const uint32_t word = slot_word(rg, 0, at);
+            int used = 0;
+            idx = bsample<PAR_THREADS, 4>(lv, n, c.top_k, (float)(1.0 / (double)c.temp), c.top_p, word, &used, S);
+            if (tid == 0) rg->rng.consumed = at + (unsigned long long)used;
+        }
+        if (tid == 0) {
+            const uint32_t tok = audio_tok(c, idx);  // rescale_semantic_tokens (utils.rs:45-46)
+            st->cur[0] = tok;
+            if (tok == c.im_end_id) st->done = 1;  // the frame's codebook decisions are skipped; the slot freezes at the end of the frame
+        }
+    }
+    if (po.epoch && b == 0 && tid == 0) po.epoch[0] += 1;
+    if (po.g) block_prep_row(XF + (size_t)b * dim, dim, po, b, red4);
+}
+template <typename WT>
+__global__ __launch_bounds__(SLOT_THREADS) void k_sample_fast_slots(const float* __restrict__ logits, int cb, int n_cb, int cb_size,
+                                                                     const SampleCfg* __restrict__ cfgs, SlotRng* __restrict__ rngs, RepPenState rp,
+                                                                     SeqState* __restrict__ states, const WT* __restrict__ fast_emb, float* __restrict__ XF,
+                                                                     const WT* __restrict__ tok_emb, const WT* __restrict__ cb_emb, float* __restrict__ X,
+                                                                     int dim, uint32_t* __restrict__ out_codes, int out_cap, PrepOut po) {
+    __shared__ float red4[4];
+    __shared__ BSampLds S;
+    __shared__ unsigned long long s_key;
+    const int tid = threadIdx.x, b = blockIdx.x, n = cb_size;
+    SeqState* st = states + b;
+    SlotRng* rg = rngs + b;
+    // done != 0: parked / frozen / finished, or this frame's slow token was <|im_end|> (single_batch.rs:153-156: push 0, skip the fast step)
+    const bool live = st->done == 0;
+    const float temp = cfgs[b].temp;
+    if (tid >= PAR_THREADS) {  // the look-ahead wave: the next decision is codebook cb + 1, or the next frame's slow token
+        if (tid == PAR_THREADS && live && temp != 0.f) slot_word_ahead(rg, cb == n_cb - 1 ? 0 : cb + 2);
+        return;
+    }
+    const SampleCfg c = cfgs[b];
+    if (tid == 0) s_key = 0ull;
+    int code = 0;
+    if (live) {
+        // the slot's RepPenState of this codebook: mask [slot][n_cb][cb_size], ring [slot][n_cb][17], meta [slot][n_cb][2]
+        const size_t sc = (size_t)b * n_cb + cb;
+        float* mask = rp.mask + sc * cb_size;
+        int* ring = rp.ring + sc * 17;
+        int* meta = rp.ring_meta + sc * 2;
+        const bool pen = st->have_prev != 0;
+        // SingleBatchedRepPenProcessor::apply (rep_pen.rs:37-65), as k_sample_fast: push_front the codebook's previous pick, pop_back past
+        // 16 entries; "token in tokens_seen" == "mask[token] == penalty".  The ring is read here and written behind the decision's barriers.
+        int last = -1, dropped = -1, head = 0, len = 0;
+        bool drop = false;
+        if (pen) {
+            last = (int)st->prev[cb + 1];
+            head = (meta[0] + 16) % 17; len = meta[1] + 1;
+            drop = len > 16;
+            if (drop) dropped = ring[(head + len - 1) % 17];  // (never the slot about to be written)
+        }
+        float lv[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const int i = tid * 2 + s;
+            lv[s] = 0.f;
+            if (i < n) {
+                lv[s] = logits[(size_t)b * n + i];
+                if (pen) {
+                    const float m0 = mask[i];
+                    float m = m0;
+                    if (i == last) m = c.rep_pen;
+                    if (i == dropped && m == c.rep_pen) m = 1.0f;
+                    if (m != m0) mask[i] = m;
+                    lv[s] = lv[s] / m;  // whatever the sign (rep_pen.rs:62)
+                }
+            }
+        }
+        if (temp == 0.f) {
+            __syncthreads();  // s_key
+            code = slot_greedy_pick<2>(lv, n, &s_key);
+        } else {
+            const unsigned long long at = rg->rng.consumed;
+            const uint32_t word = slot_word(rg, 1 + cb, at);
+            int used = 0;
+            code = bsample<PAR_THREADS, 2>(lv, n, c.top_k, (float)(1.0 / (double)c.temp), c.top_p, word, &used, S);
+            if (tid == 0) rg->rng.consumed = at + (unsigned long long)used;
+        }
+        if (tid == 0) {
+            if (pen) { ring[head] = last; meta[0] = head; meta[1] = drop ? 16 : len; }
+            st->cur[cb + 1] = (uint32_t)code;  // (also the next pass's qkv-table row)
+        }
+    }
+    if (cb != n_cb - 1) {
+        for (int d = tid; d < dim; d += PAR_THREADS) XF[(size_t)b * dim + d] = WTr<WT>::to_f32(fast_emb[(size_t)code * dim + d]);
+        if (po.g) block_prep_row(XF + (size_t)b * dim, dim, po, b, red4);
+        return;
+    }
+    // ---- end of frame: the bookkeeping of k_sample_fast_rows with the session's frozen-slot rule (single_batch.rs:185-210: first frame
+    // emitted unconditionally, the terminating iteration's codes are not)
+    __syncthreads();
+    __shared__ uint32_t cur[16];
+    if (tid <= n_cb) {
+        const uint32_t slow = st->cur[0];
+        const bool is_audio = slow >= c.sem_lo;
+        uint32_t v = tid == 0 ? slow : (tid == n_cb && live ? (uint32_t)code : st->cur[tid]);
+        if (tid > 0 && !is_audio) v = 0;
+        cur[tid] = v;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const int frame = st->frame;
+        const bool frozen = st->done != 0 && frame > 0;
+        if (!frozen) {
+            if (frame == 0 || !st->done) {
+                if (frame == 0 && cur[0] < c.sem_lo) st->step = -1;  // (see k_sample_fast_rows)
+                const int o = st->n_out;
+                uint32_t* oc = out_codes + (size_t)b * n_cb * out_cap;
+                if (o < out_cap)
+                    for (int cc = 0; cc < n_cb; ++cc) oc[(size_t)cc * out_cap + o] = cur[cc + 1];
+                st->n_out = o + 1;
+            }
+            for (int i = 0; i <= n_cb; ++i) { st->prev[i] = cur[i]; st->cur[i] = cur[i]; }
+            st->have_prev = 1;
+            st->pos += 1;
+            st->frame = frame + 1;
+        }
+    }
+    embed_tokens<WT>(tok_emb, cb_emb, dim, n_cb, cb_size, c.sem_lo, c.sem_hi, cur, 1, X + (size_t)b * dim, tid, PAR_THREADS);
+}
+
 // test hook of the block-parallel sampler (lm_bsample_dev.h) with the static-batch RNG derivation of k_sample_slow_rows
 template <int NT, int EPT>
 __global__ __launch_bounds__(NT) void k_bsample_rows_test(const float* __restrict__ logits, int n, const SampleCfg* __restrict__ cp,
@@ -3298,6 +3500,30 @@ void SampleKernels<WT>::sample_fast_rows(const ModelDims& d, const float* logits
     }
     hipLaunchKernelGGL((k_sample_fast_rows<KVT<WT>>), dim3(B), dim3(SAMPLE_THREADS), 0, st, logits, cb, n_cb, cb_size, c, master, B, states,
                        (const KVT<WT>*)fast_emb, XF, (const KVT<WT>*)tok_emb, (const KVT<WT>*)cb_emb, X, d.dim, out_codes, out_cap, po);
+    FS_LAUNCH_CHECK();
+}
+
+template <typename WT>
+void SampleKernels<WT>::sample_slow_slots(const ModelDims& d, const float* logits, int ld, int n, const SampleCfg* cfgs, SlotRng* rngs, int B,
+                                          SeqState* states, const float* X, float* XF, hipStream_t st, const float* prep_g, uint16_t* prep_A,
+                                          uint32_t* epoch) {
+    FS_REQUIRE(n <= PAR_THREADS * 4 && n <= ld, "audio-range vocabulary larger than the per-slot sampler capacity (2048)");
+    FS_REQUIRE(!prep_g || (d.dim <= 1024 && d.dim % 4 == 0), "sampler-side RMSNorm of the next input row: dim <= 1024");
+    const PrepOut po{prep_g, d.eps, prep_A, epoch};
+    hipLaunchKernelGGL((k_sample_slow_slots<KVT<WT>>), dim3(B), dim3(SLOT_THREADS), 0, st, logits, ld, n, cfgs, rngs, states, X, XF, d.dim, po);
+    FS_LAUNCH_CHECK();
+}
+template <typename WT>
+void SampleKernels<WT>::sample_fast_slots(const ModelDims& d, const float* logits, int cb, int n_cb, int cb_size, const SampleCfg* cfgs,
+                                          SlotRng* rngs, RepPenState rp, int B, SeqState* states, const void* fast_emb, float* XF,
+                                          const void* tok_emb, const void* cb_emb, float* X, uint32_t* out_codes, int out_cap, hipStream_t st,
+                                          const float* prep_g, uint16_t* prep_A) {
+    FS_REQUIRE(cb_size <= PAR_THREADS * 2 && n_cb + 1 <= 16, "codebook larger than the per-slot sampler capacity (1024)");
+    FS_REQUIRE(!prep_g || (d.dim <= 1024 && d.dim % 4 == 0), "sampler-side RMSNorm of the next input row: dim <= 1024");
+    const PrepOut po{prep_g, d.eps, prep_A, nullptr};
+    hipLaunchKernelGGL((k_sample_fast_slots<KVT<WT>>), dim3(B), dim3(SLOT_THREADS), 0, st, logits, cb, n_cb, cb_size, cfgs, rngs, rp, states,
+                       reinterpret_cast<const KVT<WT>*>(fast_emb), XF, reinterpret_cast<const KVT<WT>*>(tok_emb),
+                       reinterpret_cast<const KVT<WT>*>(cb_emb), X, d.dim, out_codes, out_cap, po);
     FS_LAUNCH_CHECK();
 }
 

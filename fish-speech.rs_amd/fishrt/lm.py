@@ -213,9 +213,10 @@ class DualARTransformer:
         _ffi.check(_ffi.lib().fs_lm_weights_adopt(self._h))
         return self
 
-    def session(self, temp=0.7, top_p=0.9, top_k=50, seed=42, ignore_eos=False, rows=False, repetition_penalty=1.2):
-        """continuous batching over this handle's max_batch slots (fishrt.h: fs_lm_session_*): `with lm.session(...) as s:`"""
-        return Session(self, temp, top_p, top_k, seed, ignore_eos, rows, repetition_penalty)
+    def session(self, temp=0.7, top_p=0.9, top_k=50, seed=42, ignore_eos=False, rows=False, repetition_penalty=1.2, per_slot=False):
+        """continuous batching over this handle's max_batch slots (fishrt.h: fs_lm_session_*): `with lm.session(...) as s:`
+        per_slot=True: FS_SESSION_PER_SLOT -- every slot samples like its own generate_blocking call (own settings, seed, repetition penalty)"""
+        return Session(self, temp, top_p, top_k, seed, ignore_eos, rows, repetition_penalty, per_slot)
 
     def last_stats(self):
         st = _ffi.GenStats()
@@ -264,12 +265,21 @@ class Session:
     step(n) runs up to n frames for all live slots and returns how many are still generating; poll(slot) -> (codes (C, n), done);
     release(slot) frees the slot.  A slot generates what a one-prompt generate_static_batch would (no repetition penalty)."""
 
-    def __init__(self, lm, temp, top_p, top_k, seed, ignore_eos, rows=False, repetition_penalty=1.2):
+    SAMPLING_KEYS = ("temp", "top_p", "top_k", "repetition_penalty")
+
+    def __init__(self, lm, temp, top_p, top_k, seed, ignore_eos, rows=False, repetition_penalty=1.2, per_slot=False):
         """rows=True: FS_SESSION_ROWS -- the slots run on the request-row persistent kernels with batch-1 semantics (repetition penalty, own
-        sampler stream per slot); max_batch <= 8"""
+        sampler stream per slot); max_batch <= 8.
+        per_slot=True: FS_SESSION_PER_SLOT -- the slots stay on the static-batch step (any max_batch, bf16 / fp8) and every slot samples like
+        its own generate_blocking call, with the settings and seed of its add() (default: the session's, seed + admission number)"""
         self.lm, self._open = lm, False
-        s = _ffi.Sampling(float(temp), float(top_p), int(top_k), float(repetition_penalty) if rows else 1.0)
-        _ffi.check(_ffi.lib().fs_lm_session_begin(lm._h, C.byref(s), C.c_uint64(seed), (1 if ignore_eos else 0) | (8 if rows else 0)))
+        if rows and per_slot:
+            raise ValueError("rows and per_slot exclude each other (a row session's slots already sample per slot)")
+        self.rows, self.per_slot = bool(rows), bool(per_slot)
+        self.sampling = dict(temp=float(temp), top_p=float(top_p), top_k=int(top_k), repetition_penalty=float(repetition_penalty))
+        s = _ffi.Sampling(float(temp), float(top_p), int(top_k), float(repetition_penalty) if (rows or per_slot) else 1.0)
+        flags = (_ffi.FS_GEN_IGNORE_EOS if ignore_eos else 0) | (_ffi.FS_SESSION_ROWS if rows else 0) | (_ffi.FS_SESSION_PER_SLOT if per_slot else 0)
+        _ffi.check(_ffi.lib().fs_lm_session_begin(lm._h, C.byref(s), C.c_uint64(seed), flags))
         self._open = True
 
     def __enter__(self):
@@ -289,12 +299,39 @@ class Session:
             raise ValueError(f"{what} must be u32 [{self.lm.cfg['num_codebooks'] + 1}, L >= 1], got {p.shape}")
         return p
 
-    def add(self, prompt, max_new_tokens, prefix=None):
+    def _sampling(self, sampling):
+        """dict or SamplingArgs-like (temp / top_p / top_k / repetition_penalty; missing entries: the session's) -> _ffi.Sampling"""
+        if isinstance(sampling, dict):
+            unknown = set(sampling) - set(self.SAMPLING_KEYS)
+            if unknown:
+                raise ValueError(f"unknown sampling settings {sorted(unknown)} (known: {', '.join(self.SAMPLING_KEYS)})")
+            get = sampling.get
+        else:
+            if not any(hasattr(sampling, k) for k in self.SAMPLING_KEYS):
+                raise ValueError("sampling must be a dict or an object with temp / top_p / top_k / repetition_penalty")
+            get = lambda k, d: getattr(sampling, k, d)
+        v = {k: get(k, self.sampling[k]) for k in self.SAMPLING_KEYS}
+        if not (float(v["temp"]) >= 0.0) or int(v["top_k"]) < 0:
+            raise ValueError("sampling: temp and top_k must not be negative")
+        return _ffi.Sampling(float(v["temp"]), float(v["top_p"]), int(v["top_k"]), float(v["repetition_penalty"]))
+
+    def add(self, prompt, max_new_tokens, prefix=None, sampling=None, seed=None):
         """prefix (an add_prefix id): `prompt` is the request's BODY -- the slot generates what add(concat(prefix prompt, body)) would,
-        reading the prefix's K/V from its shared pages and prefilling the body only"""
+        reading the prefix's K/V from its shared pages and prefilling the body only.
+        sampling (dict or SamplingArgs-like) / seed: the slot's own sampler settings / StdRng seed (fs_lm_session_add_ex) -- per_slot and rows
+        sessions only; a plain session has one lock-step sampler and refuses them"""
         p = self._prompt(prompt, "prompt" if prefix is None else "body")
         slot = C.c_int(-1)
-        if prefix is None:
+        if sampling is not None or seed is not None:
+            if not (self.rows or self.per_slot):
+                raise ValueError("per-slot sampling / seed need lm.session(per_slot=True) or lm.session(rows=True)")
+            sp = C.byref(self._sampling(sampling)) if sampling is not None else None
+            if seed is not None and not 0 <= int(seed) < 2**64:
+                raise ValueError("seed must fit an unsigned 64-bit integer")
+            sd = C.byref(C.c_uint64(int(seed))) if seed is not None else None
+            _ffi.check(_ffi.lib().fs_lm_session_add_ex(self.lm._h, -1 if prefix is None else int(prefix), p.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                       int(p.shape[1]), int(max_new_tokens), sp, sd, C.byref(slot)))
+        elif prefix is None:
             _ffi.check(_ffi.lib().fs_lm_session_add(self.lm._h, p.ctypes.data_as(C.POINTER(C.c_uint32)), int(p.shape[1]), int(max_new_tokens),
                                                     C.byref(slot)))
         else:

@@ -22,6 +22,14 @@ several jobs are in flight (or a request asks for `batch_size`) on a `max_batch 
 (`fs_lm_session_*`), a job joins as soon as a slot is free and leaves when it is done -- token-level admission, no lock-step batches.
 A lone job takes the batch-1 path with its persistent decode kernels.  `Scheduler(continuous=False)` keeps the lock-step variant
 (jobs waiting together go through one `generate_static_batch` call).
+
+Per-request sampling (`Scheduler(per_slot_sampling=True)`, off by default).  A session that cannot take the request-row kernels is opened
+with FS_SESSION_PER_SLOT instead of the lock-step sampler: every job is admitted with the server's settings (repetition penalty included)
+and a sampler seed of its own, so what a job generates no longer depends on its slot or on the other jobs, and every chunk may join the
+session without `batch_size`.  Requests may then carry `temperature`, `top_p`, `top_k`, `repetition_penalty` and `seed` (an extension:
+the reference's `GenerateRequest` has none).  They are honoured on the batch-1 path and in per-slot / row sessions; a job that carries
+any of them never enters a lock-step sampler path -- it runs alone instead -- and a job with a `seed` always runs in the session on a
+`max_batch > 1` handle, alone or not, so that the same request gives the same audio whatever else the server is doing.
 """
 import collections
 import hashlib
@@ -101,17 +109,20 @@ class LMState:  # server/lib/state.rs:12-21
 
 class AppState:  # server/lib/state.rs:23-29
     def __init__(self, lm_state, codec, sample_rate=44100, opus_encoder=None, preprocess=preprocess_text, batch_window_s=0.002,
-                 continuous=True, auto_batch=False, session_prefixes=False):
+                 continuous=True, auto_batch=False, session_prefixes=False, per_slot_sampling=False):
         self.lm, self.codec, self.sample_rate, self.opus_encoder, self.preprocess = lm_state, codec, sample_rate, opus_encoder, preprocess
+        self.codec_lock = threading.Lock()  # a codec handle takes one call at a time (include/fishrt.h); requests vocode from their own threads
         self.auto_batch = auto_batch  # True: every chunk may join the batching session (batch sampling semantics) without `batch_size`
         # session_prefixes (off by default): session jobs share their voice's conditioning prefix (Session.add_prefix) instead of prefilling
         # it per chunk.  A prefix prefilled on its own may round differently from the full prompt and flip a near-tie, so it stays opt-in.
-        self.scheduler = Scheduler(lm_state, batch_window_s, continuous, session_prefixes=session_prefixes)
+        # per_slot_sampling (off by default): per-request sampler semantics in sessions + request-level sampling fields (module docstring)
+        self.scheduler = Scheduler(lm_state, batch_window_s, continuous, session_prefixes=session_prefixes, per_slot_sampling=per_slot_sampling)
 
 
 class _Job:
-    def __init__(self, cond, body, n_cond, allow_batch):
+    def __init__(self, cond, body, n_cond, allow_batch, sampling=None, seed=None):
         self.cond, self.body, self.n_cond, self.allow_batch, self.future = cond, body, n_cond, allow_batch, Future()
+        self.sampling, self.seed = sampling, seed  # request-level SamplingArgs / sampler seed (None: the server's / a fresh one)
         self.cond_key = hashlib.sha1(cond.tobytes()).hexdigest() if cond is not None else None
 
     def full_prompt(self):
@@ -126,23 +137,46 @@ class Scheduler:
 
     PREFIX_LRU = 8  # conditioning prefixes kept per session (session_prefixes)
 
-    def __init__(self, lm_state, batch_window_s=0.002, continuous=True, step_frames=8, session_prefixes=False):
+    def __init__(self, lm_state, batch_window_s=0.002, continuous=True, step_frames=8, session_prefixes=False, per_slot_sampling=False):
         self.s, self.q, self.window = lm_state, queue.Queue(), batch_window_s
         self.continuous, self.step_frames = continuous, step_frames
         self.session_prefixes = session_prefixes
+        self.per_slot_sampling = per_slot_sampling
+        self.sess_mode = None  # "rows" | "per_slot" | "plain" while a session is open
         self.prefixes = collections.OrderedDict()  # session_prefixes: cond_key -> prefix id of the open session (LRU order)
         self.cached_key = None
         self.stats = dict(jobs=0, single=0, batched_rows=0, batches=0, prefix_hits=0, rerolls=0)
         if session_prefixes:
             self.stats.update(session_prefix_hits=0, session_prefix_tokens_saved=0)
+        if per_slot_sampling:
+            self.stats.update(per_slot_sessions=0)
         self._stop = False
         self.th = threading.Thread(target=self._run, daemon=True)
         self.th.start()
 
-    def submit(self, cond, body, n_cond, allow_batch):
-        j = _Job(cond, body, n_cond, allow_batch)
+    def submit(self, cond, body, n_cond, allow_batch, sampling=None, seed=None):
+        j = _Job(cond, body, n_cond, allow_batch, sampling, seed)
         self.q.put(j)
         return j.future
+
+    @staticmethod
+    def _own(j):
+        return getattr(j, "sampling", None) is not None or getattr(j, "seed", None) is not None
+
+    def _session_ok(self, j):
+        """may job j join a session?  Jobs without request-level settings: always.  With: only where a slot samples per request
+        (per_slot_sampling) and with settings inside the per-slot samplers' limit -- greedy, or temp > 0 with 0 < top_k <= 256; on handles
+        whose sessions take the request-row kernels (2 / 4 / 8 slots) additionally greedy like the server's default or sampled like it."""
+        if not self._own(j):
+            return True
+        if not self.per_slot_sampling:
+            return False
+        sa, d = j.sampling or self.s.default_sampling_args, self.s.default_sampling_args
+        if not (sa.temp == 0 or (sa.temp > 0 and 0 < sa.top_k <= 256)):
+            return False
+        if getattr(self.s.lm, "max_batch", 0) in (2, 4, 8) and self.sess_mode != "per_slot" and (sa.temp == 0) != (d.temp == 0):
+            return False
+        return True
 
     def close(self):
         self._stop = True
@@ -169,8 +203,9 @@ class Scheduler:
                         self.q.put(_STOP)
                         break
                     batch.append(n)  # (a job that must not be batched still shares the gather; it runs alone below)
-            runs_alone = [b for b in batch if not b.allow_batch]
-            together = [b for b in batch if b.allow_batch]
+            # (a job with request-level sampling settings never enters the lock-step sampler: it runs alone)
+            runs_alone = [b for b in batch if not b.allow_batch or self._own(b)]
+            together = [b for b in batch if b.allow_batch and not self._own(b)]
             try:
                 if len(together) >= 2:
                     self._batched(together)
@@ -220,8 +255,10 @@ class Scheduler:
                         self.prefixes.clear()
                     return
                 if held is not None:
-                    lone = not live and self.q.empty()
-                    if not held.allow_batch or lone:
+                    joins = held.allow_batch and self._session_ok(held)
+                    # (per_slot_sampling: a job with a seed of its own runs in the session even when it is alone -- same kernels, same audio)
+                    lone = not live and self.q.empty() and not (self.per_slot_sampling and joins and held.seed is not None)
+                    if not joins or lone:
                         if not live:  # drain first; then the batch-1 path
                             if sess is not None:
                                 sess.close()
@@ -243,10 +280,22 @@ class Scheduler:
                                                   repetition_penalty=sa.repetition_penalty) if rows else None
                             except Exception:  # (f32 / fp8 / Fish <= 1.4 handles, or the device's persistent kernels are taken)
                                 sess = None
-                            if sess is None:
-                                sess = lm.session(temp=sa.temp, top_p=sa.top_p, top_k=sa.top_k, seed=seed)
-                            else:
+                            if sess is not None:
                                 self.stats["row_sessions"] = self.stats.get("row_sessions", 0) + 1
+                                self.sess_mode = "rows"
+                            elif self.per_slot_sampling:
+                                try:
+                                    sess = lm.session(temp=sa.temp, top_p=sa.top_p, top_k=sa.top_k, seed=seed, per_slot=True,
+                                                      repetition_penalty=sa.repetition_penalty)
+                                except Exception:  # (no per-slot session on this handle / with these defaults: never the lock-step sampler instead)
+                                    j, held = held, None
+                                    self._single(j)
+                                    continue
+                                self.stats["per_slot_sessions"] += 1
+                                self.sess_mode = "per_slot"
+                            else:
+                                sess = lm.session(temp=sa.temp, top_p=sa.top_p, top_k=sa.top_k, seed=seed)
+                                self.sess_mode = "plain"
                             self.cached_key = None
                             self.prefixes.clear()
                         try:
@@ -309,8 +358,12 @@ class Scheduler:
         """admit job j into the session -> (slot or None, whether it joined on an existing prefix).  session_prefixes: the job's
         conditioning prefix is prefilled once per session (LRU of PREFIX_LRU) and the job prefills its body only; a prefix the KV pool
         cannot hold falls back to the full prompt"""
+        kw = {}
+        if self.per_slot_sampling and self.sess_mode in ("rows", "per_slot"):  # the job's own settings and seed, else the server's and a fresh seed
+            sa = j.sampling or self.s.default_sampling_args
+            kw = dict(sampling=sa.kw(), seed=(j.seed if j.seed is not None else self.s.seed_source()) & (2**64 - 1))
         if not self.session_prefixes or j.cond is None or j.cond.shape[1] < 1 or j.body.shape[1] < 1:
-            return sess.add(j.full_prompt(), self.s.max_new_tokens), False
+            return sess.add(j.full_prompt(), self.s.max_new_tokens, **kw), False
         pid = self.prefixes.get(j.cond_key)
         hit = pid is not None and not getattr(j, "made_prefix", False)  # (a job retried while the slots were full created its own)
         if pid is not None:
@@ -318,13 +371,13 @@ class Scheduler:
         else:
             pid = sess.add_prefix(j.cond)
             if pid is None:
-                return sess.add(j.full_prompt(), self.s.max_new_tokens), False
+                return sess.add(j.full_prompt(), self.s.max_new_tokens, **kw), False
             self.prefixes[j.cond_key] = pid
             j.made_prefix = True
             while len(self.prefixes) > self.PREFIX_LRU:  # (slots still on an evicted prefix keep its pages until they are released)
                 _, old = self.prefixes.popitem(last=False)
                 sess.release_prefix(old)
-        return sess.add(j.body, self.s.max_new_tokens, prefix=pid), hit
+        return sess.add(j.body, self.s.max_new_tokens, prefix=pid, **kw), hit
 
     def _codes_out(self, codes):
         if self.s.model_type != fprompt.FISH_1_5:  # speech.rs:63-68: Fish <= 1.4 codes are shifted by one
@@ -335,7 +388,9 @@ class Scheduler:
 
     def _single(self, j):
         try:
-            lm, sa = self.s.lm, self.s.default_sampling_args
+            lm, sa = self.s.lm, getattr(j, "sampling", None) or self.s.default_sampling_args
+            own_seed = getattr(j, "seed", None)
+            draw = (lambda: own_seed) if own_seed is not None else self.s.seed_source
             self.stats["jobs"] += 1
             self.stats["single"] += 1
             if j.cond_key is not None and j.cond_key == self.cached_key and lm.curr_kv_size() == j.n_cond:
@@ -344,7 +399,7 @@ class Scheduler:
             else:
                 lm.clear_slow_layer_caches()
                 prompt = j.full_prompt()
-            codes = lm.generate_blocking(prompt, self.s.max_new_tokens, seed=self.s.seed_source(), **sa.kw())
+            codes = lm.generate_blocking(prompt, self.s.max_new_tokens, seed=draw(), **sa.kw())
             lm.clear_slow_caches_until(j.n_cond)  # speech.rs:40
             self.cached_key = j.cond_key if j.cond is not None else None
             if codes.shape[1] == self.s.max_new_tokens and getattr(j, "reroll", False):  # this WAS the re-roll of a session job
@@ -414,6 +469,28 @@ def _prompts_for_request(state, req):
     return n_cond, cond, bodies
 
 
+_REQ_SAMPLING = (("temperature", "temp", float), ("top_p", "top_p", float), ("top_k", "top_k", int), ("repetition_penalty", "repetition_penalty", float))
+
+
+def _request_sampling(state, req):
+    """the optional request-level sampling fields (per_slot_sampling servers only; an extension, the reference's GenerateRequest has none)
+    -> (SamplingArgs or None, seed or None)"""
+    if not getattr(state.scheduler, "per_slot_sampling", False):
+        return None, None
+    sa, d = None, state.lm.default_sampling_args
+    if any(req.get(k) is not None for k, _, _ in _REQ_SAMPLING):
+        kw = {name: conv(req[k]) if req.get(k) is not None else getattr(d, name) for k, name, conv in _REQ_SAMPLING}
+        if not (kw["temp"] >= 0.0) or kw["top_k"] < 0 or not (kw["repetition_penalty"] > 0.0):
+            raise AppError("temperature and top_k must not be negative, repetition_penalty must be positive")
+        sa = SamplingArgs(**kw)
+    seed = req.get("seed")
+    if seed is not None:
+        seed = int(seed)
+        if not 0 <= seed < 2**64:
+            raise AppError("seed must fit an unsigned 64-bit integer")
+    return sa, seed
+
+
 def generate_speech(state, req):
     """POST /v1/audio/speech -> (status, content_type, body bytes | iterator of bytes)"""
     for k in ("model", "voice", "input"):
@@ -429,13 +506,21 @@ def generate_speech(state, req):
         # like the reference (speech.rs:72-96) chunks are batched only when the request asks for it (`batch_size` > 1): the batch paths sample
         # with BatchedLogitsProcessor semantics and no repetition penalty, so what a client hears must not depend on the server's load.
         # `auto_batch` (server option, off by default) lets every chunk join the continuous-batching session when other work is in flight.
-        want_batch = int(req.get("batch_size") or 1) > 1 or getattr(state, "auto_batch", False)
-        futs = [state.scheduler.submit(cond, b, n_cond, state.lm.max_batch > 1 and want_batch) for b in bodies]
+        # With per_slot_sampling a session slot samples like the batch-1 path (own stream, repetition penalty), so every chunk may join.
+        sa, seed = _request_sampling(state, req)
+        per_slot = getattr(state.scheduler, "per_slot_sampling", False)
+        want_batch = int(req.get("batch_size") or 1) > 1 or getattr(state, "auto_batch", False) or per_slot
+        if sa is None and seed is None:
+            futs = [state.scheduler.submit(cond, b, n_cond, state.lm.max_batch > 1 and want_batch) for b in bodies]
+        else:  # (chunk i of a seeded request draws from seed + i, as fishrt.lm.LM does)
+            futs = [state.scheduler.submit(cond, b, n_cond, state.lm.max_batch > 1 and want_batch, sampling=sa,
+                                           seed=None if seed is None else (seed + i) & (2**64 - 1)) for i, b in enumerate(bodies)]
 
         def pcm_chunks():
             for f in futs:
                 codes = f.result()
-                pcm = state.codec.decode(np.ascontiguousarray(codes[None]))[0, 0]  # (an out-of-range code is an error, as in the reference)
+                with state.codec_lock:
+                    pcm = state.codec.decode(np.ascontiguousarray(codes[None]))[0, 0]  # (an out-of-range code is an error, as in the reference)
                 yield pcm
 
         if fmt == "pcm":  # extension: chunked little-endian s16 PCM at the codec rate, one HTTP chunk per text chunk

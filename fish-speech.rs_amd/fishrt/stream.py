@@ -184,17 +184,24 @@ class SessionStreamer:
     def __exit__(self, *exc):
         self.close()
 
-    def add(self, prompt, max_new_tokens, tag=None, prefix=None):
+    def add(self, prompt, max_new_tokens, tag=None, prefix=None, sampling=None, seed=None):
         """admit a request: -> its session slot, or None when the session is full (nothing is opened then).  tag: the name its audio and
         stats are reported under (default: the admission number 0, 1, 2, ...).  prefix: a Session.add_prefix id -- `prompt` is then the
-        request's body (Session.add)"""
+        request's body (Session.add).  sampling / seed: the request's own sampler settings / seed (Session.add; per_slot and rows sessions)"""
         if tag is None:
             tag = self._admitted
         if tag in self.stats:
             raise ValueError(f"tag {tag!r} is already in use")
         sid = self.codec.streams_open()
         try:
-            slot = self.session.add(prompt, max_new_tokens) if prefix is None else self.session.add(prompt, max_new_tokens, prefix=prefix)
+            kw = {}
+            if prefix is not None:
+                kw["prefix"] = prefix
+            if sampling is not None:
+                kw["sampling"] = sampling
+            if seed is not None:
+                kw["seed"] = seed
+            slot = self.session.add(prompt, max_new_tokens, **kw)
         except BaseException:
             self.codec.streams_close(sid)
             raise

@@ -273,7 +273,26 @@ int fs_comm_all_gather_codes(fs_comm_t* comm, const uint32_t* codes, const int32
  * frames; a decode frame costs one slow launch for all slots + one fast launch per 4 slots instead of the 373-node step.  bf16 Fish-1.5
  * handles with 2 <= max_batch <= 8, greedy or 0 < top_k <= 256; the device's persistent kernels are held for the session's lifetime. */
 #define FS_SESSION_ROWS 8u
-int fs_lm_session_begin(fs_lm_t* lm, const fs_sampling* sampling, uint64_t seed, uint32_t flags /* FS_GEN_IGNORE_EOS | FS_SESSION_ROWS */);
+/* FS_SESSION_PER_SLOT: what a slot samples depends on the REQUEST, not on the session, at every max_batch and on every handle type
+ * sessions take (bf16 / fp8, Fish 1.5 token layout, max_batch <= 256).  The session runs on the static-batch step exactly as without the
+ * flag -- same GEMM / attention nodes, prefill, paging, prefixes, poll / release / info, slot lifetime (1 + max(0, max_new_tokens - L + 1)
+ * iterations, frame 0 emitted unconditionally, stop at <|im_end|> / budget / max_seq_len, FS_GEN_IGNORE_EOS) -- but each of a frame's 9
+ * decisions is that of the slot's OWN fs_lm_generate call (generate/single_batch.rs:102-210, sampling/mod.rs:51-75, rep_pen.rs:4-72):
+ *   - one StdRng stream per slot, seeded when the slot is activated, words consumed in decision order (slow, c0..c7 per frame);
+ *   - repetition penalty per codebook: the 16-deep window and mask of the reference's RepPenState, applied from the slot's second frame
+ *     on, logits divided by the mask whatever their sign, reset when a slot is (re)activated;
+ *   - LogitsProcessor rules: greedy iff temp == 0 with the batch-1 tie rule (the last maximal index), top-p compared in f32, and when the
+ *     slow token is <|im_end|> the codebook decisions are skipped (codes 0) and draw nothing;
+ *   - the slot's own settings and seed (fs_lm_session_add_ex), else the session's settings and `seed + the slot's admission number`.
+ * So a slot's codes do not depend on its slot index, on max_batch or on what the other slots do; against its own fs_lm_generate call
+ * they can differ only where two candidates are within rounding of each other (the row path and the batch-1 kernels sum in different
+ * orders).  Settings accepted per slot and for the session: greedy (temp == 0), or temp > 0 with 0 < top_k <= 256 -- the limit of the
+ * in-launch samplers (see fs_lm_generate); anything else is an error from fs_lm_session_begin / fs_lm_session_add_ex, never another
+ * sampler.  About 40 KB of device memory per slot; the step has as many graph nodes as the lock-step one (one fewer when sampling).
+ * FS_SESSION_PER_SLOT | FS_SESSION_ROWS is an error.  fs_lm_debug_capture records the head's RAW logits (before the penalty; <|im_end|>
+ * masked under FS_GEN_IGNORE_EOS) and the picks of every slot, readable with fs_lm_debug_read_row(slot). */
+#define FS_SESSION_PER_SLOT 16u
+int fs_lm_session_begin(fs_lm_t* lm, const fs_sampling* sampling, uint64_t seed, uint32_t flags /* FS_GEN_IGNORE_EOS | FS_SESSION_ROWS | FS_SESSION_PER_SLOT */);
 /* prompt u32 [C+1, L] row-major (copied); *slot = the slot taken, or -1 when all max_batch slots are busy or the KV page pool cannot hold
  * the request right now (not an error: retry after a release).  Returns once the
  * prefill is enqueued (one prefill in flight: a second add first waits for the previous one); the slot starts generating in a later step */
@@ -298,6 +317,18 @@ int fs_lm_session_prefix_release(fs_lm_t* lm, int prefix_id);
  * L = P + L_body, max_seq_len rule, admission number -> rows-mode sampler seed, frame-0 rule, EOS, budget), except that only the
  * L_body - 1 body positions are prefilled.  body u32 [C+1, L_body], L_body >= 1. */
 int fs_lm_session_add_prefixed(fs_lm_t* lm, int prefix_id, const uint32_t* body, int L_body, int max_new_tokens, int* slot);
+/* An add whose slot samples with its own settings and / or sampler seed.  prefix_id < 0: `prompt` u32 [C+1, L] is the whole prompt
+ * (== fs_lm_session_add); prefix_id >= 0: it is the body on that prefix (== fs_lm_session_add_prefixed).  sampling NULL: the session's
+ * settings; seed NULL: session seed + the slot's admission number.  With both NULL this is exactly the plain call, in every session.
+ *   FS_SESSION_PER_SLOT sessions: any settings inside the limit stated there (else an error that names it).
+ *   FS_SESSION_ROWS sessions: the row kernels read one setting and one stream per row already; the slot's settings must stay inside what
+ *     fs_lm_rows_supported accepts together with the session's (all greedy or all sampled with 0 < top_k <= 256), else an error.
+ *   plain sessions: a non-NULL sampling or seed is an error -- the lock-step sampler has no per-slot notion and keeps its outputs.
+ * A slot admitted with a seed of its own is prefilled in a pass of its own (a group pass of several joining prompts rounds differently
+ * from a single one), so its codes are a function of (prompt, budget, settings, seed) alone -- not of what was queued with it.
+ * *slot = -1 when no slot / KV pages are free right now, as fs_lm_session_add. */
+int fs_lm_session_add_ex(fs_lm_t* lm, int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling,
+                         const uint64_t* seed, int* slot);
 /* out[8] = {free pages, pages referenced by more than one owner, live prefixes, prefill passes, tokens prefilled,
  *           prefix tokens reused, tail pages copied, prefill-stream microseconds (HIP events around each pass)};
  * counters since fs_lm_session_begin */
