@@ -45,14 +45,14 @@ size_t codec_pack_bf3_elems(int Cin, int K, int Cout, bool f16);
 void codec_pack_bf3(const float* relaid, uint16_t* dst, int Cin, int K, int Cout, bool f16, hipStream_t st);
 void codec_conv1d_bf3(const float* x, const uint16_t* xp, int B, int Cin, int T, const uint16_t* wp, bool f16, const float* bias, int Cout, int K,
                       int dil, bool pre_silu, int epi, const float* res, const float* gamma, float* y, uint16_t* yp, bool post_silu, int ps,
-                      hipStream_t st, const uint16_t* ctx_in, uint16_t* ctx_out, const float* mean_a, const float* mean_b, const long long* ctx_off);
+                      hipStream_t st, const uint16_t* ctx_in, uint16_t* ctx_out, const float* mean_a, const float* mean_b, const long long* ctx_off, CtxLen rl);
 void codec_respair_f16(const uint16_t* xp, int B, int C, int T, const uint16_t* w1p, const float* b1, const uint16_t* w2p, const float* b2, int K, int dil,
                        const float* res, float* y, uint16_t* yp, hipStream_t st, const uint16_t* mid_ctx_in, uint16_t* mid_ctx_out,
-                       const uint16_t* ctx_in, uint16_t* ctx_out, const float* mean_a, const float* mean_b, const long long* ctx_off);
+                       const uint16_t* ctx_in, uint16_t* ctx_out, const float* mean_a, const float* mean_b, const long long* ctx_off, CtxLen rl);
 void codec_act_split(const float* x, int B, int C, int T, bool silu, uint16_t* planes, bool f16, hipStream_t st, const uint16_t* ctx_in, uint16_t* ctx_out,
-                     const long long* ctx_off);
+                     const long long* ctx_off, CtxLen rl);
 void codec_mean3_planes(const float* a, const float* b, const float* c, int B, int C, int T, bool silu, uint16_t* planes, bool f16, hipStream_t st,
-                        const uint16_t* ctx_in, uint16_t* ctx_out, const long long* ctx_off);
+                        const uint16_t* ctx_in, uint16_t* ctx_out, const long long* ctx_off, CtxLen rl);
 void codec_range_reset(hipStream_t st);
 void codec_range_read(unsigned long long* out2, hipStream_t st);
 }  // namespace c3chk
@@ -168,9 +168,15 @@ __device__ unsigned long long g_c3prof[8];
 // before it is stored / split, so the third block's f32 output and the mean kernel's three reads never touch memory.
 // Multi-stream decoding (fs_codec_streams_*): the items of a launch are chunks of different streams, each with its own contexts -- item z reads
 // its context at ci + off[2z] and writes it at co + off[2z + 1] (u16 element offsets into the engine's context pool; off null: one stream).
+// Ragged items (fs_codec_streams_decode_ragged): `len` = per-item lengths in code frames, `per` = slots of this tensor per frame.  Item z's
+// own data ends at slot Te = len[z] * per of the launch extent T, and its new context is the PP slots that END there: slot j of `co` is slot
+// Te - PP + j of the item where that is >= 0 (written by the thread that produces the slot) and slot j + Te of `ci` where it is not (copied by
+// the block that fills the row's padding).  ci and co are the two halves of a ping-pong pair, so the copy needs no ordering.  len null: Te = T.
 struct PlaneCtx {
     const uint16_t* ci; uint16_t* co; const float* mean_a = nullptr; const float* mean_b = nullptr; const long long* off = nullptr;
+    const long long* len = nullptr; int per = 0;
 };
+__device__ __forceinline__ int c3_item_end(const PlaneCtx& pc, int z, int T) { return pc.len ? (int)pc.len[z] * pc.per : T; }
 __device__ __forceinline__ PlaneCtx c3_item_ctx(PlaneCtx pc, int z) {
     if (pc.off) {
         if (pc.ci) pc.ci += pc.off[2 * z];
@@ -189,6 +195,19 @@ __device__ __forceinline__ void c3_zero_pad(uint16_t* pb, int CG, int T, int g_f
                 ci ? *reinterpret_cast<const u32x4*>(ci + ((size_t)(part * CG + g) * PP + slot) * 8) : z;
     }
 }
+// ragged items shorter than the context (Te < PP): the front PP - Te slots of the new context are the old context shifted by Te
+template <bool F16>
+__device__ __forceinline__ void c3_shift_ctx(const uint16_t* ci, uint16_t* co, int CG, int Te, int g_first, int n_groups, int tid, int nthreads) {
+    constexpr int NP = F16 ? 1 : 2;
+    if (!co || Te >= PP) return;
+    const u32x4 z{0u, 0u, 0u, 0u};
+    for (int e = tid; e < n_groups * NP * PP; e += nthreads) {
+        const int slot = e % PP, gp = e / PP, g = g_first + gp / NP, part = gp % NP;
+        if (g < CG && slot + Te < PP)
+            *reinterpret_cast<u32x4*>(co + ((size_t)(part * CG + g) * PP + slot) * 8) =
+                ci ? *reinterpret_cast<const u32x4*>(ci + ((size_t)(part * CG + g) * PP + slot + Te) * 8) : z;
+    }
+}
 
 // f32 (C, T) -> planes, optional SiLU.  One thread per (8-channel group, t).
 template <bool F16>
@@ -197,7 +216,11 @@ __global__ void k_act_split(const float* __restrict__ x, int C, int T, int silu,
     const int t = blockIdx.x * blockDim.x + threadIdx.x, g = blockIdx.y, CG = C >> 3;
     const float* xb = x + (size_t)blockIdx.z * C * T;
     uint16_t* pb = planes + (size_t)blockIdx.z * (F16 ? 1 : 2) * CG * (PP + T) * 8;
-    if (blockIdx.x == 0) c3_zero_pad<F16>(pb, CG, T, g, 1, threadIdx.x, blockDim.x, pc.ci);
+    const int Te = c3_item_end(pc, blockIdx.z, T);
+    if (blockIdx.x == 0) {
+        c3_zero_pad<F16>(pb, CG, T, g, 1, threadIdx.x, blockDim.x, pc.ci);
+        if (pc.len) c3_shift_ctx<F16>(pc.ci, pc.co, CG, Te, g, 1, threadIdx.x, blockDim.x);
+    }
     if (t >= T) return;
     u32x4 vh, vl;
 #pragma unroll
@@ -210,9 +233,9 @@ __global__ void k_act_split(const float* __restrict__ x, int C, int T, int silu,
     }
     *reinterpret_cast<u32x4*>(pb + ((size_t)g * (PP + T) + PP + t) * 8) = vh;
     if constexpr (!F16) *reinterpret_cast<u32x4*>(pb + ((size_t)(CG + g) * (PP + T) + PP + t) * 8) = vl;
-    if (pc.co && t >= T - PP) {
-        *reinterpret_cast<u32x4*>(pc.co + ((size_t)g * PP + (t - (T - PP))) * 8) = vh;
-        if constexpr (!F16) *reinterpret_cast<u32x4*>(pc.co + ((size_t)(CG + g) * PP + (t - (T - PP))) * 8) = vl;
+    if (pc.co && t >= Te - PP && t < Te) {
+        *reinterpret_cast<u32x4*>(pc.co + ((size_t)g * PP + (t - (Te - PP))) * 8) = vh;
+        if constexpr (!F16) *reinterpret_cast<u32x4*>(pc.co + ((size_t)(CG + g) * PP + (t - (Te - PP))) * 8) = vl;
     }
 }
 
@@ -224,7 +247,11 @@ __global__ void k_mean3_planes(const float* __restrict__ a, const float* __restr
     const int t = blockIdx.x * blockDim.x + threadIdx.x, g = blockIdx.y, CG = C >> 3;
     const size_t boff = (size_t)blockIdx.z * C * T;
     uint16_t* pb = planes + (size_t)blockIdx.z * (F16 ? 1 : 2) * CG * (PP + T) * 8;
-    if (blockIdx.x == 0) c3_zero_pad<F16>(pb, CG, T, g, 1, threadIdx.x, blockDim.x, pc.ci);
+    const int Te = c3_item_end(pc, blockIdx.z, T);
+    if (blockIdx.x == 0) {
+        c3_zero_pad<F16>(pb, CG, T, g, 1, threadIdx.x, blockDim.x, pc.ci);
+        if (pc.len) c3_shift_ctx<F16>(pc.ci, pc.co, CG, Te, g, 1, threadIdx.x, blockDim.x);
+    }
     if (t >= T) return;
     const float third = (float)(1.0 / 3.0);
     u32x4 vh, vl;
@@ -239,9 +266,9 @@ __global__ void k_mean3_planes(const float* __restrict__ a, const float* __restr
     }
     *reinterpret_cast<u32x4*>(pb + ((size_t)g * (PP + T) + PP + t) * 8) = vh;
     if constexpr (!F16) *reinterpret_cast<u32x4*>(pb + ((size_t)(CG + g) * (PP + T) + PP + t) * 8) = vl;
-    if (pc.co && t >= T - PP) {
-        *reinterpret_cast<u32x4*>(pc.co + ((size_t)g * PP + (t - (T - PP))) * 8) = vh;
-        if constexpr (!F16) *reinterpret_cast<u32x4*>(pc.co + ((size_t)(CG + g) * PP + (t - (T - PP))) * 8) = vl;
+    if (pc.co && t >= Te - PP && t < Te) {
+        *reinterpret_cast<u32x4*>(pc.co + ((size_t)g * PP + (t - (Te - PP))) * 8) = vh;
+        if constexpr (!F16) *reinterpret_cast<u32x4*>(pc.co + ((size_t)(CG + g) * PP + (t - (Te - PP))) * 8) = vl;
     }
 }
 
@@ -256,7 +283,7 @@ __global__ void k_mean3_planes(const float* __restrict__ a, const float* __restr
 template <bool F16, int NT, int E, bool PS1>
 __device__ __forceinline__ void c3_epilogue_k(const f32x16 (&acc)[NT], int ob, int tbase, int h, int c, int Cout, int T, int ps,
                                               const float* __restrict__ bias, const float* __restrict__ res, const float* __restrict__ gamma,
-                                              float* __restrict__ y, uint16_t* __restrict__ ypb, int post_silu, uint16_t* __restrict__ yco = nullptr,
+                                              float* __restrict__ y, uint16_t* __restrict__ ypb, int post_silu, uint16_t* __restrict__ yco, int Te,
                                               const float* __restrict__ m0 = nullptr, const float* __restrict__ m1 = nullptr) {
     constexpr bool RES = E == CODEC_EPI_RES || E == CODEC_EPI_GAMMA_RES;
     const bool mean3 = E == CODEC_EPI_RES && m0 != nullptr;  // (uniform: a kernel argument)
@@ -310,8 +337,8 @@ __device__ __forceinline__ void c3_epilogue_k(const f32x16 (&acc)[NT], int ob, i
                 *reinterpret_cast<uint2*>(d) = make_uint2(hi[0] | (hi[1] << 16), hi[2] | (hi[3] << 16));
                 if constexpr (!F16)
                     *reinterpret_cast<uint2*>(d + (size_t)CGo * (PP + T) * 8) = make_uint2(lo[0] | (lo[1] << 16), lo[2] | (lo[3] << 16));
-                if (yco && t >= T - PP) {  // streaming: the last PP slots are the next chunk's left context
-                    uint16_t* dc = yco + ((size_t)(ob8 >> 3) * PP + (t - (T - PP))) * 8 + h * 4;
+                if (yco && t >= Te - PP && t < Te) {  // streaming: the last PP slots (of the item: Te <= T) are the next chunk's left context
+                    uint16_t* dc = yco + ((size_t)(ob8 >> 3) * PP + (t - (Te - PP))) * 8 + h * 4;
                     *reinterpret_cast<uint2*>(dc) = make_uint2(hi[0] | (hi[1] << 16), hi[2] | (hi[3] << 16));
                     if constexpr (!F16) *reinterpret_cast<uint2*>(dc + (size_t)CGo * PP * 8) = make_uint2(lo[0] | (lo[1] << 16), lo[2] | (lo[3] << 16));
                 }
@@ -327,16 +354,16 @@ template <bool F16, int NT, int EPI = -1, bool PS1 = false>
 __device__ __forceinline__ void c3_epilogue(const f32x16 (&acc)[NT], int ob, int tbase, int h, int c, int Cout, int T, int ps,
                                             const float* __restrict__ bias, int epi, const float* __restrict__ res,
                                             const float* __restrict__ gamma, float* __restrict__ y, uint16_t* __restrict__ ypb,
-                                            int post_silu, uint16_t* __restrict__ yco = nullptr, const float* __restrict__ m0 = nullptr,
+                                            int post_silu, uint16_t* __restrict__ yco, int Te, const float* __restrict__ m0 = nullptr,
                                             const float* __restrict__ m1 = nullptr) {
     if constexpr (EPI >= 0) {
-        c3_epilogue_k<F16, NT, EPI, PS1>(acc, ob, tbase, h, c, Cout, T, ps, bias, res, gamma, y, ypb, post_silu, yco, m0, m1);
+        c3_epilogue_k<F16, NT, EPI, PS1>(acc, ob, tbase, h, c, Cout, T, ps, bias, res, gamma, y, ypb, post_silu, yco, Te, m0, m1);
     } else {
-        if (epi == CODEC_EPI_GELU) c3_epilogue_k<F16, NT, CODEC_EPI_GELU, false>(acc, ob, tbase, h, c, Cout, T, ps, bias, res, gamma, y, ypb, post_silu, yco);
-        else if (epi == CODEC_EPI_GAMMA_RES) c3_epilogue_k<F16, NT, CODEC_EPI_GAMMA_RES, false>(acc, ob, tbase, h, c, Cout, T, ps, bias, res, gamma, y, ypb, post_silu, yco);
-        else if (epi == CODEC_EPI_RES) c3_epilogue_k<F16, NT, CODEC_EPI_RES, false>(acc, ob, tbase, h, c, Cout, T, ps, bias, res, gamma, y, ypb, post_silu, yco, m0, m1);
-        else if (epi == CODEC_EPI_TANH) c3_epilogue_k<F16, NT, CODEC_EPI_TANH, false>(acc, ob, tbase, h, c, Cout, T, ps, bias, res, gamma, y, ypb, post_silu, yco);
-        else c3_epilogue_k<F16, NT, CODEC_EPI_NONE, false>(acc, ob, tbase, h, c, Cout, T, ps, bias, res, gamma, y, ypb, post_silu, yco);
+        if (epi == CODEC_EPI_GELU) c3_epilogue_k<F16, NT, CODEC_EPI_GELU, false>(acc, ob, tbase, h, c, Cout, T, ps, bias, res, gamma, y, ypb, post_silu, yco, Te);
+        else if (epi == CODEC_EPI_GAMMA_RES) c3_epilogue_k<F16, NT, CODEC_EPI_GAMMA_RES, false>(acc, ob, tbase, h, c, Cout, T, ps, bias, res, gamma, y, ypb, post_silu, yco, Te);
+        else if (epi == CODEC_EPI_RES) c3_epilogue_k<F16, NT, CODEC_EPI_RES, false>(acc, ob, tbase, h, c, Cout, T, ps, bias, res, gamma, y, ypb, post_silu, yco, Te, m0, m1);
+        else if (epi == CODEC_EPI_TANH) c3_epilogue_k<F16, NT, CODEC_EPI_TANH, false>(acc, ob, tbase, h, c, Cout, T, ps, bias, res, gamma, y, ypb, post_silu, yco, Te);
+        else c3_epilogue_k<F16, NT, CODEC_EPI_NONE, false>(acc, ob, tbase, h, c, Cout, T, ps, bias, res, gamma, y, ypb, post_silu, yco, Te);
     }
 }
 
@@ -465,8 +492,9 @@ __global__ __launch_bounds__(256) void k_conv1d_bf3(const float* __restrict__ x,
         const PlaneCtx pcb = c3_item_ctx(pc, blockIdx.z);
         uint16_t* ypb = yp ? yp + (size_t)blockIdx.z * (F16 ? 1 : 2) * (Cout >> 3) * (PP + T) * 8 : nullptr;
         if (ypb && t0 == 0) c3_zero_pad<F16>(ypb, Cout >> 3, T, o0 >> 3, OT / 8, tid, 256, pcb.ci);
+        // (no ragged items here: the f32-input conv is not part of the streams' plane data flow, the launcher refuses a length table)
         c3_epilogue<F16, NT>(acc, o0 + ob, t0 + tb, h, c, Cout, T, ps, bias, epi, res ? res + boff_out : nullptr, gamma, y ? y + boff_out : nullptr,
-                        ypb, post_silu, ypb ? pcb.co : nullptr);
+                        ypb, post_silu, ypb ? pcb.co : nullptr, T);
     }
 }
 
@@ -568,9 +596,13 @@ __global__ __launch_bounds__(256, F16 ? 3 : 2) void k_conv1d_bf3p(const uint16_t
     }
     pc = c3_item_ctx(pc, blockIdx.z);  // (here, not at the top: nothing of it is live across the main loop)
     uint16_t* ypb = yp ? yp + (size_t)blockIdx.z * NPART * (Cout >> 3) * row * 8 : nullptr;
-    if (ypb && t0 == 0) c3_zero_pad<F16>(ypb, Cout >> 3, T, o0 >> 3, OT / 8, tid, 256, pc.ci);
+    const int Te = c3_item_end(pc, blockIdx.z, T);
+    if (ypb && t0 == 0) {
+        c3_zero_pad<F16>(ypb, Cout >> 3, T, o0 >> 3, OT / 8, tid, 256, pc.ci);
+        if (pc.len) c3_shift_ctx<F16>(pc.ci, pc.co, Cout >> 3, Te, o0 >> 3, OT / 8, tid, 256);
+    }
     c3_epilogue<F16, NT, EPI, PS1>(acc, o0 + ob, t0 + tb, h, c, Cout, T, ps, bias, epi, res ? res + boff_out : nullptr, gamma,
-                              y ? y + boff_out : nullptr, ypb, post_silu, ypb ? pc.co : nullptr, pc.mean_a ? pc.mean_a + boff_out : nullptr,
+                              y ? y + boff_out : nullptr, ypb, post_silu, ypb ? pc.co : nullptr, Te, pc.mean_a ? pc.mean_a + boff_out : nullptr,
                               pc.mean_a ? pc.mean_b + boff_out : nullptr);
     C3_TICK(5);
 #ifdef FS_C3_PROF
@@ -606,7 +638,11 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void k_conv1d_bf3t(const uint
     const u32x4* xpb = reinterpret_cast<const u32x4*>(xp) + (size_t)blockIdx.z * NPART * CGi * row + PP - halo + c;
     const size_t boff_out = (size_t)blockIdx.z * Cout * T;
     uint16_t* ypb = yp ? yp + (size_t)blockIdx.z * NPART * (Cout >> 3) * row * 8 : nullptr;
-    if (ypb && blockIdx.x == 0) c3_zero_pad<F16>(ypb, Cout >> 3, T, o0 >> 3, 4, tid, 256, pc.ci);
+    const int Te = c3_item_end(pc, blockIdx.z, T);
+    if (ypb && blockIdx.x == 0) {
+        c3_zero_pad<F16>(ypb, Cout >> 3, T, o0 >> 3, 4, tid, 256, pc.ci);
+        if (pc.len) c3_shift_ctx<F16>(pc.ci, pc.co, Cout >> 3, Te, o0 >> 3, 4, tid, 256);
+    }
     for (int wt = blockIdx.x * 4 + wave; wt < nwt; wt += gridDim.x * 4) {
         const int t0 = wt * (32 * NT);
         f32x16 acc[NT];
@@ -640,7 +676,7 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void k_conv1d_bf3t(const uint
         int Tl = T;  // opaque per tile: keeps the epilogue's ~100 row addresses from being hoisted out of the tile loop (200+ VGPRs)
         asm volatile("" : "+s"(Tl));
         c3_epilogue<F16, NT, EPI, PS1>(acc, o0, t0, h, c, Cout, Tl, ps, bias, epi, res ? res + boff_out : nullptr, gamma, y ? y + boff_out : nullptr,
-                                  ypb, post_silu, ypb ? pc.co : nullptr, pc.mean_a ? pc.mean_a + boff_out : nullptr,
+                                  ypb, post_silu, ypb ? pc.co : nullptr, Te, pc.mean_a ? pc.mean_a + boff_out : nullptr,
                                   pc.mean_a ? pc.mean_b + boff_out : nullptr);
     }
 }
@@ -654,7 +690,8 @@ __global__ __launch_bounds__(256, NT == 1 ? 3 : 2) void k_conv1d_bf3t(const uint
 // products in the same order as the two separate kernels: bit-identical output.  Per pair the planes of the intermediate (one write + one
 // read of C x T x 2 bytes) and one launch disappear: 8 -> 6 plane-passes of HBM traffic on convs that are bandwidth-bound.
 // Positions in front of the signal (t < 0) take the intermediate's streaming context (or zeros); the wave that owns t in [T - PP, T) saves it.
-template <int K, int NIB, int NTO, int NH, int NW>
+// RAG: ragged items (PlaneCtx::len) -- an instantiation of its own, so that the uniform paths keep their registers.
+template <int K, int NIB, int NTO, int NH, int NW, bool RAG = false>
 __global__ __launch_bounds__(NW * 64) void k_respair_f16t(const uint16_t* __restrict__ xp, int T, const uint16_t* __restrict__ w1p, const uint16_t* __restrict__ w2p,
                                                    int Cp, const float* __restrict__ b1, const float* __restrict__ b2, int dil, const float* __restrict__ res,
                                                    float* __restrict__ y, uint16_t* __restrict__ yp, int nwt, PlaneCtx pc, const uint16_t* __restrict__ mci,
@@ -683,6 +720,15 @@ __global__ __launch_bounds__(NW * 64) void k_respair_f16t(const uint16_t* __rest
     const size_t boff = (size_t)blockIdx.z * C * T;
     uint16_t* ypb = yp ? yp + (size_t)blockIdx.z * CG * row * 8 : nullptr;
     if (ypb && blockIdx.x == 0) c3_zero_pad<true>(ypb, CG, T, 0, CG, tid, NW * 64, pc.ci);
+    int Tend = T;
+    if constexpr (RAG) {
+        Tend = c3_item_end(pc, blockIdx.z, T);
+        if (blockIdx.x == 0) {  // an item shorter than the context: shift the old contexts of the output (if any) and of the intermediate
+            if (ypb) c3_shift_ctx<true>(pc.ci, pc.co, CG, Tend, 0, CG, tid, NW * 64);
+            c3_shift_ctx<true>(mci, mco, CG, Tend, 0, CG, tid, NW * 64);
+        }
+    }
+    const int Te = Tend;
     float bv1[4 * CG > 16 ? 16 : 4 * CG];
 #pragma unroll
     for (int r = 0; r < 4 * CG; ++r) bv1[r] = b1[(r >> 2) * 8 + h * 4 + (r & 3)];
@@ -732,8 +778,8 @@ __global__ __launch_bounds__(NW * 64) void k_respair_f16t(const uint16_t* __rest
                         if (mci && s >= -PP) v = *reinterpret_cast<const uint2*>(mci + ((size_t)q4 * PP + (PP + s)) * 8 + h * 4);
                     }
                     *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(hs + (size_t)q4 * HS + 32 * j + c) + h * 4) = v;
-                    if (mco && j >= NH && s >= T - PP && s < T)
-                        *reinterpret_cast<uint2*>(mco + ((size_t)q4 * PP + (s - (T - PP))) * 8 + h * 4) = v;
+                    if (mco && j >= NH && s >= Te - PP && s < Te)
+                        *reinterpret_cast<uint2*>(mco + ((size_t)q4 * PP + (s - (Te - PP))) * 8 + h * 4) = v;
                 }
             }
         }
@@ -760,7 +806,7 @@ __global__ __launch_bounds__(NW * 64) void k_respair_f16t(const uint16_t* __rest
         int Tl = T;
         asm volatile("" : "+s"(Tl));
         c3_epilogue<true, NTO, CODEC_EPI_RES, true>(acc2, 0, t0, h, c, C, Tl, 1, b2, CODEC_EPI_RES, res + boff, nullptr, y ? y + boff : nullptr, ypb, 1,
-                                                  ypb ? pc.co : nullptr, pc.mean_a ? pc.mean_a + boff : nullptr, pc.mean_a ? pc.mean_b + boff : nullptr);
+                                                  ypb ? pc.co : nullptr, RAG ? Te : Tl, pc.mean_a ? pc.mean_a + boff : nullptr, pc.mean_a ? pc.mean_b + boff : nullptr);
     }
 }
 
@@ -791,12 +837,14 @@ template <bool F16>
 static void conv1d_bf3_impl(const float* x, const uint16_t* xp, int B, int Cin, int T, const uint16_t* wp, const float* bias, int Cout, int K,
                             int dil, bool pre_silu, int epi, const float* res, const float* gamma, float* y, uint16_t* yp, bool post_silu, int ps,
                             hipStream_t st, const uint16_t* ctx_in, uint16_t* ctx_out, const float* mean_a, const float* mean_b,
-                            const long long* ctx_off) {
+                            const long long* ctx_off, CtxLen rl) {
     constexpr int NPL = F16 ? 2 : 4;
-    const PlaneCtx pc{ctx_in, ctx_out, mean_a, mean_b, ctx_off};
+    FS_REQUIRE(!rl.len || (xp && ctx_off && ctx_in && ctx_out && rl.frames >= 1 && T % rl.frames == 0),
+               "ragged items need a plane input, both context halves and per-item offsets");
+    const PlaneCtx pc{ctx_in, ctx_out, mean_a, mean_b, ctx_off, rl.len, rl.len ? T / rl.frames : 0};
     FS_REQUIRE((mean_a != nullptr) == (mean_b != nullptr) && (!mean_a || (xp && epi == CODEC_EPI_RES && ps == 1)),
                "the folded ParallelBlock mean needs both partners and a plane-input residual conv");
-    FS_REQUIRE((!ctx_in && !ctx_out) || (yp && (B == 1 || ctx_off) && T >= PP),
+    FS_REQUIRE((!ctx_in && !ctx_out) || (yp && (B == 1 || ctx_off) && (T >= PP || rl.len)),
                "streaming contexts need a plane output, one item (or per-item context offsets) and >= 64 samples per chunk");
     FS_REQUIRE(codec_conv1d_bf3_ok(Cin, Cout, K, dil), "conv shape outside the bf16x3 kernel's range");
     FS_REQUIRE((x != nullptr) != (xp != nullptr), "exactly one of the f32 input and the plane input");
@@ -940,12 +988,12 @@ static void conv1d_bf3_impl(const float* x, const uint16_t* xp, int B, int Cin, 
 
 void codec_conv1d_bf3(const float* x, const uint16_t* xp, int B, int Cin, int T, const uint16_t* wp, bool f16, const float* bias, int Cout, int K,
                       int dil, bool pre_silu, int epi, const float* res, const float* gamma, float* y, uint16_t* yp, bool post_silu, int ps,
-                      hipStream_t st, const uint16_t* ctx_in, uint16_t* ctx_out, const float* mean_a, const float* mean_b, const long long* ctx_off) {
+                      hipStream_t st, const uint16_t* ctx_in, uint16_t* ctx_out, const float* mean_a, const float* mean_b, const long long* ctx_off, CtxLen rl) {
 #ifndef FS_C3_CHECK
-    if (g_c3_checked) return c3chk::codec_conv1d_bf3(x, xp, B, Cin, T, wp, f16, bias, Cout, K, dil, pre_silu, epi, res, gamma, y, yp, post_silu, ps, st, ctx_in, ctx_out, mean_a, mean_b, ctx_off);
+    if (g_c3_checked) return c3chk::codec_conv1d_bf3(x, xp, B, Cin, T, wp, f16, bias, Cout, K, dil, pre_silu, epi, res, gamma, y, yp, post_silu, ps, st, ctx_in, ctx_out, mean_a, mean_b, ctx_off, rl);
 #endif
-    if (f16) conv1d_bf3_impl<true>(x, xp, B, Cin, T, wp, bias, Cout, K, dil, pre_silu, epi, res, gamma, y, yp, post_silu, ps, st, ctx_in, ctx_out, mean_a, mean_b, ctx_off);
-    else conv1d_bf3_impl<false>(x, xp, B, Cin, T, wp, bias, Cout, K, dil, pre_silu, epi, res, gamma, y, yp, post_silu, ps, st, ctx_in, ctx_out, mean_a, mean_b, ctx_off);
+    if (f16) conv1d_bf3_impl<true>(x, xp, B, Cin, T, wp, bias, Cout, K, dil, pre_silu, epi, res, gamma, y, yp, post_silu, ps, st, ctx_in, ctx_out, mean_a, mean_b, ctx_off, rl);
+    else conv1d_bf3_impl<false>(x, xp, B, Cin, T, wp, bias, Cout, K, dil, pre_silu, epi, res, gamma, y, yp, post_silu, ps, st, ctx_in, ctx_out, mean_a, mean_b, ctx_off, rl);
 }
 
 bool codec_respair_ok(int C, int K, int dil, bool f16) {
@@ -954,16 +1002,18 @@ bool codec_respair_ok(int C, int K, int dil, bool f16) {
 
 void codec_respair_f16(const uint16_t* xp, int B, int C, int T, const uint16_t* w1p, const float* b1, const uint16_t* w2p, const float* b2, int K, int dil,
                        const float* res, float* y, uint16_t* yp, hipStream_t st, const uint16_t* mid_ctx_in, uint16_t* mid_ctx_out, const uint16_t* ctx_in,
-                       uint16_t* ctx_out, const float* mean_a, const float* mean_b, const long long* ctx_off) {
+                       uint16_t* ctx_out, const float* mean_a, const float* mean_b, const long long* ctx_off, CtxLen rl) {
 #ifndef FS_C3_CHECK
-    if (g_c3_checked) return c3chk::codec_respair_f16(xp, B, C, T, w1p, b1, w2p, b2, K, dil, res, y, yp, st, mid_ctx_in, mid_ctx_out, ctx_in, ctx_out, mean_a, mean_b, ctx_off);
+    if (g_c3_checked) return c3chk::codec_respair_f16(xp, B, C, T, w1p, b1, w2p, b2, K, dil, res, y, yp, st, mid_ctx_in, mid_ctx_out, ctx_in, ctx_out, mean_a, mean_b, ctx_off, rl);
 #endif
     FS_REQUIRE(codec_respair_ok(C, K, dil, true), "ResBlock pair outside the fused kernel's range");
     FS_REQUIRE(res && (y || yp), "the fused ResBlock pair needs the residual input and an output");
     FS_REQUIRE((mean_a != nullptr) == (mean_b != nullptr), "the folded ParallelBlock mean needs both partners");
-    FS_REQUIRE((!mid_ctx_in && !mid_ctx_out && !ctx_in && !ctx_out) || ((B == 1 || ctx_off) && T >= PP),
+    FS_REQUIRE((!mid_ctx_in && !mid_ctx_out && !ctx_in && !ctx_out) || ((B == 1 || ctx_off) && (T >= PP || rl.len)),
                "streaming contexts need one item (or per-item context offsets) and >= 64 samples per chunk");
-    const PlaneCtx pc{ctx_in, ctx_out, mean_a, mean_b, ctx_off};
+    FS_REQUIRE(!rl.len || (ctx_off && mid_ctx_in && mid_ctx_out && (ctx_in != nullptr) == (ctx_out != nullptr) && rl.frames >= 1 && T % rl.frames == 0),
+               "ragged items need both context halves and per-item offsets");
+    const PlaneCtx pc{ctx_in, ctx_out, mean_a, mean_b, ctx_off, rl.len, rl.len ? T / rl.frames : 0};
     const int Cp = 64, halo = (K - 1) * dil, nib = C / 16;
     constexpr int NTO = 4;
     const int nwt = (T + 32 * NTO - 1) / (32 * NTO);
@@ -980,7 +1030,10 @@ void codec_respair_f16(const uint16_t* xp, int B, int C, int T, const uint16_t* 
     };
 #define FS_PAIR(KK, NIBv, NWv)                                                    \
     do {                                                                          \
-        if (halo <= 32) go(k_respair_f16t<KK, NIBv, NTO, 1, NWv>, NWv, 1);        \
+        if (rl.len) {                                                             \
+            if (halo <= 32) go(k_respair_f16t<KK, NIBv, NTO, 1, NWv, true>, NWv, 1); \
+            else go(k_respair_f16t<KK, NIBv, NTO, 2, NWv, true>, NWv, 2);         \
+        } else if (halo <= 32) go(k_respair_f16t<KK, NIBv, NTO, 1, NWv>, NWv, 1); \
         else go(k_respair_f16t<KK, NIBv, NTO, 2, NWv>, NWv, 2);                   \
     } while (0)
     // waves per block (the two weight sets are shared by a block's waves; every wave owns 2 nib x 6 KB of scratch): tuning knobs
@@ -994,30 +1047,32 @@ void codec_respair_f16(const uint16_t* xp, int B, int C, int T, const uint16_t* 
 }
 
 void codec_act_split(const float* x, int B, int C, int T, bool silu, uint16_t* planes, bool f16, hipStream_t st, const uint16_t* ctx_in,
-                     uint16_t* ctx_out, const long long* ctx_off) {
+                     uint16_t* ctx_out, const long long* ctx_off, CtxLen rl) {
 #ifndef FS_C3_CHECK
-    if (g_c3_checked) return c3chk::codec_act_split(x, B, C, T, silu, planes, f16, st, ctx_in, ctx_out, ctx_off);
+    if (g_c3_checked) return c3chk::codec_act_split(x, B, C, T, silu, planes, f16, st, ctx_in, ctx_out, ctx_off, rl);
 #endif
     FS_REQUIRE(C % 8 == 0, "activation planes need a multiple of 8 channels");
-    FS_REQUIRE((!ctx_in && !ctx_out) || ((B == 1 || ctx_off) && T >= PP),
+    FS_REQUIRE((!ctx_in && !ctx_out) || ((B == 1 || ctx_off) && (T >= PP || rl.len)),
                "streaming contexts need one item (or per-item context offsets) and >= 64 samples per chunk");
+    FS_REQUIRE(!rl.len || (ctx_off && ctx_in && ctx_out && rl.frames >= 1 && T % rl.frames == 0), "ragged items need both context halves and per-item offsets");
     const dim3 grid((T + 255) / 256, C / 8, B);
-    const PlaneCtx pc{ctx_in, ctx_out, nullptr, nullptr, ctx_off};
+    const PlaneCtx pc{ctx_in, ctx_out, nullptr, nullptr, ctx_off, rl.len, rl.len ? T / rl.frames : 0};
     if (f16) hipLaunchKernelGGL(k_act_split<true>, grid, dim3(256), 0, st, x, C, T, silu ? 1 : 0, planes, pc);
     else hipLaunchKernelGGL(k_act_split<false>, grid, dim3(256), 0, st, x, C, T, silu ? 1 : 0, planes, pc);
     FS_HIP(hipGetLastError());
 }
 
 void codec_mean3_planes(const float* a, const float* b, const float* c, int B, int C, int T, bool silu, uint16_t* planes, bool f16,
-                        hipStream_t st, const uint16_t* ctx_in, uint16_t* ctx_out, const long long* ctx_off) {
+                        hipStream_t st, const uint16_t* ctx_in, uint16_t* ctx_out, const long long* ctx_off, CtxLen rl) {
 #ifndef FS_C3_CHECK
-    if (g_c3_checked) return c3chk::codec_mean3_planes(a, b, c, B, C, T, silu, planes, f16, st, ctx_in, ctx_out, ctx_off);
+    if (g_c3_checked) return c3chk::codec_mean3_planes(a, b, c, B, C, T, silu, planes, f16, st, ctx_in, ctx_out, ctx_off, rl);
 #endif
     FS_REQUIRE(C % 8 == 0, "activation planes need a multiple of 8 channels");
-    FS_REQUIRE((!ctx_in && !ctx_out) || ((B == 1 || ctx_off) && T >= PP),
+    FS_REQUIRE((!ctx_in && !ctx_out) || ((B == 1 || ctx_off) && (T >= PP || rl.len)),
                "streaming contexts need one item (or per-item context offsets) and >= 64 samples per chunk");
+    FS_REQUIRE(!rl.len || (ctx_off && ctx_in && ctx_out && rl.frames >= 1 && T % rl.frames == 0), "ragged items need both context halves and per-item offsets");
     const dim3 grid((T + 255) / 256, C / 8, B);
-    const PlaneCtx pc{ctx_in, ctx_out, nullptr, nullptr, ctx_off};
+    const PlaneCtx pc{ctx_in, ctx_out, nullptr, nullptr, ctx_off, rl.len, rl.len ? T / rl.frames : 0};
     if (f16) hipLaunchKernelGGL(k_mean3_planes<true>, grid, dim3(256), 0, st, a, b, c, C, T, silu ? 1 : 0, planes, pc);
     else hipLaunchKernelGGL(k_mean3_planes<false>, grid, dim3(256), 0, st, a, b, c, C, T, silu ? 1 : 0, planes, pc);
     FS_HIP(hipGetLastError());

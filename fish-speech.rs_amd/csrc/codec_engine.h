@@ -20,6 +20,8 @@ class CodecBase {
     virtual int streams_open() = 0;
     virtual void streams_close(int id) = 0;
     virtual void streams_decode(int n, const int* ids, const uint32_t* codes, int T, float* pcm_out) = 0;
+    // ragged: item i advances stream ids[i] by T[i] >= 1 frames; codes = the items' (8, T[i]) blocks concatenated, pcm_out = their PCM concatenated
+    virtual void streams_decode_ragged(int n, const int* ids, const int* T, const uint32_t* codes, float* pcm_out) = 0;
     virtual void encode(const float* pcm, int n, uint32_t* codes_out, size_t cap, size_t* L_out) = 0;
     virtual int sample_rate() = 0;
     virtual void set_precision(int mode) = 0;  // 0 = f32 (exact f32 products), 1 = bf16x3, 2 = f16 (default); decode only

@@ -264,27 +264,73 @@ class Codec final : public CodecBase {
             FS_REQUIRE(precision() == ms_[ids[b]].prec, "the precision mode changed since the stream was opened");
         }
         check_codes(codes, (size_t)n * 8 * T);
+        fill_offset_table(n, ids, 4);
+        run_streams(codes, n, T, pcm_out, kMulti);
+        for (int b = 0; b < n; ++b) ++ms_[ids[b]].chunk;  // only after the whole call went through
+    }
+    // per-call table, `rows` x n entries: element offsets of item b's (in, out) halves -- plane table (u16), then f32 table; the ragged call
+    // appends its lengths and PCM offsets (rows 4 and 5)
+    void fill_offset_table(int n, const int* ids, int rows) {
         const size_t pb = ms_stream_p_bytes() / 2, fb = ms_stream_f_bytes() / 2;  // bytes per half
-        ms_tab_.resize((size_t)4 * n);
-        for (int b = 0; b < n; ++b) {  // element offsets of item b's (in, out) halves: plane table (u16), then f32 table
+        ms_tab_.assign((size_t)rows * n, 0);
+        for (int b = 0; b < n; ++b) {
             const int s = ids[b], par = ms_[s].chunk & 1;
             ms_tab_[2 * b] = (long long)(((size_t)2 * s + par) * pb / 2);
             ms_tab_[2 * b + 1] = (long long)(((size_t)2 * s + (par ^ 1)) * pb / 2);
             ms_tab_[2 * n + 2 * b] = (long long)(((size_t)2 * s + par) * fb / 4);
             ms_tab_[2 * n + 2 * b + 1] = (long long)(((size_t)2 * s + (par ^ 1)) * fb / 4);
         }
+    }
+    void run_streams(const uint32_t* codes, int n, int T, float* pcm_out, int kind) {
         const bool chk = range_check_ && bf3_ && f16_;
         if (chk) {
             std::lock_guard<std::mutex> g(range_guard_mutex());
             codec_range_check(true); codec_range_reset(st_);
-            try { decode_impl(codes, n, T, pcm_out, kMulti); } catch (...) { codec_range_check(false); throw; }
+            try { decode_impl(codes, n, T, pcm_out, kind); } catch (...) { codec_range_check(false); throw; }
             codec_range_check(false);
             unsigned long long r[2] = {0, 0};
             codec_range_read(r, st_);
             range_act_[0] += r[0]; range_act_[1] += r[1];
         } else {
-            decode_impl(codes, n, T, pcm_out, kMulti);
+            decode_impl(codes, n, T, pcm_out, kind);
         }
+    }
+
+    // ---- ragged multi-stream call (fs_codec_streams_decode_ragged): item i = the next T[i] >= 1 frames of stream ids[i].  The items are laid
+    // out at the stride of the longest one (codes padded with index 0 behind an item's end) and run through the launch sequence of the uniform
+    // call; the length table travels with the offset table, and only the context saves and the final PCM gather read it (codec_kernels.h
+    // CtxLen): a context becomes the last PAD slots of (old context ++ the item's own slots), which is what a chunk of any length needs.
+    // Work grows with n x the longest item.
+    void streams_decode_ragged(int n, const int* ids, const int* T, const uint32_t* codes, float* pcm_out) override {
+        FS_REQUIRE(n >= 1 && n <= kMaxStreams, "fs_codec_streams_decode_ragged takes 1 .. 64 streams per call");
+        int Tmax = 0;
+        size_t total = 0;
+        for (int b = 0; b < n; ++b) {
+            FS_REQUIRE(T[b] >= 1, "a ragged chunk needs >= 1 frame");
+            FS_REQUIRE(T[b] <= (1 << 20), "a ragged chunk of more than 2^20 frames");
+            FS_REQUIRE(ids[b] >= 0 && ids[b] < (int)ms_.size() && ms_[ids[b]].chunk >= 0, "not an open stream id of this codec handle");
+            for (int a = 0; a < b; ++a) FS_REQUIRE(ids[a] != ids[b], "a stream id appears twice in one call");
+            FS_REQUIRE(precision() == ms_[ids[b]].prec, "the precision mode changed since the stream was opened");
+            Tmax = std::max(Tmax, T[b]);
+            total += (size_t)T[b];
+        }
+        check_codes(codes, total * 8);
+        // codes [n][8][Tmax], item b's rows filled up to T[b] (index 0 behind it: a valid code whose output nothing reads)
+        rag_codes_.assign((size_t)n * 8 * Tmax, 0u);
+        {
+            const uint32_t* src = codes;
+            for (int b = 0; b < n; ++b)
+                for (int g = 0; g < 8; ++g, src += T[b]) std::memcpy(rag_codes_.data() + ((size_t)b * 8 + g) * Tmax, src, sizeof(uint32_t) * T[b]);
+        }
+        fill_offset_table(n, ids, 6);
+        const long long spf = (long long)samples_per_frame();
+        long long at = 0;
+        for (int b = 0; b < n; ++b) {  // lengths in frames, then the items' sample offsets in the packed PCM
+            ms_tab_[(size_t)4 * n + b] = T[b];
+            ms_tab_[(size_t)5 * n + b] = at;
+            at += spf * T[b];
+        }
+        run_streams(rag_codes_.data(), n, Tmax, pcm_out, kRagged);
         for (int b = 0; b < n; ++b) ++ms_[ids[b]].chunk;  // only after the whole call went through
     }
 
@@ -298,42 +344,46 @@ class Codec final : public CodecBase {
             if (codes[i] >= 1000u) throw Error("FSQ index out of range (gather out of bounds)");
     }
 
-    enum { kOneShot = 0, kSingle = 1, kMulti = 2 };  // decode_impl's `streaming`: none, fs_codec_stream_*, fs_codec_streams_*
+    // decode_impl's `streaming`: none, fs_codec_stream_*, fs_codec_streams_decode, fs_codec_streams_decode_ragged (T = the longest item)
+    enum { kOneShot = 0, kSingle = 1, kMulti = 2, kRagged = 3 };
     void decode_impl(const uint32_t* codes, int B, int T, float* pcm_out, int streaming) {
         FS_HIP(hipSetDevice(device_));
         FS_REQUIRE(loaded_, "weights not loaded: call fs_codec_load_safetensors or fs_codec_load_synthetic first");
         FS_REQUIRE(B >= 1 && T >= 1, "empty input");
-        FS_REQUIRE(streaming != kMulti || ms_tab_.size() == (size_t)4 * B, "multi-stream offset table");
+        const bool multi = streaming >= kMulti, ragged = streaming == kRagged;
+        FS_REQUIRE(!multi || ms_tab_.size() == (size_t)(ragged ? 6 : 4) * B, "multi-stream offset table");
         use_bf3_now_ = bf3_;
         const int G = 8;
         check_codes(codes, (size_t)B * G * T);
         // streaming: context slot k of this chunk is read from the buffer the previous chunk wrote and written to the other one.  Multi-stream:
         // ci = co = slot k of stream 0's first half in the pool; the per-item table adds each item's (in, out) half
         const long long *tab_p = nullptr, *tab_f = nullptr;
-        if (streaming == kMulti) {
+        CtxLen rl;  // ragged: the per-item lengths, next to the offsets in the same upload
+        if (multi) {
             // stream-ordered upload; ms_tab_ stays untouched until the synchronisation at the end of this call
             dtab_.ensure(ms_tab_.size() * sizeof(long long));
             FS_HIP(hipMemcpyAsync(dtab_.p, ms_tab_.data(), ms_tab_.size() * sizeof(long long), hipMemcpyHostToDevice, st_));
             tab_p = (const long long*)dtab_.p;
             tab_f = tab_p + 2 * B;
+            if (ragged) rl = CtxLen{tab_p + 4 * B, T};
         }
         int slot = 0, fslot = 0;
-        struct PC { const uint16_t* ci; uint16_t* co; const long long* off; };
+        struct PC { const uint16_t* ci; uint16_t* co; const long long* off; CtxLen rl; };
         auto pctx = [&]() -> PC {
-            if (!streaming) return PC{nullptr, nullptr, nullptr};
+            if (!streaming) return PC{nullptr, nullptr, nullptr, {}};
             FS_REQUIRE(slot < kCtxSlots, "streaming context slots exhausted");
             const size_t off = (size_t)slot++ * ctx_slot_bytes();
-            if (streaming == kMulti) {
+            if (multi) {
                 uint16_t* p = reinterpret_cast<uint16_t*>((uint8_t*)mpool_p_.p + off);
-                return PC{p, p, tab_p};
+                return PC{p, p, tab_p, rl};
             }
-            return PC{reinterpret_cast<const uint16_t*>((const uint8_t*)sctx_p_[stream_chunk_ & 1].p + off), reinterpret_cast<uint16_t*>((uint8_t*)sctx_p_[(stream_chunk_ + 1) & 1].p + off), nullptr};
+            return PC{reinterpret_cast<const uint16_t*>((const uint8_t*)sctx_p_[stream_chunk_ & 1].p + off), reinterpret_cast<uint16_t*>((uint8_t*)sctx_p_[(stream_chunk_ + 1) & 1].p + off), nullptr, {}};
         };
         struct FC { const float* ci; float* co; const long long* off; };
         auto fctx = [&]() -> FC {
             if (!streaming) return FC{nullptr, nullptr, nullptr};
             const size_t off = (size_t)fslot++ * C_ * CODEC_CTX_F32;
-            if (streaming == kMulti) return FC{mpool_f_.f() + off, mpool_f_.f() + off, tab_f};
+            if (multi) return FC{mpool_f_.f() + off, mpool_f_.f() + off, tab_f};
             return FC{sctx_f_[stream_chunk_ & 1].f() + off, sctx_f_[(stream_chunk_ + 1) & 1].f() + off, nullptr};
         };
         const size_t max_elems = (size_t)B * C_ * 4 * T * 8;  // largest activation: (C/2) x 32T .. (C/32) x 2048T = C*64*T
@@ -345,7 +395,7 @@ class Codec final : public CodecBase {
         float *x = buf_[0].f(), *t1 = buf_[1].f(), *t2 = buf_[2].f(), *r = buf_[3].f(), *acc0 = buf_[4].f(), *acc1 = buf_[5].f(),
               *acc2 = buf_[6].f();
         // quantizer.decode: FSQ lookup + project_out, concat groups -> (B, C, T)
-        codec_fsq_project((const uint32_t*)dcodes_.p, B, G, T, R(proj_w_), R(proj_b_), C_ / G, x, st_, streaming == kMulti);
+        codec_fsq_project((const uint32_t*)dcodes_.p, B, G, T, R(proj_w_), R(proj_b_), C_ / G, x, st_, multi);
         int Tc = T;
         // upsample.0 then upsample.1 (quantizer.rs:126-133): transposed conv (k = s = 2) + ConvNeXt block
         // bf16x3 mode with 16-channel-block widths: the pointwise convs read and write activation planes as well (codec_conv_bf3.hip)
@@ -363,14 +413,15 @@ class Codec final : public CodecBase {
                 Tc *= 2;
                 const FC fd = fctx();  // the depthwise k = 7 conv reads 6 samples of left context
                 codec_dwconv_ln(t1, B, C_, Tc, R(c.dw), R(c.db), R(c.lnw), R(c.lnb), t2, st_, fd.ci, fd.off);
-                if (streaming) codec_save_tail_f32(t1, B, C_, Tc, fd.co, st_, fd.off);
+                if (ragged) codec_save_tail_f32_ragged(t1, B, C_, Tc, fd.ci, fd.co, st_, fd.off, rl);
+                else if (streaming) codec_save_tail_f32(t1, B, C_, Tc, fd.co, st_, fd.off);
                 codec_act_split(t2, B, C_, Tc, false, bp0, f16_, st_);
                 codec_conv1d_planes(nullptr, bp0, B, C_, Tc, conv(c.pw1), 1, false, CODEC_EPI_GELU, nullptr, nullptr, nullptr, bp1, false, st_);
                 // pwconv2 + gamma + residual: the sum feeds the next transposed conv / conv_pre as planes (no SiLU in front of either);
                 // only conv_pre (after the second block) reads left context from it
-                const PC pb = i == 1 ? pctx() : PC{nullptr, nullptr, nullptr};
+                const PC pb = i == 1 ? pctx() : PC{nullptr, nullptr, nullptr, {}};
                 codec_conv1d_planes(nullptr, bp1, B, 4 * C_, Tc, conv(c.pw2), 1, false, CODEC_EPI_GAMMA_RES, t1, R(c.gamma), nullptr, bp0, false, st_,
-                                    pb.ci, pb.co, nullptr, nullptr, pb.off);
+                                    pb.ci, pb.co, nullptr, nullptr, pb.off, pb.rl);
                 continue;
             }
             codec_tconv1d(x, B, C_, Tc, conv(up_conv_[i]), 2, false, t1, st_);
@@ -390,8 +441,8 @@ class Codec final : public CodecBase {
             for (auto& b : pbuf_) b.ensure(act * sizeof(float) + (size_t)B * C_ * CODEC_PLANE_PAD * 4 + (256 << 10));
             xp = pbuf_[2].u16(); t1p = pbuf_[1].u16(); t2p = pbuf_[3].u16(); accp = pbuf_[4].u16();
             const PC px = pctx();
-            if (bb_planes) codec_conv1d_planes(nullptr, bp0, B, C_, Tc, conv(conv_pre_), 1, false, CODEC_EPI_NONE, nullptr, nullptr, nullptr, xp, true, st_, px.ci, px.co, nullptr, nullptr, px.off);
-            else codec_conv1d_planes(x, nullptr, B, C_, Tc, conv(conv_pre_), 1, false, CODEC_EPI_NONE, nullptr, nullptr, nullptr, xp, true, st_, px.ci, px.co, nullptr, nullptr, px.off);
+            if (bb_planes) codec_conv1d_planes(nullptr, bp0, B, C_, Tc, conv(conv_pre_), 1, false, CODEC_EPI_NONE, nullptr, nullptr, nullptr, xp, true, st_, px.ci, px.co, nullptr, nullptr, px.off, px.rl);
+            else codec_conv1d_planes(x, nullptr, B, C_, Tc, conv(conv_pre_), 1, false, CODEC_EPI_NONE, nullptr, nullptr, nullptr, xp, true, st_, px.ci, px.co, nullptr, nullptr, px.off, px.rl);
         } else {
             codec_conv1d(x, B, C_, Tc, conv(conv_pre_), 1, false, CODEC_EPI_NONE, nullptr, nullptr, t1, st_);
             std::swap(x, t1);
@@ -403,12 +454,12 @@ class Codec final : public CodecBase {
                 codec_tconv1d_planes(xp, B, ch, Tc, conv(ups_[s]), rates[s], t1, st_);  // ups[i](silu(x)); xp holds split(silu(x))
                 ch /= 2; Tc *= rates[s];
                 const PC p1 = pctx();
-                codec_act_split(t1, B, ch, Tc, true, t1p, f16_, st_, p1.ci, p1.co, p1.off);
+                codec_act_split(t1, B, ch, Tc, true, t1p, f16_, st_, p1.ci, p1.co, p1.off, p1.rl);
                 for (int j = 0; j < 3; ++j) {  // ResBlock1 (hifi_gan.rs:74-85): x += c2(silu(c1(silu(x)))), both convs dilated
                     const float* cur = t1;
                     const uint16_t* curp = t1p;
                     for (int m = 0; m < 3; ++m) {
-                        const PC pa = pctx(), pb2 = m < 2 ? pctx() : PC{nullptr, nullptr, nullptr};
+                        const PC pa = pctx(), pb2 = m < 2 ? pctx() : PC{nullptr, nullptr, nullptr, {}};
                         const ConvW w1 = conv(res_[s][j][0][m]), w2 = conv(res_[s][j][1][m]);
                         if (w1.f16 && w2.f16 && w1.k == w2.k && codec_respair_ok(ch, w1.k, dils[m], true)) {
                             // thin stages, f16 mode: the pair in ONE kernel (the intermediate stays in LDS).  Its output planes go to the buffer the
@@ -418,20 +469,20 @@ class Codec final : public CodecBase {
                                 if (stage_planes(s + 1)) {
                                     const PC pm = pctx();
                                     codec_respair_f16(curp, B, ch, Tc, w1.wp, w1.b, w2.wp, w2.b, w1.k, dils[m], cur, nullptr, xp, st_, pa.ci, pa.co, pm.ci, pm.co,
-                                                      acc0, acc1, pa.off);
+                                                      acc0, acc1, pa.off, pa.rl);
                                 } else {
                                     codec_respair_f16(curp, B, ch, Tc, w1.wp, w1.b, w2.wp, w2.b, w1.k, dils[m], cur, x, nullptr, st_, pa.ci, pa.co, nullptr, nullptr,
-                                                      acc0, acc1, pa.off);
+                                                      acc0, acc1, pa.off, pa.rl);
                                 }
                                 break;
                             }
                             codec_respair_f16(curp, B, ch, Tc, w1.wp, w1.b, w2.wp, w2.b, w1.k, dils[m], cur, accs[j], m < 2 ? outp : nullptr, st_, pa.ci, pa.co,
-                                              pb2.ci, pb2.co, nullptr, nullptr, pa.off);
+                                              pb2.ci, pb2.co, nullptr, nullptr, pa.off, pa.rl);
                             cur = accs[j]; curp = outp;
                             continue;
                         }
                         codec_conv1d_planes(nullptr, curp, B, ch, Tc, conv(res_[s][j][0][m]), dils[m], true, CODEC_EPI_NONE, nullptr, nullptr,
-                                            nullptr, t2p, true, st_, pa.ci, pa.co, nullptr, nullptr, pa.off);
+                                            nullptr, t2p, true, st_, pa.ci, pa.co, nullptr, nullptr, pa.off, pa.rl);
                         if (j == 2 && m == 2 && fold_mean_) {
                             // the ParallelBlock mean (hifi_gan.rs:114-117) inside the epilogue of the last residual conv: ((acc0 + acc1) + this
                             // block's output) / 3 goes straight to the next stage's input planes (or, after the last stage, to conv_post's f32
@@ -439,7 +490,7 @@ class Codec final : public CodecBase {
                             if (stage_planes(s + 1)) {
                                 const PC pm = pctx();
                                 codec_conv1d_planes(nullptr, t2p, B, ch, Tc, conv(res_[s][j][1][m]), dils[m], true, CODEC_EPI_RES, cur, nullptr, nullptr,
-                                                    xp, true, st_, pm.ci, pm.co, acc0, acc1, pm.off);
+                                                    xp, true, st_, pm.ci, pm.co, acc0, acc1, pm.off, pm.rl);
                             } else {
                                 codec_conv1d_planes(nullptr, t2p, B, ch, Tc, conv(res_[s][j][1][m]), dils[m], true, CODEC_EPI_RES, cur, nullptr, x,
                                                     nullptr, true, st_, nullptr, nullptr, acc0, acc1);
@@ -447,14 +498,14 @@ class Codec final : public CodecBase {
                             break;
                         }
                         codec_conv1d_planes(nullptr, t2p, B, ch, Tc, conv(res_[s][j][1][m]), dils[m], true, CODEC_EPI_RES, cur, nullptr, accs[j],
-                                            m < 2 ? accp : nullptr, true, st_, pb2.ci, pb2.co, nullptr, nullptr, pb2.off);
+                                            m < 2 ? accp : nullptr, true, st_, pb2.ci, pb2.co, nullptr, nullptr, pb2.off, pb2.rl);
                         cur = accs[j]; curp = accp;
                     }
                 }
                 if (fold_mean_) continue;
                 if (stage_planes(s + 1)) {
                     const PC pm = pctx();
-                    codec_mean3_planes(acc0, acc1, acc2, B, ch, Tc, true, xp, f16_, st_, pm.ci, pm.co, pm.off);
+                    codec_mean3_planes(acc0, acc1, acc2, B, ch, Tc, true, xp, f16_, st_, pm.ci, pm.co, pm.off, pm.rl);
                 } else codec_mean3(acc0, acc1, acc2, x, (size_t)B * ch * Tc, st_);
                 continue;
             }
@@ -472,6 +523,16 @@ class Codec final : public CodecBase {
         }
         const FC fp = fctx();  // conv_post (k = 13 on the 16-channel f32 mean)
         codec_conv1d(x, B, ch, Tc, conv(conv_post_), 1, true, CODEC_EPI_TANH, nullptr, nullptr, t1, st_, fp.ci, fp.off);
+        if (ragged) {
+            codec_save_tail_f32_ragged(x, B, ch, Tc, fp.ci, fp.co, st_, fp.off, rl);
+            // the items' own samples packed in item order (t2 is free by now), one copy to the host
+            size_t total = 0;
+            for (int b = 0; b < B; ++b) total += (size_t)ms_tab_[(size_t)4 * B + b] * (size_t)(Tc / T);
+            codec_gather_ragged(t1, B, Tc, rl, tab_p + 5 * B, t2, st_);
+            FS_HIP(hipMemcpyAsync(pcm_out, t2, sizeof(float) * total, hipMemcpyDeviceToHost, st_));
+            FS_HIP(hipStreamSynchronize(st_));
+            return;
+        }
         if (streaming) codec_save_tail_f32(x, B, ch, Tc, fp.co, st_, fp.off);
         FS_HIP(hipMemcpyAsync(pcm_out, t1, sizeof(float) * (size_t)B * Tc, hipMemcpyDeviceToHost, st_));
         FS_HIP(hipStreamSynchronize(st_));
@@ -748,6 +809,7 @@ class Codec final : public CodecBase {
     int ms_cap_ = 0;                               // streams the pools hold
     DBuf mpool_p_, mpool_f_, dtab_;                // context pools [stream][half][...] and the per-call device offset table
     std::vector<long long> ms_tab_;                // host side of the table (alive until the call's final synchronisation)
+    std::vector<uint32_t> rag_codes_;              // the ragged call's codes at the stride of its longest item
     std::vector<size_t> packed_off_, packed16_off_;
     bool fold_mean_ = getenv("FISHRT_VOC_NO_FOLD_MEAN") == nullptr;  // ParallelBlock mean inside the last residual conv's epilogue (A/B switch)
     bool range_check_ = false;              // fs_codec_set_range_check

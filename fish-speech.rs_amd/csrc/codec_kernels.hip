@@ -483,10 +483,10 @@ void codec_tconv1d(const float* x, int B, int Cin, int Tin, const ConvW& w, int 
 
 void codec_conv1d_planes(const float* x, const uint16_t* xp, int B, int Cin, int T, const ConvW& w, int dil, bool pre_silu, int epi,
                          const float* res, const float* gamma, float* y, uint16_t* yp, bool post_silu, hipStream_t st,
-                         const uint16_t* ctx_in, uint16_t* ctx_out, const float* mean_a, const float* mean_b, const long long* ctx_off) {
+                         const uint16_t* ctx_in, uint16_t* ctx_out, const float* mean_a, const float* mean_b, const long long* ctx_off, CtxLen rl) {
     FS_REQUIRE(w.wp, "the plane data flow needs packed bf16x3 weights");
     codec_conv1d_bf3(x, xp, B, Cin, T, w.wp, w.f16, w.b, w.cout, w.k, dil, pre_silu, epi, res, gamma, y, yp, post_silu, 1, st, ctx_in, ctx_out, mean_a,
-                     mean_b, ctx_off);
+                     mean_b, ctx_off, rl);
 }
 
 void codec_tconv1d_planes(const uint16_t* xp, int B, int Cin, int Tin, const ConvW& w, int stride, float* y, hipStream_t st) {
@@ -505,6 +505,39 @@ void codec_save_tail_f32(const float* x, int B, int C, int T, float* ctx_out, hi
     FS_REQUIRE(T >= CODEC_CTX_F32, "chunk shorter than the f32 streaming context");
     FS_REQUIRE(B == 1 || ctx_off, "f32 streaming context: one item (or per-item context offsets)");
     hipLaunchKernelGGL(k_save_tail_f32, dim3(C, B), dim3(CODEC_CTX_F32), 0, st, x, C, T, ctx_out, ctx_off);
+    FS_LAUNCH_CHECK();
+}
+
+// ragged items (CtxLen): item b ends at sample Te = len[b] * per; its new context is the last CODEC_CTX_F32 samples of (old context ++ x[:Te]).
+// The old context is read from the item's "in" half and the new one written to its "out" half (ping-pong: no ordering between threads needed)
+__global__ void k_save_tail_f32_ragged(const float* __restrict__ x, int C, int T, const float* __restrict__ ctx_in, float* __restrict__ ctx_out,
+                                       const long long* __restrict__ ctx_off, const long long* __restrict__ len, int per) {
+    const int b = blockIdx.y, j = threadIdx.x, Te = (int)len[b] * per;
+    const float* ci = ctx_in + ctx_off[2 * b];
+    float* co = ctx_out + ctx_off[2 * b + 1];
+    const int t = Te - CODEC_CTX_F32 + j;  // (Te <= T: checked by the engine)
+    co[(size_t)blockIdx.x * CODEC_CTX_F32 + j] =
+        t >= 0 ? x[((size_t)b * C + blockIdx.x) * T + t] : ci[(size_t)blockIdx.x * CODEC_CTX_F32 + CODEC_CTX_F32 + t];
+}
+void codec_save_tail_f32_ragged(const float* x, int B, int C, int T, const float* ctx_in, float* ctx_out, hipStream_t st, const long long* ctx_off,
+                                CtxLen rl) {
+    FS_REQUIRE(ctx_in && ctx_out && ctx_off && rl.len && rl.frames >= 1 && T % rl.frames == 0, "ragged f32 context: both halves, the offset and the length table");
+    hipLaunchKernelGGL(k_save_tail_f32_ragged, dim3(C, B), dim3(CODEC_CTX_F32), 0, st, x, C, T, ctx_in, ctx_out, ctx_off, rl.len, T / rl.frames);
+    FS_LAUNCH_CHECK();
+}
+
+// the items' PCM (each at stride T) packed in item order: item b contributes its first len[b] * per samples at dst_off[b]
+__global__ void k_gather_ragged(const float* __restrict__ y, int T, const long long* __restrict__ len, int per, const long long* __restrict__ dst_off,
+                                float* __restrict__ out) {
+    const int b = blockIdx.y;
+    const long long n = len[b] * per;
+    const float* src = y + (size_t)b * T;
+    float* dst = out + dst_off[b];
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) dst[i] = src[i];
+}
+void codec_gather_ragged(const float* y, int B, int T, CtxLen rl, const long long* dst_off, float* out, hipStream_t st) {
+    FS_REQUIRE(rl.len && dst_off && rl.frames >= 1 && T % rl.frames == 0, "ragged gather: the length and the destination table");
+    hipLaunchKernelGGL(k_gather_ragged, dim3((unsigned)std::min(256, (T + 255) / 256), B), dim3(256), 0, st, y, T, rl.len, T / rl.frames, dst_off, out);
     FS_LAUNCH_CHECK();
 }
 

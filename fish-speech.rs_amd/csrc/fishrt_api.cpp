@@ -280,6 +280,10 @@ int fs_codec_streams_decode(fs_codec_t* c, int n, const int* stream_ids, const u
     FS_ARG(c && stream_ids && codes && pcm_out, "null argument");
     FS_TRY(c->impl->streams_decode(n, stream_ids, codes, T, pcm_out))
 }
+int fs_codec_streams_decode_ragged(fs_codec_t* c, int n, const int* stream_ids, const int* T, const uint32_t* codes, float* pcm_out) {
+    FS_ARG(c && stream_ids && T && codes && pcm_out, "null argument");
+    FS_TRY(c->impl->streams_decode_ragged(n, stream_ids, T, codes, pcm_out))
+}
 int fs_codec_set_precision(fs_codec_t* c, int mode) { FS_ARG(c, "null argument"); FS_TRY(c->impl->set_precision(mode)) }
 int fs_codec_precision(fs_codec_t* c) { return c ? c->impl->precision() : -1; }
 int fs_codec_set_range_check(fs_codec_t* c, int on) { FS_ARG(c, "null argument"); FS_TRY(c->impl->set_range_check(on != 0)) }

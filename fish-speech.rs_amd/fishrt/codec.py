@@ -110,6 +110,28 @@ class FireflyCodec:
                                                       pcm.ctypes.data_as(C.POINTER(C.c_float))))
         return pcm
 
+    def streams_decode_ragged(self, ids, chunks):
+        """ids: n distinct open stream ids; chunks: n arrays u32 (8, T_i), T_i >= 1 and different per item: item i is the next chunk of stream
+        ids[i] -> list of n f32 (2048 T_i,) PCM arrays.  Per stream, the chunks' PCM concatenated (through this call and streams_decode in
+        any interleaving) is bit-identical to decode() of its whole sequence.  The items run at the stride of the longest one."""
+        ids = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1))
+        chunks = [np.ascontiguousarray(c, np.uint32) for c in chunks]
+        if len(chunks) != ids.shape[0]:
+            raise ValueError("streams_decode_ragged: one chunk per stream id")
+        if not 1 <= len(chunks) <= self.STREAMS_MAX:
+            raise ValueError(f"streams_decode_ragged: 1 .. {self.STREAMS_MAX} streams per call")
+        for c in chunks:
+            if c.ndim != 2 or c.shape[0] != 8 or c.shape[1] < 1:
+                raise ValueError("streams_decode_ragged: every chunk must have shape (8, T) with T >= 1")
+        T = np.array([c.shape[1] for c in chunks], np.int32)
+        codes = np.concatenate([c.reshape(-1) for c in chunks])
+        pcm = np.empty(2048 * int(T.sum()), np.float32)
+        _ffi.check(_ffi.lib().fs_codec_streams_decode_ragged(self._h, int(len(chunks)), ids.ctypes.data_as(C.POINTER(C.c_int)),
+                                                             T.ctypes.data_as(C.POINTER(C.c_int)), codes.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                             pcm.ctypes.data_as(C.POINTER(C.c_float))))
+        ends = 2048 * np.cumsum(T)
+        return [pcm[e - 2048 * t:e] for e, t in zip(ends, T)]
+
     def encode(self, pcm_data, lengths=None):
         """codec.rs:73-94 / firefly.rs:36-39: f32 (b, 1, n) mono 44.1 kHz PCM -> u32 (b, 8, L).  Every clip is encoded on its own
         (fishrt.h fs_codec_encode_batch; the reference's front-end would glue a batch into one signal, spectrogram.rs:33).  lengths: optional

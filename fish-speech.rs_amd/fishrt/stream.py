@@ -162,18 +162,25 @@ class SessionStreamer:
 
     on_audio(tag, pcm, final) is called for every PCM piece, in order per request; step() also returns the pieces as (tag, pcm, final).
     stats[tag]: frames, first_audio_s (add() to its first PCM piece), vocoder_s (wall time of the vocoder calls that carried its audio; a
-    shared call counts in full for each request in it), chunks.  calls: one record per vocoder call (quantum, kind, n, T)."""
+    shared call counts in full for each request in it), chunks.  calls: one record per vocoder call (quantum, kind, n, T).
 
-    def __init__(self, session, codec, chunk=64, first_chunk=32, halo=HALO, on_audio=None, clock=time.perf_counter):
-        min_frames = getattr(codec, "STREAM_MIN_FRAMES", 16)
+    ragged=True (FireflyCodec.streams_decode_ragged): at most ONE vocoder call per step().  Every request that is due -- its first piece of
+    `first_chunk` frames, a steady piece of `chunk` frames, or whatever is left of a finished request, down to one frame -- is an item of the
+    same call, so the kinds "tail" and "halo" never occur (the call is recorded as kind "ragged", its T = the longest item) and `chunk` /
+    `first_chunk` may be any value >= 1.  The codec runs the items of a ragged call at the stride of the longest one: a call costs about
+    n x the longest item, so one long item next to many short ones (a 64-frame chunk next to 31 one-frame tails) is paid 32 x 64 frames of
+    work for 95 frames of audio.  Chunk sizes near each other keep that waste small; the one-call rule holds whatever the mix."""
+
+    def __init__(self, session, codec, chunk=64, first_chunk=32, halo=HALO, on_audio=None, clock=time.perf_counter, ragged=False):
+        min_frames = 1 if ragged else getattr(codec, "STREAM_MIN_FRAMES", 16)
         if chunk < min_frames or first_chunk < min_frames:
             raise ValueError(f"chunk and first_chunk must be >= {min_frames} frames (the codec's minimum streamed chunk)")
         self.session, self.codec, self.chunk, self.first_chunk, self.halo = session, codec, int(chunk), int(first_chunk), halo
-        self.min_frames, self.on_audio, self.clock = min_frames, on_audio, clock
+        self.min_frames, self.on_audio, self.clock, self.ragged = min_frames, on_audio, clock, bool(ragged)
         self.live = {}       # slot -> request record
         self.results = {}    # tag -> final codes (C, n) of every finished request
         self.stats = {}      # tag -> per-request numbers
-        self.calls = []      # (quantum, kind: "chunk" | "tail" | "halo", n, T)
+        self.calls = []      # (quantum, kind: "chunk" | "tail" | "halo" | "ragged", n, T)
         self.quantum = 0
         self.n_active = 0
         self._admitted = 0
@@ -218,6 +225,8 @@ class SessionStreamer:
         session's slots still generating afterwards"""
         self.n_active = self.session.step(n_frames)
         self.quantum += 1
+        if self.ragged:
+            return self._step_ragged()
         out = []
         groups, finished = {}, []
         for slot, r in self.live.items():
@@ -239,6 +248,45 @@ class SessionStreamer:
                 out.append(self._deliver(self.live[s], pcm[i], T, False))
         for slot in finished:
             out.extend(self._finish(slot))
+        return out
+
+    def _step_ragged(self):
+        """every due request -- first piece, steady piece, or the rest of a finished one -- in ONE streams_decode_ragged call"""
+        due, finished = [], []  # due: (slot, frames, final)
+        for slot, r in self.live.items():
+            n, done = self.session.poll(slot, codes=False)
+            r["n"] = n
+            left = n - r["done_upto"]
+            if done:
+                finished.append(slot)
+                if left > 0:
+                    due.append((slot, left, True))
+                continue
+            T = self.first_chunk if r["done_upto"] == 0 else self.chunk
+            if left >= T:
+                due.append((slot, T, False))
+        out = []
+        try:
+            if due:
+                chunks = []
+                for slot, T, _ in due:
+                    a = self.live[slot]["done_upto"]
+                    chunks.append(np.ascontiguousarray(self._codes(slot)[:, a:a + T]))
+                t1 = self.clock()
+                pcm = self.codec.streams_decode_ragged([self.live[s]["sid"] for s, _, _ in due], chunks)
+                self._account([self.live[s] for s, _, _ in due], "ragged", max(T for _, T, _ in due), self.clock() - t1)
+                for (slot, T, final), p in zip(due, pcm):
+                    out.append(self._deliver(self.live[slot], p, T, final))
+            for slot in finished:
+                r = self.live[slot]
+                if r["done_upto"] == r["n"] and not any(s == slot for s, _, _ in due) and self.on_audio is not None:
+                    self.on_audio(r["tag"], np.zeros(0, np.float32), True)  # nothing left: the last piece was already delivered; signal the end
+                self.results[r["tag"]] = self._codes(slot)[:, :r["n"]].copy()
+        finally:
+            for slot in finished:
+                r = self.live.pop(slot)
+                self.codec.streams_close(r["sid"])
+                self.session.release(slot)
         return out
 
     def close(self):

@@ -402,6 +402,16 @@ int fs_codec_stream_end(fs_codec_t* c);
 int fs_codec_streams_open(fs_codec_t* c, int* stream_id);
 int fs_codec_streams_close(fs_codec_t* c, int stream_id);
 int fs_codec_streams_decode(fs_codec_t* c, int n, const int* stream_ids, const uint32_t* codes, int T, float* pcm_out);
+/* Ragged form of fs_codec_streams_decode: item i = the next T[i] >= 1 frames of stream stream_ids[i]; the lengths differ per item and a
+ * chunk may be as short as one frame (the 16-frame minimum of the calls above does not apply).  codes: the items' (8, T[i]) blocks
+ * concatenated in item order; pcm_out: their 2048 * T[i] samples concatenated in item order.  Same rules otherwise (1 <= n <= 64 distinct open
+ * ids, precision fixed per stream, everything -- n, every T[i], ids, precision, codes < 1000 -- validated before the first launch, a failed
+ * call leaves every stream untouched).  Per stream, the PCM of all its chunks -- through this call and fs_codec_streams_decode in any
+ * interleaving -- concatenated is bit-identical to fs_codec_decode of the whole sequence at b = 1; neither the order of the items nor the
+ * lengths of the other items change a stream's PCM.  The left contexts follow the rule "last 64 slots of (old context ++ new data)", so they
+ * are right for any chunk length.  The items run at the stride of the longest one: time and activation memory grow with n x max T[i], not
+ * with the sum of the lengths; the per-stream device memory is that of fs_codec_streams_open, nothing is added per call. */
+int fs_codec_streams_decode_ragged(fs_codec_t* c, int n, const int* stream_ids, const int* T, const uint32_t* codes, float* pcm_out);
 /* FireflyCodec.sample_rate (codec/firefly.rs:13) */
 int fs_codec_sample_rate(fs_codec_t* c);
 /* Arithmetic of the decode path's convolutions (no reference counterpart: the reference runs the codec in f32,
