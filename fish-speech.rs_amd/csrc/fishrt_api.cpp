@@ -228,6 +228,15 @@ int fs_lm_session_add_ex(fs_lm_t* lm, int prefix_id, const uint32_t* prompt, int
     FS_ARG(lm && prompt && slot, "null argument");
     FS_TRY(*slot = lm->impl->session_add_ex(prefix_id, prompt, L, max_new_tokens, sampling, seed))
 }
+int fs_lm_session_add_hidden(fs_lm_t* lm, int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling,
+                             const uint64_t* seed, int* slot) {
+    FS_ARG(lm && prompt && slot, "null argument");
+    FS_TRY(*slot = lm->impl->session_add_hidden(prefix_id, prompt, L, max_new_tokens, sampling, seed))
+}
+int fs_lm_session_poll_hidden(fs_lm_t* lm, int slot, size_t first_row, float* hidden_out, size_t cap_rows, size_t* n_rows) {
+    FS_ARG(lm, "null argument");
+    FS_TRY(lm->impl->session_poll_hidden(slot, first_row, hidden_out, cap_rows, n_rows))
+}
 int fs_lm_session_info(fs_lm_t* lm, int64_t out[8]) { FS_ARG(lm && out, "null argument"); FS_TRY(lm->impl->session_info(out)) }
 int fs_lm_last_stats(fs_lm_t* lm, fs_gen_stats* out) { FS_ARG(lm && out, "null argument"); FS_TRY(*out = lm->impl->last_stats()) }
 void* fs_lm_stream(fs_lm_t* lm) { return lm ? lm->impl->stream() : nullptr; }

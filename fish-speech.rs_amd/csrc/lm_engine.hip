@@ -224,6 +224,10 @@ class LM final : public LMBase {
         for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
         for (auto& e : ev_batch_) if (e) (void)hipEventDestroy(e);
         if (h_pin_) (void)hipHostFree(h_pin_);
+        for (auto& hb : hid_pool_) (void)hipFree(hb.first);
+        for (const HidSlot& h : sess_hid_) if (h.rows) (void)hipFree(h.rows);
+        for (auto* q : {&sess_flight_, &sess_queue_})  // (a handle destroyed with a session open and adds pending)
+            for (const PendingAdd& pa : *q) if (pa.hid) (void)hipFree(pa.hid);
         if (ev_pf_) (void)hipEventDestroy(ev_pf_);
         for (hipEvent_t e : ev_pft_) if (e) (void)hipEventDestroy(e);
         if (st_pf_) (void)hipStreamDestroy(st_pf_);
@@ -1047,6 +1051,10 @@ class LM final : public LMBase {
         sess_hs_.assign(B_, SeqState{});
         sess_queue_.clear(); sess_flight_.clear();
         sess_prefixes_.clear();
+        sess_hid_.assign(B_, HidSlot{});
+        sess_hid_want_.assign(B_, 0);
+        sess_hid_live_ = 0;
+        FS_HIP(hipMemsetAsync(d_hid_tab_.p, 0, d_hid_tab_.n, st_));
         for (auto& v : sess_count_) v = 0;
         sess_pf_ms_ = 0.0;
         sess_timed_ = false;
@@ -1103,6 +1111,73 @@ class LM final : public LMBase {
         }
         return b;
     }
+    // fs_lm_session_add_hidden: session_add_ex + hidden-state collection for the slot.  The row buffer (one row per generator iteration
+    // the slot can run) is taken BEFORE the add -- an allocation failure leaves the session as it was -- and goes back when the add is
+    // refused; the device table learns of it at activation, so the slot's rows start at 0 with its first iteration.
+    int session_add_hidden(int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling, const uint64_t* seed) override {
+        use_device();
+        FS_REQUIRE(sess_active_, "no open session");
+        FS_REQUIRE(L >= 1, "empty prompt");
+        const long long Lt = (long long)L + (prefix_id >= 0 ? live_prefix(prefix_id).P : 0);
+        long long n_iter = 1 + std::max<long long>(0, (long long)max_new_tokens - Lt + 1);
+        n_iter = std::max<long long>(1, std::min<long long>(n_iter, (long long)a_.max_seq_len - Lt + 1));  // (Lt > max_seq_len: the add below throws)
+        FS_REQUIRE(n_iter <= out_cap_, "generation longer than the output staging buffer");
+        std::pair<float*, int> buf = take_hid_buf((int)n_iter);
+        int b = -1;
+        try {
+            b = session_add_ex(prefix_id, prompt, L, max_new_tokens, sampling, seed);
+        } catch (...) { put_hid_buf(buf.first, buf.second); throw; }
+        if (b < 0) { put_hid_buf(buf.first, buf.second); return b; }
+        PendingAdd& pa = sess_queue_.back();
+        FS_REQUIRE(pa.n_iter <= buf.second, "hidden-state buffer shorter than the slot's iteration budget");
+        pa.hid = buf.first; pa.hid_cap = buf.second;
+        sess_hid_want_[b] = 1;
+        return b;
+    }
+    // a row buffer goes back to the pool, which never holds more than max_batch buffers (beyond that the smallest one is freed)
+    void put_hid_buf(float* p, int cap) {
+        hid_pool_.push_back({p, cap});
+        if ((int)hid_pool_.size() <= B_) return;
+        int small = 0;
+        for (int i = 1; i < (int)hid_pool_.size(); ++i) if (hid_pool_[i].second < hid_pool_[small].second) small = i;
+        (void)hipFree(hid_pool_[small].first);
+        hid_pool_.erase(hid_pool_.begin() + small);
+    }
+    // a free row buffer of >= n_rows rows (the smallest that fits), else a new one
+    std::pair<float*, int> take_hid_buf(int n_rows) {
+        int best = -1;
+        for (int i = 0; i < (int)hid_pool_.size(); ++i)
+            if (hid_pool_[i].second >= n_rows && (best < 0 || hid_pool_[i].second < hid_pool_[best].second)) best = i;
+        if (best >= 0) {
+            const std::pair<float*, int> buf = hid_pool_[best];
+            hid_pool_.erase(hid_pool_.begin() + best);
+            return buf;
+        }
+        float* p = nullptr;
+        FS_HIP(hipMalloc(&p, sizeof(float) * (size_t)n_rows * a_.dim));
+        return {p, n_rows};
+    }
+    // the slot stops collecting: null table entry (on the engine stream: ahead of the next step), buffer back to the pool
+    void drop_hid_slot(int b) {
+        if (!sess_hid_[b].rows) return;
+        put_hid_buf(sess_hid_[b].rows, sess_hid_[b].cap);
+        sess_hid_[b] = HidSlot{};
+        FS_HIP(hipMemcpyAsync(d_hid_tab_.as<HidSlot>() + b, &sess_hid_[b], sizeof(HidSlot), hipMemcpyHostToDevice, st_));
+        FS_HIP(hipStreamSynchronize(st_));
+        --sess_hid_live_;
+    }
+    void session_poll_hidden(int slot, size_t first_row, float* hidden_out, size_t cap_rows, size_t* n_rows) override {
+        use_device();
+        FS_REQUIRE(sess_active_ && slot >= 0 && slot < B_ && sess_left_[slot] != -1, "not a live session slot");
+        FS_REQUIRE(sess_hid_want_[slot], "the slot does not collect hidden states (it was not admitted with fs_lm_session_add_hidden)");
+        const size_t n = sess_left_[slot] == -2 ? 0 : (size_t)sess_hid_[slot].count;  // (-2: still prefilling)
+        if (hidden_out && first_row < n) {
+            const size_t m = std::min(n - first_row, cap_rows);
+            if (m) FS_HIP(hipMemcpyAsync(hidden_out, sess_hid_[slot].rows + first_row * (size_t)a_.dim, sizeof(float) * m * a_.dim, hipMemcpyDeviceToHost, st_));
+            FS_HIP(hipStreamSynchronize(st_));
+        }
+        if (n_rows) *n_rows = n;
+    }
     void park_slot(int b) {
         SeqState ss = {};
         ss.done = sess_rows_ ? 2 : 1; ss.frame = 1;  // (rows mode: a terminated row is skipped by the row kernels altogether)
@@ -1155,6 +1230,8 @@ class LM final : public LMBase {
         bool has_cfg = false, has_seed = false;  // fs_lm_session_add_ex: the slot's own settings / sampler seed
         SampleCfg cfg = {};
         uint64_t seed = 0;
+        float* hid = nullptr;  // fs_lm_session_add_hidden: the slot's row buffer [hid_cap][dim], handed to the device table at activation
+        int hid_cap = 0;
         std::vector<uint32_t> prompt;
         int rows() const { return create ? L : L - start - 1; }   // tokens this member runs through the slow transformer
         int cols() const { return create ? L : L - start; }       // columns of `prompt`
@@ -1459,6 +1536,11 @@ class LM final : public LMBase {
             LmKernels<WT>::embed(d_, tok_emb_, cb_emb_, a_.num_codebooks, a_.codebook_size, d_cfg_.as<SampleCfg>(), nullptr, state(b),
                                  d_pfx_.as<float>() + (size_t)b * a_.dim, st_);
             }
+            if (pa.hid) {  // the slot collects from its first iteration on (the step that runs its last prompt position): row 0
+                sess_hid_[b].rows = pa.hid; sess_hid_[b].count = 0; sess_hid_[b].cap = pa.hid_cap;
+                FS_HIP(hipMemcpyAsync(d_hid_tab_.as<HidSlot>() + b, &sess_hid_[b], sizeof(HidSlot), hipMemcpyHostToDevice, st_));
+                ++sess_hid_live_;
+            }
             sess_left_[b] = pa.n_iter;
             sess_pos_[b] = Lp;
         }
@@ -1519,6 +1601,8 @@ class LM final : public LMBase {
                 for (int i = 0; i < chunk; ++i) {
                     set_bucket(longest + i + 1);
                     launch_rows_slow(rows_slow_args(Rs), Rs, st_);
+                    // (x(r) now holds row r's pre-norm hidden state; the fast launches overwrite it with the next input)
+                    if (sess_hid_live_ > 0) launch_hidden_rows(d_hid_tab_.as<HidSlot>(), state(0), x(0), a_.dim, top, st_);
                     for (int r0 = 0; r0 < top; r0 += PR_FAST_ROWS) {
                         const int left = std::min(PR_FAST_ROWS, top - r0), Rf = left >= 3 ? 4 : left;
                         launch_rows_fast(rows_fast_args(r0, Rf), Rf, sess_sampled_, st_);
@@ -1545,6 +1629,7 @@ class LM final : public LMBase {
                 }
             // (a slot that sampled <|im_end|> inside the chunk froze itself on the device; the host learns it below)
             FS_HIP(hipMemcpyAsync(sess_hs_.data(), state(0), sizeof(SeqState) * B_, hipMemcpyDeviceToHost, st_));
+            if (sess_hid_live_ > 0) FS_HIP(hipMemcpyAsync(sess_hid_.data(), d_hid_tab_.p, sizeof(HidSlot) * B_, hipMemcpyDeviceToHost, st_));  // (the row counts)
             FS_HIP(hipStreamSynchronize(st_));
             // a spin timeout inside the chunk (the joining prefill shares the CUs the persistent launches need co-resident) means the slots'
             // codes are garbage: raise instead of handing them out; the caller ends the session (the handle is off the row path afterwards)
@@ -1588,6 +1673,8 @@ class LM final : public LMBase {
         sess_released_frames_ += (uint64_t)sess_hs_[slot].n_out;
         truncate(slot, 0);
         park_slot(slot);
+        drop_hid_slot(slot);
+        sess_hid_want_[slot] = 0;
         sess_left_[slot] = -1;
     }
     void session_end() override {
@@ -1595,7 +1682,13 @@ class LM final : public LMBase {
         use_device();
         if (!sess_flight_.empty()) (void)hipEventSynchronize(ev_pf_);
         for (auto* q : {&sess_flight_, &sess_queue_})
-            for (const PendingAdd& pa : *q) if (pa.tail >= 0) put_page(pa.tail);
+            for (const PendingAdd& pa : *q) {
+                if (pa.tail >= 0) put_page(pa.tail);
+                if (pa.hid) put_hid_buf(pa.hid, pa.hid_cap);
+            }
+        for (HidSlot& h : sess_hid_) { if (h.rows) put_hid_buf(h.rows, h.cap); h = HidSlot{}; }
+        sess_hid_live_ = 0;
+        if (d_hid_tab_.p) FS_HIP(hipMemsetAsync(d_hid_tab_.p, 0, d_hid_tab_.n, st_));
         sess_flight_.clear(); sess_queue_.clear();
         for (int b = 0; b < B_; ++b) truncate(b, 0);
         for (SessPrefix& px : sess_prefixes_) drop_prefix_pages(px);  // (live or not: the session's references end with it)
@@ -2238,6 +2331,8 @@ class LM final : public LMBase {
         FS_HIP(hipMemcpy(d_epoch_.p, e0, sizeof(e0), hipMemcpyHostToDevice));
         d_fast_table_.alloc(sizeof(int) * B_);
         FS_HIP(hipMemcpy(d_fast_table_.p, tb.data(), sizeof(int) * B_, hipMemcpyHostToDevice));
+        d_hid_tab_.alloc(sizeof(HidSlot) * B_);
+        FS_HIP(hipMemset(d_hid_tab_.p, 0, d_hid_tab_.n));
     }
     // one static-batch frame for B rows: x rows (d_pfx_) hold the embedded inputs of position state(0)->pos
     void enqueue_batch_frame(int B) {
@@ -2253,6 +2348,9 @@ class LM final : public LMBase {
             LmKernels<WT>::rows_layer(d_, B, cs, slow_[l], slow_kv(l, 0), l == 0, st_, fold ? (l + 1 < a_.n_layer ? slow_[l + 1].attn_norm : norm_w_) : nullptr);
         if (!fold) LmKernels<WT>::rows_finish(d_, B, cs, norm_w_, st_);
         LmKernels<WT>::rows_head(d_, B, cs, slow_head_w(), slow_head_s(), n_audio_, d_lrows_.as<float>(), ld_slow_, st_, fold);
+        // session steps: the collecting slots' hidden-state rows (one node behind the slow head; null table entries exit at once, so the
+        // one captured graph serves every mix of collecting and non-collecting slots)
+        if (sess_active_) launch_hidden_rows(d_hid_tab_.as<HidSlot>(), state(0), cs.X, a_.dim, B, st_);
         // block-parallel samplers (temp > 1e-7, top_k <= 256): the step's C + 1 StdRng words per row are derived up front
         const bool slots = sess_active_ && sess_slots_;  // FS_SESSION_PER_SLOT: the 9 sampler nodes are the per-slot ones, one for one
         const uint32_t* words = rows_par_ ? d_rwords_.as<uint32_t>() : nullptr;
@@ -2744,6 +2842,14 @@ class LM final : public LMBase {
     std::vector<uint32_t> sess_stage_prompts_;
     std::vector<int> sess_stage_rows_;
     std::vector<PendingAdd> sess_queue_, sess_flight_;  // joining requests: queued by session_add / prefill launched (flush_pending)
+    // hidden-state collection (fs_lm_session_add_hidden): the device table the step's k_hidden_rows node reads (allocated once per handle:
+    // the captured step graphs hold its address), its host mirror (rows / cap as uploaded, count as of the last step), the slots admitted
+    // as collectors, how many of them are live, and the handle's pool of free row buffers (device pointer, capacity in rows)
+    DevBuf d_hid_tab_;
+    std::vector<HidSlot> sess_hid_;
+    std::vector<char> sess_hid_want_;
+    int sess_hid_live_ = 0;
+    std::vector<std::pair<float*, int>> hid_pool_;
     SeqState sess_stage_ = {};
     hipStream_t st_pf_ = nullptr;
     hipEvent_t ev_pf_ = nullptr;

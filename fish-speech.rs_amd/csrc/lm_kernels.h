@@ -259,6 +259,16 @@ void launch_cap_rows_picks(const SeqState* states, const SampleCfg* cfg, int B, 
 void launch_reppen_reset(RepPenState rp, int n_cb, int cb_size, hipStream_t st);
 // copy KV page pairs[2i] -> pairs[2i + 1] (device int array) in each of n_regions pool regions region_bytes apart: ONE launch
 void launch_kv_page_copy(void* pool, int n_regions, size_t region_bytes, size_t page_bytes, const int* pairs, int n_pairs, hipStream_t st);
+// Hidden-state collection of session slots (fishrt.h: fs_lm_session_add_hidden).  One entry per slot: rows == null -> the slot does not
+// collect; else its buffer f32 [cap][dim], and count = rows stored so far == the slot's generator iterations so far.
+struct HidSlot {
+    float* rows;
+    int count, cap;
+};
+// after the slow transformer of a step, before the slow-token decision: block b appends X[b] (the pre-norm residual row the head's
+// RMSNorm reads) to tab[b].rows when the slot collects and runs this iteration (states[b].done == 0); everything else exits at once.
+// dim % 4 == 0, X and the buffers 16-byte aligned.  ONE launch (a graph node of the session step: the table is read through pointers).
+void launch_hidden_rows(HidSlot* tab, const SeqState* states, const float* X, int dim, int B, hipStream_t st);
 
 // synthetic tensor fill (fs_synth.h): n_rows x n_cols, destination row = r * row_mul + row_off (W1/W3 interleave)
 template <typename WT>

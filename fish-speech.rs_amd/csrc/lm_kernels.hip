@@ -3935,6 +3935,31 @@ void launch_kv_page_copy(void* pool, int n_regions, size_t region_bytes, size_t 
     FS_LAUNCH_CHECK();
 }
 
+// Hidden-state collection of session slots: one block per slot.  The row index is the slot's own counter in the table (== its iteration
+// index: a slot runs one iteration per step from its activation until done != 0), so a parked, frozen, finished or not yet joined slot
+// (done != 0) stores nothing and a full buffer is never overrun.  256 lanes x 16 bytes = one 1024-float row per pass.
+__global__ __launch_bounds__(256) void k_hidden_rows(HidSlot* __restrict__ tab, const SeqState* __restrict__ states, const float* __restrict__ X,
+                                                     int dim) {
+    const int b = blockIdx.x;
+    HidSlot* h = tab + b;
+    float* rows = h->rows;
+    if (!rows) return;
+    if (states[b].done != 0) return;
+    const int it = h->count;
+    if (it >= h->cap) return;
+    const float4* s = reinterpret_cast<const float4*>(X + (size_t)b * dim);
+    float4* d = reinterpret_cast<float4*>(rows + (size_t)it * dim);
+    for (int i = threadIdx.x; i < dim / 4; i += 256) d[i] = s[i];
+    __syncthreads();  // (every wave has read count)
+    if (threadIdx.x == 0) h->count = it + 1;
+}
+void launch_hidden_rows(HidSlot* tab, const SeqState* states, const float* X, int dim, int B, hipStream_t st) {
+    if (B <= 0) return;
+    FS_REQUIRE(dim % 4 == 0, "hidden rows are copied in 16-byte units");
+    hipLaunchKernelGGL(k_hidden_rows, dim3(B), dim3(256), 0, st, tab, states, X, dim);
+    FS_LAUNCH_CHECK();
+}
+
 // ---- sampler test hook (fs_selftest_sample_rows): the static-batch slow sampler on caller-provided logits, B rows of n candidates,
 // as sample() call number `call_index` of a request (child StdRng of row b = master u64 number call_index * B + b)
 void debug_sample_rows(int device, const float* logits, int B, int n, double temp, double top_p, uint64_t top_k, uint64_t seed,

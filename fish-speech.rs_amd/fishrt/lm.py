@@ -315,22 +315,25 @@ class Session:
             raise ValueError("sampling: temp and top_k must not be negative")
         return _ffi.Sampling(float(v["temp"]), float(v["top_p"]), int(v["top_k"]), float(v["repetition_penalty"]))
 
-    def add(self, prompt, max_new_tokens, prefix=None, sampling=None, seed=None):
+    def add(self, prompt, max_new_tokens, prefix=None, sampling=None, seed=None, collect_hidden=False):
         """prefix (an add_prefix id): `prompt` is the request's BODY -- the slot generates what add(concat(prefix prompt, body)) would,
         reading the prefix's K/V from its shared pages and prefilling the body only.
         sampling (dict or SamplingArgs-like) / seed: the slot's own sampler settings / StdRng seed (fs_lm_session_add_ex) -- per_slot and rows
-        sessions only; a plain session has one lock-step sampler and refuses them"""
+        sessions only; a plain session has one lock-step sampler and refuses them.
+        collect_hidden=True (fs_lm_session_add_hidden, any session kind): the slot also keeps the slow transformer's pre-norm hidden state
+        of every iteration it runs -> poll_hidden(slot); its codes are those of the same add without it"""
         p = self._prompt(prompt, "prompt" if prefix is None else "body")
         slot = C.c_int(-1)
-        if sampling is not None or seed is not None:
-            if not (self.rows or self.per_slot):
+        if sampling is not None or seed is not None or collect_hidden:
+            if (sampling is not None or seed is not None) and not (self.rows or self.per_slot):
                 raise ValueError("per-slot sampling / seed need lm.session(per_slot=True) or lm.session(rows=True)")
             sp = C.byref(self._sampling(sampling)) if sampling is not None else None
             if seed is not None and not 0 <= int(seed) < 2**64:
                 raise ValueError("seed must fit an unsigned 64-bit integer")
             sd = C.byref(C.c_uint64(int(seed))) if seed is not None else None
-            _ffi.check(_ffi.lib().fs_lm_session_add_ex(self.lm._h, -1 if prefix is None else int(prefix), p.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                       int(p.shape[1]), int(max_new_tokens), sp, sd, C.byref(slot)))
+            fn = _ffi.lib().fs_lm_session_add_hidden if collect_hidden else _ffi.lib().fs_lm_session_add_ex
+            _ffi.check(fn(self.lm._h, -1 if prefix is None else int(prefix), p.ctypes.data_as(C.POINTER(C.c_uint32)),
+                          int(p.shape[1]), int(max_new_tokens), sp, sd, C.byref(slot)))
         elif prefix is None:
             _ffi.check(_ffi.lib().fs_lm_session_add(self.lm._h, p.ctypes.data_as(C.POINTER(C.c_uint32)), int(p.shape[1]), int(max_new_tokens),
                                                     C.byref(slot)))
@@ -375,6 +378,20 @@ class Session:
         _ffi.check(_ffi.lib().fs_lm_session_poll(self.lm._h, int(slot), out.ctypes.data_as(C.POINTER(C.c_uint32)), C.c_size_t(cap), C.byref(n),
                                                  C.byref(done)))
         return out[:, : n.value].copy(), bool(done.value)
+
+    def poll_hidden(self, slot, first=0):
+        """hidden-state rows [first, rows so far) of a slot admitted with collect_hidden=True -> f32 (n, dim).  One row per iteration the
+        slot ran, the terminating <|im_end|> one included: the slot has n_frames or n_frames + 1 rows (fs_lm_session_poll_hidden)"""
+        if int(first) < 0:
+            raise ValueError("first must not be negative")
+        n = C.c_size_t(0)
+        _ffi.check(_ffi.lib().fs_lm_session_poll_hidden(self.lm._h, int(slot), C.c_size_t(0), None, C.c_size_t(0), C.byref(n)))
+        rows = max(0, int(n.value) - int(first))
+        out = np.zeros((max(1, rows), self.lm.cfg["dim"]), np.float32)
+        if rows:
+            _ffi.check(_ffi.lib().fs_lm_session_poll_hidden(self.lm._h, int(slot), C.c_size_t(int(first)), out.ctypes.data_as(C.POINTER(C.c_float)),
+                                                            C.c_size_t(rows), C.byref(n)))
+        return out[:rows].copy()
 
     def release(self, slot):
         _ffi.check(_ffi.lib().fs_lm_session_release(self.lm._h, int(slot)))

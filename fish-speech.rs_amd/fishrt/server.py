@@ -30,12 +30,20 @@ session without `batch_size`.  Requests may then carry `temperature`, `top_p`, `
 the reference's `GenerateRequest` has none).  They are honoured on the batch-1 path and in per-slot / row sessions; a job that carries
 any of them never enters a lock-step sampler path -- it runs alone instead -- and a job with a `seed` always runs in the session on a
 `max_batch > 1` handle, alone or not, so that the same request gives the same audio whatever else the server is doing.
+
+Hidden states (`generate_hidden_states`, `handlers/send_hidden_states.rs`: body {text, speaker_id, return_audio} -> a stored zip of
+`hidden_states.npy`, optional `audio.wav`, `metadata.json`).  Its chunk jobs go through the same scheduler with `collect_hidden` set: in a
+session the slot is admitted with `add(..., collect_hidden=True)` and read with `poll_hidden`, outside one the job calls
+`generate_blocking_with_hidden`; a collecting job never enters a lock-step `generate_static_batch` (the reference's static batch returns
+no hidden states) -- it runs alone instead.  The reference's router (`server/src/main.rs:60-72`) does not mount that handler; the shim
+serves it as POST /v1/audio/hidden_states.
 """
 import collections
 import hashlib
 import io
 import json
 import queue
+import zipfile
 import secrets
 import threading
 import time
@@ -120,8 +128,9 @@ class AppState:  # server/lib/state.rs:23-29
 
 
 class _Job:
-    def __init__(self, cond, body, n_cond, allow_batch, sampling=None, seed=None):
+    def __init__(self, cond, body, n_cond, allow_batch, sampling=None, seed=None, collect_hidden=False):
         self.cond, self.body, self.n_cond, self.allow_batch, self.future = cond, body, n_cond, allow_batch, Future()
+        self.collect_hidden = bool(collect_hidden)  # the future then resolves to (codes, hidden f32 (iterations, dim)) instead of codes
         self.sampling, self.seed = sampling, seed  # request-level SamplingArgs / sampler seed (None: the server's / a fresh one)
         self.cond_key = hashlib.sha1(cond.tobytes()).hexdigest() if cond is not None else None
 
@@ -154,8 +163,8 @@ class Scheduler:
         self.th = threading.Thread(target=self._run, daemon=True)
         self.th.start()
 
-    def submit(self, cond, body, n_cond, allow_batch, sampling=None, seed=None):
-        j = _Job(cond, body, n_cond, allow_batch, sampling, seed)
+    def submit(self, cond, body, n_cond, allow_batch, sampling=None, seed=None, collect_hidden=False):
+        j = _Job(cond, body, n_cond, allow_batch, sampling, seed, collect_hidden)
         self.q.put(j)
         return j.future
 
@@ -203,9 +212,10 @@ class Scheduler:
                         self.q.put(_STOP)
                         break
                     batch.append(n)  # (a job that must not be batched still shares the gather; it runs alone below)
-            # (a job with request-level sampling settings never enters the lock-step sampler: it runs alone)
-            runs_alone = [b for b in batch if not b.allow_batch or self._own(b)]
-            together = [b for b in batch if b.allow_batch and not self._own(b)]
+            # (a job with request-level sampling settings never enters the lock-step sampler: it runs alone; so does a job that collects
+            # hidden states -- the static batch returns none)
+            runs_alone = [b for b in batch if not b.allow_batch or self._own(b) or b.collect_hidden]
+            together = [b for b in batch if b.allow_batch and not self._own(b) and not b.collect_hidden]
             try:
                 if len(together) >= 2:
                     self._batched(together)
@@ -329,6 +339,7 @@ class Scheduler:
                         n, done = sess.poll(slot, codes=False)
                         if done:
                             codes, _ = sess.poll(slot)
+                            hidden = sess.poll_hidden(slot) if live[slot].collect_hidden else None
                             sess.release(slot)
                             jb = live.pop(slot)
                             try:  # (jb has left `live`: from here on fail_all no longer sees it, so its future is resolved right here)
@@ -339,7 +350,7 @@ class Scheduler:
                                         raise RuntimeError("the scheduler is shutting down; the re-roll of a failed generation was dropped")
                                     self.q.put(jb)
                                 else:
-                                    jb.future.set_result(self._codes_out(codes))
+                                    jb.future.set_result(self._result(jb, codes, hidden))
                             except BaseException as e:
                                 if not jb.future.done():
                                     jb.future.set_exception(e)
@@ -362,6 +373,8 @@ class Scheduler:
         if self.per_slot_sampling and self.sess_mode in ("rows", "per_slot"):  # the job's own settings and seed, else the server's and a fresh seed
             sa = j.sampling or self.s.default_sampling_args
             kw = dict(sampling=sa.kw(), seed=(j.seed if j.seed is not None else self.s.seed_source()) & (2**64 - 1))
+        if j.collect_hidden:  # any session kind (fs_lm_session_add_hidden); the rows come back through poll_hidden
+            kw["collect_hidden"] = True
         if not self.session_prefixes or j.cond is None or j.cond.shape[1] < 1 or j.body.shape[1] < 1:
             return sess.add(j.full_prompt(), self.s.max_new_tokens, **kw), False
         pid = self.prefixes.get(j.cond_key)
@@ -386,9 +399,25 @@ class Scheduler:
             codes = codes - np.uint32(1)
         return codes
 
+    def _result(self, j, codes, hidden):
+        """what job j's future resolves to: codes, or (codes, hidden f32 (iterations, dim)) for a collecting job"""
+        codes = self._codes_out(codes)
+        if not j.collect_hidden:
+            return codes
+        hidden = np.asarray(hidden, np.float32)
+        return codes, np.ascontiguousarray(hidden.reshape(hidden.shape[0], hidden.shape[-1]))
+
     def _single(self, j):
         try:
             lm, sa = self.s.lm, getattr(j, "sampling", None) or self.s.default_sampling_args
+            hidden = None
+            if j.collect_hidden:  # generate_blocking_with_hidden (speech.rs:27-48): same call, plus the hidden rows
+                def gen(prompt, seed):
+                    nonlocal hidden
+                    codes, hidden = lm.generate_blocking_with_hidden(prompt, self.s.max_new_tokens, True, seed=seed, **sa.kw())
+                    return codes
+            else:
+                gen = lambda prompt, seed: lm.generate_blocking(prompt, self.s.max_new_tokens, seed=seed, **sa.kw())
             own_seed = getattr(j, "seed", None)
             draw = (lambda: own_seed) if own_seed is not None else self.s.seed_source
             self.stats["jobs"] += 1
@@ -399,7 +428,7 @@ class Scheduler:
             else:
                 lm.clear_slow_layer_caches()
                 prompt = j.full_prompt()
-            codes = lm.generate_blocking(prompt, self.s.max_new_tokens, seed=draw(), **sa.kw())
+            codes = gen(prompt, draw())
             lm.clear_slow_caches_until(j.n_cond)  # speech.rs:40
             self.cached_key = j.cond_key if j.cond is not None else None
             if codes.shape[1] == self.s.max_new_tokens and getattr(j, "reroll", False):  # this WAS the re-roll of a session job
@@ -407,17 +436,18 @@ class Scheduler:
             if codes.shape[1] == self.s.max_new_tokens:  # speech.rs:41-61: "Failed generation suspected. Rerolling once"
                 self.stats["rerolls"] += 1
                 lm.clear_slow_layer_caches()
-                codes2 = lm.generate_blocking(j.full_prompt(), self.s.max_new_tokens, seed=self.s.seed_source(), **sa.kw())
+                codes2 = gen(j.full_prompt(), self.s.seed_source())
                 lm.clear_slow_caches_until(j.n_cond)
                 if codes2.shape[1] == self.s.max_new_tokens:
                     raise RuntimeError("Encoded input failed for second time. Bailing")
                 codes = codes2
-            j.future.set_result(self._codes_out(codes))
+            j.future.set_result(self._result(j, codes, hidden))
         except BaseException as e:
             self.cached_key = None
             j.future.set_exception(e)
 
     def _batched(self, jobs):
+        assert not any(j.collect_hidden for j in jobs), "a job that collects hidden states never joins a lock-step batch"
         lm, sa = self.s.lm, self.s.default_sampling_args
         self.stats["jobs"] += len(jobs)
         self.stats["batches"] += 1
@@ -449,10 +479,10 @@ class AppError(Exception):  # handlers/error.rs:17-31 -> HTTP 500 with the messa
     pass
 
 
-def _prompts_for_request(state, req):
+def _prompts_for_request(state, req, unconditioned=True):
     s = state.lm
     voice = req.get("voice")
-    if voice == "unconditioned":
+    if voice == "unconditioned" and unconditioned:
         emb = None
     else:
         with s.voices_lock:
@@ -536,6 +566,48 @@ def generate_speech(state, req):
         return 500, "text/plain", f"Something went wrong: {e}".encode()
 
 
+HIDDEN_FRAME_RATE = 21.535  # send_hidden_states.rs:114
+
+
+def generate_hidden_states(state, req):
+    """POST /v1/audio/hidden_states (handlers/send_hidden_states.rs:15-126): {text, speaker_id, return_audio} -> (status, content_type, body).
+    The body is a stored (uncompressed) zip: hidden_states.npy = f32 [frames, dim], the slow transformer's pre-norm hidden state of every
+    generator iteration of every text chunk in order (:52-69,82-96); audio.wav when return_audio (:98-104); metadata.json =
+    {frame_count, frame_rate, hidden_dim} (:106-117).  Server default sampling, default-voice fallback (:26-33)."""
+    for k in ("text", "speaker_id", "return_audio"):
+        if k not in req:
+            return 422, "application/json", json.dumps({"detail": f"missing field `{k}`"}).encode()
+    try:
+        want_audio = bool(req["return_audio"])
+        n_cond, cond, bodies = _prompts_for_request(state, dict(voice=req["speaker_id"], input=req["text"]), unconditioned=False)
+        # chunk jobs like a speech request's: they may join a session wherever a speech chunk without `batch_size` may
+        want_batch = getattr(state, "auto_batch", False) or getattr(state.scheduler, "per_slot_sampling", False)
+        futs = [state.scheduler.submit(cond, b, n_cond, state.lm.max_batch > 1 and want_batch, collect_hidden=True) for b in bodies]
+        hidden, pcm = [], []
+        for f in futs:
+            codes, hid = f.result()
+            hidden.append(hid)
+            if want_audio:
+                with state.codec_lock:
+                    pcm.append(state.codec.decode(np.ascontiguousarray(codes[None]))[0, 0])
+        if not hidden:
+            raise AppError("Failed to concatenate hidden states")  # (:82-83: no text chunk, nothing to concatenate)
+        hs = np.ascontiguousarray(np.concatenate(hidden, 0), np.float32)
+        buf = io.BytesIO()
+        with zipfile.ZipFile(buf, "w", zipfile.ZIP_STORED) as z:
+            npy = io.BytesIO()
+            np.lib.format.write_array(npy, hs, version=(1, 0))
+            z.writestr("hidden_states.npy", npy.getvalue())
+            if want_audio:
+                wav = io.BytesIO()
+                fwav.write_pcm_as_wav(wav, np.concatenate(pcm), state.sample_rate)
+                z.writestr("audio.wav", wav.getvalue())
+            z.writestr("metadata.json", json.dumps({"frame_count": int(hs.shape[0]), "frame_rate": HIDDEN_FRAME_RATE, "hidden_dim": int(hs.shape[1])}))
+        return 200, "application/zip", buf.getvalue()
+    except BaseException as e:
+        return 500, "text/plain", f"Something went wrong: {e}".encode()
+
+
 def supported_voices(state):
     with state.lm.voices_lock:
         return list(state.lm.voices.keys())
@@ -610,7 +682,7 @@ def _multipart_first_file(content_type, body):
 
 
 def make_app(state):
-    """FastAPI application with the reference's three routes (server/src/main.rs:60-72)."""
+    """FastAPI application with the reference's three routes (server/src/main.rs:60-72) and its hidden-states handler (module docstring)."""
     from fastapi import FastAPI, Request
     from fastapi.responses import JSONResponse, Response, StreamingResponse
 
@@ -627,6 +699,16 @@ def make_app(state):
         if isinstance(body, (bytes, bytearray)):
             return Response(content=body, status_code=status, media_type=ctype)
         return StreamingResponse(body, status_code=status, media_type=ctype)
+
+    @app.post("/v1/audio/hidden_states")
+    async def hidden_states(request: Request):
+        import asyncio
+        try:
+            req = await request.json()
+        except Exception:
+            return JSONResponse({"detail": "body must be a JSON object"}, status_code=422)
+        status, ctype, body = await asyncio.get_event_loop().run_in_executor(None, generate_hidden_states, state, req)
+        return Response(content=body, status_code=status, media_type=ctype)
 
     @app.post("/v1/audio/encoding")
     async def encoding(request: Request):

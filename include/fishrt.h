@@ -329,6 +329,25 @@ int fs_lm_session_add_prefixed(fs_lm_t* lm, int prefix_id, const uint32_t* body,
  * *slot = -1 when no slot / KV pages are free right now, as fs_lm_session_add. */
 int fs_lm_session_add_ex(fs_lm_t* lm, int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling,
                          const uint64_t* seed, int* slot);
+/* Hidden states of a session slot (the reference's server/lib/handlers/send_hidden_states.rs calls generate_blocking_with_hidden with
+ * collect_hidden_states = true; fs_lm_generate_with_hidden is that call at batch 1).  fs_lm_session_add_hidden IS fs_lm_session_add_ex in
+ * every respect -- prefix_id / sampling / seed rules per session kind, *slot = -1 when nothing is free, the slot's codes bit for bit --
+ * and the slot additionally keeps the slow transformer's pre-norm hidden state (the `hidden_states` of forward_generate, dual_ar.rs:629-634:
+ * the row the head's RMSNorm reads and the fast decoder starts from) of every generator iteration it runs.  Valid in plain,
+ * FS_SESSION_PER_SLOT and FS_SESSION_ROWS sessions; collecting and non-collecting slots mix freely and run the same step (a small kernel
+ * behind the slow head reads a per-slot pointer table, so admitting or releasing a collector never re-captures the step graph).
+ * Device memory: one f32 [1 + max(0, max_new_tokens - L + 1)][dim] buffer per collecting slot (iterations clipped by max_seq_len as for
+ * the add), taken from a per-handle pool when the slot is admitted and returned at fs_lm_session_release / fs_lm_session_end; nothing is
+ * allocated for slots that do not collect.
+ * fs_lm_session_poll_hidden: *n_rows (nullable) = rows the slot has so far; hidden_out (NULL: query only) f32 [cap_rows, dim] receives rows
+ * [first_row, min(*n_rows, first_row + cap_rows)).  Row count rule == the *n_hidden rule of fs_lm_generate_with_hidden: one row per
+ * iteration the slot ran, in order, row 0 being the iteration over the last prompt position (whose frame is emitted unconditionally) and
+ * the terminating <|im_end|> iteration, whose frame is not emitted, included -- so *n_rows is the slot's n_frames or n_frames + 1.  A
+ * slot still prefilling has 0 rows; a released and re-admitted slot starts again at row 0.  A slot that was not admitted with
+ * fs_lm_session_add_hidden is an error that says so. */
+int fs_lm_session_add_hidden(fs_lm_t* lm, int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling,
+                             const uint64_t* seed, int* slot);
+int fs_lm_session_poll_hidden(fs_lm_t* lm, int slot, size_t first_row, float* hidden_out, size_t cap_rows, size_t* n_rows);
 /* out[8] = {free pages, pages referenced by more than one owner, live prefixes, prefill passes, tokens prefilled,
  *           prefix tokens reused, tail pages copied, prefill-stream microseconds (HIP events around each pass)};
  * counters since fs_lm_session_begin */
