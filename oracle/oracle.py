@@ -170,6 +170,47 @@ class OracleLM:
     def force_kv_diff(self, layer):
         return float(lib().orc_lm_force_kv_diff(self.h, int(layer)))
 
+    def force_kv_rows(self, layer, k, v):
+        """test hook, the multi-row force_kv: the NEXT batch-1 pass of slow layer `layer`, which must have exactly n rows, attends over and
+        caches these K / V rows, f32 (n, Hkv, D) as in set_kv, instead of its own (one-shot; a pass of another length raises).  Afterwards
+        force_kv_diff(layer) is the largest distance in its units and force_kv_row_excess(layer) the per-row record"""
+        k = np.ascontiguousarray(k, np.float32); v = np.ascontiguousarray(v, np.float32)
+        assert k.shape == v.shape and k.ndim == 3 and k.shape[1:] == (self.cfg["n_local_heads"], self.cfg["head_dim"])
+        if lib().orc_lm_force_kv_rows(self.h, int(layer), int(k.shape[0]), _p(k, C.c_float), _p(v, C.c_float)) != 0:
+            raise RuntimeError("orc_lm_force_kv_rows: bad layer / no rows")
+
+    def force_kv_row_excess(self, layer, split=False):
+        """per row of the last force_kv_rows pass of `layer`: max over the row's K and V entries of
+        max(0, |the oracle's own entry before its bf16 rounding - forced entry| - half a bf16 ulp of the forced entry) -- ~0 for a correctly
+        rounded neighbour of any magnitude, absolute f32 error otherwise.  f32 (n,); split=True: (2, n) = K, V apart"""
+        n = lib().orc_lm_force_kv_row_records(self.h, int(layer), None, None, None)
+        if n < 0:
+            raise RuntimeError("orc_lm_force_kv_row_diff: bad layer")
+        out = np.zeros((2, n), np.float32)
+        if split:
+            lib().orc_lm_force_kv_row_records(self.h, int(layer), _p(out[0], C.c_float), _p(out[1], C.c_float), None)
+            return out
+        lib().orc_lm_force_kv_row_diff(self.h, int(layer), _p(out[0], C.c_float))
+        return out[0]
+
+    def force_kv_row_units(self, layer):
+        """per row of the last force_kv_rows pass: the distance in the units of force_kv_diff (bf16 ulp of the forced value, floored at 2^-17)"""
+        n = lib().orc_lm_force_kv_row_records(self.h, int(layer), None, None, None)
+        out = np.zeros(max(n, 0), np.float32)
+        lib().orc_lm_force_kv_row_records(self.h, int(layer), None, None, _p(out, C.c_float))
+        return out
+
+    def get_kv(self, layer, t0, n):
+        """test hook: cached K / V rows [t0, t0 + n) of slow layer `layer` (batch 1; 1000 + l: fast decoder layer l), f32 (n, Hkv, D) each"""
+        k = np.empty((int(n), self.cfg["n_local_heads"], self.cfg["head_dim"]), np.float32); v = np.empty_like(k)
+        if lib().orc_lm_get_kv(self.h, int(layer), int(t0), int(n), _p(k, C.c_float), _p(v, C.c_float)) != 0:
+            raise RuntimeError("orc_lm_get_kv: rows outside the cache")
+        return k, v
+
+    def set_acc64(self, on):
+        """test hook: accumulate the sums of linear / rms_norm / attention in double (the yardstick for the f32 oracle's own summation noise)"""
+        lib().orc_lm_set_acc64(self.h, int(on))
+
     def set_kv(self, layer, t0, k, v):
         """test hook: overwrite cached K / V rows [t0, t0 + n) of slow layer `layer` (batch 1; 1000 + l: fast decoder layer l); k, v: f32 (n, Hkv, D)"""
         k = np.ascontiguousarray(k, np.float32); v = np.ascontiguousarray(v, np.float32)

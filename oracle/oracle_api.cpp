@@ -1,4 +1,5 @@
 // TEST INFRASTRUCTURE ONLY (oracle/).  Flat C API over the CPU restatement, for ctypes (oracle/oracle.py).
+#include <algorithm>
 #include <cstring>
 #include <string>
 
@@ -103,8 +104,60 @@ int orc_lm_force_kv(void* p, int layer, const float* k, const float* v) {
     Block& b = fast ? lm->fast_layers[layer] : lm->layers[layer];
     const size_t n = (size_t)lm->a.n_local_heads * lm->a.head_dim;
     b.force_k.assign(k, k + n); b.force_v.assign(v, v + n);
+    b.force_n = 0;
     return 0;
 }
+static Block* lm_block(void* p, int layer) {
+    LM* lm = (LM*)p;
+    const bool fast = layer >= 1000;
+    if (fast) layer -= 1000;
+    if (layer < 0 || layer >= (int)(fast ? lm->fast_layers.size() : lm->layers.size())) return nullptr;
+    return fast ? &lm->fast_layers[layer] : &lm->layers[layer];
+}
+// test hook: the next batch-1 pass of this layer, which must have exactly n rows, attends over (and caches) these K / V rows [n][Hkv][D] (the
+// layout of orc_lm_set_kv) instead of its own -- the prefill counterpart of orc_lm_force_kv (tests/test_prefill_forced_gpu.py).  One-shot;
+// a pass of another length throws (and disarms)
+int orc_lm_force_kv_rows(void* p, int layer, int n, const float* k, const float* v) {
+    Block* b = lm_block(p, layer);
+    if (!b || n < 1) return 1;
+    const size_t e = (size_t)n * ((LM*)p)->a.n_local_heads * ((LM*)p)->a.head_dim;
+    b->force_k.assign(k, k + e); b->force_v.assign(v, v + e);
+    b->force_n = n;
+    return 0;
+}
+// per row of the last orc_lm_force_kv_rows pass of this layer: the excess (see Block::force_row_excess_k), max of K and V.  Returns the row count
+int orc_lm_force_kv_row_diff(void* p, int layer, float* out /*[n]*/) {
+    Block* b = lm_block(p, layer);
+    if (!b) return -1;
+    for (size_t i = 0; i < b->force_row_excess_k.size(); ++i) out[i] = std::max(b->force_row_excess_k[i], b->force_row_excess_v[i]);
+    return (int)b->force_row_excess_k.size();
+}
+// the same, K and V apart, and the rows' distances in the units of orc_lm_force_kv_diff (any of the three may be null)
+int orc_lm_force_kv_row_records(void* p, int layer, float* excess_k, float* excess_v, float* units) {
+    Block* b = lm_block(p, layer);
+    if (!b) return -1;
+    const size_t n = b->force_row_excess_k.size();
+    if (excess_k) std::memcpy(excess_k, b->force_row_excess_k.data(), sizeof(float) * n);
+    if (excess_v) std::memcpy(excess_v, b->force_row_excess_v.data(), sizeof(float) * n);
+    if (units) std::memcpy(units, b->force_row_diff.data(), sizeof(float) * n);
+    return (int)n;
+}
+// test hook: read cached K / V rows [t0, t0 + n) of one layer (batch 1) back, in the layout orc_lm_set_kv takes
+int orc_lm_get_kv(void* p, int layer, int t0, int n, float* k, float* v) {
+    Block* bp = lm_block(p, layer);
+    if (!bp) return 1;
+    const Block& b = *bp;
+    const int Hk = ((LM*)p)->a.n_local_heads, D = ((LM*)p)->a.head_dim, T = b.kv_len;
+    if (b.kv_b != 1 || t0 < 0 || n < 0 || t0 + n > T) return 1;
+    for (int t = 0; t < n; ++t)
+        for (int g = 0; g < Hk; ++g)
+            for (int d = 0; d < D; ++d) {
+                k[((size_t)t * Hk + g) * D + d] = b.k[((size_t)g * T + t0 + t) * D + d];
+                v[((size_t)t * Hk + g) * D + d] = b.v[((size_t)g * T + t0 + t) * D + d];
+            }
+    return 0;
+}
+void orc_lm_set_acc64(void* p, int on) { ((LM*)p)->acc64 = on != 0; }
 float orc_lm_force_kv_diff(void* p, int layer) {
     LM* lm = (LM*)p;
     const bool fast = layer >= 1000;

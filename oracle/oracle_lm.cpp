@@ -24,12 +24,20 @@ namespace oracle {
 // ---------------------------------------------------------------- basic ops (candle semantics)
 
 // candle_nn::Linear without bias: y = x . W^T   (W row-major [N,K])
-static void linear(const float* x, int M, const float* W, int N, int K, float* y) {
+// acc64 (LM::acc64, test hook): the same products summed in double -- the yardstick for the f32 restatement's own summation noise
+static void linear(const float* x, int M, const float* W, int N, int K, float* y, bool acc64 = false) {
 #pragma omp parallel for schedule(static) if ((size_t)N * K * M > (1u << 18))
     for (int n = 0; n < N; ++n) {
         const float* w = W + (size_t)n * K;
         for (int m = 0; m < M; ++m) {
             const float* xm = x + (size_t)m * K;
+            if (acc64) {
+                double acc = 0.0;
+#pragma omp simd reduction(+ : acc)
+                for (int k = 0; k < K; ++k) acc += (double)xm[k] * (double)w[k];
+                y[(size_t)m * N + n] = (float)acc;
+                continue;
+            }
             float acc = 0.f;
 #pragma omp simd reduction(+ : acc)
             for (int k = 0; k < K; ++k) acc += xm[k] * w[k];
@@ -39,11 +47,16 @@ static void linear(const float* x, int M, const float* W, int N, int K, float* y
 }
 
 // candle_nn::RmsNorm (f32): x / sqrt(mean(x^2) + eps) * w
-static void rms_norm(const float* x, int M, int D, const float* w, float eps, float* y) {
+static void rms_norm(const float* x, int M, int D, const float* w, float eps, float* y, bool acc64 = false) {
     for (int m = 0; m < M; ++m) {
         const float* xm = x + (size_t)m * D;
         float s = 0.f;
-        for (int i = 0; i < D; ++i) s += xm[i] * xm[i];
+        if (acc64) {
+            double s2 = 0.0;
+            for (int i = 0; i < D; ++i) s2 += (double)xm[i] * (double)xm[i];
+            s = (float)s2;
+        } else
+            for (int i = 0; i < D; ++i) s += xm[i] * xm[i];
         float d = std::sqrt(s / (float)D + eps);
         for (int i = 0; i < D; ++i) y[(size_t)m * D + i] = (xm[i] / d) * w[i];
     }
@@ -177,8 +190,8 @@ void LM::block_forward(Block& blk, float* x, int B, int L, int input_pos, int /*
     const int D = a.dim, H = a.n_head, Hk = a.n_local_heads, Dh = a.head_dim, I = a.intermediate_size;
     const int QKV = (H + 2 * Hk) * Dh, half = Dh / 2, M = B * L;
     std::vector<float> xn((size_t)M * D), qkv((size_t)M * QKV);
-    rms_norm(x, M, D, blk.attention_norm.data(), a.norm_eps, xn.data());
-    linear(xn.data(), M, blk.wqkv.data(), QKV, D, qkv.data());
+    rms_norm(x, M, D, blk.attention_norm.data(), a.norm_eps, xn.data(), acc64);
+    linear(xn.data(), M, blk.wqkv.data(), QKV, D, qkv.data(), acc64);
 
     if (input_pos + L > a.max_seq_len) throw std::runtime_error("input_pos + seqlen exceeds max_seq_len (dual_ar.rs:623)");
     // q: (B,H,L,Dh), new k/v: (B,Hk,L,Dh); interleaved RoPE (rope_i) on q and k (:239-249)
@@ -206,23 +219,57 @@ void LM::block_forward(Block& blk, float* x, int B, int L, int input_pos, int /*
                     vn[(((size_t)b * Hk + h) * L + l) * Dh + d] = row[(H + Hk) * Dh + h * Dh + d];
             }
         }
+    const bool forced = !blk.force_k.empty();
+    std::vector<float> kraw, vraw;  // the restatement's own entries before the bf16 rounding (force_row_excess is measured against these)
+    if (forced && blk.force_n > 0) { kraw = kn; vraw = vn; }
     if (kv_round_bf16) {
         for (auto& f : kn) f = fsgen::round_bf16(f);
         for (auto& f : vn) f = fsgen::round_bf16(f);
     }
-    if (!blk.force_k.empty()) {  // test hook: see Block::force_k
-        if (B != 1 || L != 1 || blk.force_k.size() != kn.size()) throw std::runtime_error("orc_lm_force_kv: needs a batch-1 single-token step");
+    if (forced) {  // test hook: see Block::force_k
+        std::vector<float> fk, fv;
+        fk.swap(blk.force_k); fv.swap(blk.force_v);  // one-shot, also when the pass is refused
+        const int n = blk.force_n;
+        blk.force_n = 0;
+        if (n == 0) {
+            if (B != 1 || L != 1 || fk.size() != kn.size()) throw std::runtime_error("orc_lm_force_kv: needs a batch-1 single-token step");
+        } else {
+            if (B != 1 || L != n || fk.size() != kn.size())
+                throw std::runtime_error("orc_lm_force_kv_rows: " + std::to_string(n) + " rows armed, the pass has B " + std::to_string(B) + ", L " + std::to_string(L));
+            // [n][Hkv][D] (the layout of orc_lm_set_kv) -> (Hkv, L, Dh), the layout of kn / vn at batch 1
+            std::vector<float> tk(fk.size()), tv(fv.size());
+            for (int l = 0; l < L; ++l)
+                for (int g = 0; g < Hk; ++g)
+                    for (int d = 0; d < Dh; ++d) {
+                        tk[((size_t)g * L + l) * Dh + d] = fk[((size_t)l * Hk + g) * Dh + d];
+                        tv[((size_t)g * L + l) * Dh + d] = fv[((size_t)l * Hk + g) * Dh + d];
+                    }
+            fk.swap(tk); fv.swap(tv);
+            blk.force_row_diff.assign(L, 0.f);
+            blk.force_row_excess_k.assign(L, 0.f);
+            blk.force_row_excess_v.assign(L, 0.f);
+        }
         float worst = 0.f;
         for (size_t i = 0; i < kn.size(); ++i) {
             // bf16 ulp (8 significant bits) of the forced value, floored at 2^-17: below |x| ~ 1e-3 the f32 summation-order noise of the
             // projection (~1e-6 absolute) is worth several ulps of the tiny value without being a rounding-boundary flip of anything that matters
-            const float uk = std::ldexp(1.f, std::max(std::ilogb(std::max(std::fabs(blk.force_k[i]), 1e-30f)) - 7, -17));
-            const float uv = std::ldexp(1.f, std::max(std::ilogb(std::max(std::fabs(blk.force_v[i]), 1e-30f)) - 7, -17));
-            worst = std::max(worst, std::max(std::fabs(kn[i] - blk.force_k[i]) / uk, std::fabs(vn[i] - blk.force_v[i]) / uv));
+            const int ek = std::ilogb(std::max(std::fabs(fk[i]), 1e-30f)) - 7, ev = std::ilogb(std::max(std::fabs(fv[i]), 1e-30f)) - 7;
+            const float uk = std::ldexp(1.f, std::max(ek, -17)), uv = std::ldexp(1.f, std::max(ev, -17));
+            const float units = std::max(std::fabs(kn[i] - fk[i]) / uk, std::fabs(vn[i] - fv[i]) / uv);
+            worst = std::max(worst, units);
+            if (n > 0) {
+                // excess: what is left of |own (unrounded) - forced| once half a bf16 ulp of the forced value (unfloored) is taken off -- a
+                // correctly rounded neighbour has ~0 whatever its magnitude, the remainder is absolute f32 error
+                const int row = (int)((i / Dh) % L);
+                const float xk = std::max(0.f, std::fabs(kraw[i] - fk[i]) - 0.5f * std::ldexp(1.f, ek));
+                const float xv = std::max(0.f, std::fabs(vraw[i] - fv[i]) - 0.5f * std::ldexp(1.f, ev));
+                blk.force_row_diff[row] = std::max(blk.force_row_diff[row], units);
+                blk.force_row_excess_k[row] = std::max(blk.force_row_excess_k[row], xk);
+                blk.force_row_excess_v[row] = std::max(blk.force_row_excess_v[row], xv);
+            }
         }
         blk.force_diff = worst;
-        kn = blk.force_k; vn = blk.force_v;
-        blk.force_k.clear(); blk.force_v.clear();
+        kn.swap(fk); vn.swap(fv);
     }
     // Tensor::cat(&[prev, new], 2): full re-copy every call (:316-324)
     const int Tp = blk.kv_len, T = Tp + L;
@@ -257,30 +304,47 @@ void LM::block_forward(Block& blk, float* x, int B, int L, int input_pos, int /*
                 float mx = -std::numeric_limits<float>::infinity();
                 for (int tt = 0; tt < T; ++tt) {
                     float acc = 0.f;
-                    for (int d = 0; d < Dh; ++d) acc += ql[d] * (K[(size_t)tt * Dh + d] * scale);  // q . (k^T * scale) (:260)
+                    if (acc64) {
+                        double a2 = 0.0;
+                        for (int d = 0; d < Dh; ++d) a2 += (double)ql[d] * (double)(K[(size_t)tt * Dh + d] * scale);
+                        acc = (float)a2;
+                    } else
+                        for (int d = 0; d < Dh; ++d) acc += ql[d] * (K[(size_t)tt * Dh + d] * scale);  // q . (k^T * scale) (:260)
                     if (L > 1 && mask[(size_t)l * T + tt]) acc = -std::numeric_limits<float>::infinity();
                     w[tt] = acc;
                     mx = std::max(mx, acc);
                 }
                 float sum = 0.f;
-                for (int tt = 0; tt < T; ++tt) { w[tt] = std::exp(w[tt] - mx); sum += w[tt]; }
+                if (acc64) {
+                    double s2 = 0.0;
+                    for (int tt = 0; tt < T; ++tt) { w[tt] = std::exp(w[tt] - mx); s2 += (double)w[tt]; }
+                    sum = (float)s2;
+                } else
+                    for (int tt = 0; tt < T; ++tt) { w[tt] = std::exp(w[tt] - mx); sum += w[tt]; }
                 for (int tt = 0; tt < T; ++tt) w[tt] /= sum;
                 float* yo = &y[((size_t)b * L + l) * D + (size_t)h * Dh];
+                if (acc64) {
+                    std::vector<double> y2(Dh, 0.0);
+                    for (int tt = 0; tt < T; ++tt)
+                        for (int d = 0; d < Dh; ++d) y2[d] += (double)w[tt] * (double)V[(size_t)tt * Dh + d];
+                    for (int d = 0; d < Dh; ++d) yo[d] = (float)y2[d];
+                    continue;
+                }
                 for (int d = 0; d < Dh; ++d) yo[d] = 0.f;
                 for (int tt = 0; tt < T; ++tt)
                     for (int d = 0; d < Dh; ++d) yo[d] += w[tt] * V[(size_t)tt * Dh + d];
             }
         }
     std::vector<float> att((size_t)M * D);
-    linear(y.data(), M, blk.wo.data(), D, D, att.data());
+    linear(y.data(), M, blk.wo.data(), D, D, att.data(), acc64);
     for (size_t i = 0; i < (size_t)M * D; ++i) x[i] = x[i] + att[i];  // residual + attention (:437)
     // FFN: w2(silu(w1 x) * w3 x) (:160-165)
-    rms_norm(x, M, D, blk.ffn_norm.data(), a.norm_eps, xn.data());
+    rms_norm(x, M, D, blk.ffn_norm.data(), a.norm_eps, xn.data(), acc64);
     std::vector<float> h1((size_t)M * I), h3((size_t)M * I);
-    linear(xn.data(), M, blk.w1.data(), I, D, h1.data());
-    linear(xn.data(), M, blk.w3.data(), I, D, h3.data());
+    linear(xn.data(), M, blk.w1.data(), I, D, h1.data(), acc64);
+    linear(xn.data(), M, blk.w3.data(), I, D, h3.data(), acc64);
     for (size_t i = 0; i < (size_t)M * I; ++i) h1[i] = silu(h1[i]) * h3[i];
-    linear(h1.data(), M, blk.w2.data(), D, I, att.data());
+    linear(h1.data(), M, blk.w2.data(), D, I, att.data(), acc64);
     for (size_t i = 0; i < (size_t)M * D; ++i) x[i] = x[i] + att[i];
 }
 
@@ -294,14 +358,14 @@ void LM::forward_generate(const uint32_t* toks, int B, int L, int input_pos, flo
     std::vector<float> last((size_t)B * D), nrm((size_t)B * D);
     for (int b = 0; b < B; ++b)
         std::memcpy(&last[(size_t)b * D], &x[((size_t)b * L + (L - 1)) * D], sizeof(float) * D);  // narrow(1, L-1, 1)
-    rms_norm(last.data(), B, D, norm.data(), a.norm_eps, nrm.data());
+    rms_norm(last.data(), B, D, norm.data(), a.norm_eps, nrm.data(), acc64);
     if (logits) {
         if (full_vocab_head) {
-            linear(nrm.data(), B, output.data(), a.vocab_size, D, logits);
+            linear(nrm.data(), B, output.data(), a.vocab_size, D, logits, acc64);
         } else {  // test-speed option: only rows [im_end, V) are ever consumed downstream (utils.rs:15)
             const int lo = (int)std::min(t.im_end_id, t.has_semantic_end ? t.semantic_start_id : t.im_end_id);  // (generic layout: utils.rs:17-30)
             std::vector<float> part((size_t)B * (a.vocab_size - lo));
-            linear(nrm.data(), B, &output[(size_t)lo * D], a.vocab_size - lo, D, part.data());
+            linear(nrm.data(), B, &output[(size_t)lo * D], a.vocab_size - lo, D, part.data(), acc64);
             for (int b = 0; b < B; ++b) {
                 for (int v = 0; v < lo; ++v) logits[(size_t)b * a.vocab_size + v] = 0.f;
                 std::memcpy(&logits[(size_t)b * a.vocab_size + lo], &part[(size_t)b * (a.vocab_size - lo)],

@@ -45,6 +45,11 @@ struct Block {
     // kernel's bf16 entries); force_diff = largest |own - forced| of that step in units of the forced value's bf16 ulp
     std::vector<float> force_k, force_v;
     float force_diff = 0.f;
+    // orc_lm_force_kv_rows: force_n > 0 rows [n][Hkv][D] armed for the next batch-1 pass of exactly n rows (0: the single-token hook above).
+    // Per row of that pass: force_row_diff = the units of force_diff; force_row_excess_k / _v = max over the row's entries of
+    // max(0, |own entry BEFORE its bf16 rounding - forced| - half a bf16 ulp of the forced value), an absolute f32 distance
+    int force_n = 0;
+    std::vector<float> force_row_diff, force_row_excess_k, force_row_excess_v;
 };
 
 // fish_speech_core/lib/lm/sampling/rep_pen.rs:4-72 (SingleBatchedRepPenProcessor)
@@ -65,6 +70,7 @@ struct LM {
     ModelArgs a;
     TokenCfg t;
     bool kv_round_bf16 = false;  // mimic a bf16 KV cache (GPU bf16 mode comparison only)
+    bool acc64 = false;          // test hook: linear / rms_norm / attention sums of the slow and fast passes accumulate in double
     int n_threads = 0;
     std::vector<float> embeddings, codebook_embeddings, fast_embeddings, output, fast_output, norm, fast_norm;
     std::vector<Block> layers, fast_layers;
