@@ -15,6 +15,7 @@
 #include <cstring>
 #include <chrono>
 #include <condition_variable>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <type_traits>
@@ -215,12 +216,7 @@ class LM final : public LMBase {
     ~LM() override {
         (void)hipSetDevice(device_);
         (void)hipStreamSynchronize(st_);
-        for (auto& kvp : batch_graphs_) if (kvp.second) (void)hipGraphExecDestroy(kvp.second);
-        for (auto& kvp : multi_graphs_) if (kvp.second) (void)hipGraphExecDestroy(kvp.second);
-        for (auto& kvp : graphs_) {
-            if (kvp.second.first) (void)hipGraphExecDestroy(kvp.second.first);
-            if (kvp.second.second) (void)hipGraphExecDestroy(kvp.second.second);
-        }
+        destroy_graphs();
         for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
         for (auto& e : ev_batch_) if (e) (void)hipEventDestroy(e);
         if (h_pin_) (void)hipHostFree(h_pin_);
@@ -383,12 +379,7 @@ class LM final : public LMBase {
         cap_frames_ = n_frames;
         if (n_frames) { d_cap_.alloc(sizeof(float) * (size_t)n_frames * 9 * 2048); FS_HIP(hipMemset(d_cap_.p, 0, d_cap_.n)); }
         else d_cap_ = DevBuf();
-        for (auto& kv : graphs_) { (void)hipGraphExecDestroy(kv.second.first); (void)hipGraphExecDestroy(kv.second.second); }
-        graphs_.clear();  // the captured launches carry the buffer pointer
-        for (auto& kv : multi_graphs_) if (kv.second) (void)hipGraphExecDestroy(kv.second);
-        multi_graphs_.clear();
-        g_frame_ = g_step_ = nullptr;
-        drop_batch_graphs();  // (the row-path step graphs include the capture kernels only while the hook is armed)
+        destroy_graphs();  // the captured launches carry the buffer pointer (the row-path step graphs include the capture kernels only while the hook is armed)
         if (!n_frames) d_rcap_ = DevBuf();
     }
     void debug_read(float* out, int n_frames) override {
@@ -554,18 +545,11 @@ class LM final : public LMBase {
         validate_tokens(prompt, (size_t)C1 * L, 1, L);
         const int n_cached = seq_len_[0];
         if (n_cached + L > a_.max_seq_len) throw Error("prompt exceeds max_seq_len (dual_ar.rs:623-624)");
-        // iteration budget (single_batch.rs:61,77,193-197): prefill iteration + one per k with L + k - 1 <= max_new_tokens
-        long long n_iter = 1 + std::max<long long>(0, (long long)max_new_tokens - L + 1);
-        bool clamped = false;
-        const long long room = (long long)a_.max_seq_len - (n_cached + L) + 1;  // iterations that fit the RoPE table / KV
-        if (n_iter > room) { n_iter = room; clamped = true; }
-        FS_REQUIRE(n_iter <= out_cap_, "generation longer than the output staging buffer");
+        const Budget budget = iter_budget(max_new_tokens, L, n_cached);
+        const long long n_iter = budget.n_iter;
         ensure_capacity(0, n_cached + L + (int)n_iter - 1);
         // device-side setup
-        SampleCfg cfg = base_cfg();
-        cfg.temp = (float)s.temp; cfg.top_p = (float)s.top_p; cfg.top_p64 = s.top_p;
-        cfg.top_k = (int)std::min<uint64_t>(s.top_k, 1u << 30);
-        cfg.rep_pen = s.repetition_penalty; cfg.ignore_eos = (flags & FS_GEN_IGNORE_EOS) ? 1 : 0;
+        SampleCfg cfg = make_cfg(s, flags);
         cfg.batch_rows = batch_rows_; cfg.batch_row = batch_row_; cfg.batch_calls = a_.num_codebooks + 1;  // batch_rows > 0 only inside generate_batch_sequential
         FS_HIP(hipMemcpyAsync(d_cfg_.p, &cfg, sizeof(cfg), hipMemcpyHostToDevice, st_));
         // greedy decoding on a Fish-geometry bf16 handle: the 8 fast-decoder passes of a frame run as ONE persistent launch
@@ -584,9 +568,8 @@ class LM final : public LMBase {
         if (hidden_out && !d_hidden_.p) d_hidden_.alloc(sizeof(float) * (size_t)out_cap_ * a_.dim);
         float* hid_dev = hidden_out ? d_hidden_.as<float>() : nullptr;
         FS_HIP(hipMemcpyAsync(d_hid_slot_.p, &hid_dev, sizeof(hid_dev), hipMemcpyHostToDevice, st_));
-        RngState rng = {};
-        seed_key(seed, rng.key);
-        FS_HIP(hipMemcpyAsync(d_rng_.p, &rng, sizeof(rng), hipMemcpyHostToDevice, st_));
+        RngState rng;
+        upload_rng(seed, rng, d_rng_.as<RngState>(), st_);
         SeqState ss = {};
         ss.pos = n_cached; ss.prompt_L = L;
         FS_HIP(hipMemcpyAsync(state(0), &ss, sizeof(ss), hipMemcpyHostToDevice, st_));
@@ -601,14 +584,14 @@ class LM final : public LMBase {
         prefill_tokens(0, L - 1, /*use_graph=*/true);
         LmKernels<WT>::embed(d_, tok_emb_, cb_emb_, C, a_.codebook_size, d_cfg_.as<SampleCfg>(), d_prompt_.as<uint32_t>(), state(0),
                              x(0), st_);
-        // frame `it` runs at KV length T = n_cached + L + it: pick the graph captured for that attention chunk bucket
+        GenRun g;
+        g.T0 = n_cached + L; g.n_iter = n_iter; g.cb = cb; g.cb_user = cb_user;
         // FS_GEN_TIME_KERNELS: the frame's two persistent launches one by one, a HIP event in front of / between / behind them
-        const bool time_k = (flags & FS_GEN_TIME_KERNELS) && use_persist_ && use_pslow_ && fold_slow_sampler();
-        bool b1_rows_fast = false;
+        g.time_k = (flags & FS_GEN_TIME_KERNELS) && use_persist_ && use_pslow_ && fold_slow_sampler();
         if constexpr (std::is_same<WT, bf16_t>::value) {
             if (getenv("FISHRT_B1_ROWS_FAST") && use_persist_ && use_pslow_ && fold_slow_sampler() && !legacy_) {
                 ensure_rows(2);
-                b1_rows_fast = true;
+                g.b1_rows_fast = true;
                 const int big = 1 << 30;
                 FS_HIP(hipMemcpyAsync(d_rcfg_.p, &cfg, sizeof(cfg), hipMemcpyHostToDevice, st_));
                 FS_HIP(hipMemcpyAsync(d_rbudget_.p, &big, sizeof(int), hipMemcpyHostToDevice, st_));
@@ -616,108 +599,14 @@ class LM final : public LMBase {
                 launch_reppen_reset(rows_rp(0), C, a_.codebook_size, st_);
             }
         }
-        std::vector<hipEvent_t> kev;
-        const bool multi_ok = use_persist_ && use_pslow_ && fold_slow_sampler() && !time_k && !b1_rows_fast;
-        auto launch_frame = [&](long long it_) {
-            set_bucket(n_cached + L + (int)it_);
-            if (b1_rows_fast) {  // experiment hook (FISHRT_B1_ROWS_FAST): the fast decoder of this batch-1 request on k_fast_rows<1>
-                launch_slow_persist(pslow_args(), st_);
-                RowsFastArgs F = rows_fast_args(0, 1);
-                F.slow_logits = d_logits_slow_.as<float>();
-                F.cap = nullptr;
-                launch_rows_fast(F, 1, persist_sampled_, st_);
-                return;
-            }
-            if (time_k && it_ >= 1) {
-                for (int i = 0; i < 3; ++i) { hipEvent_t e; FS_HIP(hipEventCreate(&e)); kev.push_back(e); }
-                FS_HIP(hipEventRecord(kev[kev.size() - 3], st_));
-                launch_slow_persist(pslow_args(), st_);
-                FS_HIP(hipEventRecord(kev[kev.size() - 2], st_));
-                launch_fast_persist(persist_args(), persist_sampled_, st_);
-                FS_HIP(hipEventRecord(kev[kev.size() - 1], st_));
-                return;
-            }
-            use_graphs_for_bucket();
-            FS_HIP(hipGraphLaunch(g_frame_, st_));
-        };
-        launch_frame(0);
+        g.multi_ok = use_persist_ && use_pslow_ && fold_slow_sampler() && !g.time_k && !g.b1_rows_fast;
+        gen_frame(g, 0);
         FS_HIP(hipEventRecord(ev_[1], st_));
         stats_.graph_launches = (uint64_t)L;
         stats_.kernels_per_frame = (uint64_t)((use_pslow_ ? 1 : a_.n_layer * 5 + 1) + (fold_slow_sampler() ? 0 : 1) +
                                               (use_persist_ ? 1 : a_.num_codebooks * (a_.n_fast_layer * 4 + 2)));
-        // decode: one graph replay per frame, enqueued in batches of CHUNK.  Behind every batch the stream copies the generator state
-        // and the batch's code columns into pinned memory and records an event; the host looks at batch b (done flag, frame callback)
-        // while batch b + 1 is already running, so the GPU never waits for the host between batches
-        const int CHUNK = cb ? 8 : 32;
-        long long it = 1;
-        size_t delivered = 0;
-        bool stop = false, ended = false;
-        SeqState* hs = reinterpret_cast<SeqState*>(h_pin_);  // final state (after the loop)
-        auto slot_state = [&](int sl) { return reinterpret_cast<SeqState*>((char*)h_pin_ + 256 + 256 * sl); };
-        auto slot_codes = [&](int sl) { return reinterpret_cast<uint32_t*>((char*)h_pin_ + 1024 + 1024 * sl); };  // [C][CHUNK]
-        static_assert(sizeof(SeqState) <= 256, "pinned slot size");
-        struct Batch { long long first, end; int slot; };
-        auto enqueue_batch = [&](int sl) {
-            Batch b{it, std::min<long long>(n_iter, it + CHUNK), sl};
-            while (it < b.end) {
-                // several frames per graph launch where the batch has them and they share an attention chunk bucket (multi_frame_graph)
-                const int nf = frames_per_graph();
-                if (multi_ok && nf == 0) {
-                    set_bucket(n_cached + L + (int)it);
-                    launch_slow_persist(pslow_args(), st_);
-                    launch_fast_persist(persist_args(), persist_sampled_, st_);
-                    ++it; stats_.graph_launches += 1;
-                } else if (multi_ok && nf > 1 && b.end - it >= nf && chunk_bucket(n_cached + L + (int)it) == chunk_bucket(n_cached + L + (int)it + nf - 1)) {
-                    set_bucket(n_cached + L + (int)it);
-                    use_graphs_for_bucket();  // (keeps the single-frame graph of the bucket current as well)
-                    FS_HIP(hipGraphLaunch(multi_frame_graph(), st_));
-                    it += nf; stats_.graph_launches += (uint64_t)nf;
-                } else {
-                    launch_frame(it); ++it; stats_.graph_launches += 1;
-                }
-            }
-            FS_HIP(hipMemcpyAsync(slot_state(sl), state(0), sizeof(SeqState), hipMemcpyDeviceToHost, st_));
-            if (cb)  // columns [first, end) of every codebook row (frame index == iteration index until <|im_end|>)
-                FS_HIP(hipMemcpy2DAsync(slot_codes(sl), sizeof(uint32_t) * CHUNK, d_out_.as<uint32_t>() + b.first, sizeof(uint32_t) * out_cap_,
-                                        sizeof(uint32_t) * (size_t)(b.end - b.first), (size_t)C, hipMemcpyDeviceToHost, st_));
-            FS_HIP(hipEventRecord(ev_batch_[sl], st_));
-            return b;
-        };
-        auto retire_batch = [&](const Batch& b) {  // true when the generator has terminated or the callback asked to stop
-            FS_HIP(hipEventSynchronize(ev_batch_[b.slot]));
-            const SeqState* s2 = slot_state(b.slot);
-            if (cb) {
-                const size_t n = std::min<size_t>((size_t)s2->n_out, (size_t)b.end);
-                std::vector<uint32_t> fr(C);
-                for (size_t f = std::max<size_t>(delivered, (size_t)b.first); f < n && !stop; ++f) {
-                    for (int c = 0; c < C; ++c) fr[c] = slot_codes(b.slot)[(size_t)c * CHUNK + (f - (size_t)b.first)];
-                    if (cb(cb_user, f, fr.data())) stop = true;
-                    delivered = f + 1;
-                }
-            }
-            if (s2->done != 0) ended = true;
-            return ended || stop;
-        };
-        if (cb) {  // frame 0 (produced by the prefill iteration) is delivered before the decode batches
-            FS_HIP(hipMemcpyAsync(slot_state(0), state(0), sizeof(SeqState), hipMemcpyDeviceToHost, st_));
-            FS_HIP(hipMemcpy2DAsync(slot_codes(0), sizeof(uint32_t) * CHUNK, d_out_.as<uint32_t>(), sizeof(uint32_t) * out_cap_, sizeof(uint32_t), (size_t)C,
-                                    hipMemcpyDeviceToHost, st_));
-            FS_HIP(hipEventRecord(ev_batch_[0], st_));
-            retire_batch(Batch{0, 1, 0});
-        }
-        {
-            Batch prev{0, 0, 0};
-            bool have_prev = false;
-            int sl = cb ? 1 : 0;
-            while (it < n_iter && !(ended || stop)) {
-                const Batch cur = enqueue_batch(sl);
-                sl ^= 1;
-                if (have_prev) retire_batch(prev);  // batch b is examined while batch b + 1 runs
-                prev = cur;
-                have_prev = true;
-            }
-            if (have_prev && !(stop)) retire_batch(prev);
-        }
+        gen_decode(g);
+        SeqState* hs = reinterpret_cast<SeqState*>(h_pin_);  // final state
         FS_HIP(hipEventRecord(ev_[2], st_));
         FS_HIP(hipMemcpyAsync(hs, state(0), sizeof(SeqState), hipMemcpyDeviceToHost, st_));
         FS_HIP(hipStreamSynchronize(st_));
@@ -727,61 +616,23 @@ class LM final : public LMBase {
         FS_HIP(hipEventElapsedTime(&ms01, ev_[0], ev_[1]));
         FS_HIP(hipEventElapsedTime(&ms12, ev_[1], ev_[2]));
         stats_.prefill_ms = ms01; stats_.decode_ms = ms12; stats_.frames = n; stats_.prompt_tokens = (uint64_t)L;
-        if (!kev.empty()) {
+        if (!g.kev.empty()) {
             double ts = 0, tf = 0;
-            for (size_t i = 0; i < kev.size(); i += 3) {
+            for (size_t i = 0; i < g.kev.size(); i += 3) {
                 float a = 0, b = 0;
-                FS_HIP(hipEventElapsedTime(&a, kev[i], kev[i + 1]));
-                FS_HIP(hipEventElapsedTime(&b, kev[i + 1], kev[i + 2]));
+                FS_HIP(hipEventElapsedTime(&a, g.kev[i], g.kev[i + 1]));
+                FS_HIP(hipEventElapsedTime(&b, g.kev[i + 1], g.kev[i + 2]));
                 ts += a; tf += b;
             }
-            stats_.slow_kernel_us = ts * 1e3 / (double)(kev.size() / 3);
-            stats_.fast_kernel_us = tf * 1e3 / (double)(kev.size() / 3);
-            for (hipEvent_t e : kev) (void)hipEventDestroy(e);
+            stats_.slow_kernel_us = ts * 1e3 / (double)(g.kev.size() / 3);
+            stats_.fast_kernel_us = tf * 1e3 / (double)(g.kev.size() / 3);
+            for (hipEvent_t e : g.kev) (void)hipEventDestroy(e);
         }
-        if (use_persist_ && getenv("FISHRT_PERSIST_PROF")) {
-            unsigned long long pr[24];
-            FS_HIP(hipMemcpy(pr, d_ctl_.as<uint32_t>() + 16, sizeof(pr), hipMemcpyDeviceToHost));
-            FS_HIP(hipMemset(d_ctl_.as<uint32_t>() + 16, 0, sizeof(pr)));
-            const double f = 0.01 / std::max<double>(1.0, (double)stats_.graph_launches - (double)L + 1);  // us per frame
-            fprintf(stderr, "persist prof (us/frame, workgroup 0; wait+work): preload %.1f  S1 %.1f+%.1f  S2 %.1f+%.1f  S3 %.1f+%.1f  S4 %.1f+%.1f  head %.1f+%.1f  decision %.1f+%.1f  tail %.1f | S3 split: gemv+reduce %.1f barrier %.1f epilogue %.1f\n",
-                    pr[0] * f, pr[9] * f, pr[1] * f, pr[10] * f, pr[2] * f, pr[11] * f, pr[3] * f, pr[12] * f, pr[4] * f, pr[13] * f, pr[5] * f, pr[14] * f, pr[6] * f, pr[7] * f, pr[8] * f, pr[15] * f, pr[3] * f);
-            fprintf(stderr, "persist boundaries (us/frame, workgroup 0): slow kernel's finish -> fast kernel's entry %.2f (%llu frames)  entry -> first stage timer (state, slow-token decision) %.2f  last timer -> finish %.2f\n",
-                    pr[20] ? pr[17] * 0.01 / (double)pr[20] : 0.0, pr[20], pr[18] * f, pr[19] * f);
-        }
-        if (use_pslow_) {
-            if (getenv("FISHRT_PERSIST_PROF")) {
-                unsigned long long pr[24];
-                FS_HIP(hipMemcpy(pr, d_sctl_.as<uint32_t>() + 16, sizeof(pr), hipMemcpyDeviceToHost));
-                FS_HIP(hipMemset(d_sctl_.as<uint32_t>() + 16, 0, sizeof(pr)));
-                const double f = 0.01 / std::max<double>(1.0, (double)stats_.graph_launches - (double)L + 1);
-                fprintf(stderr, "slow persist prof (us/frame, workgroup %d; wait+work): S1 %.1f+%.1f  S2 %.1f+%.1f  S3 %.1f+%.1f  S4 %.1f+%.1f  S5 %.1f+%.1f  head %.1f+%.1f\n",
-                        getenv("FISHRT_PERSIST_PROF_WG") ? atoi(getenv("FISHRT_PERSIST_PROF_WG")) : 0, pr[9] * f, pr[1] * f, pr[10] * f, pr[2] * f, pr[11] * f, pr[3] * f,
-                        pr[12] * f, pr[4] * f, pr[13] * f, pr[5] * f, pr[14] * f, pr[6] * f);
-                fprintf(stderr, "slow persist boundaries (us/frame): fast kernel's finish -> slow kernel's entry %.2f (%llu frames)  entry -> first stage timer (state, first loads) %.2f  last timer -> finish %.2f\n",
-                        pr[20] ? pr[17] * 0.01 / (double)pr[20] : 0.0, pr[20], pr[18] * f, pr[19] * f);
-            }
-            uint32_t ctl[4] = {0, 0, 0, 0};
-            FS_HIP(hipMemcpy(ctl, d_sctl_.p, sizeof(ctl), hipMemcpyDeviceToHost));
-            if (ctl[1]) {
-                FS_HIP(hipMemset(d_sctl_.as<uint32_t>() + 1, 0, 4));
-                pslow_ok_ = persist_ok_ = false;  // this handle stays on the per-node graphs from now on: only this request is lost
-                throw Error("persistent slow-transformer kernel: a grid-wide wait timed out (are all 256 CUs available to this process?); "
-                            "the handle falls back to per-node launches for its next calls");
-            }
-        }
-        if (use_persist_) {
-            uint32_t ctl[4] = {0, 0, 0, 0};
-            FS_HIP(hipMemcpy(ctl, d_ctl_.p, sizeof(ctl), hipMemcpyDeviceToHost));
-            if (ctl[1] || ctl[2]) {
-                FS_HIP(hipMemset(d_ctl_.as<uint32_t>() + 1, 0, 8));
-                if (ctl[1]) pslow_ok_ = persist_ok_ = false;  // (see above)
-                throw Error(ctl[1] ? "persistent fast-decoder kernel: a grid-wide wait timed out (are all 256 CUs available to this process?); "
-                                     "the handle falls back to per-node launches for its next calls"
-                                   : "persistent fast-decoder kernel launched with a sampling configuration it was not built for");
-            }
-        }
-        if (clamped && !hs->done && !stop)
+        dump_persist_prof(L);
+        if (use_pslow_) check_ctl({&d_sctl_}, "persistent slow-transformer kernel", nullptr);
+        if (use_persist_)
+            check_ctl({&d_ctl_}, "persistent fast-decoder kernel", "persistent fast-decoder kernel launched with a sampling configuration it was not built for");
+        if (budget.clamped && !hs->done && !g.stop)
             throw Error("generation ran past max_seq_len without <|im_end|> (the reference fails at dual_ar.rs:623-624)");
         FS_REQUIRE(n <= cap, "codes_out capacity too small for the generated frames");
         if (codes_out) {
@@ -796,6 +647,110 @@ class LM final : public LMBase {
             FS_HIP(hipMemcpy(hidden_out, d_hidden_.p, sizeof(float) * rows * a_.dim, hipMemcpyDeviceToHost));
             if (n_hidden) *n_hidden = rows;
         }
+    }
+
+    // one generate() call: what its frame launches and its decode loop share
+    struct GenRun {
+        int T0 = 0;  // KV length of frame 0 (cached + prompt tokens): frame `it` runs at T0 + it
+        long long n_iter = 0;
+        fs_frame_cb cb = nullptr;
+        void* cb_user = nullptr;
+        bool time_k = false, b1_rows_fast = false, multi_ok = false;
+        std::vector<hipEvent_t> kev;       // FS_GEN_TIME_KERNELS: three events per frame
+        long long it = 1;                  // the next generator iteration to enqueue
+        size_t delivered = 0;              // frames handed to the callback
+        bool stop = false, ended = false;  // the callback asked to stop / the generator has terminated
+    };
+    // frame `it_` of a generate() call: pick the graph captured for the attention chunk bucket of its KV length
+    void gen_frame(GenRun& g, long long it_) {
+        set_bucket(g.T0 + (int)it_);
+        if (g.b1_rows_fast) {  // experiment hook (FISHRT_B1_ROWS_FAST): the fast decoder of this batch-1 request on k_fast_rows<1>
+            launch_slow_persist(pslow_args(), st_);
+            RowsFastArgs F = rows_fast_args(0, 1);
+            F.slow_logits = d_logits_slow_.as<float>();
+            F.cap = nullptr;
+            launch_rows_fast(F, 1, persist_sampled_, st_);
+            return;
+        }
+        if (g.time_k && it_ >= 1) {
+            for (int i = 0; i < 3; ++i) { hipEvent_t e; FS_HIP(hipEventCreate(&e)); g.kev.push_back(e); }
+            FS_HIP(hipEventRecord(g.kev[g.kev.size() - 3], st_));
+            launch_slow_persist(pslow_args(), st_);
+            FS_HIP(hipEventRecord(g.kev[g.kev.size() - 2], st_));
+            launch_fast_persist(persist_args(), persist_sampled_, st_);
+            FS_HIP(hipEventRecord(g.kev[g.kev.size() - 1], st_));
+            return;
+        }
+        use_graphs_for_bucket();
+        FS_HIP(hipGraphLaunch(g_frame_, st_));
+    }
+    // decode: one graph replay per frame, enqueued in batches of CHUNK.  Behind every batch the stream copies the generator state
+    // and the batch's code columns into pinned memory and records an event; the host looks at batch b (done flag, frame callback)
+    // while batch b + 1 is already running, so the GPU never waits for the host between batches
+    void gen_decode(GenRun& g) {
+        const int C = a_.num_codebooks, CHUNK = g.cb ? 8 : 32;
+        auto slot_state = [&](int sl) { return reinterpret_cast<SeqState*>((char*)h_pin_ + 256 + 256 * sl); };
+        auto slot_codes = [&](int sl) { return reinterpret_cast<uint32_t*>((char*)h_pin_ + 1024 + 1024 * sl); };  // [C][CHUNK]
+        static_assert(sizeof(SeqState) <= 256, "pinned slot size");
+        struct Batch { long long first, end; int slot; };
+        auto enqueue_batch = [&](int sl) {
+            Batch b{g.it, std::min<long long>(g.n_iter, g.it + CHUNK), sl};
+            while (g.it < b.end) {
+                // several frames per graph launch where the batch has them and they share an attention chunk bucket (multi_frame_graph)
+                const int nf = frames_per_graph();
+                if (g.multi_ok && nf == 0) {
+                    set_bucket(g.T0 + (int)g.it);
+                    launch_slow_persist(pslow_args(), st_);
+                    launch_fast_persist(persist_args(), persist_sampled_, st_);
+                    ++g.it; stats_.graph_launches += 1;
+                } else if (g.multi_ok && nf > 1 && b.end - g.it >= nf && chunk_bucket(g.T0 + (int)g.it) == chunk_bucket(g.T0 + (int)g.it + nf - 1)) {
+                    set_bucket(g.T0 + (int)g.it);
+                    use_graphs_for_bucket();  // (keeps the single-frame graph of the bucket current as well)
+                    FS_HIP(hipGraphLaunch(multi_frame_graph(), st_));
+                    g.it += nf; stats_.graph_launches += (uint64_t)nf;
+                } else {
+                    gen_frame(g, g.it); ++g.it; stats_.graph_launches += 1;
+                }
+            }
+            FS_HIP(hipMemcpyAsync(slot_state(sl), state(0), sizeof(SeqState), hipMemcpyDeviceToHost, st_));
+            if (g.cb)  // columns [first, end) of every codebook row (frame index == iteration index until <|im_end|>)
+                FS_HIP(hipMemcpy2DAsync(slot_codes(sl), sizeof(uint32_t) * CHUNK, d_out_.as<uint32_t>() + b.first, sizeof(uint32_t) * out_cap_,
+                                        sizeof(uint32_t) * (size_t)(b.end - b.first), (size_t)C, hipMemcpyDeviceToHost, st_));
+            FS_HIP(hipEventRecord(ev_batch_[sl], st_));
+            return b;
+        };
+        auto retire_batch = [&](const Batch& b) {  // the generator's state behind the batch; its frames go to the callback
+            FS_HIP(hipEventSynchronize(ev_batch_[b.slot]));
+            const SeqState* s2 = slot_state(b.slot);
+            if (g.cb) {
+                const size_t n = std::min<size_t>((size_t)s2->n_out, (size_t)b.end);
+                std::vector<uint32_t> fr(C);
+                for (size_t f = std::max<size_t>(g.delivered, (size_t)b.first); f < n && !g.stop; ++f) {
+                    for (int c = 0; c < C; ++c) fr[c] = slot_codes(b.slot)[(size_t)c * CHUNK + (f - (size_t)b.first)];
+                    if (g.cb(g.cb_user, f, fr.data())) g.stop = true;
+                    g.delivered = f + 1;
+                }
+            }
+            if (s2->done != 0) g.ended = true;
+        };
+        if (g.cb) {  // frame 0 (produced by the prefill iteration) is delivered before the decode batches
+            FS_HIP(hipMemcpyAsync(slot_state(0), state(0), sizeof(SeqState), hipMemcpyDeviceToHost, st_));
+            FS_HIP(hipMemcpy2DAsync(slot_codes(0), sizeof(uint32_t) * CHUNK, d_out_.as<uint32_t>(), sizeof(uint32_t) * out_cap_, sizeof(uint32_t), (size_t)C,
+                                    hipMemcpyDeviceToHost, st_));
+            FS_HIP(hipEventRecord(ev_batch_[0], st_));
+            retire_batch(Batch{0, 1, 0});
+        }
+        Batch prev{0, 0, 0};
+        bool have_prev = false;
+        int sl = g.cb ? 1 : 0;
+        while (g.it < g.n_iter && !(g.ended || g.stop)) {
+            const Batch cur = enqueue_batch(sl);
+            sl ^= 1;
+            if (have_prev) retire_batch(prev);  // batch b is examined while batch b + 1 runs
+            prev = cur;
+            have_prev = true;
+        }
+        if (have_prev && !g.stop) retire_batch(prev);
     }
 
     // generate_static_batch (static_batch.rs:282-390).  bf16 / fp8 handles with n <= min(max_batch, kRows): the MFMA row path below
@@ -825,39 +780,28 @@ class LM final : public LMBase {
         int Lmax = 0;
         for (int i = 0; i < n; ++i) { FS_REQUIRE(lens[i] >= 1, "empty prompt"); Lmax = std::max(Lmax, lens[i]); }
         if (Lmax > a_.max_seq_len) throw Error("prompt exceeds max_seq_len (dual_ar.rs:623-624)");
-        long long n_iter = 1 + std::max<long long>(0, (long long)max_new_tokens - Lmax + 1);  // static_batch.rs:122,262-267
-        bool clamped = false;
-        const long long room = (long long)a_.max_seq_len - Lmax + 1;
-        if (n_iter > room) { n_iter = room; clamped = true; }
-        FS_REQUIRE(n_iter <= out_cap_, "generation longer than the output staging buffer");
+        const Budget budget = iter_budget(max_new_tokens, Lmax);
+        const long long n_iter = budget.n_iter;
         clear_slow();  // static_batch.rs:118-121
         clear_fast();
         ensure_prefill_buffers();
         ensure_batch_buffers();
         ensure_rows_capture(B);
-        SampleCfg cfg = base_cfg();
-        cfg.temp = (float)s.temp; cfg.top_p = (float)s.top_p; cfg.top_p64 = s.top_p;
-        cfg.top_k = (int)std::min<uint64_t>(s.top_k, 1u << 30);
-        cfg.rep_pen = 1.0f; cfg.ignore_eos = (flags & FS_GEN_IGNORE_EOS) ? 1 : 0;
+        SampleCfg cfg = make_cfg(s, flags);
+        cfg.rep_pen = 1.0f;
         rows_par_ = rows_par_sampler_ok(s.temp, s.top_k, n_audio_, a_.codebook_size) && !getenv("FISHRT_ROWS_SAMPLER_1024");
         FS_HIP(hipMemcpyAsync(d_cfg_.p, &cfg, sizeof(cfg), hipMemcpyHostToDevice, st_));
-        RngState rng = {};
-        seed_key(seed, rng.key);  // BatchedLogitsProcessor::new(seed) (the reference passes 42, static_batch.rs:63)
-        FS_HIP(hipMemcpyAsync(d_rng_.p, &rng, sizeof(rng), hipMemcpyHostToDevice, st_));
+        RngState rng;
+        upload_rng(seed, rng, d_rng_.as<RngState>(), st_);  // BatchedLogitsProcessor::new(seed) (the reference passes 42, static_batch.rs:63)
         stats_ = {};
         FS_HIP(hipEventRecord(ev_[0], st_));
-        // left-pad with <|im_end|>/0 (static_batch.rs:68-111; the pad mask is built but never applied, dual_ar.rs:589-615)
         const size_t pstride = (size_t)C1 * Lmax;
         std::vector<uint32_t> padded(pstride * B);
         size_t off = 0;
         for (int b = 0; b < B; ++b) {
-            const int L = lens[b], pad = Lmax - L;
             uint32_t* pp = padded.data() + pstride * b;
-            for (int r = 0; r < C1; ++r) {
-                for (int j = 0; j < pad; ++j) pp[(size_t)r * Lmax + j] = r == 0 ? t_.im_end_id : 0u;
-                std::memcpy(&pp[(size_t)r * Lmax + pad], prompts + off + (size_t)r * L, sizeof(uint32_t) * L);
-            }
-            off += (size_t)C1 * L;
+            left_pad(prompts + off, lens[b], Lmax, pp);
+            off += (size_t)C1 * lens[b];
             validate_tokens(pp, pstride, 1, Lmax);
             ensure_capacity(b, Lmax + (int)n_iter - 1);
         }
@@ -935,25 +879,15 @@ class LM final : public LMBase {
         FS_HIP(hipEventElapsedTime(&ms01, ev_[0], ev_[1]));
         FS_HIP(hipEventElapsedTime(&ms12, ev_[1], ev_[2]));
         stats_.prefill_ms = ms01; stats_.decode_ms = ms12; stats_.prompt_tokens = (uint64_t)Lmax * B; stats_.graph_launches = (uint64_t)it;
-        if (clamped && !done_all)
+        if (budget.clamped && !done_all)
             throw Error("generation ran past max_seq_len without <|im_end|> on every row (the reference fails at dual_ar.rs:623-624)");
-        std::vector<uint32_t> tmp((size_t)B * C * out_cap_);
-        FS_HIP(hipMemcpy(tmp.data(), d_out_.p, sizeof(uint32_t) * tmp.size(), hipMemcpyDeviceToHost));
-        uint64_t total = 0;
+        stats_.frames = copy_out_rows(hs, B, codes_out, cap, n_frames);
         for (int b = 0; b < B; ++b) {
-            const size_t nb = (size_t)hs[b].n_out;
-            FS_REQUIRE(nb <= cap, "codes_out capacity too small for the generated frames");
-            for (int c = 0; c < C; ++c)
-                std::memcpy(codes_out + ((size_t)b * C + c) * cap, tmp.data() + ((size_t)b * C + c) * out_cap_, sizeof(uint32_t) * nb);
-            n_frames[b] = nb;
-            total += nb;
-            seq_len_[b] = hs[b].pos;
             // BatchPosition::is_audio (static_batch.rs:229): the first position is returned unconditionally and is not audio when its slow token
             // was <|im_end|> (the row samplers mark that in `step`); every later returned position belongs to a live row, i.e. is a semantic token
             if (is_audio)
-                for (size_t f = 0; f < nb; ++f) is_audio[(size_t)b * cap + f] = (f == 0 && hs[b].step == -1) ? 0 : 1;
+                for (size_t f = 0; f < n_frames[b]; ++f) is_audio[(size_t)b * cap + f] = (f == 0 && hs[b].step == -1) ? 0 : 1;
         }
-        stats_.frames = total;
     }
 
     // ---- continuous batching: the rows of the static-batch step as independent request slots.  No reference counterpart (the reference
@@ -1006,10 +940,8 @@ class LM final : public LMBase {
         sess_seed_ = seed;
         sess_adds_ = 0;
         ensure_rows_capture(sess_rows_ ? sess_R_ : B_);
-        SampleCfg cfg = base_cfg();
-        cfg.temp = (float)s.temp; cfg.top_p = (float)s.top_p; cfg.top_p64 = s.top_p;
-        cfg.top_k = (int)std::min<uint64_t>(s.top_k, 1u << 30);
-        cfg.rep_pen = (sess_rows_ || per_slot) ? s.repetition_penalty : 1.0f; cfg.ignore_eos = (flags & FS_GEN_IGNORE_EOS) ? 1 : 0;
+        SampleCfg cfg = make_cfg(s, flags);
+        if (!sess_rows_ && !per_slot) cfg.rep_pen = 1.0f;
         cfg.session = sess_rows_ ? 0 : 1;
         sess_cfg_ = cfg;
         if (per_slot) {
@@ -1040,9 +972,8 @@ class LM final : public LMBase {
         }
         rows_par_ = !per_slot && rows_par_sampler_ok(s.temp, s.top_k, n_audio_, a_.codebook_size) && !getenv("FISHRT_ROWS_SAMPLER_1024");
         FS_HIP(hipMemcpyAsync(d_cfg_.p, &cfg, sizeof(cfg), hipMemcpyHostToDevice, st_));
-        RngState rng = {};
-        seed_key(seed, rng.key);
-        FS_HIP(hipMemcpyAsync(d_rng_.p, &rng, sizeof(rng), hipMemcpyHostToDevice, st_));
+        RngState rng;
+        upload_rng(seed, rng, d_rng_.as<RngState>(), st_);
         // empty slots: dead, frame 1 (so the frame-0 rule never fires), position 0 of a scratch page nobody reads
         FS_REQUIRE(!free_pages_.empty(), "KV page pool exhausted");
         sess_scratch_ = take_page();
@@ -1072,13 +1003,6 @@ class LM final : public LMBase {
         const bool ok = s.temp == 0.0 || (s.temp > 0.0 && s.top_k > 0 && s.top_k <= 256);
         if (!ok) throw Error("FS_SESSION_PER_SLOT: a slot samples greedy (temp == 0) or with temp > 0 and 0 < top_k <= 256 (the in-launch samplers' limit)");
     }
-    SampleCfg slot_cfg(const fs_sampling& s) const {  // the session's SampleCfg with one request's settings
-        SampleCfg c = sess_cfg_;
-        c.temp = (float)s.temp; c.top_p = (float)s.top_p; c.top_p64 = s.top_p;
-        c.top_k = (int)std::min<uint64_t>(s.top_k, 1u << 30);
-        c.rep_pen = s.repetition_penalty;
-        return c;
-    }
     RepPenState slot_rp(int b) {
         const size_t nc = (size_t)b * a_.num_codebooks;
         RepPenState rp;
@@ -1097,16 +1021,19 @@ class LM final : public LMBase {
                 throw Error("per-slot sampling / seed need a session begun with FS_SESSION_PER_SLOT or FS_SESSION_ROWS (the lock-step sampler has one setting and one stream per session)");
             if (sampling && sess_slots_) require_slot_sampling(*sampling);
             if (sampling && sess_rows_) {
-                const int tk = (int)std::min<uint64_t>(sampling->top_k, 1u << 30);
                 if ((sampling->temp != 0.0) != sess_sampled_) throw Error("FS_SESSION_ROWS: every slot greedy or every slot sampled, like the session's own setting");
-                if (sess_sampled_ && !fast_persist_samples((float)sampling->temp, tk, a_.codebook_size))
+                if (sess_sampled_ && !fast_persist_samples((float)sampling->temp, clamp_top_k(sampling->top_k), a_.codebook_size))
                     throw Error("FS_SESSION_ROWS: sampled slots need temp > 0 and 0 < top_k <= 256");
             }
         }
         const int b = prefix_id >= 0 ? session_add_prefixed(prefix_id, prompt, L, max_new_tokens) : session_add(prompt, L, max_new_tokens);
         if (b >= 0) {
             PendingAdd& pa = sess_queue_.back();
-            if (sampling) { pa.has_cfg = true; pa.cfg = slot_cfg(*sampling); }
+            if (sampling) {  // the session's SampleCfg with this request's settings
+                pa.has_cfg = true;
+                pa.cfg = make_cfg(*sampling, sess_cfg_.ignore_eos ? FS_GEN_IGNORE_EOS : 0);
+                pa.cfg.session = sess_cfg_.session;
+            }
             if (seed) { pa.has_seed = true; pa.seed = *seed; }
         }
         return b;
@@ -1119,9 +1046,7 @@ class LM final : public LMBase {
         FS_REQUIRE(sess_active_, "no open session");
         FS_REQUIRE(L >= 1, "empty prompt");
         const long long Lt = (long long)L + (prefix_id >= 0 ? live_prefix(prefix_id).P : 0);
-        long long n_iter = 1 + std::max<long long>(0, (long long)max_new_tokens - Lt + 1);
-        n_iter = std::max<long long>(1, std::min<long long>(n_iter, (long long)a_.max_seq_len - Lt + 1));  // (Lt > max_seq_len: the add below throws)
-        FS_REQUIRE(n_iter <= out_cap_, "generation longer than the output staging buffer");
+        const long long n_iter = std::max<long long>(1, iter_budget(max_new_tokens, Lt).n_iter);  // (Lt > max_seq_len: the add below throws)
         std::pair<float*, int> buf = take_hid_buf((int)n_iter);
         int b = -1;
         try {
@@ -1198,28 +1123,7 @@ class LM final : public LMBase {
         use_device();
         FS_REQUIRE(sess_active_, "no open session");
         FS_REQUIRE(L >= 1, "empty prompt");
-        if (L > a_.max_seq_len) throw Error("prompt exceeds max_seq_len (dual_ar.rs:623-624)");
-        int b = -1;
-        for (int i = 0; i < B_; ++i) if (sess_left_[i] == -1) { b = i; break; }
-        if (b < 0) return -1;
-        const int C1 = a_.num_codebooks + 1;
-        validate_tokens(prompt, 0, 1, L);
-        long long n_iter = 1 + std::max<long long>(0, (long long)max_new_tokens - L + 1);  // static_batch.rs:122,262-267
-        n_iter = std::min<long long>(n_iter, (long long)a_.max_seq_len - L + 1);           // a slot stops at max_seq_len instead of erroring
-        FS_REQUIRE(n_iter <= out_cap_, "generation longer than the output staging buffer");
-        ensure_prefill2_buffers();
-        {   // not enough free KV pages right now: like "all slots busy" (pages come back when slots are released), not an error
-            const int need = (L + (int)n_iter - 1 + KV_PAGE - 1) / KV_PAGE;
-            if ((int)free_pages_.size() < need - (int)seq_pages_[b].size()) return -1;
-        }
-        alloc_pages(b, L + (int)n_iter - 1);
-        PendingAdd pa;
-        pa.slot = b; pa.L = L; pa.n_iter = (int)n_iter; pa.order = sess_adds_++;
-        pa.prompt.assign(prompt, prompt + (size_t)C1 * L);
-        sess_queue_.push_back(std::move(pa));
-        sess_left_[b] = -2;  // reserved: prefilling
-        stats_.prompt_tokens += (uint64_t)L;
-        return b;
+        return admit(nullptr, -1, prompt, L, max_new_tokens);
     }
     // a queued request: plain add (prompt = all L columns, start 0), prefixed add (prompt = the body's L - start columns, start = the
     // prefix's P, tail = the prefix's partly filled last page, held until the copy has run) or a prefix's own pass (create: prompt = its P
@@ -1283,30 +1187,32 @@ class LM final : public LMBase {
         use_device();
         SessPrefix& px = live_prefix(id);
         FS_REQUIRE(L_body >= 1, "empty body (a prefixed add needs its last prompt column)");
-        const int P = px.P, L = P + L_body;
+        return admit(&px, id, body, L_body, max_new_tokens);
+    }
+    // Admission to the lowest free slot (-1: none free, or not enough free KV pages right now -- pages come back when slots are released --
+    // neither is an error).  A plain add is a prefixed add with an empty prefix (px == nullptr: P = 0, no shared pages, no tail); `cols`
+    // are the n_cols columns the slot prefills itself.  The request is only QUEUED here, with its private pages reserved.
+    int admit(const SessPrefix* px, int prefix_id, const uint32_t* cols, int n_cols, int max_new_tokens) {
+        const int P = px ? px->P : 0, L = P + n_cols;
         if (L > a_.max_seq_len) throw Error("prompt exceeds max_seq_len (dual_ar.rs:623-624)");
         int b = -1;
         for (int i = 0; i < B_; ++i) if (sess_left_[i] == -1) { b = i; break; }
         if (b < 0) return -1;
         const int C1 = a_.num_codebooks + 1;
-        validate_tokens(body, 0, 1, L_body);
-        long long n_iter = 1 + std::max<long long>(0, (long long)max_new_tokens - L + 1);  // static_batch.rs:122,262-267
-        n_iter = std::min<long long>(n_iter, (long long)a_.max_seq_len - L + 1);           // a slot stops at max_seq_len instead of erroring
-        FS_REQUIRE(n_iter <= out_cap_, "generation longer than the output staging buffer");
+        validate_tokens(cols, 0, 1, n_cols);
+        const int n_iter = (int)iter_budget(max_new_tokens, L).n_iter;  // (a slot stops at max_seq_len instead of erroring)
         ensure_prefill2_buffers();
         const int nfull = P / KV_PAGE;
         auto& pg = seq_pages_[b];
-        FS_REQUIRE(pg.empty(), "a free slot still holds KV pages");
-        {   // not enough free KV pages for the private ones right now: not an error, like session_add
-            const int need = (L + (int)n_iter - 1 + KV_PAGE - 1) / KV_PAGE;
-            if ((int)free_pages_.size() < need - nfull) return -1;
-        }
-        for (int j = 0; j < nfull; ++j) { pg.push_back(px.pages[j]); ++page_refs_[px.pages[j]]; }
-        alloc_pages(b, L + (int)n_iter - 1);
+        FS_REQUIRE(!px || pg.empty(), "a free slot still holds KV pages");
+        const int need = (L + n_iter - 1 + KV_PAGE - 1) / KV_PAGE;
+        if ((int)free_pages_.size() < need - nfull - (int)pg.size()) return -1;
+        for (int j = 0; j < nfull; ++j) { pg.push_back(px->pages[j]); ++page_refs_[px->pages[j]]; }
+        alloc_pages(b, L + n_iter - 1);
         PendingAdd pa;
-        pa.slot = b; pa.L = L; pa.n_iter = (int)n_iter; pa.order = sess_adds_++; pa.start = P; pa.prefix = id;
-        if (P % KV_PAGE) { pa.tail = px.pages[nfull]; ++page_refs_[pa.tail]; }
-        pa.prompt.assign(body, body + (size_t)C1 * L_body);
+        pa.slot = b; pa.L = L; pa.n_iter = n_iter; pa.order = sess_adds_++; pa.start = P; pa.prefix = prefix_id;
+        if (P % KV_PAGE) { pa.tail = px->pages[nfull]; ++page_refs_[pa.tail]; }
+        pa.prompt.assign(cols, cols + (size_t)C1 * n_cols);
         sess_queue_.push_back(std::move(pa));
         sess_left_[b] = -2;  // reserved: prefilling
         stats_.prompt_tokens += (uint64_t)L;
@@ -1486,10 +1392,9 @@ class LM final : public LMBase {
             sess_timed_ = false;
         }
         const int C1 = a_.num_codebooks + 1;
-        // per-slot sampler state of the joining slots, staged here until the stream has been waited for below
-        std::vector<SampleCfg> up_cfg;
+        // per-slot sampler streams of the joining slots, staged here until the stream has been waited for below
         std::vector<SlotRng> up_rng;
-        up_cfg.reserve(sess_flight_.size()); up_rng.reserve(sess_flight_.size());
+        up_rng.reserve(sess_flight_.size());
         for (const PendingAdd& pa : sess_flight_) {
             if (pa.create) {  // the prefix's K/V are in place: its pad pages go back; a prefix released meanwhile goes now
                 SessPrefix& px = sess_prefixes_[pa.prefix];
@@ -1510,31 +1415,32 @@ class LM final : public LMBase {
             for (int r = 0; r < C1; ++r) ss.cur[r] = pa.prompt[(size_t)r * cols + (cols - 1)];
             sess_hs_[b] = ss;
             FS_HIP(hipMemcpyAsync(state(b), &sess_hs_[b], sizeof(SeqState), hipMemcpyHostToDevice, st_));
+            // the slot's own settings / seed (fs_lm_session_add_ex), or the session's back after an occupant that had its own.  (The copies
+            // read pa / sess_cfg_, which outlive the wait below.)
+            const SampleCfg& cfg = pa.has_cfg ? pa.cfg : sess_cfg_;
+            const uint64_t seed = pa.has_seed ? pa.seed : sess_seed_ + (uint64_t)pa.order;
             if (sess_rows_) {  // the slot becomes a live row: first-frame input, iteration budget, fresh repetition-penalty window and sampler stream
                 LmKernels<WT>::embed(d_, tok_emb_, cb_emb_, a_.num_codebooks, a_.codebook_size, d_cfg_.as<SampleCfg>(), nullptr, state(b), x(b), st_);
                 sess_budget_tmp_ = pa.n_iter;
                 FS_HIP(hipMemcpyAsync(d_rbudget_.as<int>() + b, &sess_budget_tmp_, sizeof(int), hipMemcpyHostToDevice, st_));
-                RngState rng = {};
-                seed_key(pa.has_seed ? pa.seed : sess_seed_ + (uint64_t)pa.order, rng.key);
-                FS_HIP(hipMemcpyAsync(d_rrng_.as<RngState>() + b, &rng, sizeof(rng), hipMemcpyHostToDevice, st_));
-                up_cfg.push_back(pa.has_cfg ? pa.cfg : sess_cfg_);  // (the slot's own settings, or the session's back after an occupant that had its own)
-                FS_HIP(hipMemcpyAsync(d_rcfg_.as<SampleCfg>() + b, &up_cfg.back(), sizeof(SampleCfg), hipMemcpyHostToDevice, st_));
+                RngState rng;
+                upload_rng(seed, rng, d_rrng_.as<RngState>() + b, st_);
+                FS_HIP(hipMemcpyAsync(d_rcfg_.as<SampleCfg>() + b, &cfg, sizeof(SampleCfg), hipMemcpyHostToDevice, st_));
                 launch_reppen_reset(rows_rp(b), a_.num_codebooks, a_.codebook_size, st_);
                 FS_HIP(hipStreamSynchronize(st_));  // (rng / budget are locals)
             } else {
-            if (sess_slots_) {  // the slot's settings, a StdRng stream at word 0 (no look-ahead word yet) and empty repetition-penalty windows
-                up_cfg.push_back(pa.has_cfg ? pa.cfg : sess_cfg_);
-                SlotRng sr;
-                std::memset(&sr, 0xFF, sizeof(sr));
-                sr.rng = RngState{};
-                seed_key(pa.has_seed ? pa.seed : sess_seed_ + (uint64_t)pa.order, sr.rng.key);
-                up_rng.push_back(sr);
-                FS_HIP(hipMemcpyAsync(d_scfg_.as<SampleCfg>() + b, &up_cfg.back(), sizeof(SampleCfg), hipMemcpyHostToDevice, st_));
-                FS_HIP(hipMemcpyAsync(d_srng_.as<SlotRng>() + b, &up_rng.back(), sizeof(SlotRng), hipMemcpyHostToDevice, st_));
-                launch_reppen_reset(slot_rp(b), a_.num_codebooks, a_.codebook_size, st_);
-            }
-            LmKernels<WT>::embed(d_, tok_emb_, cb_emb_, a_.num_codebooks, a_.codebook_size, d_cfg_.as<SampleCfg>(), nullptr, state(b),
-                                 d_pfx_.as<float>() + (size_t)b * a_.dim, st_);
+                if (sess_slots_) {  // the slot's settings, a StdRng stream at word 0 (no look-ahead word yet) and empty repetition-penalty windows
+                    SlotRng sr;
+                    std::memset(&sr, 0xFF, sizeof(sr));
+                    sr.rng = RngState{};
+                    seed_key(seed, sr.rng.key);
+                    up_rng.push_back(sr);
+                    FS_HIP(hipMemcpyAsync(d_scfg_.as<SampleCfg>() + b, &cfg, sizeof(SampleCfg), hipMemcpyHostToDevice, st_));
+                    FS_HIP(hipMemcpyAsync(d_srng_.as<SlotRng>() + b, &up_rng.back(), sizeof(SlotRng), hipMemcpyHostToDevice, st_));
+                    launch_reppen_reset(slot_rp(b), a_.num_codebooks, a_.codebook_size, st_);
+                }
+                LmKernels<WT>::embed(d_, tok_emb_, cb_emb_, a_.num_codebooks, a_.codebook_size, d_cfg_.as<SampleCfg>(), nullptr, state(b),
+                                     d_pfx_.as<float>() + (size_t)b * a_.dim, st_);
             }
             if (pa.hid) {  // the slot collects from its first iteration on (the step that runs its last prompt position): row 0
                 sess_hid_[b].rows = pa.hid; sess_hid_[b].count = 0; sess_hid_[b].cap = pa.hid_cap;
@@ -1603,10 +1509,7 @@ class LM final : public LMBase {
                     launch_rows_slow(rows_slow_args(Rs), Rs, st_);
                     // (x(r) now holds row r's pre-norm hidden state; the fast launches overwrite it with the next input)
                     if (sess_hid_live_ > 0) launch_hidden_rows(d_hid_tab_.as<HidSlot>(), state(0), x(0), a_.dim, top, st_);
-                    for (int r0 = 0; r0 < top; r0 += PR_FAST_ROWS) {
-                        const int left = std::min(PR_FAST_ROWS, top - r0), Rf = left >= 3 ? 4 : left;
-                        launch_rows_fast(rows_fast_args(r0, Rf), Rf, sess_sampled_, st_);
-                    }
+                    launch_rows_fast_groups(top, sess_sampled_);
                 }
             } else
             for (int i = 0; i < chunk; ++i) {
@@ -1700,14 +1603,8 @@ class LM final : public LMBase {
         sess_active_ = false;
         sess_slots_ = false;
         sess_released_frames_ = 0;
-        if (sess_rows_) {
-            uint32_t ctl[4];
-            for (DevBuf* cb : {&d_rctl_s_, &d_rctl_f_}) {
-                FS_HIP(hipMemcpy(ctl, cb->p, sizeof(ctl), hipMemcpyDeviceToHost));
-                if (ctl[1] || ctl[2]) FS_HIP(hipMemset((uint32_t*)cb->p + 1, 0, 8));
-            }
-            sess_rows_ = false;
-        }
+        if (sess_rows_) check_ctl({&d_rctl_s_, &d_rctl_f_}, nullptr, nullptr);  // (a session that ended on an error: reset only)
+        sess_rows_ = false;
         if (sess_plock_.owns_lock()) sess_plock_.unlock();
     }
 
@@ -1722,12 +1619,8 @@ class LM final : public LMBase {
         size_t off = 0;
         std::vector<uint32_t> padded((size_t)C1 * Lmax);
         for (int i = 0; i < n; ++i) {
-            const int L = lens[i], pad = Lmax - L;
-            for (int r = 0; r < C1; ++r) {
-                for (int j = 0; j < pad; ++j) padded[(size_t)r * Lmax + j] = r == 0 ? t_.im_end_id : 0u;
-                std::memcpy(&padded[(size_t)r * Lmax + pad], prompts + off + (size_t)r * L, sizeof(uint32_t) * L);
-            }
-            off += (size_t)C1 * L;
+            left_pad(prompts + off, lens[i], Lmax, padded.data());
+            off += (size_t)C1 * lens[i];
             clear_slow();  // static_batch.rs:118-121
             // BatchedLogitsProcessor semantics on the single-sequence kernels (sampling/mod.rs:77-109): temp <= 1e-7 -> device argmax
             // (FIRST maximal index), else the child StdRng of (sample() call, row i) seeded from the master's u64 number call * n + i --
@@ -1791,9 +1684,7 @@ class LM final : public LMBase {
         for (int i = 0; i < n; ++i) {
             validate_tokens(prompts + poff[i], 0, 1, lens[i]);
             if (lens[i] > a_.max_seq_len) throw Error("prompt exceeds max_seq_len (dual_ar.rs:623-624)");
-            n_iter[i] = 1 + std::max<long long>(0, (long long)max_new_tokens[i] - lens[i] + 1);  // single_batch.rs:61,77,193-197
-            n_iter[i] = std::min<long long>(n_iter[i], (long long)a_.max_seq_len - lens[i] + 1);   // (a row stops at max_seq_len)
-            FS_REQUIRE(n_iter[i] <= out_cap_, "generation longer than the output staging buffer");
+            n_iter[i] = iter_budget(max_new_tokens[i], lens[i]).n_iter;  // (a row stops at max_seq_len)
             max_iter = std::max(max_iter, n_iter[i]);
             ensure_capacity(i, lens[i] + (int)n_iter[i] - 1);
         }
@@ -1801,15 +1692,8 @@ class LM final : public LMBase {
         std::vector<SampleCfg> cfgs(R);
         std::vector<int> budget(R, 0);
         for (int i = 0; i < R; ++i) {
-            SampleCfg cfg = base_cfg();
-            if (i < n) {
-                const fs_sampling& s = samplings[i];
-                cfg.temp = (float)s.temp; cfg.top_p = (float)s.top_p; cfg.top_p64 = s.top_p;
-                cfg.top_k = (int)std::min<uint64_t>(s.top_k, 1u << 30);
-                cfg.rep_pen = s.repetition_penalty; cfg.ignore_eos = (flags & FS_GEN_IGNORE_EOS) ? 1 : 0;
-                budget[i] = (int)n_iter[i];
-            }
-            cfgs[i] = cfg;
+            cfgs[i] = i < n ? make_cfg(samplings[i], flags) : base_cfg();
+            if (i < n) budget[i] = (int)n_iter[i];
         }
         FS_HIP(hipMemcpyAsync(d_rcfg_.p, cfgs.data(), sizeof(SampleCfg) * R, hipMemcpyHostToDevice, st_));
         FS_HIP(hipMemcpyAsync(d_rbudget_.p, budget.data(), sizeof(int) * R, hipMemcpyHostToDevice, st_));
@@ -1827,9 +1711,8 @@ class LM final : public LMBase {
             FS_HIP(hipMemcpyAsync(state(i), &ss, sizeof(ss), hipMemcpyHostToDevice, st_));
             FS_HIP(hipMemcpyAsync(d_prompt_.p, prompts + poff[i], sizeof(uint32_t) * C1 * L, hipMemcpyHostToDevice, st_));
             FS_HIP(hipMemcpyAsync(d_cfg_.p, &cfgs[i], sizeof(SampleCfg), hipMemcpyHostToDevice, st_));  // (embed reads the semantic range from d_cfg_)
-            RngState rng = {};
-            seed_key(seeds[i], rng.key);
-            FS_HIP(hipMemcpyAsync(d_rrng_.as<RngState>() + i, &rng, sizeof(rng), hipMemcpyHostToDevice, st_));
+            RngState rng;
+            upload_rng(seeds[i], rng, d_rrng_.as<RngState>() + i, st_);
             launch_reppen_reset(rows_rp(i), C, a_.codebook_size, st_);
             prefill_tokens(i, L - 1, /*use_graph=*/false);
             LmKernels<WT>::embed(d_, tok_emb_, cb_emb_, C, a_.codebook_size, d_cfg_.as<SampleCfg>(), d_prompt_.as<uint32_t>(), state(i), x(i), st_);
@@ -1852,13 +1735,8 @@ class LM final : public LMBase {
             set_bucket(maxL + (int)it_);
             RowsSlowArgs S = rows_slow_args(R);
             launch_rows_slow(S, R, st_);
-            if (rows_fast) {
-                for (int r0 = 0; r0 < n; r0 += PR_FAST_ROWS) {
-                    // the last group takes the smallest instantiation that holds its requests (n = 5: 4 + 1 rows, n = 6: 4 + 2)
-                    const int left = std::min(PR_FAST_ROWS, n - r0), Rf = left >= 3 ? 4 : left;
-                    launch_rows_fast(rows_fast_args(r0, Rf), Rf, rows_sampled, st_);
-                }
-            } else {
+            if (rows_fast) launch_rows_fast_groups(n, rows_sampled);
+            else {
                 static const int two = 2;
                 for (int i = 0; i < n; ++i) {
                     if (it_ >= n_iter[i]) { if (it_ == n_iter[i]) FS_HIP(hipMemcpyAsync(&state(i)->done, &two, sizeof(int), hipMemcpyHostToDevice, st_)); continue; }
@@ -1889,32 +1767,9 @@ class LM final : public LMBase {
         FS_HIP(hipEventElapsedTime(&ms12, ev_[1], ev_[2]));
         stats_.prefill_ms = ms01; stats_.decode_ms = ms12; stats_.graph_launches = (uint64_t)it;
         stats_.kernels_per_frame = (uint64_t)(1 + (rows_fast ? (n + PR_FAST_ROWS - 1) / PR_FAST_ROWS : n));
-        if (getenv("FISHRT_PERSIST_PROF")) {
-            unsigned long long pr[16];
-            const double f = 0.01 / std::max<double>(1.0, (double)it);  // us per frame (wall_clock64 ticks are 10 ns)
-            FS_HIP(hipMemcpy(pr, d_rctl_s_.as<uint32_t>() + 16, sizeof(pr), hipMemcpyDeviceToHost));
-            FS_HIP(hipMemset(d_rctl_s_.as<uint32_t>() + 16, 0, sizeof(pr)));
-            fprintf(stderr, "rows slow prof R=%d (us/frame, workgroup 0): S1 %.1f  S2 %.1f  S3 sweep %.1f + %.1f  S4 sweep %.1f gemm %.1f barrier %.1f publish %.1f  S5 sweep+gemm %.1f barrier %.1f publish %.1f  head %.1f\n",
-                    R, pr[1] * f, pr[2] * f, pr[8] * f, pr[3] * f, pr[9] * f, pr[10] * f, pr[11] * f, pr[4] * f, pr[12] * f, pr[13] * f, pr[5] * f, pr[6] * f);
-            FS_HIP(hipMemcpy(pr, d_rctl_f_.as<uint32_t>() + 16, sizeof(pr), hipMemcpyDeviceToHost));
-            FS_HIP(hipMemset(d_rctl_f_.as<uint32_t>() + 16, 0, sizeof(pr)));
-            fprintf(stderr, "rows fast prof (us/frame summed over the fast launches, workgroup 0; wait+work): preload %.1f  S1 %.1f+%.1f  S2 %.1f+%.1f  S3 %.1f+%.1f  S4 %.1f+%.1f  head %.1f+%.1f  decision %.1f+%.1f (rows' logits -> argmax / draw %.1f, pick -> next input %.1f)  tail %.1f\n",
-                    pr[0] * f, pr[9] * f, pr[1] * f, pr[10] * f, pr[2] * f, pr[11] * f, (pr[3] + pr[8]) * f, pr[12] * f, pr[4] * f, pr[13] * f, pr[5] * f, pr[14] * f, (pr[6] + pr[15]) * f, pr[15] * f, pr[6] * f, pr[7] * f);
-        }
+        dump_rows_prof(R, it);
         rows_check_ctl(/*include_b1_fast=*/!rows_fast);
-        std::vector<uint32_t> tmp((size_t)n * C * out_cap_);
-        FS_HIP(hipMemcpy(tmp.data(), d_out_.p, sizeof(uint32_t) * tmp.size(), hipMemcpyDeviceToHost));
-        uint64_t total = 0;
-        for (int i = 0; i < n; ++i) {
-            const size_t nb = (size_t)hs[i].n_out;
-            FS_REQUIRE(nb <= cap, "codes_out capacity too small for the generated frames");
-            for (int c = 0; c < C; ++c)
-                std::memcpy(codes_out + ((size_t)i * C + c) * cap, tmp.data() + ((size_t)i * C + c) * out_cap_, sizeof(uint32_t) * nb);
-            n_frames[i] = nb;
-            total += nb;
-            seq_len_[i] = hs[i].pos;
-        }
-        stats_.frames = total;
+        stats_.frames = copy_out_rows(hs, n, codes_out, cap, n_frames);
     }
 
     // fs_lm_rows_supported: would fs_lm_generate_multi serve these n requests on the request-row kernels (one persistent launch group per
@@ -1935,9 +1790,8 @@ class LM final : public LMBase {
             // one instantiation per launch: every request greedy, or every request within the in-launch sampler (temp > 0, 0 < top_k <= 256)
             const bool sampled = ss[0].temp != 0.0;
             for (int i = 0; i < ns && !w; ++i) {
-                const int tk = (int)std::min<uint64_t>(ss[i].top_k, 1u << 30);
                 if ((ss[i].temp != 0.0) != sampled) w = "every request greedy or every request sampled";
-                else if (sampled && !fast_persist_samples((float)ss[i].temp, tk, a_.codebook_size)) w = "sampled requests with 0 < top_k <= 256";
+                else if (sampled && !fast_persist_samples((float)ss[i].temp, clamp_top_k(ss[i].top_k), a_.codebook_size)) w = "sampled requests with 0 < top_k <= 256";
             }
         }
         if (why) *why = w;
@@ -1954,24 +1808,108 @@ class LM final : public LMBase {
         const int nslm = std::max(1, 16 / std::max(1, R));
         return ((a_.max_seq_len + nslm - 1) / nslm) / KV_PAGE + 2 <= 160;
     }
-    // the request-row kernels' control words: [1] = a grid-wide wait hit its spin bound, [2] = launched with a sampler configuration the
-    // instantiation was not built for.  Either way the codes of this call are garbage: reset the words, take the handle off the
-    // persistent kernels for its next calls (like generate() does) and raise.
-    void rows_check_ctl(bool include_b1_fast) {
+    // The persistent kernels' control words: [1] = a grid-wide wait hit its spin bound, [2] = launched with a sampler configuration the
+    // instantiation was not built for (the fast decoders only).  Either way the codes of this call are garbage: read the words of every
+    // buffer given and reset the ones that are set; then, unless `who` is null (session_end: reset only), raise -- after a timeout the
+    // handle stays on the per-node graphs from now on, so only this request is lost.
+    void check_ctl(std::initializer_list<DevBuf*> bufs, const char* who, const char* bad_cfg_msg) {
         bool timeout = false, bad_cfg = false;
-        for (DevBuf* cb : {&d_rctl_s_, &d_rctl_f_, include_b1_fast ? &d_ctl_ : (DevBuf*)nullptr}) {
+        for (DevBuf* cb : bufs) {
             if (!cb || !cb->p) continue;
             uint32_t ctl[4] = {0, 0, 0, 0};
             FS_HIP(hipMemcpy(ctl, cb->p, sizeof(ctl), hipMemcpyDeviceToHost));
             if (ctl[1] || ctl[2]) FS_HIP(hipMemset((uint32_t*)cb->p + 1, 0, 8));
             timeout |= ctl[1] != 0; bad_cfg |= ctl[2] != 0;
         }
+        if (!who) return;
         if (timeout) {
             pslow_ok_ = persist_ok_ = false;
-            throw Error("request-row persistent kernels: a grid-wide wait timed out (are all 256 CUs available to this process?); "
-                        "the handle falls back to per-node launches for its next calls");
+            throw Error(std::string(who) + ": a grid-wide wait timed out (are all 256 CUs available to this process?); "
+                                           "the handle falls back to per-node launches for its next calls");
         }
-        if (bad_cfg) throw Error("request-row persistent kernels launched with a sampling configuration they were not built for");
+        if (bad_cfg) throw Error(bad_cfg_msg);
+    }
+    void rows_check_ctl(bool include_b1_fast) {
+        check_ctl({&d_rctl_s_, &d_rctl_f_, include_b1_fast ? &d_ctl_ : (DevBuf*)nullptr}, "request-row persistent kernels",
+                  "request-row persistent kernels launched with a sampling configuration they were not built for");
+    }
+    // FISHRT_PERSIST_PROF: the stage timers workgroup 0 (FISHRT_PERSIST_PROF_WG for the slow kernel) of the batch-1 persistent kernels
+    // accumulated over this call, read and reset
+    void dump_persist_prof(int L) {
+        if (!getenv("FISHRT_PERSIST_PROF")) return;
+        unsigned long long pr[24];
+        const double f = 0.01 / std::max<double>(1.0, (double)stats_.graph_launches - (double)L + 1);  // us per frame
+        if (use_persist_) {
+            FS_HIP(hipMemcpy(pr, d_ctl_.as<uint32_t>() + 16, sizeof(pr), hipMemcpyDeviceToHost));
+            FS_HIP(hipMemset(d_ctl_.as<uint32_t>() + 16, 0, sizeof(pr)));
+            fprintf(stderr, "persist prof (us/frame, workgroup 0; wait+work): preload %.1f  S1 %.1f+%.1f  S2 %.1f+%.1f  S3 %.1f+%.1f  S4 %.1f+%.1f  head %.1f+%.1f  decision %.1f+%.1f  tail %.1f | S3 split: gemv+reduce %.1f barrier %.1f epilogue %.1f\n",
+                    pr[0] * f, pr[9] * f, pr[1] * f, pr[10] * f, pr[2] * f, pr[11] * f, pr[3] * f, pr[12] * f, pr[4] * f, pr[13] * f, pr[5] * f, pr[14] * f, pr[6] * f, pr[7] * f, pr[8] * f, pr[15] * f, pr[3] * f);
+            fprintf(stderr, "persist boundaries (us/frame, workgroup 0): slow kernel's finish -> fast kernel's entry %.2f (%llu frames)  entry -> first stage timer (state, slow-token decision) %.2f  last timer -> finish %.2f\n",
+                    pr[20] ? pr[17] * 0.01 / (double)pr[20] : 0.0, pr[20], pr[18] * f, pr[19] * f);
+        }
+        if (use_pslow_) {
+            FS_HIP(hipMemcpy(pr, d_sctl_.as<uint32_t>() + 16, sizeof(pr), hipMemcpyDeviceToHost));
+            FS_HIP(hipMemset(d_sctl_.as<uint32_t>() + 16, 0, sizeof(pr)));
+            fprintf(stderr, "slow persist prof (us/frame, workgroup %d; wait+work): S1 %.1f+%.1f  S2 %.1f+%.1f  S3 %.1f+%.1f  S4 %.1f+%.1f  S5 %.1f+%.1f  head %.1f+%.1f\n",
+                    getenv("FISHRT_PERSIST_PROF_WG") ? atoi(getenv("FISHRT_PERSIST_PROF_WG")) : 0, pr[9] * f, pr[1] * f, pr[10] * f, pr[2] * f, pr[11] * f, pr[3] * f,
+                    pr[12] * f, pr[4] * f, pr[13] * f, pr[5] * f, pr[14] * f, pr[6] * f);
+            fprintf(stderr, "slow persist boundaries (us/frame): fast kernel's finish -> slow kernel's entry %.2f (%llu frames)  entry -> first stage timer (state, first loads) %.2f  last timer -> finish %.2f\n",
+                    pr[20] ? pr[17] * 0.01 / (double)pr[20] : 0.0, pr[20], pr[18] * f, pr[19] * f);
+        }
+    }
+    void dump_rows_prof(int R, long long frames) {  // the same for the request-row kernels
+        if (!getenv("FISHRT_PERSIST_PROF")) return;
+        unsigned long long pr[16];
+        const double f = 0.01 / std::max<double>(1.0, (double)frames);  // us per frame (wall_clock64 ticks are 10 ns)
+        FS_HIP(hipMemcpy(pr, d_rctl_s_.as<uint32_t>() + 16, sizeof(pr), hipMemcpyDeviceToHost));
+        FS_HIP(hipMemset(d_rctl_s_.as<uint32_t>() + 16, 0, sizeof(pr)));
+        fprintf(stderr, "rows slow prof R=%d (us/frame, workgroup 0): S1 %.1f  S2 %.1f  S3 sweep %.1f + %.1f  S4 sweep %.1f gemm %.1f barrier %.1f publish %.1f  S5 sweep+gemm %.1f barrier %.1f publish %.1f  head %.1f\n",
+                R, pr[1] * f, pr[2] * f, pr[8] * f, pr[3] * f, pr[9] * f, pr[10] * f, pr[11] * f, pr[4] * f, pr[12] * f, pr[13] * f, pr[5] * f, pr[6] * f);
+        FS_HIP(hipMemcpy(pr, d_rctl_f_.as<uint32_t>() + 16, sizeof(pr), hipMemcpyDeviceToHost));
+        FS_HIP(hipMemset(d_rctl_f_.as<uint32_t>() + 16, 0, sizeof(pr)));
+        fprintf(stderr, "rows fast prof (us/frame summed over the fast launches, workgroup 0; wait+work): preload %.1f  S1 %.1f+%.1f  S2 %.1f+%.1f  S3 %.1f+%.1f  S4 %.1f+%.1f  head %.1f+%.1f  decision %.1f+%.1f (rows' logits -> argmax / draw %.1f, pick -> next input %.1f)  tail %.1f\n",
+                pr[0] * f, pr[9] * f, pr[1] * f, pr[10] * f, pr[2] * f, pr[11] * f, (pr[3] + pr[8]) * f, pr[12] * f, pr[4] * f, pr[13] * f, pr[5] * f, pr[14] * f, (pr[6] + pr[15]) * f, pr[15] * f, pr[6] * f, pr[7] * f);
+    }
+    // seed -> ChaCha key -> a device RngState.  The copy is asynchronous and reads `host`: the caller's, alive until the stream has been waited for
+    void upload_rng(uint64_t seed, RngState& host, RngState* dst, hipStream_t st) {
+        host = RngState{};
+        seed_key(seed, host.key);
+        FS_HIP(hipMemcpyAsync(dst, &host, sizeof(host), hipMemcpyHostToDevice, st));
+    }
+    // one prompt [C + 1][L] left-padded with <|im_end|>/0 to Lmax columns (static_batch.rs:68-111; the pad mask is built but never applied,
+    // dual_ar.rs:589-615)
+    void left_pad(const uint32_t* prompt, int L, int Lmax, uint32_t* out) const {
+        const int C1 = a_.num_codebooks + 1, pad = Lmax - L;
+        for (int r = 0; r < C1; ++r) {
+            for (int j = 0; j < pad; ++j) out[(size_t)r * Lmax + j] = r == 0 ? t_.im_end_id : 0u;
+            std::memcpy(&out[(size_t)r * Lmax + pad], prompt + (size_t)r * L, sizeof(uint32_t) * L);
+        }
+    }
+    // the results of rows [0, n) of a row-path call (hs: their final states): codes [n][C][cap] out of the staging buffer, frame counts,
+    // KV lengths -> frames of all rows
+    uint64_t copy_out_rows(const std::vector<SeqState>& hs, int n, uint32_t* codes_out, size_t cap, size_t* n_frames) {
+        const int C = a_.num_codebooks;
+        std::vector<uint32_t> tmp((size_t)n * C * out_cap_);
+        FS_HIP(hipMemcpy(tmp.data(), d_out_.p, sizeof(uint32_t) * tmp.size(), hipMemcpyDeviceToHost));
+        uint64_t total = 0;
+        for (int i = 0; i < n; ++i) {
+            const size_t nb = (size_t)hs[i].n_out;
+            FS_REQUIRE(nb <= cap, "codes_out capacity too small for the generated frames");
+            for (int c = 0; c < C; ++c)
+                std::memcpy(codes_out + ((size_t)i * C + c) * cap, tmp.data() + ((size_t)i * C + c) * out_cap_, sizeof(uint32_t) * nb);
+            n_frames[i] = nb;
+            total += nb;
+            seq_len_[i] = hs[i].pos;
+        }
+        return total;
+    }
+    // the fast decoder of request rows [0, top): one launch per group of <= PR_FAST_ROWS rows, the last group on the smallest instantiation
+    // that holds its rows (top = 5: 4 + 1 rows, top = 6: 4 + 2)
+    void launch_rows_fast_groups(int top, bool sampled) {
+        for (int r0 = 0; r0 < top; r0 += PR_FAST_ROWS) {
+            const int left = std::min(PR_FAST_ROWS, top - r0), Rf = left >= 3 ? 4 : left;
+            launch_rows_fast(rows_fast_args(r0, Rf), Rf, sampled, st_);
+        }
     }
     // use_persist_ / use_pslow_ / persist_sampled_ select graphs and sampler folding for generate(); a row-path call sets them for its own
     // launches and must leave them cleared however it ends
@@ -1981,6 +1919,27 @@ class LM final : public LMBase {
     };
     void require_loaded() { FS_REQUIRE(loaded_, "weights not loaded: call fs_lm_load_safetensors or fs_lm_load_synthetic first"); }
 
+    static int clamp_top_k(uint64_t top_k) { return (int)std::min<uint64_t>(top_k, 1u << 30); }
+    // base_cfg() + one request's sampler settings; the callers set what differs (rep_pen = 1 in the batch paths, session, batch_*)
+    SampleCfg make_cfg(const fs_sampling& s, uint32_t flags) const {
+        SampleCfg c = base_cfg();
+        c.temp = (float)s.temp; c.top_p = (float)s.top_p; c.top_p64 = s.top_p;
+        c.top_k = clamp_top_k(s.top_k);
+        c.rep_pen = s.repetition_penalty; c.ignore_eos = (flags & FS_GEN_IGNORE_EOS) ? 1 : 0;
+        return c;
+    }
+    // Iteration budget of a request of L_total prompt positions behind n_cached cached ones: the prefill iteration + one per k with
+    // L_total + k - 1 <= max_new (single_batch.rs:61,77,193-197; static_batch.rs:122,262-267), clamped to the iterations that fit the RoPE
+    // table / KV.  generate and the static batch fail on a clamped budget unless the generator ended by itself (the reference fails at
+    // dual_ar.rs:623-624); session slots and request rows stop there.
+    struct Budget { long long n_iter; bool clamped; };
+    Budget iter_budget(long long max_new, long long L_total, long long n_cached = 0) const {
+        Budget b{1 + std::max<long long>(0, max_new - L_total + 1), false};
+        const long long room = (long long)a_.max_seq_len - (n_cached + L_total) + 1;
+        if (b.n_iter > room) { b.n_iter = room; b.clamped = true; }
+        FS_REQUIRE(b.n_iter <= out_cap_, "generation longer than the output staging buffer");
+        return b;
+    }
     SampleCfg base_cfg() const {
         SampleCfg c = {};
         c.temp = 0.f; c.top_p = 1.f; c.top_k = 0; c.rep_pen = 1.f; c.ignore_eos = 0;
@@ -2414,6 +2373,15 @@ class LM final : public LMBase {
     void drop_batch_graphs() {
         for (auto& kv : batch_graphs_) if (kv.second) (void)hipGraphExecDestroy(kv.second);
         batch_graphs_.clear();
+    }
+    void destroy_graphs() {  // every captured graph of the handle
+        for (auto& kv : graphs_)
+            for (hipGraphExec_t g : {kv.second.first, kv.second.second}) if (g) (void)hipGraphExecDestroy(g);
+        graphs_.clear();
+        for (auto& kv : multi_graphs_) if (kv.second) (void)hipGraphExecDestroy(kv.second);
+        multi_graphs_.clear();
+        g_frame_ = g_step_ = nullptr;
+        drop_batch_graphs();
     }
     hipGraphExec_t batch_graph(int B) {
         const int key = (sess_active_ ? 1 << 24 : 0) + (rows_par_ ? 1 << 25 : 0) + (sess_active_ && sess_slots_ ? 1 << 26 : 0) + B * 1024 + nc_launch_;
