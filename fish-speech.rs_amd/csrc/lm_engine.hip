@@ -899,9 +899,13 @@ class LM final : public LMBase {
         use_device();
         require_loaded();
         FS_REQUIRE(!sess_active_, "a session is already open on this handle");
-        FS_REQUIRE(LmKernels<WT>::has_mfma_prefill() && B_ <= kRows && a_.dim % 128 == 0 && a_.intermediate_size % 128 == 0 &&
-                       a_.num_codebooks <= 8 && !legacy_ && t_.has_semantic_end,
-                   "sessions need the MFMA row path (bf16 / fp8 handle, Fish 1.5 token layout)");
+        FS_REQUIRE(LmKernels<WT>::has_mfma_prefill() && B_ <= kRows && a_.dim % 128 == 0 && a_.intermediate_size % 128 == 0 && a_.num_codebooks <= 8,
+                   "sessions need the MFMA row path (bf16 / fp8 handle)");
+        // Fish <= 1.4 handles (no semantic range: the slow token is the 2-way {pad, im_end} draw): only the per-slot samplers define that
+        // decision for a slot (k_sample_slow_slots, as the slot's own fs_lm_generate call); the lock-step sampler and the request-row
+        // kernels do not
+        FS_REQUIRE((!legacy_ && t_.has_semantic_end) || ((flags & FS_SESSION_PER_SLOT) && !(flags & FS_SESSION_ROWS)),
+                   "plain and FS_SESSION_ROWS sessions need the Fish 1.5 token layout; Fish <= 1.4 handles take FS_SESSION_PER_SLOT");
         clear_slow();
         clear_fast();
         ensure_prefill_buffers();
@@ -2320,7 +2324,8 @@ class LM final : public LMBase {
         const float* prep_g = fold && a_.dim <= 1024 ? fast_[0].attn_norm : nullptr;
         if (slots)
             SampleKernels<WT>::sample_slow_slots(d_, d_lrows_.as<float>(), ld_slow_, n_audio_, d_scfg_.as<SampleCfg>(), d_srng_.as<SlotRng>(), B, state(0),
-                                                 cs.X, d_xfrows_.as<float>(), st_, prep_g, cs.A, fold ? d_epoch_.as<uint32_t>() : nullptr);
+                                                 cs.X, d_xfrows_.as<float>(), st_, prep_g, cs.A, fold ? d_epoch_.as<uint32_t>() : nullptr,
+                                                 capt ? d_rcap_.as<float>() : nullptr, cap_frames_);
         else
         SampleKernels<WT>::sample_slow_rows(d_, d_lrows_.as<float>(), ld_slow_, n_audio_, d_cfg_.as<SampleCfg>(), d_rng_.as<RngState>(), B,
                                             C + 1, state(0), cs.X, d_xfrows_.as<float>(), st_, words, prep_g, cs.A, fold ? d_epoch_.as<uint32_t>() : nullptr);

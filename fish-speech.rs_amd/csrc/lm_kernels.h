@@ -235,9 +235,11 @@ struct SampleKernels {
     // per-slot samplers of a FS_SESSION_PER_SLOT session: one block per slot, every decision that of the slot's own generate_blocking --
     // cfgs[B], rngs[B] and the repetition-penalty state (rp: mask / seen [B][n_cb][cb_size], ring [B][n_cb][17], ring_meta [B][n_cb][2])
     // are per slot.  Settings per slot: temp == 0, or temp > 0 with 0 < top_k <= 256; n <= 2048, cb_size <= 1024.
+    // cfgs[b].legacy (Fish <= 1.4): logits row b = [pad, im_end], the slow token is the 2-way draw of k_sample_slow (one stream word per
+    // live frame, greedy included); cap != null: its record [B][cap_frames][9][2048] gets {pad, im_end, u, .., pick at 2047} of decision 0
     static void sample_slow_slots(const ModelDims& d, const float* logits, int ld, int n, const SampleCfg* cfgs, SlotRng* rngs, int B,
                                   SeqState* states, const float* X, float* XF, hipStream_t st, const float* prep_g = nullptr,
-                                  uint16_t* prep_A = nullptr, uint32_t* epoch = nullptr);
+                                  uint16_t* prep_A = nullptr, uint32_t* epoch = nullptr, float* cap = nullptr, int cap_frames = 0);
     static void sample_fast_slots(const ModelDims& d, const float* logits, int cb, int n_cb, int cb_size, const SampleCfg* cfgs, SlotRng* rngs,
                                   RepPenState rp, int B, SeqState* states, const void* fast_emb, float* XF, const void* tok_emb,
                                   const void* cb_emb, float* X, uint32_t* out_codes, int out_cap, hipStream_t st,

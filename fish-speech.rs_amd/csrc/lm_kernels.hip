@@ -3000,8 +3000,8 @@ __global__ __launch_bounds__(PAR_THREADS) void k_sample_fast_rows_par(const floa
 // the cell when its tag equals the stream position and derives the word itself otherwise (first decision after activation, a draw that
 // consumed nothing) -- the tag makes the look-ahead a pure latency matter, never one of correctness.
 constexpr int SLOT_THREADS = PAR_THREADS + 64;
-__device__ __forceinline__ void slot_word_ahead(SlotRng* rg, int next_decision) {
-    const unsigned long long at = rg->rng.consumed + 1ull;
+__device__ __forceinline__ void slot_word_ahead(SlotRng* rg, int next_decision, unsigned long long used = 1ull) {
+    const unsigned long long at = rg->rng.consumed + used;
     rg->ahead_word[next_decision] = chacha12_word(rg->rng.key, at);
     rg->ahead_at[next_decision] = at;
 }
@@ -3034,7 +3034,8 @@ __device__ __forceinline__ int slot_greedy_pick(const float (&lv)[EPT], int n, u
 template <typename WT>
 __global__ __launch_bounds__(SLOT_THREADS) void k_sample_slow_slots(const float* __restrict__ logits, int ld, int n, const SampleCfg* __restrict__ cfgs,
                                                                      SlotRng* __restrict__ rngs, SeqState* __restrict__ states,
-                                                                     const float* __restrict__ X, float* __restrict__ XF, int dim, PrepOut po) {
+                                                                     const float* __restrict__ X, float* __restrict__ XF, int dim, PrepOut po,
+                                                                     float* __restrict__ cap, int cap_frames) {
     __shared__ float red4[4];
     __shared__ BSampLds S;
     __shared__ unsigned long long s_key;
@@ -3043,14 +3044,35 @@ __global__ __launch_bounds__(SLOT_THREADS) void k_sample_slow_slots(const float*
     SlotRng* rg = rngs + b;
     const bool live = st->done == 0;
     const float temp = cfgs[b].temp;
-    if (tid >= PAR_THREADS) {  // the look-ahead wave (see above)
+    if (tid >= PAR_THREADS) {  // the look-ahead wave (see above); a legacy slow draw takes exactly one word, like a sampled one
         if (tid == PAR_THREADS && live && temp != 0.f) slot_word_ahead(rg, 1);
         return;
     }
     const SampleCfg c = cfgs[b];
     if (tid == 0) s_key = 0ull;
     for (int i = tid; i < dim; i += PAR_THREADS) XF[(size_t)b * dim + i] = X[(size_t)b * dim + i];  // hidden_states -> fast decoder input
-    if (live) {
+    if (live && c.legacy) {
+        // Fish <= 1.4 (k_sample_slow's legacy branch; sampling/mod.rs:8-26, single_batch.rs:104-124): the head rows are [pad, im_end];
+        // P(pad) = softmax([pad, eos])[0] in f32, u = (word >> 8) * 2^-24 from the slot's stream -- ONE word per live frame at every
+        // temperature, greedy included.  Block-uniform branch (every slot of a handle shares the token layout).
+        if (tid == 0) {
+            const float pad = logits[(size_t)b * ld], eos = logits[(size_t)b * ld + 1], m = fmaxf(pad, eos);
+            const float e_pad = expf(pad - m), e_eos = expf(eos - m);
+            const float p_pad = e_pad / (e_pad + e_eos);
+            const unsigned long long at = rg->rng.consumed;
+            const uint32_t w = slot_word(rg, 0, at);
+            rg->rng.consumed = at + 1ull;
+            const float u = (float)(w >> 8) * (1.0f / 16777216.0f);
+            const bool is_pad = u < p_pad || c.ignore_eos;
+            const uint32_t tok = is_pad ? c.pad_id : c.im_end_id;
+            st->cur[0] = tok;
+            if (tok == c.im_end_id) st->done = 1;  // the frame's codebook decisions are skipped; the slot freezes at the end of the frame
+            if (cap && st->frame < cap_frames) {  // (fs_lm_debug_capture: the two logits, the uniform draw, the pick -- k_fast_persist's record)
+                float* rec = cap + ((size_t)b * cap_frames + st->frame) * 9 * 2048;
+                rec[0] = pad; rec[1] = eos; rec[2] = u; rec[2047] = is_pad ? 0.f : 1.f;
+            }
+        }
+    } else if (live) {
         float lv[4];
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
@@ -3095,6 +3117,8 @@ __global__ __launch_bounds__(SLOT_THREADS) void k_sample_fast_slots(const float*
     const float temp = cfgs[b].temp;
     if (tid >= PAR_THREADS) {  // the look-ahead wave: the next decision is codebook cb + 1, or the next frame's slow token
         if (tid == PAR_THREADS && live && temp != 0.f) slot_word_ahead(rg, cb == n_cb - 1 ? 0 : cb + 2);
+        // (a greedy Fish <= 1.4 slot still draws its slow word: this greedy decision consumes none, so the word sits at `consumed` itself)
+        else if (tid == PAR_THREADS && live && cb == n_cb - 1 && cfgs[b].legacy) slot_word_ahead(rg, 0, 0ull);
         return;
     }
     const SampleCfg c = cfgs[b];
@@ -3506,11 +3530,12 @@ void SampleKernels<WT>::sample_fast_rows(const ModelDims& d, const float* logits
 template <typename WT>
 void SampleKernels<WT>::sample_slow_slots(const ModelDims& d, const float* logits, int ld, int n, const SampleCfg* cfgs, SlotRng* rngs, int B,
                                           SeqState* states, const float* X, float* XF, hipStream_t st, const float* prep_g, uint16_t* prep_A,
-                                          uint32_t* epoch) {
-    FS_REQUIRE(n <= PAR_THREADS * 4 && n <= ld, "audio-range vocabulary larger than the per-slot sampler capacity (2048)");
+                                          uint32_t* epoch, float* cap, int cap_frames) {
+    FS_REQUIRE(n <= PAR_THREADS * 4 && n <= ld && n >= 2, "audio-range vocabulary outside the per-slot sampler capacity (2 .. 2048)");
     FS_REQUIRE(!prep_g || (d.dim <= 1024 && d.dim % 4 == 0), "sampler-side RMSNorm of the next input row: dim <= 1024");
     const PrepOut po{prep_g, d.eps, prep_A, epoch};
-    hipLaunchKernelGGL((k_sample_slow_slots<KVT<WT>>), dim3(B), dim3(SLOT_THREADS), 0, st, logits, ld, n, cfgs, rngs, states, X, XF, d.dim, po);
+    hipLaunchKernelGGL((k_sample_slow_slots<KVT<WT>>), dim3(B), dim3(SLOT_THREADS), 0, st, logits, ld, n, cfgs, rngs, states, X, XF, d.dim, po,
+                       cap, cap_frames);
     FS_LAUNCH_CHECK();
 }
 template <typename WT>
@@ -3888,6 +3913,9 @@ __global__ __launch_bounds__(256) void k_cap_rows_logits(const float* __restrict
                                                          const SampleCfg* __restrict__ cp, float* __restrict__ cap, int cap_frames, int decision) {
     const int b = blockIdx.x, frame = states[b].frame;
     if (frame >= cap_frames) return;
+    // Fish <= 1.4 slots (per-slot sessions): the slow sampler records its own 2-way decision; a slot that is done (this frame's slow token
+    // was <|im_end|>, or frozen since) decides nothing, and its frame counter no longer moves: leave the terminating frame's record alone
+    if (cp->legacy && (decision == 0 || states[b].done != 0)) return;
     float* dst = cap + (((size_t)b * cap_frames + frame) * 9 + decision) * 2048;
     for (int i = threadIdx.x; i < n; i += 256) {
         float v = logits[(size_t)b * ld + i];
@@ -3901,6 +3929,7 @@ __global__ __launch_bounds__(64) void k_cap_rows_picks(const SeqState* __restric
     if (frame < 0 || frame >= cap_frames || t > n_cb) return;
     float* dst = cap + (((size_t)b * cap_frames + frame) * 9 + t) * 2048;
     const uint32_t v = states[b].cur[t];
+    if (t == 0 && cp->legacy) return;  // (recorded by the slow sampler itself: index 0 pad, 1 im_end)
     if (t == 0) dst[2047] = v == cp->im_end_id ? 0.f : (float)(v - cp->audio_base);
     else dst[1024] = (float)v;
 }

@@ -215,7 +215,8 @@ class DualARTransformer:
 
     def session(self, temp=0.7, top_p=0.9, top_k=50, seed=42, ignore_eos=False, rows=False, repetition_penalty=1.2, per_slot=False):
         """continuous batching over this handle's max_batch slots (fishrt.h: fs_lm_session_*): `with lm.session(...) as s:`
-        per_slot=True: FS_SESSION_PER_SLOT -- every slot samples like its own generate_blocking call (own settings, seed, repetition penalty)"""
+        per_slot=True: FS_SESSION_PER_SLOT -- every slot samples like its own generate_blocking call (own settings, seed, repetition penalty).
+        Fish <= 1.4 token configs (no semantic range) take per_slot=True only; plain and rows sessions raise and say so."""
         return Session(self, temp, top_p, top_k, seed, ignore_eos, rows, repetition_penalty, per_slot)
 
     def last_stats(self):
@@ -271,7 +272,8 @@ class Session:
         """rows=True: FS_SESSION_ROWS -- the slots run on the request-row persistent kernels with batch-1 semantics (repetition penalty, own
         sampler stream per slot); max_batch <= 8.
         per_slot=True: FS_SESSION_PER_SLOT -- the slots stay on the static-batch step (any max_batch, bf16 / fp8) and every slot samples like
-        its own generate_blocking call, with the settings and seed of its add() (default: the session's, seed + admission number)"""
+        its own generate_blocking call, with the settings and seed of its add() (default: the session's, seed + admission number).  The
+        only session kind of a Fish <= 1.4 handle: its slow token is the 2-way {pad, im_end} draw, one stream word per frame even when greedy"""
         self.lm, self._open = lm, False
         if rows and per_slot:
             raise ValueError("rows and per_slot exclude each other (a row session's slots already sample per slot)")

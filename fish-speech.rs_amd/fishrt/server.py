@@ -24,7 +24,8 @@ A lone job takes the batch-1 path with its persistent decode kernels.  `Schedule
 (jobs waiting together go through one `generate_static_batch` call).
 
 Per-request sampling (`Scheduler(per_slot_sampling=True)`, off by default).  A session that cannot take the request-row kernels is opened
-with FS_SESSION_PER_SLOT instead of the lock-step sampler: every job is admitted with the server's settings (repetition penalty included)
+with FS_SESSION_PER_SLOT instead of the lock-step sampler (on a Fish <= 1.4 `model_type` it is the only session kind the handle takes, so
+this switch is what gives such a deployment continuous batching at all): every job is admitted with the server's settings (repetition penalty included)
 and a sampler seed of its own, so what a job generates no longer depends on its slot or on the other jobs, and every chunk may join the
 session without `batch_size`.  Requests may then carry `temperature`, `top_p`, `top_k`, `repetition_penalty` and `seed` (an extension:
 the reference's `GenerateRequest` has none).  They are honoured on the batch-1 path and in per-slot / row sessions; a job that carries
@@ -183,9 +184,15 @@ class Scheduler:
         sa, d = j.sampling or self.s.default_sampling_args, self.s.default_sampling_args
         if not (sa.temp == 0 or (sa.temp > 0 and 0 < sa.top_k <= 256)):
             return False
-        if getattr(self.s.lm, "max_batch", 0) in (2, 4, 8) and self.sess_mode != "per_slot" and (sa.temp == 0) != (d.temp == 0):
+        # (a Fish <= 1.4 handle never opens a row session: its sessions are per-slot ones, whatever max_batch is)
+        if (getattr(self.s.lm, "max_batch", 0) in (2, 4, 8) and self.sess_mode != "per_slot" and not self._legacy_tokens()
+                and (sa.temp == 0) != (d.temp == 0)):
             return False
         return True
+
+    def _legacy_tokens(self):
+        """Fish <= 1.4 token layout (2-way slow token): of the session kinds only FS_SESSION_PER_SLOT takes such a handle (fishrt.h)"""
+        return self.s.model_type != fprompt.FISH_1_5
 
     def close(self):
         self._stop = True
@@ -283,7 +290,10 @@ class Scheduler:
                             seed = self.s.seed_source() & (2**64 - 1)
                             # handles with 2 / 4 / 8 slots and the request-row kernels: the slots keep the batch-1 semantics of _single
                             # (repetition penalty, one LogitsProcessor stream per job) while they share every decode launch (FS_SESSION_ROWS)
+                            # (not on Fish <= 1.4 handles: row and plain sessions refuse them; with per_slot_sampling they get a per-slot
+                            # session below -- every slot its own generate_blocking call, 2-way slow draw included)
                             rows = (getattr(lm, "max_batch", 0) in (2, 4, 8) and hasattr(lm, "rows_supported")
+                                    and not (self.per_slot_sampling and self._legacy_tokens())
                                     and lm.rows_supported(lm.max_batch, **sa.kw()))
                             try:
                                 sess = lm.session(temp=sa.temp, top_p=sa.top_p, top_k=sa.top_k, seed=seed, rows=True,

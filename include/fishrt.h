@@ -266,7 +266,10 @@ int fs_comm_all_gather_codes(fs_comm_t* comm, const uint32_t* codes, const int32
  * and KV pages), first frame emitted unconditionally, BatchedLogitsProcessor sampling (sampling/mod.rs:77-109; repetition penalty is
  * ignored like static_batch.rs:204-206), 1 + max(0, max_new_tokens - L + 1) iterations (static_batch.rs:122), stopping early at
  * <|im_end|> or at max_seq_len.  With temp <= 1e-7 a slot's codes are independent of what the other slots do.
- * bf16 / fp8 handles with the Fish 1.5 token layout only; while a session is open the handle's other entry points fail. */
+ * bf16 / fp8 handles; while a session is open the handle's other entry points fail.
+ * Which session kind takes which token layout: plain sessions (no flag) and FS_SESSION_ROWS sessions need the Fish 1.5 / DualAR layout
+ * (has_semantic_end != 0: the slow token is sampled over the audio range); a Fish <= 1.4 handle (has_semantic_end == 0: the slow token is
+ * the 2-way {pad, im_end} draw) takes FS_SESSION_PER_SLOT sessions only -- the other two kinds fail with an error that says so. */
 /* FS_SESSION_ROWS (round 4): the slots run on the request-row persistent kernels (csrc/lm_persist_rows.hip, see fs_lm_generate_multi) and keep
  * BATCH-1 semantics: a slot is its own generate_blocking call -- repetition penalty applied, LogitsProcessor sampling on its own StdRng stream
  * seeded `seed + the slot's admission number`, 1 + max(0, max_new_tokens - L + 1) iterations -- while requests join and leave between
@@ -274,7 +277,7 @@ int fs_comm_all_gather_codes(fs_comm_t* comm, const uint32_t* codes, const int32
  * handles with 2 <= max_batch <= 8, greedy or 0 < top_k <= 256; the device's persistent kernels are held for the session's lifetime. */
 #define FS_SESSION_ROWS 8u
 /* FS_SESSION_PER_SLOT: what a slot samples depends on the REQUEST, not on the session, at every max_batch and on every handle type
- * sessions take (bf16 / fp8, Fish 1.5 token layout, max_batch <= 256).  The session runs on the static-batch step exactly as without the
+ * sessions take (bf16 / fp8, Fish 1.5 AND Fish <= 1.4 token layouts, max_batch <= 256).  The session runs on the static-batch step exactly as without the
  * flag -- same GEMM / attention nodes, prefill, paging, prefixes, poll / release / info, slot lifetime (1 + max(0, max_new_tokens - L + 1)
  * iterations, frame 0 emitted unconditionally, stop at <|im_end|> / budget / max_seq_len, FS_GEN_IGNORE_EOS) -- but each of a frame's 9
  * decisions is that of the slot's OWN fs_lm_generate call (generate/single_batch.rs:102-210, sampling/mod.rs:51-75, rep_pen.rs:4-72):
@@ -283,7 +286,13 @@ int fs_comm_all_gather_codes(fs_comm_t* comm, const uint32_t* codes, const int32
  *     on, logits divided by the mask whatever their sign, reset when a slot is (re)activated;
  *   - LogitsProcessor rules: greedy iff temp == 0 with the batch-1 tie rule (the last maximal index), top-p compared in f32, and when the
  *     slow token is <|im_end|> the codebook decisions are skipped (codes 0) and draw nothing;
- *   - the slot's own settings and seed (fs_lm_session_add_ex), else the session's settings and `seed + the slot's admission number`.
+ *   - the slot's own settings and seed (fs_lm_session_add_ex), else the session's settings and `seed + the slot's admission number`;
+ *   - Fish <= 1.4 handles (has_semantic_end == 0): the slow decision is fs_lm_generate's legacy one (sampling/mod.rs:8-26,
+ *     single_batch.rs:104-124): p_pad = softmax([pad logit, im_end logit])[0] in f32, u = (word >> 8) * 2^-24, token = pad_id when
+ *     u < p_pad or under FS_GEN_IGNORE_EOS, else im_end_id.  It takes ONE stream word per live frame at every temperature, also when the
+ *     slot is greedy (temp == 0); the codebook decisions and the next input's embedding (codebook embeddings only under the pad /
+ *     <|semantic|> token) follow the rules above.  fs_lm_debug_capture records that decision as the batch-1 path does: entry 0 the pad
+ *     logit, 1 the im_end logit, 2 the draw u, 2047 the picked index (0 pad, 1 im_end).
  * So a slot's codes do not depend on its slot index, on max_batch or on what the other slots do; against its own fs_lm_generate call
  * they can differ only where two candidates are within rounding of each other (the row path and the batch-1 kernels sum in different
  * orders).  Settings accepted per slot and for the session: greedy (temp == 0), or temp > 0 with 0 < top_k <= 256 -- the limit of the
