@@ -1,6 +1,6 @@
 // Block-parallel top-k / top-p / WeightedIndex sampler (device code; include inside namespace fs).
 //
-// Same decision procedure, the same f32 operations in the same order, as the one-wave sampler of lm_kernels.hip (wave_topk_select +
+// Same decision procedure, the same f32 operations in the same order, as the one-wave sampler of lm_sample.hip (wave_topk_select +
 // wave_pick) and as oracle::LogitsProcessor (candle LogitsProcessor / BatchedLogitsProcessor, sampling/mod.rs:51-132; rand 0.8.5
 // WeightedIndex<f32> + UniformFloat<f32>): softmax(logits / temp) with an f64 denominator -> the top_k largest probabilities (ties: lower
 // index first), kept in ascending index order -> if top_p < their sequential f32 sum: zero every probability from the rank (descending

@@ -67,16 +67,6 @@ struct TensorDesc {
     double stdv;
 };
 
-// rand_core SeedableRng::seed_from_u64 (PCG32 expansion) -> ChaCha key
-void seed_key(uint64_t state, uint32_t* key) {
-    for (int i = 0; i < 8; ++i) {
-        state = state * 6364136223846793005ull + 11634580027462260723ull;
-        const uint32_t xorshifted = (uint32_t)(((state >> 18) ^ state) >> 27);
-        const uint32_t rot = (uint32_t)(state >> 59);
-        key[i] = (xorshifted >> rot) | (xorshifted << ((32 - rot) & 31));
-    }
-}
-
 
 // The persistent kernels need all of their 256 workgroups co-resident; two such launches on one GPU -- from two handles of one process
 // OR from two processes -- could each hold half of the CUs and wait for the other half forever (until their spin limits).  One call at a
@@ -1437,7 +1427,7 @@ class LM final : public LMBase {
                     SlotRng sr;
                     std::memset(&sr, 0xFF, sizeof(sr));
                     sr.rng = RngState{};
-                    seed_key(seed, sr.rng.key);
+                    seed_from_u64(seed, sr.rng.key);
                     up_rng.push_back(sr);
                     FS_HIP(hipMemcpyAsync(d_scfg_.as<SampleCfg>() + b, &cfg, sizeof(SampleCfg), hipMemcpyHostToDevice, st_));
                     FS_HIP(hipMemcpyAsync(d_srng_.as<SlotRng>() + b, &up_rng.back(), sizeof(SlotRng), hipMemcpyHostToDevice, st_));
@@ -1877,7 +1867,7 @@ class LM final : public LMBase {
     // seed -> ChaCha key -> a device RngState.  The copy is asynchronous and reads `host`: the caller's, alive until the stream has been waited for
     void upload_rng(uint64_t seed, RngState& host, RngState* dst, hipStream_t st) {
         host = RngState{};
-        seed_key(seed, host.key);
+        seed_from_u64(seed, host.key);
         FS_HIP(hipMemcpyAsync(dst, &host, sizeof(host), hipMemcpyHostToDevice, st));
     }
     // one prompt [C + 1][L] left-padded with <|im_end|>/0 to Lmax columns (static_batch.rs:68-111; the pad mask is built but never applied,

@@ -1,4 +1,4 @@
-// Launch interface of the dual-AR decode kernels (lm_kernels.hip).  gfx950 only.
+// Launch interface of the dual-AR decode kernels (lm_kernels.hip) and the on-device samplers (lm_sample.hip).  gfx950 only.
 //
 // Data layout in HBM:
 //  * weights: row-major [out, in] in WT (bf16, f32, or OCP e4m3fn bytes + one f32 scale per row), one 256-B aligned slab
@@ -80,7 +80,7 @@ struct RowsCtx {
     float* Q;            // [Mcap][dim]   rope'd queries (f32)
     float* part;         // [part_rows][H][n_chunks_max][Dh + 2] attention partials
     float* P;            // [down_split][Mcap][dim] down-projection split-K slabs
-    uint16_t* A;         // [Mcap][dim]   bf16 hi+lo GEMM input (normed x / attention output), fragment-major (lm_kernels.hip frag_off)
+    uint16_t* A;         // [Mcap][dim]   bf16 hi+lo GEMM input (normed x / attention output), fragment-major (lm_dev.h frag_off)
     uint16_t* C;         // [Mcap][inter] bf16 hi+lo SwiGLU activations, fragment-major
     uint16_t* A2 = nullptr;  // [Mcap][dim] second GEMM-input buffer: with `ss` set, the ffn RMSNorm is folded into the Wo / W13 GEMMs
     float* ss = nullptr;     // [Mcap][dim / 16] sum-of-squares partials of the Wo GEMM's blocks
@@ -199,6 +199,15 @@ struct RngState {      // rand 0.8.5 StdRng (ChaCha12) stream position
     uint32_t key[8];
     unsigned long long consumed;  // u32 words consumed so far
 };
+// rand_core SeedableRng::seed_from_u64 (PCG32 expansion) -> ChaCha key
+__host__ __device__ inline void seed_from_u64(unsigned long long state, uint32_t* key8) {
+    for (int i = 0; i < 8; ++i) {
+        state = state * 6364136223846793005ull + 11634580027462260723ull;
+        const uint32_t xorshifted = (uint32_t)(((state >> 18) ^ state) >> 27);
+        const uint32_t rot = (uint32_t)(state >> 59);
+        key8[i] = (xorshifted >> rot) | (xorshifted << ((32 - rot) & 31));
+    }
+}
 
 struct SlotRng {       // per-slot sampler stream of a FS_SESSION_PER_SLOT session (k_sample_*_slots)
     RngState rng;

@@ -1,6 +1,6 @@
-// Dual-AR transformer kernels for gfx950 (MI355X): the batch-1 token path (GEMV kernels, flash-decoding attention, on-device
-// samplers) first, then the MFMA row path (skinny GEMMs over activation rows, prefill flash attention) used by the prefill
-// and by the static-batch generator.
+// Dual-AR transformer kernels for gfx950 (MI355X): the batch-1 token path (GEMV kernels, flash-decoding attention) first, then
+// the MFMA row path (skinny GEMMs over activation rows, prefill flash attention) used by the prefill and by the static-batch
+// generator.  The on-device samplers are in lm_sample.hip; the device helpers both files use are in lm_dev.h.
 //
 // Every kernel here is HBM/latency-bound weight streaming (a 1024x1024 bf16 matrix is 2 MB; one CU can keep
 // ~32 KB in flight), so the design rules are (MI355X guide, "GEMV / M <= 16 decode weights"):
@@ -22,59 +22,13 @@
 #include "fs_common.h"
 #include "fs_synth.h"
 #include "lm_kernels.h"
+#include "lm_dev.h"
 
 namespace fs {
 
 // ------------------------------------------------------------------------------------------------ device helpers
 __device__ __forceinline__ float bf16_bits_to_f32(uint32_t hi16) { return __uint_as_float(hi16 << 16); }
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-template <typename WT>
-struct WTr;
-template <>
-struct WTr<bf16_t> {
-    static constexpr int EPL = 8;  // elements per 16-byte lane load
-    using vec = u32x4;
-    __device__ static __forceinline__ void unpack(const u32x4& v, float* f) {
-        f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xFFFF0000u);
-        f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xFFFF0000u);
-        f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xFFFF0000u);
-        f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xFFFF0000u);
-    }
-    __device__ static __forceinline__ float to_f32(bf16_t h) { return __uint_as_float((uint32_t)h << 16); }
-    __device__ static __forceinline__ bf16_t from_f32(float f) {  // RNE
-        uint32_t u = __float_as_uint(f);
-        u += 0x7FFFu + ((u >> 16) & 1u);
-        return (bf16_t)(u >> 16);
-    }
-};
-template <>
-struct WTr<float> {
-    static constexpr int EPL = 4;
-    using vec = f32x4;
-    __device__ static __forceinline__ void unpack(const f32x4& v, float* f) { f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w; }
-    __device__ static __forceinline__ float to_f32(float h) { return h; }
-    __device__ static __forceinline__ float from_f32(float f) { return f; }
-};
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-template <>
-struct WTr<fp8_t> {
-    static constexpr int EPL = 16;  // OCP e4m3fn weights: 16 per 16-byte lane load
-    using vec = u32x4;
-    __device__ static __forceinline__ void unpack(const u32x4& v, float* f) {
-        const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(w[i], true);
-            f[4 * i] = lo.x; f[4 * i + 1] = lo.y; f[4 * i + 2] = hi.x; f[4 * i + 3] = hi.y;
-        }
-    }
-    __device__ static __forceinline__ float to_f32(fp8_t h) { return e4m3_to_f32(h.v); }
-    __device__ static __forceinline__ fp8_t from_f32(float f) { return fp8_t{f32_to_e4m3(f)}; }
-};
 // per-row dequantisation scale (fp8 only; other weight types carry none)
 template <typename WT>
 __device__ __forceinline__ float row_scale(const float* __restrict__ ws, int row) {
@@ -85,35 +39,6 @@ __device__ __forceinline__ float row_scale(const float* __restrict__ ws, int row
 template <typename V>
 __device__ __forceinline__ V ld_stream(const V* p) {  // streamed-once weights: non-temporal (guide: nt-weights)
     return __builtin_nontemporal_load(p);
-}
-
-// ---- cross-lane reductions: DPP inside a 16-lane row (no LDS crossbar), v_readlane across the four rows.
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-constexpr int DPP_XOR1 = 0xB1;         // quad_perm [1,0,3,2]
-constexpr int DPP_XOR2 = 0x4E;         // quad_perm [2,3,0,1]
-constexpr int DPP_HALF_MIRROR = 0x141; // lane i <-> 7-i inside each 8
-constexpr int DPP_MIRROR = 0x140;      // lane i <-> 15-i inside each 16
-__device__ __forceinline__ float readlane(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
-
-// sum over the whole wave; the result is wave-uniform (scalar registers)
-__device__ __forceinline__ float wave_sum(float v) {
-    v += dpp_mov<DPP_XOR1>(v);
-    v += dpp_mov<DPP_XOR2>(v);
-    v += dpp_mov<DPP_HALF_MIRROR>(v);
-    v += dpp_mov<DPP_MIRROR>(v);
-    return (readlane(v, 15) + readlane(v, 31)) + (readlane(v, 47) + readlane(v, 63));
-}
-// sum / max over aligned groups of N consecutive lanes (N in {1,2,4,8,16}); every lane of the group gets the result
-template <int N>
-__device__ __forceinline__ float group_sum(float v) {
-    if (N >= 2) v += dpp_mov<DPP_XOR1>(v);
-    if (N >= 4) v += dpp_mov<DPP_XOR2>(v);
-    if (N >= 8) v += dpp_mov<DPP_HALF_MIRROR>(v);
-    if (N >= 16) v += dpp_mov<DPP_MIRROR>(v);
-    return v;
 }
 
 // Everything above this point is ISSUED before anything below it: keeps the machine scheduler from sinking the weight-stream
@@ -728,24 +653,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_head(const float* __restrict__ x
     if (lane == 0) logits[r] = d;
 }
 
-// ------------------------------------------------------------------------------------------------ embedding
-// dual_ar.rs:532-567: x = tok_emb[t0] + sum_c (sem_lo <= t0 <= sem_hi) * cb_emb[c*cb_size + t_{c+1}], summed in order.
-template <typename WT>
-__device__ __forceinline__ void embed_tokens(const WT* __restrict__ tok_emb, const WT* __restrict__ cb_emb, int dim, int n_cb,
-                                             int cb_size, uint32_t sem_lo, uint32_t sem_hi, const uint32_t* toks, int stride,
-                                             float* __restrict__ x, int tid, int nthreads) {
-    const uint32_t sem = toks[0];
-    const float m = (sem >= sem_lo && sem <= sem_hi) ? 1.f : 0.f;
-    for (int d = tid; d < dim; d += nthreads) {
-        float acc = 0.f + WTr<WT>::to_f32(tok_emb[(size_t)sem * dim + d]);
-        for (int c = 0; c < n_cb; ++c) {
-            const uint32_t code = toks[(size_t)(c + 1) * stride];
-            acc += WTr<WT>::to_f32(cb_emb[((size_t)c * cb_size + code) * dim + d]) * m;
-        }
-        x[d] = acc;
-    }
-}
-
+// ------------------------------------------------------------------------------------------------ embedding (embed_tokens: lm_dev.h)
 template <typename WT>
 __global__ void k_embed(const WT* __restrict__ tok_emb, const WT* __restrict__ cb_emb, int dim, int n_cb, int cb_size,
                         const SampleCfg* __restrict__ cfg, const uint32_t* __restrict__ prompt, SeqState* __restrict__ state,
@@ -811,22 +719,6 @@ struct RowMap {       // how activation row m maps onto sequences / positions
     int seq_rows;     // > 0: group prefill -- row m = token (m % seq_rows) of sequence (m / seq_rows), page tables pt_stride apart
 };
 
-__device__ __forceinline__ void split_bf16(float a, bf16_t& hi, bf16_t& lo) {
-    hi = WTr<bf16_t>::from_f32(a);
-    lo = WTr<bf16_t>::from_f32(a - WTr<bf16_t>::to_f32(hi));
-}
-
-// GEMM-input layout ("fragment-major"): the bf16 hi/lo activations are stored exactly as the MFMA B operand wants them, so
-// that every wave-wide operand load of k_gemm3 is ONE contiguous KiB (8 full cache lines) instead of 16 half lines strided
-// by a row (measured: the strided form cost 3.3 us of a 7 us GEMM node).  Element (row m, depth k, part hi=0 / lo=1) of a
-// [rows][K] activation matrix lives at (in bf16 elements)
-//     (((((m / 32) * (K / 32) + k / 32) * 2 + part) * 2 + (m / 16) % 2) * 64 + ((k / 8) % 4) * 16 + m % 16) * 8 + k % 8
-// i.e. [32-row panel][32-deep k-step][part][16-row tile][lane = kq*16 + row][8 consecutive k].
-__device__ __forceinline__ size_t frag_off(int m, int k, int part, int K) {
-    const int p = m >> 5, mt = (m >> 4) & 1, lr = m & 15, kk = k >> 5, lq = (k >> 3) & 3, e = k & 7;
-    return (((((size_t)p * (K >> 5) + kk) * 2 + part) * 2 + mt) * 64 + (lq * 16 + lr)) * 8 + e;
-}
-
 // X[m] (+= sum_s P[s][m], fixed order) ; optional RMSNorm ; emit bf16 hi/lo (fragment-major).  One block per row.
 __global__ __launch_bounds__(256) void k_prep(float* __restrict__ X, int D, const float* __restrict__ P, int S, size_t slab_stride,
                                               const float* __restrict__ norm_w, float eps, bf16_t* __restrict__ Ohi) {
@@ -873,34 +765,6 @@ __global__ __launch_bounds__(256) void k_prep(float* __restrict__ X, int D, cons
         *reinterpret_cast<uint2*>(Ohi + frag_off(m, e, 0, D)) = ph;
         *reinterpret_cast<uint2*>(Ohi + frag_off(m, e, 1, D)) = pl;
     }
-}
-
-// k_prep's RMSNorm + hi/lo split of ONE row by the block that has just written it (the batched samplers: the row is the fast decoder's
-// next input, so its first layer needs no k_prep node in a folded decode step).  Threads 0..255 take one float4 each (D <= 1024) and the sums
-// meet in k_prep's order: the fragments are bit-identical to what the node would have produced.
-struct PrepOut { const float* g; float eps; bf16_t* A; uint32_t* epoch; };   // g == nullptr: disabled; epoch != nullptr (slow-token sampler): the step epoch of k_gemm_down's tags is bumped here, once per step
-__device__ __forceinline__ void block_prep_row(const float* __restrict__ xm, int D, const PrepOut& po, int m, float* red4) {
-    __syncthreads();  // the row's stores by the other threads of this block
-    const int e = threadIdx.x * 4;
-    const bool act = threadIdx.x < 256 && e < D;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f), w = make_float4(1.f, 1.f, 1.f, 1.f);
-    if (act) { v = *reinterpret_cast<const float4*>(xm + e); w = *reinterpret_cast<const float4*>(po.g + e); }
-    float ss = 0.f;
-    ss = fmaf(v.x, v.x, ss); ss = fmaf(v.y, v.y, ss); ss = fmaf(v.z, v.z, ss); ss = fmaf(v.w, v.w, ss);
-    ss = wave_sum(ss);
-    if (threadIdx.x < 256 && (threadIdx.x & 63) == 0) red4[threadIdx.x >> 6] = ss;
-    __syncthreads();
-    if (!act) return;
-    const float d = sqrtf(((red4[0] + red4[1]) + (red4[2] + red4[3])) / (float)D + po.eps);
-    float a[4] = {(v.x / d) * w.x, (v.y / d) * w.y, (v.z / d) * w.z, (v.w / d) * w.w};
-    bf16_t hi[4], lo[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) split_bf16(a[i], hi[i], lo[i]);
-    uint2 ph, pl;
-    ph.x = hi[0] | ((uint32_t)hi[1] << 16); ph.y = hi[2] | ((uint32_t)hi[3] << 16);
-    pl.x = lo[0] | ((uint32_t)lo[1] << 16); pl.y = lo[2] | ((uint32_t)lo[3] << 16);
-    *reinterpret_cast<uint2*>(po.A + frag_off(m, e, 0, D)) = ph;
-    *reinterpret_cast<uint2*>(po.A + frag_off(m, e, 1, D)) = pl;
 }
 
 // Epilogue of the row-path GEMMs for one (row pair r/r+1, activation row m): a, b are the K-summed (and fp8-scaled) dot products.
@@ -1958,1284 +1822,6 @@ __global__ void k_advance_n(SeqState* state, int n) {
     state->step += n;
 }
 
-// ------------------------------------------------------------------------------------------------ sampling
-#if defined(FS_SAMPLE_DBG) && FS_SAMPLE_DBG == 9
-__device__ unsigned long long g_dbg_ts[64];
-#define FS_TS(i) do { if (threadIdx.x == 0) g_dbg_ts[i] = clock64(); } while (0)
-void fs_dbg_read_ts(unsigned long long* out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_dbg_ts), sizeof(unsigned long long) * 64); }
-#else
-#define FS_TS(i) do {} while (0)
-#endif
-#include "lm_bsample_dev.h"  // chacha12_word + the block-parallel sampler
-
-// ---- single-thread sequential f32 chains over an LDS array (the sampler's sums must not depend on a reduction order, so
-// they are evaluated exactly as the scalar reference does: one running f32 sum in ascending order).  A naive loop pays the
-// LDS latency (~100 cycles) per element; these helpers fetch 32 values per step with eight independent 16-byte reads and
-// then run the dependent adds out of registers (~10 cycles per element).  `a` must be 16-byte aligned and readable up to
-// the next multiple of 32; entries >= n count as +0.0 (x + 0.0f == x exactly for the non-negative sums used here).
-__device__ __forceinline__ void lds_fetch32(const float* a, int j, int n, float (&v)[32]) {
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        const float4 t = *reinterpret_cast<const float4*>(a + j + 4 * q);
-        v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
-    }
-    if (j + 32 > n) {  // tail chunk only: the full chunks run without per-element masking
-#pragma unroll
-        for (int e = 0; e < 32; ++e) if (j + e >= n) v[e] = 0.f;
-    }
-}
-__device__ float seq_sum(const float* a, int n) {
-    float sum = 0.f;
-    for (int j = 0; j < n; j += 32) {
-        float v[32];
-        lds_fetch32(a, j, n, v);
-#pragma unroll
-        for (int e = 0; e < 32; ++e) sum += v[e];
-    }
-    return sum;
-}
-// same chain, also leaving the running sums in cum[0..n) (cum may be written up to the next multiple of 32)
-__device__ float seq_sum_prefix(const float* a, int n, float* cum) {
-    float sum = 0.f;
-    for (int j = 0; j < n; j += 32) {
-        float v[32];
-        lds_fetch32(a, j, n, v);
-#pragma unroll
-        for (int e = 0; e < 32; ++e) { sum += v[e]; v[e] = sum; }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) *reinterpret_cast<float4*>(cum + j + 4 * q) = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-    }
-    return sum;
-}
-// top-p cut over probabilities sorted in descending order: the first rank r at which the running sum of sp[0..r) has
-// reached top_p (sampling/mod.rs:117-126); n when it never does
-__device__ int seq_topp_cut(const float* sp, int n, float top_p) {
-    float cumsum = 0.f;
-    for (int j = 0; j < n; j += 32) {
-        float v[32];
-        lds_fetch32(sp, j, n, v);
-#pragma unroll
-        for (int e = 0; e < 32; ++e) {
-            if (j + e >= n) return n;
-            if (cumsum >= top_p) return j + e;
-            cumsum += v[e];
-        }
-    }
-    return n;
-}
-
-constexpr int SAMPLE_THREADS = 1024;
-constexpr int SAMPLE_MAXN = 4096;  // candidates handled by the sampler (audio range 2037, codebook 1024)
-
-// WeightedIndex::new + sample over the contiguous weights w[0..cnt) (ascending token index; zero weights do not move the
-// cumulative sum): rand 0.8.5 UniformFloat<f32>::sample_single over [0, total) + partition_point on the cumulative weights.
-// Block-wide: thread 0 runs the one sequential f32 chain (leaving the running sums in `cum`), then every thread tests its
-// own entries -- the pick is the FIRST non-zero entry whose inclusive running sum exceeds the draw, else the last non-zero
-// entry.  `word` = the StdRng word for this draw (computed off the critical path by a side wave).  All threads must call.
-__device__ int block_weighted_pick(const float* w, int cnt, float* cum, RngState* rng, uint32_t word) {
-    __shared__ float s_chosen;
-    __shared__ int s_first, s_last, s_any;
-    const int tid = threadIdx.x;
-    if (tid == 0) {
-        const float total = seq_sum_prefix(w, cnt, cum);
-        s_any = total > 0.f ? 1 : 0;
-        if (total > 0.f) {
-            const float max_rand = __uint_as_float((0xFFFFFFFFu >> 9) | (127u << 23)) - 1.0f;
-            float scale = total;
-            while (scale * max_rand + 0.f >= total) scale = __uint_as_float(__float_as_uint(scale) - 1u);
-            rng->consumed += 1;
-            s_chosen = (__uint_as_float((word >> 9) | (127u << 23)) - 1.0f) * scale + 0.f;
-        }
-        s_first = 0x7FFFFFFF; s_last = -1;
-    }
-    __syncthreads();
-    if (s_any) {
-        const float chosen = s_chosen;
-        int first = 0x7FFFFFFF, last = -1;
-        for (int j = tid; j < cnt; j += SAMPLE_THREADS) {
-            if (w[j] == 0.f) continue;
-            last = j;
-            if (cum[j] > chosen && first == 0x7FFFFFFF) first = j;
-        }
-        if (first != 0x7FFFFFFF) atomicMin(&s_first, first);
-        if (last >= 0) atomicMax(&s_last, last);
-    }
-    __syncthreads();
-    const int res = !s_any ? 0 : (s_first != 0x7FFFFFFF ? s_first : s_last);
-    __syncthreads();
-    return res;
-}
-
-// ---- top-k (k <= 256) sampling of n <= 64 * EPL candidates by ONE wave, no block barrier inside (a barrier phase of a
-// 16-wave block costs ~0.4 us on this chip and the sort-based version needed ~40 of them; measured 36 us per call).  Lane l
-// owns the EPL consecutive candidates l*EPL .. l*EPL+EPL-1 in registers (ascending index == lane-major order):
-//   1. softmax in registers (DPP max, f64 sum);
-//   2. the k-th largest probability T by radix select on its bit pattern (8 + 8 + 8 + 6 bits, LDS histogram per pass);
-//   3. keep p > T and the first k - #{p > T} ties in index order (v_mbcnt prefix counts), compact the kept set into the
-//      contiguous index-ordered arrays kp / ki and 64-bit keys (p bits : 255 - position);
-//   4. sort the <= 256 keys descending in registers (4 per lane: in-lane swaps, DPP for lane^1 / lane^2, ds_bpermute above);
-//   5. lane 0 runs the ascending-index sum of the kept probabilities while lane 1 runs the descending-order top-p cumsum --
-//      two sequential f32 chains in one instruction stream; entries ranked at or after the cut are zeroed.
-// wave_topk_select leaves kp / ki in LDS; wave_pick then draws from them.  Decisions are identical to the sorted version
-// (top-k ties: lower index first; sequential f32 sums in the reference's order).
-// (implementation note, measured with tools/ubench_valu.hip: a lone wave retires a dependent VALU op every ~6 cycles, but a
-// VALU result consumed by the SCALAR unit -- v_cmp -> s_bcnt1, ballot -> s_and -- costs ~32 cycles per hop, and a dependent
-// ds_bpermute ~70.  Hence: counts and prefix sums stay in vector registers (v_addc, DPP scans), compare-exchanges are
-// written as max / min selects, and the sequential sums are pure add chains whose comparisons happen afterwards in parallel.)
-// inclusive prefix sum over the 64 lanes (DPP row shifts + row broadcasts, no LDS, no scalar hop)
-__device__ __forceinline__ int wave_incl_scan(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, false);  // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, false);  // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, false);  // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, false);  // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);  // row_bcast:15 -> rows 1, 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);  // row_bcast:31 -> rows 2, 3
-    return v;
-}
-__device__ __forceinline__ unsigned long long dpp_xor_lane_u64(unsigned long long v, int which /*1: lane^1, 2: lane^2*/) {
-    uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-    if (which == 1) { lo = __builtin_amdgcn_mov_dpp(lo, DPP_XOR1, 0xF, 0xF, false); hi = __builtin_amdgcn_mov_dpp(hi, DPP_XOR1, 0xF, 0xF, false); }
-    else { lo = __builtin_amdgcn_mov_dpp(lo, DPP_XOR2, 0xF, 0xF, false); hi = __builtin_amdgcn_mov_dpp(hi, DPP_XOR2, 0xF, 0xF, false); }
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-template <int EPL>
-__device__ void wave_topk_select(const float* lg, int n, int kk, float inv_t, float top_p, float* kp, int* ki, float* sp,
-                                 unsigned long long* keyb, float* cumsp, bool batch, double top_p64) {
-    const int lane = threadIdx.x & 63;
-    const int base = lane * EPL;
-    uint32_t u[EPL];
-    {
-        float v[EPL];
-        float mx = -INFINITY;
-#pragma unroll
-        for (int q = 0; q < EPL / 4; ++q) {
-            const float4 t = *reinterpret_cast<const float4*>(lg + base + 4 * q);
-            v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
-        }
-#pragma unroll
-        for (int s = 0; s < EPL; ++s) {
-            v[s] = (base + s < n) ? v[s] * inv_t : -INFINITY;
-            mx = fmaxf(mx, v[s]);
-        }
-        mx = fmaxf(mx, dpp_mov<DPP_XOR1>(mx)); mx = fmaxf(mx, dpp_mov<DPP_XOR2>(mx));
-        mx = fmaxf(mx, dpp_mov<DPP_HALF_MIRROR>(mx)); mx = fmaxf(mx, dpp_mov<DPP_MIRROR>(mx));
-        mx = fmaxf(fmaxf(readlane(mx, 15), readlane(mx, 31)), fmaxf(readlane(mx, 47), readlane(mx, 63)));
-        double part = 0.0;
-#pragma unroll
-        for (int s = 0; s < EPL; ++s) {
-            v[s] = (base + s < n) ? expf(v[s] - mx) : 0.f;
-            part += (double)v[s];
-        }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) part += __shfl_xor(part, m, 64);
-        const float denom = (float)part;
-#pragma unroll
-        for (int s = 0; s < EPL; ++s) u[s] = __float_as_uint(v[s] / denom);  // 0 for slots past n
-    }
-    FS_TS(1);
-    // k-th largest value T (#{u > T} < k <= #{u >= T}) by radix select over the 30-bit patterns, 8 + 8 + 8 + 6 bits from the top:
-    // per pass the candidates whose higher bits match the prefix are counted into a 256-bin LDS histogram (ds_add, no return),
-    // every lane takes 4 bins, a DPP scan gives the counts above each lane, and the bin holding the rank-th candidate extends
-    // the prefix -- 4 passes of ~1000 cycles instead of 30 bisection steps of ~380 (each a count over all candidates + a scalar hop)
-    uint32_t* hist = reinterpret_cast<uint32_t*>(keyb);  // 256 bins; keyb is only written after T is known
-    uint32_t prefix = 0u;
-    int krem = kk;
-#pragma unroll
-    for (int pass = 0; pass < 4; ++pass) {
-        const int shift = pass == 0 ? 22 : (pass == 1 ? 14 : (pass == 2 ? 6 : 0)), bits = pass == 3 ? 6 : 8;
-        *reinterpret_cast<uint4*>(hist + lane * 4) = make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-        for (int s2 = 0; s2 < EPL; ++s2)
-            if (pass == 0 || (u[s2] >> (shift + bits)) == prefix) atomicAdd(&hist[(u[s2] >> shift) & ((1u << bits) - 1u)], 1u);
-        const uint4 hv = *reinterpret_cast<const uint4*>(hist + lane * 4);  // bins 4 * lane .. 4 * lane + 3 (one wave: LDS ops stay in order)
-        const int h4[4] = {(int)hv.x, (int)hv.y, (int)hv.z, (int)hv.w};
-        const int mine = (h4[0] + h4[1]) + (h4[2] + h4[3]);
-        const int incl = wave_incl_scan(mine);
-        int above = __builtin_amdgcn_readlane(incl, 63) - incl;  // candidates in bins of higher lanes
-        int found_bin = -1, found_above = 0;
-#pragma unroll
-        for (int j = 3; j >= 0; --j) {  // from this lane's top bin down: the bin with above < rank <= above + count
-            if (found_bin < 0 && above < krem && krem <= above + h4[j]) { found_bin = lane * 4 + j; found_above = above; }
-            above += h4[j];
-        }
-        const unsigned long long m = __ballot(found_bin >= 0);  // exactly one lane (rank <= number of candidates)
-        const int src = __builtin_ctzll(m);
-        prefix = (prefix << bits) | (uint32_t)__builtin_amdgcn_readlane(found_bin, src);
-        krem -= __builtin_amdgcn_readlane(found_above, src);
-    }
-    const uint32_t lo = prefix;
-    const uint32_t T = lo;
-    FS_TS(2);
-    // keep p > T and the first k - #{p > T} ties in index order (lane-major, then slot)
-    const int nvalid = min(max(n - base, 0), EPL);  // only matters for ties at T == 0 (slots past n hold 0 as well)
-    int my_gt = 0, my_eq = 0;
-#pragma unroll
-    for (int s = 0; s < EPL; ++s) { my_gt += u[s] > T ? 1 : 0; my_eq += (u[s] == T && s < nvalid) ? 1 : 0; }
-    const int sc_gt = wave_incl_scan(my_gt), sc_eq = wave_incl_scan(my_eq);
-    const int r_ties = kk - __builtin_amdgcn_readlane(sc_gt, 63);  // ties to keep (>= 1)
-    int run_eq = sc_eq - my_eq;                                    // ties in lower lanes
-    uint32_t keepbits = 0u;
-    int my_keep = 0;
-#pragma unroll
-    for (int s = 0; s < EPL; ++s) {
-        const bool eq = u[s] == T && s < nvalid;
-        const bool keep = u[s] > T || (eq && run_eq < r_ties);
-        run_eq += eq ? 1 : 0;
-        keepbits |= keep ? (1u << s) : 0u;
-        my_keep += keep ? 1 : 0;
-    }
-    int pos = wave_incl_scan(my_keep) - my_keep;
-#pragma unroll
-    for (int s = 0; s < EPL; ++s)
-        if (keepbits & (1u << s)) {
-            kp[pos] = __uint_as_float(u[s]);
-            ki[pos] = base + s;
-            keyb[pos] = ((unsigned long long)u[s] << 32) | (unsigned long long)(255 - pos);
-            ++pos;
-        }
-    FS_TS(3);
-    // sort the kept keys (descending): position i = lane * 4 + s.  Bitonic network with the direction folded into the keys
-    // (keys of "ascending" regions are complemented for the duration of a merge phase), so every compare-exchange is the
-    // same max / min select.
-    unsigned long long k[4];
-    {
-        const ulonglong2 a = *reinterpret_cast<const ulonglong2*>(keyb + lane * 4), b = *reinterpret_cast<const ulonglong2*>(keyb + lane * 4 + 2);
-        k[0] = lane * 4 + 0 < kk ? a.x : 0ull; k[1] = lane * 4 + 1 < kk ? a.y : 0ull;
-        k[2] = lane * 4 + 2 < kk ? b.x : 0ull; k[3] = lane * 4 + 3 < kk ? b.y : 0ull;
-    }
-#pragma unroll
-    for (int lk = 1; lk <= 8; ++lk) {       // merge phase K = 1 << lk
-        const int K = 1 << lk;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {       // complement the regions that this phase sorts ascending
-            const uint32_t f = 0u - (uint32_t)(((lane * 4 + s) >> lk) & 1);
-            k[s] ^= ((unsigned long long)f << 32) | f;
-        }
-#pragma unroll
-        for (int j = K >> 1; j > 0; j >>= 1) {
-            if (j >= 4) {
-                const int lm = j >> 2;
-                const bool lower = (lane & lm) == 0;
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    const unsigned long long o = lm == 1 ? dpp_xor_lane_u64(k[s], 1) : (lm == 2 ? dpp_xor_lane_u64(k[s], 2) : __shfl_xor(k[s], lm, 64));
-                    const bool g = k[s] > o;
-                    const unsigned long long mxk = g ? k[s] : o, mnk = g ? o : k[s];
-                    k[s] = lower ? mxk : mnk;
-                }
-            } else {
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    if (s & j) continue;
-                    const unsigned long long a = k[s], b = k[s ^ j];
-                    const bool g = a > b;
-                    k[s] = g ? a : b;
-                    k[s ^ j] = g ? b : a;
-                }
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const uint32_t f = 0u - (uint32_t)(((lane * 4 + s) >> lk) & 1);
-            k[s] ^= ((unsigned long long)f << 32) | f;
-        }
-    }
-    *reinterpret_cast<float4*>(sp + lane * 4) = make_float4(__uint_as_float((uint32_t)(k[0] >> 32)), __uint_as_float((uint32_t)(k[1] >> 32)),
-                                                            __uint_as_float((uint32_t)(k[2] >> 32)), __uint_as_float((uint32_t)(k[3] >> 32)));
-    FS_TS(4);
-    // two sequential f32 chains in one instruction stream, pure adds: lane 0 sums kp (ascending index), lane 1 walks sp
-    // (descending order) and leaves its running sums in cumsp; the top-p cut is then found in parallel:
-    // cut = first rank r whose EXCLUSIVE running sum is >= top_p  ==  1 + first q with inclusive sum[q] >= top_p
-    const float* arr = lane == 1 ? sp : kp;
-    float cum = 0.f;
-    for (int j = 0; j < kk; j += 32) {
-        float v[32];
-        lds_fetch32(arr, j, kk, v);
-#pragma unroll
-        for (int e = 0; e < 32; ++e) { cum += v[e]; v[e] = cum; }
-        if (lane == 1) {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) *reinterpret_cast<float4*>(cumsp + j + 4 * q) = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-        }
-    }
-    const float sum_p = readlane(cum, 0);
-    const bool do_topp = batch ? !(top_p64 <= 0.0 || top_p64 >= (double)sum_p) : !(top_p <= 0.f || top_p >= sum_p);  // sampling/mod.rs:68
-    FS_TS(5);
-    if (do_topp) {  // zero every prob once the running cumsum (descending order) reached top_p
-        const float4 cq = *reinterpret_cast<const float4*>(cumsp + lane * 4);
-        const float cs[4] = {cq.x, cq.y, cq.z, cq.w};
-        int first = 0x7FFFFFFF;
-#pragma unroll
-        for (int s = 3; s >= 0; --s) if (lane * 4 + s < kk && cs[s] >= top_p) first = lane * 4 + s;
-        const unsigned long long mh = __ballot(first != 0x7FFFFFFF);
-        const int cutv = mh ? __builtin_amdgcn_readlane(first, __builtin_ctzll(mh)) + 1 : kk;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int i = lane * 4 + s;
-            if (i < kk && i >= cutv) kp[255 - (int)(k[s] & 0xFFull)] = 0.f;
-        }
-    }
-}
-
-// WeightedIndex::new + sample over the contiguous weights w[0..cnt), cnt <= 256, by one wave.  Zero weights (entries cut by top-p)
-// do not move the cumulative f32 sum (x + 0 == x exactly) and are never picked, so the sequential chain only walks the NON-ZERO
-// weights, compacted in ascending index order first (DPP prefix scan; `cval` / `cpos` = LDS scratch for <= 256 floats / ints):
-// after a top-p cut that is typically a few dozen of the 256 entries.  Every lane runs the same chain (lane 0 leaves the running
-// sums in `cum`), then each lane tests its four compacted entries.
-__device__ int wave_pick(const float* w, int cnt, float* cum, RngState* rng, uint32_t word, float* cval, int* cpos) {
-    const int lane = threadIdx.x & 63;
-    const float4 wv = *reinterpret_cast<const float4*>(w + lane * 4);
-    const float ws[4] = {wv.x, wv.y, wv.z, wv.w};
-    int mine = 0;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) mine += (lane * 4 + s < cnt && ws[s] != 0.f) ? 1 : 0;
-    const int incl = wave_incl_scan(mine);
-    const int m = __builtin_amdgcn_readlane(incl, 63);  // non-zero weights
-    if (m == 0) return 0;
-    int pos = incl - mine;
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-        if (lane * 4 + s < cnt && ws[s] != 0.f) { cval[pos] = ws[s]; cpos[pos] = lane * 4 + s; ++pos; }
-    float total = 0.f;
-    for (int j = 0; j < m; j += 32) {
-        float v[32];
-        lds_fetch32(cval, j, m, v);
-#pragma unroll
-        for (int e = 0; e < 32; ++e) { total += v[e]; v[e] = total; }
-        if (lane == 0) {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) *reinterpret_cast<float4*>(cum + j + 4 * q) = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
-        }
-    }
-    if (!(total > 0.f)) return 0;
-    const float max_rand = __uint_as_float((0xFFFFFFFFu >> 9) | (127u << 23)) - 1.0f;
-    float scale = total;
-    while (scale * max_rand + 0.f >= total) scale = __uint_as_float(__float_as_uint(scale) - 1u);
-    if (lane == 0) rng->consumed += 1;
-    const float chosen = (__uint_as_float((word >> 9) | (127u << 23)) - 1.0f) * scale + 0.f;
-    const float4 cv = *reinterpret_cast<const float4*>(cum + lane * 4);
-    const float cs[4] = {cv.x, cv.y, cv.z, cv.w};
-    int first = 0x7FFFFFFF;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        const int j = lane * 4 + s;
-        if (j < m && cs[s] > chosen && first == 0x7FFFFFFF) first = j;  // first kept item whose inclusive cumulative weight is > chosen
-    }
-    const unsigned long long mh = __ballot(first != 0x7FFFFFFF);
-    const int jsel = mh ? __builtin_amdgcn_readlane(first, __builtin_ctzll(mh)) : m - 1;  // else the last non-zero item
-    return cpos[jsel];
-}
-
-// Block-wide selection of one index from `n` logits held in LDS (already penalised / masked).
-//  temp == 0: host-ArgMax rule of candle's LogitsProcessor (max_by(total_cmp)): LAST maximal index wins.
-//  temp  > 0: softmax(logits / temp) -> top-k (ties: lower index first) -> top-p -> WeightedIndex draw, evaluated in
-//             ascending-index order with the StdRng stream (sampling/mod.rs:51-132).  Identical decision procedure to
-//             oracle::LogitsProcessor::sample; the softmax denominator is accumulated in f64 on both sides so that
-//             the result does not depend on reduction order.
-__device__ int block_sample(float* lg /*LDS [n]*/, int n, const SampleCfg& c, RngState* rng, float* sp /*LDS [SAMPLE_MAXN]*/,
-                            int* si /*LDS [SAMPLE_MAXN]*/, double* red /*LDS [SAMPLE_THREADS]*/, bool first_max = false) {
-    const int tid = threadIdx.x;
-    __shared__ int s_result;
-    if (c.temp == 0.f) {
-        // argmax with the host rule (LAST maximal index) or the device rule (FIRST): per-thread scan, DPP/readlane wave
-        // reduction of the value, ballot-free index pick, then one LDS hop across the waves
-        float bv = -INFINITY;
-        int bi = -1;
-        for (int i = tid; i < n; i += SAMPLE_THREADS) {
-            const float v = lg[i];
-            if (bi < 0 || (first_max ? (v > bv) : !(v < bv))) { bv = v; bi = i; }  // ascending i per thread
-        }
-        float wm = bv;
-        wm = fmaxf(wm, dpp_mov<DPP_XOR1>(wm)); wm = fmaxf(wm, dpp_mov<DPP_XOR2>(wm));
-        wm = fmaxf(wm, dpp_mov<DPP_HALF_MIRROR>(wm)); wm = fmaxf(wm, dpp_mov<DPP_MIRROR>(wm));
-        wm = fmaxf(fmaxf(readlane(wm, 15), readlane(wm, 31)), fmaxf(readlane(wm, 47), readlane(wm, 63)));
-        int cand = (bi >= 0 && bv == wm) ? bi : (first_max ? 0x7FFFFFFF : -1);
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            const int o = __shfl_xor(cand, m, 64);
-            cand = first_max ? min(cand, o) : max(cand, o);
-        }
-        float* rv = reinterpret_cast<float*>(red);
-        int* ri = reinterpret_cast<int*>(red) + 64;
-        const int wv = tid >> 6;
-        if ((tid & 63) == 0) { rv[wv] = wm; ri[wv] = cand; }
-        __syncthreads();
-        if (tid == 0) {
-            float gv = rv[0];
-            int gi = ri[0];
-            for (int w2 = 1; w2 < SAMPLE_THREADS / 64; ++w2) {
-                const float v2 = rv[w2];
-                const int i2 = ri[w2];
-                if (v2 > gv || (v2 == gv && (first_max ? i2 < gi : i2 > gi))) { gv = v2; gi = i2; }
-            }
-            s_result = gi;
-        }
-        __syncthreads();
-        const int res = s_result;
-        __syncthreads();
-        return res;
-    }
-    {
-        const bool use_k0 = c.top_k > 0 && c.top_k < n;
-        if (use_k0 && c.top_k <= 256 && n <= 2048) {
-            // one-wave path (see wave_topk_select): wave 0 selects, the last wave computes this draw's StdRng word meanwhile
-            const float inv_t0 = (float)(1.0 / (double)c.temp);
-            __shared__ uint32_t s_word0;
-            __shared__ __attribute__((aligned(16))) float w_kp[256 + 32];
-            __shared__ __attribute__((aligned(16))) float w_cum[256 + 32];
-            __shared__ __attribute__((aligned(16))) unsigned long long w_key[256];
-            __shared__ int w_ki[256];
-            const int kk0 = c.top_k;
-            FS_TS(0);
-            if (tid < 64) {
-                if (n <= 1024) wave_topk_select<16>(lg, n, kk0, inv_t0, c.top_p, w_kp, w_ki, sp, w_key, w_cum, first_max, c.top_p64);
-                else wave_topk_select<32>(lg, n, kk0, inv_t0, c.top_p, w_kp, w_ki, sp, w_key, w_cum, first_max, c.top_p64);
-            } else if (tid == SAMPLE_THREADS - 1) {
-                s_word0 = chacha12_word(rng->key, rng->consumed);
-            }
-            FS_TS(6);
-            __syncthreads();
-            FS_TS(7);
-            if (tid < 64) {
-                const int pick = wave_pick(w_kp, kk0, w_cum, rng, s_word0, sp, si);  // sp / si: free after the sort
-                if (tid == 0) s_result = w_ki[pick];
-            }
-            FS_TS(8);
-            __syncthreads();
-            const int res = s_result;
-            __syncthreads();
-            return res;
-        }
-    }
-    // softmax(logits * (1/temp)).  Blocked ownership: thread t owns the `ept` consecutive candidates t*ept .. t*ept+ept-1
-    // (ascending index order == thread-major order, which the index-order prefix scans below rely on).
-    FS_TS(0);
-    const float inv_t = (float)(1.0 / (double)c.temp);
-    const int ept = (n + SAMPLE_THREADS - 1) / SAMPLE_THREADS;  // 1..4
-    const int lane = tid & 63, wv = tid >> 6;
-    // the StdRng word of this call's draw: ~800 dependent integer ops, computed by the last wave while the others select
-    __shared__ uint32_t s_word;
-    if (tid == SAMPLE_THREADS - 1) s_word = chacha12_word(rng->key, rng->consumed);
-    float pv[4];
-    bool valid[4];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        const int i = tid * ept + s;
-        valid[s] = s < ept && i < n;
-        pv[s] = valid[s] ? lg[i] * inv_t : -INFINITY;
-        mx = fmaxf(mx, pv[s]);
-    }
-    float* rv = reinterpret_cast<float*>(red);
-    mx = fmaxf(mx, dpp_mov<DPP_XOR1>(mx)); mx = fmaxf(mx, dpp_mov<DPP_XOR2>(mx));
-    mx = fmaxf(mx, dpp_mov<DPP_HALF_MIRROR>(mx)); mx = fmaxf(mx, dpp_mov<DPP_MIRROR>(mx));
-    mx = fmaxf(fmaxf(readlane(mx, 15), readlane(mx, 31)), fmaxf(readlane(mx, 47), readlane(mx, 63)));
-    if (lane == 0) rv[wv] = mx;
-    __syncthreads();
-#pragma unroll
-    for (int w2 = 0; w2 < SAMPLE_THREADS / 64; ++w2) mx = fmaxf(mx, rv[w2]);
-    __syncthreads();
-    double part = 0.0;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        pv[s] = valid[s] ? expf(pv[s] - mx) : 0.f;
-        part += (double)pv[s];
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) part += __shfl_xor(part, m, 64);
-    if (lane == 0) red[wv] = part;
-    __syncthreads();
-    double dsum = 0.0;
-#pragma unroll
-    for (int w2 = 0; w2 < SAMPLE_THREADS / 64; ++w2) dsum += red[w2];
-    const float denom = (float)dsum;
-    __syncthreads();
-#pragma unroll
-    for (int s = 0; s < 4; ++s) pv[s] = pv[s] / denom;  // probabilities (by index, in registers)
-    FS_TS(1);
-    const bool use_k = c.top_k > 0 && c.top_k < n;
-    const int kk = use_k ? c.top_k : n;
-    __shared__ int s_cut;       // number of leading sorted entries that survive top-p
-    __shared__ int s_do_topp;
-    // ---- general path (no top-k, k > 256, or more than 2048 candidates): full bitonic sort by (prob desc, index asc) over the next power of two
-#pragma unroll
-    for (int s = 0; s < 4; ++s) if (valid[s]) lg[tid * ept + s] = pv[s];
-    int np2 = 1;
-    while (np2 < n) np2 <<= 1;
-    __syncthreads();
-    for (int i = tid; i < np2; i += SAMPLE_THREADS) {
-        if (i < n) { sp[i] = lg[i]; si[i] = i; } else { sp[i] = -1.f; si[i] = 0x7FFFFFFF; }
-    }
-    __syncthreads();
-    for (int k = 2; k <= np2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < np2; i += SAMPLE_THREADS) {
-                const int ixj = i ^ j;
-                if (ixj > i) {
-                    const bool up = (i & k) == 0;
-                    const float p1 = sp[i], p2 = sp[ixj];
-                    const int i1 = si[i], i2 = si[ixj];
-                    const bool before = (p1 > p2) || (p1 == p2 && i1 < i2);  // element i sorts before element ixj
-                    if (before != up) { sp[i] = p2; sp[ixj] = p1; si[i] = i2; si[ixj] = i1; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    // ---- tail.  Decision procedure and f32 rounding identical to the oracle restatement: sums and the WeightedIndex scan
-    // run in ascending token-index order, the top-p cut in descending probability order, every sum is a sequential f32
-    // chain.  To keep those chains short and free of dependent LDS indirections, the kept set (top_k entries, or all n)
-    // is materialised as CONTIGUOUS arrays: kp[j] = probability of the j-th kept token in index order, ki[j] = its index.
-    int* ki = reinterpret_cast<int*>(red);  // 8 KB scratch: up to 2048 ints
-    float* kp = lg;                          // the by-index array is no longer needed once (sp, si) are sorted
-    const bool small = use_k && kk <= 2 * SAMPLE_THREADS;
-    int cnt;                                 // entries of (ki, kp)
-    if (small) {
-        int kp2 = 1;
-        while (kp2 < kk) kp2 <<= 1;
-        __syncthreads();
-        for (int r = tid; r < kp2; r += SAMPLE_THREADS) { ki[r] = r < kk ? si[r] : 0x7FFFFFFF; kp[r] = r < kk ? sp[r] : 0.f; }
-        __syncthreads();
-        for (int k2 = 2; k2 <= kp2; k2 <<= 1)
-            for (int j = k2 >> 1; j > 0; j >>= 1) {
-                for (int i = tid; i < kp2; i += SAMPLE_THREADS) {
-                    const int ixj = i ^ j;
-                    if (ixj > i) {
-                        const int a0 = ki[i], a1 = ki[ixj];
-                        const bool up = (i & k2) == 0;
-                        if ((a0 > a1) == up) {
-                            ki[i] = a1; ki[ixj] = a0;
-                            const float t0 = kp[i]; kp[i] = kp[ixj]; kp[ixj] = t0;
-                        }
-                    }
-                }
-                __syncthreads();
-            }
-        cnt = kk;
-    } else {  // all n tokens (or a top-k too large for the scratch): index order is the identity
-        __syncthreads();
-        for (int i = tid; i < n; i += SAMPLE_THREADS) kp[i] = 0.f;
-        __syncthreads();
-        for (int r = tid; r < kk; r += SAMPLE_THREADS) kp[si[r]] = sp[r];
-        __syncthreads();
-        cnt = n;
-    }
-    if (tid == 0) {
-        bool do_topp = true;
-        if (use_k) {
-            const float sum_p = seq_sum(kp, cnt);  // ascending index; entries outside the top-k are 0 (or absent)
-            do_topp = first_max ? !(c.top_p64 <= 0.0 || c.top_p64 >= (double)sum_p) : !(c.top_p <= 0.f || c.top_p >= sum_p);  // (first_max == batch semantics)
-        }
-        // zero every prob once the running cumsum (descending order) reached top_p
-        s_cut = do_topp ? seq_topp_cut(sp, kk, c.top_p) : kk;
-        s_do_topp = do_topp ? 1 : 0;
-    }
-    __syncthreads();
-    if (s_do_topp && s_cut < kk) {  // entries sorting at or after rank `cut` are zeroed (parallel predicate on (prob, index))
-        const float pc = sp[s_cut];
-        const int ic = si[s_cut];
-        for (int j = tid; j < cnt; j += SAMPLE_THREADS) {
-            const float pj = kp[j];
-            const int ij = small ? ki[j] : j;
-            if (pj < pc || (pj == pc && ij >= ic)) kp[j] = 0.f;
-        }
-    }
-    __syncthreads();
-    {
-        const int r = block_weighted_pick(kp, cnt, sp, rng, s_word);
-        const int res = small ? ki[r] : r;
-        __syncthreads();
-        return res;
-    }
-}
-
-// Greedy pick (temp == 0, host ArgMax rule: LAST maximal index) without the three block barriers of block_sample: a thread's
-// candidates (indices tid + j * SAMPLE_THREADS) stay in registers, a wave reduces (value, then index) by DPP, lane 0 of every wave
-// does one 64-bit LDS atomicMax on {order-preserving value bits : index}, ONE barrier, everybody reads the winner.  *s_key must
-// have been zeroed before the previous barrier.  (A 16-wave barrier phase costs ~0.4 us on this chip.)
-__device__ __forceinline__ int dpp_wave_max_int(int v) {
-    v = max(v, __builtin_amdgcn_mov_dpp(v, DPP_XOR1, 0xF, 0xF, false)); v = max(v, __builtin_amdgcn_mov_dpp(v, DPP_XOR2, 0xF, 0xF, false));
-    v = max(v, __builtin_amdgcn_mov_dpp(v, DPP_HALF_MIRROR, 0xF, 0xF, false)); v = max(v, __builtin_amdgcn_mov_dpp(v, DPP_MIRROR, 0xF, 0xF, false));
-    return max(max(__builtin_amdgcn_readlane(v, 15), __builtin_amdgcn_readlane(v, 31)), max(__builtin_amdgcn_readlane(v, 47), __builtin_amdgcn_readlane(v, 63)));
-}
-__device__ __forceinline__ int greedy_pick(const float (&val)[SAMPLE_MAXN / SAMPLE_THREADS], int n, unsigned long long* s_key) {
-    const int tid = threadIdx.x;
-    float bv = -INFINITY;
-    int bi = -1;
-#pragma unroll
-    for (int j = 0; j < SAMPLE_MAXN / SAMPLE_THREADS; ++j) {
-        const int i = tid + j * SAMPLE_THREADS;
-        if (i < n && (bi < 0 || !(val[j] < bv))) { bv = val[j]; bi = i; }  // ascending i per thread: the later equal value wins
-    }
-    float wm = bv;
-    wm = fmaxf(wm, dpp_mov<DPP_XOR1>(wm)); wm = fmaxf(wm, dpp_mov<DPP_XOR2>(wm));
-    wm = fmaxf(wm, dpp_mov<DPP_HALF_MIRROR>(wm)); wm = fmaxf(wm, dpp_mov<DPP_MIRROR>(wm));
-    wm = fmaxf(fmaxf(readlane(wm, 15), readlane(wm, 31)), fmaxf(readlane(wm, 47), readlane(wm, 63)));
-    const int ci = dpp_wave_max_int((bi >= 0 && bv == wm) ? bi : -1);
-    if ((tid & 63) == 0 && ci >= 0) {
-        uint32_t u = __float_as_uint(wm);
-        u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;  // unsigned order == float order
-        atomicMax(s_key, ((unsigned long long)u << 32) | (unsigned long long)(uint32_t)ci);
-    }
-    __syncthreads();
-    return (int)(*s_key & 0xFFFFFFFFull);
-}
-
-__device__ inline void child_rng(const RngState* master, unsigned long long n64, RngState* out);
-
-template <typename WT>
-__global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_slow(const float* __restrict__ logits, int n,
-                                                                const SampleCfg* __restrict__ cp, RngState* rng, SeqState* __restrict__ state,
-                                                                const float* __restrict__ x, float* __restrict__ xf, int dim,
-                                                                float* const* __restrict__ hid_slot) {
-    __shared__ __attribute__((aligned(16))) float lg[SAMPLE_MAXN];
-    __shared__ __attribute__((aligned(16))) float sp[SAMPLE_MAXN];
-    __shared__ __attribute__((aligned(16))) int si[SAMPLE_MAXN];
-    __shared__ double red[SAMPLE_THREADS];
-    const int tid = threadIdx.x;
-    const SampleCfg c = *cp;
-    // generate_blocking_with_hidden (single_batch.rs:250,264-266): the hidden state of every generator iteration, the terminating one
-    // included, row = iteration index; replays after termination (done != 0 on entry) write nothing
-    float* hid = hid_slot ? *hid_slot : nullptr;
-    if (hid && state->done != 0) hid = nullptr;
-    if (hid) hid += (size_t)state->frame * dim;
-    __shared__ unsigned long long s_key;
-    if (c.batch_rows > 0 && !c.legacy) {  // row `batch_row` of a static batch on the single-sequence path: sampling/mod.rs:77-109
-        __shared__ RngState lrng;
-        SampleCfg cb = c;
-        if (cb.temp <= 1e-7f) cb.temp = 0.f;
-        for (int i = tid; i < n; i += SAMPLE_THREADS) lg[i] = logits[i];
-        for (int i = tid; i < dim; i += SAMPLE_THREADS) { const float h = x[i]; xf[i] = h; if (hid) hid[i] = h; }
-        if (tid == 0 && cb.temp != 0.f)
-            child_rng(rng, (unsigned long long)state->frame * (unsigned long long)c.batch_calls * c.batch_rows + c.batch_row, &lrng);
-        __syncthreads();
-        if (cb.ignore_eos && tid == 0) lg[0] = -INFINITY;
-        __syncthreads();
-        const int idx = block_sample(lg, n, cb, &lrng, sp, si, red, /*first_max=*/true);
-        if (tid == 0) {
-            uint32_t tok = audio_tok(c, idx);
-            if (state->done) tok = c.im_end_id;
-            state->cur[0] = tok;
-            if (tok == c.im_end_id && state->done == 0) state->done = 1;
-        }
-        return;
-    }
-    if (c.temp == 0.f && !c.legacy) {  // greedy: two barriers instead of five (see greedy_pick)
-        if (tid == 0) s_key = 0ull;
-        float val[SAMPLE_MAXN / SAMPLE_THREADS];
-#pragma unroll
-        for (int j = 0; j < SAMPLE_MAXN / SAMPLE_THREADS; ++j) {
-            const int i = tid + j * SAMPLE_THREADS;
-            val[j] = i < n ? logits[i] : -INFINITY;
-            if (i == 0 && c.ignore_eos) val[j] = -INFINITY;
-        }
-        for (int i = tid; i < dim; i += SAMPLE_THREADS) { const float h = x[i]; xf[i] = h; if (hid) hid[i] = h; }  // hidden_states -> fast decoder input (:149)
-        __syncthreads();
-        const int idx = greedy_pick(val, n, &s_key);
-        if (tid == 0) {
-            uint32_t tok = audio_tok(c, idx);  // rescale_semantic_tokens (utils.rs:45-46)
-            if (state->done) tok = c.im_end_id;
-            state->cur[0] = tok;
-            if (tok == c.im_end_id && state->done == 0) state->done = 1;
-        }
-        return;
-    }
-    for (int i = tid; i < n; i += SAMPLE_THREADS) lg[i] = logits[i];
-    for (int i = tid; i < dim; i += SAMPLE_THREADS) { const float h = x[i]; xf[i] = h; if (hid) hid[i] = h; }  // hidden_states -> fast decoder input (:149)
-    __syncthreads();
-    if (c.legacy) {
-        // legacy_softmax_sample (sampling/mod.rs:8-26): P(pad) = softmax([pad, eos])[0]; u ~ U[0,1) = (next_u32 >> 8) * 2^-24
-        // (rand Standard<f32>).  The reference draws from an unseeded thread_rng; here the draw comes from the request's
-        // seeded StdRng stream so that runs are reproducible.
-        if (tid == 0) {
-            const float pad = lg[0], eos = lg[1], m = fmaxf(pad, eos);
-            const float e_pad = expf(pad - m), e_eos = expf(eos - m);
-            const float p_pad = e_pad / (e_pad + e_eos);
-            const uint32_t w = chacha12_word(rng->key, rng->consumed);
-            rng->consumed += 1;
-            const float u = (float)(w >> 8) * (1.0f / 16777216.0f);
-            uint32_t tok = (u < p_pad || c.ignore_eos) ? c.pad_id : c.im_end_id;
-            if (state->done) tok = c.im_end_id;
-            state->cur[0] = tok;
-            if (tok == c.im_end_id && state->done == 0) state->done = 1;
-        }
-        return;
-    }
-    if (c.ignore_eos && tid == 0) lg[0] = -INFINITY;
-    __syncthreads();
-    const int idx = block_sample(lg, n, c, rng, sp, si, red);
-    if (tid == 0) {
-        uint32_t tok = audio_tok(c, idx);  // rescale_semantic_tokens (utils.rs:45-46)
-        if (state->done) tok = c.im_end_id;  // generator already terminated (single_batch.rs:86-88): stay terminated
-        state->cur[0] = tok;
-        if (tok == c.im_end_id && state->done == 0) state->done = 1;  // 1 = terminated by THIS frame, 2 = earlier
-    }
-}
-
-template <typename WT>
-__global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast(const float* __restrict__ logits, int cb, int n_cb, int cb_size,
-                                                                const SampleCfg* __restrict__ cp, RngState* rng, RepPenState rp,
-                                                                SeqState* __restrict__ state, const WT* __restrict__ fast_emb,
-                                                                float* __restrict__ xf, const WT* __restrict__ tok_emb,
-                                                                const WT* __restrict__ cb_emb, float* __restrict__ x, int dim,
-                                                                uint32_t* __restrict__ out_codes, int out_cap) {
-    __shared__ __attribute__((aligned(16))) float lg[SAMPLE_MAXN];
-    __shared__ __attribute__((aligned(16))) float sp[SAMPLE_MAXN];
-    __shared__ __attribute__((aligned(16))) int si[SAMPLE_MAXN];
-    __shared__ double red[SAMPLE_THREADS];
-    const int tid = threadIdx.x;
-    const int n = cb_size;
-    const SampleCfg c = *cp;
-    // one round trip for everything the decision needs: state words, the repetition-penalty ring, logits and mask
-    __shared__ int s_ring[17], s_meta[2];
-    __shared__ uint32_t s_prev, s_cur0, s_have_prev;
-    __shared__ unsigned long long s_key;
-    // batch_rows > 0: BatchedLogitsProcessor semantics (see k_sample_slow): first-max argmax at temp <= 1e-7, else the child StdRng of
-    // (frame, codebook call, row)
-    const bool bm = c.batch_rows > 0;
-    SampleCfg cc = c;
-    if (bm && cc.temp <= 1e-7f) cc.temp = 0.f;
-    const bool greedy = cc.temp == 0.f && !bm;
-    __shared__ RngState lrng;
-    if (bm && tid == 23 && cc.temp != 0.f)
-        child_rng(rng, ((unsigned long long)state->frame * (unsigned long long)(n_cb + 1) + 1ull + (unsigned long long)cb) * c.batch_rows + c.batch_row, &lrng);
-    if (tid == 22) s_key = 0ull;
-    if (tid < 17) s_ring[tid] = rp.ring[cb * 17 + tid];
-    else if (tid < 19) s_meta[tid - 17] = rp.ring_meta[cb * 2 + tid - 17];
-    else if (tid == 19) s_prev = state->prev[cb + 1];
-    else if (tid == 20) s_cur0 = state->cur[0];
-    else if (tid == 21) s_have_prev = (uint32_t)state->have_prev;
-    float* mask = rp.mask + (size_t)cb * cb_size;
-    float lv[SAMPLE_MAXN / SAMPLE_THREADS], mv[SAMPLE_MAXN / SAMPLE_THREADS];
-#pragma unroll
-    for (int j = 0; j < SAMPLE_MAXN / SAMPLE_THREADS; ++j) {
-        const int i = tid + j * SAMPLE_THREADS;
-        lv[j] = i < n ? logits[i] : 0.f;
-        mv[j] = i < n ? mask[i] : 1.f;
-    }
-    __syncthreads();
-    const bool eos = s_cur0 == c.im_end_id;  // single_batch.rs:153-156: push 0, skip the fast step
-    if (!eos) {
-        const bool pen = s_have_prev != 0;
-        // SingleBatchedRepPenProcessor::apply (rep_pen.rs:37-65) on the register copy of the mask.  "token in tokens_seen"
-        // == "mask[token] == penalty" (set on insert, reset to 1 on removal; with penalty == 1 the mask never changes).
-        int last = -1, dropped = -1;
-        if (pen) {
-            last = (int)s_prev;
-            const int head = (s_meta[0] + 16) % 17, len = s_meta[1] + 1;  // push_front
-            const bool drop = len > 16;
-            if (drop) dropped = s_ring[(head + len - 1) % 17];            // pop_back (never the slot just written)
-            if (tid == 0) { rp.ring[cb * 17 + head] = last; rp.ring_meta[cb * 2] = head; rp.ring_meta[cb * 2 + 1] = drop ? 16 : len; }
-        }
-#pragma unroll
-        for (int j = 0; j < SAMPLE_MAXN / SAMPLE_THREADS; ++j) {
-            const int i = tid + j * SAMPLE_THREADS;
-            if (i < n) {
-                float m = mv[j];
-                if (pen) {
-                    const float m0 = m;
-                    if (i == last) m = c.rep_pen;
-                    if (i == dropped && m == c.rep_pen) m = 1.0f;
-                    if (m != m0) mask[i] = m;
-                }
-                lv[j] = pen ? lv[j] / m : lv[j];
-                if (!greedy) lg[i] = lv[j];
-            }
-        }
-        if (!greedy) __syncthreads();
-    }
-    int code = 0;
-    if (!eos) code = greedy ? greedy_pick(lv, n, &s_key) : block_sample(lg, n, cc, bm ? &lrng : rng, sp, si, red, /*first_max=*/bm);
-    if (tid == 0) state->cur[cb + 1] = (uint32_t)code;
-    if (cb != n_cb - 1) {
-        if (!eos)
-            for (int d = tid; d < dim; d += SAMPLE_THREADS) xf[d] = WTr<WT>::to_f32(fast_emb[(size_t)code * dim + d]);
-        return;
-    }
-    // ---- end of frame (single_batch.rs:185-210 + generate_blocking :250,264-266)
-    __syncthreads();
-    __shared__ uint32_t cur[16];
-    if (tid <= n_cb) cur[tid] = (tid == n_cb) ? (uint32_t)code : state->cur[tid];
-    __syncthreads();
-    if (tid == 0 && state->done != 2) {
-        const int frame = state->frame;
-        if (state->done == 1) state->done = 2;  // replays after termination leave pos / outputs untouched
-        if (frame == 0 || cur[0] != c.im_end_id) {
-            const int o = state->n_out;
-            if (o < out_cap)
-                for (int cc = 0; cc < n_cb; ++cc) out_codes[(size_t)cc * out_cap + o] = cur[cc + 1];
-            state->n_out = o + 1;
-        }
-        for (int i = 0; i <= n_cb; ++i) state->prev[i] = cur[i];
-        state->have_prev = 1;
-        state->pos += 1;
-        state->frame = frame + 1;
-    }
-    // next slow input: embed([slow, c0..c7]) (dual_ar.rs:532-567)
-    embed_tokens<WT>(tok_emb, cb_emb, dim, n_cb, cb_size, c.sem_lo, c.sem_hi, cur, 1, x, tid, SAMPLE_THREADS);
-}
-
-// ------------------------------------------------------------------------------------------------ batched (static-batch) sampling
-// generate/static_batch.rs:117-274 + sampling/mod.rs:77-109: one block per batch row.  temp <= 1e-7 -> device argmax
-// (FIRST maximal index); else softmax(logits / temp) and, per sample() call, every row draws from its OWN child StdRng
-// seeded with the next u64 of the master StdRng (sampling/mod.rs:93-95): call c of the request, row b uses master u64
-// number c * B + b, and the single WeightedIndex draw consumes word 0 of the child stream.
-__device__ inline void child_rng(const RngState* master, unsigned long long n64, RngState* out) {
-    const unsigned long long lo = chacha12_word(master->key, 2 * n64), hi = chacha12_word(master->key, 2 * n64 + 1);
-    unsigned long long state = (hi << 32) | lo;
-    for (int i = 0; i < 8; ++i) {  // rand_core seed_from_u64 (PCG32 expansion)
-        state = state * 6364136223846793005ull + 11634580027462260723ull;
-        const uint32_t xorshifted = (uint32_t)(((state >> 18) ^ state) >> 27);
-        const uint32_t rot = (uint32_t)(state >> 59);
-        out->key[i] = (xorshifted >> rot) | (xorshifted << ((32 - rot) & 31));
-    }
-    out->consumed = 0;
-}
-
-template <typename WT>
-__global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_slow_rows(const float* __restrict__ logits, int ld, int n,
-                                                                     const SampleCfg* __restrict__ cp, const RngState* __restrict__ master,
-                                                                     int B, int calls_per_frame, SeqState* __restrict__ states,
-                                                                     const float* __restrict__ X, float* __restrict__ XF, int dim, PrepOut po) {
-    __shared__ float red4[4];
-    __shared__ __attribute__((aligned(16))) float lg[SAMPLE_MAXN];
-    __shared__ __attribute__((aligned(16))) float sp[SAMPLE_MAXN];
-    __shared__ __attribute__((aligned(16))) int si[SAMPLE_MAXN];
-    __shared__ double red[SAMPLE_THREADS];
-    __shared__ RngState lrng;
-    const int tid = threadIdx.x, b = blockIdx.x;
-    SeqState* st = states + b;
-    SampleCfg c = *cp;
-    if (c.temp <= 1e-7f) c.temp = 0.f;  // sampling/mod.rs:80
-    for (int i = tid; i < n; i += SAMPLE_THREADS) lg[i] = logits[(size_t)b * ld + i];
-    for (int i = tid; i < dim; i += SAMPLE_THREADS) XF[(size_t)b * dim + i] = X[(size_t)b * dim + i];  // hidden_states (:175)
-    __syncthreads();
-    if (c.ignore_eos && tid == 0) lg[0] = -INFINITY;
-    __syncthreads();
-    // the child StdRng (two ChaCha12 blocks + the PCG expansion: ~3 us of dependent integer work) is derived by the thread that also
-    // computes the draw's word inside block_sample -- the last one -- while wave 0 already selects; nobody else reads lrng before the
-    // barrier in front of the pick
-    if (tid == SAMPLE_THREADS - 1 && c.temp != 0.f) child_rng(master, (unsigned long long)st->frame * calls_per_frame * B + b, &lrng);
-    const int idx = block_sample(lg, n, c, &lrng, sp, si, red, /*first_max=*/true);
-    if (tid == 0) {
-        const uint32_t tok = audio_tok(c, idx);  // rescale_semantic_tokens (utils.rs:45-46)
-        st->cur[0] = tok;
-        if (tok == c.im_end_id) st->done = 1;  // batch_item_is_dead |= newly dead (:160-173)
-    }
-    if (po.epoch && b == 0 && tid == 0) po.epoch[0] += 1;
-    if (po.g) block_prep_row(XF + (size_t)b * dim, dim, po, b, red4);
-}
-
-template <typename WT>
-__global__ __launch_bounds__(SAMPLE_THREADS) void k_sample_fast_rows(const float* __restrict__ logits, int cb, int n_cb, int cb_size,
-                                                                     const SampleCfg* __restrict__ cp, const RngState* __restrict__ master,
-                                                                     int B, SeqState* __restrict__ states, const WT* __restrict__ fast_emb,
-                                                                     float* __restrict__ XF, const WT* __restrict__ tok_emb,
-                                                                     const WT* __restrict__ cb_emb, float* __restrict__ X, int dim,
-                                                                     uint32_t* __restrict__ out_codes, int out_cap, PrepOut po) {
-    __shared__ float red4[4];
-    __shared__ __attribute__((aligned(16))) float lg[SAMPLE_MAXN];
-    __shared__ __attribute__((aligned(16))) float sp[SAMPLE_MAXN];
-    __shared__ __attribute__((aligned(16))) int si[SAMPLE_MAXN];
-    __shared__ double red[SAMPLE_THREADS];
-    __shared__ RngState lrng;
-    const int tid = threadIdx.x, b = blockIdx.x, n = cb_size;
-    SeqState* st = states + b;
-    SampleCfg c = *cp;
-    if (c.temp <= 1e-7f) c.temp = 0.f;
-    // the batch repetition-penalty mask is never updated for Fish models (static_batch.rs:204-206): logits / 1.0
-    for (int i = tid; i < n; i += SAMPLE_THREADS) lg[i] = logits[(size_t)b * n + i];
-    __syncthreads();
-    if (tid == SAMPLE_THREADS - 1 && c.temp != 0.f)  // (see k_sample_slow_rows: off wave 0's critical path)
-        child_rng(master, ((unsigned long long)st->frame * (n_cb + 1) + 1 + cb) * B + b, &lrng);
-    const int code = block_sample(lg, n, c, &lrng, sp, si, red, /*first_max=*/true);
-    if (tid == 0) st->cur[cb + 1] = (uint32_t)code;
-    if (cb != n_cb - 1) {
-        for (int d = tid; d < dim; d += SAMPLE_THREADS) XF[(size_t)b * dim + d] = WTr<WT>::to_f32(fast_emb[(size_t)code * dim + d]);
-        if (po.g) block_prep_row(XF + (size_t)b * dim, dim, po, b, red4);
-        return;
-    }
-    // ---- end of frame (static_batch.rs:224-267 + generate_static_batch :305-338)
-    __syncthreads();
-    __shared__ uint32_t cur[16];
-    if (tid <= n_cb) {
-        const uint32_t slow = st->cur[0];
-        const bool is_audio = slow >= c.sem_lo;  // :229 (non-audio rows carry zero codes)
-        uint32_t v = tid == 0 ? slow : (tid == n_cb ? (uint32_t)code : st->cur[tid]);
-        if (tid > 0 && !is_audio) v = 0;
-        cur[tid] = v;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const int frame = st->frame;
-        // session slots (SampleCfg::session): a dead slot is frozen -- it neither emits nor advances -- from the frame after its last one
-        const bool frozen = c.session != 0 && st->done != 0 && frame > 0;
-        if (!frozen) {
-            if (frame == 0 || !st->done) {  // first position unconditionally, then only while the row is active
-                if (frame == 0 && cur[0] < c.sem_lo) st->step = -1;  // BatchPosition::is_audio of the first position (static_batch.rs:229): `step` is free during decode
-                const int o = st->n_out;
-                uint32_t* oc = out_codes + (size_t)b * n_cb * out_cap;
-                if (o < out_cap)
-                    for (int cc = 0; cc < n_cb; ++cc) oc[(size_t)cc * out_cap + o] = cur[cc + 1];
-                st->n_out = o + 1;
-            }
-            for (int i = 0; i <= n_cb; ++i) { st->prev[i] = cur[i]; st->cur[i] = cur[i]; }
-            st->have_prev = 1;
-            st->pos += 1;  // dead rows keep stepping in lock-step (:255-261)
-            st->frame = frame + 1;
-        }
-    }
-    embed_tokens<WT>(tok_emb, cb_emb, dim, n_cb, cb_size, c.sem_lo, c.sem_hi, cur, 1, X + (size_t)b * dim, tid, SAMPLE_THREADS);
-}
-
-// ---- the batched samplers on the block-parallel sampler (lm_bsample_dev.h): 512 threads per row, for temp > 1e-7 with 0 < top_k <= 256
-// (BASELINE configs[2]: top-k 256 / top-p 0.8).  The per-(call, row) child StdRng derivation -- two ChaCha12 blocks, the PCG expansion
-// and the word of the draw: ~5 us of dependent integer work -- no longer hides behind a 13 us one-wave selection, so it runs once per
-// step for all the step's calls: k_rows_rng_words, thread c of block b = call c of row b (the same master u64 numbers as above).
-constexpr int ROWS_WORDS_LD = 16;
-__global__ __launch_bounds__(64) void k_rows_rng_words(const RngState* __restrict__ master, int B, int calls_per_frame,
-                                                       const SeqState* __restrict__ states, uint32_t* __restrict__ words) {
-    const int b = blockIdx.x, c = threadIdx.x;
-    if (c >= calls_per_frame) return;
-    RngState child;
-    child_rng(master, ((unsigned long long)states[b].frame * calls_per_frame + c) * B + b, &child);
-    words[b * ROWS_WORDS_LD + c] = chacha12_word(child.key, 0);
-}
-constexpr int PAR_THREADS = 512;
-template <typename WT>
-__global__ __launch_bounds__(PAR_THREADS) void k_sample_slow_rows_par(const float* __restrict__ logits, int ld, int n, const SampleCfg* __restrict__ cp,
-                                                                       const uint32_t* __restrict__ words, SeqState* __restrict__ states,
-                                                                       const float* __restrict__ X, float* __restrict__ XF, int dim, PrepOut po) {
-    __shared__ float red4[4];
-    __shared__ BSampLds S;
-    const int tid = threadIdx.x, b = blockIdx.x;
-    SeqState* st = states + b;
-    const SampleCfg c = *cp;
-    float lv[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        const int i = tid * 4 + s;
-        lv[s] = i < n ? logits[(size_t)b * ld + i] : 0.f;
-        if (i == 0 && c.ignore_eos) lv[s] = -INFINITY;
-    }
-    for (int i = tid; i < dim; i += PAR_THREADS) XF[(size_t)b * dim + i] = X[(size_t)b * dim + i];  // hidden_states (:175)
-    int used = 0;
-    const int idx = bsample<PAR_THREADS, 4>(lv, n, c.top_k, (float)(1.0 / (double)c.temp), c.top_p, words[b * ROWS_WORDS_LD], &used, S, true, c.top_p64);
-    if (tid == 0) {
-        const uint32_t tok = audio_tok(c, idx);  // rescale_semantic_tokens (utils.rs:45-46)
-        st->cur[0] = tok;
-        if (tok == c.im_end_id) st->done = 1;  // batch_item_is_dead |= newly dead (:160-173)
-    }
-    if (po.epoch && b == 0 && tid == 0) po.epoch[0] += 1;
-    if (po.g) block_prep_row(XF + (size_t)b * dim, dim, po, b, red4);
-}
-template <typename WT>
-__global__ __launch_bounds__(PAR_THREADS) void k_sample_fast_rows_par(const float* __restrict__ logits, int cb, int n_cb, int cb_size,
-                                                                       const SampleCfg* __restrict__ cp, const uint32_t* __restrict__ words, SeqState* __restrict__ states,
-                                                                       const WT* __restrict__ fast_emb, float* __restrict__ XF, const WT* __restrict__ tok_emb,
-                                                                       const WT* __restrict__ cb_emb, float* __restrict__ X, int dim,
-                                                                       uint32_t* __restrict__ out_codes, int out_cap, PrepOut po) {
-    __shared__ float red4[4];
-    __shared__ BSampLds S;
-    const int tid = threadIdx.x, b = blockIdx.x, n = cb_size;
-    SeqState* st = states + b;
-    const SampleCfg c = *cp;
-    // the batch repetition-penalty mask is never updated for Fish models (static_batch.rs:204-206): logits / 1.0
-    float lv[2];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) { const int i = tid * 2 + s; lv[s] = i < n ? logits[(size_t)b * n + i] : 0.f; }
-    int used = 0;
-    const int code = bsample<PAR_THREADS, 2>(lv, n, c.top_k, (float)(1.0 / (double)c.temp), c.top_p, words[b * ROWS_WORDS_LD + 1 + cb], &used, S, true, c.top_p64);
-    if (tid == 0) st->cur[cb + 1] = (uint32_t)code;
-    if (cb != n_cb - 1) {
-        for (int d = tid; d < dim; d += PAR_THREADS) XF[(size_t)b * dim + d] = WTr<WT>::to_f32(fast_emb[(size_t)code * dim + d]);
-        if (po.g) block_prep_row(XF + (size_t)b * dim, dim, po, b, red4);
-        return;
-    }
-    // ---- end of frame (static_batch.rs:224-267 + generate_static_batch :305-338): as k_sample_fast_rows
-    __syncthreads();
-    __shared__ uint32_t cur[16];
-    if (tid <= n_cb) {
-        const uint32_t slow = st->cur[0];
-        const bool is_audio = slow >= c.sem_lo;  // :229 (non-audio rows carry zero codes)
-        uint32_t v = tid == 0 ? slow : (tid == n_cb ? (uint32_t)code : st->cur[tid]);
-        if (tid > 0 && !is_audio) v = 0;
-        cur[tid] = v;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const int frame = st->frame;
-        const bool frozen = c.session != 0 && st->done != 0 && frame > 0;
-        if (!frozen) {
-            if (frame == 0 || !st->done) {
-                if (frame == 0 && cur[0] < c.sem_lo) st->step = -1;  // (see k_sample_fast_rows)
-                const int o = st->n_out;
-                uint32_t* oc = out_codes + (size_t)b * n_cb * out_cap;
-                if (o < out_cap)
-                    for (int cc = 0; cc < n_cb; ++cc) oc[(size_t)cc * out_cap + o] = cur[cc + 1];
-                st->n_out = o + 1;
-            }
-            for (int i = 0; i <= n_cb; ++i) { st->prev[i] = cur[i]; st->cur[i] = cur[i]; }
-            st->have_prev = 1;
-            st->pos += 1;
-            st->frame = frame + 1;
-        }
-    }
-    embed_tokens<WT>(tok_emb, cb_emb, dim, n_cb, cb_size, c.sem_lo, c.sem_hi, cur, 1, X + (size_t)b * dim, tid, PAR_THREADS);
-}
-
-// ---- per-slot samplers (fs_lm_session_begin with FS_SESSION_PER_SLOT): one block per session slot on the static-batch step, every decision
-// that of the slot's OWN generate_blocking call (k_sample_slow / k_sample_fast above; single_batch.rs:102-210, sampling/mod.rs:51-75,
-// rep_pen.rs:4-72): the slot's SampleCfg, one StdRng stream per slot whose consumed count lives on the device, the 16-deep repetition
-// penalty window per codebook from the slot's second frame on, greedy iff temp == 0 with the LAST-max tie rule, top-p compared in f32, and
-// no codebook decision (codes 0, nothing drawn, window untouched) once the slow token is <|im_end|>.  Everything is read through per-slot
-// pointers, so one captured graph serves every mix of settings; greedy / sampled is a block-uniform branch.  A parked, frozen or
-// finished slot (done != 0) decides nothing, draws nothing and leaves its generator state alone; it still writes finite fast-decoder
-// input rows, because the step's GEMMs run over all rows.
-// The block has one wave more than the sampler needs.  The StdRng word of a draw is one ChaCha12 block of dependent integer work; all
-// PAR_THREADS threads take part in bsample's barriers, so none of them can compute it while the selection runs.  The extra wave does:
-// while decision d selects, it derives the word decision d + 1 will most likely need (stream position consumed + 1) into the slot's
-// look-ahead cell, tagged with that position, and ends (a terminated wave does not count at the block's barriers).  Decision d + 1 takes
-// the cell when its tag equals the stream position and derives the word itself otherwise (first decision after activation, a draw that
-// consumed nothing) -- the tag makes the look-ahead a pure latency matter, never one of correctness.
-constexpr int SLOT_THREADS = PAR_THREADS + 64;
-__device__ __forceinline__ void slot_word_ahead(SlotRng* rg, int next_decision, unsigned long long used = 1ull) {
-    const unsigned long long at = rg->rng.consumed + used;
-    rg->ahead_word[next_decision] = chacha12_word(rg->rng.key, at);
-    rg->ahead_at[next_decision] = at;
-}
-__device__ __forceinline__ uint32_t slot_word(const SlotRng* rg, int decision, unsigned long long at) {
-    if (rg->ahead_at[decision] == at) return rg->ahead_word[decision];
-    return chacha12_word(rg->rng.key, at);  // (block-uniform: every thread derives the same word)
-}
-// greedy_pick's rule (host ArgMax: the LAST maximal index) for bsample's blocked ownership (thread t owns candidates t * EPT ..): the
-// block maximum of {order-preserving value bits : index}.  *s_key must have been zeroed before the previous barrier; one barrier.
-template <int EPT>
-__device__ __forceinline__ int slot_greedy_pick(const float (&lv)[EPT], int n, unsigned long long* s_key) {
-    const int tid = threadIdx.x;
-    unsigned long long key = 0ull;
-#pragma unroll
-    for (int s = 0; s < EPT; ++s) {
-        const int i = tid * EPT + s;
-        if (i < n) {
-            uint32_t u = __float_as_uint(lv[s] + 0.f);  // (-0 -> +0: equal values, the later index wins)
-            u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;  // unsigned order == float order
-            const unsigned long long k = ((unsigned long long)u << 32) | (unsigned long long)(uint32_t)i;
-            key = k > key ? k : key;
-        }
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) { const unsigned long long o = __shfl_xor(key, m, 64); key = o > key ? o : key; }
-    if ((tid & 63) == 0) atomicMax(s_key, key);
-    __syncthreads();
-    return (int)(*s_key & 0xFFFFFFFFull);
-}
-template <typename WT>
-__global__ __launch_bounds__(SLOT_THREADS) void k_sample_slow_slots(const float* __restrict__ logits, int ld, int n, const SampleCfg* __restrict__ cfgs,
-                                                                     SlotRng* __restrict__ rngs, SeqState* __restrict__ states,
-                                                                     const float* __restrict__ X, float* __restrict__ XF, int dim, PrepOut po,
-                                                                     float* __restrict__ cap, int cap_frames) {
-    __shared__ float red4[4];
-    __shared__ BSampLds S;
-    __shared__ unsigned long long s_key;
-    const int tid = threadIdx.x, b = blockIdx.x;
-    SeqState* st = states + b;
-    SlotRng* rg = rngs + b;
-    const bool live = st->done == 0;
-    const float temp = cfgs[b].temp;
-    if (tid >= PAR_THREADS) {  // the look-ahead wave (see above); a legacy slow draw takes exactly one word, like a sampled one
-        if (tid == PAR_THREADS && live && temp != 0.f) slot_word_ahead(rg, 1);
-        return;
-    }
-    const SampleCfg c = cfgs[b];
-    if (tid == 0) s_key = 0ull;
-    for (int i = tid; i < dim; i += PAR_THREADS) XF[(size_t)b * dim + i] = X[(size_t)b * dim + i];  // hidden_states -> fast decoder input
-    if (live && c.legacy) {
-        // Fish <= 1.4 (k_sample_slow's legacy branch; sampling/mod.rs:8-26, single_batch.rs:104-124): the head rows are [pad, im_end];
-        // P(pad) = softmax([pad, eos])[0] in f32, u = (word >> 8) * 2^-24 from the slot's stream -- ONE word per live frame at every
-        // temperature, greedy included.  Block-uniform branch (every slot of a handle shares the token layout).
-        if (tid == 0) {
-            const float pad = logits[(size_t)b * ld], eos = logits[(size_t)b * ld + 1], m = fmaxf(pad, eos);
-            const float e_pad = expf(pad - m), e_eos = expf(eos - m);
-            const float p_pad = e_pad / (e_pad + e_eos);
-            const unsigned long long at = rg->rng.consumed;
-            const uint32_t w = slot_word(rg, 0, at);
-            rg->rng.consumed = at + 1ull;
-            const float u = (float)(w >> 8) * (1.0f / 16777216.0f);
-            const bool is_pad = u < p_pad || c.ignore_eos;
-            const uint32_t tok = is_pad ? c.pad_id : c.im_end_id;
-            st->cur[0] = tok;
-            if (tok == c.im_end_id) st->done = 1;  // the frame's codebook decisions are skipped; the slot freezes at the end of the frame
-            if (cap && st->frame < cap_frames) {  // (fs_lm_debug_capture: the two logits, the uniform draw, the pick -- k_fast_persist's record)
-                float* rec = cap + ((size_t)b * cap_frames + st->frame) * 9 * 2048;
-                rec[0] = pad; rec[1] = eos; rec[2] = u; rec[2047] = is_pad ? 0.f : 1.f;
-            }
-        }
-    } else if (live) {
-        float lv[4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int i = tid * 4 + s;
-            lv[s] = i < n ? logits[(size_t)b * ld + i] : 0.f;
-            if (i == 0 && c.ignore_eos) lv[s] = -INFINITY;
-        }
-        int idx;
-        if (temp == 0.f) {
-            __syncthreads();  // s_key
-            idx = slot_greedy_pick<4>(lv, n, &s_key);
-        } else {
-            const unsigned long long at = rg->rng.consumed;
-            const uint32_t word = slot_word(rg, 0, at);
-            int used = 0;
-            idx = bsample<PAR_THREADS, 4>(lv, n, c.top_k, (float)(1.0 / (double)c.temp), c.top_p, word, &used, S);
-            if (tid == 0) rg->rng.consumed = at + (unsigned long long)used;
-        }
-        if (tid == 0) {
-            const uint32_t tok = audio_tok(c, idx);  // rescale_semantic_tokens (utils.rs:45-46)
-            st->cur[0] = tok;
-            if (tok == c.im_end_id) st->done = 1;  // the frame's codebook decisions are skipped; the slot freezes at the end of the frame
-        }
-    }
-    if (po.epoch && b == 0 && tid == 0) po.epoch[0] += 1;
-    if (po.g) block_prep_row(XF + (size_t)b * dim, dim, po, b, red4);
-}
-template <typename WT>
-__global__ __launch_bounds__(SLOT_THREADS) void k_sample_fast_slots(const float* __restrict__ logits, int cb, int n_cb, int cb_size,
-                                                                     const SampleCfg* __restrict__ cfgs, SlotRng* __restrict__ rngs, RepPenState rp,
-                                                                     SeqState* __restrict__ states, const WT* __restrict__ fast_emb, float* __restrict__ XF,
-                                                                     const WT* __restrict__ tok_emb, const WT* __restrict__ cb_emb, float* __restrict__ X,
-                                                                     int dim, uint32_t* __restrict__ out_codes, int out_cap, PrepOut po) {
-    __shared__ float red4[4];
-    __shared__ BSampLds S;
-    __shared__ unsigned long long s_key;
-    const int tid = threadIdx.x, b = blockIdx.x, n = cb_size;
-    SeqState* st = states + b;
-    SlotRng* rg = rngs + b;
-    // done != 0: parked / frozen / finished, or this frame's slow token was <|im_end|> (single_batch.rs:153-156: push 0, skip the fast step)
-    const bool live = st->done == 0;
-    const float temp = cfgs[b].temp;
-    if (tid >= PAR_THREADS) {  // the look-ahead wave: the next decision is codebook cb + 1, or the next frame's slow token
-        if (tid == PAR_THREADS && live && temp != 0.f) slot_word_ahead(rg, cb == n_cb - 1 ? 0 : cb + 2);
-        // (a greedy Fish <= 1.4 slot still draws its slow word: this greedy decision consumes none, so the word sits at `consumed` itself)
-        else if (tid == PAR_THREADS && live && cb == n_cb - 1 && cfgs[b].legacy) slot_word_ahead(rg, 0, 0ull);
-        return;
-    }
-    const SampleCfg c = cfgs[b];
-    if (tid == 0) s_key = 0ull;
-    int code = 0;
-    if (live) {
-        // the slot's RepPenState of this codebook: mask [slot][n_cb][cb_size], ring [slot][n_cb][17], meta [slot][n_cb][2]
-        const size_t sc = (size_t)b * n_cb + cb;
-        float* mask = rp.mask + sc * cb_size;
-        int* ring = rp.ring + sc * 17;
-        int* meta = rp.ring_meta + sc * 2;
-        const bool pen = st->have_prev != 0;
-        // SingleBatchedRepPenProcessor::apply (rep_pen.rs:37-65), as k_sample_fast: push_front the codebook's previous pick, pop_back past
-        // 16 entries; "token in tokens_seen" == "mask[token] == penalty".  The ring is read here and written behind the decision's barriers.
-        int last = -1, dropped = -1, head = 0, len = 0;
-        bool drop = false;
-        if (pen) {
-            last = (int)st->prev[cb + 1];
-            head = (meta[0] + 16) % 17; len = meta[1] + 1;
-            drop = len > 16;
-            if (drop) dropped = ring[(head + len - 1) % 17];  // (never the slot about to be written)
-        }
-        float lv[2];
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const int i = tid * 2 + s;
-            lv[s] = 0.f;
-            if (i < n) {
-                lv[s] = logits[(size_t)b * n + i];
-                if (pen) {
-                    const float m0 = mask[i];
-                    float m = m0;
-                    if (i == last) m = c.rep_pen;
-                    if (i == dropped && m == c.rep_pen) m = 1.0f;
-                    if (m != m0) mask[i] = m;
-                    lv[s] = lv[s] / m;  // whatever the sign (rep_pen.rs:62)
-                }
-            }
-        }
-        if (temp == 0.f) {
-            __syncthreads();  // s_key
-            code = slot_greedy_pick<2>(lv, n, &s_key);
-        } else {
-            const unsigned long long at = rg->rng.consumed;
-            const uint32_t word = slot_word(rg, 1 + cb, at);
-            int used = 0;
-            code = bsample<PAR_THREADS, 2>(lv, n, c.top_k, (float)(1.0 / (double)c.temp), c.top_p, word, &used, S);
-            if (tid == 0) rg->rng.consumed = at + (unsigned long long)used;
-        }
-        if (tid == 0) {
-            if (pen) { ring[head] = last; meta[0] = head; meta[1] = drop ? 16 : len; }
-            st->cur[cb + 1] = (uint32_t)code;  // (also the next pass's qkv-table row)
-        }
-    }
-    if (cb != n_cb - 1) {
-        for (int d = tid; d < dim; d += PAR_THREADS) XF[(size_t)b * dim + d] = WTr<WT>::to_f32(fast_emb[(size_t)code * dim + d]);
-        if (po.g) block_prep_row(XF + (size_t)b * dim, dim, po, b, red4);
-        return;
-    }
-    // ---- end of frame: the bookkeeping of k_sample_fast_rows with the session's frozen-slot rule (single_batch.rs:185-210: first frame
-    // emitted unconditionally, the terminating iteration's codes are not)
-    __syncthreads();
-    __shared__ uint32_t cur[16];
-    if (tid <= n_cb) {
-        const uint32_t slow = st->cur[0];
-        const bool is_audio = slow >= c.sem_lo;
-        uint32_t v = tid == 0 ? slow : (tid == n_cb && live ? (uint32_t)code : st->cur[tid]);
-        if (tid > 0 && !is_audio) v = 0;
-        cur[tid] = v;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const int frame = st->frame;
-        const bool frozen = st->done != 0 && frame > 0;
-        if (!frozen) {
-            if (frame == 0 || !st->done) {
-                if (frame == 0 && cur[0] < c.sem_lo) st->step = -1;  // (see k_sample_fast_rows)
-                const int o = st->n_out;
-                uint32_t* oc = out_codes + (size_t)b * n_cb * out_cap;
-                if (o < out_cap)
-                    for (int cc = 0; cc < n_cb; ++cc) oc[(size_t)cc * out_cap + o] = cur[cc + 1];
-                st->n_out = o + 1;
-            }
-            for (int i = 0; i <= n_cb; ++i) { st->prev[i] = cur[i]; st->cur[i] = cur[i]; }
-            st->have_prev = 1;
-            st->pos += 1;
-            st->frame = frame + 1;
-        }
-    }
-    embed_tokens<WT>(tok_emb, cb_emb, dim, n_cb, cb_size, c.sem_lo, c.sem_hi, cur, 1, X + (size_t)b * dim, tid, PAR_THREADS);
-}
-
-// test hook of the block-parallel sampler (lm_bsample_dev.h) with the static-batch RNG derivation of k_sample_slow_rows
-template <int NT, int EPT>
-__global__ __launch_bounds__(NT) void k_bsample_rows_test(const float* __restrict__ logits, int n, const SampleCfg* __restrict__ cp,
-                                                          const RngState* __restrict__ master, int B, int call, uint32_t* __restrict__ out) {
-    __shared__ BSampLds S;
-    __shared__ RngState lrng;
-    __shared__ uint32_t s_word;
-    const int tid = threadIdx.x, b = blockIdx.x;
-    const SampleCfg c = *cp;
-    float lv[EPT];
-#pragma unroll
-    for (int s = 0; s < EPT; ++s) { const int i = tid * EPT + s; lv[s] = i < n ? logits[(size_t)b * n + i] : 0.f; }
-    if (tid == NT - 1) { child_rng(master, (unsigned long long)call * B + b, &lrng); s_word = chacha12_word(lrng.key, 0); }
-    __syncthreads();
-    int consumed = 0;
-    const int idx = bsample<NT, EPT>(lv, n, c.top_k, (float)(1.0 / (double)c.temp), c.top_p, s_word, &consumed, S, /*batch=*/true, c.top_p64);
-    if (tid == 0) out[b] = (uint32_t)idx;
-}
-
-__global__ void k_reppen_reset(RepPenState rp, int n_cb, int cb_size) {
-    const int n = n_cb * cb_size;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) { rp.mask[i] = 1.0f; rp.seen[i] = 0; }
-    if (blockIdx.x == 0 && threadIdx.x < n_cb) { rp.ring_meta[threadIdx.x * 2] = 0; rp.ring_meta[threadIdx.x * 2 + 1] = 0; }
-}
-
 // ------------------------------------------------------------------------------------------------ weight fill / convert
 template <typename WT>
 __global__ void k_synth_fill(WT* __restrict__ dst, uint64_t key, long long n_rows, long long n_cols, int row_mul, int row_off,
@@ -3464,95 +2050,6 @@ void LmKernels<WT>::fast_embed(const ModelDims& d, const void* fast_emb, const u
 }
 
 template <typename WT>
-void SampleKernels<WT>::sample_slow(const ModelDims& d, const float* logits, int n, const SampleCfg* c, RngState* rng,
-                                    SeqState* state, const float* x, float* xf, hipStream_t st, float* const* hid_slot) {
-    FS_REQUIRE(n <= SAMPLE_MAXN, "audio-range vocabulary larger than the sampler capacity");
-    hipLaunchKernelGGL((k_sample_slow<KVT<WT>>), dim3(1), dim3(SAMPLE_THREADS), 0, st, logits, n, c, rng, state, x, xf, d.dim, hid_slot);
-    FS_LAUNCH_CHECK();
-}
-
-template <typename WT>
-void SampleKernels<WT>::sample_fast(const ModelDims& d, const float* logits, int cb, int n_cb, int cb_size, const SampleCfg* c,
-                                    RngState* rng, RepPenState rp, SeqState* state, const void* fast_emb, float* xf,
-                                    const void* tok_emb, const void* cb_emb, float* x, uint32_t* out_codes, int out_cap,
-                                    hipStream_t st) {
-    FS_REQUIRE(cb_size <= SAMPLE_MAXN, "codebook larger than the sampler capacity");
-    hipLaunchKernelGGL((k_sample_fast<KVT<WT>>), dim3(1), dim3(SAMPLE_THREADS), 0, st, logits, cb, n_cb, cb_size, c, rng, rp, state,
-                       (const KVT<WT>*)fast_emb, xf, (const KVT<WT>*)tok_emb, (const KVT<WT>*)cb_emb, x, d.dim, out_codes, out_cap);
-    FS_LAUNCH_CHECK();
-}
-
-template <typename WT>
-void SampleKernels<WT>::rows_rng_words(const RngState* master, int B, int calls_per_frame, const SeqState* states, uint32_t* words, hipStream_t st) {
-    FS_REQUIRE(calls_per_frame <= ROWS_WORDS_LD, "too many sample() calls per frame");
-    hipLaunchKernelGGL(k_rows_rng_words, dim3(B), dim3(64), 0, st, master, B, calls_per_frame, states, words);
-    FS_LAUNCH_CHECK();
-}
-bool rows_par_sampler_ok(double temp, uint64_t top_k, int n_slow, int cb_size) {
-    return temp > 1e-7 && top_k > 0 && top_k <= (uint64_t)BS_MAXK && (int)top_k < cb_size && (int)top_k < n_slow && n_slow <= 2048 && cb_size <= 1024;
-}
-template <typename WT>
-void SampleKernels<WT>::sample_slow_rows(const ModelDims& d, const float* logits, int ld, int n, const SampleCfg* c, const RngState* master,
-                                         int B, int calls_per_frame, SeqState* states, const float* X, float* XF, hipStream_t st, const uint32_t* words,
-                                         const float* prep_g, uint16_t* prep_A, uint32_t* epoch) {
-    FS_REQUIRE(n <= SAMPLE_MAXN, "audio-range vocabulary larger than the sampler capacity");
-    FS_REQUIRE(!prep_g || (d.dim <= 1024 && d.dim % 4 == 0), "sampler-side RMSNorm of the next input row: dim <= 1024");
-    const PrepOut po{prep_g, d.eps, prep_A, epoch};
-    if (words) {
-        hipLaunchKernelGGL((k_sample_slow_rows_par<KVT<WT>>), dim3(B), dim3(PAR_THREADS), 0, st, logits, ld, n, c, words, states, X, XF, d.dim, po);
-        FS_LAUNCH_CHECK();
-        return;
-    }
-    hipLaunchKernelGGL((k_sample_slow_rows<KVT<WT>>), dim3(B), dim3(SAMPLE_THREADS), 0, st, logits, ld, n, c, master, B, calls_per_frame, states,
-                       X, XF, d.dim, po);
-    FS_LAUNCH_CHECK();
-}
-template <typename WT>
-void SampleKernels<WT>::sample_fast_rows(const ModelDims& d, const float* logits, int cb, int n_cb, int cb_size, const SampleCfg* c,
-                                         const RngState* master, int B, SeqState* states, const void* fast_emb, float* XF,
-                                         const void* tok_emb, const void* cb_emb, float* X, uint32_t* out_codes, int out_cap,
-                                         hipStream_t st, const uint32_t* words, const float* prep_g, uint16_t* prep_A) {
-    FS_REQUIRE(cb_size <= SAMPLE_MAXN, "codebook larger than the sampler capacity");
-    FS_REQUIRE(!prep_g || (d.dim <= 1024 && d.dim % 4 == 0), "sampler-side RMSNorm of the next input row: dim <= 1024");
-    const PrepOut po{prep_g, d.eps, prep_A, nullptr};
-    if (words) {
-        hipLaunchKernelGGL((k_sample_fast_rows_par<KVT<WT>>), dim3(B), dim3(PAR_THREADS), 0, st, logits, cb, n_cb, cb_size, c, words, states,
-                           reinterpret_cast<const KVT<WT>*>(fast_emb), XF, reinterpret_cast<const KVT<WT>*>(tok_emb), reinterpret_cast<const KVT<WT>*>(cb_emb), X, d.dim,
-                           out_codes, out_cap, po);
-        FS_LAUNCH_CHECK();
-        return;
-    }
-    hipLaunchKernelGGL((k_sample_fast_rows<KVT<WT>>), dim3(B), dim3(SAMPLE_THREADS), 0, st, logits, cb, n_cb, cb_size, c, master, B, states,
-                       (const KVT<WT>*)fast_emb, XF, (const KVT<WT>*)tok_emb, (const KVT<WT>*)cb_emb, X, d.dim, out_codes, out_cap, po);
-    FS_LAUNCH_CHECK();
-}
-
-template <typename WT>
-void SampleKernels<WT>::sample_slow_slots(const ModelDims& d, const float* logits, int ld, int n, const SampleCfg* cfgs, SlotRng* rngs, int B,
-                                          SeqState* states, const float* X, float* XF, hipStream_t st, const float* prep_g, uint16_t* prep_A,
-                                          uint32_t* epoch, float* cap, int cap_frames) {
-    FS_REQUIRE(n <= PAR_THREADS * 4 && n <= ld && n >= 2, "audio-range vocabulary outside the per-slot sampler capacity (2 .. 2048)");
-    FS_REQUIRE(!prep_g || (d.dim <= 1024 && d.dim % 4 == 0), "sampler-side RMSNorm of the next input row: dim <= 1024");
-    const PrepOut po{prep_g, d.eps, prep_A, epoch};
-    hipLaunchKernelGGL((k_sample_slow_slots<KVT<WT>>), dim3(B), dim3(SLOT_THREADS), 0, st, logits, ld, n, cfgs, rngs, states, X, XF, d.dim, po,
-                       cap, cap_frames);
-    FS_LAUNCH_CHECK();
-}
-template <typename WT>
-void SampleKernels<WT>::sample_fast_slots(const ModelDims& d, const float* logits, int cb, int n_cb, int cb_size, const SampleCfg* cfgs,
-                                          SlotRng* rngs, RepPenState rp, int B, SeqState* states, const void* fast_emb, float* XF,
-                                          const void* tok_emb, const void* cb_emb, float* X, uint32_t* out_codes, int out_cap, hipStream_t st,
-                                          const float* prep_g, uint16_t* prep_A) {
-    FS_REQUIRE(cb_size <= PAR_THREADS * 2 && n_cb + 1 <= 16, "codebook larger than the per-slot sampler capacity (1024)");
-    FS_REQUIRE(!prep_g || (d.dim <= 1024 && d.dim % 4 == 0), "sampler-side RMSNorm of the next input row: dim <= 1024");
-    const PrepOut po{prep_g, d.eps, prep_A, nullptr};
-    hipLaunchKernelGGL((k_sample_fast_slots<KVT<WT>>), dim3(B), dim3(SLOT_THREADS), 0, st, logits, cb, n_cb, cb_size, cfgs, rngs, rp, states,
-                       reinterpret_cast<const KVT<WT>*>(fast_emb), XF, reinterpret_cast<const KVT<WT>*>(tok_emb),
-                       reinterpret_cast<const KVT<WT>*>(cb_emb), X, d.dim, out_codes, out_cap, po);
-    FS_LAUNCH_CHECK();
-}
-
-template <typename WT>
 void launch_gather_rows(const void* src, int dim, uint32_t r0, uint32_t r1, void* dst, hipStream_t st) {
     hipLaunchKernelGGL((k_gather_rows<WT>), dim3(1), dim3(256), 0, st, (const WT*)src, dim, r0, r1, (WT*)dst);
     FS_LAUNCH_CHECK();
@@ -3563,10 +2060,6 @@ template void launch_gather_rows<fp8_t>(const void*, int, uint32_t, uint32_t, vo
 
 void launch_advance(SeqState* state, hipStream_t st) {
     hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, st, state);
-    FS_LAUNCH_CHECK();
-}
-void launch_reppen_reset(RepPenState rp, int n_cb, int cb_size, hipStream_t st) {
-    hipLaunchKernelGGL(k_reppen_reset, dim3(8), dim3(256), 0, st, rp, n_cb, cb_size);
     FS_LAUNCH_CHECK();
 }
 
@@ -3907,40 +2400,6 @@ void LmKernels<WT>::rows_head(const ModelDims& d, int M, const RowsCtx& c, const
     }
 }
 
-// ---- decision capture on the row path (fs_lm_debug_capture for generate_static_batch / sessions): what every row's decision saw and picked,
-// in the layout of the request-row kernels' record: cap[row][cap_frames][9][2048], logits at [0, n), the pick at [2047] (slow) / [1024] (fast)
-__global__ __launch_bounds__(256) void k_cap_rows_logits(const float* __restrict__ logits, int ld, int n, const SeqState* __restrict__ states,
-                                                         const SampleCfg* __restrict__ cp, float* __restrict__ cap, int cap_frames, int decision) {
-    const int b = blockIdx.x, frame = states[b].frame;
-    if (frame >= cap_frames) return;
-    // Fish <= 1.4 slots (per-slot sessions): the slow sampler records its own 2-way decision; a slot that is done (this frame's slow token
-    // was <|im_end|>, or frozen since) decides nothing, and its frame counter no longer moves: leave the terminating frame's record alone
-    if (cp->legacy && (decision == 0 || states[b].done != 0)) return;
-    float* dst = cap + (((size_t)b * cap_frames + frame) * 9 + decision) * 2048;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        float v = logits[(size_t)b * ld + i];
-        if (decision == 0 && i == 0 && cp->ignore_eos) v = -INFINITY;  // (what the slow samplers do to <|im_end|> before they select)
-        dst[i] = v;
-    }
-}
-__global__ __launch_bounds__(64) void k_cap_rows_picks(const SeqState* __restrict__ states, const SampleCfg* __restrict__ cp, float* __restrict__ cap,
-                                                       int cap_frames, int n_cb) {
-    const int b = blockIdx.x, frame = states[b].frame - 1, t = threadIdx.x;  // (the last sampler of the frame advanced the counter)
-    if (frame < 0 || frame >= cap_frames || t > n_cb) return;
-    float* dst = cap + (((size_t)b * cap_frames + frame) * 9 + t) * 2048;
-    const uint32_t v = states[b].cur[t];
-    if (t == 0 && cp->legacy) return;  // (recorded by the slow sampler itself: index 0 pad, 1 im_end)
-    if (t == 0) dst[2047] = v == cp->im_end_id ? 0.f : (float)(v - cp->audio_base);
-    else dst[1024] = (float)v;
-}
-void launch_cap_rows_logits(const float* logits, int ld, int n, const SeqState* states, const SampleCfg* cfg, int B, float* cap, int cap_frames, int decision,
-                            hipStream_t st) {
-    hipLaunchKernelGGL(k_cap_rows_logits, dim3(B), dim3(256), 0, st, logits, ld, n, states, cfg, cap, cap_frames, decision);
-}
-void launch_cap_rows_picks(const SeqState* states, const SampleCfg* cfg, int B, float* cap, int cap_frames, int n_cb, hipStream_t st) {
-    hipLaunchKernelGGL(k_cap_rows_picks, dim3(B), dim3(64), 0, st, states, cfg, cap, cap_frames, n_cb);
-}
-
 void launch_advance_n(SeqState* state, int n, hipStream_t st) {
     hipLaunchKernelGGL(k_advance_n, dim3(1), dim3(1), 0, st, state, n);
     FS_LAUNCH_CHECK();
@@ -3989,60 +2448,9 @@ void launch_hidden_rows(HidSlot* tab, const SeqState* states, const float* X, in
     FS_LAUNCH_CHECK();
 }
 
-// ---- sampler test hook (fs_selftest_sample_rows): the static-batch slow sampler on caller-provided logits, B rows of n candidates,
-// as sample() call number `call_index` of a request (child StdRng of row b = master u64 number call_index * B + b)
-void debug_sample_rows(int device, const float* logits, int B, int n, double temp, double top_p, uint64_t top_k, uint64_t seed,
-                       int call_index, uint32_t* out) {
-    FS_REQUIRE(B >= 1 && n >= 1 && n <= SAMPLE_MAXN, "bad sampler test shape");
-    FS_HIP(hipSetDevice(device));
-    float* d_logits = nullptr; SampleCfg* d_cfg = nullptr; RngState* d_rng = nullptr; SeqState* d_st = nullptr;
-    FS_HIP(hipMalloc(&d_logits, sizeof(float) * (size_t)B * n));
-    FS_HIP(hipMalloc(&d_cfg, sizeof(SampleCfg))); FS_HIP(hipMalloc(&d_rng, sizeof(RngState))); FS_HIP(hipMalloc(&d_st, sizeof(SeqState) * B));
-    FS_HIP(hipMemcpy(d_logits, logits, sizeof(float) * (size_t)B * n, hipMemcpyHostToDevice));
-    SampleCfg c = {};
-    c.temp = (float)temp; c.top_p = (float)top_p; c.top_k = (int)std::min<uint64_t>(top_k, 1u << 30); c.rep_pen = 1.f; c.top_p64 = top_p;
-    FS_HIP(hipMemcpy(d_cfg, &c, sizeof(c), hipMemcpyHostToDevice));
-    RngState r = {};
-    unsigned long long state = seed;
-    for (int i = 0; i < 8; ++i) {  // rand_core seed_from_u64 (PCG32 expansion)
-        state = state * 6364136223846793005ull + 11634580027462260723ull;
-        const uint32_t xorshifted = (uint32_t)(((state >> 18) ^ state) >> 27);
-        const uint32_t rot = (uint32_t)(state >> 59);
-        r.key[i] = (xorshifted >> rot) | (xorshifted << ((32 - rot) & 31));
-    }
-    FS_HIP(hipMemcpy(d_rng, &r, sizeof(r), hipMemcpyHostToDevice));
-    std::vector<SeqState> hs(B);
-    for (auto& s : hs) { s = SeqState{}; s.frame = call_index; }
-    FS_HIP(hipMemcpy(d_st, hs.data(), sizeof(SeqState) * B, hipMemcpyHostToDevice));
-    // FISHRT_SAMPLER_IMPL=par512: the block-parallel sampler the persistent fast decoder uses (lm_bsample_dev.h), 512 threads per row
-    const char* impl = getenv("FISHRT_SAMPLER_IMPL");
-    const bool par = impl && std::string(impl) == "par512" && temp > 1e-7 && top_k > 0 && top_k <= 256 && (int)top_k < n && n <= 2048;
-    if (par) {
-        uint32_t* d_out = nullptr;
-        FS_HIP(hipMalloc(&d_out, sizeof(uint32_t) * B));
-        if (n <= 1024) hipLaunchKernelGGL((k_bsample_rows_test<512, 2>), dim3(B), dim3(512), 0, nullptr, d_logits, n, d_cfg, d_rng, B, call_index, d_out);
-        else hipLaunchKernelGGL((k_bsample_rows_test<512, 4>), dim3(B), dim3(512), 0, nullptr, d_logits, n, d_cfg, d_rng, B, call_index, d_out);
-        FS_LAUNCH_CHECK();
-        FS_HIP(hipDeviceSynchronize());
-        FS_HIP(hipMemcpy(out, d_out, sizeof(uint32_t) * B, hipMemcpyDeviceToHost));
-        (void)hipFree(d_out);
-    } else {
-    hipLaunchKernelGGL((k_sample_slow_rows<bf16_t>), dim3(B), dim3(SAMPLE_THREADS), 0, nullptr, d_logits, n, n, d_cfg, d_rng, B, 1, d_st,
-                       (const float*)nullptr, (float*)nullptr, 0, PrepOut{nullptr, 0.f, nullptr, nullptr});
-    FS_LAUNCH_CHECK();
-    FS_HIP(hipDeviceSynchronize());
-    FS_HIP(hipMemcpy(hs.data(), d_st, sizeof(SeqState) * B, hipMemcpyDeviceToHost));
-    for (int b = 0; b < B; ++b) out[b] = hs[b].cur[0];
-    }
-    (void)hipFree(d_logits); (void)hipFree(d_cfg); (void)hipFree(d_rng); (void)hipFree(d_st);
-}
-
 template struct LmKernels<bf16_t>;
 template struct LmKernels<float>;
-template struct SampleKernels<bf16_t>;
-template struct SampleKernels<float>;
 template struct LmKernels<fp8_t>;
-template struct SampleKernels<fp8_t>;
 template void launch_synth_fill<bf16_t>(bf16_t*, uint64_t, int64_t, int64_t, int, int, float, float, int, hipStream_t);
 template void launch_synth_fill<float>(float*, uint64_t, int64_t, int64_t, int, int, float, float, int, hipStream_t);
 template void launch_convert_rows<bf16_t>(bf16_t*, const float*, int64_t, int64_t, int, int, hipStream_t);

@@ -1,7 +1,7 @@
 """Step time of a FS_SESSION_PER_SLOT session against the lock-step session step (include/fishrt.h).
 
     python tools/bench_session_per_slot.py --out new.json                      # this build: both modes, alternated in one process
-    python tools/bench_session_per_slot.py --lib /path/libfishrt.so --out parent.json   # another build (a parent commit: lock-step only)
+    python tools/bench_session_per_slot.py --lib /path/libfishrt.so --out parent.json   # another build (a parent commit; lock-step only if it lacks the mode)
     python tools/bench_session_per_slot.py --merge parent.json [parent2.json ...] new.json --out profiles/session_per_slot_step.json
 
 32 live slots (--slots), ignore-eos, sampling 0.7 / 0.8 / 256 with repetition penalty 1.4, Fish-1.5 shapes, synthetic bf16 weights.  A
@@ -10,7 +10,8 @@ own HIP-event time around the session_step launches (last_stats()["decode_ms"]) 
 alternate, every round starts from the same prompts, so both modes walk the same KV lengths.  Per mode: every round's figure, the median
 and the run-to-run spread (max - min) / median.  --merge states the two checks: the per-slot step within 5 % of the PARENT's lock-step
 step, and this build's lock-step step inside the parent's own run-to-run spread (over all rounds of all the parent runs given: run the
-parent before AND after the new build, a process-to-process shift is larger than the spread inside one process)."""
+parent before AND after the new build, a process-to-process shift is larger than the spread inside one process).  Where the parent runs
+have the per-slot mode too, the same spread check is stated for per-slot against the parent's per-slot."""
 import argparse
 import json
 import os
@@ -83,6 +84,13 @@ def merge(parents, new):
     out["per_slot_within_5_percent"] = out["per_slot_over_parent_lock_step"] <= 0.05
     out["lock_step_new_over_parent"] = new["lock_step"]["median_us"] / base - 1.0
     out["lock_step_inside_parent_spread"] = min(rounds) <= new["lock_step"]["median_us"] <= max(rounds)
+    if all("per_slot" in p for p in parents):  # a parent that has the mode: the same spread check, per-slot against per-slot
+        ps = [x for p in parents for x in p["per_slot"]["us_per_step"]]
+        pbase = statistics.median(ps)
+        out["parent_per_slot_us"] = dict(median=pbase, min=min(ps), max=max(ps), spread=(max(ps) - min(ps)) / pbase,
+                                         run_medians=[p["per_slot"]["median_us"] for p in parents])
+        out["per_slot_new_over_parent"] = new["per_slot"]["median_us"] / pbase - 1.0
+        out["per_slot_inside_parent_spread"] = min(ps) <= new["per_slot"]["median_us"] <= max(ps)
     return out
 
 

@@ -1,4 +1,4 @@
-// Micro-benchmark of the on-device sampler (k_sample_slow: n candidates, one block): 64 graph nodes, us/node for greedy
+// Micro-benchmark of the on-device sampler (lm_sample.hip, k_sample_slow: n candidates, one block): 64 graph nodes, us/node for greedy
 // and sampled configurations.  Build: tools/build_ubench.sh.  usage: ubench_sample.bin [n]
 #include <hip/hip_runtime.h>
 #include <cstdio>
