@@ -11,6 +11,7 @@
 #include "lm_kernels.h"
 #include "lm_persist.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -75,6 +76,26 @@ int fs_selftest(int device_id, const char* what) {
 int fs_selftest_sample_rows(int device_id, const float* logits, int B, int n, const fs_sampling* s, uint64_t seed, int call_index, uint32_t* out) {
     FS_ARG(logits && s && out, "null argument");
     FS_TRY(fs::debug_sample_rows(device_id, logits, B, n, s->temp, s->top_p, s->top_k, seed, call_index, out))
+}
+
+int fs_selftest_sample_slots(int device_id, const float* logits, int S, int R, int n, const fs_sampling* samplings, const uint64_t* seeds,
+                             uint32_t* out, uint64_t* words_used) {
+    FS_ARG(logits && samplings && seeds && out && words_used, "null argument");
+    FS_ARG(S >= 1 && R >= 1 && n >= 1 && n <= 2048, "bad sampler test shape (S, R >= 1; 1 <= n <= 2048)");
+    FS_TRY({
+        std::vector<fs::SampleCfg> cfgs((size_t)S);
+        for (int i = 0; i < S; ++i) {
+            const fs_sampling& sa = samplings[i];
+            if (!std::isfinite(sa.temp) || sa.temp < 0.0) throw fs::Error("fs_selftest_sample_slots: temp must be finite and >= 0");
+            if (!std::isfinite(sa.top_p)) throw fs::Error("fs_selftest_sample_slots: top_p must be finite");
+            fs::SampleCfg c = {};
+            c.temp = (float)sa.temp; c.top_p = (float)sa.top_p; c.top_p64 = sa.top_p;
+            c.top_k = (int)std::min<uint64_t>(sa.top_k, 1u << 30);
+            c.rep_pen = 1.f;
+            cfgs[(size_t)i] = c;
+        }
+        fs::debug_sample_slots(device_id, logits, S, R, n, cfgs.data(), seeds, out, words_used);
+    })
 }
 
 // ---- replica fan-out over RCCL (fs_comm.h)

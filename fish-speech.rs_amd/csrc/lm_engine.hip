@@ -907,12 +907,17 @@ class LM final : public LMBase {
         // FS_SESSION_PER_SLOT: the slots stay on the static-batch step, but its 9 sampler nodes are the per-slot ones (k_sample_*_slots):
         // every slot decides like its own generate_blocking call, with its own settings, StdRng stream and repetition-penalty windows
         const bool per_slot = (flags & FS_SESSION_PER_SLOT) != 0;
+        // FS_SESSION_WIDE_SAMPLER: the per-slot sampler nodes are the instantiation that also covers nucleus-only and top_k > 256 settings
+        const bool wide = (flags & FS_SESSION_WIDE_SAMPLER) != 0;
+        FS_REQUIRE(!wide || (per_slot && !(flags & FS_SESSION_ROWS)),
+                   "FS_SESSION_WIDE_SAMPLER is valid only together with FS_SESSION_PER_SLOT (not alone, not with FS_SESSION_ROWS)");
         FS_REQUIRE(!(per_slot && (flags & FS_SESSION_ROWS)), "FS_SESSION_PER_SLOT and FS_SESSION_ROWS exclude each other (a row session's slots already sample per slot)");
         if (per_slot) {
             FS_REQUIRE(n_audio_ <= 2048 && a_.codebook_size <= 1024, "FS_SESSION_PER_SLOT needs <= 2048 slow candidates and codebooks of <= 1024 entries");
-            require_slot_sampling(s);
+            require_slot_sampling(s, wide);
         }
         sess_slots_ = false;
+        sess_wide_ = false;
         std::unique_lock<PersistLock> rows_lock;
         struct RowsGuard {  // anything thrown below leaves the handle out of row mode (the local lock releases itself)
             bool& flag; bool armed = true;
@@ -990,10 +995,17 @@ class LM final : public LMBase {
         rows_guard.armed = false;
         if (sess_rows_) sess_plock_ = std::move(rows_lock);
         sess_slots_ = per_slot;
+        sess_wide_ = wide;
         sess_active_ = true;
     }
     // what a slot of a FS_SESSION_PER_SLOT session may sample with: the boundary of the in-launch samplers (fishrt.h: fs_lm_generate)
-    void require_slot_sampling(const fs_sampling& s) const {
+    // In a wide session (FS_SESSION_WIDE_SAMPLER): greedy, or temp > 0 with any top_k and any finite top_p.
+    void require_slot_sampling(const fs_sampling& s, bool wide) const {
+        if (wide) {
+            if (!std::isfinite(s.temp) || s.temp < 0.0) throw Error("FS_SESSION_WIDE_SAMPLER: temp must be finite and >= 0 (0 = greedy)");
+            if (!std::isfinite(s.top_p)) throw Error("FS_SESSION_WIDE_SAMPLER: top_p must be finite");
+            return;
+        }
         const bool ok = s.temp == 0.0 || (s.temp > 0.0 && s.top_k > 0 && s.top_k <= 256);
         if (!ok) throw Error("FS_SESSION_PER_SLOT: a slot samples greedy (temp == 0) or with temp > 0 and 0 < top_k <= 256 (the in-launch samplers' limit)");
     }
@@ -1013,7 +1025,7 @@ class LM final : public LMBase {
         if (sampling || seed) {
             if (!sess_slots_ && !sess_rows_)
                 throw Error("per-slot sampling / seed need a session begun with FS_SESSION_PER_SLOT or FS_SESSION_ROWS (the lock-step sampler has one setting and one stream per session)");
-            if (sampling && sess_slots_) require_slot_sampling(*sampling);
+            if (sampling && sess_slots_) require_slot_sampling(*sampling, sess_wide_);
             if (sampling && sess_rows_) {
                 if ((sampling->temp != 0.0) != sess_sampled_) throw Error("FS_SESSION_ROWS: every slot greedy or every slot sampled, like the session's own setting");
                 if (sess_sampled_ && !fast_persist_samples((float)sampling->temp, clamp_top_k(sampling->top_k), a_.codebook_size))
@@ -1596,6 +1608,7 @@ class LM final : public LMBase {
         FS_HIP(hipStreamSynchronize(st_));
         sess_active_ = false;
         sess_slots_ = false;
+        sess_wide_ = false;
         sess_released_frames_ = 0;
         if (sess_rows_) check_ctl({&d_rctl_s_, &d_rctl_f_}, nullptr, nullptr);  // (a session that ended on an error: reset only)
         sess_rows_ = false;
@@ -2315,7 +2328,7 @@ class LM final : public LMBase {
         if (slots)
             SampleKernels<WT>::sample_slow_slots(d_, d_lrows_.as<float>(), ld_slow_, n_audio_, d_scfg_.as<SampleCfg>(), d_srng_.as<SlotRng>(), B, state(0),
                                                  cs.X, d_xfrows_.as<float>(), st_, prep_g, cs.A, fold ? d_epoch_.as<uint32_t>() : nullptr,
-                                                 capt ? d_rcap_.as<float>() : nullptr, cap_frames_);
+                                                 capt ? d_rcap_.as<float>() : nullptr, cap_frames_, sess_wide_);
         else
         SampleKernels<WT>::sample_slow_rows(d_, d_lrows_.as<float>(), ld_slow_, n_audio_, d_cfg_.as<SampleCfg>(), d_rng_.as<RngState>(), B,
                                             C + 1, state(0), cs.X, d_xfrows_.as<float>(), st_, words, prep_g, cs.A, fold ? d_epoch_.as<uint32_t>() : nullptr);
@@ -2350,7 +2363,7 @@ class LM final : public LMBase {
                 RepPenState rp0 = slot_rp(0);
                 SampleKernels<WT>::sample_fast_slots(d_, d_lfast_.as<float>(), cbi, C, a_.codebook_size, d_scfg_.as<SampleCfg>(), d_srng_.as<SlotRng>(), rp0,
                                                      B, state(0), fast_emb_, d_xfrows_.as<float>(), tok_emb_, cb_emb_, cs.X, d_out_.as<uint32_t>(), out_cap_,
-                                                     st_, prep_f, cs.A);
+                                                     st_, prep_f, cs.A, sess_wide_);
             } else
             SampleKernels<WT>::sample_fast_rows(d_, d_lfast_.as<float>(), cbi, C, a_.codebook_size, d_cfg_.as<SampleCfg>(),
                                                 d_rng_.as<RngState>(), B, state(0), fast_emb_, d_xfrows_.as<float>(), tok_emb_, cb_emb_,
@@ -2379,7 +2392,7 @@ class LM final : public LMBase {
         drop_batch_graphs();
     }
     hipGraphExec_t batch_graph(int B) {
-        const int key = (sess_active_ ? 1 << 24 : 0) + (rows_par_ ? 1 << 25 : 0) + (sess_active_ && sess_slots_ ? 1 << 26 : 0) + B * 1024 + nc_launch_;
+        const int key = (sess_active_ ? 1 << 24 : 0) + (rows_par_ ? 1 << 25 : 0) + (sess_active_ && sess_slots_ ? 1 << 26 : 0) + (sess_active_ && sess_slots_ && sess_wide_ ? 1 << 27 : 0) + B * 1024 + nc_launch_;
         auto it = batch_graphs_.find(key);
         if (it != batch_graphs_.end()) return it->second;
         {   // the co-residency query of the folded step (rows_fold_ok -> occupancy API) is answered once, OUTSIDE stream capture
@@ -2784,6 +2797,7 @@ class LM final : public LMBase {
     // continuous-batching session: per-slot remaining iterations (-1 = empty), host copy of the slot states, scratch KV page of empty slots
     bool sess_active_ = false, sess_rows_ = false, sess_sampled_ = false;  // sess_rows_: FS_SESSION_ROWS (slots on the request-row kernels)
     bool sess_slots_ = false;  // FS_SESSION_PER_SLOT (slots on the static-batch step with the per-slot samplers)
+    bool sess_wide_ = false;   // FS_SESSION_WIDE_SAMPLER (the per-slot sampler nodes that also take nucleus-only / top_k > 256 settings)
     SampleCfg sess_cfg_ = {};  // the session's own SampleCfg (slots admitted without settings of their own)
     DevBuf d_scfg_, d_srng_, d_srp_mask_, d_srp_seen_, d_srp_ring_, d_srp_meta_;  // per-slot sampler state [max_batch] (k_sample_*_slots)
     int sess_R_ = 0, sess_adds_ = 0, sess_budget_tmp_ = 0;

@@ -246,13 +246,15 @@ struct SampleKernels {
     // are per slot.  Settings per slot: temp == 0, or temp > 0 with 0 < top_k <= 256; n <= 2048, cb_size <= 1024.
     // cfgs[b].legacy (Fish <= 1.4): logits row b = [pad, im_end], the slow token is the 2-way draw of k_sample_slow (one stream word per
     // live frame, greedy included); cap != null: its record [B][cap_frames][9][2048] gets {pad, im_end, u, .., pick at 2047} of decision 0
+    // wide (FS_SESSION_WIDE_SAMPLER): the instantiation whose sampled decisions outside that limit (top_k == 0, top_k > 256, top_k >= the
+    // candidates) run the block-wide general sampler (wide_sample in lm_sample.hip) instead of being excluded; inside it nothing changes
     static void sample_slow_slots(const ModelDims& d, const float* logits, int ld, int n, const SampleCfg* cfgs, SlotRng* rngs, int B,
                                   SeqState* states, const float* X, float* XF, hipStream_t st, const float* prep_g = nullptr,
-                                  uint16_t* prep_A = nullptr, uint32_t* epoch = nullptr, float* cap = nullptr, int cap_frames = 0);
+                                  uint16_t* prep_A = nullptr, uint32_t* epoch = nullptr, float* cap = nullptr, int cap_frames = 0, bool wide = false);
     static void sample_fast_slots(const ModelDims& d, const float* logits, int cb, int n_cb, int cb_size, const SampleCfg* cfgs, SlotRng* rngs,
                                   RepPenState rp, int B, SeqState* states, const void* fast_emb, float* XF, const void* tok_emb,
                                   const void* cb_emb, float* X, uint32_t* out_codes, int out_cap, hipStream_t st,
-                                  const float* prep_g = nullptr, uint16_t* prep_A = nullptr);
+                                  const float* prep_g = nullptr, uint16_t* prep_A = nullptr, bool wide = false);
     // words[b * 16 + call] = the StdRng word of sample() call `call` of this step for row b (child stream of master u64 number (frame * calls + call) * B + b)
     static void rows_rng_words(const RngState* master, int B, int calls_per_frame, const SeqState* states, uint32_t* words, hipStream_t st);
 };
@@ -301,5 +303,7 @@ void launch_fp8_decode_table(float* out, hipStream_t st);
 // test hook behind fs_selftest_sample_rows (include/fishrt.h)
 void debug_sample_rows(int device, const float* logits, int B, int n, double temp, double top_p, uint64_t top_k, uint64_t seed,
                        int call_index, uint32_t* out);
+void debug_sample_slots(int device, const float* logits, int S, int R, int n, const SampleCfg* cfgs, const uint64_t* seeds, uint32_t* out,
+                        uint64_t* words_used);
 
 }  // namespace fs

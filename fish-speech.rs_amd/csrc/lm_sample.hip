@@ -87,7 +87,9 @@ constexpr int SAMPLE_MAXN = 4096;  // candidates handled by the sampler (audio r
 // Block-wide: thread 0 runs the one sequential f32 chain (leaving the running sums in `cum`), then every thread tests its
 // own entries -- the pick is the FIRST non-zero entry whose inclusive running sum exceeds the draw, else the last non-zero
 // entry.  `word` = the StdRng word for this draw (computed off the critical path by a side wave).  All threads must call.
-__device__ int block_weighted_pick(const float* w, int cnt, float* cum, RngState* rng, uint32_t word) {
+// NT = threads of the calling block; *drew (every thread) = 1 iff the draw consumed `word` (WeightedIndex needs a positive total).
+template <int NT>
+__device__ int block_weighted_pick_nt(const float* w, int cnt, float* cum, uint32_t word, int* drew) {
     __shared__ float s_chosen;
     __shared__ int s_first, s_last, s_any;
     const int tid = threadIdx.x;
@@ -98,7 +100,6 @@ __device__ int block_weighted_pick(const float* w, int cnt, float* cum, RngState
             const float max_rand = __uint_as_float((0xFFFFFFFFu >> 9) | (127u << 23)) - 1.0f;
             float scale = total;
             while (scale * max_rand + 0.f >= total) scale = __uint_as_float(__float_as_uint(scale) - 1u);
-            rng->consumed += 1;
             s_chosen = (__uint_as_float((word >> 9) | (127u << 23)) - 1.0f) * scale + 0.f;
         }
         s_first = 0x7FFFFFFF; s_last = -1;
@@ -107,7 +108,7 @@ __device__ int block_weighted_pick(const float* w, int cnt, float* cum, RngState
     if (s_any) {
         const float chosen = s_chosen;
         int first = 0x7FFFFFFF, last = -1;
-        for (int j = tid; j < cnt; j += SAMPLE_THREADS) {
+        for (int j = tid; j < cnt; j += NT) {
             if (w[j] == 0.f) continue;
             last = j;
             if (cum[j] > chosen && first == 0x7FFFFFFF) first = j;
@@ -117,7 +118,14 @@ __device__ int block_weighted_pick(const float* w, int cnt, float* cum, RngState
     }
     __syncthreads();
     const int res = !s_any ? 0 : (s_first != 0x7FFFFFFF ? s_first : s_last);
+    *drew = s_any;
     __syncthreads();
+    return res;
+}
+__device__ int block_weighted_pick(const float* w, int cnt, float* cum, RngState* rng, uint32_t word) {
+    int drew = 0;
+    const int res = block_weighted_pick_nt<SAMPLE_THREADS>(w, cnt, cum, word, &drew);
+    if (threadIdx.x == 0 && drew) rng->consumed += 1;
     return res;
 }
 
@@ -1088,7 +1096,119 @@ __device__ __forceinline__ int slot_greedy_pick(const float (&lv)[EPT], int n, u
     __syncthreads();
     return (int)(*s_key & 0xFFFFFFFFull);
 }
-template <typename WT>
+// ---- the wide decision of a slot block (FS_SESSION_WIDE_SAMPLER): no top-k (top_k == 0 or >= n: nucleus-only) or 256 < top_k < n, over
+// n <= NT * EPT <= 2048 candidates, by the NT threads of the block in bsample's blocked ownership (thread t owns candidates t * EPT ..) and with
+// bsample's contract: `word` = the StdRng word the draw would consume, *consumed = 1 iff it did, the pick on every thread.  The arithmetic is
+// block_sample's general path, operation for operation: lg * inv_t, block max, expf, the f64 denominator narrowed to f32, the division; the
+// order (probability descending, index ascending); seq_sum over the kept probabilities in index order (top-k only; entries outside the
+// top-k weigh +0.0, which moves no f32 sum); seq_topp_cut along the descending order; block_weighted_pick's cumulative chain over all n
+// weights in index order.  Only the sort is organised differently: one 64-bit key {probability bits : ~index} per candidate (probabilities
+// are >= +0, so the bit patterns order like the values, and a larger key sorts FIRST: higher probability, then lower index), every thread
+// taking np2 / (2 NT) compare-exchanges per bitonic stage.  The two chains that do not depend on each other (the index-order sum, the
+// descending top-p walk) run at the same time on lanes of two different waves.
+struct alignas(16) WideLds {  // 32.2 KB
+    unsigned long long key[2048];  // sort keys; [r] = rank r of the descending order once sorted
+    float p[2048];                 // probabilities by index; zeroed outside the top-k and behind the top-p cut: the draw's weights
+    float sp[2048];                // probabilities in descending order; then the draw's cumulative weights
+    double wsum[16];
+    float wmax[16];
+    float sum_p;
+    int cut;
+};
+template <int NT, int EPT>
+__device__ int wide_sample(const float (&lv)[EPT], int n, int top_k, float inv_t, float top_p, uint32_t word, int* consumed, WideLds& W) {
+    static_assert(NT % 64 == 0 && NT >= 128 && NT * EPT <= 2048, "block shape");
+    constexpr int NW = NT / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int base = tid * EPT;
+    // softmax(logits * (1 / temp)), as bsample phase A
+    float v[EPT];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int s = 0; s < EPT; ++s) {
+        v[s] = (base + s < n) ? lv[s] * inv_t : -INFINITY;
+        mx = fmaxf(mx, v[s]);
+    }
+    mx = bs_wave_max(mx);
+    if (lane == 0) W.wmax[wv] = mx;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < NW; ++w) mx = fmaxf(mx, W.wmax[w]);
+    double part = 0.0;
+#pragma unroll
+    for (int s = 0; s < EPT; ++s) {
+        v[s] = (base + s < n) ? expf(v[s] - mx) : 0.f;
+        part += (double)v[s];
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) part += __shfl_xor(part, m, 64);
+    if (lane == 0) W.wsum[wv] = part;
+    __syncthreads();
+    double dsum = 0.0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) dsum += W.wsum[w];
+    const float denom = (float)dsum;
+    int np2 = 1;
+    while (np2 < n) np2 <<= 1;  // <= NT * EPT (a power of two)
+#pragma unroll
+    for (int s = 0; s < EPT; ++s) {
+        const int i = base + s;
+        if (i < n) {
+            const float pr = v[s] / denom;
+            W.p[i] = pr;
+            W.key[i] = ((unsigned long long)__float_as_uint(pr) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)i);
+        } else if (i < np2) {
+            W.key[i] = 0ull;  // behind every candidate (a candidate's low word is never 0)
+        }
+    }
+    __syncthreads();
+    // bitonic sort, descending: np2 / 2 compare-exchanges per stage, pair q = (i, i | j) with bit j of i clear
+    for (int k = 2; k <= np2; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int q = tid; q < (np2 >> 1); q += NT) {
+                const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1)), ixj = i | j;
+                const unsigned long long a = W.key[i], b = W.key[ixj];
+                const bool up = (i & k) == 0;
+                if ((a > b) != up) { W.key[i] = b; W.key[ixj] = a; }
+            }
+            __syncthreads();
+        }
+    }
+    const bool use_k = top_k > 0 && top_k < n;
+    const int kk = use_k ? top_k : n;
+    for (int r = tid; r < n; r += NT) {
+        const unsigned long long kr = W.key[r];
+        W.sp[r] = __uint_as_float((uint32_t)(kr >> 32));
+        if (r >= kk) W.p[0xFFFFFFFFu - (uint32_t)kr] = 0.f;  // outside the top-k (ties at the boundary: the lower index was kept)
+    }
+    __syncthreads();
+    // the index-order sum of the kept probabilities (top-k only: it decides whether top-p applies at all) and the descending top-p walk
+    if (tid == 0) W.sum_p = use_k ? seq_sum(W.p, n) : 0.f;
+    if (tid == 64) W.cut = seq_topp_cut(W.sp, kk, top_p);
+    __syncthreads();
+    const bool do_topp = !use_k || !(top_p <= 0.f || top_p >= W.sum_p);
+    const int cut = do_topp ? W.cut : kk;
+    if (cut < kk) {  // entries sorting at or after rank `cut` are zeroed: a parallel predicate on the keys
+        const unsigned long long kc = W.key[cut];
+        for (int j = tid; j < n; j += NT) {
+            const unsigned long long kj = ((unsigned long long)__float_as_uint(W.p[j]) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)j);
+            if (kj <= kc) W.p[j] = 0.f;
+        }
+    }
+    __syncthreads();
+    int drew = 0;
+    const int res = block_weighted_pick_nt<NT>(W.p, n, W.sp, word, &drew);
+    *consumed = drew;
+    return res;
+}
+// one sampled (temp > 0) decision of a slot in a wide session: the block-uniform choice between the two samplers
+template <int EPT>
+__device__ __forceinline__ int slot_sample_wide(const float (&lv)[EPT], int n, const SampleCfg& c, uint32_t word, int* used, BSampLds& S, WideLds& W) {
+    const float inv_t = (float)(1.0 / (double)c.temp);
+    if (c.top_k == 0 || c.top_k > BS_MAXK || c.top_k >= n) return wide_sample<PAR_THREADS, EPT>(lv, n, c.top_k, inv_t, c.top_p, word, used, W);
+    return bsample<PAR_THREADS, EPT>(lv, n, c.top_k, inv_t, c.top_p, word, used, S);
+}
+template <typename WT, bool WIDE>
 __global__ __launch_bounds__(SLOT_THREADS) void k_sample_slow_slots(const float* __restrict__ logits, int ld, int n, const SampleCfg* __restrict__ cfgs,
                                                                      SlotRng* __restrict__ rngs, SeqState* __restrict__ states,
                                                                      const float* __restrict__ X, float* __restrict__ XF, int dim, PrepOut po,
@@ -1141,7 +1261,12 @@ __global__ __launch_bounds__(SLOT_THREADS) void k_sample_slow_slots(const float*
             const unsigned long long at = rg->rng.consumed;
             const uint32_t word = slot_word(rg, 0, at);
             int used = 0;
-            idx = bsample<PAR_THREADS, 4>(lv, n, c.top_k, (float)(1.0 / (double)c.temp), c.top_p, word, &used, S);
+            if constexpr (WIDE) {
+                __shared__ WideLds Wd;
+                idx = slot_sample_wide<4>(lv, n, c, word, &used, S, Wd);
+            } else {
+                idx = bsample<PAR_THREADS, 4>(lv, n, c.top_k, (float)(1.0 / (double)c.temp), c.top_p, word, &used, S);
+            }
             if (tid == 0) rg->rng.consumed = at + (unsigned long long)used;
         }
         if (tid == 0) {
@@ -1153,7 +1278,7 @@ __global__ __launch_bounds__(SLOT_THREADS) void k_sample_slow_slots(const float*
     if (po.epoch && b == 0 && tid == 0) po.epoch[0] += 1;
     if (po.g) block_prep_row(XF + (size_t)b * dim, dim, po, b, red4);
 }
-template <typename WT>
+template <typename WT, bool WIDE>
 __global__ __launch_bounds__(SLOT_THREADS) void k_sample_fast_slots(const float* __restrict__ logits, int cb, int n_cb, int cb_size,
                                                                      const SampleCfg* __restrict__ cfgs, SlotRng* __restrict__ rngs, RepPenState rp,
                                                                      SeqState* __restrict__ states, const WT* __restrict__ fast_emb, float* __restrict__ XF,
@@ -1207,7 +1332,12 @@ __global__ __launch_bounds__(SLOT_THREADS) void k_sample_fast_slots(const float*
             const unsigned long long at = rg->rng.consumed;
             const uint32_t word = slot_word(rg, 1 + cb, at);
             int used = 0;
-            code = bsample<PAR_THREADS, 2>(lv, n, c.top_k, (float)(1.0 / (double)c.temp), c.top_p, word, &used, S);
+            if constexpr (WIDE) {
+                __shared__ WideLds Wd;
+                code = slot_sample_wide<2>(lv, n, c, word, &used, S, Wd);
+            } else {
+                code = bsample<PAR_THREADS, 2>(lv, n, c.top_k, (float)(1.0 / (double)c.temp), c.top_p, word, &used, S);
+            }
             if (tid == 0) rg->rng.consumed = at + (unsigned long long)used;
         }
         if (tid == 0) {
@@ -1241,6 +1371,46 @@ __global__ __launch_bounds__(NT) void k_bsample_rows_test(const float* __restric
     int consumed = 0;
     const int idx = bsample<NT, EPT>(lv, n, c.top_k, (float)(1.0 / (double)c.temp), c.top_p, s_word, &consumed, S, /*batch=*/true, c.top_p64);
     if (tid == 0) out[b] = (uint32_t)idx;
+}
+
+// test hook of the per-slot decision of a wide session (fs_selftest_sample_slots): block b is one slot -- its own StdRng stream, its own
+// settings -- making R decisions in order on caller-provided rows; greedy, bsample or wide_sample exactly as k_sample_*_slots<.., true> choose
+template <int EPT>
+__global__ __launch_bounds__(PAR_THREADS) void k_sample_slots_test(const float* __restrict__ logits, int R, int n, const SampleCfg* __restrict__ cfgs,
+                                                                   const unsigned long long* __restrict__ seeds, uint32_t* __restrict__ out,
+                                                                   unsigned long long* __restrict__ words_used) {
+    __shared__ BSampLds S;
+    __shared__ WideLds Wd;
+    __shared__ unsigned long long s_key;
+    __shared__ uint32_t s_rkey[8];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const SampleCfg c = cfgs[b];
+    if (tid == 0) seed_from_u64(seeds[b], s_rkey);
+    __syncthreads();
+    uint32_t key[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) key[i] = s_rkey[i];
+    unsigned long long at = 0ull;
+    for (int r = 0; r < R; ++r) {
+        const float* row = logits + ((size_t)b * R + r) * n;
+        float lv[EPT];
+#pragma unroll
+        for (int s = 0; s < EPT; ++s) { const int i = tid * EPT + s; lv[s] = i < n ? row[i] : 0.f; }
+        int idx;
+        if (c.temp == 0.f) {
+            if (tid == 0) s_key = 0ull;
+            __syncthreads();
+            idx = slot_greedy_pick<EPT>(lv, n, &s_key);
+            __syncthreads();  // (the next decision zeroes s_key)
+        } else {
+            const uint32_t word = chacha12_word(key, at);  // (block-uniform)
+            int used = 0;
+            idx = slot_sample_wide<EPT>(lv, n, c, word, &used, S, Wd);
+            at += (unsigned long long)used;
+        }
+        if (tid == 0) out[(size_t)b * R + r] = (uint32_t)idx;
+    }
+    if (tid == 0) words_used[b] = at;
 }
 
 __global__ void k_reppen_reset(RepPenState rp, int n_cb, int cb_size) {
@@ -1322,23 +1492,32 @@ void SampleKernels<WT>::sample_fast_rows(const ModelDims& d, const float* logits
 template <typename WT>
 void SampleKernels<WT>::sample_slow_slots(const ModelDims& d, const float* logits, int ld, int n, const SampleCfg* cfgs, SlotRng* rngs, int B,
                                           SeqState* states, const float* X, float* XF, hipStream_t st, const float* prep_g, uint16_t* prep_A,
-                                          uint32_t* epoch, float* cap, int cap_frames) {
+                                          uint32_t* epoch, float* cap, int cap_frames, bool wide) {
     FS_REQUIRE(n <= PAR_THREADS * 4 && n <= ld && n >= 2, "audio-range vocabulary outside the per-slot sampler capacity (2 .. 2048)");
     const PrepOut po = prep_out(d, prep_g, prep_A, epoch);
-    hipLaunchKernelGGL((k_sample_slow_slots<KVT<WT>>), dim3(B), dim3(SLOT_THREADS), 0, st, logits, ld, n, cfgs, rngs, states, X, XF, d.dim, po,
-                       cap, cap_frames);
+    if (wide)
+        hipLaunchKernelGGL((k_sample_slow_slots<KVT<WT>, true>), dim3(B), dim3(SLOT_THREADS), 0, st, logits, ld, n, cfgs, rngs, states, X, XF, d.dim, po,
+                           cap, cap_frames);
+    else
+        hipLaunchKernelGGL((k_sample_slow_slots<KVT<WT>, false>), dim3(B), dim3(SLOT_THREADS), 0, st, logits, ld, n, cfgs, rngs, states, X, XF, d.dim, po,
+                           cap, cap_frames);
     FS_LAUNCH_CHECK();
 }
 template <typename WT>
 void SampleKernels<WT>::sample_fast_slots(const ModelDims& d, const float* logits, int cb, int n_cb, int cb_size, const SampleCfg* cfgs,
                                           SlotRng* rngs, RepPenState rp, int B, SeqState* states, const void* fast_emb, float* XF,
                                           const void* tok_emb, const void* cb_emb, float* X, uint32_t* out_codes, int out_cap, hipStream_t st,
-                                          const float* prep_g, uint16_t* prep_A) {
+                                          const float* prep_g, uint16_t* prep_A, bool wide) {
     FS_REQUIRE(cb_size <= PAR_THREADS * 2 && n_cb + 1 <= 16, "codebook larger than the per-slot sampler capacity (1024)");
     const PrepOut po = prep_out(d, prep_g, prep_A, nullptr);
-    hipLaunchKernelGGL((k_sample_fast_slots<KVT<WT>>), dim3(B), dim3(SLOT_THREADS), 0, st, logits, cb, n_cb, cb_size, cfgs, rngs, rp, states,
-                       reinterpret_cast<const KVT<WT>*>(fast_emb), XF, reinterpret_cast<const KVT<WT>*>(tok_emb),
-                       reinterpret_cast<const KVT<WT>*>(cb_emb), X, d.dim, out_codes, out_cap, po);
+    if (wide)
+        hipLaunchKernelGGL((k_sample_fast_slots<KVT<WT>, true>), dim3(B), dim3(SLOT_THREADS), 0, st, logits, cb, n_cb, cb_size, cfgs, rngs, rp, states,
+                           reinterpret_cast<const KVT<WT>*>(fast_emb), XF, reinterpret_cast<const KVT<WT>*>(tok_emb),
+                           reinterpret_cast<const KVT<WT>*>(cb_emb), X, d.dim, out_codes, out_cap, po);
+    else
+        hipLaunchKernelGGL((k_sample_fast_slots<KVT<WT>, false>), dim3(B), dim3(SLOT_THREADS), 0, st, logits, cb, n_cb, cb_size, cfgs, rngs, rp, states,
+                           reinterpret_cast<const KVT<WT>*>(fast_emb), XF, reinterpret_cast<const KVT<WT>*>(tok_emb),
+                           reinterpret_cast<const KVT<WT>*>(cb_emb), X, d.dim, out_codes, out_cap, po);
     FS_LAUNCH_CHECK();
 }
 
@@ -1421,6 +1600,29 @@ void debug_sample_rows(int device, const float* logits, int B, int n, double tem
         for (int b = 0; b < B; ++b) out[b] = hs[b].cur[0];
     }
     (void)hipFree(d_logits); (void)hipFree(d_cfg); (void)hipFree(d_rng); (void)hipFree(d_st);
+}
+
+// ---- per-slot sampler test hook (fs_selftest_sample_slots): S independent slot streams of R decisions each on caller-provided logits
+// f32 [S][R][n]; cfgs[s] / seeds[s] = the slot's settings and StdRng seed; out [S][R] the picks, words_used [S] the stream positions afterwards
+void debug_sample_slots(int device, const float* logits, int S, int R, int n, const SampleCfg* cfgs, const uint64_t* seeds, uint32_t* out,
+                        uint64_t* words_used) {
+    FS_REQUIRE(S >= 1 && R >= 1 && n >= 1 && n <= PAR_THREADS * 4 && (size_t)S * R <= (1u << 20), "bad sampler test shape (n <= 2048)");
+    FS_HIP(hipSetDevice(device));
+    const size_t nl = (size_t)S * R * n;
+    float* d_logits = nullptr; SampleCfg* d_cfg = nullptr; unsigned long long* d_seeds = nullptr; uint32_t* d_out = nullptr; unsigned long long* d_used = nullptr;
+    FS_HIP(hipMalloc(&d_logits, sizeof(float) * nl));
+    FS_HIP(hipMalloc(&d_cfg, sizeof(SampleCfg) * S)); FS_HIP(hipMalloc(&d_seeds, sizeof(unsigned long long) * S));
+    FS_HIP(hipMalloc(&d_out, sizeof(uint32_t) * (size_t)S * R)); FS_HIP(hipMalloc(&d_used, sizeof(unsigned long long) * S));
+    FS_HIP(hipMemcpy(d_logits, logits, sizeof(float) * nl, hipMemcpyHostToDevice));
+    FS_HIP(hipMemcpy(d_cfg, cfgs, sizeof(SampleCfg) * S, hipMemcpyHostToDevice));
+    FS_HIP(hipMemcpy(d_seeds, seeds, sizeof(unsigned long long) * S, hipMemcpyHostToDevice));
+    if (n <= PAR_THREADS * 2) hipLaunchKernelGGL((k_sample_slots_test<2>), dim3(S), dim3(PAR_THREADS), 0, nullptr, d_logits, R, n, d_cfg, d_seeds, d_out, d_used);
+    else hipLaunchKernelGGL((k_sample_slots_test<4>), dim3(S), dim3(PAR_THREADS), 0, nullptr, d_logits, R, n, d_cfg, d_seeds, d_out, d_used);
+    FS_LAUNCH_CHECK();
+    FS_HIP(hipDeviceSynchronize());
+    FS_HIP(hipMemcpy(out, d_out, sizeof(uint32_t) * (size_t)S * R, hipMemcpyDeviceToHost));
+    FS_HIP(hipMemcpy(words_used, d_used, sizeof(unsigned long long) * S, hipMemcpyDeviceToHost));
+    (void)hipFree(d_logits); (void)hipFree(d_cfg); (void)hipFree(d_seeds); (void)hipFree(d_out); (void)hipFree(d_used);
 }
 
 template struct SampleKernels<bf16_t>;

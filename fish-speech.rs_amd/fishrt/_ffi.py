@@ -40,10 +40,10 @@ SYMBOLS = ["fs_last_error", "fs_version", "fs_device_count", "fs_lm_create", "fs
            "fs_comm_all_reduce_f64", "fs_comm_broadcast_weights", "fs_comm_broadcast_prompt_dims", "fs_comm_broadcast_prompts", "fs_comm_all_gather_codes", "fs_lm_session_begin", "fs_lm_session_add", "fs_lm_session_step", "fs_lm_session_poll", "fs_lm_session_release", "fs_lm_session_end",
            "fs_lm_session_prefix_create", "fs_lm_session_prefix_release", "fs_lm_session_add_prefixed", "fs_lm_session_add_ex", "fs_lm_session_add_hidden", "fs_lm_session_poll_hidden", "fs_lm_session_info",
            "fs_codec_create", "fs_codec_destroy", "fs_codec_load_safetensors", "fs_codec_load_synthetic",
-           "fs_codec_decode", "fs_codec_encode", "fs_codec_encode_batch", "fs_codec_sample_rate", "fs_codec_set_precision", "fs_codec_precision", "fs_codec_set_range_check", "fs_codec_range_stats", "fs_codec_stream_begin", "fs_codec_stream_decode", "fs_codec_stream_end", "fs_codec_streams_open", "fs_codec_streams_close", "fs_codec_streams_decode", "fs_codec_streams_decode_ragged", "fs_fp8_quantize_rows", "fs_fp8_decode_table", "fs_selftest", "fs_lm_selftest", "fs_selftest_sample_rows", "fs_lm_debug_capture", "fs_lm_debug_read"]
+           "fs_codec_decode", "fs_codec_encode", "fs_codec_encode_batch", "fs_codec_sample_rate", "fs_codec_set_precision", "fs_codec_precision", "fs_codec_set_range_check", "fs_codec_range_stats", "fs_codec_stream_begin", "fs_codec_stream_decode", "fs_codec_stream_end", "fs_codec_streams_open", "fs_codec_streams_close", "fs_codec_streams_decode", "fs_codec_streams_decode_ragged", "fs_fp8_quantize_rows", "fs_fp8_decode_table", "fs_selftest", "fs_lm_selftest", "fs_selftest_sample_rows", "fs_selftest_sample_slots", "fs_lm_debug_capture", "fs_lm_debug_read"]
 
 # flags of fs_lm_generate* / fs_lm_session_begin (include/fishrt.h)
-FS_GEN_IGNORE_EOS, FS_SESSION_ROWS, FS_SESSION_PER_SLOT = 1, 8, 16
+FS_GEN_IGNORE_EOS, FS_SESSION_ROWS, FS_SESSION_PER_SLOT, FS_SESSION_WIDE_SAMPLER = 1, 8, 16, 32
 
 _lib = None
 

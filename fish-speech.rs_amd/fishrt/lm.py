@@ -213,11 +213,12 @@ class DualARTransformer:
         _ffi.check(_ffi.lib().fs_lm_weights_adopt(self._h))
         return self
 
-    def session(self, temp=0.7, top_p=0.9, top_k=50, seed=42, ignore_eos=False, rows=False, repetition_penalty=1.2, per_slot=False):
+    def session(self, temp=0.7, top_p=0.9, top_k=50, seed=42, ignore_eos=False, rows=False, repetition_penalty=1.2, per_slot=False, wide=False):
         """continuous batching over this handle's max_batch slots (fishrt.h: fs_lm_session_*): `with lm.session(...) as s:`
         per_slot=True: FS_SESSION_PER_SLOT -- every slot samples like its own generate_blocking call (own settings, seed, repetition penalty).
+        wide=True (with per_slot=True): FS_SESSION_WIDE_SAMPLER -- slots may also sample nucleus-only (top_k == 0) or with top_k > 256.
         Fish <= 1.4 token configs (no semantic range) take per_slot=True only; plain and rows sessions raise and say so."""
-        return Session(self, temp, top_p, top_k, seed, ignore_eos, rows, repetition_penalty, per_slot)
+        return Session(self, temp, top_p, top_k, seed, ignore_eos, rows, repetition_penalty, per_slot, wide)
 
     def last_stats(self):
         st = _ffi.GenStats()
@@ -268,19 +269,24 @@ class Session:
 
     SAMPLING_KEYS = ("temp", "top_p", "top_k", "repetition_penalty")
 
-    def __init__(self, lm, temp, top_p, top_k, seed, ignore_eos, rows=False, repetition_penalty=1.2, per_slot=False):
+    def __init__(self, lm, temp, top_p, top_k, seed, ignore_eos, rows=False, repetition_penalty=1.2, per_slot=False, wide=False):
         """rows=True: FS_SESSION_ROWS -- the slots run on the request-row persistent kernels with batch-1 semantics (repetition penalty, own
         sampler stream per slot); max_batch <= 8.
         per_slot=True: FS_SESSION_PER_SLOT -- the slots stay on the static-batch step (any max_batch, bf16 / fp8) and every slot samples like
         its own generate_blocking call, with the settings and seed of its add() (default: the session's, seed + admission number).  The
-        only session kind of a Fish <= 1.4 handle: its slow token is the 2-way {pad, im_end} draw, one stream word per frame even when greedy"""
+        only session kind of a Fish <= 1.4 handle: its slow token is the 2-way {pad, im_end} draw, one stream word per frame even when greedy
+        wide=True: FS_SESSION_WIDE_SAMPLER, per_slot sessions only -- the session's and every add()'s settings may be greedy or any
+        temp > 0 with any top_k >= 0 (0 = no top-k) and any top_p; settings inside the 0 < top_k <= 256 limit give the same codes as without it"""
         self.lm, self._open = lm, False
         if rows and per_slot:
             raise ValueError("rows and per_slot exclude each other (a row session's slots already sample per slot)")
-        self.rows, self.per_slot = bool(rows), bool(per_slot)
+        if wide and not per_slot:
+            raise ValueError("wide=True needs per_slot=True (FS_SESSION_WIDE_SAMPLER is valid only together with FS_SESSION_PER_SLOT)")
+        self.rows, self.per_slot, self.wide = bool(rows), bool(per_slot), bool(wide)
         self.sampling = dict(temp=float(temp), top_p=float(top_p), top_k=int(top_k), repetition_penalty=float(repetition_penalty))
         s = _ffi.Sampling(float(temp), float(top_p), int(top_k), float(repetition_penalty) if (rows or per_slot) else 1.0)
         flags = (_ffi.FS_GEN_IGNORE_EOS if ignore_eos else 0) | (_ffi.FS_SESSION_ROWS if rows else 0) | (_ffi.FS_SESSION_PER_SLOT if per_slot else 0)
+        flags |= _ffi.FS_SESSION_WIDE_SAMPLER if wide else 0
         _ffi.check(_ffi.lib().fs_lm_session_begin(lm._h, C.byref(s), C.c_uint64(seed), flags))
         self._open = True
 

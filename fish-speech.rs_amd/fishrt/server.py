@@ -32,6 +32,12 @@ the reference's `GenerateRequest` has none).  They are honoured on the batch-1 p
 any of them never enters a lock-step sampler path -- it runs alone instead -- and a job with a `seed` always runs in the session on a
 `max_batch > 1` handle, alone or not, so that the same request gives the same audio whatever else the server is doing.
 
+Wide sampling (`Scheduler(per_slot_sampling=True, wide_sampling=True)`, off by default).  Per-slot sessions are opened with
+FS_SESSION_WIDE_SAMPLER as well, so a slot may sample nucleus-only (`top_k == 0`, what upstream Fish-Speech does) or with `top_k > 256`:
+such a request joins the per-slot session instead of waiting for it to drain and running alone, and a server whose DEFAULT settings are
+nucleus-only gets a per-slot session at all.  Handles whose sessions take the request-row kernels (2 / 4 / 8 slots, Fish 1.5) keep their
+limit: a job outside it still runs alone.
+
 Hidden states (`generate_hidden_states`, `handlers/send_hidden_states.rs`: body {text, speaker_id, return_audio} -> a stored zip of
 `hidden_states.npy`, optional `audio.wav`, `metadata.json`).  Its chunk jobs go through the same scheduler with `collect_hidden` set: in a
 session the slot is admitted with `add(..., collect_hidden=True)` and read with `poll_hidden`, outside one the job calls
@@ -118,14 +124,16 @@ class LMState:  # server/lib/state.rs:12-21
 
 class AppState:  # server/lib/state.rs:23-29
     def __init__(self, lm_state, codec, sample_rate=44100, opus_encoder=None, preprocess=preprocess_text, batch_window_s=0.002,
-                 continuous=True, auto_batch=False, session_prefixes=False, per_slot_sampling=False):
+                 continuous=True, auto_batch=False, session_prefixes=False, per_slot_sampling=False, wide_sampling=False):
         self.lm, self.codec, self.sample_rate, self.opus_encoder, self.preprocess = lm_state, codec, sample_rate, opus_encoder, preprocess
         self.codec_lock = threading.Lock()  # a codec handle takes one call at a time (include/fishrt.h); requests vocode from their own threads
         self.auto_batch = auto_batch  # True: every chunk may join the batching session (batch sampling semantics) without `batch_size`
         # session_prefixes (off by default): session jobs share their voice's conditioning prefix (Session.add_prefix) instead of prefilling
         # it per chunk.  A prefix prefilled on its own may round differently from the full prompt and flip a near-tie, so it stays opt-in.
         # per_slot_sampling (off by default): per-request sampler semantics in sessions + request-level sampling fields (module docstring)
-        self.scheduler = Scheduler(lm_state, batch_window_s, continuous, session_prefixes=session_prefixes, per_slot_sampling=per_slot_sampling)
+        # wide_sampling (off by default; needs per_slot_sampling): per-slot sessions also take nucleus-only / top_k > 256 settings
+        self.scheduler = Scheduler(lm_state, batch_window_s, continuous, session_prefixes=session_prefixes, per_slot_sampling=per_slot_sampling,
+                                   wide_sampling=wide_sampling)
 
 
 class _Job:
@@ -147,11 +155,15 @@ class Scheduler:
 
     PREFIX_LRU = 8  # conditioning prefixes kept per session (session_prefixes)
 
-    def __init__(self, lm_state, batch_window_s=0.002, continuous=True, step_frames=8, session_prefixes=False, per_slot_sampling=False):
+    def __init__(self, lm_state, batch_window_s=0.002, continuous=True, step_frames=8, session_prefixes=False, per_slot_sampling=False,
+                 wide_sampling=False):
+        if wide_sampling and not per_slot_sampling:
+            raise ValueError("wide_sampling=True needs per_slot_sampling=True (FS_SESSION_WIDE_SAMPLER is a per-slot session flag)")
         self.s, self.q, self.window = lm_state, queue.Queue(), batch_window_s
         self.continuous, self.step_frames = continuous, step_frames
         self.session_prefixes = session_prefixes
         self.per_slot_sampling = per_slot_sampling
+        self.wide_sampling = bool(wide_sampling)
         self.sess_mode = None  # "rows" | "per_slot" | "plain" while a session is open
         self.prefixes = collections.OrderedDict()  # session_prefixes: cond_key -> prefix id of the open session (LRU order)
         self.cached_key = None
@@ -160,6 +172,8 @@ class Scheduler:
             self.stats.update(session_prefix_hits=0, session_prefix_tokens_saved=0)
         if per_slot_sampling:
             self.stats.update(per_slot_sessions=0)
+        if wide_sampling:
+            self.stats.update(wide_sessions=0)
         self._stop = False
         self.th = threading.Thread(target=self._run, daemon=True)
         self.th.start()
@@ -176,14 +190,19 @@ class Scheduler:
     def _session_ok(self, j):
         """may job j join a session?  Jobs without request-level settings: always.  With: only where a slot samples per request
         (per_slot_sampling) and with settings inside the per-slot samplers' limit -- greedy, or temp > 0 with 0 < top_k <= 256; on handles
-        whose sessions take the request-row kernels (2 / 4 / 8 slots) additionally greedy like the server's default or sampled like it."""
+        whose sessions take the request-row kernels (2 / 4 / 8 slots) additionally greedy like the server's default or sampled like it.
+        wide_sampling: in per-slot session mode any temp >= 0 with any top_k >= 0 (the sessions carry FS_SESSION_WIDE_SAMPLER); the
+        row-session handles keep the limit above."""
         if not self._own(j):
             return True
         if not self.per_slot_sampling:
             return False
         sa, d = j.sampling or self.s.default_sampling_args, self.s.default_sampling_args
         if not (sa.temp == 0 or (sa.temp > 0 and 0 < sa.top_k <= 256)):
-            return False
+            if not (self.wide_sampling and sa.temp >= 0 and sa.top_k >= 0):
+                return False
+            if self.sess_mode != "per_slot" and getattr(self.s.lm, "max_batch", 0) in (2, 4, 8) and not self._legacy_tokens():
+                return False  # (a row session's slots stay inside the row kernels' samplers)
         # (a Fish <= 1.4 handle never opens a row session: its sessions are per-slot ones, whatever max_batch is)
         if (getattr(self.s.lm, "max_batch", 0) in (2, 4, 8) and self.sess_mode != "per_slot" and not self._legacy_tokens()
                 and (sa.temp == 0) != (d.temp == 0)):
@@ -305,13 +324,16 @@ class Scheduler:
                                 self.sess_mode = "rows"
                             elif self.per_slot_sampling:
                                 try:
+                                    wide = dict(wide=True) if self.wide_sampling else {}
                                     sess = lm.session(temp=sa.temp, top_p=sa.top_p, top_k=sa.top_k, seed=seed, per_slot=True,
-                                                      repetition_penalty=sa.repetition_penalty)
+                                                      repetition_penalty=sa.repetition_penalty, **wide)
                                 except Exception:  # (no per-slot session on this handle / with these defaults: never the lock-step sampler instead)
                                     j, held = held, None
                                     self._single(j)
                                     continue
                                 self.stats["per_slot_sessions"] += 1
+                                if self.wide_sampling:
+                                    self.stats["wide_sessions"] += 1
                                 self.sess_mode = "per_slot"
                             else:
                                 sess = lm.session(temp=sa.temp, top_p=sa.top_p, top_k=sa.top_k, seed=seed)

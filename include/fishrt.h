@@ -87,6 +87,15 @@ int fs_selftest(int device_id, const char* what);
 int fs_selftest_sample_rows(int device_id, const float* logits, int B, int n, const fs_sampling* s, uint64_t seed, int call_index,
                             uint32_t* out);
 
+/* The per-slot sampler of a FS_SESSION_PER_SLOT | FS_SESSION_WIDE_SAMPLER session on caller-provided logits f32 [S][R][n] (n <= 2048).
+ * Stream s is one slot: its StdRng is seeded seeds[s], its settings are samplings[s] (greedy, or temp > 0 with any top_k / top_p), and it
+ * makes the decisions r = 0 .. R-1 in order on its rows -- no repetition penalty, no EOS masking.  out[s * R + r] = the picked index,
+ * words_used[s] = stream words consumed after the R decisions.  One block per stream runs the device function the wide slot kernels
+ * call; settings inside the narrow limit (0 < top_k <= 256 < n) take the block-parallel sampler, exactly as a slot's would.
+ * Diagnostics / parity tests. */
+int fs_selftest_sample_slots(int device_id, const float* logits, int S, int R, int n, const fs_sampling* samplings, const uint64_t* seeds,
+                             uint32_t* out, uint64_t* words_used);
+
 /* Self-test of a LOADED handle, by name.  "persist": the persistent decode kernels of this binary (csrc/lm_persist.hip, lm_persist_slow.hip:
  * pinned weight registers, loads issued outside the compiler's wait-count bookkeeping) against the per-node kernels on the handle's own
  * weights -- 4 greedy frames on the persistent path with the decision capture armed, then one teacher-forced per-node step
@@ -301,7 +310,23 @@ int fs_comm_all_gather_codes(fs_comm_t* comm, const uint32_t* codes, const int32
  * FS_SESSION_PER_SLOT | FS_SESSION_ROWS is an error.  fs_lm_debug_capture records the head's RAW logits (before the penalty; <|im_end|>
  * masked under FS_GEN_IGNORE_EOS) and the picks of every slot, readable with fs_lm_debug_read_row(slot). */
 #define FS_SESSION_PER_SLOT 16u
-int fs_lm_session_begin(fs_lm_t* lm, const fs_sampling* sampling, uint64_t seed, uint32_t flags /* FS_GEN_IGNORE_EOS | FS_SESSION_ROWS | FS_SESSION_PER_SLOT */);
+/* FS_SESSION_WIDE_SAMPLER: valid only together with FS_SESSION_PER_SLOT (alone, or with FS_SESSION_ROWS, fs_lm_session_begin fails and
+ * says so).  It lifts the sampling limit of a per-slot session: the session's own setting and every fs_lm_session_add_ex /
+ * fs_lm_session_add_hidden setting may be greedy (temp == 0), or ANY temp > 0 with ANY top_k >= 0 and ANY finite top_p -- top_k == 0 (no
+ * top-k: nucleus-only, what upstream Fish-Speech samples with) and top_k > 256 included; temp < 0 or a non-finite temp / top_p is an error
+ * that names the field.  Per decision over n candidates (n = the audio range for the slow token, codebook_size for a codebook) the rule is
+ * LogitsProcessor's (sampling/mod.rs:51-75): top_k == 0 or top_k >= n is nucleus-only (descending stable order, the lower index first on
+ * ties; entries zeroed once the sequential f32 running sum has reached top_p; the WeightedIndex draw over all n weights in index order);
+ * otherwise the top_k largest in ascending index order, their sequential f32 sum, the top-p cut only if 0 < top_p < sum, then the draw.  So
+ * one slot can be top-k on the slow decision and nucleus-only on the codebooks (top_k = 1500 on Fish 1.5: n = 2037 and 1024).  Decisions
+ * with 0 < top_k <= 256 < n and greedy ones run the same code as without the flag and give the same codes, bit for bit; the others run a
+ * block-wide general sampler inside the same sampler nodes (no extra graph nodes, no device memory per slot; tens of microseconds more
+ * per such decision).  Everything else FS_SESSION_PER_SLOT promises holds as written: one StdRng stream per slot with words consumed in
+ * decision order, the repetition-penalty window, the last-max greedy rule, top-p compared in f32, no codebook decisions after <|im_end|>,
+ * the legacy 2-way slow draw on Fish <= 1.4 handles, the capture record; the handle limits stay (<= 2048 slow candidates, codebooks of
+ * <= 1024 entries).  Sessions begun without the flag are unchanged: same kernels, same errors, same codes. */
+#define FS_SESSION_WIDE_SAMPLER 32u
+int fs_lm_session_begin(fs_lm_t* lm, const fs_sampling* sampling, uint64_t seed, uint32_t flags /* FS_GEN_IGNORE_EOS | FS_SESSION_ROWS | FS_SESSION_PER_SLOT | FS_SESSION_WIDE_SAMPLER */);
 /* prompt u32 [C+1, L] row-major (copied); *slot = the slot taken, or -1 when all max_batch slots are busy or the KV page pool cannot hold
  * the request right now (not an error: retry after a release).  Returns once the
  * prefill is enqueued (one prefill in flight: a second add first waits for the previous one); the slot starts generating in a later step */
@@ -329,7 +354,8 @@ int fs_lm_session_add_prefixed(fs_lm_t* lm, int prefix_id, const uint32_t* body,
 /* An add whose slot samples with its own settings and / or sampler seed.  prefix_id < 0: `prompt` u32 [C+1, L] is the whole prompt
  * (== fs_lm_session_add); prefix_id >= 0: it is the body on that prefix (== fs_lm_session_add_prefixed).  sampling NULL: the session's
  * settings; seed NULL: session seed + the slot's admission number.  With both NULL this is exactly the plain call, in every session.
- *   FS_SESSION_PER_SLOT sessions: any settings inside the limit stated there (else an error that names it).
+ *   FS_SESSION_PER_SLOT sessions: any settings inside the limit stated there (else an error that names it); with
+ *     FS_SESSION_WIDE_SAMPLER: greedy, or any temp > 0 with any top_k and any finite top_p.
  *   FS_SESSION_ROWS sessions: the row kernels read one setting and one stream per row already; the slot's settings must stay inside what
  *     fs_lm_rows_supported accepts together with the session's (all greedy or all sampled with 0 < top_k <= 256), else an error.
  *   plain sessions: a non-NULL sampling or seed is an error -- the lock-step sampler has no per-slot notion and keeps its outputs.
