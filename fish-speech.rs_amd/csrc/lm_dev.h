@@ -1,5 +1,6 @@
-// Device helpers shared by the transformer kernels (lm_kernels.hip) and the on-device samplers (lm_sample.hip): weight-type traits,
-// cross-lane reductions, the token embedding, and the fragment-major GEMM-input layout with the one-row RMSNorm + hi/lo split.
+// Device helpers shared by the transformer kernels (lm_kernels.hip), the attention kernels (lm_attn.hip) and the on-device samplers
+// (lm_sample.hip): weight-type traits, cross-lane reductions, the token embedding, row positions, and the fragment-major GEMM-input
+// layout with the one-row RMSNorm + hi/lo split.
 // Device code only; the host-side launch interface is lm_kernels.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -11,6 +12,21 @@ namespace fs {
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));   // MFMA operands / accumulators
+typedef float f32x4v __attribute__((ext_vector_type(4)));
+
+// Everything above this point is ISSUED before anything below it: keeps the machine scheduler from sinking the weight-stream
+// loads under the wait for the small L2-resident vectors (it otherwise serialises x-load -> RMSNorm -> weight request, which
+// costs a full L2 round trip + the norm per kernel node before the first HBM byte is even asked for).
+#define FS_ISSUE_FENCE() __builtin_amdgcn_sched_barrier(0)
+
+__device__ __forceinline__ float bf16_bits_to_f32(uint32_t hi16) { return __uint_as_float(hi16 << 16); }
+
+// position of activation row m: pos_step 1 = consecutive tokens of one sequence (prefill), 0 = every row at state->pos (lock-step static
+// batch), -1 = row m is its own sequence with its own state (session slots, fs_lm_session_*)
+__device__ __forceinline__ int row_pos(const SeqState* __restrict__ state, int m, int pos_step) {
+    return pos_step < 0 ? state[m].pos : state->pos + m * pos_step;
+}
 
 template <typename WT>
 struct WTr;
@@ -119,6 +135,18 @@ __device__ __forceinline__ size_t frag_off(int m, int k, int part, int K) {
     return (((((size_t)p * (K >> 5) + kk) * 2 + part) * 2 + mt) * 64 + (lq * 16 + lr)) * 8 + e;
 }
 
+// elements (m, e .. e + 3), e % 4 == 0, of a fragment-major [rows][K] matrix: hi/lo split of a[0..3], one 8-byte store per part
+__device__ __forceinline__ void store_frag4(bf16_t* A, int m, int e, int K, const float (&a)[4]) {
+    bf16_t hi[4], lo[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) split_bf16(a[i], hi[i], lo[i]);
+    uint2 ph, pl;
+    ph.x = hi[0] | ((uint32_t)hi[1] << 16); ph.y = hi[2] | ((uint32_t)hi[3] << 16);
+    pl.x = lo[0] | ((uint32_t)lo[1] << 16); pl.y = lo[2] | ((uint32_t)lo[3] << 16);
+    *reinterpret_cast<uint2*>(A + frag_off(m, e, 0, K)) = ph;
+    *reinterpret_cast<uint2*>(A + frag_off(m, e, 1, K)) = pl;
+}
+
 // k_prep's RMSNorm + hi/lo split of ONE row by the block that has just written it (the batched samplers: the row is the fast decoder's
 // next input, so its first layer needs no k_prep node in a folded decode step).  Threads 0..255 take one float4 each (D <= 1024) and the sums
 // meet in k_prep's order: the fragments are bit-identical to what the node would have produced.
@@ -136,15 +164,8 @@ __device__ __forceinline__ void block_prep_row(const float* __restrict__ xm, int
     __syncthreads();
     if (!act) return;
     const float d = sqrtf(((red4[0] + red4[1]) + (red4[2] + red4[3])) / (float)D + po.eps);
-    float a[4] = {(v.x / d) * w.x, (v.y / d) * w.y, (v.z / d) * w.z, (v.w / d) * w.w};
-    bf16_t hi[4], lo[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) split_bf16(a[i], hi[i], lo[i]);
-    uint2 ph, pl;
-    ph.x = hi[0] | ((uint32_t)hi[1] << 16); ph.y = hi[2] | ((uint32_t)hi[3] << 16);
-    pl.x = lo[0] | ((uint32_t)lo[1] << 16); pl.y = lo[2] | ((uint32_t)lo[3] << 16);
-    *reinterpret_cast<uint2*>(po.A + frag_off(m, e, 0, D)) = ph;
-    *reinterpret_cast<uint2*>(po.A + frag_off(m, e, 1, D)) = pl;
+    const float a[4] = {(v.x / d) * w.x, (v.y / d) * w.y, (v.z / d) * w.z, (v.w / d) * w.w};
+    store_frag4(po.A, m, e, D, a);
 }
 
 }  // namespace fs

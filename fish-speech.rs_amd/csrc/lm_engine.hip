@@ -500,7 +500,7 @@ class LM final : public LMBase {
             KVView kv = slow_kv(l, 0);
             switch (kind) {
                 case 0: LmKernels<WT>::qkv(d_, x(0), w, d_cos_.as<float>(), d_sin_.as<float>(), state(0), 0, 0, d_q_.as<float>(), kv, st_); break;
-                case 1: LmKernels<WT>::attn_decode(d_, d_q_.as<float>(), kv, state(0), d_part_.as<float>(), n_chunks_, nc_launch_, st_); break;
+                case 1: AttnKernels<WT>::decode(d_, d_q_.as<float>(), kv, state(0), d_part_.as<float>(), n_chunks_, nc_launch_, st_); break;
                 case 2: LmKernels<WT>::wo(d_, d_part_.as<float>(), n_chunks_, nc_launch_, state(0), nullptr, kv, 0, w, x(0), st_); break;
                 case 3: LmKernels<WT>::ffn_up(d_, x(0), w, d_act_.as<float>(), st_); break;
                 default: LmKernels<WT>::ffn_down(d_, d_act_.as<float>(), w, x(0), st_); break;
@@ -2064,9 +2064,9 @@ class LM final : public LMBase {
         FS_HIP(hipMemcpy(d_sin_.p, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
         // paged KV: one pool per slow layer, page = KV_PAGE tokens x Hk heads x Dh
         // (the table covers whole attention chunks: k_attn_decode reads the slot of every launched chunk unconditionally)
-        n_chunks_ = (a_.max_seq_len + LmKernels<WT>::attn_chunk() - 1) / LmKernels<WT>::attn_chunk();
+        n_chunks_ = (a_.max_seq_len + AttnKernels<WT>::chunk() - 1) / AttnKernels<WT>::chunk();
         FS_REQUIRE(n_chunks_ <= 128, "max_seq_len too large for the attention chunking (128 chunks)");
-        max_pages_ = std::max((a_.max_seq_len + KV_PAGE - 1) / KV_PAGE, n_chunks_ * LmKernels<WT>::attn_chunk() / KV_PAGE);
+        max_pages_ = std::max((a_.max_seq_len + KV_PAGE - 1) / KV_PAGE, n_chunks_ * AttnKernels<WT>::chunk() / KV_PAGE);
         n_pages_ = max_pages_ * B_;
         page_elems_ = (size_t)a_.n_local_heads * KV_PAGE * a_.head_dim;
         // pools and partial buffers start zeroed: the attention kernels read rows / chunks past the current length
@@ -2332,7 +2332,11 @@ class LM final : public LMBase {
         else
         SampleKernels<WT>::sample_slow_rows(d_, d_lrows_.as<float>(), ld_slow_, n_audio_, d_cfg_.as<SampleCfg>(), d_rng_.as<RngState>(), B,
                                             C + 1, state(0), cs.X, d_xfrows_.as<float>(), st_, words, prep_g, cs.A, fold ? d_epoch_.as<uint32_t>() : nullptr);
-        for (int cbi = 0; cbi < C; ++cbi) {
+        // the fast decoder's context of codebook pass cbi.  Passes 1..: the first fast layer's q / k / v come from the qkv table (row = the code the
+        // previous pass picked; no k_prep, no Wqkv node) where rows_layer will take it -- ONE predicate decides the table, the sampler's
+        // normalised fragments and first_prepped, so a pass never finds neither the table nor its prepared input
+        const bool qkv0_on = fold && d_qkv0_.p && !getenv("FISHRT_ROWS_NO_QKV0") && a_.codebook_size == 1024;
+        auto fast_ctx = [&](int cbi) {
             RowsCtx cf = cs;
             cf.X = d_xfrows_.as<float>();
             cf.state = d_fast_state_.as<SeqState>() + cbi;
@@ -2340,12 +2344,14 @@ class LM final : public LMBase {
             cf.pt_stride = 1;
             cf.nc_launch = 1;
             cf.small_attn = a_.num_codebooks <= 8;
-            cf.first_prepped = prep_g != nullptr;
             cf.identity_pages = true;  // d_fast_table_[i] == i
             cf.attn_t1 = cbi == 0;     // d_fast_state_[0].pos == 0
-            // passes 1..: the first fast layer's q / k / v come from the qkv table (row = the code the previous pass picked): no Wqkv node
-            const bool tbl = fold && cbi > 0 && d_qkv0_.p && !getenv("FISHRT_ROWS_NO_QKV0") && a_.codebook_size == 1024;
-            if (tbl) { cf.qkv0_tbl = d_qkv0_.as<float>(); cf.row_states = state(0); cf.code_slot = cbi; }
+            if (qkv0_on && AttnKernels<WT>::rows_qkv0_ok(d_, cf)) { cf.qkv0_tbl = d_qkv0_.as<float>(); cf.row_states = state(0); cf.code_slot = cbi; }
+            return cf;
+        };
+        RowsCtx cf = fast_ctx(0);
+        cf.first_prepped = prep_g != nullptr;  // (left by the slow-token sampler)
+        for (int cbi = 0; cbi < C; ++cbi) {
             for (int l = 0; l < a_.n_fast_layer; ++l) {
                 KVView kv;
                 KT* base = fast_pool_.as<KT>() + ((size_t)l * 2 * B_) * page_elems_;
@@ -2357,8 +2363,10 @@ class LM final : public LMBase {
             LmKernels<WT>::rows_head(d_, B, cf, fast_out_w_, kFp8 ? fast_out_s_ : nullptr, a_.codebook_size, d_lfast_.as<float>(), a_.codebook_size, st_, fold);
             if (capt) launch_cap_rows_logits(d_lfast_.as<float>(), a_.codebook_size, a_.codebook_size, state(0), d_cfg_.as<SampleCfg>(), B, d_rcap_.as<float>(),
                                              cap_frames_, 1 + cbi, st_);
-            // (with the qkv table the next pass's first layer needs no normalised GEMM input from this sampler)
-            const float* prep_f = (fold && d_qkv0_.p && !getenv("FISHRT_ROWS_NO_QKV0") && a_.codebook_size == 1024) ? nullptr : prep_g;
+            // the pass that reads this sampler's row: with the qkv table its first layer needs no normalised GEMM input from the sampler
+            RowsCtx nf = fast_ctx(cbi + 1);
+            const float* prep_f = nf.qkv0_tbl ? nullptr : prep_g;
+            nf.first_prepped = prep_f != nullptr;
             if (slots) {
                 RepPenState rp0 = slot_rp(0);
                 SampleKernels<WT>::sample_fast_slots(d_, d_lfast_.as<float>(), cbi, C, a_.codebook_size, d_scfg_.as<SampleCfg>(), d_srng_.as<SlotRng>(), rp0,
@@ -2368,6 +2376,7 @@ class LM final : public LMBase {
             SampleKernels<WT>::sample_fast_rows(d_, d_lfast_.as<float>(), cbi, C, a_.codebook_size, d_cfg_.as<SampleCfg>(),
                                                 d_rng_.as<RngState>(), B, state(0), fast_emb_, d_xfrows_.as<float>(), tok_emb_, cb_emb_,
                                                 cs.X, d_out_.as<uint32_t>(), out_cap_, st_, words, prep_f, cs.A);
+            cf = nf;
         }
         if (capt) launch_cap_rows_picks(state(0), d_cfg_.as<SampleCfg>(), B, d_rcap_.as<float>(), cap_frames_, C, st_);
     }
@@ -2402,8 +2411,6 @@ class LM final : public LMBase {
         }
         hipGraph_t g = nullptr;
         hipGraphExec_t ge = nullptr;
-        // warm every kernel once outside capture (function attributes are set lazily on first launch)
-        if (!batch_warm_) { enqueue_batch_frame_dry(B); batch_warm_ = true; }
         FS_HIP(hipStreamBeginCapture(st_, hipStreamCaptureModeThreadLocal));
         enqueue_batch_frame(B);
         FS_HIP(hipStreamEndCapture(st_, &g));
@@ -2412,9 +2419,6 @@ class LM final : public LMBase {
         batch_graphs_[key] = ge;
         return ge;
     }
-    // hipFuncSetAttribute (dynamic LDS of the GEMM) is not capturable: issue it before the first capture
-    void enqueue_batch_frame_dry(int) { LmKernels<WT>::rows_warmup(); }
-
     RowsCtx rows_ctx(const SeqState* st, int pos_step, int pt_stride) {
         RowsCtx c;
         c.X = d_pfx_.as<float>(); c.Q = d_pfq_.as<float>(); c.part = d_pfpart_.as<float>(); c.P = d_pfslab_.as<float>();
@@ -2443,6 +2447,9 @@ class LM final : public LMBase {
     // ---- persistent fast decoder (lm_persist.hip): per-lane weight image, edge buffers, control words
     void pack_persist() {
         persist_ok_ = false;
+        // the layer-0 qkv table is a function of the weights: it goes with them (every return below that builds none leaves none), and with it
+        // the captured graphs that carry its address
+        if (d_qkv0_.p) { destroy_graphs(); d_qkv0_.free(); }
         if constexpr (std::is_same<WT, bf16_t>::value || std::is_same<WT, fp8_t>::value) {
             constexpr bool FP8 = std::is_same<WT, fp8_t>::value;
             if (getenv("FISHRT_NO_PERSIST")) return;
@@ -2461,7 +2468,7 @@ class LM final : public LMBase {
             launch_fast_persist_pack(fast_.data(), fast_out_w_, d_pack_.p, st_, FP8, fast_out_s_, d_fscl_.as<float>());
             // layer-0 qkv table of the codebook passes 1..7 (lm_persist.hip: 7 of a frame's 137 stages become three loads per lane)
             if (!getenv("FISHRT_FAST_NO_QKV0")) {
-                if (!d_qkv0_.p) d_qkv0_.alloc(fast_persist_qkv0_bytes());
+                d_qkv0_.alloc(fast_persist_qkv0_bytes());
                 launch_fast_persist_qkv0_table(d_pack_.p, FP8 ? d_fscl_.as<float>() : nullptr, fast_[0].attn_norm, fast_emb_, d_.eps, d_qkv0_.as<float>(), st_);
             }
             FS_HIP(hipStreamSynchronize(st_));
@@ -2656,7 +2663,7 @@ class LM final : public LMBase {
             const LayerW& w = slow_[l];
             KVView kv = slow_kv(l, b);
             LmKernels<WT>::qkv(d_, x(b), w, d_cos_.as<float>(), d_sin_.as<float>(), state(b), 0, 0, d_q_.as<float>(), kv, st_);
-            LmKernels<WT>::attn_decode(d_, d_q_.as<float>(), kv, state(b), d_part_.as<float>(), n_chunks_, nc_launch_, st_);
+            AttnKernels<WT>::decode(d_, d_q_.as<float>(), kv, state(b), d_part_.as<float>(), n_chunks_, nc_launch_, st_);
             LmKernels<WT>::wo(d_, d_part_.as<float>(), n_chunks_, nc_launch_, state(b), nullptr, kv, 0, w, x(b), st_);
             LmKernels<WT>::ffn_up(d_, x(b), w, d_act_.as<float>(), st_);
             LmKernels<WT>::ffn_down(d_, d_act_.as<float>(), w, x(b), st_);
@@ -2675,7 +2682,7 @@ class LM final : public LMBase {
 
     // smallest power-of-two chunk count covering KV length T (the host knows every frame's position in advance)
     int chunk_bucket(int T) const {
-        const int need = (T + LmKernels<WT>::attn_chunk() - 1) / LmKernels<WT>::attn_chunk();
+        const int need = (T + AttnKernels<WT>::chunk() - 1) / AttnKernels<WT>::chunk();
         int b = 1;
         while (b < need) b <<= 1;
         return std::min(b, n_chunks_);
@@ -2839,7 +2846,6 @@ class LM final : public LMBase {
     bool rows_par_ = false;  // this batch / session samples with the block-parallel row samplers
     int ld_slow_ = 0, down_split_ = 4;
     bool fold_off_ = false;  // set after a reported exchange timeout of the folded decode step: the handle keeps the slab path from then on
-    bool batch_warm_ = false;
     std::map<int, hipGraphExec_t> batch_graphs_;
     RepPenState rp_ = {};
     DevBuf d_rimg_, d_rhimg_, d_redges_s_, d_redges_f_, d_rctl_s_, d_rctl_f_, d_rlogits_, d_rcfg_, d_rrng_, d_rbudget_;  // request rows (lm_persist_rows.hip)

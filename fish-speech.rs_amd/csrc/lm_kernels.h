@@ -1,4 +1,5 @@
-// Launch interface of the dual-AR decode kernels (lm_kernels.hip) and the on-device samplers (lm_sample.hip).  gfx950 only.
+// Launch interface of the dual-AR decode kernels (lm_kernels.hip), the attention kernels (lm_attn.hip) and the on-device samplers
+// (lm_sample.hip).  gfx950 only.
 //
 // Data layout in HBM:
 //  * weights: row-major [out, in] in WT (bf16, f32, or OCP e4m3fn bytes + one f32 scale per row), one 256-B aligned slab
@@ -115,16 +116,9 @@ struct LmKernels {
     // (state != null: KV index = state->pos, RoPE row = state->pos + state->rope_off; else the two static values)
     static void qkv(const ModelDims& d, const float* x, const LayerW& w, const float* cos_t, const float* sin_t,
                     const SeqState* state, int pos_static, int rope_static, float* q_out, KVView kv, hipStream_t st);
-    // decode attention over the paged cache: un-normalised partial {o[Dh], m, l} per (q head, token chunk);
-    // part: [H][n_chunks_max][Dh + 2]; chunk c covers tokens [c * attn_chunk(), (c + 1) * attn_chunk())
-    static int attn_chunk();
-    // nc_launch: chunks actually launched (>= ceil(T / attn_chunk()) for every T the launch will see; the host knows
-    // the position of every frame, so graphs are captured per power-of-two bucket of nc_launch)
-    static void attn_decode(const ModelDims& d, const float* q, KVView kv, const SeqState* state, float* part,
-                            int n_chunks_max, int nc_launch, hipStream_t st);
     // combine the chunks of state->pos + 1 tokens (or, fused_T > 0: attend over fused_T <= 8 cached tokens in the
     // prologue) -> Wo GEMV -> x += .
-    // nc_launch = the chunk count attn_decode was launched with (ignored when fused_T > 0)
+    // nc_launch = the chunk count AttnKernels::decode was launched with (ignored when fused_T > 0)
     static void wo(const ModelDims& d, const float* part, int n_chunks_max, int nc_launch, const SeqState* state, const float* q,
                    KVView kv, int fused_T, const LayerW& w, float* x, hipStream_t st);
     static void ffn_up(const ModelDims& d, const float* x, const LayerW& w, float* act, hipStream_t st);
@@ -152,12 +146,32 @@ struct LmKernels {
                            const float* next_norm = nullptr);
     static bool rows_fold_ok(const ModelDims& d, int M, const RowsCtx& c);
     static void rows_finish(const ModelDims& d, int M, const RowsCtx& c, const float* norm_w, hipStream_t st);
-    static void rows_warmup();
     static void rows_head(const ModelDims& d, int M, const RowsCtx& c, const void* W, const float* wscale, int n_rows, float* logits, int ld,
                           hipStream_t st, bool rms = false);
     // fast_embeddings gather: out[i] = fast_emb[ids[i]]
     static void fast_embed(const ModelDims& d, const void* fast_emb, const uint32_t* ids, int n, float* out,
                            hipStream_t st);
+};
+
+// ---- attention launchers (lm_attn.hip; all asynchronous on `st`)
+template <typename WT>
+struct AttnKernels {
+    // tokens per attention chunk: chunk c covers tokens [c * chunk(), (c + 1) * chunk())
+    static int chunk();
+    // batch-1 decode over more than 8 chunks: attention blocks take this many consecutive chunks each so that k_wo merges 8 partials
+    // (1: one chunk per block; FISHRT_ATTN_SUPERCHUNK=0 disables: tuning / test hook)
+    static int tiles_per_block(const ModelDims& d, int nc_launch);
+    // decode attention over the paged cache: un-normalised partial {o[Dh], m, l} per (q head, token chunk); part: [H][n_chunks_max][Dh + 2]
+    // nc_launch: chunks actually launched (>= ceil(T / chunk()) for every T the launch will see; the host knows
+    // the position of every frame, so graphs are captured per power-of-two bucket of nc_launch)
+    static void decode(const ModelDims& d, const float* q, KVView kv, const SeqState* state, float* part, int n_chunks_max, int nc_launch,
+                       hipStream_t st);
+    // attention step of LmKernels::rows_layer over M activation rows: c.Q (or, tbl0, row code of c.qkv0_tbl) against each row's KV prefix ->
+    // hi/lo fragments in c.A.  tbl0 is rows_layer's decision (it also drops the layer's k_prep and Wqkv nodes)
+    static void rows(const ModelDims& d, int M, const RowsCtx& c, KVView kv, bool tbl0, hipStream_t st);
+    // may the first layer of a pass with this context take q / k / v from a qkv table (RowsCtx::qkv0_tbl)?  The engine asks before it sets the
+    // table and withholds the sampler's first_prepped fragments; rows_layer asks again before it drops the k_prep and Wqkv nodes
+    static bool rows_qkv0_ok(const ModelDims& d, const RowsCtx& c);
 };
 
 struct SampleCfg {  // device-resident (the captured graphs read it through a pointer, so one graph serves every config)

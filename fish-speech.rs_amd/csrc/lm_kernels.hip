@@ -1,6 +1,6 @@
-// Dual-AR transformer kernels for gfx950 (MI355X): the batch-1 token path (GEMV kernels, flash-decoding attention) first, then
-// the MFMA row path (skinny GEMMs over activation rows, prefill flash attention) used by the prefill and by the static-batch
-// generator.  The on-device samplers are in lm_sample.hip; the device helpers both files use are in lm_dev.h.
+// Dual-AR transformer kernels for gfx950 (MI355X): the batch-1 token path (GEMV kernels) first, then the MFMA row path (skinny
+// GEMMs over activation rows) used by the prefill and by the static-batch generator.  The attention kernels of both paths are in
+// lm_attn.hip, the on-device samplers in lm_sample.hip; the device helpers the three files use are in lm_dev.h.
 //
 // Every kernel here is HBM/latency-bound weight streaming (a 1024x1024 bf16 matrix is 2 MB; one CU can keep
 // ~32 KB in flight), so the design rules are (MI355X guide, "GEMV / M <= 16 decode weights"):
@@ -27,8 +27,6 @@
 namespace fs {
 
 // ------------------------------------------------------------------------------------------------ device helpers
-__device__ __forceinline__ float bf16_bits_to_f32(uint32_t hi16) { return __uint_as_float(hi16 << 16); }
-
 // per-row dequantisation scale (fp8 only; other weight types carry none)
 template <typename WT>
 __device__ __forceinline__ float row_scale(const float* __restrict__ ws, int row) {
@@ -40,11 +38,6 @@ template <typename V>
 __device__ __forceinline__ V ld_stream(const V* p) {  // streamed-once weights: non-temporal (guide: nt-weights)
     return __builtin_nontemporal_load(p);
 }
-
-// Everything above this point is ISSUED before anything below it: keeps the machine scheduler from sinking the weight-stream
-// loads under the wait for the small L2-resident vectors (it otherwise serialises x-load -> RMSNorm -> weight request, which
-// costs a full L2 round trip + the norm per kernel node before the first HBM byte is even asked for).
-#define FS_ISSUE_FENCE() __builtin_amdgcn_sched_barrier(0)
 
 // A wave's view of a length-K vector / weight row: chunk c covers elements [c*64*EPL, (c+1)*64*EPL), lane l owns
 // EPL consecutive elements starting at c*64*EPL + l*EPL.
@@ -163,163 +156,6 @@ __global__ __launch_bounds__(WAVES * 64) void k_qkv(const float* __restrict__ x,
         else { dst[0] = WTr<KT>::from_f32(o0); dst[1] = WTr<KT>::from_f32(o1); }
     } else {
         dst[0] = WTr<KT>::from_f32(a); dst[1] = WTr<KT>::from_f32(b);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ decode attention
-// Flash-decoding over the paged cache.  grid = Hk * n_chunks_max blocks of 4 waves; block (g, c) owns the n_rep query
-// heads of kv head g and the ATTN_CHUNK tokens [c*CH, (c+1)*CH); blocks past the current length exit at once, so the
-// captured graph serves every sequence length.  Each wave stages its TW tokens of K and V (one coalesced 16-B/lane
-// load per KiB, all in flight together) into its private LDS tile, then lane GROUPS of LPT lanes (LPT*16 B = one head
-// row) each own one (query head, token subset): scores by DPP group-sums, a two-pass softmax in registers (no rescale
-// chain), P.V accumulated on the group's own dims -- no cross-group reduction of the output.  The block merges its
-// waves in LDS and writes one un-normalised partial {o[Dh], m, l} per (head, chunk); k_wo combines the chunks.
-// chunk = NW waves x TW tokens (16 waves x 8 tokens was measured too: 4.49 vs 4.36 us, the wider block merge eats the shorter loop)
-template <typename WT, int DH> struct AttnGeom { static constexpr int TW = 16, NW = 8; };                          // bf16: 8 waves x 16 tokens = 128-token chunks
-template <int DH> struct AttnGeom<float, DH> { static constexpr int TW = 16, NW = 4; };                           // f32 :  64-token chunks
-
-// position of activation row m: pos_step 1 = consecutive tokens of one sequence (prefill), 0 = every row at state->pos (lock-step static
-// batch), -1 = row m is its own sequence with its own state (session slots, fs_lm_session_*)
-__device__ __forceinline__ int row_pos(const SeqState* __restrict__ state, int m, int pos_step) {
-    return pos_step < 0 ? state[m].pos : state->pos + m * pos_step;
-}
-
-template <typename WT, int DH, int NREP>
-__global__ __launch_bounds__((AttnGeom<WT, DH>::NW * 64)) void k_attn_decode(const float* __restrict__ q_all, KVView kv,
-                                                     const SeqState* __restrict__ state, float* __restrict__ part_all,
-                                                     int Hk, int n_chunks_max, int nc_launch, int pos_step, int pt_stride, int hsplit) {
-    // hsplit > 1: the query heads of a kv group are spread over hsplit blocks of NREP heads each (the score / P.V work of a wave is
-    // VALU-bound: 16 tokens x 8 heads ~ 900 instructions; the K/V tiles are then read hsplit times, from L2)
-    const int GH = NREP * hsplit;
-    // blockIdx.y = activation row m (0 for the batch-1 decode step): prefill -> token pos + m of one sequence (pos_step 1,
-    // pt_stride 0); batched decode -> sequence m at pos (pos_step 0, pt_stride = page-table stride)
-    kv.page_table += (size_t)blockIdx.y * pt_stride;
-    const float* q = q_all + (size_t)blockIdx.y * Hk * GH * DH;
-    float* part = part_all + (size_t)blockIdx.y * Hk * GH * n_chunks_max * (DH + 2);
-    constexpr int EPL = WTr<WT>::EPL;
-    constexpr int LPT = DH / EPL;            // lanes per head row
-    constexpr int G = 64 / LPT;              // lane groups per wave
-    constexpr int NRP = NREP < G ? NREP : G; // heads served per pass
-    constexpr int NTS = G / NRP;             // token subsets per head
-    constexpr int NHP = NREP / NRP;          // head passes
-    constexpr int TW = AttnGeom<WT, DH>::TW;     // tokens per wave
-    constexpr int NW = AttnGeom<WT, DH>::NW;     // waves per block
-    constexpr int CH = NW * TW;              // tokens per block
-    constexpr int TPG = TW / NTS;            // tokens per group
-    constexpr int NLD = TW * LPT / 64;       // 16-B loads per lane per tile
-    static_assert(TW % NTS == 0 && NLD >= 1, "attention geometry");
-    using vec = typename WTr<WT>::vec;
-    // block id = head part * (Hk * nc_launch) + (kv head * nc_launch + chunk): with Hk * nc_launch a multiple of 8 the blocks that share
-    // a K/V tile get ids congruent mod 8, i.e. the same XCD and L2 (workgroups go round-robin over the 8 XCDs)
-    const int tile = blockIdx.x % (Hk * nc_launch), hb = (int)(blockIdx.x / (Hk * nc_launch)) * NREP;
-    const int g = tile / nc_launch, c = tile % nc_launch;  // nc_launch <= n_chunks_max chunks are launched
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __shared__ __attribute__((aligned(16))) WT sk[NW][TW * DH];
-    __shared__ __attribute__((aligned(16))) WT sv[NW][TW * DH];
-    __shared__ float sp[NW][NREP][NTS][DH + 2];
-    const int t_base = c * CH + wave * TW;
-    // stage K/V tiles: lane l of load i covers token (i*64 + l) / LPT, 16-B slice l % LPT (1 KiB contiguous per load)
-    // all TW tokens of a wave live in ONE page (TW divides KV_PAGE, t_base is TW-aligned): a single wave-uniform
-    // (scalar) page-table read, then 1 KiB-contiguous tile loads.  Neither depends on the current length: the page-table
-    // slot exists for every launched chunk (unassigned slots hold a valid page id) and rows past the length are stale but
-    // in bounds (the pools are zero-initialised, so always finite) -- they are masked below.  The length itself is read
-    // in parallel instead of in front of the chain.
-    static_assert(KV_PAGE % TW == 0, "a wave's tokens must not straddle a KV page");
-    const int t_base_u = __builtin_amdgcn_readfirstlane(t_base);
-    const int page = kv.page_table[t_base_u / KV_PAGE];
-    const WT* kpage = reinterpret_cast<const WT*>(kv.k) + (size_t)(page * Hk + g) * KV_PAGE * DH;
-    const WT* vpage = reinterpret_cast<const WT*>(kv.v) + (size_t)(page * Hk + g) * KV_PAGE * DH;
-    vec kreg[NLD], vreg[NLD];
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-        const int tl = (i * 64 + lane) / LPT, sl = lane % LPT;
-        const int t = t_base + tl;
-        kreg[i] = *reinterpret_cast<const vec*>(kpage + (size_t)(t % KV_PAGE) * DH + sl * EPL);
-        vreg[i] = *reinterpret_cast<const vec*>(vpage + (size_t)(t % KV_PAGE) * DH + sl * EPL);
-    }
-    const int gi = lane / LPT, sub = lane % LPT;
-    const int rl = gi % NRP, ts = gi / NRP;
-    float qr[NHP][EPL];
-#pragma unroll
-    for (int hp = 0; hp < NHP; ++hp) {
-        const float* qp = q + (size_t)(g * GH + hb + hp * NRP + rl) * DH + sub * EPL;
-#pragma unroll
-        for (int i = 0; i < EPL; ++i) qr[hp][i] = qp[i];
-    }
-    // q . (k^T * scale)  (dual_ar.rs:260).  For head_dim 64 the scale is 2^-3: scaling by a power of two commutes with every
-    // f32 rounding, so folding it into q once is bit-identical to scaling each k element (8 multiplies per token saved).
-    constexpr bool POW2 = (DH == 64 || DH == 16 || DH == 256);
-    if (POW2) {
-        const float s0 = 1.0f / sqrtf((float)DH);
-#pragma unroll
-        for (int hp = 0; hp < NHP; ++hp)
-#pragma unroll
-            for (int i = 0; i < EPL; ++i) qr[hp][i] *= s0;
-    }
-    FS_ISSUE_FENCE();
-    const int T = row_pos(state, (int)blockIdx.y, pos_step) + 1;  // the row's own K/V were appended by the qkv stage
-    if (c * CH >= T) return;
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-        *reinterpret_cast<vec*>(&sk[wave][(size_t)(i * 64 + lane) * EPL]) = kreg[i];
-        *reinterpret_cast<vec*>(&sv[wave][(size_t)(i * 64 + lane) * EPL]) = vreg[i];
-    }
-    // (each wave reads only the tile it wrote: no block barrier needed, the compiler orders the LDS accesses)
-    const float scale = 1.0f / sqrtf((float)DH);
-#pragma unroll
-    for (int hp = 0; hp < NHP; ++hp) {
-        float sc[TPG];
-        float m = -1e30f;
-#pragma unroll
-        for (int j = 0; j < TPG; ++j) {
-            const int tl = ts + j * NTS;
-            float kf[EPL];
-            WTr<WT>::unpack(*reinterpret_cast<const vec*>(&sk[wave][(size_t)tl * DH + sub * EPL]), kf);
-            float a = 0.f;
-#pragma unroll
-            for (int i = 0; i < EPL; ++i) a = POW2 ? fmaf(qr[hp][i], kf[i], a) : fmaf(qr[hp][i], kf[i] * scale, a);
-            a = group_sum<LPT>(a);
-            sc[j] = (t_base + tl < T) ? a : -1e30f;
-            m = fmaxf(m, sc[j]);
-        }
-        float l = 0.f, o[EPL];
-#pragma unroll
-        for (int i = 0; i < EPL; ++i) o[i] = 0.f;
-#pragma unroll
-        for (int j = 0; j < TPG; ++j) {
-            const int tl = ts + j * NTS;
-            const float p = (t_base + tl < T) ? __expf(sc[j] - m) : 0.f;
-            l += p;
-            float vf[EPL];
-            WTr<WT>::unpack(*reinterpret_cast<const vec*>(&sv[wave][(size_t)tl * DH + sub * EPL]), vf);
-#pragma unroll
-            for (int i = 0; i < EPL; ++i) o[i] = fmaf(p, vf[i], o[i]);
-        }
-        float* dst = sp[wave][hp * NRP + rl][ts];
-#pragma unroll
-        for (int i = 0; i < EPL; ++i) dst[sub * EPL + i] = o[i];
-        if (sub == 0) { dst[DH] = m; dst[DH + 1] = l; }
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < NREP * DH; e += NW * 64) {
-        const int r = e / DH, dd = e % DH;
-        float mn = -1e30f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w)
-#pragma unroll
-            for (int k = 0; k < NTS; ++k) mn = fmaxf(mn, sp[w][r][k][DH]);
-        float L = 0.f, O = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w)
-#pragma unroll
-            for (int k = 0; k < NTS; ++k) {
-                const float cf = __expf(sp[w][r][k][DH] - mn);
-                L += sp[w][r][k][DH + 1] * cf;
-                O += sp[w][r][k][dd] * cf;
-            }
-        float* dst = part + ((size_t)(g * GH + hb + r) * n_chunks_max + c) * (DH + 2);
-        dst[dd] = O;
-        if (dd == 0) { dst[DH] = mn; dst[DH + 1] = L; }
     }
 }
 
@@ -691,8 +527,6 @@ __global__ void k_advance(SeqState* state) {
 // f32 accumulation, so the MFMA path agrees with the f32-activation GEMV path far below bf16 resolution (the reference's
 // own CUDA path rounds activations to bf16).  Kernel: k_gemm3 below (A operand = weights straight from global, non-temporal;
 // B operand = fragment-major activations straight from L2; no LDS staging).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 constexpr int PF_M = 32;    // activation rows per pass
 
 // EPI_QKV_SEQ: EPI_QKV for a group prefill pass whose sequences start at different positions -- sequence s of the pass sits at
@@ -756,14 +590,7 @@ __global__ __launch_bounds__(256) void k_prep(float* __restrict__ X, int D, cons
             const float4 w = one ? wkeep : *reinterpret_cast<const float4*>(norm_w + e);
             a[0] = (a[0] / d) * w.x; a[1] = (a[1] / d) * w.y; a[2] = (a[2] / d) * w.z; a[3] = (a[3] / d) * w.w;
         }
-        bf16_t hi[4], lo[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) split_bf16(a[i], hi[i], lo[i]);
-        uint2 ph, pl;
-        ph.x = hi[0] | ((uint32_t)hi[1] << 16); ph.y = hi[2] | ((uint32_t)hi[3] << 16);
-        pl.x = lo[0] | ((uint32_t)lo[1] << 16); pl.y = lo[2] | ((uint32_t)lo[3] << 16);
-        *reinterpret_cast<uint2*>(Ohi + frag_off(m, e, 0, D)) = ph;
-        *reinterpret_cast<uint2*>(Ohi + frag_off(m, e, 1, D)) = pl;
+        store_frag4(Ohi, m, e, D, a);
     }
 }
 
@@ -1261,552 +1088,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm_big(const bf16_t* __restrict__ 
     }
 }
 
-// combine the per-chunk attention partials of M rows -> attn hi/lo bf16 [PF_M][H*DH] (input of the Wo GEMM)
-template <int DH>
-__global__ __launch_bounds__(256) void k_attn_combine(const float* __restrict__ part_all, int n_chunks_max, int chunk,
-                                                      const SeqState* __restrict__ state, int pos_step, bf16_t* __restrict__ Ohi, int H) {
-    const int m = blockIdx.x;
-    const int T = row_pos(state, m, pos_step) + 1, nc = (T + chunk - 1) / chunk;
-    const float* part = part_all + (size_t)m * H * n_chunks_max * (DH + 2);
-    __shared__ float wl[32 * 128];
-    for (int h = threadIdx.x; h < H; h += 256) {
-        const float* p = part + (size_t)h * n_chunks_max * (DH + 2);
-        float mn = -1e30f;
-        for (int c = 0; c < nc; ++c) mn = fmaxf(mn, p[c * (DH + 2) + DH]);
-        float L = 0.f;
-        for (int c = 0; c < nc; ++c) L += p[c * (DH + 2) + DH + 1] * __expf(p[c * (DH + 2) + DH] - mn);
-        const float inv = 1.f / L;
-        for (int c = 0; c < nc; ++c) wl[h * 128 + c] = __expf(p[c * (DH + 2) + DH] - mn) * inv;
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < H * DH; e += 256) {
-        const int h = e / DH, dd = e % DH;
-        const float* p = part + (size_t)h * n_chunks_max * (DH + 2) + dd;
-        float O = 0.f;
-        for (int c = 0; c < nc; ++c) O = fmaf(wl[h * 128 + c], p[c * (DH + 2)], O);
-        bf16_t hi, lo;
-        split_bf16(O, hi, lo);
-        Ohi[frag_off(m, e, 0, H * DH)] = hi;
-        Ohi[frag_off(m, e, 1, H * DH)] = lo;
-    }
-}
-
-// Whole attention of one activation row over <= 8 cached tokens (the fast decoder in the batched row path): all H heads in one
-// block, scores by two threads per (head, token), softmax . V with four output dims per thread, result straight into the
-// fragment-major hi/lo GEMM input -- replaces k_attn_decode + k_attn_combine (two graph nodes) where one 8-token page is all
-// there is.  The row's page is page_table[m * pt_stride] (single page), its length state->pos + 1 + m * pos_step <= 8.
-template <int DH>
-__global__ __launch_bounds__(256) void k_attn_small_rows(const float* __restrict__ q_all, KVView kv, const SeqState* __restrict__ state,
-                                                         int H, int Hk, int pos_step, int pt_stride, bf16_t* __restrict__ Ohi, int identity_pages) {
-    __shared__ float sc[32 * 8];
-    const int m = blockIdx.x, tid = threadIdx.x;
-    // identity_pages: row m's only page IS page m (the batched fast decoder's table) -- one dependent L2 round trip less in a node that is
-    // nothing but a chain of them
-    const int page = identity_pages ? m : kv.page_table[(size_t)m * pt_stride];
-    const int n_rep = H / Hk;
-    const float* q = q_all + (size_t)m * H * DH;
-    const bf16_t* kb = reinterpret_cast<const bf16_t*>(kv.k) + (size_t)page * Hk * KV_PAGE * DH;
-    const bf16_t* vb = reinterpret_cast<const bf16_t*>(kv.v) + (size_t)page * Hk * KV_PAGE * DH;
-    const float scale = 1.0f / sqrtf((float)DH);
-    constexpr int QD = DH / 2;
-    // the V values of this thread's first (head, 4 dims) output item are requested with the K rows, not behind the score barrier (all 8
-    // token slots of the page exist; slots >= T hold stale finite bf16 and are masked by t < T below)
-    uint2 vpre[8];
-    {
-        const int e4 = tid * 4;
-        if (e4 < H * DH) {
-            const int h = e4 / DH, dd = e4 % DH;
-#pragma unroll
-            for (int t = 0; t < 8; ++t) vpre[t] = *reinterpret_cast<const uint2*>(vb + ((size_t)(h / n_rep) * KV_PAGE + t) * DH + dd);
-        }
-    }
-    const int T = row_pos(state, m, pos_step) + 1;
-    for (int e1 = tid >> 1; e1 < H * 8; e1 += 128) {
-        const int h = e1 >> 3, t = e1 & 7, sl = tid & 1;
-        const bf16_t* kp = kb + ((size_t)(h / n_rep) * KV_PAGE + t) * DH + sl * QD;
-        const float* qp = q + h * DH + sl * QD;
-        float acc = 0.f;
-#pragma unroll
-        for (int i = 0; i < QD; i += 8) {
-            float kf[8];
-            WTr<bf16_t>::unpack(*reinterpret_cast<const u32x4*>(kp + i), kf);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc = fmaf(qp[i + j], kf[j] * scale, acc);  // q . (k^T * scale)  (dual_ar.rs:260)
-        }
-        acc += dpp_mov<DPP_XOR1>(acc);
-        if (sl == 0) sc[e1] = acc;
-    }
-    __syncthreads();
-    for (int e4 = tid * 4; e4 < H * DH; e4 += 1024) {
-        const int h = e4 / DH, dd = e4 % DH;
-        const bool firstit = e4 == tid * 4;
-        float mx = -1e30f;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) if (t < T) mx = fmaxf(mx, sc[h * 8 + t]);
-        float L = 0.f, O[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int t = 0; t < 8; ++t)
-            if (t < T) {
-                const float p = __expf(sc[h * 8 + t] - mx);
-                L += p;
-                const uint2 vv = firstit ? vpre[t] : *reinterpret_cast<const uint2*>(vb + ((size_t)(h / n_rep) * KV_PAGE + t) * DH + dd);
-                O[0] = fmaf(p, bf16_bits_to_f32((bf16_t)(vv.x & 0xFFFFu)), O[0]); O[1] = fmaf(p, bf16_bits_to_f32((bf16_t)(vv.x >> 16)), O[1]);
-                O[2] = fmaf(p, bf16_bits_to_f32((bf16_t)(vv.y & 0xFFFFu)), O[2]); O[3] = fmaf(p, bf16_bits_to_f32((bf16_t)(vv.y >> 16)), O[3]);
-            }
-        const float inv = 1.f / L;
-        bf16_t hi[4], lo[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) split_bf16(O[i] * inv, hi[i], lo[i]);
-        uint2 ph, pl;
-        ph.x = hi[0] | ((uint32_t)hi[1] << 16); ph.y = hi[2] | ((uint32_t)hi[3] << 16);
-        pl.x = lo[0] | ((uint32_t)lo[1] << 16); pl.y = lo[2] | ((uint32_t)lo[3] << 16);
-        *reinterpret_cast<uint2*>(Ohi + frag_off(m, e4, 0, H * DH)) = ph;
-        *reinterpret_cast<uint2*>(Ohi + frag_off(m, e4, 1, H * DH)) = pl;
-    }
-}
-
-// k_attn_small_rows for the FIRST fast layer of the codebook passes 1.. (round 6): that layer's input row is fast_embeddings[code] of the code the
-// previous pass's sampler picked (static_batch.rs:236-241 / single_batch.rs:181-183), so attention_norm + Wqkv of it is row `code` of the qkv
-// table the persistent fast decoder builds at load time (lm_persist.hip k_pf_qkv0_table: 1024 x 1280 f32, pre-RoPE).  The node takes q / k / v of
-// the new token from that row instead of from a Wqkv GEMM node in front of it (7 nodes of a step disappear): RoPE at the pass's position, K / V
-// appended to the row's page exactly as the GEMM epilogue would (bf16, EPI_QKV), and the new position's K / V used from LDS in their cached
-// (bf16-rounded) form.  code = row_states[m].cur[code_slot] (written by the sampler node in front of this one).
-template <int DH>
-__global__ __launch_bounds__(256) void k_attn_small_rows_tbl(const float* __restrict__ tbl, const SeqState* __restrict__ row_states, int code_slot, KVView kv,
-                                                             const SeqState* __restrict__ state, int H, int Hk, int pos_step, int pt_stride,
-                                                             const float* __restrict__ cos_t, const float* __restrict__ sin_t, bf16_t* __restrict__ Ohi,
-                                                             int identity_pages) {
-    __shared__ float sc[32 * 8];
-    __shared__ __attribute__((aligned(16))) float qS[32 * DH];
-    __shared__ __attribute__((aligned(16))) float knS[4 * DH], vnS[4 * DH];
-    const int m = blockIdx.x, tid = threadIdx.x;
-    const int page = identity_pages ? m : kv.page_table[(size_t)m * pt_stride];
-    const int n_rep = H / Hk;
-    bf16_t* kb = reinterpret_cast<bf16_t*>(kv.k) + (size_t)page * Hk * KV_PAGE * DH;
-    bf16_t* vb = reinterpret_cast<bf16_t*>(kv.v) + (size_t)page * Hk * KV_PAGE * DH;
-    const float scale = 1.0f / sqrtf((float)DH);
-    constexpr int QD = DH / 2;
-    uint2 vpre[8];  // (as k_attn_small_rows: requested up front; the slot of the new position is stale here and replaced below)
-    {
-        const int e4 = tid * 4;
-        if (e4 < H * DH) {
-            const int h = e4 / DH, dd = e4 % DH;
-#pragma unroll
-            for (int t = 0; t < 8; ++t) vpre[t] = *reinterpret_cast<const uint2*>(vb + ((size_t)(h / n_rep) * KV_PAGE + t) * DH + dd);
-        }
-    }
-    const int pos = row_pos(state, m, pos_step), T = pos + 1;
-    const int rpos = pos + (pos_step < 0 ? state[m].rope_off : state->rope_off);
-    const uint32_t code = row_states[m].cur[code_slot];
-    const int qdim = H * DH, kdim = Hk * DH;
-    const float* row = tbl + (size_t)code * (qdim + 2 * kdim);
-    for (int i = tid; i < (qdim + 2 * kdim) / 2; i += 256) {
-        const int r = 2 * i;
-        const float2 ab = *reinterpret_cast<const float2*>(row + r);
-        if (r < qdim + kdim) {  // rope_i (dual_ar.rs:246-247)
-            const int j = (r % DH) / 2;
-            const float cs = cos_t[(size_t)rpos * QD + j], sn = sin_t[(size_t)rpos * QD + j];
-            const float o0 = ab.x * cs - ab.y * sn, o1 = ab.x * sn + ab.y * cs;
-            if (r < qdim) { qS[r] = o0; qS[r + 1] = o1; }
-            else {
-                const int rk = r - qdim;
-                const bf16_t b0 = WTr<bf16_t>::from_f32(o0), b1 = WTr<bf16_t>::from_f32(o1);
-                *reinterpret_cast<uint32_t*>(kb + ((size_t)(rk / DH) * KV_PAGE + pos) * DH + rk % DH) = b0 | ((uint32_t)b1 << 16);
-                knS[rk] = bf16_bits_to_f32(b0); knS[rk + 1] = bf16_bits_to_f32(b1);
-            }
-        } else {
-            const int rv = r - qdim - kdim;
-            const bf16_t b0 = WTr<bf16_t>::from_f32(ab.x), b1 = WTr<bf16_t>::from_f32(ab.y);
-            *reinterpret_cast<uint32_t*>(vb + ((size_t)(rv / DH) * KV_PAGE + pos) * DH + rv % DH) = b0 | ((uint32_t)b1 << 16);
-            vnS[rv] = bf16_bits_to_f32(b0); vnS[rv + 1] = bf16_bits_to_f32(b1);
-        }
-    }
-    __syncthreads();
-    for (int e1 = tid >> 1; e1 < H * 8; e1 += 128) {
-        const int h = e1 >> 3, t = e1 & 7, sl = tid & 1;
-        const bf16_t* kp = kb + ((size_t)(h / n_rep) * KV_PAGE + t) * DH + sl * QD;
-        const float* kn = knS + (h / n_rep) * DH + sl * QD;
-        const float* qp = qS + h * DH + sl * QD;
-        float acc = 0.f;
-#pragma unroll
-        for (int i = 0; i < QD; i += 8) {
-            float kf[8];
-            WTr<bf16_t>::unpack(*reinterpret_cast<const u32x4*>(kp + i), kf);
-            if (t == pos) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) kf[j] = kn[i + j];
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc = fmaf(qp[i + j], kf[j] * scale, acc);  // q . (k^T * scale)  (dual_ar.rs:260)
-        }
-        acc += dpp_mov<DPP_XOR1>(acc);
-        if (sl == 0) sc[e1] = acc;
-    }
-    __syncthreads();
-    for (int e4 = tid * 4; e4 < H * DH; e4 += 1024) {
-        const int h = e4 / DH, dd = e4 % DH;
-        const bool firstit = e4 == tid * 4;
-        float mx = -1e30f;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) if (t < T) mx = fmaxf(mx, sc[h * 8 + t]);
-        float L = 0.f, O[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int t = 0; t < 8; ++t)
-            if (t < T) {
-                const float p = __expf(sc[h * 8 + t] - mx);
-                L += p;
-                if (t == pos) {
-                    const float* vn = vnS + (h / n_rep) * DH + dd;
-                    O[0] = fmaf(p, vn[0], O[0]); O[1] = fmaf(p, vn[1], O[1]); O[2] = fmaf(p, vn[2], O[2]); O[3] = fmaf(p, vn[3], O[3]);
-                } else {
-                    const uint2 vv = firstit ? vpre[t] : *reinterpret_cast<const uint2*>(vb + ((size_t)(h / n_rep) * KV_PAGE + t) * DH + dd);
-                    O[0] = fmaf(p, bf16_bits_to_f32((bf16_t)(vv.x & 0xFFFFu)), O[0]); O[1] = fmaf(p, bf16_bits_to_f32((bf16_t)(vv.x >> 16)), O[1]);
-                    O[2] = fmaf(p, bf16_bits_to_f32((bf16_t)(vv.y & 0xFFFFu)), O[2]); O[3] = fmaf(p, bf16_bits_to_f32((bf16_t)(vv.y >> 16)), O[3]);
-                }
-            }
-        const float inv = 1.f / L;
-        bf16_t hi[4], lo[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) split_bf16(O[i] * inv, hi[i], lo[i]);
-        uint2 ph, pl;
-        ph.x = hi[0] | ((uint32_t)hi[1] << 16); ph.y = hi[2] | ((uint32_t)hi[3] << 16);
-        pl.x = lo[0] | ((uint32_t)lo[1] << 16); pl.y = lo[2] | ((uint32_t)lo[3] << 16);
-        *reinterpret_cast<uint2*>(Ohi + frag_off(m, e4, 0, H * DH)) = ph;
-        *reinterpret_cast<uint2*>(Ohi + frag_off(m, e4, 1, H * DH)) = pl;
-    }
-}
-
-// Static-batch decode attention in ONE node: block = (kv head g, activation row m) walks the row's whole KV prefix chunk by
-// chunk (same wave / lane-group geometry as k_attn_decode; the next chunk's K/V tiles are in flight while the current one is
-// scored), every lane group keeps a running (max, sum, o) (online softmax), the waves meet once in LDS and the normalised result
-// goes straight into the fragment-major hi/lo input of the Wo GEMM -- replaces k_attn_decode over (chunks x rows) blocks +
-// k_attn_combine (two graph nodes and the partials round trip) for the rows-are-sequences passes.
-// PART (batch-1 decode over a LONG prefix, > 8 chunks of 128 tokens): blockIdx.z = super-chunk of `tpb` consecutive chunks; instead
-// of the normalised hi/lo row the block leaves {o, m, l} in slot blockIdx.z of k_attn_decode's partials layout, so that k_wo always
-// merges <= 8 partials in registers (its general LDS merge over 32..64 chunks costs 9..16 us per layer at 4..8 k tokens).
-template <typename WT, int DH, int NREP, bool PART = false>
-__global__ __launch_bounds__((AttnGeom<WT, DH>::NW * 64)) void k_attn_rows(const float* __restrict__ q_all, KVView kv,
-                                                   const SeqState* __restrict__ state, int Hk, int pos_step, int pt_stride,
-                                                   bf16_t* __restrict__ Ohi, int hsplit, float* __restrict__ part_all = nullptr,
-                                                   int n_chunks_max = 0, int tpb = 1 << 30) {
-    // hsplit > 1: the query heads of a kv group are spread over hsplit blocks of NREP heads each (small batches: more blocks,
-    // less VALU work per wave; the K/V tiles are then read hsplit times, from L2)
-    int g = blockIdx.x / hsplit, hb = (blockIdx.x % hsplit) * NREP, mrow = blockIdx.y;
-    if (!PART && hsplit > 1) {
-        // XCD-aware placement: workgroups go round-robin over the 8 XCDs by linear id, and each XCD has its own L2 -- the hsplit blocks
-        // that share one (kv head, row) K/V stream must land on ONE XCD or the stream crosses the fabric hsplit times (PMC at B = 32:
-        // 711 MB per step for 162 MB of K/V with the plain mapping)
-        const int total = gridDim.x * gridDim.y, per_xcd = total / (8 * hsplit);
-        if (per_xcd * 8 * hsplit == total) {
-            const int lin = blockIdx.x + gridDim.x * blockIdx.y, k = lin >> 3, grp = (lin & 7) * per_xcd + k / hsplit;
-            g = grp % Hk; mrow = grp / Hk; hb = (k % hsplit) * NREP;
-        }
-    }
-    const int GH = NREP * hsplit;  // query heads per kv head
-    kv.page_table += (size_t)mrow * pt_stride;
-    const float* q = q_all + (size_t)mrow * Hk * GH * DH;
-    constexpr int EPL = WTr<WT>::EPL;
-    constexpr int LPT = DH / EPL, G = 64 / LPT, NRP = NREP < G ? NREP : G, NTS = G / NRP, NHP = NREP / NRP;
-    constexpr int TW = AttnGeom<WT, DH>::TW, NW = AttnGeom<WT, DH>::NW, CH = NW * TW, TPG = TW / NTS, NLD = TW * LPT / 64;
-    static_assert(TW % NTS == 0 && NLD >= 1 && KV_PAGE % TW == 0, "attention geometry");
-    using vec = typename WTr<WT>::vec;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __shared__ __attribute__((aligned(16))) WT sk[NW][TW * DH];
-    __shared__ __attribute__((aligned(16))) WT sv[NW][TW * DH];
-    __shared__ float sp[NW][NREP][NTS][DH + 2];
-    const int T = row_pos(state, mrow, pos_step) + 1;  // the row's own K/V were appended by the qkv stage
-    const int nc_all = (T + CH - 1) / CH;
-    const int c0 = PART ? (int)blockIdx.z * tpb : 0, nc = PART ? min(nc_all, c0 + tpb) : nc_all;  // this block's chunks [c0, nc)
-    if (c0 >= nc) return;  // super-chunk past the current length (the graph bucket launches a power of two of them)
-    vec kreg[NLD], vreg[NLD];
-    auto load_tiles = [&](int c) {  // chunk c: this wave's TW tokens live in one page
-        const int t_base = __builtin_amdgcn_readfirstlane(c * CH + wave * TW);
-        const int page = kv.page_table[t_base / KV_PAGE];
-        const WT* kpage = reinterpret_cast<const WT*>(kv.k) + (size_t)(page * Hk + g) * KV_PAGE * DH;
-        const WT* vpage = reinterpret_cast<const WT*>(kv.v) + (size_t)(page * Hk + g) * KV_PAGE * DH;
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            const int tl = (i * 64 + lane) / LPT, sl = lane % LPT;
-            const int t = t_base + tl;
-            kreg[i] = *reinterpret_cast<const vec*>(kpage + (size_t)(t % KV_PAGE) * DH + sl * EPL);
-            vreg[i] = *reinterpret_cast<const vec*>(vpage + (size_t)(t % KV_PAGE) * DH + sl * EPL);
-        }
-    };
-    load_tiles(c0);
-    const int gi = lane / LPT, sub = lane % LPT;
-    const int rl = gi % NRP, ts = gi / NRP;
-    constexpr bool POW2 = (DH == 64 || DH == 16 || DH == 256);
-    const float scale = 1.0f / sqrtf((float)DH);
-    float qr[NHP][EPL];
-#pragma unroll
-    for (int hp = 0; hp < NHP; ++hp) {
-        const float* qp = q + (size_t)(g * GH + hb + hp * NRP + rl) * DH + sub * EPL;
-#pragma unroll
-        for (int i = 0; i < EPL; ++i) qr[hp][i] = POW2 ? qp[i] * scale : qp[i];  // 2^-k scale folded into q (exact), see k_attn_decode
-    }
-    float mr[NHP], lr[NHP], orun[NHP][EPL];
-#pragma unroll
-    for (int hp = 0; hp < NHP; ++hp) {
-        mr[hp] = -1e30f; lr[hp] = 0.f;
-#pragma unroll
-        for (int i = 0; i < EPL; ++i) orun[hp][i] = 0.f;
-    }
-    for (int c = c0; c < nc; ++c) {
-        const int t_base = c * CH + wave * TW;
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            *reinterpret_cast<vec*>(&sk[wave][(size_t)(i * 64 + lane) * EPL]) = kreg[i];
-            *reinterpret_cast<vec*>(&sv[wave][(size_t)(i * 64 + lane) * EPL]) = vreg[i];
-        }
-        if (c + 1 < nc) load_tiles(c + 1);
-        // (each wave reads only the tile it wrote: no block barrier, LDS operations of one wave stay in order)
-#pragma unroll
-        for (int hp = 0; hp < NHP; ++hp) {
-            float sc[TPG];
-            float mc = -1e30f;
-#pragma unroll
-            for (int j = 0; j < TPG; ++j) {
-                const int tl = ts + j * NTS;
-                float kf[EPL];
-                WTr<WT>::unpack(*reinterpret_cast<const vec*>(&sk[wave][(size_t)tl * DH + sub * EPL]), kf);
-                float a = 0.f;
-#pragma unroll
-                for (int i = 0; i < EPL; ++i) a = POW2 ? fmaf(qr[hp][i], kf[i], a) : fmaf(qr[hp][i], kf[i] * scale, a);
-                a = group_sum<LPT>(a);
-                sc[j] = (t_base + tl < T) ? a : -1e30f;
-                mc = fmaxf(mc, sc[j]);
-            }
-            const float mn = fmaxf(mr[hp], mc), f = __expf(mr[hp] - mn);
-            float l = lr[hp] * f, o[EPL];
-#pragma unroll
-            for (int i = 0; i < EPL; ++i) o[i] = orun[hp][i] * f;
-#pragma unroll
-            for (int j = 0; j < TPG; ++j) {
-                const int tl = ts + j * NTS;
-                const float p = (t_base + tl < T) ? __expf(sc[j] - mn) : 0.f;
-                l += p;
-                float vf[EPL];
-                WTr<WT>::unpack(*reinterpret_cast<const vec*>(&sv[wave][(size_t)tl * DH + sub * EPL]), vf);
-#pragma unroll
-                for (int i = 0; i < EPL; ++i) o[i] = fmaf(p, vf[i], o[i]);
-            }
-            mr[hp] = mn; lr[hp] = l;
-#pragma unroll
-            for (int i = 0; i < EPL; ++i) orun[hp][i] = o[i];
-        }
-    }
-#pragma unroll
-    for (int hp = 0; hp < NHP; ++hp) {
-        float* dst = sp[wave][hp * NRP + rl][ts];
-#pragma unroll
-        for (int i = 0; i < EPL; ++i) dst[sub * EPL + i] = orun[hp][i];
-        if (sub == 0) { dst[DH] = mr[hp]; dst[DH + 1] = lr[hp]; }
-    }
-    __syncthreads();
-    const int H = Hk * GH;
-    for (int e = threadIdx.x; e < NREP * DH; e += NW * 64) {
-        const int r = e / DH, dd = e % DH;
-        float mn = -1e30f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w)
-#pragma unroll
-            for (int k = 0; k < NTS; ++k) mn = fmaxf(mn, sp[w][r][k][DH]);
-        float L = 0.f, O = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w)
-#pragma unroll
-            for (int k = 0; k < NTS; ++k) {
-                const float cf = __expf(sp[w][r][k][DH] - mn);
-                L += sp[w][r][k][DH + 1] * cf;
-                O += sp[w][r][k][dd] * cf;
-            }
-        if (PART) {
-            float* dst = part_all + (((size_t)mrow * H + g * GH + hb + r) * n_chunks_max + blockIdx.z) * (DH + 2);
-            dst[dd] = O;
-            if (dd == 0) { dst[DH] = mn; dst[DH + 1] = L; }
-        } else {
-            bf16_t hi, lo;
-            split_bf16(O / L, hi, lo);
-            const int col = (g * GH + hb + r) * DH + dd;
-            Ohi[frag_off(mrow, col, 0, H * DH)] = hi;
-            Ohi[frag_off(mrow, col, 1, H * DH)] = lo;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ prefill attention (MFMA)
-// Causal flash attention for the rows of a prefill pass (consecutive tokens of ONE sequence, bf16 KV, head_dim 64): block =
-// (query head, 16-row tile); its 4 waves split the sequence page-wise (wave w takes KV pages w, w+4, ...), each producing a
-// local (max, sum, O) with a two-pass softmax over its own pages; one LDS merge, and the normalised result goes straight into
-// the fragment-major hi/lo GEMM input (replaces k_attn_decode over (chunks x rows) blocks + k_attn_combine: 57 + 7 us per
-// layer at 384 rows).  Per page (64 tokens = 4 MFMA token tiles) every operand load is in flight before the first MFMA.
-//   S^T[token][row] = K_tile[16 x 64] . Q^T[64 x 16]   v_mfma_f32_16x16x32_bf16, A = K straight from the paged cache (one 16-B load
-//                                                      per lane per 32 dims), B = the rows' q split bf16 hi + lo (held in VGPRs)
-//   two-pass softmax: pass 1 only takes the column maxima; pass 2 recomputes S, p = exp(s - max) -- the S^T accumulator layout
-//   (lane: row l&15, tokens (l>>4)*4..+3) IS the A-operand layout of the 16x16x16 MFMA, so
-//   O[row][dim] += P[row][16 tokens] . V[16 tokens][dim]   v_mfma_f32_16x16x16_bf16, p split hi + lo, B = V gathered from the
-//                                                      wave's private LDS copy of the tile (token-major -> 4 strided bf16)
-// The softmax scale 2^-3 is folded into q (exact).  Rows >= M and tokens past a row's position are masked.
-typedef short short4v __attribute__((ext_vector_type(4)));
-// blockIdx.y = sequence of a group pass (rows [y * M, (y + 1) * M), page table y * pt_stride further on, first position state->pos +
-// seq_states[y].pos when seq_states is set: members that join on a shared prefix start past it); one sequence: gridDim.y = 1.
-__global__ __launch_bounds__(256) void k_attn_prefill_mfma(const float* __restrict__ q_all, KVView kv, const SeqState* __restrict__ state,
-                                                           int M, int H, int Hk, bf16_t* __restrict__ Ohi, int pt_stride,
-                                                           const SeqState* __restrict__ seq_states) {
-    constexpr int DH = 64, VLD = DH + 8;
-    __shared__ __attribute__((aligned(16))) bf16_t vt[4][KV_PAGE * VLD];
-    __shared__ __attribute__((aligned(16))) float sm_o[4][16][DH + 4];
-    __shared__ float sm_m[4][16], sm_l[4][16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int h = blockIdx.x % H, rt = blockIdx.x / H;  // query head, row tile
-    const int g = h / (H / Hk);
-    const int row0 = rt * 16, pos0 = seq_states ? seq_states[blockIdx.y].pos : state->pos;  // row m of this sequence sits at position pos0 + m
-    const int mbase = (int)blockIdx.y * M;              // first activation row of this sequence
-    const int* ptab = kv.page_table + (size_t)blockIdx.y * pt_stride;
-    const int c16 = lane & 15, q4 = lane >> 4;
-    // B operand of QK^T: q[row0 + c16][h][ks*32 + q4*8 ..+8], scaled, split hi/lo
-    bf16x8 qh[2], ql[2];
-    {
-        const int m = min(row0 + c16, M - 1);
-        const float* qp = q_all + ((size_t)(mbase + m) * H + h) * DH + q4 * 8;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const float4 a = *reinterpret_cast<const float4*>(qp + ks * 32), b = *reinterpret_cast<const float4*>(qp + ks * 32 + 4);
-            const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-            uint32_t hw[4], lw[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                bf16_t h0, l0, h1, l1;
-                split_bf16(v[2 * i] * 0.125f, h0, l0); split_bf16(v[2 * i + 1] * 0.125f, h1, l1);
-                hw[i] = h0 | ((uint32_t)h1 << 16); lw[i] = l0 | ((uint32_t)l1 << 16);
-            }
-            u32x4 hv, lv; hv.x = hw[0]; hv.y = hw[1]; hv.z = hw[2]; hv.w = hw[3]; lv.x = lw[0]; lv.y = lw[1]; lv.z = lw[2]; lv.w = lw[3];
-            qh[ks] = __builtin_bit_cast(bf16x8, hv); ql[ks] = __builtin_bit_cast(bf16x8, lv);
-        }
-    }
-    const int my_pos = pos0 + row0 + c16;                       // last token this lane's row may see
-    const int n_tok = pos0 + min(row0 + 15, M - 1) + 1;           // tokens the tile's LAST row needs
-    const int n_groups = (n_tok + KV_PAGE - 1) / KV_PAGE;         // one group = one KV page = 4 token tiles of 16
-    const bf16_t* kpool = reinterpret_cast<const bf16_t*>(kv.k);
-    const bf16_t* vpool = reinterpret_cast<const bf16_t*>(kv.v);
-    // S^T of the 4 token tiles of page `grp`: all 8 K loads (A operands, straight from the cache) are in flight together
-    auto scores = [&](int grp, f32x4v (&sacc)[4]) {
-        const int page = ptab[grp];
-        const bf16_t* kp = kpool + ((size_t)(page * Hk + g) * KV_PAGE + c16) * DH + q4 * 8;
-        u32x4 k0[4], k1[4];
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) {
-            k0[tt] = *reinterpret_cast<const u32x4*>(kp + (size_t)tt * 16 * DH);
-            k1[tt] = *reinterpret_cast<const u32x4*>(kp + (size_t)tt * 16 * DH + 32);
-        }
-        FS_ISSUE_FENCE();
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) {
-            f32x4v a = f32x4v{0.f, 0.f, 0.f, 0.f};
-            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, k0[tt]), qh[0], a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, k0[tt]), ql[0], a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, k1[tt]), qh[1], a, 0, 0, 0);
-            a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, k1[tt]), ql[1], a, 0, 0, 0);
-            const int t0 = grp * KV_PAGE + tt * 16;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) if (t0 + q4 * 4 + i > my_pos) a[i] = -1e30f;  // causal mask (also hides stale rows of the page)
-            sacc[tt] = a;
-        }
-    };
-    // pass 1: column maxima
-    float mx = -1e30f;
-    for (int grp = wave; grp < n_groups; grp += 4) {
-        f32x4v s4[4];
-        scores(grp, s4);
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) mx = fmaxf(fmaxf(mx, fmaxf(s4[tt][0], s4[tt][1])), fmaxf(s4[tt][2], s4[tt][3]));
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    // pass 2: P . V
-    f32x4v o[4];
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) o[nt] = f32x4v{0.f, 0.f, 0.f, 0.f};
-    float lsum = 0.f;
-    bf16_t* myv = vt[wave];
-    for (int grp = wave; grp < n_groups; grp += 4) {
-        {   // stage the page's V (64 tokens x 64 dims) token-major into the wave's private LDS region: 8 x 16-B loads per lane
-            const int page = ptab[grp];
-            const bf16_t* vp = vpool + (size_t)(page * Hk + g) * KV_PAGE * DH;
-            u32x4 vr[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) vr[j] = *reinterpret_cast<const u32x4*>(vp + (size_t)(j * 64 + lane) * 8);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int e = j * 64 + lane, tk = e >> 3, d8 = (e & 7) * 8;
-                *reinterpret_cast<u32x4*>(myv + tk * VLD + d8) = vr[j];
-            }
-        }
-        f32x4v s4[4];
-        scores(grp, s4);
-#pragma unroll
-        for (int tt = 0; tt < 4; ++tt) {
-            uint32_t ph[2], pl[2];
-            {
-                bf16_t hb[4], lb[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float p = s4[tt][i] > -1e29f ? __expf(s4[tt][i] - mx) : 0.f;
-                    lsum += p;
-                    split_bf16(p, hb[i], lb[i]);
-                }
-                ph[0] = hb[0] | ((uint32_t)hb[1] << 16); ph[1] = hb[2] | ((uint32_t)hb[3] << 16);
-                pl[0] = lb[0] | ((uint32_t)lb[1] << 16); pl[1] = lb[2] | ((uint32_t)lb[3] << 16);
-            }
-            uint2 phv, plv; phv.x = ph[0]; phv.y = ph[1]; plv.x = pl[0]; plv.y = pl[1];
-            const short4v pa_h = __builtin_bit_cast(short4v, phv), pa_l = __builtin_bit_cast(short4v, plv);
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) {
-                const bf16_t* vq = myv + (tt * 16 + q4 * 4) * VLD + nt * 16 + c16;  // V[token tt*16 + q4*4 + j][dim nt*16 + c16]
-                uint2 bv;
-                bv.x = vq[0] | ((uint32_t)vq[VLD] << 16);
-                bv.y = vq[2 * VLD] | ((uint32_t)vq[3 * VLD] << 16);
-                const short4v vb = __builtin_bit_cast(short4v, bv);
-                o[nt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(pa_h, vb, o[nt], 0, 0, 0);
-                o[nt] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(pa_l, vb, o[nt], 0, 0, 0);
-            }
-        }
-    }
-    lsum += __shfl_xor(lsum, 16, 64);
-    lsum += __shfl_xor(lsum, 32, 64);
-    // merge the 4 page-splits: o[nt][i] = O_w[row q4*4 + i][dim nt*16 + c16]; max / sum live in column layout (row = c16)
-    if (q4 == 0) { sm_m[wave][c16] = mx; sm_l[wave][c16] = lsum; }
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) sm_o[wave][q4 * 4 + i][nt * 16 + c16] = o[nt][i];
-    __syncthreads();
-    {
-        const int r = threadIdx.x >> 4, d4 = (threadIdx.x & 15) * 4, m = row0 + r;
-        if (m < M) {
-            const float mg = fmaxf(fmaxf(sm_m[0][r], sm_m[1][r]), fmaxf(sm_m[2][r], sm_m[3][r]));
-            float L = 0.f, O[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int w2 = 0; w2 < 4; ++w2) {
-                const float cf = __expf(sm_m[w2][r] - mg);  // a split without pages has max -1e30, sum 0, O 0
-                L = fmaf(sm_l[w2][r], cf, L);
-                const float4 ov = *reinterpret_cast<const float4*>(&sm_o[w2][r][d4]);
-                O[0] = fmaf(ov.x, cf, O[0]); O[1] = fmaf(ov.y, cf, O[1]); O[2] = fmaf(ov.z, cf, O[2]); O[3] = fmaf(ov.w, cf, O[3]);
-            }
-            const float inv = 1.f / L;
-            bf16_t hi[4], lo[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) split_bf16(O[i] * inv, hi[i], lo[i]);
-            uint2 phv, plv;
-            phv.x = hi[0] | ((uint32_t)hi[1] << 16); phv.y = hi[2] | ((uint32_t)hi[3] << 16);
-            plv.x = lo[0] | ((uint32_t)lo[1] << 16); plv.y = lo[2] | ((uint32_t)lo[3] << 16);
-            const int e = h * DH + d4;
-            *reinterpret_cast<uint2*>(Ohi + frag_off(mbase + m, e, 0, H * DH)) = phv;
-            *reinterpret_cast<uint2*>(Ohi + frag_off(mbase + m, e, 1, H * DH)) = plv;
-        }
-    }
-}
-
 template <typename WT>
 __global__ void k_embed_rows(const WT* __restrict__ tok_emb, const WT* __restrict__ cb_emb, int dim, int n_cb, int cb_size,
                              const SampleCfg* __restrict__ cfg, const uint32_t* __restrict__ prompt,
@@ -1918,55 +1199,12 @@ void LmKernels<WT>::qkv(const ModelDims& d, const float* x, const LayerW& w, con
 }
 
 template <typename WT>
-int LmKernels<WT>::attn_chunk() { return AttnGeom<KVT<WT>, 64>::NW * AttnGeom<KVT<WT>, 64>::TW; }  // same for every head_dim
-
-// batch-1 decode over more than 8 chunks: attention blocks take `tpb` consecutive chunks each so that k_wo merges 8 partials
-// (FISHRT_ATTN_SUPERCHUNK=0 disables: tuning / test hook)
-template <typename WT>
-static int attn_tiles_per_block(const ModelDims& d, int nc_launch) {
-    static const bool on = [] { const char* e = std::getenv("FISHRT_ATTN_SUPERCHUNK"); return !e || std::atoi(e) != 0; }();
-    if (!on || std::is_same<WT, float>::value || d.Dh != 64 || d.n_rep != 8 || nc_launch <= 8) return 1;
-    return (nc_launch + 7) / 8;
-}
-template <typename WT>
-void LmKernels<WT>::attn_decode(const ModelDims& d, const float* q, KVView kv, const SeqState* state, float* part,
-                                int n_chunks_max, int nc_launch, hipStream_t st) {
-    FS_REQUIRE(nc_launch >= 1 && nc_launch <= n_chunks_max, "bad attention chunk count");
-    const int grid = d.Hk * nc_launch;
-    FS_REQUIRE(n_chunks_max <= 128, "attention supports at most 128 chunks per sequence");
-    static const int hs8 = [] { const char* e = std::getenv("FISHRT_ATTN_HSPLIT"); return e ? std::atoi(e) : 4; }();  // tuning hook: 1, 2 or 4
-    if (const int tpb = attn_tiles_per_block<WT>(d, nc_launch); tpb > 1) {
-        if constexpr (!std::is_same<WT, float>::value)
-            hipLaunchKernelGGL((k_attn_rows<KVT<WT>, 64, 2, true>), dim3(d.Hk * 4, 1, (nc_launch + tpb - 1) / tpb), dim3(AttnGeom<KVT<WT>, 64>::NW * 64), 0,
-                               st, q, kv, state, d.Hk, 0, 0, (bf16_t*)nullptr, 4, part, n_chunks_max, tpb);
-        FS_LAUNCH_CHECK();
-        return;
-    }
-    if (d.Dh == 64 && d.n_rep == 8 && hs8 == 8 && !std::is_same<WT, float>::value)
-        hipLaunchKernelGGL((k_attn_decode<KVT<WT>, 64, 1>), dim3(grid * 8), dim3(AttnGeom<KVT<WT>, 64>::NW * 64), 0, st, q, kv, state, part, d.Hk, n_chunks_max, nc_launch, 0, 0, 8);
-    else if (d.Dh == 64 && d.n_rep == 8 && hs8 == 4 && !std::is_same<WT, float>::value)
-        hipLaunchKernelGGL((k_attn_decode<KVT<WT>, 64, 2>), dim3(grid * 4), dim3(AttnGeom<KVT<WT>, 64>::NW * 64), 0, st, q, kv, state, part, d.Hk, n_chunks_max, nc_launch, 0, 0, 4);
-    else if (d.Dh == 64 && d.n_rep == 8 && hs8 == 2 && !std::is_same<WT, float>::value)
-        hipLaunchKernelGGL((k_attn_decode<KVT<WT>, 64, 4>), dim3(grid * 2), dim3(AttnGeom<KVT<WT>, 64>::NW * 64), 0, st, q, kv, state, part, d.Hk, n_chunks_max, nc_launch, 0, 0, 2);
-    else if (d.Dh == 64 && d.n_rep == 8)
-        hipLaunchKernelGGL((k_attn_decode<KVT<WT>, 64, 8>), dim3(grid), dim3(AttnGeom<KVT<WT>, 64>::NW * 64), 0, st, q, kv, state, part, d.Hk, n_chunks_max, nc_launch, 0, 0, 1);
-    else if (d.Dh == 32 && d.n_rep == 2)
-        hipLaunchKernelGGL((k_attn_decode<KVT<WT>, 32, 2>), dim3(grid), dim3(AttnGeom<KVT<WT>, 32>::NW * 64), 0, st, q, kv, state, part, d.Hk, n_chunks_max, nc_launch, 0, 0, 1);
-    else if (d.Dh == 64 && d.n_rep == 2)
-        hipLaunchKernelGGL((k_attn_decode<KVT<WT>, 64, 2>), dim3(grid), dim3(AttnGeom<KVT<WT>, 64>::NW * 64), 0, st, q, kv, state, part, d.Hk, n_chunks_max, nc_launch, 0, 0, 1);
-    else
-        throw Error("unsupported attention geometry (head_dim, n_rep) = (" + std::to_string(d.Dh) + ", " +
-                    std::to_string(d.n_rep) + ")");
-    FS_LAUNCH_CHECK();
-}
-
-template <typename WT>
 void LmKernels<WT>::wo(const ModelDims& d, const float* part, int n_chunks_max, int nc_launch, const SeqState* state, const float* q,
                        KVView kv, int fused_T, const LayerW& w, float* x, hipStream_t st) {
-    int chunk = attn_chunk();
+    int chunk = AttnKernels<WT>::chunk();
     if (fused_T <= 0) {
         FS_REQUIRE(nc_launch >= 1 && nc_launch <= n_chunks_max, "bad attention chunk count");
-        const int tpb = attn_tiles_per_block<WT>(d, nc_launch);  // attn_decode left one partial per super-chunk
+        const int tpb = AttnKernels<WT>::tiles_per_block(d, nc_launch);  // AttnKernels::decode left one partial per super-chunk
         chunk *= tpb;
         nc_launch = (nc_launch + tpb - 1) / tpb;
     } else nc_launch = 1;
@@ -2242,7 +1480,6 @@ void LmKernels<WT>::rows_layer(const ModelDims& d, int M, const RowsCtx& c, cons
     if constexpr (std::is_same<WT, float>::value) {
         throw Error("the MFMA row path needs bf16 or fp8 weights");
     } else {
-        using KT = KVT<WT>;  // bf16 KV cache for both weight types
         FS_REQUIRE(M >= 1 && M <= c.Mcap, "more activation rows than the row buffers hold");
         FS_REQUIRE(d.dim % 128 == 0 && d.inter % 128 == 0, "row path needs dim % 128 == 0 and intermediate_size % 128 == 0");
         const int qkv_rows = (d.H + 2 * d.Hk) * d.Dh;
@@ -2265,7 +1502,7 @@ void LmKernels<WT>::rows_layer(const ModelDims& d, int M, const RowsCtx& c, cons
         // (1) x += previous layer's down-proj slabs ; RMSNorm(attention_norm) -> hi/lo
         // c.qkv0_tbl (fold, small_attn, first layer of a codebook pass >= 1): q / k / v of the new token are a row of the qkv table -- no k_prep, no Wqkv
         // GEMM; the attention node reads the table itself (k_attn_small_rows_tbl)
-        const bool tbl0 = fold && first && c.qkv0_tbl != nullptr && c.small_attn && !c.attn_t1 && d.Dh == 64 && d.H <= 32 && d.Hk <= 4 && (c.stage_mask & 4u);
+        const bool tbl0 = fold && first && c.qkv0_tbl != nullptr && AttnKernels<WT>::rows_qkv0_ok(d, c);
         if (tbl0) {}
         else if (fold && (!first || c.first_prepped)) {}   // (first_prepped: the sampler that wrote the input row left its normalised fragments in c.A)
         else if (c.stage_mask & 1u) hipLaunchKernelGGL(k_prep, dim3(M), dim3(256), 0, st, c.X, d.dim, c.P, first ? 0 : DOWN_SPLIT, slab, w.attn_norm, d.eps, c.A);
@@ -2287,61 +1524,8 @@ void LmKernels<WT>::rows_layer(const ModelDims& d, int M, const RowsCtx& c, cons
                                       c.cos_t, c.sin_t, c.seq_states, kv, d.H, d.Hk, d.Dh, rm);
         else if (c.stage_mask & 2u) launch_gemm3<EPI_QKV>(qkv_rows, 1, rt_qkv, st, c.A, M, d.dim, w.wqkv, w.s_qkv, c.Q, d.dim, 0, o1, 0,
                               c.cos_t, c.sin_t, c.state, kv, d.H, d.Hk, d.Dh, rm);
-        // (3) attention over each row's KV prefix + chunk combine -> hi/lo
-        if (t1) {}
-        else if (tbl0)
-            hipLaunchKernelGGL((k_attn_small_rows_tbl<64>), dim3(M), dim3(256), 0, st, c.qkv0_tbl, c.row_states, c.code_slot, kv, c.state, d.H, d.Hk, c.pos_step,
-                               c.pt_stride, c.cos_t, c.sin_t, c.A, (int)c.identity_pages);
-        else if (c.seq_rows > 0) {
-            // group prefill: M = n_seq * seq_rows rows, sequence s starts at state->pos (or c.seq_states[s].pos); flash attention per sequence
-            FS_REQUIRE(d.Dh == 64 && M % c.seq_rows == 0 && !c.no_flash, "group prefill needs head_dim 64 and whole sequences");
-            if (c.stage_mask & 4u)
-                hipLaunchKernelGGL(k_attn_prefill_mfma, dim3(d.H * ((c.seq_rows + 15) / 16), M / c.seq_rows), dim3(256), 0, st, c.Q, kv, c.state,
-                                   c.seq_rows, d.H, d.Hk, c.A, c.pt_stride, c.seq_states);
-        } else if (c.pos_step == 1 && c.pt_stride == 0 && (c.stage_mask & 4u) && d.Dh == 64 && M > 1 && !c.no_flash) {
-            // prefill: causal flash attention on the matrix cores, result straight into the Wo GEMM's input
-            hipLaunchKernelGGL(k_attn_prefill_mfma, dim3(d.H * ((M + 15) / 16)), dim3(256), 0, st, c.Q, kv, c.state, M, d.H, d.Hk, c.A, 0,
-                               (const SeqState*)nullptr);
-        } else if (c.small_attn && (c.stage_mask & 4u) && d.H <= 32 && (d.Dh == 64 || d.Dh == 32)) {
-            // fast decoder: <= 8 tokens in one page -> one node instead of two
-            if (d.Dh == 64)
-                hipLaunchKernelGGL((k_attn_small_rows<64>), dim3(M), dim3(256), 0, st, c.Q, kv, c.state, d.H, d.Hk, c.pos_step, c.pt_stride, c.A, (int)c.identity_pages);
-            else
-                hipLaunchKernelGGL((k_attn_small_rows<32>), dim3(M), dim3(256), 0, st, c.Q, kv, c.state, d.H, d.Hk, c.pos_step, c.pt_stride, c.A, (int)c.identity_pages);
-        } else if (c.pos_step <= 0 && !c.chunked_attn && ((d.Dh == 64 && (d.n_rep == 8 || d.n_rep == 2)) || (d.Dh == 32 && d.n_rep == 2))) {
-            // static-batch decode: one fused node per layer (whole KV prefix per (kv head, row) block)
-            // few rows: split the 8 query heads of a kv group over two blocks (64 -> 128 blocks at 32 rows)
-            const int hs = (d.Dh == 64 && d.n_rep == 8) ? (d.Hk * M <= 64 ? 4 : (d.Hk * M < 256 ? 2 : 1)) : 1;
-            const dim3 gr(d.Hk * hs, M);
-            if (!(c.stage_mask & 4u)) {}
-            else if (d.Dh == 64 && d.n_rep == 8 && hs == 4)
-                hipLaunchKernelGGL((k_attn_rows<KT, 64, 2>), gr, dim3(AttnGeom<KT, 64>::NW * 64), 0, st, c.Q, kv, c.state, d.Hk, c.pos_step, c.pt_stride, c.A, 4);
-            else if (d.Dh == 64 && d.n_rep == 8 && hs == 2)
-                hipLaunchKernelGGL((k_attn_rows<KT, 64, 4>), gr, dim3(AttnGeom<KT, 64>::NW * 64), 0, st, c.Q, kv, c.state, d.Hk, c.pos_step, c.pt_stride, c.A, 2);
-            else if (d.Dh == 64 && d.n_rep == 8)
-                hipLaunchKernelGGL((k_attn_rows<KT, 64, 8>), gr, dim3(AttnGeom<KT, 64>::NW * 64), 0, st, c.Q, kv, c.state, d.Hk, c.pos_step, c.pt_stride, c.A, 1);
-            else if (d.Dh == 64)
-                hipLaunchKernelGGL((k_attn_rows<KT, 64, 2>), gr, dim3(AttnGeom<KT, 64>::NW * 64), 0, st, c.Q, kv, c.state, d.Hk, c.pos_step, c.pt_stride, c.A, 1);
-            else
-                hipLaunchKernelGGL((k_attn_rows<KT, 32, 2>), gr, dim3(AttnGeom<KT, 32>::NW * 64), 0, st, c.Q, kv, c.state, d.Hk, c.pos_step, c.pt_stride, c.A, 1);
-        } else {
-        FS_REQUIRE(M <= c.part_rows, "more rows than the attention-partials buffer holds");
-        const dim3 ga(d.Hk * c.nc_launch, M);
-            if (!(c.stage_mask & 4u)) {}
-            else if (d.Dh == 64 && d.n_rep == 8)
-                hipLaunchKernelGGL((k_attn_decode<KT, 64, 8>), ga, dim3(AttnGeom<KT, 64>::NW * 64), 0, st, c.Q, kv, c.state, c.part, d.Hk, c.n_chunks_max, c.nc_launch, c.pos_step, c.pt_stride, 1);
-            else if (d.Dh == 32 && d.n_rep == 2)
-                hipLaunchKernelGGL((k_attn_decode<KT, 32, 2>), ga, dim3(AttnGeom<KT, 32>::NW * 64), 0, st, c.Q, kv, c.state, c.part, d.Hk, c.n_chunks_max, c.nc_launch, c.pos_step, c.pt_stride, 1);
-            else if (d.Dh == 64 && d.n_rep == 2)
-                hipLaunchKernelGGL((k_attn_decode<KT, 64, 2>), ga, dim3(AttnGeom<KT, 64>::NW * 64), 0, st, c.Q, kv, c.state, c.part, d.Hk, c.n_chunks_max, c.nc_launch, c.pos_step, c.pt_stride, 1);
-            else
-                throw Error("unsupported attention geometry");
-            if (!(c.stage_mask & 8u)) {}
-            else if (d.Dh == 64)
-                hipLaunchKernelGGL((k_attn_combine<64>), dim3(M), dim3(256), 0, st, c.part, c.n_chunks_max, attn_chunk(), c.state, c.pos_step, c.A, d.H);
-            else
-                hipLaunchKernelGGL((k_attn_combine<32>), dim3(M), dim3(256), 0, st, c.part, c.n_chunks_max, attn_chunk(), c.state, c.pos_step, c.A, d.H);
-        }
+        // (3) attention over each row's KV prefix (+ chunk combine) -> hi/lo in c.A
+        if (!t1) AttnKernels<WT>::rows(d, M, c, kv, tbl0, st);
         // (4) Wo + residual (each output element owned by one lane: deterministic)
         const bool fuse_norm = c.A2 != nullptr && c.ss != nullptr && nblk_o % 8 == 0 && d.dim % (16 * rt_o) == 0;
         NormAux na{w.ffn_norm, c.ss, c.A2, nblk_o, d.dim, d.eps};
@@ -2368,11 +1552,6 @@ void LmKernels<WT>::rows_layer(const ModelDims& d, int M, const RowsCtx& c, cons
     }
 }
 
-// (kept for API stability: the row kernels need no one-time setup any more)
-template <typename WT>
-void LmKernels<WT>::rows_warmup() {}
-
-// x += last layer's down-proj slabs (closes a rows_layer chain); optionally RMSNorm -> hi/lo for a head GEMM
 template <typename WT>
 void LmKernels<WT>::rows_finish(const ModelDims& d, int M, const RowsCtx& c, const float* norm_w, hipStream_t st) {
     hipLaunchKernelGGL(k_prep, dim3(M), dim3(256), 0, st, c.X, d.dim, c.P, c.down_split, (size_t)c.Mcap * d.dim, norm_w, d.eps,

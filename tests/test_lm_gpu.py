@@ -402,6 +402,41 @@ def test_static_batch_more_rows_than_one_mfma_panel():
     lm.close()
 
 
+@pytest.fixture(scope="module")
+def ofish3():
+    o = orc.OracleLM(dict(orc.FISH15, n_layer=3)).load_synthetic(SEED, bf16=True)
+    o.set_kv_round_bf16(True)
+    return o
+
+
+@pytest.mark.parametrize("B", [33, 40])
+def test_fish_width_static_batch_beyond_32_rows_vs_oracle(B, ofish3):
+    """Fish-1.5 width (16 heads of 64 dims over 2 kv heads, 3 slow layers) with more rows than one MFMA panel: the decode steps take
+    k_attn_rows<bf16, 64, 4> (the 8 query heads of a kv head over two blocks), which no TINY / MID batch reaches.  B = 33: 2 * 2 * 33 = 132
+    blocks, not a multiple of 16 -> the plain block mapping; B = 40: 160 blocks -> the XCD-aware mapping.  Greedy rows vs the oracle's
+    static_batch restatement on the same bf16-rounded weights and K/V, near-tie referee as for the TINY B = 40 test."""
+    lm = fishrt.DualARTransformer(dict(fcfg.FISH_1_5, n_layer=3), fcfg.FISH_1_5_TOKENS, 0, "bf16", B).load_synthetic(SEED)
+    sem = fcfg.FISH_1_5_TOKENS["semantic_start_id"]
+    rng = np.random.RandomState(1500 + B)
+    prompts = []
+    for i in range(B):
+        L = 3 + (7 * i) % 11
+        p = np.zeros((9, L), np.uint32)
+        p[0] = rng.randint(0, 100000, L)
+        if L >= 6:  # a VQ span so that codebook embeddings are exercised
+            codes = rng.randint(0, 1024, (8, 3))
+            p[0, 2:5] = sem + codes[0]
+            p[1:, 2:5] = codes
+        prompts.append(p)
+    M = 13 + 6 - 2  # longest prompt 13 columns -> 6 frames
+    got = lm.generate_static_batch(prompts, M, seed=42, temp=0.0, top_p=1.0, top_k=0, ignore_eos=True)
+    lm.close()
+    exp = ofish3.generate_batch(prompts, M, seed=42, temp=0.0, top_p=1.0, top_k=0, ignore_eos=True)
+    assert [g.shape for g in got] == [e.shape for e in exp] == [(8, 6)] * B
+    flips = _rows_leave_oracle_only_at_near_ties(got, exp, ofish3, f"fish B={B}")
+    print(f"fish B={B}: {B - flips}/{B} rows identical to the oracle over 6 frames, {flips} left it at a near-tie")
+
+
 # head_dim 64 at a small width: the configuration that takes the causal flash-attention prefill kernel and the group prefill of
 # static batches (the TINY config has head_dim 32 and keeps the chunked row attention)
 MID = dict(fcfg.TINY, dim=256, n_head=4, n_local_heads=2, head_dim=64, intermediate_size=1024)

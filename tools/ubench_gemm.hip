@@ -36,7 +36,7 @@ int main(int argc, char** argv) {
     RowsCtx c;
     c.Mcap = 2048; c.part_rows = 512; c.down_split = 4;
     auto dalloc = [&](size_t n) { void* p; CK(hipMalloc(&p, n)); CK(hipMemset(p, 0, n)); return p; };
-    const int NC = 8192 / LmKernels<WT>::attn_chunk();
+    const int NC = 8192 / AttnKernels<WT>::chunk();
     c.X = (float*)dalloc(2048 * 1024 * 4); c.Q = (float*)dalloc(2048 * 1024 * 4); c.part = (float*)dalloc((size_t)512 * 16 * NC * 66 * 4);
     c.P = (float*)dalloc((size_t)4 * 2048 * 1024 * 4); c.A = (uint16_t*)dalloc(2 * 2048 * 1024 * 2);
     c.C = (uint16_t*)dalloc((size_t)2 * 2048 * 4096 * 2); c.A2 = (uint16_t*)dalloc(2 * 2048 * 1024 * 2); c.ss = (float*)dalloc(2048 * 64 * 4);
