@@ -2437,6 +2437,9 @@ class LM final : public LMBase {
     // the same coordinate descent on the in-launch-sampler instantiation of k_fast_persist (680 -> 662 us per sampled frame) and on the
     // e4m3 image of k_slow_persist (595 -> 585 us per fp8 frame): their stage arithmetic differs, so the edges complete at other times
     static constexpr int kNapsFastSampled[6] = {12, 16, 12, 20, 12, 16}, kNapsSlowFp8[6] = {20, 4, 28, 24, 24, 0};  // (round 5 re-tune: profiles/r05_tune_naps.txt)
+    // default stream policy of k_slow_persist per dtype, decided by same-box interleaved A/B (profiles/slow_stream_policy_ab.txt: bf16
+    // 525.2 -> 513.4 us per frame, fp8 531.5 -> 519.7, five interleaved repetitions, identical tokens)
+    static constexpr bool kSlowStreamNt = true, kSlowStreamNtFp8 = true;
     static void set_naps(int (&naps)[6], const char* env, const int (&dflt)[6]) {
         for (int i = 0; i < 6; ++i) naps[i] = dflt[i];
         if (const char* v = getenv(env)) {
@@ -2476,6 +2479,8 @@ class LM final : public LMBase {
             // slow transformer: same geometry, the audio-range head must fit 8 rows per workgroup
             pslow_ok_ = false;
             if (getenv("FISHRT_NO_PERSIST_SLOW") || n_audio_ > 8 * PF_BLOCKS) return;
+            if (const char* c = getenv("FISHRT_SLOW_STREAM"))  // (checked here, outside any capture; pslow_args() reads it)
+                FS_REQUIRE(strcmp(c, "default") == 0 || strcmp(c, "nt") == 0, "FISHRT_SLOW_STREAM must be 'default' or 'nt'");
             if (!d_spack_.p) {
                 d_spack_.alloc(slow_persist_pack_bytes(a_.n_layer, FP8));
                 d_hpack_.alloc((size_t)PF_BLOCKS * PS_HEAD_IMAGE);
@@ -2525,7 +2530,15 @@ class LM final : public LMBase {
         // k_slow_persist early_mode bits.  bit 3 (round 6, bf16 images): an attention workgroup requests its first K/V tile BEHIND S1's publish instead of
         // in front of the Wqkv rows -- the publishing stores used to queue behind the tile's 32 KB of loads in the CU's vector-memory pipeline (S1 work
         // 1.2 -> 0.7 us on those workgroups; 529.3 -> 526.1 us per frame, 614.5 -> 604.6 at 4100 cached tokens; fp8: no difference, left off)
-        A.l2_touch = getenv("FISHRT_SLOW_EARLY") ? atoi(getenv("FISHRT_SLOW_EARLY")) : (kFp8 ? 1 : 9);
+        A.l2_touch = (getenv("FISHRT_SLOW_EARLY") ? atoi(getenv("FISHRT_SLOW_EARLY")) : (kFp8 ? 1 : 9)) & 15;
+        // (bits 0..3 only: bit 4 belongs to the stream policy below, higher bits have no meaning)
+        // The stream policy of the slow kernel's weight images (PS_STREAM_NT: non-temporal loads of the bytes a CU reads once per frame).  Read here, by
+        // the handle that sets up a launch (a graph capture or a direct launch), like the bits above and the naps: two handles of one process can differ,
+        // and an A/B sets it before the handle's first call and leaves it.  FISHRT_SLOW_STREAM=default | nt (anything else is refused when the handle
+        // packs its images, pack_persist()); without it the per-dtype default.
+        bool stream_nt = kFp8 ? kSlowStreamNtFp8 : kSlowStreamNt;
+        if (const char* c = getenv("FISHRT_SLOW_STREAM")) stream_nt = strcmp(c, "nt") == 0;
+        if (stream_nt) A.l2_touch |= PS_STREAM_NT;
         return A;
     }
     // the persistent fast decoder takes the slow-token decision in its prologue (no k_sample_slow node) whenever it runs

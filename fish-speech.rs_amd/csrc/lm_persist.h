@@ -91,8 +91,10 @@ struct SlowPersistArgs {
     uint32_t* ctl;          // [0] epoch, [1] timeouts
     int naps[6];            // 64-clock naps before the first sweep of S1 / S2 / S3 / S4 / S5 / head
     int prof_wg;            // the workgroup whose stage timers go to `prof` (FISHRT_PERSIST_PROF_WG; default 0 = an attention workgroup)
-    int l2_touch;           // 1: workgroups without an attention item request a layer's W13 slice behind S1's publish instead of in S3 (FISHRT_SLOW_NO_EARLY13=1 switches it off)
+    int l2_touch;           // mode bits.  1: workgroups without an attention item request a layer's W13 slice behind S1's publish instead of in S3; 2: W2 as well;
+                            // 4: W13 as MFMA fragments (set by launch_slow_persist); 8: first K/V tile behind S1's publish; PS_STREAM_NT: the stream policy
 };
+constexpr int PS_STREAM_NT = 16;  // SlowPersistArgs::l2_touch bit 4: the once-read weight images are loaded non-temporal (k_slow_persist<., true>)
 size_t slow_persist_pack_bytes(int n_layer, bool fp8 = false);
 size_t slow_persist_scale_floats(int n_layer);
 void launch_slow_persist_pack_fp8(const LayerW* layers, int n_layer, const void* head_w, const float* head_s, int n_head_rows,

@@ -109,8 +109,20 @@ __device__ __forceinline__ void pf_sweep8u(const u64* base, const int (&unit)[8]
 // A 16-byte load the compiler's s_waitcnt bookkeeping does not see: dst is valid after the next sweep (every sweep statement ends in
 // s_waitcnt vmcnt(0)).  Used where the ISSUE POINT of a prefetch depends on the workgroup's role: as ordinary loads in two branches they
 // made every later wait for an older load a vmcnt(0) (the pass cannot count loads of a branch not taken) and cost what the early issue gained.
+// NT: the stream policy of k_slow_persist (below) -- the same request with the nt modifier
+template <bool NT>
 __device__ __forceinline__ void ps_load16_unseen(u32x4& dst, const unsigned char* base, unsigned voff) {
-    asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(voff), "s"(base));
+    if constexpr (NT) asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "=v"(dst) : "v"(voff), "s"(base));
+    else asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst) : "v"(voff), "s"(base));
+}
+// A compiler-visible load of a streamed weight image (Wqkv, Wo, head rows): every byte is read once per frame, by one CU.  NT: non-temporal
+// (as ld_stream of the per-node kernels, lm_kernels.hip), so that the 717 MB stream does not allocate beside what IS re-read -- the edges, the
+// K/V tiles, the norm vectors, the fast decoder's resident image.  Never on the sc1 sweeps / publishes (MI355X: nt on hand-off granules
+// costs every edge), the K/V tiles, A.norms, the rope tables, the page table, A.x, state or ctl.
+template <bool NT, typename V>
+__device__ __forceinline__ V ps_ld_w(const V* p) {
+    if constexpr (NT) return __builtin_nontemporal_load(p);
+    else return *p;
 }
 
 }  // namespace
@@ -207,7 +219,9 @@ __global__ __launch_bounds__(PF_THREADS) void k_ps_pack_head_fp8(const uint16_t*
 __global__ void k_ps_copy_norm(const float* __restrict__ src, float* __restrict__ dst) { dst[blockIdx.x * 256 + threadIdx.x] = src[blockIdx.x * 256 + threadIdx.x]; }
 
 // ------------------------------------------------------------------------------------------------ the step kernel
-template <bool FP8>
+// NT: the cache policy of the weight stream, a template parameter and not a branch on A.l2_touch (compiler-visible loads in two branches turn
+// later waits into vmcnt(0), see ps_load16_unseen); launch_slow_persist picks the instantiation from bit 4 of A.l2_touch
+template <bool FP8, bool NT>
 __global__ __launch_bounds__(PF_THREADS) void k_slow_persist(SlowPersistArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const unsigned long long t_entry = A.prof ? wall_clock64() : 0;  // launch-boundary stamps: see k_fast_persist
@@ -267,13 +281,14 @@ __global__ __launch_bounds__(PF_THREADS) void k_slow_persist(SlowPersistArgs A) 
     u32x4 w13f[4], w2f[2];
     uint32_t wq1;
     if constexpr (FP8) {
-        wq4f = reinterpret_cast<const u32x2*>(wimg + I8_QKV4)[tid];
-        wq1 = reinterpret_cast<const uint32_t*>(wimg + I8_QKV1)[tid];
+        wq4f = ps_ld_w<NT>(reinterpret_cast<const u32x2*>(wimg + I8_QKV4) + tid);
+        wq1 = ps_ld_w<NT>(reinterpret_cast<const uint32_t*>(wimg + I8_QKV1) + tid);
     } else {
-        wq4 = reinterpret_cast<const u32x4*>(wimg + IM_QKV4)[tid];
-        wq1 = reinterpret_cast<const uint32_t*>(wimg + IM_QKV1)[tid];
+        wq4 = ps_ld_w<NT>(reinterpret_cast<const u32x4*>(wimg + IM_QKV4) + tid);
+        wq1 = ps_ld_w<NT>(reinterpret_cast<const uint32_t*>(wimg + IM_QKV1) + tid);
     }
-    // fp8: this workgroup's row scales of the current layer (read by the publishing lanes, requested at the top of each stage)
+    // fp8: this workgroup's row scales of the current layer (read by the publishing lanes, requested at the top of each stage; 1.2 MB per
+    // frame against the 359 MB of the images: they keep the default policy under NT as well)
     const float* scl = FP8 ? A.scales + (size_t)b * PS_SC : nullptr;
     const size_t scl_layer = (size_t)PF_BLOCKS * PS_SC;
     u32x4 kreg[2] = {u32x4{0, 0, 0, 0}, u32x4{0, 0, 0, 0}}, vreg[2] = {u32x4{0, 0, 0, 0}, u32x4{0, 0, 0, 0}};  // zero unless this slice has cached tokens
@@ -300,18 +315,18 @@ __global__ __launch_bounds__(PF_THREADS) void k_slow_persist(SlowPersistArgs A) 
     auto request_w13 = [&](const unsigned char* wl_) {  // the W13 slice of this layer -> registers, valid after the next sweep
         if constexpr (FP8) {
 #pragma unroll
-            for (int c = 0; c < 4; ++c) ps_load16_unseen(w13f[c], wl_ + I8_W13 + (size_t)c * PF_THREADS * 16, (unsigned)tid_k * 16u);
+            for (int c = 0; c < 4; ++c) ps_load16_unseen<NT>(w13f[c], wl_ + I8_W13 + (size_t)c * PF_THREADS * 16, (unsigned)tid_k * 16u);
         } else {
 #pragma unroll
-            for (int c = 0; c < 8; ++c) ps_load16_unseen(w13[c], wl_ + IM_W13 + (size_t)c * PF_THREADS * 16, (unsigned)tid_k * 16u);
+            for (int c = 0; c < 8; ++c) ps_load16_unseen<NT>(w13[c], wl_ + IM_W13 + (size_t)c * PF_THREADS * 16, (unsigned)tid_k * 16u);
         }
     };
     auto request_w2 = [&](const unsigned char* wl_) {
         if constexpr (FP8) {
-            ps_load16_unseen(w2f[0], wl_ + I8_W2, (unsigned)tid_k * 16u); ps_load16_unseen(w2f[1], wl_ + I8_W2 + PF_THREADS * 16, (unsigned)tid_k * 16u);
+            ps_load16_unseen<NT>(w2f[0], wl_ + I8_W2, (unsigned)tid_k * 16u); ps_load16_unseen<NT>(w2f[1], wl_ + I8_W2 + PF_THREADS * 16, (unsigned)tid_k * 16u);
         } else {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) ps_load16_unseen(w2r[q], wl_ + IM_W2 + (size_t)q * PF_THREADS * 16, (unsigned)tid_k * 16u);
+            for (int q = 0; q < 4; ++q) ps_load16_unseen<NT>(w2r[q], wl_ + IM_W2 + (size_t)q * PF_THREADS * 16, (unsigned)tid_k * 16u);
         }
     };
     unsigned long long tk[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, t_last = A.prof ? wall_clock64() : 0;  // [1..6] work of S1..S5 / head, [9..14] the wait (nap + sweep) in front of it
@@ -408,8 +423,8 @@ __global__ __launch_bounds__(PF_THREADS) void k_slow_persist(SlowPersistArgs A) 
             PS_TICK(1);
         }
         // ================= S2: attention of (head ah, slice as)
-        if constexpr (FP8) wo4f = reinterpret_cast<const u32x2*>(wl + I8_WO)[tid];  // next stage's weights
-        else wo4 = reinterpret_cast<const u32x4*>(wl + IM_WO)[tid];
+        if constexpr (FP8) wo4f = ps_ld_w<NT>(reinterpret_cast<const u32x2*>(wl + I8_WO) + tid);  // next stage's weights
+        else wo4 = ps_ld_w<NT>(reinterpret_cast<const u32x4*>(wl + IM_WO) + tid);
         if (att) {
             tid = pf_opaque(tid_k); lane = tid & 63; wave = tid >> 6;
             const u64* eb = my_edges + (size_t)(e & 3) * ering;
@@ -788,11 +803,11 @@ __global__ __launch_bounds__(PF_THREADS) void k_slow_persist(SlowPersistArgs A) 
             if constexpr (FP8) { if (tid < 64) rsc = scl[(size_t)l * scl_layer + SC_W2 + min(tid & 15, 3)]; }
             if (l + 1 < A.n_layer) {  // next layer's Wqkv rows
                 if constexpr (FP8) {
-                    wq4f = reinterpret_cast<const u32x2*>(wl + layer_img + I8_QKV4)[tid];
-                    wq1 = reinterpret_cast<const uint32_t*>(wl + layer_img + I8_QKV1)[tid];
+                    wq4f = ps_ld_w<NT>(reinterpret_cast<const u32x2*>(wl + layer_img + I8_QKV4) + tid);
+                    wq1 = ps_ld_w<NT>(reinterpret_cast<const uint32_t*>(wl + layer_img + I8_QKV1) + tid);
                 } else {
-                    wq4 = reinterpret_cast<const u32x4*>(wl + layer_img + IM_QKV4)[tid];
-                    wq1 = reinterpret_cast<const uint32_t*>(wl + layer_img + IM_QKV1)[tid];
+                    wq4 = ps_ld_w<NT>(reinterpret_cast<const u32x4*>(wl + layer_img + IM_QKV4) + tid);
+                    wq1 = ps_ld_w<NT>(reinterpret_cast<const uint32_t*>(wl + layer_img + IM_QKV1) + tid);
                 }
             }
             float a4[4] = {0.f, 0.f, 0.f, 0.f};
@@ -836,7 +851,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_slow_persist(SlowPersistArgs A) 
         tid = pf_opaque(tid_k); lane = tid & 63; wave = tid >> 6;
         const float2 nw = *reinterpret_cast<const float2*>(A.norms + (size_t)(2 * A.n_layer) * 1024 + 2 * tid);
         const u32x4* hp = reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(A.hpack) + (size_t)b * (FP8 ? PS_HEAD_IMAGE_FP8 : PS_HEAD_IMAGE));
-        const u32x4 h0 = hp[tid], h1 = FP8 ? u32x4{0, 0, 0, 0} : hp[PF_THREADS + tid];
+        const u32x4 h0 = ps_ld_w<NT>(hp + tid), h1 = FP8 ? u32x4{0, 0, 0, 0} : ps_ld_w<NT>(hp + PF_THREADS + tid);
         float rsc = 1.f;
         if constexpr (FP8) { if (tid < 64) rsc = A.hscales[8 * b + min(tid & 15, 7)]; }
         u32x4 v;
@@ -913,18 +928,18 @@ void launch_slow_persist_pack_fp8(const LayerW* layers, int n_layer, const void*
 }
 
 void launch_slow_persist(const SlowPersistArgs& a, hipStream_t st) {
+    using kern_t = void (*)(SlowPersistArgs);
+    static const kern_t kern[2][2] = {{k_slow_persist<false, false>, k_slow_persist<false, true>}, {k_slow_persist<true, false>, k_slow_persist<true, true>}};
     static bool attr_set = false;
     if (!attr_set) {
-        FS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_slow_persist<false>), hipFuncAttributeMaxDynamicSharedMemorySize, PS_LDS));
-        FS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_slow_persist<true>), hipFuncAttributeMaxDynamicSharedMemorySize, PS_LDS));
+        for (int i = 0; i < 4; ++i)
+            FS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern[i >> 1][i & 1]), hipFuncAttributeMaxDynamicSharedMemorySize, PS_LDS));
         attr_set = true;
     }
-    if (a.scales) hipLaunchKernelGGL(k_slow_persist<true>, dim3(PF_BLOCKS), dim3(PF_THREADS), PS_LDS, st, a);
-    else {
-        SlowPersistArgs b2 = a;
-        if (slow_s4_mfma()) b2.l2_touch |= 4;  // bit 2: the bf16 image carries W13 as MFMA fragments (launch_slow_persist_pack)
-        hipLaunchKernelGGL(k_slow_persist<false>, dim3(PF_BLOCKS), dim3(PF_THREADS), PS_LDS, st, b2);
-    }
+    SlowPersistArgs b2 = a;
+    if (!a.scales && slow_s4_mfma()) b2.l2_touch |= 4;  // bit 2: the bf16 image carries W13 as MFMA fragments (launch_slow_persist_pack)
+    const bool nt = (a.l2_touch & PS_STREAM_NT) != 0;    // bit 4: the stream policy (an instantiation; the kernel does not read the bit)
+    hipLaunchKernelGGL(kern[a.scales ? 1 : 0][nt ? 1 : 0], dim3(PF_BLOCKS), dim3(PF_THREADS), PS_LDS, st, b2);
     FS_HIP(hipGetLastError());
 }
 
