@@ -1,7 +1,7 @@
 // Attention kernels of the dual-AR transformer for gfx950 (MI355X): flash-decoding over the paged KV cache for the batch-1 token
 // path (k_attn_decode, merged by k_wo in lm_kernels.hip), and the row path's attention nodes -- one-node static-batch decode
 // (k_attn_rows), the fast decoder's <= 8-token rows (k_attn_small_rows, _tbl), the chunk combine, and the causal MFMA prefill.
-// Launch interface: AttnKernels<WT> in lm_kernels.h; LmKernels<WT>::rows_layer (lm_kernels.hip) decides which rows get an attention node.
+// Launch interface: AttnKernels<WT> in lm_kernels.h; RowKernels<WT>::rows_layer (lm_gemm.hip) decides which rows get an attention node.
 // Reference semantics implemented: fish_speech_core/lib/lm/dual_ar.rs:252-279 (SDPA), :239-249 (rope_i, k_attn_small_rows_tbl).
 #include <hip/hip_runtime.h>
 #include <cstdlib>

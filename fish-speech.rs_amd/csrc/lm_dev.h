@@ -1,6 +1,6 @@
-// Device helpers shared by the transformer kernels (lm_kernels.hip), the attention kernels (lm_attn.hip) and the on-device samplers
-// (lm_sample.hip): weight-type traits, cross-lane reductions, the token embedding, row positions, and the fragment-major GEMM-input
-// layout with the one-row RMSNorm + hi/lo split.
+// Device helpers shared by the transformer kernels (lm_kernels.hip), the row-path GEMMs (lm_gemm.hip), the attention kernels (lm_attn.hip)
+// and the on-device samplers (lm_sample.hip): weight-type traits, the streamed weight load, the paged KV address, cross-lane reductions,
+// the token embedding, row positions, and the fragment-major GEMM-input layout with the one-row RMSNorm + hi/lo split.
 // Device code only; the host-side launch interface is lm_kernels.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -21,6 +21,18 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 #define FS_ISSUE_FENCE() __builtin_amdgcn_sched_barrier(0)
 
 __device__ __forceinline__ float bf16_bits_to_f32(uint32_t hi16) { return __uint_as_float(hi16 << 16); }
+
+template <typename V>
+__device__ __forceinline__ V ld_stream(const V* p) {  // streamed-once weights: non-temporal (guide: nt-weights)
+    return __builtin_nontemporal_load(p);
+}
+
+// element (token t, kv head g, dim 0) of a paged KV pool (layout: lm_kernels.h)
+template <typename WT>
+__device__ __forceinline__ WT* kv_addr(void* pool, const int* __restrict__ page_table, int t, int g, int Hk, int Dh) {
+    const int page = page_table[t / KV_PAGE];
+    return reinterpret_cast<WT*>(pool) + ((size_t)(page * Hk + g) * KV_PAGE + (t % KV_PAGE)) * Dh;
+}
 
 // position of activation row m: pos_step 1 = consecutive tokens of one sequence (prefill), 0 = every row at state->pos (lock-step static
 // batch), -1 = row m is its own sequence with its own state (session slots, fs_lm_session_*)

@@ -751,7 +751,7 @@ class LM final : public LMBase {
                         uint32_t flags, uint32_t* codes_out, size_t cap, size_t* n_frames, uint8_t* is_audio) override {
         FS_REQUIRE(n >= 1, "Must have at least one prompt");  // static_batch.rs:69-71
         FS_REQUIRE(!sess_active_, "the handle is in session mode (fs_lm_session_end first)");
-        if (LmKernels<WT>::has_mfma_prefill() && n <= kRows && n <= B_ && a_.dim % 128 == 0 && a_.intermediate_size % 128 == 0 &&
+        if (RowKernels<WT>::has_mfma_prefill() && n <= kRows && n <= B_ && a_.dim % 128 == 0 && a_.intermediate_size % 128 == 0 &&
             a_.num_codebooks <= 8 && !legacy_) {
             generate_batch_rows(prompts, lens, n, max_new_tokens, s, seed, flags, codes_out, cap, n_frames, is_audio);
             return;
@@ -810,9 +810,9 @@ class LM final : public LMBase {
                 const int S = std::min(per_pass, B - b0), M = S * Lp;
                 RowsCtx c = rows_ctx(state(0), /*pos_step=*/1, /*pt_stride=*/max_pages_);
                 c.seq_rows = Lp;
-                LmKernels<WT>::prefill_embed(d_, tok_emb_, cb_emb_, C, a_.codebook_size, d_cfg_.as<SampleCfg>(),
+                RowKernels<WT>::prefill_embed(d_, tok_emb_, cb_emb_, C, a_.codebook_size, d_cfg_.as<SampleCfg>(),
                                              d_bprompt_.as<uint32_t>() + pstride * b0, state(0), M, d_pfx_.as<float>(), st_, Lp, pstride);
-                for (int l = 0; l < a_.n_layer; ++l) LmKernels<WT>::rows_layer(d_, M, c, slow_[l], slow_kv(l, b0), l == 0, st_);
+                for (int l = 0; l < a_.n_layer; ++l) RowKernels<WT>::rows_layer(d_, M, c, slow_[l], slow_kv(l, b0), l == 0, st_);
             }
             FS_HIP(hipStreamSynchronize(st_));
             for (int b = 0; b < B; ++b) seq_len_[b] = Lp;
@@ -889,7 +889,7 @@ class LM final : public LMBase {
         use_device();
         require_loaded();
         FS_REQUIRE(!sess_active_, "a session is already open on this handle");
-        FS_REQUIRE(LmKernels<WT>::has_mfma_prefill() && B_ <= kRows && a_.dim % 128 == 0 && a_.intermediate_size % 128 == 0 && a_.num_codebooks <= 8,
+        FS_REQUIRE(RowKernels<WT>::has_mfma_prefill() && B_ <= kRows && a_.dim % 128 == 0 && a_.intermediate_size % 128 == 0 && a_.num_codebooks <= 8,
                    "sessions need the MFMA row path (bf16 / fp8 handle)");
         // Fish <= 1.4 handles (no semantic range: the slow token is the 2-way {pad, im_end} draw): only the per-slot samplers define that
         // decision for a slot (k_sample_slow_slots, as the slot's own fs_lm_generate call); the lock-step sampler and the request-row
@@ -1302,10 +1302,10 @@ class LM final : public LMBase {
                 for (int done = 0; done < Lp;) {
                     const int M = std::min(flash ? kRowsCap : kPartRows, Lp - done);
                     c.nc_launch = chunk_bucket(pa.start + done + M);
-                    LmKernels<WT>::prefill_embed(d_, tok_emb_, cb_emb_, C, a_.codebook_size, d_cfg_.as<SampleCfg>(),
+                    RowKernels<WT>::prefill_embed(d_, tok_emb_, cb_emb_, C, a_.codebook_size, d_cfg_.as<SampleCfg>(),
                                                  d2_prompt_.as<uint32_t>(), state(B_), M, d2_pfx_.as<float>(), st_pf_);
-                    for (int l = 0; l < a_.n_layer; ++l) LmKernels<WT>::rows_layer(d_, M, c, slow_[l], slow_kv(l, B_), l == 0, st_pf_);
-                    LmKernels<WT>::rows_finish(d_, M, c, nullptr, st_pf_);
+                    for (int l = 0; l < a_.n_layer; ++l) RowKernels<WT>::rows_layer(d_, M, c, slow_[l], slow_kv(l, B_), l == 0, st_pf_);
+                    RowKernels<WT>::rows_finish(d_, M, c, nullptr, st_pf_);
                     launch_advance_n(state(B_), M, st_pf_);
                     done += M;
                 }
@@ -1348,9 +1348,9 @@ class LM final : public LMBase {
                     c.seq_states = d2_seqpos_.as<SeqState>();
                 }
                 const int M = S * Lp;
-                LmKernels<WT>::prefill_embed(d_, tok_emb_, cb_emb_, C, a_.codebook_size, d_cfg_.as<SampleCfg>(), d2_prompt_.as<uint32_t>(), state(B_), M,
+                RowKernels<WT>::prefill_embed(d_, tok_emb_, cb_emb_, C, a_.codebook_size, d_cfg_.as<SampleCfg>(), d2_prompt_.as<uint32_t>(), state(B_), M,
                                              d2_pfx_.as<float>(), st_pf_, Lp, pstride);
-                for (int l = 0; l < a_.n_layer; ++l) LmKernels<WT>::rows_layer(d_, M, c, slow_[l], slow_kv(l, B_), l == 0, st_pf_);
+                for (int l = 0; l < a_.n_layer; ++l) RowKernels<WT>::rows_layer(d_, M, c, slow_[l], slow_kv(l, B_), l == 0, st_pf_);
             }
         }
         ++sess_count_[0];
@@ -2214,16 +2214,16 @@ class LM final : public LMBase {
     // appending their K/V.  Afterwards x(b) holds the pre-norm hidden state of the last processed token.
     void prefill_tokens(int b, int n, bool use_graph) {
         if (n <= 0) return;
-        if (LmKernels<WT>::has_mfma_prefill() && n > 1 && a_.dim % 128 == 0 && a_.intermediate_size % 128 == 0) {
+        if (RowKernels<WT>::has_mfma_prefill() && n > 1 && a_.dim % 128 == 0 && a_.intermediate_size % 128 == 0) {
             ensure_prefill_buffers();
             RowsCtx c = rows_ctx(state(b), /*pos_step=*/1, /*pt_stride=*/0);
             for (int done = 0; done < n;) {
                 const int M = std::min(a_.head_dim == 64 ? kRowsCap : kPartRows, n - done);
                 c.nc_launch = chunk_bucket(seq_len_[b] + done + M);
-                LmKernels<WT>::prefill_embed(d_, tok_emb_, cb_emb_, a_.num_codebooks, a_.codebook_size, d_cfg_.as<SampleCfg>(),
+                RowKernels<WT>::prefill_embed(d_, tok_emb_, cb_emb_, a_.num_codebooks, a_.codebook_size, d_cfg_.as<SampleCfg>(),
                                              d_prompt_.as<uint32_t>(), state(b), M, d_pfx_.as<float>(), st_);
-                for (int l = 0; l < a_.n_layer; ++l) LmKernels<WT>::rows_layer(d_, M, c, slow_[l], slow_kv(l, b), l == 0, st_);
-                LmKernels<WT>::rows_finish(d_, M, c, nullptr, st_);
+                for (int l = 0; l < a_.n_layer; ++l) RowKernels<WT>::rows_layer(d_, M, c, slow_[l], slow_kv(l, b), l == 0, st_);
+                RowKernels<WT>::rows_finish(d_, M, c, nullptr, st_);
                 launch_advance_n(state(b), M, st_);
                 done += M;
                 if (done == n)
@@ -2308,12 +2308,12 @@ class LM final : public LMBase {
         cs.nc_launch = nc_launch_;
         // decode steps of <= 32 rows: the down projections close every layer themselves (in-launch split-K sums: no slabs, no k_prep nodes but the first)
         cs.xchg = d_xchg_.p; cs.epoch = d_epoch_.as<uint32_t>();
-        const bool fold = !fold_off_ && LmKernels<WT>::rows_fold_ok(d_, B, cs) && a_.n_layer <= 64 && a_.n_fast_layer <= 8 && C <= 32;
+        const bool fold = !fold_off_ && RowKernels<WT>::rows_fold_ok(d_, B, cs) && a_.n_layer <= 64 && a_.n_fast_layer <= 8 && C <= 32;
         cs.fold = fold;
         for (int l = 0; l < a_.n_layer; ++l, cs.node_id = (uint32_t)l)
-            LmKernels<WT>::rows_layer(d_, B, cs, slow_[l], slow_kv(l, 0), l == 0, st_, fold ? (l + 1 < a_.n_layer ? slow_[l + 1].attn_norm : norm_w_) : nullptr);
-        if (!fold) LmKernels<WT>::rows_finish(d_, B, cs, norm_w_, st_);
-        LmKernels<WT>::rows_head(d_, B, cs, slow_head_w(), slow_head_s(), n_audio_, d_lrows_.as<float>(), ld_slow_, st_, fold);
+            RowKernels<WT>::rows_layer(d_, B, cs, slow_[l], slow_kv(l, 0), l == 0, st_, fold ? (l + 1 < a_.n_layer ? slow_[l + 1].attn_norm : norm_w_) : nullptr);
+        if (!fold) RowKernels<WT>::rows_finish(d_, B, cs, norm_w_, st_);
+        RowKernels<WT>::rows_head(d_, B, cs, slow_head_w(), slow_head_s(), n_audio_, d_lrows_.as<float>(), ld_slow_, st_, fold);
         // session steps: the collecting slots' hidden-state rows (one node behind the slow head; null table entries exit at once, so the
         // one captured graph serves every mix of collecting and non-collecting slots)
         if (sess_active_) launch_hidden_rows(d_hid_tab_.as<HidSlot>(), state(0), cs.X, a_.dim, B, st_);
@@ -2357,10 +2357,10 @@ class LM final : public LMBase {
                 KT* base = fast_pool_.as<KT>() + ((size_t)l * 2 * B_) * page_elems_;
                 kv.k = base; kv.v = base + (size_t)B_ * page_elems_; kv.page_table = d_fast_table_.as<int>();
                 cf.node_id = 64u + (uint32_t)cbi * 8u + (uint32_t)l;
-                LmKernels<WT>::rows_layer(d_, B, cf, fast_[l], kv, l == 0, st_, fold ? (l + 1 < a_.n_fast_layer ? fast_[l + 1].attn_norm : fast_norm_w_) : nullptr);
+                RowKernels<WT>::rows_layer(d_, B, cf, fast_[l], kv, l == 0, st_, fold ? (l + 1 < a_.n_fast_layer ? fast_[l + 1].attn_norm : fast_norm_w_) : nullptr);
             }
-            if (!fold) LmKernels<WT>::rows_finish(d_, B, cf, fast_norm_w_, st_);
-            LmKernels<WT>::rows_head(d_, B, cf, fast_out_w_, kFp8 ? fast_out_s_ : nullptr, a_.codebook_size, d_lfast_.as<float>(), a_.codebook_size, st_, fold);
+            if (!fold) RowKernels<WT>::rows_finish(d_, B, cf, fast_norm_w_, st_);
+            RowKernels<WT>::rows_head(d_, B, cf, fast_out_w_, kFp8 ? fast_out_s_ : nullptr, a_.codebook_size, d_lfast_.as<float>(), a_.codebook_size, st_, fold);
             if (capt) launch_cap_rows_logits(d_lfast_.as<float>(), a_.codebook_size, a_.codebook_size, state(0), d_cfg_.as<SampleCfg>(), B, d_rcap_.as<float>(),
                                              cap_frames_, 1 + cbi, st_);
             // the pass that reads this sampler's row: with the qkv table its first layer needs no normalised GEMM input from the sampler
@@ -2407,7 +2407,7 @@ class LM final : public LMBase {
         {   // the co-residency query of the folded step (rows_fold_ok -> occupancy API) is answered once, OUTSIDE stream capture
             RowsCtx cs = rows_ctx(state(0), 0, max_pages_);
             cs.xchg = d_xchg_.p; cs.epoch = d_epoch_.as<uint32_t>();
-            (void)LmKernels<WT>::rows_fold_ok(d_, B, cs);
+            (void)RowKernels<WT>::rows_fold_ok(d_, B, cs);
         }
         hipGraph_t g = nullptr;
         hipGraphExec_t ge = nullptr;

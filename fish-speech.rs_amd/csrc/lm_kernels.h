@@ -1,5 +1,5 @@
-// Launch interface of the dual-AR decode kernels (lm_kernels.hip), the attention kernels (lm_attn.hip) and the on-device samplers
-// (lm_sample.hip).  gfx950 only.
+// Launch interface of the dual-AR decode kernels (lm_kernels.hip), the MFMA row-path GEMMs (lm_gemm.hip), the attention kernels
+// (lm_attn.hip) and the on-device samplers (lm_sample.hip).  gfx950 only.
 //
 // Data layout in HBM:
 //  * weights: row-major [out, in] in WT (bf16, f32, or OCP e4m3fn bytes + one f32 scale per row), one 256-B aligned slab
@@ -130,7 +130,14 @@ struct LmKernels {
     // state->step (prompt != null) or from state->cur
     static void embed(const ModelDims& d, const void* tok_emb, const void* cb_emb, int n_cb, int cb_size,
                       const SampleCfg* cfg, const uint32_t* prompt, SeqState* state, float* x, hipStream_t st);
-    // ---- MFMA row path (prefill passes, static-batch steps): bf16 weights, or fp8 weights widened to bf16 in registers
+    // fast_embeddings gather: out[i] = fast_emb[ids[i]]
+    static void fast_embed(const ModelDims& d, const void* fast_emb, const uint32_t* ids, int n, float* out,
+                           hipStream_t st);
+};
+
+// ---- MFMA row path (lm_gemm.hip; prefill passes, static-batch steps): bf16 weights, or fp8 weights widened to bf16 in registers
+template <typename WT>
+struct RowKernels {
     static bool has_mfma_prefill();
     // X[m] = embed(prompt column state->step + m), m < M
     static void prefill_embed(const ModelDims& d, const void* tok_emb, const void* cb_emb, int n_cb, int cb_size,
@@ -148,9 +155,6 @@ struct LmKernels {
     static void rows_finish(const ModelDims& d, int M, const RowsCtx& c, const float* norm_w, hipStream_t st);
     static void rows_head(const ModelDims& d, int M, const RowsCtx& c, const void* W, const float* wscale, int n_rows, float* logits, int ld,
                           hipStream_t st, bool rms = false);
-    // fast_embeddings gather: out[i] = fast_emb[ids[i]]
-    static void fast_embed(const ModelDims& d, const void* fast_emb, const uint32_t* ids, int n, float* out,
-                           hipStream_t st);
 };
 
 // ---- attention launchers (lm_attn.hip; all asynchronous on `st`)
@@ -166,7 +170,7 @@ struct AttnKernels {
     // the position of every frame, so graphs are captured per power-of-two bucket of nc_launch)
     static void decode(const ModelDims& d, const float* q, KVView kv, const SeqState* state, float* part, int n_chunks_max, int nc_launch,
                        hipStream_t st);
-    // attention step of LmKernels::rows_layer over M activation rows: c.Q (or, tbl0, row code of c.qkv0_tbl) against each row's KV prefix ->
+    // attention step of RowKernels::rows_layer over M activation rows: c.Q (or, tbl0, row code of c.qkv0_tbl) against each row's KV prefix ->
     // hi/lo fragments in c.A.  tbl0 is rows_layer's decision (it also drops the layer's k_prep and Wqkv nodes)
     static void rows(const ModelDims& d, int M, const RowsCtx& c, KVView kv, bool tbl0, hipStream_t st);
     // may the first layer of a pass with this context take q / k / v from a qkv table (RowsCtx::qkv0_tbl)?  The engine asks before it sets the

@@ -1,4 +1,4 @@
-// Micro-benchmark of the MFMA row path (rows_layer: k_prep, k_gemm3 / k_gemm_big, attention) stage by stage: graph of 24 layers over distinct weights.
+// Micro-benchmark of the MFMA row path (RowKernels::rows_layer in lm_gemm.hip: k_prep, k_gemm3 / k_gemm_big, attention) stage by stage: graph of 24 layers over distinct weights.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <functional>
@@ -51,11 +51,11 @@ int main(int argc, char** argv) {
     std::vector<int> pt(max_pages); for (int i = 0; i < max_pages; ++i) pt[i] = i;
     int* d_pt = (int*)dalloc(max_pages * 4); CK(hipMemcpy(d_pt, pt.data(), max_pages * 4, hipMemcpyHostToDevice));
     auto kv = [&](int l) { KVView v; v.k = kvpool + (size_t)l * 2 * max_pages * page_elems; v.v = (WT*)v.k + max_pages * page_elems; v.page_table = d_pt; return v; };
-    float us = time_graph(st, NL, 10, [&](int i) { LmKernels<WT>::rows_layer(d, M, c, lw[i % NL], kv(i % NL), i == 0, st); });
+    float us = time_graph(st, NL, 10, [&](int i) { RowKernels<WT>::rows_layer(d, M, c, lw[i % NL], kv(i % NL), i == 0, st); });
     static const char* names[8] = {"prep(attn_norm)", "gemm qkv+rope+kv", "attention", "attn combine", "gemm wo+res", "prep(ffn_norm)", "gemm w13+swiglu", "gemm w2 slabs"};
     for (int sI = 0; sI < 8; ++sI) {
         c.stage_mask = 1u << sI;
-        float t = time_graph(st, NL, 10, [&](int i) { LmKernels<WT>::rows_layer(d, M, c, lw[i % NL], kv(i % NL), false, st); });
+        float t = time_graph(st, NL, 10, [&](int i) { RowKernels<WT>::rows_layer(d, M, c, lw[i % NL], kv(i % NL), false, st); });
         printf("  stage %d %-18s %7.2f us/node\n", sI, names[sI], t);
     }
     c.stage_mask = 0xFFu;
