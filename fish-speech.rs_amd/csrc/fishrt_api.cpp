@@ -239,6 +239,19 @@ int fs_lm_session_prefix_create(fs_lm_t* lm, const uint32_t* prompt, int P, int*
     FS_ARG(lm && prompt && prefix_id, "null argument");
     FS_TRY(*prefix_id = lm->impl->session_prefix_create(prompt, P))
 }
+static_assert(sizeof(fs_kv_blob_header) == 64, "fs_kv_blob_header is the 64-byte blob header of fishrt.h");
+int fs_lm_weights_fingerprint(fs_lm_t* lm, uint64_t* out) {
+    FS_ARG(lm && out, "null argument");
+    FS_TRY(*out = lm->impl->weights_fingerprint())
+}
+int fs_lm_session_prefix_export(fs_lm_t* lm, int prefix_id, void* blob_out, size_t cap, size_t* bytes) {
+    FS_ARG(lm, "null argument");
+    FS_TRY(lm->impl->session_prefix_export(prefix_id, blob_out, cap, bytes))
+}
+int fs_lm_session_prefix_import(fs_lm_t* lm, const void* blob, size_t bytes, int* prefix_id) {
+    FS_ARG(lm && blob && prefix_id, "null argument");
+    FS_TRY(*prefix_id = lm->impl->session_prefix_import(blob, bytes))
+}
 int fs_lm_session_prefix_release(fs_lm_t* lm, int prefix_id) { FS_ARG(lm, "null argument"); FS_TRY(lm->impl->session_prefix_release(prefix_id)) }
 int fs_lm_session_add_prefixed(fs_lm_t* lm, int prefix_id, const uint32_t* body, int L_body, int max_new_tokens, int* slot) {
     FS_ARG(lm && body && slot, "null argument");

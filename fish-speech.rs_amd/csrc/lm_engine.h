@@ -47,6 +47,10 @@ class LMBase {
     virtual void session_prefix_release(int id) = 0;
     virtual int session_add_prefixed(int id, const uint32_t* body, int L_body, int max_new_tokens) = 0;
     virtual void session_info(int64_t out[8]) = 0;
+    // prefix KV blobs (fishrt.h: fs_lm_weights_fingerprint / fs_lm_session_prefix_export / _import)
+    virtual uint64_t weights_fingerprint() = 0;
+    virtual void session_prefix_export(int id, void* blob_out, size_t cap, size_t* bytes) = 0;
+    virtual int session_prefix_import(const void* blob, size_t bytes) = 0;
     // fishrt.h: fs_lm_session_add_ex (prefix_id < 0: plain add; sampling / seed nullable: the session's)
     virtual int session_add_ex(int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling,
                                const uint64_t* seed) = 0;

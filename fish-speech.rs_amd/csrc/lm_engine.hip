@@ -241,6 +241,7 @@ class LM final : public LMBase {
         }
         FS_HIP(hipStreamSynchronize(st_));
         loaded_ = true;
+        fp_valid_ = false;
         refresh_legacy_head();
         pack_persist();
     }
@@ -273,6 +274,7 @@ class LM final : public LMBase {
             FS_HIP(hipStreamSynchronize(st_));
         }
         loaded_ = true;
+        fp_valid_ = false;
         refresh_legacy_head();
         pack_persist();
     }
@@ -289,6 +291,7 @@ class LM final : public LMBase {
         FS_REQUIRE(!sess_active_, "the handle is in session mode (fs_lm_session_end first)");
         FS_HIP(hipDeviceSynchronize());  // the bytes were written by another stream (the communicator's)
         loaded_ = true;
+        fp_valid_ = false;
         refresh_legacy_head();
         pack_persist();
     }
@@ -1133,17 +1136,19 @@ class LM final : public LMBase {
     }
     // a queued request: plain add (prompt = all L columns, start 0), prefixed add (prompt = the body's L - start columns, start = the
     // prefix's P, tail = the prefix's partly filled last page, held until the copy has run) or a prefix's own pass (create: prompt = its P
-    // columns, all of them prefilled into the prefix's pages; slot -1)
+    // columns, all of them prefilled into the prefix's pages; slot -1) or a prefix's import (create and import_kv: blob = the payload of
+    // fs_lm_session_prefix_import, copied and scattered into the prefix's pages; no prompt, nothing runs through the slow transformer)
     struct PendingAdd {
         int slot = -1, L = 0, n_iter = 0, order = 0, start = 0, prefix = -1, tail = -1;
-        bool create = false;
+        bool create = false, import_kv = false;
+        std::vector<uint8_t> blob;
         bool has_cfg = false, has_seed = false;  // fs_lm_session_add_ex: the slot's own settings / sampler seed
         SampleCfg cfg = {};
         uint64_t seed = 0;
         float* hid = nullptr;  // fs_lm_session_add_hidden: the slot's row buffer [hid_cap][dim], handed to the device table at activation
         int hid_cap = 0;
         std::vector<uint32_t> prompt;
-        int rows() const { return create ? L : L - start - 1; }   // tokens this member runs through the slow transformer
+        int rows() const { return import_kv ? 0 : (create ? L : L - start - 1); }   // tokens this member runs through the slow transformer
         int cols() const { return create ? L : L - start; }       // columns of `prompt`
         int end() const { return create ? L : L + n_iter - 1; }   // positions whose K/V the member keeps
     };
@@ -1232,8 +1237,138 @@ class LM final : public LMBase {
         for (int k = 0; k < 4; ++k) out[3 + k] = sess_count_[k];
         out[7] = (int64_t)std::llround(sess_pf_ms_ * 1000.0);
     }
+    // ---- prefix KV blobs (fishrt.h: fs_lm_weights_fingerprint / fs_lm_session_prefix_export / _import)
+    uint64_t weights_fingerprint() override {
+        use_device();
+        require_loaded();
+        if (!fp_valid_) {
+            hipStream_t s = st_pf_ ? st_pf_ : st_;  // (inside a session: not the decode stream)
+            if (!d_fp_.p) d_fp_.alloc(sizeof(uint64_t));
+            FS_REQUIRE(arena_bytes_ / 4 < (1ull << 32), "weight arena too large for the fingerprint's swap guarantee");
+            uint64_t z = 0;
+            FS_HIP(hipMemsetAsync(d_fp_.p, 0, sizeof(uint64_t), s));
+            launch_arena_fingerprint(arena_.p, arena_bytes_, d_fp_.as<uint64_t>(), s);
+            FS_HIP(hipMemcpyAsync(&z, d_fp_.p, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+            FS_HIP(hipStreamSynchronize(s));
+            z ^= (uint64_t)(arena_bytes_ / 4) * 0x9E3779B97F4A7C15ull;
+            z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+            z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+            fp_ = z ^ (z >> 31);
+            fp_valid_ = true;
+        }
+        return fp_;
+    }
+    static constexpr uint32_t kv_dtype_id() { return std::is_same<KT, float>::value ? (uint32_t)FS_F32 : (uint32_t)FS_BF16; }
+    size_t prefix_payload_bytes(int P) const { return (size_t)a_.n_layer * 2 * (size_t)P * a_.n_local_heads * a_.head_dim * sizeof(KT); }
+    // grow the staging buffer / the page-id buffer (the prefill stream is drained first: an earlier pass may still read them)
+    void kvb_reserve(size_t bytes, size_t n_page_ids) {
+        if (d_kvb_.n >= bytes && d_kvb_pages_.n >= sizeof(int) * n_page_ids) return;
+        FS_HIP(hipStreamSynchronize(st_pf_));
+        if (d_kvb_.n < bytes) d_kvb_.alloc(bytes);
+        if (d_kvb_pages_.n < sizeof(int) * n_page_ids) d_kvb_pages_.alloc(sizeof(int) * std::max(n_page_ids, (size_t)max_pages_));
+    }
+    void session_prefix_export(int id, void* blob_out, size_t cap, size_t* bytes) override {
+        use_device();
+        const int P = live_prefix(id).P;
+        const size_t payload = prefix_payload_bytes(P), total = sizeof(fs_kv_blob_header) + payload;
+        if (bytes) *bytes = total;
+        if (!blob_out) return;
+        FS_REQUIRE(cap >= total, "blob_out capacity is smaller than the prefix blob (query the size with blob_out == NULL)");
+        while (sess_prefixes_[id].pending) { flush_pending(); activate_pending(true); }  // (its own pass first, as session_release does for a slot)
+        fs_kv_blob_header h = {};
+        std::memcpy(h.magic, "FSKVPFX1", 8);
+        h.version = 1; h.kv_dtype = kv_dtype_id();
+        h.n_layer = a_.n_layer; h.n_local_heads = a_.n_local_heads; h.head_dim = a_.head_dim; h.P = P;
+        h.header_bytes = (uint32_t)sizeof(h);
+        h.weights_fingerprint = weights_fingerprint();
+        h.payload_bytes = payload;
+        const std::vector<int>& pg = sess_prefixes_[id].pages;
+        FS_REQUIRE((int)pg.size() * KV_PAGE >= P, "the prefix holds fewer pages than its length");
+        kvb_reserve(payload, pg.size());
+        FS_HIP(hipMemcpyAsync(d_kvb_pages_.p, pg.data(), sizeof(int) * pg.size(), hipMemcpyHostToDevice, st_pf_));
+        const size_t page_bytes = page_elems_ * sizeof(KT);
+        launch_kv_rows_gather(kv_pool_.p, 2 * a_.n_layer, (size_t)n_pages_ * page_bytes, page_bytes, d_kvb_pages_.as<int>(), P, a_.n_local_heads,
+                              a_.head_dim, sizeof(KT), d_kvb_.p, st_pf_);
+        FS_HIP(hipMemcpyAsync(static_cast<uint8_t*>(blob_out) + sizeof(h), d_kvb_.p, payload, hipMemcpyDeviceToHost, st_pf_));
+        FS_HIP(hipStreamSynchronize(st_pf_));
+        std::memcpy(blob_out, &h, sizeof(h));
+    }
+    int session_prefix_import(const void* blob, size_t bytes) override {
+        use_device();
+        FS_REQUIRE(sess_active_, "no open session");
+        fs_kv_blob_header h;
+        FS_REQUIRE(bytes >= sizeof(h), "prefix blob: bytes is smaller than the 64-byte header");
+        std::memcpy(&h, blob, sizeof(h));
+        FS_REQUIRE(std::memcmp(h.magic, "FSKVPFX1", 8) == 0, "prefix blob: wrong magic (not \"FSKVPFX1\")");
+        FS_REQUIRE(h.version == 1, "prefix blob: unsupported version (this library reads version 1)");
+        FS_REQUIRE(h.header_bytes == sizeof(h), "prefix blob: header_bytes is not 64");
+        FS_REQUIRE((uint64_t)(bytes - sizeof(h)) == h.payload_bytes, "prefix blob: bytes != 64 + payload_bytes (truncated or padded blob)");
+        FS_REQUIRE(h.kv_dtype == kv_dtype_id(), "prefix blob: kv_dtype differs from this handle's KV storage type");
+        FS_REQUIRE(h.n_layer == a_.n_layer, "prefix blob: n_layer differs from this handle's");
+        FS_REQUIRE(h.n_local_heads == a_.n_local_heads, "prefix blob: n_local_heads differs from this handle's");
+        FS_REQUIRE(h.head_dim == a_.head_dim, "prefix blob: head_dim differs from this handle's");
+        FS_REQUIRE(h.P >= 1 && h.P < a_.max_seq_len, "prefix blob: P outside 1 <= P < max_seq_len (a prefix must leave room for a body)");
+        FS_REQUIRE(h.payload_bytes == (uint64_t)prefix_payload_bytes(h.P), "prefix blob: payload_bytes does not match n_layer * 2 * P * n_local_heads * head_dim elements");
+        FS_REQUIRE(h.weights_fingerprint == weights_fingerprint(), "prefix blob: weights_fingerprint differs from this handle's (other weights or storage type)");
+        ensure_prefill2_buffers();
+        const int P = h.P, np = (P + KV_PAGE - 1) / KV_PAGE;
+        if ((int)free_pages_.size() < np) return -1;
+        SessPrefix px;
+        px.P = P; px.live = true; px.pending = true;
+        for (int j = 0; j < np; ++j) px.pages.push_back(take_page());
+        sess_prefixes_.push_back(std::move(px));
+        PendingAdd pa;
+        pa.create = true; pa.import_kv = true; pa.L = P; pa.prefix = (int)sess_prefixes_.size() - 1;
+        const uint8_t* payload = static_cast<const uint8_t*>(blob) + sizeof(h);
+        pa.blob.assign(payload, payload + h.payload_bytes);  // (the caller may free its blob as soon as this returns)
+        sess_queue_.push_back(std::move(pa));
+        return (int)sess_prefixes_.size() - 1;
+    }
+    // the pass of the imports at the head of the (sorted) queue: per import one host-to-device copy into the staging buffer and one
+    // k_kv_rows_scatter into its pages, on the prefill stream; activated like a creating pass (pa.create).  No counter of a transformer
+    // pass moves.
+    void launch_import_pass() {
+        size_t n = 0, total = 0, n_ids = 0;
+        while (n < sess_queue_.size() && sess_queue_[n].import_kv) {  // (everything is checked before the first launch)
+            const SessPrefix& px = sess_prefixes_[sess_queue_[n].prefix];
+            FS_REQUIRE(sess_queue_[n].blob.size() == prefix_payload_bytes(px.P) && (int)px.pages.size() * KV_PAGE >= px.P,
+                       "prefix import: payload / pages do not match P");
+            // (slots already queued on this prefix hold references on its pages too; none of them reads or writes one before this pass)
+            for (int p : px.pages) FS_REQUIRE(p >= 0 && p < n_pages_ && page_refs_[p] >= 1, "prefix import: a page of the prefix is not held");
+            total += sess_queue_[n].blob.size();
+            n_ids += sess_prefixes_[sess_queue_[n].prefix].pages.size();
+            ++n;
+        }
+        kvb_reserve(total, n_ids);
+        std::vector<int>& ids = sess_stage_imp_pages_;  // (alive until the pass has been activated)
+        ids.clear();
+        for (size_t i = 0; i < n; ++i) {
+            const auto& pg = sess_prefixes_[sess_queue_[i].prefix].pages;
+            ids.insert(ids.end(), pg.begin(), pg.end());
+        }
+        FS_HIP(hipMemcpyAsync(d_kvb_pages_.p, ids.data(), sizeof(int) * ids.size(), hipMemcpyHostToDevice, st_pf_));
+        const size_t page_bytes = page_elems_ * sizeof(KT);
+        size_t off = 0, id_off = 0;
+        for (size_t i = 0; i < n; ++i) {
+            const PendingAdd& pa = sess_queue_[i];
+            const SessPrefix& px = sess_prefixes_[pa.prefix];
+            uint8_t* stage = d_kvb_.as<uint8_t>() + off;  // (payloads are whole 16-byte units: head_dim % 8 == 0)
+            FS_HIP(hipMemcpyAsync(stage, pa.blob.data(), pa.blob.size(), hipMemcpyHostToDevice, st_pf_));
+            launch_kv_rows_scatter(kv_pool_.p, 2 * a_.n_layer, (size_t)n_pages_ * page_bytes, page_bytes, d_kvb_pages_.as<int>() + id_off, px.P,
+                                   a_.n_local_heads, a_.head_dim, sizeof(KT), stage, st_pf_);
+            off += pa.blob.size();
+            id_off += px.pages.size();
+        }
+        FS_HIP(hipEventRecord(ev_pft_[1], st_pf_));
+        FS_HIP(hipEventRecord(ev_pf_, st_pf_));
+        sess_flight_.assign(std::make_move_iterator(sess_queue_.begin()), std::make_move_iterator(sess_queue_.begin() + n));
+        sess_queue_.erase(sess_queue_.begin(), sess_queue_.begin() + n);
+    }
     // launch the prefill of the next group of queued requests (ONE pass on the prefill stream, nothing waited for); no-op while an
     // earlier group is still in flight -- the rest of the queue follows once that one has been activated.
+    // Imported prefixes (fs_lm_session_prefix_import) go first, all of them in ONE pass of their own kind (launch_import_pass: copies and
+    // scatters, no transformer pass): whatever was queued with them -- creations, adds, an add with a one-column body that prefills nothing --
+    // stays queued until that pass has been activated.
     // Shared prefixes: a prefix's own pass (pa.create) prefills all P of its positions into its pages; creations go in passes of their
     // own, ahead of every add queued with them (an add on a prefix reads its pages, and stream order on the prefill stream puts that
     // read after the creating pass).  A prefixed member starts at position P (RowsCtx.seq_states in a group pass) and runs its body
@@ -1243,12 +1378,16 @@ class LM final : public LMBase {
         if (sess_queue_.empty() || !sess_flight_.empty()) return;
         const int C1 = a_.num_codebooks + 1, C = a_.num_codebooks;
         std::stable_sort(sess_queue_.begin(), sess_queue_.end(),
-                         [](const PendingAdd& x, const PendingAdd& y) { return x.create != y.create ? x.create : x.rows() > y.rows(); });
+                         [](const PendingAdd& x, const PendingAdd& y) {
+                             if (x.import_kv != y.import_kv) return x.import_kv;
+                             return x.create != y.create ? x.create : x.rows() > y.rows();
+                         });
         const bool flash = a_.head_dim == 64;
         size_t i = 0;
         int S = 1;
         FS_HIP(hipEventRecord(ev_pft_[0], st_pf_));
         sess_timed_ = true;
+        if (sess_queue_[0].import_kv) { launch_import_pass(); return; }
         {
             const int Lp = sess_queue_[i].rows();  // the longest of this pass (sorted): tokens that run through the slow transformer
             if (Lp < 1) {                          // only single-token prompts are left: no pass, they go live at the next activation
@@ -2839,6 +2978,12 @@ class LM final : public LMBase {
     std::vector<uint32_t> sess_stage_prompts_;
     std::vector<int> sess_stage_rows_;
     std::vector<PendingAdd> sess_queue_, sess_flight_;  // joining requests: queued by session_add / prefill launched (flush_pending)
+    // prefix KV blobs: the handle's staging buffer (grow-only: the largest payload moved so far -- one export, or the imports of one pass),
+    // the page ids of the prefixes being moved (device + the host vector the upload reads), the cached arena fingerprint
+    DevBuf d_kvb_, d_kvb_pages_, d_fp_;
+    std::vector<int> sess_stage_imp_pages_;
+    bool fp_valid_ = false;
+    uint64_t fp_ = 0;
     // hidden-state collection (fs_lm_session_add_hidden): the device table the step's k_hidden_rows node reads (allocated once per handle:
     // the captured step graphs hold its address), its host mirror (rows / cap as uploaded, count as of the last step), the slots admitted
     // as collectors, how many of them are live, and the handle's pool of free row buffers (device pointer, capacity in rows)

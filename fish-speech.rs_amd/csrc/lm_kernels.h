@@ -290,6 +290,16 @@ void launch_cap_rows_picks(const SeqState* states, const SampleCfg* cfg, int B, 
 void launch_reppen_reset(RepPenState rp, int n_cb, int cb_size, hipStream_t st);
 // copy KV page pairs[2i] -> pairs[2i + 1] (device int array) in each of n_regions pool regions region_bytes apart: ONE launch
 void launch_kv_page_copy(void* pool, int n_regions, size_t region_bytes, size_t page_bytes, const int* pairs, int n_pairs, hipStream_t st);
+// Prefix KV blobs (fishrt.h: fs_lm_session_prefix_export / _import): the P rows of a prefix between its pages (`pages`: device int array
+// of its ceil(P / 64) page ids, each page [Hk][64][Dh]) and the packed payload [n_regions][P][Hk][Dh] (`packed`, 16-byte aligned), in each
+// of the n_regions pool regions region_bytes apart (k_kv_rows_gather: pages -> packed; k_kv_rows_scatter: packed -> pages; only the
+// valid rows of the last page move).  16-byte loads and stores along Dh: head_dim % 8 != 0 is an error.  ONE launch each.
+void launch_kv_rows_gather(const void* pool, int n_regions, size_t region_bytes, size_t page_bytes, const int* pages, int P, int Hk, int Dh,
+                           size_t elem_bytes, void* packed, hipStream_t st);
+void launch_kv_rows_scatter(void* pool, int n_regions, size_t region_bytes, size_t page_bytes, const int* pages, int P, int Hk, int Dh,
+                            size_t elem_bytes, const void* packed, hipStream_t st);
+// k_arena_fingerprint: *acc (device, zeroed by the caller) += sum_i w[i] * (2 i + 1) mod 2^64 over the bytes / 4 32-bit words of the arena
+void launch_arena_fingerprint(const void* arena, size_t bytes, uint64_t* acc, hipStream_t st);
 // Hidden-state collection of session slots (fishrt.h: fs_lm_session_add_hidden).  One entry per slot: rows == null -> the slot does not
 // collect; else its buffer f32 [cap][dim], and count = rows stored so far == the slot's generator iterations so far.
 struct HidSlot {

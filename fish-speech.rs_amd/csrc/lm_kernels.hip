@@ -770,6 +770,83 @@ void launch_kv_page_copy(void* pool, int n_regions, size_t region_bytes, size_t 
     FS_LAUNCH_CHECK();
 }
 
+// Prefix KV blobs (fishrt.h: fs_lm_session_prefix_export / _import).  Block = (page j of the prefix, region); the regions are those of
+// k_kv_page_copy.  A page holds [Hk][64][Dh]; the packed payload of a region holds the prefix's P rows as [t][Hk][Dh].  The block moves
+// only the min(64, P - 64 j) valid rows of its page, in 16-byte units along Dh (`upr` units per [Dh] row): unit i of the block's packed
+// span is (t, g, u) = (i / (Hk upr), i / upr % Hk, i % upr), its place in the page is ((g 64 + t) upr + u).
+template <bool kScatter>
+__device__ __forceinline__ void kv_rows_move(uint8_t* pool, size_t region_bytes, size_t page_bytes, const int* __restrict__ pages, int P, int Hk,
+                                             int upr, uint8_t* packed) {
+    const int j = blockIdx.x;
+    const int rows = min(KV_PAGE, P - KV_PAGE * j);
+    if (rows <= 0) return;
+    uint4* const page = reinterpret_cast<uint4*>(pool + (size_t)blockIdx.y * region_bytes + (size_t)pages[j] * page_bytes);
+    const int row_units = Hk * upr;  // 16-byte units of one packed row
+    uint4* const pk = reinterpret_cast<uint4*>(packed) + ((size_t)blockIdx.y * P + (size_t)KV_PAGE * j) * row_units;
+    const int n = rows * row_units;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const int t = i / row_units, rem = i - t * row_units, g = rem / upr, u = rem - g * upr;
+        const int at = (g * KV_PAGE + t) * upr + u;
+        if (kScatter) page[at] = pk[i];
+        else pk[i] = page[at];
+    }
+}
+__global__ __launch_bounds__(256) void k_kv_rows_gather(const uint8_t* __restrict__ pool, size_t region_bytes, size_t page_bytes,
+                                                        const int* __restrict__ pages, int P, int Hk, int upr, uint8_t* __restrict__ packed) {
+    kv_rows_move<false>(const_cast<uint8_t*>(pool), region_bytes, page_bytes, pages, P, Hk, upr, packed);
+}
+__global__ __launch_bounds__(256) void k_kv_rows_scatter(uint8_t* __restrict__ pool, size_t region_bytes, size_t page_bytes,
+                                                         const int* __restrict__ pages, int P, int Hk, int upr, const uint8_t* __restrict__ packed) {
+    kv_rows_move<true>(pool, region_bytes, page_bytes, pages, P, Hk, upr, const_cast<uint8_t*>(packed));
+}
+static void check_kv_rows(size_t region_bytes, size_t page_bytes, int P, int Hk, int Dh, size_t elem_bytes) {
+    FS_REQUIRE(Dh % 8 == 0, "prefix KV blobs need head_dim % 8 == 0 (the rows move in 16-byte units along head_dim)");
+    FS_REQUIRE(P >= 1 && Hk >= 1 && (Dh * elem_bytes) % 16 == 0 && page_bytes == (size_t)Hk * KV_PAGE * Dh * elem_bytes && region_bytes % page_bytes == 0,
+               "prefix KV blob: page geometry does not match the pool");
+}
+void launch_kv_rows_gather(const void* pool, int n_regions, size_t region_bytes, size_t page_bytes, const int* pages, int P, int Hk, int Dh,
+                           size_t elem_bytes, void* packed, hipStream_t st) {
+    check_kv_rows(region_bytes, page_bytes, P, Hk, Dh, elem_bytes);
+    hipLaunchKernelGGL(k_kv_rows_gather, dim3((P + KV_PAGE - 1) / KV_PAGE, n_regions), dim3(256), 0, st, reinterpret_cast<const uint8_t*>(pool),
+                       region_bytes, page_bytes, pages, P, Hk, (int)(Dh * elem_bytes / 16), reinterpret_cast<uint8_t*>(packed));
+    FS_LAUNCH_CHECK();
+}
+void launch_kv_rows_scatter(void* pool, int n_regions, size_t region_bytes, size_t page_bytes, const int* pages, int P, int Hk, int Dh,
+                            size_t elem_bytes, const void* packed, hipStream_t st) {
+    check_kv_rows(region_bytes, page_bytes, P, Hk, Dh, elem_bytes);
+    hipLaunchKernelGGL(k_kv_rows_scatter, dim3((P + KV_PAGE - 1) / KV_PAGE, n_regions), dim3(256), 0, st, reinterpret_cast<uint8_t*>(pool),
+                       region_bytes, page_bytes, pages, P, Hk, (int)(Dh * elem_bytes / 16), reinterpret_cast<const uint8_t*>(packed));
+    FS_LAUNCH_CHECK();
+}
+
+// Fingerprint of the weight arena (fishrt.h: fs_lm_weights_fingerprint): *acc += sum over the arena's 32-bit words w[i] of
+// w[i] * (2 i + 1), in wrapping 64-bit integer arithmetic -- a sum of integers, so the grid size and the order of the atomics do not
+// change a bit of it.  Lanes read 16 bytes (4 words) per step; the n % 4 last words are taken by the first lanes of block 0.
+__global__ __launch_bounds__(256) void k_arena_fingerprint(const uint32_t* __restrict__ w, uint64_t n, unsigned long long* __restrict__ acc) {
+    __shared__ unsigned long long part[4];
+    const uint64_t n4 = n / 4;
+    const uint4* w4 = reinterpret_cast<const uint4*>(w);
+    unsigned long long s = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (uint64_t)gridDim.x * 256) {
+        const uint4 v = w4[i];
+        const uint64_t k = 8 * i + 1;  // 2 * (4 i) + 1
+        s += (uint64_t)v.x * k + (uint64_t)v.y * (k + 2) + (uint64_t)v.z * (k + 4) + (uint64_t)v.w * (k + 6);
+    }
+    if (blockIdx.x == 0 && 4 * n4 + threadIdx.x < n) s += (uint64_t)w[4 * n4 + threadIdx.x] * (2 * (4 * n4 + threadIdx.x) + 1);
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(acc, part[0] + part[1] + part[2] + part[3]);
+}
+void launch_arena_fingerprint(const void* arena, size_t bytes, uint64_t* acc, hipStream_t st) {
+    FS_REQUIRE(bytes % 4 == 0 && ((uintptr_t)arena & 15) == 0, "the weight arena must be whole 32-bit words, 16-byte aligned");
+    const uint64_t n = bytes / 4;
+    const int grid = (int)std::max<uint64_t>(1, std::min<uint64_t>((n / 4 + 255) / 256, 2048));
+    hipLaunchKernelGGL(k_arena_fingerprint, dim3(grid), dim3(256), 0, st, reinterpret_cast<const uint32_t*>(arena), n,
+                       reinterpret_cast<unsigned long long*>(acc));
+    FS_LAUNCH_CHECK();
+}
+
 // Hidden-state collection of session slots: one block per slot.  The row index is the slot's own counter in the table (== its iteration
 // index: a slot runs one iteration per step from its activation until done != 0), so a parked, frozen, finished or not yet joined slot
 // (done != 0) stores nothing and a full buffer is never overrun.  256 lanes x 16 bytes = one 1024-float row per pass.

@@ -3,7 +3,7 @@ Python here is only the host-side mirror of the reference's PyO3 surface; all co
 from . import config
 from ._ffi import LIB_PATH, SYMBOLS, lib
 from .codec import FireflyCodec
-from .lm import LM, DualARTransformer
+from .lm import LM, DualARTransformer, prefix_blob_info
 from .stream import SessionStreamer, StreamingSynth, decode_chunk
 
-__all__ = ["config", "lib", "LIB_PATH", "SYMBOLS", "DualARTransformer", "LM", "FireflyCodec", "StreamingSynth", "SessionStreamer", "decode_chunk"]
+__all__ = ["config", "lib", "LIB_PATH", "SYMBOLS", "DualARTransformer", "LM", "prefix_blob_info", "FireflyCodec", "StreamingSynth", "SessionStreamer", "decode_chunk"]

@@ -29,6 +29,13 @@ class GenStats(C.Structure):
                 ("slow_kernel_us", C.c_double), ("fast_kernel_us", C.c_double)]
 
 
+class KvBlobHeader(C.LittleEndianStructure):  # fs_kv_blob_header: the 64 bytes in front of a prefix KV blob's payload
+    _fields_ = [("magic", C.c_char * 8), ("version", C.c_uint32), ("kv_dtype", C.c_uint32), ("n_layer", C.c_int32),
+                ("n_local_heads", C.c_int32), ("head_dim", C.c_int32), ("P", C.c_int32), ("header_bytes", C.c_uint32),
+                ("reserved", C.c_uint32), ("weights_fingerprint", C.c_uint64), ("payload_bytes", C.c_uint64),
+                ("reserved2", C.c_uint64)]
+
+
 FRAME_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32))
 
 # every symbol include/fishrt.h declares (tests/test_abi.py checks the library exports all of them)
@@ -39,6 +46,7 @@ SYMBOLS = ["fs_last_error", "fs_version", "fs_device_count", "fs_lm_create", "fs
            "fs_lm_weights_arena", "fs_lm_weights_adopt", "fs_comm_unique_id", "fs_comm_create", "fs_comm_destroy", "fs_comm_rank", "fs_comm_world", "fs_comm_barrier",
            "fs_comm_all_reduce_f64", "fs_comm_broadcast_weights", "fs_comm_broadcast_prompt_dims", "fs_comm_broadcast_prompts", "fs_comm_all_gather_codes", "fs_lm_session_begin", "fs_lm_session_add", "fs_lm_session_step", "fs_lm_session_poll", "fs_lm_session_release", "fs_lm_session_end",
            "fs_lm_session_prefix_create", "fs_lm_session_prefix_release", "fs_lm_session_add_prefixed", "fs_lm_session_add_ex", "fs_lm_session_add_hidden", "fs_lm_session_poll_hidden", "fs_lm_session_info",
+           "fs_lm_weights_fingerprint", "fs_lm_session_prefix_export", "fs_lm_session_prefix_import",
            "fs_codec_create", "fs_codec_destroy", "fs_codec_load_safetensors", "fs_codec_load_synthetic",
            "fs_codec_decode", "fs_codec_encode", "fs_codec_encode_batch", "fs_codec_sample_rate", "fs_codec_set_precision", "fs_codec_precision", "fs_codec_set_range_check", "fs_codec_range_stats", "fs_codec_stream_begin", "fs_codec_stream_decode", "fs_codec_stream_end", "fs_codec_streams_open", "fs_codec_streams_close", "fs_codec_streams_decode", "fs_codec_streams_decode_ragged", "fs_fp8_quantize_rows", "fs_fp8_decode_table", "fs_selftest", "fs_lm_selftest", "fs_selftest_sample_rows", "fs_selftest_sample_slots", "fs_lm_debug_capture", "fs_lm_debug_read"]
 

@@ -4,6 +4,7 @@
 generate_blocking / generate_static_batch (generate/*.rs); `LM` mirrors the PyO3 class
 (fish_speech_python/src/lm.rs:23-199) minus tokenisation (the caller supplies token ids: SURVEY.md §2 row 7)."""
 import ctypes as C
+import struct
 
 import numpy as np
 
@@ -14,6 +15,47 @@ DTYPES = {"f32": 0, "bf16": 1, "fp8": 2}
 
 def _u32(a):
     return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+KV_BLOB_MAGIC = b"FSKVPFX1"
+_KV_BLOB_HEADER = struct.Struct("<8sIIiiiiIIQQQ")  # fs_kv_blob_header (include/fishrt.h), little-endian, 64 bytes
+_KV_BLOB_FIELDS = ("magic", "version", "kv_dtype", "n_layer", "n_local_heads", "head_dim", "P", "header_bytes", "reserved",
+                   "weights_fingerprint", "payload_bytes", "reserved2")
+_KV_ELEM_BYTES = {0: 4, 1: 2}  # fs_dtype of the KV storage -> bytes per element (FS_F32, FS_BF16; fp8 handles keep a bf16 cache)
+
+
+def prefix_blob_info(blob):
+    """Parse and check the header of a prefix KV blob (Session.export_prefix; include/fishrt.h: fs_kv_blob_header) without a GPU.
+    -> dict of the header fields plus "bytes" (the blob's length).  Raises ValueError naming the field that is wrong: magic, version,
+    header_bytes, bytes (!= 64 + payload_bytes), kv_dtype, the dimensions, payload_bytes (against the dimensions).  What only a handle
+    can judge -- the dimensions against the model, P < max_seq_len, weights_fingerprint -- is left to Session.import_prefix."""
+    blob = bytes(blob) if not isinstance(blob, (bytes, bytearray, memoryview)) else blob
+    n = len(blob)
+    if n < _KV_BLOB_HEADER.size:
+        raise ValueError(f"prefix blob: bytes = {n} is smaller than the 64-byte header")
+    h = dict(zip(_KV_BLOB_FIELDS, _KV_BLOB_HEADER.unpack_from(blob, 0)))
+    if h["magic"] != KV_BLOB_MAGIC:
+        raise ValueError(f"prefix blob: wrong magic {h['magic']!r} (not {KV_BLOB_MAGIC!r})")
+    if h["version"] != 1:
+        raise ValueError(f"prefix blob: unsupported version {h['version']} (this package reads version 1)")
+    if h["header_bytes"] != _KV_BLOB_HEADER.size:
+        raise ValueError(f"prefix blob: header_bytes = {h['header_bytes']}, not 64")
+    if n != _KV_BLOB_HEADER.size + h["payload_bytes"]:
+        raise ValueError(f"prefix blob: bytes = {n} != 64 + payload_bytes = {64 + h['payload_bytes']} (truncated or padded blob)")
+    if h["kv_dtype"] not in _KV_ELEM_BYTES:
+        raise ValueError(f"prefix blob: kv_dtype = {h['kv_dtype']} is no KV storage type (0 f32, 1 bf16)")
+    for k in ("n_layer", "n_local_heads", "head_dim", "P"):
+        if h[k] < 1:
+            raise ValueError(f"prefix blob: {k} = {h[k]} must be >= 1")
+    if h["head_dim"] % 8:
+        raise ValueError(f"prefix blob: head_dim = {h['head_dim']} is no multiple of 8")
+    want = h["n_layer"] * 2 * h["P"] * h["n_local_heads"] * h["head_dim"] * _KV_ELEM_BYTES[h["kv_dtype"]]
+    if h["payload_bytes"] != want:
+        raise ValueError(f"prefix blob: payload_bytes = {h['payload_bytes']} does not match the dimensions "
+                         f"(n_layer * 2 * P * n_local_heads * head_dim elements = {want} bytes)")
+    h["magic"] = h["magic"].decode()
+    h["bytes"] = n
+    return h
 
 
 class DualARTransformer:
@@ -213,6 +255,13 @@ class DualARTransformer:
         _ffi.check(_ffi.lib().fs_lm_weights_adopt(self._h))
         return self
 
+    def weights_fingerprint(self):
+        """64-bit fingerprint of the weight arena (fishrt.h: fs_lm_weights_fingerprint): equal for handles with the same weights in the
+        same storage type, which may exchange prefix KV blobs (Session.export_prefix / import_prefix).  Cached until the next load."""
+        out = C.c_uint64(0)
+        _ffi.check(_ffi.lib().fs_lm_weights_fingerprint(self._h, C.byref(out)))
+        return int(out.value)
+
     def session(self, temp=0.7, top_p=0.9, top_k=50, seed=42, ignore_eos=False, rows=False, repetition_penalty=1.2, per_slot=False, wide=False):
         """continuous batching over this handle's max_batch slots (fishrt.h: fs_lm_session_*): `with lm.session(...) as s:`
         per_slot=True: FS_SESSION_PER_SLOT -- every slot samples like its own generate_blocking call (own settings, seed, repetition penalty).
@@ -361,6 +410,24 @@ class Session:
     def release_prefix(self, prefix):
         """drop the session's reference; the pages go back once no slot uses them any more"""
         _ffi.check(_ffi.lib().fs_lm_session_prefix_release(self.lm._h, int(prefix)))
+
+    def export_prefix(self, prefix):
+        """the K/V rows of a live prefix as bytes (fishrt.h: fs_lm_session_prefix_export; header: prefix_blob_info).  Waits for the
+        prefix's own pass if that is still queued or in flight; changes nothing in the session."""
+        n = C.c_size_t(0)
+        _ffi.check(_ffi.lib().fs_lm_session_prefix_export(self.lm._h, int(prefix), None, C.c_size_t(0), C.byref(n)))
+        buf = C.create_string_buffer(int(n.value))
+        _ffi.check(_ffi.lib().fs_lm_session_prefix_export(self.lm._h, int(prefix), buf, C.c_size_t(n.value), C.byref(n)))
+        return buf.raw[: n.value]
+
+    def import_prefix(self, blob):
+        """a prefix from a blob of export_prefix -- of this handle or of one with the same weights_fingerprint(), in any session kind --
+        without a prefill pass -> prefix id, or None when the KV page pool cannot hold it right now.  A blob that does not fit the handle
+        raises RuntimeError naming the header field.  Afterwards the prefix is a created one in every respect."""
+        blob = bytes(blob)
+        pid = C.c_int(-1)
+        _ffi.check(_ffi.lib().fs_lm_session_prefix_import(self.lm._h, blob, C.c_size_t(len(blob)), C.byref(pid)))
+        return None if pid.value < 0 else int(pid.value)
 
     INFO_KEYS = ("free_pages", "shared_pages", "live_prefixes", "prefill_passes", "tokens_prefilled", "prefix_tokens_reused",
                  "tail_pages_copied", "prefill_us")

@@ -38,6 +38,13 @@ such a request joins the per-slot session instead of waiting for it to drain and
 nucleus-only gets a per-slot session at all.  Handles whose sessions take the request-row kernels (2 / 4 / 8 slots, Fish 1.5) keep their
 limit: a job outside it still runs alone.
 
+Host cache of prefix blobs (`Scheduler(session_prefixes=True, prefix_host_cache_bytes=N)`, off by default).  A session prefix dies with its
+session, and the session is closed at every lull, before every batch-1 job and after every error.  With a byte budget the scheduler keeps
+an LRU `cond_key -> blob` of its own (`Session.export_prefix`): a prefix is exported once, when the per-session LRU evicts it or its
+session is about to close -- not while the job that created it has no frame yet, and not from a session that failed -- and a voice that
+misses the session's map but hits the cache is imported (`Session.import_prefix`: one copy and a scatter) instead of prefilled.  No pages
+for the import falls back to the full prompt, as for a creation; a blob the handle refuses (weights reloaded) is dropped.
+
 Hidden states (`generate_hidden_states`, `handlers/send_hidden_states.rs`: body {text, speaker_id, return_audio} -> a stored zip of
 `hidden_states.npy`, optional `audio.wav`, `metadata.json`).  Its chunk jobs go through the same scheduler with `collect_hidden` set: in a
 session the slot is admitted with `add(..., collect_hidden=True)` and read with `poll_hidden`, outside one the job calls
@@ -124,7 +131,8 @@ class LMState:  # server/lib/state.rs:12-21
 
 class AppState:  # server/lib/state.rs:23-29
     def __init__(self, lm_state, codec, sample_rate=44100, opus_encoder=None, preprocess=preprocess_text, batch_window_s=0.002,
-                 continuous=True, auto_batch=False, session_prefixes=False, per_slot_sampling=False, wide_sampling=False):
+                 continuous=True, auto_batch=False, session_prefixes=False, per_slot_sampling=False, wide_sampling=False,
+                 prefix_host_cache_bytes=0):
         self.lm, self.codec, self.sample_rate, self.opus_encoder, self.preprocess = lm_state, codec, sample_rate, opus_encoder, preprocess
         self.codec_lock = threading.Lock()  # a codec handle takes one call at a time (include/fishrt.h); requests vocode from their own threads
         self.auto_batch = auto_batch  # True: every chunk may join the batching session (batch sampling semantics) without `batch_size`
@@ -132,8 +140,11 @@ class AppState:  # server/lib/state.rs:23-29
         # it per chunk.  A prefix prefilled on its own may round differently from the full prompt and flip a near-tie, so it stays opt-in.
         # per_slot_sampling (off by default): per-request sampler semantics in sessions + request-level sampling fields (module docstring)
         # wide_sampling (off by default; needs per_slot_sampling): per-slot sessions also take nucleus-only / top_k > 256 settings
+        # prefix_host_cache_bytes (0 = off; needs session_prefixes): the scheduler keeps the K/V of conditioning prefixes as host blobs
+        # (Session.export_prefix) across sessions, up to this many bytes, and imports them instead of prefilling the voice again.  An imported
+        # prefix carries the bits of a created one, so the caveat of session_prefixes is unchanged.
         self.scheduler = Scheduler(lm_state, batch_window_s, continuous, session_prefixes=session_prefixes, per_slot_sampling=per_slot_sampling,
-                                   wide_sampling=wide_sampling)
+                                   wide_sampling=wide_sampling, prefix_host_cache_bytes=prefix_host_cache_bytes)
 
 
 class _Job:
@@ -156,9 +167,13 @@ class Scheduler:
     PREFIX_LRU = 8  # conditioning prefixes kept per session (session_prefixes)
 
     def __init__(self, lm_state, batch_window_s=0.002, continuous=True, step_frames=8, session_prefixes=False, per_slot_sampling=False,
-                 wide_sampling=False):
+                 wide_sampling=False, prefix_host_cache_bytes=0):
         if wide_sampling and not per_slot_sampling:
             raise ValueError("wide_sampling=True needs per_slot_sampling=True (FS_SESSION_WIDE_SAMPLER is a per-slot session flag)")
+        if prefix_host_cache_bytes and not session_prefixes:
+            raise ValueError("prefix_host_cache_bytes needs session_prefixes=True (it keeps the blobs of session prefixes)")
+        if prefix_host_cache_bytes < 0:
+            raise ValueError("prefix_host_cache_bytes must not be negative")
         self.s, self.q, self.window = lm_state, queue.Queue(), batch_window_s
         self.continuous, self.step_frames = continuous, step_frames
         self.session_prefixes = session_prefixes
@@ -166,10 +181,18 @@ class Scheduler:
         self.wide_sampling = bool(wide_sampling)
         self.sess_mode = None  # "rows" | "per_slot" | "plain" while a session is open
         self.prefixes = collections.OrderedDict()  # session_prefixes: cond_key -> prefix id of the open session (LRU order)
+        # prefix_host_cache_bytes: cond_key -> blob (LRU order, bounded by the byte budget).  It belongs to the scheduler, not to a
+        # session: blobs outlive every session.close().  prefix_makers: cond_key -> the job whose admission created the prefix of the
+        # open session (a prefix is not exported while that job is still prefilling)
+        self.host_budget = int(prefix_host_cache_bytes)
+        self.host_blobs = collections.OrderedDict()
+        self.prefix_makers = {}
         self.cached_key = None
         self.stats = dict(jobs=0, single=0, batched_rows=0, batches=0, prefix_hits=0, rerolls=0)
         if session_prefixes:
             self.stats.update(session_prefix_hits=0, session_prefix_tokens_saved=0)
+        if self.host_budget:
+            self.stats.update(session_prefix_imports=0, session_prefix_import_tokens=0, prefix_host_cache_bytes=0)
         if per_slot_sampling:
             self.stats.update(per_slot_sessions=0)
         if wide_sampling:
@@ -279,6 +302,7 @@ class Scheduler:
                             pass
                     else:
                         if sess is not None:  # idle: give the handle back (its other entry points work between bursts)
+                            self._stash_prefixes(sess)
                             sess.close()
                             sess = None
                             self.prefixes.clear()
@@ -287,6 +311,7 @@ class Scheduler:
                         held, stopping = None, True
                 if stopping and not live:
                     if sess is not None:
+                        self._stash_prefixes(sess)
                         sess.close()
                         self.prefixes.clear()
                     return
@@ -297,6 +322,7 @@ class Scheduler:
                     if not joins or lone:
                         if not live:  # drain first; then the batch-1 path
                             if sess is not None:
+                                self._stash_prefixes(sess)
                                 sess.close()
                                 sess = None
                                 self.prefixes.clear()
@@ -357,6 +383,7 @@ class Scheduler:
                             self.stats["peak_live"] = max(self.stats.get("peak_live", 0), len(live))
                             continue  # admit more before stepping
                         if not live:  # nothing will ever free a slot / KV pages for it: the batch-1 path (or its error) instead of spinning
+                            self._stash_prefixes(sess)
                             sess.close()
                             sess = None
                             self.prefixes.clear()
@@ -374,6 +401,7 @@ class Scheduler:
                             hidden = sess.poll_hidden(slot) if live[slot].collect_hidden else None
                             sess.release(slot)
                             jb = live.pop(slot)
+                            jb.sess_slot = None
                             try:  # (jb has left `live`: from here on fail_all no longer sees it, so its future is resolved right here)
                                 if codes.shape[1] >= self.s.max_new_tokens:  # speech.rs:41-61 "Failed generation suspected. Rerolling once":
                                     self.stats["rerolls"] += 1               # the re-roll takes the batch-1 path once the session has drained
@@ -395,7 +423,56 @@ class Scheduler:
                 except BaseException:
                     pass
                 sess = None
-                self.prefixes.clear()
+                self.prefixes.clear()  # (no export from a session that failed: its device state is not trusted)
+                self.prefix_makers.clear()
+
+    # -- host cache of prefix blobs (prefix_host_cache_bytes)
+    def _settled(self, sess, key):
+        """has the prefix's own pass long finished?  Not while the job whose admission created it is still prefilling (no frame yet)"""
+        jm = self.prefix_makers.get(key)
+        if jm is None or jm.future.done():
+            return True
+        slot = getattr(jm, "sess_slot", None)
+        return slot is not None and sess.poll(slot, codes=False)[0] > 0
+
+    def _stash(self, sess, key, pid):
+        """export prefix `pid` of the open session into the host cache -- at most once per voice: a voice that is cached (exported
+        earlier, or imported from the cache) is not exported again"""
+        if not self.host_budget or key in self.host_blobs or not self._settled(sess, key):
+            return
+        blob = sess.export_prefix(pid)
+        if len(blob) > self.host_budget:
+            return
+        self.host_blobs[key] = blob
+        self.stats["prefix_host_cache_bytes"] += len(blob)
+        while self.stats["prefix_host_cache_bytes"] > self.host_budget:
+            _, old = self.host_blobs.popitem(last=False)
+            self.stats["prefix_host_cache_bytes"] -= len(old)
+
+    def _stash_prefixes(self, sess):
+        """the session is about to close: keep its prefixes (least recently used first, so that the byte budget drops those first)"""
+        if self.host_budget:
+            for key, pid in list(self.prefixes.items()):
+                self._stash(sess, key, pid)
+        self.prefix_makers.clear()
+
+    def _import_prefix(self, sess, j):
+        """the job's voice from the host cache -> prefix id, or None (not cached, no KV pages right now, or a blob this handle refuses --
+        weights reloaded since: dropped)"""
+        blob = self.host_blobs.get(j.cond_key) if self.host_budget else None
+        if blob is None:
+            return None
+        self.host_blobs.move_to_end(j.cond_key)
+        try:
+            pid = sess.import_prefix(blob)
+        except RuntimeError:
+            del self.host_blobs[j.cond_key]
+            self.stats["prefix_host_cache_bytes"] -= len(blob)
+            return None
+        if pid is not None:
+            self.stats["session_prefix_imports"] += 1
+            self.stats["session_prefix_import_tokens"] += int(j.cond.shape[1])
+        return pid
 
     def _session_add(self, sess, j):
         """admit job j into the session -> (slot or None, whether it joined on an existing prefix).  session_prefixes: the job's
@@ -414,15 +491,26 @@ class Scheduler:
         if pid is not None:
             self.prefixes.move_to_end(j.cond_key)
         else:
-            pid = sess.add_prefix(j.cond)
-            if pid is None:
+            cached = self.host_budget and j.cond_key in self.host_blobs
+            pid = self._import_prefix(sess, j) if cached else None
+            if pid is None and cached and j.cond_key in self.host_blobs:  # (no KV pages for the import: as for a creation)
                 return sess.add(j.full_prompt(), self.s.max_new_tokens, **kw), False
+            if pid is None:
+                pid = sess.add_prefix(j.cond)
+                if pid is None:
+                    return sess.add(j.full_prompt(), self.s.max_new_tokens, **kw), False
+                if self.host_budget:
+                    self.prefix_makers[j.cond_key] = j
             self.prefixes[j.cond_key] = pid
             j.made_prefix = True
             while len(self.prefixes) > self.PREFIX_LRU:  # (slots still on an evicted prefix keep its pages until they are released)
-                _, old = self.prefixes.popitem(last=False)
+                key, old = self.prefixes.popitem(last=False)
+                self._stash(sess, key, old)
+                self.prefix_makers.pop(key, None)
                 sess.release_prefix(old)
-        return sess.add(j.body, self.s.max_new_tokens, prefix=pid, **kw), hit
+        slot = sess.add(j.body, self.s.max_new_tokens, prefix=pid, **kw)
+        j.sess_slot = slot
+        return slot, hit
 
     def _codes_out(self, codes):
         if self.s.model_type != fprompt.FISH_1_5:  # speech.rs:63-68: Fish <= 1.4 codes are shifted by one

@@ -388,6 +388,57 @@ int fs_lm_session_poll_hidden(fs_lm_t* lm, int slot, size_t first_row, float* hi
  * counters since fs_lm_session_begin */
 int fs_lm_session_info(fs_lm_t* lm, int64_t out[8]);
 
+/* ---- prefix KV blobs (no reference counterpart).  The K/V rows of a shared prefix are a pure function of (weights, KV storage type, prefix
+ * tokens): fs_lm_session_prefix_export hands them out as bytes, fs_lm_session_prefix_import puts them back into pages of any later
+ * session -- of this handle or of another one with the same weights -- without running the slow transformer.
+ * A blob is one 64-byte header followed by the payload; everything little-endian.
+ * Payload: the KV elements (kv_dtype) as [n_layer][2 (K, then V)][P][n_local_heads][head_dim], position-major: exactly the P rows, nothing
+ * of the unused part of the last page, and nothing that depends on the page size, max_batch, the pool size or the session kind.  K is
+ * stored as the cache holds it: AFTER RoPE, at the absolute positions 0 .. P-1; a prefix always starts at position 0, so the rows are
+ * reusable as they are.  No payload checksum: callers that persist blobs wrap their own. */
+typedef struct fs_kv_blob_header {
+    char magic[8];                 /* "FSKVPFX1" */
+    uint32_t version;              /* 1 */
+    uint32_t kv_dtype;             /* fs_dtype of the KV storage: FS_BF16 on every handle that takes sessions */
+    int32_t n_layer, n_local_heads, head_dim, P;
+    uint32_t header_bytes;         /* 64 */
+    uint32_t reserved;             /* 0 */
+    uint64_t weights_fingerprint;  /* fs_lm_weights_fingerprint of the exporting handle */
+    uint64_t payload_bytes;        /* n_layer * 2 * P * n_local_heads * head_dim * sizeof(element) */
+    uint64_t reserved2;            /* 0 */
+} fs_kv_blob_header;
+/* 64-bit fingerprint of the handle's weight arena (fs_lm_weights_arena: n bytes = n / 4 little-endian 32-bit words w[0 .. n/4)), integer
+ * arithmetic only, all of it mod 2^64:
+ *     S = sum_i w[i] * (2 i + 1)
+ *     z = S ^ ((n / 4) * 0x9E3779B97F4A7C15);  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *     fingerprint = z ^ (z >> 31)
+ * S is a sum of integers, so it is bit-identical for any grid size and any order of the device's atomic adds; the weights 2 i + 1 are
+ * odd and distinct, so S changes when two unequal words swap places ((w[a] - w[b]) * 2 (a - b) != 0 mod 2^64 for arenas below 2^32 words);
+ * the last three lines are a bijection (the splitmix64 finaliser).  Computed on the device at the first call that needs it (this one, an
+ * export or an import), cached per handle, invalidated by fs_lm_load_* and fs_lm_weights_adopt.  A bf16 and an fp8 handle of the same
+ * checkpoint have different arenas, hence different fingerprints -- and different K/V. */
+int fs_lm_weights_fingerprint(fs_lm_t* lm, uint64_t* out);
+/* The blob of live prefix `prefix_id` of the open session: *bytes (nullable) = 64 + payload_bytes; blob_out NULL queries the size only,
+ * cap < *bytes is an error.  If the prefix's own pass (creation or import) is still queued or in flight the call first lets it finish and
+ * activates it, as fs_lm_session_step would.  The rows are gathered on the prefill stream into the handle's staging buffer and copied to
+ * blob_out; the call returns once the bytes are there.  It does not touch the decode stream, any slot's codes, any page reference or any
+ * counter of fs_lm_session_info.  Valid in every session kind, on bf16 and fp8 handles.
+ * Staging: ONE grow-only device buffer per handle, freed with the handle; its size is the largest payload moved so far -- one export's
+ * payload, or the summed payloads of the imports launched as one pass. */
+int fs_lm_session_prefix_export(fs_lm_t* lm, int prefix_id, void* blob_out, size_t cap, size_t* bytes);
+/* A prefix from a blob.  The whole header is validated before any page is taken and before any byte moves; each of these is an error
+ * that names the field and leaves the pool as it was: magic, version, header_bytes, bytes == 64 + payload_bytes, kv_dtype, n_layer /
+ * n_local_heads / head_dim against the handle, 1 <= P < max_seq_len, payload_bytes against the dimensions, weights_fingerprint against the
+ * handle's.  Then the call behaves like fs_lm_session_prefix_create: the ceil(P / 64) pages are taken now, *prefix_id = -1 (not an
+ * error) when the pool cannot hold them right now, and the prefix is the same object afterwards -- fs_lm_session_add_prefixed, the shared
+ * full pages, the copied last page, release, fs_lm_session_end and fs_lm_session_info treat it as a created one.  The payload is copied
+ * before the call returns (the caller may free the blob at once); the host-to-device copy and the scatter into the pages are queued on
+ * the prefill stream as a pass of their own, ahead of every creation and every add queued with them, and activated through the same
+ * event as a creating pass -- so an add with a one-column body on it, which prefills nothing, cannot go live before the rows are in
+ * place.  No slow-transformer pass runs: the prefill passes / tokens prefilled counters of fs_lm_session_info do not move.
+ * Blobs are portable between session kinds and between handles with equal fingerprints. */
+int fs_lm_session_prefix_import(fs_lm_t* lm, const void* blob, size_t bytes, int* prefix_id);
+
 /* timing of the last generate call, measured with HIP events on the handle's stream (the reference prints the
  * same quantities: single_batch.rs:233-246,291-304) */
 typedef struct fs_gen_stats {
