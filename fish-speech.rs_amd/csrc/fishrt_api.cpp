@@ -97,6 +97,12 @@ int fs_selftest_sample_slots(int device_id, const float* logits, int S, int R, i
         fs::debug_sample_slots(device_id, logits, S, R, n, cfgs.data(), seeds, out, words_used);
     })
 }
+int fs_selftest_score_rows(int device_id, const float* logits, int S, int n, const uint32_t* targets, int exclude0, float* logprob_out,
+                           float* top_logprob_out, uint32_t* top_out, float* row_out) {
+    FS_ARG(logits && targets, "null argument");
+    FS_ARG(S >= 1 && n >= 2 && n <= 2048, "bad score test shape (S >= 1; 2 <= n <= 2048)");
+    FS_TRY(fs::debug_score_rows(device_id, logits, S, n, targets, exclude0, logprob_out, top_logprob_out, top_out, row_out))
+}
 
 // ---- replica fan-out over RCCL (fs_comm.h)
 int fs_comm_unique_id(uint8_t id_out[FS_COMM_ID_BYTES]) { FS_ARG(id_out, "null argument"); FS_TRY(fs::Comm::unique_id(id_out)) }
@@ -270,6 +276,16 @@ int fs_lm_session_add_hidden(fs_lm_t* lm, int prefix_id, const uint32_t* prompt,
 int fs_lm_session_poll_hidden(fs_lm_t* lm, int slot, size_t first_row, float* hidden_out, size_t cap_rows, size_t* n_rows) {
     FS_ARG(lm, "null argument");
     FS_TRY(lm->impl->session_poll_hidden(slot, first_row, hidden_out, cap_rows, n_rows))
+}
+int fs_lm_session_add_scored(fs_lm_t* lm, int prefix_id, const uint32_t* prompt, int L, const uint32_t* frames, int N, int collect_hidden,
+                             int* slot) {
+    FS_ARG(lm && prompt && frames && slot, "null argument");
+    FS_TRY(*slot = lm->impl->session_add_scored(prefix_id, prompt, L, frames, N, collect_hidden))
+}
+int fs_lm_session_poll_scores(fs_lm_t* lm, int slot, size_t first_row, float* logprob, float* top_logprob, uint32_t* top, float* eos_logprob,
+                              size_t cap_rows, size_t* n_rows) {
+    FS_ARG(lm, "null argument");
+    FS_TRY(lm->impl->session_poll_scores(slot, first_row, logprob, top_logprob, top, eos_logprob, cap_rows, n_rows))
 }
 int fs_lm_session_info(fs_lm_t* lm, int64_t out[8]) { FS_ARG(lm && out, "null argument"); FS_TRY(lm->impl->session_info(out)) }
 int fs_lm_last_stats(fs_lm_t* lm, fs_gen_stats* out) { FS_ARG(lm && out, "null argument"); FS_TRY(*out = lm->impl->last_stats()) }

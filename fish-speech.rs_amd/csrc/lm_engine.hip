@@ -894,6 +894,16 @@ class LM final : public LMBase {
         FS_REQUIRE(!sess_active_, "a session is already open on this handle");
         FS_REQUIRE(RowKernels<WT>::has_mfma_prefill() && B_ <= kRows && a_.dim % 128 == 0 && a_.intermediate_size % 128 == 0 && a_.num_codebooks <= 8,
                    "sessions need the MFMA row path (bf16 / fp8 handle)");
+        // FS_SESSION_SCORE: the step graphs of the session carry one score node in front of each per-slot sampler node (k_score_slots);
+        // slots admitted with fs_lm_session_add_scored are forced through them, every other slot is untouched
+        const bool score = (flags & FS_SESSION_SCORE) != 0;
+        if (score) {
+            if (flags & FS_SESSION_ROWS) throw Error("FS_SESSION_SCORE is valid only together with FS_SESSION_PER_SLOT: not with FS_SESSION_ROWS");
+            if (!(flags & FS_SESSION_PER_SLOT)) throw Error("FS_SESSION_SCORE is valid only together with FS_SESSION_PER_SLOT: not alone");
+            if (legacy_ || !t_.has_semantic_end)
+                throw Error("FS_SESSION_SCORE needs the Fish 1.5 token layout (has_semantic_end != 0): a Fish <= 1.4 handle has no slow-token distribution to score");
+            FS_REQUIRE(a_.num_codebooks == 8, "FS_SESSION_SCORE needs num_codebooks == 8 (the score record holds 9 decisions per iteration)");
+        }
         // Fish <= 1.4 handles (no semantic range: the slow token is the 2-way {pad, im_end} draw): only the per-slot samplers define that
         // decision for a slot (k_sample_slow_slots, as the slot's own fs_lm_generate call); the lock-step sampler and the request-row
         // kernels do not
@@ -921,6 +931,7 @@ class LM final : public LMBase {
         }
         sess_slots_ = false;
         sess_wide_ = false;
+        sess_score_ = false;
         std::unique_lock<PersistLock> rows_lock;
         struct RowsGuard {  // anything thrown below leaves the handle out of row mode (the local lock releases itself)
             bool& flag; bool armed = true;
@@ -988,6 +999,8 @@ class LM final : public LMBase {
         sess_hid_want_.assign(B_, 0);
         sess_hid_live_ = 0;
         FS_HIP(hipMemsetAsync(d_hid_tab_.p, 0, d_hid_tab_.n, st_));
+        sc_book_.begin(B_, a_.num_codebooks + 1);
+        FS_HIP(hipMemsetAsync(d_sc_tab_.p, 0, d_sc_tab_.n, st_));
         for (auto& v : sess_count_) v = 0;
         sess_pf_ms_ = 0.0;
         sess_timed_ = false;
@@ -999,6 +1012,7 @@ class LM final : public LMBase {
         if (sess_rows_) sess_plock_ = std::move(rows_lock);
         sess_slots_ = per_slot;
         sess_wide_ = wide;
+        sess_score_ = score;
         sess_active_ = true;
     }
     // what a slot of a FS_SESSION_PER_SLOT session may sample with: the boundary of the in-launch samplers (fishrt.h: fs_lm_generate)
@@ -1112,6 +1126,83 @@ class LM final : public LMBase {
         }
         if (n_rows) *n_rows = n;
     }
+    // fs_lm_session_add_scored: a slot whose N iterations are forced to `frames` [C + 1][N] and scored (k_score_slots in front of each of
+    // the step's sampler nodes).  Everything is validated before anything is taken or queued; the buffer (records + targets, one
+    // allocation) is taken BEFORE the add and goes back when the add is refused; the device table learns of it at activation, like a
+    // hidden-state collector's.  The slot's SampleCfg is the session's made greedy with no repetition penalty, so its sampler nodes pick
+    // the +INFINITY the score node leaves at the target; a seed of its own only gives it a prefill pass of its own (it draws no word).
+    int session_add_scored(int prefix_id, const uint32_t* prompt, int L, const uint32_t* frames, int N, int collect_hidden) override {
+        use_device();
+        FS_REQUIRE(sess_active_, "no open session");
+        FS_REQUIRE(sess_score_, "fs_lm_session_add_scored needs FS_SESSION_SCORE (begin the session with FS_SESSION_PER_SLOT | FS_SESSION_SCORE)");
+        FS_REQUIRE(L >= 1, "empty prompt");
+        FS_REQUIRE(N >= 1, "frames: N must be >= 1");
+        const int C1 = a_.num_codebooks + 1;
+        for (int i = 0; i < N; ++i) {
+            const uint32_t tok = frames[i];
+            if (tok < t_.semantic_start_id || tok >= (uint32_t)a_.vocab_size)
+                throw Error("frames[0][" + std::to_string(i) + "] = " + std::to_string(tok) + ": a forced slow token must lie in [semantic_start_id, vocab_size) "
+                            "(<|im_end|> and text tokens cannot be scored as a frame)");
+            for (int r = 1; r < C1; ++r)
+                if (frames[(size_t)r * N + i] >= (uint32_t)a_.codebook_size)
+                    throw Error("frames[" + std::to_string(r) + "][" + std::to_string(i) + "] = " + std::to_string(frames[(size_t)r * N + i]) + ": a code must be < codebook_size");
+        }
+        const long long Lt = (long long)L + (prefix_id >= 0 ? live_prefix(prefix_id).P : 0);
+        if (Lt + N - 1 > a_.max_seq_len)
+            throw Error("L + N - 1 = " + std::to_string(Lt + N - 1) + " exceeds max_seq_len (L counts the prefix; a scored sequence is never clipped)");
+        const int max_new = (int)(Lt + N - 2);  // exactly N iterations (iter_budget)
+        ScoreBuf buf = sc_book_.take(N);
+        const uint64_t seed = sess_seed_ + (uint64_t)sess_adds_;
+        int b = -1;
+        try {
+            b = collect_hidden ? session_add_hidden(prefix_id, prompt, L, max_new, nullptr, &seed) : session_add_ex(prefix_id, prompt, L, max_new, nullptr, &seed);
+        } catch (...) { sc_book_.put(buf); throw; }
+        if (b < 0) { sc_book_.put(buf); return b; }
+        PendingAdd& pa = sess_queue_.back();
+        pa.has_cfg = true;
+        pa.cfg = sess_cfg_;
+        pa.cfg.temp = 0.f; pa.cfg.rep_pen = 1.f;
+        pa.sc = buf;
+        pa.sc_targets.resize((size_t)N * C1);  // [N][C + 1]: one iteration's 9 targets side by side
+        for (int i = 0; i < N; ++i)
+            for (int r = 0; r < C1; ++r) pa.sc_targets[(size_t)i * C1 + r] = frames[(size_t)r * N + i];
+        sc_book_.admitted(b);
+        return b;
+    }
+    void session_poll_scores(int slot, size_t first_row, float* logprob, float* top_logprob, uint32_t* top, float* eos_logprob, size_t cap_rows,
+                             size_t* n_rows) override {
+        use_device();
+        FS_REQUIRE(sess_active_, "no open session");
+        FS_REQUIRE(sess_score_, "fs_lm_session_poll_scores needs FS_SESSION_SCORE (begin the session with FS_SESSION_PER_SLOT | FS_SESSION_SCORE)");
+        FS_REQUIRE(slot >= 0 && slot < B_ && sess_left_[slot] != -1, "not a live session slot");
+        FS_REQUIRE(sc_book_.wanted(slot), "the slot is not a scoring slot (it was not admitted with fs_lm_session_add_scored)");
+        const ScoreSlot& e = sc_book_.entry(slot);
+        const size_t n = sess_left_[slot] == -2 ? 0 : (size_t)e.count;  // (-2: still prefilling)
+        if ((logprob || top_logprob || top || eos_logprob) && first_row < n) {
+            const size_t m = std::min(n - first_row, cap_rows), C1 = (size_t)a_.num_codebooks + 1;
+            std::vector<float> rec(m * SCORE_REC_WORDS);
+            if (m) FS_HIP(hipMemcpyAsync(rec.data(), e.rec + first_row * SCORE_REC_WORDS, sizeof(float) * rec.size(), hipMemcpyDeviceToHost, st_));
+            FS_HIP(hipStreamSynchronize(st_));
+            for (size_t i = 0; i < m; ++i) {
+                const float* r = rec.data() + i * SCORE_REC_WORDS;
+                for (size_t d = 0; d < C1; ++d) {
+                    if (logprob) logprob[i * C1 + d] = r[d];
+                    if (top_logprob) top_logprob[i * C1 + d] = r[9 + d];
+                    if (top) std::memcpy(&top[i * C1 + d], &r[18 + d], sizeof(uint32_t));
+                }
+                if (eos_logprob) eos_logprob[i] = r[27];
+            }
+        }
+        if (n_rows) *n_rows = n;
+    }
+    // the slot stops being scored: null table entry (on the engine stream: ahead of the next step), buffer back to the pool
+    void drop_score_slot(int b) {
+        if (!sc_book_.drop(b)) return;
+        FS_HIP(hipMemcpyAsync(d_sc_tab_.as<ScoreSlot>() + b, &sc_book_.entry(b), sizeof(ScoreSlot), hipMemcpyHostToDevice, st_));
+        FS_HIP(hipStreamSynchronize(st_));
+    }
+    static void* sc_alloc(size_t n) { void* p = nullptr; return hipMalloc(&p, n) == hipSuccess ? p : nullptr; }
+    static void sc_free(void* p) { (void)hipFree(p); }
     void park_slot(int b) {
         SeqState ss = {};
         ss.done = sess_rows_ ? 2 : 1; ss.frame = 1;  // (rows mode: a terminated row is skipped by the row kernels altogether)
@@ -1147,6 +1238,8 @@ class LM final : public LMBase {
         uint64_t seed = 0;
         float* hid = nullptr;  // fs_lm_session_add_hidden: the slot's row buffer [hid_cap][dim], handed to the device table at activation
         int hid_cap = 0;
+        ScoreBuf sc;                       // fs_lm_session_add_scored: the slot's records + targets buffer, handed to the device table at activation
+        std::vector<uint32_t> sc_targets;  // ... and the staged targets [n_iter][C + 1], copied into the buffer then
         std::vector<uint32_t> prompt;
         int rows() const { return import_kv ? 0 : (create ? L : L - start - 1); }   // tokens this member runs through the slow transformer
         int cols() const { return create ? L : L - start; }       // columns of `prompt`
@@ -1592,6 +1685,12 @@ class LM final : public LMBase {
                 FS_HIP(hipMemcpyAsync(d_hid_tab_.as<HidSlot>() + b, &sess_hid_[b], sizeof(HidSlot), hipMemcpyHostToDevice, st_));
                 ++sess_hid_live_;
             }
+            if (pa.sc.p) {  // the slot is scored from its first iteration on: targets into its buffer, table entry with count 0
+                FS_REQUIRE(pa.n_iter <= pa.sc.cap && pa.sc_targets.size() == (size_t)pa.n_iter * C1, "score buffer shorter than the slot's iterations");
+                FS_HIP(hipMemcpyAsync(ScoreBook::targets_of(pa.sc), pa.sc_targets.data(), sizeof(uint32_t) * pa.sc_targets.size(), hipMemcpyHostToDevice, st_));
+                const ScoreSlot& e = sc_book_.activate(b, pa.sc);
+                FS_HIP(hipMemcpyAsync(d_sc_tab_.as<ScoreSlot>() + b, &e, sizeof(ScoreSlot), hipMemcpyHostToDevice, st_));
+            }
             sess_left_[b] = pa.n_iter;
             sess_pos_[b] = Lp;
         }
@@ -1678,7 +1777,12 @@ class LM final : public LMBase {
             // (a slot that sampled <|im_end|> inside the chunk froze itself on the device; the host learns it below)
             FS_HIP(hipMemcpyAsync(sess_hs_.data(), state(0), sizeof(SeqState) * B_, hipMemcpyDeviceToHost, st_));
             if (sess_hid_live_ > 0) FS_HIP(hipMemcpyAsync(sess_hid_.data(), d_hid_tab_.p, sizeof(HidSlot) * B_, hipMemcpyDeviceToHost, st_));  // (the row counts)
+            if (sc_book_.live() > 0) {
+                sess_sc_stage_.resize(B_);
+                FS_HIP(hipMemcpyAsync(sess_sc_stage_.data(), d_sc_tab_.p, sizeof(ScoreSlot) * B_, hipMemcpyDeviceToHost, st_));  // (the record counts)
+            }
             FS_HIP(hipStreamSynchronize(st_));
+            if (sc_book_.live() > 0) sc_book_.refresh_counts(sess_sc_stage_.data());
             // a spin timeout inside the chunk (the joining prefill shares the CUs the persistent launches need co-resident) means the slots'
             // codes are garbage: raise instead of handing them out; the caller ends the session (the handle is off the row path afterwards)
             if (sess_rows_) rows_check_ctl(/*include_b1_fast=*/false);
@@ -1723,6 +1827,7 @@ class LM final : public LMBase {
         park_slot(slot);
         drop_hid_slot(slot);
         sess_hid_want_[slot] = 0;
+        drop_score_slot(slot);
         sess_left_[slot] = -1;
     }
     void session_end() override {
@@ -1733,10 +1838,13 @@ class LM final : public LMBase {
             for (const PendingAdd& pa : *q) {
                 if (pa.tail >= 0) put_page(pa.tail);
                 if (pa.hid) put_hid_buf(pa.hid, pa.hid_cap);
+                sc_book_.put(pa.sc);
             }
         for (HidSlot& h : sess_hid_) { if (h.rows) put_hid_buf(h.rows, h.cap); h = HidSlot{}; }
         sess_hid_live_ = 0;
         if (d_hid_tab_.p) FS_HIP(hipMemsetAsync(d_hid_tab_.p, 0, d_hid_tab_.n, st_));
+        sc_book_.end();
+        if (d_sc_tab_.p) FS_HIP(hipMemsetAsync(d_sc_tab_.p, 0, d_sc_tab_.n, st_));
         sess_flight_.clear(); sess_queue_.clear();
         for (int b = 0; b < B_; ++b) truncate(b, 0);
         for (SessPrefix& px : sess_prefixes_) drop_prefix_pages(px);  // (live or not: the session's references end with it)
@@ -1748,6 +1856,7 @@ class LM final : public LMBase {
         sess_active_ = false;
         sess_slots_ = false;
         sess_wide_ = false;
+        sess_score_ = false;
         sess_released_frames_ = 0;
         if (sess_rows_) check_ctl({&d_rctl_s_, &d_rctl_f_}, nullptr, nullptr);  // (a session that ended on an error: reset only)
         sess_rows_ = false;
@@ -2438,6 +2547,8 @@ class LM final : public LMBase {
         FS_HIP(hipMemcpy(d_fast_table_.p, tb.data(), sizeof(int) * B_, hipMemcpyHostToDevice));
         d_hid_tab_.alloc(sizeof(HidSlot) * B_);
         FS_HIP(hipMemset(d_hid_tab_.p, 0, d_hid_tab_.n));
+        d_sc_tab_.alloc(sizeof(ScoreSlot) * B_);
+        FS_HIP(hipMemset(d_sc_tab_.p, 0, d_sc_tab_.n));
     }
     // one static-batch frame for B rows: x rows (d_pfx_) hold the embedded inputs of position state(0)->pos
     void enqueue_batch_frame(int B) {
@@ -2464,6 +2575,10 @@ class LM final : public LMBase {
         if (capt) launch_cap_rows_logits(d_lrows_.as<float>(), ld_slow_, n_audio_, state(0), d_cfg_.as<SampleCfg>(), B, d_rcap_.as<float>(), cap_frames_, 0, st_);
         // folded steps: the sampler that writes a fast-decoder input row also leaves its first layer's normalised GEMM input (no k_prep node)
         const float* prep_g = fold && a_.dim <= 1024 ? fast_[0].attn_norm : nullptr;
+        // FS_SESSION_SCORE: one score node in front of each per-slot sampler node, behind the capture of the raw row (null table entries
+        // exit at once, so the one captured graph serves every mix of scoring and generating slots)
+        const bool score = slots && sess_score_;
+        if (score) launch_score_slots(d_sc_tab_.as<ScoreSlot>(), state(0), d_scfg_.as<SampleCfg>(), d_lrows_.as<float>(), ld_slow_, n_audio_, 0, C, B, st_);
         if (slots)
             SampleKernels<WT>::sample_slow_slots(d_, d_lrows_.as<float>(), ld_slow_, n_audio_, d_scfg_.as<SampleCfg>(), d_srng_.as<SlotRng>(), B, state(0),
                                                  cs.X, d_xfrows_.as<float>(), st_, prep_g, cs.A, fold ? d_epoch_.as<uint32_t>() : nullptr,
@@ -2506,6 +2621,8 @@ class LM final : public LMBase {
             RowsCtx nf = fast_ctx(cbi + 1);
             const float* prep_f = nf.qkv0_tbl ? nullptr : prep_g;
             nf.first_prepped = prep_f != nullptr;
+            if (score) launch_score_slots(d_sc_tab_.as<ScoreSlot>(), state(0), d_scfg_.as<SampleCfg>(), d_lfast_.as<float>(), a_.codebook_size, a_.codebook_size,
+                                          1 + cbi, C, B, st_);
             if (slots) {
                 RepPenState rp0 = slot_rp(0);
                 SampleKernels<WT>::sample_fast_slots(d_, d_lfast_.as<float>(), cbi, C, a_.codebook_size, d_scfg_.as<SampleCfg>(), d_srng_.as<SlotRng>(), rp0,
@@ -2540,7 +2657,8 @@ class LM final : public LMBase {
         drop_batch_graphs();
     }
     hipGraphExec_t batch_graph(int B) {
-        const int key = (sess_active_ ? 1 << 24 : 0) + (rows_par_ ? 1 << 25 : 0) + (sess_active_ && sess_slots_ ? 1 << 26 : 0) + (sess_active_ && sess_slots_ && sess_wide_ ? 1 << 27 : 0) + B * 1024 + nc_launch_;
+        const int key = (sess_active_ ? 1 << 24 : 0) + (rows_par_ ? 1 << 25 : 0) + (sess_active_ && sess_slots_ ? 1 << 26 : 0) + (sess_active_ && sess_slots_ && sess_wide_ ? 1 << 27 : 0) +
+                        (sess_active_ && sess_slots_ && sess_score_ ? 1 << 28 : 0) + B * 1024 + nc_launch_;
         auto it = batch_graphs_.find(key);
         if (it != batch_graphs_.end()) return it->second;
         {   // the co-residency query of the folded step (rows_fold_ok -> occupancy API) is answered once, OUTSIDE stream capture
@@ -2992,6 +3110,12 @@ class LM final : public LMBase {
     std::vector<char> sess_hid_want_;
     int sess_hid_live_ = 0;
     std::vector<std::pair<float*, int>> hid_pool_;
+    // scoring slots (fs_lm_session_add_scored): the device table the step's k_score_slots nodes read (allocated once per handle, like
+    // d_hid_tab_), its host mirror + the buffer pool (fs_score_book.h), and the landing place of the end-of-chunk copy of the counts
+    bool sess_score_ = false;  // FS_SESSION_SCORE (the session's step graphs carry the 9 score nodes)
+    DevBuf d_sc_tab_;
+    ScoreBook sc_book_{&sc_alloc, &sc_free};
+    std::vector<ScoreSlot> sess_sc_stage_;
     SeqState sess_stage_ = {};
     hipStream_t st_pf_ = nullptr;
     hipEvent_t ev_pf_ = nullptr;

@@ -16,6 +16,7 @@
 #include <cstdint>
 
 #include "fs_common.h"
+#include "fs_score_book.h"
 
 namespace fs {
 
@@ -310,6 +311,13 @@ struct HidSlot {
 // RMSNorm reads) to tab[b].rows when the slot collects and runs this iteration (states[b].done == 0); everything else exits at once.
 // dim % 4 == 0, X and the buffers 16-byte aligned.  ONE launch (a graph node of the session step: the table is read through pointers).
 void launch_hidden_rows(HidSlot* tab, const SeqState* states, const float* X, int dim, int B, hipStream_t st);
+// Scoring slots of a FS_SESSION_SCORE session (fishrt.h: fs_lm_session_add_scored): the per-slot table is fs_score_book.h's ScoreSlot.
+// In front of the per-slot sampler node of decision `decision` (0 = slow token over n candidates of rows ld apart; 1 + c = codebook c):
+// block b records f32 log-softmax figures of logits row b for the slot's target (candidate 0 left out of a slow decision when
+// cfgs[b].ignore_eos), then stores +INFINITY over the target's logit so that the greedy sampler behind it picks the target; at the last
+// decision it bumps tab[b].count.  Null entries, done slots and full records exit at once.  2 <= n <= 2048, n_cb == 8.  ONE launch.
+void launch_score_slots(ScoreSlot* tab, const SeqState* states, const SampleCfg* cfgs, float* logits, int ld, int n, int decision, int n_cb, int B,
+                        hipStream_t st);
 
 // synthetic tensor fill (fs_synth.h): n_rows x n_cols, destination row = r * row_mul + row_off (W1/W3 interleave)
 template <typename WT>
@@ -333,5 +341,8 @@ void debug_sample_rows(int device, const float* logits, int B, int n, double tem
                        int call_index, uint32_t* out);
 void debug_sample_slots(int device, const float* logits, int S, int R, int n, const SampleCfg* cfgs, const uint64_t* seeds, uint32_t* out,
                         uint64_t* words_used);
+// test hook behind fs_selftest_score_rows: the score node's device function on S caller rows of n candidates, one block per row
+void debug_score_rows(int device, const float* logits, int S, int n, const uint32_t* targets, int exclude0, float* logprob_out,
+                      float* top_logprob_out, uint32_t* top_out, float* row_out);
 
 }  // namespace fs

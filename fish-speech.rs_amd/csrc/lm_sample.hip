@@ -1560,6 +1560,134 @@ void launch_cap_rows_picks(const SeqState* states, const SampleCfg* cfg, int B, 
     hipLaunchKernelGGL(k_cap_rows_picks, dim3(B), dim3(64), 0, st, states, cfg, cap, cap_frames, n_cb);
 }
 
+// ---- scoring slots of a FS_SESSION_SCORE session (fishrt.h: fs_lm_session_add_scored): one node in front of each of the step's 9 per-slot
+// sampler nodes.  Block b scores the row its slot's sampler is about to read against the slot's forced target -- f32 log-softmax entry of
+// the target, of the maximum, the LAST maximal index (slot_greedy_pick's rule and key) -- and then stores +INFINITY over the target's
+// logit, so the (unchanged, greedy) sampler node behind it picks the target and does the frame bookkeeping as for any slot.
+// 256 threads, thread t owns the float4 groups at 4 t and 1024 + 4 t (n <= 2048); a group is one 16-byte load where the row start is
+// 16-byte aligned and the group lies inside [0, n), guarded scalar loads otherwise.  Two barriers (max key, sum), each behind one
+// __shfl_xor wave reduction and a 4-entry LDS array every thread folds itself.  All 256 threads take the same path.
+constexpr int SCORE_THREADS = 256;
+struct ScoreOut { float logprob, top_logprob, eos_logprob; uint32_t top; };
+__device__ __forceinline__ ScoreOut score_row(float* __restrict__ row, int n, int t, bool exclude0) {
+    __shared__ unsigned long long s_k[SCORE_THREADS / 64];
+    __shared__ float s_s[SCORE_THREADS / 64];
+    const int tid = threadIdx.x;
+    const bool vec = (reinterpret_cast<uintptr_t>(row) & 15u) == 0;
+    float lv[8];
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        const int i0 = g * (SCORE_THREADS * 4) + tid * 4;
+        if (vec && i0 + 3 < n) {
+            const float4 v = *reinterpret_cast<const float4*>(row + i0);
+            lv[g * 4 + 0] = v.x; lv[g * 4 + 1] = v.y; lv[g * 4 + 2] = v.z; lv[g * 4 + 3] = v.w;
+        } else {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) lv[g * 4 + s] = i0 + s < n ? row[i0 + s] : -INFINITY;
+        }
+    }
+    if (tid == 0 && exclude0) lv[0] = -INFINITY;
+    // the target's and <|im_end|>'s logits, read by thread 0 ahead of the barriers (the store at the end comes behind them)
+    float xt = 0.f, x0 = 0.f;
+    const bool t_ok = (unsigned)t < (unsigned)n;
+    if (tid == 0) {
+        x0 = lv[0];
+        xt = !t_ok ? __uint_as_float(0x7FC00000u) : (t == 0 ? lv[0] : row[t]);
+    }
+    unsigned long long key = 0ull;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+        const int i = (s >> 2) * (SCORE_THREADS * 4) + tid * 4 + (s & 3);
+        if (i < n) {
+            uint32_t u = __float_as_uint(lv[s] + 0.f);  // (-0 -> +0: equal values, the later index wins)
+            u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;  // unsigned order == float order
+            const unsigned long long k = ((unsigned long long)u << 32) | (unsigned long long)(uint32_t)i;
+            key = k > key ? k : key;
+        }
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) { const unsigned long long o = __shfl_xor(key, m, 64); key = o > key ? o : key; }
+    if ((tid & 63) == 0) s_k[tid >> 6] = key;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < SCORE_THREADS / 64; ++w) { const unsigned long long o = s_k[w]; key = o > key ? o : key; }
+    uint32_t mu = (uint32_t)(key >> 32);
+    mu ^= (mu >> 31) ? 0x80000000u : 0xFFFFFFFFu;
+    const float m = __uint_as_float(mu);
+    float sum = 0.f;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) sum += expf(lv[s] - m);  // (owned entries at or beyond n hold -inf: +0)
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    if ((tid & 63) == 0) s_s[tid >> 6] = sum;
+    __syncthreads();
+    sum = (s_s[0] + s_s[1]) + (s_s[2] + s_s[3]);
+    const float ls = logf(sum);
+    ScoreOut r;
+    r.logprob = (xt - m) - ls;
+    r.top_logprob = -ls;
+    r.eos_logprob = (x0 - m) - ls;
+    r.top = (uint32_t)(key & 0xFFFFFFFFull);
+    if (tid == 0 && t_ok) row[t] = INFINITY;  // the forcing: the unique maximum of a finite row
+    return r;  // (logprob / eos_logprob: thread 0's are the row's)
+}
+__global__ __launch_bounds__(SCORE_THREADS) void k_score_slots(ScoreSlot* __restrict__ tab, const SeqState* __restrict__ states,
+                                                               const SampleCfg* __restrict__ cfgs, float* __restrict__ logits, int ld, int n,
+                                                               int d, int n_cb) {
+    const int b = blockIdx.x;
+    ScoreSlot* sc = tab + b;
+    float* rec = sc->rec;
+    const int count = sc->count;
+    if (!rec || states[b].done != 0 || count >= sc->cap) return;  // (block-uniform)
+    const uint32_t tok = sc->targets[(size_t)count * (n_cb + 1) + d];
+    const int t = d == 0 ? (int)(tok - cfgs[b].audio_base) : (int)tok;
+    const ScoreOut r = score_row(logits + (size_t)b * ld, n, t, d == 0 && cfgs[b].ignore_eos != 0);
+    if (threadIdx.x == 0) {
+        rec += (size_t)count * 32;
+        rec[d] = r.logprob;
+        rec[9 + d] = r.top_logprob;
+        rec[18 + d] = __uint_as_float(r.top);
+        if (d == 0) { rec[27] = r.eos_logprob; rec[28] = 0.f; rec[29] = 0.f; rec[30] = 0.f; rec[31] = 0.f; }
+        if (d == n_cb) sc->count = count + 1;
+    }
+}
+void launch_score_slots(ScoreSlot* tab, const SeqState* states, const SampleCfg* cfgs, float* logits, int ld, int n, int decision, int n_cb, int B,
+                        hipStream_t st) {
+    FS_REQUIRE(n >= 2 && n <= SCORE_THREADS * 8 && n <= ld && n_cb == 8 && decision >= 0 && decision <= n_cb,
+               "score node: 2 .. 2048 candidates, 8 codebooks (the 32-word record holds 9 decisions)");
+    hipLaunchKernelGGL(k_score_slots, dim3(B), dim3(SCORE_THREADS), 0, st, tab, states, cfgs, logits, ld, n, decision, n_cb);
+    FS_LAUNCH_CHECK();
+}
+// test hook (fs_selftest_score_rows): score_row on caller rows, one block per row
+__global__ __launch_bounds__(SCORE_THREADS) void k_score_rows_test(float* __restrict__ rows, int n, const uint32_t* __restrict__ targets, int exclude0,
+                                                                   float* __restrict__ logprob, float* __restrict__ top_logprob,
+                                                                   uint32_t* __restrict__ top) {
+    const int b = blockIdx.x;
+    const ScoreOut r = score_row(rows + (size_t)b * n, n, (int)targets[b], exclude0 != 0);
+    if (threadIdx.x == 0) { logprob[b] = r.logprob; top_logprob[b] = r.top_logprob; top[b] = r.top; }
+}
+void debug_score_rows(int device, const float* logits, int S, int n, const uint32_t* targets, int exclude0, float* logprob_out,
+                      float* top_logprob_out, uint32_t* top_out, float* row_out) {
+    FS_REQUIRE(S >= 1 && S <= (1 << 16) && n >= 2 && n <= SCORE_THREADS * 8, "bad score test shape (1 <= S <= 65536 rows of 2 <= n <= 2048)");
+    for (int s = 0; s < S; ++s) FS_REQUIRE(targets[s] < (uint32_t)n, "score test: a target is outside [0, n)");
+    FS_HIP(hipSetDevice(device));
+    const size_t nl = (size_t)S * n;
+    float *d_rows = nullptr, *d_lp = nullptr, *d_tlp = nullptr; uint32_t *d_t = nullptr, *d_top = nullptr;
+    FS_HIP(hipMalloc(&d_rows, sizeof(float) * nl));
+    FS_HIP(hipMalloc(&d_lp, sizeof(float) * S)); FS_HIP(hipMalloc(&d_tlp, sizeof(float) * S));
+    FS_HIP(hipMalloc(&d_t, sizeof(uint32_t) * S)); FS_HIP(hipMalloc(&d_top, sizeof(uint32_t) * S));
+    FS_HIP(hipMemcpy(d_rows, logits, sizeof(float) * nl, hipMemcpyHostToDevice));
+    FS_HIP(hipMemcpy(d_t, targets, sizeof(uint32_t) * S, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_score_rows_test, dim3(S), dim3(SCORE_THREADS), 0, nullptr, d_rows, n, d_t, exclude0, d_lp, d_tlp, d_top);
+    FS_LAUNCH_CHECK();
+    FS_HIP(hipDeviceSynchronize());
+    if (logprob_out) FS_HIP(hipMemcpy(logprob_out, d_lp, sizeof(float) * S, hipMemcpyDeviceToHost));
+    if (top_logprob_out) FS_HIP(hipMemcpy(top_logprob_out, d_tlp, sizeof(float) * S, hipMemcpyDeviceToHost));
+    if (top_out) FS_HIP(hipMemcpy(top_out, d_top, sizeof(uint32_t) * S, hipMemcpyDeviceToHost));
+    if (row_out) FS_HIP(hipMemcpy(row_out, d_rows, sizeof(float) * nl, hipMemcpyDeviceToHost));
+    (void)hipFree(d_rows); (void)hipFree(d_lp); (void)hipFree(d_tlp); (void)hipFree(d_t); (void)hipFree(d_top);
+}
+
 // ---- sampler test hook (fs_selftest_sample_rows): the static-batch slow sampler on caller-provided logits, B rows of n candidates,
 // as sample() call number `call_index` of a request (child StdRng of row b = master u64 number call_index * B + b)
 void debug_sample_rows(int device, const float* logits, int B, int n, double temp, double top_p, uint64_t top_k, uint64_t seed,

@@ -262,12 +262,46 @@ class DualARTransformer:
         _ffi.check(_ffi.lib().fs_lm_weights_fingerprint(self._h, C.byref(out)))
         return int(out.value)
 
-    def session(self, temp=0.7, top_p=0.9, top_k=50, seed=42, ignore_eos=False, rows=False, repetition_penalty=1.2, per_slot=False, wide=False):
+    def session(self, temp=0.7, top_p=0.9, top_k=50, seed=42, ignore_eos=False, rows=False, repetition_penalty=1.2, per_slot=False, wide=False,
+                score=False):
         """continuous batching over this handle's max_batch slots (fishrt.h: fs_lm_session_*): `with lm.session(...) as s:`
         per_slot=True: FS_SESSION_PER_SLOT -- every slot samples like its own generate_blocking call (own settings, seed, repetition penalty).
         wide=True (with per_slot=True): FS_SESSION_WIDE_SAMPLER -- slots may also sample nucleus-only (top_k == 0) or with top_k > 256.
+        score=True (with per_slot=True): FS_SESSION_SCORE -- the session also takes scoring slots (Session.add_scored / poll_scores).
         Fish <= 1.4 token configs (no semantic range) take per_slot=True only; plain and rows sessions raise and say so."""
-        return Session(self, temp, top_p, top_k, seed, ignore_eos, rows, repetition_penalty, per_slot, wide)
+        return Session(self, temp, top_p, top_k, seed, ignore_eos, rows, repetition_penalty, per_slot, wide, score)
+
+    def score(self, prompts, frames, collect_hidden=False):
+        """Teacher-forced log-probabilities of given code sequences: sequence i is frames[i] (u32 [C+1, N_i]: row 0 the slow tokens, rows
+        1..C the codes) behind prompts[i] (u32 [C+1, L_i]).  Opens a greedy per-slot score session, feeds the sequences through the
+        handle's max_batch slots -- admitting the next one as slots free up, so the weights are streamed once per step for all of them --
+        and returns one dict per sequence: logprob / top_logprob f32 [N, C+1], top u32 [N, C+1], eos_logprob f32 [N]
+        (Session.poll_scores), total = logprob.sum() (f64), plus hidden f32 [N, dim] with collect_hidden."""
+        if len(prompts) != len(frames):
+            raise ValueError(f"score: {len(prompts)} prompts for {len(frames)} frame arrays")
+        out = [None] * len(prompts)
+        with self.session(temp=0.0, top_p=1.0, top_k=0, seed=0, repetition_penalty=1.0, per_slot=True, score=True) as s:
+            todo = [(i, s._prompt(p), s._frames(f)) for i, (p, f) in enumerate(zip(prompts, frames))]  # (every shape is checked first)
+            live = {}
+            while todo or live:
+                while todo:
+                    i, p, f = todo[0]
+                    slot = s.add_scored(p, f, collect_hidden=collect_hidden)
+                    if slot is None:
+                        if not live:
+                            raise RuntimeError(f"score: sequence {i} does not fit an empty session (KV page pool too small)")
+                        break
+                    live[slot] = i
+                    todo.pop(0)
+                s.step(8)
+                for slot in [k for k in live if s.poll(k, codes=False)[1]]:
+                    r = s.poll_scores(slot)
+                    r["total"] = float(r["logprob"].sum(dtype=np.float64))
+                    if collect_hidden:
+                        r["hidden"] = s.poll_hidden(slot)
+                    out[live.pop(slot)] = r
+                    s.release(slot)
+        return out
 
     def last_stats(self):
         st = _ffi.GenStats()
@@ -318,24 +352,29 @@ class Session:
 
     SAMPLING_KEYS = ("temp", "top_p", "top_k", "repetition_penalty")
 
-    def __init__(self, lm, temp, top_p, top_k, seed, ignore_eos, rows=False, repetition_penalty=1.2, per_slot=False, wide=False):
+    def __init__(self, lm, temp, top_p, top_k, seed, ignore_eos, rows=False, repetition_penalty=1.2, per_slot=False, wide=False, score=False):
         """rows=True: FS_SESSION_ROWS -- the slots run on the request-row persistent kernels with batch-1 semantics (repetition penalty, own
         sampler stream per slot); max_batch <= 8.
         per_slot=True: FS_SESSION_PER_SLOT -- the slots stay on the static-batch step (any max_batch, bf16 / fp8) and every slot samples like
         its own generate_blocking call, with the settings and seed of its add() (default: the session's, seed + admission number).  The
         only session kind of a Fish <= 1.4 handle: its slow token is the 2-way {pad, im_end} draw, one stream word per frame even when greedy
         wide=True: FS_SESSION_WIDE_SAMPLER, per_slot sessions only -- the session's and every add()'s settings may be greedy or any
-        temp > 0 with any top_k >= 0 (0 = no top-k) and any top_p; settings inside the 0 < top_k <= 256 limit give the same codes as without it"""
+        temp > 0 with any top_k >= 0 (0 = no top-k) and any top_p; settings inside the 0 < top_k <= 256 limit give the same codes as without it
+        score=True: FS_SESSION_SCORE, per_slot sessions only (Fish 1.5 token layout) -- add_scored() admits slots that are forced along a given
+        code sequence and record its log-probabilities (poll_scores); generating slots of the session are unaffected"""
         self.lm, self._open = lm, False
         if rows and per_slot:
             raise ValueError("rows and per_slot exclude each other (a row session's slots already sample per slot)")
         if wide and not per_slot:
             raise ValueError("wide=True needs per_slot=True (FS_SESSION_WIDE_SAMPLER is valid only together with FS_SESSION_PER_SLOT)")
-        self.rows, self.per_slot, self.wide = bool(rows), bool(per_slot), bool(wide)
+        if score and not per_slot:
+            raise ValueError("score=True needs per_slot=True (FS_SESSION_SCORE is valid only together with FS_SESSION_PER_SLOT)")
+        self.rows, self.per_slot, self.wide, self.score = bool(rows), bool(per_slot), bool(wide), bool(score)
         self.sampling = dict(temp=float(temp), top_p=float(top_p), top_k=int(top_k), repetition_penalty=float(repetition_penalty))
         s = _ffi.Sampling(float(temp), float(top_p), int(top_k), float(repetition_penalty) if (rows or per_slot) else 1.0)
         flags = (_ffi.FS_GEN_IGNORE_EOS if ignore_eos else 0) | (_ffi.FS_SESSION_ROWS if rows else 0) | (_ffi.FS_SESSION_PER_SLOT if per_slot else 0)
         flags |= _ffi.FS_SESSION_WIDE_SAMPLER if wide else 0
+        flags |= _ffi.FS_SESSION_SCORE if score else 0
         _ffi.check(_ffi.lib().fs_lm_session_begin(lm._h, C.byref(s), C.c_uint64(seed), flags))
         self._open = True
 
@@ -467,6 +506,47 @@ class Session:
             _ffi.check(_ffi.lib().fs_lm_session_poll_hidden(self.lm._h, int(slot), C.c_size_t(int(first)), out.ctypes.data_as(C.POINTER(C.c_float)),
                                                             C.c_size_t(rows), C.byref(n)))
         return out[:rows].copy()
+
+    def _frames(self, frames):
+        f = np.asarray(frames)
+        C1 = self.lm.cfg["num_codebooks"] + 1
+        if f.dtype != np.uint32 or f.ndim != 2 or f.shape[0] != C1 or f.shape[1] < 1:  # the C side reads (C + 1) * N words
+            raise ValueError(f"frames must be a u32 array [{C1}, N >= 1] (row 0 the slow tokens, rows 1.. the codes), got {f.dtype} {f.shape}")
+        return np.ascontiguousarray(f)
+
+    def add_scored(self, prompt, frames, prefix=None, collect_hidden=False):
+        """a scoring slot (fs_lm_session_add_scored; score=True sessions): its N iterations are forced to frames[:, i] (u32 [C+1, N]) behind
+        `prompt` (or behind prefix + body, as add) and scored -> poll_scores(slot).  The slot emits frames[1:] as its codes and is done after
+        N iterations.  -> slot, or None when no slot / KV pages are free right now.  collect_hidden=True: also poll_hidden(slot)."""
+        if not self.score:
+            raise ValueError("add_scored needs lm.session(per_slot=True, score=True)")
+        p = self._prompt(prompt, "prompt" if prefix is None else "body")
+        f = self._frames(frames)
+        slot = C.c_int(-1)
+        _ffi.check(_ffi.lib().fs_lm_session_add_scored(self.lm._h, -1 if prefix is None else int(prefix), p.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                       int(p.shape[1]), f.ctypes.data_as(C.POINTER(C.c_uint32)), int(f.shape[1]),
+                                                       1 if collect_hidden else 0, C.byref(slot)))
+        return None if slot.value < 0 else int(slot.value)
+
+    def poll_scores(self, slot, first=0):
+        """records [first, iterations so far) of a scoring slot -> dict(logprob f32 [n, C+1], top_logprob f32 [n, C+1], top u32 [n, C+1],
+        eos_logprob f32 [n]): per iteration and decision (0 the slow token, 1 + c codebook c) the log-softmax of the raw row at the forced
+        token and at its maximum, the greedy pick (a candidate index for decision 0: token - (semantic_start_id - 1), 0 = <|im_end|>; the
+        code otherwise), and the log-probability of <|im_end|> at the slow decision (-inf in an ignore_eos session)"""
+        if int(first) < 0:
+            raise ValueError("first must not be negative")
+        L, C1 = _ffi.lib(), self.lm.cfg["num_codebooks"] + 1
+        n = C.c_size_t(0)
+        _ffi.check(L.fs_lm_session_poll_scores(self.lm._h, int(slot), C.c_size_t(0), None, None, None, None, C.c_size_t(0), C.byref(n)))
+        rows = max(0, int(n.value) - int(first))
+        cap = max(1, rows)
+        lp, tlp = np.zeros((cap, C1), np.float32), np.zeros((cap, C1), np.float32)
+        top, eos = np.zeros((cap, C1), np.uint32), np.zeros(cap, np.float32)
+        if rows:
+            fp = C.POINTER(C.c_float)
+            _ffi.check(L.fs_lm_session_poll_scores(self.lm._h, int(slot), C.c_size_t(int(first)), lp.ctypes.data_as(fp), tlp.ctypes.data_as(fp),
+                                                   top.ctypes.data_as(C.POINTER(C.c_uint32)), eos.ctypes.data_as(fp), C.c_size_t(rows), C.byref(n)))
+        return dict(logprob=lp[:rows].copy(), top_logprob=tlp[:rows].copy(), top=top[:rows].copy(), eos_logprob=eos[:rows].copy())
 
     def release(self, slot):
         _ffi.check(_ffi.lib().fs_lm_session_release(self.lm._h, int(slot)))

@@ -95,6 +95,13 @@ int fs_selftest_sample_rows(int device_id, const float* logits, int B, int n, co
  * Diagnostics / parity tests. */
 int fs_selftest_sample_slots(int device_id, const float* logits, int S, int R, int n, const fs_sampling* samplings, const uint64_t* seeds,
                              uint32_t* out, uint64_t* words_used);
+/* The score node of a FS_SESSION_SCORE session (k_score_slots' device function) on caller-provided logits f32 [S][n] (2 <= n <= 2048), one
+ * block per row, target candidate targets[s] < n, exclude0 != 0: candidate 0 is left out (what FS_GEN_IGNORE_EOS does to <|im_end|> at
+ * the slow decision).  logprob_out[s] = log-softmax of the row at its target, top_logprob_out[s] = at its maximum, top_out[s] = the LAST
+ * maximal index (-0 == +0), all f32 arithmetic; row_out f32 [S][n] = the rows as the node leaves them (the input with +inf at the
+ * target).  Output pointers nullable.  Diagnostics / parity tests. */
+int fs_selftest_score_rows(int device_id, const float* logits, int S, int n, const uint32_t* targets, int exclude0, float* logprob_out,
+                           float* top_logprob_out, uint32_t* top_out, float* row_out);
 
 /* Self-test of a LOADED handle, by name.  "persist": the persistent decode kernels of this binary (csrc/lm_persist.hip, lm_persist_slow.hip:
  * pinned weight registers, loads issued outside the compiler's wait-count bookkeeping) against the per-node kernels on the handle's own
@@ -326,7 +333,17 @@ int fs_comm_all_gather_codes(fs_comm_t* comm, const uint32_t* codes, const int32
  * the legacy 2-way slow draw on Fish <= 1.4 handles, the capture record; the handle limits stay (<= 2048 slow candidates, codebooks of
  * <= 1024 entries).  Sessions begun without the flag are unchanged: same kernels, same errors, same codes. */
 #define FS_SESSION_WIDE_SAMPLER 32u
-int fs_lm_session_begin(fs_lm_t* lm, const fs_sampling* sampling, uint64_t seed, uint32_t flags /* FS_GEN_IGNORE_EOS | FS_SESSION_ROWS | FS_SESSION_PER_SLOT | FS_SESSION_WIDE_SAMPLER */);
+/* FS_SESSION_SCORE: valid only together with FS_SESSION_PER_SLOT, with or without FS_SESSION_WIDE_SAMPLER (alone, with FS_SESSION_ROWS, or
+ * on a Fish <= 1.4 handle -- has_semantic_end == 0 -- fs_lm_session_begin fails and says which; num_codebooks must be 8).  The session
+ * additionally takes SCORING slots (fs_lm_session_add_scored): slots that are not sampled but forced along a given code sequence, and that
+ * record how likely the model found every one of its tokens.  A scoring slot rides the same step as the generating slots next to it --
+ * the weights are streamed once per step for all of them -- and uses the same prefill, paging, shared prefixes, prefix blobs and
+ * hidden-state collection.  The step graphs of such a session carry one small node (k_score_slots, one block per slot) in front of each
+ * of the 9 per-slot sampler nodes and behind fs_lm_debug_capture's record of the raw row; it reads a per-slot table, so admitting or
+ * releasing a scoring slot never re-captures a graph, and for a generating slot it exits at once: every generating slot's codes are bit
+ * for bit those of the same session without the flag.  Sessions begun without the flag replay exactly the graphs they did before. */
+#define FS_SESSION_SCORE 64u
+int fs_lm_session_begin(fs_lm_t* lm, const fs_sampling* sampling, uint64_t seed, uint32_t flags /* FS_GEN_IGNORE_EOS | FS_SESSION_ROWS | FS_SESSION_PER_SLOT | FS_SESSION_WIDE_SAMPLER | FS_SESSION_SCORE */);
 /* prompt u32 [C+1, L] row-major (copied); *slot = the slot taken, or -1 when all max_batch slots are busy or the KV page pool cannot hold
  * the request right now (not an error: retry after a release).  Returns once the
  * prefill is enqueued (one prefill in flight: a second add first waits for the previous one); the slot starts generating in a later step */
@@ -383,6 +400,31 @@ int fs_lm_session_add_ex(fs_lm_t* lm, int prefix_id, const uint32_t* prompt, int
 int fs_lm_session_add_hidden(fs_lm_t* lm, int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling,
                              const uint64_t* seed, int* slot);
 int fs_lm_session_poll_hidden(fs_lm_t* lm, int slot, size_t first_row, float* hidden_out, size_t cap_rows, size_t* n_rows);
+/* Scoring slots (FS_SESSION_SCORE sessions; both calls fail with "needs FS_SESSION_SCORE" in any other).
+ * A slot that is NOT sampled: iteration i (0-based) of the slot is forced to frames[:, i] -- frames u32 [C+1, N] row-major like a prompt
+ * (row 0 the slow token, rows 1..C the codes), N >= 1 -- and records what the model thought of it.  Otherwise == fs_lm_session_add_ex
+ * (prefix_id rules, *slot = -1 when no slot / pages are free, prefill in a pass of its own like a slot with its own seed) with
+ * max_new_tokens = L + N - 2, i.e. exactly N iterations.  Validated before anything is queued, each an error naming the field and
+ * leaving the session as it was: every frames[0][i] in [semantic_start_id, vocab_size), every code < codebook_size, and
+ * L_total + N - 1 <= max_seq_len (L_total = L plus the prefix's length; a scored sequence is never clipped).  The slot emits
+ * frames[1..C] as its codes (fs_lm_session_poll), draws no stream words, and never ends early.  collect_hidden != 0: also
+ * fs_lm_session_add_hidden's rows (fs_lm_session_poll_hidden).
+ * Per decision d of an iteration (0 = the slow token over the audio range, <|im_end|> at candidate 0 left out under FS_GEN_IGNORE_EOS;
+ * 1 + c = codebook c over codebook_size entries) the record is taken from the RAW row the slot's sampler would have decided on -- no
+ * temperature, no repetition penalty, no top-k / top-p -- in f32: m = max x_i, s = sum exp(x_i - m),
+ *     logprob[d] = (x_target - m) - log(s)      top_logprob[d] = -log(s)      top[d] = the LAST index holding m (-0 == +0)
+ * and eos_logprob = (x_0 - m) - log(s) of the slow decision (-inf when <|im_end|> is left out).  An f32 sum of <= 2048 non-negative terms:
+ * within 2e-4 absolute of the exact log-softmax of the row.  Then the node stores +inf over the target's logit and the slot's own greedy
+ * sampler node, unchanged, picks it and does the frame bookkeeping as for any slot.
+ * Device memory: 128 + 4 (C + 1) bytes per iteration, one buffer per scoring slot from a per-handle pool (taken at the add, returned when
+ * the add is refused, at fs_lm_session_release and at fs_lm_session_end). */
+int fs_lm_session_add_scored(fs_lm_t* lm, int prefix_id, const uint32_t* prompt, int L, const uint32_t* frames, int N, int collect_hidden,
+                             int* slot);
+/* rows [first_row, ...) so far, one per iteration: logprob / top_logprob f32 [cap_rows][C+1], top u32 [cap_rows][C+1],
+ * eos_logprob f32 [cap_rows]; every output pointer nullable; *n_rows = rows the slot has (0 while prefilling; a released and re-admitted
+ * slot starts again at row 0).  A slot not admitted with fs_lm_session_add_scored is an error that says so. */
+int fs_lm_session_poll_scores(fs_lm_t* lm, int slot, size_t first_row, float* logprob, float* top_logprob, uint32_t* top, float* eos_logprob,
+                              size_t cap_rows, size_t* n_rows);
 /* out[8] = {free pages, pages referenced by more than one owner, live prefixes, prefill passes, tokens prefilled,
  *           prefix tokens reused, tail pages copied, prefill-stream microseconds (HIP events around each pass)};
  * counters since fs_lm_session_begin */
