@@ -55,6 +55,34 @@ struct DevBuf {
     T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// the repetition-penalty state (lm_kernels.h: RepPenState) of `rows` sampler rows, row after row: per codebook the mask and seen tables
+// over the codebook, the 17-word ring and its 2 meta words
+struct RepPenBufs {
+    DevBuf mask, seen, ring, meta;
+    size_t per_row[4] = {0, 0, 0, 0};  // elements of one row in each of the four
+    void alloc(size_t rows, size_t n_codebooks, size_t codebook_size) {
+        per_row[0] = per_row[1] = n_codebooks * codebook_size; per_row[2] = n_codebooks * 17; per_row[3] = n_codebooks * 2;
+        mask.alloc(sizeof(float) * rows * per_row[0]); seen.alloc(rows * per_row[1]);
+        ring.alloc(sizeof(int) * rows * per_row[2]); meta.alloc(sizeof(int) * rows * per_row[3]);
+    }
+    RepPenState view(size_t row) const {
+        return RepPenState{mask.as<float>() + row * per_row[0], seen.as<uint8_t>() + row * per_row[1], ring.as<int>() + row * per_row[2],
+                           meta.as<int>() + row * per_row[3]};
+    }
+};
+
+// One collector kind of a session (fs_slot_book.h; E = HidSlot: fs_lm_session_add_hidden, ScoreSlot: fs_lm_session_add_scored): the host
+// mirror of the per-slot table + the handle's buffer pool, the device table the step's node reads (allocated once per handle: the
+// captured step graphs hold its address), and the landing place of the end-of-chunk copy of the counts
+void* slot_buf_alloc(size_t n) { void* p = nullptr; return hipMalloc(&p, n) == hipSuccess ? p : nullptr; }
+void slot_buf_free(void* p) { (void)hipFree(p); }
+template <typename E>
+struct SlotTab {
+    SlotBook<E> book{&slot_buf_alloc, &slot_buf_free};
+    DevBuf dev;
+    std::vector<E> stage;
+};
+
 struct TensorDesc {
     std::string name;      // reference tensor name (dual_ar.rs loader)
     int64_t rows, cols;
@@ -210,10 +238,6 @@ class LM final : public LMBase {
         for (auto& e : ev_) if (e) (void)hipEventDestroy(e);
         for (auto& e : ev_batch_) if (e) (void)hipEventDestroy(e);
         if (h_pin_) (void)hipHostFree(h_pin_);
-        for (auto& hb : hid_pool_) (void)hipFree(hb.first);
-        for (const HidSlot& h : sess_hid_) if (h.rows) (void)hipFree(h.rows);
-        for (auto* q : {&sess_flight_, &sess_queue_})  // (a handle destroyed with a session open and adds pending)
-            for (const PendingAdd& pa : *q) if (pa.hid) (void)hipFree(pa.hid);
         if (ev_pf_) (void)hipEventDestroy(ev_pf_);
         for (hipEvent_t e : ev_pft_) if (e) (void)hipEventDestroy(e);
         if (st_pf_) (void)hipStreamDestroy(st_pf_);
@@ -567,7 +591,7 @@ class LM final : public LMBase {
         ss.pos = n_cached; ss.prompt_L = L;
         FS_HIP(hipMemcpyAsync(state(0), &ss, sizeof(ss), hipMemcpyHostToDevice, st_));
         FS_HIP(hipMemcpyAsync(d_prompt_.p, prompt, sizeof(uint32_t) * C1 * L, hipMemcpyHostToDevice, st_));
-        launch_reppen_reset(rp_, C, a_.codebook_size, st_);
+        launch_reppen_reset(rp_.view(0), C, a_.codebook_size, st_);
         clear_fast();
 
         stats_ = {};
@@ -589,7 +613,7 @@ class LM final : public LMBase {
                 FS_HIP(hipMemcpyAsync(d_rcfg_.p, &cfg, sizeof(cfg), hipMemcpyHostToDevice, st_));
                 FS_HIP(hipMemcpyAsync(d_rbudget_.p, &big, sizeof(int), hipMemcpyHostToDevice, st_));
                 FS_HIP(hipMemcpyAsync(d_rrng_.p, &rng, sizeof(rng), hipMemcpyHostToDevice, st_));
-                launch_reppen_reset(rows_rp(0), C, a_.codebook_size, st_);
+                launch_reppen_reset(rrp_.view(0), C, a_.codebook_size, st_);
             }
         }
         g.multi_ok = use_persist_ && use_pslow_ && fold_slow_sampler() && !g.time_k && !g.b1_rows_fast;
@@ -960,20 +984,16 @@ class LM final : public LMBase {
         if (per_slot) {
             // per-slot sampler state, allocated once per handle (the captured step graphs hold these pointers) and re-initialised for every
             // slot at its activation, so nothing of an earlier session or occupant is ever read
-            const size_t nc = (size_t)B_ * a_.num_codebooks;
             if (!d_scfg_.p) {
                 d_scfg_.alloc(sizeof(SampleCfg) * B_);
                 d_srng_.alloc(sizeof(SlotRng) * B_);
-                d_srp_mask_.alloc(sizeof(float) * nc * a_.codebook_size);
-                d_srp_seen_.alloc(nc * a_.codebook_size);
-                d_srp_ring_.alloc(sizeof(int) * nc * 17);
-                d_srp_meta_.alloc(sizeof(int) * nc * 2);
+                srp_.alloc(B_, a_.num_codebooks, a_.codebook_size);
             }
             std::vector<SampleCfg> cfgs(B_, cfg);
             FS_HIP(hipMemcpyAsync(d_scfg_.p, cfgs.data(), sizeof(SampleCfg) * B_, hipMemcpyHostToDevice, st_));
             FS_HIP(hipMemsetAsync(d_srng_.p, 0xFF, d_srng_.n, st_));
-            FS_HIP(hipMemsetAsync(d_srp_ring_.p, 0, d_srp_ring_.n, st_));
-            for (int b = 0; b < B_; ++b) launch_reppen_reset(slot_rp(b), a_.num_codebooks, a_.codebook_size, st_);
+            FS_HIP(hipMemsetAsync(srp_.ring.p, 0, srp_.ring.n, st_));
+            for (int b = 0; b < B_; ++b) launch_reppen_reset(srp_.view(b), a_.num_codebooks, a_.codebook_size, st_);
             FS_HIP(hipStreamSynchronize(st_));  // (cfgs is a local)
         }
         if (sess_rows_) {
@@ -990,17 +1010,13 @@ class LM final : public LMBase {
         // empty slots: dead, frame 1 (so the frame-0 rule never fires), position 0 of a scratch page nobody reads
         FS_REQUIRE(!free_pages_.empty(), "KV page pool exhausted");
         sess_scratch_ = take_page();
-        sess_left_.assign(B_, -1);
+        sess_left_.assign(B_, kSlotFree);
         sess_pos_.assign(B_, 0);
         sess_hs_.assign(B_, SeqState{});
         sess_queue_.clear(); sess_flight_.clear();
         sess_prefixes_.clear();
-        sess_hid_.assign(B_, HidSlot{});
-        sess_hid_want_.assign(B_, 0);
-        sess_hid_live_ = 0;
-        FS_HIP(hipMemsetAsync(d_hid_tab_.p, 0, d_hid_tab_.n, st_));
-        sc_book_.begin(B_, a_.num_codebooks + 1);
-        FS_HIP(hipMemsetAsync(d_sc_tab_.p, 0, d_sc_tab_.n, st_));
+        tab_begin(hid_, sizeof(float) * (size_t)a_.dim);
+        tab_begin(sc_, sizeof(float) * SCORE_REC_WORDS + sizeof(uint32_t) * ((size_t)a_.num_codebooks + 1));
         for (auto& v : sess_count_) v = 0;
         sess_pf_ms_ = 0.0;
         sess_timed_ = false;
@@ -1026,13 +1042,12 @@ class LM final : public LMBase {
         const bool ok = s.temp == 0.0 || (s.temp > 0.0 && s.top_k > 0 && s.top_k <= 256);
         if (!ok) throw Error("FS_SESSION_PER_SLOT: a slot samples greedy (temp == 0) or with temp > 0 and 0 < top_k <= 256 (the in-launch samplers' limit)");
     }
-    RepPenState slot_rp(int b) {
-        const size_t nc = (size_t)b * a_.num_codebooks;
-        RepPenState rp;
-        rp.mask = d_srp_mask_.as<float>() + nc * a_.codebook_size; rp.seen = d_srp_seen_.as<uint8_t>() + nc * a_.codebook_size;
-        rp.ring = d_srp_ring_.as<int>() + nc * 17; rp.ring_meta = d_srp_meta_.as<int>() + nc * 2;
-        return rp;
-    }
+    // the states of a slot, as sess_left_ spells them (>= 0: iterations left to a live slot), and the check of the entry points that take one
+    static constexpr int kSlotFree = -1, kSlotPrefilling = -2;
+    bool slot_free(int b) const { return sess_left_[b] == kSlotFree; }
+    bool slot_prefilling(int b) const { return sess_left_[b] == kSlotPrefilling; }
+    bool slot_running(int b) const { return sess_left_[b] > 0 && !sess_hs_[b].done; }
+    void require_live_slot(int slot) const { FS_REQUIRE(sess_active_ && slot >= 0 && slot < B_ && !slot_free(slot), "not a live session slot"); }
     // fs_lm_session_add_ex: an add (plain, or on a prefix) whose slot samples with its own settings and / or seed.  Per-slot sessions take
     // anything inside require_slot_sampling; row sessions what their launch instantiation covers together with the session's setting (all
     // greedy or all sampled); the lock-step sampler has no per-slot notion, so a plain session refuses both.
@@ -1070,58 +1085,46 @@ class LM final : public LMBase {
         FS_REQUIRE(L >= 1, "empty prompt");
         const long long Lt = (long long)L + (prefix_id >= 0 ? live_prefix(prefix_id).P : 0);
         const long long n_iter = std::max<long long>(1, iter_budget(max_new_tokens, Lt).n_iter);  // (Lt > max_seq_len: the add below throws)
-        std::pair<float*, int> buf = take_hid_buf((int)n_iter);
+        SlotBuf buf = hid_.book.take((int)n_iter);
         int b = -1;
         try {
             b = session_add_ex(prefix_id, prompt, L, max_new_tokens, sampling, seed);
-        } catch (...) { put_hid_buf(buf.first, buf.second); throw; }
-        if (b < 0) { put_hid_buf(buf.first, buf.second); return b; }
+        } catch (...) { hid_.book.put(buf); throw; }
+        if (b < 0) { hid_.book.put(buf); return b; }
         PendingAdd& pa = sess_queue_.back();
-        FS_REQUIRE(pa.n_iter <= buf.second, "hidden-state buffer shorter than the slot's iteration budget");
-        pa.hid = buf.first; pa.hid_cap = buf.second;
-        sess_hid_want_[b] = 1;
+        FS_REQUIRE(pa.n_iter <= buf.cap, "hidden-state buffer shorter than the slot's iteration budget");
+        pa.hid = buf;
+        hid_.book.admitted(b);
         return b;
     }
-    // a row buffer goes back to the pool, which never holds more than max_batch buffers (beyond that the smallest one is freed)
-    void put_hid_buf(float* p, int cap) {
-        hid_pool_.push_back({p, cap});
-        if ((int)hid_pool_.size() <= B_) return;
-        int small = 0;
-        for (int i = 1; i < (int)hid_pool_.size(); ++i) if (hid_pool_[i].second < hid_pool_[small].second) small = i;
-        (void)hipFree(hid_pool_[small].first);
-        hid_pool_.erase(hid_pool_.begin() + small);
-    }
-    // a free row buffer of >= n_rows rows (the smallest that fits), else a new one
-    std::pair<float*, int> take_hid_buf(int n_rows) {
-        int best = -1;
-        for (int i = 0; i < (int)hid_pool_.size(); ++i)
-            if (hid_pool_[i].second >= n_rows && (best < 0 || hid_pool_[i].second < hid_pool_[best].second)) best = i;
-        if (best >= 0) {
-            const std::pair<float*, int> buf = hid_pool_[best];
-            hid_pool_.erase(hid_pool_.begin() + best);
-            return buf;
-        }
-        float* p = nullptr;
-        FS_HIP(hipMalloc(&p, sizeof(float) * (size_t)n_rows * a_.dim));
-        return {p, n_rows};
-    }
-    // the slot stops collecting: null table entry (on the engine stream: ahead of the next step), buffer back to the pool
-    void drop_hid_slot(int b) {
-        if (!sess_hid_[b].rows) return;
-        put_hid_buf(sess_hid_[b].rows, sess_hid_[b].cap);
-        sess_hid_[b] = HidSlot{};
-        FS_HIP(hipMemcpyAsync(d_hid_tab_.as<HidSlot>() + b, &sess_hid_[b], sizeof(HidSlot), hipMemcpyHostToDevice, st_));
+    // What a collector table (hid_, sc_) does on the device side of the book's moves.  Session begin / end: a null device table.  Activation:
+    // the slot's entry, count 0 (it collects from its first iteration on: row 0).  Drop: the slot stops collecting -- null entry on the
+    // engine stream, ahead of the next step.  End of a chunk: the device table comes back and, once the stream has been waited for, the
+    // book takes its counts.
+    template <typename E> void tab_begin(SlotTab<E>& t, size_t row_bytes) { t.book.begin(B_, row_bytes); tab_clear(t); }
+    template <typename E> void tab_end(SlotTab<E>& t) { t.book.end(); tab_clear(t); }
+    template <typename E> void tab_clear(SlotTab<E>& t) { FS_HIP(hipMemsetAsync(t.dev.p, 0, t.dev.n, st_)); }
+    template <typename E> void tab_upload(SlotTab<E>& t, int b) { FS_HIP(hipMemcpyAsync(t.dev.template as<E>() + b, &t.book.entry(b), sizeof(E), hipMemcpyHostToDevice, st_)); }
+    template <typename E> void tab_activate(SlotTab<E>& t, int b, const SlotBuf& buf) { t.book.activate(b, buf); tab_upload(t, b); }
+    template <typename E> void tab_drop(SlotTab<E>& t, int b) {
+        if (!t.book.drop(b)) return;
+        tab_upload(t, b);
         FS_HIP(hipStreamSynchronize(st_));
-        --sess_hid_live_;
     }
+    template <typename E> void tab_fetch_counts(SlotTab<E>& t) {
+        t.stage.resize(B_);
+        if (t.book.live() > 0) FS_HIP(hipMemcpyAsync(t.stage.data(), t.dev.p, sizeof(E) * B_, hipMemcpyDeviceToHost, st_));
+    }
+    template <typename E> void tab_take_counts(SlotTab<E>& t) { if (t.book.live() > 0) t.book.refresh_counts(t.stage.data()); }
     void session_poll_hidden(int slot, size_t first_row, float* hidden_out, size_t cap_rows, size_t* n_rows) override {
         use_device();
-        FS_REQUIRE(sess_active_ && slot >= 0 && slot < B_ && sess_left_[slot] != -1, "not a live session slot");
-        FS_REQUIRE(sess_hid_want_[slot], "the slot does not collect hidden states (it was not admitted with fs_lm_session_add_hidden)");
-        const size_t n = sess_left_[slot] == -2 ? 0 : (size_t)sess_hid_[slot].count;  // (-2: still prefilling)
+        require_live_slot(slot);
+        FS_REQUIRE(hid_.book.wanted(slot), "the slot does not collect hidden states (it was not admitted with fs_lm_session_add_hidden)");
+        const HidSlot& e = hid_.book.entry(slot);
+        const size_t n = slot_prefilling(slot) ? 0 : (size_t)e.count;
         if (hidden_out && first_row < n) {
             const size_t m = std::min(n - first_row, cap_rows);
-            if (m) FS_HIP(hipMemcpyAsync(hidden_out, sess_hid_[slot].rows + first_row * (size_t)a_.dim, sizeof(float) * m * a_.dim, hipMemcpyDeviceToHost, st_));
+            if (m) FS_HIP(hipMemcpyAsync(hidden_out, e.rows + first_row * (size_t)a_.dim, sizeof(float) * m * a_.dim, hipMemcpyDeviceToHost, st_));
             FS_HIP(hipStreamSynchronize(st_));
         }
         if (n_rows) *n_rows = n;
@@ -1151,13 +1154,13 @@ class LM final : public LMBase {
         if (Lt + N - 1 > a_.max_seq_len)
             throw Error("L + N - 1 = " + std::to_string(Lt + N - 1) + " exceeds max_seq_len (L counts the prefix; a scored sequence is never clipped)");
         const int max_new = (int)(Lt + N - 2);  // exactly N iterations (iter_budget)
-        ScoreBuf buf = sc_book_.take(N);
+        SlotBuf buf = sc_.book.take(N);
         const uint64_t seed = sess_seed_ + (uint64_t)sess_adds_;
         int b = -1;
         try {
             b = collect_hidden ? session_add_hidden(prefix_id, prompt, L, max_new, nullptr, &seed) : session_add_ex(prefix_id, prompt, L, max_new, nullptr, &seed);
-        } catch (...) { sc_book_.put(buf); throw; }
-        if (b < 0) { sc_book_.put(buf); return b; }
+        } catch (...) { sc_.book.put(buf); throw; }
+        if (b < 0) { sc_.book.put(buf); return b; }
         PendingAdd& pa = sess_queue_.back();
         pa.has_cfg = true;
         pa.cfg = sess_cfg_;
@@ -1166,7 +1169,7 @@ class LM final : public LMBase {
         pa.sc_targets.resize((size_t)N * C1);  // [N][C + 1]: one iteration's 9 targets side by side
         for (int i = 0; i < N; ++i)
             for (int r = 0; r < C1; ++r) pa.sc_targets[(size_t)i * C1 + r] = frames[(size_t)r * N + i];
-        sc_book_.admitted(b);
+        sc_.book.admitted(b);
         return b;
     }
     void session_poll_scores(int slot, size_t first_row, float* logprob, float* top_logprob, uint32_t* top, float* eos_logprob, size_t cap_rows,
@@ -1174,10 +1177,10 @@ class LM final : public LMBase {
         use_device();
         FS_REQUIRE(sess_active_, "no open session");
         FS_REQUIRE(sess_score_, "fs_lm_session_poll_scores needs FS_SESSION_SCORE (begin the session with FS_SESSION_PER_SLOT | FS_SESSION_SCORE)");
-        FS_REQUIRE(slot >= 0 && slot < B_ && sess_left_[slot] != -1, "not a live session slot");
-        FS_REQUIRE(sc_book_.wanted(slot), "the slot is not a scoring slot (it was not admitted with fs_lm_session_add_scored)");
-        const ScoreSlot& e = sc_book_.entry(slot);
-        const size_t n = sess_left_[slot] == -2 ? 0 : (size_t)e.count;  // (-2: still prefilling)
+        require_live_slot(slot);
+        FS_REQUIRE(sc_.book.wanted(slot), "the slot is not a scoring slot (it was not admitted with fs_lm_session_add_scored)");
+        const ScoreSlot& e = sc_.book.entry(slot);
+        const size_t n = slot_prefilling(slot) ? 0 : (size_t)e.count;
         if ((logprob || top_logprob || top || eos_logprob) && first_row < n) {
             const size_t m = std::min(n - first_row, cap_rows), C1 = (size_t)a_.num_codebooks + 1;
             std::vector<float> rec(m * SCORE_REC_WORDS);
@@ -1195,14 +1198,6 @@ class LM final : public LMBase {
         }
         if (n_rows) *n_rows = n;
     }
-    // the slot stops being scored: null table entry (on the engine stream: ahead of the next step), buffer back to the pool
-    void drop_score_slot(int b) {
-        if (!sc_book_.drop(b)) return;
-        FS_HIP(hipMemcpyAsync(d_sc_tab_.as<ScoreSlot>() + b, &sc_book_.entry(b), sizeof(ScoreSlot), hipMemcpyHostToDevice, st_));
-        FS_HIP(hipStreamSynchronize(st_));
-    }
-    static void* sc_alloc(size_t n) { void* p = nullptr; return hipMalloc(&p, n) == hipSuccess ? p : nullptr; }
-    static void sc_free(void* p) { (void)hipFree(p); }
     void park_slot(int b) {
         SeqState ss = {};
         ss.done = sess_rows_ ? 2 : 1; ss.frame = 1;  // (rows mode: a terminated row is skipped by the row kernels altogether)
@@ -1236,9 +1231,8 @@ class LM final : public LMBase {
         bool has_cfg = false, has_seed = false;  // fs_lm_session_add_ex: the slot's own settings / sampler seed
         SampleCfg cfg = {};
         uint64_t seed = 0;
-        float* hid = nullptr;  // fs_lm_session_add_hidden: the slot's row buffer [hid_cap][dim], handed to the device table at activation
-        int hid_cap = 0;
-        ScoreBuf sc;                       // fs_lm_session_add_scored: the slot's records + targets buffer, handed to the device table at activation
+        SlotBuf hid;                       // fs_lm_session_add_hidden: the slot's row buffer [cap][dim], handed to the device table at activation
+        SlotBuf sc;                        // fs_lm_session_add_scored: the slot's records + targets buffer, likewise (both in hand until then)
         std::vector<uint32_t> sc_targets;  // ... and the staged targets [n_iter][C + 1], copied into the buffer then
         std::vector<uint32_t> prompt;
         int rows() const { return import_kv ? 0 : (create ? L : L - start - 1); }   // tokens this member runs through the slow transformer
@@ -1256,17 +1250,22 @@ class LM final : public LMBase {
         FS_REQUIRE(P >= 1, "empty prefix");
         FS_REQUIRE(P < a_.max_seq_len, "prefix leaves no room for a body within max_seq_len");
         validate_tokens(prompt, 0, 1, P);
+        const int id = queue_prefix(P);
+        if (id >= 0) sess_queue_.back().prompt.assign(prompt, prompt + (size_t)(a_.num_codebooks + 1) * P);
+        return id;
+    }
+    // a pending prefix of P positions: its pages taken, its creating pass queued (the caller gives sess_queue_.back() what the pass moves:
+    // the prompt, or an imported payload).  Returns its id, or -1 when the page pool is short right now.
+    int queue_prefix(int P) {
         ensure_prefill2_buffers();
         const int np = (P + KV_PAGE - 1) / KV_PAGE;
         if ((int)free_pages_.size() < np) return -1;
-        const int C1 = a_.num_codebooks + 1;
         SessPrefix px;
         px.P = P; px.live = true; px.pending = true;
         for (int j = 0; j < np; ++j) px.pages.push_back(take_page());
         sess_prefixes_.push_back(std::move(px));
         PendingAdd pa;
         pa.create = true; pa.L = P; pa.prefix = (int)sess_prefixes_.size() - 1;
-        pa.prompt.assign(prompt, prompt + (size_t)C1 * P);
         sess_queue_.push_back(std::move(pa));
         return (int)sess_prefixes_.size() - 1;
     }
@@ -1300,7 +1299,7 @@ class LM final : public LMBase {
         const int P = px ? px->P : 0, L = P + n_cols;
         if (L > a_.max_seq_len) throw Error("prompt exceeds max_seq_len (dual_ar.rs:623-624)");
         int b = -1;
-        for (int i = 0; i < B_; ++i) if (sess_left_[i] == -1) { b = i; break; }
+        for (int i = 0; i < B_; ++i) if (slot_free(i)) { b = i; break; }
         if (b < 0) return -1;
         const int C1 = a_.num_codebooks + 1;
         validate_tokens(cols, 0, 1, n_cols);
@@ -1318,7 +1317,7 @@ class LM final : public LMBase {
         if (P % KV_PAGE) { pa.tail = px->pages[nfull]; ++page_refs_[pa.tail]; }
         pa.prompt.assign(cols, cols + (size_t)C1 * n_cols);
         sess_queue_.push_back(std::move(pa));
-        sess_left_[b] = -2;  // reserved: prefilling
+        sess_left_[b] = kSlotPrefilling;  // (reserved)
         stats_.prompt_tokens += (uint64_t)L;
         return b;
     }
@@ -1403,19 +1402,14 @@ class LM final : public LMBase {
         FS_REQUIRE(h.P >= 1 && h.P < a_.max_seq_len, "prefix blob: P outside 1 <= P < max_seq_len (a prefix must leave room for a body)");
         FS_REQUIRE(h.payload_bytes == (uint64_t)prefix_payload_bytes(h.P), "prefix blob: payload_bytes does not match n_layer * 2 * P * n_local_heads * head_dim elements");
         FS_REQUIRE(h.weights_fingerprint == weights_fingerprint(), "prefix blob: weights_fingerprint differs from this handle's (other weights or storage type)");
-        ensure_prefill2_buffers();
-        const int P = h.P, np = (P + KV_PAGE - 1) / KV_PAGE;
-        if ((int)free_pages_.size() < np) return -1;
-        SessPrefix px;
-        px.P = P; px.live = true; px.pending = true;
-        for (int j = 0; j < np; ++j) px.pages.push_back(take_page());
-        sess_prefixes_.push_back(std::move(px));
-        PendingAdd pa;
-        pa.create = true; pa.import_kv = true; pa.L = P; pa.prefix = (int)sess_prefixes_.size() - 1;
-        const uint8_t* payload = static_cast<const uint8_t*>(blob) + sizeof(h);
-        pa.blob.assign(payload, payload + h.payload_bytes);  // (the caller may free its blob as soon as this returns)
-        sess_queue_.push_back(std::move(pa));
-        return (int)sess_prefixes_.size() - 1;
+        const int id = queue_prefix(h.P);
+        if (id >= 0) {
+            PendingAdd& pa = sess_queue_.back();
+            pa.import_kv = true;
+            const uint8_t* payload = static_cast<const uint8_t*>(blob) + sizeof(h);
+            pa.blob.assign(payload, payload + h.payload_bytes);  // (the caller may free its blob as soon as this returns)
+        }
+        return id;
     }
     // the pass of the imports at the head of the (sorted) queue: per import one host-to-device copy into the staging buffer and one
     // k_kv_rows_scatter into its pages, on the prefill stream; activated like a creating pass (pa.create).  No counter of a transformer
@@ -1452,6 +1446,11 @@ class LM final : public LMBase {
             off += pa.blob.size();
             id_off += px.pages.size();
         }
+        pass_launched(n);
+    }
+    // the pass of the first n queued entries is on the prefill stream: its end is marked (timing event, then the event activate_pending
+    // waits for) and the entries are in flight
+    void pass_launched(size_t n) {
         FS_HIP(hipEventRecord(ev_pft_[1], st_pf_));
         FS_HIP(hipEventRecord(ev_pf_, st_pf_));
         sess_flight_.assign(std::make_move_iterator(sess_queue_.begin()), std::make_move_iterator(sess_queue_.begin() + n));
@@ -1486,10 +1485,7 @@ class LM final : public LMBase {
             if (Lp < 1) {                          // only single-token prompts are left: no pass, they go live at the next activation
                 launch_tail_copies(sess_queue_.begin(), sess_queue_.end());
                 for (const PendingAdd& pa : sess_queue_) sess_count_[2] += pa.start;
-                FS_HIP(hipEventRecord(ev_pft_[1], st_pf_));
-                FS_HIP(hipEventRecord(ev_pf_, st_pf_));
-                sess_flight_ = std::move(sess_queue_);
-                sess_queue_.clear();
+                pass_launched(sess_queue_.size());
                 return;
             }
             if (flash && Lp <= kRowsCap) {
@@ -1587,10 +1583,7 @@ class LM final : public LMBase {
         }
         ++sess_count_[0];
         for (int s = 0; s < S; ++s) { sess_count_[1] += sess_queue_[i + s].rows(); sess_count_[2] += sess_queue_[i + s].create ? 0 : sess_queue_[i + s].start; }
-        FS_HIP(hipEventRecord(ev_pft_[1], st_pf_));
-        FS_HIP(hipEventRecord(ev_pf_, st_pf_));
-        sess_flight_.assign(std::make_move_iterator(sess_queue_.begin()), std::make_move_iterator(sess_queue_.begin() + S));
-        sess_queue_.erase(sess_queue_.begin(), sess_queue_.begin() + S);
+        pass_launched((size_t)S);
     }
     // copy-on-write of the partly filled last page of a prefix into the joining slot's first private page, for all members of a pass
     // that need it: ONE k_kv_page_copy launch over every slow layer's K and V pools, on the prefill stream ahead of the pass
@@ -1664,7 +1657,7 @@ class LM final : public LMBase {
                 RngState rng;
                 upload_rng(seed, rng, d_rrng_.as<RngState>() + b, st_);
                 FS_HIP(hipMemcpyAsync(d_rcfg_.as<SampleCfg>() + b, &cfg, sizeof(SampleCfg), hipMemcpyHostToDevice, st_));
-                launch_reppen_reset(rows_rp(b), a_.num_codebooks, a_.codebook_size, st_);
+                launch_reppen_reset(rrp_.view(b), a_.num_codebooks, a_.codebook_size, st_);
                 FS_HIP(hipStreamSynchronize(st_));  // (rng / budget are locals)
             } else {
                 if (sess_slots_) {  // the slot's settings, a StdRng stream at word 0 (no look-ahead word yet) and empty repetition-penalty windows
@@ -1675,21 +1668,16 @@ class LM final : public LMBase {
                     up_rng.push_back(sr);
                     FS_HIP(hipMemcpyAsync(d_scfg_.as<SampleCfg>() + b, &cfg, sizeof(SampleCfg), hipMemcpyHostToDevice, st_));
                     FS_HIP(hipMemcpyAsync(d_srng_.as<SlotRng>() + b, &up_rng.back(), sizeof(SlotRng), hipMemcpyHostToDevice, st_));
-                    launch_reppen_reset(slot_rp(b), a_.num_codebooks, a_.codebook_size, st_);
+                    launch_reppen_reset(srp_.view(b), a_.num_codebooks, a_.codebook_size, st_);
                 }
                 LmKernels<WT>::embed(d_, tok_emb_, cb_emb_, a_.num_codebooks, a_.codebook_size, d_cfg_.as<SampleCfg>(), nullptr, state(b),
                                      d_pfx_.as<float>() + (size_t)b * a_.dim, st_);
             }
-            if (pa.hid) {  // the slot collects from its first iteration on (the step that runs its last prompt position): row 0
-                sess_hid_[b].rows = pa.hid; sess_hid_[b].count = 0; sess_hid_[b].cap = pa.hid_cap;
-                FS_HIP(hipMemcpyAsync(d_hid_tab_.as<HidSlot>() + b, &sess_hid_[b], sizeof(HidSlot), hipMemcpyHostToDevice, st_));
-                ++sess_hid_live_;
-            }
-            if (pa.sc.p) {  // the slot is scored from its first iteration on: targets into its buffer, table entry with count 0
+            if (pa.hid.p) tab_activate(hid_, b, pa.hid);  // (its first iteration is the step that runs its last prompt position)
+            if (pa.sc.p) {  // the targets into the slot's buffer first
                 FS_REQUIRE(pa.n_iter <= pa.sc.cap && pa.sc_targets.size() == (size_t)pa.n_iter * C1, "score buffer shorter than the slot's iterations");
-                FS_HIP(hipMemcpyAsync(ScoreBook::targets_of(pa.sc), pa.sc_targets.data(), sizeof(uint32_t) * pa.sc_targets.size(), hipMemcpyHostToDevice, st_));
-                const ScoreSlot& e = sc_book_.activate(b, pa.sc);
-                FS_HIP(hipMemcpyAsync(d_sc_tab_.as<ScoreSlot>() + b, &e, sizeof(ScoreSlot), hipMemcpyHostToDevice, st_));
+                FS_HIP(hipMemcpyAsync(score_targets(pa.sc), pa.sc_targets.data(), sizeof(uint32_t) * pa.sc_targets.size(), hipMemcpyHostToDevice, st_));
+                tab_activate(sc_, b, pa.sc);
             }
             sess_left_[b] = pa.n_iter;
             sess_pos_[b] = Lp;
@@ -1732,7 +1720,7 @@ class LM final : public LMBase {
             activate_pending(/*wait=*/false);  // a finished prefill joins here, between two replays of the step graph
             int chunk = n_frames - launched, longest = 0, live = 0;
             for (int b = 0; b < B_; ++b)
-                if (sess_left_[b] > 0 && !sess_hs_[b].done) { chunk = std::min(chunk, sess_left_[b]); longest = std::max(longest, sess_pos_[b]); ++live; }
+                if (slot_running(b)) { chunk = std::min(chunk, sess_left_[b]); longest = std::max(longest, sess_pos_[b]); ++live; }
             if (!live && (!sess_flight_.empty() || !sess_queue_.empty())) {
                 // nothing else to run (a burst into an idle session): admit everything queued, group pass after group pass, then step
                 while (!sess_flight_.empty() || !sess_queue_.empty()) { flush_pending(); activate_pending(true); }
@@ -1746,13 +1734,13 @@ class LM final : public LMBase {
                 // live requests in slots 0, 1 pays the 2-row frame, 0.84 ms, not the 8-row one, 1.67 ms); slots are handed out lowest-first
                 int top = 0;
                 for (int b = 0; b < B_; ++b)
-                    if (sess_left_[b] > 0 && !sess_hs_[b].done) top = b + 1;
+                    if (slot_running(b)) top = b + 1;
                 const int Rs = std::min(sess_R_, top <= 2 ? 2 : (top <= 4 ? 4 : 8));
                 for (int i = 0; i < chunk; ++i) {
                     set_bucket(longest + i + 1);
                     launch_rows_slow(rows_slow_args(Rs), Rs, st_);
                     // (x(r) now holds row r's pre-norm hidden state; the fast launches overwrite it with the next input)
-                    if (sess_hid_live_ > 0) launch_hidden_rows(d_hid_tab_.as<HidSlot>(), state(0), x(0), a_.dim, top, st_);
+                    if (hid_.book.live() > 0) launch_hidden_rows(hid_.dev.as<HidSlot>(), state(0), x(0), a_.dim, top, st_);
                     launch_rows_fast_groups(top, sess_sampled_);
                 }
             } else
@@ -1762,7 +1750,7 @@ class LM final : public LMBase {
             }
             launched += chunk;
             for (int b = 0; b < B_; ++b)
-                if (sess_left_[b] > 0 && !sess_hs_[b].done) {
+                if (slot_running(b)) {
                     sess_left_[b] -= chunk; sess_pos_[b] += chunk;
                     if (sess_left_[b] == 0 && !sess_rows_) {  // iteration budget spent: the slot is finished whatever it sampled (rows mode: the kernels' own budget word terminates the row)
                         // Its last iteration left pos = L + n_iter - 1, one token PAST its page allocation (and == max_seq_len when the
@@ -1776,13 +1764,11 @@ class LM final : public LMBase {
                 }
             // (a slot that sampled <|im_end|> inside the chunk froze itself on the device; the host learns it below)
             FS_HIP(hipMemcpyAsync(sess_hs_.data(), state(0), sizeof(SeqState) * B_, hipMemcpyDeviceToHost, st_));
-            if (sess_hid_live_ > 0) FS_HIP(hipMemcpyAsync(sess_hid_.data(), d_hid_tab_.p, sizeof(HidSlot) * B_, hipMemcpyDeviceToHost, st_));  // (the row counts)
-            if (sc_book_.live() > 0) {
-                sess_sc_stage_.resize(B_);
-                FS_HIP(hipMemcpyAsync(sess_sc_stage_.data(), d_sc_tab_.p, sizeof(ScoreSlot) * B_, hipMemcpyDeviceToHost, st_));  // (the record counts)
-            }
+            tab_fetch_counts(hid_);  // (the row counts)
+            tab_fetch_counts(sc_);   // (the record counts)
             FS_HIP(hipStreamSynchronize(st_));
-            if (sc_book_.live() > 0) sc_book_.refresh_counts(sess_sc_stage_.data());
+            tab_take_counts(hid_);
+            tab_take_counts(sc_);
             // a spin timeout inside the chunk (the joining prefill shares the CUs the persistent launches need co-resident) means the slots'
             // codes are garbage: raise instead of handing them out; the caller ends the session (the handle is off the row path afterwards)
             if (sess_rows_) rows_check_ctl(/*include_b1_fast=*/false);
@@ -1797,7 +1783,7 @@ class LM final : public LMBase {
         int act = 0;
         uint64_t frames = 0;
         for (int b = 0; b < B_; ++b) {
-            if ((sess_left_[b] > 0 && !sess_hs_[b].done) || sess_left_[b] == -2) ++act;  // (-2: still prefilling)
+            if (slot_running(b) || slot_prefilling(b)) ++act;
             if (sess_left_[b] >= 0) frames += (uint64_t)sess_hs_[b].n_out;
         }
         stats_.frames = sess_released_frames_ + frames;
@@ -1805,9 +1791,9 @@ class LM final : public LMBase {
     }
     void session_poll(int slot, uint32_t* codes_out, size_t cap, size_t* n_frames, int* done) override {
         use_device();
-        FS_REQUIRE(sess_active_ && slot >= 0 && slot < B_ && sess_left_[slot] != -1, "not a live session slot");
+        require_live_slot(slot);
         const int C = a_.num_codebooks;
-        const size_t nb = sess_left_[slot] == -2 ? 0 : (size_t)sess_hs_[slot].n_out;  // (-2: still prefilling)
+        const size_t nb = slot_prefilling(slot) ? 0 : (size_t)sess_hs_[slot].n_out;
         if (codes_out) {
             FS_REQUIRE(nb <= cap, "codes_out capacity too small for the generated frames");
             for (int c = 0; c < C; ++c)
@@ -1816,35 +1802,27 @@ class LM final : public LMBase {
             FS_HIP(hipStreamSynchronize(st_));
         }
         if (n_frames) *n_frames = nb;
-        if (done) *done = (sess_left_[slot] != -2 && (sess_hs_[slot].done != 0 || sess_left_[slot] == 0)) ? 1 : 0;
+        if (done) *done = (!slot_prefilling(slot) && (sess_hs_[slot].done != 0 || sess_left_[slot] == 0)) ? 1 : 0;
     }
     void session_release(int slot) override {
         use_device();
-        FS_REQUIRE(sess_active_ && slot >= 0 && slot < B_ && sess_left_[slot] != -1, "not a live session slot");
-        while (sess_left_[slot] == -2) { flush_pending(); activate_pending(true); }  // (its prefill is queued or in flight: let it finish first)
+        require_live_slot(slot);
+        while (slot_prefilling(slot)) { flush_pending(); activate_pending(true); }  // (its prefill is queued or in flight: let it finish first)
         sess_released_frames_ += (uint64_t)sess_hs_[slot].n_out;
         truncate(slot, 0);
         park_slot(slot);
-        drop_hid_slot(slot);
-        sess_hid_want_[slot] = 0;
-        drop_score_slot(slot);
-        sess_left_[slot] = -1;
+        tab_drop(hid_, slot);
+        tab_drop(sc_, slot);
+        sess_left_[slot] = kSlotFree;
     }
     void session_end() override {
         if (!sess_active_) return;
         use_device();
         if (!sess_flight_.empty()) (void)hipEventSynchronize(ev_pf_);
         for (auto* q : {&sess_flight_, &sess_queue_})
-            for (const PendingAdd& pa : *q) {
-                if (pa.tail >= 0) put_page(pa.tail);
-                if (pa.hid) put_hid_buf(pa.hid, pa.hid_cap);
-                sc_book_.put(pa.sc);
-            }
-        for (HidSlot& h : sess_hid_) { if (h.rows) put_hid_buf(h.rows, h.cap); h = HidSlot{}; }
-        sess_hid_live_ = 0;
-        if (d_hid_tab_.p) FS_HIP(hipMemsetAsync(d_hid_tab_.p, 0, d_hid_tab_.n, st_));
-        sc_book_.end();
-        if (d_sc_tab_.p) FS_HIP(hipMemsetAsync(d_sc_tab_.p, 0, d_sc_tab_.n, st_));
+            for (const PendingAdd& pa : *q) if (pa.tail >= 0) put_page(pa.tail);
+        tab_end(hid_);  // (the collector buffers of those adds were in hand: the books take them back)
+        tab_end(sc_);
         sess_flight_.clear(); sess_queue_.clear();
         for (int b = 0; b < B_; ++b) truncate(b, 0);
         for (SessPrefix& px : sess_prefixes_) drop_prefix_pages(px);  // (live or not: the session's references end with it)
@@ -1968,7 +1946,7 @@ class LM final : public LMBase {
             FS_HIP(hipMemcpyAsync(d_cfg_.p, &cfgs[i], sizeof(SampleCfg), hipMemcpyHostToDevice, st_));  // (embed reads the semantic range from d_cfg_)
             RngState rng;
             upload_rng(seeds[i], rng, d_rrng_.as<RngState>() + i, st_);
-            launch_reppen_reset(rows_rp(i), C, a_.codebook_size, st_);
+            launch_reppen_reset(rrp_.view(i), C, a_.codebook_size, st_);
             prefill_tokens(i, L - 1, /*use_graph=*/false);
             LmKernels<WT>::embed(d_, tok_emb_, cb_emb_, C, a_.codebook_size, d_cfg_.as<SampleCfg>(), d_prompt_.as<uint32_t>(), state(i), x(i), st_);
             FS_HIP(hipStreamSynchronize(st_));  // d_prompt_ / d_cfg_ are reused by the next row
@@ -2355,13 +2333,7 @@ class LM final : public LMBase {
         d_prompt_.alloc(sizeof(uint32_t) * (size_t)(a_.num_codebooks + 1) * a_.max_seq_len);
         out_cap_ = a_.max_seq_len + 8;
         d_out_.alloc(sizeof(uint32_t) * (size_t)B_ * a_.num_codebooks * out_cap_);
-        const size_t ncb = a_.num_codebooks, cbs = a_.codebook_size;
-        d_rp_mask_.alloc(sizeof(float) * ncb * cbs);
-        d_rp_seen_.alloc(ncb * cbs);
-        d_rp_ring_.alloc(sizeof(int) * ncb * 17);
-        d_rp_meta_.alloc(sizeof(int) * ncb * 2);
-        rp_.mask = d_rp_mask_.as<float>(); rp_.seen = d_rp_seen_.as<uint8_t>(); rp_.ring = d_rp_ring_.as<int>();
-        rp_.ring_meta = d_rp_meta_.as<int>();
+        rp_.alloc(1, a_.num_codebooks, a_.codebook_size);
         FS_HIP(hipHostMalloc(&h_pin_, 4096, hipHostMallocDefault));
     }
 
@@ -2545,10 +2517,10 @@ class LM final : public LMBase {
         FS_HIP(hipMemcpy(d_epoch_.p, e0, sizeof(e0), hipMemcpyHostToDevice));
         d_fast_table_.alloc(sizeof(int) * B_);
         FS_HIP(hipMemcpy(d_fast_table_.p, tb.data(), sizeof(int) * B_, hipMemcpyHostToDevice));
-        d_hid_tab_.alloc(sizeof(HidSlot) * B_);
-        FS_HIP(hipMemset(d_hid_tab_.p, 0, d_hid_tab_.n));
-        d_sc_tab_.alloc(sizeof(ScoreSlot) * B_);
-        FS_HIP(hipMemset(d_sc_tab_.p, 0, d_sc_tab_.n));
+        hid_.dev.alloc(sizeof(HidSlot) * B_);
+        FS_HIP(hipMemset(hid_.dev.p, 0, hid_.dev.n));
+        sc_.dev.alloc(sizeof(ScoreSlot) * B_);
+        FS_HIP(hipMemset(sc_.dev.p, 0, sc_.dev.n));
     }
     // one static-batch frame for B rows: x rows (d_pfx_) hold the embedded inputs of position state(0)->pos
     void enqueue_batch_frame(int B) {
@@ -2566,7 +2538,7 @@ class LM final : public LMBase {
         RowKernels<WT>::rows_head(d_, B, cs, slow_head_w(), slow_head_s(), n_audio_, d_lrows_.as<float>(), ld_slow_, st_, fold);
         // session steps: the collecting slots' hidden-state rows (one node behind the slow head; null table entries exit at once, so the
         // one captured graph serves every mix of collecting and non-collecting slots)
-        if (sess_active_) launch_hidden_rows(d_hid_tab_.as<HidSlot>(), state(0), cs.X, a_.dim, B, st_);
+        if (sess_active_) launch_hidden_rows(hid_.dev.as<HidSlot>(), state(0), cs.X, a_.dim, B, st_);
         // block-parallel samplers (temp > 1e-7, top_k <= 256): the step's C + 1 StdRng words per row are derived up front
         const bool slots = sess_active_ && sess_slots_;  // FS_SESSION_PER_SLOT: the 9 sampler nodes are the per-slot ones, one for one
         const uint32_t* words = rows_par_ ? d_rwords_.as<uint32_t>() : nullptr;
@@ -2578,7 +2550,7 @@ class LM final : public LMBase {
         // FS_SESSION_SCORE: one score node in front of each per-slot sampler node, behind the capture of the raw row (null table entries
         // exit at once, so the one captured graph serves every mix of scoring and generating slots)
         const bool score = slots && sess_score_;
-        if (score) launch_score_slots(d_sc_tab_.as<ScoreSlot>(), state(0), d_scfg_.as<SampleCfg>(), d_lrows_.as<float>(), ld_slow_, n_audio_, 0, C, B, st_);
+        if (score) launch_score_slots(sc_.dev.as<ScoreSlot>(), state(0), d_scfg_.as<SampleCfg>(), d_lrows_.as<float>(), ld_slow_, n_audio_, 0, C, B, st_);
         if (slots)
             SampleKernels<WT>::sample_slow_slots(d_, d_lrows_.as<float>(), ld_slow_, n_audio_, d_scfg_.as<SampleCfg>(), d_srng_.as<SlotRng>(), B, state(0),
                                                  cs.X, d_xfrows_.as<float>(), st_, prep_g, cs.A, fold ? d_epoch_.as<uint32_t>() : nullptr,
@@ -2621,10 +2593,10 @@ class LM final : public LMBase {
             RowsCtx nf = fast_ctx(cbi + 1);
             const float* prep_f = nf.qkv0_tbl ? nullptr : prep_g;
             nf.first_prepped = prep_f != nullptr;
-            if (score) launch_score_slots(d_sc_tab_.as<ScoreSlot>(), state(0), d_scfg_.as<SampleCfg>(), d_lfast_.as<float>(), a_.codebook_size, a_.codebook_size,
+            if (score) launch_score_slots(sc_.dev.as<ScoreSlot>(), state(0), d_scfg_.as<SampleCfg>(), d_lfast_.as<float>(), a_.codebook_size, a_.codebook_size,
                                           1 + cbi, C, B, st_);
             if (slots) {
-                RepPenState rp0 = slot_rp(0);
+                RepPenState rp0 = srp_.view(0);
                 SampleKernels<WT>::sample_fast_slots(d_, d_lfast_.as<float>(), cbi, C, a_.codebook_size, d_scfg_.as<SampleCfg>(), d_srng_.as<SlotRng>(), rp0,
                                                      B, state(0), fast_emb_, d_xfrows_.as<float>(), tok_emb_, cb_emb_, cs.X, d_out_.as<uint32_t>(), out_cap_,
                                                      st_, prep_f, cs.A, sess_wide_);
@@ -2814,7 +2786,7 @@ class LM final : public LMBase {
         A.xf = fold ? x(0) : xf(0); A.x = x(0);
         A.slow_logits = fold ? d_logits_slow_.as<float>() : nullptr; A.n_slow = n_audio_; A.hid_slot = d_hid_slot_.as<float*>();
         A.cap = d_cap_.as<float>(); A.cap_frames = cap_frames_;
-        A.state = state(0); A.cfg = d_cfg_.as<SampleCfg>(); A.rp = rp_; A.rng = d_rng_.as<RngState>();
+        A.state = state(0); A.cfg = d_cfg_.as<SampleCfg>(); A.rp = rp_.view(0); A.rng = d_rng_.as<RngState>();
         A.out_codes = d_out_.as<uint32_t>(); A.out_cap = out_cap_;
         A.edges = d_edges_.as<unsigned long long>();
         A.ctl = d_ctl_.as<uint32_t>();
@@ -2853,24 +2825,13 @@ class LM final : public LMBase {
                 d_rcfg_.alloc(sizeof(SampleCfg) * PR_MAX_ROWS);
                 d_rrng_.alloc(sizeof(RngState) * PR_MAX_ROWS);
                 d_rbudget_.alloc(sizeof(int) * PR_MAX_ROWS);
-                const size_t ncb = a_.num_codebooks, cbs = a_.codebook_size;
-                d_rrp_mask_.alloc(sizeof(float) * PR_MAX_ROWS * ncb * cbs);
-                d_rrp_seen_.alloc((size_t)PR_MAX_ROWS * ncb * cbs);
-                d_rrp_ring_.alloc(sizeof(int) * PR_MAX_ROWS * ncb * 17);
-                d_rrp_meta_.alloc(sizeof(int) * PR_MAX_ROWS * ncb * 2);
+                rrp_.alloc(PR_MAX_ROWS, a_.num_codebooks, a_.codebook_size);
                 FS_HIP(hipStreamSynchronize(st_));
             }
             (void)R;
         } else {
             throw Error("request rows need a bf16 or fp8 handle");
         }
-    }
-    RepPenState rows_rp(int i) {
-        const size_t ncb = a_.num_codebooks, cbs = a_.codebook_size;
-        RepPenState rp;
-        rp.mask = d_rrp_mask_.as<float>() + (size_t)i * ncb * cbs; rp.seen = d_rrp_seen_.as<uint8_t>() + (size_t)i * ncb * cbs;
-        rp.ring = d_rrp_ring_.as<int>() + (size_t)i * ncb * 17; rp.ring_meta = d_rrp_meta_.as<int>() + (size_t)i * ncb * 2;
-        return rp;
     }
     static constexpr int kNapsRowsSlow[6] = {28, 4, 8, 40, 24, 28}, kNapsRowsFast[6] = {20, 16, 16, 16, 20, 20};  // tools/tune_naps_rows.py at R = 4 (945 -> 933 us per frame; re-tuned after the half-block S2)
     RowsSlowArgs rows_slow_args(int R) {
@@ -2906,7 +2867,7 @@ class LM final : public LMBase {
         A.slow_logits = d_rlogits_.as<float>() + (size_t)r0 * PR_LD; A.n_slow = n_audio_;
         A.cap = cap_frames_ ? d_rcap_.as<float>() + (size_t)r0 * cap_frames_ * 9 * 2048 : nullptr; A.cap_frames = cap_frames_;
         A.state = state(r0); A.cfg = d_rcfg_.as<SampleCfg>() + r0; A.budget = d_rbudget_.as<int>() + r0; A.rng = d_rrng_.as<RngState>() + r0;
-        const RepPenState rp = rows_rp(r0);
+        const RepPenState rp = rrp_.view(r0);
         A.rp_mask = rp.mask; A.rp_ring = rp.ring; A.rp_meta = rp.ring_meta;
         A.out_codes = d_out_.as<uint32_t>() + (size_t)r0 * a_.num_codebooks * out_cap_; A.out_cap = out_cap_;
         A.edges = d_redges_f_.as<unsigned long long>();
@@ -2922,7 +2883,7 @@ class LM final : public LMBase {
         A.xf = x(i); A.x = x(i);
         A.slow_logits = d_rlogits_.as<float>() + (size_t)i * PR_LD;
         A.cap = cap_frames_ ? d_rcap_.as<float>() + (size_t)i * cap_frames_ * 9 * 2048 : nullptr;
-        A.state = state(i); A.cfg = d_rcfg_.as<SampleCfg>() + i; A.rp = rows_rp(i); A.rng = d_rrng_.as<RngState>() + i;
+        A.state = state(i); A.cfg = d_rcfg_.as<SampleCfg>() + i; A.rp = rrp_.view(i); A.rng = d_rrng_.as<RngState>() + i;
         A.out_codes = d_out_.as<uint32_t>() + (size_t)i * a_.num_codebooks * out_cap_;
         return A;
     }
@@ -3000,7 +2961,7 @@ class LM final : public LMBase {
             enqueue_fast_layers(0, cbi, cbi);
             LmKernels<WT>::head(d_, xf(0), fast_norm_w_, fast_out_w_, fast_out_s_, a_.codebook_size, d_logits_fast_.as<float>(), st_);
             SampleKernels<WT>::sample_fast(d_, d_logits_fast_.as<float>(), cbi, C, a_.codebook_size, d_cfg_.as<SampleCfg>(),
-                                           d_rng_.as<RngState>(), rp_, state(0), fast_emb_, xf(0), tok_emb_, cb_emb_, x(0),
+                                           d_rng_.as<RngState>(), rp_.view(0), state(0), fast_emb_, xf(0), tok_emb_, cb_emb_, x(0),
                                            d_out_.as<uint32_t>(), out_cap_, st_);
         }
         FS_HIP(hipStreamEndCapture(st_, &g));
@@ -3063,7 +3024,7 @@ class LM final : public LMBase {
     std::vector<std::vector<int>> seq_pages_;
     // activations / state
     DevBuf d_x_, d_xf_, d_q_, d_part_, d_act_, d_logits_slow_, d_logits_fast_, d_state_, d_cfg_, d_rng_, d_prompt_, d_out_;
-    DevBuf d_rp_mask_, d_rp_seen_, d_rp_ring_, d_rp_meta_;
+    RepPenBufs rp_, srp_, rrp_;  // repetition-penalty state: the batch-1 generator's (1 row), the per-slot samplers' [max_batch] (allocated with d_scfg_), the request rows' [PR_MAX_ROWS] (ensure_rows)
     DevBuf d_pack_, d_edges_, d_ctl_, d_qkv0_;  // persistent fast decoder (+ the layer-0 qkv table of the codebook passes 1..7)
     DevBuf d_fscl_, d_sscl_;           // FS_FP8 handles: row scales of the persistent kernels' images
     DevBuf d_cap_;                     // fs_lm_debug_capture
@@ -3076,7 +3037,7 @@ class LM final : public LMBase {
     bool sess_slots_ = false;  // FS_SESSION_PER_SLOT (slots on the static-batch step with the per-slot samplers)
     bool sess_wide_ = false;   // FS_SESSION_WIDE_SAMPLER (the per-slot sampler nodes that also take nucleus-only / top_k > 256 settings)
     SampleCfg sess_cfg_ = {};  // the session's own SampleCfg (slots admitted without settings of their own)
-    DevBuf d_scfg_, d_srng_, d_srp_mask_, d_srp_seen_, d_srp_ring_, d_srp_meta_;  // per-slot sampler state [max_batch] (k_sample_*_slots)
+    DevBuf d_scfg_, d_srng_;   // per-slot sampler state [max_batch] (k_sample_*_slots)
     int sess_R_ = 0, sess_adds_ = 0, sess_budget_tmp_ = 0;
     uint64_t sess_seed_ = 0;
     std::unique_lock<PersistLock> sess_plock_;
@@ -3102,20 +3063,9 @@ class LM final : public LMBase {
     std::vector<int> sess_stage_imp_pages_;
     bool fp_valid_ = false;
     uint64_t fp_ = 0;
-    // hidden-state collection (fs_lm_session_add_hidden): the device table the step's k_hidden_rows node reads (allocated once per handle:
-    // the captured step graphs hold its address), its host mirror (rows / cap as uploaded, count as of the last step), the slots admitted
-    // as collectors, how many of them are live, and the handle's pool of free row buffers (device pointer, capacity in rows)
-    DevBuf d_hid_tab_;
-    std::vector<HidSlot> sess_hid_;
-    std::vector<char> sess_hid_want_;
-    int sess_hid_live_ = 0;
-    std::vector<std::pair<float*, int>> hid_pool_;
-    // scoring slots (fs_lm_session_add_scored): the device table the step's k_score_slots nodes read (allocated once per handle, like
-    // d_hid_tab_), its host mirror + the buffer pool (fs_score_book.h), and the landing place of the end-of-chunk copy of the counts
+    SlotTab<HidSlot> hid_;    // hidden-state collectors (fs_lm_session_add_hidden): the table of the step's k_hidden_rows node
+    SlotTab<ScoreSlot> sc_;   // scoring slots (fs_lm_session_add_scored): the table of the step's k_score_slots nodes
     bool sess_score_ = false;  // FS_SESSION_SCORE (the session's step graphs carry the 9 score nodes)
-    DevBuf d_sc_tab_;
-    ScoreBook sc_book_{&sc_alloc, &sc_free};
-    std::vector<ScoreSlot> sess_sc_stage_;
     SeqState sess_stage_ = {};
     hipStream_t st_pf_ = nullptr;
     hipEvent_t ev_pf_ = nullptr;
@@ -3129,9 +3079,8 @@ class LM final : public LMBase {
     int ld_slow_ = 0, down_split_ = 4;
     bool fold_off_ = false;  // set after a reported exchange timeout of the folded decode step: the handle keeps the slab path from then on
     std::map<int, hipGraphExec_t> batch_graphs_;
-    RepPenState rp_ = {};
     DevBuf d_rimg_, d_rhimg_, d_redges_s_, d_redges_f_, d_rctl_s_, d_rctl_f_, d_rlogits_, d_rcfg_, d_rrng_, d_rbudget_;  // request rows (lm_persist_rows.hip)
-    DevBuf d_rrp_mask_, d_rrp_seen_, d_rrp_ring_, d_rrp_meta_, d_rcap_, d_rpairs_, d_rones_;
+    DevBuf d_rcap_, d_rpairs_, d_rones_;
     void* h_pin_ = nullptr;
     hipGraphExec_t g_frame_ = nullptr, g_step_ = nullptr;
     hipEvent_t ev_[3] = {nullptr, nullptr, nullptr};

@@ -16,7 +16,7 @@
 #include <cstdint>
 
 #include "fs_common.h"
-#include "fs_score_book.h"
+#include "fs_slot_book.h"
 
 namespace fs {
 
@@ -301,17 +301,12 @@ void launch_kv_rows_scatter(void* pool, int n_regions, size_t region_bytes, size
                             size_t elem_bytes, const void* packed, hipStream_t st);
 // k_arena_fingerprint: *acc (device, zeroed by the caller) += sum_i w[i] * (2 i + 1) mod 2^64 over the bytes / 4 32-bit words of the arena
 void launch_arena_fingerprint(const void* arena, size_t bytes, uint64_t* acc, hipStream_t st);
-// Hidden-state collection of session slots (fishrt.h: fs_lm_session_add_hidden).  One entry per slot: rows == null -> the slot does not
-// collect; else its buffer f32 [cap][dim], and count = rows stored so far == the slot's generator iterations so far.
-struct HidSlot {
-    float* rows;
-    int count, cap;
-};
-// after the slow transformer of a step, before the slow-token decision: block b appends X[b] (the pre-norm residual row the head's
+// Hidden-state collection of session slots (fishrt.h: fs_lm_session_add_hidden): the per-slot table is fs_slot_book.h's HidSlot.
+// After the slow transformer of a step, before the slow-token decision: block b appends X[b] (the pre-norm residual row the head's
 // RMSNorm reads) to tab[b].rows when the slot collects and runs this iteration (states[b].done == 0); everything else exits at once.
 // dim % 4 == 0, X and the buffers 16-byte aligned.  ONE launch (a graph node of the session step: the table is read through pointers).
 void launch_hidden_rows(HidSlot* tab, const SeqState* states, const float* X, int dim, int B, hipStream_t st);
-// Scoring slots of a FS_SESSION_SCORE session (fishrt.h: fs_lm_session_add_scored): the per-slot table is fs_score_book.h's ScoreSlot.
+// Scoring slots of a FS_SESSION_SCORE session (fishrt.h: fs_lm_session_add_scored): the per-slot table is fs_slot_book.h's ScoreSlot.
 // In front of the per-slot sampler node of decision `decision` (0 = slow token over n candidates of rows ld apart; 1 + c = codebook c):
 // block b records f32 log-softmax figures of logits row b for the slot's target (candidate 0 left out of a slow decision when
 // cfgs[b].ignore_eos), then stores +INFINITY over the target's logit so that the greedy sampler behind it picks the target; at the last

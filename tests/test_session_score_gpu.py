@@ -303,6 +303,41 @@ def test_bookkeeping(lm16):
         assert all(s.poll_scores(sl)["logprob"].shape == (1, 9) for sl in others)
 
 
+def test_collector_kinds_swap_slots_and_reuse_each_others_buffers(lm16):
+    """A hidden-state collector and a scoring slot leave, and each kind is re-admitted into the slot the OTHER kind held: both tables
+    and the two buffer pools meet here.  Reuse against fresh on the same handle: bit-equal, no tolerance."""
+    L, N = 5, 3
+    pa, pb, fb = _prompt(L, 61), _prompt(L, 62), _frames(N, 63)
+    kw = dict(temp=0.0, top_p=1.0, top_k=0, seed=5, ignore_eos=True, per_slot=True, score=True, repetition_penalty=1.0)
+
+    def second_round(s):  # B' (scored, collecting) first, then A': slots are handed out lowest-first
+        b2 = s.add_scored(pb, fb, collect_hidden=True)
+        a2 = s.add(pa, L + N - 2, seed=77, collect_hidden=True)
+        rows0 = (s.poll_hidden(a2).shape[0], s.poll_hidden(b2).shape[0], s.poll_scores(b2)["logprob"].shape[0])
+        _run_all(s)
+        return a2, b2, rows0, s.poll(a2)[0], s.poll_hidden(a2), s.poll_scores(b2), s.poll_hidden(b2)
+
+    with lm16.session(**kw) as s:  # the fresh run
+        _, _, _, _, _, sc_ref, hid_b_ref = second_round(s)
+    with lm16.session(**kw) as s:
+        a = s.add(pa, L + N - 2, seed=77, collect_hidden=True)
+        b = s.add_scored(pb, fb)
+        assert (a, b) == (0, 1)
+        _run_all(s)
+        codes_a, hid_a, sc_b = s.poll(a)[0], s.poll_hidden(a), s.poll_scores(b)
+        s.release(a)
+        s.release(b)
+        a2, b2, rows0, codes_a2, hid_a2, sc_b2, hid_b2 = second_round(s)
+    assert (b2, a2) == (a, b), "each kind must land in the slot the other kind left"
+    assert rows0 == (0, 0, 0), "a re-admitted slot of either kind starts at row 0"
+    assert codes_a.shape == (8, N) and hid_a.shape == (N, CFG["dim"]) and sc_b["logprob"].shape == (N, 9)
+    assert hid_a2.shape == hid_a.shape and hid_b2.shape == (N, CFG["dim"]) and sc_b2["logprob"].shape == (N, 9)
+    assert np.array_equal(codes_a2, codes_a) and np.array_equal(hid_a2.view(np.uint32), hid_a.view(np.uint32)), "A' differs from A"
+    for k in ("logprob", "top_logprob", "top", "eos_logprob"):
+        assert np.array_equal(sc_b2[k].view(np.uint32), sc_ref[k].view(np.uint32)), f"B' {k}: reuse differs from fresh"
+    assert np.array_equal(hid_b2[:N].view(np.uint32), hid_b_ref[:N].view(np.uint32)), "B' hidden rows: reuse differs from fresh"
+
+
 def test_errors_name_their_field_and_leave_the_session_as_it_was(lm16):
     L = fishrt.lib()
     p, f = _prompt(19, 7), _frames(6, 8)
