@@ -287,6 +287,16 @@ int fs_lm_session_poll_scores(fs_lm_t* lm, int slot, size_t first_row, float* lo
     FS_ARG(lm, "null argument");
     FS_TRY(lm->impl->session_poll_scores(slot, first_row, logprob, top_logprob, top, eos_logprob, cap_rows, n_rows))
 }
+int fs_lm_session_add_traced(fs_lm_t* lm, int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling,
+                             const uint64_t* seed, int collect_hidden, int* slot) {
+    FS_ARG(lm && prompt && slot, "null argument");
+    FS_TRY(*slot = lm->impl->session_add_traced(prefix_id, prompt, L, max_new_tokens, sampling, seed, collect_hidden))
+}
+int fs_lm_session_poll_trace(fs_lm_t* lm, int slot, size_t first_row, uint32_t* tokens, float* logprob, float* top_logprob, uint32_t* top,
+                             float* eos_logprob, int* n_decisions, size_t cap_rows, size_t* n_rows) {
+    FS_ARG(lm, "null argument");
+    FS_TRY(lm->impl->session_poll_trace(slot, first_row, tokens, logprob, top_logprob, top, eos_logprob, n_decisions, cap_rows, n_rows))
+}
 int fs_lm_session_info(fs_lm_t* lm, int64_t out[8]) { FS_ARG(lm && out, "null argument"); FS_TRY(lm->impl->session_info(out)) }
 int fs_lm_last_stats(fs_lm_t* lm, fs_gen_stats* out) { FS_ARG(lm && out, "null argument"); FS_TRY(*out = lm->impl->last_stats()) }
 void* fs_lm_stream(fs_lm_t* lm) { return lm ? lm->impl->stream() : nullptr; }

@@ -15,6 +15,8 @@ namespace fs {
 // One entry per slot: rec == null -> the slot is not scored; else iteration `count` of the slot is forced to targets[count][0 .. C]
 // (slow token, c0..c7) and leaves the 32-word record rec[count]: [0..8] logprob of the target per decision, [9..17] logprob of the
 // maximum, [18..26] the last maximal index (u32 bits), [27] logprob of <|im_end|> at the slow decision (-inf when masked), [28..31] zero.
+// A TRACED slot (fs_lm_session_add_traced) is an entry of this table whose DEVICE copy has targets == null: it samples, its record rows
+// hold the same figures for its own picks, and the rows behind the records ([cap][C + 1] u32, the host entry's `targets`) receive the picks.
 struct ScoreSlot {
     const uint32_t* targets;  // [cap][C + 1]
     float* rec;               // [cap][32]

@@ -62,6 +62,11 @@ class LMBase {
     virtual int session_add_scored(int prefix_id, const uint32_t* prompt, int L, const uint32_t* frames, int N, int collect_hidden) = 0;
     virtual void session_poll_scores(int slot, size_t first_row, float* logprob, float* top_logprob, uint32_t* top, float* eos_logprob,
                                      size_t cap_rows, size_t* n_rows) = 0;
+    // fishrt.h: fs_lm_session_add_traced / fs_lm_session_poll_trace
+    virtual int session_add_traced(int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling,
+                                   const uint64_t* seed, int collect_hidden) = 0;
+    virtual void session_poll_trace(int slot, size_t first_row, uint32_t* tokens, float* logprob, float* top_logprob, uint32_t* top,
+                                    float* eos_logprob, int* n_decisions, size_t cap_rows, size_t* n_rows) = 0;
     virtual void debug_capture(int n_frames) = 0;
     virtual void debug_read(float* out, int n_frames) = 0;
     virtual void debug_read_row(int row, float* out, int n_frames) = 0;

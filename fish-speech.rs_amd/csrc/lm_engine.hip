@@ -928,6 +928,14 @@ class LM final : public LMBase {
                 throw Error("FS_SESSION_SCORE needs the Fish 1.5 token layout (has_semantic_end != 0): a Fish <= 1.4 handle has no slow-token distribution to score");
             FS_REQUIRE(a_.num_codebooks == 8, "FS_SESSION_SCORE needs num_codebooks == 8 (the score record holds 9 decisions per iteration)");
         }
+        // FS_SESSION_TRACE: the score nodes of the session also serve TRACED slots (fs_lm_session_add_traced: they sample, and leave the
+        // scoring slots' record of their own picks), and one tail node behind the frame's last sampler closes their rows (k_trace_commit)
+        const bool trace = (flags & FS_SESSION_TRACE) != 0;
+        if (trace) {
+            if (flags & FS_SESSION_ROWS) throw Error("FS_SESSION_TRACE is valid only together with FS_SESSION_PER_SLOT | FS_SESSION_SCORE: not with FS_SESSION_ROWS");
+            if (!(flags & FS_SESSION_PER_SLOT)) throw Error("FS_SESSION_TRACE is valid only together with FS_SESSION_PER_SLOT | FS_SESSION_SCORE: not alone");
+            if (!score) throw Error("FS_SESSION_TRACE is valid only together with FS_SESSION_PER_SLOT | FS_SESSION_SCORE: not without FS_SESSION_SCORE");
+        }
         // Fish <= 1.4 handles (no semantic range: the slow token is the 2-way {pad, im_end} draw): only the per-slot samplers define that
         // decision for a slot (k_sample_slow_slots, as the slot's own fs_lm_generate call); the lock-step sampler and the request-row
         // kernels do not
@@ -956,6 +964,7 @@ class LM final : public LMBase {
         sess_slots_ = false;
         sess_wide_ = false;
         sess_score_ = false;
+        sess_trace_ = false;
         std::unique_lock<PersistLock> rows_lock;
         struct RowsGuard {  // anything thrown below leaves the handle out of row mode (the local lock releases itself)
             bool& flag; bool armed = true;
@@ -1017,6 +1026,12 @@ class LM final : public LMBase {
         sess_prefixes_.clear();
         tab_begin(hid_, sizeof(float) * (size_t)a_.dim);
         tab_begin(sc_, sizeof(float) * SCORE_REC_WORDS + sizeof(uint32_t) * ((size_t)a_.num_codebooks + 1));
+        sess_traced_.assign(B_, 0);
+        if (trace) {
+            // the traced slots' stash, allocated once per handle (the captured step graphs of trace sessions hold its address); no row is open
+            if (!d_trace_.p) d_trace_.alloc(sizeof(float) * (size_t)B_ * TRACE_STASH_WORDS);
+            FS_HIP(hipMemsetAsync(d_trace_.p, 0, d_trace_.n, st_));
+        }
         for (auto& v : sess_count_) v = 0;
         sess_pf_ms_ = 0.0;
         sess_timed_ = false;
@@ -1029,6 +1044,7 @@ class LM final : public LMBase {
         sess_slots_ = per_slot;
         sess_wide_ = wide;
         sess_score_ = score;
+        sess_trace_ = trace;
         sess_active_ = true;
     }
     // what a slot of a FS_SESSION_PER_SLOT session may sample with: the boundary of the in-launch samplers (fishrt.h: fs_lm_generate)
@@ -1178,7 +1194,7 @@ class LM final : public LMBase {
         FS_REQUIRE(sess_active_, "no open session");
         FS_REQUIRE(sess_score_, "fs_lm_session_poll_scores needs FS_SESSION_SCORE (begin the session with FS_SESSION_PER_SLOT | FS_SESSION_SCORE)");
         require_live_slot(slot);
-        FS_REQUIRE(sc_.book.wanted(slot), "the slot is not a scoring slot (it was not admitted with fs_lm_session_add_scored)");
+        FS_REQUIRE(sc_.book.wanted(slot) && !sess_traced_[slot], "the slot is not a scoring slot (it was not admitted with fs_lm_session_add_scored)");
         const ScoreSlot& e = sc_.book.entry(slot);
         const size_t n = slot_prefilling(slot) ? 0 : (size_t)e.count;
         if ((logprob || top_logprob || top || eos_logprob) && first_row < n) {
@@ -1194,6 +1210,68 @@ class LM final : public LMBase {
                     if (top) std::memcpy(&top[i * C1 + d], &r[18 + d], sizeof(uint32_t));
                 }
                 if (eos_logprob) eos_logprob[i] = r[27];
+            }
+        }
+        if (n_rows) *n_rows = n;
+    }
+    // fs_lm_session_add_traced: session_add_ex (session_add_hidden with collect_hidden) whose slot also leaves the score record of its own
+    // picks.  Its table entry is a scoring slot's without targets, from the same book (same buffers: records [cap][32] f32, then the
+    // token rows [cap][C + 1] u32 where a scoring slot keeps its targets); the buffer, one row per iteration the slot can run, is taken
+    // BEFORE the add and goes back when the add is refused.  A seed of its own -- the one it would have had anyway when the caller gives
+    // none -- gives it a prefill pass of its own, so its records are a function of the request alone.
+    int session_add_traced(int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling, const uint64_t* seed,
+                           int collect_hidden) override {
+        use_device();
+        FS_REQUIRE(sess_active_, "no open session");
+        FS_REQUIRE(sess_trace_, "fs_lm_session_add_traced needs FS_SESSION_TRACE (begin the session with FS_SESSION_PER_SLOT | FS_SESSION_SCORE | FS_SESSION_TRACE)");
+        FS_REQUIRE(L >= 1, "empty prompt");
+        const long long Lt = (long long)L + (prefix_id >= 0 ? live_prefix(prefix_id).P : 0);
+        const long long n_iter = std::max<long long>(1, iter_budget(max_new_tokens, Lt).n_iter);  // (Lt > max_seq_len: the add below throws)
+        SlotBuf buf = sc_.book.take((int)n_iter);
+        const uint64_t own = seed ? *seed : sess_seed_ + (uint64_t)sess_adds_;
+        int b = -1;
+        try {
+            b = collect_hidden ? session_add_hidden(prefix_id, prompt, L, max_new_tokens, sampling, &own)
+                               : session_add_ex(prefix_id, prompt, L, max_new_tokens, sampling, &own);
+        } catch (...) { sc_.book.put(buf); throw; }
+        if (b < 0) { sc_.book.put(buf); return b; }
+        PendingAdd& pa = sess_queue_.back();
+        FS_REQUIRE(pa.n_iter <= buf.cap, "trace buffer shorter than the slot's iteration budget");
+        pa.sc = buf;
+        pa.traced = true;
+        sc_.book.admitted(b);
+        sess_traced_[b] = 1;
+        return b;
+    }
+    void session_poll_trace(int slot, size_t first_row, uint32_t* tokens, float* logprob, float* top_logprob, uint32_t* top, float* eos_logprob,
+                            int* n_decisions, size_t cap_rows, size_t* n_rows) override {
+        use_device();
+        FS_REQUIRE(sess_active_, "no open session");
+        FS_REQUIRE(sess_trace_, "fs_lm_session_poll_trace needs FS_SESSION_TRACE (begin the session with FS_SESSION_PER_SLOT | FS_SESSION_SCORE | FS_SESSION_TRACE)");
+        require_live_slot(slot);
+        FS_REQUIRE(sc_.book.wanted(slot) && sess_traced_[slot], "the slot is not a traced slot (it was not admitted with fs_lm_session_add_traced)");
+        const ScoreSlot& e = sc_.book.entry(slot);
+        const size_t n = slot_prefilling(slot) ? 0 : (size_t)e.count;
+        if ((tokens || logprob || top_logprob || top || eos_logprob || n_decisions) && first_row < n) {
+            const size_t m = std::min(n - first_row, cap_rows), C1 = (size_t)a_.num_codebooks + 1;
+            std::vector<float> rec(m * SCORE_REC_WORDS);
+            std::vector<uint32_t> tk(m * C1);
+            if (m) {
+                FS_HIP(hipMemcpyAsync(rec.data(), e.rec + first_row * SCORE_REC_WORDS, sizeof(float) * rec.size(), hipMemcpyDeviceToHost, st_));
+                FS_HIP(hipMemcpyAsync(tk.data(), e.targets + first_row * C1, sizeof(uint32_t) * tk.size(), hipMemcpyDeviceToHost, st_));
+            }
+            FS_HIP(hipStreamSynchronize(st_));
+            for (size_t i = 0; i < m; ++i) {
+                const float* r = rec.data() + i * SCORE_REC_WORDS;
+                for (size_t d = 0; d < C1; ++d) {
+                    if (tokens) tokens[i * C1 + d] = tk[i * C1 + d];
+                    if (logprob) logprob[i * C1 + d] = r[d];
+                    if (top_logprob) top_logprob[i * C1 + d] = r[9 + d];
+                    if (top) std::memcpy(&top[i * C1 + d], &r[18 + d], sizeof(uint32_t));
+                }
+                if (eos_logprob) eos_logprob[i] = r[27];
+                // (an iteration whose slow pick was <|im_end|> made that one decision; tokens[.][0] is then <|im_end|>'s id)
+                if (n_decisions) n_decisions[i] = tk[i * C1] == t_.im_end_id ? 1 : (int)C1;
             }
         }
         if (n_rows) *n_rows = n;
@@ -1234,6 +1312,7 @@ class LM final : public LMBase {
         SlotBuf hid;                       // fs_lm_session_add_hidden: the slot's row buffer [cap][dim], handed to the device table at activation
         SlotBuf sc;                        // fs_lm_session_add_scored: the slot's records + targets buffer, likewise (both in hand until then)
         std::vector<uint32_t> sc_targets;  // ... and the staged targets [n_iter][C + 1], copied into the buffer then
+        bool traced = false;               // fs_lm_session_add_traced: `sc` is the slot's records + token rows; its table entry has no targets
         std::vector<uint32_t> prompt;
         int rows() const { return import_kv ? 0 : (create ? L : L - start - 1); }   // tokens this member runs through the slow transformer
         int cols() const { return create ? L : L - start; }       // columns of `prompt`
@@ -1626,6 +1705,8 @@ class LM final : public LMBase {
         // per-slot sampler streams of the joining slots, staged here until the stream has been waited for below
         std::vector<SlotRng> up_rng;
         up_rng.reserve(sess_flight_.size());
+        std::vector<ScoreSlot> up_tr;  // ... and the device table entries of the traced ones
+        up_tr.reserve(sess_flight_.size());
         for (const PendingAdd& pa : sess_flight_) {
             if (pa.create) {  // the prefix's K/V are in place: its pad pages go back; a prefix released meanwhile goes now
                 SessPrefix& px = sess_prefixes_[pa.prefix];
@@ -1674,7 +1755,12 @@ class LM final : public LMBase {
                                      d_pfx_.as<float>() + (size_t)b * a_.dim, st_);
             }
             if (pa.hid.p) tab_activate(hid_, b, pa.hid);  // (its first iteration is the step that runs its last prompt position)
-            if (pa.sc.p) {  // the targets into the slot's buffer first
+            if (pa.sc.p && pa.traced) {  // a traced slot: the device entry is a scoring slot's WITHOUT targets (the book's own keeps the pointer:
+                // the token rows live there).  No row of the stash is open between two steps: the tail node closes what a step opened.
+                up_tr.push_back(sc_.book.activate(b, pa.sc));
+                up_tr.back().targets = nullptr;
+                FS_HIP(hipMemcpyAsync(sc_.dev.as<ScoreSlot>() + b, &up_tr.back(), sizeof(ScoreSlot), hipMemcpyHostToDevice, st_));
+            } else if (pa.sc.p) {  // the targets into the slot's buffer first
                 FS_REQUIRE(pa.n_iter <= pa.sc.cap && pa.sc_targets.size() == (size_t)pa.n_iter * C1, "score buffer shorter than the slot's iterations");
                 FS_HIP(hipMemcpyAsync(score_targets(pa.sc), pa.sc_targets.data(), sizeof(uint32_t) * pa.sc_targets.size(), hipMemcpyHostToDevice, st_));
                 tab_activate(sc_, b, pa.sc);
@@ -1813,6 +1899,7 @@ class LM final : public LMBase {
         park_slot(slot);
         tab_drop(hid_, slot);
         tab_drop(sc_, slot);
+        sess_traced_[slot] = 0;
         sess_left_[slot] = kSlotFree;
     }
     void session_end() override {
@@ -1835,6 +1922,7 @@ class LM final : public LMBase {
         sess_slots_ = false;
         sess_wide_ = false;
         sess_score_ = false;
+        sess_trace_ = false;
         sess_released_frames_ = 0;
         if (sess_rows_) check_ctl({&d_rctl_s_, &d_rctl_f_}, nullptr, nullptr);  // (a session that ended on an error: reset only)
         sess_rows_ = false;
@@ -2550,7 +2638,10 @@ class LM final : public LMBase {
         // FS_SESSION_SCORE: one score node in front of each per-slot sampler node, behind the capture of the raw row (null table entries
         // exit at once, so the one captured graph serves every mix of scoring and generating slots)
         const bool score = slots && sess_score_;
-        if (score) launch_score_slots(sc_.dev.as<ScoreSlot>(), state(0), d_scfg_.as<SampleCfg>(), d_lrows_.as<float>(), ld_slow_, n_audio_, 0, C, B, st_);
+        // FS_SESSION_TRACE: the score nodes know the traced slots' stash, and one tail node behind the last sampler closes their rows
+        const bool trace = score && sess_trace_;
+        float* stash = trace ? d_trace_.as<float>() : nullptr;
+        if (score) launch_score_slots(sc_.dev.as<ScoreSlot>(), state(0), d_scfg_.as<SampleCfg>(), d_lrows_.as<float>(), ld_slow_, n_audio_, 0, C, B, st_, stash);
         if (slots)
             SampleKernels<WT>::sample_slow_slots(d_, d_lrows_.as<float>(), ld_slow_, n_audio_, d_scfg_.as<SampleCfg>(), d_srng_.as<SlotRng>(), B, state(0),
                                                  cs.X, d_xfrows_.as<float>(), st_, prep_g, cs.A, fold ? d_epoch_.as<uint32_t>() : nullptr,
@@ -2594,7 +2685,7 @@ class LM final : public LMBase {
             const float* prep_f = nf.qkv0_tbl ? nullptr : prep_g;
             nf.first_prepped = prep_f != nullptr;
             if (score) launch_score_slots(sc_.dev.as<ScoreSlot>(), state(0), d_scfg_.as<SampleCfg>(), d_lfast_.as<float>(), a_.codebook_size, a_.codebook_size,
-                                          1 + cbi, C, B, st_);
+                                          1 + cbi, C, B, st_, stash);
             if (slots) {
                 RepPenState rp0 = srp_.view(0);
                 SampleKernels<WT>::sample_fast_slots(d_, d_lfast_.as<float>(), cbi, C, a_.codebook_size, d_scfg_.as<SampleCfg>(), d_srng_.as<SlotRng>(), rp0,
@@ -2606,6 +2697,7 @@ class LM final : public LMBase {
                                                 cs.X, d_out_.as<uint32_t>(), out_cap_, st_, words, prep_f, cs.A);
             cf = nf;
         }
+        if (trace) launch_trace_commit(sc_.dev.as<ScoreSlot>(), state(0), d_scfg_.as<SampleCfg>(), stash, n_audio_, a_.codebook_size, C, B, st_);
         if (capt) launch_cap_rows_picks(state(0), d_cfg_.as<SampleCfg>(), B, d_rcap_.as<float>(), cap_frames_, C, st_);
     }
     // the capture record of a row-path call: [B][cap_frames][9][2048] (allocated when fs_lm_debug_capture is armed)
@@ -2630,7 +2722,8 @@ class LM final : public LMBase {
     }
     hipGraphExec_t batch_graph(int B) {
         const int key = (sess_active_ ? 1 << 24 : 0) + (rows_par_ ? 1 << 25 : 0) + (sess_active_ && sess_slots_ ? 1 << 26 : 0) + (sess_active_ && sess_slots_ && sess_wide_ ? 1 << 27 : 0) +
-                        (sess_active_ && sess_slots_ && sess_score_ ? 1 << 28 : 0) + B * 1024 + nc_launch_;
+                        (sess_active_ && sess_slots_ && sess_score_ ? 1 << 28 : 0) +
+                        (sess_active_ && sess_slots_ && sess_score_ && sess_trace_ ? 1 << 29 : 0) + B * 1024 + nc_launch_;
         auto it = batch_graphs_.find(key);
         if (it != batch_graphs_.end()) return it->second;
         {   // the co-residency query of the folded step (rows_fold_ok -> occupancy API) is answered once, OUTSIDE stream capture
@@ -3066,6 +3159,9 @@ class LM final : public LMBase {
     SlotTab<HidSlot> hid_;    // hidden-state collectors (fs_lm_session_add_hidden): the table of the step's k_hidden_rows node
     SlotTab<ScoreSlot> sc_;   // scoring slots (fs_lm_session_add_scored): the table of the step's k_score_slots nodes
     bool sess_score_ = false;  // FS_SESSION_SCORE (the session's step graphs carry the 9 score nodes)
+    bool sess_trace_ = false;  // FS_SESSION_TRACE (... and the traced slots' tail node; the score nodes know the stash)
+    std::vector<char> sess_traced_;  // per slot: admitted with fs_lm_session_add_traced (its sc_ entry has no targets)
+    DevBuf d_trace_;                 // the traced slots' stash f32 [B][TRACE_STASH_WORDS] (lm_kernels.h), once per handle
     SeqState sess_stage_ = {};
     hipStream_t st_pf_ = nullptr;
     hipEvent_t ev_pf_ = nullptr;

@@ -311,8 +311,16 @@ void launch_hidden_rows(HidSlot* tab, const SeqState* states, const float* X, in
 // block b records f32 log-softmax figures of logits row b for the slot's target (candidate 0 left out of a slow decision when
 // cfgs[b].ignore_eos), then stores +INFINITY over the target's logit so that the greedy sampler behind it picks the target; at the last
 // decision it bumps tab[b].count.  Null entries, done slots and full records exit at once.  2 <= n <= 2048, n_cb == 8.  ONE launch.
+// trace_stash != null (FS_SESSION_TRACE sessions): an entry without targets is a TRACED slot (fishrt.h: fs_lm_session_add_traced) -- the
+// node leaves top_logprob / top / eos_logprob in the record, m, log s and the raw row in the slot's stash, and the row as it is.
 void launch_score_slots(ScoreSlot* tab, const SeqState* states, const SampleCfg* cfgs, float* logits, int ld, int n, int decision, int n_cb, int B,
-                        hipStream_t st);
+                        hipStream_t st, float* trace_stash = nullptr);
+// Traced slots: the per-handle stash f32 [B][TRACE_STASH_WORDS] (per slot a 32-word head + the step's 9 raw rows of <= 2048 candidates),
+// and the ONE node behind the frame's last sampler node that closes the rows opened in this step: the picks out of SeqState::cur, their
+// log-probs from the stash, the token row behind the records, count + 1.  Every other entry exits at once.  n_cb == 8.
+constexpr int TRACE_STASH_WORDS = 32 + 9 * 2048;
+void launch_trace_commit(ScoreSlot* tab, const SeqState* states, const SampleCfg* cfgs, float* trace_stash, int n_slow, int cb_size, int n_cb, int B,
+                         hipStream_t st);
 
 // synthetic tensor fill (fs_synth.h): n_rows x n_cols, destination row = r * row_mul + row_off (W1/W3 interleave)
 template <typename WT>

@@ -1569,12 +1569,15 @@ void launch_cap_rows_picks(const SeqState* states, const SampleCfg* cfg, int B, 
 // __shfl_xor wave reduction and a 4-entry LDS array every thread folds itself.  All 256 threads take the same path.
 constexpr int SCORE_THREADS = 256;
 struct ScoreOut { float logprob, top_logprob, eos_logprob; uint32_t top; };
-__device__ __forceinline__ ScoreOut score_row(float* __restrict__ row, int n, int t, bool exclude0) {
+// What a scoring and a traced decision share: the row in the thread's registers (lv: the blocked ownership above; entries at or beyond n
+// hold -inf, candidate 0 too when it is left out), its maximum m by the LAST-max key, log(sum exp(x - m)), the maximal index.  m, ls and
+// top are the row's on every thread; x0 (candidate 0 as scored) is thread 0's.
+struct RowStats { float m, ls, x0; uint32_t top; };
+__device__ __forceinline__ RowStats score_row_stats(const float* __restrict__ row, int n, bool exclude0, float (&lv)[8]) {
     __shared__ unsigned long long s_k[SCORE_THREADS / 64];
     __shared__ float s_s[SCORE_THREADS / 64];
     const int tid = threadIdx.x;
     const bool vec = (reinterpret_cast<uintptr_t>(row) & 15u) == 0;
-    float lv[8];
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
         const int i0 = g * (SCORE_THREADS * 4) + tid * 4;
@@ -1587,13 +1590,6 @@ __device__ __forceinline__ ScoreOut score_row(float* __restrict__ row, int n, in
         }
     }
     if (tid == 0 && exclude0) lv[0] = -INFINITY;
-    // the target's and <|im_end|>'s logits, read by thread 0 ahead of the barriers (the store at the end comes behind them)
-    float xt = 0.f, x0 = 0.f;
-    const bool t_ok = (unsigned)t < (unsigned)n;
-    if (tid == 0) {
-        x0 = lv[0];
-        xt = !t_ok ? __uint_as_float(0x7FC00000u) : (t == 0 ? lv[0] : row[t]);
-    }
     unsigned long long key = 0ull;
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
@@ -1613,33 +1609,91 @@ __device__ __forceinline__ ScoreOut score_row(float* __restrict__ row, int n, in
     for (int w = 0; w < SCORE_THREADS / 64; ++w) { const unsigned long long o = s_k[w]; key = o > key ? o : key; }
     uint32_t mu = (uint32_t)(key >> 32);
     mu ^= (mu >> 31) ? 0x80000000u : 0xFFFFFFFFu;
-    const float m = __uint_as_float(mu);
+    RowStats r;
+    r.m = __uint_as_float(mu);
     float sum = 0.f;
 #pragma unroll
-    for (int s = 0; s < 8; ++s) sum += expf(lv[s] - m);  // (owned entries at or beyond n hold -inf: +0)
+    for (int s = 0; s < 8; ++s) sum += expf(lv[s] - r.m);  // (owned entries at or beyond n hold -inf: +0)
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) sum += __shfl_xor(sum, o, 64);
     if ((tid & 63) == 0) s_s[tid >> 6] = sum;
     __syncthreads();
     sum = (s_s[0] + s_s[1]) + (s_s[2] + s_s[3]);
-    const float ls = logf(sum);
-    ScoreOut r;
-    r.logprob = (xt - m) - ls;
-    r.top_logprob = -ls;
-    r.eos_logprob = (x0 - m) - ls;
+    r.ls = logf(sum);
+    r.x0 = lv[0];
     r.top = (uint32_t)(key & 0xFFFFFFFFull);
+    return r;
+}
+__device__ __forceinline__ ScoreOut score_row(float* __restrict__ row, int n, int t, bool exclude0) {
+    const int tid = threadIdx.x;
+    // the target's logit, read by thread 0 ahead of the barriers (the store at the end comes behind them); candidate 0's comes out of lv
+    const bool t_ok = (unsigned)t < (unsigned)n;
+    float xr = 0.f;
+    if (tid == 0 && t_ok && t != 0) xr = row[t];
+    float lv[8];
+    const RowStats st = score_row_stats(row, n, exclude0, lv);
+    const float xt = !t_ok ? __uint_as_float(0x7FC00000u) : (t == 0 ? st.x0 : xr);
+    ScoreOut r;
+    r.logprob = (xt - st.m) - st.ls;
+    r.top_logprob = -st.ls;
+    r.eos_logprob = (st.x0 - st.m) - st.ls;
+    r.top = st.top;
     if (tid == 0 && t_ok) row[t] = INFINITY;  // the forcing: the unique maximum of a finite row
     return r;  // (logprob / eos_logprob: thread 0's are the row's)
 }
+// ---- traced slots of a FS_SESSION_TRACE session (fishrt.h: fs_lm_session_add_traced): slots that SAMPLE and leave the scoring slots'
+// record of their own picks.  Their table entry is a ScoreSlot without targets (targets == null, rec != null).  The pick is not known in
+// front of the sampler, and the next pass's head overwrites the codebook row, so the record is made in two parts: the score node of
+// decision d writes what does not depend on the pick (top_logprob, top, eos_logprob), keeps m and log s, and copies the raw row into the
+// slot's stash; ONE node behind the frame's last sampler (k_trace_commit) reads the picks out of SeqState::cur and closes the row.
+// The stash of slot b, TRACE_STASH_WORDS f32: a 32-word head -- [0..8] m of decision d, [9..17] log s, [18] the open-row mark (u32: set
+// by decision 0 of an iteration the slot runs, cleared by the tail node, so the iteration whose slow pick was <|im_end|> -- the slot is
+// `done` from there on and its codebook nodes exit -- is still closed, exactly once, and a parked, frozen, finished or not yet joined
+// slot adds no row) -- then the 9 raw rows [9][2048].  The row is NOT modified: the slot's sampler decides on what it always decided on.
+constexpr int TRACE_HEAD_WORDS = 32, TRACE_ROW_WORDS = 2048, TRACE_OPEN = 18;
+static_assert(TRACE_STASH_WORDS == TRACE_HEAD_WORDS + 9 * TRACE_ROW_WORDS, "stash layout");
+__device__ __forceinline__ void trace_row(float* __restrict__ rec, float* __restrict__ stash, const float* __restrict__ row, int n, int d,
+                                          bool exclude0) {
+    const int tid = threadIdx.x;
+    float lv[8];
+    const RowStats st = score_row_stats(row, n, exclude0, lv);
+    float* dst = stash + TRACE_HEAD_WORDS + (size_t)d * TRACE_ROW_WORDS;  // (16-byte aligned: the stash is, and every offset is a multiple of 4 words)
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+        const int i0 = g * (SCORE_THREADS * 4) + tid * 4;
+        if (i0 + 3 < n) {
+            *reinterpret_cast<float4*>(dst + i0) = make_float4(lv[g * 4 + 0], lv[g * 4 + 1], lv[g * 4 + 2], lv[g * 4 + 3]);
+        } else {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) if (i0 + s < n) dst[i0 + s] = lv[g * 4 + s];
+        }
+    }
+    if (tid == 0) {
+        stash[d] = st.m;
+        stash[9 + d] = st.ls;
+        rec[9 + d] = -st.ls;
+        rec[18 + d] = __uint_as_float(st.top);
+        if (d == 0) {
+            rec[27] = (st.x0 - st.m) - st.ls;
+            rec[28] = 0.f; rec[29] = 0.f; rec[30] = 0.f; rec[31] = 0.f;
+            reinterpret_cast<uint32_t*>(stash)[TRACE_OPEN] = 1u;
+        }
+    }
+}
 __global__ __launch_bounds__(SCORE_THREADS) void k_score_slots(ScoreSlot* __restrict__ tab, const SeqState* __restrict__ states,
                                                                const SampleCfg* __restrict__ cfgs, float* __restrict__ logits, int ld, int n,
-                                                               int d, int n_cb) {
+                                                               int d, int n_cb, float* __restrict__ stash) {
     const int b = blockIdx.x;
     ScoreSlot* sc = tab + b;
     float* rec = sc->rec;
     const int count = sc->count;
     if (!rec || states[b].done != 0 || count >= sc->cap) return;  // (block-uniform)
-    const uint32_t tok = sc->targets[(size_t)count * (n_cb + 1) + d];
+    const uint32_t* targets = sc->targets;
+    if (!targets) {  // a traced slot (block-uniform; only the tables of FS_SESSION_TRACE sessions hold such entries, and those have a stash)
+        if (stash) trace_row(rec + (size_t)count * 32, stash + (size_t)b * TRACE_STASH_WORDS, logits + (size_t)b * ld, n, d, d == 0 && cfgs[b].ignore_eos != 0);
+        return;
+    }
+    const uint32_t tok = targets[(size_t)count * (n_cb + 1) + d];
     const int t = d == 0 ? (int)(tok - cfgs[b].audio_base) : (int)tok;
     const ScoreOut r = score_row(logits + (size_t)b * ld, n, t, d == 0 && cfgs[b].ignore_eos != 0);
     if (threadIdx.x == 0) {
@@ -1652,10 +1706,53 @@ __global__ __launch_bounds__(SCORE_THREADS) void k_score_slots(ScoreSlot* __rest
     }
 }
 void launch_score_slots(ScoreSlot* tab, const SeqState* states, const SampleCfg* cfgs, float* logits, int ld, int n, int decision, int n_cb, int B,
-                        hipStream_t st) {
+                        hipStream_t st, float* trace_stash) {
     FS_REQUIRE(n >= 2 && n <= SCORE_THREADS * 8 && n <= ld && n_cb == 8 && decision >= 0 && decision <= n_cb,
                "score node: 2 .. 2048 candidates, 8 codebooks (the 32-word record holds 9 decisions)");
-    hipLaunchKernelGGL(k_score_slots, dim3(B), dim3(SCORE_THREADS), 0, st, tab, states, cfgs, logits, ld, n, decision, n_cb);
+    hipLaunchKernelGGL(k_score_slots, dim3(B), dim3(SCORE_THREADS), 0, st, tab, states, cfgs, logits, ld, n, decision, n_cb, trace_stash);
+    FS_LAUNCH_CHECK();
+}
+// The tail node of a traced iteration: block b closes the row its slot's decision-0 node opened in this step.  Thread d <= n_cb takes
+// decision d: the pick out of cur[] (the frame commit has run: cur[0] the slow token as it goes into the next input column, cur[1 + c] the
+// codes; slow index = tok - audio_base, <|im_end|> = candidate 0), its log-prob from the stashed row, m and log s -- the score node's
+// expression -- or, for the codebook decisions an <|im_end|> iteration skipped, NaN / NaN / 0xFFFFFFFF / token 0.  The picks go to the
+// slot's token rows u32 [cap][n_cb + 1] behind the records (where a scoring slot keeps its targets).  Then the mark is cleared and the
+// count bumped.  Everything else -- null and scoring entries, no open row -- exits at once.
+__global__ __launch_bounds__(64) void k_trace_commit(ScoreSlot* __restrict__ tab, const SeqState* __restrict__ states, const SampleCfg* __restrict__ cfgs,
+                                                    float* __restrict__ stash_all, int n_slow, int cb_size, int n_cb) {
+    const int b = blockIdx.x, d = threadIdx.x;
+    ScoreSlot* sc = tab + b;
+    float* rec = sc->rec;
+    if (!rec || sc->targets) return;  // (block-uniform)
+    float* stash = stash_all + (size_t)b * TRACE_STASH_WORDS;
+    uint32_t* open = reinterpret_cast<uint32_t*>(stash) + TRACE_OPEN;
+    const int count = sc->count, cap = sc->cap;
+    if (*open == 0u || count >= cap) return;  // (block-uniform)
+    if (d <= n_cb) {
+        const uint32_t slow = states[b].cur[0], tok = states[b].cur[d];
+        const bool eos = slow == cfgs[b].im_end_id;
+        const uint32_t idx = d == 0 ? (eos ? 0u : tok - cfgs[b].audio_base) : tok;
+        const bool made = (d == 0 || !eos) && idx < (uint32_t)(d == 0 ? n_slow : cb_size);
+        float* r = rec + (size_t)count * 32;
+        uint32_t* toks = reinterpret_cast<uint32_t*>(rec + (size_t)cap * 32) + (size_t)count * (n_cb + 1);
+        const float nan = __uint_as_float(0x7FC00000u);
+        if (made) {
+            r[d] = (stash[TRACE_HEAD_WORDS + (size_t)d * TRACE_ROW_WORDS + idx] - stash[d]) - stash[9 + d];
+            toks[d] = tok;
+        } else {
+            r[d] = nan;
+            if (d > 0 && eos) { r[9 + d] = nan; r[18 + d] = __uint_as_float(0xFFFFFFFFu); }
+            toks[d] = 0u;
+        }
+    }
+    __syncthreads();  // (every thread has read the count and the mark)
+    if (d == 0) { *open = 0u; sc->count = count + 1; }
+}
+void launch_trace_commit(ScoreSlot* tab, const SeqState* states, const SampleCfg* cfgs, float* trace_stash, int n_slow, int cb_size, int n_cb, int B,
+                         hipStream_t st) {
+    FS_REQUIRE(trace_stash && n_cb == 8 && n_slow >= 2 && n_slow <= TRACE_ROW_WORDS && cb_size >= 2 && cb_size <= TRACE_ROW_WORDS,
+               "trace node: 8 codebooks, rows of 2 .. 2048 candidates");
+    hipLaunchKernelGGL(k_trace_commit, dim3(B), dim3(64), 0, st, tab, states, cfgs, trace_stash, n_slow, cb_size, n_cb);
     FS_LAUNCH_CHECK();
 }
 // test hook (fs_selftest_score_rows): score_row on caller rows, one block per row

@@ -263,13 +263,67 @@ class DualARTransformer:
         return int(out.value)
 
     def session(self, temp=0.7, top_p=0.9, top_k=50, seed=42, ignore_eos=False, rows=False, repetition_penalty=1.2, per_slot=False, wide=False,
-                score=False):
+                score=False, trace=False):
         """continuous batching over this handle's max_batch slots (fishrt.h: fs_lm_session_*): `with lm.session(...) as s:`
         per_slot=True: FS_SESSION_PER_SLOT -- every slot samples like its own generate_blocking call (own settings, seed, repetition penalty).
         wide=True (with per_slot=True): FS_SESSION_WIDE_SAMPLER -- slots may also sample nucleus-only (top_k == 0) or with top_k > 256.
         score=True (with per_slot=True): FS_SESSION_SCORE -- the session also takes scoring slots (Session.add_scored / poll_scores).
+        trace=True (with per_slot=True, score=True): FS_SESSION_TRACE -- the session also takes traced slots (Session.add(..., trace=True) /
+        poll_trace): generating slots that record the log-probs of the tokens they pick.
         Fish <= 1.4 token configs (no semantic range) take per_slot=True only; plain and rows sessions raise and say so."""
-        return Session(self, temp, top_p, top_k, seed, ignore_eos, rows, repetition_penalty, per_slot, wide, score)
+        return Session(self, temp, top_p, top_k, seed, ignore_eos, rows, repetition_penalty, per_slot, wide, score, trace)
+
+    def generate_traced(self, prompts, max_new_tokens, samplings=None, seeds=None, collect_hidden=False):
+        """Generate behind every prompts[i] (u32 [C+1, L_i]) and return, with the codes, the log-probs the model gave the tokens it picked
+        -- one pass, no teacher-forced second one.  max_new_tokens: one int or one per prompt; samplings[i] (dict / SamplingArgs-like) and
+        seeds[i]: the request's own settings / StdRng seed, None = the session's (temp 0.7, top_p 0.9, top_k 50, penalty 1.2; seed 42 +
+        admission number).  Opens one per-slot trace session (wide when a setting needs it), admits the requests as slots free up and
+        returns one dict per prompt: codes u32 [C, n_frames], the arrays of Session.poll_trace (tokens, logprob, top_logprob, top,
+        eos_logprob, n_decisions), total = the sum of the log-probs of the decisions made (f64), plus hidden f32 [n, dim] with
+        collect_hidden."""
+        n = len(prompts)
+        budgets = [int(max_new_tokens)] * n if np.ndim(max_new_tokens) == 0 else [int(m) for m in max_new_tokens]
+        samplings = [None] * n if samplings is None else list(samplings)
+        seeds = [None] * n if seeds is None else list(seeds)
+        if not (len(budgets) == len(samplings) == len(seeds) == n):
+            raise ValueError(f"generate_traced: {n} prompts for {len(budgets)} budgets, {len(samplings)} samplings, {len(seeds)} seeds")
+
+        def is_wide(sp):
+            if sp is None:
+                return False
+            get = sp.get if isinstance(sp, dict) else (lambda k, d: getattr(sp, k, d))
+            return float(get("temp", 0.7)) > 0.0 and not 0 < int(get("top_k", 50)) <= 256
+
+        out = [None] * n
+        with self.session(per_slot=True, score=True, trace=True, wide=any(is_wide(sp) for sp in samplings)) as s:
+            todo = [(i, s._prompt(p)) for i, p in enumerate(prompts)]  # (every shape is checked first)
+            for sp in samplings:
+                if sp is not None:
+                    s._sampling(sp)
+            live = {}
+            while todo or live:
+                while todo:
+                    i, p = todo[0]
+                    slot = s.add(p, budgets[i], sampling=samplings[i], seed=seeds[i], collect_hidden=collect_hidden, trace=True)
+                    if slot is None:
+                        if not live:
+                            raise RuntimeError(f"generate_traced: request {i} does not fit an empty session (KV page pool too small)")
+                        break
+                    live[slot] = i
+                    todo.pop(0)
+                s.step(8)
+                for slot in list(live):
+                    codes, done = s.poll(slot)
+                    if not done:
+                        continue
+                    r = s.poll_trace(slot)
+                    r["codes"] = codes
+                    r["total"] = float(np.nansum(r["logprob"], dtype=np.float64))
+                    if collect_hidden:
+                        r["hidden"] = s.poll_hidden(slot)
+                    out[live.pop(slot)] = r
+                    s.release(slot)
+        return out
 
     def score(self, prompts, frames, collect_hidden=False):
         """Teacher-forced log-probabilities of given code sequences: sequence i is frames[i] (u32 [C+1, N_i]: row 0 the slow tokens, rows
@@ -352,7 +406,8 @@ class Session:
 
     SAMPLING_KEYS = ("temp", "top_p", "top_k", "repetition_penalty")
 
-    def __init__(self, lm, temp, top_p, top_k, seed, ignore_eos, rows=False, repetition_penalty=1.2, per_slot=False, wide=False, score=False):
+    def __init__(self, lm, temp, top_p, top_k, seed, ignore_eos, rows=False, repetition_penalty=1.2, per_slot=False, wide=False, score=False,
+                 trace=False):
         """rows=True: FS_SESSION_ROWS -- the slots run on the request-row persistent kernels with batch-1 semantics (repetition penalty, own
         sampler stream per slot); max_batch <= 8.
         per_slot=True: FS_SESSION_PER_SLOT -- the slots stay on the static-batch step (any max_batch, bf16 / fp8) and every slot samples like
@@ -361,7 +416,9 @@ class Session:
         wide=True: FS_SESSION_WIDE_SAMPLER, per_slot sessions only -- the session's and every add()'s settings may be greedy or any
         temp > 0 with any top_k >= 0 (0 = no top-k) and any top_p; settings inside the 0 < top_k <= 256 limit give the same codes as without it
         score=True: FS_SESSION_SCORE, per_slot sessions only (Fish 1.5 token layout) -- add_scored() admits slots that are forced along a given
-        code sequence and record its log-probabilities (poll_scores); generating slots of the session are unaffected"""
+        code sequence and record its log-probabilities (poll_scores); generating slots of the session are unaffected
+        trace=True: FS_SESSION_TRACE, per_slot + score sessions only -- add(..., trace=True) admits generating slots that leave the score
+        record of the tokens they pick (poll_trace); every other slot of the session is unaffected"""
         self.lm, self._open = lm, False
         if rows and per_slot:
             raise ValueError("rows and per_slot exclude each other (a row session's slots already sample per slot)")
@@ -369,12 +426,16 @@ class Session:
             raise ValueError("wide=True needs per_slot=True (FS_SESSION_WIDE_SAMPLER is valid only together with FS_SESSION_PER_SLOT)")
         if score and not per_slot:
             raise ValueError("score=True needs per_slot=True (FS_SESSION_SCORE is valid only together with FS_SESSION_PER_SLOT)")
-        self.rows, self.per_slot, self.wide, self.score = bool(rows), bool(per_slot), bool(wide), bool(score)
+        if trace and not (per_slot and score):
+            raise ValueError("trace=True needs per_slot=True and score=True (FS_SESSION_TRACE is valid only together with "
+                             "FS_SESSION_PER_SLOT | FS_SESSION_SCORE)")
+        self.rows, self.per_slot, self.wide, self.score, self.trace = bool(rows), bool(per_slot), bool(wide), bool(score), bool(trace)
         self.sampling = dict(temp=float(temp), top_p=float(top_p), top_k=int(top_k), repetition_penalty=float(repetition_penalty))
         s = _ffi.Sampling(float(temp), float(top_p), int(top_k), float(repetition_penalty) if (rows or per_slot) else 1.0)
         flags = (_ffi.FS_GEN_IGNORE_EOS if ignore_eos else 0) | (_ffi.FS_SESSION_ROWS if rows else 0) | (_ffi.FS_SESSION_PER_SLOT if per_slot else 0)
         flags |= _ffi.FS_SESSION_WIDE_SAMPLER if wide else 0
         flags |= _ffi.FS_SESSION_SCORE if score else 0
+        flags |= _ffi.FS_SESSION_TRACE if trace else 0
         _ffi.check(_ffi.lib().fs_lm_session_begin(lm._h, C.byref(s), C.c_uint64(seed), flags))
         self._open = True
 
@@ -411,16 +472,27 @@ class Session:
             raise ValueError("sampling: temp and top_k must not be negative")
         return _ffi.Sampling(float(v["temp"]), float(v["top_p"]), int(v["top_k"]), float(v["repetition_penalty"]))
 
-    def add(self, prompt, max_new_tokens, prefix=None, sampling=None, seed=None, collect_hidden=False):
+    def add(self, prompt, max_new_tokens, prefix=None, sampling=None, seed=None, collect_hidden=False, trace=False):
         """prefix (an add_prefix id): `prompt` is the request's BODY -- the slot generates what add(concat(prefix prompt, body)) would,
         reading the prefix's K/V from its shared pages and prefilling the body only.
         sampling (dict or SamplingArgs-like) / seed: the slot's own sampler settings / StdRng seed (fs_lm_session_add_ex) -- per_slot and rows
         sessions only; a plain session has one lock-step sampler and refuses them.
         collect_hidden=True (fs_lm_session_add_hidden, any session kind): the slot also keeps the slow transformer's pre-norm hidden state
-        of every iteration it runs -> poll_hidden(slot); its codes are those of the same add without it"""
+        of every iteration it runs -> poll_hidden(slot); its codes are those of the same add without it
+        trace=True (fs_lm_session_add_traced, trace=True sessions): the slot also records the log-probs of the tokens it picks ->
+        poll_trace(slot); its codes are those of the same add without it"""
+        if trace and not self.trace:
+            raise ValueError("add(trace=True) needs lm.session(per_slot=True, score=True, trace=True)")
         p = self._prompt(prompt, "prompt" if prefix is None else "body")
         slot = C.c_int(-1)
-        if sampling is not None or seed is not None or collect_hidden:
+        if trace:
+            sp = C.byref(self._sampling(sampling)) if sampling is not None else None
+            if seed is not None and not 0 <= int(seed) < 2**64:
+                raise ValueError("seed must fit an unsigned 64-bit integer")
+            sd = C.byref(C.c_uint64(int(seed))) if seed is not None else None
+            _ffi.check(_ffi.lib().fs_lm_session_add_traced(self.lm._h, -1 if prefix is None else int(prefix), p.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                           int(p.shape[1]), int(max_new_tokens), sp, sd, 1 if collect_hidden else 0, C.byref(slot)))
+        elif sampling is not None or seed is not None or collect_hidden:
             if (sampling is not None or seed is not None) and not (self.rows or self.per_slot):
                 raise ValueError("per-slot sampling / seed need lm.session(per_slot=True) or lm.session(rows=True)")
             sp = C.byref(self._sampling(sampling)) if sampling is not None else None
@@ -547,6 +619,31 @@ class Session:
             _ffi.check(L.fs_lm_session_poll_scores(self.lm._h, int(slot), C.c_size_t(int(first)), lp.ctypes.data_as(fp), tlp.ctypes.data_as(fp),
                                                    top.ctypes.data_as(C.POINTER(C.c_uint32)), eos.ctypes.data_as(fp), C.c_size_t(rows), C.byref(n)))
         return dict(logprob=lp[:rows].copy(), top_logprob=tlp[:rows].copy(), top=top[:rows].copy(), eos_logprob=eos[:rows].copy())
+
+    def poll_trace(self, slot, first=0):
+        """records [first, iterations so far) of a traced slot (add(..., trace=True)) -> dict(tokens u32 [n, C+1], logprob f32 [n, C+1],
+        top_logprob f32 [n, C+1], top u32 [n, C+1], eos_logprob f32 [n], n_decisions i32 [n]): poll_scores' figures, taken at the token the
+        slot PICKED (tokens[:, 0] the slow token id, tokens[:, 1 + c] the code; tokens.T feeds add_scored).  One row per iteration the slot
+        ran, the terminating <|im_end|> one included (n_decisions 1: its codebook entries are NaN / 0xFFFFFFFF / 0)"""
+        if not self.trace:
+            raise ValueError("poll_trace needs lm.session(per_slot=True, score=True, trace=True)")
+        if int(first) < 0:
+            raise ValueError("first must not be negative")
+        L, C1 = _ffi.lib(), self.lm.cfg["num_codebooks"] + 1
+        n = C.c_size_t(0)
+        _ffi.check(L.fs_lm_session_poll_trace(self.lm._h, int(slot), C.c_size_t(0), None, None, None, None, None, None, C.c_size_t(0), C.byref(n)))
+        rows = max(0, int(n.value) - int(first))
+        cap = max(1, rows)
+        tok, top = np.zeros((cap, C1), np.uint32), np.zeros((cap, C1), np.uint32)
+        lp, tlp = np.zeros((cap, C1), np.float32), np.zeros((cap, C1), np.float32)
+        eos, nd = np.zeros(cap, np.float32), np.zeros(cap, np.int32)
+        if rows:
+            fp, up = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
+            _ffi.check(L.fs_lm_session_poll_trace(self.lm._h, int(slot), C.c_size_t(int(first)), tok.ctypes.data_as(up), lp.ctypes.data_as(fp),
+                                                  tlp.ctypes.data_as(fp), top.ctypes.data_as(up), eos.ctypes.data_as(fp),
+                                                  nd.ctypes.data_as(C.POINTER(C.c_int)), C.c_size_t(rows), C.byref(n)))
+        return dict(tokens=tok[:rows].copy(), logprob=lp[:rows].copy(), top_logprob=tlp[:rows].copy(), top=top[:rows].copy(),
+                    eos_logprob=eos[:rows].copy(), n_decisions=nd[:rows].copy())
 
     def release(self, slot):
         _ffi.check(_ffi.lib().fs_lm_session_release(self.lm._h, int(slot)))

@@ -343,7 +343,18 @@ int fs_comm_all_gather_codes(fs_comm_t* comm, const uint32_t* codes, const int32
  * releasing a scoring slot never re-captures a graph, and for a generating slot it exits at once: every generating slot's codes are bit
  * for bit those of the same session without the flag.  Sessions begun without the flag replay exactly the graphs they did before. */
 #define FS_SESSION_SCORE 64u
-int fs_lm_session_begin(fs_lm_t* lm, const fs_sampling* sampling, uint64_t seed, uint32_t flags /* FS_GEN_IGNORE_EOS | FS_SESSION_ROWS | FS_SESSION_PER_SLOT | FS_SESSION_WIDE_SAMPLER | FS_SESSION_SCORE */);
+/* FS_SESSION_TRACE: valid only together with FS_SESSION_PER_SLOT | FS_SESSION_SCORE, with or without FS_SESSION_WIDE_SAMPLER (alone, with
+ * FS_SESSION_ROWS, without FS_SESSION_SCORE, or on a Fish <= 1.4 handle fs_lm_session_begin fails and says which).  The session
+ * additionally takes TRACED slots (fs_lm_session_add_traced): slots that generate like any other and leave the scoring slots' record for
+ * the tokens they PICKED, so that the log-probs of a generated sequence need no second, teacher-forced pass.  The score nodes of the step
+ * take a second path for such a slot (they keep the raw row and its normaliser, and leave the row as it is), and ONE more node per step
+ * (k_trace_commit, one block per slot) behind the frame's last sampler node reads the picks and closes the record row.  Both read the
+ * per-slot table, so one captured graph serves every mix of traced, scoring and plain slots and no add or release re-captures; plain,
+ * scoring and collecting slots of such a session produce bit for bit what they produce without the flag.  The step graphs get one more
+ * key bit: sessions begun without the flag -- FS_SESSION_SCORE sessions too -- replay exactly the graphs they did before.
+ * Device memory: 4 (32 + 9 * 2048) bytes (72.1 KB) of stash per slot of the handle, allocated once at the first such session. */
+#define FS_SESSION_TRACE 128u
+int fs_lm_session_begin(fs_lm_t* lm, const fs_sampling* sampling, uint64_t seed, uint32_t flags /* FS_GEN_IGNORE_EOS | FS_SESSION_ROWS | FS_SESSION_PER_SLOT | FS_SESSION_WIDE_SAMPLER | FS_SESSION_SCORE | FS_SESSION_TRACE */);
 /* prompt u32 [C+1, L] row-major (copied); *slot = the slot taken, or -1 when all max_batch slots are busy or the KV page pool cannot hold
  * the request right now (not an error: retry after a release).  Returns once the
  * prefill is enqueued (one prefill in flight: a second add first waits for the previous one); the slot starts generating in a later step */
@@ -425,6 +436,31 @@ int fs_lm_session_add_scored(fs_lm_t* lm, int prefix_id, const uint32_t* prompt,
  * slot starts again at row 0).  A slot not admitted with fs_lm_session_add_scored is an error that says so. */
 int fs_lm_session_poll_scores(fs_lm_t* lm, int slot, size_t first_row, float* logprob, float* top_logprob, uint32_t* top, float* eos_logprob,
                               size_t cap_rows, size_t* n_rows);
+/* Traced slots (FS_SESSION_TRACE sessions; both calls fail with "needs FS_SESSION_TRACE" in any other).
+ * fs_lm_session_add_traced IS fs_lm_session_add_ex in every respect -- prefix_id / sampling / seed rules, *slot = -1 when nothing is free,
+ * the slot's codes bit for bit; any setting the session accepts: greedy, narrow, and wide in a FS_SESSION_WIDE_SAMPLER session -- and with
+ * collect_hidden != 0 it is fs_lm_session_add_hidden.  Like a slot with a seed of its own it is prefilled in a pass of its own, so its
+ * records are a function of the request alone.  Additionally the slot keeps one record row per generator iteration it runs, in order,
+ * the terminating <|im_end|> iteration included (the *n_hidden rule: *n_rows is the slot's n_frames or n_frames + 1; 0 while it is
+ * prefilling; a released and re-admitted slot starts again at row 0).
+ * The record of decision d (0 = the slow token over the audio range, candidate 0 = <|im_end|> left out under FS_GEN_IGNORE_EOS; 1 + c =
+ * codebook c) is the scoring slots' record (fs_lm_session_add_scored) taken AT THE PICK: f32, from the RAW row -- no temperature, no
+ * repetition penalty, no top-k / top-p -- m = max x_i, s = sum exp(x_i - m),
+ *     logprob[d] = (x_pick - m) - log(s)      top_logprob[d] = -log(s)      top[d] = the LAST index holding m
+ * eos_logprob = the slow row's candidate 0 (-inf when left out); tokens[.][0] = the slow token id as it goes into the next input column
+ * (<|im_end|>'s id on the terminating iteration), tokens[.][1 + c] = the code; n_decisions = C + 1, or 1 for an iteration whose slow pick
+ * was <|im_end|> -- its codebook decisions are skipped: logprob = top_logprob = NaN, top = 0xFFFFFFFF, tokens = 0 there.  So a row equals,
+ * field for field and bit for bit, what fs_lm_session_add_scored records when the same sequence is fed back.
+ * Device memory: 128 + 4 (C + 1) bytes per iteration (the record and the token row: a scoring slot's buffer, from the same per-handle
+ * pool -- taken at the add, returned when the add is refused, at fs_lm_session_release and at fs_lm_session_end), plus the slot's stash
+ * (FS_SESSION_TRACE). */
+int fs_lm_session_add_traced(fs_lm_t* lm, int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling,
+                             const uint64_t* seed, int collect_hidden, int* slot);
+/* rows [first_row, ...) so far: tokens u32 / logprob f32 / top_logprob f32 / top u32 [cap_rows][C+1], eos_logprob f32 [cap_rows],
+ * n_decisions i32 [cap_rows]; every output pointer nullable; *n_rows = rows the slot has.  A slot not admitted with
+ * fs_lm_session_add_traced is an error that says so (and fs_lm_session_poll_scores refuses a traced slot). */
+int fs_lm_session_poll_trace(fs_lm_t* lm, int slot, size_t first_row, uint32_t* tokens, float* logprob, float* top_logprob, uint32_t* top,
+                             float* eos_logprob, int* n_decisions, size_t cap_rows, size_t* n_rows);
 /* out[8] = {free pages, pages referenced by more than one owner, live prefixes, prefill passes, tokens prefilled,
  *           prefix tokens reused, tail pages copied, prefill-stream microseconds (HIP events around each pass)};
  * counters since fs_lm_session_begin */
