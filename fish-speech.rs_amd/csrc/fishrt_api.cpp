@@ -230,9 +230,15 @@ int fs_lm_session_begin(fs_lm_t* lm, const fs_sampling* sampling, uint64_t seed,
     FS_ARG(lm && sampling, "null argument");
     FS_TRY(lm->impl->session_begin(*sampling, seed, flags))
 }
+// the six fs_lm_session_add* entry points fill one request (lm_engine.h: SlotRequest); what is not set here stays off
+static fs::SlotRequest slot_request(int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling, const uint64_t* seed) {
+    fs::SlotRequest r;
+    r.prefix_id = prefix_id; r.prompt = prompt; r.L = L; r.max_new_tokens = max_new_tokens; r.sampling = sampling; r.seed = seed;
+    return r;
+}
 int fs_lm_session_add(fs_lm_t* lm, const uint32_t* prompt, int L, int max_new_tokens, int* slot) {
     FS_ARG(lm && prompt && slot, "null argument");
-    FS_TRY(*slot = lm->impl->session_add(prompt, L, max_new_tokens))
+    FS_TRY(*slot = lm->impl->session_admit(slot_request(-1, prompt, L, max_new_tokens, nullptr, nullptr)))
 }
 int fs_lm_session_step(fs_lm_t* lm, int n_frames, int* n_active) { FS_ARG(lm, "null argument"); FS_TRY(lm->impl->session_step(n_frames, n_active)) }
 int fs_lm_session_poll(fs_lm_t* lm, int slot, uint32_t* codes_out, size_t cap, size_t* n_frames, int* done) {
@@ -261,17 +267,20 @@ int fs_lm_session_prefix_import(fs_lm_t* lm, const void* blob, size_t bytes, int
 int fs_lm_session_prefix_release(fs_lm_t* lm, int prefix_id) { FS_ARG(lm, "null argument"); FS_TRY(lm->impl->session_prefix_release(prefix_id)) }
 int fs_lm_session_add_prefixed(fs_lm_t* lm, int prefix_id, const uint32_t* body, int L_body, int max_new_tokens, int* slot) {
     FS_ARG(lm && body && slot, "null argument");
-    FS_TRY(*slot = lm->impl->session_add_prefixed(prefix_id, body, L_body, max_new_tokens))
+    FS_ARG(prefix_id >= 0, "unknown or released prefix id");  // (a negative id means a plain add only where the header says so: _add_ex and later)
+    FS_TRY(*slot = lm->impl->session_admit(slot_request(prefix_id, body, L_body, max_new_tokens, nullptr, nullptr)))
 }
 int fs_lm_session_add_ex(fs_lm_t* lm, int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling,
                          const uint64_t* seed, int* slot) {
     FS_ARG(lm && prompt && slot, "null argument");
-    FS_TRY(*slot = lm->impl->session_add_ex(prefix_id, prompt, L, max_new_tokens, sampling, seed))
+    FS_TRY(*slot = lm->impl->session_admit(slot_request(prefix_id, prompt, L, max_new_tokens, sampling, seed)))
 }
 int fs_lm_session_add_hidden(fs_lm_t* lm, int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling,
                              const uint64_t* seed, int* slot) {
     FS_ARG(lm && prompt && slot, "null argument");
-    FS_TRY(*slot = lm->impl->session_add_hidden(prefix_id, prompt, L, max_new_tokens, sampling, seed))
+    fs::SlotRequest r = slot_request(prefix_id, prompt, L, max_new_tokens, sampling, seed);
+    r.collect_hidden = true;
+    FS_TRY(*slot = lm->impl->session_admit(r))
 }
 int fs_lm_session_poll_hidden(fs_lm_t* lm, int slot, size_t first_row, float* hidden_out, size_t cap_rows, size_t* n_rows) {
     FS_ARG(lm, "null argument");
@@ -280,7 +289,9 @@ int fs_lm_session_poll_hidden(fs_lm_t* lm, int slot, size_t first_row, float* hi
 int fs_lm_session_add_scored(fs_lm_t* lm, int prefix_id, const uint32_t* prompt, int L, const uint32_t* frames, int N, int collect_hidden,
                              int* slot) {
     FS_ARG(lm && prompt && frames && slot, "null argument");
-    FS_TRY(*slot = lm->impl->session_add_scored(prefix_id, prompt, L, frames, N, collect_hidden))
+    fs::SlotRequest r = slot_request(prefix_id, prompt, L, 0, nullptr, nullptr);
+    r.frames = frames; r.N = N; r.collect_hidden = collect_hidden != 0;
+    FS_TRY(*slot = lm->impl->session_admit(r))
 }
 int fs_lm_session_poll_scores(fs_lm_t* lm, int slot, size_t first_row, float* logprob, float* top_logprob, uint32_t* top, float* eos_logprob,
                               size_t cap_rows, size_t* n_rows) {
@@ -290,7 +301,9 @@ int fs_lm_session_poll_scores(fs_lm_t* lm, int slot, size_t first_row, float* lo
 int fs_lm_session_add_traced(fs_lm_t* lm, int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling,
                              const uint64_t* seed, int collect_hidden, int* slot) {
     FS_ARG(lm && prompt && slot, "null argument");
-    FS_TRY(*slot = lm->impl->session_add_traced(prefix_id, prompt, L, max_new_tokens, sampling, seed, collect_hidden))
+    fs::SlotRequest r = slot_request(prefix_id, prompt, L, max_new_tokens, sampling, seed);
+    r.traced = true; r.collect_hidden = collect_hidden != 0;
+    FS_TRY(*slot = lm->impl->session_admit(r))
 }
 int fs_lm_session_poll_trace(fs_lm_t* lm, int slot, size_t first_row, uint32_t* tokens, float* logprob, float* top_logprob, uint32_t* top,
                              float* eos_logprob, int* n_decisions, size_t cap_rows, size_t* n_rows) {

@@ -23,6 +23,8 @@ struct ScoreSlot {
     int count, cap;
 };
 constexpr int SCORE_REC_WORDS = 32;
+// first word of each part of a record (the host's unpack; the device side writes the same layout)
+constexpr int SCORE_REC_LOGPROB = 0, SCORE_REC_TOP_LOGPROB = 9, SCORE_REC_TOP = 18, SCORE_REC_EOS = 27;
 // One entry per slot: rows == null -> the slot does not collect; else its buffer f32 [cap][dim], and count = rows stored so far == the
 // slot's generator iterations so far.
 struct HidSlot {

@@ -9,6 +9,19 @@
 
 namespace fs {
 
+// One slot admission, whichever fs_lm_session_add* entry point it came through (fishrt.h)
+struct SlotRequest {
+    int prefix_id = -1;                     // < 0: a plain add; else `prompt` is the body behind that prefix
+    const uint32_t* prompt = nullptr;       // [C + 1][L]
+    int L = 0, max_new_tokens = 0;
+    const fs_sampling* sampling = nullptr;  // the slot's own settings / sampler seed (null: the session's)
+    const uint64_t* seed = nullptr;
+    bool collect_hidden = false;            // fs_lm_session_add_hidden
+    const uint32_t* frames = nullptr;       // non-null: a scoring slot forced along frames [C + 1][N] (max_new_tokens is not read)
+    int N = 0;
+    bool traced = false;                    // fs_lm_session_add_traced
+};
+
 class LMBase {
   public:
     virtual ~LMBase() {}
@@ -37,34 +50,25 @@ class LMBase {
     virtual bool rows_supported(int n, const fs_sampling* samplings) = 0;
     // continuous batching over the static-batch step (fishrt.h: fs_lm_session_*)
     virtual void session_begin(const fs_sampling& s, uint64_t seed, uint32_t flags) = 0;
-    virtual int session_add(const uint32_t* prompt, int L, int max_new_tokens) = 0;
+    // every fs_lm_session_add* entry point: the slot, or -1 when no slot / not enough KV pages are free right now
+    virtual int session_admit(const SlotRequest& r) = 0;
     virtual void session_step(int n_frames, int* n_active) = 0;
     virtual void session_poll(int slot, uint32_t* codes_out, size_t cap, size_t* n_frames, int* done) = 0;
     virtual void session_release(int slot) = 0;
     virtual void session_end() = 0;
-    // shared conditioning prefixes of a session (fishrt.h: fs_lm_session_prefix_create / _release / fs_lm_session_add_prefixed / _info)
+    // shared conditioning prefixes of a session (fishrt.h: fs_lm_session_prefix_create / _release / _info)
     virtual int session_prefix_create(const uint32_t* prompt, int P) = 0;
     virtual void session_prefix_release(int id) = 0;
-    virtual int session_add_prefixed(int id, const uint32_t* body, int L_body, int max_new_tokens) = 0;
     virtual void session_info(int64_t out[8]) = 0;
     // prefix KV blobs (fishrt.h: fs_lm_weights_fingerprint / fs_lm_session_prefix_export / _import)
     virtual uint64_t weights_fingerprint() = 0;
     virtual void session_prefix_export(int id, void* blob_out, size_t cap, size_t* bytes) = 0;
     virtual int session_prefix_import(const void* blob, size_t bytes) = 0;
-    // fishrt.h: fs_lm_session_add_ex (prefix_id < 0: plain add; sampling / seed nullable: the session's)
-    virtual int session_add_ex(int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling,
-                               const uint64_t* seed) = 0;
-    // fishrt.h: fs_lm_session_add_hidden / fs_lm_session_poll_hidden
-    virtual int session_add_hidden(int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling,
-                                   const uint64_t* seed) = 0;
+    // fishrt.h: fs_lm_session_poll_hidden
     virtual void session_poll_hidden(int slot, size_t first_row, float* hidden_out, size_t cap_rows, size_t* n_rows) = 0;
-    // fishrt.h: fs_lm_session_add_scored / fs_lm_session_poll_scores
-    virtual int session_add_scored(int prefix_id, const uint32_t* prompt, int L, const uint32_t* frames, int N, int collect_hidden) = 0;
+    // fishrt.h: fs_lm_session_poll_scores / fs_lm_session_poll_trace
     virtual void session_poll_scores(int slot, size_t first_row, float* logprob, float* top_logprob, uint32_t* top, float* eos_logprob,
                                      size_t cap_rows, size_t* n_rows) = 0;
-    // fishrt.h: fs_lm_session_add_traced / fs_lm_session_poll_trace
-    virtual int session_add_traced(int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling,
-                                   const uint64_t* seed, int collect_hidden) = 0;
     virtual void session_poll_trace(int slot, size_t first_row, uint32_t* tokens, float* logprob, float* top_logprob, uint32_t* top,
                                     float* eos_logprob, int* n_decisions, size_t cap_rows, size_t* n_rows) = 0;
     virtual void debug_capture(int n_frames) = 0;

@@ -153,7 +153,8 @@ class PersistLock {
             usleep(500);
         }
     }
-    void lock() { (void)lock_for(600.0); }
+    // (no lock(): std::unique_lock is only ever built with try_to_lock, adopt_lock or defer_lock on this -- acquire_persist -- and a wait
+    // that can time out has no business behind an interface that promises the lock)
     // (a binary semaphore, not a std::mutex: a row session takes it in session_begin and gives it back in session_end, possibly on another thread)
     void unlock() {
         if (fd_ >= 0) (void)flock(fd_, LOCK_UN);
@@ -948,28 +949,22 @@ class LM final : public LMBase {
         // FS_SESSION_ROWS: the slots run on the request-row persistent kernels (lm_persist_rows.hip) and keep BATCH-1 semantics -- every slot is
         // its own generate_blocking (repetition penalty, its own LogitsProcessor stream seeded seed + its admission number) -- instead of the
         // static-batch sampler's.  Needs max_batch <= 8, a bf16 Fish-1.5 handle and a sampler setting the in-launch decisions cover.
-        sess_rows_ = false;
+        // The mode is built in a local and becomes the handle's with sess_active_, as the last act: a throw leaves the handle as it was.
+        SessMode m;
+        m.score = score; m.trace = trace;
         // FS_SESSION_PER_SLOT: the slots stay on the static-batch step, but its 9 sampler nodes are the per-slot ones (k_sample_*_slots):
         // every slot decides like its own generate_blocking call, with its own settings, StdRng stream and repetition-penalty windows
-        const bool per_slot = (flags & FS_SESSION_PER_SLOT) != 0;
+        m.slots = (flags & FS_SESSION_PER_SLOT) != 0;
         // FS_SESSION_WIDE_SAMPLER: the per-slot sampler nodes are the instantiation that also covers nucleus-only and top_k > 256 settings
-        const bool wide = (flags & FS_SESSION_WIDE_SAMPLER) != 0;
-        FS_REQUIRE(!wide || (per_slot && !(flags & FS_SESSION_ROWS)),
+        m.wide = (flags & FS_SESSION_WIDE_SAMPLER) != 0;
+        FS_REQUIRE(!m.wide || (m.slots && !(flags & FS_SESSION_ROWS)),
                    "FS_SESSION_WIDE_SAMPLER is valid only together with FS_SESSION_PER_SLOT (not alone, not with FS_SESSION_ROWS)");
-        FS_REQUIRE(!(per_slot && (flags & FS_SESSION_ROWS)), "FS_SESSION_PER_SLOT and FS_SESSION_ROWS exclude each other (a row session's slots already sample per slot)");
-        if (per_slot) {
+        FS_REQUIRE(!(m.slots && (flags & FS_SESSION_ROWS)), "FS_SESSION_PER_SLOT and FS_SESSION_ROWS exclude each other (a row session's slots already sample per slot)");
+        if (m.slots) {
             FS_REQUIRE(n_audio_ <= 2048 && a_.codebook_size <= 1024, "FS_SESSION_PER_SLOT needs <= 2048 slow candidates and codebooks of <= 1024 entries");
-            require_slot_sampling(s, wide);
+            require_slot_sampling(s, m.wide);
         }
-        sess_slots_ = false;
-        sess_wide_ = false;
-        sess_score_ = false;
-        sess_trace_ = false;
-        std::unique_lock<PersistLock> rows_lock;
-        struct RowsGuard {  // anything thrown below leaves the handle out of row mode (the local lock releases itself)
-            bool& flag; bool armed = true;
-            ~RowsGuard() { if (armed) flag = false; }
-        } rows_guard{sess_rows_};
+        std::unique_lock<PersistLock> rows_lock;  // (a local: anything thrown below releases it)
         if (flags & FS_SESSION_ROWS) {
             const char* why = nullptr;
             if (!rows_predicate(B_, &s, 1, /*for_session=*/true, &why)) throw Error(std::string("FS_SESSION_ROWS needs ") + why);
@@ -978,19 +973,19 @@ class LM final : public LMBase {
             // leave sess_plock_ owning the mutex with sess_active_ false: session_end returned early and the device was locked out for good)
             rows_lock = acquire_persist(device_);
             FS_REQUIRE(rows_lock.owns_lock(), "another call on this device holds the persistent kernels");
-            sess_R_ = B_;
-            ensure_rows(sess_R_);
-            sess_rows_ = true;
-            sess_sampled_ = s.temp != 0.0;
+            ensure_rows(B_);
+            m.rows = true;
+            m.R = B_;
+            m.sampled = s.temp != 0.0;
         }
         sess_seed_ = seed;
         sess_adds_ = 0;
-        ensure_rows_capture(sess_rows_ ? sess_R_ : B_);
+        ensure_rows_capture(B_);
         SampleCfg cfg = make_cfg(s, flags);
-        if (!sess_rows_ && !per_slot) cfg.rep_pen = 1.0f;
-        cfg.session = sess_rows_ ? 0 : 1;
+        if (!m.rows && !m.slots) cfg.rep_pen = 1.0f;
+        cfg.session = m.rows ? 0 : 1;
         sess_cfg_ = cfg;
-        if (per_slot) {
+        if (m.slots) {
             // per-slot sampler state, allocated once per handle (the captured step graphs hold these pointers) and re-initialised for every
             // slot at its activation, so nothing of an earlier session or occupant is ever read
             if (!d_scfg_.p) {
@@ -1005,14 +1000,14 @@ class LM final : public LMBase {
             for (int b = 0; b < B_; ++b) launch_reppen_reset(srp_.view(b), a_.num_codebooks, a_.codebook_size, st_);
             FS_HIP(hipStreamSynchronize(st_));  // (cfgs is a local)
         }
-        if (sess_rows_) {
-            std::vector<SampleCfg> cfgs(sess_R_, cfg);
-            FS_HIP(hipMemcpyAsync(d_rcfg_.p, cfgs.data(), sizeof(SampleCfg) * sess_R_, hipMemcpyHostToDevice, st_));
+        if (m.rows) {
+            std::vector<SampleCfg> cfgs(m.R, cfg);
+            FS_HIP(hipMemcpyAsync(d_rcfg_.p, cfgs.data(), sizeof(SampleCfg) * m.R, hipMemcpyHostToDevice, st_));
             float* nullp = nullptr;
             FS_HIP(hipMemcpyAsync(d_hid_slot_.p, &nullp, sizeof(nullp), hipMemcpyHostToDevice, st_));
             FS_HIP(hipStreamSynchronize(st_));  // (cfgs is a local)
         }
-        rows_par_ = !per_slot && rows_par_sampler_ok(s.temp, s.top_k, n_audio_, a_.codebook_size) && !getenv("FISHRT_ROWS_SAMPLER_1024");
+        rows_par_ = !m.slots && rows_par_sampler_ok(s.temp, s.top_k, n_audio_, a_.codebook_size) && !getenv("FISHRT_ROWS_SAMPLER_1024");
         FS_HIP(hipMemcpyAsync(d_cfg_.p, &cfg, sizeof(cfg), hipMemcpyHostToDevice, st_));
         RngState rng;
         upload_rng(seed, rng, d_rng_.as<RngState>(), st_);
@@ -1035,16 +1030,12 @@ class LM final : public LMBase {
         for (auto& v : sess_count_) v = 0;
         sess_pf_ms_ = 0.0;
         sess_timed_ = false;
-        for (int b = 0; b < B_; ++b) park_slot(b);
+        for (int b = 0; b < B_; ++b) park_slot(b, m.rows);
         FS_HIP(hipMemsetAsync(d_pfx_.p, 0, sizeof(float) * (size_t)B_ * a_.dim, st_));
         FS_HIP(hipStreamSynchronize(st_));
         stats_ = {};
-        rows_guard.armed = false;
-        if (sess_rows_) sess_plock_ = std::move(rows_lock);
-        sess_slots_ = per_slot;
-        sess_wide_ = wide;
-        sess_score_ = score;
-        sess_trace_ = trace;
+        if (m.rows) sess_plock_ = std::move(rows_lock);
+        sess_ = m;
         sess_active_ = true;
     }
     // what a slot of a FS_SESSION_PER_SLOT session may sample with: the boundary of the in-launch samplers (fishrt.h: fs_lm_generate)
@@ -1064,53 +1055,110 @@ class LM final : public LMBase {
     bool slot_prefilling(int b) const { return sess_left_[b] == kSlotPrefilling; }
     bool slot_running(int b) const { return sess_left_[b] > 0 && !sess_hs_[b].done; }
     void require_live_slot(int slot) const { FS_REQUIRE(sess_active_ && slot >= 0 && slot < B_ && !slot_free(slot), "not a live session slot"); }
-    // fs_lm_session_add_ex: an add (plain, or on a prefix) whose slot samples with its own settings and / or seed.  Per-slot sessions take
-    // anything inside require_slot_sampling; row sessions what their launch instantiation covers together with the session's setting (all
-    // greedy or all sampled); the lock-step sampler has no per-slot notion, so a plain session refuses both.
-    int session_add_ex(int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling, const uint64_t* seed) override {
+    // Admission of a slot, whichever entry point asked (fishrt.h: fs_lm_session_add / _add_prefixed / _add_ex / _add_hidden / _add_scored /
+    // _add_traced; SlotRequest), to the lowest free slot: -1 when none is free or the KV page pool is short right now -- pages come back
+    // when slots are released -- neither is an error.  One path, straight down: the request is validated in full, then the slot and the
+    // pool are looked at, and only a request that will be admitted takes anything (collector buffers, pages) and is QUEUED, complete, in
+    // one push.  A plain add is a prefixed add with an empty prefix (P = 0, no shared pages, no tail); a prefixed one is the add of
+    // concat(prefix, body) except that the slot's page table starts with the prefix's full pages (shared), only the body is prefilled
+    // and the slot reserves its private pages only.
+    // Settings / seed of its own: per-slot sessions take anything inside require_slot_sampling; row sessions what their launch
+    // instantiation covers together with the session's setting (all greedy or all sampled); the lock-step sampler has no per-slot
+    // notion, so a plain session refuses both.
+    // Collectors: a hidden-state slot gets a row buffer, a scoring or traced slot a record buffer (records [cap][32] f32, then [cap][C + 1]
+    // u32: a scoring slot's targets, a traced slot's token rows), one row per iteration the slot can run; they travel in hand with the
+    // PendingAdd and the device tables learn of them at activation, so the slot's rows start at 0 with its first iteration.
+    // A scoring slot (r.frames [C + 1][N]) is forced through exactly N iterations and scored (k_score_slots in front of each of the step's
+    // sampler nodes): its SampleCfg is the session's made greedy with no repetition penalty, so its sampler nodes pick the +INFINITY
+    // the score node leaves at the target.  Scoring and traced slots always carry a seed of their own -- the one they would have had
+    // anyway when the caller gives none -- which gives them a prefill pass of their own (flush_pending), so their records are a function
+    // of the request alone (a scoring slot draws no word).
+    int session_admit(const SlotRequest& r) override {
         use_device();
+        // 1. whatever makes the request a bad one, before anything is taken or changed
         FS_REQUIRE(sess_active_, "no open session");
-        if (sampling || seed) {
-            if (!sess_slots_ && !sess_rows_)
+        const bool scored = r.frames != nullptr, prefixed = r.prefix_id >= 0;
+        FS_REQUIRE(!scored || sess_.score, "fs_lm_session_add_scored needs FS_SESSION_SCORE (begin the session with FS_SESSION_PER_SLOT | FS_SESSION_SCORE)");
+        FS_REQUIRE(!r.traced || sess_.trace, "fs_lm_session_add_traced needs FS_SESSION_TRACE (begin the session with FS_SESSION_PER_SLOT | FS_SESSION_SCORE | FS_SESSION_TRACE)");
+        FS_REQUIRE(r.L >= 1, prefixed ? "empty body (a prefixed add needs its last prompt column)" : "empty prompt");
+        const int C1 = a_.num_codebooks + 1, N = r.N;
+        if (scored) {
+            FS_REQUIRE(N >= 1, "frames: N must be >= 1");
+            for (int i = 0; i < N; ++i) {
+                const uint32_t tok = r.frames[i];
+                if (tok < t_.semantic_start_id || tok >= (uint32_t)a_.vocab_size)
+                    throw Error("frames[0][" + std::to_string(i) + "] = " + std::to_string(tok) + ": a forced slow token must lie in [semantic_start_id, vocab_size) "
+                                "(<|im_end|> and text tokens cannot be scored as a frame)");
+                for (int c = 1; c < C1; ++c)
+                    if (r.frames[(size_t)c * N + i] >= (uint32_t)a_.codebook_size)
+                        throw Error("frames[" + std::to_string(c) + "][" + std::to_string(i) + "] = " + std::to_string(r.frames[(size_t)c * N + i]) + ": a code must be < codebook_size");
+            }
+        }
+        const int P = prefixed ? live_prefix(r.prefix_id).P : 0;
+        const long long Lt = (long long)P + r.L;
+        if (scored && Lt + N - 1 > a_.max_seq_len)
+            throw Error("L + N - 1 = " + std::to_string(Lt + N - 1) + " exceeds max_seq_len (L counts the prefix; a scored sequence is never clipped)");
+        if (r.sampling || r.seed) {
+            if (!sess_.slots && !sess_.rows)
                 throw Error("per-slot sampling / seed need a session begun with FS_SESSION_PER_SLOT or FS_SESSION_ROWS (the lock-step sampler has one setting and one stream per session)");
-            if (sampling && sess_slots_) require_slot_sampling(*sampling, sess_wide_);
-            if (sampling && sess_rows_) {
-                if ((sampling->temp != 0.0) != sess_sampled_) throw Error("FS_SESSION_ROWS: every slot greedy or every slot sampled, like the session's own setting");
-                if (sess_sampled_ && !fast_persist_samples((float)sampling->temp, clamp_top_k(sampling->top_k), a_.codebook_size))
+            if (r.sampling && sess_.slots) require_slot_sampling(*r.sampling, sess_.wide);
+            if (r.sampling && sess_.rows) {
+                if ((r.sampling->temp != 0.0) != sess_.sampled) throw Error("FS_SESSION_ROWS: every slot greedy or every slot sampled, like the session's own setting");
+                if (sess_.sampled && !fast_persist_samples((float)r.sampling->temp, clamp_top_k(r.sampling->top_k), a_.codebook_size))
                     throw Error("FS_SESSION_ROWS: sampled slots need temp > 0 and 0 < top_k <= 256");
             }
         }
-        const int b = prefix_id >= 0 ? session_add_prefixed(prefix_id, prompt, L, max_new_tokens) : session_add(prompt, L, max_new_tokens);
-        if (b >= 0) {
-            PendingAdd& pa = sess_queue_.back();
-            if (sampling) {  // the session's SampleCfg with this request's settings
-                pa.has_cfg = true;
-                pa.cfg = make_cfg(*sampling, sess_cfg_.ignore_eos ? FS_GEN_IGNORE_EOS : 0);
-                pa.cfg.session = sess_cfg_.session;
-            }
-            if (seed) { pa.has_seed = true; pa.seed = *seed; }
-        }
-        return b;
-    }
-    // fs_lm_session_add_hidden: session_add_ex + hidden-state collection for the slot.  The row buffer (one row per generator iteration
-    // the slot can run) is taken BEFORE the add -- an allocation failure leaves the session as it was -- and goes back when the add is
-    // refused; the device table learns of it at activation, so the slot's rows start at 0 with its first iteration.
-    int session_add_hidden(int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling, const uint64_t* seed) override {
-        use_device();
-        FS_REQUIRE(sess_active_, "no open session");
-        FS_REQUIRE(L >= 1, "empty prompt");
-        const long long Lt = (long long)L + (prefix_id >= 0 ? live_prefix(prefix_id).P : 0);
-        const long long n_iter = std::max<long long>(1, iter_budget(max_new_tokens, Lt).n_iter);  // (Lt > max_seq_len: the add below throws)
-        SlotBuf buf = hid_.book.take((int)n_iter);
+        if (Lt > a_.max_seq_len) throw Error("prompt exceeds max_seq_len (dual_ar.rs:623-624)");
+        validate_tokens(r.prompt, 0, 1, r.L);
+        // the slot's iterations, computed once: a slot stops at max_seq_len instead of erroring; a scored one runs exactly N (never clipped)
+        const int L = (int)Lt, n_iter = (int)iter_budget(scored ? Lt + N - 2 : r.max_new_tokens, Lt).n_iter;
+        FS_REQUIRE(!scored || n_iter == N, "score buffer shorter than the slot's iterations");
+        // 2. room right now?  (reads only)
         int b = -1;
-        try {
-            b = session_add_ex(prefix_id, prompt, L, max_new_tokens, sampling, seed);
-        } catch (...) { hid_.book.put(buf); throw; }
-        if (b < 0) { hid_.book.put(buf); return b; }
-        PendingAdd& pa = sess_queue_.back();
-        FS_REQUIRE(pa.n_iter <= buf.cap, "hidden-state buffer shorter than the slot's iteration budget");
-        pa.hid = buf;
-        hid_.book.admitted(b);
+        for (int i = 0; i < B_; ++i) if (slot_free(i)) { b = i; break; }
+        if (b < 0) return -1;
+        const SessPrefix* px = prefixed ? &sess_prefixes_[r.prefix_id] : nullptr;
+        const int nfull = P / KV_PAGE, end = L + n_iter - 1;  // the prefix's full pages are shared; positions < end keep their K/V
+        auto& pg = seq_pages_[b];
+        FS_REQUIRE(!px || pg.empty(), "a free slot still holds KV pages");
+        if ((int)free_pages_.size() < (end + KV_PAGE - 1) / KV_PAGE - nfull - (int)pg.size()) return -1;
+        ensure_prefill2_buffers();
+        // 3. the queue entry, complete but for what is taken below
+        PendingAdd pa;
+        pa.slot = b; pa.L = L; pa.n_iter = n_iter; pa.start = P; pa.prefix = r.prefix_id; pa.traced = r.traced;
+        pa.prompt.assign(r.prompt, r.prompt + (size_t)C1 * r.L);
+        pa.has_seed = r.seed || scored || r.traced;
+        pa.seed = r.seed ? *r.seed : sess_seed_ + (uint64_t)sess_adds_;
+        if (scored) {
+            pa.has_cfg = true;
+            pa.cfg = sess_cfg_;
+            pa.cfg.temp = 0.f; pa.cfg.rep_pen = 1.f;
+            pa.sc_targets.resize((size_t)N * C1);  // [N][C + 1]: one iteration's 9 targets side by side
+            for (int i = 0; i < N; ++i)
+                for (int c = 0; c < C1; ++c) pa.sc_targets[(size_t)i * C1 + c] = r.frames[(size_t)c * N + i];
+        } else if (r.sampling) {  // the session's SampleCfg with this request's settings
+            pa.has_cfg = true;
+            pa.cfg = make_cfg(*r.sampling, sess_cfg_.ignore_eos ? FS_GEN_IGNORE_EOS : 0);
+            pa.cfg.session = sess_cfg_.session;
+        }
+        // 4. the collector buffers (an allocation failure leaves the session as it was)
+        if (r.collect_hidden) pa.hid = hid_.book.take(n_iter);
+        if (scored || r.traced) {
+            try { pa.sc = sc_.book.take(n_iter); } catch (...) { hid_.book.put(pa.hid); throw; }
+        }
+        // 5. the pages: references on the prefix's full ones, the slot's private ones, and a reference on the prefix's partly filled last
+        // page, held until it has been copied
+        for (int j = 0; j < nfull; ++j) { pg.push_back(px->pages[j]); ++page_refs_[px->pages[j]]; }
+        alloc_pages(b, end);
+        if (P % KV_PAGE) { pa.tail = px->pages[nfull]; ++page_refs_[pa.tail]; }
+        // 6. queued: the slot is reserved, and polls of its collectors are answered from now on
+        pa.order = sess_adds_++;
+        sess_queue_.push_back(std::move(pa));
+        sess_left_[b] = kSlotPrefilling;
+        if (r.collect_hidden) hid_.book.admitted(b);
+        if (scored || r.traced) sc_.book.admitted(b);
+        sess_traced_[b] = r.traced ? 1 : 0;
+        stats_.prompt_tokens += (uint64_t)L;
         return b;
     }
     // What a collector table (hid_, sc_) does on the device side of the book's moves.  Session begin / end: a null device table.  Activation:
@@ -1145,140 +1193,62 @@ class LM final : public LMBase {
         }
         if (n_rows) *n_rows = n;
     }
-    // fs_lm_session_add_scored: a slot whose N iterations are forced to `frames` [C + 1][N] and scored (k_score_slots in front of each of
-    // the step's sampler nodes).  Everything is validated before anything is taken or queued; the buffer (records + targets, one
-    // allocation) is taken BEFORE the add and goes back when the add is refused; the device table learns of it at activation, like a
-    // hidden-state collector's.  The slot's SampleCfg is the session's made greedy with no repetition penalty, so its sampler nodes pick
-    // the +INFINITY the score node leaves at the target; a seed of its own only gives it a prefill pass of its own (it draws no word).
-    int session_add_scored(int prefix_id, const uint32_t* prompt, int L, const uint32_t* frames, int N, int collect_hidden) override {
-        use_device();
-        FS_REQUIRE(sess_active_, "no open session");
-        FS_REQUIRE(sess_score_, "fs_lm_session_add_scored needs FS_SESSION_SCORE (begin the session with FS_SESSION_PER_SLOT | FS_SESSION_SCORE)");
-        FS_REQUIRE(L >= 1, "empty prompt");
-        FS_REQUIRE(N >= 1, "frames: N must be >= 1");
-        const int C1 = a_.num_codebooks + 1;
-        for (int i = 0; i < N; ++i) {
-            const uint32_t tok = frames[i];
-            if (tok < t_.semantic_start_id || tok >= (uint32_t)a_.vocab_size)
-                throw Error("frames[0][" + std::to_string(i) + "] = " + std::to_string(tok) + ": a forced slow token must lie in [semantic_start_id, vocab_size) "
-                            "(<|im_end|> and text tokens cannot be scored as a frame)");
-            for (int r = 1; r < C1; ++r)
-                if (frames[(size_t)r * N + i] >= (uint32_t)a_.codebook_size)
-                    throw Error("frames[" + std::to_string(r) + "][" + std::to_string(i) + "] = " + std::to_string(frames[(size_t)r * N + i]) + ": a code must be < codebook_size");
+    // the records [first_row, rows so far) of a scoring or traced slot, unpacked into whichever outputs are given ([n][C + 1] per decision,
+    // [n] per iteration); tokens / n_decisions: the rows behind the records, a traced slot's picks.  *n_rows = rows so far.
+    struct RecordsOut {
+        float *logprob, *top_logprob;
+        uint32_t* top;
+        float* eos_logprob;
+        uint32_t* tokens = nullptr;
+        int* n_decisions = nullptr;
+    };
+    void poll_records(int slot, size_t first_row, size_t cap_rows, const RecordsOut& o, size_t* n_rows) {
+        const ScoreSlot& e = sc_.book.entry(slot);
+        const size_t n = slot_prefilling(slot) ? 0 : (size_t)e.count;
+        const bool want_tokens = o.tokens || o.n_decisions;
+        if ((o.logprob || o.top_logprob || o.top || o.eos_logprob || want_tokens) && first_row < n) {
+            const size_t m = std::min(n - first_row, cap_rows), C1 = (size_t)a_.num_codebooks + 1;
+            std::vector<float> rec(m * SCORE_REC_WORDS);
+            std::vector<uint32_t> tk(want_tokens ? m * C1 : 0);
+            if (m) FS_HIP(hipMemcpyAsync(rec.data(), e.rec + first_row * SCORE_REC_WORDS, sizeof(float) * rec.size(), hipMemcpyDeviceToHost, st_));
+            if (m && want_tokens) FS_HIP(hipMemcpyAsync(tk.data(), e.targets + first_row * C1, sizeof(uint32_t) * tk.size(), hipMemcpyDeviceToHost, st_));
+            FS_HIP(hipStreamSynchronize(st_));
+            for (size_t i = 0; i < m; ++i) {
+                const float* r = rec.data() + i * SCORE_REC_WORDS;
+                for (size_t d = 0; d < C1; ++d) {
+                    if (o.tokens) o.tokens[i * C1 + d] = tk[i * C1 + d];
+                    if (o.logprob) o.logprob[i * C1 + d] = r[SCORE_REC_LOGPROB + d];
+                    if (o.top_logprob) o.top_logprob[i * C1 + d] = r[SCORE_REC_TOP_LOGPROB + d];
+                    if (o.top) std::memcpy(&o.top[i * C1 + d], &r[SCORE_REC_TOP + d], sizeof(uint32_t));
+                }
+                if (o.eos_logprob) o.eos_logprob[i] = r[SCORE_REC_EOS];
+                // (an iteration whose slow pick was <|im_end|> made that one decision; tokens[.][0] is then <|im_end|>'s id)
+                if (o.n_decisions) o.n_decisions[i] = tk[i * C1] == t_.im_end_id ? 1 : (int)C1;
+            }
         }
-        const long long Lt = (long long)L + (prefix_id >= 0 ? live_prefix(prefix_id).P : 0);
-        if (Lt + N - 1 > a_.max_seq_len)
-            throw Error("L + N - 1 = " + std::to_string(Lt + N - 1) + " exceeds max_seq_len (L counts the prefix; a scored sequence is never clipped)");
-        const int max_new = (int)(Lt + N - 2);  // exactly N iterations (iter_budget)
-        SlotBuf buf = sc_.book.take(N);
-        const uint64_t seed = sess_seed_ + (uint64_t)sess_adds_;
-        int b = -1;
-        try {
-            b = collect_hidden ? session_add_hidden(prefix_id, prompt, L, max_new, nullptr, &seed) : session_add_ex(prefix_id, prompt, L, max_new, nullptr, &seed);
-        } catch (...) { sc_.book.put(buf); throw; }
-        if (b < 0) { sc_.book.put(buf); return b; }
-        PendingAdd& pa = sess_queue_.back();
-        pa.has_cfg = true;
-        pa.cfg = sess_cfg_;
-        pa.cfg.temp = 0.f; pa.cfg.rep_pen = 1.f;
-        pa.sc = buf;
-        pa.sc_targets.resize((size_t)N * C1);  // [N][C + 1]: one iteration's 9 targets side by side
-        for (int i = 0; i < N; ++i)
-            for (int r = 0; r < C1; ++r) pa.sc_targets[(size_t)i * C1 + r] = frames[(size_t)r * N + i];
-        sc_.book.admitted(b);
-        return b;
+        if (n_rows) *n_rows = n;
     }
     void session_poll_scores(int slot, size_t first_row, float* logprob, float* top_logprob, uint32_t* top, float* eos_logprob, size_t cap_rows,
                              size_t* n_rows) override {
         use_device();
         FS_REQUIRE(sess_active_, "no open session");
-        FS_REQUIRE(sess_score_, "fs_lm_session_poll_scores needs FS_SESSION_SCORE (begin the session with FS_SESSION_PER_SLOT | FS_SESSION_SCORE)");
+        FS_REQUIRE(sess_.score, "fs_lm_session_poll_scores needs FS_SESSION_SCORE (begin the session with FS_SESSION_PER_SLOT | FS_SESSION_SCORE)");
         require_live_slot(slot);
         FS_REQUIRE(sc_.book.wanted(slot) && !sess_traced_[slot], "the slot is not a scoring slot (it was not admitted with fs_lm_session_add_scored)");
-        const ScoreSlot& e = sc_.book.entry(slot);
-        const size_t n = slot_prefilling(slot) ? 0 : (size_t)e.count;
-        if ((logprob || top_logprob || top || eos_logprob) && first_row < n) {
-            const size_t m = std::min(n - first_row, cap_rows), C1 = (size_t)a_.num_codebooks + 1;
-            std::vector<float> rec(m * SCORE_REC_WORDS);
-            if (m) FS_HIP(hipMemcpyAsync(rec.data(), e.rec + first_row * SCORE_REC_WORDS, sizeof(float) * rec.size(), hipMemcpyDeviceToHost, st_));
-            FS_HIP(hipStreamSynchronize(st_));
-            for (size_t i = 0; i < m; ++i) {
-                const float* r = rec.data() + i * SCORE_REC_WORDS;
-                for (size_t d = 0; d < C1; ++d) {
-                    if (logprob) logprob[i * C1 + d] = r[d];
-                    if (top_logprob) top_logprob[i * C1 + d] = r[9 + d];
-                    if (top) std::memcpy(&top[i * C1 + d], &r[18 + d], sizeof(uint32_t));
-                }
-                if (eos_logprob) eos_logprob[i] = r[27];
-            }
-        }
-        if (n_rows) *n_rows = n;
-    }
-    // fs_lm_session_add_traced: session_add_ex (session_add_hidden with collect_hidden) whose slot also leaves the score record of its own
-    // picks.  Its table entry is a scoring slot's without targets, from the same book (same buffers: records [cap][32] f32, then the
-    // token rows [cap][C + 1] u32 where a scoring slot keeps its targets); the buffer, one row per iteration the slot can run, is taken
-    // BEFORE the add and goes back when the add is refused.  A seed of its own -- the one it would have had anyway when the caller gives
-    // none -- gives it a prefill pass of its own, so its records are a function of the request alone.
-    int session_add_traced(int prefix_id, const uint32_t* prompt, int L, int max_new_tokens, const fs_sampling* sampling, const uint64_t* seed,
-                           int collect_hidden) override {
-        use_device();
-        FS_REQUIRE(sess_active_, "no open session");
-        FS_REQUIRE(sess_trace_, "fs_lm_session_add_traced needs FS_SESSION_TRACE (begin the session with FS_SESSION_PER_SLOT | FS_SESSION_SCORE | FS_SESSION_TRACE)");
-        FS_REQUIRE(L >= 1, "empty prompt");
-        const long long Lt = (long long)L + (prefix_id >= 0 ? live_prefix(prefix_id).P : 0);
-        const long long n_iter = std::max<long long>(1, iter_budget(max_new_tokens, Lt).n_iter);  // (Lt > max_seq_len: the add below throws)
-        SlotBuf buf = sc_.book.take((int)n_iter);
-        const uint64_t own = seed ? *seed : sess_seed_ + (uint64_t)sess_adds_;
-        int b = -1;
-        try {
-            b = collect_hidden ? session_add_hidden(prefix_id, prompt, L, max_new_tokens, sampling, &own)
-                               : session_add_ex(prefix_id, prompt, L, max_new_tokens, sampling, &own);
-        } catch (...) { sc_.book.put(buf); throw; }
-        if (b < 0) { sc_.book.put(buf); return b; }
-        PendingAdd& pa = sess_queue_.back();
-        FS_REQUIRE(pa.n_iter <= buf.cap, "trace buffer shorter than the slot's iteration budget");
-        pa.sc = buf;
-        pa.traced = true;
-        sc_.book.admitted(b);
-        sess_traced_[b] = 1;
-        return b;
+        poll_records(slot, first_row, cap_rows, RecordsOut{logprob, top_logprob, top, eos_logprob}, n_rows);
     }
     void session_poll_trace(int slot, size_t first_row, uint32_t* tokens, float* logprob, float* top_logprob, uint32_t* top, float* eos_logprob,
                             int* n_decisions, size_t cap_rows, size_t* n_rows) override {
         use_device();
         FS_REQUIRE(sess_active_, "no open session");
-        FS_REQUIRE(sess_trace_, "fs_lm_session_poll_trace needs FS_SESSION_TRACE (begin the session with FS_SESSION_PER_SLOT | FS_SESSION_SCORE | FS_SESSION_TRACE)");
+        FS_REQUIRE(sess_.trace, "fs_lm_session_poll_trace needs FS_SESSION_TRACE (begin the session with FS_SESSION_PER_SLOT | FS_SESSION_SCORE | FS_SESSION_TRACE)");
         require_live_slot(slot);
         FS_REQUIRE(sc_.book.wanted(slot) && sess_traced_[slot], "the slot is not a traced slot (it was not admitted with fs_lm_session_add_traced)");
-        const ScoreSlot& e = sc_.book.entry(slot);
-        const size_t n = slot_prefilling(slot) ? 0 : (size_t)e.count;
-        if ((tokens || logprob || top_logprob || top || eos_logprob || n_decisions) && first_row < n) {
-            const size_t m = std::min(n - first_row, cap_rows), C1 = (size_t)a_.num_codebooks + 1;
-            std::vector<float> rec(m * SCORE_REC_WORDS);
-            std::vector<uint32_t> tk(m * C1);
-            if (m) {
-                FS_HIP(hipMemcpyAsync(rec.data(), e.rec + first_row * SCORE_REC_WORDS, sizeof(float) * rec.size(), hipMemcpyDeviceToHost, st_));
-                FS_HIP(hipMemcpyAsync(tk.data(), e.targets + first_row * C1, sizeof(uint32_t) * tk.size(), hipMemcpyDeviceToHost, st_));
-            }
-            FS_HIP(hipStreamSynchronize(st_));
-            for (size_t i = 0; i < m; ++i) {
-                const float* r = rec.data() + i * SCORE_REC_WORDS;
-                for (size_t d = 0; d < C1; ++d) {
-                    if (tokens) tokens[i * C1 + d] = tk[i * C1 + d];
-                    if (logprob) logprob[i * C1 + d] = r[d];
-                    if (top_logprob) top_logprob[i * C1 + d] = r[9 + d];
-                    if (top) std::memcpy(&top[i * C1 + d], &r[18 + d], sizeof(uint32_t));
-                }
-                if (eos_logprob) eos_logprob[i] = r[27];
-                // (an iteration whose slow pick was <|im_end|> made that one decision; tokens[.][0] is then <|im_end|>'s id)
-                if (n_decisions) n_decisions[i] = tk[i * C1] == t_.im_end_id ? 1 : (int)C1;
-            }
-        }
-        if (n_rows) *n_rows = n;
+        poll_records(slot, first_row, cap_rows, RecordsOut{logprob, top_logprob, top, eos_logprob, tokens, n_decisions}, n_rows);
     }
-    void park_slot(int b) {
+    void park_slot(int b, bool rows) {
         SeqState ss = {};
-        ss.done = sess_rows_ ? 2 : 1; ss.frame = 1;  // (rows mode: a terminated row is skipped by the row kernels altogether)
+        ss.done = rows ? 2 : 1; ss.frame = 1;  // (rows mode: a terminated row is skipped by the row kernels altogether)
         sess_hs_[b] = ss;
         FS_HIP(hipMemcpyAsync(state(b), &sess_hs_[b], sizeof(SeqState), hipMemcpyHostToDevice, st_));
         FS_HIP(hipMemcpyAsync(d_page_table_.as<int>() + (size_t)b * max_pages_, &sess_scratch_, sizeof(int), hipMemcpyHostToDevice, st_));
@@ -1287,17 +1257,11 @@ class LM final : public LMBase {
     // Joining requests are prefilled on a second stream with their own row buffers, staging SeqState (index B_) and page-table rows
     // (B_ ..), so the decode steps of the live slots go on underneath; a joining slot stays parked (scratch page, frozen) until its prefill
     // has finished and activate_pending() -- between two steps -- hands it its page-table row, state and first input embedding.
-    // session_add only QUEUES the request; flush_pending() (first thing in session_step, or when the row buffers are full) prefills
+    // session_admit only QUEUES the request; flush_pending() (first thing in session_step, or when the row buffers are full) prefills
     // everything queued as GROUP passes: requests sorted by length, each pass = as many of them as fit the 2048 activation rows,
     // right-padded to the longest of the pass (rows = sequences x tokens, RowMap.seq_rows; causal attention: a real token never sees a
     // pad token, and the K/V a pad position writes into the slot's own pages lies beyond its length, where the first decode steps
     // overwrite it before anything reads it).  A burst of 32 requests is admitted in 2-3 passes instead of 32.
-    int session_add(const uint32_t* prompt, int L, int max_new_tokens) override {
-        use_device();
-        FS_REQUIRE(sess_active_, "no open session");
-        FS_REQUIRE(L >= 1, "empty prompt");
-        return admit(nullptr, -1, prompt, L, max_new_tokens);
-    }
     // a queued request: plain add (prompt = all L columns, start 0), prefixed add (prompt = the body's L - start columns, start = the
     // prefix's P, tail = the prefix's partly filled last page, held until the copy has run) or a prefix's own pass (create: prompt = its P
     // columns, all of them prefilled into the prefix's pages; slot -1) or a prefix's import (create and import_kv: blob = the payload of
@@ -1329,13 +1293,13 @@ class LM final : public LMBase {
         FS_REQUIRE(P >= 1, "empty prefix");
         FS_REQUIRE(P < a_.max_seq_len, "prefix leaves no room for a body within max_seq_len");
         validate_tokens(prompt, 0, 1, P);
-        const int id = queue_prefix(P);
-        if (id >= 0) sess_queue_.back().prompt.assign(prompt, prompt + (size_t)(a_.num_codebooks + 1) * P);
-        return id;
+        PendingAdd pa;
+        pa.prompt.assign(prompt, prompt + (size_t)(a_.num_codebooks + 1) * P);
+        return queue_prefix(P, std::move(pa));
     }
-    // a pending prefix of P positions: its pages taken, its creating pass queued (the caller gives sess_queue_.back() what the pass moves:
-    // the prompt, or an imported payload).  Returns its id, or -1 when the page pool is short right now.
-    int queue_prefix(int P) {
+    // a pending prefix of P positions: its pages taken, its creating pass queued (`pa` holds what the pass moves: the prompt, or an
+    // imported payload).  Returns its id, or -1 when the page pool is short right now.
+    int queue_prefix(int P, PendingAdd pa) {
         ensure_prefill2_buffers();
         const int np = (P + KV_PAGE - 1) / KV_PAGE;
         if ((int)free_pages_.size() < np) return -1;
@@ -1343,7 +1307,6 @@ class LM final : public LMBase {
         px.P = P; px.live = true; px.pending = true;
         for (int j = 0; j < np; ++j) px.pages.push_back(take_page());
         sess_prefixes_.push_back(std::move(px));
-        PendingAdd pa;
         pa.create = true; pa.L = P; pa.prefix = (int)sess_prefixes_.size() - 1;
         sess_queue_.push_back(std::move(pa));
         return (int)sess_prefixes_.size() - 1;
@@ -1362,43 +1325,6 @@ class LM final : public LMBase {
         SessPrefix& px = live_prefix(id);
         px.live = false;
         if (!px.pending) drop_prefix_pages(px);  // (its pass still queued or in flight: activate_pending drops them after it)
-    }
-    // == session_add(concat(prefix, body)) except that the slot's page table starts with the prefix's full pages (shared) and only the
-    // body is prefilled; the slot reserves its private pages only
-    int session_add_prefixed(int id, const uint32_t* body, int L_body, int max_new_tokens) override {
-        use_device();
-        SessPrefix& px = live_prefix(id);
-        FS_REQUIRE(L_body >= 1, "empty body (a prefixed add needs its last prompt column)");
-        return admit(&px, id, body, L_body, max_new_tokens);
-    }
-    // Admission to the lowest free slot (-1: none free, or not enough free KV pages right now -- pages come back when slots are released --
-    // neither is an error).  A plain add is a prefixed add with an empty prefix (px == nullptr: P = 0, no shared pages, no tail); `cols`
-    // are the n_cols columns the slot prefills itself.  The request is only QUEUED here, with its private pages reserved.
-    int admit(const SessPrefix* px, int prefix_id, const uint32_t* cols, int n_cols, int max_new_tokens) {
-        const int P = px ? px->P : 0, L = P + n_cols;
-        if (L > a_.max_seq_len) throw Error("prompt exceeds max_seq_len (dual_ar.rs:623-624)");
-        int b = -1;
-        for (int i = 0; i < B_; ++i) if (slot_free(i)) { b = i; break; }
-        if (b < 0) return -1;
-        const int C1 = a_.num_codebooks + 1;
-        validate_tokens(cols, 0, 1, n_cols);
-        const int n_iter = (int)iter_budget(max_new_tokens, L).n_iter;  // (a slot stops at max_seq_len instead of erroring)
-        ensure_prefill2_buffers();
-        const int nfull = P / KV_PAGE;
-        auto& pg = seq_pages_[b];
-        FS_REQUIRE(!px || pg.empty(), "a free slot still holds KV pages");
-        const int need = (L + n_iter - 1 + KV_PAGE - 1) / KV_PAGE;
-        if ((int)free_pages_.size() < need - nfull - (int)pg.size()) return -1;
-        for (int j = 0; j < nfull; ++j) { pg.push_back(px->pages[j]); ++page_refs_[px->pages[j]]; }
-        alloc_pages(b, L + n_iter - 1);
-        PendingAdd pa;
-        pa.slot = b; pa.L = L; pa.n_iter = n_iter; pa.order = sess_adds_++; pa.start = P; pa.prefix = prefix_id;
-        if (P % KV_PAGE) { pa.tail = px->pages[nfull]; ++page_refs_[pa.tail]; }
-        pa.prompt.assign(cols, cols + (size_t)C1 * n_cols);
-        sess_queue_.push_back(std::move(pa));
-        sess_left_[b] = kSlotPrefilling;  // (reserved)
-        stats_.prompt_tokens += (uint64_t)L;
-        return b;
     }
     void session_info(int64_t out[8]) override {
         int64_t shared = 0, live = 0;
@@ -1481,14 +1407,11 @@ class LM final : public LMBase {
         FS_REQUIRE(h.P >= 1 && h.P < a_.max_seq_len, "prefix blob: P outside 1 <= P < max_seq_len (a prefix must leave room for a body)");
         FS_REQUIRE(h.payload_bytes == (uint64_t)prefix_payload_bytes(h.P), "prefix blob: payload_bytes does not match n_layer * 2 * P * n_local_heads * head_dim elements");
         FS_REQUIRE(h.weights_fingerprint == weights_fingerprint(), "prefix blob: weights_fingerprint differs from this handle's (other weights or storage type)");
-        const int id = queue_prefix(h.P);
-        if (id >= 0) {
-            PendingAdd& pa = sess_queue_.back();
-            pa.import_kv = true;
-            const uint8_t* payload = static_cast<const uint8_t*>(blob) + sizeof(h);
-            pa.blob.assign(payload, payload + h.payload_bytes);  // (the caller may free its blob as soon as this returns)
-        }
-        return id;
+        PendingAdd pa;
+        pa.import_kv = true;
+        const uint8_t* payload = static_cast<const uint8_t*>(blob) + sizeof(h);
+        pa.blob.assign(payload, payload + h.payload_bytes);  // (the caller may free its blob as soon as this returns)
+        return queue_prefix(h.P, std::move(pa));
     }
     // the pass of the imports at the head of the (sorted) queue: per import one host-to-device copy into the staging buffer and one
     // k_kv_rows_scatter into its pages, on the prefill stream; activated like a creating pass (pa.create).  No counter of a transformer
@@ -1590,7 +1513,7 @@ class LM final : public LMBase {
                     need_sum += need;
                     ++S;
                 }
-                if (need_sum > (int)free_pages_.size()) S = 1;  // (the first member alone does not fit a group pass either: its own pages were reserved by session_add)
+                if (need_sum > (int)free_pages_.size()) S = 1;  // (the first member alone does not fit a group pass either: its own pages were reserved by session_admit)
             }
             launch_tail_copies(sess_queue_.begin() + i, sess_queue_.begin() + i + S);
             if (S == 1 || !flash) {  // one sequence, passes of <= kRowsCap rows
@@ -1731,7 +1654,7 @@ class LM final : public LMBase {
             // read pa / sess_cfg_, which outlive the wait below.)
             const SampleCfg& cfg = pa.has_cfg ? pa.cfg : sess_cfg_;
             const uint64_t seed = pa.has_seed ? pa.seed : sess_seed_ + (uint64_t)pa.order;
-            if (sess_rows_) {  // the slot becomes a live row: first-frame input, iteration budget, fresh repetition-penalty window and sampler stream
+            if (sess_.rows) {  // the slot becomes a live row: first-frame input, iteration budget, fresh repetition-penalty window and sampler stream
                 LmKernels<WT>::embed(d_, tok_emb_, cb_emb_, a_.num_codebooks, a_.codebook_size, d_cfg_.as<SampleCfg>(), nullptr, state(b), x(b), st_);
                 sess_budget_tmp_ = pa.n_iter;
                 FS_HIP(hipMemcpyAsync(d_rbudget_.as<int>() + b, &sess_budget_tmp_, sizeof(int), hipMemcpyHostToDevice, st_));
@@ -1741,7 +1664,7 @@ class LM final : public LMBase {
                 launch_reppen_reset(rrp_.view(b), a_.num_codebooks, a_.codebook_size, st_);
                 FS_HIP(hipStreamSynchronize(st_));  // (rng / budget are locals)
             } else {
-                if (sess_slots_) {  // the slot's settings, a StdRng stream at word 0 (no look-ahead word yet) and empty repetition-penalty windows
+                if (sess_.slots) {  // the slot's settings, a StdRng stream at word 0 (no look-ahead word yet) and empty repetition-penalty windows
                     SlotRng sr;
                     std::memset(&sr, 0xFF, sizeof(sr));
                     sr.rng = RngState{};
@@ -1813,21 +1736,21 @@ class LM final : public LMBase {
                 continue;
             }
             if (!live) break;
-            if (sess_rows_) {
+            if (sess_.rows) {
                 PersistFlagsGuard flags_guard{*this};
-                use_persist_ = true; use_pslow_ = true; persist_sampled_ = sess_sampled_;
+                use_persist_ = true; use_pslow_ = true; persist_sampled_ = sess_.sampled;
                 // the launch group covers slots [0, top): the smallest instantiations that hold the highest live slot (an 8-slot session with two
                 // live requests in slots 0, 1 pays the 2-row frame, 0.84 ms, not the 8-row one, 1.67 ms); slots are handed out lowest-first
                 int top = 0;
                 for (int b = 0; b < B_; ++b)
                     if (slot_running(b)) top = b + 1;
-                const int Rs = std::min(sess_R_, top <= 2 ? 2 : (top <= 4 ? 4 : 8));
+                const int Rs = std::min(sess_.R, top <= 2 ? 2 : (top <= 4 ? 4 : 8));
                 for (int i = 0; i < chunk; ++i) {
                     set_bucket(longest + i + 1);
                     launch_rows_slow(rows_slow_args(Rs), Rs, st_);
                     // (x(r) now holds row r's pre-norm hidden state; the fast launches overwrite it with the next input)
                     if (hid_.book.live() > 0) launch_hidden_rows(hid_.dev.as<HidSlot>(), state(0), x(0), a_.dim, top, st_);
-                    launch_rows_fast_groups(top, sess_sampled_);
+                    launch_rows_fast_groups(top, sess_.sampled);
                 }
             } else
             for (int i = 0; i < chunk; ++i) {
@@ -1838,7 +1761,7 @@ class LM final : public LMBase {
             for (int b = 0; b < B_; ++b)
                 if (slot_running(b)) {
                     sess_left_[b] -= chunk; sess_pos_[b] += chunk;
-                    if (sess_left_[b] == 0 && !sess_rows_) {  // iteration budget spent: the slot is finished whatever it sampled (rows mode: the kernels' own budget word terminates the row)
+                    if (sess_left_[b] == 0 && !sess_.rows) {  // iteration budget spent: the slot is finished whatever it sampled (rows mode: the kernels' own budget word terminates the row)
                         // Its last iteration left pos = L + n_iter - 1, one token PAST its page allocation (and == max_seq_len when the
                         // budget was clamped), and a frozen slot still rides the step graphs, whose QKV epilogue writes K/V at pos: park
                         // the write on the scratch page at position 0 (n_out and the codes stay) before the next replay can run.
@@ -1857,7 +1780,7 @@ class LM final : public LMBase {
             tab_take_counts(sc_);
             // a spin timeout inside the chunk (the joining prefill shares the CUs the persistent launches need co-resident) means the slots'
             // codes are garbage: raise instead of handing them out; the caller ends the session (the handle is off the row path afterwards)
-            if (sess_rows_) rows_check_ctl(/*include_b1_fast=*/false);
+            if (sess_.rows) rows_check_ctl(/*include_b1_fast=*/false);
             else check_rows_xchg();
         }
         FS_HIP(hipEventRecord(ev_[2], st_));
@@ -1896,7 +1819,7 @@ class LM final : public LMBase {
         while (slot_prefilling(slot)) { flush_pending(); activate_pending(true); }  // (its prefill is queued or in flight: let it finish first)
         sess_released_frames_ += (uint64_t)sess_hs_[slot].n_out;
         truncate(slot, 0);
-        park_slot(slot);
+        park_slot(slot, sess_.rows);
         tab_drop(hid_, slot);
         tab_drop(sc_, slot);
         sess_traced_[slot] = 0;
@@ -1919,13 +1842,10 @@ class LM final : public LMBase {
         FS_HIP(hipMemcpyAsync(d_cfg_.p, &cfg, sizeof(cfg), hipMemcpyHostToDevice, st_));
         FS_HIP(hipStreamSynchronize(st_));
         sess_active_ = false;
-        sess_slots_ = false;
-        sess_wide_ = false;
-        sess_score_ = false;
-        sess_trace_ = false;
+        const bool rows = sess_.rows;
+        sess_ = {};
         sess_released_frames_ = 0;
-        if (sess_rows_) check_ctl({&d_rctl_s_, &d_rctl_f_}, nullptr, nullptr);  // (a session that ended on an error: reset only)
-        sess_rows_ = false;
+        if (rows) check_ctl({&d_rctl_s_, &d_rctl_f_}, nullptr, nullptr);  // (a session that ended on an error: reset only)
         if (sess_plock_.owns_lock()) sess_plock_.unlock();
     }
 
@@ -2628,7 +2548,7 @@ class LM final : public LMBase {
         // one captured graph serves every mix of collecting and non-collecting slots)
         if (sess_active_) launch_hidden_rows(hid_.dev.as<HidSlot>(), state(0), cs.X, a_.dim, B, st_);
         // block-parallel samplers (temp > 1e-7, top_k <= 256): the step's C + 1 StdRng words per row are derived up front
-        const bool slots = sess_active_ && sess_slots_;  // FS_SESSION_PER_SLOT: the 9 sampler nodes are the per-slot ones, one for one
+        const bool slots = sess_.slots;  // FS_SESSION_PER_SLOT: the 9 sampler nodes are the per-slot ones, one for one
         const uint32_t* words = rows_par_ ? d_rwords_.as<uint32_t>() : nullptr;
         if (rows_par_) SampleKernels<WT>::rows_rng_words(d_rng_.as<RngState>(), B, C + 1, state(0), d_rwords_.as<uint32_t>(), st_);
         const bool capt = cap_frames_ > 0 && d_rcap_.p && d_rcap_.n >= sizeof(float) * (size_t)B * cap_frames_ * 9 * 2048;  // (fs_lm_debug_capture)
@@ -2637,15 +2557,15 @@ class LM final : public LMBase {
         const float* prep_g = fold && a_.dim <= 1024 ? fast_[0].attn_norm : nullptr;
         // FS_SESSION_SCORE: one score node in front of each per-slot sampler node, behind the capture of the raw row (null table entries
         // exit at once, so the one captured graph serves every mix of scoring and generating slots)
-        const bool score = slots && sess_score_;
+        const bool score = slots && sess_.score;
         // FS_SESSION_TRACE: the score nodes know the traced slots' stash, and one tail node behind the last sampler closes their rows
-        const bool trace = score && sess_trace_;
+        const bool trace = score && sess_.trace;
         float* stash = trace ? d_trace_.as<float>() : nullptr;
         if (score) launch_score_slots(sc_.dev.as<ScoreSlot>(), state(0), d_scfg_.as<SampleCfg>(), d_lrows_.as<float>(), ld_slow_, n_audio_, 0, C, B, st_, stash);
         if (slots)
             SampleKernels<WT>::sample_slow_slots(d_, d_lrows_.as<float>(), ld_slow_, n_audio_, d_scfg_.as<SampleCfg>(), d_srng_.as<SlotRng>(), B, state(0),
                                                  cs.X, d_xfrows_.as<float>(), st_, prep_g, cs.A, fold ? d_epoch_.as<uint32_t>() : nullptr,
-                                                 capt ? d_rcap_.as<float>() : nullptr, cap_frames_, sess_wide_);
+                                                 capt ? d_rcap_.as<float>() : nullptr, cap_frames_, sess_.wide);
         else
         SampleKernels<WT>::sample_slow_rows(d_, d_lrows_.as<float>(), ld_slow_, n_audio_, d_cfg_.as<SampleCfg>(), d_rng_.as<RngState>(), B,
                                             C + 1, state(0), cs.X, d_xfrows_.as<float>(), st_, words, prep_g, cs.A, fold ? d_epoch_.as<uint32_t>() : nullptr);
@@ -2690,7 +2610,7 @@ class LM final : public LMBase {
                 RepPenState rp0 = srp_.view(0);
                 SampleKernels<WT>::sample_fast_slots(d_, d_lfast_.as<float>(), cbi, C, a_.codebook_size, d_scfg_.as<SampleCfg>(), d_srng_.as<SlotRng>(), rp0,
                                                      B, state(0), fast_emb_, d_xfrows_.as<float>(), tok_emb_, cb_emb_, cs.X, d_out_.as<uint32_t>(), out_cap_,
-                                                     st_, prep_f, cs.A, sess_wide_);
+                                                     st_, prep_f, cs.A, sess_.wide);
             } else
             SampleKernels<WT>::sample_fast_rows(d_, d_lfast_.as<float>(), cbi, C, a_.codebook_size, d_cfg_.as<SampleCfg>(),
                                                 d_rng_.as<RngState>(), B, state(0), fast_emb_, d_xfrows_.as<float>(), tok_emb_, cb_emb_,
@@ -2721,9 +2641,8 @@ class LM final : public LMBase {
         drop_batch_graphs();
     }
     hipGraphExec_t batch_graph(int B) {
-        const int key = (sess_active_ ? 1 << 24 : 0) + (rows_par_ ? 1 << 25 : 0) + (sess_active_ && sess_slots_ ? 1 << 26 : 0) + (sess_active_ && sess_slots_ && sess_wide_ ? 1 << 27 : 0) +
-                        (sess_active_ && sess_slots_ && sess_score_ ? 1 << 28 : 0) +
-                        (sess_active_ && sess_slots_ && sess_score_ && sess_trace_ ? 1 << 29 : 0) + B * 1024 + nc_launch_;
+        const int key = (sess_active_ ? 1 << 24 : 0) + (rows_par_ ? 1 << 25 : 0) + (sess_.slots ? 1 << 26 : 0) + (sess_.slots && sess_.wide ? 1 << 27 : 0) +
+                        (sess_.slots && sess_.score ? 1 << 28 : 0) + (sess_.slots && sess_.score && sess_.trace ? 1 << 29 : 0) + B * 1024 + nc_launch_;
         auto it = batch_graphs_.find(key);
         if (it != batch_graphs_.end()) return it->second;
         {   // the co-residency query of the folded step (rows_fold_ok -> occupancy API) is answered once, OUTSIDE stream capture
@@ -3126,12 +3045,20 @@ class LM final : public LMBase {
     bool persist_ok_ = false, use_persist_ = false, pslow_ok_ = false, use_pslow_ = false, persist_sampled_ = false;
     int batch_rows_ = 0, batch_row_ = 0;  // generate_batch_sequential: batch sampler semantics for the row being generated
     // continuous-batching session: per-slot remaining iterations (-1 = empty), host copy of the slot states, scratch KV page of empty slots
-    bool sess_active_ = false, sess_rows_ = false, sess_sampled_ = false;  // sess_rows_: FS_SESSION_ROWS (slots on the request-row kernels)
-    bool sess_slots_ = false;  // FS_SESSION_PER_SLOT (slots on the static-batch step with the per-slot samplers)
-    bool sess_wide_ = false;   // FS_SESSION_WIDE_SAMPLER (the per-slot sampler nodes that also take nucleus-only / top_k > 256 settings)
+    bool sess_active_ = false;
+    // what kind of session is open: set by session_begin together with sess_active_, {} again from session_end on (all false outside a session)
+    struct SessMode {
+        bool rows = false;     // FS_SESSION_ROWS (slots on the request-row kernels) ...
+        bool sampled = false;  // ... whose slots all sample (else all greedy) ...
+        int R = 0;             // ... and how many rows it has
+        bool slots = false;    // FS_SESSION_PER_SLOT (slots on the static-batch step with the per-slot samplers)
+        bool wide = false;     // FS_SESSION_WIDE_SAMPLER (the per-slot sampler nodes that also take nucleus-only / top_k > 256 settings)
+        bool score = false;    // FS_SESSION_SCORE (the session's step graphs carry the 9 score nodes)
+        bool trace = false;    // FS_SESSION_TRACE (... and the traced slots' tail node; the score nodes know the stash)
+    } sess_{};
     SampleCfg sess_cfg_ = {};  // the session's own SampleCfg (slots admitted without settings of their own)
     DevBuf d_scfg_, d_srng_;   // per-slot sampler state [max_batch] (k_sample_*_slots)
-    int sess_R_ = 0, sess_adds_ = 0, sess_budget_tmp_ = 0;
+    int sess_adds_ = 0, sess_budget_tmp_ = 0;
     uint64_t sess_seed_ = 0;
     std::unique_lock<PersistLock> sess_plock_;
     std::vector<int> sess_left_, sess_pos_;
@@ -3149,7 +3076,7 @@ class LM final : public LMBase {
     double sess_pf_ms_ = 0.0;
     std::vector<uint32_t> sess_stage_prompts_;
     std::vector<int> sess_stage_rows_;
-    std::vector<PendingAdd> sess_queue_, sess_flight_;  // joining requests: queued by session_add / prefill launched (flush_pending)
+    std::vector<PendingAdd> sess_queue_, sess_flight_;  // joining requests: queued by session_admit / prefill launched (flush_pending)
     // prefix KV blobs: the handle's staging buffer (grow-only: the largest payload moved so far -- one export, or the imports of one pass),
     // the page ids of the prefixes being moved (device + the host vector the upload reads), the cached arena fingerprint
     DevBuf d_kvb_, d_kvb_pages_, d_fp_;
@@ -3158,8 +3085,6 @@ class LM final : public LMBase {
     uint64_t fp_ = 0;
     SlotTab<HidSlot> hid_;    // hidden-state collectors (fs_lm_session_add_hidden): the table of the step's k_hidden_rows node
     SlotTab<ScoreSlot> sc_;   // scoring slots (fs_lm_session_add_scored): the table of the step's k_score_slots nodes
-    bool sess_score_ = false;  // FS_SESSION_SCORE (the session's step graphs carry the 9 score nodes)
-    bool sess_trace_ = false;  // FS_SESSION_TRACE (... and the traced slots' tail node; the score nodes know the stash)
     std::vector<char> sess_traced_;  // per slot: admitted with fs_lm_session_add_traced (its sc_ entry has no targets)
     DevBuf d_trace_;                 // the traced slots' stash f32 [B][TRACE_STASH_WORDS] (lm_kernels.h), once per handle
     SeqState sess_stage_ = {};

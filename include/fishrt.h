@@ -105,7 +105,7 @@ int fs_selftest_score_rows(int device_id, const float* logits, int S, int n, con
 
 /* Self-test of a LOADED handle, by name.  "persist": the persistent decode kernels of this binary (csrc/lm_persist.hip, lm_persist_slow.hip:
  * pinned weight registers, loads issued outside the compiler's wait-count bookkeeping) against the per-node kernels on the handle's own
- * weights -- 4 greedy frames on the persistent path with the decision capture armed, then one teacher-forced per-node step
+ * weights -- 4 greedy frames on the persistent path with the decision capture armed for the first 2, then one teacher-forced per-node step
  * (fs_lm_forward_generate / _fast) compared with the captured logits of the first k_slow_persist step and the first k_fast_persist pass
  * (bound 2e-2 x max(1, max |logit|): loose for summation order, tight for a wrong weight register).  A deployment runs it once after a
  * toolchain change; 0 = passed, the message names the remedy otherwise.  Clears the handle's KV caches.  No reference counterpart. */

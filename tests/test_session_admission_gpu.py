@@ -2,7 +2,8 @@
 add with an empty prefix: the two must give codes of the same shape, reserve the same pages beyond the prefix's full ones and generate the
 same codes (parting only where the plain slot's own recorded logits hold a near-tie); a refused add (no free slot, KV page pool short)
 returns None and leaves the page pool as it was; a slot whose budget passes max_seq_len stops there, where generate_blocking raises;
-argument errors keep their messages."""
+argument errors keep their messages; and every admission kind (plain, prefixed, own settings, hidden-state, scored, traced) refuses
+without moving anything and admits the same slot whatever was refused before it."""
 import ctypes as C
 import re
 
@@ -181,3 +182,135 @@ def test_argument_errors_keep_their_messages(lm):
             _ffi.check(L.fs_lm_session_add_ex(lm._h, -1, body.ctypes.data_as(U32P), 8, 50, C.byref(sa), None, C.byref(out)))
         assert s.info() == before and out.value == -7
         assert s.add(body, 50) == 0  # nothing above took a slot
+
+
+# ------------------------------------------------------------------------------------------------ every admission kind, one path
+# One request record and one admission function serve all six entry points: a refused add of ANY kind must leave the session exactly as
+# it was (page pool, counters, slot order, what the live slots generate), and an admitted one must not depend on what was refused before it.
+F15, TOK15 = fcfg.FISH_1_5, fcfg.FISH_1_5_TOKENS
+KINDS = ("plain", "prefixed", "sampled", "hidden", "scored", "scored_hidden", "traced", "traced_hidden")
+ON_PREFIX = ("prefixed", "scored_hidden", "traced_hidden")  # the valid add of these kinds is a body on the 37-column prefix
+P37, N_SC = 37, 3  # 37 % 64 != 0: the prefix's partly filled last page is referenced until it has been copied
+TOP_K_TEXT = "FS_SESSION_PER_SLOT: a slot samples greedy (temp == 0) or with temp > 0 and 0 < top_k <= 256 (the in-launch samplers' limit)"
+
+
+@pytest.fixture(scope="module")
+def lm16():
+    h = fishrt.DualARTransformer(F15, TOK15, 0, "bf16", max_batch=16).load_synthetic(SEED)
+    yield h
+    h.close()
+
+
+def _p15(L, seed):
+    p = np.zeros((9, L), np.uint32)
+    p[0] = np.random.RandomState(seed).randint(0, TOK15["im_end_id"], L)
+    return p
+
+
+def _f15(seed):
+    rng = np.random.RandomState(seed)
+    f = np.zeros((9, N_SC), np.uint32)
+    f[0] = TOK15["semantic_start_id"] + rng.randint(0, F15["vocab_size"] - TOK15["semantic_start_id"], N_SC)
+    f[1:] = rng.randint(0, F15["codebook_size"], (8, N_SC))
+    return f
+
+
+def _admit(s, kind, p, prefix=None, P=0, sampling=None, frames=None):
+    """one add of `kind`: max_new_tokens = L + 2 (L counts the prefix), or the N_SC frames of a scoring slot"""
+    hidden = kind.endswith("hidden")
+    if kind.startswith("scored"):
+        return s.add_scored(p, frames, prefix=prefix, collect_hidden=hidden)
+    kw = dict(sampling=dict(temp=0.9, top_p=0.7, top_k=40), seed=77) if kind == "sampled" else {}
+    if sampling is not None:
+        kw["sampling"] = sampling
+    return s.add(p, P + p.shape[1] + 2, prefix=prefix, collect_hidden=hidden, trace=kind.startswith("traced"), **kw)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def _all_kinds(lm, refuse):
+    """the session with (refuse=True) or without the refused adds; everything else -- the live slot, the probe after each refusal, one valid add
+    per kind, the slots that fill the session -- is the same in both -> (codes of the live slot, {kind: what its slot left})"""
+    msl = F15["max_seq_len"]
+    pre, frames = _p15(P37, 1), _f15(2)
+    bad = frames.copy()
+    bad[3, 1] = F15["codebook_size"]
+
+    def refused(s, kind, what, **kw):
+        """one refusal, then: nothing moved, and the lowest free slot is still the next one handed out"""
+        before, low = s.info(), min(set(range(16)) - set(taken))
+        if refuse:
+            with pytest.raises(RuntimeError, match="^" + re.escape(what) + "$"):
+                _admit(s, kind, **kw)
+            assert s.info() == before, (kind, what)
+        probe = s.add(_p15(5, 3), 5 + 2)
+        assert probe == low, (kind, what, probe, low)
+        s.release(probe)
+        assert s.info()["free_pages"] == before["free_pages"], (kind, what)
+
+    with lm.session(temp=0.7, top_p=0.8, top_k=256, seed=3, ignore_eos=True, per_slot=True, score=True, trace=True) as s:
+        pid = s.add_prefix(pre)
+        taken = [s.add(_p15(19, 4), 19 + 2)]
+        assert taken == [0] and s.step(1) == 1  # one generating slot is live
+        for i, kind in enumerate(KINDS):
+            on = kind in ON_PREFIX
+            p = _p15(5 + 2 * i, 10 + i)  # 5 .. 19 columns
+            ok = dict(p=p, prefix=pid if on else None, P=P37 if on else 0, frames=frames)
+            scored = kind.startswith("scored")
+            if kind != "plain":
+                refused(s, kind, "unknown or released prefix id", **dict(ok, prefix=pid + 5))
+            if kind in ("sampled", "hidden", "traced", "traced_hidden"):
+                refused(s, kind, TOP_K_TEXT, **dict(ok, sampling=dict(top_k=300)))
+            L_long = msl + 1 - ok["P"]
+            refused(s, kind, f"L + N - 1 = {msl + N_SC} exceeds max_seq_len (L counts the prefix; a scored sequence is never clipped)" if scored
+                    else "prompt exceeds max_seq_len (dual_ar.rs:623-624)", **dict(ok, p=_p15(L_long, 5)))
+            if scored:
+                refused(s, kind, f"frames[3][1] = {F15['codebook_size']}: a code must be < codebook_size", **dict(ok, frames=bad))
+            taken.append(_admit(s, kind, **ok))
+            assert taken[-1] == 1 + i, (kind, taken)
+        fill = [s.add(_p15(6, 20 + j), 6 + 2) for j in range(16 - len(taken))]
+        assert fill == list(range(len(taken), 16))
+        taken += fill
+        if refuse:  # all slots taken: every kind answers None, and nothing moves
+            for i, kind in enumerate(KINDS):
+                on = kind in ON_PREFIX
+                before = s.info()
+                assert _admit(s, kind, p=_p15(5 + 2 * i, 10 + i), prefix=pid if on else None, P=P37 if on else 0, frames=frames) is None, kind
+                assert s.info() == before, kind
+        for b in fill:
+            s.release(b)
+            taken.remove(b)
+        probe = s.add(_p15(5, 3), 5 + 2)  # the session has free slots again: the lowest one first
+        assert probe == len(taken)
+        s.release(probe)
+        while s.step(8):
+            pass
+        out = {}
+        for i, kind in enumerate(KINDS):
+            b = 1 + i
+            got = dict(codes=s.poll(b)[0])
+            assert s.poll(b, codes=False) == (N_SC if kind.startswith("scored") else 4, True), kind
+            if kind.endswith("hidden"):
+                got["hidden"] = s.poll_hidden(b)
+                assert got["hidden"].shape == (got["codes"].shape[1], F15["dim"]), kind
+            if kind.startswith("scored"):
+                got.update(s.poll_scores(b))
+                assert np.array_equal(got["codes"], frames[1:]) and got["logprob"].shape == (N_SC, 9), kind
+            if kind.startswith("traced"):
+                got.update(s.poll_trace(b))
+                assert np.array_equal(got["tokens"][:, 1:].T, got["codes"]), kind
+            out[kind] = got
+        return s.poll(0)[0], out
+
+
+def test_every_admission_kind_refuses_cleanly_and_admits_the_same(lm16):
+    live_a, kinds_a = _all_kinds(lm16, refuse=True)
+    live_b, kinds_b = _all_kinds(lm16, refuse=False)  # the fresh session: the same adds, nothing refused
+    assert live_a.shape == (8, 4) and np.array_equal(live_a, live_b)
+    for kind in KINDS:
+        assert kinds_a[kind].keys() == kinds_b[kind].keys(), kind
+        for key, a in kinds_a[kind].items():
+            b = kinds_b[kind][key]
+            assert a.shape == b.shape and a.size > 0 and np.array_equal(_bits(a), _bits(b)), (kind, key)

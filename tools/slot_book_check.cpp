@@ -1,6 +1,7 @@
 // Host check of the collector slots' bookkeeping (csrc/fs_slot_book.h): the buffer pool and the per-slot table of both kinds (scoring
-// slots, hidden-state collectors), driven the way the engine drives them (take before the add, put back on a refused add, activate,
-// refresh the counts, drop at release, end of session with adds still pending), with malloc / free standing in for the device allocator.
+// slots, hidden-state collectors), driven the way the engine drives them (take for an add that will be admitted, the first buffer put
+// back when the second take fails, activate, refresh the counts, drop at release, end of session with adds still pending), with malloc /
+// free standing in for the device allocator.
 // Meant to run under the sanitizers:
 //   c++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all tools/slot_book_check.cpp -o slot_book_check && ./slot_book_check
 // Every buffer is written end to end while it is live, so a pool that hands one out twice, frees one that is live, or computes the
@@ -154,10 +155,55 @@ static void scenario(size_t row_bytes, int width) {
     }
 }
 
+// The engine's one admission path takes the buffers of a request that will be admitted, hidden rows first, records second; when the second
+// take fails the first buffer goes back, and nothing is in hand in either book.  A request that needs both and gets both hands each to
+// its book at activation.
+static size_t g_alloc_budget = 0;  // allocations budget_alloc still grants
+static void* budget_alloc(size_t n) { if (!g_alloc_budget) return nullptr; --g_alloc_budget; return book_alloc(n); }
+
+static void admission(size_t hid_row_bytes, size_t sc_row_bytes, int dim, int C1) {
+    {
+        fs::SlotBook<fs::HidSlot> hid(budget_alloc, book_free);
+        fs::SlotBook<fs::ScoreSlot> sc(budget_alloc, book_free);
+        hid.begin(4, hid_row_bytes);
+        sc.begin(4, sc_row_bytes);
+        auto take_both = [&](int n_iter, fs::SlotBuf& h, fs::SlotBuf& s) {  // (step 4 of session_admit)
+            h = hid.take(n_iter);
+            try { s = sc.take(n_iter); } catch (...) { hid.put(h); throw; }
+        };
+        fs::SlotBuf h, s;
+        g_alloc_budget = 1;  // the hidden-row buffer is granted, the record buffer is not
+        bool threw = false;
+        try { take_both(6, h, s); } catch (const std::exception&) { threw = true; }
+        CHECK(threw && hid.in_hand() == 0 && sc.in_hand() == 0 && hid.pooled() == 1 && sc.pooled() == 0 && s.p == nullptr);
+        hid.put(h);  // (put back already: left alone)
+        CHECK(hid.pooled() == 1 && g_live_allocs == 1);
+        g_alloc_budget = 0;  // the first take fails: nothing was taken, nothing to put back
+        threw = false;
+        try { take_both(9, h, s); } catch (const std::exception&) { threw = true; }
+        CHECK(threw && hid.in_hand() == 0 && sc.in_hand() == 0 && hid.pooled() == 1);
+        g_alloc_budget = 1;  // the same request again: the pooled row buffer serves it, the record buffer is new
+        take_both(6, h, s);
+        CHECK(hid.in_hand() == 1 && sc.in_hand() == 1 && hid.pooled() == 0 && g_live_allocs == 2 && g_alloc_budget == 0);
+        hid.admitted(2); sc.admitted(2);
+        touch(hid.activate(2, h), dim, 3u);
+        touch(sc.activate(2, s), C1, 4u);
+        CHECK(hid.in_hand() == 0 && sc.in_hand() == 0 && hid.live() == 1 && sc.live() == 1);
+        // a request admitted but never activated (the session ends with it queued): both buffers are reclaimed by their books
+        g_alloc_budget = 2;
+        take_both(11, h, s);
+        hid.admitted(3); sc.admitted(3);
+        hid.end(); sc.end();
+        CHECK(hid.in_hand() == 0 && sc.in_hand() == 0 && hid.live() == 0 && sc.live() == 0 && hid.pooled() == 2 && sc.pooled() == 2);
+    }
+    CHECK(g_live_allocs == 0);
+}
+
 int main() {
     const int C1 = 9, dim = 24;
     scenario<fs::ScoreSlot>(128 + 4 * C1, C1);
     scenario<fs::HidSlot>(4 * dim, dim);
+    admission(4 * dim, 128 + 4 * C1, dim, C1);
     std::puts("slot_book_check ok");
     return 0;
 }
