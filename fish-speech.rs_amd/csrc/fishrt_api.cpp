@@ -103,6 +103,13 @@ int fs_selftest_score_rows(int device_id, const float* logits, int S, int n, con
     FS_ARG(S >= 1 && n >= 2 && n <= 2048, "bad score test shape (S >= 1; 2 <= n <= 2048)");
     FS_TRY(fs::debug_score_rows(device_id, logits, S, n, targets, exclude0, logprob_out, top_logprob_out, top_out, row_out))
 }
+int fs_selftest_alt_rows(int device_id, const float* logits, int S, int n, int exclude0, int n_alts, uint32_t* alt_index_out, float* alt_logprob_out,
+                         float* entropy_out) {
+    FS_ARG(logits, "null argument");
+    FS_ARG(S >= 1 && n >= 2 && n <= 2048, "bad alternatives test shape (S >= 1; 2 <= n <= 2048)");
+    FS_ARG(n_alts >= 1 && n_alts <= (int)FS_ALTS_MAX, "bad alternatives test shape (1 <= n_alts <= 16)");
+    FS_TRY(fs::debug_alt_rows(device_id, logits, S, n, exclude0, n_alts, alt_index_out, alt_logprob_out, entropy_out))
+}
 
 // ---- replica fan-out over RCCL (fs_comm.h)
 int fs_comm_unique_id(uint8_t id_out[FS_COMM_ID_BYTES]) { FS_ARG(id_out, "null argument"); FS_TRY(fs::Comm::unique_id(id_out)) }
@@ -309,6 +316,11 @@ int fs_lm_session_poll_trace(fs_lm_t* lm, int slot, size_t first_row, uint32_t* 
                              float* eos_logprob, int* n_decisions, size_t cap_rows, size_t* n_rows) {
     FS_ARG(lm, "null argument");
     FS_TRY(lm->impl->session_poll_trace(slot, first_row, tokens, logprob, top_logprob, top, eos_logprob, n_decisions, cap_rows, n_rows))
+}
+int fs_lm_session_poll_alts(fs_lm_t* lm, int slot, size_t first_row, uint32_t* alt_index, float* alt_logprob, float* entropy, size_t cap_rows,
+                            size_t* n_rows, int* n_alts) {
+    FS_ARG(lm, "null argument");
+    FS_TRY(lm->impl->session_poll_alts(slot, first_row, alt_index, alt_logprob, entropy, cap_rows, n_rows, n_alts))
 }
 int fs_lm_session_info(fs_lm_t* lm, int64_t out[8]) { FS_ARG(lm && out, "null argument"); FS_TRY(lm->impl->session_info(out)) }
 int fs_lm_last_stats(fs_lm_t* lm, fs_gen_stats* out) { FS_ARG(lm && out, "null argument"); FS_TRY(*out = lm->impl->last_stats()) }

@@ -17,6 +17,8 @@ namespace fs {
 // maximum, [18..26] the last maximal index (u32 bits), [27] logprob of <|im_end|> at the slow decision (-inf when masked), [28..31] zero.
 // A TRACED slot (fs_lm_session_add_traced) is an entry of this table whose DEVICE copy has targets == null: it samples, its record rows
 // hold the same figures for its own picks, and the rows behind the records ([cap][C + 1] u32, the host entry's `targets`) receive the picks.
+// In a FS_SESSION_ALTS session the buffer goes on behind those rows: alt_index u32 [cap][C + 1][N], alt_logprob f32 [cap][C + 1][N],
+// entropy f32 [cap][C + 1] (score_alts_bytes per row); the kernels derive the three from rec, cap and N, the entry stays as it is.
 struct ScoreSlot {
     const uint32_t* targets;  // [cap][C + 1]
     float* rec;               // [cap][32]
@@ -44,6 +46,11 @@ struct SlotBuf {
 };
 inline float* score_rec(const SlotBuf& b) { return static_cast<float*>(b.p); }
 inline uint32_t* score_targets(const SlotBuf& b) { return reinterpret_cast<uint32_t*>(static_cast<float*>(b.p) + (size_t)b.cap * SCORE_REC_WORDS); }
+// the alternatives of a FS_SESSION_ALTS session (n_alts = N per decision, C1 = C + 1 decisions): bytes per row, and the three blocks of a buffer
+inline size_t score_alts_bytes(int C1, int n_alts) { return (size_t)C1 * (8 * (size_t)n_alts + 4); }
+inline uint32_t* score_alt_index(const ScoreSlot& e, int C1) { return const_cast<uint32_t*>(e.targets) + (size_t)e.cap * C1; }
+inline float* score_alt_logprob(const ScoreSlot& e, int C1, int n_alts) { return reinterpret_cast<float*>(score_alt_index(e, C1) + (size_t)e.cap * C1 * n_alts); }
+inline float* score_alt_entropy(const ScoreSlot& e, int C1, int n_alts) { return score_alt_logprob(e, C1, n_alts) + (size_t)e.cap * C1 * n_alts; }
 
 // what the book needs of an entry type: the entry of a buffer (count 0) and the pointer that identifies the buffer; E{} is the null entry
 template <typename E> struct SlotKind;
@@ -72,9 +79,15 @@ public:
         end();
         for (SlotBuf& b : pool_) free_(b.p);
     }
-    // session_begin: B slots, buffers of row_bytes per row, no slot holds one; buffers a previous session left live go back to the pool
+    // session_begin: B slots, buffers of row_bytes per row, no slot holds one; buffers a previous session left live go back to the pool.
+    // take() matches pooled buffers by their rows alone, so a pool filled under another row size is freed here: a buffer allocated for
+    // shorter rows would be handed out too short (the score book's rows grow in a FS_SESSION_ALTS session)
     void begin(int B, size_t row_bytes) {
         end();
+        if (row_bytes != row_bytes_) {
+            for (SlotBuf& b : pool_) free_(b.p);
+            pool_.clear();
+        }
         B_ = B; row_bytes_ = row_bytes;
         tab_.assign((size_t)B, E{});
         want_.assign((size_t)B, 0);

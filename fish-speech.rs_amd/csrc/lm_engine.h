@@ -71,6 +71,9 @@ class LMBase {
                                      size_t cap_rows, size_t* n_rows) = 0;
     virtual void session_poll_trace(int slot, size_t first_row, uint32_t* tokens, float* logprob, float* top_logprob, uint32_t* top,
                                     float* eos_logprob, int* n_decisions, size_t cap_rows, size_t* n_rows) = 0;
+    // fishrt.h: fs_lm_session_poll_alts
+    virtual void session_poll_alts(int slot, size_t first_row, uint32_t* alt_index, float* alt_logprob, float* entropy, size_t cap_rows,
+                                   size_t* n_rows, int* n_alts) = 0;
     virtual void debug_capture(int n_frames) = 0;
     virtual void debug_read(float* out, int n_frames) = 0;
     virtual void debug_read_row(int row, float* out, int n_frames) = 0;

@@ -937,6 +937,20 @@ class LM final : public LMBase {
             if (!(flags & FS_SESSION_PER_SLOT)) throw Error("FS_SESSION_TRACE is valid only together with FS_SESSION_PER_SLOT | FS_SESSION_SCORE: not alone");
             if (!score) throw Error("FS_SESSION_TRACE is valid only together with FS_SESSION_PER_SLOT | FS_SESSION_SCORE: not without FS_SESSION_SCORE");
         }
+        // FS_SESSION_ALTS: the score nodes of the session are the instantiation that also leaves the N most likely candidates and the entropy
+        // of every decision of a scoring or traced slot (fs_lm_session_poll_alts); N = the FS_SESSION_ALTS_N field of the flags, 0 = 8
+        const uint32_t alts_field = (flags >> 16) & 31u;
+        int alts_n = 0;
+        if (flags & FS_SESSION_ALTS) {
+            if (flags & FS_SESSION_ROWS) throw Error("FS_SESSION_ALTS is valid only together with FS_SESSION_PER_SLOT | FS_SESSION_SCORE: not with FS_SESSION_ROWS");
+            if (!(flags & FS_SESSION_PER_SLOT)) throw Error("FS_SESSION_ALTS is valid only together with FS_SESSION_PER_SLOT | FS_SESSION_SCORE: not alone");
+            if (!score) throw Error("FS_SESSION_ALTS is valid only together with FS_SESSION_PER_SLOT | FS_SESSION_SCORE: not without FS_SESSION_SCORE");
+            if (alts_field > FS_ALTS_MAX)
+                throw Error("FS_SESSION_ALTS_N(" + std::to_string(alts_field) + ") exceeds FS_ALTS_MAX (16): a decision records 1 .. 16 alternatives (0 = the default of 8)");
+            alts_n = alts_field ? (int)alts_field : 8;
+        } else if (alts_field) {
+            throw Error("FS_SESSION_ALTS_N(" + std::to_string(alts_field) + ") without FS_SESSION_ALTS: the field is read only together with the flag");
+        }
         // Fish <= 1.4 handles (no semantic range: the slow token is the 2-way {pad, im_end} draw): only the per-slot samplers define that
         // decision for a slot (k_sample_slow_slots, as the slot's own fs_lm_generate call); the lock-step sampler and the request-row
         // kernels do not
@@ -951,7 +965,7 @@ class LM final : public LMBase {
         // static-batch sampler's.  Needs max_batch <= 8, a bf16 Fish-1.5 handle and a sampler setting the in-launch decisions cover.
         // The mode is built in a local and becomes the handle's with sess_active_, as the last act: a throw leaves the handle as it was.
         SessMode m;
-        m.score = score; m.trace = trace;
+        m.score = score; m.trace = trace; m.alts = alts_n;
         // FS_SESSION_PER_SLOT: the slots stay on the static-batch step, but its 9 sampler nodes are the per-slot ones (k_sample_*_slots):
         // every slot decides like its own generate_blocking call, with its own settings, StdRng stream and repetition-penalty windows
         m.slots = (flags & FS_SESSION_PER_SLOT) != 0;
@@ -1020,7 +1034,9 @@ class LM final : public LMBase {
         sess_queue_.clear(); sess_flight_.clear();
         sess_prefixes_.clear();
         tab_begin(hid_, sizeof(float) * (size_t)a_.dim);
-        tab_begin(sc_, sizeof(float) * SCORE_REC_WORDS + sizeof(uint32_t) * ((size_t)a_.num_codebooks + 1));
+        // (the book frees its pool when the row size differs from the previous session's: FS_SESSION_ALTS rows are longer, by N)
+        tab_begin(sc_, sizeof(float) * SCORE_REC_WORDS + sizeof(uint32_t) * ((size_t)a_.num_codebooks + 1) +
+                           (alts_n ? score_alts_bytes(a_.num_codebooks + 1, alts_n) : 0));
         sess_traced_.assign(B_, 0);
         if (trace) {
             // the traced slots' stash, allocated once per handle (the captured step graphs of trace sessions hold its address); no row is open
@@ -1245,6 +1261,30 @@ class LM final : public LMBase {
         require_live_slot(slot);
         FS_REQUIRE(sc_.book.wanted(slot) && sess_traced_[slot], "the slot is not a traced slot (it was not admitted with fs_lm_session_add_traced)");
         poll_records(slot, first_row, cap_rows, RecordsOut{logprob, top_logprob, top, eos_logprob, tokens, n_decisions}, n_rows);
+    }
+    // the alternatives [first_row, rows so far) of a scoring or traced slot of a FS_SESSION_ALTS session: the three blocks behind the slot's
+    // records and targets / token rows, [n][C + 1][N] / [n][C + 1] as they lie on the device
+    void session_poll_alts(int slot, size_t first_row, uint32_t* alt_index, float* alt_logprob, float* entropy, size_t cap_rows, size_t* n_rows,
+                           int* n_alts) override {
+        use_device();
+        FS_REQUIRE(sess_active_, "no open session");
+        FS_REQUIRE(sess_.alts > 0, "fs_lm_session_poll_alts needs FS_SESSION_ALTS (begin the session with FS_SESSION_PER_SLOT | FS_SESSION_SCORE | FS_SESSION_ALTS)");
+        require_live_slot(slot);
+        FS_REQUIRE(sc_.book.wanted(slot), "the slot is neither a scoring nor a traced slot (it was not admitted with fs_lm_session_add_scored / _add_traced)");
+        const ScoreSlot& e = sc_.book.entry(slot);
+        const size_t n = slot_prefilling(slot) ? 0 : (size_t)e.count;
+        if ((alt_index || alt_logprob || entropy) && first_row < n) {
+            const size_t m = std::min(n - first_row, cap_rows), C1 = (size_t)a_.num_codebooks + 1, N = (size_t)sess_.alts;
+            if (m && alt_index)
+                FS_HIP(hipMemcpyAsync(alt_index, score_alt_index(e, (int)C1) + first_row * C1 * N, sizeof(uint32_t) * m * C1 * N, hipMemcpyDeviceToHost, st_));
+            if (m && alt_logprob)
+                FS_HIP(hipMemcpyAsync(alt_logprob, score_alt_logprob(e, (int)C1, (int)N) + first_row * C1 * N, sizeof(float) * m * C1 * N, hipMemcpyDeviceToHost, st_));
+            if (m && entropy)
+                FS_HIP(hipMemcpyAsync(entropy, score_alt_entropy(e, (int)C1, (int)N) + first_row * C1, sizeof(float) * m * C1, hipMemcpyDeviceToHost, st_));
+            FS_HIP(hipStreamSynchronize(st_));
+        }
+        if (n_rows) *n_rows = n;
+        if (n_alts) *n_alts = sess_.alts;
     }
     void park_slot(int b, bool rows) {
         SeqState ss = {};
@@ -2561,7 +2601,9 @@ class LM final : public LMBase {
         // FS_SESSION_TRACE: the score nodes know the traced slots' stash, and one tail node behind the last sampler closes their rows
         const bool trace = score && sess_.trace;
         float* stash = trace ? d_trace_.as<float>() : nullptr;
-        if (score) launch_score_slots(sc_.dev.as<ScoreSlot>(), state(0), d_scfg_.as<SampleCfg>(), d_lrows_.as<float>(), ld_slow_, n_audio_, 0, C, B, st_, stash);
+        // FS_SESSION_ALTS: the score nodes (and the tail node) are their second instantiation, N a launch argument
+        const int alts = score ? sess_.alts : 0;
+        if (score) launch_score_slots(sc_.dev.as<ScoreSlot>(), state(0), d_scfg_.as<SampleCfg>(), d_lrows_.as<float>(), ld_slow_, n_audio_, 0, C, B, st_, stash, alts);
         if (slots)
             SampleKernels<WT>::sample_slow_slots(d_, d_lrows_.as<float>(), ld_slow_, n_audio_, d_scfg_.as<SampleCfg>(), d_srng_.as<SlotRng>(), B, state(0),
                                                  cs.X, d_xfrows_.as<float>(), st_, prep_g, cs.A, fold ? d_epoch_.as<uint32_t>() : nullptr,
@@ -2605,7 +2647,7 @@ class LM final : public LMBase {
             const float* prep_f = nf.qkv0_tbl ? nullptr : prep_g;
             nf.first_prepped = prep_f != nullptr;
             if (score) launch_score_slots(sc_.dev.as<ScoreSlot>(), state(0), d_scfg_.as<SampleCfg>(), d_lfast_.as<float>(), a_.codebook_size, a_.codebook_size,
-                                          1 + cbi, C, B, st_, stash);
+                                          1 + cbi, C, B, st_, stash, alts);
             if (slots) {
                 RepPenState rp0 = srp_.view(0);
                 SampleKernels<WT>::sample_fast_slots(d_, d_lfast_.as<float>(), cbi, C, a_.codebook_size, d_scfg_.as<SampleCfg>(), d_srng_.as<SlotRng>(), rp0,
@@ -2617,7 +2659,7 @@ class LM final : public LMBase {
                                                 cs.X, d_out_.as<uint32_t>(), out_cap_, st_, words, prep_f, cs.A);
             cf = nf;
         }
-        if (trace) launch_trace_commit(sc_.dev.as<ScoreSlot>(), state(0), d_scfg_.as<SampleCfg>(), stash, n_audio_, a_.codebook_size, C, B, st_);
+        if (trace) launch_trace_commit(sc_.dev.as<ScoreSlot>(), state(0), d_scfg_.as<SampleCfg>(), stash, n_audio_, a_.codebook_size, C, B, st_, alts);
         if (capt) launch_cap_rows_picks(state(0), d_cfg_.as<SampleCfg>(), B, d_rcap_.as<float>(), cap_frames_, C, st_);
     }
     // the capture record of a row-path call: [B][cap_frames][9][2048] (allocated when fs_lm_debug_capture is armed)
@@ -2641,8 +2683,10 @@ class LM final : public LMBase {
         drop_batch_graphs();
     }
     hipGraphExec_t batch_graph(int B) {
-        const int key = (sess_active_ ? 1 << 24 : 0) + (rows_par_ ? 1 << 25 : 0) + (sess_.slots ? 1 << 26 : 0) + (sess_.slots && sess_.wide ? 1 << 27 : 0) +
-                        (sess_.slots && sess_.score ? 1 << 28 : 0) + (sess_.slots && sess_.score && sess_.trace ? 1 << 29 : 0) + B * 1024 + nc_launch_;
+        // (FS_SESSION_ALTS: N is an argument of the captured nodes, so it is part of the key -- bits 32 and up, 0 without the flag)
+        const long long key = (sess_active_ ? 1 << 24 : 0) + (rows_par_ ? 1 << 25 : 0) + (sess_.slots ? 1 << 26 : 0) + (sess_.slots && sess_.wide ? 1 << 27 : 0) +
+                              (sess_.slots && sess_.score ? 1 << 28 : 0) + (sess_.slots && sess_.score && sess_.trace ? 1 << 29 : 0) + B * 1024 + nc_launch_ +
+                              ((long long)(sess_.slots && sess_.score ? sess_.alts : 0) << 32);
         auto it = batch_graphs_.find(key);
         if (it != batch_graphs_.end()) return it->second;
         {   // the co-residency query of the folded step (rows_fold_ok -> occupancy API) is answered once, OUTSIDE stream capture
@@ -3055,6 +3099,7 @@ class LM final : public LMBase {
         bool wide = false;     // FS_SESSION_WIDE_SAMPLER (the per-slot sampler nodes that also take nucleus-only / top_k > 256 settings)
         bool score = false;    // FS_SESSION_SCORE (the session's step graphs carry the 9 score nodes)
         bool trace = false;    // FS_SESSION_TRACE (... and the traced slots' tail node; the score nodes know the stash)
+        int alts = 0;          // FS_SESSION_ALTS: N alternatives per decision (1 .. 16; the score nodes' second instantiation), 0 = off
     } sess_{};
     SampleCfg sess_cfg_ = {};  // the session's own SampleCfg (slots admitted without settings of their own)
     DevBuf d_scfg_, d_srng_;   // per-slot sampler state [max_batch] (k_sample_*_slots)
@@ -3099,7 +3144,7 @@ class LM final : public LMBase {
     bool rows_par_ = false;  // this batch / session samples with the block-parallel row samplers
     int ld_slow_ = 0, down_split_ = 4;
     bool fold_off_ = false;  // set after a reported exchange timeout of the folded decode step: the handle keeps the slab path from then on
-    std::map<int, hipGraphExec_t> batch_graphs_;
+    std::map<long long, hipGraphExec_t> batch_graphs_;
     DevBuf d_rimg_, d_rhimg_, d_redges_s_, d_redges_f_, d_rctl_s_, d_rctl_f_, d_rlogits_, d_rcfg_, d_rrng_, d_rbudget_;  // request rows (lm_persist_rows.hip)
     DevBuf d_rcap_, d_rpairs_, d_rones_;
     void* h_pin_ = nullptr;

@@ -314,13 +314,19 @@ void launch_hidden_rows(HidSlot* tab, const SeqState* states, const float* X, in
 // trace_stash != null (FS_SESSION_TRACE sessions): an entry without targets is a TRACED slot (fishrt.h: fs_lm_session_add_traced) -- the
 // node leaves top_logprob / top / eos_logprob in the record, m, log s and the raw row in the slot's stash, and the row as it is.
 void launch_score_slots(ScoreSlot* tab, const SeqState* states, const SampleCfg* cfgs, float* logits, int ld, int n, int decision, int n_cb, int B,
-                        hipStream_t st, float* trace_stash = nullptr);
+                        hipStream_t st, float* trace_stash = nullptr, int n_alts = 0);
+// n_alts > 0 (FS_SESSION_ALTS sessions, 1 .. 16): the second instantiation of the node -- every scoring and traced slot also leaves, behind
+// its records [cap][32] and targets / token rows [cap][n_cb + 1], the n_alts most likely candidates of the decision by the node's own key
+// (value descending, -0 == +0, the higher index first among equals; padding 0xFFFFFFFF / NaN where there are fewer) and its entropy:
+// alt_index u32 [cap][n_cb + 1][n_alts], alt_logprob f32 [cap][n_cb + 1][n_alts], entropy f32 [cap][n_cb + 1] (fishrt.h:
+// fs_lm_session_poll_alts).  n_alts == 0 launches the node as it always was.  The same holds for launch_trace_commit, which fills the
+// skipped decisions of an <|im_end|> iteration.
 // Traced slots: the per-handle stash f32 [B][TRACE_STASH_WORDS] (per slot a 32-word head + the step's 9 raw rows of <= 2048 candidates),
 // and the ONE node behind the frame's last sampler node that closes the rows opened in this step: the picks out of SeqState::cur, their
 // log-probs from the stash, the token row behind the records, count + 1.  Every other entry exits at once.  n_cb == 8.
 constexpr int TRACE_STASH_WORDS = 32 + 9 * 2048;
 void launch_trace_commit(ScoreSlot* tab, const SeqState* states, const SampleCfg* cfgs, float* trace_stash, int n_slow, int cb_size, int n_cb, int B,
-                         hipStream_t st);
+                         hipStream_t st, int n_alts = 0);
 
 // synthetic tensor fill (fs_synth.h): n_rows x n_cols, destination row = r * row_mul + row_off (W1/W3 interleave)
 template <typename WT>
@@ -347,5 +353,8 @@ void debug_sample_slots(int device, const float* logits, int S, int R, int n, co
 // test hook behind fs_selftest_score_rows: the score node's device function on S caller rows of n candidates, one block per row
 void debug_score_rows(int device, const float* logits, int S, int n, const uint32_t* targets, int exclude0, float* logprob_out,
                       float* top_logprob_out, uint32_t* top_out, float* row_out);
+// test hook behind fs_selftest_alt_rows: the FS_SESSION_ALTS node's device functions on S caller rows of n candidates, one block per row
+void debug_alt_rows(int device, const float* logits, int S, int n, int exclude0, int n_alts, uint32_t* alt_index_out, float* alt_logprob_out,
+                    float* entropy_out);
 
 }  // namespace fs

@@ -1572,10 +1572,14 @@ struct ScoreOut { float logprob, top_logprob, eos_logprob; uint32_t top; };
 // What a scoring and a traced decision share: the row in the thread's registers (lv: the blocked ownership above; entries at or beyond n
 // hold -inf, candidate 0 too when it is left out), its maximum m by the LAST-max key, log(sum exp(x - m)), the maximal index.  m, ls and
 // top are the row's on every thread; x0 (candidate 0 as scored) is thread 0's.
-struct RowStats { float m, ls, x0; uint32_t top; };
+// ALTS (the FS_SESSION_ALTS instantiation of the node): the exp pass also sums exp(x - m) (x - m) over the finite entries, and
+// ent = log(s) - that sum / s is the row's entropy on every thread.  Without ALTS the function is what it was, instruction for instruction.
+struct RowStats { float m, ls, x0; uint32_t top; float ent; };
+template <bool ALTS = false>
 __device__ __forceinline__ RowStats score_row_stats(const float* __restrict__ row, int n, bool exclude0, float (&lv)[8]) {
     __shared__ unsigned long long s_k[SCORE_THREADS / 64];
     __shared__ float s_s[SCORE_THREADS / 64];
+    __shared__ float s_e[ALTS ? SCORE_THREADS / 64 : 1];
     const int tid = threadIdx.x;
     const bool vec = (reinterpret_cast<uintptr_t>(row) & 15u) == 0;
 #pragma unroll
@@ -1611,27 +1615,156 @@ __device__ __forceinline__ RowStats score_row_stats(const float* __restrict__ ro
     mu ^= (mu >> 31) ? 0x80000000u : 0xFFFFFFFFu;
     RowStats r;
     r.m = __uint_as_float(mu);
-    float sum = 0.f;
+    float sum = 0.f, esum = 0.f;
+    if constexpr (ALTS) {
 #pragma unroll
-    for (int s = 0; s < 8; ++s) sum += expf(lv[s] - r.m);  // (owned entries at or beyond n hold -inf: +0)
+        for (int s = 0; s < 8; ++s) {
+            const float dx = lv[s] - r.m, e = expf(dx);
+            sum += e;
+            esum += lv[s] == -INFINITY ? 0.f : e * dx;  // (a -inf entry contributes exactly 0, not 0 * -inf)
+        }
+    } else {
+#pragma unroll
+        for (int s = 0; s < 8; ++s) sum += expf(lv[s] - r.m);  // (owned entries at or beyond n hold -inf: +0)
+    }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    if ((tid & 63) == 0) s_s[tid >> 6] = sum;
+    if constexpr (ALTS) {
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) esum += __shfl_xor(esum, o, 64);
+    }
+    if ((tid & 63) == 0) { s_s[tid >> 6] = sum; if constexpr (ALTS) s_e[tid >> 6] = esum; }
     __syncthreads();
     sum = (s_s[0] + s_s[1]) + (s_s[2] + s_s[3]);
     r.ls = logf(sum);
+    r.ent = 0.f;
+    if constexpr (ALTS) r.ent = r.ls - ((s_e[0] + s_e[1]) + (s_e[2] + s_e[3])) / sum;
     r.x0 = lv[0];
     r.top = (uint32_t)(key & 0xFFFFFFFFull);
     return r;
 }
-__device__ __forceinline__ ScoreOut score_row(float* __restrict__ row, int n, int t, bool exclude0) {
+// ---- the alternatives of a FS_SESSION_ALTS session (fishrt.h: fs_lm_session_poll_alts): the N <= ALTS_MAX largest candidates of the row
+// in lv (score_row_stats' ownership), by the node's own key -- value descending, -0 == +0, the HIGHER index first among equals -- with the
+// node's log-prob expression (x - m) - log s.  ONE barrier on top of score_row_stats' two: each of the 4 waves extracts its own top N
+// with wave-only key reductions, the owner lane dropping the winner from its registers each round, and parks N {key, x} pairs in LDS
+// arrays of its own; then wave 0 holds the 4 N <= 64 pairs one per lane, and a lane whose key has fewer than N larger ones among them
+// stores its pair as the alternative of that rank.  A key of 0 is "no candidate" (entries at or beyond n, candidate 0 when it is left
+// out; no finite or infinite value has the key 0); the ranks behind the last candidate get the padding, 0xFFFFFFFF / NaN.  All 256
+// threads take the same path; n_alts is block-uniform; once per launch.
+constexpr int ALTS_MAX = 16;
+// the maximum of a 64-bit key over the wave, on every lane: an all-VALU butterfly (the DPP controls and lane swaps of
+// lm_persist_rows.hip's pr_wave_max_*: xor 1, xor 2, half mirror, row mirror, then the 16- and 32-lane swaps), both words moved with the
+// same control.  A round of the selection is this reduction and little else, and the LDS crossbar form (__shfl_xor: 12 ds_bpermute
+// round trips per key) measured 1.1 us per round and node.
+template <int CTRL>
+__device__ __forceinline__ unsigned long long key_max_dpp(unsigned long long k) {
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(k >> 32), CTRL, 0xF, 0xF, false);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)k, CTRL, 0xF, 0xF, false);
+    const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+    return o > k ? o : k;
+}
+__device__ __forceinline__ unsigned long long wave_max_key(unsigned long long k) {
+    constexpr int XOR1 = 0xB1, XOR2 = 0x4E, HALF_MIRROR = 0x141, MIRROR = 0x140;
+    k = key_max_dpp<XOR1>(k); k = key_max_dpp<XOR2>(k); k = key_max_dpp<HALF_MIRROR>(k); k = key_max_dpp<MIRROR>(k);
+    {
+        const uint32_t hi = (uint32_t)(k >> 32), lo = (uint32_t)k;
+        const auto rh = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+        const auto rl = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+        const unsigned long long a = ((unsigned long long)rh[0] << 32) | rl[0], b = ((unsigned long long)rh[1] << 32) | rl[1];
+        k = a > b ? a : b;
+    }
+    {
+        const uint32_t hi = (uint32_t)(k >> 32), lo = (uint32_t)k;
+        const auto rh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+        const auto rl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+        const unsigned long long a = ((unsigned long long)rh[0] << 32) | rl[0], b = ((unsigned long long)rh[1] << 32) | rl[1];
+        k = a > b ? a : b;
+    }
+    return k;
+}
+__device__ __forceinline__ void row_alts(const float (&lv)[8], int n, bool exclude0, const RowStats& st, int n_alts, uint32_t* __restrict__ alt_index,
+                                         float* __restrict__ alt_logprob) {
+    __shared__ unsigned long long s_ak[SCORE_THREADS / 64][ALTS_MAX];
+    __shared__ float s_ax[SCORE_THREADS / 64][ALTS_MAX];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned long long k[8];
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+        const int i = (s >> 2) * (SCORE_THREADS * 4) + tid * 4 + (s & 3);
+        uint32_t u = __float_as_uint(lv[s] + 0.f);
+        u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;
+        k[s] = (i < n && !(exclude0 && i == 0)) ? (((unsigned long long)u << 32) | (unsigned long long)(uint32_t)i) : 0ull;
+    }
+    unsigned long long best = 0ull;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) best = k[s] > best ? k[s] : best;
+    for (int r = 0; r < n_alts; ++r) {
+        const unsigned long long win = wave_max_key(best);
+        if (win != 0ull && best == win) {  // the owner lane (keys are distinct: the index is part of them)
+            float x = 0.f;
+            best = 0ull;
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+                if (k[s] == win) { k[s] = 0ull; x = lv[s]; }
+                best = k[s] > best ? k[s] : best;
+            }
+            s_ak[wave][r] = win; s_ax[wave][r] = x;
+        } else if (win == 0ull && lane == 0) {
+            s_ak[wave][r] = 0ull; s_ax[wave][r] = 0.f;
+        }
+    }
+    __syncthreads();
+    if (wave == 0) {
+        const int w = lane >> 4, j = lane & (ALTS_MAX - 1);
+        const unsigned long long key = j < n_alts ? s_ak[w][j] : 0ull;
+        const float x = j < n_alts ? s_ax[w][j] : 0.f;
+        // the rank of the lane's key among the 4 N parked ones = how many are larger (they are distinct): 4 N independent broadcast
+        // reads instead of N more dependent reductions; cnt = the candidates there are (wave-uniform)
+        int rank = 0, cnt = 0;
+        for (int w2 = 0; w2 < SCORE_THREADS / 64; ++w2) {
+#pragma unroll 4
+            for (int j2 = 0; j2 < n_alts; ++j2) {
+                const unsigned long long o = s_ak[w2][j2];
+                rank += o > key ? 1 : 0;
+                cnt += o != 0ull ? 1 : 0;
+            }
+        }
+        if (key != 0ull && rank < n_alts) {
+            alt_index[rank] = (uint32_t)(key & 0xFFFFFFFFull);
+            alt_logprob[rank] = (x - st.m) - st.ls;
+        }
+        if (lane < n_alts && lane >= cnt) {
+            alt_index[lane] = 0xFFFFFFFFu;
+            alt_logprob[lane] = __uint_as_float(0x7FC00000u);
+        }
+    }
+}
+// where the alternatives of a slot's buffer lie: behind the records [cap][32] and the targets / token rows [cap][n_cb + 1] --
+// alt_index u32 [cap][n_cb + 1][N], alt_logprob f32 [cap][n_cb + 1][N], entropy f32 [cap][n_cb + 1] (fs_slot_book.h)
+struct AltsOut { uint32_t* index; float* logprob; float* entropy; };
+__device__ __forceinline__ AltsOut alts_out(float* rec, int cap, int count, int d, int n_cb, int n_alts) {
+    const size_t C1 = (size_t)n_cb + 1, per = (size_t)cap * C1 * (size_t)n_alts, at = (size_t)count * C1 + (size_t)d;
+    uint32_t* base = reinterpret_cast<uint32_t*>(rec + (size_t)cap * 32) + (size_t)cap * C1;
+    AltsOut o;
+    o.index = base + at * n_alts;
+    o.logprob = reinterpret_cast<float*>(base + per) + at * n_alts;
+    o.entropy = reinterpret_cast<float*>(base + 2 * per) + at;
+    return o;
+}
+template <bool ALTS = false>
+__device__ __forceinline__ ScoreOut score_row(float* __restrict__ row, int n, int t, bool exclude0, int n_alts = 0, uint32_t* alt_index = nullptr,
+                                              float* alt_logprob = nullptr, float* entropy = nullptr) {
     const int tid = threadIdx.x;
     // the target's logit, read by thread 0 ahead of the barriers (the store at the end comes behind them); candidate 0's comes out of lv
     const bool t_ok = (unsigned)t < (unsigned)n;
     float xr = 0.f;
     if (tid == 0 && t_ok && t != 0) xr = row[t];
     float lv[8];
-    const RowStats st = score_row_stats(row, n, exclude0, lv);
+    const RowStats st = score_row_stats<ALTS>(row, n, exclude0, lv);
+    if constexpr (ALTS) {  // (from the registers: the row as it was, before +inf goes over the target)
+        row_alts(lv, n, exclude0, st, n_alts, alt_index, alt_logprob);
+        if (tid == 0) *entropy = st.ent;
+    }
     const float xt = !t_ok ? __uint_as_float(0x7FC00000u) : (t == 0 ? st.x0 : xr);
     ScoreOut r;
     r.logprob = (xt - st.m) - st.ls;
@@ -1652,11 +1785,17 @@ __device__ __forceinline__ ScoreOut score_row(float* __restrict__ row, int n, in
 // slot adds no row) -- then the 9 raw rows [9][2048].  The row is NOT modified: the slot's sampler decides on what it always decided on.
 constexpr int TRACE_HEAD_WORDS = 32, TRACE_ROW_WORDS = 2048, TRACE_OPEN = 18;
 static_assert(TRACE_STASH_WORDS == TRACE_HEAD_WORDS + 9 * TRACE_ROW_WORDS, "stash layout");
+template <bool ALTS = false>
 __device__ __forceinline__ void trace_row(float* __restrict__ rec, float* __restrict__ stash, const float* __restrict__ row, int n, int d,
-                                          bool exclude0) {
+                                          bool exclude0, int n_alts = 0, uint32_t* alt_index = nullptr, float* alt_logprob = nullptr,
+                                          float* entropy = nullptr) {
     const int tid = threadIdx.x;
     float lv[8];
-    const RowStats st = score_row_stats(row, n, exclude0, lv);
+    const RowStats st = score_row_stats<ALTS>(row, n, exclude0, lv);
+    if constexpr (ALTS) {  // (neither depends on the pick)
+        row_alts(lv, n, exclude0, st, n_alts, alt_index, alt_logprob);
+        if (tid == 0) *entropy = st.ent;
+    }
     float* dst = stash + TRACE_HEAD_WORDS + (size_t)d * TRACE_ROW_WORDS;  // (16-byte aligned: the stash is, and every offset is a multiple of 4 words)
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
@@ -1680,22 +1819,28 @@ __device__ __forceinline__ void trace_row(float* __restrict__ rec, float* __rest
         }
     }
 }
+// ALTS: the node of FS_SESSION_ALTS sessions -- every scoring and traced slot also leaves the n_alts most likely candidates and the
+// entropy of the decision behind its records (alts_out).  The other instantiation does not read n_alts and is the node it always was.
+template <bool ALTS>
 __global__ __launch_bounds__(SCORE_THREADS) void k_score_slots(ScoreSlot* __restrict__ tab, const SeqState* __restrict__ states,
                                                                const SampleCfg* __restrict__ cfgs, float* __restrict__ logits, int ld, int n,
-                                                               int d, int n_cb, float* __restrict__ stash) {
+                                                               int d, int n_cb, float* __restrict__ stash, int n_alts) {
     const int b = blockIdx.x;
     ScoreSlot* sc = tab + b;
     float* rec = sc->rec;
     const int count = sc->count;
     if (!rec || states[b].done != 0 || count >= sc->cap) return;  // (block-uniform)
     const uint32_t* targets = sc->targets;
+    AltsOut ao = {nullptr, nullptr, nullptr};
+    if constexpr (ALTS) ao = alts_out(rec, sc->cap, count, d, n_cb, n_alts);
     if (!targets) {  // a traced slot (block-uniform; only the tables of FS_SESSION_TRACE sessions hold such entries, and those have a stash)
-        if (stash) trace_row(rec + (size_t)count * 32, stash + (size_t)b * TRACE_STASH_WORDS, logits + (size_t)b * ld, n, d, d == 0 && cfgs[b].ignore_eos != 0);
+        if (stash) trace_row<ALTS>(rec + (size_t)count * 32, stash + (size_t)b * TRACE_STASH_WORDS, logits + (size_t)b * ld, n, d, d == 0 && cfgs[b].ignore_eos != 0,
+                                   n_alts, ao.index, ao.logprob, ao.entropy);
         return;
     }
     const uint32_t tok = targets[(size_t)count * (n_cb + 1) + d];
     const int t = d == 0 ? (int)(tok - cfgs[b].audio_base) : (int)tok;
-    const ScoreOut r = score_row(logits + (size_t)b * ld, n, t, d == 0 && cfgs[b].ignore_eos != 0);
+    const ScoreOut r = score_row<ALTS>(logits + (size_t)b * ld, n, t, d == 0 && cfgs[b].ignore_eos != 0, n_alts, ao.index, ao.logprob, ao.entropy);
     if (threadIdx.x == 0) {
         rec += (size_t)count * 32;
         rec[d] = r.logprob;
@@ -1706,10 +1851,14 @@ __global__ __launch_bounds__(SCORE_THREADS) void k_score_slots(ScoreSlot* __rest
     }
 }
 void launch_score_slots(ScoreSlot* tab, const SeqState* states, const SampleCfg* cfgs, float* logits, int ld, int n, int decision, int n_cb, int B,
-                        hipStream_t st, float* trace_stash) {
+                        hipStream_t st, float* trace_stash, int n_alts) {
     FS_REQUIRE(n >= 2 && n <= SCORE_THREADS * 8 && n <= ld && n_cb == 8 && decision >= 0 && decision <= n_cb,
                "score node: 2 .. 2048 candidates, 8 codebooks (the 32-word record holds 9 decisions)");
-    hipLaunchKernelGGL(k_score_slots, dim3(B), dim3(SCORE_THREADS), 0, st, tab, states, cfgs, logits, ld, n, decision, n_cb, trace_stash);
+    FS_REQUIRE(n_alts >= 0 && n_alts <= ALTS_MAX, "score node: at most 16 alternatives");
+    if (n_alts > 0)
+        hipLaunchKernelGGL(k_score_slots<true>, dim3(B), dim3(SCORE_THREADS), 0, st, tab, states, cfgs, logits, ld, n, decision, n_cb, trace_stash, n_alts);
+    else
+        hipLaunchKernelGGL(k_score_slots<false>, dim3(B), dim3(SCORE_THREADS), 0, st, tab, states, cfgs, logits, ld, n, decision, n_cb, trace_stash, 0);
     FS_LAUNCH_CHECK();
 }
 // The tail node of a traced iteration: block b closes the row its slot's decision-0 node opened in this step.  Thread d <= n_cb takes
@@ -1718,8 +1867,10 @@ void launch_score_slots(ScoreSlot* tab, const SeqState* states, const SampleCfg*
 // expression -- or, for the codebook decisions an <|im_end|> iteration skipped, NaN / NaN / 0xFFFFFFFF / token 0.  The picks go to the
 // slot's token rows u32 [cap][n_cb + 1] behind the records (where a scoring slot keeps its targets).  Then the mark is cleared and the
 // count bumped.  Everything else -- null and scoring entries, no open row -- exits at once.
+// ALTS (FS_SESSION_ALTS sessions): a skipped decision's alternatives and entropy get the same fill -- 0xFFFFFFFF / NaN / NaN.
+template <bool ALTS>
 __global__ __launch_bounds__(64) void k_trace_commit(ScoreSlot* __restrict__ tab, const SeqState* __restrict__ states, const SampleCfg* __restrict__ cfgs,
-                                                    float* __restrict__ stash_all, int n_slow, int cb_size, int n_cb) {
+                                                    float* __restrict__ stash_all, int n_slow, int cb_size, int n_cb, int n_alts) {
     const int b = blockIdx.x, d = threadIdx.x;
     ScoreSlot* sc = tab + b;
     float* rec = sc->rec;
@@ -1743,16 +1894,25 @@ __global__ __launch_bounds__(64) void k_trace_commit(ScoreSlot* __restrict__ tab
             r[d] = nan;
             if (d > 0 && eos) { r[9 + d] = nan; r[18 + d] = __uint_as_float(0xFFFFFFFFu); }
             toks[d] = 0u;
+            if constexpr (ALTS) {
+                if (d > 0 && eos) {
+                    const AltsOut ao = alts_out(rec, cap, count, d, n_cb, n_alts);
+                    for (int j = 0; j < n_alts; ++j) { ao.index[j] = 0xFFFFFFFFu; ao.logprob[j] = nan; }
+                    *ao.entropy = nan;
+                }
+            }
         }
     }
     __syncthreads();  // (every thread has read the count and the mark)
     if (d == 0) { *open = 0u; sc->count = count + 1; }
 }
 void launch_trace_commit(ScoreSlot* tab, const SeqState* states, const SampleCfg* cfgs, float* trace_stash, int n_slow, int cb_size, int n_cb, int B,
-                         hipStream_t st) {
+                         hipStream_t st, int n_alts) {
     FS_REQUIRE(trace_stash && n_cb == 8 && n_slow >= 2 && n_slow <= TRACE_ROW_WORDS && cb_size >= 2 && cb_size <= TRACE_ROW_WORDS,
                "trace node: 8 codebooks, rows of 2 .. 2048 candidates");
-    hipLaunchKernelGGL(k_trace_commit, dim3(B), dim3(64), 0, st, tab, states, cfgs, trace_stash, n_slow, cb_size, n_cb);
+    FS_REQUIRE(n_alts >= 0 && n_alts <= ALTS_MAX, "trace node: at most 16 alternatives");
+    if (n_alts > 0) hipLaunchKernelGGL(k_trace_commit<true>, dim3(B), dim3(64), 0, st, tab, states, cfgs, trace_stash, n_slow, cb_size, n_cb, n_alts);
+    else hipLaunchKernelGGL(k_trace_commit<false>, dim3(B), dim3(64), 0, st, tab, states, cfgs, trace_stash, n_slow, cb_size, n_cb, 0);
     FS_LAUNCH_CHECK();
 }
 // test hook (fs_selftest_score_rows): score_row on caller rows, one block per row
@@ -1783,6 +1943,34 @@ void debug_score_rows(int device, const float* logits, int S, int n, const uint3
     if (top_out) FS_HIP(hipMemcpy(top_out, d_top, sizeof(uint32_t) * S, hipMemcpyDeviceToHost));
     if (row_out) FS_HIP(hipMemcpy(row_out, d_rows, sizeof(float) * nl, hipMemcpyDeviceToHost));
     (void)hipFree(d_rows); (void)hipFree(d_lp); (void)hipFree(d_tlp); (void)hipFree(d_t); (void)hipFree(d_top);
+}
+// test hook (fs_selftest_alt_rows): the ALTS node's device functions on caller rows, one block per row
+__global__ __launch_bounds__(SCORE_THREADS) void k_alt_rows_test(const float* __restrict__ rows, int n, int exclude0, int n_alts,
+                                                                 uint32_t* __restrict__ alt_index, float* __restrict__ alt_logprob,
+                                                                 float* __restrict__ entropy) {
+    const int b = blockIdx.x;
+    float lv[8];
+    const RowStats st = score_row_stats<true>(rows + (size_t)b * n, n, exclude0 != 0, lv);
+    row_alts(lv, n, exclude0 != 0, st, n_alts, alt_index + (size_t)b * n_alts, alt_logprob + (size_t)b * n_alts);
+    if (threadIdx.x == 0) entropy[b] = st.ent;
+}
+void debug_alt_rows(int device, const float* logits, int S, int n, int exclude0, int n_alts, uint32_t* alt_index_out, float* alt_logprob_out,
+                    float* entropy_out) {
+    FS_REQUIRE(S >= 1 && S <= (1 << 16) && n >= 2 && n <= SCORE_THREADS * 8, "bad alternatives test shape (1 <= S <= 65536 rows of 2 <= n <= 2048)");
+    FS_REQUIRE(n_alts >= 1 && n_alts <= ALTS_MAX, "alternatives test: 1 <= n_alts <= 16");
+    FS_HIP(hipSetDevice(device));
+    const size_t nl = (size_t)S * n, na = (size_t)S * n_alts;
+    float *d_rows = nullptr, *d_lp = nullptr, *d_ent = nullptr; uint32_t* d_idx = nullptr;
+    FS_HIP(hipMalloc(&d_rows, sizeof(float) * nl));
+    FS_HIP(hipMalloc(&d_lp, sizeof(float) * na)); FS_HIP(hipMalloc(&d_idx, sizeof(uint32_t) * na)); FS_HIP(hipMalloc(&d_ent, sizeof(float) * S));
+    FS_HIP(hipMemcpy(d_rows, logits, sizeof(float) * nl, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_alt_rows_test, dim3(S), dim3(SCORE_THREADS), 0, nullptr, d_rows, n, exclude0, n_alts, d_idx, d_lp, d_ent);
+    FS_LAUNCH_CHECK();
+    FS_HIP(hipDeviceSynchronize());
+    if (alt_index_out) FS_HIP(hipMemcpy(alt_index_out, d_idx, sizeof(uint32_t) * na, hipMemcpyDeviceToHost));
+    if (alt_logprob_out) FS_HIP(hipMemcpy(alt_logprob_out, d_lp, sizeof(float) * na, hipMemcpyDeviceToHost));
+    if (entropy_out) FS_HIP(hipMemcpy(entropy_out, d_ent, sizeof(float) * S, hipMemcpyDeviceToHost));
+    (void)hipFree(d_rows); (void)hipFree(d_lp); (void)hipFree(d_idx); (void)hipFree(d_ent);
 }
 
 // ---- sampler test hook (fs_selftest_sample_rows): the static-batch slow sampler on caller-provided logits, B rows of n candidates,

@@ -48,6 +48,7 @@ SYMBOLS = ["fs_last_error", "fs_version", "fs_device_count", "fs_lm_create", "fs
            "fs_lm_session_prefix_create", "fs_lm_session_prefix_release", "fs_lm_session_add_prefixed", "fs_lm_session_add_ex", "fs_lm_session_add_hidden", "fs_lm_session_poll_hidden", "fs_lm_session_info",
            "fs_lm_session_add_scored", "fs_lm_session_poll_scores", "fs_selftest_score_rows",
            "fs_lm_session_add_traced", "fs_lm_session_poll_trace",
+           "fs_lm_session_poll_alts", "fs_selftest_alt_rows",
            "fs_lm_weights_fingerprint", "fs_lm_session_prefix_export", "fs_lm_session_prefix_import",
            "fs_codec_create", "fs_codec_destroy", "fs_codec_load_safetensors", "fs_codec_load_synthetic",
            "fs_codec_decode", "fs_codec_encode", "fs_codec_encode_batch", "fs_codec_sample_rate", "fs_codec_set_precision", "fs_codec_precision", "fs_codec_set_range_check", "fs_codec_range_stats", "fs_codec_stream_begin", "fs_codec_stream_decode", "fs_codec_stream_end", "fs_codec_streams_open", "fs_codec_streams_close", "fs_codec_streams_decode", "fs_codec_streams_decode_ragged", "fs_fp8_quantize_rows", "fs_fp8_decode_table", "fs_selftest", "fs_lm_selftest", "fs_selftest_sample_rows", "fs_selftest_sample_slots", "fs_lm_debug_capture", "fs_lm_debug_read"]
@@ -56,6 +57,13 @@ SYMBOLS = ["fs_last_error", "fs_version", "fs_device_count", "fs_lm_create", "fs
 FS_GEN_IGNORE_EOS, FS_SESSION_ROWS, FS_SESSION_PER_SLOT, FS_SESSION_WIDE_SAMPLER = 1, 8, 16, 32
 FS_SESSION_SCORE = 64
 FS_SESSION_TRACE = 128
+FS_SESSION_ALTS = 256
+FS_ALTS_MAX = 16
+
+
+def FS_SESSION_ALTS_N(n):  # the 5-bit N field of the flags (0 = the default of 8)
+    return (int(n) & 0xFFFFFFFF) << 16
+
 
 # argument types of the scoring entry points (the size_t / pointer arguments must not go through ctypes' int default)
 _U32P, _F32P = C.POINTER(C.c_uint32), C.POINTER(C.c_float)
@@ -69,6 +77,11 @@ TRACE_PROTOTYPES = {
     "fs_lm_session_add_traced": [C.c_void_p, C.c_int, _U32P, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_int)],
     "fs_lm_session_poll_trace": [C.c_void_p, C.c_int, C.c_size_t, _U32P, _F32P, _F32P, _U32P, _F32P, C.POINTER(C.c_int), C.c_size_t,
                                  C.POINTER(C.c_size_t)],
+}
+# ... and of the alternatives' entry points (FS_SESSION_ALTS sessions)
+ALTS_PROTOTYPES = {
+    "fs_lm_session_poll_alts": [C.c_void_p, C.c_int, C.c_size_t, _U32P, _F32P, _F32P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)],
+    "fs_selftest_alt_rows": [C.c_int, _F32P, C.c_int, C.c_int, C.c_int, C.c_int, _U32P, _F32P, _F32P],
 }
 
 _lib = None
@@ -90,7 +103,7 @@ def lib():
         L.fs_comm_destroy.argtypes = [C.c_void_p]
         L.fs_lm_destroy.argtypes = [C.c_void_p]
         L.fs_codec_destroy.argtypes = [C.c_void_p]
-        for name, argtypes in {**SCORE_PROTOTYPES, **TRACE_PROTOTYPES}.items():
+        for name, argtypes in {**SCORE_PROTOTYPES, **TRACE_PROTOTYPES, **ALTS_PROTOTYPES}.items():
             getattr(L, name).argtypes = argtypes
         _lib = L
     return _lib

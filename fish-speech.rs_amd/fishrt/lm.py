@@ -263,30 +263,34 @@ class DualARTransformer:
         return int(out.value)
 
     def session(self, temp=0.7, top_p=0.9, top_k=50, seed=42, ignore_eos=False, rows=False, repetition_penalty=1.2, per_slot=False, wide=False,
-                score=False, trace=False):
+                score=False, trace=False, alts=0):
         """continuous batching over this handle's max_batch slots (fishrt.h: fs_lm_session_*): `with lm.session(...) as s:`
         per_slot=True: FS_SESSION_PER_SLOT -- every slot samples like its own generate_blocking call (own settings, seed, repetition penalty).
         wide=True (with per_slot=True): FS_SESSION_WIDE_SAMPLER -- slots may also sample nucleus-only (top_k == 0) or with top_k > 256.
         score=True (with per_slot=True): FS_SESSION_SCORE -- the session also takes scoring slots (Session.add_scored / poll_scores).
         trace=True (with per_slot=True, score=True): FS_SESSION_TRACE -- the session also takes traced slots (Session.add(..., trace=True) /
         poll_trace): generating slots that record the log-probs of the tokens they pick.
+        alts=N (1 .. 16, with per_slot=True, score=True; 0 = off): FS_SESSION_ALTS -- every scoring and traced slot also records the N most
+        likely candidates and the entropy of each decision (Session.poll_alts).
         Fish <= 1.4 token configs (no semantic range) take per_slot=True only; plain and rows sessions raise and say so."""
-        return Session(self, temp, top_p, top_k, seed, ignore_eos, rows, repetition_penalty, per_slot, wide, score, trace)
+        return Session(self, temp, top_p, top_k, seed, ignore_eos, rows, repetition_penalty, per_slot, wide, score, trace, alts)
 
-    def generate_traced(self, prompts, max_new_tokens, samplings=None, seeds=None, collect_hidden=False):
+    def generate_traced(self, prompts, max_new_tokens, samplings=None, seeds=None, collect_hidden=False, top_n=0):
         """Generate behind every prompts[i] (u32 [C+1, L_i]) and return, with the codes, the log-probs the model gave the tokens it picked
         -- one pass, no teacher-forced second one.  max_new_tokens: one int or one per prompt; samplings[i] (dict / SamplingArgs-like) and
         seeds[i]: the request's own settings / StdRng seed, None = the session's (temp 0.7, top_p 0.9, top_k 50, penalty 1.2; seed 42 +
         admission number).  Opens one per-slot trace session (wide when a setting needs it), admits the requests as slots free up and
         returns one dict per prompt: codes u32 [C, n_frames], the arrays of Session.poll_trace (tokens, logprob, top_logprob, top,
         eos_logprob, n_decisions), total = the sum of the log-probs of the decisions made (f64), plus hidden f32 [n, dim] with
-        collect_hidden."""
+        collect_hidden.  top_n > 0 (<= 16): an alts=top_n session, and each dict also holds Session.poll_alts' alt_index, alt_logprob
+        and entropy."""
         n = len(prompts)
         budgets = [int(max_new_tokens)] * n if np.ndim(max_new_tokens) == 0 else [int(m) for m in max_new_tokens]
         samplings = [None] * n if samplings is None else list(samplings)
         seeds = [None] * n if seeds is None else list(seeds)
         if not (len(budgets) == len(samplings) == len(seeds) == n):
             raise ValueError(f"generate_traced: {n} prompts for {len(budgets)} budgets, {len(samplings)} samplings, {len(seeds)} seeds")
+        alts = dict(alts=Session._alts(top_n, "top_n")) if top_n else {}
 
         def is_wide(sp):
             if sp is None:
@@ -295,7 +299,7 @@ class DualARTransformer:
             return float(get("temp", 0.7)) > 0.0 and not 0 < int(get("top_k", 50)) <= 256
 
         out = [None] * n
-        with self.session(per_slot=True, score=True, trace=True, wide=any(is_wide(sp) for sp in samplings)) as s:
+        with self.session(per_slot=True, score=True, trace=True, wide=any(is_wide(sp) for sp in samplings), **alts) as s:
             todo = [(i, s._prompt(p)) for i, p in enumerate(prompts)]  # (every shape is checked first)
             for sp in samplings:
                 if sp is not None:
@@ -319,22 +323,27 @@ class DualARTransformer:
                     r = s.poll_trace(slot)
                     r["codes"] = codes
                     r["total"] = float(np.nansum(r["logprob"], dtype=np.float64))
+                    if alts:
+                        r.update(s.poll_alts(slot))
                     if collect_hidden:
                         r["hidden"] = s.poll_hidden(slot)
                     out[live.pop(slot)] = r
                     s.release(slot)
         return out
 
-    def score(self, prompts, frames, collect_hidden=False):
+    def score(self, prompts, frames, collect_hidden=False, top_n=0):
         """Teacher-forced log-probabilities of given code sequences: sequence i is frames[i] (u32 [C+1, N_i]: row 0 the slow tokens, rows
         1..C the codes) behind prompts[i] (u32 [C+1, L_i]).  Opens a greedy per-slot score session, feeds the sequences through the
         handle's max_batch slots -- admitting the next one as slots free up, so the weights are streamed once per step for all of them --
         and returns one dict per sequence: logprob / top_logprob f32 [N, C+1], top u32 [N, C+1], eos_logprob f32 [N]
-        (Session.poll_scores), total = logprob.sum() (f64), plus hidden f32 [N, dim] with collect_hidden."""
+        (Session.poll_scores), total = logprob.sum() (f64), plus hidden f32 [N, dim] with collect_hidden.  top_n > 0 (<= 16): an
+        alts=top_n session, and each dict also holds Session.poll_alts' alt_index u32 / alt_logprob f32 [N, C+1, top_n] and entropy
+        f32 [N, C+1]."""
         if len(prompts) != len(frames):
             raise ValueError(f"score: {len(prompts)} prompts for {len(frames)} frame arrays")
+        alts = dict(alts=Session._alts(top_n, "top_n")) if top_n else {}
         out = [None] * len(prompts)
-        with self.session(temp=0.0, top_p=1.0, top_k=0, seed=0, repetition_penalty=1.0, per_slot=True, score=True) as s:
+        with self.session(temp=0.0, top_p=1.0, top_k=0, seed=0, repetition_penalty=1.0, per_slot=True, score=True, **alts) as s:
             todo = [(i, s._prompt(p), s._frames(f)) for i, (p, f) in enumerate(zip(prompts, frames))]  # (every shape is checked first)
             live = {}
             while todo or live:
@@ -351,6 +360,8 @@ class DualARTransformer:
                 for slot in [k for k in live if s.poll(k, codes=False)[1]]:
                     r = s.poll_scores(slot)
                     r["total"] = float(r["logprob"].sum(dtype=np.float64))
+                    if alts:
+                        r.update(s.poll_alts(slot))
                     if collect_hidden:
                         r["hidden"] = s.poll_hidden(slot)
                     out[live.pop(slot)] = r
@@ -407,7 +418,7 @@ class Session:
     SAMPLING_KEYS = ("temp", "top_p", "top_k", "repetition_penalty")
 
     def __init__(self, lm, temp, top_p, top_k, seed, ignore_eos, rows=False, repetition_penalty=1.2, per_slot=False, wide=False, score=False,
-                 trace=False):
+                 trace=False, alts=0):
         """rows=True: FS_SESSION_ROWS -- the slots run on the request-row persistent kernels with batch-1 semantics (repetition penalty, own
         sampler stream per slot); max_batch <= 8.
         per_slot=True: FS_SESSION_PER_SLOT -- the slots stay on the static-batch step (any max_batch, bf16 / fp8) and every slot samples like
@@ -418,8 +429,11 @@ class Session:
         score=True: FS_SESSION_SCORE, per_slot sessions only (Fish 1.5 token layout) -- add_scored() admits slots that are forced along a given
         code sequence and record its log-probabilities (poll_scores); generating slots of the session are unaffected
         trace=True: FS_SESSION_TRACE, per_slot + score sessions only -- add(..., trace=True) admits generating slots that leave the score
-        record of the tokens they pick (poll_trace); every other slot of the session is unaffected"""
+        record of the tokens they pick (poll_trace); every other slot of the session is unaffected
+        alts=N (1 .. 16; 0 = off): FS_SESSION_ALTS | FS_SESSION_ALTS_N(N), per_slot + score sessions only -- every scoring and traced slot
+        also records the N most likely candidates and the entropy of each of its decisions (poll_alts); codes and records are unaffected"""
         self.lm, self._open = lm, False
+        alts = self._alts(alts)
         if rows and per_slot:
             raise ValueError("rows and per_slot exclude each other (a row session's slots already sample per slot)")
         if wide and not per_slot:
@@ -429,13 +443,21 @@ class Session:
         if trace and not (per_slot and score):
             raise ValueError("trace=True needs per_slot=True and score=True (FS_SESSION_TRACE is valid only together with "
                              "FS_SESSION_PER_SLOT | FS_SESSION_SCORE)")
+        if alts and rows:
+            raise ValueError("alts needs per_slot=True and score=True (FS_SESSION_ALTS is valid only together with "
+                             "FS_SESSION_PER_SLOT | FS_SESSION_SCORE: not with rows=True)")
+        if alts and not (per_slot and score):
+            raise ValueError("alts needs per_slot=True and score=True (FS_SESSION_ALTS is valid only together with "
+                             "FS_SESSION_PER_SLOT | FS_SESSION_SCORE)")
         self.rows, self.per_slot, self.wide, self.score, self.trace = bool(rows), bool(per_slot), bool(wide), bool(score), bool(trace)
+        self.alts = alts
         self.sampling = dict(temp=float(temp), top_p=float(top_p), top_k=int(top_k), repetition_penalty=float(repetition_penalty))
         s = _ffi.Sampling(float(temp), float(top_p), int(top_k), float(repetition_penalty) if (rows or per_slot) else 1.0)
         flags = (_ffi.FS_GEN_IGNORE_EOS if ignore_eos else 0) | (_ffi.FS_SESSION_ROWS if rows else 0) | (_ffi.FS_SESSION_PER_SLOT if per_slot else 0)
         flags |= _ffi.FS_SESSION_WIDE_SAMPLER if wide else 0
         flags |= _ffi.FS_SESSION_SCORE if score else 0
         flags |= _ffi.FS_SESSION_TRACE if trace else 0
+        flags |= (_ffi.FS_SESSION_ALTS | _ffi.FS_SESSION_ALTS_N(alts)) if alts else 0
         _ffi.check(_ffi.lib().fs_lm_session_begin(lm._h, C.byref(s), C.c_uint64(seed), flags))
         self._open = True
 
@@ -449,6 +471,13 @@ class Session:
         if self._open:
             self._open = False
             _ffi.check(_ffi.lib().fs_lm_session_end(self.lm._h))
+
+    @staticmethod
+    def _alts(n, what="alts"):
+        """the N of an alts session: an integer in 0 .. FS_ALTS_MAX (0 = off)"""
+        if isinstance(n, bool) or int(n) != n or not 0 <= int(n) <= _ffi.FS_ALTS_MAX:
+            raise ValueError(f"{what} must be an integer in 0 .. {_ffi.FS_ALTS_MAX} (alternatives per decision; 0 = off), got {n!r}")
+        return int(n)
 
     def _prompt(self, prompt, what="prompt"):
         p = _u32(prompt)
@@ -644,6 +673,27 @@ class Session:
                                                   nd.ctypes.data_as(C.POINTER(C.c_int)), C.c_size_t(rows), C.byref(n)))
         return dict(tokens=tok[:rows].copy(), logprob=lp[:rows].copy(), top_logprob=tlp[:rows].copy(), top=top[:rows].copy(),
                     eos_logprob=eos[:rows].copy(), n_decisions=nd[:rows].copy())
+
+    def poll_alts(self, slot, first=0):
+        """alternatives [first, iterations so far) of a scoring or traced slot of an alts=N session (fs_lm_session_poll_alts) ->
+        dict(alt_index u32 [n, C+1, N], alt_logprob f32 [n, C+1, N], entropy f32 [n, C+1]): per iteration and decision the N most likely
+        candidates of the raw row, the most likely first (alt_index[..., 0] == top; among equal values the higher index first; padding
+        0xFFFFFFFF / NaN where a decision has fewer than N candidates or was skipped), and the entropy of the decision in nats"""
+        if not self.alts:
+            raise ValueError("poll_alts needs lm.session(per_slot=True, score=True, alts=N)")
+        if int(first) < 0:
+            raise ValueError("first must not be negative")
+        L, C1 = _ffi.lib(), self.lm.cfg["num_codebooks"] + 1
+        n, na = C.c_size_t(0), C.c_int(0)
+        _ffi.check(L.fs_lm_session_poll_alts(self.lm._h, int(slot), C.c_size_t(0), None, None, None, C.c_size_t(0), C.byref(n), C.byref(na)))
+        rows, N = max(0, int(n.value) - int(first)), int(na.value) or self.alts
+        cap = max(1, rows)
+        idx, lp, ent = np.zeros((cap, C1, N), np.uint32), np.zeros((cap, C1, N), np.float32), np.zeros((cap, C1), np.float32)
+        if rows:
+            fp = C.POINTER(C.c_float)
+            _ffi.check(L.fs_lm_session_poll_alts(self.lm._h, int(slot), C.c_size_t(int(first)), idx.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                 lp.ctypes.data_as(fp), ent.ctypes.data_as(fp), C.c_size_t(rows), C.byref(n), C.byref(na)))
+        return dict(alt_index=idx[:rows].copy(), alt_logprob=lp[:rows].copy(), entropy=ent[:rows].copy())
 
     def release(self, slot):
         _ffi.check(_ffi.lib().fs_lm_session_release(self.lm._h, int(slot)))

@@ -102,6 +102,12 @@ int fs_selftest_sample_slots(int device_id, const float* logits, int S, int R, i
  * target).  Output pointers nullable.  Diagnostics / parity tests. */
 int fs_selftest_score_rows(int device_id, const float* logits, int S, int n, const uint32_t* targets, int exclude0, float* logprob_out,
                            float* top_logprob_out, uint32_t* top_out, float* row_out);
+/* The score node of a FS_SESSION_ALTS session (its device functions) on caller-provided logits f32 [S][n] (2 <= n <= 2048), one block per
+ * row, 1 <= n_alts <= 16, exclude0 as above (candidate 0 takes no part).  alt_index_out u32 / alt_logprob_out f32 [S][n_alts],
+ * entropy_out f32 [S]: order, padding and arithmetic as stated at fs_lm_session_poll_alts.  Output pointers nullable.
+ * Diagnostics / parity tests. */
+int fs_selftest_alt_rows(int device_id, const float* logits, int S, int n, int exclude0, int n_alts, uint32_t* alt_index_out,
+                         float* alt_logprob_out, float* entropy_out);
 
 /* Self-test of a LOADED handle, by name.  "persist": the persistent decode kernels of this binary (csrc/lm_persist.hip, lm_persist_slow.hip:
  * pinned weight registers, loads issued outside the compiler's wait-count bookkeeping) against the per-node kernels on the handle's own
@@ -461,6 +467,39 @@ int fs_lm_session_add_traced(fs_lm_t* lm, int prefix_id, const uint32_t* prompt,
  * fs_lm_session_add_traced is an error that says so (and fs_lm_session_poll_scores refuses a traced slot). */
 int fs_lm_session_poll_trace(fs_lm_t* lm, int slot, size_t first_row, uint32_t* tokens, float* logprob, float* top_logprob, uint32_t* top,
                              float* eos_logprob, int* n_decisions, size_t cap_rows, size_t* n_rows);
+/* FS_SESSION_ALTS (a flag of fs_lm_session_begin): valid only together with FS_SESSION_PER_SLOT | FS_SESSION_SCORE, with or without
+ * FS_SESSION_WIDE_SAMPLER and FS_SESSION_TRACE (alone, with FS_SESSION_ROWS, without FS_SESSION_SCORE, or on a Fish <= 1.4 handle
+ * fs_lm_session_begin fails and says which).  Every scoring and every traced slot of such a session additionally records, per iteration
+ * and decision d (0 = the slow token, 1 + c = codebook c), the N most likely candidates with their log-probs and the entropy of the
+ * decision -- OpenAI's top_logprobs, what a distillation consumes, and a confidence figure -- without the host copy of whole rows that
+ * fs_lm_debug_capture makes.  N = FS_SESSION_ALTS_N(n), a 5-bit field of the flags: 1 .. FS_ALTS_MAX, 0 = the default of 8; a value
+ * above 16, or a non-zero field without FS_SESSION_ALTS, is an error that names it.
+ * The score nodes of the session are a second instantiation of k_score_slots (same launch shape, one more barrier, N a launch argument);
+ * sessions begun without the flag replay exactly the graphs they did before, and plain, collecting, scoring and traced slots of an
+ * FS_SESSION_ALTS session produce bit for bit the codes and records they produce without it.
+ *   Candidates: those of the existing record -- under FS_GEN_IGNORE_EOS candidate 0 of the slow decision takes no part and never appears --
+ *     from the RAW row: no temperature, no repetition penalty, no top-k / top-p.
+ *   Order: the score node's own 64-bit key -- value descending, -0 == +0, among equal values the HIGHER index first -- so
+ *     alt_index[d][0] == top[d] and alt_logprob[d][0] == top_logprob[d].  Slow-decision indices are candidate indices, as `top` is
+ *     (0 = <|im_end|>).
+ *   alt_logprob = (x - m) - log(s) in f32, the very expression of logprob[d]: bit-identical to it whenever the forced or picked token is
+ *     among the alternatives (within 2e-4 of the exact log-softmax, as there).  Candidates holding -inf rank last, with log-prob -inf.
+ *     With fewer than N candidates the tail is padded: index 0xFFFFFFFF, log-prob NaN.
+ *   entropy[d] = log(s) - (sum_i exp(x_i - m) (x_i - m)) / s in f32 over the candidates with finite x_i (a -inf entry contributes exactly
+ *     0): within 2.5e-3 absolute of the exact entropy of the row (two f32 sums of <= 2048 same-signed terms, a ratio of at most log 2048).
+ *   On the <|im_end|> iteration of a traced slot the skipped codebook decisions hold index 0xFFFFFFFF, log-prob NaN and entropy NaN.
+ *   A traced slot's alternatives and entropies are, field for field and bit for bit, those of fs_lm_session_add_scored fed the same tokens
+ *     (a scoring slot's are taken before +inf goes over the target).
+ * Device memory: 9 (8 N + 4) more bytes per iteration of a scoring or traced slot, behind its records in the same buffer (the per-handle
+ * pool is emptied when a session's row size differs from the previous one's). */
+#define FS_SESSION_ALTS 256u
+#define FS_SESSION_ALTS_N(n) ((uint32_t)(n) << 16)
+#define FS_ALTS_MAX 16u
+/* rows [first_row, ...) so far of a scoring or a traced slot: alt_index u32 / alt_logprob f32 [cap_rows][C+1][N], entropy f32
+ * [cap_rows][C+1]; every output pointer nullable; *n_rows = rows the slot has (the rule of fs_lm_session_poll_scores / _poll_trace),
+ * *n_alts = the session's N.  A slot that is neither, or a session without the flag ("needs FS_SESSION_ALTS"), is an error. */
+int fs_lm_session_poll_alts(fs_lm_t* lm, int slot, size_t first_row, uint32_t* alt_index, float* alt_logprob, float* entropy, size_t cap_rows,
+                            size_t* n_rows, int* n_alts);
 /* out[8] = {free pages, pages referenced by more than one owner, live prefixes, prefill passes, tokens prefilled,
  *           prefix tokens reused, tail pages copied, prefill-stream microseconds (HIP events around each pass)};
  * counters since fs_lm_session_begin */

@@ -199,8 +199,62 @@ static void admission(size_t hid_row_bytes, size_t sc_row_bytes, int dim, int C1
     CHECK(g_live_allocs == 0);
 }
 
+// A handle's sessions need not agree on the row size: the score book's rows are longer in a FS_SESSION_ALTS session, by its N.  take()
+// matches pooled buffers by their rows alone, so a buffer pooled under shorter rows must not serve a session with longer ones: begin()
+// frees the pool when the row size changes (and keeps it when it does not).  The alternatives' blocks are written end to end behind the
+// targets, so a buffer handed out too short is a sanitizer report.
+static size_t g_last_alloc = 0;
+static void* sized_alloc(size_t n) { g_last_alloc = n; return book_alloc(n); }
+static void touch_alts(const fs::ScoreSlot& e, int C1, int n_alts) {
+    touch(e, C1, 5u);
+    uint32_t* idx = fs::score_alt_index(e, C1);
+    float *lp = fs::score_alt_logprob(e, C1, n_alts), *ent = fs::score_alt_entropy(e, C1, n_alts);
+    CHECK((const char*)idx == (const char*)e.rec + (size_t)e.cap * (128 + 4 * C1));
+    for (int i = 0; i < e.cap * C1 * n_alts; ++i) { idx[i] = (uint32_t)i; lp[i] = -1.f; }
+    for (int i = 0; i < e.cap * C1; ++i) ent[i] = 2.f;
+    for (int i = 0; i < e.cap * C1 * n_alts; ++i) CHECK(idx[i] == (uint32_t)i);  // (the three blocks do not overlap)
+    CHECK((const char*)(ent + (size_t)e.cap * C1) == (const char*)e.rec + (size_t)e.cap * (128 + 4 * C1 + fs::score_alts_bytes(C1, n_alts)));
+}
+static void row_size_change(int C1) {
+    {
+        fs::SlotBook<fs::ScoreSlot> book(sized_alloc, book_free);
+        const size_t a = 128 + 4 * C1, b8 = a + fs::score_alts_bytes(C1, 8), b16 = a + fs::score_alts_bytes(C1, 16);
+        CHECK(b8 == a + 9 * (8 * 8 + 4) && b16 > b8);
+        book.begin(4, a);
+        fs::SlotBuf s = book.take(12);
+        CHECK(g_last_alloc == a * 12);
+        book.put(s);
+        CHECK(book.pooled() == 1 && g_live_allocs == 1);
+        book.begin(4, a);  // (the same row size: the pool is kept, and serves the take)
+        fs::SlotBuf s2 = book.take(12);
+        CHECK(book.pooled() == 0 && s2.p == s.p && g_live_allocs == 1);
+        book.put(s2);
+        book.begin(4, b8);  // (longer rows: the pooled buffer is freed, the take is a fresh allocation of b8 * cap bytes)
+        CHECK(book.pooled() == 0 && g_live_allocs == 0 && book.row_bytes() == b8);
+        g_last_alloc = 0;
+        fs::SlotBuf l = book.take(12);
+        CHECK(l.p && l.cap == 12 && g_last_alloc == b8 * 12 && g_live_allocs == 1);
+        book.admitted(0);
+        touch_alts(book.activate(0, l), C1, 8);
+        // the session ends with the slot live; another N, then a session without the flag: each starts with an empty pool
+        book.begin(4, b16);
+        CHECK(book.pooled() == 0 && g_live_allocs == 0);
+        g_last_alloc = 0;
+        fs::SlotBuf m = book.take(5);
+        CHECK(g_last_alloc == b16 * 5);
+        book.admitted(1);
+        touch_alts(book.activate(1, m), C1, 16);
+        book.begin(4, a);
+        CHECK(book.pooled() == 0 && g_live_allocs == 0);
+        touch(book.activate(2, book.take(5)), C1, 6u);
+        CHECK(g_last_alloc == a * 5);
+    }
+    CHECK(g_live_allocs == 0);
+}
+
 int main() {
     const int C1 = 9, dim = 24;
+    row_size_change(C1);
     scenario<fs::ScoreSlot>(128 + 4 * C1, C1);
     scenario<fs::HidSlot>(4 * dim, dim);
     admission(4 * dim, 128 + 4 * C1, dim, C1);
