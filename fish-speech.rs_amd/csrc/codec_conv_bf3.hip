@@ -31,6 +31,14 @@
 #include "codec_kernels.h"
 #include "fs_common.h"
 
+// Launch diagnostics (codec_variant_note, codec_kernels.h): <twin>/<mode>/<family>/<shape>
+#ifdef FS_C3_CHECK
+#define FS_VPFX "chk/"
+#else
+#define FS_VPFX ""
+#endif
+#define FS_VN(s) codec_variant_note(F16 ? FS_VPFX "f16/" s : FS_VPFX "bf3/" s)
+
 namespace fs {
 
 // Range-checked twin (f16 precision mode only): this file is compiled a second time with -DFS_C3_CHECK into namespace
@@ -871,10 +879,10 @@ static void conv1d_bf3_impl(const float* x, const uint16_t* xp, int B, int Cin, 
                 hipLaunchKernelGGL(kern, dim3((T + TT - 1) / TT, (Cout + OT - 1) / OT, B), dim3(256), smem, st, xp, Cin, T, wp, Cp, bias, Cout, K, dil,
                                    epi, res, gamma, y, yp, post_silu ? 1 : 0, ps, pc);
             };
-            if (epi == CODEC_EPI_GELU) go(k_conv1d_bf3p<F16, OT, TT, 1, CODEC_EPI_GELU, true, NIBS>);
-            else if (epi == CODEC_EPI_GAMMA_RES) go(k_conv1d_bf3p<F16, OT, TT, 1, CODEC_EPI_GAMMA_RES, true, NIBS>);
-            else if (ps1) go(k_conv1d_bf3p<F16, OT, TT, 1, CODEC_EPI_NONE, true, NIBS>);
-            else go(k_conv1d_bf3p<F16, OT, TT, 1, CODEC_EPI_NONE, false, NIBS>);
+            if (epi == CODEC_EPI_GELU) { FS_VN("bf3p/pw8/GELU"); go(k_conv1d_bf3p<F16, OT, TT, 1, CODEC_EPI_GELU, true, NIBS>); }
+            else if (epi == CODEC_EPI_GAMMA_RES) { FS_VN("bf3p/pw8/GAMMA_RES"); go(k_conv1d_bf3p<F16, OT, TT, 1, CODEC_EPI_GAMMA_RES, true, NIBS>); }
+            else if (ps1) { FS_VN("bf3p/pw8/NONE/ps1"); go(k_conv1d_bf3p<F16, OT, TT, 1, CODEC_EPI_NONE, true, NIBS>); }
+            else { FS_VN("bf3p/pw8/NONE/psN"); go(k_conv1d_bf3p<F16, OT, TT, 1, CODEC_EPI_NONE, false, NIBS>); }
             FS_HIP(hipGetLastError());
             return;
         }
@@ -893,9 +901,9 @@ static void conv1d_bf3_impl(const float* x, const uint16_t* xp, int B, int Cin, 
             };
 #define FS_THIN2(KK, NIB)                                                                        \
     do {                                                                                         \
-        if (resid) go(k_conv1d_bf3t<F16, KK, NIB, NT, CODEC_EPI_RES, true>);                     \
-        else if (ps1) go(k_conv1d_bf3t<F16, KK, NIB, NT, CODEC_EPI_NONE, true>);                 \
-        else go(k_conv1d_bf3t<F16, KK, NIB, NT, CODEC_EPI_NONE, false>);                         \
+        if (resid) { FS_VN("bf3t/K" #KK "/nib" #NIB "/RES"); go(k_conv1d_bf3t<F16, KK, NIB, NT, CODEC_EPI_RES, true>); }              \
+        else if (ps1) { FS_VN("bf3t/K" #KK "/nib" #NIB "/NONE/ps1"); go(k_conv1d_bf3t<F16, KK, NIB, NT, CODEC_EPI_NONE, true>); }     \
+        else { FS_VN("bf3t/K" #KK "/nib" #NIB "/NONE/psN"); go(k_conv1d_bf3t<F16, KK, NIB, NT, CODEC_EPI_NONE, false>); }             \
     } while (0)
 #define FS_THIN(KK)                            \
     do {                                       \
@@ -925,9 +933,9 @@ static void conv1d_bf3_impl(const float* x, const uint16_t* xp, int B, int Cin, 
             const int TT = cfg ? atoi(cfg) : (b256 >= 1024 ? 256 : 128);
 #define FS_WIDE(TTv)                                                                             \
     do {                                                                                         \
-        if (resid) go(k_conv1d_bf3p<F16, 32, TTv, 13, CODEC_EPI_RES, true>, 32, TTv);            \
-        else if (ps1) go(k_conv1d_bf3p<F16, 32, TTv, 13, CODEC_EPI_NONE, true>, 32, TTv);        \
-        else go(k_conv1d_bf3p<F16, 32, TTv, 13, CODEC_EPI_NONE, false>, 32, TTv);                \
+        if (resid) { FS_VN("bf3p/TT" #TTv "/nibs1/RES"); go(k_conv1d_bf3p<F16, 32, TTv, 13, CODEC_EPI_RES, true>, 32, TTv); }            \
+        else if (ps1) { FS_VN("bf3p/TT" #TTv "/nibs1/NONE/ps1"); go(k_conv1d_bf3p<F16, 32, TTv, 13, CODEC_EPI_NONE, true>, 32, TTv); }   \
+        else { FS_VN("bf3p/TT" #TTv "/nibs1/NONE/psN"); go(k_conv1d_bf3p<F16, 32, TTv, 13, CODEC_EPI_NONE, false>, 32, TTv); }           \
     } while (0)
             // channel blocks per stage (same summation order: blocks ascending, taps ascending): more matrix work between two barriers
             // f16 mode (half the LDS per channel block): 2 blocks per stage, still 3 thread blocks per CU -- 2.555 -> 2.470 ms per 256 frames,
@@ -941,9 +949,9 @@ static void conv1d_bf3_impl(const float* x, const uint16_t* xp, int B, int Cin, 
             const int nibs = (F16 && want > 0 && nib % want == 0) ? want : 1;
 #define FS_WIDEN(TTv, NB)                                                                                \
     do {                                                                                                 \
-        if (resid) go(k_conv1d_bf3p<F16, 32, TTv, 13, CODEC_EPI_RES, true, NB>, 32, TTv, NB);            \
-        else if (ps1) go(k_conv1d_bf3p<F16, 32, TTv, 13, CODEC_EPI_NONE, true, NB>, 32, TTv, NB);        \
-        else go(k_conv1d_bf3p<F16, 32, TTv, 13, CODEC_EPI_NONE, false, NB>, 32, TTv, NB);                \
+        if (resid) { FS_VN("bf3p/TT" #TTv "/nibs" #NB "/RES"); go(k_conv1d_bf3p<F16, 32, TTv, 13, CODEC_EPI_RES, true, NB>, 32, TTv, NB); }            \
+        else if (ps1) { FS_VN("bf3p/TT" #TTv "/nibs" #NB "/NONE/ps1"); go(k_conv1d_bf3p<F16, 32, TTv, 13, CODEC_EPI_NONE, true, NB>, 32, TTv, NB); }   \
+        else { FS_VN("bf3p/TT" #TTv "/nibs" #NB "/NONE/psN"); go(k_conv1d_bf3p<F16, 32, TTv, 13, CODEC_EPI_NONE, false, NB>, 32, TTv, NB); }           \
     } while (0)
             if constexpr (F16) {
                 if (nibs == 2) { if (TT == 256) FS_WIDEN(256, 2); else FS_WIDEN(128, 2); FS_HIP(hipGetLastError()); return; }
@@ -957,31 +965,32 @@ static void conv1d_bf3_impl(const float* x, const uint16_t* xp, int B, int Cin, 
         FS_HIP(hipGetLastError());
         return;
     }
-    auto go = [&](auto kern, int OT, int TT, int NIBS, bool loop_tiles) {
+    auto go = [&](auto kern, int OT, int TT, int NIBS, bool loop_tiles, const char* name) {
         const int XS = TT + halo;
         const size_t smem = 16 * ((size_t)NIBS * NPL * XS + (size_t)NIBS * K * NPL * OT);
         raise_lds((const void*)kern, smem);
         const int ntiles = (T + TT - 1) / TT, ytiles = (Cout + OT - 1) / OT;
         int gx = ntiles;
         if (loop_tiles) gx = std::max(1, std::min(ntiles, 1024 / std::max(1, ytiles * B)));  // weights stay in LDS over a loop of time tiles
+        codec_variant_note(name);
         hipLaunchKernelGGL(kern, dim3(gx, ytiles, B), dim3(256), smem, st, x, Cin, T, wp, Cp, bias, Cout, K, dil, pre_silu ? 1 : 0, epi, res,
                            gamma, y, yp, post_silu ? 1 : 0, ps, ntiles, pc);
     };
     if (K == 1 && Cin >= 128) {
         // pointwise convs of the ConvNeXt blocks (frame-rate T, 512..2048 channels): 8 channel blocks per barrier pair
-        go(k_conv1d_bf3<F16, 32, 128, 8, 1, 1>, 32, 128, 8, false);
+        go(k_conv1d_bf3<F16, 32, 128, 8, 1, 1>, 32, 128, 8, false, F16 ? FS_VPFX "f16/bf3x/pw8" : FS_VPFX "bf3/bf3x/pw8");
     } else if (nib <= 2) {
         // thin layers: the whole weight set is resident, the block walks over time tiles
-        if (nib == 1) go(k_conv1d_bf3<F16, 32, 256, 1, 13, 2>, 32, 256, 1, true);
-        else go(k_conv1d_bf3<F16, 32, 128, 2, 13, 2>, 32, 128, 2, true);
+        if (nib == 1) go(k_conv1d_bf3<F16, 32, 256, 1, 13, 2>, 32, 256, 1, true, F16 ? FS_VPFX "f16/bf3x/resident/nib1" : FS_VPFX "bf3/bf3x/resident/nib1");
+        else go(k_conv1d_bf3<F16, 32, 128, 2, 13, 2>, 32, 128, 2, true, F16 ? FS_VPFX "f16/bf3x/resident/nib2" : FS_VPFX "bf3/bf3x/resident/nib2");
     } else {
         const bool tall = Cout >= 64 && (long long)((T + 127) / 128) * ((Cout + 63) / 64) * B >= 256;
         const int OT = tall ? 64 : 32;
         const bool wide = (long long)((T + 255) / 256) * ((Cout + OT - 1) / OT) * B >= 512;
-        if (OT == 64 && wide) go(k_conv1d_bf3<F16, 64, 256, 1, 13, 2>, 64, 256, 1, false);
-        else if (OT == 64) go(k_conv1d_bf3<F16, 64, 128, 1, 13, 2>, 64, 128, 1, false);
-        else if (wide) go(k_conv1d_bf3<F16, 32, 256, 1, 13, 2>, 32, 256, 1, false);
-        else go(k_conv1d_bf3<F16, 32, 128, 1, 13, 2>, 32, 128, 1, false);
+        if (OT == 64 && wide) go(k_conv1d_bf3<F16, 64, 256, 1, 13, 2>, 64, 256, 1, false, F16 ? FS_VPFX "f16/bf3x/OT64/TT256" : FS_VPFX "bf3/bf3x/OT64/TT256");
+        else if (OT == 64) go(k_conv1d_bf3<F16, 64, 128, 1, 13, 2>, 64, 128, 1, false, F16 ? FS_VPFX "f16/bf3x/OT64/TT128" : FS_VPFX "bf3/bf3x/OT64/TT128");
+        else if (wide) go(k_conv1d_bf3<F16, 32, 256, 1, 13, 2>, 32, 256, 1, false, F16 ? FS_VPFX "f16/bf3x/OT32/TT256" : FS_VPFX "bf3/bf3x/OT32/TT256");
+        else go(k_conv1d_bf3<F16, 32, 128, 1, 13, 2>, 32, 128, 1, false, F16 ? FS_VPFX "f16/bf3x/OT32/TT128" : FS_VPFX "bf3/bf3x/OT32/TT128");
     }
     FS_HIP(hipGetLastError());
 }
@@ -1017,7 +1026,7 @@ void codec_respair_f16(const uint16_t* xp, int B, int C, int T, const uint16_t* 
     const int Cp = 64, halo = (K - 1) * dil, nib = C / 16;
     constexpr int NTO = 4;
     const int nwt = (T + 32 * NTO - 1) / (32 * NTO);
-    auto go = [&](auto kern, int NW, int NH) {
+    auto go = [&](auto kern, int NW, int NH, const char* name) {
         const size_t smem = 16 * ((size_t)2 * nib * K * 2 * 32 + (size_t)NW * 2 * nib * (NTO + NH) * 32);
         FS_REQUIRE(smem <= 160 * 1024, "fused ResBlock pair does not fit LDS");
         if (smem > 64 * 1024) {
@@ -1026,15 +1035,17 @@ void codec_respair_f16(const uint16_t* xp, int B, int C, int T, const uint16_t* 
         }
         const int per_cu = std::max(1, (int)((150 * 1024) / smem));
         const int gx = std::max(1, std::min((nwt + NW - 1) / NW, 256 * per_cu / std::max(1, B)));
+        codec_variant_note(name);
         hipLaunchKernelGGL(kern, dim3(gx, 1, B), dim3(NW * 64), smem, st, xp, T, w1p, w2p, Cp, b1, b2, dil, res, y, yp, nwt, pc, mid_ctx_in, mid_ctx_out);
     };
+#define FS_PAIRN(KK, NIBv, NWv, tail) FS_VPFX "f16/pair/K" #KK "/nib" #NIBv "/NW" #NWv tail
 #define FS_PAIR(KK, NIBv, NWv)                                                    \
     do {                                                                          \
         if (rl.len) {                                                             \
-            if (halo <= 32) go(k_respair_f16t<KK, NIBv, NTO, 1, NWv, true>, NWv, 1); \
-            else go(k_respair_f16t<KK, NIBv, NTO, 2, NWv, true>, NWv, 2);         \
-        } else if (halo <= 32) go(k_respair_f16t<KK, NIBv, NTO, 1, NWv>, NWv, 1); \
-        else go(k_respair_f16t<KK, NIBv, NTO, 2, NWv>, NWv, 2);                   \
+            if (halo <= 32) go(k_respair_f16t<KK, NIBv, NTO, 1, NWv, true>, NWv, 1, FS_PAIRN(KK, NIBv, NWv, "/NH1/ragged")); \
+            else go(k_respair_f16t<KK, NIBv, NTO, 2, NWv, true>, NWv, 2, FS_PAIRN(KK, NIBv, NWv, "/NH2/ragged"));            \
+        } else if (halo <= 32) go(k_respair_f16t<KK, NIBv, NTO, 1, NWv>, NWv, 1, FS_PAIRN(KK, NIBv, NWv, "/NH1"));           \
+        else go(k_respair_f16t<KK, NIBv, NTO, 2, NWv>, NWv, 2, FS_PAIRN(KK, NIBv, NWv, "/NH2"));                             \
     } while (0)
     // waves per block (the two weight sets are shared by a block's waves; every wave owns 2 nib x 6 KB of scratch): tuning knobs
     static const int nw1 = getenv("FISHRT_PAIR_NW1") ? atoi(getenv("FISHRT_PAIR_NW1")) : 4, nw2 = getenv("FISHRT_PAIR_NW2") ? atoi(getenv("FISHRT_PAIR_NW2")) : 8;
@@ -1043,6 +1054,7 @@ void codec_respair_f16(const uint16_t* xp, int B, int C, int T, const uint16_t* 
     else { if (nw2 == 4) FS_PAIRK(2, 4); else FS_PAIRK(2, 8); }
 #undef FS_PAIRK
 #undef FS_PAIR
+#undef FS_PAIRN
     FS_HIP(hipGetLastError());
 }
 

@@ -33,3 +33,13 @@ class CodecBase {
 CodecBase* make_codec(int device, int channel_div);
 
 }  // namespace fs
+
+struct fs_conv_case;  // include/fishrt.h
+
+namespace fs {
+
+// fs_selftest_conv1d: one conv through re-layout, pack, plane producers and one launcher of codec_kernels.h (see include/fishrt.h)
+void codec_conv_selftest(int device, const fs_conv_case& c, float* y_out, float* planes_out, char* variant_out, size_t variant_cap,
+                         uint64_t* range_out);
+
+}  // namespace fs

@@ -6,12 +6,14 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <map>
 #include <mutex>
 #include <string>
 #include <vector>
 
+#include "../../include/fishrt.h"
 #include "codec_kernels.h"
 #include "fs_common.h"
 #include "fs_synth.h"
@@ -830,5 +832,150 @@ class Codec final : public CodecBase {
 };
 
 CodecBase* make_codec(int device, int channel_div) { return new Codec(device, channel_div); }
+
+// fs_selftest_conv1d (include/fishrt.h): one conv through the load-time functions (re-layout, pack), the plane producers and ONE launcher of
+// codec_kernels.h, on host data.  Plane buffers are sized as decode_impl sizes them (256 KB of slack for window reads past T) and filled with
+// 0xFF first, so a consumer that let a slot behind T -- or an unwritten pad slot -- reach a stored sample returns NaN.
+void codec_conv_selftest(int device, const fs_conv_case& c, float* y_out, float* planes_out, char* variant_out, size_t variant_cap,
+                         uint64_t* range_out) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw Error("no HIP device visible: libfishrt has no CPU fallback (MI355X / gfx950 required)");
+    FS_REQUIRE(device >= 0 && device < ndev, "device_id out of range");
+    FS_HIP(hipSetDevice(device));
+    const int B = c.B, Cin = c.Cin, Cout = c.Cout, T = c.T, K = c.K, dil = c.dil;
+    const bool tconv = c.flow == FS_CONV_TCONV1D || c.flow == FS_CONV_TCONV1D_PLANES, pair = c.flow == FS_CONV_RESPAIR_F16;
+    const bool planes_flow = c.flow == FS_CONV_CONV1D_PLANES || c.flow == FS_CONV_TCONV1D_PLANES || pair;
+    const int stride = tconv ? c.stride : 1;
+    FS_REQUIRE(c.flow >= FS_CONV_CONV1D && c.flow <= FS_CONV_RESPAIR_F16, "conv self-test: unknown flow");
+    FS_REQUIRE(c.precision >= 0 && c.precision <= 2, "conv self-test: precision 0 = f32, 1 = bf16x3, 2 = f16");
+    FS_REQUIRE(B >= 1 && Cin >= 1 && Cout >= 1 && T >= 1 && K >= 1 && dil >= 1 && stride >= 1 && K % stride == 0, "conv self-test: bad shape");
+    FS_REQUIRE(B <= 64 && Cin <= 4096 && Cout <= 4096 && K <= 64 && dil <= 256 && stride <= 64, "conv self-test: shape above the test range");
+    FS_REQUIRE((long long)B * std::max(Cin, Cout * stride) * ((long long)T + CODEC_PLANE_PAD) < (1LL << 28), "conv self-test: activation above 2^28 elements");
+    FS_REQUIRE(c.epi >= CODEC_EPI_NONE && c.epi <= CODEC_EPI_TANH, "conv self-test: unknown epilogue");
+    FS_REQUIRE(c.input >= FS_CONV_IN_F32 && c.input <= FS_CONV_IN_MEAN3_SILU, "conv self-test: unknown input kind");
+    FS_REQUIRE(c.x && c.w && c.bias, "conv self-test: x, w and bias are required");
+    FS_REQUIRE(!planes_flow || c.precision >= 1, "conv self-test: the plane data flow needs precision 1 (bf16x3) or 2 (f16)");
+    FS_REQUIRE(planes_flow || (c.input == FS_CONV_IN_F32 && c.outputs == FS_CONV_OUT_F32 && !c.mean_a && !c.mean_b && !c.post_silu),
+               "conv self-test: codec_conv1d / codec_tconv1d read f32 and write f32");
+    FS_REQUIRE(c.outputs >= 1 && c.outputs <= 3 && (!(c.outputs & FS_CONV_OUT_F32) || y_out) && (!(c.outputs & FS_CONV_OUT_PLANES) || planes_out),
+               "conv self-test: outputs = FS_CONV_OUT_F32 | FS_CONV_OUT_PLANES, each with its buffer");
+    FS_REQUIRE(!tconv || (c.epi == CODEC_EPI_NONE && dil == 1 && c.outputs == FS_CONV_OUT_F32), "conv self-test: a transposed conv has no epilogue, no dilation and an f32 output");
+    FS_REQUIRE(c.flow != FS_CONV_TCONV1D_PLANES || c.input != FS_CONV_IN_F32, "conv self-test: codec_tconv1d_planes reads planes");
+    FS_REQUIRE(!pair || (c.precision == 2 && Cin == Cout && c.input != FS_CONV_IN_F32 && c.w2 && c.bias2 && c.res && codec_respair_ok(Cin, K, dil, true)),
+               "conv self-test: the fused pair needs f16 precision, Cin == Cout, a plane input, w2 / bias2 / res and a shape codec_respair_ok accepts");
+    const bool need_res = c.epi == CODEC_EPI_RES || c.epi == CODEC_EPI_GAMMA_RES || pair;
+    FS_REQUIRE(!need_res || c.res, "conv self-test: the residual epilogues need res");
+    FS_REQUIRE(c.epi != CODEC_EPI_GAMMA_RES || c.gamma, "conv self-test: FS_CONV_EPI_GAMMA_RES needs gamma");
+    FS_REQUIRE((c.mean_a != nullptr) == (c.mean_b != nullptr), "conv self-test: mean_a and mean_b come together");
+    FS_REQUIRE(c.input < FS_CONV_IN_MEAN3 || (c.x_b && c.x_c), "conv self-test: the mean3 producer needs x_b and x_c");
+    FS_REQUIRE(c.input == FS_CONV_IN_F32 || Cin % 16 == 0, "conv self-test: plane input needs Cin % 16 == 0");
+    FS_REQUIRE(!(c.outputs & FS_CONV_OUT_PLANES) || Cout % 8 == 0, "conv self-test: plane output needs Cout % 8 == 0");
+    FS_REQUIRE(!c.range_check || (c.precision >= 1 && range_out), "conv self-test: the range check needs precision 1 | 2 and range_out");
+    FS_REQUIRE(variant_out && variant_cap >= 1, "conv self-test: variant_out");
+
+    const bool f16 = c.precision == 2;
+    const int NP = f16 ? 1 : 2;  // plane parts
+    const size_t nx = (size_t)B * Cin * T, Tout = (size_t)T * stride, ny = (size_t)B * Cout * Tout, nw = (size_t)Cout * Cin * K;
+    const size_t row = (size_t)CODEC_PLANE_PAD + T, slack = 256 << 10;
+    auto plane_bytes = [&](int C) { return (size_t)B * NP * (C / 8) * row * 16 + slack; };
+    hipStream_t st = nullptr;
+    FS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } sg{st};
+    DBuf dx, dxb, dxc, dw, dw2, drel, drel2, dpk, dpk2, dbias, dbias2, dres, dgamma, dma, dmb, dy, dxp, dyp;
+    auto up = [&](DBuf& d, const float* src, size_t n) {
+        d.alloc(n * sizeof(float));
+        FS_HIP(hipMemcpyAsync(d.p, src, n * sizeof(float), hipMemcpyHostToDevice, st));
+    };
+    up(dx, c.x, nx);
+    if (c.input >= FS_CONV_IN_MEAN3) { up(dxb, c.x_b, nx); up(dxc, c.x_c, nx); }
+    up(dw, c.w, nw); up(dbias, c.bias, Cout);
+    if (pair) { up(dw2, c.w2, nw); up(dbias2, c.bias2, Cout); }
+    if (need_res) up(dres, c.res, ny);
+    if (c.epi == CODEC_EPI_GAMMA_RES) up(dgamma, c.gamma, Cout);
+    if (c.mean_a) { up(dma, c.mean_a, ny); up(dmb, c.mean_b, ny); }
+
+    std::unique_lock<std::mutex> range_lock;  // one checked call at a time per process (one counter pair per device)
+    struct CheckGuard { bool on = false; ~CheckGuard() { if (on) codec_range_check(false); } } chk;
+    if (c.range_check) {
+        range_lock = std::unique_lock<std::mutex>(Codec::range_guard_mutex());
+        codec_range_check(true);
+        chk.on = true;
+        codec_range_reset(st);
+    }
+    // load time: checkpoint layout -> [Cin][K][Cout] (polyphase form for a transposed conv) -> MFMA operand order of the precision mode
+    const int Kg = K / stride, Cg = Cout * stride;  // GEMM shape
+    auto load = [&](DBuf& raw, DBuf& rel, DBuf& pk, const DBuf& b) {
+        rel.alloc(nw * sizeof(float));
+        if (tconv) codec_relayout_tconv(raw.f(), rel.f(), Cout, Cin, K, stride, st);
+        else codec_relayout(raw.f(), rel.f(), Cout, Cin, K, false, st);
+        ConvW w;
+        w.wt = rel.f(); w.b = b.f(); w.cout = Cout; w.k = K;
+        if (c.precision >= 1) {
+            pk.alloc(codec_pack_bf3_elems(Cin, Kg, Cg, f16) * sizeof(uint16_t));
+            codec_pack_bf3(rel.f(), pk.u16(), Cin, Kg, Cg, f16, st);
+            w.wp = pk.u16(); w.f16 = f16;
+        }
+        return w;
+    };
+    const ConvW w1 = load(dw, drel, dpk, dbias);
+    ConvW w2;
+    if (pair) w2 = load(dw2, drel2, dpk2, dbias2);
+    // producers of the plane input
+    if (c.input != FS_CONV_IN_F32) {
+        dxp.alloc(plane_bytes(Cin));
+        FS_HIP(hipMemsetAsync(dxp.p, 0xFF, dxp.n, st));
+        const bool silu = c.input == FS_CONV_IN_SPLIT_SILU || c.input == FS_CONV_IN_MEAN3_SILU;
+        if (c.input >= FS_CONV_IN_MEAN3) codec_mean3_planes(dx.f(), dxb.f(), dxc.f(), B, Cin, T, silu, dxp.u16(), f16, st);
+        else codec_act_split(dx.f(), B, Cin, T, silu, dxp.u16(), f16, st);
+    }
+    if (c.outputs & FS_CONV_OUT_F32) { dy.alloc(ny * sizeof(float)); FS_HIP(hipMemsetAsync(dy.p, 0xFF, dy.n, st)); }
+    if (c.outputs & FS_CONV_OUT_PLANES) { dyp.alloc(plane_bytes(Cout)); FS_HIP(hipMemsetAsync(dyp.p, 0xFF, dyp.n, st)); }
+    const float* xin = c.input == FS_CONV_IN_F32 ? dx.f() : nullptr;
+    codec_variant_note(nullptr);
+    switch (c.flow) {
+    case FS_CONV_CONV1D: codec_conv1d(dx.f(), B, Cin, T, w1, dil, c.pre_silu != 0, c.epi, dres.f(), dgamma.f(), dy.f(), st); break;
+    case FS_CONV_TCONV1D: codec_tconv1d(dx.f(), B, Cin, T, w1, stride, c.pre_silu != 0, dy.f(), st); break;
+    case FS_CONV_CONV1D_PLANES:
+        codec_conv1d_planes(xin, dxp.u16(), B, Cin, T, w1, dil, c.pre_silu != 0, c.epi, dres.f(), dgamma.f(), dy.f(), dyp.u16(), c.post_silu != 0, st, nullptr,
+                            nullptr, dma.f(), dmb.f());
+        break;
+    case FS_CONV_TCONV1D_PLANES: codec_tconv1d_planes(dxp.u16(), B, Cin, T, w1, stride, dy.f(), st); break;
+    default:
+        codec_respair_f16(dxp.u16(), B, Cin, T, w1.wp, w1.b, w2.wp, w2.b, K, dil, dres.f(), dy.f(), dyp.u16(), st, nullptr, nullptr, nullptr, nullptr, dma.f(),
+                          dmb.f());
+        break;
+    }
+    const char* name = codec_variant_last();
+    if (c.range_check) {
+        codec_range_check(false);
+        chk.on = false;
+        unsigned long long r[2] = {0, 0};
+        codec_range_read(r, st);
+        range_out[0] = r[0]; range_out[1] = r[1];
+        range_lock.unlock();
+    }
+    if (c.outputs & FS_CONV_OUT_F32) FS_HIP(hipMemcpyAsync(y_out, dy.p, ny * sizeof(float), hipMemcpyDeviceToHost, st));
+    std::vector<uint16_t> hp;
+    if (c.outputs & FS_CONV_OUT_PLANES) {
+        hp.resize((size_t)B * NP * (Cout / 8) * row * 8);
+        FS_HIP(hipMemcpyAsync(hp.data(), dyp.p, hp.size() * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
+    }
+    FS_HIP(hipStreamSynchronize(st));
+    if (c.outputs & FS_CONV_OUT_PLANES) {  // planes [B][part][Cout/8][64 + T][8] -> f32 [B][Cout][64 + T]
+        const size_t CG = (size_t)Cout / 8;
+        auto bf = [](uint16_t h) { const uint32_t u = (uint32_t)h << 16; float f; std::memcpy(&f, &u, 4); return f; };
+        for (size_t b = 0; b < (size_t)B; ++b)
+            for (size_t o = 0; o < (size_t)Cout; ++o)
+                for (size_t s = 0; s < row; ++s) {
+                    const size_t i0 = (((b * NP) * CG + o / 8) * row + s) * 8 + o % 8;
+                    float v;
+                    if (f16) { _Float16 h; std::memcpy(&h, &hp[i0], 2); v = (float)h; }
+                    else v = bf(hp[i0]) + bf(hp[i0 + CG * row * 8]);
+                    planes_out[(b * Cout + o) * row + s] = v;
+                }
+    }
+    FS_REQUIRE(name, "conv self-test: the launcher recorded no variant name");
+    std::snprintf(variant_out, variant_cap, "%s", name);
+}
 
 }  // namespace fs

@@ -90,6 +90,11 @@ void codec_respair_f16(const uint16_t* xp, int B, int C, int T, const uint16_t* 
 void codec_range_check(bool on);
 void codec_range_reset(hipStream_t st);
 void codec_range_read(unsigned long long* out2, hipStream_t st);
+// launch diagnostics (fs_selftest_conv1d): the conv launchers above store, per calling thread, a short stable name of the kernel
+// instantiation they launch, e.g. "f16/bf3p/TT256/nibs4/RES" ("chk/" in front: the range-checked twin).  Host side only -- a pointer to a
+// string literal beside the launch.  codec_variant_note(nullptr) clears it.
+void codec_variant_note(const char* name);
+const char* codec_variant_last();
 // ---- encoder side (FireflyCodec::encode)
 void codec_stft_mag(const float* pcm, int n, int n_fft, int hop, int n_frames, float* lin /*[n_fft/2+1][frames]*/, hipStream_t st);
 void codec_mel_log(const float* lin, const float* fb /*[nf][n_mels]*/, int nf, int n_mels, int F, float* mel /*[n_mels][F]*/, hipStream_t st);

@@ -402,6 +402,11 @@ __global__ void k_synth_f32(float* __restrict__ dst, uint64_t key, size_t n, flo
 // ================================================================================================ launchers
 #define FS_LAUNCH_CHECK() FS_HIP(hipGetLastError())
 
+// launch diagnostics (codec_kernels.h): the name of the last conv instantiation launched from this thread
+static thread_local const char* g_variant = nullptr;
+void codec_variant_note(const char* name) { g_variant = name; }
+const char* codec_variant_last() { return g_variant; }
+
 void codec_fsq_project(const uint32_t* codes, int B, int G, int T, const float* pw, const float* pb, int dg, float* z, hipStream_t st, bool item_rows) {
     hipLaunchKernelGGL(k_fsq_project, dim3((T + 63) / 64, G, B), dim3(64), 0, st, codes, B, G, T, pw, pb, dg, z, item_rows ? 1 : 0);
     FS_LAUNCH_CHECK();
@@ -418,6 +423,7 @@ static void conv1d_launch(const float* x, int B, int Cin, int T, const ConvW& w,
         constexpr int OT = 8 * CPT, TT = 32 * TPT;
         const size_t smem = sizeof(float) * ((size_t)ICH * (TT + halo) + (size_t)ICH * K * OT);
         FS_REQUIRE(smem <= 64 * 1024, "conv tile does not fit LDS");
+        codec_variant_note(OT == 64 ? "f32/valu/OT64/TT128" : OT == 32 ? "f32/valu/OT32/TT128" : OT == 16 ? "f32/valu/OT16/TT256" : "f32/valu/OT8/TT256");
         hipLaunchKernelGGL((k_conv1d<CPT, TPT, ICH>), dim3((T + TT - 1) / TT, (Cout + OT - 1) / OT, B), dim3(256), smem, st, x, Cin, T,
                            w.wt, w.b, Cout, K, dil, pre_silu ? 1 : 0, epi, res, gamma, y, ps, ctx, ctx_off);
     };
@@ -425,6 +431,7 @@ static void conv1d_launch(const float* x, int B, int Cin, int T, const ConvW& w,
     using I8 = std::integral_constant<int, 8>; using I16 = std::integral_constant<int, 16>;
     const bool mfma_ok = Cin >= 16 && Cout >= 16 && K <= 13 && halo <= 256;
     if (Cout == 1 && Cin == 16 && dil == 1 && ps == 1 && K - 1 <= CODEC_CTX_F32 && (epi == CODEC_EPI_NONE || epi == CODEC_EPI_TANH || epi == CODEC_EPI_GELU)) {
+        codec_variant_note("f32/one/CIN16");
         hipLaunchKernelGGL((k_conv1d_one<16>), dim3((T + 511) / 512, 1, B), dim3(128), 0, st, x, T, w.wt, w.b, K, pre_silu ? 1 : 0, epi, y, ctx, ctx_off);
         FS_LAUNCH_CHECK();
         return;
@@ -445,19 +452,20 @@ static void conv1d_launch(const float* x, int B, int Cin, int T, const ConvW& w,
         FS_REQUIRE(TT + halo <= (TT == 256 ? 512 : 256), "conv window does not fit the MFMA kernel's staging");
         const size_t smem = sizeof(float) * ((((size_t)ICH * (TT + halo) + 3) & ~(size_t)3) + (size_t)ICH * K * OT);
         FS_REQUIRE(smem <= 128 * 1024, "conv tile does not fit LDS");
-        auto go = [&](auto kern) {
+        auto go = [&](auto kern, const char* name) {
             if (smem > 64 * 1024) {  // above the default dynamic-LDS limit: raise it once per kernel (not inside a graph capture)
                 static thread_local std::set<const void*> raised;
                 if (raised.insert((const void*)kern).second)
                     FS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
             }
+            codec_variant_note(name);
             hipLaunchKernelGGL(kern, dim3((T + TT - 1) / TT, (Cout + OT - 1) / OT, B), dim3(256), smem, st, x, Cin, T, w.wt, w.b, Cout, K, dil,
                                pre_silu ? 1 : 0, epi, res, gamma, y, ps);
         };
-        if (OT == 64 && TT == 256) go(k_conv1d_mfma<ICH, 64, 256>);
-        else if (OT == 64) go(k_conv1d_mfma<ICH, 64, 128>);
-        else if (TT == 256) go(k_conv1d_mfma<ICH, 32, 256>);
-        else go(k_conv1d_mfma<ICH, 32, 128>);
+        if (OT == 64 && TT == 256) go(k_conv1d_mfma<ICH, 64, 256>, "f32/mfma/OT64/TT256");
+        else if (OT == 64) go(k_conv1d_mfma<ICH, 64, 128>, "f32/mfma/OT64/TT128");
+        else if (TT == 256) go(k_conv1d_mfma<ICH, 32, 256>, "f32/mfma/OT32/TT256");
+        else go(k_conv1d_mfma<ICH, 32, 128>, "f32/mfma/OT32/TT128");
     } else if (Cout >= 64) launch(I8(), I4(), I8());   // 64 ch x 128 t
     else if (Cout >= 32) launch(I4(), I4(), I8());     // 32 ch x 128 t
     else if (Cout >= 16) launch(I2(), I8(), I16());    // 16 ch x 256 t

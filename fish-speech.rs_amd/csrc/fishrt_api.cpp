@@ -110,6 +110,13 @@ int fs_selftest_alt_rows(int device_id, const float* logits, int S, int n, int e
     FS_ARG(n_alts >= 1 && n_alts <= (int)FS_ALTS_MAX, "bad alternatives test shape (1 <= n_alts <= 16)");
     FS_TRY(fs::debug_alt_rows(device_id, logits, S, n, exclude0, n_alts, alt_index_out, alt_logprob_out, entropy_out))
 }
+static_assert(sizeof(fs_conv_case) == 16 * 4 + 11 * 8, "fs_conv_case is 16 x int32 and 11 pointers (fishrt/_ffi.py: ConvCase)");
+int fs_selftest_conv1d(int device_id, const fs_conv_case* c, float* y_out, float* planes_out, char* variant_out, size_t variant_cap,
+                       uint64_t* range_out) {
+    FS_ARG(c && variant_out && variant_cap >= 1, "null argument");
+    variant_out[0] = 0;
+    FS_TRY(fs::codec_conv_selftest(device_id, *c, y_out, planes_out, variant_out, variant_cap, range_out))
+}
 
 // ---- replica fan-out over RCCL (fs_comm.h)
 int fs_comm_unique_id(uint8_t id_out[FS_COMM_ID_BYTES]) { FS_ARG(id_out, "null argument"); FS_TRY(fs::Comm::unique_id(id_out)) }

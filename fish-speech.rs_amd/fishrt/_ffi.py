@@ -36,6 +36,12 @@ class KvBlobHeader(C.LittleEndianStructure):  # fs_kv_blob_header: the 64 bytes 
                 ("reserved2", C.c_uint64)]
 
 
+class ConvCase(C.Structure):  # fs_conv_case: one convolution for fs_selftest_conv1d
+    _fields_ = [(n, C.c_int32) for n in ("flow", "precision", "B", "Cin", "Cout", "T", "K", "dil", "stride", "pre_silu", "epi",
+                                         "post_silu", "input", "outputs", "range_check", "reserved")] + \
+               [(n, C.POINTER(C.c_float)) for n in ("x", "x_b", "x_c", "w", "bias", "w2", "bias2", "res", "gamma", "mean_a", "mean_b")]
+
+
 FRAME_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32))
 
 # every symbol include/fishrt.h declares (tests/test_abi.py checks the library exports all of them)
@@ -49,6 +55,7 @@ SYMBOLS = ["fs_last_error", "fs_version", "fs_device_count", "fs_lm_create", "fs
            "fs_lm_session_add_scored", "fs_lm_session_poll_scores", "fs_selftest_score_rows",
            "fs_lm_session_add_traced", "fs_lm_session_poll_trace",
            "fs_lm_session_poll_alts", "fs_selftest_alt_rows",
+           "fs_selftest_conv1d",
            "fs_lm_weights_fingerprint", "fs_lm_session_prefix_export", "fs_lm_session_prefix_import",
            "fs_codec_create", "fs_codec_destroy", "fs_codec_load_safetensors", "fs_codec_load_synthetic",
            "fs_codec_decode", "fs_codec_encode", "fs_codec_encode_batch", "fs_codec_sample_rate", "fs_codec_set_precision", "fs_codec_precision", "fs_codec_set_range_check", "fs_codec_range_stats", "fs_codec_stream_begin", "fs_codec_stream_decode", "fs_codec_stream_end", "fs_codec_streams_open", "fs_codec_streams_close", "fs_codec_streams_decode", "fs_codec_streams_decode_ragged", "fs_fp8_quantize_rows", "fs_fp8_decode_table", "fs_selftest", "fs_lm_selftest", "fs_selftest_sample_rows", "fs_selftest_sample_slots", "fs_lm_debug_capture", "fs_lm_debug_read"]
@@ -84,6 +91,15 @@ ALTS_PROTOTYPES = {
     "fs_selftest_alt_rows": [C.c_int, _F32P, C.c_int, C.c_int, C.c_int, C.c_int, _U32P, _F32P, _F32P],
 }
 
+# fs_selftest_conv1d (flows, input kinds, epilogues, outputs: include/fishrt.h)
+FS_CONV_CONV1D, FS_CONV_TCONV1D, FS_CONV_CONV1D_PLANES, FS_CONV_TCONV1D_PLANES, FS_CONV_RESPAIR_F16 = range(5)
+FS_CONV_IN_F32, FS_CONV_IN_SPLIT, FS_CONV_IN_SPLIT_SILU, FS_CONV_IN_MEAN3, FS_CONV_IN_MEAN3_SILU = range(5)
+FS_CONV_EPI_NONE, FS_CONV_EPI_GELU, FS_CONV_EPI_GAMMA_RES, FS_CONV_EPI_RES, FS_CONV_EPI_TANH = range(5)
+FS_CONV_OUT_F32, FS_CONV_OUT_PLANES = 1, 2
+CONV_PROTOTYPES = {
+    "fs_selftest_conv1d": [C.c_int, C.POINTER(ConvCase), _F32P, _F32P, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64)],
+}
+
 _lib = None
 
 
@@ -103,7 +119,7 @@ def lib():
         L.fs_comm_destroy.argtypes = [C.c_void_p]
         L.fs_lm_destroy.argtypes = [C.c_void_p]
         L.fs_codec_destroy.argtypes = [C.c_void_p]
-        for name, argtypes in {**SCORE_PROTOTYPES, **TRACE_PROTOTYPES, **ALTS_PROTOTYPES}.items():
+        for name, argtypes in {**SCORE_PROTOTYPES, **TRACE_PROTOTYPES, **ALTS_PROTOTYPES, **CONV_PROTOTYPES}.items():
             getattr(L, name).argtypes = argtypes
         _lib = L
     return _lib

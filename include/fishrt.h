@@ -109,6 +109,45 @@ int fs_selftest_score_rows(int device_id, const float* logits, int S, int n, con
 int fs_selftest_alt_rows(int device_id, const float* logits, int S, int n, int exclude0, int n_alts, uint32_t* alt_index_out,
                          float* alt_logprob_out, float* entropy_out);
 
+/* ONE convolution of the vocoder on caller-provided host data, through the load-time and launch functions the codec engine itself uses
+ * (csrc/codec_kernels.h) and nothing else: the weights arrive in checkpoint layout -- Conv1d [Cout][Cin][K], ConvTranspose1d [Cin][Cout][K]
+ * -- and go through codec_relayout / codec_relayout_tconv and, for the matrix modes, codec_pack_bf3; then one launcher call of kind `flow`:
+ *   FS_CONV_CONV1D / FS_CONV_TCONV1D               codec_conv1d / codec_tconv1d: f32 in (input = FS_CONV_IN_F32), f32 out
+ *   FS_CONV_CONV1D_PLANES / FS_CONV_TCONV1D_PLANES codec_conv1d_planes / codec_tconv1d_planes (precision 1 | 2): f32 or plane input, f32 and / or
+ *                                                  plane output, post_silu, and with mean_a / mean_b the ParallelBlock mean folded into a
+ *                                                  FS_CONV_EPI_RES epilogue: ((mean_a + mean_b) + (res + conv)) * (float)(1/3)
+ *   FS_CONV_RESPAIR_F16                            codec_respair_f16 (precision 2, Cin == Cout in {16, 32}): res + conv2(silu(conv1(xp))) with
+ *                                                  w / bias and w2 / bias2, the same K and dil on both
+ * precision: 0 = f32, 1 = bf16x3, 2 = f16, the meaning fs_codec_set_precision gives them.  Causal, stride 1, left zero pad (K-1)*dil; a
+ * transposed conv has `stride`, K % stride == 0, right trim K - stride, and T * stride output samples.  epi = FS_CONV_EPI_*; res [B][Cout][T],
+ * gamma [Cout], bias [Cout].  No streaming contexts: every call is the start of a signal.
+ * input: FS_CONV_IN_F32 = the launcher reads x [B][Cin][T] itself (pre_silu applies); the others first make the activation planes the launcher
+ * reads: codec_act_split(x) without / with SiLU, or codec_mean3_planes(x, x_b, x_c) without / with SiLU (pre_silu is then not applied again).
+ * outputs: bit FS_CONV_OUT_F32 -> y_out f32 [B][Cout][T (* stride)]; bit FS_CONV_OUT_PLANES -> planes_out f32 [B][Cout][64 + T]: the plane
+ * tensor the launcher wrote, read back and returned as the values it encodes (bf16x3: hi + lo, f16: the f16 value), INCLUDING the 64 pad
+ * slots in front of every row (zeros at the start of a signal).  Both output buffers are poisoned (NaN) before the launch.
+ * variant_out receives the NUL-terminated name of the kernel instantiation the launcher chose ("f32/mfma/OT64/TT256",
+ * "f16/bf3p/TT256/nibs4/RES", "f16/pair/K7/nib2/NW8/NH2", ...; "chk/" in front: the range-checked twin).
+ * range_check != 0 (precision 1 | 2): pack, producers and launcher run as under fs_codec_set_range_check, and range_out[0] / [1] receive
+ * the operands counted as saturated (|v| > 65504) / flushed (0 < |v| < 2^-24) by the f32 -> f16 conversions of this call (each weight once
+ * at pack time; each activation once per conversion, i.e. once for a plane producer).  Diagnostics / parity tests. */
+enum { FS_CONV_CONV1D = 0, FS_CONV_TCONV1D = 1, FS_CONV_CONV1D_PLANES = 2, FS_CONV_TCONV1D_PLANES = 3, FS_CONV_RESPAIR_F16 = 4 };
+enum { FS_CONV_IN_F32 = 0, FS_CONV_IN_SPLIT = 1, FS_CONV_IN_SPLIT_SILU = 2, FS_CONV_IN_MEAN3 = 3, FS_CONV_IN_MEAN3_SILU = 4 };
+enum { FS_CONV_EPI_NONE = 0, FS_CONV_EPI_GELU = 1, FS_CONV_EPI_GAMMA_RES = 2, FS_CONV_EPI_RES = 3, FS_CONV_EPI_TANH = 4 };
+enum { FS_CONV_OUT_F32 = 1, FS_CONV_OUT_PLANES = 2 };
+typedef struct fs_conv_case {
+    int32_t flow, precision;
+    int32_t B, Cin, Cout, T, K, dil, stride;
+    int32_t pre_silu, epi, post_silu;
+    int32_t input, outputs;
+    int32_t range_check, reserved;
+    const float *x, *x_b, *x_c;
+    const float *w, *bias, *w2, *bias2;
+    const float *res, *gamma, *mean_a, *mean_b;
+} fs_conv_case;
+int fs_selftest_conv1d(int device_id, const fs_conv_case* c, float* y_out, float* planes_out, char* variant_out, size_t variant_cap,
+                       uint64_t* range_out);
+
 /* Self-test of a LOADED handle, by name.  "persist": the persistent decode kernels of this binary (csrc/lm_persist.hip, lm_persist_slow.hip:
  * pinned weight registers, loads issued outside the compiler's wait-count bookkeeping) against the per-node kernels on the handle's own
  * weights -- 4 greedy frames on the persistent path with the decision capture armed for the first 2, then one teacher-forced per-node step

@@ -33,6 +33,7 @@ def test_struct_layouts_match_header():
     assert ctypes.sizeof(_ffi.TokenCfg) == 5 * 4
     assert ctypes.sizeof(_ffi.Sampling) == 32
     assert ctypes.sizeof(_ffi.GenStats) == 64
+    assert ctypes.sizeof(_ffi.ConvCase) == 16 * 4 + 11 * 8  # fs_conv_case: 16 x int32, 11 pointers (static_assert in csrc/fishrt_api.cpp)
 
 
 def test_product_never_imports_oracle():
