@@ -27,6 +27,7 @@
 #include <unistd.h>
 
 #include "fs_common.h"
+#include "fs_kv_pages.h"
 #include "fs_synth.h"
 #include "lm_kernels.h"
 #include "lm_persist.h"
@@ -410,7 +411,7 @@ class LM final : public LMBase {
     void debug_read_kv(int slot, int layer, int t0, int n, float* k_out, float* v_out) override {
         use_device();
         FS_REQUIRE(slot >= 0 && slot < B_ && layer >= 0 && layer < a_.n_layer, "bad KV slot / layer");
-        FS_REQUIRE(t0 >= 0 && n >= 0 && t0 + n <= (int)seq_pages_[slot].size() * KV_PAGE, "rows outside the slot's KV pages");
+        FS_REQUIRE(t0 >= 0 && n >= 0 && t0 + n <= (int)pages_.of(slot).size() * KV_PAGE, "rows outside the slot's KV pages");
         FS_HIP(hipStreamSynchronize(st_));
         const int Hk = a_.n_local_heads, Dh = a_.head_dim;
         std::vector<KT> pk(page_elems_), pv(page_elems_);
@@ -418,7 +419,7 @@ class LM final : public LMBase {
         const KT* vpool = kpool + (size_t)n_pages_ * page_elems_;
         int have = -1;
         for (int t = t0; t < t0 + n; ++t) {
-            const int pg = seq_pages_[slot][t >> 6];
+            const int pg = pages_.of(slot)[t >> 6];
             if (pg != have) {
                 FS_HIP(hipMemcpy(pk.data(), kpool + (size_t)pg * page_elems_, sizeof(KT) * page_elems_, hipMemcpyDeviceToHost));
                 FS_HIP(hipMemcpy(pv.data(), vpool + (size_t)pg * page_elems_, sizeof(KT) * page_elems_, hipMemcpyDeviceToHost));
@@ -982,7 +983,7 @@ class LM final : public LMBase {
         if (flags & FS_SESSION_ROWS) {
             const char* why = nullptr;
             if (!rows_predicate(B_, &s, 1, /*for_session=*/true, &why)) throw Error(std::string("FS_SESSION_ROWS needs ") + why);
-            FS_REQUIRE(!free_pages_.empty(), "KV page pool exhausted");
+            FS_REQUIRE(pages_.free_count() > 0, "KV page pool exhausted");  // (the scratch page below: nothing may throw once the lock is held)
             // the device's persistent-kernel lock is held in a LOCAL until nothing below can throw any more (a throw after taking it used to
             // leave sess_plock_ owning the mutex with sess_active_ false: session_end returned early and the device was locked out for good)
             rows_lock = acquire_persist(device_);
@@ -1026,8 +1027,7 @@ class LM final : public LMBase {
         RngState rng;
         upload_rng(seed, rng, d_rng_.as<RngState>(), st_);
         // empty slots: dead, frame 1 (so the frame-0 rule never fires), position 0 of a scratch page nobody reads
-        FS_REQUIRE(!free_pages_.empty(), "KV page pool exhausted");
-        sess_scratch_ = take_page();
+        sess_scratch_ = pages_.hold_new();
         sess_left_.assign(B_, kSlotFree);
         sess_pos_.assign(B_, 0);
         sess_hs_.assign(B_, SeqState{});
@@ -1133,11 +1133,9 @@ class LM final : public LMBase {
         int b = -1;
         for (int i = 0; i < B_; ++i) if (slot_free(i)) { b = i; break; }
         if (b < 0) return -1;
-        const SessPrefix* px = prefixed ? &sess_prefixes_[r.prefix_id] : nullptr;
         const int nfull = P / KV_PAGE, end = L + n_iter - 1;  // the prefix's full pages are shared; positions < end keep their K/V
-        auto& pg = seq_pages_[b];
-        FS_REQUIRE(!px || pg.empty(), "a free slot still holds KV pages");
-        if ((int)free_pages_.size() < (end + KV_PAGE - 1) / KV_PAGE - nfull - (int)pg.size()) return -1;
+        const KvPages::Share shared{prefixed ? pages_.prefix_owner(r.prefix_id) : -1, nfull};
+        if (!pages_.room(b, end, shared).fits) return -1;  // (a free slot that still holds pages is an error, raised here)
         ensure_prefill2_buffers();
         // 3. the queue entry, complete but for what is taken below
         PendingAdd pa;
@@ -1157,16 +1155,17 @@ class LM final : public LMBase {
             pa.cfg = make_cfg(*r.sampling, sess_cfg_.ignore_eos ? FS_GEN_IGNORE_EOS : 0);
             pa.cfg.session = sess_cfg_.session;
         }
-        // 4. the collector buffers (an allocation failure leaves the session as it was)
+        // 4. the collector buffers, the first thing taken (an allocation failure leaves the session as it was)
         if (r.collect_hidden) pa.hid = hid_.book.take(n_iter);
         if (scored || r.traced) {
             try { pa.sc = sc_.book.take(n_iter); } catch (...) { hid_.book.put(pa.hid); throw; }
         }
-        // 5. the pages: references on the prefix's full ones, the slot's private ones, and a reference on the prefix's partly filled last
-        // page, held until it has been copied
-        for (int j = 0; j < nfull; ++j) { pg.push_back(px->pages[j]); ++page_refs_[px->pages[j]]; }
-        alloc_pages(b, end);
-        if (P % KV_PAGE) { pa.tail = px->pages[nfull]; ++page_refs_[pa.tail]; }
+        // 5. the pages: references on the prefix's full ones, the slot's private ones, and a hold on the prefix's partly filled last page
+        // until it has been copied.  None of the three can fail: the room query of step 2 asked for exactly this, and nothing has touched
+        // the book since.  (No upload: the row of a parked slot keeps pointing at the scratch page until activate_pending.)
+        pages_.share(b, shared);
+        pages_.grow(b, end);
+        if (P % KV_PAGE) pa.tail = pages_.hold_page_of(shared.from, nfull);
         // 6. queued: the slot is reserved, and polls of its collectors are answered from now on
         pa.order = sess_adds_++;
         sess_queue_.push_back(std::move(pa));
@@ -1291,7 +1290,7 @@ class LM final : public LMBase {
         ss.done = rows ? 2 : 1; ss.frame = 1;  // (rows mode: a terminated row is skipped by the row kernels altogether)
         sess_hs_[b] = ss;
         FS_HIP(hipMemcpyAsync(state(b), &sess_hs_[b], sizeof(SeqState), hipMemcpyHostToDevice, st_));
-        FS_HIP(hipMemcpyAsync(d_page_table_.as<int>() + (size_t)b * max_pages_, &sess_scratch_, sizeof(int), hipMemcpyHostToDevice, st_));
+        upload_row(b, st_, &sess_scratch_, 1);
         FS_HIP(hipStreamSynchronize(st_));
     }
     // Joining requests are prefilled on a second stream with their own row buffers, staging SeqState (index B_) and page-table rows
@@ -1322,9 +1321,9 @@ class LM final : public LMBase {
         int cols() const { return create ? L : L - start; }       // columns of `prompt`
         int end() const { return create ? L : L + n_iter - 1; }   // positions whose K/V the member keeps
     };
-    // a session's shared prefix: its pages (one reference each, held until released or the session ends; slots add their own on the
-    // full ones) and whether its own pass has still to be activated (a release then waits for that)
-    struct SessPrefix { int P = 0; std::vector<int> pages; bool live = false, pending = false; };
+    // a session's shared prefix; its pages are those of owner pages_.prefix_owner(id) (one reference each, held until released or the
+    // session ends; slots add their own on the full ones).  pending: its own pass has still to be activated (a release then waits for that)
+    struct SessPrefix { int P = 0; bool live = false, pending = false; };
     // Shared conditioning prefixes (fishrt.h: fs_lm_session_prefix_create).  The prefix is queued like an add; its pages are taken now,
     // so the pool check stays cumulative over everything admitted since.
     int session_prefix_create(const uint32_t* prompt, int P) override {
@@ -1341,12 +1340,13 @@ class LM final : public LMBase {
     // imported payload).  Returns its id, or -1 when the page pool is short right now.
     int queue_prefix(int P, PendingAdd pa) {
         ensure_prefill2_buffers();
-        const int np = (P + KV_PAGE - 1) / KV_PAGE;
-        if ((int)free_pages_.size() < np) return -1;
+        if (!pages_.room(KvPages::kNewOwner, P).fits) return -1;
         SessPrefix px;
         px.P = P; px.live = true; px.pending = true;
-        for (int j = 0; j < np; ++j) px.pages.push_back(take_page());
-        sess_prefixes_.push_back(std::move(px));
+        sess_prefixes_.push_back(px);
+        const int owner = pages_.add_prefix();
+        FS_REQUIRE(owner == pages_.prefix_owner((int)sess_prefixes_.size() - 1), "prefix ids and the page book's owners are out of step");
+        pages_.grow(owner, P);
         pa.create = true; pa.L = P; pa.prefix = (int)sess_prefixes_.size() - 1;
         sess_queue_.push_back(std::move(pa));
         return (int)sess_prefixes_.size() - 1;
@@ -1356,21 +1356,16 @@ class LM final : public LMBase {
         FS_REQUIRE(id >= 0 && id < (int)sess_prefixes_.size() && sess_prefixes_[id].live, "unknown or released prefix id");
         return sess_prefixes_[id];
     }
-    void drop_prefix_pages(SessPrefix& px) {
-        for (int p : px.pages) put_page(p);
-        px.pages.clear();
-    }
     void session_prefix_release(int id) override {
         use_device();
         SessPrefix& px = live_prefix(id);
         px.live = false;
-        if (!px.pending) drop_prefix_pages(px);  // (its pass still queued or in flight: activate_pending drops them after it)
+        if (!px.pending) pages_.drop(pages_.prefix_owner(id));  // (its pass still queued or in flight: activate_pending drops them after it)
     }
     void session_info(int64_t out[8]) override {
-        int64_t shared = 0, live = 0;
-        for (int r : page_refs_) shared += r > 1;
+        int64_t live = 0;
         for (const SessPrefix& px : sess_prefixes_) live += px.live;
-        out[0] = (int64_t)free_pages_.size(); out[1] = shared; out[2] = live;
+        out[0] = pages_.free_count(); out[1] = pages_.shared_count(); out[2] = live;
         for (int k = 0; k < 4; ++k) out[3 + k] = sess_count_[k];
         out[7] = (int64_t)std::llround(sess_pf_ms_ * 1000.0);
     }
@@ -1419,7 +1414,7 @@ class LM final : public LMBase {
         h.header_bytes = (uint32_t)sizeof(h);
         h.weights_fingerprint = weights_fingerprint();
         h.payload_bytes = payload;
-        const std::vector<int>& pg = sess_prefixes_[id].pages;
+        const std::vector<int>& pg = pages_.of(pages_.prefix_owner(id));
         FS_REQUIRE((int)pg.size() * KV_PAGE >= P, "the prefix holds fewer pages than its length");
         kvb_reserve(payload, pg.size());
         FS_HIP(hipMemcpyAsync(d_kvb_pages_.p, pg.data(), sizeof(int) * pg.size(), hipMemcpyHostToDevice, st_pf_));
@@ -1460,19 +1455,20 @@ class LM final : public LMBase {
         size_t n = 0, total = 0, n_ids = 0;
         while (n < sess_queue_.size() && sess_queue_[n].import_kv) {  // (everything is checked before the first launch)
             const SessPrefix& px = sess_prefixes_[sess_queue_[n].prefix];
-            FS_REQUIRE(sess_queue_[n].blob.size() == prefix_payload_bytes(px.P) && (int)px.pages.size() * KV_PAGE >= px.P,
+            const int owner = pages_.prefix_owner(sess_queue_[n].prefix);
+            FS_REQUIRE(sess_queue_[n].blob.size() == prefix_payload_bytes(px.P) && (int)pages_.of(owner).size() * KV_PAGE >= px.P,
                        "prefix import: payload / pages do not match P");
             // (slots already queued on this prefix hold references on its pages too; none of them reads or writes one before this pass)
-            for (int p : px.pages) FS_REQUIRE(p >= 0 && p < n_pages_ && page_refs_[p] >= 1, "prefix import: a page of the prefix is not held");
+            FS_REQUIRE(pages_.intact(owner), "prefix import: a page of the prefix is not held");
             total += sess_queue_[n].blob.size();
-            n_ids += sess_prefixes_[sess_queue_[n].prefix].pages.size();
+            n_ids += pages_.of(owner).size();
             ++n;
         }
         kvb_reserve(total, n_ids);
         std::vector<int>& ids = sess_stage_imp_pages_;  // (alive until the pass has been activated)
         ids.clear();
         for (size_t i = 0; i < n; ++i) {
-            const auto& pg = sess_prefixes_[sess_queue_[i].prefix].pages;
+            const auto& pg = pages_.of(pages_.prefix_owner(sess_queue_[i].prefix));
             ids.insert(ids.end(), pg.begin(), pg.end());
         }
         FS_HIP(hipMemcpyAsync(d_kvb_pages_.p, ids.data(), sizeof(int) * ids.size(), hipMemcpyHostToDevice, st_pf_));
@@ -1486,7 +1482,7 @@ class LM final : public LMBase {
             launch_kv_rows_scatter(kv_pool_.p, 2 * a_.n_layer, (size_t)n_pages_ * page_bytes, page_bytes, d_kvb_pages_.as<int>() + id_off, px.P,
                                    a_.n_local_heads, a_.head_dim, sizeof(KT), stage, st_pf_);
             off += pa.blob.size();
-            id_off += px.pages.size();
+            id_off += pages_.of(pages_.prefix_owner(pa.prefix)).size();
         }
         pass_launched(n);
     }
@@ -1534,33 +1530,31 @@ class LM final : public LMBase {
                 const int fit = std::max(1, std::min(kRowsCap / Lp, B_));
                 // pad positions write K/V up to start + Lp: every member must own pages that far (bounded: they go back with the slot,
                 // or at activation for a prefix).  The extra pages are counted CUMULATIVELY over the group -- checked per member,
-                // several short-budget members could each pass and alloc_pages would then throw in the middle of the flush with the
+                // several short-budget members could each pass and the growth would then throw in the middle of the flush with the
                 // queue half consumed
-                auto extra = [&](const PendingAdd& pa) {
-                    const int want = (std::max(pa.end(), pa.start + Lp) + KV_PAGE - 1) / KV_PAGE;
-                    return std::max(0, want - (int)member_pages(pa).size());
-                };
+                int need_sum = 0;
+                auto extra = [&](const PendingAdd& pa) { return pages_.room(member_owner(pa), pad_end(pa, Lp), {}, need_sum); };
                 const bool create = sess_queue_[i].create;
-                int need_sum = extra(sess_queue_[i]);
+                const KvPages::Room first = extra(sess_queue_[i]);
+                need_sum = first.cost;
                 // A member admitted with a sampler seed of its own (fs_lm_session_add_ex) is prefilled in a pass of its own: a group pass
                 // rounds differently from a single one (other tiling: ~5e-4 on the first logits), and whoever names a seed asks for codes
                 // that are a function of the request alone, not of what happened to be queued with it
                 while (i + S < sess_queue_.size() && S < fit && sess_queue_[i + S].rows() >= 1 && sess_queue_[i + S].create == create &&
                        !sess_queue_[i].has_seed && !sess_queue_[i + S].has_seed &&
                        sess_queue_[i + S].start + Lp <= a_.max_seq_len) {
-                    const int need = extra(sess_queue_[i + S]);
-                    if (need_sum + need > (int)free_pages_.size()) break;
-                    need_sum += need;
+                    const KvPages::Room more = extra(sess_queue_[i + S]);
+                    if (!more.fits) break;
+                    need_sum += more.cost;
                     ++S;
                 }
-                if (need_sum > (int)free_pages_.size()) S = 1;  // (the first member alone does not fit a group pass either: its own pages were reserved by session_admit)
+                if (!first.fits) S = 1;  // (the first member alone does not fit a group pass either: its own pages were reserved by session_admit)
             }
             launch_tail_copies(sess_queue_.begin() + i, sess_queue_.begin() + i + S);
             if (S == 1 || !flash) {  // one sequence, passes of <= kRowsCap rows
                 const PendingAdd& pa = sess_queue_[i];
-                const auto& pg = member_pages(pa);
-                if (!pa.create) require_private(pa.slot, pa.start);
-                FS_HIP(hipMemcpyAsync(d_page_table_.as<int>() + (size_t)B_ * max_pages_, pg.data(), sizeof(int) * pg.size(), hipMemcpyHostToDevice, st_pf_));
+                if (!pa.create) pages_.writable_from(pa.slot, pa.start);
+                upload_row(B_, st_pf_, pages_.of(member_owner(pa)));
                 const int cols = pa.cols();
                 if (d2_prompt_.n < sizeof(uint32_t) * (size_t)C1 * cols) d2_prompt_.alloc(sizeof(uint32_t) * (size_t)C1 * cols);
                 FS_HIP(hipMemcpyAsync(d2_prompt_.p, pa.prompt.data(), sizeof(uint32_t) * (size_t)C1 * cols, hipMemcpyHostToDevice, st_pf_));
@@ -1590,23 +1584,18 @@ class LM final : public LMBase {
                 int max_start = 0;
                 for (int s = 0; s < S; ++s) {
                     PendingAdd& pa = sess_queue_[i + s];
-                    if (pa.create) {
-                        auto& pp = sess_prefixes_[pa.prefix].pages;
-                        while ((int)pp.size() * KV_PAGE < std::max(pa.L, Lp)) pp.push_back(take_page());  // (pad rows; trimmed at activation)
-                    } else {
-                        alloc_pages(pa.slot, std::max(pa.end(), pa.start + Lp));
-                        require_private(pa.slot, pa.start);
-                    }
+                    pages_.grow(member_owner(pa), pad_end(pa, Lp));  // (pad rows; a prefix's are trimmed at activation)
+                    if (!pa.create) pages_.writable_from(pa.slot, pa.start);
                     const int n = pa.rows(), cols = pa.cols();
                     for (int r = 0; r < C1; ++r) std::memcpy(&padded[pstride * s + (size_t)r * Lp], &pa.prompt[(size_t)r * cols], sizeof(uint32_t) * n);
-                    const auto& pg = member_pages(pa);
+                    const auto& pg = pages_.of(member_owner(pa));
                     std::copy(pg.begin(), pg.end(), rows.begin() + (size_t)s * max_pages_);
                     pos0[s].pos = pa.start;
                     max_start = std::max(max_start, pa.start);
                 }
                 if (d2_prompt_.n < sizeof(uint32_t) * padded.size()) d2_prompt_.alloc(sizeof(uint32_t) * padded.size());
                 FS_HIP(hipMemcpyAsync(d2_prompt_.p, padded.data(), sizeof(uint32_t) * padded.size(), hipMemcpyHostToDevice, st_pf_));
-                FS_HIP(hipMemcpyAsync(d_page_table_.as<int>() + (size_t)B_ * max_pages_, rows.data(), sizeof(int) * rows.size(), hipMemcpyHostToDevice, st_pf_));
+                upload_row(B_, st_pf_, rows);
                 sess_stage_ = SeqState{};
                 sess_stage_.prompt_L = Lp;
                 FS_HIP(hipMemcpyAsync(state(B_), &sess_stage_, sizeof(SeqState), hipMemcpyHostToDevice, st_pf_));
@@ -1635,10 +1624,9 @@ class LM final : public LMBase {
         pairs.clear();
         for (It it = first; it != last; ++it)
             if (!it->create && it->tail >= 0) {
-                const int dst = seq_pages_[it->slot][it->start / KV_PAGE];
-                FS_REQUIRE(page_refs_[dst] == 1, "a session slot would write a shared KV page");
+                pages_.writable_from(it->slot, it->start);
                 pairs.push_back(it->tail);
-                pairs.push_back(dst);
+                pairs.push_back(pages_.of(it->slot)[it->start / KV_PAGE]);
             }
         if (pairs.empty()) return;
         const int n = (int)pairs.size() / 2;
@@ -1648,7 +1636,9 @@ class LM final : public LMBase {
         launch_kv_page_copy(kv_pool_.p, 2 * a_.n_layer, (size_t)n_pages_ * page_bytes, page_bytes, d2_copy_.as<int>(), n, st_pf_);
         sess_count_[3] += n;
     }
-    const std::vector<int>& member_pages(const PendingAdd& pa) const { return pa.create ? sess_prefixes_[pa.prefix].pages : seq_pages_[pa.slot]; }
+    // whose pages a queued request's pass writes, and how far a pass whose longest member runs Lp tokens makes it write
+    int member_owner(const PendingAdd& pa) const { return pa.create ? pages_.prefix_owner(pa.prefix) : pa.slot; }
+    static int pad_end(const PendingAdd& pa, int Lp) { return std::max(pa.end(), pa.start + Lp); }
     // the requests whose prefill is in flight (if it has finished, or after waiting for it) become live slots; called between steps only
     void activate_pending(bool wait) {
         if (sess_flight_.empty()) return;
@@ -1674,16 +1664,14 @@ class LM final : public LMBase {
             if (pa.create) {  // the prefix's K/V are in place: its pad pages go back; a prefix released meanwhile goes now
                 SessPrefix& px = sess_prefixes_[pa.prefix];
                 px.pending = false;
-                const size_t keep = (size_t)((px.P + KV_PAGE - 1) / KV_PAGE);
-                while (px.pages.size() > keep) { put_page(px.pages.back()); px.pages.pop_back(); }
-                if (!px.live) drop_prefix_pages(px);
+                pages_.truncate(pages_.prefix_owner(pa.prefix), px.P);
+                if (!px.live) pages_.drop(pages_.prefix_owner(pa.prefix));
                 continue;
             }
-            if (pa.tail >= 0) put_page(pa.tail);  // (copied: the joining slot's hold on the prefix's last page ends)
+            if (pa.tail >= 0) pages_.drop_hold(pa.tail);  // (copied: the joining slot's hold on the prefix's last page ends)
             const int b = pa.slot, L = pa.L, Lp = L - 1, cols = pa.cols();
-            require_private(b, Lp);
-            const auto& pg = seq_pages_[b];
-            FS_HIP(hipMemcpyAsync(d_page_table_.as<int>() + (size_t)b * max_pages_, pg.data(), sizeof(int) * pg.size(), hipMemcpyHostToDevice, st_));
+            pages_.writable_from(b, Lp);
+            upload_row(b, st_, pages_.of(b));
             seq_len_[b] = Lp;
             SeqState ss = {};
             ss.pos = Lp; ss.prompt_L = L; ss.step = Lp;
@@ -1733,13 +1721,6 @@ class LM final : public LMBase {
         }
         FS_HIP(hipStreamSynchronize(st_));
         sess_flight_.clear();
-    }
-    void alloc_pages(int b, int n_tokens) {  // ensure_capacity without the upload: the row of a parked slot must keep pointing at the scratch page
-        FS_REQUIRE(n_tokens <= a_.max_seq_len, "sequence longer than max_seq_len");
-        const int need = (n_tokens + KV_PAGE - 1) / KV_PAGE;
-        auto& pg = seq_pages_[b];
-        FS_REQUIRE((int)free_pages_.size() >= need - (int)pg.size(), "KV page pool exhausted");
-        while ((int)pg.size() < need) pg.push_back(take_page());
     }
     void ensure_prefill2_buffers() {
         if (d2_pfx_.p) return;
@@ -1808,7 +1789,7 @@ class LM final : public LMBase {
                         static const int one = 1, zero = 0;
                         FS_HIP(hipMemcpyAsync(&state(b)->done, &one, sizeof(int), hipMemcpyHostToDevice, st_));
                         FS_HIP(hipMemcpyAsync(&state(b)->pos, &zero, sizeof(int), hipMemcpyHostToDevice, st_));
-                        FS_HIP(hipMemcpyAsync(d_page_table_.as<int>() + (size_t)b * max_pages_, &sess_scratch_, sizeof(int), hipMemcpyHostToDevice, st_));
+                        upload_row(b, st_, &sess_scratch_, 1);
                     }
                 }
             // (a slot that sampled <|im_end|> inside the chunk froze itself on the device; the host learns it below)
@@ -1869,15 +1850,19 @@ class LM final : public LMBase {
         if (!sess_active_) return;
         use_device();
         if (!sess_flight_.empty()) (void)hipEventSynchronize(ev_pf_);
+        // the page book's verdict on the session, asked once, while every owner and hold is still in place; it is raised below, when the
+        // session has been closed all the same
+        std::string bad_book;
+        try { pages_.check(); } catch (const std::exception& e) { bad_book = e.what(); }
+        // the holds of the adds still pending go first, in flight and queue order (the order pages return in decides who gets which next)
         for (auto* q : {&sess_flight_, &sess_queue_})
-            for (const PendingAdd& pa : *q) if (pa.tail >= 0) put_page(pa.tail);
+            for (const PendingAdd& pa : *q) if (pa.tail >= 0) pages_.drop_hold(pa.tail);
         tab_end(hid_);  // (the collector buffers of those adds were in hand: the books take them back)
         tab_end(sc_);
         sess_flight_.clear(); sess_queue_.clear();
-        for (int b = 0; b < B_; ++b) truncate(b, 0);
-        for (SessPrefix& px : sess_prefixes_) drop_prefix_pages(px);  // (live or not: the session's references end with it)
+        pages_.end_session();  // (the slots' pages, the prefixes' -- live or not: the session's references end with it -- and the scratch page)
+        std::fill(seq_len_.begin(), seq_len_.end(), 0);
         sess_prefixes_.clear();
-        put_page(sess_scratch_);
         SampleCfg cfg = base_cfg();
         FS_HIP(hipMemcpyAsync(d_cfg_.p, &cfg, sizeof(cfg), hipMemcpyHostToDevice, st_));
         FS_HIP(hipStreamSynchronize(st_));
@@ -1887,6 +1872,7 @@ class LM final : public LMBase {
         sess_released_frames_ = 0;
         if (rows) check_ctl({&d_rctl_s_, &d_rctl_f_}, nullptr, nullptr);  // (a session that ended on an error: reset only)
         if (sess_plock_.owns_lock()) sess_plock_.unlock();
+        if (!bad_book.empty()) throw Error(bad_book);
     }
 
     void generate_batch_sequential(const uint32_t* prompts, const int* lens, int n, int max_new_tokens, const fs_sampling& s, uint64_t seed,
@@ -2349,9 +2335,7 @@ class LM final : public LMBase {
         FS_HIP(hipMemset(kv_pool_.p, 0, kv_pool_.n));
         d_page_table_.alloc(sizeof(int) * (size_t)std::max(2 * B_ + 1, PR_MAX_ROWS) * max_pages_);  // + the staging rows of a session's joining requests (one group pass)
         FS_HIP(hipMemset(d_page_table_.p, 0, d_page_table_.n));
-        for (int p = n_pages_ - 1; p >= 0; --p) free_pages_.push_back(p);
-        page_refs_.assign(n_pages_, 0);
-        seq_pages_.assign(B_, {});
+        pages_.init(n_pages_, B_, KV_PAGE, a_.max_seq_len);
         seq_len_.assign(B_, 0);
         fast_len_.assign(B_, 0);
         // fast-decoder KV: one page per (layer, sequence); its page table is a single zero
@@ -2439,44 +2423,24 @@ class LM final : public LMBase {
     }
 
     // ---- KV paging (host side; the device only ever sees the page table)
+    // Who holds which page is the book's business (fs_kv_pages.h: pages are reference counted -- a session's shared prefix pages have the
+    // prefix + every slot on it as owners -- and outside sessions every page has one owner); the engine uploads rows and counts tokens.
     void ensure_capacity(int b, int n_tokens) {
-        FS_REQUIRE(n_tokens <= a_.max_seq_len, "sequence longer than max_seq_len");
-        const int need = (n_tokens + KV_PAGE - 1) / KV_PAGE;
-        auto& pg = seq_pages_[b];
-        if ((int)pg.size() >= need) return;
-        while ((int)pg.size() < need) {
-            FS_REQUIRE(!free_pages_.empty(), "KV page pool exhausted");
-            pg.push_back(take_page());
-        }
-        FS_HIP(hipMemcpyAsync(d_page_table_.as<int>() + (size_t)b * max_pages_, pg.data(), sizeof(int) * pg.size(),
-                              hipMemcpyHostToDevice, st_));
-        FS_HIP(hipStreamSynchronize(st_));  // pg may be reallocated by the next call
+        if (!pages_.grow(b, n_tokens)) return;
+        upload_row(b, st_, pages_.of(b));
+        FS_HIP(hipStreamSynchronize(st_));  // the list may be reallocated by the next call
     }
     void truncate(int b, int pos) {  // keep the first `pos` tokens (dual_ar.rs:392-404)
-        const int keep = (pos + KV_PAGE - 1) / KV_PAGE;
-        auto& pg = seq_pages_[b];
-        while ((int)pg.size() > keep) { put_page(pg.back()); pg.pop_back(); }
+        pages_.truncate(b, pos);
         seq_len_[b] = pos;
     }
-    // pages are reference counted (a session's shared prefix pages have the prefix + every slot on it as owners); a page goes back to the
-    // free list when its last owner drops it.  Outside sessions every page has one owner and this is the plain free list.
-    int take_page() {
-        const int p = free_pages_.back();
-        free_pages_.pop_back();
-        page_refs_[p] = 1;
-        return p;
+    // the one copy of page ids into the device's page table, from its row `row` on (rows >= B_: the staging rows of a joining pass), on
+    // stream st: a sequence's or a prefix's list, the scratch page of a parked slot, or the rows of a group pass side by side.  The
+    // source must outlive the copy.
+    void upload_row(int row, hipStream_t st, const int* ids, size_t n) {
+        FS_HIP(hipMemcpyAsync(d_page_table_.as<int>() + (size_t)row * max_pages_, ids, sizeof(int) * n, hipMemcpyHostToDevice, st));
     }
-    void put_page(int p) {
-        FS_REQUIRE(page_refs_[p] > 0, "KV page released twice");
-        if (--page_refs_[p] == 0) free_pages_.push_back(p);
-    }
-    // the ownership invariant: nothing writes a page with more than one owner.  Slot b writes positions >= pos0 (its prefill starts there,
-    // its pad rows and decode steps lie beyond), so every page from pos0's on must be the slot's alone.
-    void require_private(int b, int pos0) {
-        const auto& pg = seq_pages_[b];
-        for (size_t j = (size_t)(pos0 / KV_PAGE); j < pg.size(); ++j)
-            FS_REQUIRE(page_refs_[pg[j]] == 1, "a session slot would write a shared KV page");
-    }
+    void upload_row(int row, hipStream_t st, const std::vector<int>& ids) { upload_row(row, st, ids.data(), ids.size()); }
 
     // Runs the next `n` prompt tokens (columns state->step ..) of the staged prompt through the slow transformer,
     // appending their K/V.  Afterwards x(b) holds the pre-norm hidden state of the last processed token.
@@ -3076,8 +3040,8 @@ class LM final : public LMBase {
     }
     size_t page_elems_ = 0;
     DevBuf kv_pool_, fast_pool_, d_page_table_, d_zero_table_;
-    std::vector<int> free_pages_, seq_len_, fast_len_;
-    std::vector<std::vector<int>> seq_pages_;
+    KvPages pages_;  // the slow KV pool's book: free list, reference counts, the sequences' and prefixes' page lists, the holds
+    std::vector<int> seq_len_, fast_len_;
     // activations / state
     DevBuf d_x_, d_xf_, d_q_, d_part_, d_act_, d_logits_slow_, d_logits_fast_, d_state_, d_cfg_, d_rng_, d_prompt_, d_out_;
     RepPenBufs rp_, srp_, rrp_;  // repetition-penalty state: the batch-1 generator's (1 row), the per-slot samplers' [max_batch] (allocated with d_scfg_), the request rows' [PR_MAX_ROWS] (ensure_rows)
@@ -3108,10 +3072,9 @@ class LM final : public LMBase {
     std::unique_lock<PersistLock> sess_plock_;
     std::vector<int> sess_left_, sess_pos_;
     std::vector<SeqState> sess_hs_;
-    int sess_scratch_ = 0;
+    int sess_scratch_ = 0;  // (a hold of the page book's; a member because parked slots' rows are uploaded from here)
     uint64_t sess_released_frames_ = 0;
     std::vector<SessPrefix> sess_prefixes_;
-    std::vector<int> page_refs_;                       // owners of every slow KV page (0: on the free list)
     std::vector<SeqState> sess_stage_pos0_;            // a group pass's member start positions (pos; rope_off 0)
     std::vector<int> sess_stage_copy_;
     DevBuf d2_seqpos_, d2_copy_;                       // device copies of the two above: member start states / tail-copy page pairs
