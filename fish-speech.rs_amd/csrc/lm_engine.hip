@@ -28,6 +28,7 @@
 
 #include "fs_common.h"
 #include "fs_kv_pages.h"
+#include "fs_prefill_plan.h"
 #include "fs_synth.h"
 #include "lm_kernels.h"
 #include "lm_persist.h"
@@ -194,6 +195,45 @@ constexpr int kRowsCap = 2048; // row capacity of the MFMA row buffers: prompt t
                                // left-padded static-batch prompts)
 constexpr int kPartRows = 512; // rows of the chunked-attention partials buffer (static-batch steps; prefill passes when head_dim != 64)
 
+// One set of the MFMA row path's activation buffers (kRowsCap rows), with the stream its passes run on and the prompt staged for them.
+// A handle has two: the main lane on the engine stream -- its buffers are also the static-batch decode steps', whose captured graphs
+// hold their addresses, so a lane allocates once and never again -- and the join lane on a session's prefill stream.
+struct PrefillLane {
+    hipStream_t& st;
+    DevBuf x, q, slab, a, a2, ss, c, part;  // RowsCtx: X, Q, P, A, A2, ss, C, part
+    DevBuf prompt;                          // the staged prompt [C + 1][cols] (the join lane's group passes: [S][C + 1][Lp])
+    RowsCtx base = {};                      // what no pass changes of a RowsCtx
+    explicit PrefillLane(hipStream_t& s) : st(s) {}
+    void ensure(const fs_model_args& m, int down_split, int n_chunks, const float* cos_t, const float* sin_t) {
+        if (x.p) return;
+        x.alloc(sizeof(float) * kRowsCap * m.dim);
+        q.alloc(sizeof(float) * kRowsCap * m.dim);
+        slab.alloc(sizeof(float) * down_split * kRowsCap * m.dim);
+        a.alloc(sizeof(uint16_t) * 2 * kRowsCap * m.dim);
+        a2.alloc(sizeof(uint16_t) * 2 * kRowsCap * m.dim);
+        ss.alloc(sizeof(float) * kRowsCap * (m.dim / 16));
+        c.alloc(sizeof(uint16_t) * 2 * kRowsCap * m.intermediate_size);
+        part.alloc(sizeof(float) * kPartRows * (size_t)m.n_head * n_chunks * (m.head_dim + 2));
+        for (DevBuf* bf : {&x, &a, &a2, &ss, &c, &part}) FS_HIP(hipMemsetAsync(bf->p, 0, bf->n, st));
+        base.X = x.as<float>(); base.Q = q.as<float>(); base.part = part.as<float>(); base.P = slab.as<float>();
+        base.Mcap = kRowsCap; base.part_rows = kPartRows; base.down_split = down_split;
+        base.A = a.as<uint16_t>(); base.C = c.as<uint16_t>();
+        base.A2 = a2.as<uint16_t>(); base.ss = ss.as<float>();
+        base.cos_t = cos_t; base.sin_t = sin_t;
+        base.n_chunks_max = n_chunks; base.nc_launch = n_chunks;
+    }
+    RowsCtx ctx(const SeqState* state, int pos_step, int pt_stride) const {
+        RowsCtx r = base;
+        r.state = state; r.pos_step = pos_step; r.pt_stride = pt_stride;
+        return r;
+    }
+    // the prompt of the lane's next pass, on its stream (the source must outlive the copy; a pass that still reads the buffer has been waited for)
+    void stage_prompt(const uint32_t* src, size_t n) {
+        if (prompt.n < sizeof(uint32_t) * n) prompt.alloc(sizeof(uint32_t) * n);
+        FS_HIP(hipMemcpyAsync(prompt.p, src, sizeof(uint32_t) * n, hipMemcpyHostToDevice, st));
+    }
+};
+
 }  // namespace
 
 template <typename WT>
@@ -336,7 +376,7 @@ class LM final : public LMBase {
         std::vector<float> lg, hd;
         for (int b = 0; b < B; ++b) {
             ensure_capacity(b, seq_len_[b] + L);
-            FS_HIP(hipMemcpyAsync(d_prompt_.p, toks + (size_t)b * C1 * L, sizeof(uint32_t) * C1 * L, hipMemcpyHostToDevice, st_));
+            FS_HIP(hipMemcpyAsync(main_.prompt.p, toks + (size_t)b * C1 * L, sizeof(uint32_t) * C1 * L, hipMemcpyHostToDevice, st_));
             SeqState s = {};
             s.pos = seq_len_[b]; s.rope_off = input_pos - seq_len_[b]; s.prompt_L = L;
             FS_HIP(hipMemcpyAsync(state(b), &s, sizeof(s), hipMemcpyHostToDevice, st_));
@@ -592,7 +632,7 @@ class LM final : public LMBase {
         SeqState ss = {};
         ss.pos = n_cached; ss.prompt_L = L;
         FS_HIP(hipMemcpyAsync(state(0), &ss, sizeof(ss), hipMemcpyHostToDevice, st_));
-        FS_HIP(hipMemcpyAsync(d_prompt_.p, prompt, sizeof(uint32_t) * C1 * L, hipMemcpyHostToDevice, st_));
+        FS_HIP(hipMemcpyAsync(main_.prompt.p, prompt, sizeof(uint32_t) * C1 * L, hipMemcpyHostToDevice, st_));
         launch_reppen_reset(rp_.view(0), C, a_.codebook_size, st_);
         clear_fast();
 
@@ -601,7 +641,7 @@ class LM final : public LMBase {
         // prefill: the first L-1 prompt tokens (MFMA chunks of <= 64 tokens for bf16 weights; sequential token steps for
         // f32 parity handles), then the last prompt token runs as the first frame
         prefill_tokens(0, L - 1, /*use_graph=*/true);
-        LmKernels<WT>::embed(d_, tok_emb_, cb_emb_, C, a_.codebook_size, d_cfg_.as<SampleCfg>(), d_prompt_.as<uint32_t>(), state(0),
+        LmKernels<WT>::embed(d_, tok_emb_, cb_emb_, C, a_.codebook_size, d_cfg_.as<SampleCfg>(), main_.prompt.as<uint32_t>(), state(0),
                              x(0), st_);
         GenRun g;
         g.T0 = n_cached + L; g.n_iter = n_iter; g.cb = cb; g.cb_user = cb_user;
@@ -835,28 +875,22 @@ class LM final : public LMBase {
             ss.prompt_L = Lmax;
             FS_HIP(hipMemcpyAsync(state(0), &ss, sizeof(ss), hipMemcpyHostToDevice, st_));
             const int per_pass = std::max(1, kRowsCap / Lp);
-            for (int b0 = 0; b0 < B; b0 += per_pass) {
-                const int S = std::min(per_pass, B - b0), M = S * Lp;
-                RowsCtx c = rows_ctx(state(0), /*pos_step=*/1, /*pt_stride=*/max_pages_);
-                c.seq_rows = Lp;
-                RowKernels<WT>::prefill_embed(d_, tok_emb_, cb_emb_, C, a_.codebook_size, d_cfg_.as<SampleCfg>(),
-                                             d_bprompt_.as<uint32_t>() + pstride * b0, state(0), M, d_pfx_.as<float>(), st_, Lp, pstride);
-                for (int l = 0; l < a_.n_layer; ++l) RowKernels<WT>::rows_layer(d_, M, c, slow_[l], slow_kv(l, b0), l == 0, st_);
-            }
+            for (int b0 = 0; b0 < B; b0 += per_pass)
+                launch_group_pass(main_, d_bprompt_.as<uint32_t>() + pstride * b0, std::min(per_pass, B - b0), Lp, pstride, state(0), b0, nullptr, n_chunks_);
             FS_HIP(hipStreamSynchronize(st_));
             for (int b = 0; b < B; ++b) seq_len_[b] = Lp;
         } else {
             for (int b = 0; b < B; ++b) {
-                FS_HIP(hipMemcpyAsync(d_prompt_.p, padded.data() + pstride * b, sizeof(uint32_t) * pstride, hipMemcpyHostToDevice, st_));
+                FS_HIP(hipMemcpyAsync(main_.prompt.p, padded.data() + pstride * b, sizeof(uint32_t) * pstride, hipMemcpyHostToDevice, st_));
                 SeqState ss = {};
                 ss.prompt_L = Lmax;
                 FS_HIP(hipMemcpyAsync(state(b), &ss, sizeof(ss), hipMemcpyHostToDevice, st_));
                 prefill_tokens(b, Lp, /*use_graph=*/false);
-                FS_HIP(hipStreamSynchronize(st_));  // d_prompt_ is reused by the next row
+                FS_HIP(hipStreamSynchronize(st_));  // main_.prompt is reused by the next row
                 seq_len_[b] = Lp;
             }
         }
-        // first-frame inputs: the rows of d_pfx_ are scratch during prefill, so the last prompt column of every row is
+        // first-frame inputs: the rows of main_.x are scratch during prefill, so the last prompt column of every row is
         // embedded only now (through the state's `cur` slots)
         for (int b = 0; b < B; ++b) {
             const int L = lens[b];
@@ -868,7 +902,7 @@ class LM final : public LMBase {
             for (int r = 0; r < C1; ++r) ss.cur[r] = src[o2 + (size_t)r * L + (L - 1)];
             FS_HIP(hipMemcpyAsync(state(b), &ss, sizeof(ss), hipMemcpyHostToDevice, st_));
             LmKernels<WT>::embed(d_, tok_emb_, cb_emb_, C, a_.codebook_size, d_cfg_.as<SampleCfg>(), nullptr, state(b),
-                                 d_pfx_.as<float>() + (size_t)b * a_.dim, st_);
+                                 main_.x.as<float>() + (size_t)b * a_.dim, st_);
             FS_HIP(hipStreamSynchronize(st_));
         }
         auto launch_frame = [&](long long it_) {
@@ -1047,7 +1081,7 @@ class LM final : public LMBase {
         sess_pf_ms_ = 0.0;
         sess_timed_ = false;
         for (int b = 0; b < B_; ++b) park_slot(b, m.rows);
-        FS_HIP(hipMemsetAsync(d_pfx_.p, 0, sizeof(float) * (size_t)B_ * a_.dim, st_));
+        FS_HIP(hipMemsetAsync(main_.x.p, 0, sizeof(float) * (size_t)B_ * a_.dim, st_));
         FS_HIP(hipStreamSynchronize(st_));
         stats_ = {};
         if (m.rows) sess_plock_ = std::move(rows_lock);
@@ -1136,10 +1170,10 @@ class LM final : public LMBase {
         const int nfull = P / KV_PAGE, end = L + n_iter - 1;  // the prefix's full pages are shared; positions < end keep their K/V
         const KvPages::Share shared{prefixed ? pages_.prefix_owner(r.prefix_id) : -1, nfull};
         if (!pages_.room(b, end, shared).fits) return -1;  // (a free slot that still holds pages is an error, raised here)
-        ensure_prefill2_buffers();
+        ensure_join_lane();
         // 3. the queue entry, complete but for what is taken below
         PendingAdd pa;
-        pa.slot = b; pa.L = L; pa.n_iter = n_iter; pa.start = P; pa.prefix = r.prefix_id; pa.traced = r.traced;
+        pa.slot = pa.owner = b; pa.L = L; pa.n_iter = n_iter; pa.start = P; pa.prefix = r.prefix_id; pa.traced = r.traced;
         pa.prompt.assign(r.prompt, r.prompt + (size_t)C1 * r.L);
         pa.has_seed = r.seed || scored || r.traced;
         pa.seed = r.seed ? *r.seed : sess_seed_ + (uint64_t)sess_adds_;
@@ -1305,21 +1339,19 @@ class LM final : public LMBase {
     // prefix's P, tail = the prefix's partly filled last page, held until the copy has run) or a prefix's own pass (create: prompt = its P
     // columns, all of them prefilled into the prefix's pages; slot -1) or a prefix's import (create and import_kv: blob = the payload of
     // fs_lm_session_prefix_import, copied and scattered into the prefix's pages; no prompt, nothing runs through the slow transformer)
-    struct PendingAdd {
-        int slot = -1, L = 0, n_iter = 0, order = 0, start = 0, prefix = -1, tail = -1;
-        bool create = false, import_kv = false;
+    // What the choice of a pass reads of it is its PrefillMember (fs_prefill_plan.h: L, n_iter, start, create, import_kv, has_seed -- a
+    // sampler seed of its own, fs_lm_session_add_ex -- and owner, whose pages its pass writes: the slot, or the prefix being created).
+    struct PendingAdd : PrefillMember {
+        int slot = -1, order = 0, prefix = -1, tail = -1;
         std::vector<uint8_t> blob;
-        bool has_cfg = false, has_seed = false;  // fs_lm_session_add_ex: the slot's own settings / sampler seed
+        bool has_cfg = false;  // fs_lm_session_add_ex: the slot's own settings
         SampleCfg cfg = {};
         uint64_t seed = 0;
         SlotBuf hid;                       // fs_lm_session_add_hidden: the slot's row buffer [cap][dim], handed to the device table at activation
         SlotBuf sc;                        // fs_lm_session_add_scored: the slot's records + targets buffer, likewise (both in hand until then)
         std::vector<uint32_t> sc_targets;  // ... and the staged targets [n_iter][C + 1], copied into the buffer then
         bool traced = false;               // fs_lm_session_add_traced: `sc` is the slot's records + token rows; its table entry has no targets
-        std::vector<uint32_t> prompt;
-        int rows() const { return import_kv ? 0 : (create ? L : L - start - 1); }   // tokens this member runs through the slow transformer
-        int cols() const { return create ? L : L - start; }       // columns of `prompt`
-        int end() const { return create ? L : L + n_iter - 1; }   // positions whose K/V the member keeps
+        std::vector<uint32_t> prompt;      // [C + 1][cols()]
     };
     // a session's shared prefix; its pages are those of owner pages_.prefix_owner(id) (one reference each, held until released or the
     // session ends; slots add their own on the full ones).  pending: its own pass has still to be activated (a release then waits for that)
@@ -1339,7 +1371,7 @@ class LM final : public LMBase {
     // a pending prefix of P positions: its pages taken, its creating pass queued (`pa` holds what the pass moves: the prompt, or an
     // imported payload).  Returns its id, or -1 when the page pool is short right now.
     int queue_prefix(int P, PendingAdd pa) {
-        ensure_prefill2_buffers();
+        ensure_join_lane();
         if (!pages_.room(KvPages::kNewOwner, P).fits) return -1;
         SessPrefix px;
         px.P = P; px.live = true; px.pending = true;
@@ -1347,7 +1379,7 @@ class LM final : public LMBase {
         const int owner = pages_.add_prefix();
         FS_REQUIRE(owner == pages_.prefix_owner((int)sess_prefixes_.size() - 1), "prefix ids and the page book's owners are out of step");
         pages_.grow(owner, P);
-        pa.create = true; pa.L = P; pa.prefix = (int)sess_prefixes_.size() - 1;
+        pa.create = true; pa.L = P; pa.prefix = (int)sess_prefixes_.size() - 1; pa.owner = owner;
         sess_queue_.push_back(std::move(pa));
         return (int)sess_prefixes_.size() - 1;
     }
@@ -1451,18 +1483,17 @@ class LM final : public LMBase {
     // the pass of the imports at the head of the (sorted) queue: per import one host-to-device copy into the staging buffer and one
     // k_kv_rows_scatter into its pages, on the prefill stream; activated like a creating pass (pa.create).  No counter of a transformer
     // pass moves.
-    void launch_import_pass() {
-        size_t n = 0, total = 0, n_ids = 0;
-        while (n < sess_queue_.size() && sess_queue_[n].import_kv) {  // (everything is checked before the first launch)
-            const SessPrefix& px = sess_prefixes_[sess_queue_[n].prefix];
-            const int owner = pages_.prefix_owner(sess_queue_[n].prefix);
-            FS_REQUIRE(sess_queue_[n].blob.size() == prefix_payload_bytes(px.P) && (int)pages_.of(owner).size() * KV_PAGE >= px.P,
+    void launch_import_pass(size_t n) {
+        size_t total = 0, n_ids = 0;
+        for (size_t i = 0; i < n; ++i) {  // (everything is checked before the first launch)
+            const SessPrefix& px = sess_prefixes_[sess_queue_[i].prefix];
+            const int owner = pages_.prefix_owner(sess_queue_[i].prefix);
+            FS_REQUIRE(sess_queue_[i].blob.size() == prefix_payload_bytes(px.P) && (int)pages_.of(owner).size() * KV_PAGE >= px.P,
                        "prefix import: payload / pages do not match P");
             // (slots already queued on this prefix hold references on its pages too; none of them reads or writes one before this pass)
             FS_REQUIRE(pages_.intact(owner), "prefix import: a page of the prefix is not held");
-            total += sess_queue_[n].blob.size();
+            total += sess_queue_[i].blob.size();
             n_ids += pages_.of(owner).size();
-            ++n;
         }
         kvb_reserve(total, n_ids);
         std::vector<int>& ids = sess_stage_imp_pages_;  // (alive until the pass has been activated)
@@ -1484,7 +1515,6 @@ class LM final : public LMBase {
             off += pa.blob.size();
             id_off += pages_.of(pages_.prefix_owner(pa.prefix)).size();
         }
-        pass_launched(n);
     }
     // the pass of the first n queued entries is on the prefill stream: its end is marked (timing event, then the event activate_pending
     // waits for) and the entries are in flight
@@ -1506,115 +1536,69 @@ class LM final : public LMBase {
     // one launch for the pass, in stream order ahead of it).
     void flush_pending() {
         if (sess_queue_.empty() || !sess_flight_.empty()) return;
-        const int C1 = a_.num_codebooks + 1, C = a_.num_codebooks;
-        std::stable_sort(sess_queue_.begin(), sess_queue_.end(),
-                         [](const PendingAdd& x, const PendingAdd& y) {
-                             if (x.import_kv != y.import_kv) return x.import_kv;
-                             return x.create != y.create ? x.create : x.rows() > y.rows();
-                         });
-        const bool flash = a_.head_dim == 64;
-        size_t i = 0;
-        int S = 1;
+        // which pass (fs_prefill_plan.h: the order of the queue, the kind of the pass, its members -- the first ps.n of the ordered queue)
+        const PrefillPlan plan = plan_prefill({sess_queue_.begin(), sess_queue_.end()}, pages_, {kRowsCap, B_, a_.max_seq_len, a_.head_dim == 64});
+        std::vector<PendingAdd> ordered;
+        ordered.reserve(sess_queue_.size());
+        for (int j : plan.order) ordered.push_back(std::move(sess_queue_[(size_t)j]));
+        sess_queue_.swap(ordered);
+        const PrefillPass& ps = plan.pass;
         FS_HIP(hipEventRecord(ev_pft_[0], st_pf_));
         sess_timed_ = true;
-        if (sess_queue_[0].import_kv) { launch_import_pass(); return; }
-        {
-            const int Lp = sess_queue_[i].rows();  // the longest of this pass (sorted): tokens that run through the slow transformer
-            if (Lp < 1) {                          // only single-token prompts are left: no pass, they go live at the next activation
-                launch_tail_copies(sess_queue_.begin(), sess_queue_.end());
-                for (const PendingAdd& pa : sess_queue_) sess_count_[2] += pa.start;
-                pass_launched(sess_queue_.size());
-                return;
-            }
-            if (flash && Lp <= kRowsCap) {
-                const int fit = std::max(1, std::min(kRowsCap / Lp, B_));
-                // pad positions write K/V up to start + Lp: every member must own pages that far (bounded: they go back with the slot,
-                // or at activation for a prefix).  The extra pages are counted CUMULATIVELY over the group -- checked per member,
-                // several short-budget members could each pass and the growth would then throw in the middle of the flush with the
-                // queue half consumed
-                int need_sum = 0;
-                auto extra = [&](const PendingAdd& pa) { return pages_.room(member_owner(pa), pad_end(pa, Lp), {}, need_sum); };
-                const bool create = sess_queue_[i].create;
-                const KvPages::Room first = extra(sess_queue_[i]);
-                need_sum = first.cost;
-                // A member admitted with a sampler seed of its own (fs_lm_session_add_ex) is prefilled in a pass of its own: a group pass
-                // rounds differently from a single one (other tiling: ~5e-4 on the first logits), and whoever names a seed asks for codes
-                // that are a function of the request alone, not of what happened to be queued with it
-                while (i + S < sess_queue_.size() && S < fit && sess_queue_[i + S].rows() >= 1 && sess_queue_[i + S].create == create &&
-                       !sess_queue_[i].has_seed && !sess_queue_[i + S].has_seed &&
-                       sess_queue_[i + S].start + Lp <= a_.max_seq_len) {
-                    const KvPages::Room more = extra(sess_queue_[i + S]);
-                    if (!more.fits) break;
-                    need_sum += more.cost;
-                    ++S;
-                }
-                if (!first.fits) S = 1;  // (the first member alone does not fit a group pass either: its own pages were reserved by session_admit)
-            }
-            launch_tail_copies(sess_queue_.begin() + i, sess_queue_.begin() + i + S);
-            if (S == 1 || !flash) {  // one sequence, passes of <= kRowsCap rows
-                const PendingAdd& pa = sess_queue_[i];
-                if (!pa.create) pages_.writable_from(pa.slot, pa.start);
-                upload_row(B_, st_pf_, pages_.of(member_owner(pa)));
-                const int cols = pa.cols();
-                if (d2_prompt_.n < sizeof(uint32_t) * (size_t)C1 * cols) d2_prompt_.alloc(sizeof(uint32_t) * (size_t)C1 * cols);
-                FS_HIP(hipMemcpyAsync(d2_prompt_.p, pa.prompt.data(), sizeof(uint32_t) * (size_t)C1 * cols, hipMemcpyHostToDevice, st_pf_));
-                sess_stage_ = SeqState{};
-                sess_stage_.prompt_L = cols;
-                sess_stage_.pos = pa.start;  // (a prefixed member: its body's first column sits at position P)
-                FS_HIP(hipMemcpyAsync(state(B_), &sess_stage_, sizeof(SeqState), hipMemcpyHostToDevice, st_pf_));
-                RowsCtx c = rows_ctx2(state(B_), /*pos_step=*/1, /*pt_stride=*/0);
-                for (int done = 0; done < Lp;) {
-                    const int M = std::min(flash ? kRowsCap : kPartRows, Lp - done);
-                    c.nc_launch = chunk_bucket(pa.start + done + M);
-                    RowKernels<WT>::prefill_embed(d_, tok_emb_, cb_emb_, C, a_.codebook_size, d_cfg_.as<SampleCfg>(),
-                                                 d2_prompt_.as<uint32_t>(), state(B_), M, d2_pfx_.as<float>(), st_pf_);
-                    for (int l = 0; l < a_.n_layer; ++l) RowKernels<WT>::rows_layer(d_, M, c, slow_[l], slow_kv(l, B_), l == 0, st_pf_);
-                    RowKernels<WT>::rows_finish(d_, M, c, nullptr, st_pf_);
-                    launch_advance_n(state(B_), M, st_pf_);
-                    done += M;
-                }
-            } else {
-                const size_t pstride = (size_t)C1 * Lp;
-                std::vector<uint32_t>& padded = sess_stage_prompts_;  // (members: alive until the pass has been activated)
-                std::vector<int>& rows = sess_stage_rows_;
-                std::vector<SeqState>& pos0 = sess_stage_pos0_;
-                padded.assign(pstride * S, 0u);
-                rows.assign((size_t)S * max_pages_, sess_scratch_);
-                pos0.assign(S, SeqState{});
-                int max_start = 0;
-                for (int s = 0; s < S; ++s) {
-                    PendingAdd& pa = sess_queue_[i + s];
-                    pages_.grow(member_owner(pa), pad_end(pa, Lp));  // (pad rows; a prefix's are trimmed at activation)
-                    if (!pa.create) pages_.writable_from(pa.slot, pa.start);
-                    const int n = pa.rows(), cols = pa.cols();
-                    for (int r = 0; r < C1; ++r) std::memcpy(&padded[pstride * s + (size_t)r * Lp], &pa.prompt[(size_t)r * cols], sizeof(uint32_t) * n);
-                    const auto& pg = pages_.of(member_owner(pa));
-                    std::copy(pg.begin(), pg.end(), rows.begin() + (size_t)s * max_pages_);
-                    pos0[s].pos = pa.start;
-                    max_start = std::max(max_start, pa.start);
-                }
-                if (d2_prompt_.n < sizeof(uint32_t) * padded.size()) d2_prompt_.alloc(sizeof(uint32_t) * padded.size());
-                FS_HIP(hipMemcpyAsync(d2_prompt_.p, padded.data(), sizeof(uint32_t) * padded.size(), hipMemcpyHostToDevice, st_pf_));
-                upload_row(B_, st_pf_, rows);
-                sess_stage_ = SeqState{};
-                sess_stage_.prompt_L = Lp;
-                FS_HIP(hipMemcpyAsync(state(B_), &sess_stage_, sizeof(SeqState), hipMemcpyHostToDevice, st_pf_));
-                RowsCtx c = rows_ctx2(state(B_), /*pos_step=*/1, /*pt_stride=*/max_pages_);
-                c.seq_rows = Lp;
-                c.nc_launch = chunk_bucket(max_start + Lp);
-                if (max_start > 0) {  // (members that all start at 0 keep the plain group pass)
-                    FS_HIP(hipMemcpyAsync(d2_seqpos_.p, pos0.data(), sizeof(SeqState) * S, hipMemcpyHostToDevice, st_pf_));
-                    c.seq_states = d2_seqpos_.as<SeqState>();
-                }
-                const int M = S * Lp;
-                RowKernels<WT>::prefill_embed(d_, tok_emb_, cb_emb_, C, a_.codebook_size, d_cfg_.as<SampleCfg>(), d2_prompt_.as<uint32_t>(), state(B_), M,
-                                             d2_pfx_.as<float>(), st_pf_, Lp, pstride);
-                for (int l = 0; l < a_.n_layer; ++l) RowKernels<WT>::rows_layer(d_, M, c, slow_[l], slow_kv(l, B_), l == 0, st_pf_);
-            }
+        if (ps.kind != PrefillPass::Imports) launch_tail_copies(sess_queue_.begin(), sess_queue_.begin() + ps.n);
+        switch (ps.kind) {
+        case PrefillPass::Imports: launch_import_pass((size_t)ps.n); break;
+        case PrefillPass::NoRows: break;  // only one-column bodies are left: no pass, they go live at the next activation
+        case PrefillPass::Single: join_single(sess_queue_[0]); break;
+        case PrefillPass::Group: join_group(ps); break;
         }
-        ++sess_count_[0];
-        for (int s = 0; s < S; ++s) { sess_count_[1] += sess_queue_[i + s].rows(); sess_count_[2] += sess_queue_[i + s].create ? 0 : sess_queue_[i + s].start; }
-        pass_launched((size_t)S);
+        // (an import moves no counter of a transformer pass: it runs no row and reuses nothing)
+        sess_count_[0] += ps.kind == PrefillPass::Single || ps.kind == PrefillPass::Group;
+        for (int s = 0; s < ps.n; ++s) { sess_count_[1] += sess_queue_[s].rows(); sess_count_[2] += sess_queue_[s].create ? 0 : sess_queue_[s].start; }
+        pass_launched((size_t)ps.n);
+    }
+    // one sequence on the join lane: its page list in the staging row B_, its columns staged, the staging state at its first position
+    void join_single(const PendingAdd& pa) {
+        if (!pa.create) pages_.writable_from(pa.slot, pa.start);
+        upload_row(B_, st_pf_, pages_.of(pa.owner));
+        const int cols = pa.cols();
+        join_.stage_prompt(pa.prompt.data(), (size_t)(a_.num_codebooks + 1) * cols);
+        sess_stage_ = SeqState{};
+        sess_stage_.prompt_L = cols;
+        sess_stage_.pos = pa.start;  // (a prefixed member: its body's first column sits at position P)
+        FS_HIP(hipMemcpyAsync(state(B_), &sess_stage_, sizeof(SeqState), hipMemcpyHostToDevice, st_pf_));
+        launch_seq_pass(join_, state(B_), B_, pa.start, pa.rows());
+    }
+    // the first ps.n queued members side by side on the join lane, right-padded to ps.Lp rows: page lists in the staging rows B_ .., each
+    // grown to where its pad rows write (the plan has asked the book for exactly this)
+    void join_group(const PrefillPass& ps) {
+        const int C1 = a_.num_codebooks + 1, S = ps.n, Lp = ps.Lp;
+        const size_t pstride = (size_t)C1 * Lp;
+        std::vector<uint32_t>& padded = sess_stage_prompts_;  // (members: alive until the pass has been activated)
+        std::vector<int>& rows = sess_stage_rows_;
+        std::vector<SeqState>& pos0 = sess_stage_pos0_;
+        padded.assign(pstride * S, 0u);
+        rows.assign((size_t)S * max_pages_, sess_scratch_);
+        pos0.assign(S, SeqState{});
+        for (int s = 0; s < S; ++s) {
+            const PendingAdd& pa = sess_queue_[s];
+            pages_.grow(pa.owner, ps.pad_end[s]);  // (pad rows; a prefix's are trimmed at activation)
+            if (!pa.create) pages_.writable_from(pa.slot, pa.start);
+            const int n = pa.rows(), cols = pa.cols();
+            for (int r = 0; r < C1; ++r) std::memcpy(&padded[pstride * s + (size_t)r * Lp], &pa.prompt[(size_t)r * cols], sizeof(uint32_t) * n);
+            const auto& pg = pages_.of(pa.owner);
+            std::copy(pg.begin(), pg.end(), rows.begin() + (size_t)s * max_pages_);
+            pos0[s].pos = pa.start;
+        }
+        join_.stage_prompt(padded.data(), padded.size());
+        upload_row(B_, st_pf_, rows);
+        sess_stage_ = SeqState{};
+        sess_stage_.prompt_L = Lp;
+        FS_HIP(hipMemcpyAsync(state(B_), &sess_stage_, sizeof(SeqState), hipMemcpyHostToDevice, st_pf_));
+        // (members that all start at 0 keep the plain group pass)
+        if (ps.max_start > 0) FS_HIP(hipMemcpyAsync(d2_seqpos_.p, pos0.data(), sizeof(SeqState) * S, hipMemcpyHostToDevice, st_pf_));
+        launch_group_pass(join_, join_.prompt.as<uint32_t>(), S, Lp, pstride, state(B_), B_, ps.max_start > 0 ? d2_seqpos_.as<SeqState>() : nullptr,
+                          chunk_bucket(ps.max_start + Lp));
     }
     // copy-on-write of the partly filled last page of a prefix into the joining slot's first private page, for all members of a pass
     // that need it: ONE k_kv_page_copy launch over every slow layer's K and V pools, on the prefill stream ahead of the pass
@@ -1636,9 +1620,6 @@ class LM final : public LMBase {
         launch_kv_page_copy(kv_pool_.p, 2 * a_.n_layer, (size_t)n_pages_ * page_bytes, page_bytes, d2_copy_.as<int>(), n, st_pf_);
         sess_count_[3] += n;
     }
-    // whose pages a queued request's pass writes, and how far a pass whose longest member runs Lp tokens makes it write
-    int member_owner(const PendingAdd& pa) const { return pa.create ? pages_.prefix_owner(pa.prefix) : pa.slot; }
-    static int pad_end(const PendingAdd& pa, int Lp) { return std::max(pa.end(), pa.start + Lp); }
     // the requests whose prefill is in flight (if it has finished, or after waiting for it) become live slots; called between steps only
     void activate_pending(bool wait) {
         if (sess_flight_.empty()) return;
@@ -1703,7 +1684,7 @@ class LM final : public LMBase {
                     launch_reppen_reset(srp_.view(b), a_.num_codebooks, a_.codebook_size, st_);
                 }
                 LmKernels<WT>::embed(d_, tok_emb_, cb_emb_, a_.num_codebooks, a_.codebook_size, d_cfg_.as<SampleCfg>(), nullptr, state(b),
-                                     d_pfx_.as<float>() + (size_t)b * a_.dim, st_);
+                                     main_.x.as<float>() + (size_t)b * a_.dim, st_);
             }
             if (pa.hid.p) tab_activate(hid_, b, pa.hid);  // (its first iteration is the step that runs its last prompt position)
             if (pa.sc.p && pa.traced) {  // a traced slot: the device entry is a scoring slot's WITHOUT targets (the book's own keeps the pointer:
@@ -1722,23 +1703,15 @@ class LM final : public LMBase {
         FS_HIP(hipStreamSynchronize(st_));
         sess_flight_.clear();
     }
-    void ensure_prefill2_buffers() {
-        if (d2_pfx_.p) return;
+    void ensure_join_lane() {
+        if (join_.x.p) return;
         FS_HIP(hipStreamCreateWithFlags(&st_pf_, hipStreamNonBlocking));
         FS_HIP(hipEventCreateWithFlags(&ev_pf_, hipEventDisableTiming));
         for (hipEvent_t& e : ev_pft_) FS_HIP(hipEventCreate(&e));  // (timed: fs_lm_session_info's prefill-stream time)
         d2_seqpos_.alloc(sizeof(SeqState) * (size_t)B_);
         d2_copy_.alloc(sizeof(int) * 2 * (size_t)B_);
-        d2_pfx_.alloc(d_pfx_.n); d2_pfq_.alloc(d_pfq_.n); d2_pfslab_.alloc(d_pfslab_.n); d2_pfa_.alloc(d_pfa_.n); d2_pfa2_.alloc(d_pfa2_.n);
-        d2_pfss_.alloc(d_pfss_.n); d2_pfc_.alloc(d_pfc_.n); d2_pfpart_.alloc(d_pfpart_.n);
-        for (DevBuf* bf : {&d2_pfx_, &d2_pfa_, &d2_pfa2_, &d2_pfss_, &d2_pfc_, &d2_pfpart_}) FS_HIP(hipMemsetAsync(bf->p, 0, bf->n, st_pf_));
+        join_.ensure(a_, down_split_, n_chunks_, d_cos_.as<float>(), d_sin_.as<float>());  // (down_split_: the main lane's, ensured at session begin)
         FS_HIP(hipStreamSynchronize(st_pf_));
-    }
-    RowsCtx rows_ctx2(const SeqState* st, int pos_step, int pt_stride) {
-        RowsCtx c = rows_ctx(st, pos_step, pt_stride);
-        c.X = d2_pfx_.as<float>(); c.Q = d2_pfq_.as<float>(); c.part = d2_pfpart_.as<float>(); c.P = d2_pfslab_.as<float>();
-        c.A = d2_pfa_.as<uint16_t>(); c.C = d2_pfc_.as<uint16_t>(); c.A2 = d2_pfa2_.as<uint16_t>(); c.ss = d2_pfss_.as<float>();
-        return c;
     }
     void session_step(int n_frames, int* n_active) override {
         use_device();
@@ -1976,14 +1949,14 @@ class LM final : public LMBase {
             const int L = lens[i];
             ss.prompt_L = L;
             FS_HIP(hipMemcpyAsync(state(i), &ss, sizeof(ss), hipMemcpyHostToDevice, st_));
-            FS_HIP(hipMemcpyAsync(d_prompt_.p, prompts + poff[i], sizeof(uint32_t) * C1 * L, hipMemcpyHostToDevice, st_));
+            FS_HIP(hipMemcpyAsync(main_.prompt.p, prompts + poff[i], sizeof(uint32_t) * C1 * L, hipMemcpyHostToDevice, st_));
             FS_HIP(hipMemcpyAsync(d_cfg_.p, &cfgs[i], sizeof(SampleCfg), hipMemcpyHostToDevice, st_));  // (embed reads the semantic range from d_cfg_)
             RngState rng;
             upload_rng(seeds[i], rng, d_rrng_.as<RngState>() + i, st_);
             launch_reppen_reset(rrp_.view(i), C, a_.codebook_size, st_);
             prefill_tokens(i, L - 1, /*use_graph=*/false);
-            LmKernels<WT>::embed(d_, tok_emb_, cb_emb_, C, a_.codebook_size, d_cfg_.as<SampleCfg>(), d_prompt_.as<uint32_t>(), state(i), x(i), st_);
-            FS_HIP(hipStreamSynchronize(st_));  // d_prompt_ / d_cfg_ are reused by the next row
+            LmKernels<WT>::embed(d_, tok_emb_, cb_emb_, C, a_.codebook_size, d_cfg_.as<SampleCfg>(), main_.prompt.as<uint32_t>(), state(i), x(i), st_);
+            FS_HIP(hipStreamSynchronize(st_));  // main_.prompt / d_cfg_ are reused by the next row
             seq_len_[i] = L - 1;
             stats_.prompt_tokens += (uint64_t)L;
         }
@@ -2362,7 +2335,7 @@ class LM final : public LMBase {
         SampleCfg c = base_cfg();
         FS_HIP(hipMemcpy(d_cfg_.p, &c, sizeof(c), hipMemcpyHostToDevice));
         d_rng_.alloc(sizeof(RngState));
-        d_prompt_.alloc(sizeof(uint32_t) * (size_t)(a_.num_codebooks + 1) * a_.max_seq_len);
+        main_.prompt.alloc(sizeof(uint32_t) * (size_t)(a_.num_codebooks + 1) * a_.max_seq_len);
         out_cap_ = a_.max_seq_len + 8;
         d_out_.alloc(sizeof(uint32_t) * (size_t)B_ * a_.num_codebooks * out_cap_);
         rp_.alloc(1, a_.num_codebooks, a_.codebook_size);
@@ -2448,49 +2421,55 @@ class LM final : public LMBase {
         if (n <= 0) return;
         if (RowKernels<WT>::has_mfma_prefill() && n > 1 && a_.dim % 128 == 0 && a_.intermediate_size % 128 == 0) {
             ensure_prefill_buffers();
-            RowsCtx c = rows_ctx(state(b), /*pos_step=*/1, /*pt_stride=*/0);
-            for (int done = 0; done < n;) {
-                const int M = std::min(a_.head_dim == 64 ? kRowsCap : kPartRows, n - done);
-                c.nc_launch = chunk_bucket(seq_len_[b] + done + M);
-                RowKernels<WT>::prefill_embed(d_, tok_emb_, cb_emb_, a_.num_codebooks, a_.codebook_size, d_cfg_.as<SampleCfg>(),
-                                             d_prompt_.as<uint32_t>(), state(b), M, d_pfx_.as<float>(), st_);
-                for (int l = 0; l < a_.n_layer; ++l) RowKernels<WT>::rows_layer(d_, M, c, slow_[l], slow_kv(l, b), l == 0, st_);
-                RowKernels<WT>::rows_finish(d_, M, c, nullptr, st_);
-                launch_advance_n(state(b), M, st_);
-                done += M;
-                if (done == n)
-                    FS_HIP(hipMemcpyAsync(x(b), d_pfx_.as<float>() + (size_t)(M - 1) * a_.dim, sizeof(float) * a_.dim,
-                                          hipMemcpyDeviceToDevice, st_));
-            }
+            const int M = launch_seq_pass(main_, state(b), b, seq_len_[b], n);
+            FS_HIP(hipMemcpyAsync(x(b), main_.x.as<float>() + (size_t)(M - 1) * a_.dim, sizeof(float) * a_.dim, hipMemcpyDeviceToDevice, st_));
             return;
         }
         for (int l = 0; l < n; ++l) {
             set_bucket(seq_len_[b] + l + 1);
             if (use_graph && b == 0) { use_graphs_for_bucket(); FS_HIP(hipGraphLaunch(g_step_, st_)); continue; }
             LmKernels<WT>::embed(d_, tok_emb_, cb_emb_, a_.num_codebooks, a_.codebook_size, d_cfg_.as<SampleCfg>(),
-                                 d_prompt_.as<uint32_t>(), state(b), x(b), st_);
+                                 main_.prompt.as<uint32_t>(), state(b), x(b), st_);
             enqueue_slow_layers(b);
             launch_advance(state(b), st_);
         }
     }
+    // One sequence's next n prompt tokens -- the columns state->step .. of the lane's staged prompt, at positions start .. -- through the
+    // slow transformer on the lane's stream, in passes of the row buffers' capacity; their K/V go to page-table row kv_row.  Returns the
+    // rows of the last pass: row M - 1 of the lane's x then holds the pre-norm hidden state of the last token.
+    int launch_seq_pass(PrefillLane& ln, SeqState* st, int kv_row, int start, int n) {
+        RowsCtx c = ln.ctx(st, /*pos_step=*/1, /*pt_stride=*/0);
+        int M = 0;
+        for (int done = 0; done < n; done += M) {
+            M = std::min(a_.head_dim == 64 ? kRowsCap : kPartRows, n - done);
+            c.nc_launch = chunk_bucket(start + done + M);
+            RowKernels<WT>::prefill_embed(d_, tok_emb_, cb_emb_, a_.num_codebooks, a_.codebook_size, d_cfg_.as<SampleCfg>(),
+                                         ln.prompt.as<uint32_t>(), st, M, ln.x.as<float>(), ln.st);
+            for (int l = 0; l < a_.n_layer; ++l) RowKernels<WT>::rows_layer(d_, M, c, slow_[l], slow_kv(l, kv_row), l == 0, ln.st);
+            RowKernels<WT>::rows_finish(d_, M, c, nullptr, ln.st);
+            launch_advance_n(st, M, ln.st);
+        }
+        return M;
+    }
+    // ONE group pass on the lane's stream: S sequences of Lp rows each side by side (prompts: device [S][pstride], C + 1 rows of Lp columns
+    // per sequence), K/V into the page-table rows kv_row ..; seq_states (device [S], or null: all at st->pos) gives each its first position,
+    // nc_launch the attention chunks that cover the longest
+    void launch_group_pass(PrefillLane& ln, const uint32_t* prompts, int S, int Lp, size_t pstride, SeqState* st, int kv_row,
+                           const SeqState* seq_states, int nc_launch) {
+        RowsCtx c = ln.ctx(st, /*pos_step=*/1, /*pt_stride=*/max_pages_);
+        c.seq_rows = Lp;
+        c.nc_launch = nc_launch;
+        c.seq_states = seq_states;
+        const int M = S * Lp;
+        RowKernels<WT>::prefill_embed(d_, tok_emb_, cb_emb_, a_.num_codebooks, a_.codebook_size, d_cfg_.as<SampleCfg>(), prompts, st, M,
+                                     ln.x.as<float>(), ln.st, Lp, pstride);
+        for (int l = 0; l < a_.n_layer; ++l) RowKernels<WT>::rows_layer(d_, M, c, slow_[l], slow_kv(l, kv_row), l == 0, ln.st);
+    }
     void ensure_prefill_buffers() {
-        if (d_pfx_.p) return;
+        if (main_.x.p) return;
         const int I = a_.intermediate_size;
         down_split_ = I % 1024 == 0 ? I / 1024 : (I % 256 == 0 ? I / 256 : I / 128);
-        d_pfx_.alloc(sizeof(float) * kRowsCap * a_.dim);
-        d_pfq_.alloc(sizeof(float) * kRowsCap * a_.dim);
-        d_pfslab_.alloc(sizeof(float) * down_split_ * kRowsCap * a_.dim);
-        d_pfa_.alloc(sizeof(uint16_t) * 2 * kRowsCap * a_.dim);
-        d_pfa2_.alloc(sizeof(uint16_t) * 2 * kRowsCap * a_.dim);
-        d_pfss_.alloc(sizeof(float) * kRowsCap * (a_.dim / 16));
-        FS_HIP(hipMemsetAsync(d_pfa2_.p, 0, d_pfa2_.n, st_));
-        FS_HIP(hipMemsetAsync(d_pfss_.p, 0, d_pfss_.n, st_));
-        d_pfc_.alloc(sizeof(uint16_t) * 2 * kRowsCap * a_.intermediate_size);
-        d_pfpart_.alloc(sizeof(float) * kPartRows * (size_t)a_.n_head * n_chunks_ * (a_.head_dim + 2));
-        FS_HIP(hipMemsetAsync(d_pfx_.p, 0, d_pfx_.n, st_));
-        FS_HIP(hipMemsetAsync(d_pfpart_.p, 0, d_pfpart_.n, st_));
-        FS_HIP(hipMemsetAsync(d_pfa_.p, 0, d_pfa_.n, st_));
-        FS_HIP(hipMemsetAsync(d_pfc_.p, 0, d_pfc_.n, st_));
+        main_.ensure(a_, down_split_, n_chunks_, d_cos_.as<float>(), d_sin_.as<float>());
     }
     // the in-launch split-K sums of the folded decode steps give up after ~0.1 s of polling (a tile's blocks were not co-resident): loud failure
     void check_rows_xchg() {
@@ -2534,11 +2513,11 @@ class LM final : public LMBase {
         sc_.dev.alloc(sizeof(ScoreSlot) * B_);
         FS_HIP(hipMemset(sc_.dev.p, 0, sc_.dev.n));
     }
-    // one static-batch frame for B rows: x rows (d_pfx_) hold the embedded inputs of position state(0)->pos
+    // one static-batch frame for B rows: x rows (main_.x) hold the embedded inputs of position state(0)->pos
     void enqueue_batch_frame(int B) {
         const int C = a_.num_codebooks;
         // lock-step static batch: every row at state(0)->pos (left-padded prompts); session: row m is its own sequence at state(m)->pos
-        RowsCtx cs = rows_ctx(state(0), /*pos_step=*/sess_active_ ? -1 : 0, /*pt_stride=*/max_pages_);
+        RowsCtx cs = main_.ctx(state(0), /*pos_step=*/sess_active_ ? -1 : 0, /*pt_stride=*/max_pages_);
         cs.nc_launch = nc_launch_;
         // decode steps of <= 32 rows: the down projections close every layer themselves (in-launch split-K sums: no slabs, no k_prep nodes but the first)
         cs.xchg = d_xchg_.p; cs.epoch = d_epoch_.as<uint32_t>();
@@ -2654,7 +2633,7 @@ class LM final : public LMBase {
         auto it = batch_graphs_.find(key);
         if (it != batch_graphs_.end()) return it->second;
         {   // the co-residency query of the folded step (rows_fold_ok -> occupancy API) is answered once, OUTSIDE stream capture
-            RowsCtx cs = rows_ctx(state(0), 0, max_pages_);
+            RowsCtx cs = main_.ctx(state(0), 0, max_pages_);
             cs.xchg = d_xchg_.p; cs.epoch = d_epoch_.as<uint32_t>();
             (void)RowKernels<WT>::rows_fold_ok(d_, B, cs);
         }
@@ -2667,16 +2646,6 @@ class LM final : public LMBase {
         FS_HIP(hipGraphDestroy(g));
         batch_graphs_[key] = ge;
         return ge;
-    }
-    RowsCtx rows_ctx(const SeqState* st, int pos_step, int pt_stride) {
-        RowsCtx c;
-        c.X = d_pfx_.as<float>(); c.Q = d_pfq_.as<float>(); c.part = d_pfpart_.as<float>(); c.P = d_pfslab_.as<float>();
-        c.Mcap = kRowsCap; c.part_rows = kPartRows; c.down_split = down_split_;
-        c.A = d_pfa_.as<uint16_t>(); c.C = d_pfc_.as<uint16_t>();
-        c.A2 = d_pfa2_.as<uint16_t>(); c.ss = d_pfss_.as<float>();
-        c.cos_t = d_cos_.as<float>(); c.sin_t = d_sin_.as<float>();
-        c.state = st; c.n_chunks_max = n_chunks_; c.nc_launch = n_chunks_; c.pos_step = pos_step; c.pt_stride = pt_stride;
-        return c;
     }
 
     // naps before the first sweep of each stage kind (64-clock units; tuned on MI355X, profiles/r03_poll_naps.txt); the environment
@@ -2958,7 +2927,7 @@ class LM final : public LMBase {
         hipGraph_t g = nullptr;
         // (1) prefill step: embed prompt column state->step, 24 blocks, pos++/step++
         FS_HIP(hipStreamBeginCapture(st_, hipStreamCaptureModeThreadLocal));
-        LmKernels<WT>::embed(d_, tok_emb_, cb_emb_, C, a_.codebook_size, d_cfg_.as<SampleCfg>(), d_prompt_.as<uint32_t>(), state(0), x(0), st_);
+        LmKernels<WT>::embed(d_, tok_emb_, cb_emb_, C, a_.codebook_size, d_cfg_.as<SampleCfg>(), main_.prompt.as<uint32_t>(), state(0), x(0), st_);
         enqueue_slow_layers(0);
         launch_advance(state(0), st_);
         FS_HIP(hipStreamEndCapture(st_, &g));
@@ -3043,7 +3012,7 @@ class LM final : public LMBase {
     KvPages pages_;  // the slow KV pool's book: free list, reference counts, the sequences' and prefixes' page lists, the holds
     std::vector<int> seq_len_, fast_len_;
     // activations / state
-    DevBuf d_x_, d_xf_, d_q_, d_part_, d_act_, d_logits_slow_, d_logits_fast_, d_state_, d_cfg_, d_rng_, d_prompt_, d_out_;
+    DevBuf d_x_, d_xf_, d_q_, d_part_, d_act_, d_logits_slow_, d_logits_fast_, d_state_, d_cfg_, d_rng_, d_out_;
     RepPenBufs rp_, srp_, rrp_;  // repetition-penalty state: the batch-1 generator's (1 row), the per-slot samplers' [max_batch] (allocated with d_scfg_), the request rows' [PR_MAX_ROWS] (ensure_rows)
     DevBuf d_pack_, d_edges_, d_ctl_, d_qkv0_;  // persistent fast decoder (+ the layer-0 qkv table of the codebook passes 1..7)
     DevBuf d_fscl_, d_sscl_;           // FS_FP8 handles: row scales of the persistent kernels' images
@@ -3098,9 +3067,9 @@ class LM final : public LMBase {
     SeqState sess_stage_ = {};
     hipStream_t st_pf_ = nullptr;
     hipEvent_t ev_pf_ = nullptr;
-    DevBuf d2_pfx_, d2_pfq_, d2_pfslab_, d2_pfa_, d2_pfa2_, d2_pfss_, d2_pfc_, d2_pfpart_, d2_prompt_;  // row buffers of the session's prefill stream
+    PrefillLane join_{st_pf_};  // row buffers and staged prompt of the session's prefill stream
     DevBuf d_spack_, d_hpack_, d_snorms_, d_sedges_, d_sctl_;  // persistent slow transformer
-    DevBuf d_pfx_, d_pfq_, d_pfslab_, d_pfa_, d_pfa2_, d_pfss_, d_pfc_, d_pfpart_;  // MFMA row-path activations (kRowsCap rows)
+    PrefillLane main_{st_};  // MFMA row-path activations (kRowsCap rows) of the engine stream: prefill passes and the static-batch steps; the one staged prompt
     DevBuf d_bprompt_;  // static batch: all left-padded prompts [B][C + 1][Lmax] (group prefill)
     DevBuf d_xfrows_, d_lrows_, d_lfast_, d_fast_state_, d_fast_table_, d_rwords_;  // static-batch generator
     DevBuf d_xchg_, d_epoch_;  // folded decode steps: split-K exchange units, {step epoch, timeouts}

@@ -164,6 +164,65 @@ def test_members_with_different_starts_share_one_group_pass():
     assert flips <= 1
 
 
+def test_one_session_runs_every_kind_of_prefill_pass():
+    """The kinds of pass a session's queue is taken apart into (csrc/fs_prefill_plan.h), in ONE per-slot session of a max_batch = 2 handle
+    (MID: the TINY handle with head_dim 64 -- the group pass needs the flash kernel): an imported prefix of 65 positions, a created one of
+    63, unseeded prefixed adds with bodies of 1 and 7 columns, a seeded plain add of 2 columns.  Of those only ONE member is unseeded
+    and has a row to run, so they make an import pass, single passes and a pass without rows; two more unseeded prefixed adds (bodies of
+    5 and 3 columns, once the slots are free again) make the group pass.  The four counters after each stage are computed here from the
+    rules, and every slot's codes are those of a plain add of the concatenation (parting only at an oracle near-tie)."""
+    lm, o = _lm_and_oracle(MID, "bf16", max_batch=2)
+    rng = np.random.RandomState(23)
+    Pi, Pc = 65, 63
+    pre_i, pre_c = _prompt(rng, Pi), _prompt(rng, Pc)
+    # (tag, prefix or None, body columns, seed)
+    reqs = [("one", "i", 1, None), ("seven", "c", 7, None), ("seeded", None, 2, 1234), ("five", "i", 5, None), ("three", "c", 3, None)]
+    pre = {"i": pre_i, "c": pre_c, None: np.zeros((9, 0), np.uint32)}
+    bodies = {tag: _prompt(rng, Lb) for tag, _, Lb, _ in reqs}
+    full = {tag: np.concatenate([pre[k], bodies[tag]], 1) for tag, k, _, _ in reqs}
+    budget = {tag: f.shape[1] + 10 for tag, f in full.items()}
+    kw = dict(temp=0.0, top_p=1.0, top_k=0, seed=42, ignore_eos=True, per_slot=True, repetition_penalty=1.0)
+    counters = ("prefill_passes", "tokens_prefilled", "prefix_tokens_reused", "tail_pages_copied")
+    with lm.session(**kw) as s:
+        blob = s.export_prefix(s.add_prefix(pre_i))
+    got, plain = {}, {}
+    with lm.session(**kw) as s:
+        def add(tag):
+            _, k, _, seed = next(r for r in reqs if r[0] == tag)
+            slot = s.add(bodies[tag], budget[tag], prefix=ids[k] if k else None, seed=seed)
+            assert slot is not None, tag
+            return slot
+        ids = {"i": s.import_prefix(blob), "c": s.add_prefix(pre_c)}
+        live = {add("one"): "one", add("seven"): "seven"}
+        s.step(1)  # nothing live: the whole queue is taken apart, pass after pass
+        # the import (no transformer pass, no counter) | the creation alone, 63 rows | "seven" alone (6 rows from position 63; "one" has
+        # no row to run and cannot join) | "one" without a pass.  Both prefixes end inside a page: one tail copy per add.
+        info = s.info()
+        assert [info[k] for k in counters] == [2, Pc + 6, Pc + Pi, 2], info
+        _drain(s, live, got)
+        live = {add("seeded"): "seeded"}  # a seed of its own: alone by rule, 1 row
+        s.step(1)
+        info = s.info()
+        assert [info[k] for k in counters] == [3, Pc + 6 + 1, Pc + Pi, 2], info
+        _drain(s, live, got)
+        live = {add("five"): "five", add("three"): "three"}  # ONE group pass of 2 x 4 rows, starts 65 and 63: 4 + 2 rows are tokens
+        s.step(1)
+        info = s.info()
+        assert [info[k] for k in counters] == [4, Pc + 6 + 1 + 4 + 2, 2 * (Pc + Pi), 4], info
+        _drain(s, live, got)
+    with lm.session(**kw) as s:  # the plain adds of the concatenations, each in a pass of its own
+        for tag, _, _, seed in reqs:
+            _drain(s, {s.add(full[tag], budget[tag], seed=seed): tag}, plain)
+    flips = 0
+    for tag, _, _, _ in reqs:
+        assert got[tag].shape == plain[tag].shape == (8, budget[tag] - full[tag].shape[1] + 2), tag
+        if not np.array_equal(got[tag], plain[tag]):  # both sides of a parting sit at a near-tie of the oracle's stream
+            flips += 1
+            _check_vs_oracle(o, full[tag], budget[tag], got[tag], f"{tag}", ignore_eos=True)
+            _check_vs_oracle(o, full[tag], budget[tag], plain[tag], f"{tag} (plain)", ignore_eos=True)
+    assert flips <= 1
+
+
 def _pages(n):
     return (n + 63) // 64
 
