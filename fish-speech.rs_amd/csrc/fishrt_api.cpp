@@ -279,6 +279,14 @@ int fs_lm_session_prefix_import(fs_lm_t* lm, const void* blob, size_t bytes, int
     FS_TRY(*prefix_id = lm->impl->session_prefix_import(blob, bytes))
 }
 int fs_lm_session_prefix_release(fs_lm_t* lm, int prefix_id) { FS_ARG(lm, "null argument"); FS_TRY(lm->impl->session_prefix_release(prefix_id)) }
+int fs_lm_session_prefix_from_slot(fs_lm_t* lm, int slot, int n_positions, int* prefix_id, int* P_out) {
+    FS_ARG(lm && prefix_id, "null argument");
+    FS_TRY(*prefix_id = lm->impl->session_prefix_from_slot(slot, n_positions, P_out))
+}
+int fs_lm_session_last_frame(fs_lm_t* lm, int slot, uint32_t* column) {
+    FS_ARG(lm && column, "null argument");
+    FS_TRY(lm->impl->session_last_frame(slot, column))
+}
 int fs_lm_session_add_prefixed(fs_lm_t* lm, int prefix_id, const uint32_t* body, int L_body, int max_new_tokens, int* slot) {
     FS_ARG(lm && body && slot, "null argument");
     FS_ARG(prefix_id >= 0, "unknown or released prefix id");  // (a negative id means a plain add only where the header says so: _add_ex and later)

@@ -60,6 +60,9 @@ class LMBase {
     virtual int session_prefix_create(const uint32_t* prompt, int P) = 0;
     virtual void session_prefix_release(int id) = 0;
     virtual void session_info(int64_t out[8]) = 0;
+    // a prefix out of a slot's history (fishrt.h: fs_lm_session_prefix_from_slot / fs_lm_session_last_frame)
+    virtual int session_prefix_from_slot(int slot, int n_positions, int* P) = 0;
+    virtual void session_last_frame(int slot, uint32_t* column) = 0;
     // prefix KV blobs (fishrt.h: fs_lm_weights_fingerprint / fs_lm_session_prefix_export / _import)
     virtual uint64_t weights_fingerprint() = 0;
     virtual void session_prefix_export(int id, void* blob_out, size_t cap, size_t* bytes) = 0;

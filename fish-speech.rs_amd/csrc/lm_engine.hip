@@ -1064,6 +1064,7 @@ class LM final : public LMBase {
         sess_scratch_ = pages_.hold_new();
         sess_left_.assign(B_, kSlotFree);
         sess_pos_.assign(B_, 0);
+        sess_L_.assign(B_, 0);
         sess_hs_.assign(B_, SeqState{});
         sess_queue_.clear(); sess_flight_.clear();
         sess_prefixes_.clear();
@@ -1394,6 +1395,66 @@ class LM final : public LMBase {
         px.live = false;
         if (!px.pending) pages_.drop(pages_.prefix_owner(id));  // (its pass still queued or in flight: activate_pending drops them after it)
     }
+    // A prefix out of a slot's history (fishrt.h: fs_lm_session_prefix_from_slot).  The slot has T = L + n_out - 1 positions that nobody
+    // writes again: a live slot's next step writes row T (it feeds its last frame there), a slot finished on its budget is parked on the
+    // scratch page, and a slot frozen by <|im_end|> keeps rewriting the row its terminating iteration wrote, which is row T as well
+    // (rows_frame_commit: a frozen slot neither emits nor advances).  The prefix shares the slot's first P / 64 pages and, when P is not
+    // page-aligned, owns a copy of the slot's page P / 64 -- so from page T / 64 on everything stays the slot's alone.  Nothing is
+    // prefilled and nothing is queued: the prefix is active when the call returns.
+    int session_prefix_from_slot(int slot, int n_positions, int* P_out) override {
+        use_device();
+        // 1. whatever makes the request a bad one, before anything is taken or changed
+        FS_REQUIRE(sess_active_, "no open session");
+        FS_REQUIRE(!sess_.rows, "fs_lm_session_prefix_from_slot: FS_SESSION_ROWS sessions are not supported (their rows terminate by the row kernels' own "
+                                "budget word and their launch shape depends on the highest live slot); use a plain or FS_SESSION_PER_SLOT session");
+        require_live_slot(slot);
+        while (slot_prefilling(slot)) { flush_pending(); activate_pending(true); }  // (its prefill is queued or in flight: let it finish first)
+        const int L = sess_L_[slot], T = L + sess_hs_[slot].n_out - 1;
+        if (T < 1) throw Error("T = " + std::to_string(T) + ": the slot has no history yet (a one-column prompt before its first step has no cached position)");
+        if (n_positions != -1 && (n_positions < 1 || n_positions > T))
+            throw Error("n_positions = " + std::to_string(n_positions) + " outside [1, T = " + std::to_string(T) + "] (-1 takes all T; T = L + n_frames - 1: the "
+                        "column of the last emitted frame is not history)");
+        const int P = n_positions == -1 ? T : n_positions;
+        if (P >= a_.max_seq_len) throw Error("P = " + std::to_string(P) + " >= max_seq_len: the prefix leaves no room for a body within max_seq_len");
+        // 2. room right now?  (reads only; the one page a cut inside a page needs)
+        const int nfull = P / KV_PAGE;  // (a slot's owner in the page book is its index)
+        FS_REQUIRE((int)pages_.of(slot).size() * KV_PAGE >= P, "the slot holds fewer pages than its history");
+        const KvPages::Share shared{slot, nfull};
+        if (!pages_.room(KvPages::kNewOwner, P, shared).fits) {
+            if (P_out) *P_out = P;
+            return -1;
+        }
+        if (P % KV_PAGE && !d_promo_pair_.p) d_promo_pair_.alloc(sizeof(int) * 2);
+        // 3. the prefix: references on the slot's full pages, then its own last page (neither can fail: step 2 asked for exactly this)
+        SessPrefix px;
+        px.P = P; px.live = true; px.pending = false;
+        sess_prefixes_.push_back(px);
+        const int id = (int)sess_prefixes_.size() - 1, owner = pages_.add_prefix();
+        FS_REQUIRE(owner == pages_.prefix_owner(id), "prefix ids and the page book's owners are out of step");
+        pages_.share(owner, shared);
+        pages_.grow(owner, P);
+        if (P % KV_PAGE) {
+            // the slot's page P / 64 into the prefix's own, on the decode stream: behind every step enqueued so far, and finished before
+            // this returns, so ahead of whatever is queued on the prefix afterwards (and of the slot's next step, which writes that page)
+            const int pair[2] = {pages_.of(slot)[(size_t)nfull], pages_.of(owner)[(size_t)nfull]};
+            FS_HIP(hipMemcpyAsync(d_promo_pair_.p, pair, sizeof(pair), hipMemcpyHostToDevice, st_));
+            const size_t page_bytes = page_elems_ * sizeof(KT);
+            launch_kv_page_copy(kv_pool_.p, 2 * a_.n_layer, (size_t)n_pages_ * page_bytes, page_bytes, d_promo_pair_.as<int>(), 1, st_);
+            FS_HIP(hipStreamSynchronize(st_));  // (pair is a local)
+            sess_count_[3] += 1;
+        }
+        pages_.writable_from(slot, T);  // (the source's write target and everything behind it is still its alone)
+        if (P_out) *P_out = P;
+        return id;
+    }
+    // fishrt.h: fs_lm_session_last_frame -- SeqState::prev of the host mirror, which session_step refreshes after every chunk
+    void session_last_frame(int slot, uint32_t* column) override {
+        use_device();
+        FS_REQUIRE(sess_active_, "no open session");
+        require_live_slot(slot);
+        FS_REQUIRE(!slot_prefilling(slot) && sess_hs_[slot].n_out > 0 && sess_hs_[slot].have_prev, "the slot has not emitted a frame yet (fs_lm_session_last_frame needs its first step)");
+        for (int i = 0; i <= a_.num_codebooks; ++i) column[i] = sess_hs_[slot].prev[i];
+    }
     void session_info(int64_t out[8]) override {
         int64_t live = 0;
         for (const SessPrefix& px : sess_prefixes_) live += px.live;
@@ -1699,6 +1760,7 @@ class LM final : public LMBase {
             }
             sess_left_[b] = pa.n_iter;
             sess_pos_[b] = Lp;
+            sess_L_[b] = L;
         }
         FS_HIP(hipStreamSynchronize(st_));
         sess_flight_.clear();
@@ -3040,6 +3102,7 @@ class LM final : public LMBase {
     uint64_t sess_seed_ = 0;
     std::unique_lock<PersistLock> sess_plock_;
     std::vector<int> sess_left_, sess_pos_;
+    std::vector<int> sess_L_;  // a live slot's total prompt length, prefix included (fs_lm_session_prefix_from_slot: T = L + frames - 1)
     std::vector<SeqState> sess_hs_;
     int sess_scratch_ = 0;  // (a hold of the page book's; a member because parked slots' rows are uploaded from here)
     uint64_t sess_released_frames_ = 0;
@@ -3047,6 +3110,7 @@ class LM final : public LMBase {
     std::vector<SeqState> sess_stage_pos0_;            // a group pass's member start positions (pos; rope_off 0)
     std::vector<int> sess_stage_copy_;
     DevBuf d2_seqpos_, d2_copy_;                       // device copies of the two above: member start states / tail-copy page pairs
+    DevBuf d_promo_pair_;                              // fs_lm_session_prefix_from_slot: the one (source, destination) page pair of its copy, read on the decode stream
     hipEvent_t ev_pft_[2] = {nullptr, nullptr};        // timing events around each prefill-stream pass (fs_lm_session_info)
     bool sess_timed_ = false;
     int64_t sess_count_[4] = {0, 0, 0, 0};             // passes, tokens prefilled, prefix tokens reused, tail pages copied

@@ -57,6 +57,7 @@ SYMBOLS = ["fs_last_error", "fs_version", "fs_device_count", "fs_lm_create", "fs
            "fs_lm_session_poll_alts", "fs_selftest_alt_rows",
            "fs_selftest_conv1d",
            "fs_lm_weights_fingerprint", "fs_lm_session_prefix_export", "fs_lm_session_prefix_import",
+           "fs_lm_session_prefix_from_slot", "fs_lm_session_last_frame",
            "fs_codec_create", "fs_codec_destroy", "fs_codec_load_safetensors", "fs_codec_load_synthetic",
            "fs_codec_decode", "fs_codec_encode", "fs_codec_encode_batch", "fs_codec_sample_rate", "fs_codec_set_precision", "fs_codec_precision", "fs_codec_set_range_check", "fs_codec_range_stats", "fs_codec_stream_begin", "fs_codec_stream_decode", "fs_codec_stream_end", "fs_codec_streams_open", "fs_codec_streams_close", "fs_codec_streams_decode", "fs_codec_streams_decode_ragged", "fs_fp8_quantize_rows", "fs_fp8_decode_table", "fs_selftest", "fs_lm_selftest", "fs_selftest_sample_rows", "fs_selftest_sample_slots", "fs_lm_debug_capture", "fs_lm_debug_read"]
 
@@ -100,6 +101,12 @@ CONV_PROTOTYPES = {
     "fs_selftest_conv1d": [C.c_int, C.POINTER(ConvCase), _F32P, _F32P, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64)],
 }
 
+# ... and of the calls that make a prefix out of a slot's history
+HISTORY_PROTOTYPES = {
+    "fs_lm_session_prefix_from_slot": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "fs_lm_session_last_frame": [C.c_void_p, C.c_int, _U32P],
+}
+
 _lib = None
 
 
@@ -119,7 +126,7 @@ def lib():
         L.fs_comm_destroy.argtypes = [C.c_void_p]
         L.fs_lm_destroy.argtypes = [C.c_void_p]
         L.fs_codec_destroy.argtypes = [C.c_void_p]
-        for name, argtypes in {**SCORE_PROTOTYPES, **TRACE_PROTOTYPES, **ALTS_PROTOTYPES, **CONV_PROTOTYPES}.items():
+        for name, argtypes in {**SCORE_PROTOTYPES, **TRACE_PROTOTYPES, **ALTS_PROTOTYPES, **CONV_PROTOTYPES, **HISTORY_PROTOTYPES}.items():
             getattr(L, name).argtypes = argtypes
         _lib = L
     return _lib

@@ -275,6 +275,56 @@ class DualARTransformer:
         Fish <= 1.4 token configs (no semantic range) take per_slot=True only; plain and rows sessions raise and say so."""
         return Session(self, temp, top_p, top_k, seed, ignore_eos, rows, repetition_penalty, per_slot, wide, score, trace, alts)
 
+    def generate_turns(self, cond, bodies, max_new_tokens, between=None, temp=0.7, top_p=0.9, top_k=50, repetition_penalty=1.2, seed=42,
+                       ignore_eos=False, step_frames=8):
+        """The bodies as the turns of ONE conversation (upstream Fish-Speech's long-form mode: the earlier segments -- text and generated
+        codes -- stay in the context of the next one), through a per-slot session: turn 0 is add(concat(cond, bodies[0])), turn i + 1 is
+        Session.continue_from(turn i's slot, concat(between, bodies[i + 1])), so nothing of the history is ever prefilled again and its
+        rows are the very rows that produced the audio.  cond: u32 [C+1, n] or None; bodies[i]: u32 [C+1, L_i] (encode_text("user", chunk)
+        + encode_vq(None)); between: u32 [C+1, k] columns that close an assistant turn (the tokens of "<|im_end|>"; None = nothing).
+        Every turn gets the frame budget it would have had on cond alone: max_new_tokens raised by what its history adds to its prompt.
+        Turn i samples with seed + i.  When history + body + budget no longer fit max_seq_len (or no KV page is free) the turn starts over on cond alone,
+        as upstream drops old segments.  -> the list of per-turn codes u32 [C, n_i]."""
+        C1 = self.cfg["num_codebooks"] + 1
+        empty = np.zeros((C1, 0), np.uint32)
+        cond = empty if cond is None else _u32(cond)
+        between = empty if between is None else _u32(between)
+        bodies = [_u32(b) for b in bodies]
+        for what, a in [("cond", cond), ("between", between)] + [(f"bodies[{i}]", b) for i, b in enumerate(bodies)]:
+            if a.ndim != 2 or a.shape[0] != C1 or (what.startswith("bodies") and a.shape[1] < 1):
+                raise ValueError(f"{what} must be u32 [{C1}, n], got {a.shape}")
+        if int(max_new_tokens) < 1:
+            raise ValueError("max_new_tokens must be >= 1")
+        out = []
+        with self.session(temp=temp, top_p=top_p, top_k=top_k, seed=seed, ignore_eos=ignore_eos, per_slot=True,
+                          repetition_penalty=repetition_penalty) as s:
+            prev, hist = None, 0  # the previous turn's slot (kept until the next one is queued) and its token history
+            for i, body in enumerate(bodies):
+                sd = (int(seed) + i) & (2**64 - 1)
+                slot = None
+                if prev is not None:
+                    tail = np.concatenate([between, body], 1)
+                    Lh, Lc = hist + 1 + tail.shape[1], cond.shape[1] + body.shape[1]
+                    if Lh + max(0, int(max_new_tokens) - Lc + 1) <= self.cfg["max_seq_len"]:  # the frames it would have had on cond alone fit
+                        slot, _ = s.continue_from(prev, tail, int(max_new_tokens) + (Lh - Lc), seed=sd)
+                    s.release(prev)
+                if slot is None:  # the first turn, or a history that no longer fits: the conditioning alone
+                    full = np.ascontiguousarray(np.concatenate([cond, body], 1))
+                    slot = s.add(full, int(max_new_tokens), seed=sd)
+                    if slot is None:
+                        raise RuntimeError("generate_turns: the session has no room for the turn")
+                    L = full.shape[1]
+                else:
+                    L = hist + 1 + tail.shape[1]
+                while not s.poll(slot, codes=False)[1]:
+                    s.step(step_frames)
+                codes, _ = s.poll(slot)
+                out.append(codes)
+                prev, hist = slot, L + codes.shape[1] - 1
+            if prev is not None:
+                s.release(prev)
+        return out
+
     def generate_traced(self, prompts, max_new_tokens, samplings=None, seeds=None, collect_hidden=False, top_n=0):
         """Generate behind every prompts[i] (u32 [C+1, L_i]) and return, with the codes, the log-probs the model gave the tokens it picked
         -- one pass, no teacher-forced second one.  max_new_tokens: one int or one per prompt; samplings[i] (dict / SamplingArgs-like) and
@@ -550,6 +600,51 @@ class Session:
     def release_prefix(self, prefix):
         """drop the session's reference; the pages go back once no slot uses them any more"""
         _ffi.check(_ffi.lib().fs_lm_session_prefix_release(self.lm._h, int(prefix)))
+
+    def prefix_from_slot(self, slot, n_positions=None):
+        """a prefix out of the first P cached positions of `slot` (fs_lm_session_prefix_from_slot): nothing is prefilled, the slot's full
+        pages are shared and its partly filled page copied.  n_positions None: all T = L + n_frames - 1 positions the slot has (the column
+        of its last emitted frame is not among them: last_frame); else 1 <= n_positions <= T.  -> (prefix id, P); (None, P) when the one
+        page a cut inside a page needs is not free right now.  The slot goes on as if nothing had happened; plain and per_slot sessions."""
+        if self.rows:
+            raise ValueError("prefix_from_slot needs a plain or per_slot session (FS_SESSION_ROWS sessions are not supported)")
+        if n_positions is not None and (isinstance(n_positions, bool) or int(n_positions) != n_positions or int(n_positions) < 1):
+            raise ValueError(f"n_positions must be None (the slot's whole history) or an integer >= 1, got {n_positions!r}")
+        pid, P = C.c_int(-1), C.c_int(0)
+        _ffi.check(_ffi.lib().fs_lm_session_prefix_from_slot(self.lm._h, int(slot), -1 if n_positions is None else int(n_positions), C.byref(pid),
+                                                              C.byref(P)))
+        return (None if pid.value < 0 else int(pid.value)), int(P.value)
+
+    def last_frame(self, slot):
+        """u32 (C + 1,): the input column [slow token, c0..] of the slot's last emitted frame, as the engine would feed it next
+        (fs_lm_session_last_frame); an error before the slot's first frame.  For a cut at an earlier frame take the slow token from a traced
+        slot's poll_trace()["tokens"] or from the frames a scoring slot was forced along."""
+        out = np.zeros(self.lm.cfg["num_codebooks"] + 1, np.uint32)
+        _ffi.check(_ffi.lib().fs_lm_session_last_frame(self.lm._h, int(slot), out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def continue_from(self, slot, body, max_new_tokens, **add_kwargs):
+        """the next turn of `slot`: its whole history becomes a prefix, and a new slot is admitted on it with body = [last_frame(slot),
+        body...] (body u32 [C+1, n >= 0]; what follows the slot's last frame) -> (new slot, prefix id), or (None, None) when the pool or
+        the slots are short right now (nothing is kept then).  The session's reference on the prefix is dropped as soon as the add is
+        queued, so its pages go when the new slot -- and the source -- are released; the id is returned for the record only.
+        max_new_tokens and add_kwargs (sampling, seed, collect_hidden, trace) are add()'s: the budget counts from the new slot's whole
+        prompt, history included."""
+        if "prefix" in add_kwargs:
+            raise ValueError("continue_from admits on the prefix it makes: no prefix argument")
+        b = _u32(body)
+        C1 = self.lm.cfg["num_codebooks"] + 1
+        if b.ndim != 2 or b.shape[0] != C1:
+            raise ValueError(f"body must be u32 [{C1}, n >= 0], got {b.shape}")
+        col = self.last_frame(slot)
+        pid, _ = self.prefix_from_slot(slot)
+        if pid is None:
+            return None, None
+        try:
+            new = self.add(np.concatenate([col[:, None], b], axis=1), max_new_tokens, prefix=pid, **add_kwargs)
+        finally:
+            self.release_prefix(pid)
+        return (new, pid) if new is not None else (None, None)
 
     def export_prefix(self, prefix):
         """the K/V rows of a live prefix as bytes (fishrt.h: fs_lm_session_prefix_export; header: prefix_blob_info).  Waits for the

@@ -45,6 +45,17 @@ session is about to close -- not while the job that created it has no frame yet,
 misses the session's map but hits the cache is imported (`Session.import_prefix`: one copy and a scatter) instead of prefilled.  No pages
 for the import falls back to the full prompt, as for a creation; a blob the handle refuses (weights reloaded) is dropped.
 
+Chunk history (`AppState(chunk_history=True)`, off by default: it changes what a client hears; needs the continuous scheduler with
+`per_slot_sampling`).  Upstream Fish-Speech keeps the earlier segments of a long text -- their text and their generated codes -- in the
+context of the next one, so prosody carries over; the reference, and this shim by default, generate every chunk on the conditioning
+prefix alone.  With the option the chunks of ONE request run as the turns of a conversation: chunk i + 1 is admitted when chunk i's slot
+is done, on a prefix made of that slot's whole history (`Session.continue_from`: `fs_lm_session_prefix_from_slot`, nothing is prefilled
+again), with the body [the last frame's column, the tokens of "<|im_end|>", encode_text("user", chunk), encode_vq(None)] -- the columns
+`PromptEncoder` puts between one assistant turn and the next.  The chunk keeps the frame budget it would have had without history
+(`max_new_tokens` raised by what the history adds to its prompt); when history + body + budget would not fit `max_seq_len`, or the
+session has no room right now, it falls back to the conditioning prefix alone, as upstream drops old segments.  Chunks of different
+requests still share the session, and responses keep their shape (a streamed chunk is sent when its turn is done, as before).
+
 Hidden states (`generate_hidden_states`, `handlers/send_hidden_states.rs`: body {text, speaker_id, return_audio} -> a stored zip of
 `hidden_states.npy`, optional `audio.wav`, `metadata.json`).  Its chunk jobs go through the same scheduler with `collect_hidden` set: in a
 session the slot is admitted with `add(..., collect_hidden=True)` and read with `poll_hidden`, outside one the job calls
@@ -132,7 +143,7 @@ class LMState:  # server/lib/state.rs:12-21
 class AppState:  # server/lib/state.rs:23-29
     def __init__(self, lm_state, codec, sample_rate=44100, opus_encoder=None, preprocess=preprocess_text, batch_window_s=0.002,
                  continuous=True, auto_batch=False, session_prefixes=False, per_slot_sampling=False, wide_sampling=False,
-                 prefix_host_cache_bytes=0):
+                 prefix_host_cache_bytes=0, chunk_history=False):
         self.lm, self.codec, self.sample_rate, self.opus_encoder, self.preprocess = lm_state, codec, sample_rate, opus_encoder, preprocess
         self.codec_lock = threading.Lock()  # a codec handle takes one call at a time (include/fishrt.h); requests vocode from their own threads
         self.auto_batch = auto_batch  # True: every chunk may join the batching session (batch sampling semantics) without `batch_size`
@@ -143,8 +154,11 @@ class AppState:  # server/lib/state.rs:23-29
         # prefix_host_cache_bytes (0 = off; needs session_prefixes): the scheduler keeps the K/V of conditioning prefixes as host blobs
         # (Session.export_prefix) across sessions, up to this many bytes, and imports them instead of prefilling the voice again.  An imported
         # prefix carries the bits of a created one, so the caveat of session_prefixes is unchanged.
+        # chunk_history (off by default; needs continuous and per_slot_sampling): the chunks of one request run as turns of one conversation,
+        # each on the history of the one before (module docstring).  It changes what a client hears.
+        self.chunk_history = bool(chunk_history)
         self.scheduler = Scheduler(lm_state, batch_window_s, continuous, session_prefixes=session_prefixes, per_slot_sampling=per_slot_sampling,
-                                   wide_sampling=wide_sampling, prefix_host_cache_bytes=prefix_host_cache_bytes)
+                                   wide_sampling=wide_sampling, prefix_host_cache_bytes=prefix_host_cache_bytes, chunk_history=chunk_history)
 
 
 class _Job:
@@ -153,6 +167,8 @@ class _Job:
         self.collect_hidden = bool(collect_hidden)  # the future then resolves to (codes, hidden f32 (iterations, dim)) instead of codes
         self.sampling, self.seed = sampling, seed  # request-level SamplingArgs / sampler seed (None: the server's / a fresh one)
         self.cond_key = hashlib.sha1(cond.tobytes()).hexdigest() if cond is not None else None
+        # chunk_history: the job of the request's next chunk (submitted when this one is done) and the columns that close this turn
+        self.next, self.sep = None, None
 
     def full_prompt(self):
         return self.body if self.cond is None else np.ascontiguousarray(np.concatenate([self.cond, self.body], 1))
@@ -167,7 +183,9 @@ class Scheduler:
     PREFIX_LRU = 8  # conditioning prefixes kept per session (session_prefixes)
 
     def __init__(self, lm_state, batch_window_s=0.002, continuous=True, step_frames=8, session_prefixes=False, per_slot_sampling=False,
-                 wide_sampling=False, prefix_host_cache_bytes=0):
+                 wide_sampling=False, prefix_host_cache_bytes=0, chunk_history=False):
+        if chunk_history and not (continuous and per_slot_sampling):
+            raise ValueError("chunk_history=True needs continuous=True and per_slot_sampling=True (a turn is a slot of a per-slot session)")
         if wide_sampling and not per_slot_sampling:
             raise ValueError("wide_sampling=True needs per_slot_sampling=True (FS_SESSION_WIDE_SAMPLER is a per-slot session flag)")
         if prefix_host_cache_bytes and not session_prefixes:
@@ -179,6 +197,7 @@ class Scheduler:
         self.session_prefixes = session_prefixes
         self.per_slot_sampling = per_slot_sampling
         self.wide_sampling = bool(wide_sampling)
+        self.chunk_history = bool(chunk_history)
         self.sess_mode = None  # "rows" | "per_slot" | "plain" while a session is open
         self.prefixes = collections.OrderedDict()  # session_prefixes: cond_key -> prefix id of the open session (LRU order)
         # prefix_host_cache_bytes: cond_key -> blob (LRU order, bounded by the byte budget).  It belongs to the scheduler, not to a
@@ -197,6 +216,8 @@ class Scheduler:
             self.stats.update(per_slot_sessions=0)
         if wide_sampling:
             self.stats.update(wide_sessions=0)
+        if chunk_history:
+            self.stats.update(history_turns=0, history_fallbacks=0)
         self._stop = False
         self.th = threading.Thread(target=self._run, daemon=True)
         self.th.start()
@@ -205,6 +226,60 @@ class Scheduler:
         j = _Job(cond, body, n_cond, allow_batch, sampling, seed, collect_hidden)
         self.q.put(j)
         return j.future
+
+    def submit_turns(self, cond, bodies, n_cond, allow_batch, sep, sampling=None, seeds=None, collect_hidden=False):
+        """chunk_history: the chunks of one request as a chain of jobs -> their futures.  Only the first is queued; each of the others
+        is admitted when the one before it is done, on that one's history (`_turn_add`) or, failing that, like any job.  sep: the
+        columns that close an assistant turn (the tokens of "<|im_end|>")."""
+        jobs = [_Job(cond, b, n_cond, allow_batch, sampling, None if seeds is None else seeds[i], collect_hidden) for i, b in enumerate(bodies)]
+        for a, b in zip(jobs, jobs[1:]):
+            a.next, a.sep = b, sep
+        if jobs:
+            self.q.put(jobs[0])
+        return [j.future for j in jobs]
+
+    @staticmethod
+    def _fail(j, e):
+        """the job's future gets the error, and so does every later chunk of its request (nothing will ever submit them)"""
+        while j is not None:
+            if not j.future.done():
+                j.future.set_exception(e)
+            j = getattr(j, "next", None)
+
+    def _after(self, j):
+        """job j is done outside a turn hand-over: the next chunk of its request joins the queue like any job (conditioning alone)"""
+        nxt = getattr(j, "next", None)
+        if nxt is not None:
+            j.next = None
+            if self._stop:
+                self._fail(nxt, RuntimeError("the scheduler is shutting down; the rest of the request was dropped"))
+            else:
+                self.stats["history_fallbacks"] = self.stats.get("history_fallbacks", 0) + 1
+                self.q.put(nxt)
+
+    def _turn_add(self, sess, slot, j, codes):
+        """chunk_history: job j's slot is done with `codes`; admit the next chunk of its request on the slot's history -> its slot, or
+        None (no next chunk / it would not fit max_seq_len / no room right now: the caller lets it fall back)"""
+        nxt = getattr(j, "next", None)
+        if nxt is None or self.sess_mode != "per_slot" or getattr(j, "sess_L", None) is None or not self._session_ok(nxt):
+            return None
+        hist = j.sess_L + int(codes.shape[1]) - 1  # the slot's history: its prompt and its frames but the last one's column
+        tail = np.ascontiguousarray(np.concatenate([j.sep, nxt.body], 1))
+        L_turn, L_plain = hist + 1 + tail.shape[1], (nxt.cond.shape[1] if nxt.cond is not None else 0) + nxt.body.shape[1]
+        # the frames the chunk would have had on the conditioning alone must fit behind history + body
+        if L_turn + max(0, self.s.max_new_tokens - L_plain + 1) > self.s.lm.cfg["max_seq_len"]:
+            return None
+        sa = nxt.sampling or self.s.default_sampling_args
+        kw = dict(sampling=sa.kw(), seed=(nxt.seed if nxt.seed is not None else self.s.seed_source()) & (2**64 - 1))
+        if nxt.collect_hidden:
+            kw["collect_hidden"] = True
+        new, _ = sess.continue_from(slot, tail, self.s.max_new_tokens + (L_turn - L_plain), **kw)
+        if new is None:
+            return None
+        j.next = None
+        nxt.sess_slot, nxt.sess_L = new, L_turn
+        self.stats["history_turns"] = self.stats.get("history_turns", 0) + 1
+        return new
 
     @staticmethod
     def _own(j):
@@ -286,8 +361,7 @@ class Scheduler:
 
         def fail_all(e):
             for jb in list(live.values()) + ([held] if held is not None else []):
-                if not jb.future.done():
-                    jb.future.set_exception(e)
+                self._fail(jb, e)
             live.clear()
 
         stopping = False
@@ -318,7 +392,9 @@ class Scheduler:
                 if held is not None:
                     joins = held.allow_batch and self._session_ok(held)
                     # (per_slot_sampling: a job with a seed of its own runs in the session even when it is alone -- same kernels, same audio)
-                    lone = not live and self.q.empty() and not (self.per_slot_sampling and joins and held.seed is not None)
+                    # (chunk_history: a job with chunks behind it runs in the session too -- its history is a slot's)
+                    lone = not live and self.q.empty() and not (self.per_slot_sampling and joins and
+                                                                (held.seed is not None or getattr(held, "next", None) is not None))
                     if not joins or lone:
                         if not live:  # drain first; then the batch-1 path
                             if sess is not None:
@@ -369,7 +445,7 @@ class Scheduler:
                         try:
                             slot, hit = self._session_add(sess, held)
                         except BaseException as e:  # a bad request (prompt longer than max_seq_len, ...) fails ALONE: the live slots go on
-                            held.future.set_exception(e)
+                            self._fail(held, e)
                             held = None
                             continue
                         if slot is not None:
@@ -399,9 +475,17 @@ class Scheduler:
                         if done:
                             codes, _ = sess.poll(slot)
                             hidden = sess.poll_hidden(slot) if live[slot].collect_hidden else None
+                            failed = codes.shape[1] >= self.s.max_new_tokens
+                            # chunk_history: the next chunk of the request takes this slot's history before the slot goes
+                            nxt = getattr(live[slot], "next", None)
+                            turn = None if failed or stopping else self._turn_add(sess, slot, live[slot], codes)
                             sess.release(slot)
                             jb = live.pop(slot)
                             jb.sess_slot = None
+                            if turn is not None:  # (the old slot's pages the turn shares stay until the turn's slot is released)
+                                live[turn] = nxt
+                                self.stats["jobs"] += 1
+                                self.stats["batched_rows"] += 1
                             try:  # (jb has left `live`: from here on fail_all no longer sees it, so its future is resolved right here)
                                 if codes.shape[1] >= self.s.max_new_tokens:  # speech.rs:41-61 "Failed generation suspected. Rerolling once":
                                     self.stats["rerolls"] += 1               # the re-roll takes the batch-1 path once the session has drained
@@ -411,9 +495,9 @@ class Scheduler:
                                     self.q.put(jb)
                                 else:
                                     jb.future.set_result(self._result(jb, codes, hidden))
+                                    self._after(jb)  # (chunk_history: a next chunk that could not take the history joins like any job)
                             except BaseException as e:
-                                if not jb.future.done():
-                                    jb.future.set_exception(e)
+                                self._fail(jb, e)
             except BaseException as e:  # every in-flight request gets the error (AppError -> HTTP 500); the session is rebuilt
                 fail_all(e)
                 held = None
@@ -484,6 +568,7 @@ class Scheduler:
             kw = dict(sampling=sa.kw(), seed=(j.seed if j.seed is not None else self.s.seed_source()) & (2**64 - 1))
         if j.collect_hidden:  # any session kind (fs_lm_session_add_hidden); the rows come back through poll_hidden
             kw["collect_hidden"] = True
+        j.sess_L = (j.cond.shape[1] if j.cond is not None else 0) + j.body.shape[1]  # (chunk_history: the slot's prompt length)
         if not self.session_prefixes or j.cond is None or j.cond.shape[1] < 1 or j.body.shape[1] < 1:
             return sess.add(j.full_prompt(), self.s.max_new_tokens, **kw), False
         pid = self.prefixes.get(j.cond_key)
@@ -562,9 +647,10 @@ class Scheduler:
                     raise RuntimeError("Encoded input failed for second time. Bailing")
                 codes = codes2
             j.future.set_result(self._result(j, codes, hidden))
+            self._after(j)
         except BaseException as e:
             self.cached_key = None
-            j.future.set_exception(e)
+            self._fail(j, e)
 
     def _batched(self, jobs):
         assert not any(j.collect_hidden for j in jobs), "a job that collects hidden states never joins a lock-step batch"
@@ -660,7 +746,12 @@ def generate_speech(state, req):
         sa, seed = _request_sampling(state, req)
         per_slot = getattr(state.scheduler, "per_slot_sampling", False)
         want_batch = int(req.get("batch_size") or 1) > 1 or getattr(state, "auto_batch", False) or per_slot
-        if sa is None and seed is None:
+        if getattr(state, "chunk_history", False) and len(bodies) > 1:  # the chunks as turns of one conversation (module docstring)
+            enc = fprompt.PromptEncoder(state.lm.tokenizer, state.lm.lm.cfg["num_codebooks"], state.lm.model_type)
+            seeds = None if seed is None else [(seed + i) & (2**64 - 1) for i in range(len(bodies))]
+            futs = state.scheduler.submit_turns(cond, bodies, n_cond, state.lm.max_batch > 1 and want_batch, enc.tokenize_text("<|im_end|>"),
+                                                sampling=sa, seeds=seeds)
+        elif sa is None and seed is None:
             futs = [state.scheduler.submit(cond, b, n_cond, state.lm.max_batch > 1 and want_batch) for b in bodies]
         else:  # (chunk i of a seeded request draws from seed + i, as fishrt.lm.LM does)
             futs = [state.scheduler.submit(cond, b, n_cond, state.lm.max_batch > 1 and want_batch, sampling=sa,

@@ -595,6 +595,46 @@ int fs_lm_session_prefix_export(fs_lm_t* lm, int prefix_id, void* blob_out, size
  * Blobs are portable between session kinds and between handles with equal fingerprints. */
 int fs_lm_session_prefix_import(fs_lm_t* lm, const void* blob, size_t bytes, int* prefix_id);
 
+/* ---- prefixes from a slot's history (no reference counterpart): multi-turn continuity, forks, "this voice, having said this".
+ * fs_lm_session_prefix_from_slot makes a session prefix out of the first P cached positions of `slot` -- K/V rows the slot's prefill and
+ * its DECODE steps wrote -- without running anything through the slow transformer.  The result is an ordinary prefix:
+ * fs_lm_session_add_prefixed / _add_ex / _add_hidden / _add_scored / _add_traced on it, fs_lm_session_prefix_export, _prefix_release,
+ * fs_lm_session_end and fs_lm_session_info treat it exactly as a created one.  The source slot is unchanged: it keeps generating if it
+ * is live, keeps its frames and records, is released by its caller as before, and its later codes are bit for bit what they would have
+ * been without the call.
+ * How many positions are history: with L the slot's total prompt length (its prefix included) and n the frames it has emitted so far
+ * (fs_lm_session_poll's *n_frames; 0 before its first step) the slot has T = L + n - 1 positions to give, in every state -- live,
+ * finished on its budget, finished on <|im_end|>.  The column of the last emitted frame is never part of them: a live slot feeds it with
+ * its next step, a slot finished on its budget never fed it, and a slot frozen by <|im_end|> (or dead at frame 0) keeps rewriting row T
+ * with the <|im_end|> column while it rides the step.  Rows [0, T) are never written again by anyone.
+ * n_positions == -1: P = T.  Otherwise 1 <= n_positions <= T and P = n_positions: a cut may lie inside the prompt or at any frame.
+ * P < max_seq_len, as for every prefix (it must leave room for a body).  *P_out (nullable) = P.
+ * Pages: the prefix takes one more reference on the slot's first P / 64 pages (also on pages the slot itself shares from another prefix:
+ * chains of turns keep sharing) and, when P % 64 != 0, ONE new page from the pool, into which the slot's page P / 64 is copied
+ * (k_kv_page_copy; rows [64 (P / 64), P) are the ones that count) on the decode stream, behind every step already enqueued; the call
+ * returns when the copy is done, so it is ahead of any add on the prefix.  It counts in `tail pages copied`; no other counter of
+ * fs_lm_session_info moves (no prefill pass, no tokens prefilled).  When that page is not free right now *prefix_id = -1 and nothing has
+ * changed (not an error, as fs_lm_session_prefix_create); with P % 64 == 0 no page is taken and the call cannot be refused for room.
+ * Everything from page T / 64 on stays the slot's alone, so the single-writer rule holds for a live and for a frozen source.
+ * A slot still prefilling is first let finish and activated, as fs_lm_session_release does.
+ * Valid in plain and FS_SESSION_PER_SLOT sessions with any of the WIDE / SCORE / TRACE / ALTS flags, on bf16 and fp8 handles, Fish 1.5 and
+ * Fish <= 1.4 token layouts, for plain, collecting, scoring and traced source slots.  FS_SESSION_ROWS sessions refuse with an error that
+ * says so.  Errors (each names its field and leaves the session as it was): no open session, not a live slot, n_positions outside
+ * [1, T], T < 1 (a one-column prompt before its first step), P >= max_seq_len.
+ * Semantics: let S be the slot's token history [C+1, L + n] -- its prompt columns, then one column per emitted frame.  A slot admitted on
+ * the new prefix with body B is fs_lm_session_add_ex(concat(S[:, :P], B)) in every respect -- iteration count from P + L_body, max_seq_len
+ * rule, admission number, own seed and settings, frame-0 rule, fresh repetition-penalty window, fresh StdRng stream -- except that rows
+ * [0, P) are the ones the source slot computed (decode-step rows are not a prefill pass's rows) and only the body is prefilled.  To
+ * continue a slot exactly where it stands: P = T and a body that starts with fs_lm_session_last_frame's column.  No kernel and no step
+ * graph is specific to this call: sessions that never make it replay exactly the graphs they did before. */
+int fs_lm_session_prefix_from_slot(fs_lm_t* lm, int slot, int n_positions, int* prefix_id, int* P_out);
+/* column u32 [C+1] = the full input column [slow token, c0..c7] of the slot's last emitted frame, exactly as the engine would feed it
+ * next (the host mirror of the slot's state after fs_lm_session_step).  The slow token of a Fish 1.5 frame is sampled, not derivable
+ * from code 0, and fs_lm_session_poll does not return it: a continuation needs this call to be exact.  An error before the slot's first
+ * frame.  For a cut at an EARLIER frame the caller needs that frame's slow token from elsewhere: a traced slot's token rows
+ * (fs_lm_session_poll_trace) or the frames it forced a scoring slot along. */
+int fs_lm_session_last_frame(fs_lm_t* lm, int slot, uint32_t* column);
+
 /* timing of the last generate call, measured with HIP events on the handle's stream (the reference prints the
  * same quantities: single_batch.rs:233-246,291-304) */
 typedef struct fs_gen_stats {
