@@ -23,6 +23,14 @@ class CodecBase {
     // ragged: item i advances stream ids[i] by T[i] >= 1 frames; codes = the items' (8, T[i]) blocks concatenated, pcm_out = their PCM concatenated
     virtual void streams_decode_ragged(int n, const int* ids, const int* T, const uint32_t* codes, float* pcm_out) = 0;
     virtual void encode(const float* pcm, int n, uint32_t* codes_out, size_t cap, size_t* L_out) = 0;
+    // ---- device sample-rate conversion of the PCM (fs_codec_*_pcm, include/fishrt.h; codec_resample.hip).  spec = {rate, mode, format}
+    virtual void decode_pcm(const uint32_t* codes, int b, int T, const int* spec3, void* out, size_t cap, int64_t* n_out) = 0;
+    virtual int streams_open_pcm(const int* spec3) = 0;
+    virtual int64_t streams_pending(int id, int T, bool final) = 0;
+    virtual void streams_decode_pcm(int n, const int* ids, const int* T, const uint8_t* final, const uint32_t* codes, void* out,
+                                    size_t cap_bytes, int64_t* n_out) = 0;
+    virtual void encode_pcm(const float* pcm, int channels, int64_t frames, int rate, int mode, uint32_t* codes_out, size_t cap,
+                            size_t* L_out) = 0;
     virtual int sample_rate() = 0;
     virtual void set_precision(int mode) = 0;  // 0 = f32 (exact f32 products), 1 = bf16x3, 2 = f16 (default); decode only
     virtual int precision() = 0;
@@ -37,6 +45,10 @@ CodecBase* make_codec(int device, int channel_div);
 struct fs_conv_case;  // include/fishrt.h
 
 namespace fs {
+
+// fs_resample: b host rows of their own lengths, host -> device -> host, no codec handle
+void resample_rows(int device, const float* pcm, int b, size_t stride, const int64_t* n_samples, int from_rate, const int* spec3, void* out,
+                   size_t out_stride, int64_t* out_len);
 
 // fs_selftest_conv1d: one conv through re-layout, pack, plane producers and one launcher of codec_kernels.h (see include/fishrt.h)
 void codec_conv_selftest(int device, const fs_conv_case& c, float* y_out, float* planes_out, char* variant_out, size_t variant_cap,

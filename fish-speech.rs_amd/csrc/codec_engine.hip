@@ -9,12 +9,14 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/fishrt.h"
 #include "codec_kernels.h"
+#include "codec_resample.h"
 #include "fs_common.h"
 #include "fs_synth.h"
 #include "safetensors.h"
@@ -248,6 +250,7 @@ class Codec final : public CodecBase {
         FS_HIP(hipMemsetAsync((uint8_t*)mpool_p_.p + (size_t)id * ms_stream_p_bytes(), 0, ms_stream_p_bytes(), st_));
         FS_HIP(hipMemsetAsync((uint8_t*)mpool_f_.p + (size_t)id * ms_stream_f_bytes(), 0, ms_stream_f_bytes(), st_));
         FS_HIP(hipStreamSynchronize(st_));
+        ms_[id] = MStream{};  // a reopened id starts clean: plain, nothing seen, not flushed
         ms_[id].chunk = 0;
         ms_[id].prec = precision();
         return id;
@@ -264,6 +267,7 @@ class Codec final : public CodecBase {
             FS_REQUIRE(ids[b] >= 0 && ids[b] < (int)ms_.size() && ms_[ids[b]].chunk >= 0, "not an open stream id of this codec handle");
             for (int a = 0; a < b; ++a) FS_REQUIRE(ids[a] != ids[b], "a stream id appears twice in one call");
             FS_REQUIRE(precision() == ms_[ids[b]].prec, "the precision mode changed since the stream was opened");
+            FS_REQUIRE(!ms_[ids[b]].spec, kSpecStreamMsg);
         }
         check_codes(codes, (size_t)n * 8 * T);
         fill_offset_table(n, ids, 4);
@@ -283,18 +287,18 @@ class Codec final : public CodecBase {
             ms_tab_[2 * n + 2 * b + 1] = (long long)(((size_t)2 * s + (par ^ 1)) * fb / 4);
         }
     }
-    void run_streams(const uint32_t* codes, int n, int T, float* pcm_out, int kind) {
+    void run_streams(const uint32_t* codes, int n, int T, float* pcm_out, int kind, const float** dev_pcm = nullptr) {
         const bool chk = range_check_ && bf3_ && f16_;
         if (chk) {
             std::lock_guard<std::mutex> g(range_guard_mutex());
             codec_range_check(true); codec_range_reset(st_);
-            try { decode_impl(codes, n, T, pcm_out, kind); } catch (...) { codec_range_check(false); throw; }
+            try { decode_impl(codes, n, T, pcm_out, kind, dev_pcm); } catch (...) { codec_range_check(false); throw; }
             codec_range_check(false);
             unsigned long long r[2] = {0, 0};
             codec_range_read(r, st_);
             range_act_[0] += r[0]; range_act_[1] += r[1];
         } else {
-            decode_impl(codes, n, T, pcm_out, kind);
+            decode_impl(codes, n, T, pcm_out, kind, dev_pcm);
         }
     }
 
@@ -313,10 +317,16 @@ class Codec final : public CodecBase {
             FS_REQUIRE(ids[b] >= 0 && ids[b] < (int)ms_.size() && ms_[ids[b]].chunk >= 0, "not an open stream id of this codec handle");
             for (int a = 0; a < b; ++a) FS_REQUIRE(ids[a] != ids[b], "a stream id appears twice in one call");
             FS_REQUIRE(precision() == ms_[ids[b]].prec, "the precision mode changed since the stream was opened");
+            FS_REQUIRE(!ms_[ids[b]].spec, kSpecStreamMsg);
             Tmax = std::max(Tmax, T[b]);
             total += (size_t)T[b];
         }
         check_codes(codes, total * 8);
+        ragged_launch(n, ids, T, Tmax, codes, pcm_out, nullptr);
+        for (int b = 0; b < n; ++b) ++ms_[ids[b]].chunk;  // only after the whole call went through
+    }
+    // the launch sequence of a validated ragged call; with dev_pcm the packed PCM stays on the device (decode_impl)
+    void ragged_launch(int n, const int* ids, const int* T, int Tmax, const uint32_t* codes, float* pcm_out, const float** dev_pcm) {
         // codes [n][8][Tmax], item b's rows filled up to T[b] (index 0 behind it: a valid code whose output nothing reads)
         rag_codes_.assign((size_t)n * 8 * Tmax, 0u);
         {
@@ -332,8 +342,165 @@ class Codec final : public CodecBase {
             ms_tab_[(size_t)5 * n + b] = at;
             at += spf * T[b];
         }
-        run_streams(rag_codes_.data(), n, Tmax, pcm_out, kRagged);
-        for (int b = 0; b < n; ++b) ++ms_[ids[b]].chunk;  // only after the whole call went through
+        run_streams(rag_codes_.data(), n, Tmax, pcm_out, kRagged, dev_pcm);
+    }
+
+    // ---- device sample-rate conversion of the vocoder's PCM and the encoder's input (fs_codec_*_pcm; kernels in codec_resample.hip, counting
+    // in fs_resample_plan.h).  The PCM is converted where the vocoder left it, before the copy to the host.  A spec at the codec's own rate is
+    // a format conversion only (kResampleCopy), whatever its mode.
+    static void parse_spec(const int* s3, int from, int to, int& mode, int& format, ResampleRates& r) {
+        FS_REQUIRE(s3[0] > 0, "fs_pcm_spec: the rate must be positive");
+        FS_REQUIRE(s3[1] == FS_RESAMPLE_LINEAR || s3[1] == FS_RESAMPLE_SINC, "fs_pcm_spec: mode is FS_RESAMPLE_LINEAR or FS_RESAMPLE_SINC");
+        FS_REQUIRE(s3[2] == FS_PCM_F32 || s3[2] == FS_PCM_S16, "fs_pcm_spec: format is FS_PCM_F32 or FS_PCM_S16");
+        r = resample_rates(from, to);
+        mode = from == to ? (int)kResampleCopy : s3[1];
+        format = s3[2];
+        if (mode == kResampleSinc) resample_require_table(r);
+    }
+    static size_t pcm_bytes(int format) { return format == kPcmS16 ? 2 : 4; }
+
+    void decode_pcm(const uint32_t* codes, int B, int T, const int* spec3, void* out, size_t cap, int64_t* n_out) override {
+        FS_HIP(hipSetDevice(device_));
+        FS_REQUIRE(B >= 1 && T >= 1, "empty input");
+        int mode, format;
+        ResampleRates r;
+        parse_spec(spec3, sample_rate(), spec3[0], mode, format, r);
+        const int64_t n_in = (int64_t)samples_per_frame() * T, ol = resample_out_len(r, mode, n_in);
+        FS_REQUIRE((int64_t)cap >= ol, "fs_codec_decode_pcm: cap is smaller than fs_resample_out_len of a row");
+        const float* d = nullptr;
+        decode_impl(codes, B, T, nullptr, kOneShot, &d);
+        const size_t esz = pcm_bytes(format), row = ((size_t)ol * esz + 3) & ~(size_t)3;
+        rs_out_.ensure((size_t)B * row);
+        std::vector<ResampleItem> items((size_t)B);
+        for (int b = 0; b < B; ++b) {
+            ResampleItem& it = items[(size_t)b];
+            resampler().set_rates(it, r, mode);
+            it.format = format;
+            it.src = d + (size_t)b * n_in; it.n_src = n_in;
+            it.out = (uint8_t*)rs_out_.p + (size_t)b * row; it.n_out = ol;
+        }
+        resampler().run(items);
+        for (int b = 0; b < B; ++b) {
+            FS_HIP(hipMemcpyAsync((uint8_t*)out + (size_t)b * cap * esz, (const uint8_t*)rs_out_.p + (size_t)b * row, (size_t)ol * esz, hipMemcpyDeviceToHost, st_));
+            n_out[b] = ol;
+        }
+        FS_HIP(hipStreamSynchronize(st_));
+    }
+
+    int streams_open_pcm(const int* spec3) override {
+        int mode, format;
+        ResampleRates r;
+        parse_spec(spec3, sample_rate(), spec3[0], mode, format, r);
+        const int id = streams_open();
+        auto& s = ms_[id];
+        s.spec = true; s.mode = mode; s.format = format; s.rates = r;
+        if (mode != kResampleCopy) {
+            s.carry_cap = resample_carry_cap(r, mode);
+            s.carry = std::make_shared<DBuf>();
+            try { s.carry->alloc((size_t)2 * s.carry_cap * sizeof(float)); } catch (...) { s.chunk = -1; throw; }
+        }
+        return id;
+    }
+    void require_open(int id) const {
+        FS_REQUIRE(id >= 0 && id < (int)ms_.size() && ms_[id].chunk >= 0, "not an open stream id of this codec handle");
+    }
+    int64_t streams_pending(int id, int T, bool final) override {
+        require_open(id);
+        const auto& s = ms_[id];
+        FS_REQUIRE(T >= 0 && T <= (1 << 20), "a chunk of 0 .. 2^20 frames");
+        return resample_plan_step(s.rates, s.mode, s.book, (int64_t)samples_per_frame() * T, final).n_emit;
+    }
+    void streams_decode_pcm(int n, const int* ids, const int* T, const uint8_t* final, const uint32_t* codes, void* out, size_t cap_bytes,
+                            int64_t* n_out) override {
+        FS_HIP(hipSetDevice(device_));
+        // everything is validated and counted before the first launch: a rejected call leaves the vocoder contexts and the books as they were
+        FS_REQUIRE(n >= 1 && n <= kMaxStreams, "fs_codec_streams_decode_pcm takes 1 .. 64 streams per call");
+        const int64_t spf = (int64_t)samples_per_frame();
+        std::vector<ResampleStep> steps((size_t)n);
+        std::vector<size_t> doff((size_t)n);  // byte offset of the item's row in rs_out_ (4-byte aligned; the caller's buffer is packed)
+        std::vector<int> vid, vT;
+        int Tmax = 0;
+        size_t total_codes = 0, packed = 0, dbytes = 0;
+        for (int b = 0; b < n; ++b) {
+            require_open(ids[b]);
+            const auto& s = ms_[ids[b]];
+            for (int a = 0; a < b; ++a) FS_REQUIRE(ids[a] != ids[b], "a stream id appears twice in one call");
+            FS_REQUIRE(precision() == s.prec, "the precision mode changed since the stream was opened");
+            const bool fin = final && final[b];
+            FS_REQUIRE(T[b] >= 0 && T[b] <= (1 << 20), "a chunk of 0 .. 2^20 frames");
+            FS_REQUIRE(T[b] >= 1 || fin, "an item of 0 frames must be final (a pure flush)");
+            FS_REQUIRE(!s.book.final, "the stream was already flushed by a final item (fs_codec_streams_close it)");
+            steps[(size_t)b] = resample_plan_step(s.rates, s.mode, s.book, spf * T[b], fin);
+            FS_REQUIRE(steps[(size_t)b].carry_len <= s.carry_cap, "resample carry exceeds the stream's carry rows");
+            doff[(size_t)b] = dbytes;
+            packed += (size_t)steps[(size_t)b].n_emit * pcm_bytes(s.format);
+            dbytes += ((size_t)steps[(size_t)b].n_emit * pcm_bytes(s.format) + 3) & ~(size_t)3;
+            if (T[b] >= 1) { vid.push_back(ids[b]); vT.push_back(T[b]); Tmax = std::max(Tmax, T[b]); total_codes += (size_t)T[b] * 8; }
+        }
+        FS_REQUIRE(packed <= cap_bytes, "fs_codec_streams_decode_pcm: cap_bytes is smaller than the samples this call emits (fs_codec_streams_pending)");
+        check_codes(codes, total_codes);
+        const float* d = nullptr;
+        if (!vid.empty()) ragged_launch((int)vid.size(), vid.data(), vT.data(), Tmax, codes, nullptr, &d);
+        rs_out_.ensure(dbytes);
+        std::vector<ResampleItem> items((size_t)n);
+        int64_t at = 0;
+        for (int b = 0; b < n; ++b) {
+            const auto& s = ms_[ids[b]];
+            const ResampleStep& p = steps[(size_t)b];
+            ResampleItem& it = items[(size_t)b];
+            resampler().set_rates(it, s.rates, s.mode);
+            it.format = s.format;
+            it.in0 = p.in0; it.n_src = spf * T[b]; it.out0 = p.out0; it.n_out = p.n_emit;
+            if (T[b] >= 1) { it.src = d + at; at += it.n_src; }
+            if (s.carry) {
+                it.carry = s.carry->f() + (size_t)s.par * s.carry_cap; it.carry_len = (int)s.book.carry_len;
+                it.carry_out = s.carry->f() + (size_t)(s.par ^ 1) * s.carry_cap; it.new_carry_len = (int)p.carry_len;
+            }
+            it.out = (uint8_t*)rs_out_.p + doff[(size_t)b];
+        }
+        resampler().run(items);
+        rs_host_.resize(dbytes);
+        if (dbytes) FS_HIP(hipMemcpyAsync(rs_host_.data(), rs_out_.p, dbytes, hipMemcpyDeviceToHost, st_));
+        FS_HIP(hipStreamSynchronize(st_));
+        uint8_t* dst = (uint8_t*)out;
+        for (int b = 0; b < n; ++b) {  // only after the whole call went through
+            auto& s = ms_[ids[b]];
+            const size_t bytes = (size_t)steps[(size_t)b].n_emit * pcm_bytes(s.format);
+            if (bytes) std::memcpy(dst, rs_host_.data() + doff[(size_t)b], bytes);
+            dst += bytes;
+            n_out[b] = steps[(size_t)b].n_emit;
+            if (T[b] >= 1) ++s.chunk;
+            if (s.carry) s.par ^= 1;
+            resample_commit(s.book, steps[(size_t)b], final && final[b]);
+        }
+    }
+
+    // downmix, resample to the codec's rate, encode: the clip goes to the device once and only the codes come back
+    void encode_pcm(const float* pcm, int channels, int64_t frames, int rate, int mode_in, uint32_t* codes_out, size_t cap, size_t* L_out) override {
+        FS_HIP(hipSetDevice(device_));
+        FS_REQUIRE(loaded_, "weights not loaded: call fs_codec_load_safetensors or fs_codec_load_synthetic first");
+        FS_REQUIRE(channels >= 1 && channels <= 64 && frames >= 1 && frames < (1ll << 31), "fs_codec_encode_pcm: 1 .. 64 channels, 1 .. 2^31 - 1 frames");
+        const int spec3[3] = {sample_rate(), mode_in, FS_PCM_F32};
+        int mode, format;
+        ResampleRates r;
+        parse_spec(spec3, rate, sample_rate(), mode, format, r);
+        const int64_t n = resample_out_len(r, mode, frames);
+        (void)encode_frames(n);
+        const size_t in_elems = (size_t)frames * channels;
+        rs_mix_.ensure((in_elems + (channels > 1 ? (size_t)frames : 0)) * sizeof(float));
+        FS_HIP(hipMemcpyAsync(rs_mix_.p, pcm, in_elems * sizeof(float), hipMemcpyHostToDevice, st_));
+        const float* mono = rs_mix_.f();
+        if (channels > 1) {
+            codec_downmix(rs_mix_.f(), channels, frames, rs_mix_.f() + in_elems, st_);
+            mono = rs_mix_.f() + in_elems;
+        }
+        dpcm_.ensure(sizeof(float) * (size_t)n);
+        std::vector<ResampleItem> items(1);
+        resampler().set_rates(items[0], r, mode);
+        items[0].src = mono; items[0].n_src = frames;
+        items[0].out = dpcm_.p; items[0].n_out = n;
+        resampler().run(items);
+        encode_device((int)n, codes_out, cap, L_out);
     }
 
     static constexpr int kCtxSlots = 96, kStreamMinFrames = 16;
@@ -348,7 +515,8 @@ class Codec final : public CodecBase {
 
     // decode_impl's `streaming`: none, fs_codec_stream_*, fs_codec_streams_decode, fs_codec_streams_decode_ragged (T = the longest item)
     enum { kOneShot = 0, kSingle = 1, kMulti = 2, kRagged = 3 };
-    void decode_impl(const uint32_t* codes, int B, int T, float* pcm_out, int streaming) {
+    // dev_pcm: leave the PCM on the device (*dev_pcm, rows as pcm_out would get them) for the resampler: no copy to the host, no synchronisation
+    void decode_impl(const uint32_t* codes, int B, int T, float* pcm_out, int streaming, const float** dev_pcm = nullptr) {
         FS_HIP(hipSetDevice(device_));
         FS_REQUIRE(loaded_, "weights not loaded: call fs_codec_load_safetensors or fs_codec_load_synthetic first");
         FS_REQUIRE(B >= 1 && T >= 1, "empty input");
@@ -531,11 +699,13 @@ class Codec final : public CodecBase {
             size_t total = 0;
             for (int b = 0; b < B; ++b) total += (size_t)ms_tab_[(size_t)4 * B + b] * (size_t)(Tc / T);
             codec_gather_ragged(t1, B, Tc, rl, tab_p + 5 * B, t2, st_);
+            if (dev_pcm) { *dev_pcm = t2; return; }
             FS_HIP(hipMemcpyAsync(pcm_out, t2, sizeof(float) * total, hipMemcpyDeviceToHost, st_));
             FS_HIP(hipStreamSynchronize(st_));
             return;
         }
         if (streaming) codec_save_tail_f32(x, B, ch, Tc, fp.co, st_, fp.off);
+        if (dev_pcm) { *dev_pcm = t1; return; }
         FS_HIP(hipMemcpyAsync(pcm_out, t1, sizeof(float) * (size_t)B * Tc, hipMemcpyDeviceToHost, st_));
         FS_HIP(hipStreamSynchronize(st_));
     }
@@ -544,17 +714,27 @@ class Codec final : public CodecBase {
     void encode(const float* pcm, int n, uint32_t* codes_out, size_t cap, size_t* L_out) override {
         FS_HIP(hipSetDevice(device_));
         FS_REQUIRE(loaded_, "weights not loaded: call fs_codec_load_safetensors or fs_codec_load_synthetic first");
-        use_bf3_now_ = false;  // the indices are a discontinuous function of the activations: exact-f32 products only
+        (void)encode_frames(n);
+        dpcm_.ensure(sizeof(float) * n);
+        FS_HIP(hipMemcpyAsync(dpcm_.p, pcm, sizeof(float) * n, hipMemcpyHostToDevice, st_));
+        encode_device(n, codes_out, cap, L_out);
+    }
+    // mel frames of an n-sample clip, or the reason it cannot be encoded
+    static int encode_frames(long long n) {
         const int pad = (kFft - kHop) / 2;
         if (n < pad) throw Error("input shorter than the reflect padding (range end index out of range, spectrogram.rs:19)");
+        FS_REQUIRE(n < (1ll << 31) - 2 * pad, "clip too long");
         const long long Lp = (long long)n + 2 * pad, full = Lp / kHop, rem = Lp % kHop;
         long long F = std::max(0LL, full - (kFft / kHop - 1));  // frames the streaming STFT emits (stft.rs:52-90)
         if (rem > 0 && Lp >= kFft) F += 1;
         FS_REQUIRE(F >= 4, "clip too short: the quantizer downsamples 4 mel frames into one code");
-        const int T = (int)F, G = 8, nf = kFft / 2 + 1;
+        return (int)F;
+    }
+    // the encoder on the n mono samples at the codec rate that dpcm_ holds on the device
+    void encode_device(int n, uint32_t* codes_out, size_t cap, size_t* L_out) {
+        use_bf3_now_ = false;  // the indices are a discontinuous function of the activations: exact-f32 products only
+        const int T = encode_frames(n), G = 8, nf = kFft / 2 + 1;
         ensure_mel_table();
-        dpcm_.ensure(sizeof(float) * n);
-        FS_HIP(hipMemcpyAsync(dpcm_.p, pcm, sizeof(float) * n, hipMemcpyHostToDevice, st_));
         const size_t act = (size_t)std::max(nf, 4 * C_) * T;  // largest activation: lin (1025 x T) or a ConvNeXt hidden (4C x T)
         for (int i = 0; i < 4; ++i) buf_[i].ensure(act * sizeof(float));
         float *x = buf_[0].f(), *t1 = buf_[1].f(), *t2 = buf_[2].f(), *r = buf_[3].f();
@@ -806,7 +986,24 @@ class Codec final : public CodecBase {
     DBuf raw_, relaid_, packed_, packed16_, dcodes_, buf_[7], pbuf_[5];
     DBuf sctx_p_[2], sctx_f_[2];            // streaming contexts (plane tensors / f32 conv inputs), ping-pong per chunk
     int stream_chunk_ = -1, stream_prec_ = 0;  // -1: no stream open
-    struct MStream { int chunk = -1, prec = 0; };  // chunk: chunks decoded so far (its parity picks the "in" half), -1 = id free
+    // chunk: chunks decoded so far (its parity picks the "in" half), -1 = id free.  spec: opened by fs_codec_streams_open_pcm; mode / format /
+    // rates: how its PCM leaves (a plain stream: copy, f32); book: samples in and out so far; carry: two rows of resample_carry_cap samples,
+    // row `par` holds the carry_len samples in front of the next chunk
+    struct MStream {
+        int chunk = -1, prec = 0;
+        bool spec = false;
+        int mode = kResampleCopy, format = kPcmF32, par = 0;
+        ResampleRates rates;
+        ResampleBook book;
+        std::shared_ptr<DBuf> carry;
+        int64_t carry_cap = 0;
+    };
+    static constexpr const char* kSpecStreamMsg =
+        "the stream was opened with a PCM spec (fs_codec_streams_open_pcm): decode it with fs_codec_streams_decode_pcm";
+    std::unique_ptr<Resampler> rs_;                // made on first use, on st_
+    DBuf rs_out_, rs_mix_;                         // the resampled rows of a call; the downmixed clip of fs_codec_encode_pcm
+    std::vector<uint8_t> rs_host_;                 // host side of rs_out_ (rows at 4-byte aligned offsets), unpacked into the caller's buffer
+    Resampler& resampler() { if (!rs_) rs_.reset(new Resampler(st_)); return *rs_; }
     std::vector<MStream> ms_;                      // fs_codec_streams_*, index = stream id
     int ms_cap_ = 0;                               // streams the pools hold
     DBuf mpool_p_, mpool_f_, dtab_;                // context pools [stream][half][...] and the per-call device offset table
@@ -832,6 +1029,62 @@ class Codec final : public CodecBase {
 };
 
 CodecBase* make_codec(int device, int channel_div) { return new Codec(device, channel_div); }
+
+// fs_resample (include/fishrt.h): the rows go to the device, through ONE ragged launch of the resampler, and back.  Follows the two definitions
+// to the letter, equal rates included (linear: the identity; sinc: the 1 x 15 filter)
+void resample_rows(int device, const float* pcm, int b, size_t stride, const int64_t* n_samples, int from_rate, const int* spec3, void* out,
+                   size_t out_stride, int64_t* out_len) {
+    FS_REQUIRE(b >= 1 && b <= 4096, "fs_resample takes 1 .. 4096 rows");
+    FS_REQUIRE(from_rate > 0 && spec3[0] > 0, "fs_resample: sample rates must be positive");
+    FS_REQUIRE(spec3[1] == FS_RESAMPLE_LINEAR || spec3[1] == FS_RESAMPLE_SINC, "fs_pcm_spec: mode is FS_RESAMPLE_LINEAR or FS_RESAMPLE_SINC");
+    FS_REQUIRE(spec3[2] == FS_PCM_F32 || spec3[2] == FS_PCM_S16, "fs_pcm_spec: format is FS_PCM_F32 or FS_PCM_S16");
+    const ResampleRates r = resample_rates(from_rate, spec3[0]);
+    const int mode = spec3[1], format = spec3[2];
+    if (mode == kResampleSinc) resample_require_table(r);  // refused before anything touches the device
+    const size_t esz = format == kPcmS16 ? 2 : 4;
+    std::vector<int64_t> ol((size_t)b);
+    std::vector<size_t> ioff((size_t)b), ooff((size_t)b);
+    size_t in_elems = 0, out_bytes = 0;
+    for (int i = 0; i < b; ++i) {
+        FS_REQUIRE(n_samples[i] >= 0 && (size_t)n_samples[i] <= stride && n_samples[i] < (1ll << 40), "fs_resample: a row's length must be in 0 .. stride");
+        ol[(size_t)i] = resample_out_len(r, mode, n_samples[i]);
+        FS_REQUIRE((size_t)ol[(size_t)i] <= out_stride, "fs_resample: out_stride is smaller than fs_resample_out_len of a row");
+        ioff[(size_t)i] = in_elems; in_elems += (size_t)n_samples[i];
+        ooff[(size_t)i] = out_bytes; out_bytes += ((size_t)ol[(size_t)i] * esz + 3) & ~(size_t)3;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw Error("no HIP device visible: libfishrt has no CPU fallback (MI355X / gfx950 required)");
+    FS_REQUIRE(device >= 0 && device < ndev, "device_id out of range");
+    FS_HIP(hipSetDevice(device));
+    struct Stream {
+        hipStream_t s = nullptr;
+        ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+    } st;
+    FS_HIP(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    DBuf din, dout;
+    din.alloc(std::max<size_t>(in_elems, 1) * sizeof(float));
+    dout.alloc(std::max<size_t>(out_bytes, 4));
+    {
+        Resampler rs(st.s);
+        std::vector<ResampleItem> items((size_t)b);
+        for (int i = 0; i < b; ++i) {
+            ResampleItem& it = items[(size_t)i];
+            if (n_samples[i])
+                FS_HIP(hipMemcpyAsync(din.f() + ioff[(size_t)i], pcm + (size_t)i * stride, (size_t)n_samples[i] * sizeof(float), hipMemcpyHostToDevice, st.s));
+            rs.set_rates(it, r, mode);
+            it.format = format;
+            it.src = din.f() + ioff[(size_t)i]; it.n_src = n_samples[i];
+            it.out = (uint8_t*)dout.p + ooff[(size_t)i]; it.n_out = ol[(size_t)i];
+        }
+        rs.run(items);
+        for (int i = 0; i < b; ++i) {
+            if (ol[(size_t)i])
+                FS_HIP(hipMemcpyAsync((uint8_t*)out + (size_t)i * out_stride * esz, (const uint8_t*)dout.p + ooff[(size_t)i], (size_t)ol[(size_t)i] * esz, hipMemcpyDeviceToHost, st.s));
+            out_len[i] = ol[(size_t)i];
+        }
+        FS_HIP(hipStreamSynchronize(st.s));
+    }
+}
 
 // fs_selftest_conv1d (include/fishrt.h): one conv through the load-time functions (re-layout, pack), the plane producers and ONE launcher of
 // codec_kernels.h, on host data.  Plane buffers are sized as decode_impl sizes them (256 KB of slack for window reads past T) and filled with

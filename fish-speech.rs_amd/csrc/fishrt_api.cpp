@@ -7,6 +7,7 @@
 #include "codec_engine.h"
 #include "fs_comm.h"
 #include "fs_common.h"
+#include "fs_resample_plan.h"
 #include "lm_engine.h"
 #include "lm_kernels.h"
 #include "lm_persist.h"
@@ -392,6 +393,40 @@ int fs_codec_streams_decode(fs_codec_t* c, int n, const int* stream_ids, const u
 int fs_codec_streams_decode_ragged(fs_codec_t* c, int n, const int* stream_ids, const int* T, const uint32_t* codes, float* pcm_out) {
     FS_ARG(c && stream_ids && T && codes && pcm_out, "null argument");
     FS_TRY(c->impl->streams_decode_ragged(n, stream_ids, T, codes, pcm_out))
+}
+static_assert(sizeof(fs_pcm_spec) == 3 * sizeof(int32_t), "fs_pcm_spec is passed to the engine as int[3]");
+int fs_resample_out_len(int from_rate, int to_rate, int mode, int64_t n, int64_t* out_len) {
+    FS_ARG(out_len, "null argument");
+    FS_ARG(mode == FS_RESAMPLE_LINEAR || mode == FS_RESAMPLE_SINC, "mode is FS_RESAMPLE_LINEAR or FS_RESAMPLE_SINC");
+    FS_ARG(n >= 0 && n < ((int64_t)1 << 40), "n out of range");
+    FS_TRY(*out_len = fs::resample_out_len(fs::resample_rates(from_rate, to_rate), mode, n))
+}
+int fs_resample(int device_id, const float* pcm, int b, size_t stride, const int64_t* n_samples, int from_rate, const fs_pcm_spec* out,
+                void* out_buf, size_t out_stride, int64_t* out_len) {
+    FS_ARG(pcm && n_samples && out && out_buf && out_len, "null argument");
+    FS_TRY(fs::resample_rows(device_id, pcm, b, stride, n_samples, from_rate, &out->rate, out_buf, out_stride, out_len))
+}
+int fs_codec_decode_pcm(fs_codec_t* c, const uint32_t* codes, int b, int T, const fs_pcm_spec* spec, void* out, size_t cap, int64_t* n_out) {
+    FS_ARG(c && codes && spec && out && n_out, "null argument");
+    FS_TRY(c->impl->decode_pcm(codes, b, T, &spec->rate, out, cap, n_out))
+}
+int fs_codec_streams_open_pcm(fs_codec_t* c, const fs_pcm_spec* spec, int* stream_id) {
+    FS_ARG(c && spec && stream_id, "null argument");
+    FS_TRY(*stream_id = c->impl->streams_open_pcm(&spec->rate))
+}
+int fs_codec_streams_pending(fs_codec_t* c, int stream_id, int T, int final, int64_t* n_out) {
+    FS_ARG(c && n_out, "null argument");
+    FS_TRY(*n_out = c->impl->streams_pending(stream_id, T, final != 0))
+}
+int fs_codec_streams_decode_pcm(fs_codec_t* c, int n, const int* stream_ids, const int* T, const uint8_t* final, const uint32_t* codes, void* out,
+                                size_t cap_bytes, int64_t* n_out) {
+    FS_ARG(c && stream_ids && T && n_out && (out || cap_bytes == 0), "null argument");
+    FS_TRY(c->impl->streams_decode_pcm(n, stream_ids, T, final, codes, out, cap_bytes, n_out))
+}
+int fs_codec_encode_pcm(fs_codec_t* c, const float* pcm, int channels, int64_t frames, int rate, int mode, uint32_t* codes_out, size_t cap,
+                        size_t* n_frames) {
+    FS_ARG(c && pcm && codes_out && n_frames, "null argument");
+    FS_TRY(c->impl->encode_pcm(pcm, channels, frames, rate, mode, codes_out, cap, n_frames))
 }
 int fs_codec_set_precision(fs_codec_t* c, int mode) { FS_ARG(c, "null argument"); FS_TRY(c->impl->set_precision(mode)) }
 int fs_codec_precision(fs_codec_t* c) { return c ? c->impl->precision() : -1; }

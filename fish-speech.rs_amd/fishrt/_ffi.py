@@ -59,7 +59,10 @@ SYMBOLS = ["fs_last_error", "fs_version", "fs_device_count", "fs_lm_create", "fs
            "fs_lm_weights_fingerprint", "fs_lm_session_prefix_export", "fs_lm_session_prefix_import",
            "fs_lm_session_prefix_from_slot", "fs_lm_session_last_frame",
            "fs_codec_create", "fs_codec_destroy", "fs_codec_load_safetensors", "fs_codec_load_synthetic",
-           "fs_codec_decode", "fs_codec_encode", "fs_codec_encode_batch", "fs_codec_sample_rate", "fs_codec_set_precision", "fs_codec_precision", "fs_codec_set_range_check", "fs_codec_range_stats", "fs_codec_stream_begin", "fs_codec_stream_decode", "fs_codec_stream_end", "fs_codec_streams_open", "fs_codec_streams_close", "fs_codec_streams_decode", "fs_codec_streams_decode_ragged", "fs_fp8_quantize_rows", "fs_fp8_decode_table", "fs_selftest", "fs_lm_selftest", "fs_selftest_sample_rows", "fs_selftest_sample_slots", "fs_lm_debug_capture", "fs_lm_debug_read"]
+           "fs_codec_decode", "fs_codec_encode", "fs_codec_encode_batch", "fs_codec_sample_rate", "fs_codec_set_precision", "fs_codec_precision", "fs_codec_set_range_check", "fs_codec_range_stats", "fs_codec_stream_begin", "fs_codec_stream_decode", "fs_codec_stream_end", "fs_codec_streams_open", "fs_codec_streams_close", "fs_codec_streams_decode", "fs_codec_streams_decode_ragged",
+           "fs_resample_out_len", "fs_resample", "fs_codec_decode_pcm", "fs_codec_streams_open_pcm", "fs_codec_streams_pending",
+           "fs_codec_streams_decode_pcm", "fs_codec_encode_pcm",
+           "fs_fp8_quantize_rows", "fs_fp8_decode_table", "fs_selftest", "fs_lm_selftest", "fs_selftest_sample_rows", "fs_selftest_sample_slots", "fs_lm_debug_capture", "fs_lm_debug_read"]
 
 # flags of fs_lm_generate* / fs_lm_session_begin (include/fishrt.h)
 FS_GEN_IGNORE_EOS, FS_SESSION_ROWS, FS_SESSION_PER_SLOT, FS_SESSION_WIDE_SAMPLER = 1, 8, 16, 32
@@ -107,6 +110,36 @@ HISTORY_PROTOTYPES = {
     "fs_lm_session_last_frame": [C.c_void_p, C.c_int, _U32P],
 }
 
+# device sample-rate conversion (include/fishrt.h: FS_RESAMPLE_*, FS_PCM_*, fs_pcm_spec)
+RESAMPLE_MODES = {"linear": 0, "sinc": 1}
+PCM_FORMATS = {"f32": 0, "s16": 1}
+PCM_DTYPES = {"f32": "<f4", "s16": "<i2"}
+
+
+class PcmSpec(C.Structure):  # fs_pcm_spec
+    _fields_ = [("rate", C.c_int32), ("mode", C.c_int32), ("format", C.c_int32)]
+
+
+def pcm_spec(rate, mode, dtype):
+    if mode not in RESAMPLE_MODES:
+        raise ValueError(f"resample mode must be one of {sorted(RESAMPLE_MODES)}")
+    if dtype not in PCM_FORMATS:
+        raise ValueError(f"PCM dtype must be one of {sorted(PCM_FORMATS)}")
+    return PcmSpec(int(rate), RESAMPLE_MODES[mode], PCM_FORMATS[dtype])
+
+
+_I64P = C.POINTER(C.c_int64)
+RESAMPLE_PROTOTYPES = {
+    "fs_resample_out_len": [C.c_int, C.c_int, C.c_int, C.c_int64, _I64P],
+    "fs_resample": [C.c_int, _F32P, C.c_int, C.c_size_t, _I64P, C.c_int, C.POINTER(PcmSpec), C.c_void_p, C.c_size_t, _I64P],
+    "fs_codec_decode_pcm": [C.c_void_p, _U32P, C.c_int, C.c_int, C.POINTER(PcmSpec), C.c_void_p, C.c_size_t, _I64P],
+    "fs_codec_streams_open_pcm": [C.c_void_p, C.POINTER(PcmSpec), C.POINTER(C.c_int)],
+    "fs_codec_streams_pending": [C.c_void_p, C.c_int, C.c_int, C.c_int, _I64P],
+    "fs_codec_streams_decode_pcm": [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint8), _U32P, C.c_void_p,
+                                    C.c_size_t, _I64P],
+    "fs_codec_encode_pcm": [C.c_void_p, _F32P, C.c_int, C.c_int64, C.c_int, C.c_int, _U32P, C.c_size_t, C.POINTER(C.c_size_t)],
+}
+
 _lib = None
 
 
@@ -126,7 +159,8 @@ def lib():
         L.fs_comm_destroy.argtypes = [C.c_void_p]
         L.fs_lm_destroy.argtypes = [C.c_void_p]
         L.fs_codec_destroy.argtypes = [C.c_void_p]
-        for name, argtypes in {**SCORE_PROTOTYPES, **TRACE_PROTOTYPES, **ALTS_PROTOTYPES, **CONV_PROTOTYPES, **HISTORY_PROTOTYPES}.items():
+        for name, argtypes in {**SCORE_PROTOTYPES, **TRACE_PROTOTYPES, **ALTS_PROTOTYPES, **CONV_PROTOTYPES, **HISTORY_PROTOTYPES,
+                               **RESAMPLE_PROTOTYPES}.items():
             getattr(L, name).argtypes = argtypes
         _lib = L
     return _lib

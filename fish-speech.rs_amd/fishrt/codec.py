@@ -19,6 +19,10 @@ class FireflyCodec:
         _ffi.check(_ffi.lib().fs_codec_set_precision(self._h, self.PRECISIONS[precision]))
         self.precision = precision
 
+    def _dtypes(self):
+        """stream id -> "f32" | "s16" of the streams opened with a PCM spec"""
+        return self.__dict__.setdefault("_stream_dtype", {})
+
     def close(self):
         if getattr(self, "_h", None) and _ffi is not None and getattr(_ffi, "lib", None):  # (module globals are gone at interpreter exit)
             _ffi.lib().fs_codec_destroy(self._h)
@@ -38,13 +42,31 @@ class FireflyCodec:
     def sample_rate(self):
         return _ffi.lib().fs_codec_sample_rate(self._h)
 
-    def decode(self, codes):
+    def _spec(self, sample_rate, resample, dtype):
+        """None when the arguments ask for what the plain calls return (codec rate, f32), else the fs_pcm_spec"""
+        if sample_rate is None and dtype == "f32":
+            return None
+        return _ffi.pcm_spec(self.sample_rate if sample_rate is None else sample_rate, resample, dtype)
+
+    def decode(self, codes, sample_rate=None, resample="linear", dtype="f32"):
+        """sample_rate / dtype: convert every PCM row on the device before it is copied to the host (fishrt.h fs_codec_decode_pcm) ->
+        (b, 1, out_len) f32 or int16; resample: "linear" (the reference's resample, bit for bit) or "sinc" (band-limited)"""
         if not isinstance(codes, np.ndarray) or not codes.flags["C_CONTIGUOUS"]:
             raise ValueError("Input array must be contiguous")  # codec.rs:97-101
         if codes.ndim != 3 or codes.shape[1] != 8:
             raise ValueError("codes must have shape (b, 8, T)")
         codes = codes.astype(np.uint32, copy=False)
         b, _, T = codes.shape
+        spec = self._spec(sample_rate, resample, dtype)
+        if spec is not None:
+            from ._resample import resample_out_len
+            n = resample_out_len(2048 * T, self.sample_rate, spec.rate, resample) if spec.rate != self.sample_rate else 2048 * T
+            out = np.empty((b, 1, max(n, 1)), _ffi.PCM_DTYPES[dtype])
+            got = (C.c_int64 * b)()
+            _ffi.check(_ffi.lib().fs_codec_decode_pcm(self._h, codes.ctypes.data_as(C.POINTER(C.c_uint32)), b, T, C.byref(spec),
+                                                      out.ctypes.data_as(C.c_void_p), C.c_size_t(out.shape[2]), got))
+            assert all(got[i] == n for i in range(b))
+            return out[:, :, :n]
         pcm = np.empty((b, 1, 2048 * T), np.float32)
         _ffi.check(_ffi.lib().fs_codec_decode(self._h, codes.ctypes.data_as(C.POINTER(C.c_uint32)), b, T,
                                               pcm.ctypes.data_as(C.POINTER(C.c_float))))
@@ -87,14 +109,29 @@ class FireflyCodec:
     # ---- many concurrent streams on one handle (fishrt.h fs_codec_streams_*): one launch sequence advances n streams by T frames each
     STREAMS_MAX = 64
 
-    def streams_open(self):
-        """-> stream id: a new stream from zero left context, in the handle's current precision mode"""
+    def streams_open(self, sample_rate=None, resample="linear", dtype="f32"):
+        """-> stream id: a new stream from zero left context, in the handle's current precision mode.  sample_rate / dtype: its PCM leaves
+        converted on the device (fishrt.h fs_codec_streams_open_pcm); such a stream is decoded by streams_decode_ragged only"""
         sid = C.c_int(-1)
-        _ffi.check(_ffi.lib().fs_codec_streams_open(self._h, C.byref(sid)))
+        spec = self._spec(sample_rate, resample, dtype)
+        if spec is None:
+            _ffi.check(_ffi.lib().fs_codec_streams_open(self._h, C.byref(sid)))
+        else:
+            _ffi.check(_ffi.lib().fs_codec_streams_open_pcm(self._h, C.byref(spec), C.byref(sid)))
+        self._dtypes().pop(int(sid.value), None)
+        if spec is not None:
+            self._dtypes()[int(sid.value)] = dtype
         return int(sid.value)
 
     def streams_close(self, stream_id):
         _ffi.check(_ffi.lib().fs_codec_streams_close(self._h, int(stream_id)))
+        self._dtypes().pop(int(stream_id), None)
+
+    def streams_pending(self, stream_id, T, final=False):
+        """samples the next streams_decode_ragged item of T frames (final or not) would emit for this stream"""
+        n = C.c_int64(0)
+        _ffi.check(_ffi.lib().fs_codec_streams_pending(self._h, int(stream_id), int(T), 1 if final else 0, C.byref(n)))
+        return int(n.value)
 
     def streams_decode(self, ids, codes):
         """ids: n distinct open stream ids; codes u32 (n, 8, T), T >= 16: item i is the next chunk of stream ids[i] -> f32 (n, 2048 T) PCM.
@@ -110,7 +147,29 @@ class FireflyCodec:
                                                       pcm.ctypes.data_as(C.POINTER(C.c_float))))
         return pcm
 
-    def streams_decode_ragged(self, ids, chunks):
+    def _streams_decode_pcm(self, ids, chunks, final):
+        n = len(chunks)
+        final = np.zeros(n, np.uint8) if final is None else np.ascontiguousarray(np.asarray(final).reshape(-1) != 0, np.uint8)
+        if final.shape != (n,):
+            raise ValueError("streams_decode_ragged: one final flag per item")
+        T = np.array([c.shape[1] for c in chunks], np.int32)
+        codes = np.concatenate([c.reshape(-1) for c in chunks] + [np.zeros(1, np.uint32)])
+        dts = [self._dtypes().get(int(i), "f32") for i in ids]
+        counts = [self.streams_pending(int(i), int(t), bool(f)) for i, t, f in zip(ids, T, final)]
+        sizes = [c * np.dtype(_ffi.PCM_DTYPES[d]).itemsize for c, d in zip(counts, dts)]
+        buf = np.zeros(max(1, sum(sizes)), np.uint8)
+        got = (C.c_int64 * n)()
+        _ffi.check(_ffi.lib().fs_codec_streams_decode_pcm(self._h, int(n), ids.ctypes.data_as(C.POINTER(C.c_int)), T.ctypes.data_as(C.POINTER(C.c_int)),
+                                                          final.ctypes.data_as(C.POINTER(C.c_uint8)), codes.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                          buf.ctypes.data_as(C.c_void_p), C.c_size_t(sum(sizes)), got))
+        out, at = [], 0
+        for i in range(n):
+            assert got[i] == counts[i]
+            out.append(np.frombuffer(buf[at:at + sizes[i]].tobytes(), _ffi.PCM_DTYPES[dts[i]]))  # (a copy: an f32 item may start at an odd offset)
+            at += sizes[i]
+        return out
+
+    def streams_decode_ragged(self, ids, chunks, final=None):
         """ids: n distinct open stream ids; chunks: n arrays u32 (8, T_i), T_i >= 1 and different per item: item i is the next chunk of stream
         ids[i] -> list of n f32 (2048 T_i,) PCM arrays.  Per stream, the chunks' PCM concatenated (through this call and streams_decode in
         any interleaving) is bit-identical to decode() of its whole sequence.  The items run at the stride of the longest one."""
@@ -120,6 +179,13 @@ class FireflyCodec:
             raise ValueError("streams_decode_ragged: one chunk per stream id")
         if not 1 <= len(chunks) <= self.STREAMS_MAX:
             raise ValueError(f"streams_decode_ragged: 1 .. {self.STREAMS_MAX} streams per call")
+        if final is not None or any(int(i) in self._dtypes() for i in ids):
+            # fishrt.h fs_codec_streams_decode_pcm: a final flag per item (an (8, 0) chunk with final set is a pure flush), every item's PCM
+            # in its stream's rate and dtype; a stream emits the samples whose input exists and the rest on its final item
+            for c in chunks:
+                if c.ndim != 2 or c.shape[0] != 8:
+                    raise ValueError("streams_decode_ragged: every chunk must have shape (8, T)")
+            return self._streams_decode_pcm(ids, chunks, final)
         for c in chunks:
             if c.ndim != 2 or c.shape[0] != 8 or c.shape[1] < 1:
                 raise ValueError("streams_decode_ragged: every chunk must have shape (8, T) with T >= 1")
@@ -132,12 +198,39 @@ class FireflyCodec:
         ends = 2048 * np.cumsum(T)
         return [pcm[e - 2048 * t:e] for e, t in zip(ends, T)]
 
-    def encode(self, pcm_data, lengths=None):
+    def _encode_pcm(self, pcm_data, lengths, sample_rate, resample):
+        if resample not in _ffi.RESAMPLE_MODES:
+            raise ValueError(f"resample mode must be one of {sorted(_ffi.RESAMPLE_MODES)}")
+        if pcm_data.ndim != 3:
+            raise ValueError("pcm_data must be a 3-D array (b, channels, n)")
+        b, ch, n_max = pcm_data.shape
+        ns = [n_max] * b if lengths is None else [int(v) for v in lengths]
+        if len(ns) != b or any(v <= 0 or v > n_max for v in ns):
+            raise ValueError("lengths must hold one sample count in (0, n] per clip")
+        out = []
+        for i in range(b):
+            inter = np.ascontiguousarray(pcm_data[i, :, : ns[i]].astype(np.float32, copy=False).T)  # [frames][channels]
+            cap = int(ns[i] * (self.sample_rate / float(sample_rate))) // 2048 + 8
+            codes = np.zeros((8, cap), np.uint32)
+            nf = C.c_size_t(0)
+            _ffi.check(_ffi.lib().fs_codec_encode_pcm(self._h, inter.ctypes.data_as(C.POINTER(C.c_float)), int(ch), int(ns[i]), int(sample_rate),
+                                                      _ffi.RESAMPLE_MODES[resample], codes.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                      C.c_size_t(cap), C.byref(nf)))
+            out.append(codes[:, : nf.value].copy())
+        if lengths is not None:
+            return out
+        assert len(set(c.shape[1] for c in out)) == 1
+        return np.stack(out)
+
+    def encode(self, pcm_data, lengths=None, sample_rate=None, resample="linear"):
         """codec.rs:73-94 / firefly.rs:36-39: f32 (b, 1, n) mono 44.1 kHz PCM -> u32 (b, 8, L).  Every clip is encoded on its own
         (fishrt.h fs_codec_encode_batch; the reference's front-end would glue a batch into one signal, spectrogram.rs:33).  lengths: optional
         per-clip sample counts <= n (ragged clips, zero-padded rows) -> list of (8, L_i) instead of one array."""
         if not isinstance(pcm_data, np.ndarray) or not pcm_data.flags["C_CONTIGUOUS"]:
             raise ValueError("Data must be a contiguous array")
+        if sample_rate is not None:
+            # fishrt.h fs_codec_encode_pcm: (b, channels, n) at sample_rate Hz -> downmix, resample to the codec rate and encode on the device
+            return self._encode_pcm(pcm_data, lengths, sample_rate, resample)
         if pcm_data.ndim != 3 or pcm_data.shape[1] != 1:
             raise ValueError("pcm_data must be a 3-D array (b, 1, n)")
         b, _, n_max = pcm_data.shape

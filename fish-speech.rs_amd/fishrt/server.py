@@ -13,6 +13,11 @@ What is mirrored (file:line in the reference):
     `prompt` query registering the voice, duplicate id -> error (`handlers/encode_speech.rs:36-94`).
 What is NOT: Opus / Ogg streaming (`audio/opus.rs`; out of scope) -- `response_format: "opus"` answers 501 unless the
 caller supplies an encoder; audio decoding other than WAV; the text cleaner is a compact restatement (`preprocess_text`, pluggable).
+Sample rates (opt-in, `AppState(device_resample=None | "linear" | "sinc", opus_rate=None)`): with `device_resample` the codec converts on
+the device -- `/v1/audio/speech` takes a `sample_rate` field for its WAV and `pcm` answers (rejected with a message otherwise) and
+`/v1/audio/encoding` downmixes and resamples an upload through `codec.encode(..., sample_rate=sr)` ("linear" is the reference's
+`functional.rs::resample`, `speech.rs:184-216` / `encode_speech.rs:50-54`) instead of scipy on the host; with `opus_rate` (the reference:
+24000) the Opus hook gets PCM at that rate, and that rate.
 
 Scheduler.  One worker thread per LM handle (= per GPU) drains a queue of chunk jobs.  A job whose conditioning prefix equals the one
 sitting in the handle's KV cache skips the prefix (the reference's `assume_kv_cache`); jobs of different voices simply invalidate it
@@ -143,8 +148,16 @@ class LMState:  # server/lib/state.rs:12-21
 class AppState:  # server/lib/state.rs:23-29
     def __init__(self, lm_state, codec, sample_rate=44100, opus_encoder=None, preprocess=preprocess_text, batch_window_s=0.002,
                  continuous=True, auto_batch=False, session_prefixes=False, per_slot_sampling=False, wide_sampling=False,
-                 prefix_host_cache_bytes=0, chunk_history=False):
+                 prefix_host_cache_bytes=0, chunk_history=False, device_resample=None, opus_rate=None):
         self.lm, self.codec, self.sample_rate, self.opus_encoder, self.preprocess = lm_state, codec, sample_rate, opus_encoder, preprocess
+        # device_resample (None | "linear" | "sinc", off by default): the codec converts sample rates on the device (FireflyCodec.decode /
+        # encode with sample_rate=): /v1/audio/speech takes a `sample_rate` field for WAV and `pcm` answers, and /v1/audio/encoding resamples
+        # an upload with the codec ("linear" = the reference's resample, bit for bit) instead of scipy on the host.
+        # opus_rate (None | Hz; the reference uses 24000, speech.rs:184-216): the opus_encoder hook gets PCM at that rate, and that rate
+        # (converted in the device_resample mode, "sinc" when that is off), instead of 44.1 kHz PCM
+        if device_resample not in (None, "linear", "sinc"):
+            raise ValueError('device_resample must be None, "linear" or "sinc"')
+        self.device_resample, self.opus_rate = device_resample, (None if opus_rate is None else int(opus_rate))
         self.codec_lock = threading.Lock()  # a codec handle takes one call at a time (include/fishrt.h); requests vocode from their own threads
         self.auto_batch = auto_batch  # True: every chunk may join the batching session (batch sampling semantics) without `batch_size`
         # session_prefixes (off by default): session jobs share their voice's conditioning prefix (Session.add_prefix) instead of prefilling
@@ -739,6 +752,16 @@ def generate_speech(state, req):
             if state.opus_encoder is None:
                 return 501, "application/json", json.dumps({"detail": "Opus / Ogg streaming is outside this shim (audio/opus.rs); use the default WAV "
                                                                       "response or response_format 'pcm'"}).encode()
+        out_rate = req.get("sample_rate")
+        if out_rate is not None:
+            if getattr(state, "device_resample", None) is None:
+                return 422, "application/json", json.dumps({"detail": "`sample_rate` needs a server started with device_resample (the codec "
+                                                                      f"answers at {state.sample_rate} Hz otherwise)"}).encode()
+            if fmt == "opus":
+                return 422, "application/json", json.dumps({"detail": "`sample_rate` goes with the WAV and 'pcm' answers; Opus runs at the "
+                                                                      "server's opus_rate"}).encode()
+            if isinstance(out_rate, bool) or not isinstance(out_rate, int) or not 1000 <= out_rate <= 384000:
+                return 422, "application/json", json.dumps({"detail": "`sample_rate` must be an integer number of Hz in 1000 .. 384000"}).encode()
         # like the reference (speech.rs:72-96) chunks are batched only when the request asks for it (`batch_size` > 1): the batch paths sample
         # with BatchedLogitsProcessor semantics and no repetition penalty, so what a client hears must not depend on the server's load.
         # `auto_batch` (server option, off by default) lets every chunk join the continuous-batching session when other work is in flight.
@@ -757,18 +780,30 @@ def generate_speech(state, req):
             futs = [state.scheduler.submit(cond, b, n_cond, state.lm.max_batch > 1 and want_batch, sampling=sa,
                                            seed=None if seed is None else (seed + i) & (2**64 - 1)) for i, b in enumerate(bodies)]
 
-        def pcm_chunks():
+        def pcm_chunks(**spec):  # spec: sample_rate / resample / dtype of FireflyCodec.decode (converted on the device); none = as ever
             for f in futs:
                 codes = f.result()
                 with state.codec_lock:
-                    pcm = state.codec.decode(np.ascontiguousarray(codes[None]))[0, 0]  # (an out-of-range code is an error, as in the reference)
+                    pcm = state.codec.decode(np.ascontiguousarray(codes[None]), **spec)[0, 0]  # (an out-of-range code is an error, as in the reference)
                 yield pcm
 
-        if fmt == "pcm":  # extension: chunked little-endian s16 PCM at the codec rate, one HTTP chunk per text chunk
+        s16 = dict(sample_rate=out_rate, resample=state.device_resample, dtype="s16") if out_rate is not None else None
+        if fmt == "pcm":  # extension: chunked little-endian s16 PCM at the codec rate (or `sample_rate`), one HTTP chunk per text chunk
+            if s16:
+                return 200, "audio/pcm", (np.ascontiguousarray(p, "<i2").tobytes() for p in pcm_chunks(**s16))
             return 200, "audio/pcm", (fwav.pcm_to_i16(p).tobytes() for p in pcm_chunks())
         if fmt == "opus":
             enc = state.opus_encoder
+            opus_rate = getattr(state, "opus_rate", None)
+            if opus_rate is not None:
+                spec = dict(sample_rate=opus_rate, resample=getattr(state, "device_resample", None) or "sinc", dtype="f32")
+                return 200, "audio/ogg", (b for p in pcm_chunks(**spec) for b in enc(p, opus_rate))
             return 200, "audio/ogg", (b for p in pcm_chunks() for b in enc(p, state.sample_rate))
+        if s16:
+            all_pcm = np.concatenate(list(pcm_chunks(**s16))) if futs else np.zeros(0, np.int16)
+            buf = io.BytesIO()
+            fwav.write_pcm_as_wav(buf, all_pcm, out_rate)
+            return 200, "audio/wav", buf.getvalue()
         all_pcm = np.concatenate(list(pcm_chunks())) if futs else np.zeros(0, np.float32)
         buf = io.BytesIO()
         fwav.write_pcm_as_wav(buf, all_pcm, state.sample_rate)
@@ -857,14 +892,18 @@ def encode_speaker(state, file_bytes, params):
     """POST /v1/audio/encoding (handlers/encode_speech.rs:36-94) -> (status, content_type, body)"""
     try:
         audio, sr = _read_wav(file_bytes)
-        if audio.shape[0] > 1:
-            audio = audio.mean(0, keepdims=True)
-        if sr != state.sample_rate:
-            from math import gcd
-            from scipy.signal import resample_poly
-            g = gcd(int(sr), int(state.sample_rate))
-            audio = resample_poly(audio, state.sample_rate // g, sr // g, axis=1).astype(np.float32)
-        codes = state.codec.encode(np.ascontiguousarray(audio[None], np.float32))[0]  # (8, T)
+        if getattr(state, "device_resample", None) is not None:
+            # downmix, resample and encode on the device (fs_codec_encode_pcm): "linear" is the reference's arithmetic (encode_speech.rs:50-54)
+            codes = state.codec.encode(np.ascontiguousarray(audio[None], np.float32), sample_rate=int(sr), resample=state.device_resample)[0]
+        else:
+            if audio.shape[0] > 1:
+                audio = audio.mean(0, keepdims=True)
+            if sr != state.sample_rate:
+                from math import gcd
+                from scipy.signal import resample_poly
+                g = gcd(int(sr), int(state.sample_rate))
+                audio = resample_poly(audio, state.sample_rate // g, sr // g, axis=1).astype(np.float32)
+            codes = state.codec.encode(np.ascontiguousarray(audio[None], np.float32))[0]  # (8, T)
         vid, text = params.get("id"), params.get("prompt")
         if vid is not None and text is not None:
             s = state.lm

@@ -171,7 +171,18 @@ class SessionStreamer:
     n x the longest item, so one long item next to many short ones (a 64-frame chunk next to 31 one-frame tails) is paid 32 x 64 frames of
     work for 95 frames of audio.  Chunk sizes near each other keep that waste small; the one-call rule holds whatever the mix."""
 
-    def __init__(self, session, codec, chunk=64, first_chunk=32, halo=HALO, on_audio=None, clock=time.perf_counter, ragged=False):
+    def __init__(self, session, codec, chunk=64, first_chunk=32, halo=HALO, on_audio=None, clock=time.perf_counter, ragged=False,
+                 sample_rate=None, resample="sinc", pcm_dtype="f32"):
+        """sample_rate / pcm_dtype (ragged=True only): every request's stream is opened with that PCM spec (FireflyCodec.streams_open), so
+        its pieces arrive at sample_rate Hz as f32 or int16, converted on the device by `resample` ("sinc" or "linear").  Every item carries
+        its final flag: a piece holds the samples whose input exists, so pieces vary in length (the first one of a sinc stream is short),
+        and a finished request with no frames left still gets a flush item, which delivers the samples held back.  Per request the pieces
+        concatenated equal codec.decode(final codes, sample_rate=, resample=, dtype=), bit for bit.  stats[tag]["samples"] counts them."""
+        self.pcm_spec = None
+        if sample_rate is not None or pcm_dtype != "f32":
+            if not ragged:
+                raise ValueError("sample_rate / pcm_dtype need ragged=True (the uniform vocoder calls return f32 at the codec rate)")
+            self.pcm_spec = dict(sample_rate=sample_rate, resample=resample, dtype=pcm_dtype)
         min_frames = 1 if ragged else getattr(codec, "STREAM_MIN_FRAMES", 16)
         if chunk < min_frames or first_chunk < min_frames:
             raise ValueError(f"chunk and first_chunk must be >= {min_frames} frames (the codec's minimum streamed chunk)")
@@ -199,7 +210,7 @@ class SessionStreamer:
             tag = self._admitted
         if tag in self.stats:
             raise ValueError(f"tag {tag!r} is already in use")
-        sid = self.codec.streams_open()
+        sid = self.codec.streams_open(**self.pcm_spec) if self.pcm_spec else self.codec.streams_open()
         try:
             kw = {}
             if prefix is not None:
@@ -217,7 +228,7 @@ class SessionStreamer:
             return None
         self._admitted += 1
         self.live[slot] = dict(tag=tag, sid=sid, done_upto=0, t_add=self.clock())
-        self.stats[tag] = dict(frames=0, first_audio_s=None, vocoder_s=0.0, chunks=0)
+        self.stats[tag] = dict(frames=0, first_audio_s=None, vocoder_s=0.0, chunks=0, samples=0)
         return slot
 
     def step(self, n_frames=8):
@@ -259,7 +270,7 @@ class SessionStreamer:
             left = n - r["done_upto"]
             if done:
                 finished.append(slot)
-                if left > 0:
+                if left > 0 or self.pcm_spec:  # (a spec stream holds samples back until its final item: flush it even with no frames left)
                     due.append((slot, left, True))
                 continue
             T = self.first_chunk if r["done_upto"] == 0 else self.chunk
@@ -273,7 +284,10 @@ class SessionStreamer:
                     a = self.live[slot]["done_upto"]
                     chunks.append(np.ascontiguousarray(self._codes(slot)[:, a:a + T]))
                 t1 = self.clock()
-                pcm = self.codec.streams_decode_ragged([self.live[s]["sid"] for s, _, _ in due], chunks)
+                if self.pcm_spec:
+                    pcm = self.codec.streams_decode_ragged([self.live[s]["sid"] for s, _, _ in due], chunks, final=[f for _, _, f in due])
+                else:
+                    pcm = self.codec.streams_decode_ragged([self.live[s]["sid"] for s, _, _ in due], chunks)
                 self._account([self.live[s] for s, _, _ in due], "ragged", max(T for _, T, _ in due), self.clock() - t1)
                 for (slot, T, final), p in zip(due, pcm):
                     out.append(self._deliver(self.live[slot], p, T, final))
@@ -315,6 +329,7 @@ class SessionStreamer:
         st = self.stats[r["tag"]]
         st["frames"] = r["done_upto"]
         st["chunks"] += 1
+        st["samples"] += int(np.asarray(pcm).shape[-1])
         if st["first_audio_s"] is None:
             st["first_audio_s"] = self.clock() - r["t_add"]
         if self.on_audio is not None:

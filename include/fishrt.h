@@ -737,6 +737,74 @@ int fs_codec_precision(fs_codec_t* c);
 int fs_codec_set_range_check(fs_codec_t* c, int on);
 int fs_codec_range_stats(fs_codec_t* c, uint64_t* out5, double* last_pcm_rms_diff);
 
+/* ---- Device sample-rate conversion (csrc/codec_resample.hip; counting rules and host evaluators in csrc/fs_resample_plan.h).  The reference
+ * resamples on the CPU: server/lib/handlers/encode_speech.rs:50-54 (an uploaded clip, to the codec rate) and speech.rs:184-216 (every vocoded
+ * chunk, 44.1 -> 24 kHz in front of the Opus encoder), both through audio/functional.rs::resample.  Two definitions:
+ *
+ * FS_RESAMPLE_LINEAR = fish_speech_core/lib/audio/functional.rs:3-37, bit for bit:
+ *   ratio = (double)to / (double)from;  out_len = ceil((double)n * ratio);
+ *   output i: idx = (double)i / ratio (an f64 division, not i * from / to);  f = floor(idx), c = min(ceil(idx), n - 1);
+ *             t = (float)(idx - (double)f), u = 1.0f - t;  out = x[f] * u + x[c] * t, two f32 products rounded separately, then one f32 add.
+ *   Where f64 rounding makes the last floor index n (n = 147 at 44.1 -> 24 kHz: out_len = 81, idx(80) = 147.0) the reference's gather is out
+ *   of range and it returns an error; here f is clamped to n - 1 like c, and t = 0 there, so that sample repeats x[n - 1].
+ *   from == to returns the input unchanged (finite samples).  Two taps and no low-pass: downsampling aliases at full level (a 19 845 Hz tone
+ *   of amplitude 1 comes out of 44.1 -> 24 kHz at RMS 0.42).  It is there for parity with the reference on the encode path.
+ *
+ * FS_RESAMPLE_SINC = a Hann-windowed sinc polyphase filter, the construction of torchaudio's sinc_interp_hann with W = 6, rolloff = 0.99:
+ *   g = gcd(from, to), o = from / g, p = to / g;  base = min(o, p) * rolloff, width = ceil(W * o / base), K = 2 * width + o taps;
+ *   phase j < p, tap k < K: t = clamp((-j / p + (k - width) / o) * base, -W, W),
+ *                           h[j][k] = (t == 0 ? 1 : sin(pi t) / (pi t)) * cos(pi t / (2 W))^2 * base / o, built in f64 once per pair, stored f32;
+ *   out[m * p + j] = sum_{k = 0 .. K-1} h[j][k] * x[m * o + k - width], x = 0 outside [0, n), accumulated in f32 in ascending k (the fixed
+ *   order is what makes chunked output equal one-shot output);  out_len = ceil(p * n / o) in integer arithmetic.
+ *   44.1 -> 24 kHz: 80 x 171 taps, 44.1 -> 48: 160 x 161, 44.1 -> 16: 160 x 475, 22.05 -> 44.1: 2 x 15, 48 -> 44.1: 147 x 174, 8 -> 44.1: 441 x 94.
+ *   A pair whose table would exceed 2^20 entries is refused with an error that names it.  The same tone comes out at RMS 5.6e-4.
+ *
+ * FS_PCM_F32: f32 samples.  FS_PCM_S16: fishrt/wav.py pcm_to_i16 (wav.rs:27-58) fused into the kernel's store: clip to [-1, 1], times
+ * 32767.0f, truncate toward zero, NaN -> 0.  In the fs_codec_* calls a spec at the codec's own rate is a format conversion only, whatever
+ * its mode; fs_resample follows the definitions to the letter, equal rates included. */
+#define FS_RESAMPLE_LINEAR 0
+#define FS_RESAMPLE_SINC 1
+#define FS_PCM_F32 0
+#define FS_PCM_S16 1
+typedef struct fs_pcm_spec {
+    int32_t rate, mode /* FS_RESAMPLE_* */, format /* FS_PCM_* */;
+} fs_pcm_spec;
+/* samples that n input samples become (either definition's out_len); no device */
+int fs_resample_out_len(int from_rate, int to_rate, int mode, int64_t n, int64_t* out_len);
+/* Stand-alone, no codec handle: b rows f32 at pcm + i * stride, row i n_samples[i] <= stride samples long (0 allowed), host -> device -> one
+ * launch -> host.  out_buf: float or int16_t by out->format, row i at element i * out_stride, out_len[i] samples written; out_stride must hold
+ * fs_resample_out_len of every row (checked before anything is launched). */
+int fs_resample(int device_id, const float* pcm, int b, size_t stride, const int64_t* n_samples, int from_rate, const fs_pcm_spec* out,
+                void* out_buf, size_t out_stride /* elements */, int64_t* out_len /* [b] */);
+/* fs_codec_decode with every PCM row converted on the device, each on its own, before the copy to the host.  out: b rows of `cap` elements,
+ * n_out[i] samples written in row i.  Equals fs_resample of fs_codec_decode's rows bit for bit. */
+int fs_codec_decode_pcm(fs_codec_t* c, const uint32_t* codes, int b, int T, const fs_pcm_spec* spec, void* out, size_t cap /* elements per row */,
+                        int64_t* n_out);
+/* A multi-stream (fs_codec_streams_open) whose PCM leaves at spec->rate in spec->format.  On top of the stream's vocoder contexts it owns two
+ * carry rows on the device -- the input samples that an output not yet emitted still reads: 2 x 2 floats in linear mode, 2 x (K + o) floats
+ * in sinc mode (44.1 -> 24 kHz: 2.5 KB, 44.1 -> 16 kHz: 7.3 KB), none at the codec's own rate -- and three counters on the host.
+ * fs_codec_streams_decode and fs_codec_streams_decode_ragged refuse such a stream (their PCM layout is fixed); use the call below. */
+int fs_codec_streams_open_pcm(fs_codec_t* c, const fs_pcm_spec* spec, int* stream_id);
+/* samples the next fs_codec_streams_decode_pcm item of T frames (final or not) would emit for this stream; changes nothing */
+int fs_codec_streams_pending(fs_codec_t* c, int stream_id, int T, int final, int64_t* n_out);
+/* fs_codec_streams_decode_ragged with a `final` flag per item (final == NULL: none) and every item's PCM converted by its stream's spec before
+ * the copy to the host.  Streams opened either way are accepted: one from fs_codec_streams_open is codec rate, f32.  out: the items' outputs
+ * concatenated in item order, each in its stream's format (so an f32 item may start at an odd 2-byte offset: copy it out before use);
+ * n_out[i] = samples of item i.  A stream emits an output sample once all the input it reads exists -- linear: ceil(i / ratio) <= N - 1 after
+ * N input samples, sinc: whole blocks of p outputs whose last tap lies inside the input -- and the rest, with the reference's clamp and the
+ * right zero pad, when its item is final.  T[i] == 0 is allowed only with final[i] != 0: a pure flush.  After its final item a stream takes
+ * no more items (close it).  Everything is validated before the first launch -- the rules of the ragged call, and cap_bytes against the
+ * counted output, and final streams; a failed call leaves every stream untouched, vocoder contexts and resample counters alike.
+ * Per stream, the outputs of all its calls concatenated equal fs_codec_decode_pcm of the whole sequence at b = 1, bit for bit, in both modes
+ * and both formats, whatever the chunk lengths, the other items or their order. */
+int fs_codec_streams_decode_pcm(fs_codec_t* c, int n, const int* stream_ids, const int* T, const uint8_t* final, const uint32_t* codes, void* out,
+                                size_t cap_bytes, int64_t* n_out /* [n] samples */);
+/* encode_speech.rs:50-54 on the device: pcm f32 interleaved [frames][channels] at `rate` Hz -> downmix (the channels summed in order in f32,
+ * divided by (float)channels) -> resample to fs_codec_sample_rate in `mode` -> fs_codec_encode, with no trip to the host in between.  The
+ * codes equal fs_codec_encode of the same resampled buffer bit for bit. */
+int fs_codec_encode_pcm(fs_codec_t* c, const float* pcm, int channels, int64_t frames, int rate, int mode, uint32_t* codes_out, size_t cap,
+                        size_t* n_frames);
+
 #ifdef __cplusplus
 }
 #endif
