@@ -23,6 +23,8 @@ class CodecBase {
     // ragged: item i advances stream ids[i] by T[i] >= 1 frames; codes = the items' (8, T[i]) blocks concatenated, pcm_out = their PCM concatenated
     virtual void streams_decode_ragged(int n, const int* ids, const int* T, const uint32_t* codes, float* pcm_out) = 0;
     virtual void encode(const float* pcm, int n, uint32_t* codes_out, size_t cap, size_t* L_out) = 0;
+    // fs_selftest_codec_encode_stage: encode() with one intermediate tensor copied out (stage -1 .. 6), or the mel table (stage -2)
+    virtual void encode_stage(const float* pcm, int n, int stage, float* out, size_t cap, size_t* n_out) = 0;
     // ---- device sample-rate conversion of the PCM (fs_codec_*_pcm, include/fishrt.h; codec_resample.hip).  spec = {rate, mode, format}
     virtual void decode_pcm(const uint32_t* codes, int b, int T, const int* spec3, void* out, size_t cap, int64_t* n_out) = 0;
     virtual int streams_open_pcm(const int* spec3) = 0;
@@ -43,6 +45,7 @@ CodecBase* make_codec(int device, int channel_div);
 }  // namespace fs
 
 struct fs_conv_case;  // include/fishrt.h
+struct fs_codec_op_case;
 
 namespace fs {
 
@@ -53,5 +56,8 @@ void resample_rows(int device, const float* pcm, int b, size_t stride, const int
 // fs_selftest_conv1d: one conv through re-layout, pack, plane producers and one launcher of codec_kernels.h (see include/fishrt.h)
 void codec_conv_selftest(int device, const fs_conv_case& c, float* y_out, float* planes_out, char* variant_out, size_t variant_cap,
                          uint64_t* range_out);
+
+// fs_selftest_codec_op: one encoder-side / ConvNeXt / FSQ launcher of codec_kernels.h on host data, output poisoned and guarded (see include/fishrt.h)
+void codec_op_selftest(int device, const fs_codec_op_case& c, void* out, size_t out_cap, size_t* n_out, int* guard_ok);
 
 }  // namespace fs

@@ -719,6 +719,26 @@ class Codec final : public CodecBase {
         FS_HIP(hipMemcpyAsync(dpcm_.p, pcm, sizeof(float) * n, hipMemcpyHostToDevice, st_));
         encode_device(n, codes_out, cap, L_out);
     }
+    // fs_selftest_codec_encode_stage: encode() with the tap armed for one call; the codes are computed and dropped
+    void encode_stage(const float* pcm, int n, int stage, float* out, size_t cap, size_t* n_out) override {
+        FS_HIP(hipSetDevice(device_));
+        if (stage == -2) {  // the table as the device holds it
+            ensure_mel_table();
+            const size_t ne = mel_fb_.n / sizeof(float);
+            FS_REQUIRE(ne <= cap, "encoder stage tap: out capacity too small");
+            FS_HIP(hipMemcpy(out, mel_fb_.p, mel_fb_.n, hipMemcpyDeviceToHost));
+            *n_out = ne;
+            return;
+        }
+        const int F = encode_frames(n);
+        std::vector<uint32_t> codes((size_t)8 * (F / 4));
+        size_t L = 0;
+        struct Disarm { Codec* c; ~Disarm() { c->tap_stage_ = kTapOff; c->tap_out_ = nullptr; } } disarm{this};
+        tap_stage_ = stage; tap_out_ = out; tap_cap_ = cap; tap_n_ = 0;
+        encode(pcm, n, codes.data(), (size_t)(F / 4), &L);
+        FS_REQUIRE(tap_n_ > 0, "encoder stage tap: the stage was not reached");
+        *n_out = tap_n_;
+    }
     // mel frames of an n-sample clip, or the reason it cannot be encoded
     static int encode_frames(long long n) {
         const int pad = (kFft - kHop) / 2;
@@ -740,6 +760,14 @@ class Codec final : public CodecBase {
         float *x = buf_[0].f(), *t1 = buf_[1].f(), *t2 = buf_[2].f(), *r = buf_[3].f();
         codec_stft_mag((const float*)dpcm_.p, n, kFft, kHop, T, t1, st_);
         codec_mel_log(t1, mel_fb_.f(), nf, kMels, T, x, st_);
+        // fs_selftest_codec_encode_stage: the armed call copies one tensor out (the copy is complete at the call's final synchronisation)
+        auto tap = [&](int stage, const float* p, size_t ne) {
+            if (tap_stage_ != stage) return;
+            FS_REQUIRE(ne <= tap_cap_, "encoder stage tap: out capacity too small");
+            FS_HIP(hipMemcpyAsync(tap_out_, p, ne * sizeof(float), hipMemcpyDeviceToHost, st_));
+            tap_n_ = ne;
+        };
+        tap(-1, x, (size_t)kMels * T);
         auto block = [&](const CnxSpec& c, int Cb, int Tc) {  // x -> x (ConvNeXtBlock, convnext.rs:110-126)
             codec_dwconv_ln(x, 1, Cb, Tc, R(c.dw), R(c.db), R(c.lnw), R(c.lnb), t2, st_);
             codec_conv1d(t2, 1, Cb, Tc, conv(c.pw1), 1, false, CODEC_EPI_GELU, nullptr, nullptr, r, st_);
@@ -750,13 +778,16 @@ class Codec final : public CodecBase {
         codec_conv1d(x, 1, kMels, T, conv(stem_conv_), 1, false, CODEC_EPI_NONE, nullptr, nullptr, t1, st_);
         codec_layernorm_cf(t1, edims_[0], T, R(stem_lnw_), R(stem_lnb_), x, st_);
         for (const auto& c : stages_[0]) block(c, edims_[0], T);
+        tap(0, x, (size_t)edims_[0] * T);
         for (int i = 1; i < 4; ++i) {
             codec_layernorm_cf(x, edims_[i - 1], T, R(mid_lnw_[i]), R(mid_lnb_[i]), t1, st_);
             codec_conv1d(t1, 1, edims_[i - 1], T, conv(mid_conv_[i]), 1, false, CODEC_EPI_NONE, nullptr, nullptr, x, st_);
             for (const auto& c : stages_[i]) block(c, edims_[i], T);
+            tap(i, x, (size_t)edims_[i] * T);
         }
         codec_layernorm_cf(x, edims_[3], T, R(enc_lnw_), R(enc_lnb_), t1, st_);
         std::swap(x, t1);
+        tap(4, x, (size_t)C_ * T);
         // quantizer.encode (quantizer.rs:104-124): (strided conv k = s = 2 as space-to-depth + 1x1 conv) + ConvNeXt block, twice
         int Tc = T;
         for (int i = 0; i < 2; ++i) {
@@ -766,6 +797,7 @@ class Codec final : public CodecBase {
             w.k = 1;  // re-laid [Cin][2][Cout] == [2 Cin][1][Cout] over the space-to-depth channels
             codec_conv1d(t1, 1, 2 * C_, Tc, w, 1, false, CODEC_EPI_NONE, nullptr, nullptr, x, st_);
             block(down_cnx_[i], C_, Tc);
+            tap(5 + i, x, (size_t)C_ * Tc);
         }
         FS_REQUIRE((size_t)Tc <= cap, "codes_out capacity too small");
         dcodes_.ensure(sizeof(uint32_t) * G * Tc);
@@ -1026,6 +1058,11 @@ class Codec final : public CodecBase {
     std::vector<CnxSpec> stages_[4];
     CnxSpec down_cnx_[2] = {};
     DBuf mel_fb_, dpcm_;
+    // encoder stage tap (encode_stage): off except inside that call
+    static constexpr int kTapOff = -1000;
+    int tap_stage_ = kTapOff;
+    float* tap_out_ = nullptr;
+    size_t tap_cap_ = 0, tap_n_ = 0;
 };
 
 CodecBase* make_codec(int device, int channel_div) { return new Codec(device, channel_div); }
@@ -1229,6 +1266,111 @@ void codec_conv_selftest(int device, const fs_conv_case& c, float* y_out, float*
     }
     FS_REQUIRE(name, "conv self-test: the launcher recorded no variant name");
     std::snprintf(variant_out, variant_cap, "%s", name);
+}
+
+// fs_selftest_codec_op (include/fishrt.h): ONE launcher of the encoder-side / ConvNeXt / FSQ kernels on host data.  The output buffer is
+// [256 guard][logical extent][256 guard] 4-byte elements, all 0xFF before the launch: an element the launcher skipped returns as NaN, a
+// write outside the extent shows in the guards.  Every shape is checked against the launcher's own reads before anything is launched.
+void codec_op_selftest(int device, const fs_codec_op_case& c, void* out, size_t out_cap, size_t* n_out, int* guard_ok) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw Error("no HIP device visible: libfishrt has no CPU fallback (MI355X / gfx950 required)");
+    FS_REQUIRE(device >= 0 && device < ndev, "device_id out of range");
+    FS_HIP(hipSetDevice(device));
+    constexpr size_t kGuard = 256;
+    const int B = c.B, C = c.C, T = c.T;
+    FS_REQUIRE(c.op >= FS_CODEC_OP_STFT_MAG && c.op <= FS_CODEC_OP_FSQ_PROJECT, "codec op self-test: unknown op");
+    FS_REQUIRE(T >= 1 && T <= (1 << 20), "codec op self-test: 1 <= T <= 2^20");
+    size_t n_x = 0, n_w[4] = {0, 0, 0, 0}, n_y = 0, n_codes = 0, n_ctx = 0;
+    switch (c.op) {
+    case FS_CODEC_OP_STFT_MAG: {
+        FS_REQUIRE(c.n_fft >= 2 && c.n_fft <= 8192 && c.hop >= 1 && c.hop <= c.n_fft && (c.n_fft - c.hop) % 2 == 0, "codec op self-test: bad STFT shape");
+        const long long pad = (c.n_fft - c.hop) / 2;
+        FS_REQUIRE(c.n >= 1 && c.n >= pad && c.n < (1 << 28), "codec op self-test: the clip is shorter than the reflect padding");
+        FS_REQUIRE((long long)(T - 1) * c.hop < (long long)c.n + 2 * pad, "codec op self-test: a frame starts behind the padded signal");
+        n_x = (size_t)c.n; n_y = (size_t)(c.n_fft / 2 + 1) * T;
+        break;
+    }
+    case FS_CODEC_OP_MEL_LOG:
+        FS_REQUIRE(c.nf >= 1 && c.nf <= 8192 && c.n_mels >= 1 && c.n_mels <= 4096, "codec op self-test: bad mel shape");
+        n_x = (size_t)c.nf * T; n_w[0] = (size_t)c.nf * c.n_mels; n_y = (size_t)c.n_mels * T;
+        break;
+    case FS_CODEC_OP_LAYERNORM_CF:
+        FS_REQUIRE(C >= 1 && C <= 4096, "codec op self-test: 1 <= C <= 4096");
+        n_x = n_y = (size_t)C * T; n_w[0] = n_w[1] = (size_t)C;
+        break;
+    case FS_CODEC_OP_DWCONV_LN:
+        FS_REQUIRE(C >= 1 && C <= 4096 && B >= 1 && B <= 64, "codec op self-test: 1 <= C <= 4096, 1 <= B <= 64");
+        FS_REQUIRE(c.ctx_mode >= 0 && c.ctx_mode <= 2, "codec op self-test: ctx_mode 0 = none, 1 = one context, 2 = per-item offsets");
+        n_x = n_y = (size_t)B * C * T; n_w[0] = (size_t)C * 7; n_w[1] = n_w[2] = n_w[3] = (size_t)C;
+        if (c.ctx_mode == 1) {
+            FS_REQUIRE(B == 1 && c.ctx, "codec op self-test: one context needs B == 1 and ctx");
+            n_ctx = (size_t)C * CODEC_CTX_F32;
+        } else if (c.ctx_mode == 2) {
+            FS_REQUIRE(c.ctx && c.ctx_off && c.ctx_elems >= 1 && c.ctx_elems < (1ll << 28), "codec op self-test: per-item contexts need ctx, ctx_off and ctx_elems");
+            for (int b = 0; b < B; ++b)
+                FS_REQUIRE(c.ctx_off[2 * b] >= 0 && c.ctx_off[2 * b] + (long long)C * CODEC_CTX_F32 <= c.ctx_elems,
+                           "codec op self-test: a context offset points outside the pool");
+            n_ctx = (size_t)c.ctx_elems;
+        }
+        break;
+    case FS_CODEC_OP_SPACE_TO_DEPTH:
+        FS_REQUIRE(C >= 1 && C <= 4096 && c.s >= 1 && c.s <= 16, "codec op self-test: 1 <= C <= 4096, 1 <= s <= 16");
+        n_x = (size_t)C * T; n_y = (size_t)C * c.s * (T / c.s);
+        break;
+    case FS_CODEC_OP_FSQ_ENCODE:
+        FS_REQUIRE(c.G >= 1 && c.G <= 64 && C >= c.G && C <= 4096 && C % c.G == 0, "codec op self-test: C is a multiple of G, 1 <= G <= 64, C <= 4096");
+        n_x = (size_t)C * T; n_w[0] = (size_t)4 * C; n_w[1] = (size_t)4 * c.G; n_y = (size_t)c.G * T;
+        break;
+    default:
+        FS_REQUIRE(c.G >= 1 && c.G <= 64 && c.dg >= 1 && c.dg <= 512 && B >= 1 && B <= 64, "codec op self-test: 1 <= G, B <= 64, 1 <= dg <= 512");
+        FS_REQUIRE(c.codes, "codec op self-test: codes are required");
+        n_codes = (size_t)B * c.G * T; n_w[0] = (size_t)c.G * c.dg * 4; n_w[1] = (size_t)c.G * c.dg; n_y = (size_t)B * c.G * c.dg * T;
+        for (size_t i = 0; i < n_codes; ++i) FS_REQUIRE(c.codes[i] < 1000u, "codec op self-test: an index is outside the codebook");
+        break;
+    }
+    FS_REQUIRE(n_x < (1u << 28) && n_y < (1u << 28), "codec op self-test: tensor above 2^28 elements");
+    FS_REQUIRE(n_y <= out_cap, "codec op self-test: out capacity too small");
+    const float* wsrc[4] = {c.w0, c.w1, c.w2, c.w3};
+    FS_REQUIRE(!n_x || c.x, "codec op self-test: x is required");
+    for (int i = 0; i < 4; ++i) FS_REQUIRE(!n_w[i] || wsrc[i], "codec op self-test: a weight tensor of this op is missing");
+
+    hipStream_t st = nullptr;
+    FS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } sg{st};
+    DBuf dx, dw[4], dctx, doff, dcodes, dy;
+    auto up = [&](DBuf& d, const void* src, size_t bytes) {
+        d.alloc(bytes);
+        FS_HIP(hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, st));
+    };
+    if (n_x) up(dx, c.x, n_x * sizeof(float));
+    for (int i = 0; i < 4; ++i) if (n_w[i]) up(dw[i], wsrc[i], n_w[i] * sizeof(float));
+    if (n_ctx) up(dctx, c.ctx, n_ctx * sizeof(float));
+    if (c.op == FS_CODEC_OP_DWCONV_LN && c.ctx_mode == 2) up(doff, c.ctx_off, (size_t)2 * B * sizeof(long long));
+    if (n_codes) up(dcodes, c.codes, n_codes * sizeof(uint32_t));
+    dy.alloc((n_y + 2 * kGuard) * 4);
+    FS_HIP(hipMemsetAsync(dy.p, 0xFF, dy.n, st));
+    float* y = dy.f() + kGuard;
+    static_assert(sizeof(long long) == sizeof(int64_t), "ctx_off is the launchers' long long table");
+    switch (c.op) {
+    case FS_CODEC_OP_STFT_MAG: codec_stft_mag(dx.f(), c.n, c.n_fft, c.hop, T, y, st); break;
+    case FS_CODEC_OP_MEL_LOG: codec_mel_log(dx.f(), dw[0].f(), c.nf, c.n_mels, T, y, st); break;
+    case FS_CODEC_OP_LAYERNORM_CF: codec_layernorm_cf(dx.f(), C, T, dw[0].f(), dw[1].f(), y, st); break;
+    case FS_CODEC_OP_DWCONV_LN:
+        codec_dwconv_ln(dx.f(), B, C, T, dw[0].f(), dw[1].f(), dw[2].f(), dw[3].f(), y, st, c.ctx_mode ? dctx.f() : nullptr,
+                        c.ctx_mode == 2 ? (const long long*)doff.p : nullptr);
+        break;
+    case FS_CODEC_OP_SPACE_TO_DEPTH: codec_space_to_depth(dx.f(), C, T, c.s, y, st); break;
+    case FS_CODEC_OP_FSQ_ENCODE: codec_fsq_encode(dx.f(), C, T, c.G, dw[0].f(), dw[1].f(), (uint32_t*)y, st); break;
+    default: codec_fsq_project((const uint32_t*)dcodes.p, B, c.G, T, dw[0].f(), dw[1].f(), c.dg, y, st, c.item_rows != 0); break;
+    }
+    std::vector<uint32_t> host(n_y + 2 * kGuard);
+    FS_HIP(hipMemcpyAsync(host.data(), dy.p, dy.n, hipMemcpyDeviceToHost, st));
+    FS_HIP(hipStreamSynchronize(st));
+    bool intact = true;
+    for (size_t i = 0; i < kGuard; ++i) intact = intact && host[i] == 0xFFFFFFFFu && host[kGuard + n_y + i] == 0xFFFFFFFFu;
+    if (n_y) std::memcpy(out, host.data() + kGuard, n_y * 4);
+    *n_out = n_y;
+    *guard_ok = intact ? 1 : 0;
 }
 
 }  // namespace fs

@@ -709,6 +709,7 @@ void codec_layernorm_cf(const float* x, int C, int T, const float* w, const floa
 }
 void codec_space_to_depth(const float* x, int C, int T, int s, float* y, hipStream_t st) {
     const int Tout = T / s;
+    if (Tout <= 0) return;  // T < s: every column is dropped, and a grid of zero blocks is a launch error
     hipLaunchKernelGGL(k_space_to_depth, dim3((Tout + 63) / 64, C * s), dim3(64), 0, st, x, C, T, s, Tout, y);
     FS_HIP(hipGetLastError());
 }

@@ -118,6 +118,12 @@ int fs_selftest_conv1d(int device_id, const fs_conv_case* c, float* y_out, float
     variant_out[0] = 0;
     FS_TRY(fs::codec_conv_selftest(device_id, *c, y_out, planes_out, variant_out, variant_cap, range_out))
 }
+static_assert(sizeof(fs_codec_op_case) == 16 * 4 + 8 + 8 * 8, "fs_codec_op_case is 16 x int32, one int64 and 8 pointers (fishrt/_ffi.py: CodecOpCase)");
+int fs_selftest_codec_op(int device_id, const fs_codec_op_case* c, void* out, size_t out_cap, size_t* n_out, int* guard_ok) {
+    FS_ARG(c && out && n_out && guard_ok, "null argument");
+    *n_out = 0; *guard_ok = 0;
+    FS_TRY(fs::codec_op_selftest(device_id, *c, out, out_cap, n_out, guard_ok))
+}
 
 // ---- replica fan-out over RCCL (fs_comm.h)
 int fs_comm_unique_id(uint8_t id_out[FS_COMM_ID_BYTES]) { FS_ARG(id_out, "null argument"); FS_TRY(fs::Comm::unique_id(id_out)) }
@@ -365,6 +371,13 @@ int fs_codec_encode(fs_codec_t* c, const float* pcm, int n_samples, uint32_t* co
     FS_ARG(c && pcm && codes_out && n_frames, "null argument");
     FS_ARG(n_samples > 0, "empty input");
     FS_TRY(c->impl->encode(pcm, n_samples, codes_out, cap, n_frames))
+}
+int fs_selftest_codec_encode_stage(fs_codec_t* c, const float* pcm, int n_samples, int stage, float* out, size_t cap, size_t* n_out) {
+    FS_ARG(c && out && n_out && (pcm || stage == -2), "null argument");
+    FS_ARG(stage >= -2 && stage <= 6, "encoder stage tap: stage is -2 (mel table), -1 (log-mel) or 0 .. 6");
+    FS_ARG(stage == -2 || n_samples > 0, "empty input");
+    *n_out = 0;
+    FS_TRY(c->impl->encode_stage(pcm, n_samples, stage, out, cap, n_out))
 }
 int fs_codec_encode_batch(fs_codec_t* c, const float* pcm, int b, size_t stride, const int* n_samples, uint32_t* codes_out, size_t cap, size_t* n_frames) {
     FS_ARG(c && pcm && n_samples && codes_out && n_frames, "null argument");

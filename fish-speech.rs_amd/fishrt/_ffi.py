@@ -42,6 +42,13 @@ class ConvCase(C.Structure):  # fs_conv_case: one convolution for fs_selftest_co
                [(n, C.POINTER(C.c_float)) for n in ("x", "x_b", "x_c", "w", "bias", "w2", "bias2", "res", "gamma", "mean_a", "mean_b")]
 
 
+class CodecOpCase(C.Structure):  # fs_codec_op_case: one encoder-side / ConvNeXt / FSQ launcher for fs_selftest_codec_op
+    _fields_ = [(n, C.c_int32) for n in ("op", "B", "C", "T", "n", "n_fft", "hop", "nf", "n_mels", "s", "G", "dg", "ctx_mode", "item_rows",
+                                         "reserved0", "reserved1")] + [("ctx_elems", C.c_int64)] + \
+               [(n, C.POINTER(C.c_float)) for n in ("x", "w0", "w1", "w2", "w3", "ctx")] + \
+               [("ctx_off", C.POINTER(C.c_int64)), ("codes", C.POINTER(C.c_uint32))]
+
+
 FRAME_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32))
 
 # every symbol include/fishrt.h declares (tests/test_abi.py checks the library exports all of them)
@@ -55,7 +62,7 @@ SYMBOLS = ["fs_last_error", "fs_version", "fs_device_count", "fs_lm_create", "fs
            "fs_lm_session_add_scored", "fs_lm_session_poll_scores", "fs_selftest_score_rows",
            "fs_lm_session_add_traced", "fs_lm_session_poll_trace",
            "fs_lm_session_poll_alts", "fs_selftest_alt_rows",
-           "fs_selftest_conv1d",
+           "fs_selftest_conv1d", "fs_selftest_codec_op", "fs_selftest_codec_encode_stage",
            "fs_lm_weights_fingerprint", "fs_lm_session_prefix_export", "fs_lm_session_prefix_import",
            "fs_lm_session_prefix_from_slot", "fs_lm_session_last_frame",
            "fs_codec_create", "fs_codec_destroy", "fs_codec_load_safetensors", "fs_codec_load_synthetic",
@@ -102,6 +109,14 @@ FS_CONV_EPI_NONE, FS_CONV_EPI_GELU, FS_CONV_EPI_GAMMA_RES, FS_CONV_EPI_RES, FS_C
 FS_CONV_OUT_F32, FS_CONV_OUT_PLANES = 1, 2
 CONV_PROTOTYPES = {
     "fs_selftest_conv1d": [C.c_int, C.POINTER(ConvCase), _F32P, _F32P, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64)],
+}
+
+# fs_selftest_codec_op (ops: include/fishrt.h) and the encoder stage tap
+(FS_CODEC_OP_STFT_MAG, FS_CODEC_OP_MEL_LOG, FS_CODEC_OP_LAYERNORM_CF, FS_CODEC_OP_DWCONV_LN, FS_CODEC_OP_SPACE_TO_DEPTH, FS_CODEC_OP_FSQ_ENCODE,
+ FS_CODEC_OP_FSQ_PROJECT) = range(7)
+CODEC_OP_PROTOTYPES = {
+    "fs_selftest_codec_op": [C.c_int, C.POINTER(CodecOpCase), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)],
+    "fs_selftest_codec_encode_stage": [C.c_void_p, _F32P, C.c_int, C.c_int, _F32P, C.c_size_t, C.POINTER(C.c_size_t)],
 }
 
 # ... and of the calls that make a prefix out of a slot's history
@@ -159,7 +174,7 @@ def lib():
         L.fs_comm_destroy.argtypes = [C.c_void_p]
         L.fs_lm_destroy.argtypes = [C.c_void_p]
         L.fs_codec_destroy.argtypes = [C.c_void_p]
-        for name, argtypes in {**SCORE_PROTOTYPES, **TRACE_PROTOTYPES, **ALTS_PROTOTYPES, **CONV_PROTOTYPES, **HISTORY_PROTOTYPES,
+        for name, argtypes in {**SCORE_PROTOTYPES, **TRACE_PROTOTYPES, **ALTS_PROTOTYPES, **CONV_PROTOTYPES, **CODEC_OP_PROTOTYPES, **HISTORY_PROTOTYPES,
                                **RESAMPLE_PROTOTYPES}.items():
             getattr(L, name).argtypes = argtypes
         _lib = L

@@ -198,6 +198,24 @@ class FireflyCodec:
         ends = 2048 * np.cumsum(T)
         return [pcm[e - 2048 * t:e] for e, t in zip(ends, T)]
 
+    def encode_stage(self, pcm, stage):
+        """fishrt.h fs_selftest_codec_encode_stage: encode() of one mono clip at the codec rate with ONE intermediate tensor copied out -> f32,
+        channel-first, flat (the log-mel as (160, frames)): stage -1 the log-mel, 0..3 after each backbone stage, 4 after the final LayerNorm, 5 / 6 after each downsample block;
+        stage -2 (pcm ignored): the handle's mel filterbank (1025, 160).  Diagnostics / parity tests."""
+        if stage == -2:
+            out, n = np.empty(1025 * 160, np.float32), C.c_size_t(0)
+            _ffi.check(_ffi.lib().fs_selftest_codec_encode_stage(self._h, None, 0, -2, out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size),
+                                                                 C.byref(n)))
+            return out[: n.value].reshape(1025, 160)
+        pcm = np.ascontiguousarray(pcm, np.float32).reshape(-1)
+        frames = pcm.size // 512 + 8
+        out, n = np.empty(1025 * frames, np.float32), C.c_size_t(0)
+        _ffi.check(_ffi.lib().fs_selftest_codec_encode_stage(self._h, pcm.ctypes.data_as(C.POINTER(C.c_float)), int(pcm.size), int(stage),
+                                                             out.ctypes.data_as(C.POINTER(C.c_float)), C.c_size_t(out.size), C.byref(n)))
+        rows = 160 if stage == -1 else None
+        got = out[: n.value].copy()
+        return got.reshape(rows, -1) if rows else got  # stages 0..6: flat (channels * frames); the caller knows the stage's width
+
     def _encode_pcm(self, pcm_data, lengths, sample_rate, resample):
         if resample not in _ffi.RESAMPLE_MODES:
             raise ValueError(f"resample mode must be one of {sorted(_ffi.RESAMPLE_MODES)}")

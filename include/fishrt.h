@@ -148,6 +148,63 @@ typedef struct fs_conv_case {
 int fs_selftest_conv1d(int device_id, const fs_conv_case* c, float* y_out, float* planes_out, char* variant_out, size_t variant_cap,
                        uint64_t* range_out);
 
+/* ONE launcher of the codec's encoder-side / ConvNeXt / FSQ kernels (csrc/codec_kernels.h) on caller-provided host data, and nothing else:
+ * the inputs go to the device as they are (no re-layout: these launchers read the checkpoint's own layouts), one launcher call of kind `op`
+ * runs, the output comes back.  All tensors f32 row-major unless stated; T >= 1, every other dimension >= 1.
+ *   FS_CODEC_OP_STFT_MAG        codec_stft_mag: x = PCM (n), n_fft (2048 only), hop, T = frames to compute -> lin [n_fft/2+1][T].  Frame f
+ *                               = padded[f * hop, f * hop + n_fft) of the reflect pad that REPEATS the edge sample ((n_fft - hop) / 2 per
+ *                               side, so n >= that), zero behind the padded signal, periodic Hann, f64 FFT, (f32)|.| + 1e-6f.  T is the
+ *                               caller's: (T - 1) * hop < n + n_fft - hop is required (every frame starts inside the padded signal)
+ *   FS_CODEC_OP_MEL_LOG         codec_mel_log: x = lin [nf][T], w0 = filterbank [nf][n_mels] -> [n_mels][T] = logf(clamp(sum_k lin[k][t] *
+ *                               fb[k][m], 1e-5, 100)), the sum an ascending-k chain of separately rounded f32 products and sums
+ *   FS_CODEC_OP_LAYERNORM_CF    codec_layernorm_cf: x [C][T], w0 = weight [C], w1 = bias [C] -> [C][T]; per time step over the channels,
+ *                               biased variance, eps 1e-6
+ *   FS_CODEC_OP_DWCONV_LN       codec_dwconv_ln: x [B][C][T], w0 = depthwise taps [C][7], w1 = their bias [C], w2 / w3 = LayerNorm weight /
+ *                               bias [C] -> [B][C][T]; causal (tap k reads x[t + k - 6]).  ctx_mode 0: zeros in front of the signal; 1 (B ==
+ *                               1): ctx [C][16] = the last 16 samples per channel of what came before; 2: ctx = a pool of ctx_elems floats
+ *                               and ctx_off int64 [2B], item b reading its [C][16] context at ctx + ctx_off[2b] (the layout of the
+ *                               multi-stream decoder's offset table; entry 2b + 1 is not read).  C > 1024 is the launcher's own error
+ *   FS_CODEC_OP_SPACE_TO_DEPTH  codec_space_to_depth: x [C][T], s >= 1 -> [C * s][T / s], y[c * s + k][t] = x[c][t * s + k]; the last
+ *                               T % s columns are dropped, T < s gives an empty output
+ *   FS_CODEC_OP_FSQ_ENCODE      codec_fsq_encode: x [C][T], G groups (C % G == 0, dg = C / G), w0 = project_in weight [G][4][dg], w1 = its
+ *                               bias [G][4] -> uint32 indices [G][T] (levels 8, 5, 5, 5; bases 1, 8, 40, 200)
+ *   FS_CODEC_OP_FSQ_PROJECT     codec_fsq_project: codes uint32 [B * G][T] (each < 1000), dg, w0 = project_out weight [G][dg][4], w1 = its
+ *                               bias [G][dg] -> [B][G * dg][T]; item (b, g) reads row g * B + b, or with item_rows != 0 row b * G + g
+ * `out` receives n_out 4-byte elements (f32, or uint32 for FS_CODEC_OP_FSQ_ENCODE), out_cap >= that.  The device output buffer has 256
+ * guard elements in front of and behind its logical extent and is filled with 0xFF bytes (f32 NaN, uint32 0xFFFFFFFF) before the launch:
+ * an element the launcher did not write comes back as NaN, and guard_ok = 1 iff every guard byte is still 0xFF afterwards -- a write past
+ * either end is reported instead of corrupting a neighbour.  Diagnostics / parity tests. */
+enum { FS_CODEC_OP_STFT_MAG = 0, FS_CODEC_OP_MEL_LOG = 1, FS_CODEC_OP_LAYERNORM_CF = 2, FS_CODEC_OP_DWCONV_LN = 3,
+       FS_CODEC_OP_SPACE_TO_DEPTH = 4, FS_CODEC_OP_FSQ_ENCODE = 5, FS_CODEC_OP_FSQ_PROJECT = 6 };
+typedef struct fs_codec_op_case {
+    int32_t op;
+    int32_t B, C, T;
+    int32_t n, n_fft, hop;   /* FS_CODEC_OP_STFT_MAG */
+    int32_t nf, n_mels;      /* FS_CODEC_OP_MEL_LOG */
+    int32_t s;               /* FS_CODEC_OP_SPACE_TO_DEPTH */
+    int32_t G, dg;           /* FS_CODEC_OP_FSQ_* */
+    int32_t ctx_mode;        /* FS_CODEC_OP_DWCONV_LN */
+    int32_t item_rows;       /* FS_CODEC_OP_FSQ_PROJECT */
+    int32_t reserved[2];
+    int64_t ctx_elems;
+    const float *x, *w0, *w1, *w2, *w3, *ctx;
+    const int64_t* ctx_off;
+    const uint32_t* codes;
+} fs_codec_op_case;
+int fs_selftest_codec_op(int device_id, const fs_codec_op_case* c, void* out, size_t out_cap, size_t* n_out, int* guard_ok);
+
+/* Stage tap of the encoder on a LOADED handle: runs fs_codec_encode's device path on the clip exactly as fs_codec_encode does (same buffers,
+ * same launches, the codes are computed and dropped) and copies ONE intermediate tensor to the host:
+ *   stage -1     the log-mel [160][F], F = mel frames of the clip
+ *   stage 0..3   the activation after backbone stage i, [dims[i]][F]
+ *   stage 4      after the backbone's final LayerNorm, [C][F]
+ *   stage 5, 6   after the first / second downsample block of the quantizer, [C][F / 2] / [C][F / 4]
+ *   stage -2     no encoder run (pcm may be null): the handle's regenerated slaney mel filterbank, [1025][160]
+ * out receives *n_out floats (cap >= that).  The tap is one device-to-host copy on the handle's stream between two launches of the armed
+ * call; an unarmed call (every other entry point) launches nothing more and writes no buffer it did not write before.
+ * Diagnostics / parity tests. */
+int fs_selftest_codec_encode_stage(fs_codec_t* c, const float* pcm, int n_samples, int stage, float* out, size_t cap, size_t* n_out);
+
 /* Self-test of a LOADED handle, by name.  "persist": the persistent decode kernels of this binary (csrc/lm_persist.hip, lm_persist_slow.hip:
  * pinned weight registers, loads issued outside the compiler's wait-count bookkeeping) against the per-node kernels on the handle's own
  * weights -- 4 greedy frames on the persistent path with the decision capture armed for the first 2, then one teacher-forced per-node step
