@@ -124,6 +124,13 @@ int fs_selftest_codec_op(int device_id, const fs_codec_op_case* c, void* out, si
     *n_out = 0; *guard_ok = 0;
     FS_TRY(fs::codec_op_selftest(device_id, *c, out, out_cap, n_out, guard_ok))
 }
+static_assert(sizeof(fs_attn_case) == 32 * 4 + 13 * 8, "fs_attn_case is 30 x int32, one float, one int32 and 13 pointers (fishrt/_ffi.py: AttnCase)");
+int fs_selftest_attn(int device_id, const fs_attn_case* c, float* out, size_t out_cap, size_t* n_out, float* k_out, float* v_out,
+                     char* variant_out, size_t variant_cap, int* guard_ok) {
+    FS_ARG(c && n_out && variant_out && variant_cap >= 1 && guard_ok, "null argument");
+    *n_out = 0; *guard_ok = 0; variant_out[0] = 0;
+    FS_TRY(fs::attn_selftest(device_id, *c, out, out_cap, n_out, k_out, v_out, variant_out, variant_cap, guard_ok))
+}
 
 // ---- replica fan-out over RCCL (fs_comm.h)
 int fs_comm_unique_id(uint8_t id_out[FS_COMM_ID_BYTES]) { FS_ARG(id_out, "null argument"); FS_TRY(fs::Comm::unique_id(id_out)) }

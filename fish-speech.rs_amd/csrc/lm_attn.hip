@@ -4,10 +4,15 @@
 // Launch interface: AttnKernels<WT> in lm_kernels.h; RowKernels<WT>::rows_layer (lm_gemm.hip) decides which rows get an attention node.
 // Reference semantics implemented: fish_speech_core/lib/lm/dual_ar.rs:252-279 (SDPA), :239-249 (rope_i, k_attn_small_rows_tbl).
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <type_traits>
+#include <vector>
 
+#include "../../include/fishrt.h"
 #include "fs_common.h"
 #include "lm_kernels.h"
 #include "lm_dev.h"
@@ -696,33 +701,62 @@ int AttnKernels<WT>::tiles_per_block(const ModelDims& d, int nc_launch) {
     return (nc_launch + 7) / 8;
 }
 
+// ---- one place that decides the path: the launchers below dispatch through these plans and fs_selftest_attn reports their names
+std::string AttnPlan::name() const {
+    const std::string dh = std::to_string(DH), hs = hsplit > 1 ? "/hs" + std::to_string(hsplit) : std::string();
+    switch (kind) {
+    case DECODE: return std::string("decode/") + (f32_kv ? "f32/" : "bf16/") + dh + "/" + std::to_string(nrep) + hs;
+    case DECODE_PART: return "decode/part/tpb" + std::to_string(tpb);
+    case ROWS: return "rows/bf16/" + dh + "/" + std::to_string(nrep) + hs + (remap ? "/remap" : "");
+    case ROWS_CHUNKED: return "rows/chunked/" + dh;
+    case SMALL: return "small/" + dh + (ident ? "/ident" : "");
+    case SMALL_TBL: return "small_tbl/" + dh;
+    default: return group ? "prefill_mfma/group" : "prefill_mfma/seq";
+    }
+}
+
+template <typename WT>
+AttnPlan AttnKernels<WT>::decode_plan(const ModelDims& d, int nc_launch) {
+    static const int hs8 = [] { const char* e = std::getenv("FISHRT_ATTN_HSPLIT"); return e ? std::atoi(e) : 4; }();  // tuning hook: 1, 2 or 4
+    AttnPlan p;
+    p.f32_kv = std::is_same<KVT<WT>, float>::value;
+    p.DH = d.Dh;
+    if (const int tpb = tiles_per_block(d, nc_launch); tpb > 1) {
+        p.kind = AttnPlan::DECODE_PART; p.DH = 64; p.nrep = 2; p.hsplit = 4; p.tpb = tpb;
+        p.gx = d.Hk * 4; p.gz = (nc_launch + tpb - 1) / tpb;
+        return p;
+    }
+    // the 8 query heads of a Fish kv group go over hs blocks (bf16 KV only)
+    const bool split = d.Dh == 64 && d.n_rep == 8 && !std::is_same<WT, float>::value;
+    const int hs = split && (hs8 == 8 || hs8 == 4 || hs8 == 2) ? hs8 : 1;
+    p.kind = AttnPlan::DECODE; p.hsplit = hs; p.nrep = d.n_rep / hs; p.gx = d.Hk * nc_launch * hs;
+    if (hs != 8 && !(attn_geom_ok(d) && dispatch_attn(d.Dh, p.nrep, [](auto, auto) {})))
+        throw Error("unsupported attention geometry (head_dim, n_rep) = (" + std::to_string(d.Dh) + ", " +
+                    std::to_string(d.n_rep) + ")");
+    return p;
+}
+
 template <typename WT>
 void AttnKernels<WT>::decode(const ModelDims& d, const float* q, KVView kv, const SeqState* state, float* part,
                              int n_chunks_max, int nc_launch, hipStream_t st) {
     using KT = KVT<WT>;
     FS_REQUIRE(nc_launch >= 1 && nc_launch <= n_chunks_max, "bad attention chunk count");
-    const int grid = d.Hk * nc_launch;
     FS_REQUIRE(n_chunks_max <= 128, "attention supports at most 128 chunks per sequence");
-    static const int hs8 = [] { const char* e = std::getenv("FISHRT_ATTN_HSPLIT"); return e ? std::atoi(e) : 4; }();  // tuning hook: 1, 2 or 4
-    if (const int tpb = tiles_per_block(d, nc_launch); tpb > 1) {
+    const AttnPlan p = decode_plan(d, nc_launch);
+    if (p.kind == AttnPlan::DECODE_PART) {
         if constexpr (!std::is_same<WT, float>::value)
-            hipLaunchKernelGGL((k_attn_rows<KT, 64, 2, true>), dim3(d.Hk * 4, 1, (nc_launch + tpb - 1) / tpb), dim3(AttnGeom<KT, 64>::NW * 64), 0,
-                               st, q, kv, state, d.Hk, 0, 0, (bf16_t*)nullptr, 4, part, n_chunks_max, tpb);
+            hipLaunchKernelGGL((k_attn_rows<KT, 64, 2, true>), dim3(p.gx, 1, p.gz), dim3(AttnGeom<KT, 64>::NW * 64), 0,
+                               st, q, kv, state, d.Hk, 0, 0, (bf16_t*)nullptr, p.hsplit, part, n_chunks_max, p.tpb);
         FS_LAUNCH_CHECK();
         return;
     }
-    // the 8 query heads of a Fish kv group go over hs blocks (bf16 KV only)
-    const bool split = d.Dh == 64 && d.n_rep == 8 && !std::is_same<WT, float>::value;
-    const int hs = split && (hs8 == 8 || hs8 == 4 || hs8 == 2) ? hs8 : 1;
     auto go = [&](auto dh, auto nr) {
         constexpr int DH = decltype(dh)::value, NREP = decltype(nr)::value;
-        hipLaunchKernelGGL((k_attn_decode<KT, DH, NREP>), dim3(grid * hs), dim3(AttnGeom<KT, DH>::NW * 64), 0, st, q, kv, state, part, d.Hk, n_chunks_max,
-                           nc_launch, 0, 0, hs);
+        hipLaunchKernelGGL((k_attn_decode<KT, DH, NREP>), dim3(p.gx), dim3(AttnGeom<KT, DH>::NW * 64), 0, st, q, kv, state, part, d.Hk, n_chunks_max,
+                           nc_launch, 0, 0, p.hsplit);
     };
-    if (hs == 8) go(std::integral_constant<int, 64>(), std::integral_constant<int, 1>());
-    else if (!attn_geom_ok(d) || !dispatch_attn(d.Dh, d.n_rep / hs, go))
-        throw Error("unsupported attention geometry (head_dim, n_rep) = (" + std::to_string(d.Dh) + ", " +
-                    std::to_string(d.n_rep) + ")");
+    if (p.nrep == 1) go(std::integral_constant<int, 64>(), std::integral_constant<int, 1>());
+    else dispatch_attn(p.DH, p.nrep, go);
     FS_LAUNCH_CHECK();
 }
 
@@ -732,46 +766,73 @@ bool AttnKernels<WT>::rows_qkv0_ok(const ModelDims& d, const RowsCtx& c) {
 }
 
 template <typename WT>
-void AttnKernels<WT>::rows(const ModelDims& d, int M, const RowsCtx& c, KVView kv, bool tbl0, hipStream_t st) {
-    if constexpr (std::is_same<WT, float>::value) {
-        throw Error("the MFMA row path needs bf16 or fp8 weights");
+AttnPlan AttnKernels<WT>::rows_plan(const ModelDims& d, int M, const RowsCtx& c, bool tbl0) {
+    if (std::is_same<WT, float>::value) throw Error("the MFMA row path needs bf16 or fp8 weights");
+    AttnPlan p;
+    p.DH = d.Dh; p.nrep = d.n_rep;
+    if (tbl0) {
+        p.kind = AttnPlan::SMALL_TBL; p.DH = 64; p.ident = c.identity_pages; p.gx = M;
+    } else if (c.seq_rows > 0) {
+        // group prefill: M = n_seq * seq_rows rows, sequence s starts at state->pos (or c.seq_states[s].pos); flash attention per sequence
+        FS_REQUIRE(d.Dh == 64 && M % c.seq_rows == 0 && !c.no_flash, "group prefill needs head_dim 64 and whole sequences");
+        p.kind = AttnPlan::PREFILL_MFMA; p.group = true; p.gx = d.H * ((c.seq_rows + 15) / 16); p.gy = M / c.seq_rows;
+    } else if (c.pos_step == 1 && c.pt_stride == 0 && (c.stage_mask & 4u) && d.Dh == 64 && M > 1 && !c.no_flash) {
+        // prefill: causal flash attention on the matrix cores, result straight into the Wo GEMM's input
+        p.kind = AttnPlan::PREFILL_MFMA; p.gx = d.H * ((M + 15) / 16);
+    } else if (c.small_attn && (c.stage_mask & 4u) && d.H <= 32 && (d.Dh == 64 || d.Dh == 32)) {
+        // fast decoder: <= 8 tokens in one page -> one node instead of two
+        p.kind = AttnPlan::SMALL; p.ident = c.identity_pages; p.gx = M;
+    } else if (c.pos_step <= 0 && !c.chunked_attn && attn_geom_ok(d)) {
+        // static-batch decode: one fused node per layer (whole KV prefix per (kv head, row) block)
+        // few rows: split the 8 query heads of a kv group over two blocks (64 -> 128 blocks at 32 rows)
+        const int hs = (d.Dh == 64 && d.n_rep == 8) ? (d.Hk * M <= 64 ? 4 : (d.Hk * M < 256 ? 2 : 1)) : 1;
+        p.kind = AttnPlan::ROWS; p.hsplit = hs; p.nrep = d.n_rep / hs; p.gx = d.Hk * hs; p.gy = M;
+        const int total = (int)(p.gx * p.gy), per_xcd = total / (8 * hs);  // k_attn_rows' own condition
+        p.remap = hs > 1 && per_xcd * 8 * hs == total;
     } else {
+        FS_REQUIRE(M <= c.part_rows, "more rows than the attention-partials buffer holds");
+        p.kind = AttnPlan::ROWS_CHUNKED; p.gx = d.Hk * c.nc_launch; p.gy = M;
+    }
+    return p;
+}
+
+template <typename WT>
+void AttnKernels<WT>::rows(const ModelDims& d, int M, const RowsCtx& c, KVView kv, bool tbl0, hipStream_t st) {
+    const AttnPlan p = rows_plan(d, M, c, tbl0);
+    if constexpr (!std::is_same<WT, float>::value) {
         using KT = KVT<WT>;  // bf16 KV cache for both weight types
-        if (tbl0)
-            hipLaunchKernelGGL((k_attn_small_rows_tbl<64>), dim3(M), dim3(256), 0, st, c.qkv0_tbl, c.row_states, c.code_slot, kv, c.state, d.H, d.Hk, c.pos_step,
+        switch (p.kind) {
+        case AttnPlan::SMALL_TBL:
+            hipLaunchKernelGGL((k_attn_small_rows_tbl<64>), dim3(p.gx), dim3(256), 0, st, c.qkv0_tbl, c.row_states, c.code_slot, kv, c.state, d.H, d.Hk, c.pos_step,
                                c.pt_stride, c.cos_t, c.sin_t, c.A, (int)c.identity_pages);
-        else if (c.seq_rows > 0) {
-            // group prefill: M = n_seq * seq_rows rows, sequence s starts at state->pos (or c.seq_states[s].pos); flash attention per sequence
-            FS_REQUIRE(d.Dh == 64 && M % c.seq_rows == 0 && !c.no_flash, "group prefill needs head_dim 64 and whole sequences");
-            if (c.stage_mask & 4u)
-                hipLaunchKernelGGL(k_attn_prefill_mfma, dim3(d.H * ((c.seq_rows + 15) / 16), M / c.seq_rows), dim3(256), 0, st, c.Q, kv, c.state,
+            break;
+        case AttnPlan::PREFILL_MFMA:
+            if (!p.group)
+                hipLaunchKernelGGL(k_attn_prefill_mfma, dim3(p.gx), dim3(256), 0, st, c.Q, kv, c.state, M, d.H, d.Hk, c.A, 0,
+                                   (const SeqState*)nullptr);
+            else if (c.stage_mask & 4u)
+                hipLaunchKernelGGL(k_attn_prefill_mfma, dim3(p.gx, p.gy), dim3(256), 0, st, c.Q, kv, c.state,
                                    c.seq_rows, d.H, d.Hk, c.A, c.pt_stride, c.seq_states);
-        } else if (c.pos_step == 1 && c.pt_stride == 0 && (c.stage_mask & 4u) && d.Dh == 64 && M > 1 && !c.no_flash) {
-            // prefill: causal flash attention on the matrix cores, result straight into the Wo GEMM's input
-            hipLaunchKernelGGL(k_attn_prefill_mfma, dim3(d.H * ((M + 15) / 16)), dim3(256), 0, st, c.Q, kv, c.state, M, d.H, d.Hk, c.A, 0,
-                               (const SeqState*)nullptr);
-        } else if (c.small_attn && (c.stage_mask & 4u) && d.H <= 32 && (d.Dh == 64 || d.Dh == 32)) {
-            // fast decoder: <= 8 tokens in one page -> one node instead of two
-            if (d.Dh == 64)
-                hipLaunchKernelGGL((k_attn_small_rows<64>), dim3(M), dim3(256), 0, st, c.Q, kv, c.state, d.H, d.Hk, c.pos_step, c.pt_stride, c.A, (int)c.identity_pages);
+            break;
+        case AttnPlan::SMALL:
+            if (p.DH == 64)
+                hipLaunchKernelGGL((k_attn_small_rows<64>), dim3(p.gx), dim3(256), 0, st, c.Q, kv, c.state, d.H, d.Hk, c.pos_step, c.pt_stride, c.A, (int)c.identity_pages);
             else
-                hipLaunchKernelGGL((k_attn_small_rows<32>), dim3(M), dim3(256), 0, st, c.Q, kv, c.state, d.H, d.Hk, c.pos_step, c.pt_stride, c.A, (int)c.identity_pages);
-        } else if (c.pos_step <= 0 && !c.chunked_attn && attn_geom_ok(d)) {
-            // static-batch decode: one fused node per layer (whole KV prefix per (kv head, row) block)
-            // few rows: split the 8 query heads of a kv group over two blocks (64 -> 128 blocks at 32 rows)
-            const int hs = (d.Dh == 64 && d.n_rep == 8) ? (d.Hk * M <= 64 ? 4 : (d.Hk * M < 256 ? 2 : 1)) : 1;
+                hipLaunchKernelGGL((k_attn_small_rows<32>), dim3(p.gx), dim3(256), 0, st, c.Q, kv, c.state, d.H, d.Hk, c.pos_step, c.pt_stride, c.A, (int)c.identity_pages);
+            break;
+        case AttnPlan::ROWS:
             if (c.stage_mask & 4u)
-                dispatch_attn(d.Dh, d.n_rep / hs, [&](auto dh, auto nr) {
+                dispatch_attn(p.DH, p.nrep, [&](auto dh, auto nr) {
                     constexpr int DH = decltype(dh)::value, NREP = decltype(nr)::value;
-                    hipLaunchKernelGGL((k_attn_rows<KT, DH, NREP>), dim3(d.Hk * hs, M), dim3(AttnGeom<KT, DH>::NW * 64), 0, st, c.Q, kv, c.state, d.Hk, c.pos_step,
-                                       c.pt_stride, c.A, hs);
+                    hipLaunchKernelGGL((k_attn_rows<KT, DH, NREP>), dim3(p.gx, p.gy), dim3(AttnGeom<KT, DH>::NW * 64), 0, st, c.Q, kv, c.state, d.Hk, c.pos_step,
+                                       c.pt_stride, c.A, p.hsplit);
                 });
-        } else {
-            FS_REQUIRE(M <= c.part_rows, "more rows than the attention-partials buffer holds");
+            break;
+        default:
             if (c.stage_mask & 4u) {
-                const bool ok = attn_geom_ok(d) && dispatch_attn(d.Dh, d.n_rep, [&](auto dh, auto nr) {
+                const bool ok = attn_geom_ok(d) && dispatch_attn(p.DH, p.nrep, [&](auto dh, auto nr) {
                     constexpr int DH = decltype(dh)::value, NREP = decltype(nr)::value;
-                    hipLaunchKernelGGL((k_attn_decode<KT, DH, NREP>), dim3(d.Hk * c.nc_launch, M), dim3(AttnGeom<KT, DH>::NW * 64), 0, st, c.Q, kv, c.state, c.part,
+                    hipLaunchKernelGGL((k_attn_decode<KT, DH, NREP>), dim3(p.gx, p.gy), dim3(AttnGeom<KT, DH>::NW * 64), 0, st, c.Q, kv, c.state, c.part,
                                        d.Hk, c.n_chunks_max, c.nc_launch, c.pos_step, c.pt_stride, 1);
                 });
                 if (!ok) throw Error("unsupported attention geometry");
@@ -789,5 +850,331 @@ void AttnKernels<WT>::rows(const ModelDims& d, int M, const RowsCtx& c, KVView k
 template struct AttnKernels<bf16_t>;
 template struct AttnKernels<float>;
 template struct AttnKernels<fp8_t>;
+
+// ================================================================================================ fs_selftest_attn (include/fishrt.h)
+// ONE launcher call on caller data through AttnKernels / LmKernels::wo and nothing else.  Everything the launch writes lies between
+// 256-element guards of 0xFF bytes, outputs are NaN-poisoned, and the whole case is validated on the host before the first device call.
+__global__ void k_attn_expf_probe(const float* __restrict__ x, float* __restrict__ y, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) y[i] = __expf(x[i]);
+}
+
+namespace {
+constexpr size_t kAttnGuard = 256;
+struct AttnDev {  // device buffer of n elements of es bytes between two guards, all 0xFF bytes at first
+    void* p = nullptr;
+    size_t n = 0, es = 4;
+    void alloc(size_t n_, size_t es_, hipStream_t st) {
+        n = n_; es = es_;
+        FS_HIP(hipMalloc(&p, (n + 2 * kAttnGuard) * es));
+        FS_HIP(hipMemsetAsync(p, 0xFF, (n + 2 * kAttnGuard) * es, st));
+    }
+    char* data() const { return (char*)p + kAttnGuard * es; }
+    void up(const void* src, hipStream_t st) { FS_HIP(hipMemcpyAsync(data(), src, n * es, hipMemcpyHostToDevice, st)); }
+    bool intact(hipStream_t st) const {
+        if (!p) return true;
+        std::vector<uint8_t> g(2 * kAttnGuard * es);
+        FS_HIP(hipMemcpyAsync(g.data(), p, kAttnGuard * es, hipMemcpyDeviceToHost, st));
+        FS_HIP(hipMemcpyAsync(g.data() + kAttnGuard * es, data() + n * es, kAttnGuard * es, hipMemcpyDeviceToHost, st));
+        FS_HIP(hipStreamSynchronize(st));
+        for (uint8_t b : g) if (b != 0xFF) return false;
+        return true;
+    }
+    ~AttnDev() { if (p) (void)hipFree(p); }
+};
+
+// everything validate() derives from a case: the launch plan, its name, the output extent
+struct AttnCaseInfo {
+    ModelDims d{};
+    AttnPlan plan;
+    std::string name;
+    int K = 0, CH = 0, Mcap = 0, n_seq = 0;
+    bool f32_kv = false, use_part = false;
+    size_t n_out = 0, n_pool = 0, n_part = 0;
+    RowsCtx rc{};
+};
+
+template <typename WT>
+void attn_validate(const fs_attn_case& c, AttnCaseInfo& I) {
+    auto req = [](bool ok, const char* msg) { if (!ok) throw Error(std::string("attention self-test: ") + msg); };
+    req(c.H >= 1 && c.H <= 32 && c.Hk >= 1 && c.Hk <= c.H && c.H % c.Hk == 0, "1 <= Hk <= H <= 32, H a multiple of Hk");
+    ModelDims& d = I.d;
+    d.H = c.H; d.Hk = c.Hk; d.Dh = c.Dh; d.n_rep = c.H / c.Hk; d.dim = c.dim; d.inter = 0; d.eps = 1e-6f;
+    req(attn_geom_ok(d), "(head_dim, n_rep) must be (64, 8), (64, 2) or (32, 2)");
+    req(c.dim == c.H * c.Dh, "dim must equal H * Dh");
+    I.K = c.H * c.Dh;
+    I.f32_kv = std::is_same<KVT<WT>, float>::value;
+    I.CH = AttnKernels<WT>::chunk();
+    req(c.n_pages >= 1 && c.n_pages <= 4096 && c.k && c.v, "1 <= n_pages <= 4096, k and v are required");
+    I.n_pool = (size_t)c.n_pages * c.Hk * KV_PAGE * c.Dh;
+    const bool wo_op = c.op == FS_ATTN_DECODE_WO || c.op == FS_ATTN_WO_FUSED;
+    if (wo_op) req(c.wo && c.x && (c.dim == 128 || c.dim == 256 || c.dim == 1024) && c.H <= 16, "wo and x are required, dim in {128, 256, 1024}, H <= 16");
+    if (c.op == FS_ATTN_WO_FUSED) {
+        req(c.M == 1 && c.fused_T >= 1 && c.fused_T <= 8 && c.q, "fused wo: M == 1, 1 <= fused_T <= 8, q is required");
+        I.name = "wo/fused/" + std::to_string(c.Dh);
+        I.n_out = (size_t)c.dim;
+        return;
+    }
+    // the page table: every entry a page of the pool, whichever slot a block may read
+    req(c.page_table && c.pt_rows >= 1 && c.pt_len >= 1 && (long long)c.pt_rows * c.pt_len <= (1 << 20) && c.pt_stride >= 0, "page_table [pt_rows][pt_len] is required");
+    const long long n_tab = (long long)c.pt_rows * c.pt_len;
+    for (long long i = 0; i < n_tab; ++i) req(c.page_table[i] >= 0 && c.page_table[i] < c.n_pages, "a page id is outside the pool");
+    // table row r (at r * pt_stride) is read at slots [0, n): inside the table, and inside its own pt_len
+    auto need = [&](int r, long long n) {
+        req(n <= c.pt_len && (long long)r * c.pt_stride + n <= n_tab, "a launched block would read a page-table slot outside the table (T <= pt_len * 64)");
+    };
+    auto pos_ok = [&](long long p) { req(p >= 0 && p < (1 << 20), "a row position is outside [0, 2^20)"); };
+    req(c.q, "q is required");
+    if (c.op == FS_ATTN_DECODE || c.op == FS_ATTN_DECODE_WO) {
+        req(c.M == 1 && c.pos_step == 0, "decode: M == 1, pos_step 0");
+        pos_ok(c.pos);
+        req(c.nc_launch >= 1 && c.nc_launch <= c.n_chunks_max && c.n_chunks_max <= 128, "1 <= nc_launch <= n_chunks_max <= 128");
+        const long long T = (long long)c.pos + 1;
+        req(T <= (long long)c.nc_launch * I.CH, "the launched chunks do not cover the length");
+        I.plan = AttnKernels<WT>::decode_plan(d, c.nc_launch);
+        // k_attn_decode reads the slot of every launched chunk, whatever the length; the super-chunk kernel those below the length
+        need(0, I.plan.kind == AttnPlan::DECODE ? (long long)c.nc_launch * I.CH / KV_PAGE : (T + I.CH - 1) / I.CH * I.CH / KV_PAGE);
+        I.name = I.plan.name();
+        I.n_part = (size_t)c.H * c.n_chunks_max * (c.Dh + 2);
+        I.use_part = true;
+        if (c.op == FS_ATTN_DECODE_WO) {
+            const int tpb = AttnKernels<WT>::tiles_per_block(d, c.nc_launch);
+            I.name += (c.nc_launch + tpb - 1) / tpb <= 8 ? "+wo/reg" : "+wo/lds";
+            I.n_out = (size_t)c.dim;
+        } else I.n_out = I.n_part;
+        return;
+    }
+    req(c.op == FS_ATTN_ROWS, "unknown op");
+    req(c.M >= 1 && c.M <= 512, "rows: 1 <= M <= 512");
+    req(c.pos_step == 1 || c.pos_step == 0 || c.pos_step == -1, "pos_step is 1, 0 or -1");
+    req(c.pos_step >= 0 || c.row_pos, "pos_step < 0 needs row_pos");
+    req(c.seq_rows >= 0 && (c.seq_rows == 0 || (c.pos_step == 1 && c.M % c.seq_rows == 0)), "group prefill: pos_step 1, M a multiple of seq_rows");
+    I.Mcap = (c.M + 31) / 32 * 32;
+    I.n_seq = c.seq_rows > 0 ? c.M / c.seq_rows : 0;
+    RowsCtx& rc = I.rc;
+    rc.Mcap = I.Mcap; rc.part_rows = c.part_rows; rc.n_chunks_max = c.n_chunks_max; rc.nc_launch = c.nc_launch;
+    rc.pos_step = c.pos_step; rc.pt_stride = c.pt_stride; rc.seq_rows = c.seq_rows;
+    rc.no_flash = c.no_flash != 0; rc.chunked_attn = c.chunked_attn != 0; rc.small_attn = c.small_attn != 0; rc.identity_pages = c.identity_pages != 0;
+    rc.code_slot = c.code_slot;
+    if (c.tbl0) req(AttnKernels<WT>::rows_qkv0_ok(d, rc), "tbl0 needs small_attn, head_dim 64, H <= 32, Hk <= 4");
+    I.plan = AttnKernels<WT>::rows_plan(d, c.M, rc, c.tbl0 != 0);
+    I.name = I.plan.name();
+    auto T_of = [&](int m) -> long long {
+        if (c.seq_rows > 0) return (long long)(c.seq_pos ? c.seq_pos[m / c.seq_rows] : c.pos) + m % c.seq_rows + 1;
+        return (c.pos_step < 0 ? (long long)c.row_pos[m] : (long long)c.pos + (long long)m * c.pos_step) + 1;
+    };
+    for (int m = 0; m < c.M; ++m) pos_ok(T_of(m) - 1);
+    if (c.small_attn) for (int m = 0; m < c.M; ++m) req(T_of(m) <= 8, "small_attn: every row attends over <= 8 tokens");
+    switch (I.plan.kind) {
+    case AttnPlan::SMALL_TBL:
+    case AttnPlan::SMALL:
+        req(c.small_attn, "the one-page kernels need small_attn");
+        for (int m = 0; m < c.M; ++m) {
+            if (c.identity_pages) req(m < c.n_pages, "identity pages: row m uses page m");
+            else need(m, 1);
+        }
+        if (I.plan.kind == AttnPlan::SMALL_TBL) {
+            req(c.tbl && c.codes && c.cos_t && c.sin_t && c.tbl_rows >= 1 && c.tbl_rows <= 4096 && c.rope_rows >= 1 && c.rope_rows <= (1 << 16),
+                "tbl0 needs tbl, codes, cos_t, sin_t, 1 <= tbl_rows <= 4096, 1 <= rope_rows <= 2^16");
+            req(c.code_slot >= 0 && c.code_slot < 16, "code_slot is one of the 16 cur[] cells");
+            std::vector<char> used((size_t)c.n_pages, 0);
+            for (int m = 0; m < c.M; ++m) {
+                req(c.codes[m] < (uint32_t)c.tbl_rows, "a code is outside the qkv table");
+                const long long rp = T_of(m) - 1 + c.rope_off;
+                req(rp >= 0 && rp < c.rope_rows, "a RoPE row is outside the cos / sin tables");
+                const int page = c.identity_pages ? m : c.page_table[(size_t)m * c.pt_stride];
+                req(!used[(size_t)page], "tbl0: two rows append to the same page");
+                used[(size_t)page] = 1;
+            }
+        }
+        break;
+    case AttnPlan::PREFILL_MFMA:
+        if (I.plan.group) for (int s = 0; s < I.n_seq; ++s) need(s, (T_of(s * c.seq_rows + c.seq_rows - 1) + KV_PAGE - 1) / KV_PAGE);
+        else need(0, (T_of(c.M - 1) + KV_PAGE - 1) / KV_PAGE);
+        break;
+    case AttnPlan::ROWS:
+        for (int m = 0; m < c.M; ++m) need(m, (T_of(m) + I.CH - 1) / I.CH * I.CH / KV_PAGE);
+        break;
+    default:  // k_attn_decode over (chunks x rows) + k_attn_combine
+        req(c.nc_launch >= 1 && c.nc_launch <= c.n_chunks_max && c.n_chunks_max <= 128 && c.part_rows >= c.M && c.part_rows <= 512,
+            "chunked rows: 1 <= nc_launch <= n_chunks_max <= 128, M <= part_rows <= 512");
+        for (int m = 0; m < c.M; ++m) {
+            req(T_of(m) <= (long long)c.nc_launch * I.CH, "the launched chunks do not cover a row's length");
+            need(m, (long long)c.nc_launch * I.CH / KV_PAGE);
+        }
+        I.use_part = true;
+        I.n_part = (size_t)c.part_rows * c.H * c.n_chunks_max * (c.Dh + 2);
+    }
+    I.n_out = (size_t)2 * I.Mcap * I.K;
+}
+
+template <typename WT>
+void attn_selftest_run(int device, const fs_attn_case& c, const AttnCaseInfo& I, float* out, float* k_out, float* v_out, int* guard_ok) {
+    using KT = KVT<WT>;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw Error("no HIP device visible: libfishrt has no CPU fallback (MI355X / gfx950 required)");
+    FS_REQUIRE(device >= 0 && device < ndev, "device_id out of range");
+    FS_HIP(hipSetDevice(device));
+    hipStream_t st = nullptr;
+    FS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } sg{st};
+    const ModelDims& d = I.d;
+    // pools in the KV type
+    AttnDev dk, dv, dtab, dq, dpart, dx, dA, dwo, dso, dstate, drstate, dsstate, dtbl, dcos, dsin;
+    std::vector<KT> hk(I.n_pool), hv(I.n_pool);
+    for (size_t i = 0; i < I.n_pool; ++i) {
+        if constexpr (std::is_same<KT, float>::value) { hk[i] = c.k[i]; hv[i] = c.v[i]; }
+        else { hk[i] = f32_to_bf16_host(c.k[i]); hv[i] = f32_to_bf16_host(c.v[i]); }
+    }
+    dk.alloc(I.n_pool, sizeof(KT), st); dk.up(hk.data(), st);
+    dv.alloc(I.n_pool, sizeof(KT), st); dv.up(hv.data(), st);
+    if (c.page_table) { dtab.alloc((size_t)c.pt_rows * c.pt_len, 4, st); dtab.up(c.page_table, st); }
+    dq.alloc((size_t)c.M * I.K, 4, st); dq.up(c.q, st);
+    KVView kv{dk.data(), dv.data(), c.page_table ? (const int*)dtab.data() : nullptr};
+    // generator states: positions, RoPE offset, the rows' codes
+    const int n_state = std::max(c.M, 1);
+    std::vector<SeqState> hs((size_t)n_state), hseq((size_t)std::max(I.n_seq, 1));
+    for (auto& s : hs) std::memset(&s, 0, sizeof(SeqState));
+    for (auto& s : hseq) std::memset(&s, 0, sizeof(SeqState));
+    for (int m = 0; m < n_state; ++m) {
+        hs[(size_t)m].pos = (c.op == FS_ATTN_ROWS && c.pos_step < 0) ? c.row_pos[m] : c.pos;
+        hs[(size_t)m].rope_off = c.rope_off;
+        if (c.op == FS_ATTN_ROWS && c.tbl0) hs[(size_t)m].cur[c.code_slot] = c.codes[m];
+    }
+    for (int s = 0; s < I.n_seq; ++s) hseq[(size_t)s].pos = c.seq_pos ? c.seq_pos[s] : c.pos;
+    dstate.alloc(hs.size() * sizeof(SeqState), 1, st); dstate.up(hs.data(), st);
+    const SeqState* state = (const SeqState*)dstate.data();
+    std::vector<float> host_out;
+    std::vector<uint16_t> host_A;
+    if (I.use_part) {
+        dpart.alloc(I.n_part, 4, st);
+        if (c.op == FS_ATTN_DECODE_WO) {  // stale partials instead of poison: the merge has to mask them
+            std::vector<float> fill(I.n_part, c.stale_part);
+            dpart.up(fill.data(), st);
+            FS_HIP(hipStreamSynchronize(st));
+        }
+    }
+    LayerW w{};
+    if (c.op == FS_ATTN_DECODE_WO || c.op == FS_ATTN_WO_FUSED) {
+        const size_t nw = (size_t)c.dim * c.dim;
+        std::vector<WT> hw(nw);
+        for (size_t i = 0; i < nw; ++i) {
+            if constexpr (std::is_same<WT, float>::value) hw[i] = c.wo[i];
+            else if constexpr (std::is_same<WT, bf16_t>::value) hw[i] = f32_to_bf16_host(c.wo[i]);
+            else hw[i] = fp8_t{f32_to_e4m3(c.wo[i])};
+        }
+        dwo.alloc(nw, sizeof(WT), st); dwo.up(hw.data(), st);
+        w.wo = dwo.data();
+        if constexpr (std::is_same<WT, fp8_t>::value) {
+            std::vector<float> ones((size_t)c.dim, 1.0f);
+            dso.alloc((size_t)c.dim, 4, st); dso.up(ones.data(), st);
+            FS_HIP(hipStreamSynchronize(st));
+            w.s_o = (const float*)dso.data();
+        }
+        dx.alloc((size_t)c.dim, 4, st); dx.up(c.x, st);
+        FS_HIP(hipStreamSynchronize(st));  // hw goes out of scope below
+    }
+    switch (c.op) {
+    case FS_ATTN_DECODE:
+        AttnKernels<WT>::decode(d, (const float*)dq.data(), kv, state, (float*)dpart.data(), c.n_chunks_max, c.nc_launch, st);
+        break;
+    case FS_ATTN_DECODE_WO:
+        AttnKernels<WT>::decode(d, (const float*)dq.data(), kv, state, (float*)dpart.data(), c.n_chunks_max, c.nc_launch, st);
+        LmKernels<WT>::wo(d, (const float*)dpart.data(), c.n_chunks_max, c.nc_launch, state, (const float*)dq.data(), kv, 0, w, (float*)dx.data(), st);
+        break;
+    case FS_ATTN_WO_FUSED:
+        LmKernels<WT>::wo(d, nullptr, 1, 1, state, (const float*)dq.data(), kv, c.fused_T, w, (float*)dx.data(), st);
+        break;
+    default: {
+        RowsCtx rc = I.rc;
+        dA.alloc((size_t)2 * I.Mcap * I.K, 2, st);
+        rc.Q = (float*)dq.data(); rc.A = (uint16_t*)dA.data(); rc.part = I.use_part ? (float*)dpart.data() : nullptr;
+        rc.state = state;
+        if (I.n_seq > 0 && c.seq_pos) {
+            dsstate.alloc(hseq.size() * sizeof(SeqState), 1, st); dsstate.up(hseq.data(), st);
+            rc.seq_states = (const SeqState*)dsstate.data();
+        }
+        if (c.tbl0) {
+            const size_t row = (size_t)(c.H + 2 * c.Hk) * c.Dh;
+            dtbl.alloc((size_t)c.tbl_rows * row, 4, st); dtbl.up(c.tbl, st);
+            dcos.alloc((size_t)c.rope_rows * (c.Dh / 2), 4, st); dcos.up(c.cos_t, st);
+            dsin.alloc((size_t)c.rope_rows * (c.Dh / 2), 4, st); dsin.up(c.sin_t, st);
+            rc.qkv0_tbl = (const float*)dtbl.data(); rc.cos_t = (const float*)dcos.data(); rc.sin_t = (const float*)dsin.data();
+            rc.row_states = state;
+        }
+        AttnKernels<WT>::rows(d, c.M, rc, kv, c.tbl0 != 0, st);
+    }
+    }
+    // results
+    if (c.op == FS_ATTN_ROWS) {
+        host_A.resize((size_t)2 * I.Mcap * I.K);
+        FS_HIP(hipMemcpyAsync(host_A.data(), dA.data(), host_A.size() * 2, hipMemcpyDeviceToHost, st));
+    } else {
+        host_out.resize(I.n_out);
+        FS_HIP(hipMemcpyAsync(host_out.data(), c.op == FS_ATTN_DECODE ? dpart.data() : dx.data(), I.n_out * 4, hipMemcpyDeviceToHost, st));
+    }
+    FS_HIP(hipMemcpyAsync(hk.data(), dk.data(), I.n_pool * sizeof(KT), hipMemcpyDeviceToHost, st));
+    FS_HIP(hipMemcpyAsync(hv.data(), dv.data(), I.n_pool * sizeof(KT), hipMemcpyDeviceToHost, st));
+    FS_HIP(hipStreamSynchronize(st));
+    bool ok = true;
+    for (const AttnDev* b : {&dk, &dv, &dpart, &dx, &dA}) ok = b->intact(st) && ok;
+    *guard_ok = ok ? 1 : 0;
+    if (c.op == FS_ATTN_ROWS) {
+        const size_t plane = (size_t)I.Mcap * I.K;
+        for (int m = 0; m < I.Mcap; ++m)
+            for (int k = 0; k < I.K; ++k) {
+                out[(size_t)m * I.K + k] = bf16_to_f32_host(host_A[frag_off(m, k, 0, I.K)]);
+                out[plane + (size_t)m * I.K + k] = bf16_to_f32_host(host_A[frag_off(m, k, 1, I.K)]);
+            }
+    } else std::memcpy(out, host_out.data(), I.n_out * 4);
+    for (size_t i = 0; i < I.n_pool; ++i) {
+        if constexpr (std::is_same<KT, float>::value) { if (k_out) k_out[i] = hk[i]; if (v_out) v_out[i] = hv[i]; }
+        else { if (k_out) k_out[i] = bf16_to_f32_host(hk[i]); if (v_out) v_out[i] = bf16_to_f32_host(hv[i]); }
+    }
+}
+
+void attn_expf_probe(int device, const fs_attn_case& c, float* out) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw Error("no HIP device visible: libfishrt has no CPU fallback (MI355X / gfx950 required)");
+    FS_REQUIRE(device >= 0 && device < ndev, "device_id out of range");
+    FS_HIP(hipSetDevice(device));
+    hipStream_t st = nullptr;
+    FS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } sg{st};
+    AttnDev dx, dy;
+    dx.alloc((size_t)c.n_expf, 4, st); dx.up(c.expf_x, st);
+    dy.alloc((size_t)c.n_expf, 4, st);
+    hipLaunchKernelGGL(k_attn_expf_probe, dim3((c.n_expf + 255) / 256), dim3(256), 0, st, (const float*)dx.data(), (float*)dy.data(), c.n_expf);
+    FS_LAUNCH_CHECK();
+    FS_HIP(hipMemcpyAsync(out, dy.data(), (size_t)c.n_expf * 4, hipMemcpyDeviceToHost, st));
+    FS_HIP(hipStreamSynchronize(st));
+}
+}  // namespace
+
+void attn_selftest(int device, const fs_attn_case& c, float* out, size_t out_cap, size_t* n_out, float* k_out, float* v_out, char* variant_out,
+                   size_t variant_cap, int* guard_ok) {
+    FS_REQUIRE(c.op >= FS_ATTN_DECODE && c.op <= FS_ATTN_EXPF, "attention self-test: unknown op");
+    if (c.op == FS_ATTN_EXPF) {
+        FS_REQUIRE(c.n_expf >= 1 && c.n_expf <= (1 << 22) && c.expf_x, "attention self-test: 1 <= n_expf <= 2^22, expf_x is required");
+        std::snprintf(variant_out, variant_cap, "expf");
+        if (c.plan_only) return;
+        FS_REQUIRE(out && out_cap >= (size_t)c.n_expf, "attention self-test: out capacity too small");
+        attn_expf_probe(device, c, out);
+        *n_out = (size_t)c.n_expf; *guard_ok = 1;
+        return;
+    }
+    FS_REQUIRE(c.wt >= FS_ATTN_WT_F32 && c.wt <= FS_ATTN_WT_FP8, "attention self-test: unknown weight type");
+    AttnCaseInfo I;
+    if (c.wt == FS_ATTN_WT_F32) attn_validate<float>(c, I);
+    else if (c.wt == FS_ATTN_WT_BF16) attn_validate<bf16_t>(c, I);
+    else attn_validate<fp8_t>(c, I);
+    std::snprintf(variant_out, variant_cap, "%s", I.name.c_str());
+    if (c.plan_only) return;
+    FS_REQUIRE(out && out_cap >= I.n_out, "attention self-test: out capacity too small");
+    if (c.wt == FS_ATTN_WT_F32) attn_selftest_run<float>(device, c, I, out, k_out, v_out, guard_ok);
+    else if (c.wt == FS_ATTN_WT_BF16) attn_selftest_run<bf16_t>(device, c, I, out, k_out, v_out, guard_ok);
+    else attn_selftest_run<fp8_t>(device, c, I, out, k_out, v_out, guard_ok);
+    *n_out = I.n_out;
+}
 
 }  // namespace fs

@@ -1,7 +1,7 @@
 // Device helpers shared by the transformer kernels (lm_kernels.hip), the row-path GEMMs (lm_gemm.hip), the attention kernels (lm_attn.hip)
 // and the on-device samplers (lm_sample.hip): weight-type traits, the streamed weight load, the paged KV address, cross-lane reductions,
 // the token embedding, row positions, and the fragment-major GEMM-input layout with the one-row RMSNorm + hi/lo split.
-// Device code only; the host-side launch interface is lm_kernels.h.
+// Device code only -- except frag_off, which the host side of fs_selftest_attn uses to de-fragment; the host-side launch interface is lm_kernels.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -142,7 +142,7 @@ __device__ __forceinline__ void split_bf16(float a, bf16_t& hi, bf16_t& lo) {
 // [rows][K] activation matrix lives at (in bf16 elements)
 //     (((((m / 32) * (K / 32) + k / 32) * 2 + part) * 2 + (m / 16) % 2) * 64 + ((k / 8) % 4) * 16 + m % 16) * 8 + k % 8
 // i.e. [32-row panel][32-deep k-step][part][16-row tile][lane = kq*16 + row][8 consecutive k].
-__device__ __forceinline__ size_t frag_off(int m, int k, int part, int K) {
+__host__ __device__ __forceinline__ size_t frag_off(int m, int k, int part, int K) {
     const int p = m >> 5, mt = (m >> 4) & 1, lr = m & 15, kk = k >> 5, lq = (k >> 3) & 3, e = k & 7;
     return (((((size_t)p * (K >> 5) + kk) * 2 + part) * 2 + mt) * 64 + (lq * 16 + lr)) * 8 + e;
 }

@@ -14,9 +14,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <string>
 
 #include "fs_common.h"
 #include "fs_slot_book.h"
+
+struct fs_attn_case;
 
 namespace fs {
 
@@ -159,8 +162,28 @@ struct RowKernels {
 };
 
 // ---- attention launchers (lm_attn.hip; all asynchronous on `st`)
+// What an attention launcher will launch for a given call: decided in ONE place (AttnKernels::decode_plan / rows_plan), the launchers
+// dispatch through it, and fs_selftest_attn reports its name ("decode/bf16/64/2/hs4", "rows/bf16/64/4/hs2/remap", "small/64/ident", ...)
+struct AttnPlan {
+    enum Kind { DECODE, DECODE_PART, ROWS, ROWS_CHUNKED, SMALL, SMALL_TBL, PREFILL_MFMA };
+    Kind kind = DECODE;
+    bool f32_kv = false;   // KV type of the instantiation (f32 weights only)
+    int DH = 0;            // head_dim of the instantiation
+    int nrep = 0;          // query heads per block (template NREP; n_rep of the model for the kernels without it)
+    int hsplit = 1;        // blocks the query heads of one kv group are spread over
+    int tpb = 1;           // DECODE_PART: chunks per super-chunk block
+    bool remap = false;    // ROWS, hsplit > 1: k_attn_rows' XCD placement condition per_xcd * 8 * hsplit == total holds for this grid
+    bool group = false;    // PREFILL_MFMA: group pass (RowsCtx::seq_rows > 0)
+    bool ident = false;    // SMALL / SMALL_TBL: identity page table
+    unsigned gx = 1, gy = 1, gz = 1;  // grid
+    std::string name() const;
+};
+
 template <typename WT>
 struct AttnKernels {
+    // the kernel AttnKernels::decode / rows launch for these arguments (host only; throws what the launcher would throw)
+    static AttnPlan decode_plan(const ModelDims& d, int nc_launch);
+    static AttnPlan rows_plan(const ModelDims& d, int M, const RowsCtx& c, bool tbl0);
     // tokens per attention chunk: chunk c covers tokens [c * chunk(), (c + 1) * chunk())
     static int chunk();
     // batch-1 decode over more than 8 chunks: attention blocks take this many consecutive chunks each so that k_wo merges 8 partials
@@ -345,6 +368,9 @@ void launch_quant_rows_fp8(uint8_t* dst, float* scales, const float* src, int64_
 // out[slot * 256 + b] = f32 value the fp8 GEMV unpack path gives byte b at lane-slot `slot` (16 x 256 floats)
 void launch_fp8_decode_table(float* out, hipStream_t st);
 
+// test hook behind fs_selftest_attn (include/fishrt.h; harness at the bottom of lm_attn.hip)
+void attn_selftest(int device, const fs_attn_case& c, float* out, size_t out_cap, size_t* n_out, float* k_out, float* v_out, char* variant_out,
+                   size_t variant_cap, int* guard_ok);
 // test hook behind fs_selftest_sample_rows (include/fishrt.h)
 void debug_sample_rows(int device, const float* logits, int B, int n, double temp, double top_p, uint64_t top_k, uint64_t seed,
                        int call_index, uint32_t* out);

@@ -49,6 +49,16 @@ class CodecOpCase(C.Structure):  # fs_codec_op_case: one encoder-side / ConvNeXt
                [("ctx_off", C.POINTER(C.c_int64)), ("codes", C.POINTER(C.c_uint32))]
 
 
+class AttnCase(C.Structure):  # fs_attn_case: one attention launcher call for fs_selftest_attn
+    _fields_ = [(n, C.c_int32) for n in ("op", "wt", "H", "Hk", "Dh", "dim", "M", "pos", "pos_step", "rope_off", "pt_stride", "pt_rows", "pt_len",
+                                         "seq_rows", "n_chunks_max", "nc_launch", "part_rows", "no_flash", "chunked_attn", "small_attn",
+                                         "identity_pages", "n_pages", "fused_T", "tbl0", "code_slot", "tbl_rows", "rope_rows", "n_expf",
+                                         "plan_only", "reserved")] + [("stale_part", C.c_float), ("reserved2", C.c_int32)] + \
+               [(n, C.POINTER(C.c_int32)) for n in ("row_pos", "seq_pos", "page_table")] + \
+               [(n, C.POINTER(C.c_float)) for n in ("k", "v", "q", "wo", "x", "tbl", "cos_t", "sin_t", "expf_x")] + \
+               [("codes", C.POINTER(C.c_uint32))]
+
+
 FRAME_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32))
 
 # every symbol include/fishrt.h declares (tests/test_abi.py checks the library exports all of them)
@@ -62,7 +72,7 @@ SYMBOLS = ["fs_last_error", "fs_version", "fs_device_count", "fs_lm_create", "fs
            "fs_lm_session_add_scored", "fs_lm_session_poll_scores", "fs_selftest_score_rows",
            "fs_lm_session_add_traced", "fs_lm_session_poll_trace",
            "fs_lm_session_poll_alts", "fs_selftest_alt_rows",
-           "fs_selftest_conv1d", "fs_selftest_codec_op", "fs_selftest_codec_encode_stage",
+           "fs_selftest_conv1d", "fs_selftest_codec_op", "fs_selftest_codec_encode_stage", "fs_selftest_attn",
            "fs_lm_weights_fingerprint", "fs_lm_session_prefix_export", "fs_lm_session_prefix_import",
            "fs_lm_session_prefix_from_slot", "fs_lm_session_last_frame",
            "fs_codec_create", "fs_codec_destroy", "fs_codec_load_safetensors", "fs_codec_load_synthetic",
@@ -117,6 +127,14 @@ CONV_PROTOTYPES = {
 CODEC_OP_PROTOTYPES = {
     "fs_selftest_codec_op": [C.c_int, C.POINTER(CodecOpCase), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)],
     "fs_selftest_codec_encode_stage": [C.c_void_p, _F32P, C.c_int, C.c_int, _F32P, C.c_size_t, C.POINTER(C.c_size_t)],
+}
+
+# fs_selftest_attn (ops, weight types: include/fishrt.h)
+FS_ATTN_DECODE, FS_ATTN_DECODE_WO, FS_ATTN_WO_FUSED, FS_ATTN_ROWS, FS_ATTN_EXPF = range(5)
+FS_ATTN_WT_F32, FS_ATTN_WT_BF16, FS_ATTN_WT_FP8 = range(3)
+ATTN_PROTOTYPES = {
+    "fs_selftest_attn": [C.c_int, C.POINTER(AttnCase), _F32P, C.c_size_t, C.POINTER(C.c_size_t), _F32P, _F32P, C.c_char_p, C.c_size_t,
+                         C.POINTER(C.c_int)],
 }
 
 # ... and of the calls that make a prefix out of a slot's history
@@ -174,9 +192,10 @@ def lib():
         L.fs_comm_destroy.argtypes = [C.c_void_p]
         L.fs_lm_destroy.argtypes = [C.c_void_p]
         L.fs_codec_destroy.argtypes = [C.c_void_p]
-        for name, argtypes in {**SCORE_PROTOTYPES, **TRACE_PROTOTYPES, **ALTS_PROTOTYPES, **CONV_PROTOTYPES, **CODEC_OP_PROTOTYPES, **HISTORY_PROTOTYPES,
+        for name, argtypes in {**SCORE_PROTOTYPES, **TRACE_PROTOTYPES, **ALTS_PROTOTYPES, **CONV_PROTOTYPES, **CODEC_OP_PROTOTYPES, **ATTN_PROTOTYPES, **HISTORY_PROTOTYPES,
                                **RESAMPLE_PROTOTYPES}.items():
-            getattr(L, name).argtypes = argtypes
+            if hasattr(L, name):  # (an older build loaded through LIB_PATH -- tools/attn_paths_dump.py --lib -- may lack the newest entry points)
+                getattr(L, name).argtypes = argtypes
         _lib = L
     return _lib
 

@@ -193,6 +193,50 @@ typedef struct fs_codec_op_case {
 } fs_codec_op_case;
 int fs_selftest_codec_op(int device_id, const fs_codec_op_case* c, void* out, size_t out_cap, size_t* n_out, int* guard_ok);
 
+/* ONE attention launcher call (csrc/lm_kernels.h: AttnKernels::decode / rows, LmKernels::wo) on caller-provided host data, and nothing else.
+ *   FS_ATTN_DECODE     AttnKernels::decode (M == 1, position `pos`) -> out = the partials f32 [H][n_chunks_max][Dh + 2] ({o[Dh], m, l},
+ *                      un-normalised), NaN-poisoned before the launch: slots of chunks the launch did not produce come back NaN
+ *   FS_ATTN_DECODE_WO  decode, then LmKernels::wo with wo [dim][dim] and x [dim] -> out = x [dim] (x += Wo . merged attention); the
+ *                      partials buffer is pre-filled with `stale_part` instead of NaN (the merge must mask every slot decode did not write)
+ *   FS_ATTN_WO_FUSED   LmKernels::wo with fused_T in 1..8: attention of q over rows 0 .. fused_T - 1 of page 0, then Wo -> out = x [dim]
+ *   FS_ATTN_ROWS       AttnKernels::rows with the RowsCtx flags below -> out = hi plane then lo plane, each f32 [Mcap][H * Dh], Mcap = M
+ *                      rounded up to 32: the fragment-major bf16 GEMM input de-fragmented; rows >= M come back NaN (never written)
+ *   FS_ATTN_EXPF       out[i] = __expf(expf_x[i]), i < n_expf, in a kernel of its own (the device function the softmaxes use)
+ * wt: FS_ATTN_WT_F32 / _BF16 / _FP8 selects AttnKernels<WT> / LmKernels<WT>; the KV type is f32 for F32 and bf16 otherwise; with FP8 wo
+ * is stored as e4m3fn bytes of its values with scale 1 per row.  dim == H * Dh.  Row positions: row m sits at pos + m * pos_step
+ * (pos_step 1 / 0), at row_pos[m] (pos_step < 0), or -- seq_rows > 0, group prefill -- row m of sequence s at (seq_pos ? seq_pos[s] : pos) +
+ * m; its length T is that + 1.  k / v: the pools in pool layout f32 [n_pages][Hk][64][Dh], converted to the KV type (RNE; exact for values
+ * already in it); every row of every page is the caller's, stale ones included.  page_table int32 [pt_rows][pt_len] (row stride pt_stride
+ * as the launcher sees it).  q f32 [M][H * Dh].  tbl0 != 0 (k_attn_small_rows_tbl): tbl f32 [tbl_rows][(H + 2 Hk) Dh], codes[m] < tbl_rows
+ * the row's code (stored in cur[code_slot] of its state), cos_t / sin_t f32 [rope_rows][Dh / 2], RoPE row = position + rope_off.
+ * Every device buffer the launch writes (outputs, partials, both pools) lies between 256-element guards of 0xFF bytes; guard_ok = 1 iff all
+ * of them are intact afterwards.  k_out / v_out (nullable): the pools after the launch, f32 in pool layout.  variant_out: the name of the
+ * launch plan (AttnPlan::name: "decode/bf16/64/2/hs4", "decode/part/tpb2", "rows/bf16/64/4/hs2/remap", "rows/chunked/32", "small/64/ident",
+ * "small_tbl/64", "prefill_mfma/group", ...; DECODE_WO appends "+wo/reg" or "+wo/lds", the merge k_wo takes; "wo/fused/64").
+ * The case is VALIDATED BEFORE ANY DEVICE CALL: geometry, capacities, every page id < n_pages, every page-table slot any launched block
+ * reads inside the table, T <= pt_len * 64, small_attn => T <= 8; a bad case is an error and nothing is launched.  plan_only != 0: validate,
+ * return the plan name, touch no device (works without a GPU).  Diagnostics / parity tests. */
+enum { FS_ATTN_DECODE = 0, FS_ATTN_DECODE_WO = 1, FS_ATTN_WO_FUSED = 2, FS_ATTN_ROWS = 3, FS_ATTN_EXPF = 4 };
+enum { FS_ATTN_WT_F32 = 0, FS_ATTN_WT_BF16 = 1, FS_ATTN_WT_FP8 = 2 };
+typedef struct fs_attn_case {
+    int32_t op, wt;
+    int32_t H, Hk, Dh, dim;
+    int32_t M, pos, pos_step, rope_off;
+    int32_t pt_stride, pt_rows, pt_len, seq_rows;
+    int32_t n_chunks_max, nc_launch, part_rows;
+    int32_t no_flash, chunked_attn, small_attn, identity_pages;
+    int32_t n_pages, fused_T;
+    int32_t tbl0, code_slot, tbl_rows, rope_rows;
+    int32_t n_expf, plan_only, reserved;
+    float stale_part;
+    int32_t reserved2;
+    const int32_t *row_pos, *seq_pos, *page_table;
+    const float *k, *v, *q, *wo, *x, *tbl, *cos_t, *sin_t, *expf_x;
+    const uint32_t* codes;
+} fs_attn_case;
+int fs_selftest_attn(int device_id, const fs_attn_case* c, float* out, size_t out_cap, size_t* n_out, float* k_out, float* v_out,
+                     char* variant_out, size_t variant_cap, int* guard_ok);
+
 /* Stage tap of the encoder on a LOADED handle: runs fs_codec_encode's device path on the clip exactly as fs_codec_encode does (same buffers,
  * same launches, the codes are computed and dropped) and copies ONE intermediate tensor to the host:
  *   stage -1     the log-mel [160][F], F = mel frames of the clip

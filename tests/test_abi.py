@@ -35,6 +35,8 @@ def test_struct_layouts_match_header():
     assert ctypes.sizeof(_ffi.GenStats) == 64
     assert ctypes.sizeof(_ffi.ConvCase) == 16 * 4 + 11 * 8  # fs_conv_case: 16 x int32, 11 pointers (static_assert in csrc/fishrt_api.cpp)
     assert ctypes.sizeof(_ffi.CodecOpCase) == 16 * 4 + 8 + 8 * 8  # fs_codec_op_case: 16 x int32, one int64, 8 pointers (static_assert there too)
+    assert ctypes.sizeof(_ffi.AttnCase) == 32 * 4 + 13 * 8  # fs_attn_case: 30 x int32, one float, one int32, 13 pointers (static_assert there too)
+    assert _ffi.AttnCase.stale_part.offset == 120 and _ffi.AttnCase.row_pos.offset == 128 and _ffi.AttnCase.codes.offset == 224
     assert _ffi.CodecOpCase.ctx_elems.offset == 64 and _ffi.CodecOpCase.x.offset == 72 and _ffi.CodecOpCase.codes.offset == 128
 
 

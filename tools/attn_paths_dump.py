@@ -2,8 +2,11 @@
 as .npy files -- for a byte-for-byte comparison of two builds (a refactor of the attention kernels must not move one bit):
     python tools/attn_paths_dump.py --out DIR                      # the in-tree build
     python tools/attn_paths_dump.py --lib /path/libfishrt.so --out DIR2   # another build (a parent commit); then: cmp every file of DIR and DIR2
-One process per library.  Cases and the kernels they are meant to reach: CASES below (not yet run on a GPU: confirm with a
-rocprofv3 --kernel-trace of one run)."""
+One process per library.  Cases and the kernels they are meant to reach: CASES below.  Observed on an MI355X: the 28 files of the build
+that moved the launchers' if / else ladders into AttnKernels::decode_plan / rows_plan and of its parent are cmp-equal, file by file.  Which
+instantiation a call reaches is no longer this file's to claim: every launcher reports the plan it dispatched through, and
+tests/test_attn_paths_gpu.py asserts that name for each of its cases and that the names reached are the whole table (attn_refs.PLAN_TABLE);
+the list below is still the intent only, it has not been confirmed by a kernel trace of this tool."""
 import argparse, os, sys
 import numpy as np
 
