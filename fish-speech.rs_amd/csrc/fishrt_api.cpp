@@ -131,6 +131,14 @@ int fs_selftest_attn(int device_id, const fs_attn_case* c, float* out, size_t ou
     *n_out = 0; *guard_ok = 0; variant_out[0] = 0;
     FS_TRY(fs::attn_selftest(device_id, *c, out, out_cap, n_out, k_out, v_out, variant_out, variant_cap, guard_ok))
 }
+static_assert(sizeof(fs_gemm_case) == 36 * 4 + 18 * 8, "fs_gemm_case is 34 x int32, one float, one int32 and 18 pointers (fishrt/_ffi.py: GemmCase)");
+static_assert(sizeof(fs_gemm_out) == 7 * 8 + 8 * 8 + 4 * 4, "fs_gemm_out is 7 pointers, 8 x size_t and 4 x int32 (fishrt/_ffi.py: GemmOut)");
+int fs_selftest_gemm(int device_id, const fs_gemm_case* c, fs_gemm_out* out) {
+    FS_ARG(c && out && out->variant && out->variant_cap >= 1, "null argument");
+    out->variant[0] = 0; out->guard_ok = 0; out->n_y = out->n_planes = out->n_ss = 0;
+    out->grid[0] = out->grid[1] = out->grid[2] = 0;
+    FS_TRY(fs::gemm_selftest(device_id, *c, *out))
+}
 
 // ---- replica fan-out over RCCL (fs_comm.h)
 int fs_comm_unique_id(uint8_t id_out[FS_COMM_ID_BYTES]) { FS_ARG(id_out, "null argument"); FS_TRY(fs::Comm::unique_id(id_out)) }

@@ -6,9 +6,15 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdlib>
+#include <cmath>
+#include <cstring>
+#include <set>
 #include <string>
 #include <type_traits>
+#include <utility>
+#include <vector>
 
+#include "../../include/fishrt.h"
 #include "fs_common.h"
 #include "lm_kernels.h"
 #include "lm_dev.h"
@@ -455,9 +461,9 @@ static int gemm_big_min_m() {  // FISHRT_GEMM_BIG_MIN_M: tuning / test hook (row
 // measured (tools/ubench_gemm, Fish-1.5 shapes): a block's fixed cost (128 KB weight tile + 4 latency-exposed chunk rounds) is
 // ~8 us, so the variant wins from 128 rows for the wide GEMMs (W13: 128 tiles, W2: 16 tiles x 4 K ranges) and only from
 // ~512 rows for Wqkv / Wo (20 / 16 tiles)
-static bool gemm_big_ok(int M, int N, int K, int ksplit) {
+static bool gemm_big_ok(int M, int N, int K, int ksplit, int big_min_m = 0) {  // big_min_m > 0: this call's own threshold (fs_selftest_gemm)
     if (K % ksplit != 0 || K / ksplit != 1024) return false;
-    const int m0 = gemm_big_min_m();
+    const int m0 = big_min_m > 0 ? big_min_m : gemm_big_min_m();
     return M >= 4 * m0 || (M >= m0 && (N + GB_ROWS - 1) / GB_ROWS * ksplit >= 64);
 }
 template <int EPI, bool FP8>
@@ -605,7 +611,7 @@ void RowKernels<WT>::prefill_embed(const ModelDims& d, const void* tok_emb, cons
 
 // Host-side arguments of one row-path GEMM: Y[M, N] (+)= f(X[M, K]) . W[N, K]^T over `ksplit` K ranges (slabs Y + s * slab_stride for
 // EPI_STORE).  A call site states the parts its epilogue uses; launch_gemm3 unpacks them into the kernels' parameter list.
-struct GemmIn { const bf16_t* Xf; int M, K; const void* W; const float* wscale; int N; int ksplit = 1; };
+struct GemmIn { const bf16_t* Xf; int M, K; const void* W; const float* wscale; int N; int ksplit = 1; int big_min_m = 0; };  // big_min_m: gemm_plan's
 struct GemmOut { float* Y = nullptr; int ldy = 0; size_t slab_stride = 0; bf16_t* Of = nullptr; int ldo = 0; };
 struct GemmQkv {   // EPI_QKV*: RoPE tables, position source, KV cache and head geometry, row -> sequence mapping
     const float *cos_t = nullptr, *sin_t = nullptr; const SeqState* state = nullptr;
@@ -617,24 +623,19 @@ struct GemmArgs { GemmIn in; GemmOut out; GemmQkv qkv = {}; NormAux na = {}; };
 template <int EPI, int RT = 1>
 static void launch_gemm3(hipStream_t st, const GemmArgs& g) {
     const GemmIn& in = g.in; const GemmOut& out = g.out; const GemmQkv& q = g.qkv;
-    const int M = in.M, N = in.N, K = in.K, ksplit = in.ksplit;
-    FS_REQUIRE(K % (ksplit * 128) == 0, "GEMM depth must be a multiple of 128 per K range");
-    const int panels = (M + PF_M - 1) / PF_M;
-    if (gemm_big_ok(M, N, K, ksplit)) {
-        const int tiles = (N + GB_ROWS - 1) / GB_ROWS;
-        const dim3 grid(tiles, ksplit, std::max(1, std::min(panels, 512 / std::max(1, tiles * ksplit))));
-        with_bool(in.wscale != nullptr, [&](auto fp8) {
+    const int M = in.M, N = in.N, K = in.K;
+    const GemmPlan p = gemm_plan(EPI, RT, M, N, K, in.ksplit, in.wscale != nullptr, in.big_min_m);
+    const dim3 grid(p.gx, p.gy, p.gz);
+    if (p.kind == GemmPlan::BIG) {
+        with_bool(p.fp8, [&](auto fp8) {
             hipLaunchKernelGGL((k_gemm_big<EPI, decltype(fp8)::value>), grid, dim3(256), 0, st, in.Xf, M, K, in.W, in.wscale, N, out.Y, out.ldy,
                                out.slab_stride, out.Of, out.ldo, q.cos_t, q.sin_t, q.state, q.kv, q.H, q.Hk, q.Dh, q.rm, g.na);
         });
         return;
     }
-    // enough blocks to fill 256 CUs a few times over: spread the row panels over blockIdx.z until ~1024 blocks
-    const int tiles = (N + 16 * RT - 1) / (16 * RT);
-    const dim3 grid(tiles, ksplit, std::max(1, std::min(panels, 1024 / std::max(1, tiles * ksplit))));
-    with_nks(K / ksplit / 128, [&](auto nks) {
-        with_bool(in.wscale != nullptr, [&](auto fp8) {
-            with_bool(M <= 16, [&](auto half) {
+    with_nks(p.nks, [&](auto nks) {
+        with_bool(p.fp8, [&](auto fp8) {
+            with_bool(p.half, [&](auto half) {
                 hipLaunchKernelGGL((k_gemm3<EPI, decltype(nks)::value, RT, decltype(fp8)::value, decltype(half)::value>), grid, dim3(256), 0, st,
                                    in.Xf, M, K, in.W, in.wscale, N, out.Y, out.ldy, out.slab_stride, out.Of, out.ldo, q.cos_t, q.sin_t, q.state,
                                    q.kv, q.H, q.Hk, q.Dh, q.rm, g.na);
@@ -655,14 +656,58 @@ static DownShape down_shape(int K) {  // {0, 0}: not a depth k_gemm_down takes
 }
 static bool gemm_down_ok(int M, int N, int K) { return M <= PF_M && N % 128 == 0 && down_shape(K).nks != 0; }
 size_t rows_xchg_bytes(int dim) { return (size_t)(dim / 16) * 4 * PF_M * 8 * 16; }
+
+// ---- the one place that decides which instantiation and grid a row-path GEMM runs (GemmPlan: lm_kernels.h)
+static const char* const kEpiNames[] = {"STORE", "RESIDUAL", "SWIGLU", "QKV", "RESIDUAL_NORM", "SWIGLU_RMS", "QKV_RMS", "STORE_RMS", "QKV_SEQ"};
+std::string GemmPlan::name() const {
+    const std::string wt = fp8 ? "fp8" : "bf16";
+    switch (kind) {
+    case BIG: return std::string("big/") + kEpiNames[epi] + "/" + wt;
+    case DOWN: return "down/nks" + std::to_string(nks) + "/ks" + std::to_string(ksplit) + "/" + wt;
+    default: return std::string("gemm3/") + kEpiNames[epi] + "/nks" + std::to_string(nks) + "/rt" + std::to_string(rt) + "/" + wt + (half ? "/half" : "");
+    }
+}
+GemmPlan gemm_plan(int epi, int rt, int M, int N, int K, int ksplit, bool fp8, int big_min_m) {
+    GemmPlan p;
+    p.epi = epi; p.fp8 = fp8;
+    FS_REQUIRE(M >= 1 && N >= 1 && K >= 1, "GEMM needs M, N, K >= 1");
+    if (epi == GEMM_EPI_DOWN) {
+        FS_REQUIRE(gemm_down_ok(M, N, K), "down projection on a shape k_gemm_down does not take (M <= 32, N % 128 == 0, K in {4096, 1024, 256})");
+        const DownShape s = down_shape(K);
+        p.kind = GemmPlan::DOWN; p.nks = s.nks; p.ksplit = s.ksplit; p.gx = N / 16; p.gy = s.ksplit;
+        return p;
+    }
+    FS_REQUIRE(epi >= EPI_STORE && epi <= EPI_QKV_SEQ && (rt == 1 || rt == 2), "unknown GEMM epilogue or tile count");
+    FS_REQUIRE(ksplit >= 1 && K % (ksplit * 128) == 0, "GEMM depth must be a multiple of 128 per K range");
+    p.ksplit = ksplit; p.gy = ksplit;
+    const int panels = (M + PF_M - 1) / PF_M;
+    if (gemm_big_ok(M, N, K, ksplit, big_min_m)) {
+        const int tiles = (N + GB_ROWS - 1) / GB_ROWS;
+        p.kind = GemmPlan::BIG; p.nks = 16; p.rt = GB_ROWS / 16;
+        p.gx = tiles; p.gz = std::max(1, std::min(panels, 512 / std::max(1, tiles * ksplit)));
+        return p;
+    }
+    // enough blocks to fill 256 CUs a few times over: spread the row panels over blockIdx.z until ~1024 blocks
+    const int tiles = (N + 16 * rt - 1) / (16 * rt);
+    p.kind = GemmPlan::GEMM3; p.rt = rt; p.half = M <= 16;
+    p.nks = K / ksplit / 128;  // k-steps of 32 per wave: depth per K range / 128
+    if (p.nks != 8 && p.nks != 2 && p.nks != 1)
+        throw Error("unsupported GEMM depth per K range " + std::to_string(p.nks * 128) + " (supported: 1024, 256, 128)");
+    p.gx = tiles; p.gz = std::max(1, std::min(panels, 1024 / std::max(1, tiles * ksplit)));
+    return p;
+}
+// what rows_layer / rows_fold_ok need to know about a launch before they make it (the Wo GEMM's block count, the o1 and fold decisions):
+// asked of the plan itself, with the arguments of that launch (one K range, RT 1)
+static bool plan_is_big(int epi, int M, int N, int K) { return gemm_plan(epi, 1, M, N, K, 1, false).kind == GemmPlan::BIG; }
+
 static void launch_gemm_down(hipStream_t st, const bf16_t* Xf, int M, int K, const void* W, const float* wscale, int N, float* Y, int ldy, NormAux na,
                              void* xchg, uint32_t* epoch, uint32_t node_id) {
     FS_REQUIRE(xchg && epoch, "folded decode step without an exchange buffer");
-    const DownShape s = down_shape(K);
+    const GemmPlan p = gemm_plan(GEMM_EPI_DOWN, 1, M, N, K, 0, wscale != nullptr);
     static const int nap = [] { const char* e = std::getenv("FISHRT_DOWN_NAP"); return e ? std::atoi(e) : 8; }();  // 64-clock units before the first sweep (0 / 8 / 16 / 24 / 40: 1820 / 1813 / 1820 / 1853 / 1890 us per B = 32 step)
-    with_nks(s.nks, [&](auto nks) {
-        with_bool(wscale != nullptr, [&](auto fp8) {
-            hipLaunchKernelGGL((k_gemm_down<decltype(nks)::value, decltype(fp8)::value>), dim3(N / 16, s.ksplit), dim3(256), 0, st, Xf, M, K, W, wscale,
+    with_nks(p.nks, [&](auto nks) {
+        with_bool(p.fp8, [&](auto fp8) {
+            hipLaunchKernelGGL((k_gemm_down<decltype(nks)::value, decltype(fp8)::value>), dim3(p.gx, p.gy), dim3(256), 0, st, Xf, M, K, W, wscale,
                                N, Y, ldy, na, (u32x4*)xchg, epoch, node_id, nap);
         });
     });
@@ -705,7 +750,7 @@ bool RowKernels<WT>::rows_fold_ok(const ModelDims& d, int M, const RowsCtx& c) {
     if constexpr (std::is_same<WT, float>::value) return false;
     else
         return rows_fold_enabled() && c.A2 != nullptr && c.ss != nullptr && c.xchg != nullptr && c.epoch != nullptr && gemm_down_ok(M, d.dim, d.inter) &&
-               !gemm_big_ok(M, d.dim, d.dim, 1) && c.stage_mask == 0xFFu && gemm_down_resident(d.dim, d.inter, std::is_same<WT, fp8_t>::value);
+               !plan_is_big(EPI_RESIDUAL_NORM, M, d.dim, d.dim) && c.stage_mask == 0xFFu && gemm_down_resident(d.dim, d.inter, std::is_same<WT, fp8_t>::value);
 }
 
 template <typename WT>
@@ -719,7 +764,7 @@ void RowKernels<WT>::rows_layer(const ModelDims& d, int M, const RowsCtx& c, con
         // 16-row tiles per wave (launch_gemm3's RT): 1 everywhere, 2 for the wide W13 (halves the L2 re-reads of the activation fragments).
         // 64-row blocks (RT = 4) were measured for prefill-sized passes and are SLOWER (W13 at 384 rows: 33 -> 41 us): the lost
         // occupancy costs more than the saved fragment traffic.
-        const int nblk_o = gemm_big_ok(M, d.dim, d.dim, 1) ? d.dim / GB_ROWS : d.dim / 16;  // blocks of the Wo GEMM (sum-of-squares partials)
+        const int nblk_o = plan_is_big(EPI_RESIDUAL_NORM, M, d.dim, d.dim) ? d.dim / GB_ROWS : d.dim / 16;  // blocks of the Wo GEMM (sum-of-squares partials)
         const size_t slab = (size_t)c.Mcap * d.dim;
         const int DOWN_SPLIT = c.down_split;
         // decode steps (c.fold): the previous layer's un-split down projection (k_gemm_down) closed the residual stream and left
@@ -737,7 +782,7 @@ void RowKernels<WT>::rows_layer(const ModelDims& d, int M, const RowsCtx& c, con
         // (2) Wqkv + rope + KV scatter
         // c.attn_t1 (fold, small_attn; every row at position 0 of an empty cache): the Wqkv epilogue leaves the attention output itself
         // (GemmEpi::o1) in c.C -- free until this layer's W13 -- and the attention node is not launched
-        const bool t1 = fold && c.attn_t1 && c.small_attn && !gemm_big_ok(M, qkv_rows, d.dim, 1);
+        const bool t1 = fold && c.attn_t1 && c.small_attn && !plan_is_big(EPI_QKV_RMS, M, qkv_rows, d.dim);
         const GemmIn in_qkv{c.A, M, d.dim, w.wqkv, w.s_qkv, qkv_rows};
         const GemmOut out_qkv{c.Q, d.dim, 0, t1 ? c.C : nullptr, 0};
         const GemmQkv rope{c.cos_t, c.sin_t, c.state, kv, d.H, d.Hk, d.Dh, RowMap{c.pos_step, c.pt_stride, c.seq_rows}};
@@ -803,5 +848,347 @@ void RowKernels<WT>::rows_head(const ModelDims& d, int M, const RowsCtx& c, cons
 template struct RowKernels<bf16_t>;
 template struct RowKernels<float>;
 template struct RowKernels<fp8_t>;
+
+// ================================================================================================ fs_selftest_gemm (include/fishrt.h)
+// ONE launcher call of this file on caller data and nothing else.  Everything a launch writes lies between 256-element guards of 0xFF bytes
+// and is poisoned with 0xFF bytes (f32 / bf16 NaN) where the caller provides nothing; the fragment rows [M, Mcap) of a GEMM input are bf16
+// NaN, so a live output that depends on a row that does not exist comes back NaN; the whole case is validated before the first device call.
+namespace {
+constexpr size_t kGemmGuard = 256;
+struct GemmDev {  // device buffer of n elements of es bytes between two guards, all 0xFF bytes at first
+    void* p = nullptr;
+    size_t n = 0, es = 4;
+    void alloc(size_t n_, size_t es_, hipStream_t st) {
+        n = n_; es = es_;
+        FS_HIP(hipMalloc(&p, (n + 2 * kGemmGuard) * es));
+        FS_HIP(hipMemsetAsync(p, 0xFF, (n + 2 * kGemmGuard) * es, st));
+    }
+    char* data() const { return (char*)p + kGemmGuard * es; }
+    void up(const void* src, size_t count, hipStream_t st) { FS_HIP(hipMemcpyAsync(data(), src, count * es, hipMemcpyHostToDevice, st)); }
+    void down(void* dst, hipStream_t st) const { FS_HIP(hipMemcpyAsync(dst, data(), n * es, hipMemcpyDeviceToHost, st)); }
+    void poison(hipStream_t st) { FS_HIP(hipMemsetAsync(data(), 0xFF, n * es, st)); }
+    bool intact(hipStream_t st) const {
+        if (!p) return true;
+        std::vector<uint8_t> g(2 * kGemmGuard * es);
+        FS_HIP(hipMemcpyAsync(g.data(), p, kGemmGuard * es, hipMemcpyDeviceToHost, st));
+        FS_HIP(hipMemcpyAsync(g.data() + kGemmGuard * es, data() + n * es, kGemmGuard * es, hipMemcpyDeviceToHost, st));
+        FS_HIP(hipStreamSynchronize(st));
+        for (uint8_t b : g) if (b != 0xFF) return false;
+        return true;
+    }
+    ~GemmDev() { if (p) (void)hipFree(p); }
+};
+
+struct GemmRowPos { int pos, rpos, sq; };
+// everything validation derives from a case: the launch plan, its name, the output extents
+struct GemmCaseInfo {
+    GemmPlan plan;
+    std::string name;
+    int Mcap = 0, nblk = 0, C = 0, ldo = 0, n_seq = 0, n_state = 1;
+    bool qkv = false, rms = false, store = false, residual = false, swiglu = false;
+    size_t n_y = 0, n_planes = 0, n_ss = 0, n_pool = 0;
+    std::vector<GemmRowPos> rows;
+};
+void gemm_req(bool ok, const char* msg) { if (!ok) throw Error(std::string("GEMM self-test: ") + msg); }
+
+// position, RoPE row and sequence of activation row m, as gemm_epilogue's QKV branch derives them
+GemmRowPos gemm_row_pos(const fs_gemm_case& c, int m) {
+    const int sq = c.seq_rows > 0 ? m / c.seq_rows : m, j = c.seq_rows > 0 ? m - sq * c.seq_rows : 0;
+    long long pos = (long long)c.pos + (c.seq_rows > 0 ? j : (long long)m * c.pos_step), rpos = pos + c.rope_off;
+    if (c.pos_step < 0) { pos = c.row_pos[m]; rpos = pos + (c.row_rope_off ? c.row_rope_off[m] : c.rope_off); }
+    if (c.epi == EPI_QKV_SEQ) { pos = (long long)c.seq_pos[sq] + j; rpos = pos + (c.seq_rope_off ? c.seq_rope_off[sq] : c.rope_off); }
+    gemm_req(pos >= 0 && pos < (1 << 20) && rpos >= 0 && rpos < c.rope_rows, "a row's position or RoPE row is outside [0, 2^20) / the cos / sin tables");
+    return {(int)pos, (int)rpos, sq};
+}
+
+void gemm_validate(const fs_gemm_case& c, GemmCaseInfo& I) {
+    const auto req = gemm_req;
+    req(c.op >= FS_GEMM_PREP && c.op <= FS_GEMM_DOWN, "unknown op");
+    req(c.M >= 1 && c.M <= 1024, "1 <= M <= 1024");
+    req(std::isfinite(c.eps) && c.eps >= 0.f, "eps must be finite and >= 0");
+    I.Mcap = (c.M + PF_M - 1) / PF_M * PF_M;
+    if (c.op == FS_GEMM_PREP) {
+        req(c.D >= 32 && c.D <= 8192 && c.D % 32 == 0, "prep: 32 <= D <= 8192, D a multiple of 32 (fragment layout)");
+        req(c.S >= 0 && c.S <= 8 && c.x && (c.S == 0 || c.p), "prep: 0 <= S <= 8, x is required, p with S > 0");
+        I.name = c.D <= 1024 ? "prep/one" : "prep/reread";
+        I.plan.gx = (unsigned)c.M;
+        I.n_y = (size_t)c.M * c.D;
+        I.n_planes = c.want_frag ? (size_t)2 * I.Mcap * c.D : 0;
+        return;
+    }
+    req(c.N >= 1 && c.N <= 16384 && c.K >= 128 && c.K <= 8192 && c.K % 128 == 0, "1 <= N <= 16384, 128 <= K <= 8192, K a multiple of 128");
+    req(c.x && c.w && (!c.fp8 || c.wscale), "x and w are required, wscale with fp8");
+    if (c.op == FS_GEMM_DOWN) {
+        I.plan = gemm_plan(GEMM_EPI_DOWN, 1, c.M, c.N, c.K, 0, c.fp8 != 0);
+        req(c.y && c.g, "down: y and g are required");
+        req((c.n_launches == 1 || c.n_launches == 2) && (c.n_launches == 1 || c.x2), "down: n_launches is 1 or 2, x2 with 2");
+        req(c.epoch >= 1 && c.epoch < (1 << 19) && c.node_id >= 0 && c.node_id + c.n_launches <= 4096, "down: 1 <= epoch < 2^19, node ids < 4096");
+        for (int l = 0; l < c.n_launches; ++l)
+            req((uint32_t)c.stale_tag != (uint32_t)c.epoch * 4096u + (uint32_t)(c.node_id + l), "down: stale_tag equals a launch's own tag");
+        I.nblk = c.N / 16; I.C = c.N;
+        I.n_y = (size_t)c.n_launches * PF_M * c.N;
+        I.n_planes = (size_t)c.n_launches * 2 * PF_M * c.N;
+        I.n_ss = (size_t)c.n_launches * PF_M * I.nblk;
+    } else {
+        static const int pair_rt[9] = {1, 1, 2, 1, 1, 2, 1, 1, 1};  // the (EPI, RT) pairs rows_layer / rows_head launch
+        req(c.epi >= EPI_STORE && c.epi <= EPI_QKV_SEQ && c.rt == pair_rt[c.epi], "rows: (epi, rt) is not a pair rows_layer / rows_head launch");
+        req(c.ksplit >= 1 && c.ksplit <= 4, "rows: 1 <= ksplit <= 4");
+        I.plan = gemm_plan(c.epi, c.rt, c.M, c.N, c.K, c.ksplit, c.fp8 != 0, c.big_min_m);
+        I.store = c.epi == EPI_STORE || c.epi == EPI_STORE_RMS;
+        I.residual = c.epi == EPI_RESIDUAL || c.epi == EPI_RESIDUAL_NORM;
+        I.swiglu = c.epi == EPI_SWIGLU || c.epi == EPI_SWIGLU_RMS;
+        I.qkv = c.epi == EPI_QKV || c.epi == EPI_QKV_RMS || c.epi == EPI_QKV_SEQ;
+        I.rms = epi_rms(c.epi);
+        req(I.store || c.ksplit == 1, "rows: only the STORE epilogues take split-K slabs");
+        if (I.rms) {
+            req(c.ss && c.nblk >= 8 && c.nblk <= 1024 && c.nblk % 8 == 0, "rows: *_RMS needs ss [M][nblk], nblk a multiple of 8 in [8, 1024]");
+            I.nblk = c.nblk;
+        }
+        if (I.store) {
+            req(c.ldy >= c.N, "rows: ldy must cover N");
+            I.n_y = (size_t)c.ksplit * I.Mcap * c.ldy;
+        } else if (I.residual) {
+            req(c.y && c.N % 2 == 0 && c.ldy >= c.N && c.ldy % 2 == 0, "rows: RESIDUAL* needs y, even N, even ldy >= N");
+            I.n_y = (size_t)I.Mcap * c.ldy;
+            if (c.epi == EPI_RESIDUAL_NORM) {
+                const int rows = I.plan.kind == GemmPlan::BIG ? GB_ROWS : 16;
+                I.nblk = (int)I.plan.gx;
+                req(c.g && c.N % rows == 0 && c.N % 32 == 0 && I.nblk % 8 == 0, "rows: RESIDUAL_NORM needs g, whole blocks and a block count that is a multiple of 8");
+                I.C = c.N; I.n_planes = (size_t)2 * I.Mcap * c.N; I.n_ss = (size_t)I.Mcap * I.nblk;
+            }
+        } else if (I.swiglu) {
+            I.ldo = c.ldo ? c.ldo : c.N / 2;
+            req(c.N % 64 == 0 && I.ldo >= c.N / 2 && I.ldo % 32 == 0, "rows: SWIGLU* needs N a multiple of 64 and ldo >= N / 2, a multiple of 32");
+            I.C = I.ldo; I.n_planes = (size_t)2 * I.Mcap * I.ldo;
+        } else {
+            req((c.Dh == 64 || c.Dh == 32) && c.Hk >= 1 && c.H >= c.Hk && c.H <= 32 && c.H % c.Hk == 0, "rows: QKV* needs Dh in {32, 64}, 1 <= Hk <= H <= 32, H a multiple of Hk");
+            const int qdim = c.H * c.Dh;
+            req(c.N == (c.H + 2 * c.Hk) * c.Dh && c.ldy >= qdim && c.ldy % 2 == 0, "rows: QKV* needs N == (H + 2 Hk) Dh and an even ldy >= H Dh");
+            req(c.cos_t && c.sin_t && c.rope_rows >= 1 && c.rope_rows <= (1 << 16), "rows: QKV* needs cos_t, sin_t, 1 <= rope_rows <= 2^16");
+            req(c.k && c.v && c.n_pages >= 1 && c.n_pages <= 4096, "rows: QKV* needs k, v, 1 <= n_pages <= 4096");
+            req(c.page_table && c.pt_rows >= 1 && c.pt_len >= 1 && (long long)c.pt_rows * c.pt_len <= (1 << 20) && c.pt_stride >= 0, "rows: page_table [pt_rows][pt_len] is required");
+            const long long n_tab = (long long)c.pt_rows * c.pt_len;
+            for (long long i = 0; i < n_tab; ++i) req(c.page_table[i] >= 0 && c.page_table[i] < c.n_pages, "a page id is outside the pool");
+            req(c.pos_step == 1 || c.pos_step == 0 || c.pos_step == -1, "pos_step is 1, 0 or -1");
+            req(c.pos_step >= 0 || c.row_pos, "pos_step < 0 needs row_pos");
+            req(c.seq_rows >= 0 && (c.seq_rows == 0 || (c.pos_step == 1 && c.M % c.seq_rows == 0)), "group rows: pos_step 1, M a multiple of seq_rows");
+            req(c.epi != EPI_QKV_SEQ || (c.seq_rows > 0 && c.seq_pos), "QKV_SEQ needs seq_rows > 0 and seq_pos");
+            I.n_seq = c.seq_rows > 0 ? c.M / c.seq_rows : 0;
+            I.n_state = std::max(std::max(c.M, I.n_seq), 1);
+            std::set<std::pair<int, int>> cells;
+            for (int m = 0; m < c.M; ++m) {
+                const GemmRowPos rp = gemm_row_pos(c, m);
+                const long long slot = (long long)rp.sq * c.pt_stride + rp.pos / KV_PAGE;
+                req(rp.pos / KV_PAGE < c.pt_len && slot < n_tab, "a row's page-table slot is outside the table");
+                req(cells.insert({c.page_table[slot], rp.pos % KV_PAGE}).second, "two rows write the same cache row");
+                I.rows.push_back(rp);
+            }
+            if (c.o1) {
+                req(I.plan.kind == GemmPlan::GEMM3 && qdim % 32 == 0, "rows: o1 needs the k_gemm3 path and H Dh a multiple of 32");
+                I.C = qdim; I.n_planes = (size_t)2 * I.Mcap * qdim;
+            }
+            I.n_y = (size_t)I.Mcap * c.ldy;
+            I.n_pool = (size_t)c.n_pages * c.Hk * KV_PAGE * c.Dh;
+        }
+    }
+    I.name = I.plan.name();
+    // the weights: exactly representable in the weight type, so that the caller's f32 matrix IS what the kernel multiplies
+    const size_t nw = (size_t)c.N * c.K;
+    for (size_t i = 0; i < nw; ++i) {
+        const float w = c.w[i];
+        const bool exact = c.fp8 ? e4m3_to_f32(f32_to_e4m3(w)) == w : bf16_to_f32_host(f32_to_bf16_host(w)) == w;
+        req(exact, c.fp8 ? "a weight is not an e4m3fn value" : "a weight is not a bf16 value");
+    }
+}
+
+struct GemmStream {
+    hipStream_t st = nullptr;
+    explicit GemmStream(int device) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw Error("no HIP device visible: libfishrt has no CPU fallback (MI355X / gfx950 required)");
+        FS_REQUIRE(device >= 0 && device < ndev, "device_id out of range");
+        FS_HIP(hipSetDevice(device));
+        FS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    }
+    ~GemmStream() { if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); } }
+};
+
+// fragment-major bf16 [Mcap][C] (hi and lo parts) -> two f32 planes [Mcap][C]
+void gemm_defrag(const std::vector<uint16_t>& A, int Mcap, int C, float* out) {
+    const size_t plane = (size_t)Mcap * C;
+    for (int m = 0; m < Mcap; ++m)
+        for (int k = 0; k < C; ++k) {
+            out[(size_t)m * C + k] = bf16_to_f32_host(A[frag_off(m, k, 0, C)]);
+            out[plane + (size_t)m * C + k] = bf16_to_f32_host(A[frag_off(m, k, 1, C)]);
+        }
+}
+// the GEMM input of x [M][K]: a plain split by k_prep (no norm), rows [M, Mcap) left as bf16 NaN
+void gemm_make_frags(const float* x, int M, int Mcap, int K, GemmDev& dX, GemmDev& dXf, hipStream_t st) {
+    dX.alloc((size_t)M * K, 4, st); dX.up(x, (size_t)M * K, st);
+    dXf.alloc((size_t)2 * Mcap * K, 2, st);
+    hipLaunchKernelGGL(k_prep, dim3(M), dim3(256), 0, st, (float*)dX.data(), K, (const float*)nullptr, 0, (size_t)0, (const float*)nullptr, 0.f, (bf16_t*)dXf.data());
+    FS_LAUNCH_CHECK();
+}
+void gemm_upload_w(const fs_gemm_case& c, GemmDev& dW, GemmDev& dS, hipStream_t st) {
+    const size_t nw = (size_t)c.N * c.K;
+    if (c.fp8) {
+        std::vector<uint8_t> h(nw);
+        for (size_t i = 0; i < nw; ++i) h[i] = f32_to_e4m3(c.w[i]);
+        dW.alloc(nw, 1, st); dW.up(h.data(), nw, st);
+        dS.alloc((size_t)c.N, 4, st); dS.up(c.wscale, (size_t)c.N, st);
+        FS_HIP(hipStreamSynchronize(st));
+    } else {
+        std::vector<uint16_t> h(nw);
+        for (size_t i = 0; i < nw; ++i) h[i] = f32_to_bf16_host(c.w[i]);
+        dW.alloc(nw, 2, st); dW.up(h.data(), nw, st);
+        FS_HIP(hipStreamSynchronize(st));
+    }
+}
+
+void gemm_run_prep(const fs_gemm_case& c, const GemmCaseInfo& I, fs_gemm_out& o, hipStream_t st) {
+    GemmDev dX, dP, dW, dA;
+    dX.alloc((size_t)c.M * c.D, 4, st); dX.up(c.x, (size_t)c.M * c.D, st);
+    if (c.S > 0) { dP.alloc((size_t)c.S * c.M * c.D, 4, st); dP.up(c.p, (size_t)c.S * c.M * c.D, st); }
+    if (c.norm_w) { dW.alloc((size_t)c.D, 4, st); dW.up(c.norm_w, (size_t)c.D, st); }
+    if (c.want_frag) dA.alloc((size_t)2 * I.Mcap * c.D, 2, st);
+    hipLaunchKernelGGL(k_prep, dim3(c.M), dim3(256), 0, st, (float*)dX.data(), c.D, c.S > 0 ? (const float*)dP.data() : nullptr, c.S, (size_t)c.M * c.D,
+                       c.norm_w ? (const float*)dW.data() : nullptr, c.eps, c.want_frag ? (bf16_t*)dA.data() : nullptr);
+    FS_LAUNCH_CHECK();
+    std::vector<uint16_t> hA(dA.n);
+    if (o.y) dX.down(o.y, st);
+    if (c.want_frag) dA.down(hA.data(), st);
+    FS_HIP(hipStreamSynchronize(st));
+    if (c.want_frag && o.planes) gemm_defrag(hA, I.Mcap, c.D, o.planes);
+    o.guard_ok = (dX.intact(st) && dA.intact(st)) ? 1 : 0;
+}
+
+template <int EPI, int RT>
+void gemm_launch_pair(hipStream_t st, const GemmArgs& g) { launch_gemm3<EPI, RT>(st, g); }
+
+void gemm_run_rows(const fs_gemm_case& c, const GemmCaseInfo& I, fs_gemm_out& o, hipStream_t st) {
+    GemmDev dX, dXf, dW, dS, dY, dOf, dSS, dG, dCos, dSin, dK, dV, dTab, dState;
+    gemm_make_frags(c.x, c.M, I.Mcap, c.K, dX, dXf, st);
+    gemm_upload_w(c, dW, dS, st);
+    GemmArgs g;
+    g.in = GemmIn{(const bf16_t*)dXf.data(), c.M, c.K, dW.data(), c.fp8 ? (const float*)dS.data() : nullptr, c.N, c.ksplit, c.big_min_m};
+    if (I.n_y) {
+        dY.alloc(I.n_y, 4, st);
+        if (I.residual)
+            FS_HIP(hipMemcpyAsync(dY.data(), c.y, (size_t)c.M * c.ldy * 4, hipMemcpyHostToDevice, st));
+    }
+    if (I.n_planes) dOf.alloc(I.n_planes, 2, st);
+    g.out = GemmOut{I.n_y ? (float*)dY.data() : nullptr, c.ldy, (size_t)I.Mcap * c.ldy, nullptr, 0};
+    if (I.swiglu) { g.out.Of = (bf16_t*)dOf.data(); g.out.ldo = I.ldo; }
+    if (I.qkv && c.o1) g.out.Of = (bf16_t*)dOf.data();
+    if (I.rms) {
+        dSS.alloc((size_t)I.Mcap * I.nblk, 4, st); dSS.up(c.ss, (size_t)c.M * I.nblk, st);
+        g.na = NormAux{nullptr, (float*)dSS.data(), nullptr, I.nblk, c.K, c.eps};
+    }
+    if (c.epi == EPI_RESIDUAL_NORM) {
+        dSS.alloc(I.n_ss, 4, st);
+        dG.alloc((size_t)c.N, 4, st); dG.up(c.g, (size_t)c.N, st);
+        g.na = NormAux{(const float*)dG.data(), (float*)dSS.data(), (bf16_t*)dOf.data(), I.nblk, c.N, c.eps};
+    }
+    std::vector<SeqState> hs((size_t)I.n_state);
+    std::vector<uint16_t> hk, hv;
+    if (I.qkv) {
+        for (auto& s : hs) { std::memset(&s, 0, sizeof(SeqState)); s.pos = c.pos; s.rope_off = c.rope_off; }
+        if (c.pos_step < 0)
+            for (int m = 0; m < c.M; ++m) { hs[(size_t)m].pos = c.row_pos[m]; if (c.row_rope_off) hs[(size_t)m].rope_off = c.row_rope_off[m]; }
+        if (c.epi == EPI_QKV_SEQ)
+            for (int s = 0; s < I.n_seq; ++s) { hs[(size_t)s].pos = c.seq_pos[s]; if (c.seq_rope_off) hs[(size_t)s].rope_off = c.seq_rope_off[s]; }
+        dState.alloc(hs.size() * sizeof(SeqState), 1, st); dState.up(hs.data(), hs.size() * sizeof(SeqState), st);
+        const size_t nr = (size_t)c.rope_rows * (c.Dh / 2);
+        dCos.alloc(nr, 4, st); dCos.up(c.cos_t, nr, st);
+        dSin.alloc(nr, 4, st); dSin.up(c.sin_t, nr, st);
+        hk.resize(I.n_pool); hv.resize(I.n_pool);
+        for (size_t i = 0; i < I.n_pool; ++i) { hk[i] = f32_to_bf16_host(c.k[i]); hv[i] = f32_to_bf16_host(c.v[i]); }
+        dK.alloc(I.n_pool, 2, st); dK.up(hk.data(), I.n_pool, st);
+        dV.alloc(I.n_pool, 2, st); dV.up(hv.data(), I.n_pool, st);
+        const size_t nt = (size_t)c.pt_rows * c.pt_len;
+        dTab.alloc(nt, 4, st); dTab.up(c.page_table, nt, st);
+        g.qkv = GemmQkv{(const float*)dCos.data(), (const float*)dSin.data(), (const SeqState*)dState.data(),
+                        KVView{dK.data(), dV.data(), (const int*)dTab.data()}, c.H, c.Hk, c.Dh, RowMap{c.pos_step, c.pt_stride, c.seq_rows}};
+    }
+    switch (c.epi) {
+    case EPI_STORE: gemm_launch_pair<EPI_STORE, 1>(st, g); break;
+    case EPI_RESIDUAL: gemm_launch_pair<EPI_RESIDUAL, 1>(st, g); break;
+    case EPI_SWIGLU: gemm_launch_pair<EPI_SWIGLU, 2>(st, g); break;
+    case EPI_QKV: gemm_launch_pair<EPI_QKV, 1>(st, g); break;
+    case EPI_RESIDUAL_NORM: gemm_launch_pair<EPI_RESIDUAL_NORM, 1>(st, g); break;
+    case EPI_SWIGLU_RMS: gemm_launch_pair<EPI_SWIGLU_RMS, 2>(st, g); break;
+    case EPI_QKV_RMS: gemm_launch_pair<EPI_QKV_RMS, 1>(st, g); break;
+    case EPI_STORE_RMS: gemm_launch_pair<EPI_STORE_RMS, 1>(st, g); break;
+    default: gemm_launch_pair<EPI_QKV_SEQ, 1>(st, g); break;
+    }
+    FS_LAUNCH_CHECK();
+    std::vector<uint16_t> hA(dOf.n);
+    if (o.y && I.n_y) dY.down(o.y, st);
+    if (I.n_planes) dOf.down(hA.data(), st);
+    if (o.ss && I.n_ss) dSS.down(o.ss, st);
+    if (I.qkv) { dK.down(hk.data(), st); dV.down(hv.data(), st); }
+    FS_HIP(hipStreamSynchronize(st));
+    if (I.n_planes && o.planes) gemm_defrag(hA, I.Mcap, I.C, o.planes);
+    if (I.qkv)
+        for (size_t i = 0; i < I.n_pool; ++i) { if (o.k) o.k[i] = bf16_to_f32_host(hk[i]); if (o.v) o.v[i] = bf16_to_f32_host(hv[i]); }
+    bool ok = true;
+    for (const GemmDev* b : {&dXf, &dY, &dOf, &dSS, &dK, &dV}) ok = b->intact(st) && ok;
+    o.guard_ok = ok ? 1 : 0;
+}
+
+void gemm_run_down(const fs_gemm_case& c, const GemmCaseInfo& I, fs_gemm_out& o, hipStream_t st) {
+    // the owner waves wait for blocks of the same launch: never launched where the engine would not launch it
+    gemm_req(gemm_down_resident(c.N, c.K, c.fp8 != 0), "down: this device does not hold the whole grid at once (gemm_down_resident)");
+    GemmDev dX[2], dXf[2], dW, dS, dY, dA, dSS, dG, dXchg, dEpoch;
+    gemm_make_frags(c.x, c.M, PF_M, c.K, dX[0], dXf[0], st);
+    if (c.n_launches == 2) gemm_make_frags(c.x2, c.M, PF_M, c.K, dX[1], dXf[1], st);
+    gemm_upload_w(c, dW, dS, st);
+    dY.alloc((size_t)PF_M * c.N, 4, st); dY.up(c.y, (size_t)c.M * c.N, st);
+    dA.alloc((size_t)2 * PF_M * c.N, 2, st);
+    dSS.alloc((size_t)PF_M * I.nblk, 4, st);
+    dG.alloc((size_t)c.N, 4, st); dG.up(c.g, (size_t)c.N, st);
+    const size_t units = rows_xchg_bytes(c.N) / 16;
+    std::vector<uint32_t> hx(units * 4);
+    for (size_t u = 0; u < units; ++u) { hx[4 * u] = 0x7FC00000u; hx[4 * u + 1] = (uint32_t)c.stale_tag; hx[4 * u + 2] = 0x7FC00000u; hx[4 * u + 3] = (uint32_t)c.stale_tag; }
+    dXchg.alloc(units * 4, 4, st); dXchg.up(hx.data(), units * 4, st);
+    const uint32_t he[2] = {(uint32_t)c.epoch, 0u};
+    dEpoch.alloc(2, 4, st); dEpoch.up(he, 2, st);
+    FS_HIP(hipStreamSynchronize(st));
+    const NormAux na{(const float*)dG.data(), (float*)dSS.data(), (bf16_t*)dA.data(), I.nblk, c.N, c.eps};
+    std::vector<uint16_t> hA(dA.n);
+    for (int l = 0; l < c.n_launches; ++l) {
+        if (l > 0) { dA.poison(st); dSS.poison(st); }
+        launch_gemm_down(st, (const bf16_t*)dXf[l].data(), c.M, c.K, dW.data(), c.fp8 ? (const float*)dS.data() : nullptr, c.N, (float*)dY.data(), c.N, na,
+                         dXchg.data(), (uint32_t*)dEpoch.data(), (uint32_t)(c.node_id + l));
+        FS_LAUNCH_CHECK();
+        uint32_t e[2] = {0u, 0u};
+        if (o.y) dY.down(o.y + (size_t)l * PF_M * c.N, st);
+        dA.down(hA.data(), st);
+        if (o.ss) dSS.down(o.ss + (size_t)l * PF_M * I.nblk, st);
+        FS_HIP(hipMemcpyAsync(e, dEpoch.data(), 8, hipMemcpyDeviceToHost, st));
+        FS_HIP(hipStreamSynchronize(st));
+        if (o.planes) gemm_defrag(hA, PF_M, c.N, o.planes + (size_t)l * 2 * PF_M * c.N);
+        if (o.epoch1) o.epoch1[l] = e[1];
+    }
+    bool ok = true;
+    for (const GemmDev* b : {&dXf[0], &dXf[1], &dY, &dA, &dSS, &dXchg, &dEpoch}) ok = b->intact(st) && ok;
+    o.guard_ok = ok ? 1 : 0;
+}
+}  // namespace
+
+void gemm_selftest(int device, const fs_gemm_case& c, fs_gemm_out& o) {
+    GemmCaseInfo I;
+    gemm_validate(c, I);
+    std::snprintf(o.variant, o.variant_cap, "%s", I.name.c_str());
+    o.grid[0] = (int32_t)I.plan.gx; o.grid[1] = (int32_t)I.plan.gy; o.grid[2] = (int32_t)I.plan.gz;
+    o.n_y = I.n_y; o.n_planes = I.n_planes; o.n_ss = I.n_ss;
+    if (c.plan_only) return;
+    gemm_req((!o.y || o.y_cap >= I.n_y) && (!o.planes || o.planes_cap >= I.n_planes) && (!o.ss || o.ss_cap >= I.n_ss) &&
+             ((!o.k && !o.v) || o.pool_cap >= I.n_pool), "an output capacity is too small");
+    GemmStream gs(device);
+    if (c.op == FS_GEMM_PREP) gemm_run_prep(c, I, o, gs.st);
+    else if (c.op == FS_GEMM_ROWS) gemm_run_rows(c, I, o, gs.st);
+    else gemm_run_down(c, I, o, gs.st);
+}
 
 }  // namespace fs

@@ -20,6 +20,8 @@
 #include "fs_slot_book.h"
 
 struct fs_attn_case;
+struct fs_gemm_case;
+struct fs_gemm_out;
 
 namespace fs {
 
@@ -160,6 +162,25 @@ struct RowKernels {
     static void rows_head(const ModelDims& d, int M, const RowsCtx& c, const void* W, const float* wscale, int n_rows, float* logits, int ld,
                           hipStream_t st, bool rms = false);
 };
+
+// What a row-path GEMM launcher will launch for a given call: decided in ONE place (gemm_plan, lm_gemm.hip), launch_gemm3 and
+// launch_gemm_down dispatch through it, and fs_selftest_gemm reports its name ("gemm3/QKV_RMS/nks8/rt1/bf16/half", "big/SWIGLU_RMS/fp8",
+// "down/nks8/ks4/bf16").  The name is the kernel instantiation; ksplit of a GEMM3 / BIG launch is a grid dimension, not part of it.
+struct GemmPlan {
+    enum Kind { GEMM3, BIG, DOWN };
+    Kind kind = GEMM3;
+    int epi = 0;           // EPI_* of the instantiation (DOWN: its own epilogue, GEMM_EPI_DOWN)
+    int nks = 0;           // 32-deep k-steps per wave (BIG: 16)
+    int rt = 1;            // 16-row weight tiles per wave (GEMM3)
+    bool fp8 = false;
+    bool half = false;     // GEMM3, M <= 16: rows 16..31 of the only panel are skipped
+    int ksplit = 1;        // K ranges == gridDim.y
+    unsigned gx = 1, gy = 1, gz = 1;
+    std::string name() const;
+};
+constexpr int GEMM_EPI_DOWN = 9;  // not a k_gemm3 epilogue: selects launch_gemm_down's plan (ksplit and nks follow from K)
+// big_min_m: 0 = FISHRT_GEMM_BIG_MIN_M / the built-in row count from which the LDS-staged variant is taken
+GemmPlan gemm_plan(int epi, int rt, int M, int N, int K, int ksplit, bool fp8, int big_min_m = 0);
 
 // ---- attention launchers (lm_attn.hip; all asynchronous on `st`)
 // What an attention launcher will launch for a given call: decided in ONE place (AttnKernels::decode_plan / rows_plan), the launchers
@@ -371,6 +392,8 @@ void launch_fp8_decode_table(float* out, hipStream_t st);
 // test hook behind fs_selftest_attn (include/fishrt.h; harness at the bottom of lm_attn.hip)
 void attn_selftest(int device, const fs_attn_case& c, float* out, size_t out_cap, size_t* n_out, float* k_out, float* v_out, char* variant_out,
                    size_t variant_cap, int* guard_ok);
+// test hook behind fs_selftest_gemm (include/fishrt.h; harness at the bottom of lm_gemm.hip)
+void gemm_selftest(int device, const fs_gemm_case& c, fs_gemm_out& out);
 // test hook behind fs_selftest_sample_rows (include/fishrt.h)
 void debug_sample_rows(int device, const float* logits, int B, int n, double temp, double top_p, uint64_t top_k, uint64_t seed,
                        int call_index, uint32_t* out);

@@ -59,6 +59,21 @@ class AttnCase(C.Structure):  # fs_attn_case: one attention launcher call for fs
                [("codes", C.POINTER(C.c_uint32))]
 
 
+class GemmCase(C.Structure):  # fs_gemm_case: one row-path GEMM launcher call for fs_selftest_gemm
+    _fields_ = [(n, C.c_int32) for n in ("op", "fp8", "epi", "rt", "M", "N", "K", "ksplit", "D", "S", "want_frag", "ldy", "ldo", "H", "Hk", "Dh",
+                                         "pos", "rope_off", "pos_step", "pt_stride", "seq_rows", "pt_rows", "pt_len", "n_pages", "rope_rows",
+                                         "o1", "nblk", "big_min_m", "n_launches", "stale_tag", "node_id", "epoch", "plan_only",
+                                         "reserved")] + [("eps", C.c_float), ("reserved2", C.c_int32)] + \
+               [(n, C.POINTER(C.c_float)) for n in ("x", "x2", "p", "norm_w", "w", "wscale", "y", "g", "ss", "cos_t", "sin_t", "k", "v")] + \
+               [(n, C.POINTER(C.c_int32)) for n in ("row_pos", "row_rope_off", "seq_pos", "seq_rope_off", "page_table")]
+
+
+class GemmOut(C.Structure):  # fs_gemm_out: where fs_selftest_gemm leaves its results
+    _fields_ = [(n, C.POINTER(C.c_float)) for n in ("y", "planes", "ss", "k", "v")] + [("epoch1", C.POINTER(C.c_uint32)), ("variant", C.c_char_p)] + \
+               [(n, C.c_size_t) for n in ("y_cap", "planes_cap", "ss_cap", "pool_cap", "variant_cap", "n_y", "n_planes", "n_ss")] + \
+               [("grid", C.c_int32 * 3), ("guard_ok", C.c_int32)]
+
+
 FRAME_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32))
 
 # every symbol include/fishrt.h declares (tests/test_abi.py checks the library exports all of them)
@@ -72,7 +87,7 @@ SYMBOLS = ["fs_last_error", "fs_version", "fs_device_count", "fs_lm_create", "fs
            "fs_lm_session_add_scored", "fs_lm_session_poll_scores", "fs_selftest_score_rows",
            "fs_lm_session_add_traced", "fs_lm_session_poll_trace",
            "fs_lm_session_poll_alts", "fs_selftest_alt_rows",
-           "fs_selftest_conv1d", "fs_selftest_codec_op", "fs_selftest_codec_encode_stage", "fs_selftest_attn",
+           "fs_selftest_conv1d", "fs_selftest_codec_op", "fs_selftest_codec_encode_stage", "fs_selftest_attn", "fs_selftest_gemm",
            "fs_lm_weights_fingerprint", "fs_lm_session_prefix_export", "fs_lm_session_prefix_import",
            "fs_lm_session_prefix_from_slot", "fs_lm_session_last_frame",
            "fs_codec_create", "fs_codec_destroy", "fs_codec_load_safetensors", "fs_codec_load_synthetic",
@@ -137,6 +152,11 @@ ATTN_PROTOTYPES = {
                          C.POINTER(C.c_int)],
 }
 
+# fs_selftest_gemm (ops, epilogues: include/fishrt.h)
+FS_GEMM_PREP, FS_GEMM_ROWS, FS_GEMM_DOWN = range(3)
+GEMM_EPI = {n: i for i, n in enumerate(("STORE", "RESIDUAL", "SWIGLU", "QKV", "RESIDUAL_NORM", "SWIGLU_RMS", "QKV_RMS", "STORE_RMS", "QKV_SEQ"))}
+GEMM_PROTOTYPES = {"fs_selftest_gemm": [C.c_int, C.POINTER(GemmCase), C.POINTER(GemmOut)]}
+
 # ... and of the calls that make a prefix out of a slot's history
 HISTORY_PROTOTYPES = {
     "fs_lm_session_prefix_from_slot": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)],
@@ -192,7 +212,7 @@ def lib():
         L.fs_comm_destroy.argtypes = [C.c_void_p]
         L.fs_lm_destroy.argtypes = [C.c_void_p]
         L.fs_codec_destroy.argtypes = [C.c_void_p]
-        for name, argtypes in {**SCORE_PROTOTYPES, **TRACE_PROTOTYPES, **ALTS_PROTOTYPES, **CONV_PROTOTYPES, **CODEC_OP_PROTOTYPES, **ATTN_PROTOTYPES, **HISTORY_PROTOTYPES,
+        for name, argtypes in {**SCORE_PROTOTYPES, **TRACE_PROTOTYPES, **ALTS_PROTOTYPES, **CONV_PROTOTYPES, **CODEC_OP_PROTOTYPES, **ATTN_PROTOTYPES, **GEMM_PROTOTYPES, **HISTORY_PROTOTYPES,
                                **RESAMPLE_PROTOTYPES}.items():
             if hasattr(L, name):  # (an older build loaded through LIB_PATH -- tools/attn_paths_dump.py --lib -- may lack the newest entry points)
                 getattr(L, name).argtypes = argtypes

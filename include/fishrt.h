@@ -237,6 +237,64 @@ typedef struct fs_attn_case {
 int fs_selftest_attn(int device_id, const fs_attn_case* c, float* out, size_t out_cap, size_t* n_out, float* k_out, float* v_out,
                      char* variant_out, size_t variant_cap, int* guard_ok);
 
+/* ONE launcher call of the row-path GEMM family (csrc/lm_gemm.hip: k_prep, launch_gemm3 -> k_gemm3 / k_gemm_big, launch_gemm_down ->
+ * k_gemm_down) on caller-provided host data, and nothing else.  All tensors f32 row-major unless stated; Mcap = M rounded up to 32.
+ *   FS_GEMM_PREP  k_prep as rows_layer / rows_finish launch it: x [M][D] (+= the S slabs p [S][M][D], S may be 0), norm_w [D] (nullable),
+ *                 eps; want_frag = 0 launches it without a fragment output.  out.y = X [M][D]; out.planes = hi then lo, each [Mcap][D].
+ *   FS_GEMM_ROWS  launch_gemm3<epi, rt> for the (epi, rt) pairs of rows_layer / rows_head (SWIGLU / SWIGLU_RMS with rt 2, every other
+ *                 epilogue with rt 1; anything else is an error).  x [M][K]: the harness makes the hi / lo fragments with k_prep (no norm: a
+ *                 plain split).  w [N][K]: fp8 == 0 -> every value exactly a bf16 value; fp8 != 0 -> every value exactly an e4m3fn value and
+ *                 wscale [N] the row scales (anything else is an error).  Epilogue inputs: y [M][ldy] (the residual stream of RESIDUAL /
+ *                 RESIDUAL_NORM), g [N] (RESIDUAL_NORM), ss [M][nblk] + eps (the *_RMS epilogues; the row's rms is sqrt(sum_b ss / K + eps)),
+ *                 QKV*: cos_t / sin_t [rope_rows][Dh / 2], N == (H + 2 Hk) Dh, the pools k / v f32 [n_pages][Hk][64][Dh] (bf16 values),
+ *                 page_table int32 [pt_rows][pt_len]; positions: row m at pos + m * pos_step (pos_step 1 / 0), at row_pos[m] with rope offset
+ *                 row_rope_off[m] (pos_step < 0: per-row states), token m % seq_rows of sequence m / seq_rows at pos (QKV, QKV_RMS) or at
+ *                 seq_pos[s] with seq_rope_off[s] (QKV_SEQ), page-table row of a sequence pt_stride apart; o1 != 0: the QKV launch also
+ *                 leaves the attention output of a one-token cache.  ldy: row stride of Y; ldo: of the SwiGLU planes (0 = N / 2).
+ *                 big_min_m (0 = the production value) replaces FISHRT_GEMM_BIG_MIN_M for this call.
+ *                 out.y = Y: STORE / STORE_RMS [ksplit][Mcap][ldy] (every slab), else [Mcap][ldy]; out.planes = hi then lo of the fragment
+ *                 output, each [Mcap][C]: SWIGLU* C = ldo, RESIDUAL_NORM C = N, QKV* with o1 C = H Dh; out.ss [Mcap][grid.x] (RESIDUAL_NORM);
+ *                 out.k / out.v = both pools after the launch.
+ *   FS_GEMM_DOWN  launch_gemm_down: x [M][K] (x2: the second launch's), w [N][K], y = X [M][N], g [N], n_launches 1 or 2 on the same
+ *                 exchange buffer with node ids node_id, node_id + 1 and step epoch `epoch` (>= 1).  Every exchange unit starts as {NaN,
+ *                 stale_tag, NaN, stale_tag}.  Refused unless gemm_down_ok AND the device holds the whole grid at once (the owner waves
+ *                 wait for blocks of the same launch); with plan_only residency is not queried.  Per launch: out.y [32][N], out.planes
+ *                 [2][32][N], out.ss [32][N / 16], out.epoch1 = the give-up counter.
+ * Every device buffer a launch writes lies between 256-element guards of 0xFF bytes and is itself filled with 0xFF bytes (f32 / bf16 NaN)
+ * where the caller provides nothing; out.guard_ok = 1 iff every guard is intact.  Fragment rows [M, Mcap) of every GEMM input hold bf16 NaN.
+ * out.variant: GemmPlan::name ("gemm3/QKV_RMS/nks8/rt1/bf16/half", "big/SWIGLU_RMS/fp8", "down/nks8/ks4/bf16", "prep/one", "prep/reread");
+ * out.grid: the launch grid.  Output pointers are nullable; a non-null one needs its capacity.  The case is VALIDATED BEFORE ANY DEVICE
+ * CALL; a bad case is an error and nothing is launched.  plan_only != 0: validate, return name and grid, touch no device.
+ * Diagnostics / parity tests. */
+enum { FS_GEMM_PREP = 0, FS_GEMM_ROWS = 1, FS_GEMM_DOWN = 2 };
+enum { FS_GEMM_EPI_STORE = 0, FS_GEMM_EPI_RESIDUAL = 1, FS_GEMM_EPI_SWIGLU = 2, FS_GEMM_EPI_QKV = 3, FS_GEMM_EPI_RESIDUAL_NORM = 4,
+       FS_GEMM_EPI_SWIGLU_RMS = 5, FS_GEMM_EPI_QKV_RMS = 6, FS_GEMM_EPI_STORE_RMS = 7, FS_GEMM_EPI_QKV_SEQ = 8 };
+typedef struct fs_gemm_case {
+    int32_t op, fp8, epi, rt;
+    int32_t M, N, K, ksplit;
+    int32_t D, S, want_frag, ldy;
+    int32_t ldo, H, Hk, Dh;
+    int32_t pos, rope_off, pos_step, pt_stride;
+    int32_t seq_rows, pt_rows, pt_len, n_pages;
+    int32_t rope_rows, o1, nblk, big_min_m;
+    int32_t n_launches, stale_tag, node_id, epoch;
+    int32_t plan_only, reserved;
+    float eps;
+    int32_t reserved2;
+    const float *x, *x2, *p, *norm_w, *w, *wscale, *y, *g, *ss, *cos_t, *sin_t, *k, *v;
+    const int32_t *row_pos, *row_rope_off, *seq_pos, *seq_rope_off, *page_table;
+} fs_gemm_case;
+typedef struct fs_gemm_out {
+    float *y, *planes, *ss, *k, *v;
+    uint32_t* epoch1;
+    char* variant;
+    size_t y_cap, planes_cap, ss_cap, pool_cap, variant_cap;
+    size_t n_y, n_planes, n_ss;
+    int32_t grid[3];
+    int32_t guard_ok;
+} fs_gemm_out;
+int fs_selftest_gemm(int device_id, const fs_gemm_case* c, fs_gemm_out* out);
+
 /* Stage tap of the encoder on a LOADED handle: runs fs_codec_encode's device path on the clip exactly as fs_codec_encode does (same buffers,
  * same launches, the codes are computed and dropped) and copies ONE intermediate tensor to the host:
  *   stage -1     the log-mel [160][F], F = mel frames of the clip

@@ -37,6 +37,10 @@ def test_struct_layouts_match_header():
     assert ctypes.sizeof(_ffi.CodecOpCase) == 16 * 4 + 8 + 8 * 8  # fs_codec_op_case: 16 x int32, one int64, 8 pointers (static_assert there too)
     assert ctypes.sizeof(_ffi.AttnCase) == 32 * 4 + 13 * 8  # fs_attn_case: 30 x int32, one float, one int32, 13 pointers (static_assert there too)
     assert _ffi.AttnCase.stale_part.offset == 120 and _ffi.AttnCase.row_pos.offset == 128 and _ffi.AttnCase.codes.offset == 224
+    assert ctypes.sizeof(_ffi.GemmCase) == 36 * 4 + 18 * 8  # fs_gemm_case: 34 x int32, one float, one int32, 18 pointers (static_assert there too)
+    assert ctypes.sizeof(_ffi.GemmOut) == 7 * 8 + 8 * 8 + 4 * 4  # fs_gemm_out: 7 pointers, 8 x size_t, 4 x int32
+    assert _ffi.GemmCase.eps.offset == 136 and _ffi.GemmCase.x.offset == 144 and _ffi.GemmCase.page_table.offset == 280
+    assert _ffi.GemmOut.y_cap.offset == 56 and _ffi.GemmOut.grid.offset == 120
     assert _ffi.CodecOpCase.ctx_elems.offset == 64 and _ffi.CodecOpCase.x.offset == 72 and _ffi.CodecOpCase.codes.offset == 128
 
 
