@@ -27,6 +27,8 @@ class CodecBase {
     virtual void encode_stage(const float* pcm, int n, int stage, float* out, size_t cap, size_t* n_out) = 0;
     // ---- device sample-rate conversion of the PCM (fs_codec_*_pcm, include/fishrt.h; codec_resample.hip).  spec = {rate, mode, format}
     virtual void decode_pcm(const uint32_t* codes, int b, int T, const int* spec3, void* out, size_t cap, int64_t* n_out) = 0;
+    // fs_codec_decode_speed: the rows time-stretched (codec_tsm.hip, default parameters) between the vocoder and the stage above
+    virtual void decode_speed(const uint32_t* codes, int b, int T, double speed, const int* spec3, void* out, size_t cap, int64_t* n_out) = 0;
     virtual int streams_open_pcm(const int* spec3) = 0;
     virtual int64_t streams_pending(int id, int T, bool final) = 0;
     virtual void streams_decode_pcm(int n, const int* ids, const int* T, const uint8_t* final, const uint32_t* codes, void* out,
@@ -52,6 +54,10 @@ namespace fs {
 // fs_resample: b host rows of their own lengths, host -> device -> host, no codec handle
 void resample_rows(int device, const float* pcm, int b, size_t stride, const int64_t* n_samples, int from_rate, const int* spec3, void* out,
                    size_t out_stride, int64_t* out_len);
+
+// fs_time_stretch: b host rows of their own lengths, host -> device -> host, no codec handle; params2 = {frame, radius} or null
+void time_stretch_rows(int device, const float* pcm, int b, size_t stride, const int64_t* n_samples, double speed, const int* params2, float* out,
+                       size_t out_stride, int64_t* out_len, int64_t* positions, size_t pos_stride);
 
 // fs_selftest_conv1d: one conv through re-layout, pack, plane producers and one launcher of codec_kernels.h (see include/fishrt.h)
 void codec_conv_selftest(int device, const fs_conv_case& c, float* y_out, float* planes_out, char* variant_out, size_t variant_cap,

@@ -17,6 +17,7 @@
 #include "../../include/fishrt.h"
 #include "codec_kernels.h"
 #include "codec_resample.h"
+#include "codec_tsm.h"
 #include "fs_common.h"
 #include "fs_synth.h"
 #include "safetensors.h"
@@ -360,15 +361,41 @@ class Codec final : public CodecBase {
     static size_t pcm_bytes(int format) { return format == kPcmS16 ? 2 : 4; }
 
     void decode_pcm(const uint32_t* codes, int B, int T, const int* spec3, void* out, size_t cap, int64_t* n_out) override {
+        decode_pcm_speed(codes, B, T, 1.0, spec3, out, cap, n_out, "fs_codec_decode_pcm: cap is smaller than fs_resample_out_len of a row");
+    }
+    // speed == 1.0: no stretch stage
+    void decode_speed(const uint32_t* codes, int B, int T, double speed, const int* spec3, void* out, size_t cap, int64_t* n_out) override {
+        tsm_require_speed(speed);
+        decode_pcm_speed(codes, B, T, speed, spec3, out, cap, n_out,
+                         "fs_codec_decode_speed: cap is smaller than fs_resample_out_len of fs_time_stretch_out_len of a row");
+    }
+    void decode_pcm_speed(const uint32_t* codes, int B, int T, double speed, const int* spec3, void* out, size_t cap, int64_t* n_out,
+                          const char* cap_msg) {
         FS_HIP(hipSetDevice(device_));
         FS_REQUIRE(B >= 1 && T >= 1, "empty input");
         int mode, format;
         ResampleRates r;
         parse_spec(spec3, sample_rate(), spec3[0], mode, format, r);
-        const int64_t n_in = (int64_t)samples_per_frame() * T, ol = resample_out_len(r, mode, n_in);
-        FS_REQUIRE((int64_t)cap >= ol, "fs_codec_decode_pcm: cap is smaller than fs_resample_out_len of a row");
+        const bool stretch = speed != 1.0;
+        const TsmParams tp;
+        const int64_t n_voc = (int64_t)samples_per_frame() * T, n_in = stretch ? tsm_out_len(n_voc, speed) : n_voc;
+        const int64_t ol = resample_out_len(r, mode, n_in);
+        FS_REQUIRE((int64_t)cap >= ol, cap_msg);
         const float* d = nullptr;
         decode_impl(codes, B, T, nullptr, kOneShot, &d);
+        if (stretch) {  // the vocoder's rows -> ts_out_, the rows the stage below reads
+            const int64_t K = tsm_frames(n_in, tp);
+            ts_out_.ensure((size_t)B * std::max<int64_t>(n_in, 1) * sizeof(float));
+            ts_pos_.ensure((size_t)B * std::max<int64_t>(K, 1) * sizeof(long long));
+            std::vector<TsmItem> rows((size_t)B);
+            for (int b = 0; b < B; ++b) {
+                rows[(size_t)b].src = d + (size_t)b * n_voc; rows[(size_t)b].n = n_voc;
+                rows[(size_t)b].out = ts_out_.f() + (size_t)b * n_in;
+                rows[(size_t)b].pos = (long long*)ts_pos_.p + (size_t)b * K;
+            }
+            stretcher().run(rows, speed, tp);
+            d = ts_out_.f();
+        }
         const size_t esz = pcm_bytes(format), row = ((size_t)ol * esz + 3) & ~(size_t)3;
         rs_out_.ensure((size_t)B * row);
         std::vector<ResampleItem> items((size_t)B);
@@ -1036,6 +1063,9 @@ class Codec final : public CodecBase {
     DBuf rs_out_, rs_mix_;                         // the resampled rows of a call; the downmixed clip of fs_codec_encode_pcm
     std::vector<uint8_t> rs_host_;                 // host side of rs_out_ (rows at 4-byte aligned offsets), unpacked into the caller's buffer
     Resampler& resampler() { if (!rs_) rs_.reset(new Resampler(st_)); return *rs_; }
+    std::unique_ptr<TimeStretcher> ts_;            // made on first use, on st_ (fs_codec_decode_speed)
+    DBuf ts_out_, ts_pos_;                         // the stretched rows of a call and their frame positions
+    TimeStretcher& stretcher() { if (!ts_) ts_.reset(new TimeStretcher(st_)); return *ts_; }
     std::vector<MStream> ms_;                      // fs_codec_streams_*, index = stream id
     int ms_cap_ = 0;                               // streams the pools hold
     DBuf mpool_p_, mpool_f_, dtab_;                // context pools [stream][half][...] and the per-call device offset table
@@ -1117,6 +1147,65 @@ void resample_rows(int device, const float* pcm, int b, size_t stride, const int
         for (int i = 0; i < b; ++i) {
             if (ol[(size_t)i])
                 FS_HIP(hipMemcpyAsync((uint8_t*)out + (size_t)i * out_stride * esz, (const uint8_t*)dout.p + ooff[(size_t)i], (size_t)ol[(size_t)i] * esz, hipMemcpyDeviceToHost, st.s));
+            out_len[i] = ol[(size_t)i];
+        }
+        FS_HIP(hipStreamSynchronize(st.s));
+    }
+}
+
+// fs_time_stretch (include/fishrt.h): the rows go to the device, through the two launches of the time stretcher, and back.  Follows the
+// definition to the letter, speed 1.0 included
+void time_stretch_rows(int device, const float* pcm, int b, size_t stride, const int64_t* n_samples, double speed, const int* params2, float* out,
+                       size_t out_stride, int64_t* out_len, int64_t* positions, size_t pos_stride) {
+    FS_REQUIRE(b >= 1 && b <= 4096, "fs_time_stretch takes 1 .. 4096 rows");
+    tsm_require_speed(speed);
+    TsmParams tp;
+    if (params2) { tp.N = params2[0]; tp.D = params2[1]; }
+    tsm_require_params(tp);
+    std::vector<int64_t> ol((size_t)b), K((size_t)b);
+    std::vector<size_t> ioff((size_t)b), ooff((size_t)b), poff((size_t)b);
+    size_t in_elems = 0, out_elems = 0, pos_elems = 0;
+    for (int i = 0; i < b; ++i) {
+        FS_REQUIRE(n_samples[i] >= 0 && (size_t)n_samples[i] <= stride && n_samples[i] < (1ll << 40), "fs_time_stretch: a row's length must be in 0 .. stride");
+        ol[(size_t)i] = tsm_out_len(n_samples[i], speed);
+        K[(size_t)i] = tsm_frames(ol[(size_t)i], tp);
+        FS_REQUIRE((size_t)ol[(size_t)i] <= out_stride, "fs_time_stretch: out_stride is smaller than fs_time_stretch_out_len of a row");
+        FS_REQUIRE(!positions || (size_t)K[(size_t)i] <= pos_stride, "fs_time_stretch: pos_stride is smaller than the frame count of a row");
+        ioff[(size_t)i] = in_elems; in_elems += (size_t)n_samples[i];
+        ooff[(size_t)i] = out_elems; out_elems += (size_t)ol[(size_t)i];
+        poff[(size_t)i] = pos_elems; pos_elems += (size_t)K[(size_t)i];
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw Error("no HIP device visible: libfishrt has no CPU fallback (MI355X / gfx950 required)");
+    FS_REQUIRE(device >= 0 && device < ndev, "device_id out of range");
+    FS_HIP(hipSetDevice(device));
+    struct Stream {
+        hipStream_t s = nullptr;
+        ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+    } st;
+    FS_HIP(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    DBuf din, dout, dpos;
+    din.alloc(std::max<size_t>(in_elems, 1) * sizeof(float));
+    dout.alloc(std::max<size_t>(out_elems, 1) * sizeof(float));
+    dpos.alloc(std::max<size_t>(pos_elems, 1) * sizeof(long long));
+    {
+        TimeStretcher ts(st.s);
+        std::vector<TsmItem> items((size_t)b);
+        for (int i = 0; i < b; ++i) {
+            TsmItem& it = items[(size_t)i];
+            if (n_samples[i])
+                FS_HIP(hipMemcpyAsync(din.f() + ioff[(size_t)i], pcm + (size_t)i * stride, (size_t)n_samples[i] * sizeof(float), hipMemcpyHostToDevice, st.s));
+            it.src = din.f() + ioff[(size_t)i]; it.n = n_samples[i];
+            it.out = dout.f() + ooff[(size_t)i];
+            it.pos = (long long*)dpos.p + poff[(size_t)i];
+        }
+        ts.run(items, speed, tp);
+        static_assert(sizeof(long long) == sizeof(int64_t), "positions are copied out as they are");
+        for (int i = 0; i < b; ++i) {
+            if (ol[(size_t)i])
+                FS_HIP(hipMemcpyAsync(out + (size_t)i * out_stride, dout.f() + ooff[(size_t)i], (size_t)ol[(size_t)i] * sizeof(float), hipMemcpyDeviceToHost, st.s));
+            if (positions && K[(size_t)i])
+                FS_HIP(hipMemcpyAsync(positions + (size_t)i * pos_stride, (const long long*)dpos.p + poff[(size_t)i], (size_t)K[(size_t)i] * sizeof(int64_t), hipMemcpyDeviceToHost, st.s));
             out_len[i] = ol[(size_t)i];
         }
         FS_HIP(hipStreamSynchronize(st.s));

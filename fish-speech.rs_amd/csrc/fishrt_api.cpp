@@ -8,6 +8,7 @@
 #include "fs_comm.h"
 #include "fs_common.h"
 #include "fs_resample_plan.h"
+#include "fs_tsm_plan.h"
 #include "lm_engine.h"
 #include "lm_kernels.h"
 #include "lm_persist.h"
@@ -437,6 +438,23 @@ int fs_resample(int device_id, const float* pcm, int b, size_t stride, const int
 int fs_codec_decode_pcm(fs_codec_t* c, const uint32_t* codes, int b, int T, const fs_pcm_spec* spec, void* out, size_t cap, int64_t* n_out) {
     FS_ARG(c && codes && spec && out && n_out, "null argument");
     FS_TRY(c->impl->decode_pcm(codes, b, T, &spec->rate, out, cap, n_out))
+}
+static_assert(sizeof(fs_tsm_params) == 2 * sizeof(int32_t), "fs_tsm_params is passed to the engine as int[2]");
+int fs_time_stretch_out_len(int64_t n, double speed, int64_t* out_len) {
+    FS_ARG(out_len, "null argument");
+    FS_ARG(n >= 0 && n < ((int64_t)1 << 40), "n out of range");
+    FS_TRY(fs::tsm_require_speed(speed); *out_len = fs::tsm_out_len(n, speed))
+}
+int fs_time_stretch(int device_id, const float* pcm, int b, size_t stride, const int64_t* n_samples, double speed, const fs_tsm_params* params,
+                    float* out, size_t out_stride, int64_t* out_len, int64_t* positions, size_t pos_stride) {
+    FS_ARG(pcm && n_samples && out && out_len, "null argument");
+    FS_TRY(fs::time_stretch_rows(device_id, pcm, b, stride, n_samples, speed, params ? &params->frame : nullptr, out, out_stride, out_len, positions,
+                                 pos_stride))
+}
+int fs_codec_decode_speed(fs_codec_t* c, const uint32_t* codes, int b, int T, double speed, const fs_pcm_spec* spec, void* out, size_t cap,
+                          int64_t* n_out) {
+    FS_ARG(c && codes && spec && out && n_out, "null argument");
+    FS_TRY(c->impl->decode_speed(codes, b, T, speed, &spec->rate, out, cap, n_out))
 }
 int fs_codec_streams_open_pcm(fs_codec_t* c, const fs_pcm_spec* spec, int* stream_id) {
     FS_ARG(c && spec && stream_id, "null argument");

@@ -94,6 +94,7 @@ SYMBOLS = ["fs_last_error", "fs_version", "fs_device_count", "fs_lm_create", "fs
            "fs_codec_decode", "fs_codec_encode", "fs_codec_encode_batch", "fs_codec_sample_rate", "fs_codec_set_precision", "fs_codec_precision", "fs_codec_set_range_check", "fs_codec_range_stats", "fs_codec_stream_begin", "fs_codec_stream_decode", "fs_codec_stream_end", "fs_codec_streams_open", "fs_codec_streams_close", "fs_codec_streams_decode", "fs_codec_streams_decode_ragged",
            "fs_resample_out_len", "fs_resample", "fs_codec_decode_pcm", "fs_codec_streams_open_pcm", "fs_codec_streams_pending",
            "fs_codec_streams_decode_pcm", "fs_codec_encode_pcm",
+           "fs_time_stretch_out_len", "fs_time_stretch", "fs_codec_decode_speed",
            "fs_fp8_quantize_rows", "fs_fp8_decode_table", "fs_selftest", "fs_lm_selftest", "fs_selftest_sample_rows", "fs_selftest_sample_slots", "fs_lm_debug_capture", "fs_lm_debug_read"]
 
 # flags of fs_lm_generate* / fs_lm_session_begin (include/fishrt.h)
@@ -193,6 +194,19 @@ RESAMPLE_PROTOTYPES = {
     "fs_codec_encode_pcm": [C.c_void_p, _F32P, C.c_int, C.c_int64, C.c_int, C.c_int, _U32P, C.c_size_t, C.POINTER(C.c_size_t)],
 }
 
+
+
+# device time-stretch (include/fishrt.h: fs_tsm_params; speed is a double)
+class TsmParams(C.Structure):  # fs_tsm_params
+    _fields_ = [("frame", C.c_int32), ("radius", C.c_int32)]
+
+
+TSM_PROTOTYPES = {
+    "fs_time_stretch_out_len": [C.c_int64, C.c_double, _I64P],
+    "fs_time_stretch": [C.c_int, _F32P, C.c_int, C.c_size_t, _I64P, C.c_double, C.POINTER(TsmParams), _F32P, C.c_size_t, _I64P, _I64P, C.c_size_t],
+    "fs_codec_decode_speed": [C.c_void_p, _U32P, C.c_int, C.c_int, C.c_double, C.POINTER(PcmSpec), C.c_void_p, C.c_size_t, _I64P],
+}
+
 _lib = None
 
 
@@ -213,7 +227,7 @@ def lib():
         L.fs_lm_destroy.argtypes = [C.c_void_p]
         L.fs_codec_destroy.argtypes = [C.c_void_p]
         for name, argtypes in {**SCORE_PROTOTYPES, **TRACE_PROTOTYPES, **ALTS_PROTOTYPES, **CONV_PROTOTYPES, **CODEC_OP_PROTOTYPES, **ATTN_PROTOTYPES, **GEMM_PROTOTYPES, **HISTORY_PROTOTYPES,
-                               **RESAMPLE_PROTOTYPES}.items():
+                               **RESAMPLE_PROTOTYPES, **TSM_PROTOTYPES}.items():
             if hasattr(L, name):  # (an older build loaded through LIB_PATH -- tools/attn_paths_dump.py --lib -- may lack the newest entry points)
                 getattr(L, name).argtypes = argtypes
         _lib = L

@@ -48,15 +48,30 @@ class FireflyCodec:
             return None
         return _ffi.pcm_spec(self.sample_rate if sample_rate is None else sample_rate, resample, dtype)
 
-    def decode(self, codes, sample_rate=None, resample="linear", dtype="f32"):
+    def decode(self, codes, sample_rate=None, resample="linear", dtype="f32", speed=None):
         """sample_rate / dtype: convert every PCM row on the device before it is copied to the host (fishrt.h fs_codec_decode_pcm) ->
-        (b, 1, out_len) f32 or int16; resample: "linear" (the reference's resample, bit for bit) or "sinc" (band-limited)"""
+        (b, 1, out_len) f32 or int16; resample: "linear" (the reference's resample, bit for bit) or "sinc" (band-limited).
+        speed (0.25 .. 4.0; None = no stretch stage): every row time-stretched on the device first (fishrt.h fs_codec_decode_speed: WSOLA,
+        the pitch stays) -- 2048 T / speed samples per row, before sample_rate / dtype apply"""
         if not isinstance(codes, np.ndarray) or not codes.flags["C_CONTIGUOUS"]:
             raise ValueError("Input array must be contiguous")  # codec.rs:97-101
         if codes.ndim != 3 or codes.shape[1] != 8:
             raise ValueError("codes must have shape (b, 8, T)")
         codes = codes.astype(np.uint32, copy=False)
         b, _, T = codes.shape
+        if speed is not None:
+            from ._resample import resample_out_len
+            from ._tsm import time_stretch_out_len
+            spec = _ffi.pcm_spec(self.sample_rate if sample_rate is None else sample_rate, resample, dtype)
+            n = time_stretch_out_len(2048 * T, speed)  # (refuses a speed outside 0.25 .. 4.0)
+            if spec.rate != self.sample_rate:
+                n = resample_out_len(n, self.sample_rate, spec.rate, resample)
+            out = np.empty((b, 1, max(n, 1)), _ffi.PCM_DTYPES[dtype])
+            got = (C.c_int64 * b)()
+            _ffi.check(_ffi.lib().fs_codec_decode_speed(self._h, codes.ctypes.data_as(C.POINTER(C.c_uint32)), b, T, C.c_double(float(speed)),
+                                                        C.byref(spec), out.ctypes.data_as(C.c_void_p), C.c_size_t(out.shape[2]), got))
+            assert all(got[i] == n for i in range(b))
+            return out[:, :, :n]
         spec = self._spec(sample_rate, resample, dtype)
         if spec is not None:
             from ._resample import resample_out_len

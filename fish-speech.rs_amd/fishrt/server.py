@@ -18,6 +18,12 @@ the device -- `/v1/audio/speech` takes a `sample_rate` field for its WAV and `pc
 `/v1/audio/encoding` downmixes and resamples an upload through `codec.encode(..., sample_rate=sr)` ("linear" is the reference's
 `functional.rs::resample`, `speech.rs:184-216` / `encode_speech.rs:50-54`) instead of scipy on the host; with `opus_rate` (the reference:
 24000) the Opus hook gets PCM at that rate, and that rate.
+Speed (opt-in, `AppState(device_speed=False)`): the `speed` field of the OpenAI schema.  With the option off (the default) the field is
+ignored, as it always was: normal-rate audio, no message.  With it on, `speed` must be a real number in 0.25 .. 4.0 (a JSON number, not a
+string or a boolean; anything else answers 422 with a message) and every vocoded chunk is time-stretched on the device
+(`codec.decode(..., speed=)`: WSOLA, the pitch stays; include/fishrt.h fs_codec_decode_speed) BEFORE it is resampled and formatted -- for the
+WAV, `pcm` and Opus-hook answers alike, with and without `sample_rate` / `opus_rate`.  A request without the field makes the codec calls it
+made before.
 
 Scheduler.  One worker thread per LM handle (= per GPU) drains a queue of chunk jobs.  A job whose conditioning prefix equals the one
 sitting in the handle's KV cache skips the prefix (the reference's `assume_kv_cache`); jobs of different voices simply invalidate it
@@ -148,7 +154,7 @@ class LMState:  # server/lib/state.rs:12-21
 class AppState:  # server/lib/state.rs:23-29
     def __init__(self, lm_state, codec, sample_rate=44100, opus_encoder=None, preprocess=preprocess_text, batch_window_s=0.002,
                  continuous=True, auto_batch=False, session_prefixes=False, per_slot_sampling=False, wide_sampling=False,
-                 prefix_host_cache_bytes=0, chunk_history=False, device_resample=None, opus_rate=None):
+                 prefix_host_cache_bytes=0, chunk_history=False, device_resample=None, opus_rate=None, device_speed=False):
         self.lm, self.codec, self.sample_rate, self.opus_encoder, self.preprocess = lm_state, codec, sample_rate, opus_encoder, preprocess
         # device_resample (None | "linear" | "sinc", off by default): the codec converts sample rates on the device (FireflyCodec.decode /
         # encode with sample_rate=): /v1/audio/speech takes a `sample_rate` field for WAV and `pcm` answers, and /v1/audio/encoding resamples
@@ -158,6 +164,9 @@ class AppState:  # server/lib/state.rs:23-29
         if device_resample not in (None, "linear", "sinc"):
             raise ValueError('device_resample must be None, "linear" or "sinc"')
         self.device_resample, self.opus_rate = device_resample, (None if opus_rate is None else int(opus_rate))
+        # device_speed (off by default: the `speed` field is ignored, as ever): requests may carry `speed` (0.25 .. 4.0) and the codec
+        # time-stretches every chunk on the device before it resamples and formats it (FireflyCodec.decode(speed=))
+        self.device_speed = bool(device_speed)
         self.codec_lock = threading.Lock()  # a codec handle takes one call at a time (include/fishrt.h); requests vocode from their own threads
         self.auto_batch = auto_batch  # True: every chunk may join the batching session (batch sampling semantics) without `batch_size`
         # session_prefixes (off by default): session jobs share their voice's conditioning prefix (Session.add_prefix) instead of prefilling
@@ -762,6 +771,11 @@ def generate_speech(state, req):
                                                                       "server's opus_rate"}).encode()
             if isinstance(out_rate, bool) or not isinstance(out_rate, int) or not 1000 <= out_rate <= 384000:
                 return 422, "application/json", json.dumps({"detail": "`sample_rate` must be an integer number of Hz in 1000 .. 384000"}).encode()
+        speed = req.get("speed") if getattr(state, "device_speed", False) else None  # (option off: the field is ignored)
+        if speed is not None:
+            if isinstance(speed, bool) or not isinstance(speed, (int, float)) or not 0.25 <= speed <= 4.0:  # (NaN fails the comparison)
+                return 422, "application/json", json.dumps({"detail": "`speed` must be a number in 0.25 .. 4.0"}).encode()
+            speed = float(speed)
         # like the reference (speech.rs:72-96) chunks are batched only when the request asks for it (`batch_size` > 1): the batch paths sample
         # with BatchedLogitsProcessor semantics and no repetition penalty, so what a client hears must not depend on the server's load.
         # `auto_batch` (server option, off by default) lets every chunk join the continuous-batching session when other work is in flight.
@@ -781,6 +795,8 @@ def generate_speech(state, req):
                                            seed=None if seed is None else (seed + i) & (2**64 - 1)) for i, b in enumerate(bodies)]
 
         def pcm_chunks(**spec):  # spec: sample_rate / resample / dtype of FireflyCodec.decode (converted on the device); none = as ever
+            if speed is not None:  # stretched on the device, before the conversion
+                spec = dict(spec, speed=speed)
             for f in futs:
                 codes = f.result()
                 with state.codec_lock:

@@ -964,6 +964,48 @@ int fs_codec_streams_decode_pcm(fs_codec_t* c, int n, const int* stream_ids, con
 int fs_codec_encode_pcm(fs_codec_t* c, const float* pcm, int channels, int64_t frames, int rate, int mode, uint32_t* codes_out, size_t cap,
                         size_t* n_frames);
 
+/* ---- Device time-stretch: the `speed` of a request (csrc/codec_tsm.hip; lengths, checks and a host evaluator of this text in
+ * csrc/fs_tsm_plan.h).  The reference has no speed control, and the LM cannot change its speaking rate, so speed is a time-scale modification
+ * of the vocoder's PCM, done where the vocoder left it.  WSOLA with a squared-difference measure:
+ *
+ * Defaults: frame N = 1024, synthesis hop Hs = N / 2 = 512, search radius D = 512, at any rate.  fs_tsm_params may override them with N even,
+ *   64 <= N <= 2048, 0 <= D <= 1024; the vocoder path (fs_codec_decode_speed) always uses the defaults.
+ * Input x: f32, n samples, taken as zero outside [0, n).  speed: a double in [0.25, 4.0].
+ *   out_len = floor(n / speed + 0.5), computed in f64;  K = ceil(out_len / Hs) frames;  nominal position q_k = floor(k * Hs * speed + 0.5), in f64.
+ * Positions: p_0 = 0.  For k >= 1 the template is t[i] = x[p_{k-1} + Hs + i], i < N -- the natural continuation of the previous frame -- and
+ *   for each lag d in [-D, D]:  e[d] = sum_{i < N} (t[i] - x[q_k + d + i])^2, accumulated in f32 in ONE order, the same for every lag:
+ *     seg = ceil(N / 6); segment s = 0 .. 5 covers i in [s * seg, min(N, (s + 1) * seg)); within it, from a_s = 0 and in ascending i,
+ *     df = t[i] - x[q_k + d + i] (one f32 subtraction), a_s = fma(df, df, a_s) (one rounding);
+ *     e[d] = ((((a_0 + a_1) + a_2) + a_3) + a_4) + a_5, five f32 additions.
+ *   p_k = q_k + d*, where d* minimises e; among equal e the smallest |d|, and of +-d the negative one.  A lag whose e is NaN never wins; when no
+ *   lag's e is below +inf, d* = 0.
+ * Window: w[i] = 0.5 - 0.5 cos(2 pi i / N), built in f64 and stored as f32.
+ * Output sample m, with k = m / Hs and i = m - k * Hs:  k == 0: y[m] = x[m];  k >= 1: y[m] = w[i + Hs] * x[p_{k-1} + Hs + i] + w[i] * x[p_k + i],
+ *   the two f32 products rounded separately, then one f32 add (no contraction into an FMA).
+ * Consequences: at speed == 1 every e[0] is exactly 0 and p_k = k * Hs, so y is x up to the rounding of the two products.  Digital silence
+ *   picks d = 0.  A signal that repeats bit for bit with an integer period P makes e[d] == e[d + P] bitwise -- every lag runs the same
+ *   operations in the same order, which is why the order is fixed -- so there the tie rule decides.
+ * In the fs_codec_* calls speed == 1.0 means "no stretch stage", as a spec at the codec's rate means no resample stage; fs_time_stretch follows
+ * the definition to the letter, 1.0 included.  Multi-streams (fs_codec_streams_*) do not stretch: a chunked stretch has to carry a position
+ * and a template from chunk to chunk, and is left to a change of its own. */
+typedef struct fs_tsm_params {
+    int32_t frame /* N */, radius /* D */;
+} fs_tsm_params;
+/* samples that n input samples become at `speed` (out_len above); no device */
+int fs_time_stretch_out_len(int64_t n, double speed, int64_t* out_len);
+/* Stand-alone, no codec handle: b rows f32 at pcm + i * stride, row i n_samples[i] <= stride samples long (0 allowed), host -> device -> the two
+ * launches -> host.  params == NULL: the defaults.  out: f32, row i at element i * out_stride, out_len[i] samples written; out_stride must hold
+ * fs_time_stretch_out_len of every row.  positions (nullable): int64, row i at element i * pos_stride, its K_i = ceil(out_len[i] / Hs) entries
+ * p_0 .. p_{K_i - 1} written; pos_stride must hold every K_i.  Everything is checked before anything is launched. */
+int fs_time_stretch(int device_id, const float* pcm, int b, size_t stride, const int64_t* n_samples, double speed, const fs_tsm_params* params,
+                    float* out, size_t out_stride /* elements */, int64_t* out_len /* [b] */, int64_t* positions, size_t pos_stride);
+/* fs_codec_decode -> time-stretch of every PCM row (the defaults) -> the resample / format stage of fs_codec_decode_pcm -> host, all on the
+ * device.  out: b rows of `cap` elements, n_out[i] samples written in row i; cap must hold fs_resample_out_len of fs_time_stretch_out_len of a
+ * row (checked, like speed and spec, before the first launch).  Equals fs_resample of fs_time_stretch of fs_codec_decode's rows bit for bit
+ * (at the codec's own rate: the format conversion of fs_time_stretch's rows); with speed == 1.0 it is fs_codec_decode_pcm. */
+int fs_codec_decode_speed(fs_codec_t* c, const uint32_t* codes, int b, int T, double speed, const fs_pcm_spec* spec, void* out,
+                          size_t cap /* elements per row */, int64_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif
