@@ -30,6 +30,8 @@ class CodecBase {
     // fs_codec_decode_speed: the rows time-stretched (codec_tsm.hip, default parameters) between the vocoder and the stage above
     virtual void decode_speed(const uint32_t* codes, int b, int T, double speed, const int* spec3, void* out, size_t cap, int64_t* n_out) = 0;
     virtual int streams_open_pcm(const int* spec3) = 0;
+    // fs_codec_streams_open_speed: a stream with a stretch stage between the vocoder and its resample / format stage; spec3 null = codec rate, f32
+    virtual int streams_open_speed(double speed, const int* spec3) = 0;
     virtual int64_t streams_pending(int id, int T, bool final) = 0;
     virtual void streams_decode_pcm(int n, const int* ids, const int* T, const uint8_t* final, const uint32_t* codes, void* out,
                                     size_t cap_bytes, int64_t* n_out) = 0;
@@ -58,6 +60,10 @@ void resample_rows(int device, const float* pcm, int b, size_t stride, const int
 // fs_time_stretch: b host rows of their own lengths, host -> device -> host, no codec handle; params2 = {frame, radius} or null
 void time_stretch_rows(int device, const float* pcm, int b, size_t stride, const int64_t* n_samples, double speed, const int* params2, float* out,
                        size_t out_stride, int64_t* out_len, int64_t* positions, size_t pos_stride);
+
+// fs_selftest_tsm_chunks: one host row through the chunked stretch, one launch pair per chunk (the last chunk is final); params2 as above
+void time_stretch_chunks(int device, const float* pcm, int64_t n, const int64_t* chunks, int n_chunks, double speed, const int* params2, float* out,
+                         size_t out_cap, int64_t* out_len, int64_t* emitted, int64_t* positions, size_t pos_cap, int64_t* n_pos);
 
 // fs_selftest_conv1d: one conv through re-layout, pack, plane producers and one launcher of codec_kernels.h (see include/fishrt.h)
 void codec_conv_selftest(int device, const fs_conv_case& c, float* y_out, float* planes_out, char* variant_out, size_t variant_cap,

@@ -268,6 +268,7 @@ class Codec final : public CodecBase {
             FS_REQUIRE(ids[b] >= 0 && ids[b] < (int)ms_.size() && ms_[ids[b]].chunk >= 0, "not an open stream id of this codec handle");
             for (int a = 0; a < b; ++a) FS_REQUIRE(ids[a] != ids[b], "a stream id appears twice in one call");
             FS_REQUIRE(precision() == ms_[ids[b]].prec, "the precision mode changed since the stream was opened");
+            FS_REQUIRE(!ms_[ids[b]].stretch, kSpeedStreamMsg);
             FS_REQUIRE(!ms_[ids[b]].spec, kSpecStreamMsg);
         }
         check_codes(codes, (size_t)n * 8 * T);
@@ -318,6 +319,7 @@ class Codec final : public CodecBase {
             FS_REQUIRE(ids[b] >= 0 && ids[b] < (int)ms_.size() && ms_[ids[b]].chunk >= 0, "not an open stream id of this codec handle");
             for (int a = 0; a < b; ++a) FS_REQUIRE(ids[a] != ids[b], "a stream id appears twice in one call");
             FS_REQUIRE(precision() == ms_[ids[b]].prec, "the precision mode changed since the stream was opened");
+            FS_REQUIRE(!ms_[ids[b]].stretch, kSpeedStreamMsg);
             FS_REQUIRE(!ms_[ids[b]].spec, kSpecStreamMsg);
             Tmax = std::max(Tmax, T[b]);
             total += (size_t)T[b];
@@ -428,6 +430,22 @@ class Codec final : public CodecBase {
         }
         return id;
     }
+    // spec3 null: codec rate, f32 (a plain stream's output).  speed == 1.0: no stretch stage, the stream is what the spec alone makes it
+    int streams_open_speed(double speed, const int* spec3) override {
+        tsm_require_speed(speed);
+        const int id = spec3 ? streams_open_pcm(spec3) : streams_open();
+        if (speed == 1.0) return id;
+        auto& s = ms_[id];
+        s.stretch = true; s.speed = speed;
+        s.tcarry_cap = tsm_carry_bound(TsmParams{}, speed);
+        s.tcarry = std::make_shared<DBuf>();
+        try {
+            s.tcarry->alloc(16 + (size_t)2 * s.tcarry_cap * sizeof(float));
+            FS_HIP(hipMemsetAsync(s.tcarry->p, 0, 16, st_));
+            FS_HIP(hipStreamSynchronize(st_));
+        } catch (...) { s.chunk = -1; throw; }
+        return id;
+    }
     void require_open(int id) const {
         FS_REQUIRE(id >= 0 && id < (int)ms_.size() && ms_[id].chunk >= 0, "not an open stream id of this codec handle");
     }
@@ -435,7 +453,9 @@ class Codec final : public CodecBase {
         require_open(id);
         const auto& s = ms_[id];
         FS_REQUIRE(T >= 0 && T <= (1 << 20), "a chunk of 0 .. 2^20 frames");
-        return resample_plan_step(s.rates, s.mode, s.book, (int64_t)samples_per_frame() * T, final).n_emit;
+        int64_t n_feed = (int64_t)samples_per_frame() * T;
+        if (s.stretch && !s.tbook.final) n_feed = tsm_plan_step(TsmParams{}, s.speed, s.tbook, n_feed, final).n_emit;  // through both stages
+        return resample_plan_step(s.rates, s.mode, s.book, n_feed, final).n_emit;
     }
     void streams_decode_pcm(int n, const int* ids, const int* T, const uint8_t* final, const uint32_t* codes, void* out, size_t cap_bytes,
                             int64_t* n_out) override {
@@ -444,10 +464,13 @@ class Codec final : public CodecBase {
         FS_REQUIRE(n >= 1 && n <= kMaxStreams, "fs_codec_streams_decode_pcm takes 1 .. 64 streams per call");
         const int64_t spf = (int64_t)samples_per_frame();
         std::vector<ResampleStep> steps((size_t)n);
+        std::vector<TsmStep> tsteps((size_t)n);  // the stretch stage of the speed streams among the items; its output feeds the stage above
         std::vector<size_t> doff((size_t)n);  // byte offset of the item's row in rs_out_ (4-byte aligned; the caller's buffer is packed)
+        std::vector<size_t> toff((size_t)n), tpoff((size_t)n);  // the item's row in ts_out_ (samples) and in ts_pos_ (positions)
         std::vector<int> vid, vT;
-        int Tmax = 0;
-        size_t total_codes = 0, packed = 0, dbytes = 0;
+        int Tmax = 0, n_stretch = 0;
+        size_t total_codes = 0, packed = 0, dbytes = 0, tsamples = 0, tpositions = 0;
+        const TsmParams tp;
         for (int b = 0; b < n; ++b) {
             require_open(ids[b]);
             const auto& s = ms_[ids[b]];
@@ -457,7 +480,17 @@ class Codec final : public CodecBase {
             FS_REQUIRE(T[b] >= 0 && T[b] <= (1 << 20), "a chunk of 0 .. 2^20 frames");
             FS_REQUIRE(T[b] >= 1 || fin, "an item of 0 frames must be final (a pure flush)");
             FS_REQUIRE(!s.book.final, "the stream was already flushed by a final item (fs_codec_streams_close it)");
-            steps[(size_t)b] = resample_plan_step(s.rates, s.mode, s.book, spf * T[b], fin);
+            int64_t n_feed = spf * T[b];
+            if (s.stretch) {
+                TsmStep& ts = tsteps[(size_t)b];
+                ts = tsm_plan_step(tp, s.speed, s.tbook, n_feed, fin);
+                FS_REQUIRE(ts.carry_len <= s.tcarry_cap, "time stretch carry exceeds the stream's carry rows");
+                toff[(size_t)b] = tsamples; tsamples += (size_t)ts.n_emit;
+                tpoff[(size_t)b] = tpositions; tpositions += (size_t)(ts.k1 - ts.k0 + 1);
+                n_feed = ts.n_emit;
+                ++n_stretch;
+            }
+            steps[(size_t)b] = resample_plan_step(s.rates, s.mode, s.book, n_feed, fin);
             FS_REQUIRE(steps[(size_t)b].carry_len <= s.carry_cap, "resample carry exceeds the stream's carry rows");
             doff[(size_t)b] = dbytes;
             packed += (size_t)steps[(size_t)b].n_emit * pcm_bytes(s.format);
@@ -468,6 +501,31 @@ class Codec final : public CodecBase {
         check_codes(codes, total_codes);
         const float* d = nullptr;
         if (!vid.empty()) ragged_launch((int)vid.size(), vid.data(), vT.data(), Tmax, codes, nullptr, &d);
+        if (n_stretch) {  // one launch pair for all speed streams of the call: the vocoder's items -> ts_out_, the rows the stage below reads
+            ts_out_.ensure(std::max<size_t>(tsamples, 1) * sizeof(float));
+            ts_pos_.ensure(tpositions * sizeof(long long));
+            std::vector<TsmItem> rows;
+            int64_t vat = 0;
+            for (int b = 0; b < n; ++b) {
+                const auto& s = ms_[ids[b]];
+                const int64_t n_voc = spf * T[b];
+                if (s.stretch) {
+                    const TsmStep& ts = tsteps[(size_t)b];
+                    TsmItem it;
+                    if (n_voc) it.src = d + vat;
+                    it.in0 = ts.in0; it.n = ts.n_total;
+                    it.carry = s.trow(s.tpar); it.carry_len = (int)s.tbook.carry_len;
+                    it.carry_out = s.trow(s.tpar ^ 1); it.new_carry_len = (int)ts.carry_len;
+                    it.state = s.tstate();
+                    it.k0 = ts.k0; it.k1 = ts.k1; it.pos0 = std::max<int64_t>(ts.k0 - 1, 0); it.speed = s.speed;
+                    it.out = ts_out_.f() + toff[(size_t)b]; it.out_len = ts.n_emit;
+                    it.pos = (long long*)ts_pos_.p + tpoff[(size_t)b];
+                    rows.push_back(it);
+                }
+                vat += n_voc;
+            }
+            stretcher().run_items(rows, tp);
+        }
         rs_out_.ensure(dbytes);
         std::vector<ResampleItem> items((size_t)n);
         int64_t at = 0;
@@ -479,6 +537,7 @@ class Codec final : public CodecBase {
             it.format = s.format;
             it.in0 = p.in0; it.n_src = spf * T[b]; it.out0 = p.out0; it.n_out = p.n_emit;
             if (T[b] >= 1) { it.src = d + at; at += it.n_src; }
+            if (s.stretch) { it.n_src = tsteps[(size_t)b].n_emit; it.src = it.n_src ? ts_out_.f() + toff[(size_t)b] : nullptr; }
             if (s.carry) {
                 it.carry = s.carry->f() + (size_t)s.par * s.carry_cap; it.carry_len = (int)s.book.carry_len;
                 it.carry_out = s.carry->f() + (size_t)(s.par ^ 1) * s.carry_cap; it.new_carry_len = (int)p.carry_len;
@@ -499,6 +558,7 @@ class Codec final : public CodecBase {
             if (T[b] >= 1) ++s.chunk;
             if (s.carry) s.par ^= 1;
             resample_commit(s.book, steps[(size_t)b], final && final[b]);
+            if (s.stretch) { s.tpar ^= 1; tsm_commit(s.tbook, tsteps[(size_t)b], final && final[b]); }
         }
     }
 
@@ -1056,9 +1116,22 @@ class Codec final : public CodecBase {
         ResampleBook book;
         std::shared_ptr<DBuf> carry;
         int64_t carry_cap = 0;
+        // opened by fs_codec_streams_open_speed with speed != 1: a stretch stage in front of the stage above.  tbook: samples in, frames and
+        // samples out so far; tcarry: the position word p_{k_next - 1} (8 bytes, padded to 16), then two rows of tcarry_cap =
+        // tsm_carry_bound samples, row `tpar` holds the tbook.carry_len samples in front of the next chunk
+        bool stretch = false;
+        double speed = 1.0;
+        TsmBook tbook;
+        std::shared_ptr<DBuf> tcarry;
+        int64_t tcarry_cap = 0;
+        int tpar = 0;
+        long long* tstate() const { return (long long*)tcarry->p; }
+        float* trow(int half) const { return (float*)((uint8_t*)tcarry->p + 16) + (size_t)half * (size_t)tcarry_cap; }
     };
     static constexpr const char* kSpecStreamMsg =
         "the stream was opened with a PCM spec (fs_codec_streams_open_pcm): decode it with fs_codec_streams_decode_pcm";
+    static constexpr const char* kSpeedStreamMsg =
+        "the stream was opened with a speed (fs_codec_streams_open_speed): decode it with fs_codec_streams_decode_pcm";
     std::unique_ptr<Resampler> rs_;                // made on first use, on st_
     DBuf rs_out_, rs_mix_;                         // the resampled rows of a call; the downmixed clip of fs_codec_encode_pcm
     std::vector<uint8_t> rs_host_;                 // host side of rs_out_ (rows at 4-byte aligned offsets), unpacked into the caller's buffer
@@ -1210,6 +1283,80 @@ void time_stretch_rows(int device, const float* pcm, int b, size_t stride, const
         }
         FS_HIP(hipStreamSynchronize(st.s));
     }
+}
+
+// fs_selftest_tsm_chunks (include/fishrt.h): what a speed stream does to its vocoder PCM, on a host row and without a codec: per chunk one
+// plan step (fs_tsm_plan.h), one item, one launch pair, with the carry rows and the position word a stream owns.  Every chunk is uploaded into
+// the same buffer, filled with 0xFF (NaN) first: a sample of an earlier chunk can only come from the carry.
+void time_stretch_chunks(int device, const float* pcm, int64_t n, const int64_t* chunks, int n_chunks, double speed, const int* params2, float* out,
+                         size_t out_cap, int64_t* out_len, int64_t* emitted, int64_t* positions, size_t pos_cap, int64_t* n_pos) {
+    FS_REQUIRE(n_chunks >= 1 && n_chunks <= (1 << 20), "fs_selftest_tsm_chunks takes 1 .. 2^20 chunks");
+    FS_REQUIRE(n >= 0 && n < (1ll << 31), "fs_selftest_tsm_chunks: the row's length");
+    tsm_require_speed(speed);
+    TsmParams tp;
+    if (params2) { tp.N = params2[0]; tp.D = params2[1]; }
+    tsm_require_params(tp);
+    int64_t sum = 0, longest = 0;
+    for (int c = 0; c < n_chunks; ++c) {
+        FS_REQUIRE(chunks[c] >= 0 && chunks[c] <= n, "fs_selftest_tsm_chunks: a chunk's length");
+        sum += chunks[c];
+        longest = std::max(longest, chunks[c]);
+    }
+    FS_REQUIRE(sum == n, "fs_selftest_tsm_chunks: the chunk lengths must add up to the row's length");
+    const int64_t ol = tsm_out_len(n, speed), K = tsm_frames(ol, tp), cap = tsm_carry_bound(tp, speed);
+    FS_REQUIRE((size_t)ol <= out_cap, "fs_selftest_tsm_chunks: out_cap is smaller than fs_time_stretch_out_len of the row");
+    FS_REQUIRE(!positions || (size_t)K <= pos_cap, "fs_selftest_tsm_chunks: pos_cap is smaller than the frame count of the row");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw Error("no HIP device visible: libfishrt has no CPU fallback (MI355X / gfx950 required)");
+    FS_REQUIRE(device >= 0 && device < ndev, "device_id out of range");
+    FS_HIP(hipSetDevice(device));
+    struct Stream {
+        hipStream_t s = nullptr;
+        ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+    } st;
+    FS_HIP(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    DBuf dchunk, dcarry, dout, dpos;
+    dchunk.alloc(std::max<int64_t>(longest, 1) * sizeof(float));
+    dcarry.alloc(16 + (size_t)2 * cap * sizeof(float));
+    dout.alloc(std::max<int64_t>(ol, 1) * sizeof(float));
+    dpos.alloc((size_t)(K + 1) * sizeof(long long));
+    FS_HIP(hipMemsetAsync(dcarry.p, 0, 16, st.s));
+    float* rows = (float*)((uint8_t*)dcarry.p + 16);
+    {
+        TimeStretcher ts(st.s);
+        TsmBook book;
+        int par = 0;
+        int64_t at = 0;
+        for (int c = 0; c < n_chunks; ++c) {
+            const bool fin = c + 1 == n_chunks;
+            const TsmStep s = tsm_plan_step(tp, speed, book, chunks[c], fin);
+            FS_REQUIRE(s.carry_len <= cap, "time stretch carry exceeds the carry rows");
+            FS_HIP(hipMemsetAsync(dchunk.p, 0xFF, dchunk.n, st.s));
+            if (chunks[c]) FS_HIP(hipMemcpyAsync(dchunk.p, pcm + at, (size_t)chunks[c] * sizeof(float), hipMemcpyHostToDevice, st.s));
+            std::vector<TsmItem> items(1);
+            TsmItem& it = items[0];
+            if (chunks[c]) it.src = dchunk.f();
+            it.in0 = s.in0; it.n = s.n_total;
+            it.carry = rows + (size_t)par * cap; it.carry_len = (int)book.carry_len;
+            it.carry_out = rows + (size_t)(par ^ 1) * cap; it.new_carry_len = (int)s.carry_len;
+            it.state = (long long*)dcarry.p;
+            it.k0 = s.k0; it.k1 = s.k1; it.pos0 = std::max<int64_t>(s.k0 - 1, 0); it.speed = speed;
+            it.out = dout.f(); it.out_len = s.n_emit;
+            it.pos = (long long*)dpos.p;
+            ts.run_items(items, tp);
+            if (s.n_emit) FS_HIP(hipMemcpyAsync(out + s.out0, dout.p, (size_t)s.n_emit * sizeof(float), hipMemcpyDeviceToHost, st.s));
+            if (positions && s.k1 > s.k0)
+                FS_HIP(hipMemcpyAsync(positions + s.k0, (const long long*)dpos.p + (s.k0 - it.pos0), (size_t)(s.k1 - s.k0) * sizeof(int64_t), hipMemcpyDeviceToHost, st.s));
+            FS_HIP(hipStreamSynchronize(st.s));  // (the next chunk overwrites dchunk, dout and dpos)
+            emitted[c] = s.n_emit;
+            at += chunks[c];
+            par ^= 1;
+            tsm_commit(book, s, fin);
+        }
+        FS_REQUIRE(book.n_out == ol && book.k_next == K, "time stretch stream: the emitted totals");
+    }
+    *out_len = ol;
+    if (n_pos) *n_pos = K;
 }
 
 // fs_selftest_conv1d (include/fishrt.h): one conv through the load-time functions (re-layout, pack), the plane producers and ONE launcher of

@@ -456,6 +456,17 @@ int fs_codec_decode_speed(fs_codec_t* c, const uint32_t* codes, int b, int T, do
     FS_ARG(c && codes && spec && out && n_out, "null argument");
     FS_TRY(c->impl->decode_speed(codes, b, T, speed, &spec->rate, out, cap, n_out))
 }
+int fs_codec_streams_open_speed(fs_codec_t* c, double speed, const fs_pcm_spec* spec, int* stream_id) {
+    FS_ARG(c && stream_id, "null argument");
+    FS_TRY(*stream_id = c->impl->streams_open_speed(speed, spec ? &spec->rate : nullptr))
+}
+int fs_selftest_tsm_chunks(int device_id, const float* pcm, int64_t n, const int64_t* chunk_len, int n_chunks, double speed,
+                           const fs_tsm_params* params, float* out, size_t out_cap, int64_t* out_len, int64_t* emitted, int64_t* positions,
+                           size_t pos_cap, int64_t* n_positions) {
+    FS_ARG((pcm || n == 0) && chunk_len && out && out_len && emitted, "null argument");
+    FS_TRY(fs::time_stretch_chunks(device_id, pcm, n, chunk_len, n_chunks, speed, params ? &params->frame : nullptr, out, out_cap, out_len, emitted,
+                                   positions, pos_cap, n_positions))
+}
 int fs_codec_streams_open_pcm(fs_codec_t* c, const fs_pcm_spec* spec, int* stream_id) {
     FS_ARG(c && spec && stream_id, "null argument");
     FS_TRY(*stream_id = c->impl->streams_open_pcm(&spec->rate))

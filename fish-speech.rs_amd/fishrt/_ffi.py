@@ -95,6 +95,7 @@ SYMBOLS = ["fs_last_error", "fs_version", "fs_device_count", "fs_lm_create", "fs
            "fs_resample_out_len", "fs_resample", "fs_codec_decode_pcm", "fs_codec_streams_open_pcm", "fs_codec_streams_pending",
            "fs_codec_streams_decode_pcm", "fs_codec_encode_pcm",
            "fs_time_stretch_out_len", "fs_time_stretch", "fs_codec_decode_speed",
+           "fs_codec_streams_open_speed", "fs_selftest_tsm_chunks",
            "fs_fp8_quantize_rows", "fs_fp8_decode_table", "fs_selftest", "fs_lm_selftest", "fs_selftest_sample_rows", "fs_selftest_sample_slots", "fs_lm_debug_capture", "fs_lm_debug_read"]
 
 # flags of fs_lm_generate* / fs_lm_session_begin (include/fishrt.h)
@@ -205,6 +206,9 @@ TSM_PROTOTYPES = {
     "fs_time_stretch_out_len": [C.c_int64, C.c_double, _I64P],
     "fs_time_stretch": [C.c_int, _F32P, C.c_int, C.c_size_t, _I64P, C.c_double, C.POINTER(TsmParams), _F32P, C.c_size_t, _I64P, _I64P, C.c_size_t],
     "fs_codec_decode_speed": [C.c_void_p, _U32P, C.c_int, C.c_int, C.c_double, C.POINTER(PcmSpec), C.c_void_p, C.c_size_t, _I64P],
+    "fs_codec_streams_open_speed": [C.c_void_p, C.c_double, C.POINTER(PcmSpec), C.POINTER(C.c_int)],
+    "fs_selftest_tsm_chunks": [C.c_int, _F32P, C.c_int64, _I64P, C.c_int, C.c_double, C.POINTER(TsmParams), _F32P, C.c_size_t, _I64P, _I64P, _I64P,
+                               C.c_size_t, _I64P],
 }
 
 _lib = None

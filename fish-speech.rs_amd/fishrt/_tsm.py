@@ -59,3 +59,26 @@ def time_stretch(pcm, speed, return_positions=False, lengths=None, frame=None, r
         return y
     p = pos[:, : frames[0]]
     return y, (p[0].copy() if one else np.ascontiguousarray(p))
+
+
+def time_stretch_chunks(pcm, chunk_lens, speed, frame=None, radius=None, device=0):
+    """the test hook of the chunked stretch (fishrt.h fs_selftest_tsm_chunks): pcm f32 (n,) cut into consecutive chunks of chunk_lens samples
+    (they add up to n; the last one is the final item and may be 0), one plan step and one launch pair per chunk, the state a speed stream
+    keeps carried between them -> (y f32 (out_len,), emitted int64 (len(chunk_lens),), positions int64 (K,))"""
+    params = None
+    if frame is not None or radius is not None:
+        params = _ffi.TsmParams(FRAME if frame is None else int(frame), RADIUS if radius is None else int(radius))
+    hs = (FRAME if frame is None else int(frame)) // 2
+    x = np.ascontiguousarray(pcm, np.float32).reshape(-1)
+    lens = np.ascontiguousarray(np.asarray(chunk_lens, np.int64).reshape(-1))
+    cap = max(1, time_stretch_out_len(x.shape[0], speed))
+    pcap = max(1, -(-cap // max(hs, 1)))
+    out, emitted, pos = np.zeros(cap, np.float32), np.zeros(max(1, lens.shape[0]), np.int64), np.zeros(pcap, np.int64)
+    n_out, n_pos = C.c_int64(0), C.c_int64(0)
+    xs = x if x.shape[0] else np.zeros(1, np.float32)
+    _ffi.check(_ffi.lib().fs_selftest_tsm_chunks(int(device), xs.ctypes.data_as(C.POINTER(C.c_float)), C.c_int64(x.shape[0]),
+                                                 lens.ctypes.data_as(C.POINTER(C.c_int64)), int(lens.shape[0]), C.c_double(float(speed)),
+                                                 C.byref(params) if params is not None else None, out.ctypes.data_as(C.POINTER(C.c_float)),
+                                                 C.c_size_t(cap), C.byref(n_out), emitted.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                 pos.ctypes.data_as(C.POINTER(C.c_int64)), C.c_size_t(pcap), C.byref(n_pos)))
+    return out[: n_out.value].copy(), emitted[: lens.shape[0]].copy(), pos[: n_pos.value].copy()

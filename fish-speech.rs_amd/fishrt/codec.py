@@ -124,17 +124,23 @@ class FireflyCodec:
     # ---- many concurrent streams on one handle (fishrt.h fs_codec_streams_*): one launch sequence advances n streams by T frames each
     STREAMS_MAX = 64
 
-    def streams_open(self, sample_rate=None, resample="linear", dtype="f32"):
+    def streams_open(self, sample_rate=None, resample="linear", dtype="f32", speed=None):
         """-> stream id: a new stream from zero left context, in the handle's current precision mode.  sample_rate / dtype: its PCM leaves
-        converted on the device (fishrt.h fs_codec_streams_open_pcm); such a stream is decoded by streams_decode_ragged only"""
+        converted on the device (fishrt.h fs_codec_streams_open_pcm); such a stream is decoded by streams_decode_ragged only.
+        speed (0.25 .. 4.0; None = no stretch stage): its PCM is time-stretched on the device first, chunk by chunk (fishrt.h
+        fs_codec_streams_open_speed), before sample_rate / dtype apply; decoded by streams_decode_ragged only, with a final flag on its last
+        item.  Its pieces concatenated equal decode(..., speed=) of the whole sequence bit for bit."""
         sid = C.c_int(-1)
         spec = self._spec(sample_rate, resample, dtype)
-        if spec is None:
+        if speed is not None:
+            _ffi.check(_ffi.lib().fs_codec_streams_open_speed(self._h, C.c_double(float(speed)), C.byref(spec) if spec is not None else None,
+                                                              C.byref(sid)))
+        elif spec is None:
             _ffi.check(_ffi.lib().fs_codec_streams_open(self._h, C.byref(sid)))
         else:
             _ffi.check(_ffi.lib().fs_codec_streams_open_pcm(self._h, C.byref(spec), C.byref(sid)))
         self._dtypes().pop(int(sid.value), None)
-        if spec is not None:
+        if spec is not None or speed is not None:  # (a speed stream goes through fs_codec_streams_decode_pcm whatever its dtype)
             self._dtypes()[int(sid.value)] = dtype
         return int(sid.value)
 

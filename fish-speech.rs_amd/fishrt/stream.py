@@ -172,12 +172,20 @@ class SessionStreamer:
     work for 95 frames of audio.  Chunk sizes near each other keep that waste small; the one-call rule holds whatever the mix."""
 
     def __init__(self, session, codec, chunk=64, first_chunk=32, halo=HALO, on_audio=None, clock=time.perf_counter, ragged=False,
-                 sample_rate=None, resample="sinc", pcm_dtype="f32"):
+                 sample_rate=None, resample="sinc", pcm_dtype="f32", speed=None):
         """sample_rate / pcm_dtype (ragged=True only): every request's stream is opened with that PCM spec (FireflyCodec.streams_open), so
         its pieces arrive at sample_rate Hz as f32 or int16, converted on the device by `resample` ("sinc" or "linear").  Every item carries
         its final flag: a piece holds the samples whose input exists, so pieces vary in length (the first one of a sinc stream is short),
         and a finished request with no frames left still gets a flush item, which delivers the samples held back.  Per request the pieces
-        concatenated equal codec.decode(final codes, sample_rate=, resample=, dtype=), bit for bit.  stats[tag]["samples"] counts them."""
+        concatenated equal codec.decode(final codes, sample_rate=, resample=, dtype=), bit for bit.  stats[tag]["samples"] counts them.
+        speed (ragged=True only; 0.25 .. 4.0, None = none): the default speed of every request; add(speed=) sets a request's own.  Such a
+        request's stream time-stretches its PCM on the device chunk by chunk (FireflyCodec.streams_open(speed=)), before sample_rate /
+        pcm_dtype apply: a piece holds the whole stretch frames whose input exists (the first pieces of a request may be empty), the
+        finished request always gets its flush item, and per request the pieces concatenated equal codec.decode(final codes, speed=,
+        sample_rate=, resample=, dtype=), bit for bit."""
+        if speed is not None and not ragged:
+            raise ValueError("speed needs ragged=True (the uniform vocoder calls return f32 at the codec rate)")
+        self.speed = speed
         self.pcm_spec = None
         if sample_rate is not None or pcm_dtype != "f32":
             if not ragged:
@@ -202,15 +210,22 @@ class SessionStreamer:
     def __exit__(self, *exc):
         self.close()
 
-    def add(self, prompt, max_new_tokens, tag=None, prefix=None, sampling=None, seed=None):
+    def add(self, prompt, max_new_tokens, tag=None, prefix=None, sampling=None, seed=None, speed=None):
         """admit a request: -> its session slot, or None when the session is full (nothing is opened then).  tag: the name its audio and
         stats are reported under (default: the admission number 0, 1, 2, ...).  prefix: a Session.add_prefix id -- `prompt` is then the
-        request's body (Session.add).  sampling / seed: the request's own sampler settings / seed (Session.add; per_slot and rows sessions)"""
+        request's body (Session.add).  sampling / seed: the request's own sampler settings / seed (Session.add; per_slot and rows sessions).  speed: the request's own speed (ragged=True only; None: the streamer's default)"""
+        if speed is not None and not self.ragged:
+            raise ValueError("speed needs ragged=True (the uniform vocoder calls return f32 at the codec rate)")
+        if speed is None:
+            speed = self.speed
         if tag is None:
             tag = self._admitted
         if tag in self.stats:
             raise ValueError(f"tag {tag!r} is already in use")
-        sid = self.codec.streams_open(**self.pcm_spec) if self.pcm_spec else self.codec.streams_open()
+        okw = dict(self.pcm_spec) if self.pcm_spec else {}
+        if speed is not None:
+            okw["speed"] = speed
+        sid = self.codec.streams_open(**okw)
         try:
             kw = {}
             if prefix is not None:
@@ -227,7 +242,7 @@ class SessionStreamer:
             self.codec.streams_close(sid)
             return None
         self._admitted += 1
-        self.live[slot] = dict(tag=tag, sid=sid, done_upto=0, t_add=self.clock())
+        self.live[slot] = dict(tag=tag, sid=sid, done_upto=0, t_add=self.clock(), flush=bool(self.pcm_spec) or speed is not None)
         self.stats[tag] = dict(frames=0, first_audio_s=None, vocoder_s=0.0, chunks=0, samples=0)
         return slot
 
@@ -270,7 +285,7 @@ class SessionStreamer:
             left = n - r["done_upto"]
             if done:
                 finished.append(slot)
-                if left > 0 or self.pcm_spec:  # (a spec stream holds samples back until its final item: flush it even with no frames left)
+                if left > 0 or r["flush"]:  # (a spec or speed stream holds samples back until its final item: flush it even with no frames left)
                     due.append((slot, left, True))
                 continue
             T = self.first_chunk if r["done_upto"] == 0 else self.chunk
@@ -284,7 +299,7 @@ class SessionStreamer:
                     a = self.live[slot]["done_upto"]
                     chunks.append(np.ascontiguousarray(self._codes(slot)[:, a:a + T]))
                 t1 = self.clock()
-                if self.pcm_spec:
+                if self.pcm_spec or any(self.live[s]["flush"] for s, _, _ in due):
                     pcm = self.codec.streams_decode_ragged([self.live[s]["sid"] for s, _, _ in due], chunks, final=[f for _, _, f in due])
                 else:
                     pcm = self.codec.streams_decode_ragged([self.live[s]["sid"] for s, _, _ in due], chunks)

@@ -947,7 +947,8 @@ int fs_codec_streams_open_pcm(fs_codec_t* c, const fs_pcm_spec* spec, int* strea
 /* samples the next fs_codec_streams_decode_pcm item of T frames (final or not) would emit for this stream; changes nothing */
 int fs_codec_streams_pending(fs_codec_t* c, int stream_id, int T, int final, int64_t* n_out);
 /* fs_codec_streams_decode_ragged with a `final` flag per item (final == NULL: none) and every item's PCM converted by its stream's spec before
- * the copy to the host.  Streams opened either way are accepted: one from fs_codec_streams_open is codec rate, f32.  out: the items' outputs
+ * the copy to the host.  Streams opened any way are accepted: one from fs_codec_streams_open is codec rate, f32; one from
+ * fs_codec_streams_open_speed (below) has a stretch stage in front of its conversion.  out: the items' outputs
  * concatenated in item order, each in its stream's format (so an f32 item may start at an odd 2-byte offset: copy it out before use);
  * n_out[i] = samples of item i.  A stream emits an output sample once all the input it reads exists -- linear: ceil(i / ratio) <= N - 1 after
  * N input samples, sinc: whole blocks of p outputs whose last tap lies inside the input -- and the rest, with the reference's clamp and the
@@ -986,8 +987,22 @@ int fs_codec_encode_pcm(fs_codec_t* c, const float* pcm, int channels, int64_t f
  *   picks d = 0.  A signal that repeats bit for bit with an integer period P makes e[d] == e[d + P] bitwise -- every lag runs the same
  *   operations in the same order, which is why the order is fixed -- so there the tie rule decides.
  * In the fs_codec_* calls speed == 1.0 means "no stretch stage", as a spec at the codec's rate means no resample stage; fs_time_stretch follows
- * the definition to the letter, 1.0 included.  Multi-streams (fs_codec_streams_*) do not stretch: a chunked stretch has to carry a position
- * and a template from chunk to chunk, and is left to a change of its own. */
+ * the definition to the letter, 1.0 included.
+ *
+ * Streams (fs_codec_streams_open_speed below).  The definition above stays the definition; a stream only adds WHEN a frame may be emitted, as
+ * a function of n, the input samples it has seen so far.  With hi_k = lo_k = 0 for k == 0, else hi_k = q_k + D and lo_k = q_k - D, frame k --
+ * output samples [k Hs, (k + 1) Hs) -- is emittable at n before the final item if and only if
+ *     (k + 1) Hs <= out_len(n)                  it is a whole frame of whatever the final length turns out to be;
+ *     k == 0:  Hs <= n;
+ *     k >= 1:  q_k + D + N <= n                 the search region lies inside the input,
+ *              hi_{k-1} + Hs + N <= n           and so does the template, wherever p_{k-1} was placed (the host does not know).
+ *   A call emits the longest prefix of the frames not yet emitted that are emittable at its new n (emittability is monotone in k).  The final
+ *   item emits every remaining frame up to K = ceil(out_len(n) / Hs), the last one cut at out_len(n), with x zero from n on as above; a final
+ *   item of a stream that never saw a sample emits nothing.  At the defaults a frame waits for D + N = 1536 input samples beyond its nominal position.
+ * Between calls a stream keeps p of its last frame (one int64 on the device) and the input the frames not yet emitted may still read: with k
+ *   the next such frame, everything from max(0, min(lo_k, lo_{k-1} + Hs)) up to n.  That is fewer than
+ *     ceil(max(g + 1, D + N, D + N + Hs - g + 1)) + ceil(max(D, g + 1 + D - Hs)),  g = Hs * speed
+ *   samples whatever the chunk lengths (derived in csrc/fs_tsm_plan.h): at the defaults 4098 at speed 4.0, 2433 at speed 0.25. */
 typedef struct fs_tsm_params {
     int32_t frame /* N */, radius /* D */;
 } fs_tsm_params;
@@ -1005,6 +1020,26 @@ int fs_time_stretch(int device_id, const float* pcm, int b, size_t stride, const
  * (at the codec's own rate: the format conversion of fs_time_stretch's rows); with speed == 1.0 it is fs_codec_decode_pcm. */
 int fs_codec_decode_speed(fs_codec_t* c, const uint32_t* codes, int b, int T, double speed, const fs_pcm_spec* spec, void* out,
                           size_t cap /* elements per row */, int64_t* n_out);
+/* A multi-stream with a stretch stage (the defaults) between the vocoder and the stream's resample / format stage: the `speed` of a request
+ * that streams.  spec == NULL: codec rate, f32.  speed == 1.0 means no stretch stage: the stream is then what fs_codec_streams_open_pcm (or,
+ * with spec == NULL, fs_codec_streams_open) returns.  On top of what such a stream owns, a speed stream owns two stretch carry rows of the
+ * bound above (2 x 16 KB at speed 4.0) and the position word on the device, and its frame and sample counters on the host.  It is decoded by
+ * fs_codec_streams_decode_pcm, in any mix with plain and PCM streams; all speed streams of a call share one pair of stretch launches.  An
+ * item's vocoder PCM goes through the stretch stage, which emits by the rule above; what that emits is fed, with the item's final flag, to the
+ * stream's resample / format stage, which emits by its own rule.  fs_codec_streams_pending counts through both stages.  Per stream, the
+ * outputs of all its calls concatenated equal fs_codec_decode_speed of the whole sequence at b = 1, bit for bit, whatever the chunk lengths,
+ * the other items or their order.  speed and spec are checked here; fs_codec_streams_decode and fs_codec_streams_decode_ragged refuse a speed
+ * stream.  A failed fs_codec_streams_decode_pcm call leaves the stretch counters, the carry rows' parity and the position word untouched too. */
+int fs_codec_streams_open_speed(fs_codec_t* c, double speed, const fs_pcm_spec* spec /* nullable */, int* stream_id);
+/* Test hook, no codec handle: the chunked stretch of ONE row.  pcm: n samples, cut into n_chunks consecutive chunks of chunk_len[i] >= 0
+ * samples that add up to n; the last chunk is the final item (it may be empty: a pure flush).  Per chunk one plan step, one item and one
+ * launch pair, with the two carry rows and the position word a speed stream owns; every chunk is uploaded on its own into poisoned storage,
+ * so an earlier sample can only come from the carry.  out: the emitted samples concatenated, *out_len of them (out_cap must hold
+ * fs_time_stretch_out_len); emitted[i]: samples chunk i emitted; positions (nullable): p_0 .. p_{K-1}, *n_positions = K (pos_cap must hold
+ * K).  params == NULL: the defaults. */
+int fs_selftest_tsm_chunks(int device_id, const float* pcm, int64_t n, const int64_t* chunk_len, int n_chunks, double speed,
+                           const fs_tsm_params* params, float* out, size_t out_cap, int64_t* out_len, int64_t* emitted /* [n_chunks] */,
+                           int64_t* positions, size_t pos_cap, int64_t* n_positions /* nullable */);
 
 #ifdef __cplusplus
 }
