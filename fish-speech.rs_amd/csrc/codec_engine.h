@@ -29,6 +29,10 @@ class CodecBase {
     virtual void decode_pcm(const uint32_t* codes, int b, int T, const int* spec3, void* out, size_t cap, int64_t* n_out) = 0;
     // fs_codec_decode_speed: the rows time-stretched (codec_tsm.hip, default parameters) between the vocoder and the stage above
     virtual void decode_speed(const uint32_t* codes, int b, int T, double speed, const int* spec3, void* out, size_t cap, int64_t* n_out) = 0;
+    // fs_codec_decode_loud: the rows measured and scaled (codec_loud.hip) between the vocoder and the stretch stage.  loud3 = {target_lufs,
+    // peak_db, max_gain_db} or null (then it is decode_speed); res24 = b fs_loud_result records or null
+    virtual void decode_loud(const uint32_t* codes, int b, int T, const double* loud3, double speed, const int* spec3, void* out, size_t cap,
+                             int64_t* n_out, void* res24) = 0;
     virtual int streams_open_pcm(const int* spec3) = 0;
     // fs_codec_streams_open_speed: a stream with a stretch stage between the vocoder and its resample / format stage; spec3 null = codec rate, f32
     virtual int streams_open_speed(double speed, const int* spec3) = 0;
@@ -60,6 +64,11 @@ void resample_rows(int device, const float* pcm, int b, size_t stride, const int
 // fs_time_stretch: b host rows of their own lengths, host -> device -> host, no codec handle; params2 = {frame, radius} or null
 void time_stretch_rows(int device, const float* pcm, int b, size_t stride, const int64_t* n_samples, double speed, const int* params2, float* out,
                        size_t out_stride, int64_t* out_len, int64_t* positions, size_t pos_stride);
+
+// fs_loudness_normalize: b host rows of their own lengths, host -> device -> host, no codec handle; loud3 as above or null (measure only, out
+// null too), out null = measure only; res24 = b fs_loud_result records.  hops (nullable, b == 1): the row's hop energies s_i
+void loudness_rows(int device, const float* pcm, int b, size_t stride, const int64_t* n_samples, int rate, const double* loud3, float* out,
+                   size_t out_stride, void* res24, double* hops, size_t hops_cap, int64_t* n_hops);
 
 // fs_selftest_tsm_chunks: one host row through the chunked stretch, one launch pair per chunk (the last chunk is final); params2 as above
 void time_stretch_chunks(int device, const float* pcm, int64_t n, const int64_t* chunks, int n_chunks, double speed, const int* params2, float* out,

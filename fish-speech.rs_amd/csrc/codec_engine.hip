@@ -17,6 +17,7 @@
 #include "../../include/fishrt.h"
 #include "codec_kernels.h"
 #include "codec_resample.h"
+#include "codec_loud.h"
 #include "codec_tsm.h"
 #include "fs_common.h"
 #include "fs_synth.h"
@@ -371,8 +372,22 @@ class Codec final : public CodecBase {
         decode_pcm_speed(codes, B, T, speed, spec3, out, cap, n_out,
                          "fs_codec_decode_speed: cap is smaller than fs_resample_out_len of fs_time_stretch_out_len of a row");
     }
+    // loud3 null: fs_codec_decode_speed.  Everything is checked before the vocoder runs
+    void decode_loud(const uint32_t* codes, int B, int T, const double* loud3, double speed, const int* spec3, void* out, size_t cap,
+                     int64_t* n_out, void* res24) override {
+        tsm_require_speed(speed);
+        LoudParams lp;
+        if (loud3) {
+            lp.target_lufs = loud3[0]; lp.peak_db = loud3[1]; lp.max_gain_db = loud3[2];
+            loud_require_params(lp);
+            loud_require_rate(sample_rate());
+        }
+        decode_pcm_speed(codes, B, T, speed, spec3, out, cap, n_out,
+                         "fs_codec_decode_loud: cap is smaller than fs_resample_out_len of fs_time_stretch_out_len of a row", loud3 ? &lp : nullptr,
+                         loud3 ? res24 : nullptr);
+    }
     void decode_pcm_speed(const uint32_t* codes, int B, int T, double speed, const int* spec3, void* out, size_t cap, int64_t* n_out,
-                          const char* cap_msg) {
+                          const char* cap_msg, const LoudParams* lp = nullptr, void* res24 = nullptr) {
         FS_HIP(hipSetDevice(device_));
         FS_REQUIRE(B >= 1 && T >= 1, "empty input");
         int mode, format;
@@ -385,7 +400,18 @@ class Codec final : public CodecBase {
         FS_REQUIRE((int64_t)cap >= ol, cap_msg);
         const float* d = nullptr;
         decode_impl(codes, B, T, nullptr, kOneShot, &d);
-        if (stretch) {  // the vocoder's rows -> ts_out_, the rows the stage below reads
+        if (lp) {  // the vocoder's rows, scaled -> ld_out_, the rows the stages below read
+            ld_out_.ensure((size_t)B * (size_t)n_voc * sizeof(float));
+            std::vector<LoudItem> rows((size_t)B);
+            for (int b = 0; b < B; ++b) {
+                rows[(size_t)b].src = d + (size_t)b * n_voc; rows[(size_t)b].n = n_voc;
+                rows[(size_t)b].out = ld_out_.f() + (size_t)b * n_voc;
+            }
+            loudness().run(rows, sample_rate(), lp);
+            if (res24) FS_HIP(hipMemcpyAsync(res24, loudness().results(), (size_t)B * sizeof(LoudResult), hipMemcpyDeviceToHost, st_));
+            d = ld_out_.f();
+        }
+        if (stretch) {  // those rows -> ts_out_, the rows the stage below reads
             const int64_t K = tsm_frames(n_in, tp);
             ts_out_.ensure((size_t)B * std::max<int64_t>(n_in, 1) * sizeof(float));
             ts_pos_.ensure((size_t)B * std::max<int64_t>(K, 1) * sizeof(long long));
@@ -1139,6 +1165,9 @@ class Codec final : public CodecBase {
     std::unique_ptr<TimeStretcher> ts_;            // made on first use, on st_ (fs_codec_decode_speed)
     DBuf ts_out_, ts_pos_;                         // the stretched rows of a call and their frame positions
     TimeStretcher& stretcher() { if (!ts_) ts_.reset(new TimeStretcher(st_)); return *ts_; }
+    std::unique_ptr<Loudness> ld_;                 // made on first use, on st_ (fs_codec_decode_loud)
+    DBuf ld_out_;                                  // the scaled rows of a call
+    Loudness& loudness() { if (!ld_) ld_.reset(new Loudness(st_)); return *ld_; }
     std::vector<MStream> ms_;                      // fs_codec_streams_*, index = stream id
     int ms_cap_ = 0;                               // streams the pools hold
     DBuf mpool_p_, mpool_f_, dtab_;                // context pools [stream][half][...] and the per-call device offset table
@@ -1357,6 +1386,62 @@ void time_stretch_chunks(int device, const float* pcm, int64_t n, const int64_t*
     }
     *out_len = ol;
     if (n_pos) *n_pos = K;
+}
+
+// fs_loudness_normalize (include/fishrt.h): the rows go to the device, through the launches of codec_loud.hip, and back
+void loudness_rows(int device, const float* pcm, int b, size_t stride, const int64_t* n_samples, int rate, const double* loud3, float* out,
+                   size_t out_stride, void* res24, double* hops, size_t hops_cap, int64_t* n_hops) {
+    FS_REQUIRE(b >= 1 && b <= 4096, "fs_loudness_normalize takes 1 .. 4096 rows");
+    loud_require_rate(rate);
+    LoudParams lp;
+    if (loud3) {
+        lp.target_lufs = loud3[0]; lp.peak_db = loud3[1]; lp.max_gain_db = loud3[2];
+        loud_require_params(lp);
+    }
+    FS_REQUIRE(loud3 || !out, "fs_loudness_normalize: an output needs params");
+    FS_REQUIRE(!hops || b == 1, "the hop energies are read one row at a time");
+    std::vector<size_t> off((size_t)b);
+    size_t elems = 0;
+    for (int i = 0; i < b; ++i) {
+        FS_REQUIRE(n_samples[i] >= 0 && (size_t)n_samples[i] <= stride && n_samples[i] <= kLoudMaxSamples,
+                   "fs_loudness_normalize: a row's length must be in 0 .. stride and at most 2^30");
+        FS_REQUIRE(!out || (size_t)n_samples[i] <= out_stride, "fs_loudness_normalize: out_stride is smaller than a row");
+        off[(size_t)i] = elems; elems += (size_t)n_samples[i];
+    }
+    FS_REQUIRE(!hops || (size_t)loud_hops(n_samples[0], rate) <= hops_cap, "the hop energies do not fit");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw Error("no HIP device visible: libfishrt has no CPU fallback (MI355X / gfx950 required)");
+    FS_REQUIRE(device >= 0 && device < ndev, "device_id out of range");
+    FS_HIP(hipSetDevice(device));
+    struct Stream {
+        hipStream_t s = nullptr;
+        ~Stream() { if (s) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } }
+    } st;
+    FS_HIP(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking));
+    DBuf din, dout;
+    din.alloc(std::max<size_t>(elems, 1) * sizeof(float));
+    if (out) dout.alloc(std::max<size_t>(elems, 1) * sizeof(float));
+    {
+        Loudness ld(st.s);
+        std::vector<LoudItem> items((size_t)b);
+        for (int i = 0; i < b; ++i) {
+            LoudItem& it = items[(size_t)i];
+            if (n_samples[i])
+                FS_HIP(hipMemcpyAsync(din.f() + off[(size_t)i], pcm + (size_t)i * stride, (size_t)n_samples[i] * sizeof(float), hipMemcpyHostToDevice, st.s));
+            it.src = din.f() + off[(size_t)i]; it.n = n_samples[i];
+            it.out = out ? dout.f() + off[(size_t)i] : nullptr;
+        }
+        ld.run(items, rate, loud3 ? &lp : nullptr);
+        FS_HIP(hipMemcpyAsync(res24, ld.results(), (size_t)b * sizeof(LoudResult), hipMemcpyDeviceToHost, st.s));
+        for (int i = 0; out && i < b; ++i)
+            if (n_samples[i])
+                FS_HIP(hipMemcpyAsync(out + (size_t)i * out_stride, dout.f() + off[(size_t)i], (size_t)n_samples[i] * sizeof(float), hipMemcpyDeviceToHost, st.s));
+        if (hops) {
+            if (ld.n_hops(0)) FS_HIP(hipMemcpyAsync(hops, ld.hops(0), (size_t)ld.n_hops(0) * sizeof(double), hipMemcpyDeviceToHost, st.s));
+            if (n_hops) *n_hops = ld.n_hops(0);
+        }
+        FS_HIP(hipStreamSynchronize(st.s));
+    }
 }
 
 // fs_selftest_conv1d (include/fishrt.h): one conv through the load-time functions (re-layout, pack), the plane producers and ONE launcher of

@@ -8,6 +8,7 @@
 #include "fs_comm.h"
 #include "fs_common.h"
 #include "fs_resample_plan.h"
+#include "fs_loud_plan.h"
 #include "fs_tsm_plan.h"
 #include "lm_engine.h"
 #include "lm_kernels.h"
@@ -466,6 +467,25 @@ int fs_selftest_tsm_chunks(int device_id, const float* pcm, int64_t n, const int
     FS_ARG((pcm || n == 0) && chunk_len && out && out_len && emitted, "null argument");
     FS_TRY(fs::time_stretch_chunks(device_id, pcm, n, chunk_len, n_chunks, speed, params ? &params->frame : nullptr, out, out_cap, out_len, emitted,
                                    positions, pos_cap, n_positions))
+}
+static_assert(sizeof(fs_loud_params) == 3 * sizeof(double), "fs_loud_params is passed to the engine as double[3]");
+static_assert(sizeof(fs_loud_result) == sizeof(fs::LoudResult) && offsetof(fs_loud_result, gain) == offsetof(fs::LoudResult, gain) &&
+                  offsetof(fs_loud_result, blocks_kept) == offsetof(fs::LoudResult, blocks_kept),
+              "fs_loud_result is the engine's record");
+int fs_loudness_normalize(int device_id, const float* pcm, int b, size_t stride, const int64_t* n_samples, int rate, const fs_loud_params* params,
+                          float* out, size_t out_stride, fs_loud_result* res) {
+    FS_ARG(pcm && n_samples && res, "null argument");
+    FS_TRY(fs::loudness_rows(device_id, pcm, b, stride, n_samples, rate, params ? &params->target_lufs : nullptr, out, out_stride, res, nullptr, 0,
+                             nullptr))
+}
+int fs_codec_decode_loud(fs_codec_t* c, const uint32_t* codes, int b, int T, const fs_loud_params* loud, double speed, const fs_pcm_spec* spec,
+                         void* out, size_t cap, int64_t* n_out, fs_loud_result* res) {
+    FS_ARG(c && codes && spec && out && n_out, "null argument");
+    FS_TRY(c->impl->decode_loud(codes, b, T, loud ? &loud->target_lufs : nullptr, speed, &spec->rate, out, cap, n_out, res))
+}
+int fs_selftest_loud_hops(int device_id, const float* pcm, int64_t n, int rate, double* hops, size_t cap, int64_t* n_hops, fs_loud_result* res) {
+    FS_ARG(pcm && hops && n_hops && res, "null argument");
+    FS_TRY(fs::loudness_rows(device_id, pcm, 1, (size_t)n, &n, rate, nullptr, nullptr, 0, res, hops, cap, n_hops))
 }
 int fs_codec_streams_open_pcm(fs_codec_t* c, const fs_pcm_spec* spec, int* stream_id) {
     FS_ARG(c && spec && stream_id, "null argument");

@@ -6,7 +6,8 @@ from .codec import FireflyCodec
 from .lm import LM, DualARTransformer, prefix_blob_info
 from ._resample import resample, resample_out_len
 from ._tsm import time_stretch, time_stretch_out_len
+from ._loud import loudness, loudness_normalize
 from .stream import SessionStreamer, StreamingSynth, decode_chunk
 
 __all__ = ["config", "lib", "LIB_PATH", "SYMBOLS", "DualARTransformer", "LM", "prefix_blob_info", "FireflyCodec", "StreamingSynth", "SessionStreamer", "decode_chunk",
-           "resample", "resample_out_len", "time_stretch", "time_stretch_out_len"]
+           "resample", "resample_out_len", "time_stretch", "time_stretch_out_len", "loudness", "loudness_normalize"]

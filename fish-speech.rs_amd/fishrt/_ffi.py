@@ -96,6 +96,7 @@ SYMBOLS = ["fs_last_error", "fs_version", "fs_device_count", "fs_lm_create", "fs
            "fs_codec_streams_decode_pcm", "fs_codec_encode_pcm",
            "fs_time_stretch_out_len", "fs_time_stretch", "fs_codec_decode_speed",
            "fs_codec_streams_open_speed", "fs_selftest_tsm_chunks",
+           "fs_loudness_normalize", "fs_codec_decode_loud", "fs_selftest_loud_hops",
            "fs_fp8_quantize_rows", "fs_fp8_decode_table", "fs_selftest", "fs_lm_selftest", "fs_selftest_sample_rows", "fs_selftest_sample_slots", "fs_lm_debug_capture", "fs_lm_debug_read"]
 
 # flags of fs_lm_generate* / fs_lm_session_begin (include/fishrt.h)
@@ -211,6 +212,24 @@ TSM_PROTOTYPES = {
                                C.c_size_t, _I64P],
 }
 
+
+
+# device loudness normalisation (include/fishrt.h: fs_loud_params, fs_loud_result)
+class LoudParams(C.Structure):  # fs_loud_params
+    _fields_ = [("target_lufs", C.c_double), ("peak_db", C.c_double), ("max_gain_db", C.c_double)]
+
+
+class LoudResult(C.Structure):  # fs_loud_result
+    _fields_ = [("lufs", C.c_double), ("peak", C.c_float), ("gain", C.c_float), ("blocks_total", C.c_int32), ("blocks_kept", C.c_int32)]
+
+
+LOUD_PROTOTYPES = {
+    "fs_loudness_normalize": [C.c_int, _F32P, C.c_int, C.c_size_t, _I64P, C.c_int, C.POINTER(LoudParams), _F32P, C.c_size_t, C.POINTER(LoudResult)],
+    "fs_codec_decode_loud": [C.c_void_p, _U32P, C.c_int, C.c_int, C.POINTER(LoudParams), C.c_double, C.POINTER(PcmSpec), C.c_void_p, C.c_size_t,
+                             _I64P, C.POINTER(LoudResult)],
+    "fs_selftest_loud_hops": [C.c_int, _F32P, C.c_int64, C.c_int, C.POINTER(C.c_double), C.c_size_t, _I64P, C.POINTER(LoudResult)],
+}
+
 _lib = None
 
 
@@ -231,7 +250,7 @@ def lib():
         L.fs_lm_destroy.argtypes = [C.c_void_p]
         L.fs_codec_destroy.argtypes = [C.c_void_p]
         for name, argtypes in {**SCORE_PROTOTYPES, **TRACE_PROTOTYPES, **ALTS_PROTOTYPES, **CONV_PROTOTYPES, **CODEC_OP_PROTOTYPES, **ATTN_PROTOTYPES, **GEMM_PROTOTYPES, **HISTORY_PROTOTYPES,
-                               **RESAMPLE_PROTOTYPES, **TSM_PROTOTYPES}.items():
+                               **RESAMPLE_PROTOTYPES, **TSM_PROTOTYPES, **LOUD_PROTOTYPES}.items():
             if hasattr(L, name):  # (an older build loaded through LIB_PATH -- tools/attn_paths_dump.py --lib -- may lack the newest entry points)
                 getattr(L, name).argtypes = argtypes
         _lib = L

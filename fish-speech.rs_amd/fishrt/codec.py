@@ -48,17 +48,44 @@ class FireflyCodec:
             return None
         return _ffi.pcm_spec(self.sample_rate if sample_rate is None else sample_rate, resample, dtype)
 
-    def decode(self, codes, sample_rate=None, resample="linear", dtype="f32", speed=None):
+    last_loudness = None  # the per-row records of the last decode(loudness=) call
+
+    def decode(self, codes, sample_rate=None, resample="linear", dtype="f32", speed=None, loudness=None, peak_db=None, max_gain_db=None):
         """sample_rate / dtype: convert every PCM row on the device before it is copied to the host (fishrt.h fs_codec_decode_pcm) ->
         (b, 1, out_len) f32 or int16; resample: "linear" (the reference's resample, bit for bit) or "sinc" (band-limited).
         speed (0.25 .. 4.0; None = no stretch stage): every row time-stretched on the device first (fishrt.h fs_codec_decode_speed: WSOLA,
-        the pitch stays) -- 2048 T / speed samples per row, before sample_rate / dtype apply"""
+        the pitch stays) -- 2048 T / speed samples per row, before sample_rate / dtype apply.
+        loudness (LUFS, -40 .. -5; None = no loudness stage): every row measured (BS.1770 integrated loudness) and multiplied by its own gain
+        on the device, in front of the stretch stage (fishrt.h fs_codec_decode_loud); peak_db (default -1) bounds the sample peak the gain may
+        produce, max_gain_db (default 30) the gain.  Returns what it returns without; the rows' records -- dict(lufs, peak, gain,
+        blocks_total, blocks_kept), lufs as measured before the gain -- are in self.last_loudness"""
         if not isinstance(codes, np.ndarray) or not codes.flags["C_CONTIGUOUS"]:
             raise ValueError("Input array must be contiguous")  # codec.rs:97-101
         if codes.ndim != 3 or codes.shape[1] != 8:
             raise ValueError("codes must have shape (b, 8, T)")
         codes = codes.astype(np.uint32, copy=False)
         b, _, T = codes.shape
+        if loudness is not None:
+            from . import _loud
+            from ._resample import resample_out_len
+            from ._tsm import time_stretch_out_len
+            spec = _ffi.pcm_spec(self.sample_rate if sample_rate is None else sample_rate, resample, dtype)
+            params = _ffi.LoudParams(float(loudness), _loud.PEAK_DB if peak_db is None else float(peak_db),
+                                     _loud.MAX_GAIN_DB if max_gain_db is None else float(max_gain_db))
+            speed = 1.0 if speed is None else float(speed)
+            n = time_stretch_out_len(2048 * T, speed) if speed != 1.0 else 2048 * T  # (refuses a speed outside 0.25 .. 4.0)
+            if spec.rate != self.sample_rate:
+                n = resample_out_len(n, self.sample_rate, spec.rate, resample)
+            out = np.empty((b, 1, max(n, 1)), _ffi.PCM_DTYPES[dtype])
+            got, res = (C.c_int64 * b)(), (_ffi.LoudResult * b)()
+            _ffi.check(_ffi.lib().fs_codec_decode_loud(self._h, codes.ctypes.data_as(C.POINTER(C.c_uint32)), b, T, C.byref(params),
+                                                       C.c_double(speed), C.byref(spec), out.ctypes.data_as(C.c_void_p),
+                                                       C.c_size_t(out.shape[2]), got, res))
+            assert all(got[i] == n for i in range(b))
+            self.last_loudness = [_loud._record(r) for r in res]
+            return out[:, :, :n]
+        if peak_db is not None or max_gain_db is not None:
+            raise ValueError("peak_db / max_gain_db go with loudness=")
         if speed is not None:
             from ._resample import resample_out_len
             from ._tsm import time_stretch_out_len

@@ -24,6 +24,13 @@ string or a boolean; anything else answers 422 with a message) and every vocoded
 (`codec.decode(..., speed=)`: WSOLA, the pitch stays; include/fishrt.h fs_codec_decode_speed) BEFORE it is resampled and formatted -- for the
 WAV, `pcm` and Opus-hook answers alike, with and without `sample_rate` / `opus_rate`.  A request without the field makes the codec calls it
 made before.
+Loudness (opt-in, `AppState(device_loudness=False)`): a request field `loudness`, the level the answer is to have in LUFS (ITU-R BS.1770
+integrated loudness; include/fishrt.h fs_codec_decode_loud).  It must be a real number in -40 .. -5, else 422 with a message; with the
+option off the field answers 422 saying so (a level a client asked for is not dropped silently).  Integrated loudness is a property of the
+whole signal, so the field goes with the WAV answers, which are whole: the request's chunks are vocoded in ONE `codec.decode(...,
+loudness=)` call over their codes in order, measured, scaled (never above a sample peak of -1 dBFS), then stretched (`speed`) and
+resampled / packed (`sample_rate`) on the device.  The `pcm` and Opus answers stream chunk by chunk and refuse the field with a 422 that
+says why.  A request without the field makes the calls it made before.
 
 Scheduler.  One worker thread per LM handle (= per GPU) drains a queue of chunk jobs.  A job whose conditioning prefix equals the one
 sitting in the handle's KV cache skips the prefix (the reference's `assume_kv_cache`); jobs of different voices simply invalidate it
@@ -154,7 +161,8 @@ class LMState:  # server/lib/state.rs:12-21
 class AppState:  # server/lib/state.rs:23-29
     def __init__(self, lm_state, codec, sample_rate=44100, opus_encoder=None, preprocess=preprocess_text, batch_window_s=0.002,
                  continuous=True, auto_batch=False, session_prefixes=False, per_slot_sampling=False, wide_sampling=False,
-                 prefix_host_cache_bytes=0, chunk_history=False, device_resample=None, opus_rate=None, device_speed=False):
+                 prefix_host_cache_bytes=0, chunk_history=False, device_resample=None, opus_rate=None, device_speed=False,
+                 device_loudness=False):
         self.lm, self.codec, self.sample_rate, self.opus_encoder, self.preprocess = lm_state, codec, sample_rate, opus_encoder, preprocess
         # device_resample (None | "linear" | "sinc", off by default): the codec converts sample rates on the device (FireflyCodec.decode /
         # encode with sample_rate=): /v1/audio/speech takes a `sample_rate` field for WAV and `pcm` answers, and /v1/audio/encoding resamples
@@ -167,6 +175,9 @@ class AppState:  # server/lib/state.rs:23-29
         # device_speed (off by default: the `speed` field is ignored, as ever): requests may carry `speed` (0.25 .. 4.0) and the codec
         # time-stretches every chunk on the device before it resamples and formats it (FireflyCodec.decode(speed=))
         self.device_speed = bool(device_speed)
+        # device_loudness (off by default: a `loudness` field answers 422): WAV requests may carry `loudness` (LUFS, -40 .. -5) and the codec
+        # measures and scales the whole answer on the device (FireflyCodec.decode(loudness=))
+        self.device_loudness = bool(device_loudness)
         self.codec_lock = threading.Lock()  # a codec handle takes one call at a time (include/fishrt.h); requests vocode from their own threads
         self.auto_batch = auto_batch  # True: every chunk may join the batching session (batch sampling semantics) without `batch_size`
         # session_prefixes (off by default): session jobs share their voice's conditioning prefix (Session.add_prefix) instead of prefilling
@@ -776,6 +787,16 @@ def generate_speech(state, req):
             if isinstance(speed, bool) or not isinstance(speed, (int, float)) or not 0.25 <= speed <= 4.0:  # (NaN fails the comparison)
                 return 422, "application/json", json.dumps({"detail": "`speed` must be a number in 0.25 .. 4.0"}).encode()
             speed = float(speed)
+        loud = req.get("loudness")
+        if loud is not None:
+            if not getattr(state, "device_loudness", False):
+                return 422, "application/json", json.dumps({"detail": "`loudness` needs a server started with device_loudness"}).encode()
+            if isinstance(loud, bool) or not isinstance(loud, (int, float)) or not -40.0 <= loud <= -5.0:  # (NaN fails the comparison)
+                return 422, "application/json", json.dumps({"detail": "`loudness` must be a number of LUFS in -40 .. -5"}).encode()
+            if fmt in ("pcm", "opus"):
+                return 422, "application/json", json.dumps({"detail": f"`loudness` goes with the WAV answer: '{fmt}' streams chunk by chunk, and "
+                                                                      "integrated loudness needs the whole signal"}).encode()
+            loud = float(loud)
         # like the reference (speech.rs:72-96) chunks are batched only when the request asks for it (`batch_size` > 1): the batch paths sample
         # with BatchedLogitsProcessor semantics and no repetition penalty, so what a client hears must not depend on the server's load.
         # `auto_batch` (server option, off by default) lets every chunk join the continuous-batching session when other work is in flight.
@@ -803,6 +824,15 @@ def generate_speech(state, req):
                     pcm = state.codec.decode(np.ascontiguousarray(codes[None]), **spec)[0, 0]  # (an out-of-range code is an error, as in the reference)
                 yield pcm
 
+        def pcm_whole(empty, **spec):  # `loudness`: one codec call over the request's codes in order, measured and scaled as one signal
+            if speed is not None:
+                spec = dict(spec, speed=speed)
+            codes = [f.result() for f in futs]
+            if not codes:
+                return np.zeros(0, empty)
+            with state.codec_lock:
+                return state.codec.decode(np.ascontiguousarray(np.concatenate(codes, axis=-1)[None]), loudness=loud, **spec)[0, 0]
+
         s16 = dict(sample_rate=out_rate, resample=state.device_resample, dtype="s16") if out_rate is not None else None
         if fmt == "pcm":  # extension: chunked little-endian s16 PCM at the codec rate (or `sample_rate`), one HTTP chunk per text chunk
             if s16:
@@ -816,11 +846,17 @@ def generate_speech(state, req):
                 return 200, "audio/ogg", (b for p in pcm_chunks(**spec) for b in enc(p, opus_rate))
             return 200, "audio/ogg", (b for p in pcm_chunks() for b in enc(p, state.sample_rate))
         if s16:
-            all_pcm = np.concatenate(list(pcm_chunks(**s16))) if futs else np.zeros(0, np.int16)
+            if loud is not None:
+                all_pcm = pcm_whole(np.int16, **s16)
+            else:
+                all_pcm = np.concatenate(list(pcm_chunks(**s16))) if futs else np.zeros(0, np.int16)
             buf = io.BytesIO()
             fwav.write_pcm_as_wav(buf, all_pcm, out_rate)
             return 200, "audio/wav", buf.getvalue()
-        all_pcm = np.concatenate(list(pcm_chunks())) if futs else np.zeros(0, np.float32)
+        if loud is not None:
+            all_pcm = pcm_whole(np.float32)
+        else:
+            all_pcm = np.concatenate(list(pcm_chunks())) if futs else np.zeros(0, np.float32)
         buf = io.BytesIO()
         fwav.write_pcm_as_wav(buf, all_pcm, state.sample_rate)
         return 200, "audio/wav", buf.getvalue()

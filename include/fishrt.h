@@ -1041,6 +1041,63 @@ int fs_selftest_tsm_chunks(int device_id, const float* pcm, int64_t n, const int
                            const fs_tsm_params* params, float* out, size_t out_cap, int64_t* out_len, int64_t* emitted /* [n_chunks] */,
                            int64_t* positions, size_t pos_cap, int64_t* n_positions /* nullable */);
 
+/* ---- Device loudness normalisation: the `loudness` of a request (csrc/codec_loud.hip; coefficients, counting, checks and a serial host
+ * evaluator of this text in csrc/fs_loud_plan.h).  The vocoder's level depends on the voice's reference clip and on the text, and the
+ * reference has no level control; a request that states a loudness in LUFS gets one gain for its whole PCM, measured and applied where the
+ * vocoder left it.
+ *
+ * Measure: the integrated loudness of ITU-R BS.1770-4 for one channel, at any integer rate fs in 8000 .. 48000.
+ * K-weighting: two biquads in cascade, their coefficients computed in f64 from the analogue prototypes (the libebur128 construction, which
+ *   reproduces the standard's 48 kHz table).  For either stage K = tan(pi f0 / fs) and a0 = 1 + K/Q + K^2.
+ *   Shelf: f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196, Vh = 10^(G/20), Vb = Vh^0.4996667741545416,
+ *     b = [(Vh + Vb K/Q + K^2)/a0, 2 (K^2 - Vh)/a0, (Vh - Vb K/Q + K^2)/a0],  a = [1, 2 (K^2 - 1)/a0, (1 - K/Q + K^2)/a0].
+ *   High-pass: f0 = 38.13547087602444, Q = 0.5003270373238773,  b = [1, -2, 1],  a = [1, 2 (K^2 - 1)/a0, (1 - K/Q + K^2)/a0].
+ *   The input is f32, widened to f64, and zero before sample 0.  Both stages run in f64 from zero state, each in transposed direct form II:
+ *     y = b0 x + s0;  s0 = b1 x - a1 y + s1;  s1 = b2 x - a2 y   (shelf)      z = y + s2;  s2 = -2 y - d1 z + s3;  s3 = y - d2 z   (high-pass,
+ *     a = [1, d1, d2]).  An implementation may contract a product and a sum into an fma and may evaluate the recurrence in chunks (it is
+ *     linear: the state after a chunk is A^len s_in + the state the chunk leaves from zero state); hop energies are held to a derived bound
+ *     (tests/loud_refs.py), not to bits.
+ * Hops and blocks: hop h = (fs + 5) / 10 in integer arithmetic (4410 at 44.1 kHz);  s_i = sum of z^2 over [i h, (i + 1) h) for the nb = n / h
+ *   whole hops;  block j < nb - 3 has the mean square m_j = (s_j + s_{j+1} + s_{j+2} + s_{j+3}) / (4 h) and the loudness
+ *   l_j = -0.691 + 10 log10(m_j).
+ * Gates: absolute, keep the blocks with l_j > -70;  relative, Gamma = -0.691 + 10 log10(mean of the kept m_j) - 10, keep the blocks with
+ *   l_j > -70 and l_j > Gamma;  L = -0.691 + 10 log10(mean of those m_j).  A comparison with a NaN is false, so such a block is never kept.
+ *   With nb < 4, or when no block survives, the row has no loudness: L is reported as -inf and the gain is exactly 1.
+ * Peak: the largest |x| of the row, in f32, NaN ignored (the sample peak, an exact quantity).
+ * Gain: g_L = 10^((target_lufs - L) / 20) in f64;  g = min(g_L, 10^(max_gain_db / 20), 10^(peak_db / 20) / peak), the last term only when
+ *   peak > 0;  rounded once to f32.  Output y[i] = x[i] * g, one f32 multiply.  No limiter, no look-ahead, no oversampling: the peak clause
+ *   is what keeps the s16 pack from clipping.
+ * Parameters: target_lufs in -40 .. -5;  peak_db <= 0 (FS_LOUD_PEAK_DB_DEFAULT = -1.0);  max_gain_db in 0 .. 60 (FS_LOUD_MAX_GAIN_DB_DEFAULT
+ *   = 30).  A row takes at most 2^30 samples.
+ * Out of scope, each a change of its own: loudness for multi-streams (fs_codec_streams_*: integrated loudness needs the whole signal, a stream
+ *   needs a different, causal definition); normalising uploaded reference clips in fs_codec_encode_pcm; true-peak measurement (oversampled);
+ *   multichannel weighting. */
+#define FS_LOUD_PEAK_DB_DEFAULT (-1.0)
+#define FS_LOUD_MAX_GAIN_DB_DEFAULT 30.0
+typedef struct fs_loud_params {
+    double target_lufs, peak_db, max_gain_db;
+} fs_loud_params;
+typedef struct fs_loud_result {
+    double lufs;                       /* L, or -inf */
+    float peak, gain;                  /* gain: 1 when the call only measures */
+    int32_t blocks_total, blocks_kept; /* max(nb - 3, 0); the blocks that passed both gates */
+} fs_loud_result;
+/* Stand-alone, no codec handle: b rows f32 at pcm + i * stride, row i n_samples[i] <= stride samples long (0 allowed), host -> device -> host.
+ * out == NULL measures only; then params may be NULL too and every gain is 1.  out: f32, row i at element i * out_stride, its n_samples[i]
+ * samples written.  res: one record per row.  A row's record and output do not depend on the other rows of the call.  Everything (rate,
+ * params, lengths, strides) is checked before anything is launched. */
+int fs_loudness_normalize(int device_id, const float* pcm, int b, size_t stride, const int64_t* n_samples, int rate, const fs_loud_params* params,
+                          float* out, size_t out_stride /* elements */, fs_loud_result* res /* [b] */);
+/* fs_codec_decode -> loudness (measure, gain, multiply) of every PCM row at the codec's rate -> time-stretch (speed != 1.0 only) -> the
+ * resample / format stage of fs_codec_decode_pcm -> host, all on the device.  res (nullable): one record per row.  Equals fs_resample of
+ * fs_time_stretch of fs_loudness_normalize of fs_codec_decode's rows bit for bit.  loud == NULL: it is fs_codec_decode_speed (res untouched).
+ * loud, speed, spec and cap are checked before the first launch; a refused call leaves the handle as it was. */
+int fs_codec_decode_loud(fs_codec_t* c, const uint32_t* codes, int b, int T, const fs_loud_params* loud, double speed, const fs_pcm_spec* spec,
+                         void* out, size_t cap /* elements per row */, int64_t* n_out, fs_loud_result* res);
+/* Test hook, no codec handle: the hop energies s_0 .. s_{nb-1} of ONE row as the device summed them (cap must hold nb = n / h), and the row's
+ * record of a measuring call. */
+int fs_selftest_loud_hops(int device_id, const float* pcm, int64_t n, int rate, double* hops, size_t cap, int64_t* n_hops, fs_loud_result* res);
+
 #ifdef __cplusplus
 }
 #endif
