@@ -141,6 +141,14 @@ int fs_selftest_gemm(int device_id, const fs_gemm_case* c, fs_gemm_out* out) {
     out->grid[0] = out->grid[1] = out->grid[2] = 0;
     FS_TRY(fs::gemm_selftest(device_id, *c, *out))
 }
+static_assert(sizeof(fs_gemv_case) == 28 * 4 + 14 * 8, "fs_gemv_case is 24 x int32, two uint32, one float, one int32 and 14 pointers (fishrt/_ffi.py: GemvCase)");
+static_assert(sizeof(fs_gemv_out) == 4 * 8 + 5 * 8 + 4 * 4, "fs_gemv_out is 4 pointers, 5 x size_t and 4 x int32 (fishrt/_ffi.py: GemvOut)");
+int fs_selftest_gemv(int device_id, const fs_gemv_case* c, fs_gemv_out* out) {
+    FS_ARG(c && out && out->variant && out->variant_cap >= 1, "null argument");
+    out->variant[0] = 0; out->guard_ok = 0; out->n_y = out->n_pool = 0;
+    out->grid[0] = out->grid[1] = out->grid[2] = 0;
+    FS_TRY(fs::gemv_selftest(device_id, *c, *out))
+}
 
 // ---- replica fan-out over RCCL (fs_comm.h)
 int fs_comm_unique_id(uint8_t id_out[FS_COMM_ID_BYTES]) { FS_ARG(id_out, "null argument"); FS_TRY(fs::Comm::unique_id(id_out)) }

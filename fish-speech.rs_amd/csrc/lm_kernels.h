@@ -22,6 +22,8 @@
 struct fs_attn_case;
 struct fs_gemm_case;
 struct fs_gemm_out;
+struct fs_gemv_case;
+struct fs_gemv_out;
 
 namespace fs {
 
@@ -140,6 +142,24 @@ struct LmKernels {
     static void fast_embed(const ModelDims& d, const void* fast_emb, const uint32_t* ids, int n, float* out,
                            hipStream_t st);
 };
+
+// What a batch-1 GEMV launcher of LmKernels will launch for a given call: decided in ONE place (gemv_plan, lm_kernels.hip), the five launchers
+// dispatch through it, and fs_selftest_gemv reports its name ("qkv/bf16/K1024/w2/nt", "wo/bf16/K1024/w4/dh64/nt", "up/f32/K256/w4/res",
+// "down/fp8/K4096/ks4/res", "head/f32/K128/w4").  nt / res: non-temporal or default weight loads (LayerW::cache_resident); k_head has one policy.
+struct GemvPlan {
+    enum Op { QKV, WO, FFN_UP, FFN_DOWN, HEAD };
+    Op op = QKV;
+    int wt = 1;            // 0 f32, 1 bf16, 2 fp8 (FS_GEMV_WT_*)
+    int K = 0;             // GEMV width of the instantiation (dim; FFN_DOWN: inter)
+    int waves = 0;         // waves == weight rows (FFN_UP: row pairs) per block; FFN_DOWN: the KS waves that share one row
+    bool nt = true;        // non-temporal weight loads (!cache_resident)
+    bool fused = false;    // WO: the fused small attention prologue (fused_T > 0)
+    int DH = 0;            // WO: head_dim of the instantiation
+    unsigned gx = 1, block = 64;
+    std::string name() const;
+};
+// host only; throws what the launcher would throw (unsupported width, unsupported wo geometry).  n_rows: output rows (FFN_UP: inter)
+GemvPlan gemv_plan(int op, int wt, const ModelDims& d, int n_rows, bool cache_resident, int fused_T = 0);
 
 // ---- MFMA row path (lm_gemm.hip; prefill passes, static-batch steps): bf16 weights, or fp8 weights widened to bf16 in registers
 template <typename WT>
@@ -394,6 +414,8 @@ void attn_selftest(int device, const fs_attn_case& c, float* out, size_t out_cap
                    size_t variant_cap, int* guard_ok);
 // test hook behind fs_selftest_gemm (include/fishrt.h; harness at the bottom of lm_gemm.hip)
 void gemm_selftest(int device, const fs_gemm_case& c, fs_gemm_out& out);
+// test hook behind fs_selftest_gemv (include/fishrt.h; harness at the bottom of lm_kernels.hip)
+void gemv_selftest(int device, const fs_gemv_case& c, fs_gemv_out& out);
 // test hook behind fs_selftest_sample_rows (include/fishrt.h)
 void debug_sample_rows(int device, const float* logits, int B, int n, double temp, double top_p, uint64_t top_k, uint64_t seed,
                        int call_index, uint32_t* out);

@@ -17,9 +17,14 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
+#include "../../include/fishrt.h"
 #include "fs_common.h"
 #include "fs_synth.h"
 #include "lm_kernels.h"
@@ -591,19 +596,54 @@ static void dispatch_k(int K, F&& f) {
     }
 }
 
+// ---- the one place that decides which instantiation and grid a batch-1 GEMV launcher runs (GemvPlan: lm_kernels.h)
+constexpr int GEMV_QKV_WAVES = 2;  // one row per wave, one RoPE pair per block
+constexpr int GEMV_ROW_WAVES = 4;  // k_wo, k_ffn_up, k_head
+constexpr int GEMV_DOWN_KS = 4;    // k_ffn_down: waves that share one row
+template <typename WT> constexpr int gemv_wt() { return std::is_same<WT, float>::value ? 0 : (std::is_same<WT, bf16_t>::value ? 1 : 2); }
+
+std::string GemvPlan::name() const {
+    static const char* const ops[] = {"qkv", "wo", "up", "down", "head"};
+    static const char* const wts[] = {"f32", "bf16", "fp8"};
+    std::string n = std::string(ops[op]) + "/" + wts[wt] + "/K" + std::to_string(K) + (op == FFN_DOWN ? "/ks" : "/w") + std::to_string(waves);
+    if (op == WO) n += (fused ? "/fused" : "") + std::string("/dh") + std::to_string(DH);
+    if (op != HEAD) n += nt ? "/nt" : "/res";
+    return n;
+}
+
+GemvPlan gemv_plan(int op, int wt, const ModelDims& d, int n_rows, bool cache_resident, int fused_T) {
+    FS_REQUIRE(op >= GemvPlan::QKV && op <= GemvPlan::HEAD && wt >= 0 && wt <= 2, "unknown GEMV op or weight type");
+    GemvPlan p;
+    p.op = (GemvPlan::Op)op; p.wt = wt; p.nt = !cache_resident;
+    p.K = op == GemvPlan::FFN_DOWN ? d.inter : d.dim;
+    if (op == GemvPlan::WO) {
+        FS_REQUIRE(fused_T <= 8 && d.H <= 32 && d.H * 8 * 2 <= GEMV_ROW_WAVES * 64 && d.dim <= 4 * GEMV_ROW_WAVES * 64, "fused attention supports at most 8 cached tokens and 16 heads");
+        FS_REQUIRE(d.Dh == 64 || d.Dh == 32, "unsupported head_dim");
+        p.fused = fused_T > 0; p.DH = d.Dh;
+    }
+    dispatch_k(p.K, [](auto) {});  // (throws for a width without an instantiation)
+    if (op == GemvPlan::FFN_DOWN) { p.waves = GEMV_DOWN_KS; p.gx = (unsigned)n_rows; }  // one row per block
+    else {
+        p.waves = op == GemvPlan::QKV ? GEMV_QKV_WAVES : GEMV_ROW_WAVES;
+        p.gx = (unsigned)((n_rows + p.waves - 1) / p.waves);
+    }
+    p.block = (unsigned)p.waves * 64;
+    if (op == GemvPlan::HEAD) p.nt = true;
+    return p;
+}
+
 template <typename WT>
 void LmKernels<WT>::qkv(const ModelDims& d, const float* x, const LayerW& w, const float* cos_t, const float* sin_t,
                         const SeqState* state, int pos_static, int rope_static, float* q_out, KVView kv, hipStream_t st) {
-    constexpr int WAVES = 2;  // one row per wave, one RoPE pair per block
-    const int n_rows = (d.H + 2 * d.Hk) * d.Dh;
-    const int grid = (n_rows + WAVES - 1) / WAVES;
-    dispatch_k(d.dim, [&](auto Kc) {
+    constexpr int WAVES = GEMV_QKV_WAVES;
+    const GemvPlan p = gemv_plan(GemvPlan::QKV, gemv_wt<WT>(), d, (d.H + 2 * d.Hk) * d.Dh, w.cache_resident);
+    dispatch_k(p.K, [&](auto Kc) {
         constexpr int K = decltype(Kc)::value;
-        if (w.cache_resident)
-            hipLaunchKernelGGL((k_qkv<WT, K, WAVES, false>), dim3(grid), dim3(WAVES * 64), 0, st, x, w.attn_norm, d.eps,
+        if (!p.nt)
+            hipLaunchKernelGGL((k_qkv<WT, K, WAVES, false>), dim3(p.gx), dim3(p.block), 0, st, x, w.attn_norm, d.eps,
                                (const WT*)w.wqkv, cos_t, sin_t, state, pos_static, rope_static, q_out, kv, d.H, d.Hk, d.Dh, w.s_qkv);
         else
-            hipLaunchKernelGGL((k_qkv<WT, K, WAVES, true>), dim3(grid), dim3(WAVES * 64), 0, st, x, w.attn_norm, d.eps,
+            hipLaunchKernelGGL((k_qkv<WT, K, WAVES, true>), dim3(p.gx), dim3(p.block), 0, st, x, w.attn_norm, d.eps,
                                (const WT*)w.wqkv, cos_t, sin_t, state, pos_static, rope_static, q_out, kv, d.H, d.Hk, d.Dh, w.s_qkv);
     });
     FS_LAUNCH_CHECK();
@@ -619,39 +659,37 @@ void LmKernels<WT>::wo(const ModelDims& d, const float* part, int n_chunks_max, 
         chunk *= tpb;
         nc_launch = (nc_launch + tpb - 1) / tpb;
     } else nc_launch = 1;
-    constexpr int WAVES = 4;
-    const int grid = (d.dim + WAVES - 1) / WAVES;
-    FS_REQUIRE(fused_T <= 8 && d.H <= 32 && d.H * 8 * 2 <= WAVES * 64 && d.dim <= 4 * WAVES * 64, "fused attention supports at most 8 cached tokens and 16 heads");
-    FS_REQUIRE(d.Dh == 64 || d.Dh == 32, "unsupported head_dim");
-    dispatch_k(d.dim, [&](auto Kc) {
+    constexpr int WAVES = GEMV_ROW_WAVES;
+    const GemvPlan p = gemv_plan(GemvPlan::WO, gemv_wt<WT>(), d, d.dim, w.cache_resident, fused_T);
+    dispatch_k(p.K, [&](auto Kc) {
         constexpr int K = decltype(Kc)::value;
         auto go = [&](auto fused, auto dh) {
-            if (w.cache_resident)
-                hipLaunchKernelGGL((k_wo<WT, K, WAVES, decltype(fused)::value, decltype(dh)::value, false>), dim3(grid), dim3(WAVES * 64), 0,
+            if (!p.nt)
+                hipLaunchKernelGGL((k_wo<WT, K, WAVES, decltype(fused)::value, decltype(dh)::value, false>), dim3(p.gx), dim3(p.block), 0,
                                    st, part, n_chunks_max, chunk, state, q, kv, fused_T, (const WT*)w.wo, x, d.H, d.Hk, d.dim, w.s_o, nc_launch);
             else
-                hipLaunchKernelGGL((k_wo<WT, K, WAVES, decltype(fused)::value, decltype(dh)::value, true>), dim3(grid), dim3(WAVES * 64), 0,
+                hipLaunchKernelGGL((k_wo<WT, K, WAVES, decltype(fused)::value, decltype(dh)::value, true>), dim3(p.gx), dim3(p.block), 0,
                                    st, part, n_chunks_max, chunk, state, q, kv, fused_T, (const WT*)w.wo, x, d.H, d.Hk, d.dim, w.s_o, nc_launch);
         };
         using T = std::true_type; using F = std::false_type;
         using D64 = std::integral_constant<int, 64>; using D32 = std::integral_constant<int, 32>;
-        if (fused_T > 0) { if (d.Dh == 64) go(T(), D64()); else go(T(), D32()); }
-        else { if (d.Dh == 64) go(F(), D64()); else go(F(), D32()); }
+        if (p.fused) { if (p.DH == 64) go(T(), D64()); else go(T(), D32()); }
+        else { if (p.DH == 64) go(F(), D64()); else go(F(), D32()); }
     });
     FS_LAUNCH_CHECK();
 }
 
 template <typename WT>
 void LmKernels<WT>::ffn_up(const ModelDims& d, const float* x, const LayerW& w, float* act, hipStream_t st) {
-    constexpr int WAVES = 4;
-    const int grid = (d.inter + WAVES - 1) / WAVES;
-    dispatch_k(d.dim, [&](auto Kc) {
+    constexpr int WAVES = GEMV_ROW_WAVES;
+    const GemvPlan p = gemv_plan(GemvPlan::FFN_UP, gemv_wt<WT>(), d, d.inter, w.cache_resident);
+    dispatch_k(p.K, [&](auto Kc) {
         constexpr int K = decltype(Kc)::value;
-        if (w.cache_resident)
-            hipLaunchKernelGGL((k_ffn_up<WT, K, WAVES, false>), dim3(grid), dim3(WAVES * 64), 0, st, x, w.ffn_norm, d.eps,
+        if (!p.nt)
+            hipLaunchKernelGGL((k_ffn_up<WT, K, WAVES, false>), dim3(p.gx), dim3(p.block), 0, st, x, w.ffn_norm, d.eps,
                                (const WT*)w.w13, act, d.inter, w.s_13);
         else
-            hipLaunchKernelGGL((k_ffn_up<WT, K, WAVES, true>), dim3(grid), dim3(WAVES * 64), 0, st, x, w.ffn_norm, d.eps,
+            hipLaunchKernelGGL((k_ffn_up<WT, K, WAVES, true>), dim3(p.gx), dim3(p.block), 0, st, x, w.ffn_norm, d.eps,
                                (const WT*)w.w13, act, d.inter, w.s_13);
     });
     FS_LAUNCH_CHECK();
@@ -659,13 +697,14 @@ void LmKernels<WT>::ffn_up(const ModelDims& d, const float* x, const LayerW& w, 
 
 template <typename WT>
 void LmKernels<WT>::ffn_down(const ModelDims& d, const float* act, const LayerW& w, float* x, hipStream_t st) {
-    constexpr int KS = 4;
-    dispatch_k(d.inter, [&](auto Kc) {
+    constexpr int KS = GEMV_DOWN_KS;
+    const GemvPlan p = gemv_plan(GemvPlan::FFN_DOWN, gemv_wt<WT>(), d, d.dim, w.cache_resident);
+    dispatch_k(p.K, [&](auto Kc) {
         constexpr int K = decltype(Kc)::value;
-        if (w.cache_resident)
-            hipLaunchKernelGGL((k_ffn_down<WT, K, KS, false>), dim3(d.dim), dim3(KS * 64), 0, st, act, (const WT*)w.w2, x, d.dim, w.s_2);
+        if (!p.nt)
+            hipLaunchKernelGGL((k_ffn_down<WT, K, KS, false>), dim3(p.gx), dim3(p.block), 0, st, act, (const WT*)w.w2, x, d.dim, w.s_2);
         else
-            hipLaunchKernelGGL((k_ffn_down<WT, K, KS, true>), dim3(d.dim), dim3(KS * 64), 0, st, act, (const WT*)w.w2, x, d.dim, w.s_2);
+            hipLaunchKernelGGL((k_ffn_down<WT, K, KS, true>), dim3(p.gx), dim3(p.block), 0, st, act, (const WT*)w.w2, x, d.dim, w.s_2);
     });
     FS_LAUNCH_CHECK();
 }
@@ -673,11 +712,11 @@ void LmKernels<WT>::ffn_down(const ModelDims& d, const float* act, const LayerW&
 template <typename WT>
 void LmKernels<WT>::head(const ModelDims& d, const float* x, const float* norm_w, const void* W, const float* wscale, int n_rows,
                          float* logits, hipStream_t st) {
-    constexpr int WAVES = 4;
-    const int grid = (n_rows + WAVES - 1) / WAVES;
-    dispatch_k(d.dim, [&](auto Kc) {
+    constexpr int WAVES = GEMV_ROW_WAVES;
+    const GemvPlan p = gemv_plan(GemvPlan::HEAD, gemv_wt<WT>(), d, n_rows, false);
+    dispatch_k(p.K, [&](auto Kc) {
         constexpr int K = decltype(Kc)::value;
-        hipLaunchKernelGGL((k_head<WT, K, WAVES>), dim3(grid), dim3(WAVES * 64), 0, st, x, norm_w, d.eps, (const WT*)W,
+        hipLaunchKernelGGL((k_head<WT, K, WAVES>), dim3(p.gx), dim3(p.block), 0, st, x, norm_w, d.eps, (const WT*)W,
                            n_rows, logits, wscale);
     });
     FS_LAUNCH_CHECK();
@@ -879,5 +918,266 @@ template void launch_synth_fill<bf16_t>(bf16_t*, uint64_t, int64_t, int64_t, int
 template void launch_synth_fill<float>(float*, uint64_t, int64_t, int64_t, int, int, float, float, int, hipStream_t);
 template void launch_convert_rows<bf16_t>(bf16_t*, const float*, int64_t, int64_t, int, int, hipStream_t);
 template void launch_convert_rows<float>(float*, const float*, int64_t, int64_t, int, int, hipStream_t);
+
+// ================================================================================================ fs_selftest_gemv (include/fishrt.h)
+// ONE launcher call of LmKernels on caller data and nothing else.  Everything a launch writes (the output vector, both KV pools) lies between
+// 256-element guards of 0xFF bytes and is poisoned with 0xFF bytes (NaN) where the caller provides nothing; the whole case is validated before
+// the first device call.
+namespace {
+constexpr size_t kGemvGuard = 256;
+struct GemvDev {  // device buffer of n elements of es bytes between two guards, all 0xFF bytes at first
+    void* p = nullptr;
+    size_t n = 0, es = 4;
+    void alloc(size_t n_, size_t es_, hipStream_t st) {
+        n = n_; es = es_;
+        FS_HIP(hipMalloc(&p, (n + 2 * kGemvGuard) * es));
+        FS_HIP(hipMemsetAsync(p, 0xFF, (n + 2 * kGemvGuard) * es, st));
+    }
+    char* data() const { return (char*)p + kGemvGuard * es; }
+    void up(const void* src, size_t count, hipStream_t st) {  // synchronous: the source may be a temporary
+        FS_HIP(hipMemcpyAsync(data(), src, count * es, hipMemcpyHostToDevice, st));
+        FS_HIP(hipStreamSynchronize(st));
+    }
+    void put(const void* src, size_t count, size_t es_, hipStream_t st) { alloc(count, es_, st); up(src, count, st); }
+    bool intact(hipStream_t st) const {
+        if (!p) return true;
+        std::vector<uint8_t> g(2 * kGemvGuard * es);
+        FS_HIP(hipMemcpyAsync(g.data(), p, kGemvGuard * es, hipMemcpyDeviceToHost, st));
+        FS_HIP(hipMemcpyAsync(g.data() + kGemvGuard * es, data() + n * es, kGemvGuard * es, hipMemcpyDeviceToHost, st));
+        FS_HIP(hipStreamSynchronize(st));
+        for (uint8_t b : g) if (b != 0xFF) return false;
+        return true;
+    }
+    ~GemvDev() { if (p) (void)hipFree(p); }
+};
+
+void gemv_req(bool ok, const char* msg) { if (!ok) throw Error(std::string("GEMV self-test: ") + msg); }
+
+// f32 values -> the storage type T (exact: validation has checked that every value is on T's grid)
+template <typename T> T gemv_cast(float f) {
+    if constexpr (std::is_same<T, float>::value) return f;
+    else if constexpr (std::is_same<T, bf16_t>::value) return f32_to_bf16_host(f);
+    else return fp8_t{f32_to_e4m3(f)};
+}
+template <typename T> float gemv_f32(T v) {
+    if constexpr (std::is_same<T, float>::value) return v;
+    else if constexpr (std::is_same<T, bf16_t>::value) return bf16_to_f32_host(v);
+    else return e4m3_to_f32(v.v);
+}
+template <typename T> void gemv_put_as(GemvDev& b, const float* src, size_t n, hipStream_t st) {
+    std::vector<T> h(n);
+    for (size_t i = 0; i < n; ++i) h[i] = gemv_cast<T>(src[i]);
+    b.put(h.data(), n, sizeof(T), st);
+}
+void gemv_on_grid(const float* a, size_t n, int wt, const char* msg) {  // wt: 0 f32 (anything), 1 bf16, 2 e4m3fn
+    if (wt == FS_GEMV_WT_F32) return;
+    for (size_t i = 0; i < n; ++i) {
+        const float w = a[i];
+        gemv_req(wt == FS_GEMV_WT_FP8 ? e4m3_to_f32(f32_to_e4m3(w)) == w : bf16_to_f32_host(f32_to_bf16_host(w)) == w, msg);
+    }
+}
+
+// everything validation derives from a case: the dims, the plan's name and grid, the extents
+struct GemvCaseInfo {
+    ModelDims d{};
+    std::string name;
+    unsigned gx = 1;
+    size_t w_rows = 0, w_cols = 0, n_x = 0, n_y = 0, n_pool = 0;
+};
+
+void gemv_validate(const fs_gemv_case& c, GemvCaseInfo& I) {
+    const auto req = gemv_req;
+    static const char* const wts[] = {"f32", "bf16", "fp8"};
+    req(c.op >= FS_GEMV_QKV && c.op <= FS_GEMV_FAST_EMBED, "unknown op");
+    req(c.wt >= FS_GEMV_WT_F32 && c.wt <= FS_GEMV_WT_FP8, "unknown weight type");
+    req(std::isfinite(c.eps) && c.eps >= 0.f, "eps must be finite and >= 0");
+    const int kvt = c.wt == FS_GEMV_WT_F32 ? FS_GEMV_WT_F32 : FS_GEMV_WT_BF16;  // KVT<WT>: pools and embedding tables
+    ModelDims& d = I.d;
+    d.dim = c.dim; d.inter = c.inter; d.H = c.H; d.Hk = c.Hk; d.Dh = c.Dh; d.n_rep = c.Hk > 0 ? c.H / c.Hk : 0; d.eps = c.eps;
+    req(c.dim >= 1 && c.dim <= 16384, "1 <= dim <= 16384");
+    if (c.op == FS_GEMV_EMBED || c.op == FS_GEMV_FAST_EMBED) {
+        req(c.tok_emb && c.tok_rows >= 1 && (size_t)c.tok_rows * c.dim <= ((size_t)1 << 24), "tok_emb [tok_rows][dim] is required, at most 2^24 elements");
+        gemv_on_grid(c.tok_emb, (size_t)c.tok_rows * c.dim, kvt, "an embedding value is not a value of the table type");
+        if (c.op == FS_GEMV_FAST_EMBED) {
+            req(c.ids && c.n_ids >= 1 && c.n_ids <= 4096, "fast embed: ids [n_ids] is required, 1 <= n_ids <= 4096");
+            for (int i = 0; i < c.n_ids; ++i) req(c.ids[i] < (uint32_t)c.tok_rows, "fast embed: an id is outside the table");
+            I.name = std::string("fast_embed/") + wts[kvt]; I.gx = (unsigned)c.n_ids; I.n_y = (size_t)c.n_ids * c.dim;
+            return;
+        }
+        req(c.n_cb >= 0 && c.n_cb <= 15 && c.cb_size >= 1 && (c.n_cb == 0 || c.cb_emb) && (size_t)std::max(c.n_cb, 1) * c.cb_size * c.dim <= ((size_t)1 << 24),
+            "embed: 0 <= n_cb <= 15 (SeqState::cur holds 16 tokens), cb_size >= 1, cb_emb [n_cb cb_size][dim] of at most 2^24 elements");
+        gemv_on_grid(c.cb_emb, (size_t)c.n_cb * c.cb_size * c.dim, kvt, "an embedding value is not a value of the table type");
+        req(c.tokens != nullptr, "embed: tokens is required");
+        int stride = 1;
+        if (c.use_prompt) {
+            req(c.prompt_L >= 1 && c.step >= 0 && c.step < c.prompt_L, "embed: prompt source needs prompt_L >= 1 and 0 <= step < prompt_L");
+            req((long long)c.n_tokens >= (long long)c.n_cb * c.prompt_L + c.step + 1, "embed: the staged prompt does not hold every token the column reads");
+            stride = c.prompt_L;
+        } else req(c.n_tokens >= c.n_cb + 1, "embed: cur source needs n_cb + 1 tokens");
+        const uint32_t* t = c.tokens + (c.use_prompt ? c.step : 0);
+        req(t[0] < (uint32_t)c.tok_rows, "embed: the semantic token is outside tok_emb");
+        for (int k = 0; k < c.n_cb; ++k) req(t[(size_t)(k + 1) * stride] < (uint32_t)c.cb_size, "embed: a code is outside its codebook");
+        I.name = std::string("embed/") + wts[kvt]; I.gx = 1; I.n_y = (size_t)c.dim;
+        return;
+    }
+    req(c.x && c.w, "x and w are required");
+    req(c.wt != FS_GEMV_WT_FP8 || c.wscale, "fp8 weights need their row scales (wscale)");
+    const bool resident = c.cache_resident != 0;
+    GemvPlan p;
+    switch (c.op) {
+    case FS_GEMV_QKV:
+        req(c.H >= 1 && c.H <= 64 && c.Hk >= 1 && c.Hk <= c.H && c.H % c.Hk == 0, "1 <= Hk <= H <= 64, H a multiple of Hk");
+        req(c.Dh >= 2 && c.Dh <= 256 && c.Dh % 2 == 0, "head_dim must be even (RoPE rotates pairs), 2 <= Dh <= 256");
+        req(c.dim == c.H * c.Dh, "dim must equal H * Dh");
+        p = gemv_plan(GemvPlan::QKV, c.wt, d, (c.H + 2 * c.Hk) * c.Dh, resident);
+        req(c.norm_w && c.cos_t && c.sin_t && c.k && c.v && c.page_table, "qkv: norm_w, cos_t, sin_t, k, v and page_table are required");
+        req(c.n_pages >= 1 && c.n_pages <= 4096 && c.pt_len >= 1 && c.pt_len <= (1 << 16), "qkv: 1 <= n_pages <= 4096, 1 <= pt_len <= 2^16");
+        req(c.pos >= 0 && c.pos < (1 << 20) && c.rope_off >= 0 && c.rope_off < (1 << 20) && c.rope_rows >= 1 && c.pos + c.rope_off < c.rope_rows,
+            "qkv: the position or the RoPE row is outside [0, 2^20) / the cos / sin tables");
+        req(c.pos / KV_PAGE < c.pt_len, "qkv: the page table does not cover pos");
+        for (int i = 0; i < c.pt_len; ++i) req(c.page_table[i] >= 0 && c.page_table[i] < c.n_pages, "qkv: a page id is outside the pool");
+        I.w_rows = (size_t)(c.H + 2 * c.Hk) * c.Dh; I.w_cols = (size_t)c.dim; I.n_x = (size_t)c.dim; I.n_y = (size_t)c.H * c.Dh;
+        I.n_pool = (size_t)c.n_pages * c.Hk * KV_PAGE * c.Dh;
+        gemv_on_grid(c.k, I.n_pool, kvt, "a pool value is not a value of the KV type");
+        gemv_on_grid(c.v, I.n_pool, kvt, "a pool value is not a value of the KV type");
+        break;
+    case FS_GEMV_FFN_UP:
+        req(c.inter >= 1 && c.inter <= 16384 && c.norm_w, "up: 1 <= inter <= 16384, norm_w is required");
+        p = gemv_plan(GemvPlan::FFN_UP, c.wt, d, c.inter, resident);
+        I.w_rows = (size_t)2 * c.inter; I.w_cols = (size_t)c.dim; I.n_x = (size_t)c.dim; I.n_y = (size_t)c.inter;
+        break;
+    case FS_GEMV_FFN_DOWN:
+        req(c.inter >= 1 && c.y, "down: inter >= 1, y (the residual stream) is required");
+        p = gemv_plan(GemvPlan::FFN_DOWN, c.wt, d, c.dim, resident);
+        I.w_rows = (size_t)c.dim; I.w_cols = (size_t)c.inter; I.n_x = (size_t)c.inter; I.n_y = (size_t)c.dim;
+        break;
+    case FS_GEMV_HEAD:
+        req(c.n_rows >= 1 && c.n_rows <= (1 << 18) && c.norm_w, "head: 1 <= n_rows <= 2^18, norm_w is required");
+        p = gemv_plan(GemvPlan::HEAD, c.wt, d, c.n_rows, false);
+        I.w_rows = (size_t)c.n_rows; I.w_cols = (size_t)c.dim; I.n_x = (size_t)c.dim; I.n_y = (size_t)c.n_rows;
+        break;
+    default:  // FS_GEMV_WO_BODY
+        req(c.H >= 1 && c.H <= 16 && c.Hk >= 1 && c.Hk <= c.H && c.H % c.Hk == 0, "wo: 1 <= Hk <= H <= 16, H a multiple of Hk");
+        req(c.Dh >= 2 && c.Dh % 2 == 0, "head_dim must be even (RoPE rotates pairs), 2 <= Dh <= 256");
+        req(c.dim == c.H * c.Dh, "dim must equal H * Dh");
+        req(c.y != nullptr, "wo: y (the residual stream) is required");
+        p = gemv_plan(GemvPlan::WO, c.wt, d, c.dim, resident, 0);
+        I.w_rows = (size_t)c.dim; I.w_cols = (size_t)c.dim; I.n_x = (size_t)c.dim; I.n_y = (size_t)c.dim;
+        break;
+    }
+    req(I.w_rows * I.w_cols <= ((size_t)1 << 26), "the weight matrix has more than 2^26 elements");
+    I.name = p.name(); I.gx = p.gx;
+    gemv_on_grid(c.w, I.w_rows * I.w_cols, c.wt, c.wt == FS_GEMV_WT_FP8 ? "a weight is not an e4m3fn value" : "a weight is not a bf16 value");
+}
+
+template <typename WT>
+void gemv_run(const fs_gemv_case& c, const GemvCaseInfo& I, fs_gemv_out& o, hipStream_t st) {
+    using KT = KVT<WT>;
+    const ModelDims& d = I.d;
+    GemvDev dX, dG, dW, dS, dY, dCos, dSin, dK, dV, dTab, dState, dPart, dCfg, dTok, dCb, dIds, dPrompt;
+    SeqState hs;
+    std::memset(&hs, 0, sizeof(SeqState));
+    if (c.op == FS_GEMV_EMBED || c.op == FS_GEMV_FAST_EMBED) {
+        gemv_put_as<KT>(dTok, c.tok_emb, (size_t)c.tok_rows * c.dim, st);
+        dY.alloc(I.n_y, 4, st);
+        if (c.op == FS_GEMV_FAST_EMBED) {
+            dIds.put(c.ids, (size_t)c.n_ids, 4, st);
+            LmKernels<WT>::fast_embed(d, dTok.data(), (const uint32_t*)dIds.data(), c.n_ids, (float*)dY.data(), st);
+        } else {
+            if (c.n_cb > 0) gemv_put_as<KT>(dCb, c.cb_emb, (size_t)c.n_cb * c.cb_size * c.dim, st);
+            SampleCfg hc = {};
+            hc.sem_lo = c.sem_lo; hc.sem_hi = c.sem_hi;
+            dCfg.put(&hc, sizeof(SampleCfg), 1, st);
+            hs.step = c.step; hs.prompt_L = c.prompt_L;
+            if (c.use_prompt) dPrompt.put(c.tokens, (size_t)c.n_tokens, 4, st);
+            else for (int i = 0; i <= c.n_cb; ++i) hs.cur[i] = c.tokens[i];
+            dState.put(&hs, sizeof(SeqState), 1, st);
+            LmKernels<WT>::embed(d, dTok.data(), c.n_cb > 0 ? dCb.data() : nullptr, c.n_cb, c.cb_size, (const SampleCfg*)dCfg.data(),
+                                 c.use_prompt ? (const uint32_t*)dPrompt.data() : nullptr, (SeqState*)dState.data(), (float*)dY.data(), st);
+        }
+    } else {
+        dX.put(c.x, I.n_x, 4, st);
+        if (c.norm_w) dG.put(c.norm_w, I.n_x, 4, st);
+        gemv_put_as<WT>(dW, c.w, I.w_rows * I.w_cols, st);
+        const float* scale = nullptr;
+        if (std::is_same<WT, fp8_t>::value) { dS.put(c.wscale, I.w_rows, 4, st); scale = (const float*)dS.data(); }
+        LayerW w{};
+        w.cache_resident = c.cache_resident != 0;
+        dY.alloc(I.n_y, 4, st);
+        if (c.op == FS_GEMV_FFN_DOWN || c.op == FS_GEMV_WO_BODY) dY.up(c.y, I.n_y, st);
+        switch (c.op) {
+        case FS_GEMV_QKV: {
+            w.wqkv = dW.data(); w.attn_norm = (const float*)dG.data(); w.s_qkv = scale;
+            const size_t nr = (size_t)c.rope_rows * (c.Dh / 2);
+            dCos.put(c.cos_t, nr, 4, st); dSin.put(c.sin_t, nr, 4, st);
+            gemv_put_as<KT>(dK, c.k, I.n_pool, st); gemv_put_as<KT>(dV, c.v, I.n_pool, st);
+            dTab.put(c.page_table, (size_t)c.pt_len, 4, st);
+            hs.pos = c.pos; hs.rope_off = c.rope_off;
+            if (c.use_state) dState.put(&hs, sizeof(SeqState), 1, st);
+            const KVView kv{dK.data(), dV.data(), (const int*)dTab.data()};
+            LmKernels<WT>::qkv(d, (const float*)dX.data(), w, (const float*)dCos.data(), (const float*)dSin.data(),
+                               c.use_state ? (const SeqState*)dState.data() : nullptr, c.use_state ? 0 : c.pos, c.use_state ? 0 : c.pos + c.rope_off,
+                               (float*)dY.data(), kv, st);
+            break;
+        }
+        case FS_GEMV_FFN_UP:
+            w.w13 = dW.data(); w.ffn_norm = (const float*)dG.data(); w.s_13 = scale;
+            LmKernels<WT>::ffn_up(d, (const float*)dX.data(), w, (float*)dY.data(), st);
+            break;
+        case FS_GEMV_FFN_DOWN:
+            w.w2 = dW.data(); w.s_2 = scale;
+            LmKernels<WT>::ffn_down(d, (const float*)dX.data(), w, (float*)dY.data(), st);
+            break;
+        case FS_GEMV_HEAD:
+            LmKernels<WT>::head(d, (const float*)dX.data(), (const float*)dG.data(), dW.data(), scale, c.n_rows, (float*)dY.data(), st);
+            break;
+        default: {  // FS_GEMV_WO_BODY: one chunk per head, {o = x, m = 0, l = 1}, position 0 -> merge weight __expf(0) / (1 * __expf(0))
+            w.wo = dW.data(); w.s_o = scale;
+            std::vector<float> part((size_t)c.H * (c.Dh + 2));
+            for (int h = 0; h < c.H; ++h) {
+                for (int e = 0; e < c.Dh; ++e) part[(size_t)h * (c.Dh + 2) + e] = c.x[h * c.Dh + e];
+                part[(size_t)h * (c.Dh + 2) + c.Dh] = 0.f; part[(size_t)h * (c.Dh + 2) + c.Dh + 1] = 1.f;
+            }
+            dPart.put(part.data(), part.size(), 4, st);
+            dState.put(&hs, sizeof(SeqState), 1, st);  // pos = 0: T = 1, one chunk
+            LmKernels<WT>::wo(d, (const float*)dPart.data(), 1, 1, (const SeqState*)dState.data(), nullptr, KVView{nullptr, nullptr, nullptr}, 0, w,
+                              (float*)dY.data(), st);
+            break;
+        }
+        }
+    }
+    if (o.y) FS_HIP(hipMemcpyAsync(o.y, dY.data(), I.n_y * 4, hipMemcpyDeviceToHost, st));
+    std::vector<KT> hk(I.n_pool), hv(I.n_pool);
+    if (I.n_pool) {
+        FS_HIP(hipMemcpyAsync(hk.data(), dK.data(), I.n_pool * sizeof(KT), hipMemcpyDeviceToHost, st));
+        FS_HIP(hipMemcpyAsync(hv.data(), dV.data(), I.n_pool * sizeof(KT), hipMemcpyDeviceToHost, st));
+    }
+    FS_HIP(hipStreamSynchronize(st));
+    for (size_t i = 0; i < I.n_pool; ++i) { if (o.k) o.k[i] = gemv_f32<KT>(hk[i]); if (o.v) o.v[i] = gemv_f32<KT>(hv[i]); }
+    bool ok = true;
+    for (const GemvDev* b : {&dY, &dK, &dV}) ok = b->intact(st) && ok;
+    o.guard_ok = ok ? 1 : 0;
+}
+}  // namespace
+
+void gemv_selftest(int device, const fs_gemv_case& c, fs_gemv_out& o) {
+    GemvCaseInfo I;
+    gemv_validate(c, I);
+    std::snprintf(o.variant, o.variant_cap, "%s", I.name.c_str());
+    o.grid[0] = (int32_t)I.gx; o.grid[1] = 1; o.grid[2] = 1;
+    o.n_y = I.n_y; o.n_pool = I.n_pool;
+    if (c.plan_only) return;
+    gemv_req((!o.y || o.y_cap >= I.n_y) && ((!o.k && !o.v) || o.pool_cap >= I.n_pool), "an output capacity is too small");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw Error("no HIP device visible: libfishrt has no CPU fallback (MI355X / gfx950 required)");
+    FS_REQUIRE(device >= 0 && device < ndev, "device_id out of range");
+    FS_HIP(hipSetDevice(device));
+    hipStream_t st = nullptr;
+    FS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } sg{st};
+    if (c.wt == FS_GEMV_WT_F32) gemv_run<float>(c, I, o, st);
+    else if (c.wt == FS_GEMV_WT_BF16) gemv_run<bf16_t>(c, I, o, st);
+    else gemv_run<fp8_t>(c, I, o, st);
+}
 
 }  // namespace fs

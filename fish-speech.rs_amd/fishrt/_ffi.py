@@ -74,6 +74,20 @@ class GemmOut(C.Structure):  # fs_gemm_out: where fs_selftest_gemm leaves its re
                [("grid", C.c_int32 * 3), ("guard_ok", C.c_int32)]
 
 
+class GemvCase(C.Structure):  # fs_gemv_case: one batch-1 node launcher call for fs_selftest_gemv
+    _fields_ = [(n, C.c_int32) for n in ("op", "wt", "plan_only", "cache_resident", "dim", "inter", "H", "Hk", "Dh", "n_rows", "pos", "rope_off",
+                                         "use_state", "n_pages", "pt_len", "rope_rows", "n_cb", "cb_size", "tok_rows", "prompt_L", "step",
+                                         "use_prompt", "n_tokens", "n_ids")] + \
+               [("sem_lo", C.c_uint32), ("sem_hi", C.c_uint32), ("eps", C.c_float), ("reserved", C.c_int32)] + \
+               [(n, C.POINTER(C.c_float)) for n in ("x", "norm_w", "w", "wscale", "y", "cos_t", "sin_t", "k", "v", "tok_emb", "cb_emb")] + \
+               [("page_table", C.POINTER(C.c_int32)), ("tokens", C.POINTER(C.c_uint32)), ("ids", C.POINTER(C.c_uint32))]
+
+
+class GemvOut(C.Structure):  # fs_gemv_out: where fs_selftest_gemv leaves its results
+    _fields_ = [(n, C.POINTER(C.c_float)) for n in ("y", "k", "v")] + [("variant", C.c_char_p)] + \
+               [(n, C.c_size_t) for n in ("y_cap", "pool_cap", "variant_cap", "n_y", "n_pool")] + [("grid", C.c_int32 * 3), ("guard_ok", C.c_int32)]
+
+
 FRAME_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32))
 
 # every symbol include/fishrt.h declares (tests/test_abi.py checks the library exports all of them)
@@ -88,6 +102,7 @@ SYMBOLS = ["fs_last_error", "fs_version", "fs_device_count", "fs_lm_create", "fs
            "fs_lm_session_add_traced", "fs_lm_session_poll_trace",
            "fs_lm_session_poll_alts", "fs_selftest_alt_rows",
            "fs_selftest_conv1d", "fs_selftest_codec_op", "fs_selftest_codec_encode_stage", "fs_selftest_attn", "fs_selftest_gemm",
+           "fs_selftest_gemv",
            "fs_lm_weights_fingerprint", "fs_lm_session_prefix_export", "fs_lm_session_prefix_import",
            "fs_lm_session_prefix_from_slot", "fs_lm_session_last_frame",
            "fs_codec_create", "fs_codec_destroy", "fs_codec_load_safetensors", "fs_codec_load_synthetic",
@@ -159,6 +174,11 @@ ATTN_PROTOTYPES = {
 FS_GEMM_PREP, FS_GEMM_ROWS, FS_GEMM_DOWN = range(3)
 GEMM_EPI = {n: i for i, n in enumerate(("STORE", "RESIDUAL", "SWIGLU", "QKV", "RESIDUAL_NORM", "SWIGLU_RMS", "QKV_RMS", "STORE_RMS", "QKV_SEQ"))}
 GEMM_PROTOTYPES = {"fs_selftest_gemm": [C.c_int, C.POINTER(GemmCase), C.POINTER(GemmOut)]}
+
+# fs_selftest_gemv (ops, weight types: include/fishrt.h)
+GEMV_OPS = {n: i for i, n in enumerate(("QKV", "FFN_UP", "FFN_DOWN", "HEAD", "WO_BODY", "EMBED", "FAST_EMBED"))}
+GEMV_WT = {"f32": 0, "bf16": 1, "fp8": 2}
+GEMV_PROTOTYPES = {"fs_selftest_gemv": [C.c_int, C.POINTER(GemvCase), C.POINTER(GemvOut)]}
 
 # ... and of the calls that make a prefix out of a slot's history
 HISTORY_PROTOTYPES = {
@@ -249,7 +269,7 @@ def lib():
         L.fs_comm_destroy.argtypes = [C.c_void_p]
         L.fs_lm_destroy.argtypes = [C.c_void_p]
         L.fs_codec_destroy.argtypes = [C.c_void_p]
-        for name, argtypes in {**SCORE_PROTOTYPES, **TRACE_PROTOTYPES, **ALTS_PROTOTYPES, **CONV_PROTOTYPES, **CODEC_OP_PROTOTYPES, **ATTN_PROTOTYPES, **GEMM_PROTOTYPES, **HISTORY_PROTOTYPES,
+        for name, argtypes in {**SCORE_PROTOTYPES, **TRACE_PROTOTYPES, **ALTS_PROTOTYPES, **CONV_PROTOTYPES, **CODEC_OP_PROTOTYPES, **ATTN_PROTOTYPES, **GEMM_PROTOTYPES, **GEMV_PROTOTYPES, **HISTORY_PROTOTYPES,
                                **RESAMPLE_PROTOTYPES, **TSM_PROTOTYPES, **LOUD_PROTOTYPES}.items():
             if hasattr(L, name):  # (an older build loaded through LIB_PATH -- tools/attn_paths_dump.py --lib -- may lack the newest entry points)
                 getattr(L, name).argtypes = argtypes

@@ -295,6 +295,58 @@ typedef struct fs_gemm_out {
 } fs_gemm_out;
 int fs_selftest_gemm(int device_id, const fs_gemm_case* c, fs_gemm_out* out);
 
+/* ONE launcher call of the batch-1 node kernels (csrc/lm_kernels.hip: LmKernels::qkv / ffn_up / ffn_down / head / wo / embed / fast_embed) on
+ * caller-provided host data, and nothing else.  All tensors f32 row-major unless stated.  wt: FS_GEMV_WT_F32 / _BF16 / _FP8 selects
+ * LmKernels<WT>; the KV cache and the embedding tables are f32 for F32 and bf16 otherwise.  Weights `w` are f32 values that must already lie
+ * on the weight type's grid (bf16 / e4m3fn; anything else is an error), fp8 also needs wscale, one f32 scale per weight row.
+ *   FS_GEMV_QKV         x [dim], norm_w [dim], eps, w [(H + 2 Hk) Dh][dim], cos_t / sin_t [rope_rows][Dh / 2], the pools k / v
+ *                       [n_pages][Hk][64][Dh] (values of the KV type), page_table int32 [pt_len].  use_state != 0: position and RoPE offset
+ *                       come from a device SeqState {pos, rope_off} (the slow path); use_state == 0: a null state and pos_static = pos,
+ *                       rope_static = pos + rope_off (the fast decoder).  out.y = q [H Dh]; out.k / out.v = both pools after the call.
+ *   FS_GEMV_FFN_UP      x [dim], norm_w [dim], eps, w [2 inter][dim] row-interleaved (w1[r], w3[r]) -> out.y = act [inter]
+ *   FS_GEMV_FFN_DOWN    x = act [inter], w [dim][inter], y = the residual stream [dim] -> out.y = y + s (W act) [dim]
+ *   FS_GEMV_HEAD        x [dim], norm_w [dim], eps, w [n_rows][dim] -> out.y = logits [n_rows]
+ *   FS_GEMV_WO_BODY     LmKernels::wo with fused_T = 0, nc_launch = 1 and host-written partials {o = x, m = 0, l = 1} of every head at
+ *                       position 0: the merge weight is exactly 1 and the call computes y + s (W x).  x [dim], w [dim][dim], y [dim],
+ *                       dim == H Dh -> out.y [dim]
+ *   FS_GEMV_EMBED       tok_emb [tok_rows][dim], cb_emb [n_cb cb_size][dim] (values of the KV type), sem_lo / sem_hi.  use_prompt != 0:
+ *                       tokens = the staged prompt, uint32 [n_tokens], token c of the column at tokens[step + c * prompt_L] (SeqState
+ *                       {step, prompt_L}); use_prompt == 0: tokens = SeqState::cur, uint32 [n_cb + 1].  out.y = x [dim]
+ *   FS_GEMV_FAST_EMBED  tok_emb = the fast embedding table [tok_rows][dim], ids uint32 [n_ids] -> out.y [n_ids][dim]
+ * cache_resident selects the weight-load policy of the four launchers that have one (LayerW::cache_resident).  Every device buffer a
+ * launch writes (outputs, both pools) lies between 256-element guards of 0xFF bytes and is itself 0xFF bytes (NaN) where the caller
+ * provides nothing; out.guard_ok = 1 iff every guard is intact.  out.variant: GemvPlan::name ("qkv/bf16/K1024/w2/nt",
+ * "down/fp8/K4096/ks4/res", "head/f32/K128/w4", "wo/bf16/K1024/w4/dh64/nt", "up/f32/K256/w4/res", "embed/bf16", "fast_embed/f32");
+ * out.grid: the launch grid.  The case is VALIDATED BEFORE ANY DEVICE CALL (widths, geometry, every page id, the page-table slot of pos,
+ * the RoPE row, every token id); a bad case is an error and nothing is launched.  plan_only != 0: validate, return name and grid, touch no
+ * device.  Diagnostics / parity tests. */
+enum { FS_GEMV_QKV = 0, FS_GEMV_FFN_UP = 1, FS_GEMV_FFN_DOWN = 2, FS_GEMV_HEAD = 3, FS_GEMV_WO_BODY = 4, FS_GEMV_EMBED = 5,
+       FS_GEMV_FAST_EMBED = 6 };
+enum { FS_GEMV_WT_F32 = 0, FS_GEMV_WT_BF16 = 1, FS_GEMV_WT_FP8 = 2 };
+typedef struct fs_gemv_case {
+    int32_t op, wt, plan_only, cache_resident;
+    int32_t dim, inter, H, Hk;
+    int32_t Dh, n_rows, pos, rope_off;
+    int32_t use_state, n_pages, pt_len, rope_rows;
+    int32_t n_cb, cb_size, tok_rows, prompt_L;
+    int32_t step, use_prompt, n_tokens, n_ids;
+    uint32_t sem_lo, sem_hi;
+    float eps;
+    int32_t reserved;
+    const float *x, *norm_w, *w, *wscale, *y, *cos_t, *sin_t, *k, *v, *tok_emb, *cb_emb;
+    const int32_t* page_table;
+    const uint32_t *tokens, *ids;
+} fs_gemv_case;
+typedef struct fs_gemv_out {
+    float *y, *k, *v;
+    char* variant;
+    size_t y_cap, pool_cap, variant_cap;
+    size_t n_y, n_pool;
+    int32_t grid[3];
+    int32_t guard_ok;
+} fs_gemv_out;
+int fs_selftest_gemv(int device_id, const fs_gemv_case* c, fs_gemv_out* out);
+
 /* Stage tap of the encoder on a LOADED handle: runs fs_codec_encode's device path on the clip exactly as fs_codec_encode does (same buffers,
  * same launches, the codes are computed and dropped) and copies ONE intermediate tensor to the host:
  *   stage -1     the log-mel [160][F], F = mel frames of the clip
