@@ -149,6 +149,14 @@ int fs_selftest_gemv(int device_id, const fs_gemv_case* c, fs_gemv_out* out) {
     out->grid[0] = out->grid[1] = out->grid[2] = 0;
     FS_TRY(fs::gemv_selftest(device_id, *c, *out))
 }
+static_assert(sizeof(fs_sample_case) == 28 * 4 + 10 * 8, "fs_sample_case is 20 x int32, one float, one int32, the 5-word token layout, one int32 and 10 pointers (fishrt/_ffi.py: SampleCase)");
+static_assert(sizeof(fs_sample_out) == 3 * 13 * 8 + 2 * 4, "fs_sample_out is 13 pointers, 2 x 13 size_t and 2 x int32 (fishrt/_ffi.py: SampleOut)");
+int fs_selftest_sample_frames(int device_id, const fs_sample_case* c, fs_sample_out* out) {
+    FS_ARG(c && out, "null argument");
+    out->n_launches = 0; out->guard_ok = 0;
+    for (int i = 0; i < FS_SAMPLE_OUT_COUNT; ++i) out->need[i] = 0;
+    FS_TRY(fs::sample_frames_selftest(device_id, *c, *out))
+}
 
 // ---- replica fan-out over RCCL (fs_comm.h)
 int fs_comm_unique_id(uint8_t id_out[FS_COMM_ID_BYTES]) { FS_ARG(id_out, "null argument"); FS_TRY(fs::Comm::unique_id(id_out)) }

@@ -1092,13 +1092,7 @@ class LM final : public LMBase {
     // what a slot of a FS_SESSION_PER_SLOT session may sample with: the boundary of the in-launch samplers (fishrt.h: fs_lm_generate)
     // In a wide session (FS_SESSION_WIDE_SAMPLER): greedy, or temp > 0 with any top_k and any finite top_p.
     void require_slot_sampling(const fs_sampling& s, bool wide) const {
-        if (wide) {
-            if (!std::isfinite(s.temp) || s.temp < 0.0) throw Error("FS_SESSION_WIDE_SAMPLER: temp must be finite and >= 0 (0 = greedy)");
-            if (!std::isfinite(s.top_p)) throw Error("FS_SESSION_WIDE_SAMPLER: top_p must be finite");
-            return;
-        }
-        const bool ok = s.temp == 0.0 || (s.temp > 0.0 && s.top_k > 0 && s.top_k <= 256);
-        if (!ok) throw Error("FS_SESSION_PER_SLOT: a slot samples greedy (temp == 0) or with temp > 0 and 0 < top_k <= 256 (the in-launch samplers' limit)");
+        if (const char* e = slot_sampling_error(s.temp, s.top_p, s.top_k, wide)) throw Error(e);
     }
     // the states of a slot, as sess_left_ spells them (>= 0: iterations left to a live slot), and the check of the entry points that take one
     static constexpr int kSlotFree = -1, kSlotPrefilling = -2;
@@ -1735,11 +1729,7 @@ class LM final : public LMBase {
                 FS_HIP(hipStreamSynchronize(st_));  // (rng / budget are locals)
             } else {
                 if (sess_.slots) {  // the slot's settings, a StdRng stream at word 0 (no look-ahead word yet) and empty repetition-penalty windows
-                    SlotRng sr;
-                    std::memset(&sr, 0xFF, sizeof(sr));
-                    sr.rng = RngState{};
-                    seed_from_u64(seed, sr.rng.key);
-                    up_rng.push_back(sr);
+                    up_rng.push_back(slot_rng_fresh(seed));
                     FS_HIP(hipMemcpyAsync(d_scfg_.as<SampleCfg>() + b, &cfg, sizeof(SampleCfg), hipMemcpyHostToDevice, st_));
                     FS_HIP(hipMemcpyAsync(d_srng_.as<SlotRng>() + b, &up_rng.back(), sizeof(SlotRng), hipMemcpyHostToDevice, st_));
                     launch_reppen_reset(srp_.view(b), a_.num_codebooks, a_.codebook_size, st_);
@@ -2174,8 +2164,7 @@ class LM final : public LMBase {
     }
     // seed -> ChaCha key -> a device RngState.  The copy is asynchronous and reads `host`: the caller's, alive until the stream has been waited for
     void upload_rng(uint64_t seed, RngState& host, RngState* dst, hipStream_t st) {
-        host = RngState{};
-        seed_from_u64(seed, host.key);
+        host = rng_fresh(seed);
         FS_HIP(hipMemcpyAsync(dst, &host, sizeof(host), hipMemcpyHostToDevice, st));
     }
     // one prompt [C + 1][L] left-padded with <|im_end|>/0 to Lmax columns (static_batch.rs:68-111; the pad mask is built but never applied,
@@ -2221,14 +2210,11 @@ class LM final : public LMBase {
     };
     void require_loaded() { FS_REQUIRE(loaded_, "weights not loaded: call fs_lm_load_safetensors or fs_lm_load_synthetic first"); }
 
-    static int clamp_top_k(uint64_t top_k) { return (int)std::min<uint64_t>(top_k, 1u << 30); }
+    // the handle's token layout as the shared sampler setup (lm_kernels.h) takes it
+    TokenLayout layout() const { return TokenLayout{t_.im_end_id, t_.pad_id, t_.semantic_start_id, t_.semantic_end_id, t_.has_semantic_end != 0}; }
     // base_cfg() + one request's sampler settings; the callers set what differs (rep_pen = 1 in the batch paths, session, batch_*)
     SampleCfg make_cfg(const fs_sampling& s, uint32_t flags) const {
-        SampleCfg c = base_cfg();
-        c.temp = (float)s.temp; c.top_p = (float)s.top_p; c.top_p64 = s.top_p;
-        c.top_k = clamp_top_k(s.top_k);
-        c.rep_pen = s.repetition_penalty; c.ignore_eos = (flags & FS_GEN_IGNORE_EOS) ? 1 : 0;
-        return c;
+        return sample_cfg_make(layout(), s.temp, s.top_p, s.top_k, s.repetition_penalty, (flags & FS_GEN_IGNORE_EOS) != 0);
     }
     // Iteration budget of a request of L_total prompt positions behind n_cached cached ones: the prefill iteration + one per k with
     // L_total + k - 1 <= max_new (single_batch.rs:61,77,193-197; static_batch.rs:122,262-267), clamped to the iterations that fit the RoPE
@@ -2242,17 +2228,7 @@ class LM final : public LMBase {
         FS_REQUIRE(b.n_iter <= out_cap_, "generation longer than the output staging buffer");
         return b;
     }
-    SampleCfg base_cfg() const {
-        SampleCfg c = {};
-        c.temp = 0.f; c.top_p = 1.f; c.top_k = 0; c.rep_pen = 1.f; c.ignore_eos = 0;
-        c.im_end_id = t_.im_end_id;
-        c.audio_base = legacy_ ? t_.im_end_id : t_.semantic_start_id - 1;
-        c.sem_lo = t_.semantic_start_id;
-        c.sem_hi = t_.has_semantic_end ? t_.semantic_end_id : t_.semantic_start_id;  // dual_ar.rs:554-559
-        c.legacy = legacy_ ? 1 : 0;
-        c.pad_id = t_.pad_id;
-        return c;
-    }
+    SampleCfg base_cfg() const { return sample_cfg_base(layout()); }
 
     void validate_tokens(const uint32_t* toks, size_t, int B, int L) {
         const int C1 = a_.num_codebooks + 1;

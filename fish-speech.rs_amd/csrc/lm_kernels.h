@@ -24,6 +24,8 @@ struct fs_gemm_case;
 struct fs_gemm_out;
 struct fs_gemv_case;
 struct fs_gemv_out;
+struct fs_sample_case;
+struct fs_sample_out;
 
 namespace fs {
 
@@ -300,6 +302,53 @@ struct SlotRng {       // per-slot sampler stream of a FS_SESSION_PER_SLOT sessi
     uint32_t ahead_word[16];
 };
 
+// ---- sampler setup on the host, shared by the engine (lm_engine.hip) and the sampler-node test hook (sample_frames_selftest): the
+// SampleCfg of a token layout and of one request's settings, a request's StdRng stream, a freshly activated slot's stream
+struct TokenLayout { uint32_t im_end_id, pad_id, semantic_start_id, semantic_end_id; bool has_semantic_end; };
+inline SampleCfg sample_cfg_base(const TokenLayout& t) {
+    const bool legacy = !t.has_semantic_end;  // Fish <= 1.4: slow token is a 2-way {pad, im_end} draw (single_batch.rs:104-124)
+    SampleCfg c = {};
+    c.temp = 0.f; c.top_p = 1.f; c.top_k = 0; c.rep_pen = 1.f; c.ignore_eos = 0;
+    c.im_end_id = t.im_end_id;
+    c.audio_base = legacy ? t.im_end_id : t.semantic_start_id - 1;
+    c.sem_lo = t.semantic_start_id;
+    c.sem_hi = t.has_semantic_end ? t.semantic_end_id : t.semantic_start_id;  // dual_ar.rs:554-559
+    c.legacy = legacy ? 1 : 0;
+    c.pad_id = t.pad_id;
+    return c;
+}
+inline int clamp_top_k(uint64_t top_k) { return (int)(top_k < (1u << 30) ? top_k : (1u << 30)); }
+// sample_cfg_base + one request's sampler settings; the callers set what differs (rep_pen = 1 in the batch paths, session, batch_*)
+inline SampleCfg sample_cfg_make(const TokenLayout& t, double temp, double top_p, uint64_t top_k, float rep_pen, bool ignore_eos) {
+    SampleCfg c = sample_cfg_base(t);
+    c.temp = (float)temp; c.top_p = (float)top_p; c.top_p64 = top_p;
+    c.top_k = clamp_top_k(top_k);
+    c.rep_pen = rep_pen; c.ignore_eos = ignore_eos ? 1 : 0;
+    return c;
+}
+inline RngState rng_fresh(uint64_t seed) {  // seed -> ChaCha key, stream position 0
+    RngState r = {};
+    seed_from_u64(seed, r.key);
+    return r;
+}
+inline SlotRng slot_rng_fresh(uint64_t seed) {  // a slot's stream at its activation: word 0, no look-ahead word yet (every tag ~0)
+    SlotRng sr;
+    for (int i = 0; i < 16; ++i) { sr.ahead_at[i] = ~0ull; sr.ahead_word[i] = ~0u; }
+    sr.rng = rng_fresh(seed);
+    return sr;
+}
+// what a slot of a FS_SESSION_PER_SLOT session may sample with: the boundary of the in-launch samplers (fishrt.h: fs_lm_generate); in a
+// wide session (FS_SESSION_WIDE_SAMPLER): greedy, or temp > 0 with any top_k and any finite top_p.  null = accepted, else the error text
+inline const char* slot_sampling_error(double temp, double top_p, uint64_t top_k, bool wide) {
+    if (wide) {
+        if (!(temp >= 0.0) || temp > 1.7976931348623157e308) return "FS_SESSION_WIDE_SAMPLER: temp must be finite and >= 0 (0 = greedy)";
+        if (!(top_p >= -1.7976931348623157e308 && top_p <= 1.7976931348623157e308)) return "FS_SESSION_WIDE_SAMPLER: top_p must be finite";
+        return nullptr;
+    }
+    const bool ok = temp == 0.0 || (temp > 0.0 && top_k > 0 && top_k <= 256);
+    return ok ? nullptr : "FS_SESSION_PER_SLOT: a slot samples greedy (temp == 0) or with temp > 0 and 0 < top_k <= 256 (the in-launch samplers' limit)";
+}
+
 template <typename WT>
 struct SampleKernels {
     // slow token: logits over [im_end, V) (utils.rs:13-16) -> token = idx + im_end; sets done; copies x -> xf; *hid_slot (device
@@ -416,6 +465,8 @@ void attn_selftest(int device, const fs_attn_case& c, float* out, size_t out_cap
 void gemm_selftest(int device, const fs_gemm_case& c, fs_gemm_out& out);
 // test hook behind fs_selftest_gemv (include/fishrt.h; harness at the bottom of lm_kernels.hip)
 void gemv_selftest(int device, const fs_gemv_case& c, fs_gemv_out& out);
+// test hook behind fs_selftest_sample_frames (include/fishrt.h; harness at the bottom of lm_sample.hip)
+void sample_frames_selftest(int device, const fs_sample_case& c, fs_sample_out& out);
 // test hook behind fs_selftest_sample_rows (include/fishrt.h)
 void debug_sample_rows(int device, const float* logits, int B, int n, double temp, double top_p, uint64_t top_k, uint64_t seed,
                        int call_index, uint32_t* out);

@@ -4,9 +4,12 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <algorithm>
+#include <cmath>
+#include <cstring>
 #include <string>
 #include <vector>
 
+#include "../../include/fishrt.h"
 #include "fs_common.h"
 #include "lm_kernels.h"
 #include "lm_dev.h"
@@ -391,7 +394,8 @@ __device__ int wave_pick(const float* w, int cnt, float* cum, RngState* rng, uin
 }
 
 // Block-wide selection of one index from `n` logits held in LDS (already penalised / masked).
-//  temp == 0: host-ArgMax rule of candle's LogitsProcessor (max_by(total_cmp)): LAST maximal index wins.
+//  temp == 0: the argmax by IEEE comparison, FIRST (first_max: the batch rule, the only one production reaches here) or LAST index;
+//             the host-ArgMax rule of the single-sequence and slot paths (totalOrder) is greedy_pick's / slot_greedy_pick's.
 //  temp  > 0: softmax(logits / temp) -> top-k (ties: lower index first) -> top-p -> WeightedIndex draw, evaluated in
 //             ascending-index order with the StdRng stream (sampling/mod.rs:51-132).  Identical decision procedure to
 //             oracle::LogitsProcessor::sample; the softmax denominator is accumulated in f64 on both sides so that
@@ -613,34 +617,35 @@ __device__ int block_sample(float* lg /*LDS [n]*/, int n, const SampleCfg& c, Rn
     }
 }
 
-// Greedy pick (temp == 0, host ArgMax rule: LAST maximal index) without the three block barriers of block_sample: a thread's
-// candidates (indices tid + j * SAMPLE_THREADS) stay in registers, a wave reduces (value, then index) by DPP, lane 0 of every wave
-// does one 64-bit LDS atomicMax on {order-preserving value bits : index}, ONE barrier, everybody reads the winner.  *s_key must
-// have been zeroed before the previous barrier.  (A 16-wave barrier phase costs ~0.4 us on this chip.)
+// Greedy pick (temp == 0, host ArgMax rule, fishrt.h: the maximum under IEEE totalOrder -- -0.0 < +0.0 -- and the LAST index among
+// identical bit patterns) without the three block barriers of block_sample: a thread's candidates (indices tid + j * SAMPLE_THREADS)
+// stay in registers as total-order keys, a wave reduces (key, then index) by DPP, lane 0 of every wave does one 64-bit LDS atomicMax on
+// {key : index}, ONE barrier, everybody reads the winner.  The same order at every level: thread, wave, block.  *s_key must have been
+// zeroed before the previous barrier.  (A 16-wave barrier phase costs ~0.4 us on this chip.)
 __device__ __forceinline__ int dpp_wave_max_int(int v) {
     v = max(v, __builtin_amdgcn_mov_dpp(v, DPP_XOR1, 0xF, 0xF, false)); v = max(v, __builtin_amdgcn_mov_dpp(v, DPP_XOR2, 0xF, 0xF, false));
     v = max(v, __builtin_amdgcn_mov_dpp(v, DPP_HALF_MIRROR, 0xF, 0xF, false)); v = max(v, __builtin_amdgcn_mov_dpp(v, DPP_MIRROR, 0xF, 0xF, false));
     return max(max(__builtin_amdgcn_readlane(v, 15), __builtin_amdgcn_readlane(v, 31)), max(__builtin_amdgcn_readlane(v, 47), __builtin_amdgcn_readlane(v, 63)));
 }
+// IEEE-754 totalOrder as a signed integer key: key(a) < key(b) iff a.total_cmp(b) is Less (-0.0 < +0.0; identical bit patterns are equal)
+__device__ __forceinline__ int total_key(float v) {
+    const int s = __float_as_int(v);
+    return s ^ ((s >> 31) & 0x7FFFFFFF);
+}
 __device__ __forceinline__ int greedy_pick(const float (&val)[SAMPLE_MAXN / SAMPLE_THREADS], int n, unsigned long long* s_key) {
     const int tid = threadIdx.x;
-    float bv = -INFINITY;
+    int bk = (int)0x80000000;
     int bi = -1;
 #pragma unroll
     for (int j = 0; j < SAMPLE_MAXN / SAMPLE_THREADS; ++j) {
         const int i = tid + j * SAMPLE_THREADS;
-        if (i < n && (bi < 0 || !(val[j] < bv))) { bv = val[j]; bi = i; }  // ascending i per thread: the later equal value wins
+        const int k = total_key(val[j]);
+        if (i < n && (bi < 0 || k >= bk)) { bk = k; bi = i; }  // ascending i per thread: the later identical value wins
     }
-    float wm = bv;
-    wm = fmaxf(wm, dpp_mov<DPP_XOR1>(wm)); wm = fmaxf(wm, dpp_mov<DPP_XOR2>(wm));
-    wm = fmaxf(wm, dpp_mov<DPP_HALF_MIRROR>(wm)); wm = fmaxf(wm, dpp_mov<DPP_MIRROR>(wm));
-    wm = fmaxf(fmaxf(readlane(wm, 15), readlane(wm, 31)), fmaxf(readlane(wm, 47), readlane(wm, 63)));
-    const int ci = dpp_wave_max_int((bi >= 0 && bv == wm) ? bi : -1);
-    if ((tid & 63) == 0 && ci >= 0) {
-        uint32_t u = __float_as_uint(wm);
-        u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;  // unsigned order == float order
-        atomicMax(s_key, ((unsigned long long)u << 32) | (unsigned long long)(uint32_t)ci);
-    }
+    const int wk = dpp_wave_max_int(bk);
+    const int ci = dpp_wave_max_int((bi >= 0 && bk == wk) ? bi : -1);
+    if ((tid & 63) == 0 && ci >= 0)  // (key with the sign bit flipped: unsigned order == total order)
+        atomicMax(s_key, ((unsigned long long)((uint32_t)wk ^ 0x80000000u) << 32) | (unsigned long long)(uint32_t)ci);
     __syncthreads();
     return (int)(*s_key & 0xFFFFFFFFull);
 }
@@ -1074,7 +1079,7 @@ __device__ __forceinline__ uint32_t slot_word(const SlotRng* rg, int decision, u
     if (rg->ahead_at[decision] == at) return rg->ahead_word[decision];
     return chacha12_word(rg->rng.key, at);  // (block-uniform: every thread derives the same word)
 }
-// greedy_pick's rule (host ArgMax: the LAST maximal index) for bsample's blocked ownership (thread t owns candidates t * EPT ..): the
+// greedy_pick's rule (host ArgMax: totalOrder, the LAST index among identical bit patterns) for bsample's blocked ownership (thread t owns candidates t * EPT ..): the
 // block maximum of {order-preserving value bits : index}.  *s_key must have been zeroed before the previous barrier; one barrier.
 template <int EPT>
 __device__ __forceinline__ int slot_greedy_pick(const float (&lv)[EPT], int n, unsigned long long* s_key) {
@@ -1084,8 +1089,8 @@ __device__ __forceinline__ int slot_greedy_pick(const float (&lv)[EPT], int n, u
     for (int s = 0; s < EPT; ++s) {
         const int i = tid * EPT + s;
         if (i < n) {
-            uint32_t u = __float_as_uint(lv[s] + 0.f);  // (-0 -> +0: equal values, the later index wins)
-            u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;  // unsigned order == float order
+            uint32_t u = __float_as_uint(lv[s]);          // (the bit pattern as it is: -0 sorts below +0)
+            u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;  // unsigned order == total order
             const unsigned long long k = ((unsigned long long)u << 32) | (unsigned long long)(uint32_t)i;
             key = k > key ? k : key;
         }
@@ -2036,6 +2041,282 @@ void debug_sample_slots(int device, const float* logits, int S, int R, int n, co
     FS_HIP(hipMemcpy(out, d_out, sizeof(uint32_t) * (size_t)S * R, hipMemcpyDeviceToHost));
     FS_HIP(hipMemcpy(words_used, d_used, sizeof(unsigned long long) * S, hipMemcpyDeviceToHost));
     (void)hipFree(d_logits); (void)hipFree(d_cfg); (void)hipFree(d_seeds); (void)hipFree(d_out); (void)hipFree(d_used);
+}
+
+
+// ---- sampler-node test hook (fs_selftest_sample_frames, include/fishrt.h): F frames of the production launchers above on caller logits,
+// in the engine's order, the complete sampler state copied out after every launch.  The SampleCfg, the request stream and a slot's
+// activation come from the setup the engine uses (lm_kernels.h: sample_cfg_make, rng_fresh, slot_rng_fresh, slot_sampling_error).
+namespace {
+constexpr size_t kSampGuard = 1024;  // bytes: 256 f32 elements
+struct SampDev {  // device buffer of n bytes between two guards, all 0xFF bytes at first
+    void* p = nullptr;
+    size_t n = 0;
+    void alloc(size_t bytes, hipStream_t st) {
+        n = (bytes + 15) & ~(size_t)15;
+        FS_HIP(hipMalloc(&p, n + 2 * kSampGuard));
+        FS_HIP(hipMemsetAsync(p, 0xFF, n + 2 * kSampGuard, st));
+    }
+    char* data() const { return (char*)p + kSampGuard; }
+    template <typename T> T* as() const { return reinterpret_cast<T*>(data()); }
+    void up(const void* src, size_t bytes, hipStream_t st, size_t off = 0) {  // synchronous: the source may be a temporary
+        FS_HIP(hipMemcpyAsync(data() + off, src, bytes, hipMemcpyHostToDevice, st));
+        FS_HIP(hipStreamSynchronize(st));
+    }
+    void put(const void* src, size_t bytes, hipStream_t st) { alloc(bytes, st); up(src, bytes, st); }
+    bool intact(hipStream_t st) const {
+        if (!p) return true;
+        std::vector<uint8_t> g(2 * kSampGuard);
+        FS_HIP(hipMemcpyAsync(g.data(), p, kSampGuard, hipMemcpyDeviceToHost, st));
+        FS_HIP(hipMemcpyAsync(g.data() + kSampGuard, data() + n, kSampGuard, hipMemcpyDeviceToHost, st));
+        FS_HIP(hipStreamSynchronize(st));
+        for (uint8_t b : g) if (b != 0xFF) return false;
+        return true;
+    }
+    ~SampDev() { if (p) (void)hipFree(p); }
+};
+void samp_req(bool ok, const char* msg) { if (!ok) throw Error(std::string("sampler self-test: ") + msg); }
+static_assert(sizeof(SeqState) == 40 * 4, "fs_sample_case::state0 is the SeqState as 40 words");
+static_assert(sizeof(RngState) == 10 * 4 && sizeof(SlotRng) == 58 * 4, "FS_SAMPLE_OUT_RNG word counts");
+
+struct SampInfo {
+    bool single = false, rows = false, slots = false, wide = false, par = false, legacy = false;
+    int L = 0, Lf = 0, R = 0, hid_rows = 0;
+    size_t per[FS_SAMPLE_OUT_COUNT] = {};  // bytes per launch of every output
+    std::vector<SampleCfg> cfgs;
+};
+void sample_validate(const fs_sample_case& c, SampInfo& I) {
+    samp_req(c.family >= FS_SAMPLE_SINGLE && c.family <= FS_SAMPLE_SLOTS_WIDE, "unknown family");
+    samp_req(c.wt == FS_GEMV_WT_F32 || c.wt == FS_GEMV_WT_BF16, "wt must be f32 or bf16 (the table types)");
+    I.single = c.family == FS_SAMPLE_SINGLE || c.family == FS_SAMPLE_SINGLE_BATCHROW;
+    I.rows = c.family == FS_SAMPLE_ROWS || c.family == FS_SAMPLE_ROWS_PAR;
+    I.slots = c.family == FS_SAMPLE_SLOTS || c.family == FS_SAMPLE_SLOTS_WIDE;
+    I.wide = c.family == FS_SAMPLE_SLOTS_WIDE;
+    I.par = c.family == FS_SAMPLE_ROWS_PAR;
+    I.legacy = c.tokens.has_semantic_end == 0;
+    samp_req(c.B >= 1 && c.B <= 256 && c.F >= 1 && c.F <= 4096, "1 <= B <= 256, 1 <= F <= 4096");
+    samp_req(c.n_cb >= 1 && c.n_cb + 1 <= 16, "n_cb + 1 <= 16 (SeqState::cur, the words table)");
+    samp_req(c.cb_size >= 2 && c.n_slow >= 2 && c.ld >= c.n_slow, "cb_size >= 2, 2 <= n_slow <= ld");
+    samp_req(c.dim >= 1 && c.out_cap >= 1 && c.tok_rows >= 1, "dim, out_cap, tok_rows >= 1");
+    samp_req(c.samplings && c.seeds && c.ignore_eos && c.state0 && c.tok_emb && c.cb_emb && c.fast_emb && c.x && c.logits, "null argument");
+    samp_req(c.n_cfg == (I.slots ? c.B : 1), "n_cfg: B for the slot families, 1 otherwise");
+    if (I.single) {
+        samp_req(c.B == 1, "the single-sequence kernels take one row");
+        samp_req(c.n_slow <= SAMPLE_MAXN, "audio-range vocabulary larger than the sampler capacity");
+        samp_req(c.cb_size <= SAMPLE_MAXN, "codebook larger than the sampler capacity");
+        samp_req(!c.prep && !c.session && !c.cap_frames, "the single-sequence kernels have no prep epilogue, session mode or capture record");
+        if (c.family == FS_SAMPLE_SINGLE_BATCHROW)
+            samp_req(!I.legacy && c.batch_rows >= 1 && c.batch_row >= 0 && c.batch_row < c.batch_rows, "batch row: 0 <= batch_row < batch_rows, Fish 1.5 / generic layout");
+        else samp_req(c.batch_rows == 0 && c.batch_row == 0, "batch_rows / batch_row belong to SINGLE_BATCHROW");
+    } else {
+        samp_req(!c.hid && c.batch_rows == 0 && c.batch_row == 0, "hid / batch_rows belong to the single-sequence families");
+    }
+    if (I.rows) {
+        samp_req(!I.legacy, "the static-batch samplers need the Fish 1.5 / generic token layout");
+        samp_req(c.n_slow <= SAMPLE_MAXN, "audio-range vocabulary larger than the sampler capacity");
+        samp_req(c.cb_size <= SAMPLE_MAXN, "codebook larger than the sampler capacity");
+        samp_req(c.n_cb + 1 <= ROWS_WORDS_LD, "too many sample() calls per frame");
+        samp_req(!c.cap_frames, "the capture record belongs to the slot families");
+    }
+    if (I.slots) {
+        samp_req(c.n_slow <= PAR_THREADS * 4, "audio-range vocabulary outside the per-slot sampler capacity (2 .. 2048)");
+        samp_req(c.cb_size <= PAR_THREADS * 2, "codebook larger than the per-slot sampler capacity (1024)");
+        samp_req(!c.session, "session belongs to the row families (slots always freeze)");
+        samp_req(c.cap_frames >= 0 && (size_t)c.B * (size_t)c.cap_frames <= 64, "capture record: B x cap_frames <= 64");
+    }
+    if (I.legacy) samp_req(c.n_slow == 2, "Fish <= 1.4 layout: the slow logits are [pad, im_end]");
+    if (c.prep) samp_req(c.prep_g && c.dim <= 1024 && c.dim % 32 == 0 && c.B <= 32, "sampler-side RMSNorm of the next input row: dim <= 1024, dim % 32 == 0 (whole fragments), B <= 32");
+    // the SampleCfg of every row / slot, as the engine makes it
+    const TokenLayout lay{c.tokens.im_end_id, c.tokens.pad_id, c.tokens.semantic_start_id, c.tokens.semantic_end_id, c.tokens.has_semantic_end != 0};
+    if (!I.legacy) samp_req(lay.semantic_start_id >= 1, "semantic_start_id >= 1");
+    for (int i = 0; i < c.n_cfg; ++i) {
+        const fs_sampling& s = c.samplings[i];
+        samp_req(std::isfinite(s.temp) && s.temp >= 0.0 && std::isfinite(s.top_p) && std::isfinite(s.repetition_penalty) && s.repetition_penalty > 0.f,
+                 "temp finite and >= 0, top_p finite, repetition_penalty finite and > 0");
+        SampleCfg cfg = sample_cfg_make(lay, s.temp, s.top_p, s.top_k, s.repetition_penalty, c.ignore_eos[i] != 0);
+        if (c.family == FS_SAMPLE_SINGLE_BATCHROW) { cfg.batch_rows = c.batch_rows; cfg.batch_row = c.batch_row; cfg.batch_calls = c.n_cb + 1; }
+        if (I.rows) { cfg.rep_pen = 1.0f; cfg.session = c.session ? 1 : 0; }
+        if (I.slots) {
+            cfg.session = 1;
+            if (const char* e = slot_sampling_error(s.temp, s.top_p, s.top_k, I.wide)) throw Error(std::string("sampler self-test: ") + e);
+            if (!I.wide && s.temp > 0.0)
+                samp_req((int)s.top_k < c.cb_size && (I.legacy || (int)s.top_k < c.n_slow), "a narrow slot's top_k must be below its candidate counts (0 < top_k <= 256 < n)");
+        }
+        if (I.par) samp_req(rows_par_sampler_ok(s.temp, s.top_k, c.n_slow, c.cb_size), "settings outside the block-parallel row sampler (rows_par_sampler_ok)");
+        I.cfgs.push_back(cfg);
+    }
+    // every token id the tables can be indexed with: the slow picks, <|im_end|>, pad, and the initial states' rows
+    const SampleCfg& c0 = I.cfgs[0];
+    samp_req(c0.im_end_id < (uint32_t)c.tok_rows, "im_end_id outside tok_emb");
+    if (I.legacy) samp_req(c0.pad_id < (uint32_t)c.tok_rows, "pad_id outside tok_emb");
+    else samp_req((uint64_t)c0.audio_base + (uint64_t)c.n_slow <= (uint64_t)c.tok_rows, "a slow candidate lies outside tok_emb");
+    int frame0 = 0;
+    for (int b = 0; b < c.B; ++b) {
+        const int32_t* s = c.state0 + (size_t)b * 40;
+        samp_req(s[0] >= 0 && s[2] >= 0 && s[3] >= 0 && s[3] <= 2 && s[4] >= 0 && (s[5] == 0 || s[5] == 1), "state0: pos, frame, n_out >= 0; done 0..2; have_prev 0 / 1");
+        samp_req((uint32_t)s[8] < (uint32_t)c.tok_rows && (uint32_t)s[24] < (uint32_t)c.tok_rows, "state0: a slow token outside tok_emb");
+        for (int i = 1; i <= c.n_cb; ++i)
+            samp_req((uint32_t)s[8 + i] < (uint32_t)c.cb_size && (uint32_t)s[24 + i] < (uint32_t)c.cb_size, "state0: a code outside the codebook");
+        frame0 = std::max(frame0, s[2]);
+    }
+    I.Lf = (I.par ? 1 : 0) + 1 + c.n_cb;
+    I.L = c.F * I.Lf;
+    I.R = I.slots ? c.B : (I.single ? 1 : 0);
+    I.hid_rows = c.hid ? frame0 + c.F : 0;
+    const size_t B = (size_t)c.B, C = (size_t)c.n_cb;
+    I.per[FS_SAMPLE_OUT_STATES] = B * sizeof(SeqState);
+    I.per[FS_SAMPLE_OUT_RING] = (size_t)I.R * C * 17 * 4;
+    I.per[FS_SAMPLE_OUT_META] = (size_t)I.R * C * 2 * 4;
+    I.per[FS_SAMPLE_OUT_MASK] = (size_t)I.R * C * c.cb_size * 4;
+    I.per[FS_SAMPLE_OUT_RNG] = I.slots ? B * sizeof(SlotRng) : sizeof(RngState);
+    I.per[FS_SAMPLE_OUT_WORDS] = I.par ? B * ROWS_WORDS_LD * 4 : 0;
+    I.per[FS_SAMPLE_OUT_XF] = I.per[FS_SAMPLE_OUT_X] = B * c.dim * 4;
+    I.per[FS_SAMPLE_OUT_PREP] = c.prep ? (size_t)2 * 32 * c.dim * 2 : 0;
+    I.per[FS_SAMPLE_OUT_EPOCH] = c.prep ? 8 : 0;
+    I.per[FS_SAMPLE_OUT_CODES] = B * C * c.out_cap * 4;
+    I.per[FS_SAMPLE_OUT_HID] = (size_t)I.hid_rows * c.dim * 4;
+    I.per[FS_SAMPLE_OUT_CAP] = B * (size_t)c.cap_frames * 4 * 4;
+}
+
+template <typename T> void samp_put_as(SampDev& b, const float* src, size_t n, hipStream_t st) {
+    std::vector<T> h(n);
+    for (size_t i = 0; i < n; ++i) {
+        if constexpr (std::is_same<T, float>::value) h[i] = src[i];
+        else h[i] = f32_to_bf16_host(src[i]);
+    }
+    b.put(h.data(), n * sizeof(T), st);
+}
+
+template <typename WT>
+void sample_frames_run(const fs_sample_case& c, const SampInfo& I, fs_sample_out& o, hipStream_t st) {
+    using SK = SampleKernels<WT>;
+    const int B = c.B, C = c.n_cb, dim = c.dim;
+    ModelDims d{};
+    d.dim = dim; d.eps = c.eps;
+    SampDev dTok, dCb, dFast, dG, dCfg, dRng, dState, dMask, dSeen, dRing, dMeta, dLs, dLf, dX, dXF, dA, dEp, dCodes, dHid, dHidCell, dCap, dWords;
+    samp_put_as<WT>(dTok, c.tok_emb, (size_t)c.tok_rows * dim, st);
+    samp_put_as<WT>(dCb, c.cb_emb, (size_t)C * c.cb_size * dim, st);
+    samp_put_as<WT>(dFast, c.fast_emb, (size_t)c.cb_size * dim, st);
+    if (c.prep) dG.put(c.prep_g, (size_t)dim * 4, st);
+    dCfg.put(I.cfgs.data(), I.cfgs.size() * sizeof(SampleCfg), st);
+    if (I.slots) {
+        std::vector<SlotRng> r;
+        for (int b = 0; b < B; ++b) r.push_back(slot_rng_fresh(c.seeds[b]));
+        dRng.put(r.data(), r.size() * sizeof(SlotRng), st);
+    } else {
+        const RngState r = rng_fresh(c.seeds[0]);
+        dRng.put(&r, sizeof(r), st);
+    }
+    dState.put(c.state0, (size_t)B * sizeof(SeqState), st);
+    RepPenState rp{nullptr, nullptr, nullptr, nullptr};
+    if (I.R) {  // RepPenBufs' layout, row after row; reset per row as at a request's start / a slot's activation
+        const size_t per = (size_t)C * c.cb_size;
+        dMask.alloc((size_t)I.R * per * 4, st); dSeen.alloc((size_t)I.R * per, st);
+        dRing.alloc((size_t)I.R * C * 17 * 4, st); dMeta.alloc((size_t)I.R * C * 2 * 4, st);
+        FS_HIP(hipMemsetAsync(dRing.data(), 0, (size_t)I.R * C * 17 * 4, st));
+        rp = RepPenState{dMask.as<float>(), dSeen.as<uint8_t>(), dRing.as<int>(), dMeta.as<int>()};
+        for (int r = 0; r < I.R; ++r)
+            launch_reppen_reset(RepPenState{rp.mask + r * per, rp.seen + r * per, rp.ring + (size_t)r * C * 17, rp.ring_meta + (size_t)r * C * 2}, C, c.cb_size, st);
+    }
+    dLs.alloc((size_t)B * c.ld * 4, st); dLf.alloc((size_t)B * c.cb_size * 4, st);
+    dX.alloc((size_t)B * dim * 4, st); dXF.alloc((size_t)B * dim * 4, st);
+    if (c.prep) {
+        dA.alloc((size_t)2 * 32 * dim * 2, st);
+        const uint32_t z[2] = {0u, 0u};
+        dEp.put(z, 8, st);
+    }
+    dCodes.alloc((size_t)B * C * c.out_cap * 4, st);
+    if (c.hid) {
+        dHid.alloc((size_t)I.hid_rows * dim * 4, st);
+        float* hp = dHid.as<float>();
+        dHidCell.put(&hp, sizeof(hp), st);
+    }
+    if (c.cap_frames) dCap.alloc((size_t)B * c.cap_frames * 9 * 2048 * 4, st);
+    if (I.par) dWords.alloc((size_t)B * ROWS_WORDS_LD * 4, st);
+    const float* prep_g = c.prep ? dG.as<float>() : nullptr;
+    uint16_t* prep_A = c.prep ? dA.as<uint16_t>() : nullptr;
+    uint32_t* epoch = c.prep ? dEp.as<uint32_t>() : nullptr;
+    const uint32_t* words = I.par ? dWords.as<uint32_t>() : nullptr;
+
+    int l = 0;
+    auto record = [&]() {  // the complete state after launch l
+        FS_HIP(hipStreamSynchronize(st));
+        auto down = [&](int which, const SampDev& b) {
+            if (o.buf[which] && I.per[which]) FS_HIP(hipMemcpyAsync((char*)o.buf[which] + (size_t)l * I.per[which], b.data(), I.per[which], hipMemcpyDeviceToHost, st));
+        };
+        down(FS_SAMPLE_OUT_STATES, dState);
+        if (I.R) { down(FS_SAMPLE_OUT_RING, dRing); down(FS_SAMPLE_OUT_META, dMeta); down(FS_SAMPLE_OUT_MASK, dMask); }
+        down(FS_SAMPLE_OUT_RNG, dRng);
+        if (I.par) down(FS_SAMPLE_OUT_WORDS, dWords);
+        down(FS_SAMPLE_OUT_XF, dXF); down(FS_SAMPLE_OUT_X, dX);
+        if (c.prep) { down(FS_SAMPLE_OUT_PREP, dA); down(FS_SAMPLE_OUT_EPOCH, dEp); }
+        down(FS_SAMPLE_OUT_CODES, dCodes);
+        if (c.hid) down(FS_SAMPLE_OUT_HID, dHid);
+        if (c.cap_frames && o.buf[FS_SAMPLE_OUT_CAP]) {
+            float* dst = (float*)((char*)o.buf[FS_SAMPLE_OUT_CAP] + (size_t)l * I.per[FS_SAMPLE_OUT_CAP]);
+            for (int r = 0; r < B * c.cap_frames; ++r) {
+                const float* rec = dCap.as<float>() + (size_t)r * 9 * 2048;
+                FS_HIP(hipMemcpyAsync(dst + (size_t)r * 4, rec, 12, hipMemcpyDeviceToHost, st));
+                FS_HIP(hipMemcpyAsync(dst + (size_t)r * 4 + 3, rec + 2047, 4, hipMemcpyDeviceToHost, st));
+            }
+        }
+        FS_HIP(hipStreamSynchronize(st));
+        ++l;
+    };
+    const size_t frame_logits = (size_t)B * c.n_slow + (size_t)C * B * c.cb_size;
+    for (int f = 0; f < c.F; ++f) {
+        const float* lg = c.logits + (size_t)f * frame_logits;
+        dX.up(c.x + (size_t)f * B * dim, (size_t)B * dim * 4, st);
+        for (int b = 0; b < B; ++b) dLs.up(lg + (size_t)b * c.n_slow, (size_t)c.n_slow * 4, st, (size_t)b * c.ld * 4);
+        if (I.par) { SK::rows_rng_words(dRng.as<RngState>(), B, C + 1, dState.as<SeqState>(), dWords.as<uint32_t>(), st); record(); }
+        if (I.single)
+            SK::sample_slow(d, dLs.as<float>(), c.n_slow, dCfg.as<SampleCfg>(), dRng.as<RngState>(), dState.as<SeqState>(), dX.as<float>(), dXF.as<float>(), st,
+                            c.hid ? dHidCell.as<float*>() : nullptr);
+        else if (I.rows)
+            SK::sample_slow_rows(d, dLs.as<float>(), c.ld, c.n_slow, dCfg.as<SampleCfg>(), dRng.as<RngState>(), B, C + 1, dState.as<SeqState>(), dX.as<float>(),
+                                 dXF.as<float>(), st, words, prep_g, prep_A, epoch);
+        else
+            SK::sample_slow_slots(d, dLs.as<float>(), c.ld, c.n_slow, dCfg.as<SampleCfg>(), dRng.as<SlotRng>(), B, dState.as<SeqState>(), dX.as<float>(),
+                                  dXF.as<float>(), st, prep_g, prep_A, epoch, c.cap_frames ? dCap.as<float>() : nullptr, c.cap_frames, I.wide);
+        record();
+        for (int cb = 0; cb < C; ++cb) {
+            dLf.up(lg + (size_t)B * c.n_slow + (size_t)cb * B * c.cb_size, (size_t)B * c.cb_size * 4, st);
+            if (I.single)
+                SK::sample_fast(d, dLf.as<float>(), cb, C, c.cb_size, dCfg.as<SampleCfg>(), dRng.as<RngState>(), rp, dState.as<SeqState>(), dFast.data(),
+                                dXF.as<float>(), dTok.data(), dCb.data(), dX.as<float>(), dCodes.as<uint32_t>(), c.out_cap, st);
+            else if (I.rows)
+                SK::sample_fast_rows(d, dLf.as<float>(), cb, C, c.cb_size, dCfg.as<SampleCfg>(), dRng.as<RngState>(), B, dState.as<SeqState>(), dFast.data(),
+                                     dXF.as<float>(), dTok.data(), dCb.data(), dX.as<float>(), dCodes.as<uint32_t>(), c.out_cap, st, words, prep_g, prep_A);
+            else
+                SK::sample_fast_slots(d, dLf.as<float>(), cb, C, c.cb_size, dCfg.as<SampleCfg>(), dRng.as<SlotRng>(), rp, B, dState.as<SeqState>(), dFast.data(),
+                                      dXF.as<float>(), dTok.data(), dCb.data(), dX.as<float>(), dCodes.as<uint32_t>(), c.out_cap, st, prep_g, prep_A, I.wide);
+            record();
+        }
+    }
+    bool ok = true;
+    for (const SampDev* b : {&dTok, &dCb, &dFast, &dG, &dCfg, &dRng, &dState, &dMask, &dSeen, &dRing, &dMeta, &dLs, &dLf, &dX, &dXF, &dA, &dEp, &dCodes, &dHid,
+                             &dHidCell, &dCap, &dWords})
+        ok = b->intact(st) && ok;
+    o.guard_ok = ok ? 1 : 0;
+}
+}  // namespace
+
+void sample_frames_selftest(int device, const fs_sample_case& c, fs_sample_out& o) {
+    SampInfo I;
+    sample_validate(c, I);
+    o.n_launches = I.L;
+    for (int i = 0; i < FS_SAMPLE_OUT_COUNT; ++i) o.need[i] = I.per[i] * (size_t)I.L;
+    if (c.plan_only) return;
+    for (int i = 0; i < FS_SAMPLE_OUT_COUNT; ++i) samp_req(!o.buf[i] || o.cap[i] >= o.need[i], "an output capacity is too small");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) throw Error("no HIP device visible: libfishrt has no CPU fallback (MI355X / gfx950 required)");
+    FS_REQUIRE(device >= 0 && device < ndev, "device_id out of range");
+    FS_HIP(hipSetDevice(device));
+    hipStream_t st = nullptr;
+    FS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } sg{st};
+    if (c.wt == FS_GEMV_WT_F32) sample_frames_run<float>(c, I, o, st);
+    else sample_frames_run<bf16_t>(c, I, o, st);
 }
 
 template struct SampleKernels<bf16_t>;

@@ -88,6 +88,23 @@ class GemvOut(C.Structure):  # fs_gemv_out: where fs_selftest_gemv leaves its re
                [(n, C.c_size_t) for n in ("y_cap", "pool_cap", "variant_cap", "n_y", "n_pool")] + [("grid", C.c_int32 * 3), ("guard_ok", C.c_int32)]
 
 
+class SampleCase(C.Structure):  # fs_sample_case: F frames of the production sampler launches for fs_selftest_sample_frames
+    _fields_ = [(n, C.c_int32) for n in ("family", "wt", "plan_only", "B", "F", "n_cb", "cb_size", "n_slow", "ld", "dim", "out_cap", "tok_rows",
+                                         "prep", "hid", "session", "cap_frames", "batch_rows", "batch_row", "n_cfg", "reserved")] + \
+               [("eps", C.c_float), ("reserved2", C.c_int32), ("tokens", TokenCfg), ("reserved3", C.c_int32),
+                ("samplings", C.POINTER(Sampling)), ("seeds", C.POINTER(C.c_uint64)), ("ignore_eos", C.POINTER(C.c_int32)),
+                ("state0", C.POINTER(C.c_int32))] + \
+               [(n, C.POINTER(C.c_float)) for n in ("tok_emb", "cb_emb", "fast_emb", "prep_g", "x", "logits")]
+
+
+SAMPLE_OUTS = ("STATES", "RING", "META", "MASK", "RNG", "WORDS", "XF", "X", "PREP", "EPOCH", "CODES", "HID", "CAP")
+
+
+class SampleOut(C.Structure):  # fs_sample_out: where fs_selftest_sample_frames leaves the state after every launch (sizes in bytes)
+    _fields_ = [("buf", C.c_void_p * len(SAMPLE_OUTS)), ("cap", C.c_size_t * len(SAMPLE_OUTS)), ("need", C.c_size_t * len(SAMPLE_OUTS)),
+                ("n_launches", C.c_int32), ("guard_ok", C.c_int32)]
+
+
 FRAME_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32))
 
 # every symbol include/fishrt.h declares (tests/test_abi.py checks the library exports all of them)
@@ -102,7 +119,7 @@ SYMBOLS = ["fs_last_error", "fs_version", "fs_device_count", "fs_lm_create", "fs
            "fs_lm_session_add_traced", "fs_lm_session_poll_trace",
            "fs_lm_session_poll_alts", "fs_selftest_alt_rows",
            "fs_selftest_conv1d", "fs_selftest_codec_op", "fs_selftest_codec_encode_stage", "fs_selftest_attn", "fs_selftest_gemm",
-           "fs_selftest_gemv",
+           "fs_selftest_gemv", "fs_selftest_sample_frames",
            "fs_lm_weights_fingerprint", "fs_lm_session_prefix_export", "fs_lm_session_prefix_import",
            "fs_lm_session_prefix_from_slot", "fs_lm_session_last_frame",
            "fs_codec_create", "fs_codec_destroy", "fs_codec_load_safetensors", "fs_codec_load_synthetic",
@@ -179,6 +196,10 @@ GEMM_PROTOTYPES = {"fs_selftest_gemm": [C.c_int, C.POINTER(GemmCase), C.POINTER(
 GEMV_OPS = {n: i for i, n in enumerate(("QKV", "FFN_UP", "FFN_DOWN", "HEAD", "WO_BODY", "EMBED", "FAST_EMBED"))}
 GEMV_WT = {"f32": 0, "bf16": 1, "fp8": 2}
 GEMV_PROTOTYPES = {"fs_selftest_gemv": [C.c_int, C.POINTER(GemvCase), C.POINTER(GemvOut)]}
+
+# fs_selftest_sample_frames (families: include/fishrt.h; wt: GEMV_WT's f32 / bf16)
+SAMPLE_FAMILIES = {n: i for i, n in enumerate(("single", "single_batchrow", "rows", "rows_par", "slots", "slots_wide"))}
+SAMPLE_PROTOTYPES = {"fs_selftest_sample_frames": [C.c_int, C.POINTER(SampleCase), C.POINTER(SampleOut)]}
 
 # ... and of the calls that make a prefix out of a slot's history
 HISTORY_PROTOTYPES = {
@@ -269,7 +290,7 @@ def lib():
         L.fs_comm_destroy.argtypes = [C.c_void_p]
         L.fs_lm_destroy.argtypes = [C.c_void_p]
         L.fs_codec_destroy.argtypes = [C.c_void_p]
-        for name, argtypes in {**SCORE_PROTOTYPES, **TRACE_PROTOTYPES, **ALTS_PROTOTYPES, **CONV_PROTOTYPES, **CODEC_OP_PROTOTYPES, **ATTN_PROTOTYPES, **GEMM_PROTOTYPES, **GEMV_PROTOTYPES, **HISTORY_PROTOTYPES,
+        for name, argtypes in {**SCORE_PROTOTYPES, **TRACE_PROTOTYPES, **ALTS_PROTOTYPES, **CONV_PROTOTYPES, **CODEC_OP_PROTOTYPES, **ATTN_PROTOTYPES, **GEMM_PROTOTYPES, **GEMV_PROTOTYPES, **SAMPLE_PROTOTYPES, **HISTORY_PROTOTYPES,
                                **RESAMPLE_PROTOTYPES, **TSM_PROTOTYPES, **LOUD_PROTOTYPES}.items():
             if hasattr(L, name):  # (an older build loaded through LIB_PATH -- tools/attn_paths_dump.py --lib -- may lack the newest entry points)
                 getattr(L, name).argtypes = argtypes

@@ -347,6 +347,74 @@ typedef struct fs_gemv_out {
 } fs_gemv_out;
 int fs_selftest_gemv(int device_id, const fs_gemv_case* c, fs_gemv_out* out);
 
+/* F frames of the PRODUCTION sampler launches (csrc/lm_sample.hip) on caller-provided logits, and nothing else: per frame the launchers the
+ * engine calls, in its order -- SampleKernels::rows_rng_words (ROWS_PAR only), the slow sampler, then the fast sampler for codebooks
+ * 0 .. n_cb - 1 -- with the complete sampler state copied out after EVERY launch.  L = F * ((ROWS_PAR ? 1 : 0) + 1 + n_cb) launches.
+ *   family                kernels
+ *   FS_SAMPLE_SINGLE           k_sample_slow, k_sample_fast                     (B == 1)
+ *   FS_SAMPLE_SINGLE_BATCHROW  the same two with batch_rows > 0: row batch_row of a static batch of batch_rows rows (B == 1)
+ *   FS_SAMPLE_ROWS             k_sample_slow_rows, k_sample_fast_rows
+ *   FS_SAMPLE_ROWS_PAR         k_rows_rng_words, k_sample_slow_rows_par, k_sample_fast_rows_par   (rows_par_sampler_ok settings only)
+ *   FS_SAMPLE_SLOTS            k_sample_slow_slots<false>, k_sample_fast_slots<false>   (per slot: temp == 0, or temp > 0 with 0 < top_k <= 256)
+ *   FS_SAMPLE_SLOTS_WIDE       k_sample_slow_slots<true>, k_sample_fast_slots<true>     (per slot: any finite temp >= 0, top_p)
+ * wt: FS_GEMV_WT_F32 / _BF16 selects SampleKernels<float> / <bf16_t> (the two table types KVT<WT> has); the tables tok_emb [tok_rows][dim],
+ * cb_emb [n_cb cb_size][dim], fast_emb [cb_size][dim] are f32 values that must lie on that type's grid.  tokens: the token layout, from which
+ * the SampleCfg is made as the engine makes it (has_semantic_end == 0: the Fish <= 1.4 two-way slow decision; SINGLE, SLOTS, SLOTS_WIDE
+ * only, n_slow == 2).  samplings / seeds / ignore_eos: n_cfg entries, n_cfg = B for the SLOTS families (one StdRng stream per slot, as a
+ * freshly activated slot's) and 1 otherwise (the request's stream; the master stream of the row families, whose repetition_penalty is
+ * ignored: the batch paths run with 1).  session: SampleCfg::session of the row families (0: dead rows step in lock-step, 1: they freeze).
+ * state0: the initial SeqState of every row, int32 [B][40] = {pos, rope_off, frame, done, n_out, have_prev, step, prompt_L, cur[16],
+ * prev[16]}.  x: the hidden row the slow sampler of frame f finds in X, f32 [F][B][dim] (uploaded in front of it).  logits: per frame the
+ * slow rows [B][n_slow] (placed ld apart on the device, the gap poisoned), then per codebook [B][cb_size].  prep != 0: the RMSNorm + hi/lo
+ * split epilogue with prep_g [dim], eps and the step epoch (row families, slots).  hid != 0 (SINGLE): the hidden-state rows of
+ * generate_blocking_with_hidden.  cap_frames > 0 (SLOTS families): the decision capture record of the slow sampler.
+ * Outputs, all nullable, cap[i] / need[i] in BYTES, [L] leading (the state after launch l):
+ *   STATES int32 [L][B][40]; RING int32 [L][R][n_cb][17], META int32 [L][R][n_cb][2], MASK f32 [L][R][n_cb][cb_size] (R = B for the SLOTS
+ *   families, 1 for SINGLE*, 0 for the row families, which take no penalty state); RNG: SINGLE* RngState as u32 [L][10], row families the
+ *   master's [L][10], SLOTS the SlotRng cells u32 [L][B][58] ({key[8], consumed lo, hi, ahead_at[16] lo / hi pairs, ahead_word[16]});
+ *   WORDS u32 [L][B][16] (ROWS_PAR); XF, X f32 [L][B][dim]; PREP uint16 [L][2 * 32 * dim] (the fragment-major hi / lo buffer of 32 rows),
+ *   EPOCH u32 [L][2]; CODES u32 [L][B][n_cb][out_cap]; HID f32 [L][frame0 + F][dim]; CAP f32 [L][B][cap_frames][4] = entries 0, 1, 2 and
+ *   2047 of decision 0's record.
+ * Every device buffer lies between 256-element guards of 0xFF bytes and is 0xFF bytes where the case provides nothing; the penalty state
+ * is reset with launch_reppen_reset as at a request's start.  guard_ok = 1 iff every guard is intact after the last launch.
+ * The case is VALIDATED BEFORE ANY DEVICE CALL: the launchers' capacities, n_cb + 1 <= 16, rows_par_sampler_ok for ROWS_PAR, the
+ * narrow-setting rule for SLOTS (greedy, or 0 < top_k <= 256 and below both
+ * candidate counts), dim <= 1024 in whole 32-wide fragments for the prep epilogue, every token id the tables are indexed with; a bad case is an error and nothing
+ * is launched.  plan_only != 0: validate, fill n_launches and need[], touch no device.  Diagnostics / parity tests.
+ *
+ * THE HOST ArgMax RULE (temp == 0 on the single-sequence and per-slot paths): candle's LogitsProcessor picks
+ * `iter().enumerate().max_by(|a, b| a.total_cmp(b))`: the order is IEEE-754 totalOrder, under which -0.0 < +0.0, and among candidates of
+ * IDENTICAL bit pattern the LAST index wins.  greedy_pick, slot_greedy_pick and the oracle's LogitsProcessor::sample follow it (a maximum
+ * of +0 beats a -0 wherever either stands).  The batch rule (temp <= 1e-7 on the static-batch paths) is the tensor argmax: IEEE `>`, the
+ * FIRST maximal index, -0 == +0.  NaN logits are outside both rules. */
+enum { FS_SAMPLE_SINGLE = 0, FS_SAMPLE_SINGLE_BATCHROW = 1, FS_SAMPLE_ROWS = 2, FS_SAMPLE_ROWS_PAR = 3, FS_SAMPLE_SLOTS = 4,
+       FS_SAMPLE_SLOTS_WIDE = 5 };
+enum { FS_SAMPLE_OUT_STATES = 0, FS_SAMPLE_OUT_RING = 1, FS_SAMPLE_OUT_META = 2, FS_SAMPLE_OUT_MASK = 3, FS_SAMPLE_OUT_RNG = 4,
+       FS_SAMPLE_OUT_WORDS = 5, FS_SAMPLE_OUT_XF = 6, FS_SAMPLE_OUT_X = 7, FS_SAMPLE_OUT_PREP = 8, FS_SAMPLE_OUT_EPOCH = 9,
+       FS_SAMPLE_OUT_CODES = 10, FS_SAMPLE_OUT_HID = 11, FS_SAMPLE_OUT_CAP = 12, FS_SAMPLE_OUT_COUNT = 13 };
+typedef struct fs_sample_case {
+    int32_t family, wt, plan_only, B;
+    int32_t F, n_cb, cb_size, n_slow;
+    int32_t ld, dim, out_cap, tok_rows;
+    int32_t prep, hid, session, cap_frames;
+    int32_t batch_rows, batch_row, n_cfg, reserved;
+    float eps;
+    int32_t reserved2;
+    fs_token_cfg tokens;
+    int32_t reserved3;
+    const fs_sampling* samplings;
+    const uint64_t* seeds;
+    const int32_t *ignore_eos, *state0;
+    const float *tok_emb, *cb_emb, *fast_emb, *prep_g, *x, *logits;
+} fs_sample_case;
+typedef struct fs_sample_out {
+    void* buf[FS_SAMPLE_OUT_COUNT];
+    size_t cap[FS_SAMPLE_OUT_COUNT];
+    size_t need[FS_SAMPLE_OUT_COUNT];
+    int32_t n_launches, guard_ok;
+} fs_sample_out;
+int fs_selftest_sample_frames(int device_id, const fs_sample_case* c, fs_sample_out* out);
+
 /* Stage tap of the encoder on a LOADED handle: runs fs_codec_encode's device path on the clip exactly as fs_codec_encode does (same buffers,
  * same launches, the codes are computed and dropped) and copies ONE intermediate tensor to the host:
  *   stage -1     the log-mel [160][F], F = mel frames of the clip

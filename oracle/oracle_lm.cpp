@@ -529,7 +529,8 @@ static uint32_t sample_topp(ChaCha12Rng& rng, std::vector<float>& probs, float t
 }
 
 // LogitsProcessor::sample for Sampling::ArgMax / TopKThenTopP (single_batch.rs:38-46).
-// Tie rule of the host ArgMax: `iter().enumerate().max_by(total_cmp)` => the LAST maximal index wins.
+// Tie rule of the host ArgMax: `iter().enumerate().max_by(total_cmp)` => the maximum under IEEE totalOrder (-0.0 < +0.0, so a +0
+// beats a -0 wherever either stands) and, among identical bit patterns, the LAST index.  NaN logits are outside the restatement.
 // top-k: the reference uses `select_nth_unstable_by`, whose output ORDER is unspecified; this restatement
 // (and the HIP path) fix the order to ascending token index, which leaves the sampling distribution unchanged.
 // top-k then top-p then WeightedIndex draw on a probability vector (shared by the single and the batched processor)
@@ -595,9 +596,11 @@ void rng_batched_sample(uint64_t seed, const Sampling& s, const float* logits, i
 
 uint32_t LogitsProcessor::sample(const float* logits, size_t n) {
     if (s.temp == 0.0) {
+        // f32::total_cmp as an integer key: -0.0 < +0.0, identical bit patterns equal; max_by keeps the LAST of equal maxima
+        auto key = [](float v) { int32_t b; std::memcpy(&b, &v, 4); return b ^ ((b >> 31) & 0x7FFFFFFF); };
         size_t best = 0;
         for (size_t i = 1; i < n; ++i)
-            if (!(logits[i] < logits[best])) best = i;  // >= : last max wins
+            if (key(logits[i]) >= key(logits[best])) best = i;
         return (uint32_t)best;
     }
     const float inv_t = (float)(1.0 / s.temp);

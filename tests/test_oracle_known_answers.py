@@ -61,6 +61,19 @@ def test_argmax_tie_rule():  # host ArgMax: max_by(total_cmp) -> last maximal in
     s = C.c_void_p(L.orc_sampler_create(C.c_uint64(1), C.c_double(0.0), C.c_double(1.0), C.c_uint64(0)))
     v = np.array([0.5, 2.0, -1.0, 2.0, 1.0], np.float32)
     assert L.orc_sampler_sample(s, v.ctypes.data_as(C.POINTER(C.c_float)), C.c_uint64(5)) == 3
+    # signed zeros at the maximum (fishrt.h: the host ArgMax rule): total_cmp puts -0.0 below +0.0, so the +0 wins wherever it stands;
+    # among identical bit patterns the last index wins
+    for row, want in (([-1.0, 0.0, -2.0, -0.0, -1.0], 1), ([-1.0, -0.0, -2.0, 0.0, -1.0], 3), ([-0.0, -0.0, -1.0, -0.0, -3.0], 3),
+                      ([0.0, -0.0, 0.0, -0.0, -0.0], 2), ([-0.0, 0.0], 1), ([0.0, -0.0], 0)):
+        v = np.array(row, np.float32)
+        assert L.orc_sampler_sample(s, v.ctypes.data_as(C.POINTER(C.c_float)), C.c_uint64(len(row))) == want, row
+    # the batch rule (tensor argmax: IEEE `>`, first maximal index) does not tell the zeros apart
+    out = np.zeros(1, np.uint32)
+    for row, want in (([-1.0, -0.0, -2.0, 0.0], 1), ([-1.0, 0.0, -2.0, -0.0], 1)):
+        v = np.array(row, np.float32)
+        L.orc_batched_sample(C.c_uint64(1), C.c_double(0.0), C.c_double(1.0), C.c_uint64(0), v.ctypes.data_as(C.POINTER(C.c_float)), 1, len(row), 0,
+                             out.ctypes.data_as(C.POINTER(C.c_uint32)))
+        assert out[0] == want, row
     L.orc_sampler_destroy(s)
 
 
